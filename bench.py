@@ -7,7 +7,7 @@ C2 at N=1, C4-shaped (256 per GPU, weak scaling, one RCCL all-gather of the samp
 Inputs (state tokens, goal, x_T) and the random-init weights are synthetic and already resident in HBM when the
 timed region starts.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -17,6 +17,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with the extra o
                  the same figure for the dominant kernel (the fused MFMA GEMM) timed alone through the op-level ABI
   cpu_baseline : the CPU oracle ("port" of the reference algorithm, as-written: encoder re-run every step) timed on
                  this host's cores on a bounded sample of the same workload (rank 0, N=1 only)
+
+--dump-outputs DIR writes the actions the last timed step returned (at N > 1 rank 0's gathered (N B, 10, 7) tensor) to
+DIR/actions.npy as float32.  Weights and inputs are seeded, so two builds run with the same arguments can be compared
+element for element.
 """
 import argparse
 import ctypes as C
@@ -49,7 +53,30 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=30.0, help="budget of the CPU baseline (all legs together)")
     ap.add_argument("--cpu-leg", default="", help=argparse.SUPPRESS)  # internal: "threads,hoist,budget" -> one CPU-baseline leg, JSON on stdout
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0: min(cpu_count, 16), the best of a 1..128 sweep on the EPYC host)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """{name: tensor} -> outdir/<name>.npy as float32.  An array larger than its share of DUMP_LIMIT_BYTES keeps a fixed,
+    seeded sample of its leading-dimension rows (sorted), so two builds fed the same arguments dump the same elements."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.nbytes > share:
+            keep = max(1, share // max(1, a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(outdir, f"{name}.npy"), a)
+        log(f"dumped {name} {tuple(a.shape)} -> {os.path.join(outdir, name)}.npy")
 
 
 def build_model(device):
@@ -642,6 +669,9 @@ def main():
         wall, gpu_s = t[0].item(), t[1].item()
     assert torch.isfinite(out).all()
     log(f"timed {args.steps} steps: wall {wall:.4f}s gpu {gpu_s:.4f}s")
+    if args.dump_outputs and rank == 0:
+        # before the spread run below: a graph-replayed sampler call hands back the same output buffer every call
+        dump_outputs(args.dump_outputs, {"actions": out})
     # spread (median of >= 50 timed iterations): the same step again, every call between its own pair of
     # HIP events on the launch stream; `value` stays the contract's K-step mean, this tells box-to-box noise from change
     n_spread = max(50, args.steps)

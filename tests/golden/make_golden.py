@@ -470,6 +470,23 @@ def g10():
     print(f"  wrote g10_fnv.json: {len(vec)} vectors")
 
 
+def g10b():
+    """fnv_32_buf of the REFERENCE build (oracle/_ref/) on seeded random byte buffers, for tests/test_fnv.py.  The buffers
+    are stored with the hashes (uint8, concatenated; `lengths` splits them), so the fixture does not rest on numpy's
+    random stream."""
+    from oracle import fnv_oracle as FO
+
+    assert FO.reference_available(), "run `make -C oracle` first"
+    rng = np.random.default_rng(0)
+    lengths = [0, 1, 2, 3, 7, 64, 1000, 65537]
+    seeds = [0, 1, 0x811C9DC5, 0xFFFFFFFF]
+    bufs = [rng.integers(0, 256, n, dtype=np.uint8) for n in lengths]
+    hashes = [[FO.reference_fnv_32_buf(b.tobytes(), s) for s in seeds] for b in bufs]
+    np.savez(os.path.join(HERE, "g10_fnv_buffers.npz"), data=np.concatenate(bufs), lengths=np.array(lengths, np.int64),
+             seeds=np.array(seeds, np.uint32), hashes=np.array(hashes, np.uint32))
+    print(f"  wrote g10_fnv_buffers.npz: {len(lengths)} buffers x {len(seeds)} seeds")
+
+
 G14_CLA = {
     # name: (ClipStyleProjection kwargs, (B, N tokens))
     "map_tiny": (dict(clip_style="map", token_dim=128, clip_token_index=1, num_token=4), (5, 4)),
@@ -771,7 +788,7 @@ if __name__ == "__main__":
     assert os.path.isdir(REF), "this script needs the reference checkout at /root/reference"
     install_stubs()
     torch.manual_seed(0)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g11", "g13", "g14", "g15", "g16", "g17", "manifest"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g10b", "g11", "g13", "g14", "g15", "g16", "g17", "manifest"]
     for w in which:
         print(w)
         globals()[w]()
