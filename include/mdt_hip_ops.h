@@ -90,8 +90,8 @@ typedef struct {
     int64_t a_part_stride;
     float *a_merged;
     /* optional (round 6): the three-way bf16 split image of the same weight (mdt_op_pack_weight_split; rows in the order of Wp's).
-     * Where it is given, the LayerNorm-prologue products on the wide tiles (K = 384 or 512, N a multiple of 384, from 768 rows on
-     * -- MDT_HIP_SPLIT_MIN_ROWS --, plain output rows) multiply in the split form -- six bf16 MFMA products per 32-deep step, fp32
+     * Where it is given, the LayerNorm-prologue products on the wide tiles (K = 384 or 512, N a multiple of 384, from 768 rows on,
+     * plain output rows) multiply in the split form -- six bf16 MFMA products per 32-deep step, fp32
      * accumulation: fp32's product accuracy, not the fp32 form's bits -- unless mdt_op_set_mlp_split(0).  NULL: the fp32 form. */
     const void *Wp_split;
 } mdt_gemm_args;
@@ -123,12 +123,12 @@ mdt_status mdt_op_mlp_split(const mdt_gemm_args *fc, const mdt_gemm_args *proj, 
                             float *parts, int64_t part_stride, int32_t *n_parts, void *stream);
 void mdt_op_set_mlp_split(int32_t on);
 /* Tuning / test hook: the model-level entry points run the MLP sublayer through mdt_op_mlp from `rows` rows (B * horizon)
- * on; 0 = never (the two-GEMM sequence), -1 = default (1401, or MDT_HIP_MLP_FUSE_MIN from the environment). */
+ * on; 0 = never (the two-GEMM sequence), -1 = default (1401; 768 where the split form applies).  The split form always needs
+ * 768 rows: below them a setting runs the fp32 form. */
 void mdt_op_set_mlp_fuse_min(int32_t rows);
 /* Tuning / test hook (round 5): rollout-sized model-level calls queue the products that do not depend on their neighbours in the
  * launch chain (the sigma-MLP / adaLN table of mdt_sample_ddim, the MDTV token embedding) and let each ride as extra workgroups in
- * the next split-K small-M launch.  0 = every product its own launch, 1 = on, -1 = default (on, or MDT_HIP_SIDE_JOBS from the
- * environment).  Same tiles, same order inside each product: results are bit-identical either way.
+ * the next split-K small-M launch.  0 = every product its own launch, 1 = on, -1 = default (on).  Same tiles, same order inside each product: results are bit-identical either way.
  * mdt_op_side_jobs_paired: how many launches of this process have taken such a product along so far. */
 void mdt_op_set_side_jobs(int32_t on);
 int64_t mdt_op_side_jobs_paired(void);
@@ -157,7 +157,7 @@ void mdt_op_set_ws_split(int32_t on);
 
 /* Tuning / test hook: wave schedule inside mdt_op_mlp's kernel.  Low byte = number of k-steps the second wave of every
  * SIMD starts behind the first (0 = lockstep with a workgroup barrier between the two products), | 256 = MFMA loops at
- * raised issue priority; -1 = default (18 | 256, or MDT_HIP_MLP_SKEW from the environment).  Every setting produces the
+ * raised issue priority; -1 = default (18 | 256).  Every setting produces the
  * same bits (the K order of both products does not depend on it). */
 void mdt_op_set_mlp_skew(int32_t v);
 
@@ -173,8 +173,7 @@ void mdt_op_set_mlp_skew(int32_t v);
  * -1 = the split-K small-M kernel wherever it applies.
  * 30 = the weight-stationary body wherever it is supported, whatever the row count.
  * Row-tile, tall and (fp32 form, mdt_op_set_ws_split(0)) weight-stationary geometries compute bit-identical results (same k order
- * per output element); the small-M kernel and the weight-stationary body's bf16 split form (the default) agree to fp32 rounding.  MDT_HIP_SMALLM_MAX / MDT_HIP_SMALLM_TILES / MDT_HIP_SMALLM_ROWS / MDT_HIP_MID_MAX (environment) move the
- * thresholds. */
+ * per output element); the small-M kernel and the weight-stationary body's bf16 split form (the default) agree to fp32 rounding. */
 void mdt_op_set_gemm_geometry(int32_t geometry);
 
 typedef struct {
@@ -197,7 +196,7 @@ mdt_status mdt_op_attention(const mdt_attn_args *args, void *stream);
  * Summation order: since round 5 both attention products run on the MFMA pipe inside this launch (wave = head, k order of the
  * matrix instruction), so its results differ from mdt_op_attention + mdt_op_gemm on the same operands in the last bits: within
  * 2e-5 absolute + 1e-4 relative on values of order one (tests/test_gpu_ops.py::test_fused_attention_projection_against_the_two_
- * launches_at_rollout_batches, B = 1 .. 8); the model-level entry points use it up to 32 samples (MDT_HIP_ATTN_PROJ_MAX). */
+ * launches_at_rollout_batches, B = 1 .. 8); the model-level entry points use it up to 32 samples. */
 mdt_status mdt_op_attn_proj(const mdt_gemm_args *proj, const float *qkv, int64_t ldq, int32_t hd, int32_t T, int32_t causal,
                             void *stream);
 /* (More than 64 samples: the same contract for a LARGE batch, M = samples * T rows, causal, residual, hd in {16, 32, 48} --
@@ -263,7 +262,7 @@ mdt_status mdt_op_xattn_apply(const mdt_xapply_args *args, void *stream);
  * writes the new rows to x->y_out, which must be given and differ from x->y (the other workgroups may still be reading x->y).
  * `g` as for mdt_op_gemm with g->A == x->y, lda = K = x->D, M = x->B * x->Ta, rows_per_sample = x->Ta, no residual / row remap /
  * split input.  Results equal the two launches bit for bit.  The model-level entry points use it up
- * to 2 samples (MDT_HIP_XATTN_FC_MAX_B overrides; B = 4 measured slower: 1.67 vs 1.58 ms per call). */
+ * to 2 samples (B = 4 measured slower: 1.67 vs 1.58 ms per call). */
 mdt_status mdt_op_xattn_gemm(const mdt_xapply_args *x, const mdt_gemm_args *g, void *stream);
 
 /* The middle of a ConditionedBlock for a batch of at most one sample per compute unit, ONE launch, one workgroup per sample
@@ -272,8 +271,7 @@ mdt_status mdt_op_xattn_gemm(const mdt_xapply_args *x, const mdt_gemm_args *g, v
  * sublayers stay in the workgroup's LDS and x->y == proj->out is written once.  8 heads of 48 (K = N = ldo = 384, ldq = 3 K),
  * T = x->Ta <= 16, proj->M = x->B * T; results equal the two launches up to the summation order of the self-attention
  * (this form runs q k^T and P v on the MFMA pipe, one wave per head).  The model-level entry points use it
- * from 1401 rows up to 512 samples (MDT_HIP_ATTN_XATTN_MIN / MDT_HIP_ATTN_XATTN_MAX_B; mdt_op_set_attn_wide_min(0) switches
- * it off together with the tiled form). */
+ * from 200 rows up to 512 samples (mdt_op_set_attn_wide_min(0) switches it off together with the tiled form). */
 mdt_status mdt_op_attn_xattn(const mdt_gemm_args *proj, const float *qkv, int64_t ldq, const mdt_xapply_args *x, int32_t hd,
                              int32_t T, void *stream);
 

@@ -59,7 +59,8 @@ def _compile_one(args):
 def build_library(force: bool = False, verbose: bool = False, out: str = None, defines=()) -> str:
     """Compile csrc/*.hip -> csrc/libmdt_hip.so for gfx950; returns the library path.  Every translation unit is compiled
     to its own object (in parallel; objects are kept under csrc/build/ and reused while the source and the headers are
-    older), then linked.  ``out`` / ``defines`` build an experimental variant next to the product library (tuning A/B runs)."""
+    older), then linked.  ``out`` / ``defines`` build a variant next to the product library (the phase-timing build of tools/*_phases.py:
+    -DMDT_DEBUG_TIMING)."""
     if out is None and not force and not needs_build():
         return LIB
     out = out or LIB

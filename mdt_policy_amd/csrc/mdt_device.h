@@ -17,17 +17,11 @@ __device__ __forceinline__ f32x4 ldg4(const float* p) { return *(const f32x4*)p;
 // Wave-wide sums without LDS-crossbar round trips (ds_bpermute, ~100 cycles per butterfly step): DPP lane swaps inside a
 // 16-lane row (xor 1, xor 2 as quad permutes, then the half-row and full-row mirrors leave the row's sum in every lane), then
 // row_bcast:15 / row_bcast:31 carry the running total across the four rows into lane 63, which v_readlane hands to everyone.
-// MDT_SHFL_REDUCE (tuning build) restores the butterfly.
 template <int CTRL, int ROWS>
 __device__ __forceinline__ float dpp_get(float v) {  // lanes of rows outside ROWS receive 0
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROWS, 0xf, false));
 }
 __device__ __forceinline__ float wave_sum(float v) {
-#ifdef MDT_SHFL_REDUCE
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-#else
     v += dpp_get<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
     v += dpp_get<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
     v += dpp_get<0x141, 0xf>(v);  // row_half_mirror
@@ -35,16 +29,10 @@ __device__ __forceinline__ float wave_sum(float v) {
     v += dpp_get<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
     v += dpp_get<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3: lane 63 holds the total
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-#endif
 }
 // the same for each 32-lane half of the wave (two rows of activations normalised side by side): every lane receives the sum
 // of its own half
 __device__ __forceinline__ float half_wave_sum(float v) {
-#ifdef MDT_SHFL_REDUCE
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-    return v;
-#else
     v += dpp_get<0xB1, 0xf>(v);
     v += dpp_get<0x4E, 0xf>(v);
     v += dpp_get<0x141, 0xf>(v);
@@ -53,7 +41,6 @@ __device__ __forceinline__ float half_wave_sum(float v) {
     const float lo = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 31));
     const float hi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
     return (threadIdx.x & 32) ? hi : lo;
-#endif
 }
 // wave-wide maximum, same route (rows outside a step's mask keep their own value)
 template <int CTRL, int ROWS>
@@ -62,11 +49,6 @@ __device__ __forceinline__ float dpp_keep(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, CTRL, ROWS, 0xf, false));
 }
 __device__ __forceinline__ float wave_max(float v) {
-#ifdef MDT_SHFL_REDUCE
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, WAVE));
-    return v;
-#else
     v = fmaxf(v, dpp_keep<0xB1, 0xf>(v));
     v = fmaxf(v, dpp_keep<0x4E, 0xf>(v));
     v = fmaxf(v, dpp_keep<0x141, 0xf>(v));
@@ -74,21 +56,10 @@ __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, dpp_keep<0x142, 0xa>(v));
     v = fmaxf(v, dpp_keep<0x143, 0xc>(v));
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-#endif
 }
 // N independent sums advancing together (the steps of different sums interleave: no step waits for its own result)
 template <int N>
 __device__ __forceinline__ void wave_sum_n(float (&v)[N]) {
-#ifdef MDT_SHFL_REDUCE
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        float t[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) t[i] = __shfl_xor(v[i], off, 64);
-#pragma unroll
-        for (int i = 0; i < N; ++i) v[i] += t[i];
-    }
-#else
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] += dpp_get<0xB1, 0xf>(v[i]);
 #pragma unroll
@@ -103,7 +74,6 @@ __device__ __forceinline__ void wave_sum_n(float (&v)[N]) {
     for (int i = 0; i < N; ++i) v[i] += dpp_get<0x143, 0xc>(v[i]);
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[i]), 63));
-#endif
 }
 
 
@@ -133,9 +103,6 @@ __device__ __forceinline__ float act_silu(float x) { return x / (1.0f + expf(-x)
 // lane while its SIMD partner wants the issue slots for MFMAs).  0.5 erfc(|x| / sqrt 2) = h;  x Phi(x) = max(x, 0) - |x| h.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 act_gelu2(f32x2 x) {
-#ifdef MDT_GELU_SCALAR  // A/B build: the scalar routine per value
-    return (f32x2){act_gelu(x.x), act_gelu(x.y)};
-#else
     // (not __builtin_bit_cast on x.x / x.y: on an ext-vector ELEMENT lvalue clang reads element 0 for both)
     const f32x2 nax = -__builtin_elementwise_abs(x);
     const f32x2 d = __builtin_elementwise_fma(nax, (f32x2)(-0.3275911f * 0.70710678118654752440f), (f32x2)(1.0f));
@@ -154,7 +121,6 @@ __device__ __forceinline__ f32x2 act_gelu2(f32x2 x) {
     f32x2 m;  // max(x, 0) as a clamp to [0, inf]
     m.x = __builtin_amdgcn_fmed3f(x0, 0.f, __builtin_inff()); m.y = __builtin_amdgcn_fmed3f(x1, 0.f, __builtin_inff());
     return __builtin_elementwise_fma(nax, h, m);
-#endif
 }
 
 __device__ __forceinline__ f32x4 apply_act(f32x4 v, int act) {

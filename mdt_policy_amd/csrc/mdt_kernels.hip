@@ -256,7 +256,7 @@ __global__ __launch_bounds__(64 * (NWAVES + LW)) void k_gemm_pipe(mdt_gemm_args 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int MT = MTILES * 16;
     constexpr bool KSTEP_PRIO = true;  // (a priority raised once for the waves' whole life measured 1.5 % slower)
-    constexpr int R = (NTW == 1 ? 6 : (NTW == 2 ? 4 : 3)) + MDT_RING_ADD;
+    constexpr int R = NTW == 1 ? 6 : (NTW == 2 ? 4 : 3);
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool loader = wave >= NWAVES;
@@ -425,7 +425,7 @@ __global__ __launch_bounds__(512) void k_attn_proj_wide(mdt_gemm_args a, mdt_att
 template <int HD, int TKC>
 __global__ __launch_bounds__(512) void k_attn_xattn(mdt_gemm_args a, mdt_attn_pro at, mdt_xapply_args x, const float* __restrict__ zeros) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    attn_xattn_tile<HD, TKC, 32>(a, at, x, MDT_SAMPLE_REMAP(blockIdx.x, gridDim.x), lds, zeros, threadIdx.x);
+    attn_xattn_tile<HD, TKC, 32>(a, at, x, xcd_remap(blockIdx.x, gridDim.x), lds, zeros, threadIdx.x);
 }
 
 // 256 KiB of zeros per device: stands in for absent bias / rowvec / LayerNorm-bias vectors.  ensure_zeros() points
@@ -580,8 +580,6 @@ __global__ __launch_bounds__(64 * NWAVES) void k_gemm_ws_split(mdt_gemm_args a, 
 // tiles as two independent workgroups per CU (27.6 vs 27.5 ms per head step), 4 waves x 3 tiles for the N = 576 / 192 products
 // (272 VGPRs: qkv 225 -> 215 us against the tall body, c_proj 81.6 -> 81.0 against the row tiles: not worth a shape).
 static int ws_shape(const mdt_gemm_args& a) {
-    static int w12 = -1;  // MDT_HIP_WS_WAVES=8: the 8-wave shape everywhere (A/B runs)
-    if (w12 < 0) { const char* e = getenv("MDT_HIP_WS_WAVES"); w12 = e && atoi(e) == 8 ? 0 : 1; }
     if (a.K == 384) {
         // one column tile per wave: 128- (8 waves) or 192-column (12 waves) panels.  One round of one workgroup per CU either way;
         // what differs is how evenly the row tiles divide: cost ~ tiles per workgroup x waves (a SIMD's waves share its matrix pipe).
@@ -589,7 +587,7 @@ static int ws_shape(const mdt_gemm_args& a) {
         const int ntiles = (a.M + 31) / 32;
         int best = 0, best_cost = 0;
         for (int nw : {12, 8}) {
-            if ((nw == 12 && !w12) || a.N % (nw * 16)) continue;
+            if (a.N % (nw * 16)) continue;
             const int panels = a.N / (nw * 16), groups = std::max(1, std::min(256 / (8 * panels), (ntiles + 7) / 8));
             if (8 * panels > 256) continue;
             const int tiles = (ntiles + 8 * groups - 1) / (8 * groups), cost = tiles * nw;
@@ -600,7 +598,7 @@ static int ws_shape(const mdt_gemm_args& a) {
     // 384-column panels, three waves per SIMD, 4 / 2 panels x 64 / 128 row chunks = 256 workgroups: the per-tile epilogue + barrier is
     // amortised over 18.4 k instead of 12.3 k clocks of MFMA issue and all 256 CUs work (SwishGLU forward 601 -> 544 us, plain 272 -> 248).
     // Not for the SwishGLU backward epilogue: at 168 VGPRs its u operands cannot be requested a tile ahead (348 -> 448 us)
-    if (w12 && a.N % 384 == 0 && a.aux_mode != 4) return 12;
+    if (a.N % 384 == 0 && a.aux_mode != 4) return 12;
     return a.N % 256 == 0 ? 8 : 0;
 }
 // the three-way bf16 split of the weight-stationary body (mdt_ws.h): K = 384, 128-column panels (8 waves, one column tile each)
@@ -617,12 +615,10 @@ static bool ws_split_192(const mdt_gemm_args& a) {
     return ws_split_on() && a.K == 192 && a.N % 192 == 0 && a.N % 256 != 0 && a.N / 192 <= 32 && a.aux_mode == 0 && a.act == MDT_ACT_NONE;
 }
 bool mdt_gemm_ws_supported(const mdt_gemm_args& a) {
-    static int k384 = -1;  // MDT_HIP_WS384=0: the K = 384 products stay on the row tiles / the tall body (A/B runs)
-    if (k384 < 0) { const char* e = getenv("MDT_HIP_WS384"); k384 = e ? atoi(e) : 1; }
     const bool common = !a.ln && a.a_parts <= 1 && a.batch <= 1 && a.M >= 32 && (a.lda & 3) == 0 && (a.ldo & 3) == 0 && !a.residual &&
                         a.gin == 1 && a.gout == 1 && a.goff == 0 && a.rowvec == nullptr && (int64_t)a.N * a.K < ((int64_t)1 << 30);
     if (a.K == 384)   // plain rows, or an activation / the training hooks on the epilogue (GLU = 1 instantiation)
-        return k384 && common && (a.aux_mode == 0 || ((a.aux_mode == 1 || a.aux_mode == 2) && a.aux != nullptr)) && ws_shape(a) != 0;
+        return common && (a.aux_mode == 0 || ((a.aux_mode == 1 || a.aux_mode == 2) && a.aux != nullptr)) && ws_shape(a) != 0;
     const bool mode_ok = a.aux_mode == 0 || ((a.aux_mode == 3 || a.aux_mode == 4) && a.aux != nullptr);
     return common && a.K == 192 && (ws_shape(a) != 0 || ws_split_192(a)) && a.act == MDT_ACT_NONE && mode_ok;
 }
@@ -722,7 +718,7 @@ __global__ __launch_bounds__(512) void k_gemm_smallm2(mdt_gemm_args a, mdt_gemm_
     }
 }
 
-static int g_mdt_mid_max = 1400;    // rows up to which the 16 x 64 tiled geometry is used (env MDT_HIP_MID_MAX)
+static constexpr int GEMM_MID_MAX = 1400;  // rows up to which the 16 x 64 tiled geometry is used
 // k_xattn_gemm_smallm: the collapsed cross-attention of sample b and, on its output rows, 16 columns (blockIdx.x) of the
 // LayerNorm + modulate -> Linear that follows (mlp.c_fc) -- rollout batches: the cross-attention launch (one workgroup, 6.5 us
 // of latency per decoder block at B = 1) disappears into the c_fc launch, whose 96 workgroups each repeat it on the MFMA pipe
@@ -739,9 +735,9 @@ __global__ __launch_bounds__(512) void k_xattn_gemm_smallm(mdt_xapply_args x, md
     gemm_smallm_tile<false, true>(a, blockIdx.x, b * x.Ta, s_stat, red, zeros, threadIdx.x, yo, ys, x.Ta);
 }
 
-static int g_mdt_smallm_rows = 512;   // ... up to this many rows (env MDT_HIP_SMALLM_ROWS)
-static int g_mdt_smallm_tiles = 0;    // 0: the measured rule below; > 0 (env MDT_HIP_SMALLM_TILES): one threshold for every product (A/B runs): fewer 16 x 64 tiles than this -> the split-K kernel (env MDT_HIP_SMALLM_TILES)
-static int g_mdt_smallm_max = -1;  // rows up to which k_gemm_smallm is used (env MDT_HIP_SMALLM_MAX, default below)
+// rows up to which k_gemm_smallm is used: one row tile; beyond it the tile-count rule in mdt_launch_gemm decides, up to
+// GEMM_SMALLM_ROWS rows (round 1 had 192 rows here, before the half-height tiles)
+static constexpr int GEMM_SMALLM_MAX = 15, GEMM_SMALLM_ROWS = 512;
 
 int mdt_gemm_kchunk(int K, int ln, int cap) {
     if (ln || K <= 512) return K;
@@ -760,26 +756,19 @@ static hipError_t launch_gemm_pro(const mdt_gemm_args& a, int kchunk, hipStream_
 }
 
 int g_mdt_gemm_force = 0;  // tuning hook: 0 = heuristic, 1.. selects a geometry below, -1 = the split-K small-M kernel
-static const bool g_mdt_gemm_nopipe = getenv("MDT_HIP_NOPIPE") != nullptr;  // A/B switch for k_gemm_pipe
-
-// Self-attention of ONE sample fused into its output projection (k_attn_proj_smallm).  `p` is the projection's GEMM
-// (A ignored: the attention output never reaches memory; M = the sample's T rows); q / k / v are the three column
-// blocks of the (T, 3 K) qkv rows.  Supported: 8 heads of 16 / 32 / 48 / 64, T <= 16, no RoPE, plain output rows.
-static bool attn_proj_disabled() {  // MDT_HIP_NO_ATTN_PROJ=1: the separate attention + projection launches (A/B runs)
-    static int off = -1;
-    if (off < 0) off = getenv("MDT_HIP_NO_ATTN_PROJ") != nullptr;
-    return off != 0;
-}
 
 // WStream (mdt_tiles.h) addresses a weight image with 32-bit byte offsets from its base: every launcher that feeds one checks
 // the image size (mdt_launch_gemm does for the GEMMs; the fused MLP and attn_xattn tiles bound N and K by their shape rules)
 static bool w_image_ok(int64_t N, int64_t K) { return N * K < ((int64_t)1 << 30); }
 
+// Self-attention of ONE sample fused into its output projection (k_attn_proj_smallm).  `p` is the projection's GEMM
+// (A ignored: the attention output never reaches memory; M = the sample's T rows); q / k / v are the three column
+// blocks of the (T, 3 K) qkv rows.  Supported: 8 heads of 16 / 32 / 48 / 64, T <= 16, no RoPE, plain output rows.
 bool mdt_attn_proj_supported(const mdt_gemm_args& p, int H, int hd, int T, int rope) {
     return w_image_ok(p.N, p.K) && H == 8 && (hd == 16 || hd == 32 || hd == 48 || hd == 64) && p.K == H * hd && T >= 1 && T <= 16 && p.M >= T &&
            p.M % T == 0 && p.M / T <= 64 && (p.rows_per_sample == T || p.M == T) && !rope &&
            !(p.N & 15) && p.gin == 1 && p.gout == 1 && p.goff == 0 && !p.ln && p.act == MDT_ACT_NONE && p.rowvec == nullptr &&
-           p.batch <= 1 && !attn_proj_disabled();
+           p.batch <= 1;
 }
 
 template <int HD>
@@ -895,13 +884,10 @@ static bool smallm_shape_ok(const mdt_gemm_args& a) {
            a.N <= ZEROS_FLOATS && a.K <= ZEROS_FLOATS && !(a.N & 15) && (int64_t)a.N * a.K < ((int64_t)1 << 30);
 }
 // process-wide (the queue itself is per host thread): atomics, host threads may drive different handles side by side
-static std::atomic<int> g_side_override{-1};     // mdt_op_set_side_jobs (tests / A-B runs): 0 = off, 1 = on, -1 = the environment's choice
+static std::atomic<int> g_side_override{-1};     // mdt_op_set_side_jobs (tests): 0 = off, 1 = on, -1 = the default (on)
 static std::atomic<int64_t> g_side_paired{0};    // launches that took a side job along (mdt_op_side_jobs_paired)
 static bool side_enabled() {
-    static int v = -1;  // MDT_HIP_SIDE_JOBS=0: every product its own launch (A/B runs)
-    if (v < 0) { const char* e = getenv("MDT_HIP_SIDE_JOBS"); v = e ? atoi(e) : 1; }
-    const int ov = g_side_override.load(std::memory_order_relaxed);
-    return (ov >= 0 ? ov != 0 : v != 0) && g_mdt_gemm_force == 0;
+    return g_side_override.load(std::memory_order_relaxed) != 0 && g_mdt_gemm_force == 0;
 }
 extern "C" void mdt_op_set_side_jobs(int32_t on) { g_side_override.store(on < 0 ? -1 : (on != 0)); }
 extern "C" int64_t mdt_op_side_jobs_paired(void) { return g_side_paired.load(); }
@@ -948,16 +934,6 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
     if ((int64_t)a.N * a.K >= ((int64_t)1 << 30)) return hipErrorInvalidValue;
     hipError_t ze = ensure_zeros();
     if (ze != hipSuccess) return ze;
-    if (g_mdt_smallm_max < 0) {
-        const char* e = getenv("MDT_HIP_SMALLM_MAX");
-        g_mdt_smallm_max = e ? atoi(e) : 15;  // one row tile; beyond it the tile-count rule below decides (round 1 had 192 rows here, before the half-height tiles)
-        const char* f = getenv("MDT_HIP_MID_MAX");
-        if (f) g_mdt_mid_max = atoi(f);
-        const char* t = getenv("MDT_HIP_SMALLM_TILES");
-        if (t) g_mdt_smallm_tiles = atoi(t);
-        const char* r = getenv("MDT_HIP_SMALLM_ROWS");
-        if (r) g_mdt_smallm_rows = atoi(r);
-    }
     // (not for the batched split-K products of the weight gradients: few output rows there come with a DEEP reduction --
     // N = 192 layers of the masked-image decoder: 595 us as 16-column split-K tiles vs ~300 us tiled)
     // the training hooks of the epilogue (aux) exist in the plain-prologue, non-residual tiled kernels only
@@ -965,11 +941,9 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
     if (a.aux_mode == 3 || a.aux_mode == 4) {  // SwishGLU on the epilogue: own kernels (4 waves; forward: pairs of column tiles per wave)
         if ((a.N & (a.aux_mode == 3 ? 31 : 15)) || a.gin != 1 || a.gout != 1 || a.goff != 0 || a.act != MDT_ACT_NONE)
             return hipErrorInvalidValue;
-        // from 8192 rows on, K = 192: the weight-stationary body (mdt_ws.h) with the same epilogues -- round 5; MDT_HIP_WS=0: the 32-row
-        // tiles (A/B runs).  The masked-image head's two SwishGLU products at B = 1024 (104448 rows).
-        static int ws = -1;
-        if (ws < 0) { const char* e = getenv("MDT_HIP_WS"); ws = e ? atoi(e) : 1; }
-        if (ws && a.M >= 8192 && g_mdt_gemm_force <= 0 && mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
+        // from 8192 rows on, K = 192: the weight-stationary body (mdt_ws.h) with the same epilogues -- round 5.  The masked-image
+        // head's two SwishGLU products at B = 1024 (104448 rows).
+        if (a.M >= 8192 && g_mdt_gemm_force <= 0 && mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
         const int kc = mdt_gemm_kchunk(a.K, 0, 384);
         if (a.aux_mode == 3)
             return (a.N % 256 == 0) ? launch_gemm_glu<2, 4, 4, 3>(a, kc, s) : launch_gemm_glu<2, 2, 4, 3>(a, kc, s);
@@ -983,10 +957,9 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
     // projections of a block at B = 12 ... 32.  Measured per sampler call (tools/latency.py, profiles/r04_lowbatch.txt):
     // B = 8 1.79 -> 1.69 ms, 10 2.06 -> 1.72, 16 2.43 -> 1.74, 19 2.93 -> 2.07, 24 2.36 -> 2.17, 32 2.39 -> 2.19.
     const int64_t tiles6 = (int64_t)((a.M + 15) / 16) * ((a.N + 63) / 64);
-    const bool few_tiles = a.M <= g_mdt_smallm_rows &&
-                           tiles6 < (g_mdt_smallm_tiles > 0 ? g_mdt_smallm_tiles : (a.ln ? 60 : (a.M <= 192 ? 100 : 160)));
+    const bool few_tiles = a.M <= GEMM_SMALLM_ROWS && tiles6 < (a.ln ? 60 : (a.M <= 192 ? 100 : 160));
     // (geometry hook -1: the split-K kernel wherever it applies -- tests that pin it against its fused variants)
-    if ((a.M <= g_mdt_smallm_max || few_tiles || g_mdt_gemm_force < 0) && g_mdt_gemm_force <= 0 && (!a.ln || a.K <= 512) && a.batch <= 1 && a.K <= 4096 && !a.aux_mode) {
+    if ((a.M <= GEMM_SMALLM_MAX || few_tiles || g_mdt_gemm_force < 0) && g_mdt_gemm_force <= 0 && (!a.ln || a.K <= 512) && a.batch <= 1 && a.K <= 4096 && !a.aux_mode) {
         if (g_side_next < g_side_jobs.size() && a.batch <= 1 && a.M <= 16 * 64) {  // a queued side job rides in this launch
             const mdt_gemm_args b = g_side_jobs[g_side_next++];
             ++g_side_paired;
@@ -1025,7 +998,7 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
     // tiles double the workgroup count; measured 4-17 % faster per sampler call up to M ~ 1400, slower beyond 2000
     // ... unless the output is so wide that they would be thousands (the stacked adaLN projection of a training batch:
     // 1024 x 9216 -> 9216 workgroups that each re-read their weight tile): then the scored choice stands
-    if (a.M <= g_mdt_mid_max && (int64_t)((a.M + 15) / 16) * ((a.N + 63) / 64) <= 4096) {
+    if (a.M <= GEMM_MID_MAX && (int64_t)((a.M + 15) / 16) * ((a.N + 63) / 64) <= 4096) {
         geo = 6;
         // ... except where 4-wave 32 x 192 tiles come out as (nearly) whole rounds of one workgroup per CU: the encoder's
         // and the B ~ 120..140 decoder's wide products (tools/gemm_shapes.py: 1024 x 1536 22.0 -> 18.3 us, 1024 x 3072 33.7 ->
@@ -1041,42 +1014,17 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
     // one wave only -- beat every 8-wave geometry whenever N is a multiple of 192 (tools/gemm_train_shapes.py: 10240 x 1536 x 384
     // 126 -> 107 us, 104448 x 192 x 768 372 -> 282 us, 104448 x 576 x 192 332 -> 233 us); N = 384 keeps the choices above
     // (36.5 vs 38.4 us at K = 384, the co-resident 32 x 128 tiles at K = 1536)
-    {
-        static int g9 = -1;
-        if (g9 < 0) { const char* e = getenv("MDT_HIP_GEO_TRAIN"); g9 = e ? atoi(e) : 9; }
-        if (g9 && !a.ln && a.M >= 4096 && a.N % 192 == 0 && a.N != 384 && a.batch <= 1) geo = g9;
-    }
+    if (!a.ln && a.M >= 4096 && a.N % 192 == 0 && a.N != 384 && a.batch <= 1) geo = 9;
     // ... and from 8192 rows on the TALL body (mdt_tall.h: 128-row tiles, both operands staged in LDS by LDS-DMA, each staged
     // element used by 2-4 waves) where the column count is a multiple of its 64-wide tiles: the forward / input-gradient
     // products of a B = 1024 training step and the masked-image head's 104 k rows (tools/gemm_train_shapes.py,
     // profiles/r04_gemm_train_shapes.txt: 104448 x 576 x 192 249 -> 213-231 us, 104448 x 192 x 768 290 -> 263-270,
     // 10240 x 384 x 1536 124 -> 105-112, 10240 x 1152 x 384 94 -> 88-92; 10240 x 384 x 384 unchanged, 4096 rows lose)
-    // ... and the K = 192 products among them whose column count is a multiple of 256 on the weight-stationary body (mdt_ws.h);
-    // MDT_HIP_WS=0: A/B runs
-    {
-        static int ws = -1;
-        if (ws < 0) { const char* e = getenv("MDT_HIP_WS"); ws = e ? atoi(e) : 1; }
-        if (ws && a.M >= 8192 && (a.aux_mode == 0 || a.K == 384) && g_mdt_gemm_force <= 0 && mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
-    }
-    {
-        static int gt = -1;
-        if (gt < 0) { const char* e = getenv("MDT_HIP_GEO_TALL"); gt = e ? atoi(e) : 23; }
-        if (gt && a.M >= 8192 && a.N % 64 == 0 && (a.N > 384 || a.K > 384) && a.batch <= 1 && mdt_gemm_tall_supported(a)) geo = gt;
-    }
-    if (a.batch > 1) {  // split-K partial products (deep reductions): geometry chosen for those, env override for A/B runs
-        static int bgeo = -1;
-        if (bgeo < 0) { const char* e = getenv("MDT_HIP_BATCH_GEO"); bgeo = e ? atoi(e) : 5; }
-        geo = bgeo;
-    }
+    // ... and the K = 192 products among them whose column count is a multiple of 256 on the weight-stationary body (mdt_ws.h)
+    if (a.M >= 8192 && (a.aux_mode == 0 || a.K == 384) && g_mdt_gemm_force <= 0 && mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
+    if (a.M >= 8192 && a.N % 64 == 0 && (a.N > 384 || a.K > 384) && a.batch <= 1 && mdt_gemm_tall_supported(a)) geo = 23;
+    if (a.batch > 1) geo = 5;  // split-K partial products (deep reductions): geometry chosen for those
     if (g_mdt_gemm_force > 0) geo = g_mdt_gemm_force;
-    {   // tuning hooks (A/B runs): geometry of the wide (N >= 1024) / narrow products of large batches
-        static int gw = -1, gn = -1;
-        if (gw < 0) { const char* e = getenv("MDT_HIP_GEO_WIDE"); gw = e ? atoi(e) : 0; const char* f = getenv("MDT_HIP_GEO_NARROW"); gn = f ? atoi(f) : 0; }
-        if (a.M > g_mdt_mid_max && a.batch <= 1 && g_mdt_gemm_force <= 0) {
-            if (a.N >= 1024 && gw) geo = gw;
-            if (a.N < 1024 && gn) geo = gn;
-        }
-    }
     if (geo == 30) {  // forced: the weight-stationary body (tests pin it against the other bodies)
         if (mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
         geo = 0;
@@ -1089,7 +1037,7 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
         case 23: return launch_gemm_tall<2, 2, 2, 3, 1>(a, s);  // 4 + 1 waves 128 x 64,  3 stages (72 KiB: two per CU)
         case 1: return launch_gemm_pro<2, 1, 4>(a, mdt_gemm_kchunk(a.K, a.ln, 384), s);
         case 2:
-            if (!a.ln && a.K > 512 && !g_mdt_gemm_nopipe) {  // multi-chunk K: loader waves double-buffer the activation chunk
+            if (!a.ln && a.K > 512) {  // multi-chunk K: loader waves double-buffer the activation chunk
                 const int kc = mdt_gemm_kchunk(a.K, 0, 384);
                 return a.residual ? launch_gemm_pipe_r<2, 1, 8, 4, true>(a, kc, s)
                                   : launch_gemm_pipe_r<2, 1, 8, 4, false>(a, kc, s);
@@ -1100,12 +1048,10 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
         case 6: {
             // 4 waves 16 x 64.  Deep K (the encoder's / a mid batch's c_proj, K = 4d in four LDS chunks): with two LOADER waves that
             // double-buffer the activation chunk -- as a single-buffer loop each chunk was a memory round trip of its own in front of
-            // its 24 k-steps, and half-height tiles have few workgroups per CU to hide it (MDT_HIP_PIPE6=0: A/B runs)
-            static int p6 = -1;
-            if (p6 < 0) { const char* e = getenv("MDT_HIP_PIPE6"); p6 = e ? atoi(e) : 1; }
+            // its 24 k-steps, and half-height tiles have few workgroups per CU to hide it
             // (up to one workgroup per CU: beyond that the co-resident workgroups hide each other's round trips -- the encoder's
             //  1024-row c_proj, 384 workgroups, measured +0.1 % with the loader waves)
-            if (p6 && !a.ln && a.K > 512 && !a.aux_mode && !g_mdt_gemm_nopipe && (int64_t)((a.M + 15) / 16) * ((a.N + 63) / 64) <= 256) {
+            if (!a.ln && a.K > 512 && !a.aux_mode && (int64_t)((a.M + 15) / 16) * ((a.N + 63) / 64) <= 256) {
                 const int kc = mdt_gemm_kchunk(a.K, 0, 384);
                 return a.residual ? launch_gemm_pipe_r<1, 1, 4, 2, true>(a, kc, s) : launch_gemm_pipe_r<1, 1, 4, 2, false>(a, kc, s);
             }
@@ -1130,13 +1076,10 @@ bool mdt_mlp_supported(const mdt_gemm_args& f, const mdt_gemm_args& p) {
 int mdt_mlp_slices(int D) { return 4 * D / 512; }
 
 // mlp_tile's wave schedule: low byte = k-steps the second wave of a SIMD starts behind the first (0: lockstep, workgroup
-// barrier between the two products), | 256 = MFMA loops at raised issue priority.  Measured at B = 256 (tools/gpu_skew_ab3.sh,
-// profiles/r03_mlp_skew_ab.txt): 0 -> 4.89, 6 -> 4.86, 18 | 256 -> 4.82 ms per sampler call.  MDT_HIP_MLP_SKEW / the hook: A/B runs, tests.
+// barrier between the two products), | 256 = MFMA loops at raised issue priority.  Measured at B = 256 (
+// profiles/r03_mlp_skew_ab.txt): 0 -> 4.89, 6 -> 4.86, 18 | 256 -> 4.82 ms per sampler call.  The hook: tests.
 static int g_mlp_skew = -1;
-static int mlp_skew() {
-    if (g_mlp_skew < 0) { const char* e = getenv("MDT_HIP_MLP_SKEW"); g_mlp_skew = e ? atoi(e) & 0x1ff : (18 | 256); }
-    return g_mlp_skew;
-}
+static int mlp_skew() { return g_mlp_skew < 0 ? 18 | 256 : g_mlp_skew; }
 extern "C" void mdt_op_set_mlp_skew(int32_t v) { g_mlp_skew = v < 0 ? -1 : (v & 0x1ff); }
 
 template <int NTW2, int PRO>
@@ -1229,11 +1172,7 @@ bool mdt_mlp_split_enabled() {
     return g_mlp_split != 0;
 }
 extern "C" void mdt_op_set_mlp_split(int32_t on) { g_mlp_split = on < 0 ? -1 : (on != 0); }
-int mdt_split_min_rows() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MDT_HIP_SPLIT_MIN_ROWS"); v = e ? std::max(1, atoi(e)) : 768; }
-    return v;
-}
+int mdt_split_min_rows() { return 768; }
 bool mdt_mlp_split_supported(const mdt_gemm_args& f, const mdt_gemm_args& p) {
     return mdt_mlp_supported(f, p);
 }
@@ -1324,7 +1263,7 @@ __global__ __launch_bounds__(256) void k_attn(mdt_attn_args a, const float* __re
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // sample -> XCD as the GEMMs map row tiles -> XCD (xcd_remap): the q/k/v rows this workgroup reads were written
     // by GEMM tiles of the same XCD and the rows it writes are read there again (speed only)
-    const int b = MDT_SAMPLE_REMAP(blockIdx.x, gridDim.x);
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
     attn_tile<HD, TKC, ROPE, false>(a, rope_cos, rope_sin, scale, b, blockIdx.y, gridDim.y, lds, threadIdx.x);
 }
 
@@ -1445,25 +1384,6 @@ __global__ void k_sigma_emb(const float* __restrict__ sigma, int64_t sstride, co
     out[(int64_t)r * D + half + j] = cosf(ang);
 }
 
-// per-step DDIM scalars from a device-resident schedule: steps[i] = {sigma_{i+1}/sigma_i as exp(-t')/exp(-t), -expm1(-h),
-// sigma_{i+1}, sigma_i} with t = -ln sigma, h = t' - t        (gc_sampling.py:946-950, fp32 like the reference's tensors)
-__global__ void k_ddim_steps(const float* __restrict__ sigmas, int n, float* __restrict__ steps) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float s0 = sigmas[i], s1 = sigmas[i + 1];
-    const float t = -logf(s0), tn = -logf(s1);
-    const float h = tn - t;
-    steps[4 * i + 0] = expf(-tn) / expf(-t);
-    steps[4 * i + 1] = -expm1f(-h);
-    steps[4 * i + 2] = s1;
-    steps[4 * i + 3] = s0;
-}
-
-hipError_t mdt_launch_ddim_steps(const float* sigmas_dev, int n, float* steps, hipStream_t s) {
-    hipLaunchKernelGGL(k_ddim_steps, dim3((n + 63) / 64), dim3(64), 0, s, sigmas_dev, n, steps);
-    return hipGetLastError();
-}
-
 hipError_t mdt_launch_sigma_emb(const float* sigma, int64_t sstride, const float* freqs, float* out, int R, int D,
                                 hipStream_t s) {
     const int n = R * (D / 2);
@@ -1544,8 +1464,9 @@ hipError_t mdt_launch_action_embed(const float* x, const float* sigma, int64_t s
 // k_ddim_steps + k_sigma_emb + k_action_embed: four dependent ~4.5 us launches in front of every sampler call, a tenth of a
 // rollout-sized call).  A host schedule travels in the kernel arguments; a device schedule is read in place.  Blocks
 // [0, n_act) embed the first noisy actions (k_action_embed's arithmetic with c_in(sigma_0)), blocks [n_act, n_act + n_emb) write
-// the sinusoidal sigma embeddings of all steps (k_sigma_emb's), the last block the per-step DDIM scalars (k_ddim_steps's) --
-// each from the schedule itself, so nothing in the launch depends on anything else in it, and every value has the bits the
+// the sinusoidal sigma embeddings of all steps (k_sigma_emb's), the last block the per-step DDIM scalars -- steps[i] =
+// {sigma_{i+1}/sigma_i as exp(-t')/exp(-t), -expm1(-h), sigma_{i+1}, sigma_i} with t = -ln sigma, h = t' - t (gc_sampling.py:946-950,
+// fp32 like the reference's tensors) -- each from the schedule itself, so nothing in the launch depends on anything else in it, and every value has the bits the
 // separate kernels gave.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sample_prep(const float* __restrict__ sig_dev, mdt_sched_arg sv, int n_steps,
@@ -1789,7 +1710,7 @@ hipError_t mdt_launch_xattn_fold(const mdt_xfold_args& a, hipStream_t s) { retur
 template <int NPP>
 __global__ __launch_bounds__(512) void k_xattn_apply(mdt_xapply_args a, const float* __restrict__ zeros) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    xattn_tile<NPP, false>(a, MDT_SAMPLE_REMAP(blockIdx.x, gridDim.x), lds, zeros, threadIdx.x);
+    xattn_tile<NPP, false>(a, xcd_remap(blockIdx.x, gridDim.x), lds, zeros, threadIdx.x);
 }
 
 // which configurations the collapsed path covers (others keep the q GEMM + attention + c_proj GEMM sequence)

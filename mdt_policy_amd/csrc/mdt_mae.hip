@@ -802,19 +802,15 @@ size_t attn_mid_lds(int hd, int T, bool bwd) {
 
 template <int HD>
 hipError_t launch_fwd(const float* qkv, int64_t ld, float* out, int64_t ldo, int64_t B, int H, int T, float scale, hipStream_t s) {
-    static int form = -1;  // MDT_HIP_ATTN_FWD=1: the first form (probabilities through a wave-private LDS tile), for A/B runs
-    if (form < 0) { const char* e = getenv("MDT_HIP_ATTN_FWD"); form = e ? atoi(e) : 2; }
-    // (the second form addresses a sample's rows with 32-bit byte offsets: a sample must span less than 2 GiB)
-    if (form == 2 && HD <= 32 && (int64_t)T * ld + 3ll * H * HD < (1ll << 29)) {
+    // the second form where it applies, else the first (probabilities through a wave-private LDS tile): hd > 32, T > 128.  (The
+    // second form addresses a sample's rows with 32-bit byte offsets: a sample must span less than 2 GiB.)
+    if (HD <= 32 && (int64_t)T * ld + 3ll * H * HD < (1ll << 29)) {
         const size_t lds2 = attn_mid_lds_fwd2(HD, T);
         // heads per workgroup: all of them once that still leaves four waves per SIMD on every CU, else the largest divisor of H
         // that does
-        static int hpw_env = -1;
-        if (hpw_env < 0) { const char* e = getenv("MDT_HIP_ATTN_HPW"); hpw_env = e ? atoi(e) : 0; }
         const int n = (T + 15) >> 4, per_cu = n > 4 ? 2 : 4;
         int hpw = H;
         while (hpw > 1 && (B * (H / hpw) < 256 * per_cu || H % hpw)) --hpw;
-        if (hpw_env > 0 && H % hpw_env == 0) hpw = hpw_env;
         const dim3 grid((unsigned)B, H / hpw);
 #define MDT_FWD2(N_)                                                                                                              \
     case N_: {                                                                                                                    \
@@ -837,11 +833,9 @@ hipError_t launch_fwd(const float* qkv, int64_t ld, float* out, int64_t ldo, int
 template <int HD>
 hipError_t launch_bwd(const float* qkv, int64_t ld, const float* fo, int64_t ldf, const float* d_out, int64_t ldd, float* d_qkv,
                       int64_t ldg, int64_t B, int H, int T, float scale, hipStream_t s) {
-    static int form = -1;  // MDT_HIP_ATTN_BWD=1: the first form (T x T matrices in LDS, five phases), for A/B runs
-    if (form < 0) { const char* e = getenv("MDT_HIP_ATTN_BWD"); form = e ? atoi(e) : 2; }
+    // the second form where it applies, else the first (T x T matrices in LDS, five phases): hd > 32, T > 128
     if constexpr (HD <= 32) {  // (hd 48 / 64: the T16 x hd accumulators of dK and dV no longer fit the registers)
-        if (form == 2) {
-            const size_t lds2 = attn_mid_lds2(HD, T);
+        const size_t lds2 = attn_mid_lds2(HD, T);
 #define MDT_BWD2(N_)                                                                                                              \
     case N_: {                                                                                                                    \
         hipError_t e2 = hipFuncSetAttribute((const void*)k_attn_mid_bwd2<HD, N_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
@@ -850,11 +844,10 @@ hipError_t launch_bwd(const float* qkv, int64_t ld, const float* fo, int64_t ldf
                            H, T, scale);                                                                                          \
         return hipGetLastError();                                                                                                 \
     }
-            switch ((T + 15) >> 4) {
-                MDT_BWD2(1) MDT_BWD2(2) MDT_BWD2(3) MDT_BWD2(4) MDT_BWD2(5) MDT_BWD2(6) MDT_BWD2(7) MDT_BWD2(8)
-            }
-#undef MDT_BWD2
+        switch ((T + 15) >> 4) {
+            MDT_BWD2(1) MDT_BWD2(2) MDT_BWD2(3) MDT_BWD2(4) MDT_BWD2(5) MDT_BWD2(6) MDT_BWD2(7) MDT_BWD2(8)
         }
+#undef MDT_BWD2
     }
     const size_t lds = attn_mid_lds(HD, T, true);
     hipError_t e = hipFuncSetAttribute((const void*)k_attn_mid_bwd<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -37,11 +37,9 @@ template <int NT, int R>
 struct SplitRing {
     mdt_bf16x8 w[R][NT][3];
     __amdgpu_buffer_rsrc_t rs;
-    const char* gbase;
     unsigned voff[NT];
     __device__ __forceinline__ void open(const void* image, int64_t first_byte, int64_t tile_stride, int lane) {
         rs = __builtin_amdgcn_make_buffer_rsrc((void*)image, 0, 0xffffffffu, 0x00020000);
-        gbase = (const char*)image;
 #pragma unroll
         for (int j = 0; j < NT; ++j) voff[j] = (unsigned)(first_byte + j * tile_stride) + 16u * (unsigned)lane;
     }
@@ -50,11 +48,7 @@ struct SplitRing {
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int p = 0; p < 3; ++p)
-#ifdef MDT_SPLIT_W_GLOBAL   // A/B build: 64-bit global loads
-                w[slot][j][p] = __builtin_bit_cast(mdt_bf16x8, *(const f32x4*)(gbase + voff[j] + (kk * 3 + p) * 1024));
-#else
                 w[slot][j][p] = __builtin_bit_cast(mdt_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff[j], (kk * 3 + p) * 1024, 0));
-#endif
     }
 };
 

@@ -109,8 +109,6 @@ extern "C" const char* mdt_version(void) { return "mdt_hip 0.1 (gfx950, v_mfma_f
 
 #include "mdt_model_types.h"
 
-static const int MAX_WAYS = 4;
-
 // workspace view of a contiguous slice of samples [b0, b0 + nb) for the decoder (Ta rows per sample)
 struct View {
     float *y, *qkv, *att, *hid, *qx, *kvx;
@@ -397,14 +395,6 @@ extern "C" mdt_status mdt_create(const mdt_config* cfg, mdt_model** out) {
     // the collapsed cross-attention needs a step-independent context and an unconditioned query input
     m->xfold = cond == COND_ADALN && !c.use_rot_embed && mdt_xattn_apply_supported(m->D, m->H, m->Te, m->Ta);
     if (const char* x = getenv("MDT_HIP_XFOLD")) m->xfold = m->xfold && atoi(x) != 0;
-    if (const char* w = getenv("MDT_HIP_WAYS")) m->ways = std::max(1, std::min(MAX_WAYS, atoi(w)));
-    // (the auxiliary streams of MDT_HIP_WAYS > 1 are created on first use: every stream a process creates takes a slot in the
-    //  runtime's small pool of hardware queues, and three idle ones per handle pushed the training path's side stream onto a
-    //  queue it shares -- the B = 1024 step read 9.75 ms inside bench.py, where two handles exist, against 9.19 alone)
-    if (hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) != hipSuccess) {
-        mdt_destroy(m);
-        return fail(MDT_ERR_HIP, "could not create the sampler's fork event");
-    }
     *out = m;
     return MDT_OK;
 }
@@ -412,11 +402,6 @@ extern "C" mdt_status mdt_create(const mdt_config* cfg, mdt_model** out) {
 extern "C" mdt_status mdt_destroy(mdt_model* m) {
     if (!m) return MDT_OK;
     (void)hipDeviceSynchronize();
-    for (int i = 0; i < MAX_WAYS - 1; ++i) {
-        if (m->aux[i]) (void)hipStreamDestroy(m->aux[i]);
-        if (m->ev_join[i]) (void)hipEventDestroy(m->ev_join[i]);
-    }
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
     mdt_train_free(m);
     (void)hipFree(m->arena);
     (void)hipFree(m->staging);
@@ -686,16 +671,12 @@ struct ModRef {
     ModRef(const float* m_, int64_t st, int sh, int sc, int g) : mod(m_), stride(st), shift(sh), scale(sc), gate(g) {}
 };
 
-// largest batch whose self-attention runs fused into the projection (MDT_HIP_ATTN_PROJ_MAX overrides; measured crossover)
-static int64_t g_attn_proj_max_batch() {
-    static int64_t v = -1;
-    // (round 2, B = 2 / 4 / 8: 1.87 -> 1.71, 2.02 -> 1.85, 2.24 -> 2.07 ms; B = 16 lost then, 2.76 -> 2.83.  Round 5, with the fused
-    //  kernel's attention on the MFMA pipe, its rows requested in one batch and its LDS cut to the T real rows -- two workgroups
-    //  per CU: B = 12 / 16 / 20 / 24 / 32 1.653 / 1.649 / 1.918 / 2.006 / 2.017 -> 1.49 / 1.50 / 1.74 / 1.93 / 1.95 ms; B = 48 loses,
-    //  2.30 -> 2.42)
-    if (v < 0) { const char* e = getenv("MDT_HIP_ATTN_PROJ_MAX"); v = e ? atoll(e) : 32; }
-    return v;
-}
+// largest batch whose self-attention runs fused into the projection (measured crossover)
+// (round 2, B = 2 / 4 / 8: 1.87 -> 1.71, 2.02 -> 1.85, 2.24 -> 2.07 ms; B = 16 lost then, 2.76 -> 2.83.  Round 5, with the fused
+//  kernel's attention on the MFMA pipe, its rows requested in one batch and its LDS cut to the T real rows -- two workgroups
+//  per CU: B = 12 / 16 / 20 / 24 / 32 1.653 / 1.649 / 1.918 / 2.006 / 2.017 -> 1.49 / 1.50 / 1.74 / 1.93 / 1.95 ms; B = 48 loses,
+//  2.30 -> 2.42)
+static constexpr int64_t ATTN_PROJ_MAX_BATCH = 32;
 
 // the residual stream as the previous sublayer left it: one array (parts <= 1: V.y) or the partial slabs of a fused MLP
 // launch, to be summed by whoever reads them next
@@ -705,31 +686,22 @@ struct Stream {
     int64_t stride = 0;
 };
 
-// row count from which the self-attention runs in the prologue of its output projection (MDT_HIP_ATTN_WIDE_MIN; 0 disables)
-static int g_attn_wide_override = -1;  // mdt_op_set_attn_wide_min (tests / A-B runs)
+// row count from which the self-attention runs in the prologue of its output projection
+static int g_attn_wide_override = -1;  // mdt_op_set_attn_wide_min (tests): 0 disables, -1 = the default
 static int g_attn_wide_min_rows() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MDT_HIP_ATTN_WIDE_MIN"); v = e ? atoi(e) : 1401; if (v == 0) v = 1 << 30; }
-    return g_attn_wide_override >= 0 ? (g_attn_wide_override == 0 ? 1 << 30 : g_attn_wide_override) : v;
+    return g_attn_wide_override >= 0 ? (g_attn_wide_override == 0 ? 1 << 30 : g_attn_wide_override) : 1401;
 }
 extern "C" void mdt_op_set_attn_wide_min(int32_t rows) { g_attn_wide_override = rows; }
 
 // row count from which (and batch up to which: two rounds of one workgroup per CU) one workgroup per sample runs self-attention,
-// projection AND the collapsed cross-attention (k_attn_xattn); MDT_HIP_ATTN_XATTN_MIN (0 disables) / MDT_HIP_ATTN_XATTN_MAX_B;
-// mdt_op_set_attn_wide_min(0) switches it off too
+// projection AND the collapsed cross-attention (k_attn_xattn); mdt_op_set_attn_wide_min(0) switches it off too
 static int g_attn_xattn_min_rows() {
-    static int v = -1;
     // (round 3 started it where the fused MLP launch starts, 1401 rows; measured down the batch sizes in round 4 -- tools/latency.py,
     //  profiles/r04_lowbatch.txt -- it beats k_attn + projection + k_xattn_apply from 200 rows on: B = 20 2.03 -> 1.99 ms, 32 2.13 -> 2.09,
     //  40 2.48 -> 2.35, 80 3.12 -> 3.03, 100 3.26 -> 3.17, 128 3.62 -> 3.52, 140 4.33 -> 4.14; at 160 rows it loses, 1.71 -> 1.75)
-    if (v < 0) { const char* e = getenv("MDT_HIP_ATTN_XATTN_MIN"); v = e ? atoi(e) : 200; if (v == 0) v = 1 << 30; }
-    return g_attn_wide_override == 0 ? 1 << 30 : v;
+    return g_attn_wide_override == 0 ? 1 << 30 : 200;
 }
-static int g_attn_xattn_max_batch() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MDT_HIP_ATTN_XATTN_MAX_B"); v = e ? atoi(e) : 512; }
-    return v;
-}
+static constexpr int64_t ATTN_XATTN_MAX_BATCH = 512;
 
 // `fx` (optional): the collapsed cross-attention that follows on the same rows; when the one-sample-per-workgroup kernel takes
 // both, *fused is set and the caller skips its own launch.
@@ -749,12 +721,12 @@ static mdt_status run_self_attn(mdt_model* m, const EncBlock& e, const View& V, 
     mdt_gemm_args p = gemm_args(V.att, D, e.proj, x, D, M);
     p.residual = 1; p.rows_per_sample = T;
     if (mr.mod && mr.gate >= 0) { p.mod = mr.mod; p.mod_stride = mr.stride; p.gate_off = mr.gate; }
-    if (B <= g_attn_proj_max_batch() && mdt_attn_proj_supported(p, m->H, m->hd, T, m->cfg.use_rot_embed)) {
+    if (B <= ATTN_PROJ_MAX_BATCH && mdt_attn_proj_supported(p, m->H, m->hd, T, m->cfg.use_rot_embed)) {
         // rollout batch: attention and projection in one launch (the attention output never leaves the workgroup)
         LAUNCH(mdt_launch_attn_proj(p, V.qkv, 3 * D, m->H, m->hd, T, causal, s));
         return MDT_OK;
     }
-    if (fx && fused && M >= g_attn_xattn_min_rows() && B <= g_attn_xattn_max_batch() &&
+    if (fx && fused && M >= g_attn_xattn_min_rows() && B <= ATTN_XATTN_MAX_BATCH &&
         mdt_attn_xattn_supported(p, *fx, m->H, m->hd, T, causal, m->cfg.use_rot_embed)) {
         LAUNCH(mdt_launch_attn_xattn(p, V.qkv, 3 * D, *fx, m->H, m->hd, T, s));
         *fused = true;
@@ -781,16 +753,13 @@ static mdt_status run_self_attn(mdt_model* m, const EncBlock& e, const View& V, 
 }
 
 // row count from which the MLP sublayer runs as ONE launch (k_mlp) that leaves partial slabs instead of the residual
-// stream (MDT_HIP_MLP_FUSE_MIN overrides; 0 disables): below it the wide tiles do not fill the chip
-static int g_mlp_fuse_override = -1;  // mdt_op_set_mlp_fuse_min (tests / A-B runs)
+// stream: below it the wide tiles do not fill the chip
+static int g_mlp_fuse_override = -1;  // mdt_op_set_mlp_fuse_min (tests): 0 disables, -1 = the default
 // (`split`: the launch would run in its bf16 split form, which pays from fewer rows -- mdt_split_min_rows(), B = 128: 1280 rows
-// per call 3.42 -> 2.96 ms with the qkv products split too (mdt_internal.h); an explicit setting, hook or environment, is taken as it is)
+// per call 3.42 -> 2.96 ms with the qkv products split too (mdt_internal.h); a setting made with the hook is taken as it is)
 static int g_mlp_fuse_min_rows(bool split = false) {
-    static int v = -2;
-    if (v == -2) { const char* e = getenv("MDT_HIP_MLP_FUSE_MIN"); v = e ? atoi(e) : -1; if (v == 0) v = 1 << 30; }
     if (g_mlp_fuse_override >= 0) return g_mlp_fuse_override == 0 ? 1 << 30 : g_mlp_fuse_override;
-    if (v >= 0) return v;
-    return split ? std::min(1401, mdt_split_min_rows()) : 1401;
+    return split ? mdt_split_min_rows() : 1401;
 }
 extern "C" void mdt_op_set_mlp_fuse_min(int32_t rows) { g_mlp_fuse_override = rows; }
 
@@ -882,8 +851,9 @@ static mdt_status run_mlp(mdt_model* m, const EncBlock& e, const View& V, int64_
     if (out) *out = Stream();
     // (never with `pre_x`: the caller skipped its own cross-attention launch because the c_fc launch was to run it)
     // the three-way bf16 split form of the launch (mdt_mlp_split.h) wherever its images exist and it is not switched off; it pays
-    // from fewer rows than the fp32 launch (g_mlp_fuse_min_rows)
-    const bool split = e.fc.ws && e.proj2.ws && mdt_mlp_split_enabled() && mdt_mlp_split_supported(g, p);
+    // from fewer rows than the fp32 launch (g_mlp_fuse_min_rows).  The row condition is split_ready's: below it the images may
+    // be stale (a training state's optimizer steps refresh them only for the launches that read them)
+    const bool split = e.fc.ws && e.proj2.ws && mdt_mlp_split_enabled() && M >= mdt_split_min_rows() && mdt_mlp_split_supported(g, p);
     if (out && !pre_x && M >= g_mlp_fuse_min_rows(split) && mdt_mlp_slices(D) >= 2 && mdt_mlp_supported(g, p)) {
         // the hidden buffer (M x 4D) is free in this form: it holds the S <= 4 slabs of (M x D)
         p.ldo = D;
@@ -912,12 +882,8 @@ static mdt_status run_mlp(mdt_model* m, const EncBlock& e, const View& V, int64_
 }
 
 // batch up to which the cross-attention of a decoder block runs inside the c_fc launch that follows it (rollout batches;
-// MDT_HIP_XATTN_FC_MAX_B, 0 disables)
-static int g_xattn_fc_max_batch() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MDT_HIP_XATTN_FC_MAX_B"); v = e ? atoi(e) : 2; }  // B = 4: 1.67 vs 1.58 ms per call
-    return v;
-}
+// B = 4: 1.67 vs 1.58 ms per call)
+static constexpr int64_t XATTN_FC_MAX_BATCH = 2;
 
 // sigma_emb: sinusoidal(ln(sigma)/4) -> Linear -> Mish -> Linear for R sigmas (mdtv_transformer.py:105-110,282-288);
 // the second Linear's output rows go to out (leading dimension ldo, row r -> row r*gout) after `act`.
@@ -996,8 +962,8 @@ static mdt_status run_encode(mdt_model* m, const float* tokens, const float* tok
         a.gin = 1; a.gout = Te; a.goff = m->g_row; a.rowvec = pos0;
         LAUNCH(mdt_launch_gemm(a, s));
     }
-    // The goal product above normally took the queued token embedding along.  Where it did not (a goal width or an override
-    // -- MDT_HIP_SMALLM_MAX / _ROWS / _TILES -- that routes it away from the small-M kernel), the job must not stay at the head of
+    // The goal product above normally took the queued token embedding along.  Where it did not (a goal width or a geometry
+    // override, mdt_op_set_gemm_geometry, that routes it away from the small-M kernel), the job must not stay at the head of
     // the queue: the next small-M launch would be the encoder's first LayerNorm product, which READS the rows the job writes.
     if (tok_side && mdt_gemm_side_pending() > side_before) LAUNCH(mdt_gemm_side_launch_front(s));
     // state tokens -> the rows after it                         (process_state_embeddings, :260 / mdt :300)
@@ -1115,7 +1081,7 @@ static mdt_status run_decoder_blocks(mdt_model* m, const View& V, int64_t B, con
             mdt_gemm_args gf = gemm_args(W.y, D, d.fc, W.hid, 4 * D, M);
             gf.ln = 1; gf.rows_per_sample = Ta;
             x.y_out = W.att;
-            x_in_fc = B <= g_xattn_fc_max_batch() && M <= 192 && m->Ld % 2 == 0 && mdt_xattn_gemm_supported(x, gf);
+            x_in_fc = B <= XATTN_FC_MAX_BATCH && M <= 192 && m->Ld % 2 == 0 && mdt_xattn_gemm_supported(x, gf);
             if (!x_in_fc) x.y_out = nullptr;
         }
         bool xdone = false;
@@ -1236,9 +1202,6 @@ static mdt_status sample_ddim_impl(mdt_model* m, const float* tokens, const floa
     hipStream_t s = (hipStream_t)stream;
     const int honour = m->cfg.arch == MDT_ARCH_MDTV;
     const bool per_step_ctx = m->cond == COND_TOKEN;  // sigma is a context token: the encoder cannot be hoisted
-    // ---- cut the batch into sample-aligned slices (multiples of 16 samples = 5 row tiles) on separate streams ----
-    int ways = per_step_ctx ? 1 : m->ways;  // the encoder works on whole-batch buffers
-    while (ways > 1 && batch / ways < 32) --ways;
     MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));  // before anything is enqueued
     MDT_TRY(check_loaded(m));
     MDT_TRY(mdt_reserve(m, batch));
@@ -1247,78 +1210,33 @@ static mdt_status sample_ddim_impl(mdt_model* m, const float* tokens, const floa
     // whether the schedule arrives in host memory (the reference's CPU default) or on the device (mdtv_agent.py:660-667: no
     // copy, no synchronisation then), so that the eager call, the call with device sigmas and the graph replay of either give
     // the same bits (host libm and the device's expf / logf differ in the last place)
-    if (ways == 1) {
-        // ONE launch: per-step scalars, the sigma embeddings of all steps, the first action embedding (k_sample_prep); a host
-        // schedule rides in the kernel arguments (no copy launch in front of it).  It goes FIRST: the three GEMMs of the
-        // conditioning table (M = n_steps rows) depend on nothing else and are queued as side jobs -- they ride in the launches
-        // of the encoder's first small products (rollout batches; at large batches whatever the encoder did not take along is
-        // launched behind it)
-        LAUNCH(mdt_launch_sample_prep(sigmas_dev, sigmas_dev ? nullptr : sigmas, n_steps, m->steps, m->freqs,
-                                      m->cond == COND_TOKEN ? nullptr : m->sig_e, m->D, x_T, m->cfg.sigma_data, m->Wa, m->ba,
-                                      decoder_view(m, 0).y, (int)(batch * m->Ta), m->A, s));
-        mdt_status ms = run_modulation(m, m->steps + 3, 4, n_steps, s, true, !per_step_ctx);  // one row of conditioning vectors per step
-        if (ms == MDT_OK && !per_step_ctx) ms = run_encode(m, tokens, tokens2, goal, modality, honour, batch, nullptr, 0, ctx_out, s);
-        if (ms != MDT_OK) { mdt_gemm_side_drop(); return ms; }
-        LAUNCH(mdt_gemm_side_flush(s));
-    } else {
-        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, honour, batch, nullptr, 0, ctx_out, s));
-        if (!sigmas_dev) {
-            HIP_TRY(hipMemcpyAsync(m->sigs, sigmas, (size_t)(n_steps + 1) * sizeof(float), hipMemcpyHostToDevice, s));
-            sigmas_dev = m->sigs;
-        }
-        LAUNCH(mdt_launch_ddim_steps(sigmas_dev, n_steps, m->steps, s));
-        MDT_TRY(run_modulation(m, m->steps + 3, 4, n_steps, s));
-    }
-    int64_t b0[MAX_WAYS + 1];
-    b0[0] = 0;
-    for (int w = 0; w < ways; ++w) {
-        int64_t nb = (batch - b0[w]) / (ways - w);
-        if (w + 1 < ways) nb = std::min<int64_t>(batch - b0[w], (nb + 15) / 16 * 16);
-        b0[w + 1] = b0[w] + nb;
-    }
-    hipStream_t st[MAX_WAYS];
-    st[0] = s;
-    if (ways > 1) {
-        for (int w = 1; w < ways; ++w) {
-            if (!m->aux[w - 1]) HIP_TRY(hipStreamCreateWithFlags(&m->aux[w - 1], hipStreamNonBlocking));
-            if (!m->ev_join[w - 1]) HIP_TRY(hipEventCreateWithFlags(&m->ev_join[w - 1], hipEventDisableTiming));
-        }
-        HIP_TRY(hipEventRecord(m->ev_fork, s));
-        for (int w = 1; w < ways; ++w) {
-            st[w] = m->aux[w - 1];
-            HIP_TRY(hipStreamWaitEvent(st[w], m->ev_fork, 0));
-        }
-    }
-    const int64_t xs = (int64_t)m->Ta * m->A;  // floats of x per sample
-    for (int w = 0; ways > 1 && w < ways; ++w) {
-        const int64_t nb = b0[w + 1] - b0[w];
-        const View V = decoder_view(m, b0[w]);
-        LAUNCH(mdt_launch_action_embed(x_T + b0[w] * xs, m->steps + 3, 0, m->cfg.sigma_data, m->Wa, m->ba, V.y,
-                                       (int)(nb * m->Ta), m->A, m->D, m->Ta, st[w]));
-    }
+    // ONE launch: per-step scalars, the sigma embeddings of all steps, the first action embedding (k_sample_prep); a host
+    // schedule rides in the kernel arguments (no copy launch in front of it).  It goes FIRST: the three GEMMs of the
+    // conditioning table (M = n_steps rows) depend on nothing else and are queued as side jobs -- they ride in the launches
+    // of the encoder's first small products (rollout batches; at large batches whatever the encoder did not take along is
+    // launched behind it)
+    const View V = decoder_view(m, 0);
+    LAUNCH(mdt_launch_sample_prep(sigmas_dev, sigmas_dev ? nullptr : sigmas, n_steps, m->steps, m->freqs,
+                                  m->cond == COND_TOKEN ? nullptr : m->sig_e, m->D, x_T, m->cfg.sigma_data, m->Wa, m->ba,
+                                  V.y, (int)(batch * m->Ta), m->A, s));
+    mdt_status ms = run_modulation(m, m->steps + 3, 4, n_steps, s, true, !per_step_ctx);  // one row of conditioning vectors per step
+    if (ms == MDT_OK && !per_step_ctx) ms = run_encode(m, tokens, tokens2, goal, modality, honour, batch, nullptr, 0, ctx_out, s);
+    if (ms != MDT_OK) { mdt_gemm_side_drop(); return ms; }
+    LAUNCH(mdt_gemm_side_flush(s));
     for (int i = 0; i < n_steps; ++i) {
         const bool last = i == n_steps - 1;
         if (per_step_ctx)  // the reference leaves the LAST step's context in latent_encoder_emb
             MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, honour, batch, m->steps + 4 * i + 3, 0,
                                last ? ctx_out : nullptr, s));
-        for (int w = 0; w < ways; ++w) {
-            const int64_t nb = b0[w + 1] - b0[w];
-            const View V = decoder_view(m, b0[w]);
-            Stream fin;
-            const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
-            MDT_TRY(run_decoder_blocks(m, V, nb, cond_row(m, i), 0, st[w], head_sums ? &fin : nullptr));
-            const float* xin = (i == 0 ? x_T : m->xbuf) + b0[w] * xs;
-            float* xout = (last ? out : m->xbuf) + b0[w] * xs;
-            mdt_head_args h = head_args(m, V.y, nb, xin, m->steps + 4 * i + 3, 0, xout, MDT_HEAD_DDIM);
-            if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
-            h.step = m->steps + 4 * i;
-            if (!last) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
-            MDT_TRY(run_head(m, h, V.hid, m->steps + 4 * (i + 1) + 3, st[w]));
-        }
-    }
-    for (int w = 1; w < ways; ++w) {
-        HIP_TRY(hipEventRecord(m->ev_join[w - 1], st[w]));
-        HIP_TRY(hipStreamWaitEvent(s, m->ev_join[w - 1], 0));
+        Stream fin;
+        const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
+        MDT_TRY(run_decoder_blocks(m, V, batch, cond_row(m, i), 0, s, head_sums ? &fin : nullptr));
+        mdt_head_args h = head_args(m, V.y, batch, i == 0 ? x_T : m->xbuf, m->steps + 4 * i + 3, 0, last ? out : m->xbuf,
+                                    MDT_HEAD_DDIM);
+        if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
+        h.step = m->steps + 4 * i;
+        if (!last) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
+        MDT_TRY(run_head(m, h, V.hid, m->steps + 4 * (i + 1) + 3, s));
     }
     return MDT_OK;
 }

@@ -108,13 +108,8 @@ struct mdt_model {
     float *h_enc, *qkv, *att, *hid, *ctx, *kvx, *y, *qx, *sig_e, *sig_t, *sig_c, *mod, *xbuf, *noised, *Fbuf, *steps, *sigs, *loss_part;
     float* cmod = nullptr;  // COND_NOISE: rows of [c | ones(D)], read as (shift, scale) by the LayerNorm prologue
     int64_t cached_batch = 0;  // batch of the context currently cached by mdt_encode (0 = none)
-    // sampler pipelining: the batch is cut into `ways` sample-aligned slices whose launch chains run on separate
-    // HIP streams, so one slice's prologue / epilogue / launch gaps overlap another slice's MFMA main loops
-    int ways = 1;
     // collapsed cross-attention (k_xattn_fold / k_xattn_apply): folded projections per sample and decoder block
     bool xfold = false;
     float *xU = nullptr, *xW = nullptr, *xc = nullptr;  // [Ld][cap][4 H * D] weight images (fragment order), same, [Ld][cap][4 H]
-    hipStream_t aux[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
 };
 

@@ -20,26 +20,9 @@
 // XCD-aware block id: the dispatcher places block b on XCD b % 8 (speed-only assumption); give every XCD a
 // contiguous range of logical tiles so the row tiles it touches stay in its private L2.  Bijective for any n.
 __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
-#ifdef MDT_NO_XCD_REMAP  // A/B build: dispatch order = logical order (a row tile's column tiles land on different XCDs)
-    return bid;
-#endif
     const int q = nblocks >> 3, r = nblocks & 7, xcd = bid & 7, idx = bid >> 3;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
-
-// the per-sample folded cross-attention matrices (98 KB per sample and block) are read once per launch by one workgroup,
-// but again at each of the 10 steps: plain loads (measured: non-temporal loads, -DMDT_NT_STREAM, cost 1.5 % at B = 256)
-#ifdef MDT_NT_STREAM
-#define MDT_LD_STREAM(p) __builtin_nontemporal_load((const f32x4*)(p))
-#else
-#define MDT_LD_STREAM(p) ldg4(p)
-#endif
-
-#ifdef MDT_NO_SAMPLE_REMAP  // A/B build: per-sample kernels keep sample b on XCD b % 8
-#define MDT_SAMPLE_REMAP(bid, n) (bid)
-#else
-#define MDT_SAMPLE_REMAP(bid, n) xcd_remap(bid, n)
-#endif
 
 // ---- activation loader ----
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
@@ -75,16 +58,7 @@ struct ActLd<true> {
 // against 17.7 per buffer_load_dwordx4 ... offen (17.3 with no address register at all: what is left is the data's way into the
 // registers), i.e. 113 -> 101 us for the k-loop of the fused MLP's first product alone.  (Round 3 measured buffer loads 7 %
 // SLOWER in mlp_tile: that form kept the tile base in the scalar offset behind a v_readfirstlane per request.)
-// -DMDT_W_GLOBAL: A/B build with the 64-bit global loads.  Offsets are bytes: an image (and every batched slice of one,
-// mdt_gemm_args.bs_w) stays below 4 GiB.
-#ifdef MDT_W_GLOBAL
-struct WStream {
-    const float* p;
-    __device__ __forceinline__ WStream operator+(int floats) const { return WStream{p + floats}; }
-};
-__device__ __forceinline__ WStream wstream(const float* image, int64_t float_off) { return WStream{image + float_off}; }
-__device__ __forceinline__ f32x4 wld4(const WStream& w) { return ldg4(w.p); }
-#else
+// Offsets are bytes: an image (and every batched slice of one, mdt_gemm_args.bs_w) stays below 4 GiB.
 struct WStream {
     __amdgpu_buffer_rsrc_t rs;
     unsigned off;  // bytes
@@ -96,7 +70,6 @@ __device__ __forceinline__ WStream wstream(const float* image, int64_t float_off
 __device__ __forceinline__ f32x4 wld4(const WStream& w) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w.rs, w.off, 0, 0));
 }
-#endif
 
 // prologue kinds: plain copy | LayerNorm | LayerNorm + modulate with ONE broadcast row (sampler: one sigma per
 // step) | LayerNorm + modulate with a per-sample row (GCDenoiser.forward / loss with per-sample sigma)
@@ -115,15 +88,9 @@ struct mdt_attn_pro {
 // end-of-kernel write-back (a launch that leaves B dirty bytes pays B / 6 TB/s at its boundary: 2 us behind the 11.8 MB of a
 // fused MLP's slabs or of q | k | v; with one tile per CU nothing else hides it).  With three fat launches per block it pays
 // 1.9 % per sampler call at B = 256 (round 1, six thin launches: +1 %, inside the noise; B = 1024, the training step and the
-// MGF head do not care: several tiles per CU hide the write-back).  -DMDT_ST_PLAIN: A/B build (plain stores).
+// MGF head do not care: several tiles per CU hide the write-back).
 __device__ __forceinline__ void st4(float* p, f32x4 v) {
-#if defined(MDT_ST_PLAIN)
-    *(f32x4*)p = v;
-#elif defined(MDT_ST_NT)
-    __builtin_nontemporal_store(v, (f32x4*)p);
-#else
     asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-#endif
 }
 __device__ __forceinline__ f32x4 sel4(bool c, f32x4 a, f32x4 b) { return c ? a : b; }
 __device__ __forceinline__ float hsum4(f32x4 v) { return (v.x + v.y) + (v.z + v.w); }
@@ -162,43 +129,18 @@ __device__ unsigned long long* g_dbg_ts = nullptr;
 
 // The enclosing kernel says with KSTEP_PRIO whether a k-step's MFMA block runs at raised issue priority: it pays where
 // loader waves share the SIMDs with the MFMA waves (k_gemm_pipe: mlp.c_proj 37.6 -> 36.1 us) and costs 1-3 % where
-// every wave does both (k_gemm).  -DMDT_NO_KSTEP_PRIO switches it off for A/B runs.
-#ifdef MDT_NO_KSTEP_PRIO
-#define MDT_PRIO(x)
-#else
+// every wave does both (k_gemm).
 #define MDT_PRIO(x) if constexpr (KSTEP_PRIO) __builtin_amdgcn_s_setprio(x);
-#endif
-#ifndef MDT_RING_ADD
-#define MDT_RING_ADD 0  // tuning builds: deeper weight-fragment rings (tools/gpu_ring_ab.sh)
-#endif
 // The prefetches of a k-step are written at its top and must be ISSUED there: left alone, the machine scheduler sinks the
 // loads of one ring slot out of three down to their first use (one exposed L2 round trip per three k-steps in every GEMM
 // loop of this file).  A scheduling barrier that only scalar / vector ALU instructions may cross pins memory instructions
-// and MFMAs to the k-step they were written in.  -DMDT_NO_SCHED_PIN: A/B build.
-#ifdef MDT_NO_SCHED_PIN
-#define MDT_SCHED_PIN
-#else
+// and MFMAs to the k-step they were written in.
 #define MDT_SCHED_PIN __builtin_amdgcn_sched_barrier(0x6);
-#endif
-// timing experiments only (WRONG results; tools/gpu_alone.sh, profiles/r03_mlp_alone_probe.txt): k-steps without their weight
-// loads (-DMDT_EXP_NOLOAD) / without their LDS reads (-DMDT_EXP_NOLDS)
-#ifdef MDT_EXP_NOLOAD
-#define MDT_EXP_LDG(p, old) (old)
-#else
-#define MDT_EXP_LDG(p, old) wld4(p)
-#endif
-#ifdef MDT_EXP_NOLDS
-#define MDT_EXP_LDS(x, old) (old)
-#else
-#define MDT_EXP_LDS(x, old) (x)
-#endif
 // one k-step of the MFMA main loop (uses the enclosing kernel's ring / wp / ap / stride / acc / kg / K16): prefetch the fragment R-1 steps ahead (clamped, never branches), then 4 MFMAs per tile pair
-#ifndef MDT_KSTEP_SPREAD
 #define MDT_KSTEP(U, KC)                                                                                  \
     {                                                                                                     \
         const int kpf = min(kg + (KC) + R - 1, K16 - 1);                                                  \
-        _Pragma("unroll") for (int j = 0; j < NTW; ++j) ring[((U) + R - 1) % R][j] =                      \
-            MDT_EXP_LDG(wp[j] + kpf * 256, ring[((U) + R - 1) % R][j]);                                   \
+        _Pragma("unroll") for (int j = 0; j < NTW; ++j) ring[((U) + R - 1) % R][j] = wld4(wp[j] + kpf * 256); \
         MDT_SCHED_PIN                                                                                     \
         MDT_PRIO(1)                                                                                       \
         MDT_KSTEP_MFMAS(U, 0)                                                                             \
@@ -206,7 +148,7 @@ __device__ unsigned long long* g_dbg_ts = nullptr;
         f32x4 avn[MTILES]; /* activation fragments of the NEXT k-step, requested behind the first quarter of the MFMAs: \
                               whatever LDS wait the compiler puts at the top of a step then finds them long landed */ \
         _Pragma("unroll") for (int i = 0; i < MTILES; ++i) avn[i] =                                       \
-            MDT_EXP_LDS(*(const f32x4*)(ap + i * 16 * stride + min((KC) + 1, nk - 1) * 16), av[i]);       \
+            *(const f32x4*)(ap + i * 16 * stride + min((KC) + 1, nk - 1) * 16);                           \
         MDT_SCHED_PIN                                                                                     \
         MDT_KSTEP_MFMAS(U, 1)                                                                             \
         MDT_KSTEP_MFMAS(U, 2)                                                                             \
@@ -215,40 +157,6 @@ __device__ unsigned long long* g_dbg_ts = nullptr;
         MDT_SCHED_PIN                                                                                     \
         _Pragma("unroll") for (int i = 0; i < MTILES; ++i) av[i] = avn[i];                                \
     }
-#else
-/* A/B form: the step's NTW fragment requests are SPREAD over the step, one in front of each quarter of its MFMAs, instead of
-   going out back to back at its top (tools/micro/wstream_probe.hip: 8 waves x 4 requests in one burst queue at the CU's one
-   address path and keep the issuing waves from their MFMAs: 117 -> 109 us for k_mlp's first product alone) */
-#define MDT_KSTEP_LD1(U, J)                                                                               \
-    if constexpr ((J) < NTW) {                                                                            \
-        ring[((U) + R - 1) % R][(J) < NTW ? (J) : 0] =                                                    \
-            MDT_EXP_LDG(wp[(J) < NTW ? (J) : 0] + kpf * 256, ring[((U) + R - 1) % R][(J) < NTW ? (J) : 0]); \
-        MDT_SCHED_PIN                                                                                     \
-    }
-#define MDT_KSTEP(U, KC)                                                                                  \
-    {                                                                                                     \
-        const int kpf = min(kg + (KC) + R - 1, K16 - 1);                                                  \
-        MDT_KSTEP_LD1(U, 0)                                                                               \
-        MDT_PRIO(1)                                                                                       \
-        MDT_KSTEP_MFMAS(U, 0)                                                                             \
-        MDT_SCHED_PIN                                                                                     \
-        f32x4 avn[MTILES];                                                                                \
-        _Pragma("unroll") for (int i = 0; i < MTILES; ++i) avn[i] =                                       \
-            MDT_EXP_LDS(*(const f32x4*)(ap + i * 16 * stride + min((KC) + 1, nk - 1) * 16), av[i]);       \
-        MDT_SCHED_PIN                                                                                     \
-        MDT_KSTEP_LD1(U, 1)                                                                               \
-        MDT_KSTEP_MFMAS(U, 1)                                                                             \
-        MDT_SCHED_PIN                                                                                     \
-        MDT_KSTEP_LD1(U, 2)                                                                               \
-        MDT_KSTEP_MFMAS(U, 2)                                                                             \
-        MDT_SCHED_PIN                                                                                     \
-        MDT_KSTEP_LD1(U, 3)                                                                               \
-        MDT_KSTEP_MFMAS(U, 3)                                                                             \
-        MDT_PRIO(0)                                                                                       \
-        MDT_SCHED_PIN                                                                                     \
-        _Pragma("unroll") for (int i = 0; i < MTILES; ++i) av[i] = avn[i];                                \
-    }
-#endif
 #define MDT_KSTEP_MFMAS(U, E)                                                                             \
     _Pragma("unroll") for (int i = 0; i < MTILES; ++i) {                                                  \
         _Pragma("unroll") for (int j = 0; j < NTW; ++j) acc[i][j] =                                       \
@@ -375,9 +283,7 @@ __device__ __forceinline__ void gemm_stage_tile(const mdt_gemm_args& a, float* l
                 red[r] += hsum4(v[r][p]);
             }
         }
-#ifndef MDT_EXP_NOLN   // timing experiment only (WRONG results): the prologue without its two wave reductions
         wave_sum_n<RPW>(red);
-#endif
 #pragma unroll
         for (int r = 0; r < RPW; ++r) {
             const float mean = red[r] * inv_k;
@@ -388,9 +294,7 @@ __device__ __forceinline__ void gemm_stage_tile(const mdt_gemm_args& a, float* l
                 red[r] += hsq4(v[r][p]);
             }
         }
-#ifndef MDT_EXP_NOLN
         wave_sum_n<RPW>(red);
-#endif
 #pragma unroll
         for (int r = 0; r < RPW; ++r) {
             const int m = m0 + r0 + r;
@@ -601,9 +505,6 @@ __device__ __forceinline__ void attn_sample_tile(const mdt_attn_pro& ap, float* 
         }
     }
     __syncthreads();
-#ifdef MDT_TS_ROWS_LANDED
-    MDT_TS(7)
-#endif
     // ---- wave h = head h, both products on the MFMA pipe (round 5; rounds 3-4: thread = (head, row, quarter of the head
     //      dimension), ~60 LDS reads and ~250 FMAs per thread with 6 of the 16 row slots idle: 4 k of the kernel's 42 k clocks).
     //      Scores with TRANSPOSED operand roles: A = the head's key rows, B = its query rows -> the lane ends with
@@ -682,7 +583,7 @@ __device__ __forceinline__ void gemm_tile(const mdt_gemm_args& a, int kchunk, in
     constexpr bool KSTEP_PRIO = false;
     // weight-fragment ring: R-1 k-steps of 1-KiB loads in flight per column tile.  A k-step is only 8 MFMAs
     // (256 pipe cycles) with one column tile per wave, so the narrow variants need the deeper ring to cover L2 latency.
-    constexpr int R = (NTW == 1 ? 6 : (NTW == 2 ? 4 : 3)) + MDT_RING_ADD;
+    constexpr int R = NTW == 1 ? 6 : (NTW == 2 ? 4 : 3);
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int lane = tid & 63, wave = tid >> 6;
     const int m0 = by * MT;
@@ -843,11 +744,8 @@ __device__ __forceinline__ void gemm_tile(const mdt_gemm_args& a, int kchunk, in
                     v = apply_act(v, a.act);
                 }
                 if constexpr (RES) v = res_v[i][j] + (gated ? gate_v[i][j] * v : v);
-#if defined(MDT_GEMM_OUT_PLAIN)   // A/B build: the GEMM's output tile stays in the XCD's L2 (plain store) for a same-XCD reader -- round 4: 4.50 vs 4.445 ms per B = 256 call, write-through stays
-                if (ok) *(f32x4*)(a.out + ooff[i] + ncol[j]) = v;
-#else
+                // write-through even for a same-XCD reader (round 4, plain store: 4.50 vs 4.445 ms per B = 256 call)
                 if (ok) st4(a.out + ooff[i] + ncol[j], v);
-#endif
             }
         }
     }
@@ -907,11 +805,7 @@ __device__ __forceinline__ void mlp_tile(const mdt_gemm_args& f, const mdt_gemm_
     MDT_TS_HWID()
     constexpr int MTILES = 2, NWAVES = 8, MT = 32, HS = 512, HSTR = HS + 4, NTW1 = 4;
     constexpr bool KSTEP_PRIO = false;
-#ifdef MDT_MLP_RING  // tuning builds: depth of both weight-fragment rings
-    constexpr int R1 = MDT_MLP_RING, R2 = MDT_MLP_RING;
-#else
     constexpr int R1 = 3, R2 = NTW2 == 1 ? 6 : (NTW2 == 2 ? 4 : 3);
-#endif
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int lane = tid & 63, wave = tid >> 6;
     const int m0 = by * MT;
@@ -1114,12 +1008,8 @@ __device__ __forceinline__ void gemm_smallm_tile(const mdt_gemm_args& a, int n_t
     const float* wbase = a.Wp + (int64_t)n_tile * K16 * 256 + lane * 4;
     // rollout batches (at most two samples' rows): the wave's first round of weight fragments is requested in front of the row
     // statistics (round 5: B = 1 1.295 -> 1.286 ms, B = 2 1.339 -> 1.331; from B = 8 on it LOSES 1 %, the fragments of sixteen row
-    // tiles' workgroups then queue in front of each other's rows).  -DMDT_SMALLM_WF_LATE: A/B build
-#ifdef MDT_SMALLM_WF_LATE
-    const bool WF_EARLY = false;
-#else
+    // tiles' workgroups then queue in front of each other's rows)
     const bool WF_EARLY = a.M <= 24;
-#endif
     f32x4 wf0[4];
     if (a.ln) {  // row statistics: 32 threads per row, whole row in registers (K <= 512)
         const int r = tid >> 5, l32 = tid & 31;
@@ -1682,7 +1572,8 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
 // there); the new rows still go to a.y.
 // ------------------------------------------------------------------------------------------------
 // the sample's operands that do not depend on its rows, in two groups: the fragments of its folded matrices (cold: 98 KB
-// that another workgroup used one step ago) and the shared vectors.  attn_xattn_tile requests the first group at ITS entry, a
+// that another workgroup used one step ago; read once per launch, but again at each of the 10 steps: plain loads, non-temporal
+// ones measured 1.5 % slower at B = 256) and the shared vectors.  attn_xattn_tile requests the first group at ITS entry, a
 // whole attention + projection ahead of their use, and the second before the projection's epilogue; xattn_tile consumes them.
 // DMAX: compile-time bound of D (sizes the register arrays).
 template <int NPP, int DMAX = 512>
@@ -1704,7 +1595,7 @@ __device__ __forceinline__ void xattn_request_u(const mdt_xapply_args& a, int b,
     const int ntu = wave % NTU, ks = wave / NTU;
 #pragma unroll
     for (int kk = 0; kk < KLMAX; ++kk)
-        q.u[kk] = MDT_LD_STREAM(Ub + ((int64_t)(ntu * K16 + min(ks * KL + kk, K16 - 1)) * 64 + lane) * 4);
+        q.u[kk] = ldg4(Ub + ((int64_t)(ntu * K16 + min(ks * KL + kk, K16 - 1)) * 64 + lane) * 4);
     q.cb = ldg4(a.c + (int64_t)b * NPP + 4 * min(tid >> 4, NPP / 4 - 1));   // softmax thread (t, h) = (tid % 16, tid / 16)
 }
 template <int NPP, int DMAX, int DX = 0>
@@ -1717,7 +1608,7 @@ __device__ __forceinline__ void xattn_request_wf(const mdt_xapply_args& a, int b
     for (int j = 0; j < NTWMAX; ++j)
 #pragma unroll
         for (int kc = 0; kc < KP16; ++kc)
-            q.wf[j][kc] = MDT_LD_STREAM(Wb + ((int64_t)(min(wave * NTW + min(j, NTW - 1), N16 - 1) * KP16 + kc) * 64 + lane) * 4);
+            q.wf[j][kc] = ldg4(Wb + ((int64_t)(min(wave * NTW + min(j, NTW - 1), N16 - 1) * KP16 + kc) * 64 + lane) * 4);
 }
 template <int NPP, int DMAX, int DX = 0>
 __device__ __forceinline__ void xattn_request_vec(const mdt_xapply_args& a, const float* __restrict__ zeros, int tid,

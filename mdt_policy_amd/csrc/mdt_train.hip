@@ -455,15 +455,9 @@ static void ln_cond(mdt_ln_train_args& l, const float* mod, int64_t modw, int sh
     l.mod = mod; l.mod_stride = modw; l.shift_off = sh; l.scale_off = sc; l.rows_per_sample = T;
 }
 
-// MDT_HIP_TRAIN_FUSE (A/B runs; default 3): bit 0 = every branch merge of the forward in one launch with the LayerNorm that
-// reads its result (k_merge_ln_fwd4), bit 1 = every LayerNorm backward in one launch with the merge backward behind it
-// (k_ln_bwd4<true>).  0 restores the separate launches of rounds 1-5; both forms give the same bits except the gate gradient's
-// summation order over a sample's rows.
-static int train_fuse() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MDT_HIP_TRAIN_FUSE"); v = e ? atoi(e) : 3; }
-    return v;
-}
+// Every branch merge of the forward runs in one launch with the LayerNorm that reads its result (k_merge_ln_fwd4), every
+// LayerNorm backward in one launch with the merge backward behind it (k_ln_bwd4<true>).  Against the separate launches of
+// rounds 1-5 both give the same bits except the gate gradient's summation order over a sample's rows.
 
 // the first LayerNorm of a block (ln_1 on its input, conditioned as the block is)
 static mdt_ln_train_args block_ln1_args(mdt_model* m, const EncBlock& e, BlockTape& t, int64_t B, int T, int cond, const float* mod,
@@ -472,14 +466,6 @@ static mdt_ln_train_args block_ln1_args(mdt_model* m, const EncBlock& e, BlockTa
     mdt_ln_train_args l1 = ln_args(t.x_in, e.ln1_w, e.ln1_b, t.h1, t.st1, (int)(B * T), m->D);
     ln_cond(l1, mod, modw, c.sh1, c.sc1, T);
     return l1;
-}
-
-// merge g, then LayerNorm l on its result: one launch or two (train_fuse)
-static mdt_status merge_then_ln(const mdt_merge_args& g, const mdt_ln_train_args& l, hipStream_t s) {
-    if (train_fuse() & 1) { LAUNCH(mdt_launch_merge_ln_fwd(g, l, s)); return MDT_OK; }
-    LAUNCH(mdt_launch_merge_fwd(g, s));
-    LAUNCH(mdt_launch_ln_fwd_train(l, s));
-    return MDT_OK;
 }
 
 // one block forward; mod == nullptr: plain Block, else conditioned by the rows of `mod` (stride modw) as `cond` lays
@@ -507,16 +493,16 @@ static mdt_status block_fwd(mdt_model* m, const EncBlock& e, const DecBlock* d, 
         if (half != 2) {
             mdt_ln_train_args l3 = ln_args(t.x1, d->ln3_w, d->ln3_b, t.h3, t.st3, M, D);
             ln_cond(l3, mod, modw, c.sh3, -1, T);
-            MDT_TRY(merge_then_ln(g1, l3, s));
+            LAUNCH(mdt_launch_merge_ln_fwd(g1, l3, s));
             LAUNCH(mdt_launch_gemm(gemm_args(t.h3, D, d->xq, t.q, D, M), s));
         }
         if (half == 1) return MDT_OK;
         // SDPA is_causal on a Ta x Te matrix: top-left aligned (transformer_blocks.py:204,142)
         MDT_TRY(attn_fwd(m, t.q, D, kv, kv + D, (int64_t)m->Ld * 2 * D, t.att2, B, T, m->Te, true, dr, site_id(blk, SITE_XATTN), s));
         LAUNCH(mdt_launch_gemm(gemm_args(t.att2, D, d->xproj, t.a2, D, M), s));
-        MDT_TRY(merge_then_ln(merge_args(t.x1, t.a2, nullptr, 0, t.x2, B, T, D, dr.resid_p, site_id(blk, SITE_XRESID), dr.seed), l2, s));
+        LAUNCH(mdt_launch_merge_ln_fwd(merge_args(t.x1, t.a2, nullptr, 0, t.x2, B, T, D, dr.resid_p, site_id(blk, SITE_XRESID), dr.seed), l2, s));
     } else {
-        MDT_TRY(merge_then_ln(g1, l2, s));  // t.x2 == t.x1 in an encoder block
+        LAUNCH(mdt_launch_merge_ln_fwd(g1, l2, s));  // t.x2 == t.x1 in an encoder block
     }
     {   // c_fc and its GELU in one launch: the epilogue leaves the pre-activation u (the backward's operand) beside gelu(u)
         mdt_gemm_args g = gemm_args(t.h2, D, e.fc, t.hid, 4 * D, M);
@@ -526,7 +512,7 @@ static mdt_status block_fwd(mdt_model* m, const EncBlock& e, const DecBlock* d, 
     LAUNCH(mdt_launch_gemm(gemm_args(t.hid, 4 * D, e.proj2, t.mo, D, M), s));
     const mdt_merge_args g2 = merge_args(t.x2, t.mo, c.g2 >= 0 ? mod + c.g2 : nullptr, modw, t.x3, B, T, D, dr.mlp_p,
                                          site_id(blk, SITE_MLP), dr.seed);
-    if (tail_ln) MDT_TRY(merge_then_ln(g2, *tail_ln, s));
+    if (tail_ln) LAUNCH(mdt_launch_merge_ln_fwd(g2, *tail_ln, s));
     else LAUNCH(mdt_launch_merge_fwd(g2, s));
     return MDT_OK;
 }
@@ -770,15 +756,9 @@ extern "C" mdt_status mdt_train_loss_fwd(mdt_model* m, const float* tokens, cons
 // side stream q of the handle (created on first use)
 static mdt_status side_stream(mdt_train_state* ts, int q, hipStream_t* out) {
     if (!ts->side[q]) {
-        // MDT_HIP_DW_PRIO (A/B runs): 0 = default priority, 1 = the LOWEST the device offers (the chain's kernels first, the
-        // weight gradients in what is left: measured 9.17 against 9.08 ms), 2 = the highest (9.08)
-        static int prio = -1;
-        if (prio < 0) { const char* e = getenv("MDT_HIP_DW_PRIO"); prio = e ? atoi(e) : 0; }
-        int least = 0, greatest = 0;
-        if (prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
-            HIP_TRY(hipStreamCreateWithPriority(&ts->side[q], hipStreamNonBlocking, prio == 1 ? least : greatest));
-        else
-            HIP_TRY(hipStreamCreateWithFlags(&ts->side[q], hipStreamNonBlocking));
+        // default priority (measured: the LOWEST the device offers -- the chain's kernels first, the weight gradients in what is
+        // left -- 9.17 against 9.08 ms; the highest 9.08)
+        HIP_TRY(hipStreamCreateWithFlags(&ts->side[q], hipStreamNonBlocking));
     }
     *out = ts->side[q];
     return MDT_OK;
@@ -850,7 +830,7 @@ static float* grad_of(mdt_model* m, float* grads, const float* param) {
 
 // LayerNorm backward + reduction of the per-sample weight/bias partials into the gradient slots
 // mg: the backward of the branch merge that follows in the backward order, on the gradient this call leaves in dx (its
-// `x`): rides in the same launch (train_fuse bit 1) or runs behind it
+// `x`): rides in the same launch
 static mdt_status ln_bwd(mdt_model* m, float* grads, const float* x, const float* stats, const float* w, const float* b,
                          const float* mod, int64_t modw, int shift_off, int scale_off, const float* dh, float* dx, int acc,
                          float* d_mod, int64_t B, int T, hipStream_t s, int acc_dmod = 0, const mdt_merge_args* mg = nullptr) {
@@ -867,12 +847,8 @@ static mdt_status ln_bwd(mdt_model* m, float* grads, const float* x, const float
     const bool deferred = pw && (!b || pb);
     a.pw = deferred ? pw : ts->pw; a.pb = b ? (deferred ? pb : ts->pb) : nullptr;
     a.B = (int)B; a.rows_per_sample = T; a.D = m->D;
-    if (mg && (train_fuse() & 2)) {
-        LAUNCH(mdt_launch_ln_bwd_merge(a, *mg, s));
-    } else {
-        LAUNCH(mdt_launch_ln_bwd(a, s));
-        if (mg) LAUNCH(mdt_launch_merge_bwd(*mg, s));
-    }
+    if (mg) LAUNCH(mdt_launch_ln_bwd_merge(a, *mg, s));
+    else LAUNCH(mdt_launch_ln_bwd(a, s));
     if (!grads) return MDT_OK;
     if (deferred) {
         ts->deferred.push_back(mdt_colsum_entry{pw, grad_of(m, grads, w), (int64_t)m->D, (int)B, m->D, 1});

@@ -523,11 +523,9 @@ __global__ __launch_bounds__(256) void k_ln_bwd4(mdt_ln_bwd_args a, mdt_merge_ar
 
 template <bool MG>
 static void launch_ln_bwd4(const mdt_ln_bwd_args& a, const mdt_merge_args& g, int chunks, hipStream_t s) {
-    static int rb_force = -1;  // MDT_HIP_LNB_ROWS=1..3: rows a wave keeps in flight (A/B runs; default: all of them, up to 3)
-    if (rb_force < 0) { const char* e = getenv("MDT_HIP_LNB_ROWS"); rb_force = e ? atoi(e) : 0; }
+    // rows a wave keeps in flight: all of them, up to 3
     const int per = (a.rows_per_sample + chunks - 1) / chunks;
-    int rb = per <= 4 ? 1 : (per <= 8 ? 2 : 3);
-    if (rb_force >= 1 && rb_force <= 3) rb = rb_force;
+    const int rb = per <= 4 ? 1 : (per <= 8 ? 2 : 3);
     const size_t lds = (size_t)4 * (MG ? 5 : 4) * a.D * sizeof(float);
     if (rb == 1) hipLaunchKernelGGL((k_ln_bwd4<MG, 1>), dim3(a.B, chunks), dim3(256), lds, s, a, g);
     else if (rb == 2) hipLaunchKernelGGL((k_ln_bwd4<MG, 2>), dim3(a.B, chunks), dim3(256), lds, s, a, g);
@@ -1207,11 +1205,9 @@ __global__ __launch_bounds__(64 * HG) void k_attn_bwd_mfma(mdt_attn_bwd_args a, 
     }
 }
 
-// which (hd, H) the MFMA kernels take, and MDT_HIP_ATTN_TRAIN_MFMA=0 (A/B runs: the one-wave-per-head kernels everywhere)
+// which (hd, H) the MFMA kernels take (the others: the one-wave-per-head kernels)
 static int attn_train_mfma_group(int hd, int H, int rope) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("MDT_HIP_ATTN_TRAIN_MFMA"); on = e ? atoi(e) : 1; }
-    if (!on || rope || (hd != 16 && hd != 32 && hd != 48 && hd != 64)) return 0;
+    if (rope || (hd != 16 && hd != 32 && hd != 48 && hd != 64)) return 0;
     return H % 4 == 0 ? 4 : (H % 2 == 0 ? 2 : 1);
 }
 template <int HD, int HG>
@@ -1940,7 +1936,7 @@ __global__ __launch_bounds__(256 * WN) void k_gemm_tn(const float* __restrict__ 
     // launched -- tile fastest -- XCD x got k-tile x of EVERY slice: each of the 8 L2s pulled all of dY and an eighth of X's
     // columns over all rows (k_gemm_tn<3, 3> at 10240 x 384 x 1536: 113 MB from the fabric for 79 MB of operands, L2 hit 0.30).
     // Round 6: every XCD gets a contiguous range of (slice-major) ids, i.e. whole slices -- all tiles that share a slice's rows
-    // of X and dY run behind one L2 (xcd = 0: the launch order, A/B runs).
+    // of X and dY run behind one L2 (xcd = 0, a single slice: the launch order).
     int id = blockIdx.x + gridDim.x * blockIdx.z;
     if (xcd) {
         const int nb = gridDim.x * gridDim.z, q = nb >> 3, r = nb & 7, x8 = id & 7, idx = id >> 3;
@@ -2278,20 +2274,15 @@ hipError_t mdt_launch_gemm_tn_split(const float* dY, int64_t ldy, const float* X
 // (16-byte aligned rows).  bpart: nullptr or (S, N) per-slice column sums of dY.
 // (KT, WN) instantiation behind a shape.  n-tile: 192 wide (12 waves, needs N and K multiples of 192: every Linear of this model)
 // from 8192 reduction rows on for matrices of at least 576 x 192, else 128 wide where N is a multiple of 128, else 64; k-tile:
-// 192 with the 192-wide n-tile, else the one that pads K less.  MDT_HIP_TN_WIDE = 0 / 1 / 2 forces 64 / 128 / 192 where the shape allows (A/B runs).
+// 192 with the 192-wide n-tile, else the one that pads K less.
 void mdt_gemm_tn_tile(int64_t M, int N, int K, int* tn, int* tk) {
-    static int force = -1;
-    if (force < 0) { const char* e = getenv("MDT_HIP_TN_WIDE"); force = e ? atoi(e) + 1 : 0; }
     const bool ok192 = N % 192 == 0 && K % 192 == 0, ok128 = N % 128 == 0;
     // measured, product + sum of its slices (tools/dw_bench.py, us at 64 / 128 / 192): M = 104448: 1536 x 192 712 / 689 / 628,
     // 192 x 768 357 / - / 307, 576 x 192 288 / - / 285, 192 x 192 115 / - / 139;  M = 10240: 1536 x 384 137 / 130 / 130,
     // 384 x 1536 134 / 128 / 128, 1152 x 384 108 / 98 / 108, 384 x 384 51 / 48 / 63;  M = 4096: 64 wide or a tie
     // (192 wide with ONE round of workgroups, split_rows_tn: 1536 x 192 597, 192 x 768 280, 576 x 192 263)
     // M = 10240 with that slicing: 1536 x 384 119, 384 x 1536 118, 1152 x 384 97, 384 x 384 45 -- 192 wide everywhere it fits
-    int w = ok192 && M >= 8192 && (int64_t)N * K >= 576 * 192 ? 192 : (ok128 && M >= 8192 ? 128 : 64);
-    if (force == 1) w = 64;
-    if (force == 2) w = ok128 ? 128 : 64;
-    if (force == 3) w = ok192 ? 192 : (ok128 ? 128 : 64);
+    const int w = ok192 && M >= 8192 && (int64_t)N * K >= 576 * 192 ? 192 : (ok128 && M >= 8192 ? 128 : 64);
     *tn = w;
     *tk = w == 192 ? 192 : mdt_gemm_tn_ktile(K);
 }
@@ -2308,10 +2299,8 @@ static hipError_t launch_gemm_tn_t(const float* dY, int64_t ldy, const float* X,
         if (e != hipSuccess) return e;
         attr_dev[dev] = true;
     }
-    static int xcd = -1;  // MDT_HIP_TN_XCD=0: workgroups take (slice, tile) in launch order (A/B runs)
-    if (xcd < 0) { const char* e = getenv("MDT_HIP_TN_XCD"); xcd = e ? atoi(e) : 1; }
     hipLaunchKernelGGL((k_gemm_tn<KT, WN>), dim3(((N + TN_ - 1) / TN_) * ((K + TK - 1) / TK), 1, S), dim3(256 * WN), lds, s, dY, ldy, X, ldx,
-                       out, slice_stride, M, N, K, L, accumulate, bpart, S > 1 ? xcd : 0);
+                       out, slice_stride, M, N, K, L, accumulate, bpart, S > 1 ? 1 : 0);
     return hipGetLastError();
 }
 hipError_t mdt_launch_gemm_tn(const float* dY, int64_t ldy, const float* X, int64_t ldx, float* out, int64_t slice_stride, int M, int N,
@@ -2327,9 +2316,6 @@ hipError_t mdt_launch_gemm_tn(const float* dY, int64_t ldy, const float* X, int6
 }
 // k-tile width k_gemm_tn uses for a K-column product: the one that pads K less (128 on a tie)
 int mdt_gemm_tn_ktile(int K) {
-    static int force = -1;  // MDT_HIP_TN_KTILE=128|192: A/B runs
-    if (force < 0) { const char* e = getenv("MDT_HIP_TN_KTILE"); force = e ? atoi(e) : 0; }
-    if (force == 128 || force == 192) return force;
     const int p128 = (K + 127) / 128 * 128, p192 = (K + 191) / 192 * 192;
     return p192 < p128 ? 192 : 128;
 }

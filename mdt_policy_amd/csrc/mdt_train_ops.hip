@@ -21,23 +21,15 @@
 // fills the chip with WIDE tiles however small N x K is: slice s multiplies its own (N, L) piece of dY^T with its own
 // packed (K, L) piece of X^T in ONE batched launch (grid.z = S), and the S partial (N, K) products are summed in a
 // fixed order by a column sum -- deterministic, unlike atomics.  Only worth it for deep reductions.
-static bool no_splitk() {
-    static int v = -1;
-    if (v < 0) v = getenv("MDT_HIP_NO_SPLITK") ? 1 : 0;
-    return v == 1;
-}
 static void split_rows(int64_t M, int64_t N, int64_t K, int* S, int* L) {
     const int64_t tiles = ((N + 31) / 32) * ((K + 127) / 128);   // 32 x 128 tiles of one product
-    static int64_t target = -1, min_depth = -1;  // tuning knobs (A/B runs): workgroups aimed for, least slice depth
-    if (target < 0) { const char* e = getenv("MDT_HIP_SPLIT_TARGET"); target = e ? atoll(e) : 1000; }
-    if (min_depth < 0) { const char* e = getenv("MDT_HIP_SPLIT_DEPTH"); min_depth = e ? atoll(e) : 512; }
-    // measured (tools/gpu_splitk_ab.sh, B = 1024 step): aiming for ~1000 workgroups of >= 512-deep slices instead of 400
+    constexpr int64_t target = 1000, min_depth = 512;  // workgroups aimed for, least slice depth
+    // measured (B = 1024 step): aiming for ~1000 workgroups of >= 512-deep slices instead of 400
     // of >= 1024 is 11 % faster per step (several 4-wave workgroups share a CU); reductions under 4096 rows (B = 128:
     // 1280 rows) were 2.6 % slower when cut in two, so they keep the 1024-row floor
     const int64_t depth = M >= 4096 ? min_depth : std::max<int64_t>(min_depth, 1024);
     int64_t s = std::max<int64_t>(1, std::min<int64_t>((target + tiles - 1) / tiles, M / depth));
     s = std::min<int64_t>(s, 32);
-    if (no_splitk()) s = 1;
     int64_t l = ((M + s - 1) / s + 31) / 32 * 32;                // equal slices: at most 31 pad rows each
     while (l > 16384) { ++s; l = ((M + s - 1) / s + 31) / 32 * 32; }  // keeps the GEMM's K' well inside its limit
     *S = (int)((M + l - 1) / l);
@@ -51,19 +43,16 @@ static void split_rows_tn(int64_t M, int64_t N, int64_t K, int* S, int* L) {
     mdt_gemm_tn_tile(M, (int)N, (int)K, &tn, &tk);
     // in units of 64-column tiles whatever the n-tile: a 128- / 192-wide workgroup counts two / three times (it has as many waves)
     const int64_t tiles = ((N + 63) / 64) * ((K + tk - 1) / tk);
-    static int64_t target = -1;
-    if (target < 0) { const char* e = getenv("MDT_HIP_TN_TARGET"); target = e ? atoll(e) : 512; }  // measured at B = 1024: round 2, everything in one stream: 768 -> 11.27 ms step / 42.1 ms head, 1536 -> 11.18 / 41.4, 2304 -> 11.22 / 41.4; round 6, the weight gradients beside the chain on a side stream: 1536 -> 9.34, 768 -> 9.25, 512 -> 9.23 (fewer, deeper slices: less partial-sum traffic beside the chain)
+    constexpr int64_t target = 512;  // measured at B = 1024: round 2, everything in one stream: 768 -> 11.27 ms step / 42.1 ms head, 1536 -> 11.18 / 41.4, 2304 -> 11.22 / 41.4; round 6, the weight gradients beside the chain on a side stream: 1536 -> 9.34, 768 -> 9.25, 512 -> 9.23 (fewer, deeper slices: less partial-sum traffic beside the chain)
     int64_t s = std::max<int64_t>(1, std::min<int64_t>((target + tiles - 1) / tiles, M / 128));
     if (tn == 192) {
         // twelve-wave workgroups, one per CU: ONE round of them (tools/dw_bench.py at M = 104448, us at 32 / 64 / 128 slices:
         // 1536 x 192 (8 tiles) 597 / 624 / 616, 192 x 768 (4) 495 / 280 / 302, 576 x 192 (3) 483 / 263 / 281)
         const int64_t tiles192 = (N / 192) * (K / 192);
-        static int64_t round = -1;  // MDT_HIP_TN_ROUND: workgroups aimed for (A/B runs; beside the backward chain fewer may pay)
-        if (round < 0) { const char* e = getenv("MDT_HIP_TN_ROUND"); round = e ? atoll(e) : 256; if (round < 1 || round > 256) round = 256; }
+        constexpr int64_t round = 256;  // workgroups aimed for
         s = std::max<int64_t>(1, std::min<int64_t>((round + tiles192 / 2) / tiles192, M / 128));
     }
-    static int64_t cap = -1;
-    if (cap < 0) { const char* e = getenv("MDT_HIP_TN_SLICES"); cap = e ? atoll(e) : 128; }  // measured: masked-image head 37.7 ms (64) -> 37.2 (128) = (192, 256); denoiser step unchanged
+    constexpr int64_t cap = 128;  // measured: masked-image head 37.7 ms (64) -> 37.2 (128) = (192, 256); denoiser step unchanged
     s = std::min<int64_t>(s, cap);
     if (tn != 192) {
         // whole rounds of workgroups here too where that is within a factor 1.5 of the above (192 x 192 at M = 104448, three
@@ -74,7 +63,6 @@ static void split_rows_tn(int64_t M, int64_t N, int64_t K, int* S, int* L) {
         const int64_t s2 = std::min<int64_t>((rounds * slots) / tiles_wg, M / 128);
         if (s2 >= 1 && 2 * s2 <= 3 * s && 3 * s2 >= 2 * s) s = s2;
     }
-    if (no_splitk()) s = 1;
     const int64_t l = ((M + s - 1) / s + 31) / 32 * 32;
     *S = (int)((M + l - 1) / l);
     *L = (int)l;
@@ -95,14 +83,12 @@ static int64_t linear_bwd_scratch_exact(int64_t M, int64_t N, int64_t K) {
 // slices than the capacity batch), so the exact figure at M is not enough.  Closed-form bounds of both paths:
 //   k_gemm_tn: S <= M / 128 always; S <= 3/2 x min(ceil(target / tiles), cap) for the 64- / 128-wide tiles (`tiles` counted with
 //              the k-tile that gives fewer of them), S <= (256 + t / 2) / t one-round slices for the 192-wide one;
-//   transposed-copy path (MDT_HIP_DW_TN=0 or odd shapes): its slice count s only grows with M and Mp = S L <= M + 32 s.
+//   transposed-copy path (odd shapes): its slice count s only grows with M and Mp = S L <= M + 32 s.
 // tests/test_cpu_abi.py sweeps the exact need of every row count below a capacity against this bound.
 int64_t mdt_linear_bwd_scratch(int64_t M, int64_t N, int64_t K) {
     if (M < 1) M = 1;
     // k_gemm_tn
-    static int64_t target = -1, cap = -1;
-    if (target < 0) { const char* e = getenv("MDT_HIP_TN_TARGET"); target = e ? atoll(e) : 1536; }
-    if (cap < 0) { const char* e = getenv("MDT_HIP_TN_SLICES"); cap = e ? atoll(e) : 128; }
+    constexpr int64_t target = 1536, cap = 128;
     const int64_t tiles_min = ((N + 63) / 64) * ((K + 191) / 192);
     int64_t s_tn = (3 * std::min<int64_t>((target + tiles_min - 1) / tiles_min, cap) + 1) / 2;
     if (N % 192 == 0 && K % 192 == 0) {
@@ -129,9 +115,7 @@ mdt_status mdt_linear_bwd(const mdt_linear_bwd_args& a, hipStream_t s, mdt_colsu
     if (a.dbias && !bias_from_partials) LAUNCH(mdt_launch_colsum(a.dY, a.ldy, a.M, a.N, a.dbias, a.accumulate_dw, s));
     // (bias_from_partials: the dW path below also leaves the bias gradient -- per-slice column sums of dY from k_gemm_tn,
     //  or per-32-row partials from the transpose of the older path)
-    static int use_tn = -1;  // MDT_HIP_DW_TN=0: the transposed-copy + packed-copy + forward-GEMM path (A/B runs)
-    if (use_tn < 0) { const char* e = getenv("MDT_HIP_DW_TN"); use_tn = e ? atoi(e) : 1; }
-    if (a.dW && use_tn && !(a.N % 16) && !(a.ldy % 4) && !(a.ldx % 4)) {
+    if (a.dW && !(a.N % 16) && !(a.ldy % 4) && !(a.ldx % 4)) {
         // dW straight from dY and X (k_gemm_tn): S slices of the row reduction as one batched launch, partial products and
         // the bias gradient's per-slice column sums added up in a fixed order afterwards
         int S, L;
@@ -146,8 +130,7 @@ mdt_status mdt_linear_bwd(const mdt_linear_bwd_args& a, hipStream_t s, mdt_colsu
         const bool tn_split = a.M >= 8192 && mdt_gemm_tn_split_on() && 8 * ((a.N + stn - 1) / stn * stn) <= 9 * a.N;
         if (tn_split) {
             const int64_t tiles = ((a.N + stn - 1) / stn) * ((a.K + stk - 1) / stk);
-            int64_t s2 = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(256 / tiles, S), a.M / 256));   // never a second round
-            if (no_splitk()) s2 = 1;
+            const int64_t s2 = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(256 / tiles, S), a.M / 256));   // never a second round
             const int64_t l2 = ((a.M + s2 - 1) / s2 + 31) / 32 * 32;
             S = (int)((a.M + l2 - 1) / l2);
             L = (int)l2;

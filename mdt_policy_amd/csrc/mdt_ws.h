@@ -176,12 +176,10 @@ __device__ __forceinline__ void gemm_ws_tile(const mdt_gemm_args& a, int panel, 
                 for (int j = 0; j < NTW; j += 2) {
                     f32x4 v = acc[i][j] + bias_v[j];
                     const f32x4 g = acc[i][j + 1] + bias_v[j + 1];
-#ifndef MDT_DIAG_WS_NOSTORE_U   // timing experiment only (WRONG results): the product without its 642 MB of u stores
                     if (okr[i]) {
                         *(f32x4*)(up + ncol[j]) = v;
                         *(f32x4*)(up + ncol[j + 1]) = g;
                     }
-#endif
                     v.x *= glu_silu(g.x); v.y *= glu_silu(g.y); v.z *= glu_silu(g.z); v.w *= glu_silu(g.w);
                     if (okr[i]) *(f32x4*)(a.out + oo[i] + ncol[j]) = v;
                 }

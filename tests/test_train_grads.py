@@ -773,7 +773,9 @@ def test_large_batch_sampling_after_optimizer_steps_reads_fresh_split_images():
     state exists, parameter loads do not rewrite those images (every optimizer step would); they are marked stale and re-made from the
     fp32 fragment images by the next call that reads them.  After two optimizer steps a B = 128 sampler call must give the BITS of a
     fresh model that loaded the same weights (whose images come from the raw weights), differ from the fp32 launches' bits (the split
-    form ran) and agree with them to fp32 rounding."""
+    form ran) and agree with them to fp32 rounding.  The same after two more steps at B = 56 (560 decoder rows) with the fused MLP
+    threshold moved below 768 rows (mdt_op_set_mlp_fuse_min): the split launch must not run on rows for which the images are not
+    re-made."""
     from mdt_policy_amd import _lib, configs
     from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
     from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
@@ -815,6 +817,29 @@ def test_large_batch_sampling_after_optimizer_steps_reads_fresh_split_images():
     assert torch.equal(got, want), "sampling after optimizer steps read stale split images"
     assert not torch.equal(want, fp32), "the split launches did not run at B = 128"
     assert_close(want.cpu(), fp32.cpu(), rtol=1e-4, atol=1e-4, what="split against fp32 launches, B = 128 sampler call")
+
+    mid = {k: torch.from_numpy(v).cuda() for k, v in synthetic.sampler_inputs(56, cfg, 4).items()}
+    st_mid = {"state_images": mid["state_images"], "modality": "lang"}
+    L.mdt_op_set_mlp_split(1)
+    L.mdt_op_set_mlp_fuse_min(512)
+    try:
+        model.train()
+        for _ in range(2):
+            opt.zero_grad(set_to_none=True)
+            loss, _ = model.loss({"state_images": tr["state_images"], "modality": "lang"}, li["actions"], tr["goal"], li["noise_train"], li["sigma"])
+            loss.backward()
+            opt.step()
+        model.eval()
+        with torch.no_grad():
+            got = model.sample_ddim(st_mid, mid["noise"] * 80.0, mid["goal"], sig).clone()
+            fresh = GCDenoiser(cfg, 0.5).cuda().eval()
+            fresh.load_state_dict(model.state_dict())
+            want = fresh.sample_ddim(st_mid, mid["noise"] * 80.0, mid["goal"], sig).clone()
+    finally:
+        L.mdt_op_set_mlp_fuse_min(-1)
+        L.mdt_op_set_mlp_split(-1)
+    torch.cuda.synchronize()
+    assert torch.equal(got, want), "sampling at 560 rows with the fused MLP from 512 rows read stale split images"
 
 
 @pytest.mark.gpu

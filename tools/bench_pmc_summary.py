@@ -1,4 +1,7 @@
-"""Per-kernel and whole-run MFMA-busy / HBM-side traffic from the two --pmc passes of tools/gpu_bench_pmc.sh.
+"""Per-kernel and whole-run MFMA-busy / HBM-side traffic from two rocprofv3 --pmc passes.  usage: python tools/bench_pmc_summary.py DIR
+[WHAT [ROWS]].  DIR/p1/, DIR/p2/: two separate `rocprofv3 --kernel-trace --output-format csv --pmc ... -d DIR/pN -- python bench.py
+--steps 3 --warmup 1 --no-cpu-baseline` runs (kernel trace only beside the counters), p1 with SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES
+SQ_WAVE_CYCLES, p2 with TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_HIT_sum TCC_MISS_sum.
 MFMA-busy fraction = (SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs) / (kernel duration x 2.4 GHz): the share of the peak
 MFMA issue slots (the clock behind the 157.3 TFLOP/s figure) the kernel used; durations from the dispatch timestamps
 of the same (profiled) run.  GRBM_GUI_ACTIVE is not used: it is not a per-dispatch cycle count in this rocprofv3."""

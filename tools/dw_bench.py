@@ -1,5 +1,5 @@
 """Weight-gradient products (k_gemm_tn + the sum of its slices) of the training shapes, through mdt_op_linear_bwd with dX = NULL.
-usage: [MDT_HIP_TN_WIDE=0|1] python tools/dw_bench.py"""
+usage: python tools/dw_bench.py"""
 import ctypes as C
 import os
 import sys

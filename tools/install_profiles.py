@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
-"""Copy the summaries of one tools/gpu_final.sh run (gpurun_out/<tag>/) into profiles/r<NN>_*, each with a header naming the
-round, the commit the run was built from and the command.   usage: python tools/install_profiles.py <tag> <round> <commit>"""
+"""Copy the summaries of one end-of-round measurement set (the output directory <tag>) into profiles/r<NN>_*, each with a header naming the
+round, the commit the run was built from and the command.   usage: python tools/install_profiles.py <tag> <round> <commit>
+
+The set: bench.json (the bench line); bench_kernel_stats.txt, lat_*, train_kernel_stats.txt, mae_kernel_stats.txt (tools/prof_summary.py
+tables of rocprofv3 --kernel-trace --stats runs of bench.py, tools/latency.py 1, tools/train_bench.py 1024, tools/mae_bench.py 1024);
+bench_pmc.txt and trainpmc/{train,mae}_pmc.txt (tools/bench_pmc_summary.py over two separate rocprofv3 --kernel-trace --pmc passes
+each); sweep.txt, train_bench.txt, mae_bench.txt (the same tools without the profiler)."""
 import os
 import sys
 
@@ -34,13 +39,13 @@ stats = read("bench_kernel_stats.txt").splitlines(True)
 # in-chain dominant-kernel leg)
 calls = next((l.split("|")[1].strip() for l in stats if "k_xattn_fold" in l), "?")
 write("bench_kernel_stats.txt",
-      head + "rocprofv3 --kernel-trace --stats of 'python bench.py --steps 5 --warmup 2 --no-cpu-baseline' (MI355X, 1 GPU), "
-      f"tools/gpu_final.sh\n# {calls} sampler calls x (encoder + fold + 10 decoder steps) (warm-up, timed, the 50-call spread leg, the "
+      head + "rocprofv3 --kernel-trace --stats of 'python bench.py --steps 5 --warmup 2 --no-cpu-baseline' (MI355X, 1 GPU)\n"
+      f"# {calls} sampler calls x (encoder + fold + 10 decoder steps) (warm-up, timed, the 50-call spread leg, the "
       "traced call) + the 210-launch dominant-kernel-alone leg; bench "
       f"line of the same build and box: profiles/{pre}bench.json\n" + "".join(stats[:32]))
 write("bench_pmc.txt",
-      head + "rocprofv3 --kernel-trace --pmc (two separate passes) of 'python bench.py --steps 3 --warmup 1 --no-cpu-baseline', "
-      "tools/gpu_final.sh\n" + read("bench_pmc.txt"))
+      head + "rocprofv3 --kernel-trace --pmc (two separate passes) of 'python bench.py --steps 3 --warmup 1 --no-cpu-baseline'\n"
+      + read("bench_pmc.txt"))
 lat = read("lat_kernel_stats.txt").splitlines(True)
 write("rollout_b1_kernel_stats.txt",
       head + "rollout batch B = 1: rocprofv3 --kernel-trace --stats of 'python tools/latency.py 1' (sampler calls under the "
@@ -62,13 +67,13 @@ mae = read("mae_kernel_stats.txt").splitlines(True)
 write("mae_kernel_stats.txt",
       head + "masked generative foresight head: rocprofv3 --kernel-trace --stats of 'python tools/mae_bench.py 1024' (forward + "
       "backward, B = 1024), MI355X\n# without the profiler (same box):\n" + read("mae_bench.txt") + "".join(mae[:34]))
-# PMC passes of the training step and of the masked-image head (tools/gpu_train_pmc.sh: MFMA-busy | HBM-side requests + L2 hit)
+# PMC passes of the training step and of the masked-image head (MFMA-busy | HBM-side requests + L2 hit)
 for name, what in (("train", "MDT_TRAIN_BENCH_MODES=train MDT_TRAIN_BENCH_OPT=fused python tools/train_bench.py 1024' (denoiser training step, B = 1024, train mode, FusedAdamW; weight gradients on the side stream"),
                    ("mae", "python tools/mae_bench.py 1024' (masked-image head, forward + backward, B = 1024: 104448 decoder rows")):
     fn = os.path.join("trainpmc", f"{name}_pmc.txt")
     if os.path.exists(os.path.join(src, fn)):
         write(f"{'train_step' if name == 'train' else 'mae'}_pmc.txt",
-              head + f"rocprofv3 --pmc over '{what}), two separate passes with kernel-trace only (tools/gpu_train_pmc.sh):\n"
+              head + f"rocprofv3 --pmc over '{what}), two separate passes with kernel-trace only:\n"
               "# SQ_VALU_MFMA_BUSY_CYCLES | TCC_EA0_RDREQ / WRREQ + TCC_HIT / MISS; HBM-side MB = RDREQ x 128 B / WRREQ x 64 B per launch "
               "(MI355X_MICROARCH.md, gfx950 corrections).  Reading: DESIGN.md section 5a.\n" + read(fn))
 # the dominant kernel's HBM-side traffic per launch, for bench.py's roofline.traffic (PMC counters cannot be read from inside
@@ -87,7 +92,7 @@ for l in read("bench_pmc.txt").splitlines():
             "commit": commit,
             "kernel": f"{f[0]} (LN + modulate -> c_fc -> GELU -> c_proj -> gate, {M} rows, d = {D}, hidden {N}; B = 256)",
             "source": f"rocprofv3 --kernel-trace --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_HIT_sum TCC_MISS_sum of the bench command "
-                      f"itself (own pass, tools/gpu_final.sh; table profiles/{pre}bench_pmc.txt), per launch, {f[2]} dispatches",
+                      f"itself (own pass; table profiles/{pre}bench_pmc.txt), per launch, {f[2]} dispatches",
             "read_bytes": int(rd * 1e6), "write_bytes": int(wr * 1e6), "hbm_side_bytes_per_launch": int((rd + wr) * 1e6),
             "l2_hit": float(f[8]), "mfma_busy_frac_at_2.4GHz": float(f[5]), "avg_us_under_pmc": float(f[3]),
             "whole_run_mfma_busy": float(whole.group(1)) if whole else None,

@@ -1,4 +1,5 @@
 """Per-workgroup phase timing of the fused MLP launch k_mlp (needs the -DMDT_DEBUG_TIMING build: MDT_HIP_LIB=.../libmdt_hip_dbg.so).
+usage: python tools/mlp_phases.py [SKEW]   (SKEW: mdt_op_set_mlp_skew's argument; default: the built-in schedule)
 Stamps (mlp_tile): 0 entry, 1 rows staged, 2 barrier passed, 3 phase-1 MFMA loop done, 4 GELU -> LDS done, 5 phase-2 loop done, 6 stores issued."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -6,6 +7,7 @@ import numpy as np, torch
 from mdt_policy_amd import _lib
 lib = _lib.load()
 lib.mdt_debug_set_timing_buffer.argtypes = [C.c_void_p]
+if len(sys.argv) > 1: lib.mdt_op_set_mlp_skew(int(sys.argv[1], 0))  # the wave schedule (mdt_op_set_mlp_skew), e.g. 0 or 0x112
 dev = torch.device("cuda"); M, D, N = 2560, 384, 1536
 g = torch.Generator().manual_seed(0); s = torch.cuda.current_stream().cuda_stream
 def packed(n, k):
@@ -35,7 +37,7 @@ lib.mdt_debug_set_timing_buffer(None)
 tall = buf.cpu().numpy().reshape(-1, 8); G = 240
 base = tall[:G, 0].min()
 names = ["stage rows (load + LN + LDS)", "barrier", "phase-1 MFMA loop (+ skew wait)", "W2 / gate / residual requests + GELU -> LDS", "(barrier +) phase-2 MFMA loop", "final epilogue"]
-print(f"k_mlp: {G} workgroups, event {e0.elapsed_time(e1) * 1e3:.1f} us, MDT_HIP_MLP_SKEW={os.environ.get('MDT_HIP_MLP_SKEW', 'default')}")
+print(f"k_mlp: {G} workgroups, event {e0.elapsed_time(e1) * 1e3:.1f} us, skew {sys.argv[1] if len(sys.argv) > 1 else 'default'}")
 for half, who in ((0, "wave 0 (early wave of its SIMD)"), (1, "wave 4 (its SIMD partner)")):
     t = tall[half * G:(half + 1) * G]
     if not (t[:, 0] != 0).all(): continue

@@ -1,4 +1,6 @@
-"""Summarise rocprofv3 --pmc CSVs of tools/gpu_pmc.sh into one table per kernel (averages over dispatches)."""
+"""Summarise rocprofv3 --pmc CSVs into one table per kernel (averages over dispatches).  usage: python tools/pmc_summary.py DIR
+DIR/p*/: one directory per counter pass, each its own `rocprofv3 --kernel-trace --output-format csv --pmc ... -d DIR/pN -- python
+tools/gemm_micro.py 5` run (the counters of one pass fit the hardware's counter slots; no other tracing beside them)."""
 import collections, csv, glob, os, sys
 root = sys.argv[1]
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
