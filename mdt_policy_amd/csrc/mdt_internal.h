@@ -1,5 +1,7 @@
-// mdt_internal.h -- launcher prototypes shared by mdt_kernels.hip (device code) and the host logic
-// (mdt_model.hip: denoiser handle; mdt_resampler.hip: Perceiver resampler handle), plus the host helpers both use.
+// mdt_internal.h -- launcher prototypes shared by the kernel sources and the host logic of every module (denoiser,
+// Perceiver resampler, MAP pool, masked-image decoder ops, InfoNCE), plus the host helpers they all use: error plumbing,
+// Lin, the Bump carver, gemm_args and the batch-buffer allocator.  The bookkeeping of the three stateful handles (parameter
+// slots, tapes, growing device blocks) is in mdt_handle.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "mdt_device.h"
-#include "mdt_internal.h"
+#include "mdt_handle.h"
 #include "mdt_map_pool.h"
 
 #define fail mdt_fail
@@ -237,48 +237,29 @@ namespace {
 
 const float RMS_EPS = 1e-8f;
 
-struct MSlot {
-    std::string name;
-    int64_t numel = 0;
-    bool pack = false;
-    float* dst = nullptr;
-    int rows = 0, K = 0;
-    bool loaded = false;
-    Lin* lin = nullptr;
-};
-
-struct MTape {
-    bool in_use = false;
-    int64_t B = 0, cap = 0;
-    int N = 0, cap_n = 0;
+struct MTape : TapeBase {
+    int64_t B = 0, cap = 0, cap_n = 0;
+    int N = 0;
     float* buf = nullptr;
     float *x, *xp, *kv, *probs, *att, *x1, *lat1, *u, *hid, *x2;
 };
 
 }  // namespace
 
-struct mdt_map_pool {
+struct mdt_map_pool : ParamTable {
     mdt_map_pool_config cfg;
     int Din, D, H, hd, Hm, Q;
-    float* arena = nullptr;
-    std::vector<MSlot> slots;
     float *latents, *an_g, *mn_g;
     Lin projection, q, kv, aproj, m0, m1;
-    float* staging = nullptr;
     float* qv = nullptr;  // q(latents): (Q, D), recomputed per forward (the weights may have changed)
     // inference workspace
     float* ws = nullptr;
-    int64_t cap_b = 0;
-    int cap_n = 0;
+    int64_t cap_b = 0, cap_n = 0;
     float *xp, *kvb, *att, *x1, *lat1, *u, *hid, *x2;
     // training
-    float* wt_arena = nullptr;
-    std::vector<int64_t> grad_off;
-    int64_t grad_numel = 0;
     std::vector<MTape> tapes;
     float* tscratch = nullptr;
-    int64_t ts_b = 0;
-    int ts_n = 0;
+    int64_t ts_b = 0, ts_n = 0;
     float *g_a, *g_b, *g_u, *g_hid, *g_dq, *g_dqs, *g_dkv, *g_dxp, *g_pg, *g_lin;
 };
 
@@ -286,16 +267,16 @@ static void build(mdt_map_pool* p, Bump& b, bool fill) {
     auto raw = [&](float*& dst, const std::string& name, int64_t n) {
         dst = b.take(n);
         if (!fill) return;
-        MSlot s;
-        s.name = name; s.numel = n; s.dst = dst;
+        Slot s;
+        s.name = name; s.numel = n; s.kind = SLOT_RAW; s.dst = dst;
         p->slots.push_back(s);
     };
     auto lin = [&](Lin& l, const std::string& name, int N, int K, bool bias) {
         l.N = N; l.K = K;
         l.wp = b.take((size_t)N * K);
         if (fill) {
-            MSlot s;
-            s.name = name + ".weight"; s.numel = (int64_t)N * K; s.pack = true; s.dst = l.wp; s.rows = N; s.K = K; s.lin = &l;
+            Slot s;
+            s.name = name + ".weight"; s.numel = (int64_t)N * K; s.kind = SLOT_PACK; s.dst = l.wp; s.rows = N; s.K = K; s.lin = &l;
             p->slots.push_back(s);
         }
         if (bias) raw(l.bias, name + ".bias", N);
@@ -331,17 +312,8 @@ extern "C" mdt_status mdt_map_pool_create(const mdt_map_pool_config* cfg, mdt_ma
     mdt_map_pool* p = new mdt_map_pool();
     p->cfg = c;
     p->Din = c.embed_dim; p->D = c.output_dim; p->H = 2 * c.n_heads; p->hd = p->D / p->H; p->Hm = c.mlp_hidden; p->Q = c.n_latents;
-    Bump count;
-    build(p, count, false);
-    hipError_t e = hipMalloc((void**)&p->arena, count.off * sizeof(float));
-    if (e != hipSuccess) { delete p; return fail(MDT_ERR_HIP, "hipMalloc(map pool arena) failed: %s", hipGetErrorString(e)); }
-    Bump real;
-    real.base = p->arena;
-    build(p, real, true);
-    size_t mx = 0;
-    for (const MSlot& s : p->slots) mx = std::max(mx, (size_t)s.numel);
-    e = hipMalloc((void**)&p->staging, mx * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(p->arena); delete p; return fail(MDT_ERR_HIP, "hipMalloc(staging) failed: %s", hipGetErrorString(e)); }
+    const mdt_status st = p->alloc([&](Bump& b, bool fill) { build(p, b, fill); }, "map pool");
+    if (st != MDT_OK) { p->free_params(); delete p; return st; }
     *out = p;
     return MDT_OK;
 }
@@ -349,53 +321,25 @@ extern "C" mdt_status mdt_map_pool_create(const mdt_map_pool_config* cfg, mdt_ma
 extern "C" mdt_status mdt_map_pool_destroy(mdt_map_pool* p) {
     if (!p) return MDT_OK;
     (void)hipDeviceSynchronize();
-    for (MTape& t : p->tapes) (void)mdt_dev_free(t.buf);
+    for (MTape& t : p->tapes) {
+        (void)mdt_dev_free(t.buf);
+        t.destroy_event();
+    }
     (void)mdt_dev_free(p->tscratch);
-    (void)hipFree(p->wt_arena);
-    (void)hipFree(p->arena);
-    (void)hipFree(p->staging);
+    p->free_params();
     (void)mdt_dev_free(p->ws);
     delete p;
     return MDT_OK;
 }
 
-extern "C" int64_t mdt_map_pool_param_count(const mdt_map_pool* p) { return p ? (int64_t)p->slots.size() : 0; }
-extern "C" const char* mdt_map_pool_param_name(const mdt_map_pool* p, int64_t i) {
-    return (p && i >= 0 && i < (int64_t)p->slots.size()) ? p->slots[i].name.c_str() : nullptr;
-}
-extern "C" int64_t mdt_map_pool_param_numel(const mdt_map_pool* p, int64_t i) {
-    return (p && i >= 0 && i < (int64_t)p->slots.size()) ? p->slots[i].numel : -1;
-}
+extern "C" int64_t mdt_map_pool_param_count(const mdt_map_pool* p) { return p ? p->size() : 0; }
+extern "C" const char* mdt_map_pool_param_name(const mdt_map_pool* p, int64_t i) { return p ? p->name(i) : nullptr; }
+extern "C" int64_t mdt_map_pool_param_numel(const mdt_map_pool* p, int64_t i) { return p ? p->numel(i) : -1; }
 
 extern "C" mdt_status mdt_map_pool_load_param(mdt_map_pool* p, const char* name, const float* src, int64_t numel,
                                               void* stream) {
     if (!p || !name || !src) return fail(MDT_ERR_INVALID_ARG, "mdt_map_pool_load_param: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    MSlot* slot = nullptr;
-    for (MSlot& c : p->slots)
-        if (c.name == name) { slot = &c; break; }
-    if (!slot) return fail(MDT_ERR_INVALID_ARG, "mdt_map_pool_load_param: unknown parameter '%s'", name);
-    if (numel != slot->numel)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_map_pool_load_param: '%s' has %lld elements, expected %lld", name,
-                    (long long)numel, (long long)slot->numel);
-    if (!slot->pack) {
-        HIP_TRY(hipMemcpyAsync(slot->dst, src, numel * sizeof(float), hipMemcpyDefault, s));
-    } else {
-        const float* dev = src;
-        hipPointerAttribute_t attr;
-        hipError_t pe = hipPointerGetAttributes(&attr, src);
-        if (!(pe == hipSuccess && attr.type == hipMemoryTypeDevice)) {
-            (void)hipGetLastError();  // unregistered host memory reports an error: clear it
-            HIP_TRY(hipMemcpyAsync(p->staging, src, numel * sizeof(float), hipMemcpyHostToDevice, s));
-            dev = p->staging;
-        }
-        LAUNCH(mdt_launch_pack_weight(dev, slot->rows, slot->K, slot->dst, 0, s));
-        if (slot->lin->wt)  // training: image of W^T for dX = dY W
-            LAUNCH(mdt_launch_pack_weight_t(dev, slot->rows, slot->K, slot->K, slot->lin->wt, 0, slot->lin->N / 16, s));
-        if (dev == p->staging) HIP_TRY(hipStreamSynchronize(s));  // the staging buffer is reused by the next upload
-    }
-    slot->loaded = true;
-    return MDT_OK;
+    return p->load("mdt_map_pool_load_param", name, src, numel, (hipStream_t)stream);
 }
 
 static mdt_status check_call(const mdt_map_pool* p, const float* x, const float* out, int64_t batch, int n_tokens, bool bwd) {
@@ -406,9 +350,7 @@ static mdt_status check_call(const mdt_map_pool* p, const float* x, const float*
     if (attn_lds_floats(p, n_tokens, bwd) * sizeof(float) > 64 * 1024)
         return fail(MDT_ERR_UNSUPPORTED, "map pool: %d latents x %d tokens x %d channels exceed the attention kernel's LDS budget",
                     p->Q, n_tokens, p->D);
-    for (const MSlot& sl : p->slots)
-        if (!sl.loaded) return fail(MDT_ERR_NOT_LOADED, "map pool parameter '%s' was never loaded", sl.name.c_str());
-    return MDT_OK;
+    return mdt_check_loaded(p->slots, "map pool parameter");
 }
 
 struct MBuf { float *xp, *kv, *probs, *att, *x1, *lat1, *u, *hid, *x2; };
@@ -454,18 +396,7 @@ static void carve_ws(mdt_map_pool* p, Bump& b, int64_t B, int N) {
 extern "C" mdt_status mdt_map_pool_forward(mdt_map_pool* p, const float* x, int64_t batch, int32_t n_tokens, float* out,
                                            void* stream) {
     MDT_TRY(check_call(p, x, out, batch, n_tokens, false));
-    if (batch > p->cap_b || n_tokens > p->cap_n) {
-        const int64_t B = std::max(batch, p->cap_b);
-        const int N = std::max((int)n_tokens, p->cap_n);
-        if (p->ws) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(mdt_dev_free(p->ws)); p->ws = nullptr; p->cap_b = 0; p->cap_n = 0; }
-        Bump count;
-        carve_ws(p, count, B, N);
-        HIP_TRY(mdt_dev_malloc((void**)&p->ws, count.off * sizeof(float)));
-        p->cap_b = B; p->cap_n = N;
-    }
-    Bump real;
-    real.base = p->ws;
-    carve_ws(p, real, p->cap_b, p->cap_n);
+    MDT_TRY(mdt_grow_carve(p->ws, p->cap_b, p->cap_n, batch, n_tokens, [&](Bump& b, int64_t B, int64_t N) { carve_ws(p, b, B, (int)N); }));
     MBuf w = {p->xp, p->kvb, nullptr, p->att, p->x1, p->lat1, p->u, p->hid, p->x2};
     return run_forward(p, x, batch, n_tokens, w, out, (hipStream_t)stream);
 }
@@ -476,25 +407,17 @@ extern "C" mdt_status mdt_map_pool_forward(mdt_map_pool* p, const float* x, int6
 extern "C" mdt_status mdt_map_pool_train_prepare(mdt_map_pool* p) {
     if (!p) return fail(MDT_ERR_INVALID_ARG, "mdt_map_pool_train_prepare: null handle");
     if (p->wt_arena) return MDT_OK;
-    Lin* lins[] = {&p->projection, &p->q, &p->kv, &p->aproj, &p->m0, &p->m1};
-    Bump count;
-    for (Lin* l : lins) count.take((size_t)l->N * l->K);
-    HIP_TRY(hipMalloc((void**)&p->wt_arena, count.off * sizeof(float)));
-    Bump real;
-    real.base = p->wt_arena;
-    for (Lin* l : lins) l->wt = real.take((size_t)l->N * l->K);
+    MDT_TRY(p->prepare_wt());
+    // gradient layout: slot order, every slot padded to 4 floats
     int64_t off = 0;
     p->grad_off.clear();
-    for (const MSlot& sl : p->slots) { p->grad_off.push_back(off); off += (sl.numel + 3) & ~(int64_t)3; }
+    for (const Slot& sl : p->slots) { p->grad_off.push_back(off); off += (sl.numel + 3) & ~(int64_t)3; }
     p->grad_numel = off;
-    for (MSlot& sl : p->slots) sl.loaded = false;
     return MDT_OK;
 }
 
-extern "C" int64_t mdt_map_pool_grad_numel(const mdt_map_pool* p) { return (p && p->wt_arena) ? p->grad_numel : -1; }
-extern "C" int64_t mdt_map_pool_grad_offset(const mdt_map_pool* p, int64_t i) {
-    return (p && p->wt_arena && i >= 0 && i < (int64_t)p->grad_off.size()) ? p->grad_off[i] : -1;
-}
+extern "C" int64_t mdt_map_pool_grad_numel(const mdt_map_pool* p) { return p ? p->grad_total() : -1; }
+extern "C" int64_t mdt_map_pool_grad_offset(const mdt_map_pool* p, int64_t i) { return p ? p->grad_offset(i) : -1; }
 
 static void carve_tape(mdt_map_pool* p, Bump& b, MTape& t, int64_t B, int N) {
     const int64_t rows = B * N, lr = B * p->Q;
@@ -520,18 +443,14 @@ static void carve_scratch(mdt_map_pool* p, Bump& b, int64_t B, int N) {
 }
 
 static mdt_status reserve_scratch(mdt_map_pool* p, int64_t B, int N) {
-    if (B > p->ts_b || N > p->ts_n) {
-        B = std::max(B, p->ts_b); N = std::max(N, p->ts_n);
-        if (p->tscratch) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(mdt_dev_free(p->tscratch)); p->tscratch = nullptr; }
-        Bump count;
-        carve_scratch(p, count, B, N);
-        HIP_TRY(mdt_dev_malloc((void**)&p->tscratch, count.off * sizeof(float)));
-        p->ts_b = B; p->ts_n = N;
-    }
-    Bump real;
-    real.base = p->tscratch;
-    carve_scratch(p, real, p->ts_b, p->ts_n);
-    return MDT_OK;
+    return mdt_grow_carve(p->tscratch, p->ts_b, p->ts_n, B, N, [&](Bump& b, int64_t cb, int64_t cn) { carve_scratch(p, b, cb, (int)cn); });
+}
+
+// the taped forward into t (its batch and token count set)
+static mdt_status forward_taped(mdt_map_pool* p, MTape& t, const float* x, float* out, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(t.x, x, (size_t)t.B * t.N * p->Din * sizeof(float), hipMemcpyDeviceToDevice, s));
+    MBuf w = {t.xp, t.kv, t.probs, t.att, t.x1, t.lat1, t.u, t.hid, t.x2};
+    return run_forward(p, t.x, t.B, t.N, w, out, s);
 }
 
 extern "C" mdt_status mdt_map_pool_forward_train(mdt_map_pool* p, const float* x, int64_t batch, int32_t n_tokens, float* out,
@@ -540,50 +459,24 @@ extern "C" mdt_status mdt_map_pool_forward_train(mdt_map_pool* p, const float* x
     if (p && !p->wt_arena) return fail(MDT_ERR_STATE, "map pool training was not prepared (mdt_map_pool_train_prepare)");
     MDT_TRY(check_call(p, x, out, batch, n_tokens, true));
     hipStream_t s = (hipStream_t)stream;
-    int pick = -1;
-    for (size_t i = 0; i < p->tapes.size(); ++i)
-        if (!p->tapes[i].in_use && p->tapes[i].cap >= batch && p->tapes[i].cap_n >= n_tokens) { pick = (int)i; break; }
-    if (pick < 0)
-        for (size_t i = 0; i < p->tapes.size(); ++i)
-            if (!p->tapes[i].in_use) { pick = (int)i; break; }
-    if (pick < 0) {
-        if (p->tapes.size() >= 8) return fail(MDT_ERR_STATE, "more than 8 map pool tapes alive: release tapes after their backward");
-        p->tapes.emplace_back();
-        pick = (int)p->tapes.size() - 1;
-    }
+    int32_t pick;
+    MDT_TRY(mdt_tape_acquire(p->tapes, 8, "map pool tapes", s, [&](const MTape& t) { return t.cap >= batch && t.cap_n >= n_tokens; },
+                             [&](MTape& t) {
+        return mdt_grow_carve(t.buf, t.cap, t.cap_n, batch, n_tokens, [&](Bump& b, int64_t B, int64_t N) { carve_tape(p, b, t, B, (int)N); });
+    }, &pick));
     MTape& t = p->tapes[pick];
-    if (t.cap < batch || t.cap_n < n_tokens) {
-        const int64_t B = std::max(batch, t.cap);
-        const int N = std::max((int)n_tokens, t.cap_n);
-        if (t.buf) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(mdt_dev_free(t.buf)); t.buf = nullptr; t.cap = 0; t.cap_n = 0; }
-        Bump count;
-        carve_tape(p, count, t, B, N);
-        HIP_TRY(mdt_dev_malloc((void**)&t.buf, count.off * sizeof(float)));
-        t.cap = B; t.cap_n = N;
-    }
-    Bump real;
-    real.base = t.buf;
-    carve_tape(p, real, t, t.cap, t.cap_n);
     t.B = batch; t.N = n_tokens;
-    HIP_TRY(hipMemcpyAsync(t.x, x, (size_t)batch * n_tokens * p->Din * sizeof(float), hipMemcpyDeviceToDevice, s));
-    MBuf w = {t.xp, t.kv, t.probs, t.att, t.x1, t.lat1, t.u, t.hid, t.x2};
-    MDT_TRY(run_forward(p, t.x, batch, n_tokens, w, out, s));
-    t.in_use = true;
-    *tape = pick;
-    return MDT_OK;
+    const mdt_status st = forward_taped(p, t, x, out, s);
+    if (st != MDT_OK) t.in_use = false;
+    else *tape = pick;
+    return st;
 }
 
 extern "C" mdt_status mdt_map_pool_tape_release(mdt_map_pool* p, int32_t tape) {
-    if (!p || tape < 0 || tape >= (int)p->tapes.size() || !p->tapes[tape].in_use)
-        return fail(MDT_ERR_INVALID_ARG, "invalid or released map pool tape %d", tape);
-    p->tapes[tape].in_use = false;
-    return MDT_OK;
-}
-
-static float* grad_of(mdt_map_pool* p, float* grads, const float* dst) {
-    for (size_t i = 0; i < p->slots.size(); ++i)
-        if (p->slots[i].dst == dst) return grads + p->grad_off[i];
-    return nullptr;
+    if (!p) return fail(MDT_ERR_INVALID_ARG, "invalid or released map pool tape %d", tape);
+    MTape* t;
+    MDT_TRY(mdt_tape_get(p->tapes, tape, "map pool tape", &t));
+    return t->release();
 }
 
 static mdt_status m_lin_bwd(mdt_map_pool* p, float* grads, const Lin& l, const float* X, int64_t ldx, const float* dY, int64_t ldy,
@@ -591,8 +484,8 @@ static mdt_status m_lin_bwd(mdt_map_pool* p, float* grads, const Lin& l, const f
     mdt_linear_bwd_args a;
     memset(&a, 0, sizeof a);
     a.X = X; a.ldx = ldx; a.dY = dY; a.ldy = ldy;
-    a.dW = grad_of(p, grads, l.wp);
-    a.dbias = l.bias ? grad_of(p, grads, l.bias) : nullptr;
+    a.dW = p->grad_of(grads, l.wp);
+    a.dbias = l.bias ? p->grad_of(grads, l.bias) : nullptr;
     a.accumulate_dw = 1; a.Wt = l.wt; a.dX = dX; a.ldxo = ldxo; a.accumulate_dx = acc_dx;
     a.M = (int)M; a.N = l.N; a.K = l.K; a.scratch = p->g_lin;
     return mdt_linear_bwd(a, s);
@@ -603,17 +496,18 @@ static mdt_status m_rms_bwd(mdt_map_pool* p, float* grads, const float* x, const
     const int blocks = (int)((M + 3) / 4);
     hipLaunchKernelGGL(k_rms_bwd, dim3(blocks), dim3(256), 0, s, x, g, dy, (const float*)nullptr, dx, acc, p->g_pg, (int)M, p->D, RMS_EPS);
     LAUNCH(hipGetLastError());
-    LAUNCH(mdt_launch_colsum(p->g_pg, p->D, blocks, p->D, grad_of(p, grads, g), 1, s));
+    LAUNCH(mdt_launch_colsum(p->g_pg, p->D, blocks, p->D, p->grad_of(grads, g), 1, s));
     return MDT_OK;
 }
 
 extern "C" mdt_status mdt_map_pool_backward(mdt_map_pool* p, int32_t tape, const float* g_out, float* grads, float* d_x,
                                             void* stream) {
     if (!p || !g_out || !grads) return fail(MDT_ERR_INVALID_ARG, "mdt_map_pool_backward: null argument");
-    if (tape < 0 || tape >= (int)p->tapes.size() || !p->tapes[tape].in_use)
-        return fail(MDT_ERR_INVALID_ARG, "invalid or released map pool tape %d", tape);
-    MTape& t = p->tapes[tape];
+    MTape* tp;
+    MDT_TRY(mdt_tape_get(p->tapes, tape, "map pool tape", &tp));
+    MTape& t = *tp;
     hipStream_t s = (hipStream_t)stream;
+    t.stream = s;
     const int D = p->D, Q = p->Q, Hm = p->Hm, N = t.N;
     const int64_t B = t.B, rows = B * N, lr = B * Q;
     MDT_TRY(reserve_scratch(p, B, N));
@@ -626,7 +520,7 @@ extern "C" mdt_status mdt_map_pool_backward(mdt_map_pool* p, int32_t tape, const
     MDT_TRY(m_lin_bwd(p, grads, p->m0, t.lat1, D, p->g_u, 2 * Hm, lr, p->g_a, D, 1, s));          // g_a += dX
     // lat1 = rms(x1) ; x1 = latents + attn.proj(att)
     MDT_TRY(m_rms_bwd(p, grads, t.x1, p->an_g, p->g_a, p->g_b, 0, lr, s));                        // g_b = d(x1)
-    float* g_lat = grad_of(p, grads, p->latents);
+    float* g_lat = p->grad_of(grads, p->latents);
     LAUNCH(mdt_launch_colsum(p->g_b, (int64_t)Q * D, (int)B, Q * D, g_lat, 1, s));                 // latents were repeated
     MDT_TRY(m_lin_bwd(p, grads, p->aproj, t.att, D, p->g_b, D, lr, p->g_a, D, 0, s));             // g_a = d(att)
     const float scale = 1.0f / sqrtf((float)p->hd);

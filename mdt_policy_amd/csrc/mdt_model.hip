@@ -437,52 +437,26 @@ extern "C" mdt_status mdt_load_param(mdt_model* m, const char* name, const float
     std::string nm(name);
     if (!m->cfg.use_modality_encoder && nm.rfind("inner_model.lang_emb", 0) == 0)
         nm.replace(0, strlen("inner_model.lang_emb"), "inner_model.goal_emb");  // same module in the reference
-    Slot* slot = nullptr;
-    for (Slot& c : m->slots)
-        if (c.name == nm) { slot = &c; break; }
+    Slot* slot = mdt_find_slot(m->slots, nm);
     if (!slot) {
         if (is_ignored_param(m, nm)) return MDT_OK;
         return fail(MDT_ERR_INVALID_ARG, "mdt_load_param: unknown parameter '%s'", name);
     }
-    if (numel != slot->numel)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_load_param: '%s' has %lld elements, expected %lld", name, (long long)numel,
-                    (long long)slot->numel);
+    MDT_TRY(mdt_check_numel("mdt_load_param", name, numel, *slot));
     std::vector<Slot*> targets;
     targets.push_back(slot);
     for (Slot& e : m->extra)
         if (e.name == nm) targets.push_back(&e);
     const float* dev_src = nullptr;  // device image of the source, staged at most once
     for (Slot* t : targets) {
-        if (t->kind == SLOT_RAW) {
-            HIP_TRY(hipMemcpyAsync(t->dst, src, numel * sizeof(float), hipMemcpyDefault, s));
-            continue;
-        }
-        if (t->kind == SLOT_PAD_COLS) {  // (rows, K) -> (rows, n_off): the pad columns keep the arena's zeros
-            HIP_TRY(hipMemcpy2DAsync(t->dst, (size_t)t->n_off * sizeof(float), src, (size_t)t->K * sizeof(float),
-                                     (size_t)t->K * sizeof(float), (size_t)t->rows, hipMemcpyDefault, s));
-            continue;
-        }
-        if (dev_src == nullptr) {
-            hipPointerAttribute_t attr;
-            hipError_t pe = hipPointerGetAttributes(&attr, src);
-            if (pe == hipSuccess && attr.type == hipMemoryTypeDevice) {
-                dev_src = src;
-            } else {
-                (void)hipGetLastError();  // unregistered host memory reports an error: clear it
-                HIP_TRY(hipMemcpyAsync(m->staging, src, numel * sizeof(float), hipMemcpyHostToDevice, s));
-                dev_src = m->staging;
-            }
-        }
-        if (t->kind == SLOT_PACK_SPLIT) {
-            if (m->train) { mark_split_stale(m); continue; }   // training: re-made on demand (mdt_model_types.h)
+        if (t->kind != SLOT_PACK_SPLIT) {
+            MDT_TRY(mdt_upload_slot(*t, src, numel, m->staging, s, &dev_src));
+        } else if (m->train) {
+            mark_split_stale(m);   // training: re-made on demand (mdt_model_types.h)
+        } else {
+            MDT_TRY(mdt_stage_source(src, numel, m->staging, s, &dev_src));
             HIP_TRY(mdt_launch_pack_weight_split(dev_src, t->rows, t->K, t->dst, s, t->n_off));
-            continue;
         }
-        if (t->kind == SLOT_TRANSPOSE) HIP_TRY(mdt_launch_transpose(dev_src, t->dst, t->rows, t->K, s));
-        else if (t->kind == SLOT_PACK_T) HIP_TRY(mdt_launch_pack_weight_t(dev_src, t->rows, t->K, t->K, t->dst, 0, t->rows / 16, s));  // image of the transpose
-        else HIP_TRY(mdt_launch_pack_weight(dev_src, t->rows, t->K, t->dst, t->n_off, s));
-        if (t->kind == SLOT_PACK && t->lin && t->lin->wt)  // training: image of W^T for dX = dY W
-            HIP_TRY(mdt_launch_pack_weight_t(dev_src, t->rows, t->K, t->K, t->lin->wt, t->n_off, t->lin->N / 16, s));
     }
     slot->loaded = true;
     return MDT_OK;
@@ -512,16 +486,12 @@ extern "C" mdt_status mdt_load_params(mdt_model* m, int32_t n, const char* const
         std::string nm(names[i]);
         if (!m->cfg.use_modality_encoder && nm.rfind("inner_model.lang_emb", 0) == 0)
             nm.replace(0, strlen("inner_model.lang_emb"), "inner_model.goal_emb");
-        Slot* slot = nullptr;
-        for (Slot& c : m->slots)
-            if (c.name == nm) { slot = &c; break; }
+        Slot* slot = mdt_find_slot(m->slots, nm);
         if (!slot) {
             if (is_ignored_param(m, nm)) continue;
             return fail(MDT_ERR_INVALID_ARG, "mdt_load_params: unknown parameter '%s'", names[i]);
         }
-        if (numels[i] != slot->numel)
-            return fail(MDT_ERR_INVALID_ARG, "mdt_load_params: '%s' has %lld elements, expected %lld", names[i],
-                        (long long)numels[i], (long long)slot->numel);
+        MDT_TRY(mdt_check_numel("mdt_load_params", names[i], numels[i], *slot));
         hipPointerAttribute_t attr;
         const hipError_t pe = hipPointerGetAttributes(&attr, srcs[i]);
         if (pe != hipSuccess || attr.type != hipMemoryTypeDevice || ((uintptr_t)srcs[i] & 15)) {
@@ -591,11 +561,7 @@ extern "C" mdt_status mdt_load_params(mdt_model* m, int32_t n, const char* const
     return MDT_OK;
 }
 
-static mdt_status check_loaded(const mdt_model* m) {
-    for (const Slot& s : m->slots)
-        if (!s.loaded) return fail(MDT_ERR_NOT_LOADED, "parameter '%s' was never loaded", s.name.c_str());
-    return MDT_OK;
-}
+static mdt_status check_loaded(const mdt_model* m) { return mdt_check_loaded(m->slots, "parameter"); }
 
 // ------------------------------------------------------------------------------------------------
 // workspace
@@ -635,22 +601,10 @@ extern "C" mdt_status mdt_reserve(mdt_model* m, int64_t max_batch) {
     if (!m || max_batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_reserve: bad argument");
     if (max_batch <= m->cap) return MDT_OK;
     if (max_batch * std::max(m->Te, m->Ta) > (int64_t)1 << 24) return fail(MDT_ERR_INVALID_ARG, "batch too large");
-    if (m->ws) {
-        HIP_TRY(hipDeviceSynchronize());  // previous work may still read the old workspace
-        HIP_TRY(mdt_dev_free(m->ws));
-        m->ws = nullptr;
-        m->cap = 0;
-        m->cached_batch = 0;
-    }
-    Bump count;
-    carve_ws(m, count, max_batch);
-    HIP_TRY(mdt_dev_malloc((void**)&m->ws, count.off * sizeof(float)));
-    Bump real;
-    real.base = m->ws;
-    carve_ws(m, real, max_batch);
+    m->cached_batch = 0;
+    MDT_TRY(mdt_grow_carve(m->ws, m->cap, max_batch, [&](Bump& b, int64_t cap) { carve_ws(m, b, cap); }));
     if (m->cond == COND_NOISE)  // the "scale" half of every [c | ones] row; the c half is rewritten per call
         HIP_TRY(hipMemsetD32((hipDeviceptr_t)m->cmod, 0x3f800000u, (size_t)std::max<int64_t>(max_batch, MAX_STEPS) * 2 * m->D));
-    m->cap = max_batch;
     ++m->ws_generation;
     return MDT_OK;
 }

@@ -1,27 +1,11 @@
 // mdt_model_types.h -- the denoiser handle's data structures, shared by mdt_model.hip (inference launch sequences)
-// and mdt_train.hip (training forward / backward).
+// and mdt_train.hip (training forward / backward).  Its parameter slots, upload and tape pool are the ones every handle
+// uses (mdt_handle.h); the stacked-Linear layout (LinPart) is the denoiser's own.
 #pragma once
 #include <string>
 #include <vector>
 
-#include "mdt_internal.h"
-
-// ------------------------------------------------------------------------------------------------
-// model description
-// ------------------------------------------------------------------------------------------------
-// TRANSPOSE: (rows, K) -> (K, rows);  PAD_COLS: (rows, K) -> (rows, n_off) row-major, columns K.. stay zero
-enum SlotKind { SLOT_PACK = 0, SLOT_RAW = 1, SLOT_TRANSPOSE = 2, SLOT_PAD_COLS = 3, SLOT_PACK_T = 4,  // PACK_T: fragment image of the TRANSPOSE of a (rows, K) matrix
-                SLOT_PACK_SPLIT = 5 };  // three-way bf16 split fragment image of a (rows, K) matrix (mdt_mlp_split.h): 6 rows K bytes at dst
-
-struct Slot {
-    std::string name;
-    int64_t numel = 0;
-    int kind = SLOT_RAW;
-    float* dst = nullptr;  // packed image base (SLOT_PACK) or raw destination (SLOT_RAW)
-    int rows = 0, K = 0, n_off = 0;
-    bool loaded = false;
-    Lin* lin = nullptr;    // SLOT_PACK: the Linear this part belongs to (training keeps a transposed image too)
-};
+#include "mdt_handle.h"
 
 // one reference nn.Linear inside a (possibly stacked) Lin: rows [n_off, n_off + rows) of its packed image
 struct LinPart {

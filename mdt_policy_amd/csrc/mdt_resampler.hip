@@ -18,21 +18,11 @@
 #include <utility>
 #include <vector>
 
-#include "mdt_internal.h"
+#include "mdt_handle.h"
 
 #define fail mdt_fail
 
 namespace {
-
-struct RSlot {
-    std::string name;
-    int64_t numel = 0;
-    bool pack = false;
-    float* dst = nullptr;
-    int rows = 0, K = 0, n_off = 0;
-    bool loaded = false;
-    Lin* lin = nullptr;
-};
 
 struct RLayer {
     float *nm_w, *nm_b, *nl_w, *nl_b, *ff_w, *ff_b;
@@ -43,8 +33,7 @@ struct RLayerTape {  // rows: media B*F, latents B*Q
     float *st_m, *kv, *x_in, *st_l, *lat_n, *q, *att, *x_mid, *st_f, *h, *u, *hid, *x_out;
 };
 
-struct RTape {
-    bool in_use = false;
+struct RTape : TapeBase {
     int64_t B = 0, cap_rows = 0, cap_b = 0;
     int T = 0, n = 0, has_mask = 0;
     float* buf = nullptr;
@@ -55,24 +44,16 @@ struct RTape {
 
 }  // namespace
 
-struct mdt_resampler {
+struct mdt_resampler : ParamTable {
     mdt_resampler_config cfg;
     int D, inner, ff, Q, H, hd;
-    float* arena = nullptr;
-    size_t arena_floats = 0;
-    std::vector<RSlot> slots;
     std::vector<RLayer> layers;
     float *latents = nullptr, *tpe = nullptr, *norm_w = nullptr, *norm_b = nullptr;
-    float* staging = nullptr;
-    size_t staging_floats = 0;
     // workspace for up to cap_rows media rows (B*T*n) and cap_b samples
     float* ws = nullptr;
     int64_t cap_rows = 0, cap_b = 0;
     float *xf, *kv, *x, *qb, *att, *hid;
     // training
-    float* wt_arena = nullptr;
-    std::vector<int64_t> grad_off;
-    int64_t grad_numel = 0;
     std::vector<RTape> tapes;
     float* tscratch = nullptr;
     int64_t ts_rows = 0, ts_b = 0;
@@ -84,8 +65,8 @@ static void build(mdt_resampler* r, Bump& b, bool fill) {
     auto raw = [&](float*& p, const std::string& name, int64_t n) {
         p = b.take(n);
         if (!fill) return;
-        RSlot s;
-        s.name = name; s.numel = n; s.pack = false; s.dst = p;
+        Slot s;
+        s.name = name; s.numel = n; s.kind = SLOT_RAW; s.dst = p;
         r->slots.push_back(s);
     };
     auto lin = [&](Lin& l, int N, int K) {
@@ -94,8 +75,8 @@ static void build(mdt_resampler* r, Bump& b, bool fill) {
     };
     auto part = [&](Lin& l, const std::string& name, int rows, int n_off) {
         if (!fill) return;
-        RSlot s;
-        s.name = name; s.numel = (int64_t)rows * l.K; s.pack = true; s.dst = l.wp; s.rows = rows; s.K = l.K; s.n_off = n_off;
+        Slot s;
+        s.name = name; s.numel = (int64_t)rows * l.K; s.kind = SLOT_PACK; s.dst = l.wp; s.rows = rows; s.K = l.K; s.n_off = n_off;
         s.lin = &l;
         r->slots.push_back(s);
     };
@@ -144,19 +125,8 @@ extern "C" mdt_status mdt_resampler_create(const mdt_resampler_config* cfg, mdt_
     r->cfg = c;
     r->D = c.dim; r->H = c.heads; r->hd = c.dim_head; r->inner = c.heads * c.dim_head; r->ff = c.ff_mult * c.dim;
     r->Q = c.num_latents;
-    Bump count;
-    build(r, count, false);
-    r->arena_floats = count.off;
-    hipError_t e = hipMalloc((void**)&r->arena, r->arena_floats * sizeof(float));
-    if (e != hipSuccess) { delete r; return fail(MDT_ERR_HIP, "hipMalloc(resampler arena) failed: %s", hipGetErrorString(e)); }
-    Bump real;
-    real.base = r->arena;
-    build(r, real, true);
-    size_t mx = 0;
-    for (const RSlot& s : r->slots) mx = std::max(mx, (size_t)s.numel);
-    r->staging_floats = mx;
-    e = hipMalloc((void**)&r->staging, mx * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(r->arena); delete r; return fail(MDT_ERR_HIP, "hipMalloc(staging) failed: %s", hipGetErrorString(e)); }
+    const mdt_status st = r->alloc([&](Bump& b, bool fill) { build(r, b, fill); }, "resampler");
+    if (st != MDT_OK) { r->free_params(); delete r; return st; }
     *out = r;
     return MDT_OK;
 }
@@ -164,53 +134,25 @@ extern "C" mdt_status mdt_resampler_create(const mdt_resampler_config* cfg, mdt_
 extern "C" mdt_status mdt_resampler_destroy(mdt_resampler* r) {
     if (!r) return MDT_OK;
     (void)hipDeviceSynchronize();
-    for (RTape& t : r->tapes) (void)mdt_dev_free(t.buf);
+    for (RTape& t : r->tapes) {
+        (void)mdt_dev_free(t.buf);
+        t.destroy_event();
+    }
     (void)mdt_dev_free(r->tscratch);
-    (void)hipFree(r->wt_arena);
-    (void)hipFree(r->arena);
-    (void)hipFree(r->staging);
+    r->free_params();
     (void)mdt_dev_free(r->ws);
     delete r;
     return MDT_OK;
 }
 
-extern "C" int64_t mdt_resampler_param_count(const mdt_resampler* r) { return r ? (int64_t)r->slots.size() : 0; }
-extern "C" const char* mdt_resampler_param_name(const mdt_resampler* r, int64_t i) {
-    return (r && i >= 0 && i < (int64_t)r->slots.size()) ? r->slots[i].name.c_str() : nullptr;
-}
-extern "C" int64_t mdt_resampler_param_numel(const mdt_resampler* r, int64_t i) {
-    return (r && i >= 0 && i < (int64_t)r->slots.size()) ? r->slots[i].numel : -1;
-}
+extern "C" int64_t mdt_resampler_param_count(const mdt_resampler* r) { return r ? r->size() : 0; }
+extern "C" const char* mdt_resampler_param_name(const mdt_resampler* r, int64_t i) { return r ? r->name(i) : nullptr; }
+extern "C" int64_t mdt_resampler_param_numel(const mdt_resampler* r, int64_t i) { return r ? r->numel(i) : -1; }
 
 extern "C" mdt_status mdt_resampler_load_param(mdt_resampler* r, const char* name, const float* src, int64_t numel,
                                                void* stream) {
     if (!r || !name || !src) return fail(MDT_ERR_INVALID_ARG, "mdt_resampler_load_param: null argument");
-    hipStream_t s = (hipStream_t)stream;
-    RSlot* slot = nullptr;
-    for (RSlot& c : r->slots)
-        if (c.name == name) { slot = &c; break; }
-    if (!slot) return fail(MDT_ERR_INVALID_ARG, "mdt_resampler_load_param: unknown parameter '%s'", name);
-    if (numel != slot->numel)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_resampler_load_param: '%s' has %lld elements, expected %lld", name,
-                    (long long)numel, (long long)slot->numel);
-    if (!slot->pack) {
-        HIP_TRY(hipMemcpyAsync(slot->dst, src, numel * sizeof(float), hipMemcpyDefault, s));
-    } else {
-        const float* dev = src;
-        hipPointerAttribute_t attr;
-        hipError_t pe = hipPointerGetAttributes(&attr, src);
-        if (!(pe == hipSuccess && attr.type == hipMemoryTypeDevice)) {
-            (void)hipGetLastError();  // unregistered host memory reports an error: clear it
-            HIP_TRY(hipMemcpyAsync(r->staging, src, numel * sizeof(float), hipMemcpyHostToDevice, s));
-            dev = r->staging;
-        }
-        LAUNCH(mdt_launch_pack_weight(dev, slot->rows, slot->K, slot->dst, slot->n_off, s));
-        if (slot->lin && slot->lin->wt)  // training: image of W^T for dX = dY W
-            LAUNCH(mdt_launch_pack_weight_t(dev, slot->rows, slot->K, slot->K, slot->lin->wt, slot->n_off, slot->lin->N / 16, s));
-        if (dev == r->staging) HIP_TRY(hipStreamSynchronize(s));  // the staging buffer is reused by the next upload
-    }
-    slot->loaded = true;
-    return MDT_OK;
+    return r->load("mdt_resampler_load_param", name, src, numel, (hipStream_t)stream);
 }
 
 static void carve(mdt_resampler* r, Bump& b, int64_t rows, int64_t B) {
@@ -223,27 +165,6 @@ static void carve(mdt_resampler* r, Bump& b, int64_t rows, int64_t B) {
     r->hid = b.take(lr * r->ff);
 }
 
-static mdt_status reserve(mdt_resampler* r, int64_t rows, int64_t B) {
-    if (rows <= r->cap_rows && B <= r->cap_b) return MDT_OK;
-    rows = std::max(rows, r->cap_rows);
-    B = std::max(B, r->cap_b);
-    if (r->ws) {
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(mdt_dev_free(r->ws));
-        r->ws = nullptr;
-        r->cap_rows = r->cap_b = 0;
-    }
-    Bump count;
-    carve(r, count, rows, B);
-    HIP_TRY(mdt_dev_malloc((void**)&r->ws, count.off * sizeof(float)));
-    Bump real;
-    real.base = r->ws;
-    carve(r, real, rows, B);
-    r->cap_rows = rows;
-    r->cap_b = B;
-    return MDT_OK;
-}
-
 extern "C" mdt_status mdt_resampler_forward(mdt_resampler* r, const float* x_f, const uint8_t* mask, int64_t batch,
                                             int32_t n_frames, int32_t n_tokens, float* out, void* stream) {
     if (!r || !x_f || !out || batch < 1 || n_frames < 1 || n_tokens < 1)
@@ -253,8 +174,7 @@ extern "C" mdt_status mdt_resampler_forward(mdt_resampler* r, const float* x_f, 
                     r->cfg.num_time_embeds);
     if (((uintptr_t)x_f & 15) || ((uintptr_t)out & 15))
         return fail(MDT_ERR_INVALID_ARG, "mdt_resampler_forward: pointers must be 16-byte aligned");
-    for (const RSlot& sl : r->slots)
-        if (!sl.loaded) return fail(MDT_ERR_NOT_LOADED, "resampler parameter '%s' was never loaded", sl.name.c_str());
+    MDT_TRY(mdt_check_loaded(r->slots, "resampler parameter"));
     const int D = r->D, inner = r->inner, Q = r->Q;
     const int F = n_frames * n_tokens, Tk = F + Q;
     if (!mdt_attention_long_supported(r->hd, Q, Tk))
@@ -262,7 +182,7 @@ extern "C" mdt_status mdt_resampler_forward(mdt_resampler* r, const float* x_f, 
     const int64_t rows = batch * F, lr = batch * Q;
     if (rows > ((int64_t)1 << 30) / D) return fail(MDT_ERR_INVALID_ARG, "resampler: batch too large");
     hipStream_t s = (hipStream_t)stream;
-    MDT_TRY(reserve(r, rows, batch));
+    MDT_TRY(mdt_grow_carve(r->ws, r->cap_rows, r->cap_b, rows, batch, [&](Bump& b, int64_t c0, int64_t c1) { carve(r, b, c0, c1); }));
     // x_f + time_pos_emb (masked per frame), frames flattened; latents repeated over the batch      (:141-154)
     LAUNCH(mdt_launch_add_time_emb(x_f, r->tpe, mask, r->xf, batch, n_frames, n_tokens, D, s));
     LAUNCH(mdt_launch_bcast_rows(r->latents, r->x, batch, Q, D, s));
@@ -310,28 +230,17 @@ extern "C" double mdt_resampler_flops(const mdt_resampler* r, int32_t n_frames, 
 extern "C" mdt_status mdt_resampler_train_prepare(mdt_resampler* r) {
     if (!r) return fail(MDT_ERR_INVALID_ARG, "mdt_resampler_train_prepare: null handle");
     if (r->wt_arena) return MDT_OK;
-    std::vector<Lin*> lins;
-    for (RSlot& sl : r->slots)
-        if (sl.lin && std::find(lins.begin(), lins.end(), sl.lin) == lins.end()) lins.push_back(sl.lin);
-    Bump count;
-    for (Lin* l : lins) count.take((size_t)l->N * l->K);
-    HIP_TRY(hipMalloc((void**)&r->wt_arena, count.off * sizeof(float)));
-    Bump real;
-    real.base = r->wt_arena;
-    for (Lin* l : lins) l->wt = real.take((size_t)l->N * l->K);
+    MDT_TRY(r->prepare_wt());
     // gradient layout: slot order (to_k | to_v are adjacent slots, so the stacked K|V weight is contiguous)
     int64_t off = 0;
     r->grad_off.clear();
-    for (const RSlot& sl : r->slots) { r->grad_off.push_back(off); off += sl.numel; }
+    for (const Slot& sl : r->slots) { r->grad_off.push_back(off); off += sl.numel; }
     r->grad_numel = off;
-    for (RSlot& sl : r->slots) sl.loaded = false;
     return MDT_OK;
 }
 
-extern "C" int64_t mdt_resampler_grad_numel(const mdt_resampler* r) { return (r && r->wt_arena) ? r->grad_numel : -1; }
-extern "C" int64_t mdt_resampler_grad_offset(const mdt_resampler* r, int64_t i) {
-    return (r && r->wt_arena && i >= 0 && i < (int64_t)r->grad_off.size()) ? r->grad_off[i] : -1;
-}
+extern "C" int64_t mdt_resampler_grad_numel(const mdt_resampler* r) { return r ? r->grad_total() : -1; }
+extern "C" int64_t mdt_resampler_grad_offset(const mdt_resampler* r, int64_t i) { return r ? r->grad_offset(i) : -1; }
 
 static void carve_rtape(mdt_resampler* r, Bump& b, RTape& t, int64_t rows, int64_t B) {
     const int D = r->D, I = r->inner, Q = r->Q;
@@ -372,57 +281,16 @@ static void carve_rscratch(mdt_resampler* r, Bump& b, int64_t rows, int64_t B) {
 }
 
 static mdt_status rscratch(mdt_resampler* r, int64_t rows, int64_t B) {
-    if (rows > r->ts_rows || B > r->ts_b) {
-        rows = std::max(rows, r->ts_rows); B = std::max(B, r->ts_b);
-        if (r->tscratch) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(mdt_dev_free(r->tscratch)); r->tscratch = nullptr; }
-        Bump count;
-        carve_rscratch(r, count, rows, B);
-        HIP_TRY(mdt_dev_malloc((void**)&r->tscratch, count.off * sizeof(float)));
-        r->ts_rows = rows; r->ts_b = B;
-    }
-    Bump real;
-    real.base = r->tscratch;
-    carve_rscratch(r, real, r->ts_rows, r->ts_b);
-    return MDT_OK;
+    return mdt_grow_carve(r->tscratch, r->ts_rows, r->ts_b, rows, B,
+                          [&](Bump& b, int64_t c0, int64_t c1) { carve_rscratch(r, b, c0, c1); });
 }
 
-extern "C" mdt_status mdt_resampler_forward_train(mdt_resampler* r, const float* x_f, const uint8_t* mask, int64_t batch,
-                                                  int32_t n_frames, int32_t n_tokens, float* out, int32_t* tape,
-                                                  void* stream) {
-    if (!r || !x_f || !out || !tape || batch < 1 || n_frames < 1 || n_tokens < 1)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_resampler_forward_train: bad argument");
-    if (!r->wt_arena) return fail(MDT_ERR_STATE, "resampler training was not prepared (mdt_resampler_train_prepare)");
-    if (n_frames > r->cfg.num_time_embeds) return fail(MDT_ERR_INVALID_ARG, "more frames than time embeddings");
-    for (const RSlot& sl : r->slots)
-        if (!sl.loaded) return fail(MDT_ERR_NOT_LOADED, "resampler parameter '%s' was not loaded after train_prepare", sl.name.c_str());
+// the taped forward into t (its batch and frame shape set)
+static mdt_status forward_taped(mdt_resampler* r, RTape& t, const float* x_f, const uint8_t* mask, float* out, hipStream_t s) {
+    const int64_t batch = t.B;
+    const int n_frames = t.T, n_tokens = t.n;
     const int D = r->D, I = r->inner, Q = r->Q, F = n_frames * n_tokens, Tk = F + Q;
-    if (!mdt_attention_long_bwd_supported(r->hd, Q, Tk))
-        return fail(MDT_ERR_UNSUPPORTED, "resampler: %d keys x %d latents exceeds the attention kernels' LDS budget", Tk, Q);
     const int64_t rows = batch * F, lr = batch * Q;
-    hipStream_t s = (hipStream_t)stream;
-    int pick = -1;
-    for (size_t i = 0; i < r->tapes.size(); ++i)
-        if (!r->tapes[i].in_use && r->tapes[i].cap_rows >= rows && r->tapes[i].cap_b >= batch) { pick = (int)i; break; }
-    if (pick < 0)
-        for (size_t i = 0; i < r->tapes.size(); ++i)
-            if (!r->tapes[i].in_use) { pick = (int)i; break; }
-    if (pick < 0) {
-        if (r->tapes.size() >= 8) return fail(MDT_ERR_STATE, "more than 8 resampler tapes alive");
-        r->tapes.emplace_back();
-        pick = (int)r->tapes.size() - 1;
-    }
-    RTape& t = r->tapes[pick];
-    if (t.cap_rows < rows || t.cap_b < batch) {
-        if (t.buf) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(mdt_dev_free(t.buf)); t.buf = nullptr; }
-        Bump count;
-        carve_rtape(r, count, t, rows, batch);
-        HIP_TRY(mdt_dev_malloc((void**)&t.buf, count.off * sizeof(float)));
-        t.cap_rows = rows; t.cap_b = batch;
-    }
-    Bump real;
-    real.base = t.buf;
-    carve_rtape(r, real, t, t.cap_rows, t.cap_b);
-    t.B = batch; t.T = n_frames; t.n = n_tokens; t.has_mask = mask != nullptr;
     MDT_TRY(rscratch(r, rows, batch));
     if (mask) HIP_TRY(hipMemcpyAsync(t.mask, mask, (size_t)batch * n_frames, hipMemcpyDeviceToDevice, s));
     LAUNCH(mdt_launch_add_time_emb(x_f, r->tpe, mask, t.xf, batch, n_frames, n_tokens, D, s));
@@ -457,22 +325,41 @@ extern "C" mdt_status mdt_resampler_forward_train(mdt_resampler* r, const float*
         x = P.x_out;
     }
     LAUNCH(mdt_launch_ln_fwd_train(rln(x, r->norm_w, r->norm_b, out, t.st_out, lr, D), s));
-    t.in_use = true;
-    *tape = pick;
     return MDT_OK;
+}
+
+extern "C" mdt_status mdt_resampler_forward_train(mdt_resampler* r, const float* x_f, const uint8_t* mask, int64_t batch,
+                                                  int32_t n_frames, int32_t n_tokens, float* out, int32_t* tape,
+                                                  void* stream) {
+    if (!r || !x_f || !out || !tape || batch < 1 || n_frames < 1 || n_tokens < 1)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_resampler_forward_train: bad argument");
+    if (!r->wt_arena) return fail(MDT_ERR_STATE, "resampler training was not prepared (mdt_resampler_train_prepare)");
+    if (n_frames > r->cfg.num_time_embeds) return fail(MDT_ERR_INVALID_ARG, "more frames than time embeddings");
+    MDT_TRY(mdt_check_loaded(r->slots, "resampler parameter", "was not loaded after train_prepare"));
+    const int Q = r->Q, F = n_frames * n_tokens, Tk = F + Q;
+    if (!mdt_attention_long_bwd_supported(r->hd, Q, Tk))
+        return fail(MDT_ERR_UNSUPPORTED, "resampler: %d keys x %d latents exceeds the attention kernels' LDS budget", Tk, Q);
+    const int64_t rows = batch * F;
+    hipStream_t s = (hipStream_t)stream;
+    int32_t pick;
+    MDT_TRY(mdt_tape_acquire(r->tapes, 8, "resampler tapes", s,
+                             [&](const RTape& t) { return t.cap_rows >= rows && t.cap_b >= batch; }, [&](RTape& t) {
+        return mdt_grow_carve(t.buf, t.cap_rows, t.cap_b, rows, batch,
+                              [&](Bump& b, int64_t c0, int64_t c1) { carve_rtape(r, b, t, c0, c1); });
+    }, &pick));
+    RTape& t = r->tapes[pick];
+    t.B = batch; t.T = n_frames; t.n = n_tokens; t.has_mask = mask != nullptr;
+    const mdt_status st = forward_taped(r, t, x_f, mask, out, s);
+    if (st != MDT_OK) t.in_use = false;
+    else *tape = pick;
+    return st;
 }
 
 extern "C" mdt_status mdt_resampler_tape_release(mdt_resampler* r, int32_t tape) {
-    if (!r || tape < 0 || tape >= (int)r->tapes.size() || !r->tapes[tape].in_use)
-        return fail(MDT_ERR_INVALID_ARG, "invalid or released resampler tape %d", tape);
-    r->tapes[tape].in_use = false;
-    return MDT_OK;
-}
-
-static int rslot_of(const mdt_resampler* r, const float* dst) {
-    for (size_t i = 0; i < r->slots.size(); ++i)
-        if (r->slots[i].dst == dst) return (int)i;
-    return -1;
+    if (!r) return fail(MDT_ERR_INVALID_ARG, "invalid or released resampler tape %d", tape);
+    RTape* t;
+    MDT_TRY(mdt_tape_get(r->tapes, tape, "resampler tape", &t));
+    return t->release();
 }
 
 static mdt_status r_lin_bwd(mdt_resampler* r, float* grads, const Lin& l, const float* X, int64_t ldx, const float* dY,
@@ -480,7 +367,7 @@ static mdt_status r_lin_bwd(mdt_resampler* r, float* grads, const Lin& l, const 
     mdt_linear_bwd_args a;
     memset(&a, 0, sizeof a);
     a.X = X; a.ldx = ldx; a.dY = dY; a.ldy = ldy;
-    a.dW = grads + r->grad_off[rslot_of(r, l.wp)];  // first part of the stack (rows from 0)
+    a.dW = r->grad_of(grads, l.wp);  // first part of the stack (rows from 0)
     a.accumulate_dw = 1; a.Wt = l.wt; a.dX = dX; a.ldxo = ldxo; a.accumulate_dx = acc_dx;
     a.M = (int)M; a.N = l.N; a.K = l.K; a.scratch = r->g_lin;
     return mdt_linear_bwd(a, s);
@@ -494,18 +381,18 @@ static mdt_status r_ln_bwd(mdt_resampler* r, float* grads, const float* x, const
     a.accumulate = acc; a.pw = r->g_pw; a.pb = r->g_pb; a.B = (int)B; a.rows_per_sample = rps; a.D = r->D;
     a.row_chunks = std::max(1, std::min(LN_CHUNKS, rps / 32));  // the ~400 media rows of a sample: 8 workgroups
     LAUNCH(mdt_launch_ln_bwd(a, s));
-    LAUNCH(mdt_launch_colsum2(r->g_pw, r->g_pb, r->D, (int)B * a.row_chunks, r->D, grads + r->grad_off[rslot_of(r, w)],
-                              grads + r->grad_off[rslot_of(r, b)], 1, s));
+    LAUNCH(mdt_launch_colsum2(r->g_pw, r->g_pb, r->D, (int)B * a.row_chunks, r->D, r->grad_of(grads, w), r->grad_of(grads, b), 1, s));
     return MDT_OK;
 }
 
 extern "C" mdt_status mdt_resampler_backward(mdt_resampler* r, int32_t tape, const float* g_out, float* grads, float* d_x_f,
                                              void* stream) {
     if (!r || !g_out || !grads) return fail(MDT_ERR_INVALID_ARG, "mdt_resampler_backward: null argument");
-    if (tape < 0 || tape >= (int)r->tapes.size() || !r->tapes[tape].in_use)
-        return fail(MDT_ERR_INVALID_ARG, "invalid or released resampler tape %d", tape);
-    RTape& t = r->tapes[tape];
+    RTape* tp;
+    MDT_TRY(mdt_tape_get(r->tapes, tape, "resampler tape", &tp));
+    RTape& t = *tp;
     hipStream_t s = (hipStream_t)stream;
+    t.stream = s;
     const int D = r->D, I = r->inner, Q = r->Q, F = t.T * t.n, Tk = F + Q;
     const int64_t B = t.B, rows = B * F, lr = B * Q;
     MDT_TRY(rscratch(r, rows, B));
@@ -535,8 +422,8 @@ extern "C" mdt_status mdt_resampler_backward(mdt_resampler* r, int32_t tape, con
         MDT_TRY(r_ln_bwd(r, grads, P.x_in, P.st_l, L.nl_w, L.nl_b, r->g_dlat, r->g_dx, 1, B, Q, s));
     }
     // latents were repeated over the batch; the time embedding was added (masked) to every token of its frame
-    LAUNCH(mdt_launch_colsum(r->g_dx, (int64_t)Q * D, (int)B, Q * D, grads + r->grad_off[rslot_of(r, r->latents)], 1, s));
-    LAUNCH(mdt_launch_time_emb_grad(r->g_dxf, t.has_mask ? t.mask : nullptr, grads + r->grad_off[rslot_of(r, r->tpe)],
+    LAUNCH(mdt_launch_colsum(r->g_dx, (int64_t)Q * D, (int)B, Q * D, r->grad_of(grads, r->latents), 1, s));
+    LAUNCH(mdt_launch_time_emb_grad(r->g_dxf, t.has_mask ? t.mask : nullptr, r->grad_of(grads, r->tpe),
                                     r->g_dnm /* free by now: B*T*D <= rows*D floats */, B, t.T, t.n, D, 1, s));
     if (d_x_f) HIP_TRY(hipMemcpyAsync(d_x_f, r->g_dxf, (size_t)rows * D * sizeof(float), hipMemcpyDeviceToDevice, s));
     return MDT_OK;

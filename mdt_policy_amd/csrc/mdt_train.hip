@@ -32,18 +32,12 @@ struct BlockTape {  // one transformer block; rows M = B*T
     float *st2, *h2, *u, *hid, *mo, *x3;                    // MLP half (mo: branch output before gate/dropout)
 };
 
-struct Tape {
-    bool in_use = false;
+struct Tape : TapeBase {
     bool has_decoder = false;
     int64_t B = 0, cap = 0;
     int lang = 0;  // 1: the goal went through lang_emb
     mdt_dropout drop = {0.f, 0.f, 0.f, 0.f, 0};
     float* buf = nullptr;
-    // stream of the last call that read or wrote the tape, and the event mdt_tape_release records on it: a later forward
-    // that reuses the buffers from ANOTHER stream waits for it (the release only marks the tape free on the host)
-    hipStream_t stream = nullptr;
-    hipEvent_t freed = nullptr;
-    bool freed_pending = false;
     // inputs
     float *tokens, *tokens2, *goal, *action, *noised, *sigma, *loss_part;
     float *p_pre = nullptr, *p_h = nullptr;  // proprio_emb: pre-activation and Mish output of its first layer (B, 2D)
@@ -218,7 +212,7 @@ void mdt_train_free(mdt_model* m) {
     mdt_train_state* t = m->train;
     for (Tape& tp : t->tapes) {
         (void)mdt_dev_free(tp.buf);
-        if (tp.freed) (void)hipEventDestroy(tp.freed);
+        tp.destroy_event();
     }
     (void)mdt_dev_free(t->scratch);
     if (t->scratch_done) (void)hipEventDestroy(t->scratch_done);
@@ -283,56 +277,24 @@ static void carve_tape(const mdt_model* m, Bump& b, Tape& t, int64_t B) {
 }
 
 static mdt_status acquire_tape(mdt_model* m, int64_t B, mdt_tape_id* id, hipStream_t s) {
-    mdt_train_state* ts = m->train;
-    int pick = -1;
-    for (size_t i = 0; i < ts->tapes.size(); ++i)
-        if (!ts->tapes[i].in_use && ts->tapes[i].cap >= B) { pick = (int)i; break; }
-    if (pick < 0)
-        for (size_t i = 0; i < ts->tapes.size(); ++i)
-            if (!ts->tapes[i].in_use) { pick = (int)i; break; }
-    if (pick < 0) {
-        if (ts->tapes.size() >= 16) return fail(MDT_ERR_STATE, "more than 16 tapes alive: release tapes after their backward");
-        ts->tapes.emplace_back();
-        pick = (int)ts->tapes.size() - 1;
-    }
-    Tape& t = ts->tapes[pick];
-    if (t.cap < B) {
-        if (t.buf) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(mdt_dev_free(t.buf)); t.buf = nullptr; t.cap = 0; }
-        Bump count;
-        carve_tape(m, count, t, B);
-        HIP_TRY(mdt_dev_malloc((void**)&t.buf, count.off * sizeof(float)));
-        t.cap = B;
-    }
-    Bump real;
-    real.base = t.buf;
-    carve_tape(m, real, t, t.cap);
-    if (t.freed_pending && t.stream != s) HIP_TRY(hipStreamWaitEvent(s, t.freed, 0));  // its last reader ran elsewhere
-    t.freed_pending = false;
-    t.stream = s;
-    t.in_use = true;
+    MDT_TRY(mdt_tape_acquire(m->train->tapes, 16, "tapes", s, [&](const Tape& t) { return t.cap >= B; }, [&](Tape& t) {
+        return mdt_grow_carve(t.buf, t.cap, B, [&](Bump& b, int64_t cap) { carve_tape(m, b, t, cap); });
+    }, id));
+    Tape& t = m->train->tapes[*id];
     t.B = B;
     t.has_decoder = false;
-    *id = pick;
     return MDT_OK;
 }
 
 static mdt_status get_tape(mdt_model* m, mdt_tape_id id, Tape** out) {
     if (!m || !m->train) return fail(MDT_ERR_STATE, "training was not prepared (mdt_train_prepare)");
-    if (id < 0 || id >= (int)m->train->tapes.size() || !m->train->tapes[id].in_use)
-        return fail(MDT_ERR_INVALID_ARG, "invalid or released tape %d", id);
-    *out = &m->train->tapes[id];
-    return MDT_OK;
+    return mdt_tape_get(m->train->tapes, id, "tape", out);
 }
 
 extern "C" mdt_status mdt_tape_release(mdt_model* m, mdt_tape_id id) {
     Tape* t;
     MDT_TRY(get_tape(m, id, &t));
-    // the backward that last read the tape may still be in flight on its stream: leave a marker there for the next user
-    if (!t->freed) HIP_TRY(hipEventCreateWithFlags(&t->freed, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(t->freed, t->stream));
-    t->freed_pending = true;
-    t->in_use = false;
-    return MDT_OK;
+    return t->release();
 }
 
 static void carve_scratch(const mdt_model* m, Bump& b, mdt_train_state* ts, int64_t B) {
@@ -380,17 +342,7 @@ static void carve_scratch(const mdt_model* m, Bump& b, mdt_train_state* ts, int6
 
 static mdt_status reserve_scratch(mdt_model* m, int64_t B) {
     mdt_train_state* ts = m->train;
-    if (B > ts->scratch_cap) {
-        if (ts->scratch) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(mdt_dev_free(ts->scratch)); ts->scratch = nullptr; }
-        Bump count;
-        carve_scratch(m, count, ts, B);
-        HIP_TRY(mdt_dev_malloc((void**)&ts->scratch, count.off * sizeof(float)));
-        ts->scratch_cap = B;
-    }
-    Bump real;
-    real.base = ts->scratch;
-    carve_scratch(m, real, ts, ts->scratch_cap);
-    return MDT_OK;
+    return mdt_grow_carve(ts->scratch, ts->scratch_cap, B, [&](Bump& b, int64_t cap) { carve_scratch(m, b, ts, cap); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -690,9 +642,7 @@ static mdt_dropout effective_dropout(const mdt_dropout* d) {
 static mdt_status check_ready(mdt_model* m) {
     if (!m) return fail(MDT_ERR_INVALID_ARG, "null handle");
     if (!m->train) return fail(MDT_ERR_STATE, "training was not prepared: call mdt_train_prepare() and upload the parameters");
-    for (const Slot& sl : m->slots)
-        if (!sl.loaded) return fail(MDT_ERR_NOT_LOADED, "parameter '%s' was not loaded after mdt_train_prepare()", sl.name.c_str());
-    return MDT_OK;
+    return mdt_check_loaded(m->slots, "parameter", "was not loaded after mdt_train_prepare()");
 }
 
 extern "C" mdt_status mdt_train_encode_fwd(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,

@@ -10,22 +10,7 @@ from __future__ import annotations
 
 import torch
 
-
-class _Tape:
-    """Owns one library tape: released after the backward, or when the autograd node dies without one."""
-
-    def __init__(self, eng, tape_id: int):
-        self.eng, self.id = eng, tape_id
-
-    def release(self):
-        if self.id is not None:
-            try:
-                self.eng.tape_release(self.id)
-            except Exception:
-                pass  # handle already destroyed
-            self.id = None
-
-    __del__ = release
+from ..networks._handle import LibTape
 
 
 def _needs(*ts):
@@ -38,7 +23,7 @@ class HipDiffusionLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, eng, state, tok, tok2, goal, action, noise, sigma, drop, names, *params):
         loss, mo, cx, tape = eng.train_loss_fwd(state, tok, tok2, goal, action, noise, sigma, drop)
-        ctx.eng, ctx.tape = eng, _Tape(eng, tape)
+        ctx.eng, ctx.tape = eng, LibTape(tape, eng.tape_release)
         ctx.named = list(zip(names, params))
         ctx.unused = eng.unused_goal_embedder(state, eng.cfg.arch == 0)  # MDT.forward always uses goal_emb
         ctx.inputs = (tok, tok2, goal)
@@ -122,7 +107,7 @@ class HipDiffusionLossStaged(torch.autograd.Function):
     def forward(ctx, run, link, tok, tok2, goal, action, noise, sigma, drop, state, *params):
         eng = run.eng
         loss, mo, cx, tape = eng.train_loss_fwd(state, tok, tok2, goal, action, noise, sigma, drop)
-        run.tape = _Tape(eng, tape)
+        run.tape = LibTape(tape, eng.tape_release)
         ctx.run = run
         ctx.inputs = (tok, tok2, goal)
         ctx.mark_non_differentiable(mo)
@@ -168,7 +153,7 @@ class HipContextOnly(torch.autograd.Function):
     @staticmethod
     def forward(ctx, eng, state, tok, tok2, goal, honour, drop, sigma, names, *params):
         cx, tape = eng.train_encode_fwd(state, tok, tok2, goal, honour, drop, sigma)
-        ctx.eng, ctx.tape = eng, _Tape(eng, tape)
+        ctx.eng, ctx.tape = eng, LibTape(tape, eng.tape_release)
         ctx.named = list(zip(names, params))
         ctx.unused = eng.unused_goal_embedder(state, honour)
         ctx.inputs = (tok, tok2, goal)

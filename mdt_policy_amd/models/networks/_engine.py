@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib
+from ._handle import grad_layout
 
 
 import os
@@ -295,11 +296,8 @@ class HipEngine:
         with torch.cuda.device(self.device):
             _lib.call(self.lib.mdt_train_prepare, self.handle)
         self._uploaded.clear()  # every parameter is re-uploaded so that its transposed image exists
+        self._grad_layout, self._grad_numel = grad_layout(self.lib, "mdt", self.handle)
         n = self.lib.mdt_param_count(self.handle)
-        self._grad_layout = {self.lib.mdt_param_name(self.handle, i).decode():
-                             (int(self.lib.mdt_grad_offset(self.handle, i)), int(self.lib.mdt_param_numel(self.handle, i)))
-                             for i in range(n)}
-        self._grad_numel = int(self.lib.mdt_grad_numel(self.handle))
         # the stage of the staged backward (mdt_train_loss_bwd_stage) that completes each parameter's gradient
         self._n_stages = int(self.lib.mdt_train_loss_bwd_stages(self.handle))
         self._param_stage = {self.lib.mdt_param_name(self.handle, i).decode(): int(self.lib.mdt_train_param_stage(self.handle, i))
