@@ -186,6 +186,87 @@ mdt_status mdt_sample_ddim_dev(mdt_model *m, const float *tokens, const float *t
                                int32_t modality, const float *x_T, const float *sigmas_dev, int32_t n_steps,
                                int64_t batch, float *out, float *ctx_out, void *stream);
 
+/* The other samplers of the reference's dispatch table (mdtv_agent.py:593-658) as ONE enqueue each, like mdt_sample_ddim:
+ * a plan kernel derives the sampler's denoiser evaluations and a table of per-evaluation coefficients from the schedule,
+ * then every evaluation is one decoder pass whose action-head kernel applies the sampler update and embeds the next input.
+ * Schedule assumption (what every get_sigmas_* guarantees): all n_steps + 1 levels are > 0 except the final one, which is
+ * 0.  The Python loops branch on sigmas[i + 1] == 0 (and on sigma_down == 0 for the ancestral samplers); the native
+ * call takes the branch at the last step and only there, so its launch sequence depends on the kind and n_steps alone. */
+typedef enum {
+    MDT_SAMPLER_EULER = 0,              /* sample_euler              (s_churn, s_tmin, s_tmax, s_noise) */
+    MDT_SAMPLER_EULER_ANCESTRAL = 1,    /* sample_euler_ancestral    (eta)                              */
+    MDT_SAMPLER_HEUN = 2,               /* sample_heun               (s_churn, s_tmin, s_tmax, s_noise) */
+    MDT_SAMPLER_DPM_2 = 3,              /* sample_dpm_2              (s_churn, s_tmin, s_tmax, s_noise) */
+    MDT_SAMPLER_DPM_2_ANCESTRAL = 4,    /* sample_dpm_2_ancestral    (eta)                              */
+    MDT_SAMPLER_LMS = 5,                /* sample_lms                (order 1..4)                       */
+    MDT_SAMPLER_DPMPP_2S = 6,           /* sample_dpmpp_2s                                              */
+    MDT_SAMPLER_DPMPP_2S_ANCESTRAL = 7, /* sample_dpmpp_2s_ancestral (eta, s_noise)                     */
+    MDT_SAMPLER_DPMPP_2M = 8,           /* sample_dpmpp_2m / sample_dpmpp_2_with_lms                    */
+    MDT_SAMPLER_DPMPP_SDE = 9,          /* sample_dpmpp_sde          (eta, s_noise, r)                  */
+    MDT_SAMPLER_COUNT = 10
+} mdt_sampler_kind;
+
+/* The samplers' scalar parameters; a field a kind does not take is ignored.  Python's defaults: eta 1, s_churn 0,
+ * s_tmin 0, s_tmax +inf, s_noise 1, r 0.5, order 4. */
+typedef struct mdt_sampler_params {
+    float eta, s_churn, s_tmin, s_tmax, s_noise, r;
+    int32_t order;
+} mdt_sampler_params;
+
+enum { MDT_SAMPLER_MAX_STEPS = 64, MDT_SAMPLER_MAX_EVALS = 2 * MDT_SAMPLER_MAX_STEPS, MDT_SAMPLER_NREG = 10 };
+/* Registers of the per-element update, in coefficient order: X the state, Y this evaluation's input, D its denoised output,
+ * d = (Y - D) / sigma, H0..H3 the history slots (H0 the newest), N0 / N1 this evaluation's noise rows. */
+enum { MDT_R_X = 0, MDT_R_Y = 1, MDT_R_D = 2, MDT_R_DD = 3, MDT_R_H0 = 4, MDT_R_N0 = 8, MDT_R_N1 = 9 };
+enum { MDT_PUSH_NONE = 0, MDT_PUSH_D = 1, MDT_PUSH_DD = 2 };
+
+/* One denoiser evaluation of a plan (32 words).  The head of this evaluation computes, per element,
+ *     X' = sum_k cx[k] R[k]                      (the new state; the sampler's output after the last evaluation)
+ *     Y' = cy[NREG] X' + sum_k cy[k] R[k]        (the next evaluation's input, embedded with c_in(sigma_next))
+ * and then pushes D or d into H0 (older slots move down one; the oldest is dropped) when `push` says so. */
+typedef struct mdt_sampler_eval {
+    float sigma;                     /* the denoiser's sigma (c_in / c_skip / c_out and the conditioning row)          */
+    float sigma_next;                /* the next evaluation's sigma; 0 after the last                                 */
+    float cx[MDT_SAMPLER_NREG];
+    float cy[MDT_SAMPLER_NREG + 1];
+    int32_t push;                    /* MDT_PUSH_*                                                                    */
+    int32_t noise[2];                /* rows of the noise buffer read as N0 / N1, -1 = none                           */
+    int32_t draws;                   /* noise rows the Python loop draws from this evaluation up to the next one      */
+    int32_t step;                    /* the sampler step this evaluation belongs to                                   */
+    int32_t pad[4];
+} mdt_sampler_eval;
+
+typedef struct mdt_sampler_plan_t {
+    int32_t n_evals, n_noise;        /* evaluations; noise rows the Python loop draws (the rows the call reads)        */
+    int32_t y0_noise;                /* the first input is Y_0 = x_T + y0_cn * N[y0_noise] (-1: Y_0 = x_T)             */
+    float y0_cn;
+    int32_t y0_draws;                /* noise rows the Python loop draws before the first evaluation                   */
+    int32_t pad[3];
+    mdt_sampler_eval e[MDT_SAMPLER_MAX_EVALS];
+} mdt_sampler_plan_t;
+
+/* Host helper (no GPU work): the plan mdt_sample would build for this kind, parameter set and HOST schedule (the device
+ * runs the same routine; libm and the device's math functions may differ in the last place). */
+mdt_status mdt_sampler_plan(int32_t kind, const mdt_sampler_params *params, const float *sigmas_host, int32_t n_steps,
+                            mdt_sampler_plan_t *plan);
+
+/* sample_<kind>(model, state, action, goal, sigmas, ...) as ONE enqueue (see mdt_sampler_kind).
+ *   params : host struct (NULL: Python's defaults)
+ *   noise  : NULL or (n_noise, B, Ta, A) device noise in the Python loop's draw order (plan.n_noise rows: randn_like draws
+ *            times nothing -- s_noise is applied by the call); required when the noise can matter: s_churn > 0 for euler /
+ *            heun / dpm_2, eta != 0 for the ancestral kinds and dpmpp_sde.  n_noise: rows available, at least plan.n_noise
+ *            (mdt_sample) or the structural maximum (mdt_sample_dev: n for euler / heun / dpm_2 / dpmpp_2s_ancestral, n - 1
+ *            for euler_ancestral / dpm_2_ancestral, 2 (n - 1) for dpmpp_sde with eta != 0; rows beyond the plan's are unread).
+ *   ctx_out: optional (B, Te, d): what the Python loop leaves in latent_encoder_emb.
+ * Arguments are checked before anything is enqueued.  Capture-safe; mdt_sample_dev reads its schedule at replay time. */
+mdt_status mdt_sample(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                      const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_host,
+                      int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out, float *ctx_out,
+                      void *stream);
+mdt_status mdt_sample_dev(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                          const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_dev,
+                          int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out, float *ctx_out,
+                          void *stream);
+
 /* GCDenoiser.loss(state, action, goal, noise, sigma) forward value, eval mode (reference
  * score_wrappers.py:45-63): noised = a + n*sigma; F = inner(noised*c_in); target = (a - c_skip*noised)/c_out;
  * loss = mean((F - target)^2) over all B*Ta*A elements.  loss_out: 1 float (device); model_output: (B,Ta,A). */

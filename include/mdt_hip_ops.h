@@ -27,7 +27,8 @@ extern "C" {
 
 enum { MDT_ACT_NONE = 0, MDT_ACT_GELU = 1, MDT_ACT_MISH = 2, MDT_ACT_SILU = 3,
        MDT_ACT_SWIGLU = 4 /* only as mdt_linear_bwd_args.dx_act: the layer below is a SwishGLU, dX has 2K columns */ };
-enum { MDT_HEAD_DENOISED = 0, MDT_HEAD_DDIM = 1, MDT_HEAD_RAW = 2 };
+enum { MDT_HEAD_DENOISED = 0, MDT_HEAD_DDIM = 1, MDT_HEAD_RAW = 2,
+       MDT_HEAD_PLAN = 3 /* a sampler plan's update (mdt_sample; internal: needs the plan operands, not mdt_op_head) */ };
 
 /* Number of floats of the fragment-packed image of an (N, K) Linear weight (N, K multiples of 16). */
 int64_t mdt_op_packed_numel(int64_t N, int64_t K);

@@ -69,6 +69,30 @@ class HeadArgs(C.Structure):
         ("ba", C.c_void_p), ("no_ln", C.c_int32), ("y_parts", C.c_int32), ("y_part_stride", C.c_int64)]
 
 
+class SamplerParams(C.Structure):
+    """mdt_sampler_params (include/mdt_hip.h)."""
+    _fields_ = [(n, C.c_float) for n in ("eta", "s_churn", "s_tmin", "s_tmax", "s_noise", "r")] + [("order", C.c_int32)]
+
+
+SAMPLER_MAX_STEPS, SAMPLER_MAX_EVALS, SAMPLER_NREG = 64, 128, 10
+# mdt_sampler_kind: gc_sampling function name (without "sample_") -> kind
+SAMPLER_KIND = {"euler": 0, "euler_ancestral": 1, "heun": 2, "dpm_2": 3, "dpm_2_ancestral": 4, "lms": 5, "dpmpp_2s": 6,
+                "dpmpp_2s_ancestral": 7, "dpmpp_2m": 8, "dpmpp_2_with_lms": 8, "dpmpp_sde": 9}
+
+
+class SamplerEval(C.Structure):
+    """mdt_sampler_eval (include/mdt_hip.h): one denoiser evaluation of a sampler plan."""
+    _fields_ = [("sigma", C.c_float), ("sigma_next", C.c_float), ("cx", C.c_float * SAMPLER_NREG),
+                ("cy", C.c_float * (SAMPLER_NREG + 1)), ("push", C.c_int32), ("noise", C.c_int32 * 2), ("draws", C.c_int32),
+                ("step", C.c_int32), ("pad", C.c_int32 * 4)]
+
+
+class SamplerPlan(C.Structure):
+    """mdt_sampler_plan_t (include/mdt_hip.h)."""
+    _fields_ = [("n_evals", C.c_int32), ("n_noise", C.c_int32), ("y0_noise", C.c_int32), ("y0_cn", C.c_float),
+                ("y0_draws", C.c_int32), ("pad", C.c_int32 * 3), ("e", SamplerEval * SAMPLER_MAX_EVALS)]
+
+
 class LnTrainArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("b", C.c_void_p), ("mod", C.c_void_p), ("mod_stride", C.c_int64),
                 ("shift_off", C.c_int32), ("scale_off", C.c_int32), ("rows_per_sample", C.c_int32),
@@ -172,6 +196,11 @@ SYMBOLS = [
     ("mdt_forward", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _I64, _VP, _VP, _VP]),
     ("mdt_sample_ddim", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(C.c_float), _I32, _I64, _VP, _VP, _VP]),
     ("mdt_sample_ddim_dev", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _I64, _VP, _VP, _VP]),
+    ("mdt_sample", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, _VP, _I32,
+                          _I64, _VP, _VP, _VP]),
+    ("mdt_sample_dev", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), _VP, _I32, _VP, _I32, _I64, _VP,
+                              _VP, _VP]),
+    ("mdt_sampler_plan", _I32, [_I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, C.POINTER(SamplerPlan)]),
     ("mdt_op_trace_mlp", None, [_I32]),
     ("mdt_op_trace_mlp_read", _I32, [_VP, _I32]),
     ("mdt_op_trace_mlp_read_empty", _I32, [_VP, _I32]),
@@ -335,6 +364,27 @@ def load() -> C.CDLL:
 def check(status: int) -> None:
     if status != 0:
         raise MDTHipError(status, load().mdt_last_error().decode("utf-8", "replace"))
+
+
+def sampler_params(**kw) -> SamplerParams:
+    """mdt_sampler_params with Python's defaults for every field not given (gc_sampling.py signatures)."""
+    p = dict(eta=1., s_churn=0., s_tmin=0., s_tmax=float("inf"), s_noise=1., r=0.5, order=4)
+    unknown = set(kw) - set(p)
+    if unknown:
+        raise TypeError(f"unknown sampler parameter(s) {sorted(unknown)}")
+    p.update(kw)
+    return SamplerParams(*(float(p[k]) for k in ("eta", "s_churn", "s_tmin", "s_tmax", "s_noise", "r")), int(p["order"]))
+
+
+def sampler_plan(kind, sigmas, **params) -> SamplerPlan:
+    """mdt_sampler_plan: the plan mdt_sample builds for this sampler (a name of SAMPLER_KIND or an mdt_sampler_kind),
+    parameter set and host schedule (n_steps + 1 levels), computed on the host."""
+    kind = SAMPLER_KIND[kind] if isinstance(kind, str) else int(kind)
+    sig = [float(v) for v in sigmas]
+    arr = (C.c_float * len(sig))(*sig)
+    plan = SamplerPlan()
+    check(load().mdt_sampler_plan(kind, C.byref(sampler_params(**params)), arr, len(sig) - 1, C.byref(plan)))
+    return plan
 
 
 def call(fn, *args) -> None:

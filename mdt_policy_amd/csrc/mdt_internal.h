@@ -116,6 +116,25 @@ struct mdt_sched_arg { float s[MDT_SCHED_MAX + 1]; };
 hipError_t mdt_launch_sample_prep(const float* sigmas_dev, const float* sigmas_host, int n_steps, float* steps, const float* freqs,
                                   float* sig_e, int D, const float* x, float sd, const float* Wa, const float* ba, float* y, int M,
                                   int A, hipStream_t s);
+// the other samplers' once-per-call work (mdt_kernels.hip: k_sampler_plan + k_sampler_first): the plan of mdt_sampler_plan.h
+// built on the device, the sigma embeddings of every evaluation (sig_e == nullptr: none), the first input Y_0 -> y0 (M, A), the
+// four history slots hist (4, M, A) zeroed, and Y_0's action embedding -> y
+hipError_t mdt_launch_sampler_prep(const float* sigmas_dev, const float* sigmas_host, int n_steps, int kind,
+                                   const mdt_sampler_params& prm, mdt_sampler_plan_t* plan, const float* freqs, float* sig_e,
+                                   int D, const float* x, const float* noise, int n_noise, float* y0, float* hist, float sd, const float* Wa,
+                                   const float* ba, float* y, int M, int A, hipStream_t s);
+// operands of the head's plan epilogue (MDT_HEAD_PLAN): mdt_head_args.x is the evaluation's input Y, .out receives X'
+struct mdt_head_plan {
+    const mdt_sampler_eval* e;  // this evaluation's row of the plan (device)
+    const float* xs;            // (M, A) the state X
+    float* hist;                // (4, M, A) history slots H0..H3
+    const float* noise;         // (n_noise, M, A) or nullptr (every noise operand reads as 0)
+    float* y_out;               // (M, A) receives Y' (nullptr after the last evaluation; may alias mdt_head_args.x)
+    int64_t nel;                // M * A
+    int32_t n_noise;            // rows of `noise`: a plan row at or beyond it reads as 0 (the device plan is never trusted
+                                // to stay inside the caller's buffer)
+};
+hipError_t mdt_launch_head_plan(const mdt_head_args& a, const mdt_head_plan& pl, hipStream_t s);
 hipError_t mdt_launch_action_embed(const float* x, const float* sigma, int64_t sstride, float sd, const float* Wa,
                                    const float* ba, float* y, int M, int A, int D, int rps, hipStream_t s);
 hipError_t mdt_launch_head(const mdt_head_args& a, hipStream_t s);

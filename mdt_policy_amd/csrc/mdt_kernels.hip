@@ -31,6 +31,7 @@
 
 #define MDT_TILES_TIMING_OWNER  // this translation unit owns the -DMDT_DEBUG_TIMING stamp buffer
 #include "mdt_tiles.h"  // the tile bodies
+#include "mdt_sampler_plan.h"
 #include "mdt_tall.h"  // the tall LDS-staged GEMM body (round 4)
 #include "mdt_ws.h"    // the weight-stationary GEMM body (round 5)
 #include "mdt_mlp_split.h"  // the fused MLP launch in the three-way bf16 split form (round 6)
@@ -1526,6 +1527,85 @@ hipError_t mdt_launch_sample_prep(const float* sigmas_dev, const float* sigmas_h
 }
 
 // ------------------------------------------------------------------------------------------------
+// The once-per-call scalar work of the other samplers (mdt_sample): ONE workgroup builds the plan (mdt_sampler_plan.h) from
+// the schedule -- by value from the host or read in place from the device -- in LDS, copies it out and writes the sinusoidal
+// sigma embeddings of every evaluation (k_sigma_emb's arithmetic).  k_sampler_first then forms the first input
+// Y_0 = x_T + y0_cn N[y0_noise], zeroes the history slots and embeds Y_0 with c_in(sigma of evaluation 0).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_sampler_plan(const float* __restrict__ sig_dev, mdt_sched_arg sv, int n_steps, int kind,
+                                                      mdt_sampler_params prm, mdt_sampler_plan_t* __restrict__ plan,
+                                                      const float* __restrict__ freqs, float* __restrict__ sig_e, int D) {
+    __shared__ float ss[MDT_SCHED_MAX + 1];
+    __shared__ mdt_sampler_plan_t sp;
+    __shared__ float lms[4 * MDT_SCHED_MAX];
+    for (int i = threadIdx.x; i <= n_steps; i += blockDim.x) ss[i] = sig_dev ? sig_dev[i] : sv.s[i];
+    __syncthreads();
+    const bool is_lms = kind == MDT_SAMPLER_LMS;
+    // the LMS quadratures (double) one step per thread: serially they were 85 us of a 20-step call
+    if (is_lms && threadIdx.x < n_steps) mdt_lms_step_coeffs(prm.order, ss, threadIdx.x, lms + 4 * threadIdx.x);
+    if (is_lms) __syncthreads();
+    if (threadIdx.x == 0) mdt_build_sampler_plan(kind, prm, ss, n_steps, &sp, is_lms ? lms : nullptr);  // host checked the args
+    __syncthreads();
+    const int E = sp.n_evals;
+    const int words = (int)((sizeof(mdt_sampler_plan_t) - (MDT_SAMPLER_MAX_EVALS - E) * sizeof(mdt_sampler_eval)) / 4);
+    for (int w = threadIdx.x; w < words; w += blockDim.x) ((int32_t*)plan)[w] = ((const int32_t*)&sp)[w];
+    if (!sig_e) return;
+    const int half = D >> 1;
+    for (int idx = threadIdx.x; idx < E * half; idx += blockDim.x) {
+        const int r = idx / half, j = idx % half;
+        const float ang = (logf(sp.e[r].sigma) / 4.0f) * freqs[j];
+        sig_e[(int64_t)r * D + j] = sinf(ang);
+        sig_e[(int64_t)r * D + half + j] = cosf(ang);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_sampler_first(const mdt_sampler_plan_t* __restrict__ plan, const float* __restrict__ x,
+                                                       const float* __restrict__ noise, int n_noise, float* __restrict__ y0,
+                                                       float* __restrict__ hist, float sd, const float* __restrict__ WaT,
+                                                       const float* __restrict__ ba, float* __restrict__ y, int M, int A, int D) {
+    const int n4 = D >> 2;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)M * n4) return;
+    const int m = (int)(idx / n4), n = (int)(idx % n4) * 4;
+    const int64_t nel = (int64_t)M * A;
+    const float cin = edm_c_in(plan->e[0].sigma, sd);
+    const int row = (noise && plan->y0_noise < n_noise) ? plan->y0_noise : -1;  // a row outside the buffer reads as 0
+    const float cn = plan->y0_cn;
+    f32x4 acc = *(const f32x4*)(ba + n);
+    for (int c = 0; c < A; ++c) {
+        const int64_t k = (int64_t)m * A + c;
+        float v = x[k];
+        if (row >= 0 && cn != 0.f) v = v + noise[row * nel + k] * cn;
+        if (n == 0) {
+            y0[k] = v;
+            for (int h = 0; h < 4; ++h) hist[h * nel + k] = 0.f;
+        }
+        const float xv = v * cin;
+        const f32x4 w = *(const f32x4*)(WaT + (int64_t)c * D + n);
+        acc.x = fmaf(xv, w.x, acc.x); acc.y = fmaf(xv, w.y, acc.y);
+        acc.z = fmaf(xv, w.z, acc.z); acc.w = fmaf(xv, w.w, acc.w);
+    }
+    *(f32x4*)(y + (int64_t)m * D + n) = acc;
+}
+
+hipError_t mdt_launch_sampler_prep(const float* sigmas_dev, const float* sigmas_host, int n_steps, int kind,
+                                   const mdt_sampler_params& prm, mdt_sampler_plan_t* plan, const float* freqs, float* sig_e,
+                                   int D, const float* x, const float* noise, int n_noise, float* y0, float* hist, float sd, const float* Wa,
+                                   const float* ba, float* y, int M, int A, hipStream_t s) {
+    if (n_steps < 1 || n_steps > MDT_SCHED_MAX || (!sigmas_dev) == (!sigmas_host) || (D & 3)) return hipErrorInvalidValue;
+    mdt_sched_arg sv;
+    memset(&sv, 0, sizeof sv);
+    if (sigmas_host) memcpy(sv.s, sigmas_host, (size_t)(n_steps + 1) * sizeof(float));
+    hipLaunchKernelGGL(k_sampler_plan, dim3(1), dim3(256), 0, s, sigmas_dev, sv, n_steps, kind, prm, plan, freqs, sig_e, D);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int64_t n = (int64_t)M * (D / 4);
+    hipLaunchKernelGGL(k_sampler_first, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, plan, x, noise, n_noise, y0, hist, sd, Wa, ba,
+                       y, M, A, D);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // action head: decoder LN -> action_pred -> EDM combine -> (DDIM update) -> (next step's embedding)
 // one wave per action-token row; A <= 16
 // ------------------------------------------------------------------------------------------------
@@ -1535,6 +1615,32 @@ __global__ __launch_bounds__(256) void k_head(mdt_head_args a, const float* __re
     const int base = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (base >= a.M) return;  // wave-uniform
     head_rows<AMAX, false, XP, 1>(a, base, threadIdx.x & 63, zeros);
+}
+
+// the same head with a sampler plan's update (MDT_HEAD_PLAN, mdt_tiles.h: head_rows' PLAN epilogue)
+template <int AMAX, int XP>
+__global__ __launch_bounds__(256) void k_head_plan(mdt_head_args a, mdt_head_plan pl, const float* __restrict__ zeros) {
+    const int base = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (base >= a.M) return;  // wave-uniform
+    head_rows<AMAX, false, XP, 1, true>(a, base, threadIdx.x & 63, zeros, &pl);
+}
+
+hipError_t mdt_launch_head_plan(const mdt_head_args& a, const mdt_head_plan& pl, hipStream_t s) {
+    hipError_t e = ensure_zeros();
+    if (e != hipSuccess) return e;
+    const int grid = (a.M + 3) / 4;
+    if (a.y_parts > 1) {
+        if (a.A > 8 || a.y_parts > 4) return hipErrorInvalidValue;
+        switch (a.y_parts) {
+            case 2: hipLaunchKernelGGL((k_head_plan<8, 2>), dim3(grid), dim3(256), 0, s, a, pl, g_zeros); break;
+            case 3: hipLaunchKernelGGL((k_head_plan<8, 3>), dim3(grid), dim3(256), 0, s, a, pl, g_zeros); break;
+            default: hipLaunchKernelGGL((k_head_plan<8, 4>), dim3(grid), dim3(256), 0, s, a, pl, g_zeros); break;
+        }
+        return hipGetLastError();
+    }
+    if (a.A <= 8) hipLaunchKernelGGL((k_head_plan<8, 1>), dim3(grid), dim3(256), 0, s, a, pl, g_zeros);
+    else hipLaunchKernelGGL((k_head_plan<16, 1>), dim3(grid), dim3(256), 0, s, a, pl, g_zeros);
+    return hipGetLastError();
 }
 
 hipError_t mdt_launch_head(const mdt_head_args& a, hipStream_t s) {

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "mdt_internal.h"
+#include "mdt_sampler_plan.h"
 
 // ------------------------------------------------------------------------------------------------
 // error plumbing (shared with mdt_resampler.hip through mdt_internal.h)
@@ -136,6 +137,7 @@ static View encoder_view(const mdt_model* m) {
 }
 
 static const int MAX_STEPS = MDT_SCHED_MAX;  // (a host schedule travels in k_sample_prep's kernel arguments)
+static const int MAX_EVALS = MDT_SAMPLER_MAX_EVALS;  // denoiser evaluations of one mdt_sample call
 
 // Parameter map: called twice (count pass with base == nullptr, then with the allocated arena).
 static void build_params(mdt_model* m, Bump& b, bool fill_slots) {
@@ -568,7 +570,7 @@ static mdt_status check_loaded(const mdt_model* m) { return mdt_check_loaded(m->
 // ------------------------------------------------------------------------------------------------
 static void carve_ws(mdt_model* m, Bump& b, int64_t B) {
     const int64_t Re = (int64_t)m->Te * B, Ra = (int64_t)m->Ta * B, Rx = std::max(Re, Ra);
-    const int64_t Rm = std::max<int64_t>(B, MAX_STEPS);
+    const int64_t Rm = std::max<int64_t>(B, MAX_EVALS);  // conditioning rows: one per sample or per sampler evaluation
     const int D = m->D;
     m->h_enc = b.take(Re * D);
     m->qkv = b.take(Rx * 3 * D);
@@ -589,6 +591,9 @@ static void carve_ws(mdt_model* m, Bump& b, int64_t B) {
     m->steps = b.take(MAX_STEPS * 4);
     m->sigs = b.take(MAX_STEPS + 1);
     m->loss_part = b.take(MDT_LOSS_PARTS);
+    m->ybuf = b.take(Ra * m->A);
+    m->hist = b.take(4 * Ra * m->A);
+    m->plan = (mdt_sampler_plan_t*)b.take((sizeof(mdt_sampler_plan_t) + 3) / 4);
     if (m->xfold) {
         const int64_t np = (int64_t)4 * m->H;  // every head padded to 4 context tokens (fragment order, k_xattn_fold)
         m->xU = b.take((size_t)m->Ld * B * np * D);
@@ -604,7 +609,7 @@ extern "C" mdt_status mdt_reserve(mdt_model* m, int64_t max_batch) {
     m->cached_batch = 0;
     MDT_TRY(mdt_grow_carve(m->ws, m->cap, max_batch, [&](Bump& b, int64_t cap) { carve_ws(m, b, cap); }));
     if (m->cond == COND_NOISE)  // the "scale" half of every [c | ones] row; the c half is rewritten per call
-        HIP_TRY(hipMemsetD32((hipDeviceptr_t)m->cmod, 0x3f800000u, (size_t)std::max<int64_t>(max_batch, MAX_STEPS) * 2 * m->D));
+        HIP_TRY(hipMemsetD32((hipDeviceptr_t)m->cmod, 0x3f800000u, (size_t)std::max<int64_t>(max_batch, MAX_EVALS) * 2 * m->D));
     ++m->ws_generation;
     return MDT_OK;
 }
@@ -1209,6 +1214,130 @@ extern "C" mdt_status mdt_sample_ddim_dev(mdt_model* m, const float* tokens, con
     return sample_ddim_impl(m, tokens, tokens2, goal, modality, x_T, nullptr, sigmas_dev, n_steps, batch, out, ctx_out, stream);
 }
 
+// run_head with a sampler plan's update (MDT_HEAD_PLAN).  The MLP head embeds the next input Y' (pl.y_out) in a launch of
+// its own, as run_head embeds the DDIM state.
+static mdt_status run_head_plan(mdt_model* m, mdt_head_args h, const mdt_head_plan& pl, float* scratch, const float* sigma_next,
+                                hipStream_t s) {
+    if (m->HP == 0) {
+        LAUNCH(mdt_launch_head_plan(h, pl, s));
+        return MDT_OK;
+    }
+    const int D = m->D, HP = m->HP;
+    float* ln = scratch;
+    float* hh = scratch + (int64_t)h.M * D;
+    LAUNCH(mdt_launch_layernorm(h.y, m->dec_ln_w, m->dec_ln_b, ln, h.M, D, s));
+    mdt_gemm_args g = gemm_args(ln, D, m->head0, hh, HP, h.M);
+    g.act = MDT_ACT_GELU;
+    LAUNCH(mdt_launch_gemm(g, s));
+    float* y_next = h.y_next;
+    h.y = hh; h.D = HP; h.no_ln = 1; h.y_next = nullptr;
+    LAUNCH(mdt_launch_head_plan(h, pl, s));
+    if (y_next)
+        LAUNCH(mdt_launch_action_embed(pl.y_out, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next, h.M, m->A, D,
+                                       m->Ta, s));
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_sampler_plan(int32_t kind, const mdt_sampler_params* params, const float* sigmas_host,
+                                       int32_t n_steps, mdt_sampler_plan_t* plan) {
+    if (!sigmas_host || !plan) return fail(MDT_ERR_INVALID_ARG, "mdt_sampler_plan: null argument");
+    const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
+    switch (mdt_build_sampler_plan(kind, p, sigmas_host, n_steps, plan)) {
+        case MDT_PLAN_OK: return MDT_OK;
+        case MDT_PLAN_BAD_KIND: return fail(MDT_ERR_INVALID_ARG, "mdt_sampler_plan: unknown sampler kind %d", kind);
+        case MDT_PLAN_BAD_STEPS: return fail(MDT_ERR_INVALID_ARG, "mdt_sampler_plan: n_steps must be 1..%d", MDT_SAMPLER_MAX_STEPS);
+        default: return fail(MDT_ERR_INVALID_ARG, "mdt_sampler_plan: lms order must be 1..4");
+    }
+}
+
+// sigmas_host or sigmas_dev (exactly one non-null): the n_steps + 1 noise levels.  The structure of sample_ddim_impl: the plan
+// and the sigma embeddings of every evaluation (one launch), the first input, the conditioning rows of every evaluation (their
+// GEMMs ride in the encoder's launches), the encoder and cross K/V once, then one decoder pass + plan head per evaluation.
+static mdt_status sample_plan_impl(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
+                                   const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas,
+                                   const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch,
+                                   float* out, float* ctx_out, void* stream) {
+    if (!m || !x_T || (!sigmas && !sigmas_dev) || !out || batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_sample: bad argument");
+    const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
+    int E = 0, rows = 0;
+    switch (mdt_plan_shape(kind, p, n_steps, &E, &rows)) {
+        case MDT_PLAN_OK: break;
+        case MDT_PLAN_BAD_KIND: return fail(MDT_ERR_INVALID_ARG, "mdt_sample: unknown sampler kind %d", kind);
+        case MDT_PLAN_BAD_STEPS: return fail(MDT_ERR_INVALID_ARG, "mdt_sample: n_steps must be 1..%d", MDT_SAMPLER_MAX_STEPS);
+        default: return fail(MDT_ERR_INVALID_ARG, "mdt_sample: lms order must be 1..4");
+    }
+    if (sigmas) {  // a host schedule: the loop's exact draw count (a device schedule: the structural maximum)
+        static thread_local mdt_sampler_plan_t hp;
+        mdt_build_sampler_plan(kind, p, sigmas, n_steps, &hp);
+        rows = hp.n_noise;
+    }
+    if (!noise && mdt_plan_needs_noise(kind, p))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_sample: this sampler and parameter set need the noise buffer (%d rows)", rows);
+    if (noise && n_noise < rows)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_sample: the noise buffer holds %d rows, the sampler reads %d", n_noise, rows);
+    if (misaligned(x_T) || misaligned(out) || misaligned(noise))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_sample: pointers must be 16-byte aligned");
+    if (m->A > 16) return fail(MDT_ERR_UNSUPPORTED, "mdt_sample: action_dim must be <= 16");
+    hipStream_t s = (hipStream_t)stream;
+    const int honour = m->cfg.arch == MDT_ARCH_MDTV;
+    const bool per_step_ctx = m->cond == COND_TOKEN;  // sigma is a context token: the encoder runs per evaluation
+    MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));  // before anything is enqueued
+    MDT_TRY(check_loaded(m));
+    MDT_TRY(mdt_reserve(m, batch));
+    const View V = decoder_view(m, 0);
+    const int M = (int)(batch * m->Ta);
+    const int64_t nel = (int64_t)M * m->A;
+    mdt_sampler_eval* ev = m->plan->e;
+    LAUNCH(mdt_launch_sampler_prep(sigmas_dev, sigmas_dev ? nullptr : sigmas, n_steps, kind, p, m->plan, m->freqs,
+                                   per_step_ctx ? nullptr : m->sig_e, m->D, x_T, noise, noise ? n_noise : 0, m->ybuf, m->hist,
+                                   m->cfg.sigma_data,
+                                   m->Wa, m->ba, V.y, M, m->A, s));
+    const int stride = (int)(sizeof(mdt_sampler_eval) / sizeof(float));
+    mdt_status ms = run_modulation(m, &ev[0].sigma, stride, E, s, true, !per_step_ctx);  // one conditioning row per evaluation
+    if (ms == MDT_OK && !per_step_ctx) ms = run_encode(m, tokens, tokens2, goal, modality, honour, batch, nullptr, 0, ctx_out, s);
+    if (ms != MDT_OK) { mdt_gemm_side_drop(); return ms; }
+    LAUNCH(mdt_gemm_side_flush(s));
+    for (int e = 0; e < E; ++e) {
+        const bool last = e == E - 1;
+        if (per_step_ctx)  // the Python loop leaves the LAST evaluation's context in latent_encoder_emb
+            MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, honour, batch, &ev[e].sigma, 0, last ? ctx_out : nullptr, s));
+        Stream fin;
+        const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
+        MDT_TRY(run_decoder_blocks(m, V, batch, cond_row(m, e), 0, s, head_sums ? &fin : nullptr));
+        mdt_head_args h = head_args(m, V.y, batch, m->ybuf, &ev[e].sigma, 0, last ? out : m->xbuf, MDT_HEAD_PLAN);
+        if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
+        if (!last) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
+        mdt_head_plan pl;
+        pl.e = &ev[e];
+        pl.xs = e == 0 ? x_T : m->xbuf;
+        pl.hist = m->hist;
+        pl.noise = noise;
+        pl.y_out = last ? nullptr : m->ybuf;
+        pl.nel = nel;
+        pl.n_noise = noise ? n_noise : 0;
+        MDT_TRY(run_head_plan(m, h, pl, V.hid, last ? nullptr : &ev[e].sigma_next, s));
+    }
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_sample(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
+                                 const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas_host,
+                                 int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, float* out, float* ctx_out,
+                                 void* stream) {
+    if (!sigmas_host) return fail(MDT_ERR_INVALID_ARG, "mdt_sample: null sigmas");
+    return sample_plan_impl(m, tokens, tokens2, goal, modality, x_T, kind, params, sigmas_host, nullptr, n_steps, noise, n_noise,
+                            batch, out, ctx_out, stream);
+}
+
+extern "C" mdt_status mdt_sample_dev(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                     int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
+                                     const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
+                                     int64_t batch, float* out, float* ctx_out, void* stream) {
+    if (!sigmas_dev) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dev: null sigmas");
+    return sample_plan_impl(m, tokens, tokens2, goal, modality, x_T, kind, params, nullptr, sigmas_dev, n_steps, noise, n_noise,
+                            batch, out, ctx_out, stream);
+}
+
 extern "C" mdt_status mdt_loss_fwd(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                    int32_t modality, const float* action, const float* noise, const float* sigma,
                                    int64_t batch, float* loss_out, float* model_output, float* ctx_out, void* stream) {
@@ -1429,7 +1558,7 @@ extern "C" mdt_status mdt_op_layernorm(const float* in, const float* w, const fl
 }
 
 extern "C" mdt_status mdt_op_head(const mdt_head_args* a, void* stream) {
-    if (!a || !a->y || !a->out || a->A < 1 || a->A > 16 || a->D % 4 || a->D > 512)
+    if (!a || !a->y || !a->out || a->A < 1 || a->A > 16 || a->D % 4 || a->D > 512 || a->mode == MDT_HEAD_PLAN)
         return fail(MDT_ERR_INVALID_ARG, "mdt_op_head: bad argument");
     LAUNCH(mdt_launch_head(*a, (hipStream_t)stream));
     return MDT_OK;

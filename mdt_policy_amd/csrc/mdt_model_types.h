@@ -90,6 +90,8 @@ struct mdt_model {
     int64_t cap = 0;
     int64_t ws_generation = 0;  // bumped whenever the workspace is (re)allocated: captured HIP graphs hold its addresses
     float *h_enc, *qkv, *att, *hid, *ctx, *kvx, *y, *qx, *sig_e, *sig_t, *sig_c, *mod, *xbuf, *noised, *Fbuf, *steps, *sigs, *loss_part;
+    float *ybuf, *hist;          // mdt_sample: the evaluation's input Y (Ra, A) and the history slots H0..H3 (4, Ra, A)
+    mdt_sampler_plan_t* plan;    // mdt_sample: the plan the device builds (mdt_sampler_plan.h)
     float* cmod = nullptr;  // COND_NOISE: rows of [c | ones(D)], read as (shift, scale) by the LayerNorm prologue
     int64_t cached_batch = 0;  // batch of the context currently cached by mdt_encode (0 = none)
     // collapsed cross-attention (k_xattn_fold / k_xattn_apply): folded projections per sample and decoder block

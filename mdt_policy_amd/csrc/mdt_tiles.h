@@ -1402,8 +1402,12 @@ __device__ __forceinline__ float edm_c_in(float sigma, float sd) { return 1.0f /
 // RW = rows per wave: 2 when the fragments of action_pred / action_emb a wave fetches should be used twice, 1 in
 // k_head (twice the waves, half the dot products per wave: the launch is a latency chain -- B = 256 sampler call 4.712 -> 4.686 ms,
 // four rows per wave 4.705).
-template <int AMAX, bool COH, int XP = 1, int RW = 2>
-__device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int lane, const float* __restrict__ zeros) {
+// PLAN: the MDT_HEAD_PLAN epilogue -- the per-element update of a sampler plan (mdt_sampler_plan.h) on the registers X, Y, D,
+// d = (Y - D) / sigma, H0..H3, N0, N1; writes X' to a.out, Y' to pl->y_out, shifts the history and embeds Y' (not X') as the next
+// input.  The instantiations without it are the DDIM / denoiser heads as they were.
+template <int AMAX, bool COH, int XP = 1, int RW = 2, bool PLAN = false>
+__device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int lane, const float* __restrict__ zeros,
+                                          const mdt_head_plan* pl = nullptr) {
     const int n4 = a.D >> 2;
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     const ActLd<COH> LY(a.y), LX(a.x);
@@ -1464,6 +1468,7 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
         coef = a.step[1];
         sig_next = a.step[2];
     }
+    if constexpr (PLAN) sig_next = pl->e->sigma_next;
     // ---- LayerNorm of the rows ----
     const float inv_d = 1.0f / (float)a.D;
     if constexpr (XP > 1) {
@@ -1527,6 +1532,52 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
             res[r * AMAX + c] = o;
         }
     }
+    float resy[PLAN ? RW * AMAX : 1];
+    if constexpr (PLAN) {
+        // sampler plan update: X' = sum cx R, Y' = cy[NREG] X' + sum cy R; lane c stores column c
+        const mdt_sampler_eval& e = *pl->e;
+        float cx[MDT_SAMPLER_NREG], cy[MDT_SAMPLER_NREG + 1];
+#pragma unroll
+        for (int k = 0; k < MDT_SAMPLER_NREG; ++k) { cx[k] = e.cx[k]; cy[k] = e.cy[k]; }
+        cy[MDT_SAMPLER_NREG] = e.cy[MDT_SAMPLER_NREG];
+        const int push = e.push;
+        const int64_t nel = pl->nel;
+        const int nn = pl->noise != nullptr ? pl->n_noise : 0;  // rows outside [0, n_noise) read as 0
+        const float* n0 = (e.noise[0] >= 0 && e.noise[0] < nn) ? pl->noise + e.noise[0] * nel : nullptr;
+        const float* n1 = (e.noise[1] >= 0 && e.noise[1] < nn) ? pl->noise + e.noise[1] * nel : nullptr;
+#pragma unroll
+        for (int r = 0; r < RW; ++r)
+#pragma unroll
+            for (int c = 0; c < AMAX; ++c) {
+                const int64_t k = row[r] * a.A + min(c, a.A - 1);
+                float R[MDT_SAMPLER_NREG];
+                R[MDT_R_X] = pl->xs[k];
+                R[MDT_R_Y] = xin[r][c];
+                R[MDT_R_D] = res[r * AMAX + c];
+                R[MDT_R_DD] = (R[MDT_R_Y] - R[MDT_R_D]) / sigma[r];
+#pragma unroll
+                for (int h = 0; h < 4; ++h) R[MDT_R_H0 + h] = pl->hist[h * nel + k];
+                R[MDT_R_N0] = n0 != nullptr ? n0[k] : 0.f;
+                R[MDT_R_N1] = n1 != nullptr ? n1[k] : 0.f;
+                float xn = 0.f, yn = 0.f;
+#pragma unroll
+                for (int q = 0; q < MDT_SAMPLER_NREG; ++q) xn += cx[q] * R[q];
+                yn = cy[MDT_SAMPLER_NREG] * xn;
+#pragma unroll
+                for (int q = 0; q < MDT_SAMPLER_NREG; ++q) yn += cy[q] * R[q];
+                res[r * AMAX + c] = xn;
+                resy[r * AMAX + c] = yn;
+                if (c < a.A && lane == c && base + r < a.M) {
+                    if (pl->y_out != nullptr) pl->y_out[k] = yn;
+                    if (push != MDT_PUSH_NONE) {
+                        pl->hist[3 * nel + k] = R[MDT_R_H0 + 2];
+                        pl->hist[2 * nel + k] = R[MDT_R_H0 + 1];
+                        pl->hist[nel + k] = R[MDT_R_H0];
+                        pl->hist[k] = push == MDT_PUSH_D ? R[MDT_R_D] : R[MDT_R_DD];
+                    }
+                }
+            }
+    }
     // all lanes hold all results (xor-butterfly sums); lanes 0..A-1 store one each
 #pragma unroll
     for (int r = 0; r < RW; ++r)
@@ -1543,7 +1594,9 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
         for (int c = 0; c < AMAX; ++c)
 #pragma unroll
             for (int r = 0; r < RW; ++r) {
-                const float xv = c < a.A ? res[r * AMAX + c] * cin_next : 0.f;
+                float xv;
+                if constexpr (PLAN) xv = c < a.A ? resy[r * AMAX + c] * cin_next : 0.f;
+                else xv = c < a.A ? res[r * AMAX + c] * cin_next : 0.f;
 #pragma unroll
                 for (int p = 0; p < 2; ++p) acc[r][p] += xv * wa[c][p];
             }

@@ -3,8 +3,10 @@
 ``sample_ddim`` -- the sampler MDT ships with (conf/model/mdtv_agent.yaml:14) -- runs as ONE call into
 libmdt_hip.so when ``model`` is this package's GCDenoiser and no Python hooks are requested: encoder and
 cross-attention K/V once, adaLN vectors of all steps once, the DDIM update fused into the action-head kernel.
-The other samplers keep the reference signatures and are host loops over ``model(state, x, goal, sigma)``
-(the HIP denoiser step) with the sigma-independent encoder hoisted out of the loop.
+The other fixed-step samplers (euler, heun, the ancestral ones, dpm_2, lms, dpmpp_2m / 2s / sde) run the same way --
+one call, ``GCDenoiser.sample_native`` -> mdt_sample -- under the same condition plus ``scaler=None``; otherwise, and for
+sample_dpm_fast / sample_dpm_adaptive, they are host loops over ``model(state, x, goal, sigma)`` (the HIP denoiser step)
+with the sigma-independent encoder hoisted out of the loop.
 
 Signatures follow the reference: ``sample_*(model, state, action, goal, sigmas, scaler=None, extra_args=None,
 callback=None, disable=None, ...)``.
@@ -19,6 +21,7 @@ import numpy as np
 import torch
 
 from . import utils
+from ... import _lib
 from .score_wrappers import GCDenoiser
 
 
@@ -155,7 +158,7 @@ def _graph_key(state, action, goal, sigmas):
                          for k, v in state.items())))
 
 
-def _graph_wanted(model, state, action, goal, sigmas) -> bool:
+def _graph_wanted(model, state, action, goal, sigmas, tag=None) -> bool:
     if action.device.type != "cuda" or model.inner_model.training or torch.cuda.is_current_stream_capturing():
         return False
     if _GRAPH_SAMPLER:
@@ -163,6 +166,8 @@ def _graph_wanted(model, state, action, goal, sigmas) -> bool:
     if _GRAPH_MODE != "auto" or action.shape[0] > _GRAPH_AUTO_MAX_BATCH:
         return False
     key = _graph_key(state, action, goal, sigmas)
+    if tag is not None:
+        key = (tag,) + key
     if key in model.__dict__.get("_graph_failed", ()):
         return False  # a capture of this call failed once: it stays eager
     seen = model.__dict__.setdefault("_graph_seen", {})
@@ -183,6 +188,78 @@ def _graphed(model, state, action, goal, sigmas):
     cache.append(gsamp)
     del cache[:-4]
     return gsamp(state, action, goal, sigmas)
+
+
+# ------------------------------------------------------------------------------------------------
+# The other samplers' native path (GCDenoiser.sample_native -> mdt_sample): the whole loop as one enqueue, under the condition
+# sample_ddim uses plus scaler=None (clip_output is not linear).  The noise is drawn here, by torch, with the shapes, count and
+# order of the host loop, so a seeded call gives the loop's result and leaves the generator where the loop leaves it.  The
+# plan the call builds assumes what every get_sigmas_* guarantees -- all levels > 0 but a final 0 -- which a host schedule is
+# checked for (else: the host loop); a device schedule is read in place, unchecked.
+# ------------------------------------------------------------------------------------------------
+def _native_ok(model, sigmas, scaler, callback, extra_args) -> bool:
+    if not isinstance(model, GCDenoiser) or callback is not None or extra_args or scaler is not None:
+        return False
+    n = len(sigmas) - 1
+    if n < 1 or n > _lib.SAMPLER_MAX_STEPS:
+        return False
+    if torch.is_tensor(sigmas) and sigmas.device.type == "cuda":
+        return True
+    sig = _host(sigmas)
+    return bool((sig[:-1] > 0).all()) and float(sig[-1]) == 0.0
+
+
+def _randn_rows(action, n):
+    """n draws of torch.randn_like(action), in order, as one (n, *action.shape) tensor (None for n = 0)."""
+    return torch.stack([torch.randn_like(action) for _ in range(n)]) if n else None
+
+
+def _sampled_rows(action, values):
+    """noise_sampler values (any device, broadcastable to action) as one (n, *action.shape) tensor."""
+    if not values:
+        return None
+    return torch.stack([torch.broadcast_to(v.to(device=action.device, dtype=action.dtype), action.shape) for v in values])
+
+
+def _ancestral_draws(sigmas, eta):
+    """randn draws of euler_ancestral / dpm_2_ancestral: one per step with sigma_down > 0 -- the loop's own test on a host schedule,
+    every step but the last on a device schedule (the schedule assumption; no read-back)."""
+    n = len(sigmas) - 1
+    if torch.is_tensor(sigmas) and sigmas.device.type == "cuda":
+        return n - 1
+    sig = _host(sigmas)
+    return sum(1 for i in range(n) if get_ancestral_step(sig[i], sig[i + 1], eta=eta)[0] > 0)
+
+
+def _graphed_native(model, kind, params, state, action, goal, sigmas, noise):
+    """One GraphedSampler per (kind, parameters, shapes, modality, state keys) of a model, kept on the model (at most four)."""
+    from .graphed import GraphedSampler
+    cache = model.__dict__.setdefault("_graphed_native", [])
+    for gsamp in cache:
+        if gsamp.matches_sampler(kind, params, state, action, goal, sigmas, noise):
+            return gsamp(state, action, goal, sigmas, noise=noise)
+    gsamp = GraphedSampler(model, kind, params, state, action, goal,
+                           sigmas if torch.is_tensor(sigmas) else torch.as_tensor(sigmas), noise)
+    cache.append(gsamp)
+    del cache[:-4]
+    return gsamp(state, action, goal, sigmas, noise=noise)
+
+
+def _run_native(kind, model, state, action, goal, sigmas, noise, **params):
+    """The native call, replayed as a HIP graph by sample_ddim's rule (rollout-sized batches from the third identical call)."""
+    if _graph_wanted(model, state, action, goal, sigmas, tag=(kind, tuple(sorted(params.items())))):
+        try:
+            return _graphed_native(model, kind, params, state, action, goal, sigmas, noise)
+        except Exception as exc:  # noqa: BLE001 -- as in sample_ddim: a failed capture leaves this call shape eager
+            if _GRAPH_SAMPLER:
+                raise
+            key = ((kind, tuple(sorted(params.items()))),) + _graph_key(state, action, goal, sigmas)
+            model.__dict__.setdefault("_graph_failed", set()).add(key)
+            model.__dict__.pop("_graphed_native", None)
+            import warnings
+            warnings.warn(f"mdt_policy_amd: HIP-graph capture of sample_{kind} failed ({exc!r}); this call shape stays eager")
+            torch.cuda.synchronize()
+    return model.sample_native(kind, state, action, goal, sigmas, noise=noise, **params)
 
 
 @torch.no_grad()
@@ -223,6 +300,9 @@ def sample_ddim(model, state, action, goal, sigmas, scaler=None, extra_args=None
 def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None,
                  s_churn=0., s_tmin=0., s_tmax=float('inf'), s_noise=1.):
     """Karras Algorithm 2 without the 2nd-order correction (reference gc_sampling.py:164-209)."""
+    if _native_ok(model, sigmas, scaler, callback, extra_args):
+        return _run_native("euler", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
+                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -247,6 +327,9 @@ def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=Non
 def sample_euler_ancestral(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None,
                            disable=None, eta=1.):
     """Euler steps to sigma_down plus fresh noise sigma_up (reference gc_sampling.py:213-252)."""
+    if _native_ok(model, sigmas, scaler, callback, extra_args):
+        noise = _randn_rows(action, _ancestral_draws(sigmas, eta))
+        return _run_native("euler_ancestral", model, state, action, goal, sigmas, noise, eta=eta)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -269,6 +352,9 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
                 s_churn=0., s_tmin=0., s_tmax=float('inf'), s_noise=1.):
     """Karras Algorithm 2 with Heun's trapezoidal correction; plain Euler on the final step to sigma = 0
     (reference gc_sampling.py:256-312)."""
+    if _native_ok(model, sigmas, scaler, callback, extra_args):
+        return _run_native("heun", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
+                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -299,6 +385,8 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
 @torch.no_grad()
 def sample_dpmpp_2m(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None):
     """DPM-Solver++(2M) multistep (reference gc_sampling.py:699-734)."""
+    if _native_ok(model, sigmas, scaler, callback, extra_args):
+        return _run_native("dpmpp_2m", model, state, action, goal, sigmas, None)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     old_denoised = None
@@ -323,6 +411,8 @@ def sample_dpmpp_2m(model, state, action, goal, sigmas, scaler=None, extra_args=
 def sample_dpmpp_2s(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None,
                     eta=1.):
     """DPM-Solver++(2S) single-step second order (reference gc_sampling.py:955-994)."""
+    if _native_ok(model, sigmas, scaler, callback, extra_args):
+        return _run_native("dpmpp_2s", model, state, action, goal, sigmas, None)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -349,6 +439,9 @@ def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=Non
                  s_churn=0., s_tmin=0., s_tmax=float('inf'), s_noise=1.):
     """DPM-Solver-2 flavoured midpoint steps (reference gc_sampling.py:315-371): derivative at sigma_hat, a second
     evaluation at the log-midpoint sigma, full step with the midpoint derivative; Euler on the last step."""
+    if _native_ok(model, sigmas, scaler, callback, extra_args):
+        return _run_native("dpm_2", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
+                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -380,6 +473,9 @@ def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=Non
 def sample_dpm_2_ancestral(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None,
                            disable=None, eta=1.):
     """Ancestral sampling with DPM-Solver-2 midpoint steps (reference gc_sampling.py:374-407)."""
+    if _native_ok(model, sigmas, scaler, callback, extra_args):
+        noise = _randn_rows(action, _ancestral_draws(sigmas, eta))
+        return _run_native("dpm_2_ancestral", model, state, action, goal, sigmas, noise, eta=eta)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -422,6 +518,8 @@ def linear_multistep_coeff(order, t, i, j):
 @torch.no_grad()
 def sample_lms(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None, order=4):
     """Linear multistep (Adams-Bashforth in sigma) sampler (reference gc_sampling.py:425-460)."""
+    if 1 <= order <= 4 and _native_ok(model, sigmas, scaler, callback, extra_args):
+        return _run_native("lms", model, state, action, goal, sigmas, None, order=order)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     sig_np = sig.numpy()
@@ -454,6 +552,14 @@ def sample_dpmpp_2_with_lms(model, state, action, goal, sigmas, scaler=None, ext
 def sample_dpmpp_2s_ancestral(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None,
                               disable=None, eta=1., s_noise=1., noise_sampler=None):
     """Ancestral sampling with DPM-Solver++(2S) steps (reference gc_sampling.py:864-907)."""
+    if _native_ok(model, sigmas, scaler, callback, extra_args):
+        n = len(sigmas) - 1
+        if noise_sampler is None:
+            noise = _randn_rows(action, n)  # default_noise_sampler: randn_like(action) per step
+        else:
+            sig = _host(sigmas)
+            noise = _sampled_rows(action, [noise_sampler(sig[i], sig[i + 1]) for i in range(n)])
+        return _run_native("dpmpp_2s_ancestral", model, state, action, goal, sigmas, noise, eta=eta, s_noise=s_noise)
     extra_args = {} if extra_args is None else extra_args
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
     sig = _host(sigmas)
@@ -783,6 +889,20 @@ def sample_dpmpp_sde(model, state, action, goal, sigmas, extra_args=None, callba
                      scaler=None, noise_sampler=None, r=1 / 2):
     """DPM-Solver++ (stochastic) (reference gc_sampling.py:737-790): a midpoint evaluation at s = t + r h, ancestral
     noise at both sub-steps from ``noise_sampler(sigma, sigma_next)`` (default: a torchsde Brownian tree)."""
+    if _native_ok(model, sigmas, scaler, callback, extra_args):
+        sig = _host(sigmas)  # the noise sampler takes host values (a device schedule is read back for it)
+        if noise_sampler is None:
+            noise_sampler = BrownianTreeNoiseSampler(action, sig[sig > 0].min(), sig.max())
+        values = []
+        for i in range(len(sig) - 2):  # the loop's calls, in its order
+            t, t_next = _t(sig[i]), _t(sig[i + 1])
+            s = t + (t_next - t) * r
+            if _f(get_ancestral_step(_sigma(t), _sigma(s), eta)[1]) != 0:
+                values.append(noise_sampler(_sigma(t), _sigma(s)))
+            if _f(get_ancestral_step(_sigma(t), _sigma(t_next), eta)[1]) != 0:
+                values.append(noise_sampler(_sigma(t), _sigma(t_next)))
+        return _run_native("dpmpp_sde", model, state, action, goal, sigmas, _sampled_rows(action, values), eta=eta,
+                           s_noise=s_noise, r=r)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     if noise_sampler is None:

@@ -41,6 +41,12 @@ class GraphedDDIM:
     def _engine(self):
         return self.model._engine(state=self._static_state)
 
+    def _run(self):
+        return self.model.sample_ddim(self._static_state, self._x, self._goal, self._sig)
+
+    def _extra_inputs(self, noise):
+        return [], []
+
     def _capture(self) -> None:
         model = self.model
         with torch.no_grad():
@@ -51,12 +57,12 @@ class GraphedDDIM:
             side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(side):  # warm-up on a side stream, as torch's graph capture wants it
                 for _ in range(2):
-                    model.sample_ddim(self._static_state, self._x, self._goal, self._sig)
+                    self._run()
             torch.cuda.current_stream(self.device).wait_stream(side)
             torch.cuda.synchronize(self.device)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out = model.sample_ddim(self._static_state, self._x, self._goal, self._sig)
+                out = self._run()
             self._graph, self._out = graph, out
             self._ctx = model.inner_model.latent_encoder_emb
             self._gen = int(eng.lib.mdt_ws_generation(eng.handle))
@@ -76,7 +82,8 @@ class GraphedDDIM:
         return set(state) == set(self._static_state)
 
     @torch.no_grad()
-    def __call__(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas=None, fresh: bool = True) -> torch.Tensor:
+    def __call__(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas=None, fresh: bool = True,
+                 noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Same result as ``model.sample_ddim(state, x_T, goal, sigmas)``, including ``inner_model.latent_encoder_emb``: both are
         fresh tensors the next call does not touch.  ``fresh=False`` hands out the graph's own static buffers instead (valid
         until the next call; one copy launch less)."""
@@ -96,6 +103,8 @@ class GraphedDDIM:
             if torch.is_tensor(v):
                 dst.append(v); src.append(state[k])
         dst += [self._x, self._goal]; src += [x_T, goal]
+        d2, s2 = self._extra_inputs(noise)
+        dst += d2; src += s2
         if sigmas is not None:
             # n + 1 floats: never skipped on identity -- a caller may rewrite its schedule tensor in place (same object, new values).
             # A HOST schedule (the reference's CPU default) is compared by value with the last one copied: equal -> nothing to do
@@ -127,3 +136,32 @@ class GraphedDDIM:
         both = torch.cat((self._out.reshape(-1), self._ctx.reshape(-1)))
         self.model.inner_model.latent_encoder_emb = both[n:].view(self._ctx.shape)
         return both[:n].view(self._out.shape)
+
+
+class GraphedSampler(GraphedDDIM):
+    """The same for one of the other samplers (``GCDenoiser.sample_native``): one graph per sampler kind, parameter set and
+    shapes.  The noise rows of a call (drawn by the caller in the Python loop's order) are copied into a static buffer with
+    the other inputs, so a replay consumes the same random stream as the eager call."""
+
+    def __init__(self, model, kind: str, params: dict, state: dict, x_T: torch.Tensor, goal: torch.Tensor,
+                 sigmas: torch.Tensor, noise: Optional[torch.Tensor]):
+        self.kind, self.params = kind, dict(params)
+        self._noise = None if noise is None else noise.detach().clone()
+        super().__init__(model, state, x_T, goal, sigmas)
+
+    def _run(self):
+        return self.model.sample_native(self.kind, self._static_state, self._x, self._goal, self._sig, noise=self._noise,
+                                        **self.params)
+
+    def _extra_inputs(self, noise):
+        if (noise is None) != (self._noise is None) or (noise is not None and noise.shape != self._noise.shape):
+            raise ValueError("GraphedSampler: the noise rows must have the captured shape")
+        return ([], []) if noise is None else ([self._noise], [noise])
+
+    def matches_sampler(self, kind: str, params: dict, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
+                        noise: Optional[torch.Tensor]) -> bool:
+        if kind != self.kind or params != self.params or (noise is None) != (self._noise is None):
+            return False
+        if noise is not None and noise.shape != self._noise.shape:
+            return False
+        return self.matches(state, x_T, goal, sigmas)

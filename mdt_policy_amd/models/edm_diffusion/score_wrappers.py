@@ -183,6 +183,20 @@ class GCDenoiser(nn.Module):
         return self._engine(state=state).denoise_vjp(state, action, im._goals(goal, False), sigma, v)
 
     @torch.no_grad()
+    def sample_native(self, kind, state, action, goal, sigmas, noise=None, **params):
+        """One of the other samplers (``kind``: 'euler', 'heun', 'dpmpp_2m', ... -- the gc_sampling function name without
+        'sample_') as one enqueue on the current stream (mdt_sample).  ``noise``: None or (n_noise, B, Ta, A) in the Python loop's
+        draw order -- raw randn draws (euler / heun / dpm_2 / the ancestral samplers) or the noise_sampler values (dpmpp_2s_ancestral,
+        dpmpp_sde); s_noise and the step scales are applied inside.  ``params``: the sampler's keyword arguments (eta, s_churn,
+        s_tmin, s_tmax, s_noise, r, order)."""
+        from ... import _lib
+        im = self.inner_model
+        out, ctx = self._engine(state=state).sample_native(_lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action,
+                                                           im._goals(goal, False), sigmas, noise)
+        im.latent_encoder_emb = ctx
+        return out
+
+    @torch.no_grad()
     def sample_ddim(self, state, action, goal, sigmas):
         """Whole DDIM loop (reference gc_sampling.py:922-951) as one enqueue on the current stream."""
         im = self.inner_model

@@ -271,6 +271,35 @@ class HipEngine:
                                             _ptr(x_), arr, n, B, _ptr(out), _ptr(ctx), self._stream())
         return out, ctx
 
+    def sample_native(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
+                      noise: Optional[torch.Tensor] = None):
+        """One call of another sampler (mdt_sample / mdt_sample_dev): ``kind`` an mdt_sampler_kind, ``params`` an
+        _lib.SamplerParams, ``noise`` None or (n_noise, B, Ta, A) in the Python loop's draw order.  Like sample_ddim, a device
+        schedule is read in place (no copy, no synchronisation)."""
+        self.sync_params()
+        tok, tok2, B = self._tokens(state)
+        g, x_ = self._goal(goal, B), self._in(x_T, (B, self.Ta, self.A))
+        nz = None if noise is None else self._in(noise, (-1, B, self.Ta, self.A))
+        n_noise = 0 if nz is None else nz.shape[0]
+        out = torch.empty((B, self.Ta, self.A), device=self.device, dtype=torch.float32)
+        ctx = torch.empty((B, self.Te, self.D), device=self.device, dtype=torch.float32)
+        if torch.is_tensor(sigmas) and sigmas.device.type == "cuda":
+            sig = self._in(sigmas.reshape(-1))
+            n = sig.numel() - 1
+            self._keep = (sig, nz)  # the kernels that read them are only enqueued: keep the tensors alive
+            self.ctx_generation += 1
+            _lib.call(self.lib.mdt_sample_dev, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_),
+                      int(kind), C.byref(params), _ptr(sig), n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), self._stream())
+            return out, ctx
+        sig = [float(v) for v in (sigmas.detach().tolist() if torch.is_tensor(sigmas) else sigmas)]
+        n = len(sig) - 1
+        arr = (C.c_float * len(sig))(*sig)
+        self._keep = nz
+        self.ctx_generation += 1
+        _lib.call(self.lib.mdt_sample, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_), int(kind),
+                  C.byref(params), arr, n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), self._stream())
+        return out, ctx
+
     def loss_fwd(self, state: dict, action: torch.Tensor, goal: torch.Tensor, noise: torch.Tensor, sigma: torch.Tensor):
         self.sync_params()
         tok, tok2, B = self._tokens(state)
