@@ -36,7 +36,8 @@ typedef enum {
     MDT_ERR_UNSUPPORTED = 2,   /* configuration outside what the HIP path implements (stated in msg) */
     MDT_ERR_NOT_LOADED = 3,    /* a parameter needed by the call was never loaded                    */
     MDT_ERR_HIP = 4,           /* a HIP runtime call failed (message carries hipGetErrorString)      */
-    MDT_ERR_STATE = 5          /* call sequence error, e.g. mdt_denoise_cached() without mdt_encode()  */
+    MDT_ERR_STATE = 5,         /* call sequence error, e.g. mdt_denoise_cached() without mdt_encode()  */
+    MDT_ERR_NUMERIC = 6        /* an adaptive sampler stopped: NaN error or step size, or a step that no longer moves */
 } mdt_status;
 
 enum { MDT_ARCH_MDTV = 0, MDT_ARCH_MDT = 1 };
@@ -189,7 +190,8 @@ mdt_status mdt_sample_ddim_dev(mdt_model *m, const float *tokens, const float *t
 /* The other samplers of the reference's dispatch table (mdtv_agent.py:593-658) as ONE enqueue each, like mdt_sample_ddim:
  * a plan kernel derives the sampler's denoiser evaluations and a table of per-evaluation coefficients from the schedule,
  * then every evaluation is one decoder pass whose action-head kernel applies the sampler update and embeds the next input.
- * Schedule assumption (what every get_sigmas_* guarantees): all n_steps + 1 levels are > 0 except the final one, which is
+ * Schedule: n_steps + 1 levels, except for MDT_SAMPLER_DPM_FAST (below).  Schedule assumption (what every get_sigmas_*
+ * guarantees): all n_steps + 1 levels are > 0 except the final one, which is
  * 0.  The Python loops branch on sigmas[i + 1] == 0 (and on sigma_down == 0 for the ancestral samplers); the native
  * call takes the branch at the last step and only there, so its launch sequence depends on the kind and n_steps alone. */
 typedef enum {
@@ -203,8 +205,13 @@ typedef enum {
     MDT_SAMPLER_DPMPP_2S_ANCESTRAL = 7, /* sample_dpmpp_2s_ancestral (eta, s_noise)                     */
     MDT_SAMPLER_DPMPP_2M = 8,           /* sample_dpmpp_2m / sample_dpmpp_2_with_lms                    */
     MDT_SAMPLER_DPMPP_SDE = 9,          /* sample_dpmpp_sde          (eta, s_noise, r)                  */
-    MDT_SAMPLER_COUNT = 10
+    MDT_SAMPLER_DPM_FAST = 10,          /* sample_dpm_fast           (eta, s_noise)                     */
+    MDT_SAMPLER_COUNT = 11
 } mdt_sampler_kind;
+/* MDT_SAMPLER_DPM_FAST: the schedule is the two levels {sigma_max, sigma_min}, both > 0, and n_steps is the evaluation count
+ * n (1..MDT_SAMPLER_MAX_EVALS): n // 3 + 1 solver steps uniform in t = -ln(sigma).  eta != 0 needs sigma_min < sigma_max
+ * (as the Python function: no ancestral noise when sampling in reverse).  Violations give MDT_ERR_INVALID_ARG on a host
+ * schedule; a device schedule is read at replay time and not checked. */
 
 /* The samplers' scalar parameters; a field a kind does not take is ignored.  Python's defaults: eta 1, s_churn 0,
  * s_tmin 0, s_tmax +inf, s_noise 1, r 0.5, order 4. */
@@ -232,7 +239,8 @@ typedef struct mdt_sampler_eval {
     int32_t noise[2];                /* rows of the noise buffer read as N0 / N1, -1 = none                           */
     int32_t draws;                   /* noise rows the Python loop draws from this evaluation up to the next one      */
     int32_t step;                    /* the sampler step this evaluation belongs to                                   */
-    int32_t pad[4];
+    float t;                         /* DPM-Solver kinds: t = -ln(sigma) of this evaluation as the Python loop has it   */
+    int32_t pad[3];
 } mdt_sampler_eval;
 
 typedef struct mdt_sampler_plan_t {
@@ -244,8 +252,9 @@ typedef struct mdt_sampler_plan_t {
     mdt_sampler_eval e[MDT_SAMPLER_MAX_EVALS];
 } mdt_sampler_plan_t;
 
-/* Host helper (no GPU work): the plan mdt_sample would build for this kind, parameter set and HOST schedule (the device
- * runs the same routine; libm and the device's math functions may differ in the last place). */
+/* Host helper (no GPU work): the plan mdt_sample would build for this kind, parameter set and HOST schedule (n_steps + 1
+ * levels, or the two of MDT_SAMPLER_DPM_FAST; the device runs the same routine; libm and the device's math functions may
+ * differ in the last place). */
 mdt_status mdt_sampler_plan(int32_t kind, const mdt_sampler_params *params, const float *sigmas_host, int32_t n_steps,
                             mdt_sampler_plan_t *plan);
 
@@ -255,7 +264,8 @@ mdt_status mdt_sampler_plan(int32_t kind, const mdt_sampler_params *params, cons
  *            times nothing -- s_noise is applied by the call); required when the noise can matter: s_churn > 0 for euler /
  *            heun / dpm_2, eta != 0 for the ancestral kinds and dpmpp_sde.  n_noise: rows available, at least plan.n_noise
  *            (mdt_sample) or the structural maximum (mdt_sample_dev: n for euler / heun / dpm_2 / dpmpp_2s_ancestral, n - 1
- *            for euler_ancestral / dpm_2_ancestral, 2 (n - 1) for dpmpp_sde with eta != 0; rows beyond the plan's are unread).
+ *            for euler_ancestral / dpm_2_ancestral, 2 (n - 1) for dpmpp_sde with eta != 0, n // 3 + 1 for dpm_fast with
+ *            eta != 0; rows beyond the plan's are unread).  dpm_fast: eta != 0 and s_noise != 0 need the noise buffer.
  *   ctx_out: optional (B, Te, d): what the Python loop leaves in latent_encoder_emb.
  * Arguments are checked before anything is enqueued.  Capture-safe; mdt_sample_dev reads its schedule at replay time. */
 mdt_status mdt_sample(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
@@ -266,6 +276,40 @@ mdt_status mdt_sample_dev(mdt_model *m, const float *tokens, const float *tokens
                           const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_dev,
                           int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out, float *ctx_out,
                           void *stream);
+
+/* sample_dpm_adaptive (eta = 0): DPM-Solver-12 / -23 with the PID step-size control of _StepControl, as ONE blocking call.
+ * Every attempted step runs its 2 or 3 denoiser evaluations; the head of the last one writes both the order-k ("high") and the
+ * order-(k-1) ("low") result, one small kernel writes per-workgroup partial sums of the scaled error, and the host reads them
+ * back (one synchronisation per attempt), sums them in double in a fixed order and updates the controller.  A rejected step
+ * leaves the state as it was.  Returns MDT_ERR_STATE on a capturing stream (nothing enqueued) and MDT_ERR_NUMERIC where the
+ * Python loop would spin forever (NaN error or step size, or s + h == s in fp32). */
+typedef struct mdt_dpm_adaptive_params {
+    int32_t order;                   /* 2 or 3                                                                          */
+    double rtol, atol, h_init, pcoeff, icoeff, dcoeff, accept_safety;  /* Python's defaults: 0.05 0.0078 0.05 0 1 0 0.81   */
+} mdt_dpm_adaptive_params;
+typedef struct mdt_dpm_adaptive_info {
+    int32_t steps, nfe, n_accept, n_reject;  /* the Python loop's info dict                                             */
+} mdt_dpm_adaptive_info;
+/* _StepControl's state (gc_sampling.py): step size h, filter weights, log inverse error history */
+typedef struct mdt_dpm_control {
+    double h, w[3], safety, eps, hist[3];
+    int32_t started, pad;
+} mdt_dpm_control;
+enum { MDT_DPM_REJECT = 0, MDT_DPM_ACCEPT = 1, MDT_DPM_STOP = 2 };
+
+/* Host helpers (no GPU work).  mdt_dpm_control_init / _update: the controller the call runs (update returns MDT_DPM_* in
+ * *decision; STOP where the error or the new h is NaN).  mdt_dpm_adaptive_plan: the evaluations of one attempted step from
+ * s to t (t = -ln sigma) at `order`; the last evaluation's cx is the order-k combine, its cy the order-(k-1) one. */
+mdt_status mdt_dpm_control_init(mdt_dpm_control *c, double h, double pcoeff, double icoeff, double dcoeff, double order,
+                                double accept_safety);
+mdt_status mdt_dpm_control_update(mdt_dpm_control *c, float error, int32_t *decision);
+mdt_status mdt_dpm_adaptive_plan(int32_t order, float s, float t, mdt_sampler_plan_t *plan);
+
+/* params: NULL = Python's defaults (order 3).  out (B, Ta, A), ctx_out optional (B, Te, d), info optional (host). */
+mdt_status mdt_sample_dpm_adaptive(mdt_model *m, const float *tokens, const float *tokens2, const float *goal,
+                                   int32_t modality, const float *x_T, float sigma_min, float sigma_max,
+                                   const mdt_dpm_adaptive_params *params, int64_t batch, float *out, float *ctx_out,
+                                   mdt_dpm_adaptive_info *info, void *stream);
 
 /* GCDenoiser.loss(state, action, goal, noise, sigma) forward value, eval mode (reference
  * score_wrappers.py:45-63): noised = a + n*sigma; F = inner(noised*c_in); target = (a - c_skip*noised)/c_out;

@@ -77,20 +77,40 @@ class SamplerParams(C.Structure):
 SAMPLER_MAX_STEPS, SAMPLER_MAX_EVALS, SAMPLER_NREG = 64, 128, 10
 # mdt_sampler_kind: gc_sampling function name (without "sample_") -> kind
 SAMPLER_KIND = {"euler": 0, "euler_ancestral": 1, "heun": 2, "dpm_2": 3, "dpm_2_ancestral": 4, "lms": 5, "dpmpp_2s": 6,
-                "dpmpp_2s_ancestral": 7, "dpmpp_2m": 8, "dpmpp_2_with_lms": 8, "dpmpp_sde": 9}
+                "dpmpp_2s_ancestral": 7, "dpmpp_2m": 8, "dpmpp_2_with_lms": 8, "dpmpp_sde": 9, "dpm_fast": 10}
 
 
 class SamplerEval(C.Structure):
     """mdt_sampler_eval (include/mdt_hip.h): one denoiser evaluation of a sampler plan."""
     _fields_ = [("sigma", C.c_float), ("sigma_next", C.c_float), ("cx", C.c_float * SAMPLER_NREG),
                 ("cy", C.c_float * (SAMPLER_NREG + 1)), ("push", C.c_int32), ("noise", C.c_int32 * 2), ("draws", C.c_int32),
-                ("step", C.c_int32), ("pad", C.c_int32 * 4)]
+                ("step", C.c_int32), ("t", C.c_float), ("pad", C.c_int32 * 3)]
 
 
 class SamplerPlan(C.Structure):
     """mdt_sampler_plan_t (include/mdt_hip.h)."""
     _fields_ = [("n_evals", C.c_int32), ("n_noise", C.c_int32), ("y0_noise", C.c_int32), ("y0_cn", C.c_float),
                 ("y0_draws", C.c_int32), ("pad", C.c_int32 * 3), ("e", SamplerEval * SAMPLER_MAX_EVALS)]
+
+
+class DpmAdaptiveParams(C.Structure):
+    """mdt_dpm_adaptive_params (include/mdt_hip.h)."""
+    _fields_ = [("order", C.c_int32)] + [(n, C.c_double) for n in ("rtol", "atol", "h_init", "pcoeff", "icoeff", "dcoeff",
+                                                                   "accept_safety")]
+
+
+class DpmAdaptiveInfo(C.Structure):
+    """mdt_dpm_adaptive_info (include/mdt_hip.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("steps", "nfe", "n_accept", "n_reject")]
+
+
+class DpmControl(C.Structure):
+    """mdt_dpm_control (include/mdt_hip.h): _StepControl's state."""
+    _fields_ = [("h", C.c_double), ("w", C.c_double * 3), ("safety", C.c_double), ("eps", C.c_double),
+                ("hist", C.c_double * 3), ("started", C.c_int32), ("pad", C.c_int32)]
+
+
+DPM_REJECT, DPM_ACCEPT, DPM_STOP = 0, 1, 2
 
 
 class LnTrainArgs(C.Structure):
@@ -201,6 +221,11 @@ SYMBOLS = [
     ("mdt_sample_dev", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), _VP, _I32, _VP, _I32, _I64, _VP,
                               _VP, _VP]),
     ("mdt_sampler_plan", _I32, [_I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, C.POINTER(SamplerPlan)]),
+    ("mdt_sample_dpm_adaptive", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.c_float, C.c_float, C.POINTER(DpmAdaptiveParams), _I64,
+                                       _VP, _VP, C.POINTER(DpmAdaptiveInfo), _VP]),
+    ("mdt_dpm_control_init", _I32, [C.POINTER(DpmControl)] + [C.c_double] * 6),
+    ("mdt_dpm_control_update", _I32, [C.POINTER(DpmControl), C.c_float, C.POINTER(C.c_int32)]),
+    ("mdt_dpm_adaptive_plan", _I32, [_I32, C.c_float, C.c_float, C.POINTER(SamplerPlan)]),
     ("mdt_op_trace_mlp", None, [_I32]),
     ("mdt_op_trace_mlp_read", _I32, [_VP, _I32]),
     ("mdt_op_trace_mlp_read_empty", _I32, [_VP, _I32]),
@@ -376,15 +401,48 @@ def sampler_params(**kw) -> SamplerParams:
     return SamplerParams(*(float(p[k]) for k in ("eta", "s_churn", "s_tmin", "s_tmax", "s_noise", "r")), int(p["order"]))
 
 
-def sampler_plan(kind, sigmas, **params) -> SamplerPlan:
+def sampler_plan(kind, sigmas, n_steps=None, **params) -> SamplerPlan:
     """mdt_sampler_plan: the plan mdt_sample builds for this sampler (a name of SAMPLER_KIND or an mdt_sampler_kind),
-    parameter set and host schedule (n_steps + 1 levels), computed on the host."""
+    parameter set and host schedule (n_steps + 1 levels; dpm_fast: {sigma_max, sigma_min} and ``n_steps`` evaluations),
+    computed on the host."""
     kind = SAMPLER_KIND[kind] if isinstance(kind, str) else int(kind)
     sig = [float(v) for v in sigmas]
     arr = (C.c_float * len(sig))(*sig)
     plan = SamplerPlan()
-    check(load().mdt_sampler_plan(kind, C.byref(sampler_params(**params)), arr, len(sig) - 1, C.byref(plan)))
+    n = len(sig) - 1 if n_steps is None else int(n_steps)
+    check(load().mdt_sampler_plan(kind, C.byref(sampler_params(**params)), arr, n, C.byref(plan)))
     return plan
+
+
+def dpm_adaptive_params(order=3, rtol=0.05, atol=0.0078, h_init=0.05, pcoeff=0., icoeff=1., dcoeff=0.,
+                        accept_safety=0.81) -> DpmAdaptiveParams:
+    """mdt_dpm_adaptive_params with sample_dpm_adaptive's defaults."""
+    return DpmAdaptiveParams(int(order), *(float(v) for v in (rtol, atol, h_init, pcoeff, icoeff, dcoeff, accept_safety)))
+
+
+def dpm_adaptive_plan(order, s, t) -> SamplerPlan:
+    """mdt_dpm_adaptive_plan: the evaluations of one attempted adaptive step from s to t (t = -ln sigma), on the host."""
+    plan = SamplerPlan()
+    check(load().mdt_dpm_adaptive_plan(int(order), float(s), float(t), C.byref(plan)))
+    return plan
+
+
+class DpmController:
+    """mdt_dpm_control_init / _update: the step-size controller mdt_sample_dpm_adaptive runs, on the host."""
+
+    def __init__(self, h, pcoeff, icoeff, dcoeff, order, accept_safety):
+        self.c = DpmControl()
+        check(load().mdt_dpm_control_init(C.byref(self.c), h, pcoeff, icoeff, dcoeff, order, accept_safety))
+
+    @property
+    def h(self) -> float:
+        return self.c.h
+
+    def update(self, error) -> int:
+        """DPM_ACCEPT, DPM_REJECT or DPM_STOP for the scaled error of the step just tried (taken as fp32)."""
+        d = C.c_int32()
+        check(load().mdt_dpm_control_update(C.byref(self.c), float(error), C.byref(d)))
+        return d.value
 
 
 def call(fn, *args) -> None:

@@ -123,6 +123,15 @@ hipError_t mdt_launch_sampler_prep(const float* sigmas_dev, const float* sigmas_
                                    const mdt_sampler_params& prm, mdt_sampler_plan_t* plan, const float* freqs, float* sig_e,
                                    int D, const float* x, const float* noise, int n_noise, float* y0, float* hist, float sd, const float* Wa,
                                    const float* ba, float* y, int M, int A, hipStream_t s);
+// k_sampler_first alone (the adaptive DPM-Solver's per-attempt first input, from a plan uploaded by the host)
+hipError_t mdt_launch_sampler_first(const mdt_sampler_plan_t* plan, const float* x, const float* noise, int n_noise, float* y0,
+                                    float* hist, float sd, const float* Wa, const float* ba, float* y, int M, int A, int D,
+                                    hipStream_t s);
+// the adaptive DPM-Solver's scaled-error partial sums (mdt_kernels.hip: k_dpm_error): mdt_dpm_error_parts(nel) floats -> part
+constexpr int MDT_DPM_PARTS = 256;
+int mdt_dpm_error_parts(int64_t nel);
+hipError_t mdt_launch_dpm_error(const float* lo, const float* hi, const float* prev, int64_t nel, float rtol, float atol,
+                                float* part, hipStream_t s);
 // operands of the head's plan epilogue (MDT_HEAD_PLAN): mdt_head_args.x is the evaluation's input Y, .out receives X'
 struct mdt_head_plan {
     const mdt_sampler_eval* e;  // this evaluation's row of the plan (device)

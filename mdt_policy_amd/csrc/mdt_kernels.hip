@@ -1538,7 +1538,8 @@ __global__ __launch_bounds__(256) void k_sampler_plan(const float* __restrict__ 
     __shared__ float ss[MDT_SCHED_MAX + 1];
     __shared__ mdt_sampler_plan_t sp;
     __shared__ float lms[4 * MDT_SCHED_MAX];
-    for (int i = threadIdx.x; i <= n_steps; i += blockDim.x) ss[i] = sig_dev ? sig_dev[i] : sv.s[i];
+    const int levels = mdt_plan_levels(kind, n_steps);  // the host checked levels <= MDT_SCHED_MAX + 1
+    for (int i = threadIdx.x; i < levels; i += blockDim.x) ss[i] = sig_dev ? sig_dev[i] : sv.s[i];
     __syncthreads();
     const bool is_lms = kind == MDT_SAMPLER_LMS;
     // the LMS quadratures (double) one step per thread: serially they were 85 us of a 20-step call
@@ -1592,16 +1593,55 @@ hipError_t mdt_launch_sampler_prep(const float* sigmas_dev, const float* sigmas_
                                    const mdt_sampler_params& prm, mdt_sampler_plan_t* plan, const float* freqs, float* sig_e,
                                    int D, const float* x, const float* noise, int n_noise, float* y0, float* hist, float sd, const float* Wa,
                                    const float* ba, float* y, int M, int A, hipStream_t s) {
-    if (n_steps < 1 || n_steps > MDT_SCHED_MAX || (!sigmas_dev) == (!sigmas_host) || (D & 3)) return hipErrorInvalidValue;
+    const int levels = mdt_plan_levels(kind, n_steps);
+    if (n_steps < 1 || n_steps > MDT_SAMPLER_MAX_EVALS || levels > MDT_SCHED_MAX + 1 || (!sigmas_dev) == (!sigmas_host) || (D & 3))
+        return hipErrorInvalidValue;
     mdt_sched_arg sv;
     memset(&sv, 0, sizeof sv);
-    if (sigmas_host) memcpy(sv.s, sigmas_host, (size_t)(n_steps + 1) * sizeof(float));
+    if (sigmas_host) memcpy(sv.s, sigmas_host, (size_t)levels * sizeof(float));
     hipLaunchKernelGGL(k_sampler_plan, dim3(1), dim3(256), 0, s, sigmas_dev, sv, n_steps, kind, prm, plan, freqs, sig_e, D);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return mdt_launch_sampler_first(plan, x, noise, n_noise, y0, hist, sd, Wa, ba, y, M, A, D, s);
+}
+
+hipError_t mdt_launch_sampler_first(const mdt_sampler_plan_t* plan, const float* x, const float* noise, int n_noise, float* y0,
+                                    float* hist, float sd, const float* Wa, const float* ba, float* y, int M, int A, int D,
+                                    hipStream_t s) {
+    if (D & 3) return hipErrorInvalidValue;
     const int64_t n = (int64_t)M * (D / 4);
     hipLaunchKernelGGL(k_sampler_first, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, plan, x, noise, n_noise, y0, hist, sd, Wa, ba,
                        y, M, A, D);
+    return hipGetLastError();
+}
+
+// The scaled error of an adaptive DPM-Solver step (_dpm_adaptive_run): per-workgroup partial sums over the elements of
+// ((low - high) / max(rtol max(|low|, |prev|), atol))^2 in a fixed order (grid-stride, then an LDS tree); the host adds the
+// partials in double in index order, so the error -- and every accept decision -- does not depend on scheduling.
+__global__ __launch_bounds__(256) void k_dpm_error(const float* __restrict__ lo, const float* __restrict__ hi,
+                                                   const float* __restrict__ prev, int64_t nel, float rtol, float atol,
+                                                   float* __restrict__ part) {
+    __shared__ float red[256];
+    float acc = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nel; i += (int64_t)gridDim.x * 256) {
+        const float l = lo[i];
+        const float v = (l - hi[i]) / fmaxf(rtol * fmaxf(fabsf(l), fabsf(prev[i])), atol);
+        acc += v * v;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+int mdt_dpm_error_parts(int64_t nel) { return (int)std::min<int64_t>((nel + 255) / 256, MDT_DPM_PARTS); }
+
+hipError_t mdt_launch_dpm_error(const float* lo, const float* hi, const float* prev, int64_t nel, float rtol, float atol,
+                                float* part, hipStream_t s) {
+    hipLaunchKernelGGL(k_dpm_error, dim3((unsigned)mdt_dpm_error_parts(nel)), dim3(256), 0, s, lo, hi, prev, nel, rtol, atol, part);
     return hipGetLastError();
 }
 

@@ -414,6 +414,8 @@ extern "C" mdt_status mdt_destroy(mdt_model* m) {
         if (m->ev_tab[i]) (void)hipEventDestroy(m->ev_tab[i]);
     }
     if (m->ev_tab_use) (void)hipEventDestroy(m->ev_tab_use);
+    (void)mdt_dev_free(m->ad_ws);
+    if (m->ad_host) (void)hipHostFree(m->ad_host);
     delete m;
     return MDT_OK;
 }
@@ -1238,16 +1240,55 @@ static mdt_status run_head_plan(mdt_model* m, mdt_head_args h, const mdt_head_pl
     return MDT_OK;
 }
 
+// MDT_PLAN_* -> mdt_status with the message of the failed check
+static mdt_status plan_fail(int st, const char* who, int kind) {
+    switch (st) {
+        case MDT_PLAN_OK: return MDT_OK;
+        case MDT_PLAN_BAD_KIND: return fail(MDT_ERR_INVALID_ARG, "%s: unknown sampler kind %d", who, kind);
+        case MDT_PLAN_BAD_STEPS:
+            return fail(MDT_ERR_INVALID_ARG, kind == MDT_SAMPLER_DPM_FAST ? "%s: dpm_fast takes 1..%d evaluations"
+                                                                          : "%s: n_steps must be 1..%d", who, mdt_plan_max_n(kind));
+        case MDT_PLAN_BAD_SIGMA:
+            return fail(MDT_ERR_INVALID_ARG, "%s: dpm_fast needs sigma_max, sigma_min > 0 (and sigma_min < sigma_max when eta != 0)",
+                        who);
+        default: return fail(MDT_ERR_INVALID_ARG, "%s: lms order must be 1..4", who);
+    }
+}
+
 extern "C" mdt_status mdt_sampler_plan(int32_t kind, const mdt_sampler_params* params, const float* sigmas_host,
                                        int32_t n_steps, mdt_sampler_plan_t* plan) {
     if (!sigmas_host || !plan) return fail(MDT_ERR_INVALID_ARG, "mdt_sampler_plan: null argument");
     const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
-    switch (mdt_build_sampler_plan(kind, p, sigmas_host, n_steps, plan)) {
-        case MDT_PLAN_OK: return MDT_OK;
-        case MDT_PLAN_BAD_KIND: return fail(MDT_ERR_INVALID_ARG, "mdt_sampler_plan: unknown sampler kind %d", kind);
-        case MDT_PLAN_BAD_STEPS: return fail(MDT_ERR_INVALID_ARG, "mdt_sampler_plan: n_steps must be 1..%d", MDT_SAMPLER_MAX_STEPS);
-        default: return fail(MDT_ERR_INVALID_ARG, "mdt_sampler_plan: lms order must be 1..4");
-    }
+    int E = 0, rows = 0;
+    int st = mdt_plan_shape(kind, p, n_steps, &E, &rows);
+    if (st == MDT_PLAN_OK) st = mdt_plan_check_levels(kind, p, sigmas_host);
+    if (st == MDT_PLAN_OK) st = mdt_build_sampler_plan(kind, p, sigmas_host, n_steps, plan);
+    return plan_fail(st, "mdt_sampler_plan", kind);
+}
+
+// evaluation e of the plan in m->plan: (per evaluation for COND_TOKEN: the encoder with its sigma -> ctx_out), one decoder pass,
+// the plan head reading the state xs, writing X' to out and Y' to y_out; the next input is embedded unless `last`
+static mdt_status run_plan_eval(mdt_model* m, const View& V, const float* tokens, const float* tokens2, const float* goal,
+                                int32_t modality, int64_t batch, int e, bool last, const float* xs, float* out, float* y_out,
+                                const float* noise, int32_t n_noise, float* ctx_out, hipStream_t s) {
+    mdt_sampler_eval* ev = m->plan->e;
+    if (m->cond == COND_TOKEN)
+        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, batch, &ev[e].sigma, 0, ctx_out, s));
+    Stream fin;
+    const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
+    MDT_TRY(run_decoder_blocks(m, V, batch, cond_row(m, e), 0, s, head_sums ? &fin : nullptr));
+    mdt_head_args h = head_args(m, V.y, batch, m->ybuf, &ev[e].sigma, 0, out, MDT_HEAD_PLAN);
+    if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
+    if (!last) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
+    mdt_head_plan pl;
+    pl.e = &ev[e];
+    pl.xs = xs;
+    pl.hist = m->hist;
+    pl.noise = noise;
+    pl.y_out = y_out;
+    pl.nel = (int64_t)batch * m->Ta * m->A;
+    pl.n_noise = noise ? n_noise : 0;
+    return run_head_plan(m, h, pl, V.hid, last ? nullptr : &ev[e].sigma_next, s);
 }
 
 // sigmas_host or sigmas_dev (exactly one non-null): the n_steps + 1 noise levels.  The structure of sample_ddim_impl: the plan
@@ -1260,13 +1301,9 @@ static mdt_status sample_plan_impl(mdt_model* m, const float* tokens, const floa
     if (!m || !x_T || (!sigmas && !sigmas_dev) || !out || batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_sample: bad argument");
     const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
     int E = 0, rows = 0;
-    switch (mdt_plan_shape(kind, p, n_steps, &E, &rows)) {
-        case MDT_PLAN_OK: break;
-        case MDT_PLAN_BAD_KIND: return fail(MDT_ERR_INVALID_ARG, "mdt_sample: unknown sampler kind %d", kind);
-        case MDT_PLAN_BAD_STEPS: return fail(MDT_ERR_INVALID_ARG, "mdt_sample: n_steps must be 1..%d", MDT_SAMPLER_MAX_STEPS);
-        default: return fail(MDT_ERR_INVALID_ARG, "mdt_sample: lms order must be 1..4");
-    }
+    MDT_TRY(plan_fail(mdt_plan_shape(kind, p, n_steps, &E, &rows), "mdt_sample", kind));
     if (sigmas) {  // a host schedule: the loop's exact draw count (a device schedule: the structural maximum)
+        MDT_TRY(plan_fail(mdt_plan_check_levels(kind, p, sigmas), "mdt_sample", kind));
         static thread_local mdt_sampler_plan_t hp;
         mdt_build_sampler_plan(kind, p, sigmas, n_steps, &hp);
         rows = hp.n_noise;
@@ -1286,7 +1323,6 @@ static mdt_status sample_plan_impl(mdt_model* m, const float* tokens, const floa
     MDT_TRY(mdt_reserve(m, batch));
     const View V = decoder_view(m, 0);
     const int M = (int)(batch * m->Ta);
-    const int64_t nel = (int64_t)M * m->A;
     mdt_sampler_eval* ev = m->plan->e;
     LAUNCH(mdt_launch_sampler_prep(sigmas_dev, sigmas_dev ? nullptr : sigmas, n_steps, kind, p, m->plan, m->freqs,
                                    per_step_ctx ? nullptr : m->sig_e, m->D, x_T, noise, noise ? n_noise : 0, m->ybuf, m->hist,
@@ -1299,23 +1335,8 @@ static mdt_status sample_plan_impl(mdt_model* m, const float* tokens, const floa
     LAUNCH(mdt_gemm_side_flush(s));
     for (int e = 0; e < E; ++e) {
         const bool last = e == E - 1;
-        if (per_step_ctx)  // the Python loop leaves the LAST evaluation's context in latent_encoder_emb
-            MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, honour, batch, &ev[e].sigma, 0, last ? ctx_out : nullptr, s));
-        Stream fin;
-        const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
-        MDT_TRY(run_decoder_blocks(m, V, batch, cond_row(m, e), 0, s, head_sums ? &fin : nullptr));
-        mdt_head_args h = head_args(m, V.y, batch, m->ybuf, &ev[e].sigma, 0, last ? out : m->xbuf, MDT_HEAD_PLAN);
-        if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
-        if (!last) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
-        mdt_head_plan pl;
-        pl.e = &ev[e];
-        pl.xs = e == 0 ? x_T : m->xbuf;
-        pl.hist = m->hist;
-        pl.noise = noise;
-        pl.y_out = last ? nullptr : m->ybuf;
-        pl.nel = nel;
-        pl.n_noise = noise ? n_noise : 0;
-        MDT_TRY(run_head_plan(m, h, pl, V.hid, last ? nullptr : &ev[e].sigma_next, s));
+        MDT_TRY(run_plan_eval(m, V, tokens, tokens2, goal, modality, batch, e, last, e == 0 ? x_T : m->xbuf, last ? out : m->xbuf,
+                              last ? nullptr : m->ybuf, noise, n_noise, last ? ctx_out : nullptr, s));
     }
     return MDT_OK;
 }
@@ -1336,6 +1357,123 @@ extern "C" mdt_status mdt_sample_dev(mdt_model* m, const float* tokens, const fl
     if (!sigmas_dev) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dev: null sigmas");
     return sample_plan_impl(m, tokens, tokens2, goal, modality, x_T, kind, params, nullptr, sigmas_dev, n_steps, noise, n_noise,
                             batch, out, ctx_out, stream);
+}
+
+extern "C" mdt_status mdt_dpm_control_init(mdt_dpm_control* c, double h, double pcoeff, double icoeff, double dcoeff,
+                                           double order, double accept_safety) {
+    if (!c || !(order > 0)) return fail(MDT_ERR_INVALID_ARG, "mdt_dpm_control_init: bad argument");
+    mdt_dpm_control_start(c, h, pcoeff, icoeff, dcoeff, order, accept_safety);
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_dpm_control_update(mdt_dpm_control* c, float error, int32_t* decision) {
+    if (!c || !decision) return fail(MDT_ERR_INVALID_ARG, "mdt_dpm_control_update: null argument");
+    *decision = mdt_dpm_control_step(c, error);
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_dpm_adaptive_plan(int32_t order, float s, float t, mdt_sampler_plan_t* plan) {
+    if (!plan || (order != 2 && order != 3)) return fail(MDT_ERR_INVALID_ARG, "mdt_dpm_adaptive_plan: order must be 2 or 3");
+    mdt_dpm_adaptive_step_plan(order, s, t, plan);
+    return MDT_OK;
+}
+
+// the pinned host block of mdt_sample_dpm_adaptive: one attempt's plan going up, the error partials coming back
+struct DpmHost {
+    mdt_sampler_plan_t plan;
+    float part[MDT_DPM_PARTS];
+};
+
+// _dpm_adaptive_run (gc_sampling.py) with eta = 0.  Per attempt: the step's plan built on the host and uploaded, the first
+// input (X at sigma(s)), the conditioning rows of its evaluations, one decoder pass + plan head per evaluation (the last writes
+// high -> hi and low -> lo), the error partials, one read-back and the controller.  Accepting swaps pointers: X <- high,
+// prev <- low.  Every scalar is the loop's: s and t in fp32, t = min / max(t_end, fp32(s + fp32(h))), the 1e-5 end test.
+extern "C" mdt_status mdt_sample_dpm_adaptive(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                              int32_t modality, const float* x_T, float sigma_min, float sigma_max,
+                                              const mdt_dpm_adaptive_params* params, int64_t batch, float* out, float* ctx_out,
+                                              mdt_dpm_adaptive_info* info, void* stream) {
+    if (!m || !x_T || !out || batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: bad argument");
+    mdt_dpm_adaptive_params p = {3, 0.05, 0.0078, 0.05, 0.0, 1.0, 0.0, 0.81};
+    if (params) p = *params;
+    if (p.order != 2 && p.order != 3) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: order must be 2 or 3");
+    if (!(sigma_min > 0.f) || !(sigma_max > 0.f))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: sigma_min and sigma_max must be > 0");
+    if (misaligned(x_T) || misaligned(out)) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: pointers must be 16-byte aligned");
+    if (m->A > 16) return fail(MDT_ERR_UNSUPPORTED, "mdt_sample_dpm_adaptive: action_dim must be <= 16");
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(s, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+        return fail(MDT_ERR_STATE, "mdt_sample_dpm_adaptive: the call synchronises every step and cannot be captured");
+    MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));
+    MDT_TRY(check_loaded(m));
+    MDT_TRY(mdt_reserve(m, batch));
+    const int M = (int)(batch * m->Ta);
+    const int64_t nel = (int64_t)M * m->A, nel4 = (nel + 3) & ~(int64_t)3;
+    MDT_TRY(mdt_grow_carve(m->ad_ws, m->ad_cap, nel4, [&](Bump& b, int64_t cap) { (void)b.take(4 * cap + MDT_DPM_PARTS); }));
+    if (!m->ad_host) HIP_TRY(hipHostMalloc(&m->ad_host, sizeof(DpmHost), hipHostMallocDefault));
+    DpmHost* hb = (DpmHost*)m->ad_host;
+    float *X = m->ad_ws, *prev = X + m->ad_cap, *hi = prev + m->ad_cap, *lo = hi + m->ad_cap;
+    float* part = m->ad_ws + 4 * m->ad_cap;
+    const View V = decoder_view(m, 0);
+    const bool per_step_ctx = m->cond == COND_TOKEN;
+    HIP_TRY(hipMemcpyAsync(X, x_T, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(prev, x_T, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (!per_step_ctx)
+        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, batch, nullptr, 0, ctx_out, s));
+    const float t_start = mdt_plan_detail::dpm_t(sigma_max), t_end = mdt_plan_detail::dpm_t(sigma_min);
+    const bool forward = t_end > t_start;
+    mdt_dpm_control ctl;
+    mdt_dpm_control_start(&ctl, forward ? fabs(p.h_init) : -fabs(p.h_init), p.pcoeff, p.icoeff, p.dcoeff, (double)p.order,
+                          p.accept_safety);
+    mdt_dpm_adaptive_info inf = {0, 0, 0, 0};
+    const int stride = (int)(sizeof(mdt_sampler_eval) / sizeof(float));
+    const int parts = mdt_dpm_error_parts(nel);
+    const float end_lo = t_end - 1e-5f, end_hi = t_end + 1e-5f;
+    float sv = t_start;
+    while (forward ? sv < end_lo : sv > end_hi) {
+        const float step = sv + (float)ctl.h;
+        const float t = forward ? fminf(t_end, step) : fmaxf(t_end, step);
+        if (t == sv)
+            return fail(MDT_ERR_NUMERIC, "mdt_sample_dpm_adaptive: the step no longer moves (s = %g, h = %g) after %d steps", sv,
+                        ctl.h, inf.steps);
+        mdt_dpm_adaptive_step_plan(p.order, sv, t, &hb->plan);
+        const int E = hb->plan.n_evals;
+        const size_t bytes = sizeof(mdt_sampler_plan_t) - (size_t)(MDT_SAMPLER_MAX_EVALS - E) * sizeof(mdt_sampler_eval);
+        HIP_TRY(hipMemcpyAsync(m->plan, &hb->plan, bytes, hipMemcpyHostToDevice, s));
+        LAUNCH(mdt_launch_sampler_first(m->plan, X, nullptr, 0, m->ybuf, m->hist, m->cfg.sigma_data, m->Wa, m->ba, V.y, M, m->A,
+                                        m->D, s));
+        MDT_TRY(run_modulation(m, &m->plan->e[0].sigma, stride, E, s));
+        for (int e = 0; e < E; ++e) {
+            const bool last = e == E - 1;
+            MDT_TRY(run_plan_eval(m, V, tokens, tokens2, goal, modality, batch, e, last, e == 0 ? X : m->xbuf,
+                                  last ? hi : m->xbuf, last ? lo : m->ybuf, nullptr, 0, ctx_out, s));
+        }
+        LAUNCH(mdt_launch_dpm_error(lo, hi, prev, nel, (float)p.rtol, (float)p.atol, part, s));
+        HIP_TRY(hipMemcpyAsync(hb->part, part, parts * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        double sum = 0.0;
+        for (int i = 0; i < parts; ++i) sum += hb->part[i];
+        // torch.linalg.norm in fp32, then / numel ** 0.5 (a Python float, taken as fp32 by the division)
+        const float error = (float)sqrt(sum) / (float)sqrt((double)nel);
+        inf.steps += 1;
+        inf.nfe += E;
+        const int d = mdt_dpm_control_step(&ctl, error);
+        if (d == MDT_DPM_STOP)
+            return fail(MDT_ERR_NUMERIC, "mdt_sample_dpm_adaptive: the step-size control stopped (error %g, h %g) after %d steps",
+                        error, ctl.h, inf.steps);
+        if (d == MDT_DPM_ACCEPT) {
+            std::swap(X, hi);
+            std::swap(prev, lo);
+            sv = t;
+            inf.n_accept += 1;
+        } else {
+            inf.n_reject += 1;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(out, X, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (info) *info = inf;
+    return MDT_OK;
 }
 
 extern "C" mdt_status mdt_loss_fwd(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,

@@ -92,6 +92,11 @@ struct mdt_model {
     float *h_enc, *qkv, *att, *hid, *ctx, *kvx, *y, *qx, *sig_e, *sig_t, *sig_c, *mod, *xbuf, *noised, *Fbuf, *steps, *sigs, *loss_part;
     float *ybuf, *hist;          // mdt_sample: the evaluation's input Y (Ra, A) and the history slots H0..H3 (4, Ra, A)
     mdt_sampler_plan_t* plan;    // mdt_sample: the plan the device builds (mdt_sampler_plan.h)
+    // mdt_sample_dpm_adaptive: state / prev / high / low (4, Ra, A) and the error partials, grown by mdt_grow_carve; the pinned
+    // host block it uploads each step's plan from and reads the partials back into
+    float* ad_ws = nullptr;
+    int64_t ad_cap = 0;
+    void* ad_host = nullptr;
     float* cmod = nullptr;  // COND_NOISE: rows of [c | ones(D)], read as (shift, scale) by the LayerNorm prologue
     int64_t cached_batch = 0;  // batch of the context currently cached by mdt_encode (0 = none)
     // collapsed cross-attention (k_xattn_fold / k_xattn_apply): folded projections per sample and decoder block

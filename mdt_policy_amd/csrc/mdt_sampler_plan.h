@@ -12,6 +12,10 @@
 // (fp32 can round sigma_down to 0 on a steep step) and dpmpp_sde's on sigma_up != 0 are followed as the loops follow them:
 // a second evaluation the loop skips still runs, with coefficients that leave the state as it is, and the noise rows are
 // numbered in the loop's draw order -- n_noise is the loop's draw count, at most mdt_plan_shape's.
+//
+// dpm_fast takes the two levels {sigma_max, sigma_min} and n evaluations instead (_dpm_fast_run): its steps are the uniform
+// t grid of torch.linspace, every stage's eps is d = (Y - D) / sigma of its evaluation (each evaluation's input is the stage
+// point), and the combines are linear in X, d and the pushed eps_0 / eps_1.
 #pragma once
 
 #include <math.h>
@@ -30,13 +34,26 @@ MDT_HD inline mdt_sampler_params mdt_sampler_defaults() {
     return p;
 }
 
-enum { MDT_PLAN_OK = 0, MDT_PLAN_BAD_KIND = 1, MDT_PLAN_BAD_STEPS = 2, MDT_PLAN_BAD_ORDER = 3 };
+enum { MDT_PLAN_OK = 0, MDT_PLAN_BAD_KIND = 1, MDT_PLAN_BAD_STEPS = 2, MDT_PLAN_BAD_ORDER = 3, MDT_PLAN_BAD_SIGMA = 4 };
+
+// levels of the schedule of a kind and n: n + 1, or dpm_fast's two {sigma_max, sigma_min}
+MDT_HD inline int mdt_plan_levels(int kind, int n) { return kind == MDT_SAMPLER_DPM_FAST ? 2 : n + 1; }
+
+// largest n of a kind: steps, or dpm_fast's evaluations
+MDT_HD inline int mdt_plan_max_n(int kind) {
+    return kind == MDT_SAMPLER_DPM_FAST ? MDT_SAMPLER_MAX_EVALS : MDT_SAMPLER_MAX_STEPS;
+}
 
 // evaluations and noise rows of a plan, from the structure alone (the checks of mdt_sample run this before enqueuing)
 MDT_HD inline int mdt_plan_shape(int kind, const mdt_sampler_params& p, int n, int* n_evals, int* n_noise) {
     if (kind < 0 || kind >= MDT_SAMPLER_COUNT) return MDT_PLAN_BAD_KIND;
-    if (n < 1 || n > MDT_SAMPLER_MAX_STEPS) return MDT_PLAN_BAD_STEPS;
+    if (n < 1 || n > mdt_plan_max_n(kind)) return MDT_PLAN_BAD_STEPS;
     if (kind == MDT_SAMPLER_LMS && (p.order < 1 || p.order > 4)) return MDT_PLAN_BAD_ORDER;
+    if (kind == MDT_SAMPLER_DPM_FAST) {  // n evaluations; one noise row per step with s_up != 0 (at most)
+        *n_evals = n;
+        *n_noise = p.eta != 0.f ? n / 3 + 1 : 0;
+        return MDT_PLAN_OK;
+    }
     const bool two = kind == MDT_SAMPLER_HEUN || kind == MDT_SAMPLER_DPM_2 || kind == MDT_SAMPLER_DPM_2_ANCESTRAL ||
                      kind == MDT_SAMPLER_DPMPP_2S || kind == MDT_SAMPLER_DPMPP_2S_ANCESTRAL || kind == MDT_SAMPLER_DPMPP_SDE;
     *n_evals = two ? 2 * n - 1 : n;
@@ -60,7 +77,7 @@ MDT_HD inline bool mdt_plan_needs_noise(int kind, const mdt_sampler_params& p) {
             return p.s_churn > 0.f && p.s_noise != 0.f;
         case MDT_SAMPLER_EULER_ANCESTRAL: case MDT_SAMPLER_DPM_2_ANCESTRAL:
             return p.eta != 0.f;
-        case MDT_SAMPLER_DPMPP_2S_ANCESTRAL: case MDT_SAMPLER_DPMPP_SDE:
+        case MDT_SAMPLER_DPMPP_2S_ANCESTRAL: case MDT_SAMPLER_DPMPP_SDE: case MDT_SAMPLER_DPM_FAST:
             return p.eta != 0.f && p.s_noise != 0.f;
         default:
             return false;
@@ -135,7 +152,132 @@ struct Builder {
     }
 };
 
+// torch.linspace(t0, t1, m + 1)[i] in fp32 as torch's CPU kernel computes it: from the nearer end
+MDT_HD inline float dpm_grid(float t0, float t1, int m, int i) {
+    const float step = (t1 - t0) / (float)m;
+    return i < (m + 1) / 2 ? fmaf(step, (float)i, t0) : fmaf(-step, (float)(m - i), t1);
+}
+
+// the DPM-Solver kinds' transcendental functions in double, rounded once to fp32: the same value on the host and the device,
+// and the loop's (torch's fp32 log / exp / expm1 on the host) but in rare last-place cases.  dpm_fast's step size multiplies
+// e^h ~ sigma_max / sigma_min: one ulp of t = -ln(sigma_max) (4.8e-7 at 80) moves a one-step result by ~1e-4.
+MDT_HD inline float dpm_t(float s) { return -(float)log((double)s); }
+MDT_HD inline float dpm_s(float t) { return (float)exp(-(double)t); }
+MDT_HD inline float dpm_expm1(float x) { return (float)expm1((double)x); }
+
+// one DPM-Solver step of order 1..3 from t to td (_dpm_stages + _dpm_combine, gc_sampling.py): eps_0 at t on the state, eps_k
+// at the interior node k on the estimate the lower stages give there.  Every eps is d = (Y - D) / sigma of its evaluation;
+// eps_0 and eps_1 are pushed (H0 the newest).  Returns the step's last evaluation.  No contraction: the products are the
+// loop's 0-dim fp32 tensor products.
+MDT_HD inline mdt_sampler_eval& dpm_step(Builder& b, float t, float td, int order, int step) {
+#pragma clang fp contract(off)
+    const float h = td - t, sn = dpm_s(td), em = dpm_expm1(h);
+    const float c0 = sn * em;  // x - c0 eps_0: the order-1 update
+    mdt_sampler_eval& a = b.add(dpm_s(t), step);
+    a.t = t;
+    a.cx[MDT_R_X] = 1.f;
+    if (order == 1) { a.cx[MDT_R_DD] = -c0; return a; }
+    const float r1 = order == 2 ? 0.5f : 1.f / 3.f, rh1 = r1 * h, s1 = t + rh1;
+    a.push = MDT_PUSH_DD;
+    a.cy[MDT_SAMPLER_NREG] = 0.f; a.cy[MDT_R_X] = 1.f; a.cy[MDT_R_DD] = -(dpm_s(s1) * dpm_expm1(rh1));
+    mdt_sampler_eval& c = b.add(dpm_s(s1), step);
+    c.t = s1;
+    c.cx[MDT_R_X] = 1.f;
+    if (order == 2) {  // x - c0 eps_0 - sn / (2 r_1) expm1(h) (eps_1 - eps_0), 2 r_1 = 1
+        const float c1 = sn / 1.f * em;
+        c.cx[MDT_R_H0] = c1 - c0; c.cx[MDT_R_DD] = -c1;
+        return c;
+    }
+    // the second node's input: x - a2 eps_0 - b2 (eps_1 - eps_0), b2 = sigma(s2) (r2 / r1) (expm1(r2 h) / (r2 h) - 1)
+    const float r2 = 2.f / 3.f, rh2 = r2 * h, s2 = t + rh2, e2 = dpm_expm1(rh2);
+    const float a2 = dpm_s(s2) * e2, b2 = (dpm_s(s2) * 2.f) * (e2 / rh2 - 1.f);
+    c.push = MDT_PUSH_DD;
+    c.cy[MDT_SAMPLER_NREG] = 0.f; c.cy[MDT_R_X] = 1.f; c.cy[MDT_R_H0] = b2 - a2; c.cy[MDT_R_DD] = -b2;
+    mdt_sampler_eval& d = b.add(dpm_s(s2), step);
+    d.t = s2;
+    // x - c0 eps_0 - sn / r2 (expm1(h) / h - 1) (eps_2 - eps_0); H0 = eps_1, H1 = eps_0
+    const float c2 = sn / r2 * (em / h - 1.f);
+    d.cx[MDT_R_X] = 1.f; d.cx[MDT_R_H0 + 1] = c2 - c0; d.cx[MDT_R_DD] = -c2;
+    return d;
+}
+
+// _dpm_fast_run (gc_sampling.py): m = n // 3 + 1 steps on linspace(t_start, t_end, m + 1), orders 3 .. 3 then 2, 1 (3 | n)
+// or n % 3; with eta != 0 each step ends at _ancestral_split's t_det and adds s_up s_noise times one noise row
+MDT_HD inline void dpm_fast(Builder& b, const mdt_sampler_params& p, const float* sig, int n) {
+#pragma clang fp contract(off)
+    const float t0 = dpm_t(sig[0]), t1 = dpm_t(sig[1]);
+    const int m = n / 3 + 1;
+    for (int i = 0; i < m; ++i) {
+        const int order = n % 3 == 0 ? (i < m - 2 ? 3 : i == m - 2 ? 2 : 1) : (i < m - 1 ? 3 : n % 3);
+        const float t = dpm_grid(t0, t1, m, i), tn = dpm_grid(t0, t1, m, i + 1);
+        float td = tn, up = 0.f;
+        if (p.eta != 0.f) {
+            const Anc an = ancestral(dpm_s(t), dpm_s(tn), p.eta);
+            td = fminf(t1, dpm_t(an.down));
+            const float sa = dpm_s(tn), sd = dpm_s(td);
+            up = sqrtf(sa * sa - sd * sd);
+        }
+        mdt_sampler_eval& z = dpm_step(b, t, td, order, i);
+        if (up != 0.f) z.cx[Builder::slot(z, b.draw())] = (float)((double)up * (double)p.s_noise);
+    }
+}
+
 }  // namespace mdt_plan_detail
+
+// one attempted step of _dpm_adaptive_run (gc_sampling.py) from s to t at order 2 or 3: the stages of dpm_step.  The last
+// evaluation's cx is the order-k combine ("high", the head's X'), its cy the order-(k-1) combine on the same stages ("low",
+// the head's Y', written to the low buffer; nothing is embedded after it): order 2 -> x - c0 eps_0; order 3 -> the order-2
+// combine with r_1 = 1/3, x - c0 eps_0 - sn / (2 r_1) expm1(h) (eps_1 - eps_0).
+MDT_HD inline void mdt_dpm_adaptive_step_plan(int order, float s, float t, mdt_sampler_plan_t* P) {
+#pragma clang fp contract(off)
+    using namespace mdt_plan_detail;
+    P->n_evals = 0; P->n_noise = 0; P->y0_noise = -1; P->y0_cn = 0.f; P->y0_draws = 0;
+    P->pad[0] = P->pad[1] = P->pad[2] = 0;
+    Builder b{P};
+    mdt_sampler_eval& z = dpm_step(b, s, t, order, 0);
+    for (int k = 0; k < P->n_evals; ++k) P->e[k].sigma_next = k + 1 < P->n_evals ? P->e[k + 1].sigma : 0.f;
+    const float h = t - s, sn = dpm_s(t), em = dpm_expm1(h), c0 = sn * em;
+    for (int k = 0; k <= MDT_SAMPLER_NREG; ++k) z.cy[k] = 0.f;
+    z.cy[MDT_R_X] = 1.f;
+    if (order == 2) {  // H0 = eps_0
+        z.cy[MDT_R_H0] = -c0;
+    } else {  // H0 = eps_1, H1 = eps_0
+        const float c1 = sn / (2.f / 3.f) * em;
+        z.cy[MDT_R_H0 + 1] = c1 - c0; z.cy[MDT_R_H0] = -c1;
+    }
+}
+
+// _StepControl (gc_sampling.py) in the same double arithmetic: log domain, arctan limiter, history shift on accept
+inline void mdt_dpm_control_start(mdt_dpm_control* c, double h, double kp, double ki, double kd, double order, double safety) {
+    memset(c, 0, sizeof *c);
+    c->h = h;
+    c->w[0] = (kp + ki + kd) / order; c->w[1] = -(kp + 2 * kd) / order; c->w[2] = kd / order;
+    c->safety = safety;
+    c->eps = 1e-8;
+}
+// MDT_DPM_ACCEPT / _REJECT, or _STOP where the error or the new h is NaN (the Python loop never ends there)
+inline int mdt_dpm_control_step(mdt_dpm_control* c, float error) {
+    const double cur = -log((double)error + c->eps);
+    if (!c->started) { c->hist[0] = c->hist[1] = c->hist[2] = cur; c->started = 1; }
+    else c->hist[0] = cur;
+    double acc = 0.0;
+    for (int i = 0; i < 3; ++i) acc += c->w[i] * c->hist[i];
+    const double factor = 1.0 + atan(exp(acc) - 1.0);
+    const bool ok = factor >= c->safety;
+    if (ok) { c->hist[2] = c->hist[1]; c->hist[1] = cur; }
+    c->h *= factor;
+    if (error != error || c->h != c->h) return MDT_DPM_STOP;
+    return ok ? MDT_DPM_ACCEPT : MDT_DPM_REJECT;
+}
+
+// the schedule checks of the host entry points (a device schedule is not read back): dpm_fast's two levels must be > 0, and
+// eta != 0 needs t_end > t_start (sample_dpm_fast's ValueErrors)
+inline int mdt_plan_check_levels(int kind, const mdt_sampler_params& p, const float* sig) {
+    if (kind != MDT_SAMPLER_DPM_FAST) return MDT_PLAN_OK;
+    if (!(sig[0] > 0.f) || !(sig[1] > 0.f)) return MDT_PLAN_BAD_SIGMA;
+    if (p.eta != 0.f && !(mdt_plan_detail::dpm_t(sig[1]) > mdt_plan_detail::dpm_t(sig[0]))) return MDT_PLAN_BAD_SIGMA;
+    return MDT_PLAN_OK;
+}
 
 // the LMS coefficients of step i (cur = min(i + 1, order) of them) -> c[0..cur-1]; independent across steps, so the device
 // computes them one step per thread before the serial build (k_sampler_plan)
@@ -144,7 +286,7 @@ MDT_HD inline void mdt_lms_step_coeffs(int order, const float* sig, int i, float
     for (int j = 0; j < cur; ++j) c[j] = mdt_plan_detail::lms_coeff(cur, sig, i, j);
 }
 
-// sig: n + 1 levels.  lms: nullptr, or the n x 4 table of mdt_lms_step_coeffs (the same values, computed beforehand).
+// sig: mdt_plan_levels(kind, n) levels.  lms: nullptr, or the n x 4 table of mdt_lms_step_coeffs (the same values, computed beforehand).
 // Returns MDT_PLAN_*.
 MDT_HD inline int mdt_build_sampler_plan(int kind, const mdt_sampler_params& p, const float* sig, int n, mdt_sampler_plan_t* P,
                                          const float* lms = nullptr) {
@@ -159,7 +301,8 @@ MDT_HD inline int mdt_build_sampler_plan(int kind, const mdt_sampler_params& p, 
     P->y0_draws = 0;
     P->pad[0] = P->pad[1] = P->pad[2] = 0;
     Builder b{P};
-    for (int i = 0; i < n; ++i) {
+    if (kind == MDT_SAMPLER_DPM_FAST) dpm_fast(b, p, sig, n);
+    for (int i = 0; i < n && kind != MDT_SAMPLER_DPM_FAST; ++i) {
         const float s = sig[i], sn = sig[i + 1];
         const bool last = i == n - 1;
         switch (kind) {

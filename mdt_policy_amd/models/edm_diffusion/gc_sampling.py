@@ -4,9 +4,10 @@
 libmdt_hip.so when ``model`` is this package's GCDenoiser and no Python hooks are requested: encoder and
 cross-attention K/V once, adaLN vectors of all steps once, the DDIM update fused into the action-head kernel.
 The other fixed-step samplers (euler, heun, the ancestral ones, dpm_2, lms, dpmpp_2m / 2s / sde) run the same way --
-one call, ``GCDenoiser.sample_native`` -> mdt_sample -- under the same condition plus ``scaler=None``; otherwise, and for
-sample_dpm_fast / sample_dpm_adaptive, they are host loops over ``model(state, x, goal, sigma)`` (the HIP denoiser step)
-with the sigma-independent encoder hoisted out of the loop.
+one call, ``GCDenoiser.sample_native`` -> mdt_sample -- under the same condition plus ``scaler=None``, and so does
+sample_dpm_fast (1..128 evaluations); sample_dpm_adaptive with eta = 0 on the GPU is one blocking call
+(``GCDenoiser.sample_dpm_adaptive_native`` -> mdt_sample_dpm_adaptive).  Otherwise they are host loops over
+``model(state, x, goal, sigma)`` (the HIP denoiser step) with the sigma-independent encoder hoisted out of the loop.
 
 Signatures follow the reference: ``sample_*(model, state, action, goal, sigmas, scaler=None, extra_args=None,
 callback=None, disable=None, ...)``.
@@ -231,35 +232,39 @@ def _ancestral_draws(sigmas, eta):
     return sum(1 for i in range(n) if get_ancestral_step(sig[i], sig[i + 1], eta=eta)[0] > 0)
 
 
-def _graphed_native(model, kind, params, state, action, goal, sigmas, noise):
+def _graphed_native(model, kind, params, state, action, goal, sigmas, noise, n_steps=None):
     """One GraphedSampler per (kind, parameters, shapes, modality, state keys) of a model, kept on the model (at most four)."""
     from .graphed import GraphedSampler
     cache = model.__dict__.setdefault("_graphed_native", [])
     for gsamp in cache:
-        if gsamp.matches_sampler(kind, params, state, action, goal, sigmas, noise):
+        if gsamp.matches_sampler(kind, params, state, action, goal, sigmas, noise, n_steps):
             return gsamp(state, action, goal, sigmas, noise=noise)
     gsamp = GraphedSampler(model, kind, params, state, action, goal,
-                           sigmas if torch.is_tensor(sigmas) else torch.as_tensor(sigmas), noise)
+                           sigmas if torch.is_tensor(sigmas) else torch.as_tensor(sigmas), noise, n_steps)
     cache.append(gsamp)
     del cache[:-4]
     return gsamp(state, action, goal, sigmas, noise=noise)
 
 
-def _run_native(kind, model, state, action, goal, sigmas, noise, **params):
-    """The native call, replayed as a HIP graph by sample_ddim's rule (rollout-sized batches from the third identical call)."""
-    if _graph_wanted(model, state, action, goal, sigmas, tag=(kind, tuple(sorted(params.items())))):
+def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, **params):
+    """The native call, replayed as a HIP graph by sample_ddim's rule (rollout-sized batches from the third identical call).
+    ``n_steps``: dpm_fast's evaluation count (its schedule is the two levels, which join the graph key with it)."""
+    tag = (kind, tuple(sorted(params.items())))
+    if n_steps is not None:
+        tag += (n_steps, tuple(float(v) for v in sigmas))
+    if _graph_wanted(model, state, action, goal, sigmas, tag=tag):
         try:
-            return _graphed_native(model, kind, params, state, action, goal, sigmas, noise)
+            return _graphed_native(model, kind, params, state, action, goal, sigmas, noise, n_steps)
         except Exception as exc:  # noqa: BLE001 -- as in sample_ddim: a failed capture leaves this call shape eager
             if _GRAPH_SAMPLER:
                 raise
-            key = ((kind, tuple(sorted(params.items()))),) + _graph_key(state, action, goal, sigmas)
+            key = (tag,) + _graph_key(state, action, goal, sigmas)
             model.__dict__.setdefault("_graph_failed", set()).add(key)
             model.__dict__.pop("_graphed_native", None)
             import warnings
             warnings.warn(f"mdt_policy_amd: HIP-graph capture of sample_{kind} failed ({exc!r}); this call shape stays eager")
             torch.cuda.synchronize()
-    return model.sample_native(kind, state, action, goal, sigmas, noise=noise, **params)
+    return model.sample_native(kind, state, action, goal, sigmas, noise=noise, n_steps=n_steps, **params)
 
 
 @torch.no_grad()
@@ -717,9 +722,29 @@ def sample_dpm_fast(model, state, action, goal, sigma_min, sigma_max, n, scaler=
     if eta and not t_end > t_start:
         raise ValueError('eta must be 0 for reverse sampling')
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
+    if (isinstance(model, GCDenoiser) and callback is None and not extra_args and scaler is None
+            and 1 <= n <= _lib.SAMPLER_MAX_EVALS):
+        return _run_native("dpm_fast", model, state, action, goal, [float(sigma_max), float(sigma_min)],
+                           _dpm_fast_noise(action, t_start, t_end, n, eta, noise_sampler), n_steps=n, eta=eta, s_noise=s_noise)
     with _hoist(model, state, goal):
         return _dpm_fast_run(_EpsEvaluator(model, state, goal, extra_args), action, t_start, t_end, n, eta, s_noise,
                              noise_sampler, callback)
+
+
+def _dpm_fast_noise(action, t_start, t_end, n, eta, noise_sampler):
+    """The noise_sampler values _dpm_fast_run draws, in its order: one per step with s_up != 0 (none at eta = 0), padded with
+    zero rows to one per step -- the rows a device schedule may read (rows beyond the plan's are unread)."""
+    if not eta:
+        return None
+    m = n // 3 + 1
+    grid = torch.linspace(_f(t_start), _f(t_end), m + 1)
+    values = []
+    for i in range(m):
+        t, t_next = grid[i], grid[i + 1]
+        if _f(_ancestral_split(t, t_next, t_end, eta)[1]) != 0:
+            values.append(noise_sampler(_sigma(t), _sigma(t_next)))
+    values += [torch.zeros_like(action)] * (m - len(values))
+    return _sampled_rows(action, values)
 
 
 def _dpm_fast_run(eps, action, t_start, t_end, n, eta, s_noise, noise_sampler, callback):
@@ -755,6 +780,12 @@ def sample_dpm_adaptive(model, state, action, goal, sigma_min, sigma_max, extra_
     t_end = _t(torch.tensor(float(sigma_min))).to(torch.float32)
     if eta and not bool(t_end > t_start):
         raise ValueError('eta must be 0 for reverse sampling')
+    if (isinstance(model, GCDenoiser) and callback is None and not extra_args and not eta and action.device.type == "cuda"
+            and not torch.cuda.is_current_stream_capturing()):
+        action, info = model.sample_dpm_adaptive_native(state, action, goal, float(sigma_min), float(sigma_max), order=order,
+                                                        rtol=rtol, atol=atol, h_init=h_init, pcoeff=pcoeff, icoeff=icoeff,
+                                                        dcoeff=dcoeff, accept_safety=accept_safety)
+        return (action, info) if return_info else action
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
     with _hoist(model, state, goal):
         action, info = _dpm_adaptive_run(_EpsEvaluator(model, state, goal, extra_args), action, t_start, t_end, order, rtol, atol,

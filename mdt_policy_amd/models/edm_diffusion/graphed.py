@@ -144,14 +144,14 @@ class GraphedSampler(GraphedDDIM):
     the other inputs, so a replay consumes the same random stream as the eager call."""
 
     def __init__(self, model, kind: str, params: dict, state: dict, x_T: torch.Tensor, goal: torch.Tensor,
-                 sigmas: torch.Tensor, noise: Optional[torch.Tensor]):
-        self.kind, self.params = kind, dict(params)
+                 sigmas: torch.Tensor, noise: Optional[torch.Tensor], n_steps: Optional[int] = None):
+        self.kind, self.params, self.n_steps = kind, dict(params), n_steps  # n_steps: dpm_fast's evaluation count
         self._noise = None if noise is None else noise.detach().clone()
         super().__init__(model, state, x_T, goal, sigmas)
 
     def _run(self):
         return self.model.sample_native(self.kind, self._static_state, self._x, self._goal, self._sig, noise=self._noise,
-                                        **self.params)
+                                        n_steps=self.n_steps, **self.params)
 
     def _extra_inputs(self, noise):
         if (noise is None) != (self._noise is None) or (noise is not None and noise.shape != self._noise.shape):
@@ -159,8 +159,8 @@ class GraphedSampler(GraphedDDIM):
         return ([], []) if noise is None else ([self._noise], [noise])
 
     def matches_sampler(self, kind: str, params: dict, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
-                        noise: Optional[torch.Tensor]) -> bool:
-        if kind != self.kind or params != self.params or (noise is None) != (self._noise is None):
+                        noise: Optional[torch.Tensor], n_steps: Optional[int] = None) -> bool:
+        if kind != self.kind or params != self.params or n_steps != self.n_steps or (noise is None) != (self._noise is None):
             return False
         if noise is not None and noise.shape != self._noise.shape:
             return False

@@ -183,18 +183,30 @@ class GCDenoiser(nn.Module):
         return self._engine(state=state).denoise_vjp(state, action, im._goals(goal, False), sigma, v)
 
     @torch.no_grad()
-    def sample_native(self, kind, state, action, goal, sigmas, noise=None, **params):
+    def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, **params):
         """One of the other samplers (``kind``: 'euler', 'heun', 'dpmpp_2m', ... -- the gc_sampling function name without
         'sample_') as one enqueue on the current stream (mdt_sample).  ``noise``: None or (n_noise, B, Ta, A) in the Python loop's
         draw order -- raw randn draws (euler / heun / dpm_2 / the ancestral samplers) or the noise_sampler values (dpmpp_2s_ancestral,
         dpmpp_sde); s_noise and the step scales are applied inside.  ``params``: the sampler's keyword arguments (eta, s_churn,
-        s_tmin, s_tmax, s_noise, r, order)."""
+        s_tmin, s_tmax, s_noise, r, order).  'dpm_fast': ``sigmas`` is [sigma_max, sigma_min] and ``n_steps`` the evaluation
+        count."""
         from ... import _lib
         im = self.inner_model
         out, ctx = self._engine(state=state).sample_native(_lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action,
-                                                           im._goals(goal, False), sigmas, noise)
+                                                           im._goals(goal, False), sigmas, noise, n_steps=n_steps)
         im.latent_encoder_emb = ctx
         return out
+
+    @torch.no_grad()
+    def sample_dpm_adaptive_native(self, state, action, goal, sigma_min, sigma_max, **params):
+        """sample_dpm_adaptive with eta = 0 as one blocking call (mdt_sample_dpm_adaptive): ``params`` its keyword arguments
+        (order, rtol, atol, h_init, pcoeff, icoeff, dcoeff, accept_safety).  Returns (action, info)."""
+        from ... import _lib
+        im = self.inner_model
+        out, ctx, info = self._engine(state=state).sample_dpm_adaptive(_lib.dpm_adaptive_params(**params), state, action,
+                                                                       im._goals(goal, False), sigma_min, sigma_max)
+        im.latent_encoder_emb = ctx
+        return out, info
 
     @torch.no_grad()
     def sample_ddim(self, state, action, goal, sigmas):

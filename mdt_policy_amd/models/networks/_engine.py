@@ -272,10 +272,11 @@ class HipEngine:
         return out, ctx
 
     def sample_native(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
-                      noise: Optional[torch.Tensor] = None):
+                      noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None):
         """One call of another sampler (mdt_sample / mdt_sample_dev): ``kind`` an mdt_sampler_kind, ``params`` an
-        _lib.SamplerParams, ``noise`` None or (n_noise, B, Ta, A) in the Python loop's draw order.  Like sample_ddim, a device
-        schedule is read in place (no copy, no synchronisation)."""
+        _lib.SamplerParams, ``noise`` None or (n_noise, B, Ta, A) in the Python loop's draw order, ``n_steps`` None (one less
+        than the levels) or dpm_fast's evaluation count.  Like sample_ddim, a device schedule is read in place (no copy, no
+        synchronisation)."""
         self.sync_params()
         tok, tok2, B = self._tokens(state)
         g, x_ = self._goal(goal, B), self._in(x_T, (B, self.Ta, self.A))
@@ -285,20 +286,34 @@ class HipEngine:
         ctx = torch.empty((B, self.Te, self.D), device=self.device, dtype=torch.float32)
         if torch.is_tensor(sigmas) and sigmas.device.type == "cuda":
             sig = self._in(sigmas.reshape(-1))
-            n = sig.numel() - 1
+            n = sig.numel() - 1 if n_steps is None else int(n_steps)
             self._keep = (sig, nz)  # the kernels that read them are only enqueued: keep the tensors alive
             self.ctx_generation += 1
             _lib.call(self.lib.mdt_sample_dev, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_),
                       int(kind), C.byref(params), _ptr(sig), n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), self._stream())
             return out, ctx
         sig = [float(v) for v in (sigmas.detach().tolist() if torch.is_tensor(sigmas) else sigmas)]
-        n = len(sig) - 1
+        n = len(sig) - 1 if n_steps is None else int(n_steps)
         arr = (C.c_float * len(sig))(*sig)
         self._keep = nz
         self.ctx_generation += 1
         _lib.call(self.lib.mdt_sample, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_), int(kind),
                   C.byref(params), arr, n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), self._stream())
         return out, ctx
+
+    def sample_dpm_adaptive(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigma_min: float, sigma_max: float):
+        """mdt_sample_dpm_adaptive (eta = 0): ``params`` an _lib.DpmAdaptiveParams.  Blocking: the call reads the step error
+        back every step.  Returns (out, ctx, info dict)."""
+        self.sync_params()
+        tok, tok2, B = self._tokens(state)
+        g, x_ = self._goal(goal, B), self._in(x_T, (B, self.Ta, self.A))
+        out = torch.empty((B, self.Ta, self.A), device=self.device, dtype=torch.float32)
+        ctx = torch.empty((B, self.Te, self.D), device=self.device, dtype=torch.float32)
+        info = _lib.DpmAdaptiveInfo()
+        self.ctx_generation += 1
+        _lib.call(self.lib.mdt_sample_dpm_adaptive, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_),
+                  float(sigma_min), float(sigma_max), C.byref(params), B, _ptr(out), _ptr(ctx), C.byref(info), self._stream())
+        return out, ctx, {k: int(getattr(info, k)) for k in ("steps", "nfe", "n_accept", "n_reject")}
 
     def loss_fwd(self, state: dict, action: torch.Tensor, goal: torch.Tensor, noise: torch.Tensor, sigma: torch.Tensor):
         self.sync_params()
