@@ -115,16 +115,46 @@ class PackedWeights:
 
 # ---- weight gradients beside the backward chain (round 6) -----------------------------------------------------------------
 # dW = dY^T X (and the bias gradient) of a Linear is a leaf of the backward: nothing reads it before the optimizer.  As in the
-# denoiser's own backward (csrc/mdt_train.hip, MDT_HIP_DW_STREAM) it runs on a side stream behind "dY exists" while the chain
+# denoiser's own backward (csrc/mdt_train.hip, MDT_HIP_DW_STREAM) it may run on a side stream behind "dY exists" while the chain
 # -- the input-gradient products, the norm / attention backward -- goes on; ONE join, queued as an end-of-backward callback of
-# the autograd engine, puts the side stream back in front of whatever follows loss.backward().  Only where nothing can look at
-# the gradient earlier: the parameters carry no .grad yet (AccumulateGrad then adopts the tensor without a kernel) and no tensor
-# hooks, and no multi-rank process group exists (DistributedDataParallel copies a gradient into its bucket the moment it appears).
+# the autograd engine, puts the side stream back in front of whatever follows loss.backward().
+# The rule: a gradient goes beside only when it is provably the parameter's ONLY gradient in the running backward, because
+# autograd hands it straight to AccumulateGrad, which adopts the tensor without a kernel.  Any second gradient of the same
+# parameter -- a second forward of the module before one backward (the agent's two modality scopes), an existing .grad
+# (gradient accumulation) -- is added to it by a kernel on the chain's stream that nothing orders behind the side stream; the
+# side stream's late writes then also land in blocks the allocator has meanwhile handed to other gradients.  So:
+#   * every grad-enabled forward use of a weight / bias is counted (_USES); the counts go back to zero at the end of every
+#     backward that ran a node of this head, and a gradient goes beside only when its parameters' counts are exactly 1;
+#   * the parameters carry no .grad yet and no tensor hooks;
+#   * no multi-rank process group exists (DistributedDataParallel copies a gradient into its bucket the moment it appears).
+# Otherwise the gradient runs on the chain: slower, never wrong.  SIDE_LAUNCHES counts the launches that went beside.
 _SIDE = {}
+_USES: Dict[int, int] = {}
+SIDE_LAUNCHES = 0
+
+
+def _count_uses(ctx, params) -> None:
+    """Forward: one more use of every parameter in ``params`` (a tuple of (tensor or None, its index among the Function's
+    inputs)) that this node will differentiate."""
+    for p, i in params:
+        if p is not None and ctx.needs_input_grad[i]:
+            _USES[id(p)] = _USES.get(id(p), 0) + 1
+
+
+def _arm_reset() -> bool:
+    """Queue the end-of-backward callback that forgets the use counts (one per node, like the join below: all but the first
+    find nothing to do); False outside the engine."""
+    try:
+        torch.autograd.Variable._execution_engine.queue_callback(_USES.clear)
+    except Exception:  # noqa: BLE001 -- not inside a backward pass of the engine: nothing can be proven, no deferral
+        return False
+    return True
 
 
 def _dw_beside(params) -> bool:
     import os
+    if not _arm_reset():
+        return False
     if os.environ.get("MDT_HIP_MAE_DW_STREAM", "1") in ("", "0"):
         return False
     try:
@@ -133,7 +163,7 @@ def _dw_beside(params) -> bool:
             return False
     except Exception:  # noqa: BLE001
         pass
-    return all(p is None or (p.grad is None and not p._backward_hooks) for p in params)
+    return all(p is None or (p.grad is None and not p._backward_hooks and _USES.get(id(p), 0) == 1) for p in params)
 
 
 def _side_stream(dev: torch.device):
@@ -170,6 +200,8 @@ def _linear_bwd(lib, x2, dY, N, K, wt, need_x, need_w, need_b, dx_cols=None, act
     if beside and (need_w or need_b):
         side, keep = _side_stream(dY.device)
     if side is not None:
+        global SIDE_LAUNCHES
+        SIDE_LAUNCHES += 1
         w = _lib.LinearBwdArgs(X=x2.data_ptr(), ldx=K, dY=dY.data_ptr(), ldy=N, Wt=None, dW=None if dW is None else dW.data_ptr(),
                                dbias=None if db is None else db.data_ptr(), dX=None, ldxo=xc, accumulate_dw=0, accumulate_dx=0,
                                M=M, N=N, K=K, scratch=scratch.data_ptr(), dx_act_u=None, dx_act=0)
@@ -227,6 +259,7 @@ class HipSwiGLUMLP(torch.autograd.Function):
         _lib.check(lib.mdt_op_gemm(C.byref(g), s))
         ctx.save_for_backward(x2, u, h, w0, b0, w1, b1)
         ctx.packs, ctx.xshape = packs, x.shape
+        _count_uses(ctx, ((w0, 1), (b0, 2), (w1, 3), (b1, 4)))
         return y.reshape(*x.shape[:-1], N1)
 
     @staticmethod
@@ -272,6 +305,7 @@ class HipLinear(torch.autograd.Function):
         _lib.check(lib.mdt_op_gemm(C.byref(a), _stream(x2)))
         ctx.save_for_backward(x2, weight, bias)
         ctx.packs, ctx.xshape = packs, x.shape
+        _count_uses(ctx, ((weight, 1), (bias, 2)))
         return out.reshape(*x.shape[:-1], N)
 
     @staticmethod

@@ -115,12 +115,16 @@ def test_combined_c3_step_follows_the_oracles_for_three_adamw_steps():
     opt64 = torch.optim.AdamW([PD[k] for k in used] + [v for v in P64.values() if v.requires_grad], lr=lr, weight_decay=wd)
     w0 = {k: p.detach().clone() for k, p in list(model.named_parameters()) + [("gen." + k, p) for k, p in gen.named_parameters()]}
 
+    from mdt_policy_amd.models.img_generation import _hip_ops
     for step in range(3):
         opt.zero_grad(set_to_none=True)
         loss, _ = model.loss(gstate, gl["actions"], ggoal, gl["noise_train"], gl["sigma"])
         rec, mask, restore, _ = gen(model.inner_model.latent_encoder_emb, gimg, noise=noises[step].cuda())
         aux = gen.compute_loss(gimg, rec, mask, restore)
+        side0 = _hip_ops.SIDE_LAUNCHES
         (loss + aux).backward()
+        # one head forward per backward: the head's weight gradients still go beside the chain (bench.py times this step)
+        assert _hip_ops.SIDE_LAUNCHES > side0, step
 
         opt64.zero_grad(set_to_none=True)
         lo, _ = O.loss(PD, cfg, st64, l64["actions"], g64, l64["noise_train"], l64["sigma"], arch=meta["arch"])
