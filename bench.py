@@ -7,16 +7,23 @@ C2 at N=1, C4-shaped (256 per GPU, weak scaling, one RCCL all-gather of the samp
 Inputs (state tokens, goal, x_T) and the random-init weights are synthetic and already resident in HBM when the
 timed region starts.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with the extra objects
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps, dumps
+(--dump-outputs) and prints that line with
   roofline     : algorithmic FLOPs (mdt_flops_per_chunk = 1.812 GFLOP/chunk) / HIP-event time of the timed region
-                 against the dense FP32-MFMA peak (157.3 TFLOP/s; bf16/fp16 operands fail the parity gate), plus
-                 the same figure for the dominant kernel (the fused MFMA GEMM) timed alone through the op-level ABI
+                 against the dense FP32-MFMA peak (157.3 TFLOP/s; bf16/fp16 operands fail the parity gate), and the
+                 shader clock sustained over the timed region
+--full runs the diagnostic legs behind the timed steps as well and adds their objects to the line:
+  spread       : median_ms / p10_ms / p90_ms / value_at_median from >= 50 more calls, each between its own HIP events
+  roofline.dominant_kernel : the same figure for the dominant kernel (the fused MLP launch), inside one more sampler call
+                 and alone through the op-level ABI, with the committed PMC pass's traffic and MFMA-busy figures
+  other_configs: the other BASELINE configurations (training steps, rollout batches, other samplers and architecture)
   cpu_baseline : the CPU oracle ("port" of the reference algorithm, as-written: encoder re-run every step) timed on
-                 this host's cores on a bounded sample of the same workload (rank 0, N=1 only)
+                 this host's cores on a bounded sample of the same workload
+  (other_configs and cpu_baseline at N=1 only, and not with --no-cpu-baseline)
 
 --dump-outputs DIR writes the actions the last timed step returned (at N > 1 rank 0's gathered (N B, 10, 7) tensor) to
 DIR/actions.npy as float32.  Weights and inputs are seeded, so two builds run with the same arguments can be compared
@@ -49,7 +56,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="action chunks per GPU per step")
     ap.add_argument("--denoise-steps", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the diagnostic legs: the per-call spread, the dominant kernel, "
+                         "the other configurations and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the other configurations and the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=30.0, help="budget of the CPU baseline (all legs together)")
     ap.add_argument("--cpu-leg", default="", help=argparse.SUPPRESS)  # internal: "threads,hoist,budget" -> one CPU-baseline leg, JSON on stdout
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0: min(cpu_count, 16), the best of a 1..128 sweep on the EPYC host)")
@@ -672,25 +682,27 @@ def main():
     if args.dump_outputs and rank == 0:
         # before the spread run below: a graph-replayed sampler call hands back the same output buffer every call
         dump_outputs(args.dump_outputs, {"actions": out})
-    # spread (median of >= 50 timed iterations): the same step again, every call between its own pair of
-    # HIP events on the launch stream; `value` stays the contract's K-step mean, this tells box-to-box noise from change
-    n_spread = max(50, args.steps)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_spread)]
-    for a, b in evs:
-        a.record()
-        step()
-        b.record()
-    torch.cuda.synchronize(device)
-    per_call = torch.tensor(sorted(a.elapsed_time(b) for a, b in evs), dtype=torch.float64)
-    if dist is not None:
-        dist.barrier()
-        pc = per_call.to(device)
-        dist.all_reduce(pc, op=dist.ReduceOp.MAX)  # rank-wise order statistics: the slowest rank at every quantile
-        per_call = pc.cpu()
-    q = lambda f: float(per_call[min(n_spread - 1, int(round(f * (n_spread - 1))))])
-    spread = {"calls": n_spread, "median_ms": round(q(0.5), 4), "p10_ms": round(q(0.1), 4), "p90_ms": round(q(0.9), 4),
-              "min_ms": round(float(per_call[0]), 4), "max_ms": round(float(per_call[-1]), 4), "mean_ms": round(float(per_call.mean()), 4),
-              "what": "per-call HIP-event times of one more run of the same step (each call bracketed on the launch stream)"}
+    spread = None
+    if args.full:
+        # spread (median of >= 50 timed iterations): the same step again, every call between its own pair of
+        # HIP events on the launch stream; `value` stays the contract's K-step mean, this tells box-to-box noise from change
+        n_spread = max(50, args.steps)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_spread)]
+        for a, b in evs:
+            a.record()
+            step()
+            b.record()
+        torch.cuda.synchronize(device)
+        per_call = torch.tensor(sorted(a.elapsed_time(b) for a, b in evs), dtype=torch.float64)
+        if dist is not None:
+            dist.barrier()
+            pc = per_call.to(device)
+            dist.all_reduce(pc, op=dist.ReduceOp.MAX)  # rank-wise order statistics: the slowest rank at every quantile
+            per_call = pc.cpu()
+        q = lambda f: float(per_call[min(n_spread - 1, int(round(f * (n_spread - 1))))])
+        spread = {"calls": n_spread, "median_ms": round(q(0.5), 4), "p10_ms": round(q(0.1), 4), "p90_ms": round(q(0.9), 4),
+                  "min_ms": round(float(per_call[0]), 4), "max_ms": round(float(per_call[-1]), 4), "mean_ms": round(float(per_call.mean()), 4),
+                  "what": "per-call HIP-event times of one more run of the same step (each call bracketed on the launch stream)"}
     gather_ok = None
     if dist is not None and os.environ.get("MDT_BENCH_VERIFY_GATHER") == "1":
         # every rank checks the gathered tensor: shape (world * B, Ta, A) and block r == rank r's own actions
@@ -716,9 +728,9 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(wall / args.steps * 1e3, 4),
-            "median_ms": spread["median_ms"], "p10_ms": spread["p10_ms"], "p90_ms": spread["p90_ms"],
-            "value_at_median": round(B * world / (spread["median_ms"] * 1e-3), 1),
-            "spread": spread,
+            **({"median_ms": spread["median_ms"], "p10_ms": spread["p10_ms"], "p90_ms": spread["p90_ms"],
+                "value_at_median": round(B * world / (spread["median_ms"] * 1e-3), 1),
+                "spread": spread} if spread else {}),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -768,50 +780,51 @@ def main():
                                                   "exactly the timed steps (median over the XCDs); `frac` stays quoted at the 2.4 GHz the 157.3 TFLOP/s peak assumes")
         except Exception as e:  # diagnostic only
             res["roofline"]["sustained_mhz_error"] = repr(e)
-        try:
-            dk = time_dominant_kernel(device, B * 10)
-            chain = time_dominant_kernel_in_chain(step, device) if world == 1 else None
-            if chain:  # the figure the roofline of the dominant kernel is quoted on: its launches inside one sampler call
-                tf = dk["gflop_per_launch"] * 1e9 / (chain["avg_us"] * 1e-6) / 1e12
-                if dk.get("executed_flops_per_algorithmic", 1) > 1:
-                    dk["frac_of_bf16_peak_executed"] = round(dk["executed_flops_per_algorithmic"] * tf / PEAK_BF16_MFMA_TFLOPS, 4)
-                dk.update({"avg_us": chain["avg_us"], "achieved": round(tf, 2), "frac": round(tf / PEAK_FP32_MFMA_TFLOPS, 4),
-                           "in_chain": chain,
-                           "what": f"mean over the {chain['launches']} launches of ONE sampler call, each between its own pair of HIP "
-                                   "events on the launch stream (mdt_op_trace_mlp), minus the cost of an empty event bracket measured "
-                                   f"in the same call ({chain['empty_bracket_us']} us; the raw brackets average {chain['avg_us_bracket']} us): "
-                                   "the kernel as a kernel trace of the call sees it"})
-            else:
-                dk.update({k: dk["alone"][k] for k in ("avg_us", "achieved", "frac")})
-            res["roofline"]["dominant_kernel"] = dk
-            log("dominant kernel timed")
-            # HBM-side bytes per launch of that kernel: PMC counters cannot be read from inside this process, so `traffic` is NOT
-            # a measurement of this run: it is the committed rocprofv3 --pmc pass of the same kernel and shape (latest profiles/
-            # round), labelled with the commit that pass was taken at
-            here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
-            cands = sorted(f for f in os.listdir(here) if f.endswith("_dominant_kernel_pmc.json")) if os.path.isdir(here) else []
-            if B == 256 and cands:
-                with open(os.path.join(here, cands[-1])) as f:
-                    j = json.load(f)
-                res["roofline"]["traffic"] = j["hbm_side_bytes_per_launch"]
-                # the EXECUTED share of the matrix pipe, beside the algorithmic fraction above (which credits the folded cross-
-                # attention projections and the per-step conditioning at the reference's FLOP count): whole-run MFMA-busy of the
-                # same committed PMC pass (SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs / kernel time at 2.4 GHz)
-                if "whole_run_mfma_busy" in j:
-                    res["roofline"]["mfma_busy"] = j["whole_run_mfma_busy"]
-                    res["roofline"]["mfma_busy_scope"] = (
-                        f"NOT measured by this run: whole-run MFMA-busy fraction of the committed PMC pass profiles/{cands[-1]} "
-                        "(executed MFMA issue slots / peak slots at 2.4 GHz over all kernels of the bench command); `frac` above counts "
-                        "the reference's algorithmic FLOPs, of which the folded cross-attention projections and the per-sample sigma / adaLN "
-                        "products are not executed")
-                res["roofline"]["traffic_scope"] = (
-                    f"NOT measured by this run: committed PMC pass profiles/{cands[-1]} (commit {j.get('commit', 'see its header')}), HBM-side "
-                    "bytes per launch of the dominant kernel (TCC_EA0 read x128 B + write x64 B); true algorithmic bytes "
-                    f"{dk['algorithmic_bytes_per_launch']} (rows in + both weight images + one output), "
-                    f"{dk['algorithmic_bytes_per_launch_with_slabs']} with the three partial slabs the kernel writes instead of one output")
-        except Exception as e:  # diagnostic leg only; never hides the main number
-            res["roofline"]["dominant_kernel"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            try:
+                dk = time_dominant_kernel(device, B * 10)
+                chain = time_dominant_kernel_in_chain(step, device) if world == 1 else None
+                if chain:  # the figure the roofline of the dominant kernel is quoted on: its launches inside one sampler call
+                    tf = dk["gflop_per_launch"] * 1e9 / (chain["avg_us"] * 1e-6) / 1e12
+                    if dk.get("executed_flops_per_algorithmic", 1) > 1:
+                        dk["frac_of_bf16_peak_executed"] = round(dk["executed_flops_per_algorithmic"] * tf / PEAK_BF16_MFMA_TFLOPS, 4)
+                    dk.update({"avg_us": chain["avg_us"], "achieved": round(tf, 2), "frac": round(tf / PEAK_FP32_MFMA_TFLOPS, 4),
+                               "in_chain": chain,
+                               "what": f"mean over the {chain['launches']} launches of ONE sampler call, each between its own pair of HIP "
+                                       "events on the launch stream (mdt_op_trace_mlp), minus the cost of an empty event bracket measured "
+                                       f"in the same call ({chain['empty_bracket_us']} us; the raw brackets average {chain['avg_us_bracket']} us): "
+                                       "the kernel as a kernel trace of the call sees it"})
+                else:
+                    dk.update({k: dk["alone"][k] for k in ("avg_us", "achieved", "frac")})
+                res["roofline"]["dominant_kernel"] = dk
+                log("dominant kernel timed")
+                # HBM-side bytes per launch of that kernel: PMC counters cannot be read from inside this process, so `traffic` is NOT
+                # a measurement of this run: it is the committed rocprofv3 --pmc pass of the same kernel and shape (latest profiles/
+                # round), labelled with the commit that pass was taken at
+                here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
+                cands = sorted(f for f in os.listdir(here) if f.endswith("_dominant_kernel_pmc.json")) if os.path.isdir(here) else []
+                if B == 256 and cands:
+                    with open(os.path.join(here, cands[-1])) as f:
+                        j = json.load(f)
+                    res["roofline"]["traffic"] = j["hbm_side_bytes_per_launch"]
+                    # the EXECUTED share of the matrix pipe, beside the algorithmic fraction above (which credits the folded cross-
+                    # attention projections and the per-step conditioning at the reference's FLOP count): whole-run MFMA-busy of the
+                    # same committed PMC pass (SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs / kernel time at 2.4 GHz)
+                    if "whole_run_mfma_busy" in j:
+                        res["roofline"]["mfma_busy"] = j["whole_run_mfma_busy"]
+                        res["roofline"]["mfma_busy_scope"] = (
+                            f"NOT measured by this run: whole-run MFMA-busy fraction of the committed PMC pass profiles/{cands[-1]} "
+                            "(executed MFMA issue slots / peak slots at 2.4 GHz over all kernels of the bench command); `frac` above counts "
+                            "the reference's algorithmic FLOPs, of which the folded cross-attention projections and the per-sample sigma / adaLN "
+                            "products are not executed")
+                    res["roofline"]["traffic_scope"] = (
+                        f"NOT measured by this run: committed PMC pass profiles/{cands[-1]} (commit {j.get('commit', 'see its header')}), HBM-side "
+                        "bytes per launch of the dominant kernel (TCC_EA0 read x128 B + write x64 B); true algorithmic bytes "
+                        f"{dk['algorithmic_bytes_per_launch']} (rows in + both weight images + one output), "
+                        f"{dk['algorithmic_bytes_per_launch_with_slabs']} with the three partial slabs the kernel writes instead of one output")
+            except Exception as e:  # diagnostic leg only; never hides the main number
+                res["roofline"]["dominant_kernel"] = {"error": str(e)}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:  # diagnostic legs only; never hide the main number
                 res["other_configs"] = other_configs(device)
                 log("other configurations timed")

@@ -1,13 +1,13 @@
 """Per-kernel and whole-run MFMA-busy / HBM-side traffic from two rocprofv3 --pmc passes.  usage: python tools/bench_pmc_summary.py DIR
 [WHAT [ROWS]].  DIR/p1/, DIR/p2/: two separate `rocprofv3 --kernel-trace --output-format csv --pmc ... -d DIR/pN -- python bench.py
---steps 3 --warmup 1 --no-cpu-baseline` runs (kernel trace only beside the counters), p1 with SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES
+--steps 3 --warmup 1 --full --no-cpu-baseline` runs (kernel trace only beside the counters), p1 with SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES
 SQ_WAVE_CYCLES, p2 with TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_HIT_sum TCC_MISS_sum.
 MFMA-busy fraction = (SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs) / (kernel duration x 2.4 GHz): the share of the peak
 MFMA issue slots (the clock behind the 157.3 TFLOP/s figure) the kernel used; durations from the dispatch timestamps
 of the same (profiled) run.  GRBM_GUI_ACTIVE is not used: it is not a per-dispatch cycle count in this rocprofv3."""
 import collections, csv, glob, os, sys
 root = sys.argv[1]
-WHAT = sys.argv[2] if len(sys.argv) > 2 else "'bench.py --steps 3 --warmup 1' (4 sampler calls + the 210-launch dominant-kernel leg)"
+WHAT = sys.argv[2] if len(sys.argv) > 2 else "'bench.py --steps 3 --warmup 1 --full' (4 sampler calls + the 210-launch dominant-kernel leg)"
 NROWS = int(sys.argv[3]) if len(sys.argv) > 3 else 14
 CLK = 2.4e9
 val = collections.defaultdict(lambda: collections.defaultdict(float))   # kernel -> counter -> sum

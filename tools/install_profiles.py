@@ -39,12 +39,12 @@ stats = read("bench_kernel_stats.txt").splitlines(True)
 # in-chain dominant-kernel leg)
 calls = next((l.split("|")[1].strip() for l in stats if "k_xattn_fold" in l), "?")
 write("bench_kernel_stats.txt",
-      head + "rocprofv3 --kernel-trace --stats of 'python bench.py --steps 5 --warmup 2 --no-cpu-baseline' (MI355X, 1 GPU)\n"
+      head + "rocprofv3 --kernel-trace --stats of 'python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline' (MI355X, 1 GPU)\n"
       f"# {calls} sampler calls x (encoder + fold + 10 decoder steps) (warm-up, timed, the 50-call spread leg, the "
       "traced call) + the 210-launch dominant-kernel-alone leg; bench "
       f"line of the same build and box: profiles/{pre}bench.json\n" + "".join(stats[:32]))
 write("bench_pmc.txt",
-      head + "rocprofv3 --kernel-trace --pmc (two separate passes) of 'python bench.py --steps 3 --warmup 1 --no-cpu-baseline'\n"
+      head + "rocprofv3 --kernel-trace --pmc (two separate passes) of 'python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline'\n"
       + read("bench_pmc.txt"))
 lat = read("lat_kernel_stats.txt").splitlines(True)
 write("rollout_b1_kernel_stats.txt",
