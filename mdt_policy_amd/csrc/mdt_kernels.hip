@@ -1268,10 +1268,25 @@ __global__ __launch_bounds__(256) void k_attn(mdt_attn_args a, const float* __re
     attn_tile<HD, TKC, ROPE, false>(a, rope_cos, rope_sin, scale, b, blockIdx.y, gridDim.y, lds, threadIdx.x);
 }
 
+// lanes per (head, query row): one per 16 (hd 16, 48) or 32 (hd 32, 64) dims of the head
+static int attn_lanes(int hd) { return hd == 48 ? 3 : (hd >= 32 ? 2 : 1); }
+
+// head split: the number of workgroups that share a sample, each taking H / hs heads.  Two half-size workgroups per sample from
+// 64 samples on (H even); where a group's (head, query row, slice) triples outnumber the 256 threads, the smallest divisor of H
+// that fits (hs = H always does: Tq * lanes <= 48)
+static int attn_head_split(int H, int Tq, int hd, int B) {
+    const int lp = attn_lanes(hd);
+    const int hs = (H % 2 == 0 && B >= 64) ? 2 : 1;
+    if ((H / hs) * Tq * lp <= 256) return hs;
+    for (int d = 2; d < H; ++d)
+        if (H % d == 0 && (H / d) * Tq * lp <= 256) return d;
+    return H;
+}
+
 template <int HD, int TKC, bool ROPE>
 static hipError_t launch_attn_tt(const mdt_attn_args& a, const float* rc, const float* rs, hipStream_t s) {
     constexpr int LP = HD == 48 ? 3 : (HD >= 32 ? 2 : 1);
-    const int hs = (a.H % 2 == 0 && a.B >= 64) ? 2 : 1;  // head split: 2 half-size workgroups per sample
+    const int hs = attn_head_split(a.H, a.Tq, HD, a.B);
     const int Hl = a.H / hs;
     const size_t lds = ((size_t)(a.Tq + 2 * a.Tk) * Hl * HD + (size_t)Hl * a.Tq * 16 * LP) * sizeof(float);
     static size_t lds_attr_dev[MAX_DEVICES] = {0};
@@ -1302,9 +1317,11 @@ static hipError_t launch_attn_t(const mdt_attn_args& a, const float* rc, const f
 
 hipError_t mdt_launch_attention(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin,
                                 hipStream_t s) {
-    const int lp = a.hd == 48 ? 3 : (a.hd >= 32 ? 2 : 1);
-    const size_t need = ((size_t)(a.Tq + 2 * a.Tk) * a.H * a.hd + (size_t)a.H * a.Tq * 16 * lp) * sizeof(float);
-    if (a.H * a.Tq * lp > 256 || need > 160 * 1024) return hipErrorInvalidValue;
+    if (a.H < 1 || a.Tq < 1 || a.Tq > 16 || a.Tk < 1 || a.Tk > 16) return hipErrorInvalidValue;
+    const int lp = attn_lanes(a.hd);
+    const int Hl = a.H / attn_head_split(a.H, a.Tq, a.hd, a.B);  // heads of one workgroup
+    const size_t need = ((size_t)(a.Tq + 2 * a.Tk) * Hl * a.hd + (size_t)Hl * a.Tq * 16 * lp) * sizeof(float);
+    if (Hl * a.Tq * lp > 256 || need > 160 * 1024) return hipErrorInvalidValue;
     switch (a.hd) {
         case 16: return launch_attn_t<16>(a, rope_cos, rope_sin, s);
         case 32: return launch_attn_t<32>(a, rope_cos, rope_sin, s);

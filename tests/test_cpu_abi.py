@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from mdt_policy_amd import _lib, configs
+from tests.envelope_configs import ENVELOPE
 from tests.helpers import MANIFEST, load_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,6 +51,21 @@ def test_create_without_gpu_reports_an_error_instead_of_crashing():
     h = C.c_void_p()
     st = lib.mdt_create(C.byref(cfg), C.byref(h))
     assert st == 4 and not h.value  # MDT_ERR_HIP
+    assert b"hipMalloc" in lib.mdt_last_error()
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="checks behaviour WITHOUT a GPU")
+@pytest.mark.parametrize("name", sorted(ENVELOPE))
+def test_create_accepts_every_envelope_configuration(name):
+    """Every configuration the GPU envelope test runs passes mdt_create's validation: without a GPU it gets as far as
+    hipMalloc (MDT_ERR_HIP = 4), not MDT_ERR_INVALID_ARG (1) or MDT_ERR_UNSUPPORTED (2)."""
+    from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
+    e = ENVELOPE[name]
+    lib = _lib.load()
+    cfg = GCDenoiser(e["cfg"], 0.5).inner_model._hip_config(0.5, proprio=e["proprio"])
+    h = C.c_void_p()
+    st = lib.mdt_create(C.byref(cfg), C.byref(h))
+    assert st == 4 and not h.value, (name, st, lib.mdt_last_error())
     assert b"hipMalloc" in lib.mdt_last_error()
 
 

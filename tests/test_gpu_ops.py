@@ -496,9 +496,17 @@ def ref_attn(q, k, v, H, causal, rope=False):
     return (att.softmax(-1) @ vh).transpose(1, 2).reshape(B, Tq, D).float()
 
 
+# the edges of what mdt_create accepts: (head, query row, slice) triples beyond the 256 threads of one workgroup per sample
+# (H * Tq * lanes > 256, lanes = 3 / 2 / 1 for head dim 48 / 32 and 64 / 16), odd head counts, one head
+ATTN_EDGES = [(10, 48, 10, 10, True), (10, 48, 10, 10, False), (8, 48, 16, 16, True), (8, 48, 16, 16, False),
+              (8, 48, 16, 5, True), (8, 48, 16, 5, False), (8, 48, 11, 11, True), (32, 16, 10, 10, True),
+              (24, 16, 16, 16, True), (3, 48, 10, 4, True), (1, 64, 16, 16, True), (6, 64, 16, 16, True),
+              (7, 32, 16, 16, True)]
+
+
 @pytest.mark.parametrize("H,hd,Tq,Tk,causal", [(8, 48, 10, 10, True), (8, 48, 10, 4, True), (8, 48, 4, 4, False),
                                                (8, 16, 10, 3, True), (8, 64, 10, 10, True), (4, 32, 16, 16, False),
-                                               (8, 48, 1, 1, True)])
+                                               (8, 48, 1, 1, True)] + ATTN_EDGES)
 @pytest.mark.parametrize("B", [13, 70])  # >= 64 samples: two half-size workgroups per sample (head split)
 def test_attention(lib, H, hd, Tq, Tk, causal, B):
     g = torch.Generator().manual_seed(H + hd + Tq + Tk)
@@ -623,6 +631,17 @@ def test_attention_rope(lib, hd):
                  what="rope attention")
 
 
+@pytest.mark.parametrize("H,hd,Tq,Tk,causal", [e for e in ATTN_EDGES if e[1] >= 32])
+@pytest.mark.parametrize("B", [13, 70])
+def test_attention_rope_at_the_edges(lib, H, hd, Tq, Tk, causal, B):
+    """RoPE (head dim >= 32) at the shapes of ATTN_EDGES: Tq = 16 reaches the last row of the rotary tables."""
+    g = torch.Generator().manual_seed(3 * H + hd + Tq + Tk)
+    D = H * hd
+    q, k, v = (torch.randn(B, T, D, generator=g) for T in (Tq, Tk, Tk))
+    assert_close(run_attn(lib, q, k, v, H, causal, rope=True), ref_attn(q, k, v, H, causal, rope=True), rtol=1e-4, atol=1e-5,
+                 what="rope attention")
+
+
 @pytest.mark.parametrize("D,with_bias", [(384, False), (128, True), (512, True)])
 def test_layernorm(lib, D, with_bias):
     g = torch.Generator().manual_seed(D)
@@ -637,8 +656,17 @@ def test_layernorm(lib, D, with_bias):
 
 
 def test_action_embed(lib):
+    check_action_embed(lib, 7)
+
+
+@pytest.mark.parametrize("A", [1, 8, 9, 16])  # the rest of the accepted 1..16
+def test_action_embed_other_widths(lib, A):
+    check_action_embed(lib, A)
+
+
+def check_action_embed(lib, A):
     g = torch.Generator().manual_seed(2)
-    B, T, A, D, sd = 11, 10, 7, 384, 0.5
+    B, T, D, sd = 11, 10, 384, 0.5
     x, Wa, ba = torch.randn(B * T, A, generator=g) * 30, torch.randn(D, A, generator=g), torch.randn(D, generator=g)
     sigma = torch.rand(B, generator=g) * 50 + 0.01
     xd, Wd, bd, sg = dev(x), dev(Wa.T), dev(ba), dev(sigma)  # the library keeps action_emb.weight as (A, D)
@@ -652,8 +680,18 @@ def test_action_embed(lib):
 
 @pytest.mark.parametrize("mode", ["denoised", "ddim", "raw"])
 def test_head(lib, mode):
+    check_head(lib, mode, 7)
+
+
+@pytest.mark.parametrize("A", [1, 8, 9, 16])  # A > 8: the 16-wide instantiation
+@pytest.mark.parametrize("mode", ["denoised", "ddim", "raw"])
+def test_head_other_widths(lib, mode, A):
+    check_head(lib, mode, A)
+
+
+def check_head(lib, mode, A):
     g = torch.Generator().manual_seed(4)
-    B, T, A, D, sd = 6, 10, 7, 384, 0.5
+    B, T, D, sd = 6, 10, 384, 0.5
     M = B * T
     y, lw = torch.randn(M, D, generator=g) * 2, torch.randn(D, generator=g) * 0.1 + 1
     Wp, bp = torch.randn(A, D, generator=g) / 20, torch.randn(A, generator=g)

@@ -25,6 +25,15 @@ def rnd(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
+# head counts the shipped models never use: one head per workgroup of the MFMA kernels (odd H: HG = 1), two (H = 6, 10) and
+# four (H = 24, 32), each head dim, Tq = Tk = 16; RoPE with odd H
+TRAIN_ATTN_EDGES = [(16, 1, 16, 16, 1, 0), (32, 3, 10, 10, 1, 0), (48, 5, 10, 4, 1, 0), (64, 7, 16, 16, 0, 0),
+                    (48, 3, 16, 16, 1, 0), (16, 7, 10, 10, 0, 0), (32, 5, 16, 5, 1, 0), (64, 1, 10, 10, 1, 0),
+                    (64, 6, 16, 16, 1, 0), (48, 10, 10, 10, 1, 0), (32, 10, 16, 16, 0, 0),
+                    (16, 32, 16, 16, 1, 0), (16, 24, 10, 10, 0, 0), (32, 16, 16, 16, 1, 0),
+                    (48, 5, 16, 16, 1, 1), (32, 7, 10, 4, 1, 1), (64, 1, 16, 16, 1, 1)]
+
+
 def test_pack_weight_t_layout(lib):
     W = rnd(48, 32, seed=1)                         # (rows, cols) -> image of W^T (N' = 32, K' = 64) at k offset 16
     P = torch.zeros(32 * 64, device="cuda")
@@ -138,7 +147,7 @@ def test_layernorm_shift_only_conditioning_accumulates_its_gradient(lib):
 @pytest.mark.parametrize("hd,H,Tq,Tk,causal,rope", [(48, 8, 10, 10, 1, 0), (48, 8, 10, 4, 1, 0), (48, 8, 4, 4, 0, 0),
                                                    (16, 8, 10, 5, 1, 0), (64, 2, 16, 16, 1, 0), (32, 4, 7, 3, 0, 0),
                                                    (48, 8, 10, 10, 1, 1), (48, 8, 10, 4, 1, 1), (32, 4, 7, 3, 0, 1),
-                                                   (64, 2, 16, 16, 1, 1)])
+                                                   (64, 2, 16, 16, 1, 1)] + TRAIN_ATTN_EDGES)
 def test_attention_backward(lib, hd, H, Tq, Tk, causal, rope):
     B, Dm = 3, H * hd
     rc, rs = _rope_tables()
@@ -356,7 +365,8 @@ def test_fused_pairs_of_the_training_step_equal_their_two_launches(lib, B, rps, 
 
 
 @pytest.mark.parametrize("hd,H,Tq,Tk,causal,rope", [(48, 8, 10, 10, 1, 0), (48, 8, 10, 4, 1, 0), (16, 4, 4, 4, 0, 0),
-                                                   (48, 8, 10, 10, 1, 1), (32, 4, 10, 4, 1, 1), (64, 2, 5, 16, 0, 1)])
+                                                   (48, 8, 10, 10, 1, 1), (32, 4, 10, 4, 1, 1), (64, 2, 5, 16, 0, 1)]
+                         + TRAIN_ATTN_EDGES)
 def test_attention_dropout_forward_and_backward(lib, hd, H, Tq, Tk, causal, rope):
     B, Dm, p, seed, site = 5, H * hd, 0.3, 987654321, 11
     L = lib.load()
@@ -405,6 +415,27 @@ def test_attention_dropout_forward_and_backward(lib, hd, H, Tq, Tk, causal, rope
     assert_close(dq.cpu(), q64.grad, what="dq", **G_TOL)
     assert_close(dkv[:, :Dm].cpu(), k64.grad, what="dk", **G_TOL)
     assert_close(dkv[:, Dm:].cpu(), v64.grad, what="dv", **G_TOL)
+
+
+@pytest.mark.parametrize("hd,H,Tq,Tk,causal,rope", [(48, 8, 10, 10, 1, 0), (48, 8, 10, 4, 1, 0), (16, 8, 10, 5, 1, 0),
+                                                   (64, 8, 10, 10, 1, 0), (48, 8, 10, 10, 1, 1)] + TRAIN_ATTN_EDGES)
+def test_attention_train_forward_without_dropout(lib, hd, H, Tq, Tk, causal, rope):
+    """The training forward at p = 0 (the model's forward wherever the MFMA form applies) against float64 attention."""
+    B, Dm = 7, H * hd
+    rc, rs = _rope_tables()
+    q, kv = rnd(B * Tq, Dm, seed=71), rnd(B * Tk, 2 * Dm, seed=72)
+    qd, kvd = dev(q), dev(kv)
+    out = torch.full((B * Tq, Dm), float("nan"), device="cuda")
+    a = lib.AttnTrainArgs(q=qd.data_ptr(), ldq=Dm, k=kvd.data_ptr(), v=kvd.data_ptr() + 4 * Dm, ldkv=2 * Dm,
+                          out=out.data_ptr(), ldo=Dm, B=B, H=H, hd=hd, Tq=Tq, Tk=Tk, causal=causal, p=0.0, site=0, seed=0,
+                          rope=rope, rope_cos=rc.data_ptr(), rope_sin=rs.data_ptr())
+    lib.check(lib.load().mdt_op_attn_fwd_train(C.byref(a), stream()))
+    split = lambda t, T: t.double().view(B, T, H, hd).transpose(1, 2)
+    att = _rot(split(q, Tq), rope) @ _rot(split(kv[:, :Dm], Tk), rope).transpose(-1, -2) / hd ** 0.5
+    if causal:
+        att = att.masked_fill(~torch.ones(Tq, Tk, dtype=torch.bool).tril(), float("-inf"))
+    want = (att.softmax(-1) @ split(kv[:, Dm:], Tk)).transpose(1, 2).reshape(B * Tq, Dm)
+    assert_close(out.cpu(), want, rtol=1e-4, atol=1e-5, what="training attention forward, p = 0")
 
 
 @pytest.mark.parametrize("M,N,K", [(8200, 384, 384), (8192, 1152, 384), (10240, 640, 128), (33000, 192, 768), (32768, 384, 384),
