@@ -311,6 +311,40 @@ mdt_status mdt_sample_dpm_adaptive(mdt_model *m, const float *tokens, const floa
                                    const mdt_dpm_adaptive_params *params, int64_t batch, float *out, float *ctx_out,
                                    mdt_dpm_adaptive_info *info, void *stream);
 
+/* Classifier-free guidance.  With D(x; sigma, g) the GCDenoiser output and D(x; sigma, 0) the same call with uncond=True (the
+ * goal zeroed before its embedding, reference mdtv_transformer.py:246-258), the guided denoiser is
+ *     D_lambda(x; sigma) = D(x; sigma, 0) + lambda (D(x; sigma, g) - D(x; sigma, 0))
+ * lambda = 1: the conditional model; 0: the unconditional one; > 1: a stronger pull towards the goal.  Any finite lambda is
+ * accepted; NaN / +-Inf give MDT_ERR_INVALID_ARG before anything is enqueued.  c_skip x is the same in both branches, so the
+ * calls combine the network outputs instead, F = F_0 + lambda (F_g - F_0) in fp32 per element before the output scaling.
+ *
+ * Each call takes the arguments of its unguided twin plus `cond_lambda`.  At lambda == 1, and on a model without a goal token
+ * (goal_conditioned=False with MDT, or with MDT-V and use_proprio: there `uncond` changes nothing), it runs the unguided call
+ * and gives its bits.  Otherwise ONE call runs the sampler loop over 2B samples: [0, B) conditional, [B, 2B) the same state
+ * tokens with a zero goal (and the same `modality` embedder).  The 2B encoder inputs are staged inside the stream (handle-owned
+ * buffers, no host synchronisation: capture-safe like the unguided calls); the encoder, the cross-attention K/V and every
+ * decoder pass run at 2B; each action head reads rows r and r + B Ta, combines them and updates the B samples of state.  The
+ * noise rows are those of the unguided call at B (the host loop's draws).  ctx_out receives the conditional context (B, Te, d).
+ * The workspace grows for 2B samples: mdt_reserve(m, 2 B) before capturing a guided call. */
+mdt_status mdt_sample_ddim_guided(mdt_model *m, const float *tokens, const float *tokens2, const float *goal,
+                                  int32_t modality, const float *x_T, const float *sigmas_host, int32_t n_steps,
+                                  int64_t batch, float *out, float *ctx_out, float cond_lambda, void *stream);
+mdt_status mdt_sample_ddim_dev_guided(mdt_model *m, const float *tokens, const float *tokens2, const float *goal,
+                                      int32_t modality, const float *x_T, const float *sigmas_dev, int32_t n_steps,
+                                      int64_t batch, float *out, float *ctx_out, float cond_lambda, void *stream);
+mdt_status mdt_sample_guided(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                             const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_host,
+                             int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out, float *ctx_out,
+                             float cond_lambda, void *stream);
+mdt_status mdt_sample_dev_guided(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                                 const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_dev,
+                                 int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out,
+                                 float *ctx_out, float cond_lambda, void *stream);
+mdt_status mdt_sample_dpm_adaptive_guided(mdt_model *m, const float *tokens, const float *tokens2, const float *goal,
+                                          int32_t modality, const float *x_T, float sigma_min, float sigma_max,
+                                          const mdt_dpm_adaptive_params *params, int64_t batch, float *out, float *ctx_out,
+                                          float cond_lambda, mdt_dpm_adaptive_info *info, void *stream);
+
 /* GCDenoiser.loss(state, action, goal, noise, sigma) forward value, eval mode (reference
  * score_wrappers.py:45-63): noised = a + n*sigma; F = inner(noised*c_in); target = (a - c_skip*noised)/c_out;
  * loss = mean((F - target)^2) over all B*Ta*A elements.  loss_out: 1 float (device); model_output: (B,Ta,A). */

@@ -223,6 +223,14 @@ SYMBOLS = [
     ("mdt_sampler_plan", _I32, [_I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, C.POINTER(SamplerPlan)]),
     ("mdt_sample_dpm_adaptive", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.c_float, C.c_float, C.POINTER(DpmAdaptiveParams), _I64,
                                        _VP, _VP, C.POINTER(DpmAdaptiveInfo), _VP]),
+    ("mdt_sample_ddim_guided", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(C.c_float), _I32, _I64, _VP, _VP, _F, _VP]),
+    ("mdt_sample_ddim_dev_guided", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _I64, _VP, _VP, _F, _VP]),
+    ("mdt_sample_guided", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, _VP,
+                                 _I32, _I64, _VP, _VP, _F, _VP]),
+    ("mdt_sample_dev_guided", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), _VP, _I32, _VP, _I32, _I64,
+                                     _VP, _VP, _F, _VP]),
+    ("mdt_sample_dpm_adaptive_guided", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.c_float, C.c_float, C.POINTER(DpmAdaptiveParams),
+                                              _I64, _VP, _VP, _F, C.POINTER(DpmAdaptiveInfo), _VP]),
     ("mdt_dpm_control_init", _I32, [C.POINTER(DpmControl)] + [C.c_double] * 6),
     ("mdt_dpm_control_update", _I32, [C.POINTER(DpmControl), C.c_float, C.POINTER(C.c_int32)]),
     ("mdt_dpm_adaptive_plan", _I32, [_I32, C.c_float, C.c_float, C.POINTER(SamplerPlan)]),

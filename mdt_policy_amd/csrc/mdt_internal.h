@@ -115,18 +115,19 @@ constexpr int MDT_SCHED_MAX = 64;
 struct mdt_sched_arg { float s[MDT_SCHED_MAX + 1]; };
 hipError_t mdt_launch_sample_prep(const float* sigmas_dev, const float* sigmas_host, int n_steps, float* steps, const float* freqs,
                                   float* sig_e, int D, const float* x, float sd, const float* Wa, const float* ba, float* y, int M,
-                                  int A, hipStream_t s);
+                                  int A, hipStream_t s, int Mx = 0);
+// (Mx: rows of x; 0 = M.  The guided sampler passes M = 2 Mx: the embedding goes to both halves of y)
 // the other samplers' once-per-call work (mdt_kernels.hip: k_sampler_plan + k_sampler_first): the plan of mdt_sampler_plan.h
 // built on the device, the sigma embeddings of every evaluation (sig_e == nullptr: none), the first input Y_0 -> y0 (M, A), the
 // four history slots hist (4, M, A) zeroed, and Y_0's action embedding -> y
 hipError_t mdt_launch_sampler_prep(const float* sigmas_dev, const float* sigmas_host, int n_steps, int kind,
                                    const mdt_sampler_params& prm, mdt_sampler_plan_t* plan, const float* freqs, float* sig_e,
                                    int D, const float* x, const float* noise, int n_noise, float* y0, float* hist, float sd, const float* Wa,
-                                   const float* ba, float* y, int M, int A, hipStream_t s);
+                                   const float* ba, float* y, int M, int A, hipStream_t s, int Mx = 0);
 // k_sampler_first alone (the adaptive DPM-Solver's per-attempt first input, from a plan uploaded by the host)
 hipError_t mdt_launch_sampler_first(const mdt_sampler_plan_t* plan, const float* x, const float* noise, int n_noise, float* y0,
                                     float* hist, float sd, const float* Wa, const float* ba, float* y, int M, int A, int D,
-                                    hipStream_t s);
+                                    hipStream_t s, int Mx = 0);
 // the adaptive DPM-Solver's scaled-error partial sums (mdt_kernels.hip: k_dpm_error): mdt_dpm_error_parts(nel) floats -> part
 constexpr int MDT_DPM_PARTS = 256;
 int mdt_dpm_error_parts(int64_t nel);
@@ -144,6 +145,12 @@ struct mdt_head_plan {
                                 // to stay inside the caller's buffer)
 };
 hipError_t mdt_launch_head_plan(const mdt_head_args& a, const mdt_head_plan& pl, hipStream_t s);
+// classifier-free guidance: the head (pl == nullptr) or the plan head on a.M state rows whose decoder rows are a.y's [0, M)
+// (conditional) and [M, 2M) (unconditional); F = F_u + lam (F_g - F_u); y_next (if any) receives 2M rows
+hipError_t mdt_launch_head_guided(const mdt_head_args& a, const mdt_head_plan* pl, float lam, hipStream_t s);
+// the guided sampler's 2B encoder inputs (tokens and tokens2 twice, the goal then zeros) in one launch
+hipError_t mdt_launch_guide_stage(const float* tok, const float* tok2, const float* goal, float* tok_o, float* tok2_o, float* goal_o,
+                                  int B, int w1, int w2, int G, hipStream_t s);
 hipError_t mdt_launch_action_embed(const float* x, const float* sigma, int64_t sstride, float sd, const float* Wa,
                                    const float* ba, float* y, int M, int A, int D, int rps, hipStream_t s);
 hipError_t mdt_launch_head(const mdt_head_args& a, hipStream_t s);

@@ -1486,22 +1486,25 @@ hipError_t mdt_launch_action_embed(const float* x, const float* sigma, int64_t s
 // {sigma_{i+1}/sigma_i as exp(-t')/exp(-t), -expm1(-h), sigma_{i+1}, sigma_i} with t = -ln sigma, h = t' - t (gc_sampling.py:946-950,
 // fp32 like the reference's tensors) -- each from the schedule itself, so nothing in the launch depends on anything else in it, and every value has the bits the
 // separate kernels gave.
+// DUP (the guided sampler's doubled batch): x holds Mx rows and y receives M = 2 Mx, row m + Mx the same embedding as row m.
 // ------------------------------------------------------------------------------------------------
+template <bool DUP>
 __global__ __launch_bounds__(256) void k_sample_prep(const float* __restrict__ sig_dev, mdt_sched_arg sv, int n_steps,
                                                      float* __restrict__ steps, const float* __restrict__ freqs,
                                                      float* __restrict__ sig_e, int D, const float* __restrict__ x, float sd,
                                                      const float* __restrict__ WaT, const float* __restrict__ ba,
-                                                     float* __restrict__ y, int M, int A, int n_act, int n_emb) {
+                                                     float* __restrict__ y, int M, int A, int n_act, int n_emb, int Mx) {
     const int b = blockIdx.x;
     if (b < n_act) {
         const int n4 = D >> 2;
         const int64_t idx = (int64_t)b * 256 + threadIdx.x;
         if (idx >= (int64_t)M * n4) return;
         const int m = (int)(idx / n4), n = (int)(idx % n4) * 4;
+        const int mx = DUP && m >= Mx ? m - Mx : m;
         const float cin = edm_c_in(sig_dev ? sig_dev[0] : sv.s[0], sd);
         f32x4 acc = *(const f32x4*)(ba + n);
         for (int c = 0; c < A; ++c) {
-            const float xv = x[(int64_t)m * A + c] * cin;
+            const float xv = x[(int64_t)mx * A + c] * cin;
             const f32x4 w = *(const f32x4*)(WaT + (int64_t)c * D + n);
             acc.x = fmaf(xv, w.x, acc.x); acc.y = fmaf(xv, w.y, acc.y);
             acc.z = fmaf(xv, w.z, acc.z); acc.w = fmaf(xv, w.w, acc.w);
@@ -1531,15 +1534,21 @@ __global__ __launch_bounds__(256) void k_sample_prep(const float* __restrict__ s
 // sigmas_dev or sigmas_host (exactly one non-null): n_steps + 1 levels, n_steps <= MDT_SCHED_MAX; sig_e == nullptr: no embeddings
 hipError_t mdt_launch_sample_prep(const float* sigmas_dev, const float* sigmas_host, int n_steps, float* steps, const float* freqs,
                                   float* sig_e, int D, const float* x, float sd, const float* Wa, const float* ba, float* y, int M,
-                                  int A, hipStream_t s) {
+                                  int A, hipStream_t s, int Mx) {
     if (n_steps < 1 || n_steps > MDT_SCHED_MAX || (!sigmas_dev) == (!sigmas_host) || (D & 3)) return hipErrorInvalidValue;
+    if (Mx <= 0) Mx = M;
+    if (Mx != M && M != 2 * Mx) return hipErrorInvalidValue;
     mdt_sched_arg sv;
     memset(&sv, 0, sizeof sv);
     if (sigmas_host) memcpy(sv.s, sigmas_host, (size_t)(n_steps + 1) * sizeof(float));
     const int n_act = (int)(((int64_t)M * (D / 4) + 255) / 256);
     const int n_emb = sig_e ? (n_steps * (D / 2) + 255) / 256 : 0;
-    hipLaunchKernelGGL(k_sample_prep, dim3(n_act + n_emb + 1), dim3(256), 0, s, sigmas_dev, sv, n_steps, steps, freqs, sig_e, D, x, sd,
-                       Wa, ba, y, M, A, n_act, n_emb);
+    if (Mx == M)
+        hipLaunchKernelGGL(k_sample_prep<false>, dim3(n_act + n_emb + 1), dim3(256), 0, s, sigmas_dev, sv, n_steps, steps, freqs, sig_e, D,
+                           x, sd, Wa, ba, y, M, A, n_act, n_emb, Mx);
+    else
+        hipLaunchKernelGGL(k_sample_prep<true>, dim3(n_act + n_emb + 1), dim3(256), 0, s, sigmas_dev, sv, n_steps, steps, freqs, sig_e, D,
+                           x, sd, Wa, ba, y, M, A, n_act, n_emb, Mx);
     return hipGetLastError();
 }
 
@@ -1577,24 +1586,29 @@ __global__ __launch_bounds__(256) void k_sampler_plan(const float* __restrict__ 
     }
 }
 
+// DUP: the state (x, y0, hist, noise) has Mx rows, y receives M = 2 Mx (row m + Mx embeds the same input as row m)
+template <bool DUP>
 __global__ __launch_bounds__(256) void k_sampler_first(const mdt_sampler_plan_t* __restrict__ plan, const float* __restrict__ x,
                                                        const float* __restrict__ noise, int n_noise, float* __restrict__ y0,
                                                        float* __restrict__ hist, float sd, const float* __restrict__ WaT,
-                                                       const float* __restrict__ ba, float* __restrict__ y, int M, int A, int D) {
+                                                       const float* __restrict__ ba, float* __restrict__ y, int M, int A, int D,
+                                                       int Mx) {
     const int n4 = D >> 2;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (int64_t)M * n4) return;
     const int m = (int)(idx / n4), n = (int)(idx % n4) * 4;
-    const int64_t nel = (int64_t)M * A;
+    const bool dup = DUP && m >= Mx;
+    const int mx = dup ? m - Mx : m;
+    const int64_t nel = (int64_t)Mx * A;
     const float cin = edm_c_in(plan->e[0].sigma, sd);
     const int row = (noise && plan->y0_noise < n_noise) ? plan->y0_noise : -1;  // a row outside the buffer reads as 0
     const float cn = plan->y0_cn;
     f32x4 acc = *(const f32x4*)(ba + n);
     for (int c = 0; c < A; ++c) {
-        const int64_t k = (int64_t)m * A + c;
+        const int64_t k = (int64_t)mx * A + c;
         float v = x[k];
         if (row >= 0 && cn != 0.f) v = v + noise[row * nel + k] * cn;
-        if (n == 0) {
+        if (n == 0 && !dup) {
             y0[k] = v;
             for (int h = 0; h < 4; ++h) hist[h * nel + k] = 0.f;
         }
@@ -1609,7 +1623,7 @@ __global__ __launch_bounds__(256) void k_sampler_first(const mdt_sampler_plan_t*
 hipError_t mdt_launch_sampler_prep(const float* sigmas_dev, const float* sigmas_host, int n_steps, int kind,
                                    const mdt_sampler_params& prm, mdt_sampler_plan_t* plan, const float* freqs, float* sig_e,
                                    int D, const float* x, const float* noise, int n_noise, float* y0, float* hist, float sd, const float* Wa,
-                                   const float* ba, float* y, int M, int A, hipStream_t s) {
+                                   const float* ba, float* y, int M, int A, hipStream_t s, int Mx) {
     const int levels = mdt_plan_levels(kind, n_steps);
     if (n_steps < 1 || n_steps > MDT_SAMPLER_MAX_EVALS || levels > MDT_SCHED_MAX + 1 || (!sigmas_dev) == (!sigmas_host) || (D & 3))
         return hipErrorInvalidValue;
@@ -1619,16 +1633,22 @@ hipError_t mdt_launch_sampler_prep(const float* sigmas_dev, const float* sigmas_
     hipLaunchKernelGGL(k_sampler_plan, dim3(1), dim3(256), 0, s, sigmas_dev, sv, n_steps, kind, prm, plan, freqs, sig_e, D);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return mdt_launch_sampler_first(plan, x, noise, n_noise, y0, hist, sd, Wa, ba, y, M, A, D, s);
+    return mdt_launch_sampler_first(plan, x, noise, n_noise, y0, hist, sd, Wa, ba, y, M, A, D, s, Mx);
 }
 
 hipError_t mdt_launch_sampler_first(const mdt_sampler_plan_t* plan, const float* x, const float* noise, int n_noise, float* y0,
                                     float* hist, float sd, const float* Wa, const float* ba, float* y, int M, int A, int D,
-                                    hipStream_t s) {
+                                    hipStream_t s, int Mx) {
     if (D & 3) return hipErrorInvalidValue;
+    if (Mx <= 0) Mx = M;
+    if (Mx != M && M != 2 * Mx) return hipErrorInvalidValue;
     const int64_t n = (int64_t)M * (D / 4);
-    hipLaunchKernelGGL(k_sampler_first, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, plan, x, noise, n_noise, y0, hist, sd, Wa, ba,
-                       y, M, A, D);
+    if (Mx == M)
+        hipLaunchKernelGGL(k_sampler_first<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, plan, x, noise, n_noise, y0, hist,
+                           sd, Wa, ba, y, M, A, D, Mx);
+    else
+        hipLaunchKernelGGL(k_sampler_first<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, plan, x, noise, n_noise, y0, hist,
+                           sd, Wa, ba, y, M, A, D, Mx);
     return hipGetLastError();
 }
 
@@ -1680,6 +1700,75 @@ __global__ __launch_bounds__(256) void k_head_plan(mdt_head_args a, mdt_head_pla
     const int base = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (base >= a.M) return;  // wave-uniform
     head_rows<AMAX, false, XP, 1, true>(a, base, threadIdx.x & 63, zeros, &pl);
+}
+
+// classifier-free guidance (mdt_tiles.h: head_rows GUIDE): a.M rows of state, a.y holds 2 a.M rows -- conditional [0, M),
+// unconditional [M, 2M) -- and the next input's embedding goes to both halves of a.y_next.  One wave per state row.
+template <int AMAX, int XP>
+__global__ __launch_bounds__(256) void k_head_guided(mdt_head_args a, float lam, const float* __restrict__ zeros) {
+    const int base = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (base >= a.M) return;  // wave-uniform
+    head_rows<AMAX, false, XP, 2, false, true>(a, base, threadIdx.x & 63, zeros, nullptr, lam);
+}
+
+template <int AMAX, int XP>
+__global__ __launch_bounds__(256) void k_head_plan_guided(mdt_head_args a, mdt_head_plan pl, float lam,
+                                                          const float* __restrict__ zeros) {
+    const int base = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (base >= a.M) return;  // wave-uniform
+    head_rows<AMAX, false, XP, 2, true, true>(a, base, threadIdx.x & 63, zeros, &pl, lam);
+}
+
+// pl == nullptr: the DDIM / denoiser head (k_head_guided), else the plan head (k_head_plan_guided)
+template <int AMAX, int XP>
+static void launch_head_guided(const mdt_head_args& a, const mdt_head_plan* pl, float lam, int grid, hipStream_t s) {
+    if (pl) hipLaunchKernelGGL((k_head_plan_guided<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, *pl, lam, g_zeros);
+    else hipLaunchKernelGGL((k_head_guided<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, lam, g_zeros);
+}
+
+hipError_t mdt_launch_head_guided(const mdt_head_args& a, const mdt_head_plan* pl, float lam, hipStream_t s) {
+    hipError_t e = ensure_zeros();
+    if (e != hipSuccess) return e;
+    const int grid = (a.M + 3) / 4;
+    if (a.y_parts > 1) {
+        if (a.A > 8 || a.y_parts > 4) return hipErrorInvalidValue;
+        switch (a.y_parts) {
+            case 2: launch_head_guided<8, 2>(a, pl, lam, grid, s); break;
+            case 3: launch_head_guided<8, 3>(a, pl, lam, grid, s); break;
+            default: launch_head_guided<8, 4>(a, pl, lam, grid, s); break;
+        }
+        return hipGetLastError();
+    }
+    if (a.A <= 8) launch_head_guided<8, 1>(a, pl, lam, grid, s);
+    else launch_head_guided<16, 1>(a, pl, lam, grid, s);
+    return hipGetLastError();
+}
+
+// The guided sampler's encoder inputs for 2B samples in one launch: sample b and b + B get the caller's tokens (w1 floats per
+// sample) and tokens2 (w2, may be 0); the goal (G) is the caller's for b < B and zero for b >= B (preprocess_goals with uncond).
+__global__ __launch_bounds__(256) void k_guide_stage(const float* __restrict__ tok, const float* __restrict__ tok2,
+                                                     const float* __restrict__ goal, float* __restrict__ tok_o,
+                                                     float* __restrict__ tok2_o, float* __restrict__ goal_o, int B, int w1,
+                                                     int w2, int G) {
+    const int W = w1 + w2 + G;
+    const int64_t n = (int64_t)2 * B * W;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int b2 = (int)(i / W), c = (int)(i % W);
+        const int b = b2 >= B ? b2 - B : b2;
+        if (c < w1) tok_o[(int64_t)b2 * w1 + c] = tok[(int64_t)b * w1 + c];
+        else if (c < w1 + w2) tok2_o[(int64_t)b2 * w2 + (c - w1)] = tok2[(int64_t)b * w2 + (c - w1)];
+        else goal_o[(int64_t)b2 * G + (c - w1 - w2)] = b2 < B ? goal[(int64_t)b * G + (c - w1 - w2)] : 0.f;
+    }
+}
+
+hipError_t mdt_launch_guide_stage(const float* tok, const float* tok2, const float* goal, float* tok_o, float* tok2_o, float* goal_o,
+                                  int B, int w1, int w2, int G, hipStream_t s) {
+    if (B < 1 || w1 < 0 || w2 < 0 || G < 0 || (w2 > 0 && (!tok2 || !tok2_o))) return hipErrorInvalidValue;
+    const int64_t n = (int64_t)2 * B * (w1 + w2 + G);
+    if (n == 0) return hipSuccess;
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_guide_stage, dim3(grid), dim3(256), 0, s, tok, tok2, goal, tok_o, tok2_o, goal_o, B, w1, w2, G);
+    return hipGetLastError();
 }
 
 hipError_t mdt_launch_head_plan(const mdt_head_args& a, const mdt_head_plan& pl, hipStream_t s) {

@@ -570,6 +570,10 @@ static mdt_status check_loaded(const mdt_model* m) { return mdt_check_loaded(m->
 // ------------------------------------------------------------------------------------------------
 // workspace
 // ------------------------------------------------------------------------------------------------
+// floats per sample of the encoder inputs `tokens` and `tokens2` (0: none)
+static int guide_w1(const mdt_model* m) { return (m->cfg.arch == MDT_ARCH_MDTV ? m->n_tok : 1) * m->O; }
+static int guide_w2(const mdt_model* m) { return m->cfg.arch == MDT_ARCH_MDT ? m->O : m->Pd; }
+
 static void carve_ws(mdt_model* m, Bump& b, int64_t B) {
     const int64_t Re = (int64_t)m->Te * B, Ra = (int64_t)m->Ta * B, Rx = std::max(Re, Ra);
     const int64_t Rm = std::max<int64_t>(B, MAX_EVALS);  // conditioning rows: one per sample or per sampler evaluation
@@ -602,6 +606,9 @@ static void carve_ws(mdt_model* m, Bump& b, int64_t B) {
         m->xW = b.take((size_t)m->Ld * B * np * D);
         m->xc = b.take((size_t)m->Ld * B * np);
     }
+    m->g_tok = b.take((size_t)B * guide_w1(m));
+    m->g_tok2 = b.take((size_t)B * guide_w2(m));
+    m->g_goal = b.take((size_t)B * m->G);
 }
 
 extern "C" mdt_status mdt_reserve(mdt_model* m, int64_t max_batch) {
@@ -1092,24 +1099,68 @@ static mdt_head_args head_args(mdt_model* m, const float* y, int64_t B, const fl
 // next step's embedding).  MLP head (linear_output = 0): decoder LN -> action_pred.0 + GELU on the GEMM ->
 // action_pred.2 and the rest in the head kernel reading the hidden layer as it is; `scratch` holds M * (D + HP)
 // floats (the slice's MLP hidden buffer is free at this point); the next step's embedding is its own launch then.
-static mdt_status run_head(mdt_model* m, mdt_head_args h, float* scratch, const float* sigma_next, hipStream_t s) {
+// Classifier-free guidance of a sampler call (mdt_sample_*_guided): `on` = the call runs the doubled batch, conditional samples
+// [0, B) and unconditional ones [B, 2B), and its heads combine the two halves with `lam`.
+struct Guide {
+    bool on = false;
+    float lam = 1.f;
+};
+
+// The guided MLP head's scratch and the unguided one's are the same buffer: 2 M (D + HP) floats of the 2B-sample slice's hidden
+// buffer (4 D floats per row, HP <= 3 D).
+static mdt_status run_head(mdt_model* m, mdt_head_args h, float* scratch, const float* sigma_next, hipStream_t s,
+                           Guide gd = Guide()) {
     if (m->HP == 0) {
-        LAUNCH(mdt_launch_head(h, s));
+        if (gd.on) LAUNCH(mdt_launch_head_guided(h, nullptr, gd.lam, s));
+        else LAUNCH(mdt_launch_head(h, s));
         return MDT_OK;
     }
     const int D = m->D, HP = m->HP;
+    const int rows = gd.on ? 2 * h.M : h.M;  // decoder rows: both halves go through the LN and the hidden layer
     float* ln = scratch;
-    float* hh = scratch + (int64_t)h.M * D;
-    LAUNCH(mdt_launch_layernorm(h.y, m->dec_ln_w, m->dec_ln_b, ln, h.M, D, s));
-    mdt_gemm_args g = gemm_args(ln, D, m->head0, hh, HP, h.M);
+    float* hh = scratch + (int64_t)rows * D;
+    LAUNCH(mdt_launch_layernorm(h.y, m->dec_ln_w, m->dec_ln_b, ln, rows, D, s));
+    mdt_gemm_args g = gemm_args(ln, D, m->head0, hh, HP, rows);
     g.act = MDT_ACT_GELU;
     LAUNCH(mdt_launch_gemm(g, s));
     float* y_next = h.y_next;
     h.y = hh; h.D = HP; h.no_ln = 1; h.y_next = nullptr;
-    LAUNCH(mdt_launch_head(h, s));
-    if (y_next)
+    if (gd.on) LAUNCH(mdt_launch_head_guided(h, nullptr, gd.lam, s));
+    else LAUNCH(mdt_launch_head(h, s));
+    if (y_next) {
         LAUNCH(mdt_launch_action_embed(h.out, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next, h.M, m->A, D,
                                        m->Ta, s));
+        if (gd.on)  // the unconditional half embeds the same state
+            LAUNCH(mdt_launch_action_embed(h.out, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next + (int64_t)h.M * D, h.M,
+                                           m->A, D, m->Ta, s));
+    }
+    return MDT_OK;
+}
+
+// Validate lam and decide whether a guided entry point runs the doubled batch: lam == 1 and a model without a goal token
+// (m->g_row < 0: `uncond` changes nothing there) take the unguided implementation and give its exact bits.
+static mdt_status guide_of(const mdt_model* m, float lam, const char* who, Guide* gd) {
+    if (!m) return fail(MDT_ERR_INVALID_ARG, "%s: null handle", who);
+    if (!std::isfinite(lam)) return fail(MDT_ERR_INVALID_ARG, "%s: cond_lambda must be finite", who);
+    gd->on = lam != 1.f && m->g_row >= 0;
+    gd->lam = lam;
+    return MDT_OK;
+}
+
+// the guided call's encoder inputs in the handle's staging buffers (after mdt_reserve(2B)); the pointers are redirected there
+static mdt_status guide_stage(mdt_model* m, const float*& tokens, const float*& tokens2, const float*& goal, int64_t B,
+                              hipStream_t s) {
+    const int w1 = guide_w1(m), w2 = tokens2 ? guide_w2(m) : 0;
+    LAUNCH(mdt_launch_guide_stage(tokens, tokens2, goal, m->g_tok, m->g_tok2, m->g_goal, (int)B, w1, w2, m->G, s));
+    tokens = m->g_tok;
+    tokens2 = tokens2 ? m->g_tok2 : nullptr;
+    goal = m->g_goal;
+    return MDT_OK;
+}
+
+// the conditional half of the cached context -> ctx_out (what the unguided call writes there)
+static mdt_status guide_ctx_out(mdt_model* m, float* ctx_out, int64_t B, hipStream_t s) {
+    if (ctx_out) HIP_TRY(hipMemcpyAsync(ctx_out, m->ctx, (size_t)B * m->Te * m->D * sizeof(float), hipMemcpyDeviceToDevice, s));
     return MDT_OK;
 }
 
@@ -1155,9 +1206,10 @@ extern "C" mdt_status mdt_forward(mdt_model* m, const float* tokens, const float
 }
 
 // sigmas_host or sigmas_dev (exactly one non-null): the n_steps + 1 noise levels
+// gd.on (guided): the encoder and the decoder run 2B samples, the head combines the halves and updates B samples of state
 static mdt_status sample_ddim_impl(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                    int32_t modality, const float* x_T, const float* sigmas, const float* sigmas_dev,
-                                   int32_t n_steps, int64_t batch, float* out, float* ctx_out, void* stream) {
+                                   int32_t n_steps, int64_t batch, float* out, float* ctx_out, void* stream, Guide gd = Guide()) {
     if (!m || !x_T || (!sigmas && !sigmas_dev) || !out || batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_ddim: bad argument");
     if (n_steps < 1 || n_steps > MAX_STEPS) return fail(MDT_ERR_INVALID_ARG, "n_steps must be 1..%d", MAX_STEPS);
     hipStream_t s = (hipStream_t)stream;
@@ -1165,7 +1217,13 @@ static mdt_status sample_ddim_impl(mdt_model* m, const float* tokens, const floa
     const bool per_step_ctx = m->cond == COND_TOKEN;  // sigma is a context token: the encoder cannot be hoisted
     MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));  // before anything is enqueued
     MDT_TRY(check_loaded(m));
-    MDT_TRY(mdt_reserve(m, batch));
+    const int64_t nb = gd.on ? 2 * batch : batch;  // samples through the network
+    MDT_TRY(mdt_reserve(m, nb));
+    float* const ctx_user = ctx_out;
+    if (gd.on) {
+        MDT_TRY(guide_stage(m, tokens, tokens2, goal, batch, s));
+        ctx_out = nullptr;  // the encoder's second copy would hold 2B samples: the conditional half is copied at the end
+    }
     // per-step scalars, fp32 like the reference's 0-dim tensor math (gc_sampling.py:946-950):
     // t = -ln(sigma); ratio = exp(-t_next)/exp(-t); coef = -expm1(-(t_next - t)) -- by ONE routine (on the device)
     // whether the schedule arrives in host memory (the reference's CPU default) or on the device (mdtv_agent.py:660-667: no
@@ -1179,26 +1237,27 @@ static mdt_status sample_ddim_impl(mdt_model* m, const float* tokens, const floa
     const View V = decoder_view(m, 0);
     LAUNCH(mdt_launch_sample_prep(sigmas_dev, sigmas_dev ? nullptr : sigmas, n_steps, m->steps, m->freqs,
                                   m->cond == COND_TOKEN ? nullptr : m->sig_e, m->D, x_T, m->cfg.sigma_data, m->Wa, m->ba,
-                                  V.y, (int)(batch * m->Ta), m->A, s));
+                                  V.y, (int)(nb * m->Ta), m->A, s, (int)(batch * m->Ta)));
     mdt_status ms = run_modulation(m, m->steps + 3, 4, n_steps, s, true, !per_step_ctx);  // one row of conditioning vectors per step
-    if (ms == MDT_OK && !per_step_ctx) ms = run_encode(m, tokens, tokens2, goal, modality, honour, batch, nullptr, 0, ctx_out, s);
+    if (ms == MDT_OK && !per_step_ctx) ms = run_encode(m, tokens, tokens2, goal, modality, honour, nb, nullptr, 0, ctx_out, s);
     if (ms != MDT_OK) { mdt_gemm_side_drop(); return ms; }
     LAUNCH(mdt_gemm_side_flush(s));
     for (int i = 0; i < n_steps; ++i) {
         const bool last = i == n_steps - 1;
         if (per_step_ctx)  // the reference leaves the LAST step's context in latent_encoder_emb
-            MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, honour, batch, m->steps + 4 * i + 3, 0,
+            MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, honour, nb, m->steps + 4 * i + 3, 0,
                                last ? ctx_out : nullptr, s));
         Stream fin;
         const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
-        MDT_TRY(run_decoder_blocks(m, V, batch, cond_row(m, i), 0, s, head_sums ? &fin : nullptr));
+        MDT_TRY(run_decoder_blocks(m, V, nb, cond_row(m, i), 0, s, head_sums ? &fin : nullptr));
         mdt_head_args h = head_args(m, V.y, batch, i == 0 ? x_T : m->xbuf, m->steps + 4 * i + 3, 0, last ? out : m->xbuf,
                                     MDT_HEAD_DDIM);
         if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
         h.step = m->steps + 4 * i;
         if (!last) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
-        MDT_TRY(run_head(m, h, V.hid, m->steps + 4 * (i + 1) + 3, s));
+        MDT_TRY(run_head(m, h, V.hid, m->steps + 4 * (i + 1) + 3, s, gd));
     }
+    if (gd.on) MDT_TRY(guide_ctx_out(m, ctx_user, batch, s));
     return MDT_OK;
 }
 
@@ -1216,27 +1275,52 @@ extern "C" mdt_status mdt_sample_ddim_dev(mdt_model* m, const float* tokens, con
     return sample_ddim_impl(m, tokens, tokens2, goal, modality, x_T, nullptr, sigmas_dev, n_steps, batch, out, ctx_out, stream);
 }
 
+extern "C" mdt_status mdt_sample_ddim_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                             int32_t modality, const float* x_T, const float* sigmas, int32_t n_steps,
+                                             int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
+    Guide gd;
+    MDT_TRY(guide_of(m, cond_lambda, "mdt_sample_ddim_guided", &gd));
+    if (!sigmas) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_ddim_guided: null sigmas");
+    return sample_ddim_impl(m, tokens, tokens2, goal, modality, x_T, sigmas, nullptr, n_steps, batch, out, ctx_out, stream, gd);
+}
+
+extern "C" mdt_status mdt_sample_ddim_dev_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                                 int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
+                                                 int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
+    Guide gd;
+    MDT_TRY(guide_of(m, cond_lambda, "mdt_sample_ddim_dev_guided", &gd));
+    if (!sigmas_dev) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_ddim_dev_guided: null sigmas");
+    return sample_ddim_impl(m, tokens, tokens2, goal, modality, x_T, nullptr, sigmas_dev, n_steps, batch, out, ctx_out, stream, gd);
+}
+
 // run_head with a sampler plan's update (MDT_HEAD_PLAN).  The MLP head embeds the next input Y' (pl.y_out) in a launch of
 // its own, as run_head embeds the DDIM state.
 static mdt_status run_head_plan(mdt_model* m, mdt_head_args h, const mdt_head_plan& pl, float* scratch, const float* sigma_next,
-                                hipStream_t s) {
+                                hipStream_t s, Guide gd = Guide()) {
     if (m->HP == 0) {
-        LAUNCH(mdt_launch_head_plan(h, pl, s));
+        if (gd.on) LAUNCH(mdt_launch_head_guided(h, &pl, gd.lam, s));
+        else LAUNCH(mdt_launch_head_plan(h, pl, s));
         return MDT_OK;
     }
     const int D = m->D, HP = m->HP;
+    const int rows = gd.on ? 2 * h.M : h.M;  // decoder rows (run_head)
     float* ln = scratch;
-    float* hh = scratch + (int64_t)h.M * D;
-    LAUNCH(mdt_launch_layernorm(h.y, m->dec_ln_w, m->dec_ln_b, ln, h.M, D, s));
-    mdt_gemm_args g = gemm_args(ln, D, m->head0, hh, HP, h.M);
+    float* hh = scratch + (int64_t)rows * D;
+    LAUNCH(mdt_launch_layernorm(h.y, m->dec_ln_w, m->dec_ln_b, ln, rows, D, s));
+    mdt_gemm_args g = gemm_args(ln, D, m->head0, hh, HP, rows);
     g.act = MDT_ACT_GELU;
     LAUNCH(mdt_launch_gemm(g, s));
     float* y_next = h.y_next;
     h.y = hh; h.D = HP; h.no_ln = 1; h.y_next = nullptr;
-    LAUNCH(mdt_launch_head_plan(h, pl, s));
-    if (y_next)
+    if (gd.on) LAUNCH(mdt_launch_head_guided(h, &pl, gd.lam, s));
+    else LAUNCH(mdt_launch_head_plan(h, pl, s));
+    if (y_next) {
         LAUNCH(mdt_launch_action_embed(pl.y_out, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next, h.M, m->A, D,
                                        m->Ta, s));
+        if (gd.on)
+            LAUNCH(mdt_launch_action_embed(pl.y_out, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next + (int64_t)h.M * D,
+                                           h.M, m->A, D, m->Ta, s));
+    }
     return MDT_OK;
 }
 
@@ -1268,15 +1352,17 @@ extern "C" mdt_status mdt_sampler_plan(int32_t kind, const mdt_sampler_params* p
 
 // evaluation e of the plan in m->plan: (per evaluation for COND_TOKEN: the encoder with its sigma -> ctx_out), one decoder pass,
 // the plan head reading the state xs, writing X' to out and Y' to y_out; the next input is embedded unless `last`
+// gd.on: tokens / tokens2 / goal are the staged 2B-sample inputs and ctx_out is null (the caller copies the conditional half)
 static mdt_status run_plan_eval(mdt_model* m, const View& V, const float* tokens, const float* tokens2, const float* goal,
                                 int32_t modality, int64_t batch, int e, bool last, const float* xs, float* out, float* y_out,
-                                const float* noise, int32_t n_noise, float* ctx_out, hipStream_t s) {
+                                const float* noise, int32_t n_noise, float* ctx_out, hipStream_t s, Guide gd = Guide()) {
     mdt_sampler_eval* ev = m->plan->e;
+    const int64_t nb = gd.on ? 2 * batch : batch;
     if (m->cond == COND_TOKEN)
-        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, batch, &ev[e].sigma, 0, ctx_out, s));
+        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, nb, &ev[e].sigma, 0, ctx_out, s));
     Stream fin;
     const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
-    MDT_TRY(run_decoder_blocks(m, V, batch, cond_row(m, e), 0, s, head_sums ? &fin : nullptr));
+    MDT_TRY(run_decoder_blocks(m, V, nb, cond_row(m, e), 0, s, head_sums ? &fin : nullptr));
     mdt_head_args h = head_args(m, V.y, batch, m->ybuf, &ev[e].sigma, 0, out, MDT_HEAD_PLAN);
     if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
     if (!last) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
@@ -1288,7 +1374,7 @@ static mdt_status run_plan_eval(mdt_model* m, const View& V, const float* tokens
     pl.y_out = y_out;
     pl.nel = (int64_t)batch * m->Ta * m->A;
     pl.n_noise = noise ? n_noise : 0;
-    return run_head_plan(m, h, pl, V.hid, last ? nullptr : &ev[e].sigma_next, s);
+    return run_head_plan(m, h, pl, V.hid, last ? nullptr : &ev[e].sigma_next, s, gd);
 }
 
 // sigmas_host or sigmas_dev (exactly one non-null): the n_steps + 1 noise levels.  The structure of sample_ddim_impl: the plan
@@ -1297,7 +1383,7 @@ static mdt_status run_plan_eval(mdt_model* m, const View& V, const float* tokens
 static mdt_status sample_plan_impl(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
                                    const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas,
                                    const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch,
-                                   float* out, float* ctx_out, void* stream) {
+                                   float* out, float* ctx_out, void* stream, Guide gd = Guide()) {
     if (!m || !x_T || (!sigmas && !sigmas_dev) || !out || batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_sample: bad argument");
     const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
     int E = 0, rows = 0;
@@ -1320,24 +1406,31 @@ static mdt_status sample_plan_impl(mdt_model* m, const float* tokens, const floa
     const bool per_step_ctx = m->cond == COND_TOKEN;  // sigma is a context token: the encoder runs per evaluation
     MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));  // before anything is enqueued
     MDT_TRY(check_loaded(m));
-    MDT_TRY(mdt_reserve(m, batch));
+    const int64_t nb = gd.on ? 2 * batch : batch;  // samples through the network
+    MDT_TRY(mdt_reserve(m, nb));
+    float* const ctx_user = ctx_out;
+    if (gd.on) {
+        MDT_TRY(guide_stage(m, tokens, tokens2, goal, batch, s));
+        ctx_out = nullptr;
+    }
     const View V = decoder_view(m, 0);
     const int M = (int)(batch * m->Ta);
     mdt_sampler_eval* ev = m->plan->e;
     LAUNCH(mdt_launch_sampler_prep(sigmas_dev, sigmas_dev ? nullptr : sigmas, n_steps, kind, p, m->plan, m->freqs,
                                    per_step_ctx ? nullptr : m->sig_e, m->D, x_T, noise, noise ? n_noise : 0, m->ybuf, m->hist,
                                    m->cfg.sigma_data,
-                                   m->Wa, m->ba, V.y, M, m->A, s));
+                                   m->Wa, m->ba, V.y, (int)(nb * m->Ta), m->A, s, M));
     const int stride = (int)(sizeof(mdt_sampler_eval) / sizeof(float));
     mdt_status ms = run_modulation(m, &ev[0].sigma, stride, E, s, true, !per_step_ctx);  // one conditioning row per evaluation
-    if (ms == MDT_OK && !per_step_ctx) ms = run_encode(m, tokens, tokens2, goal, modality, honour, batch, nullptr, 0, ctx_out, s);
+    if (ms == MDT_OK && !per_step_ctx) ms = run_encode(m, tokens, tokens2, goal, modality, honour, nb, nullptr, 0, ctx_out, s);
     if (ms != MDT_OK) { mdt_gemm_side_drop(); return ms; }
     LAUNCH(mdt_gemm_side_flush(s));
     for (int e = 0; e < E; ++e) {
         const bool last = e == E - 1;
         MDT_TRY(run_plan_eval(m, V, tokens, tokens2, goal, modality, batch, e, last, e == 0 ? x_T : m->xbuf, last ? out : m->xbuf,
-                              last ? nullptr : m->ybuf, noise, n_noise, last ? ctx_out : nullptr, s));
+                              last ? nullptr : m->ybuf, noise, n_noise, last ? ctx_out : nullptr, s, gd));
     }
+    if (gd.on) MDT_TRY(guide_ctx_out(m, ctx_user, batch, s));
     return MDT_OK;
 }
 
@@ -1357,6 +1450,28 @@ extern "C" mdt_status mdt_sample_dev(mdt_model* m, const float* tokens, const fl
     if (!sigmas_dev) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dev: null sigmas");
     return sample_plan_impl(m, tokens, tokens2, goal, modality, x_T, kind, params, nullptr, sigmas_dev, n_steps, noise, n_noise,
                             batch, out, ctx_out, stream);
+}
+
+extern "C" mdt_status mdt_sample_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                        int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
+                                        const float* sigmas_host, int32_t n_steps, const float* noise, int32_t n_noise,
+                                        int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
+    Guide gd;
+    MDT_TRY(guide_of(m, cond_lambda, "mdt_sample_guided", &gd));
+    if (!sigmas_host) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_guided: null sigmas");
+    return sample_plan_impl(m, tokens, tokens2, goal, modality, x_T, kind, params, sigmas_host, nullptr, n_steps, noise, n_noise,
+                            batch, out, ctx_out, stream, gd);
+}
+
+extern "C" mdt_status mdt_sample_dev_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                            int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
+                                            const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
+                                            int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
+    Guide gd;
+    MDT_TRY(guide_of(m, cond_lambda, "mdt_sample_dev_guided", &gd));
+    if (!sigmas_dev) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dev_guided: null sigmas");
+    return sample_plan_impl(m, tokens, tokens2, goal, modality, x_T, kind, params, nullptr, sigmas_dev, n_steps, noise, n_noise,
+                            batch, out, ctx_out, stream, gd);
 }
 
 extern "C" mdt_status mdt_dpm_control_init(mdt_dpm_control* c, double h, double pcoeff, double icoeff, double dcoeff,
@@ -1388,10 +1503,10 @@ struct DpmHost {
 // input (X at sigma(s)), the conditioning rows of its evaluations, one decoder pass + plan head per evaluation (the last writes
 // high -> hi and low -> lo), the error partials, one read-back and the controller.  Accepting swaps pointers: X <- high,
 // prev <- low.  Every scalar is the loop's: s and t in fp32, t = min / max(t_end, fp32(s + fp32(h))), the 1e-5 end test.
-extern "C" mdt_status mdt_sample_dpm_adaptive(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
-                                              int32_t modality, const float* x_T, float sigma_min, float sigma_max,
-                                              const mdt_dpm_adaptive_params* params, int64_t batch, float* out, float* ctx_out,
-                                              mdt_dpm_adaptive_info* info, void* stream) {
+static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                           int32_t modality, const float* x_T, float sigma_min, float sigma_max,
+                                           const mdt_dpm_adaptive_params* params, int64_t batch, float* out, float* ctx_out,
+                                           mdt_dpm_adaptive_info* info, void* stream, Guide gd) {
     if (!m || !x_T || !out || batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: bad argument");
     mdt_dpm_adaptive_params p = {3, 0.05, 0.0078, 0.05, 0.0, 1.0, 0.0, 0.81};
     if (params) p = *params;
@@ -1407,7 +1522,8 @@ extern "C" mdt_status mdt_sample_dpm_adaptive(mdt_model* m, const float* tokens,
         return fail(MDT_ERR_STATE, "mdt_sample_dpm_adaptive: the call synchronises every step and cannot be captured");
     MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));
     MDT_TRY(check_loaded(m));
-    MDT_TRY(mdt_reserve(m, batch));
+    const int64_t nb = gd.on ? 2 * batch : batch;  // samples through the network
+    MDT_TRY(mdt_reserve(m, nb));
     const int M = (int)(batch * m->Ta);
     const int64_t nel = (int64_t)M * m->A, nel4 = (nel + 3) & ~(int64_t)3;
     MDT_TRY(mdt_grow_carve(m->ad_ws, m->ad_cap, nel4, [&](Bump& b, int64_t cap) { (void)b.take(4 * cap + MDT_DPM_PARTS); }));
@@ -1419,8 +1535,13 @@ extern "C" mdt_status mdt_sample_dpm_adaptive(mdt_model* m, const float* tokens,
     const bool per_step_ctx = m->cond == COND_TOKEN;
     HIP_TRY(hipMemcpyAsync(X, x_T, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemcpyAsync(prev, x_T, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    float* const ctx_user = ctx_out;
+    if (gd.on) {
+        MDT_TRY(guide_stage(m, tokens, tokens2, goal, batch, s));
+        ctx_out = nullptr;
+    }
     if (!per_step_ctx)
-        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, batch, nullptr, 0, ctx_out, s));
+        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, nb, nullptr, 0, ctx_out, s));
     const float t_start = mdt_plan_detail::dpm_t(sigma_max), t_end = mdt_plan_detail::dpm_t(sigma_min);
     const bool forward = t_end > t_start;
     mdt_dpm_control ctl;
@@ -1441,13 +1562,13 @@ extern "C" mdt_status mdt_sample_dpm_adaptive(mdt_model* m, const float* tokens,
         const int E = hb->plan.n_evals;
         const size_t bytes = sizeof(mdt_sampler_plan_t) - (size_t)(MDT_SAMPLER_MAX_EVALS - E) * sizeof(mdt_sampler_eval);
         HIP_TRY(hipMemcpyAsync(m->plan, &hb->plan, bytes, hipMemcpyHostToDevice, s));
-        LAUNCH(mdt_launch_sampler_first(m->plan, X, nullptr, 0, m->ybuf, m->hist, m->cfg.sigma_data, m->Wa, m->ba, V.y, M, m->A,
-                                        m->D, s));
+        LAUNCH(mdt_launch_sampler_first(m->plan, X, nullptr, 0, m->ybuf, m->hist, m->cfg.sigma_data, m->Wa, m->ba, V.y, (int)(nb * m->Ta),
+                                        m->A, m->D, s, M));
         MDT_TRY(run_modulation(m, &m->plan->e[0].sigma, stride, E, s));
         for (int e = 0; e < E; ++e) {
             const bool last = e == E - 1;
             MDT_TRY(run_plan_eval(m, V, tokens, tokens2, goal, modality, batch, e, last, e == 0 ? X : m->xbuf,
-                                  last ? hi : m->xbuf, last ? lo : m->ybuf, nullptr, 0, ctx_out, s));
+                                  last ? hi : m->xbuf, last ? lo : m->ybuf, nullptr, 0, ctx_out, s, gd));
         }
         LAUNCH(mdt_launch_dpm_error(lo, hi, prev, nel, (float)p.rtol, (float)p.atol, part, s));
         HIP_TRY(hipMemcpyAsync(hb->part, part, parts * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -1472,8 +1593,27 @@ extern "C" mdt_status mdt_sample_dpm_adaptive(mdt_model* m, const float* tokens,
         }
     }
     HIP_TRY(hipMemcpyAsync(out, X, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (gd.on) MDT_TRY(guide_ctx_out(m, ctx_user, batch, s));
     if (info) *info = inf;
     return MDT_OK;
+}
+
+extern "C" mdt_status mdt_sample_dpm_adaptive(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                              int32_t modality, const float* x_T, float sigma_min, float sigma_max,
+                                              const mdt_dpm_adaptive_params* params, int64_t batch, float* out, float* ctx_out,
+                                              mdt_dpm_adaptive_info* info, void* stream) {
+    return sample_dpm_adaptive_impl(m, tokens, tokens2, goal, modality, x_T, sigma_min, sigma_max, params, batch, out, ctx_out, info,
+                                    stream, Guide());
+}
+
+extern "C" mdt_status mdt_sample_dpm_adaptive_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                                     int32_t modality, const float* x_T, float sigma_min, float sigma_max,
+                                                     const mdt_dpm_adaptive_params* params, int64_t batch, float* out,
+                                                     float* ctx_out, float cond_lambda, mdt_dpm_adaptive_info* info, void* stream) {
+    Guide gd;
+    MDT_TRY(guide_of(m, cond_lambda, "mdt_sample_dpm_adaptive_guided", &gd));
+    return sample_dpm_adaptive_impl(m, tokens, tokens2, goal, modality, x_T, sigma_min, sigma_max, params, batch, out, ctx_out, info,
+                                    stream, gd);
 }
 
 extern "C" mdt_status mdt_loss_fwd(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,

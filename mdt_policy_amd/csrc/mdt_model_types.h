@@ -102,5 +102,8 @@ struct mdt_model {
     // collapsed cross-attention (k_xattn_fold / k_xattn_apply): folded projections per sample and decoder block
     bool xfold = false;
     float *xU = nullptr, *xW = nullptr, *xc = nullptr;  // [Ld][cap][4 H * D] weight images (fragment order), same, [Ld][cap][4 H]
+    // guided samplers (classifier-free guidance): the encoder inputs of the doubled batch -- tokens / tokens2 of every sample twice,
+    // the goal rows followed by as many zero rows (k_guide_stage); cap samples each
+    float *g_tok = nullptr, *g_tok2 = nullptr, *g_goal = nullptr;
 };
 

@@ -1405,9 +1405,14 @@ __device__ __forceinline__ float edm_c_in(float sigma, float sd) { return 1.0f /
 // PLAN: the MDT_HEAD_PLAN epilogue -- the per-element update of a sampler plan (mdt_sampler_plan.h) on the registers X, Y, D,
 // d = (Y - D) / sigma, H0..H3, N0, N1; writes X' to a.out, Y' to pl->y_out, shifts the history and embeds Y' (not X') as the next
 // input.  The instantiations without it are the DDIM / denoiser heads as they were.
-template <int AMAX, bool COH, int XP = 1, int RW = 2, bool PLAN = false>
+// GUIDE (classifier-free guidance, RW = 2): a.M counts the rows of STATE; the wave reads the conditional row base of a.y and the
+// unconditional row base + a.M, combines their action_pred outputs F = F_u + lam (F_g - F_u) per element (fp32, before the EDM
+// output scaling), runs the epilogue on state row base and writes the next input's embedding to y_next rows base and base + a.M.
+template <int AMAX, bool COH, int XP = 1, int RW = 2, bool PLAN = false, bool GUIDE = false>
 __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int lane, const float* __restrict__ zeros,
-                                          const mdt_head_plan* pl = nullptr) {
+                                          const mdt_head_plan* pl = nullptr, float lam = 1.f) {
+    static_assert(!GUIDE || RW == 2, "the guided head reads one conditional and one unconditional row per wave");
+    constexpr int RS = GUIDE ? 1 : RW;  // rows of state the wave updates
     const int n4 = a.D >> 2;
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     const ActLd<COH> LY(a.y), LX(a.x);
@@ -1418,9 +1423,12 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
         cv[p] = lane + 64 * p < n4;
         cc[p] = 4 * min(lane + 64 * p, n4 - 1);
     }
-    int64_t row[RW];
+    int64_t row[RW], yrow[RW];  // state rows (x, out, sigma, plan operands); rows of a.y / a.y_next
 #pragma unroll
-    for (int r = 0; r < RW; ++r) row[r] = min(base + r, a.M - 1);
+    for (int r = 0; r < RW; ++r) {
+        row[r] = GUIDE ? (int64_t)base : (int64_t)min(base + r, a.M - 1);
+        yrow[r] = GUIDE ? (int64_t)base + (int64_t)r * a.M : row[r];
+    }
     // ---- every global operand is requested up front (clamped addresses, no load behind a branch) ----
     f32x4 v[RW][2], w[2], bb[2], wp[AMAX][2];
     float xin[RW][AMAX], bpv[AMAX], sigma[RW];
@@ -1428,7 +1436,7 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
 #pragma unroll
-        for (int r = 0; r < RW; ++r) v[r][p] = LY.ld4(row[r] * a.D + cc[p]);
+        for (int r = 0; r < RW; ++r) v[r][p] = LY.ld4(yrow[r] * a.D + cc[p]);
         w[p] = ldg4(a.ln_w + cc[p]);
         bb[p] = ldg4(lnb + cc[p]);
     }
@@ -1439,7 +1447,7 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
 #pragma unroll
             for (int p = 0; p < 2; ++p)
 #pragma unroll
-                for (int r = 0; r < RW; ++r) vx[x - 1][r][p] = LY.ld4((int64_t)x * a.y_part_stride + row[r] * a.D + cc[p]);
+                for (int r = 0; r < RW; ++r) vx[x - 1][r][p] = LY.ld4((int64_t)x * a.y_part_stride + yrow[r] * a.D + cc[p]);
     }
 #pragma unroll
     for (int c = 0; c < AMAX; ++c) {
@@ -1447,11 +1455,11 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
 #pragma unroll
         for (int p = 0; p < 2; ++p) wp[c][p] = ldg4(a.Wp + (int64_t)ce * a.D + cc[p]);
 #pragma unroll
-        for (int r = 0; r < RW; ++r) xin[r][c] = LX.ld1(row[r] * a.A + ce);
+        for (int r = 0; r < RS; ++r) xin[r][c] = LX.ld1(row[r] * a.A + ce);
         bpv[c] = a.bp[ce];
     }
 #pragma unroll
-    for (int r = 0; r < RW; ++r) sigma[r] = a.sigma[(row[r] / a.rows_per_sample) * a.sigma_stride];
+    for (int r = 0; r < RS; ++r) sigma[r] = a.sigma[(row[r] / a.rows_per_sample) * a.sigma_stride];
     // operands of the fused next-step embedding travel in the same latency window (Wa is the (A, D) image)
     const float* Wa = a.y_next != nullptr ? a.Wa : a.Wp;
     const float* bap = a.y_next != nullptr ? a.ba : zeros;
@@ -1516,14 +1524,21 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
     wave_sum_n<RW * AMAX>(res);
     const float sd = a.sigma_data;
     const float cin_next = edm_c_in(sig_next, sd);
+    if constexpr (GUIDE) {
 #pragma unroll
-    for (int r = 0; r < RW; ++r) {
+        for (int c = 0; c < AMAX; ++c) {
+            const float fg = res[c] + bpv[c], fu = res[AMAX + c] + bpv[c];
+            res[c] = fu + lam * (fg - fu);  // the network output of the guided denoiser, bias included
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RS; ++r) {
         const float den2 = sigma[r] * sigma[r] + sd * sd;
         const float c_skip = sd * sd / den2;
         const float c_out = sigma[r] * sd / sqrtf(den2);
 #pragma unroll
         for (int c = 0; c < AMAX; ++c) {
-            const float F = res[r * AMAX + c] + bpv[c];
+            const float F = GUIDE ? res[r * AMAX + c] : res[r * AMAX + c] + bpv[c];
             float o = F;
             if (a.mode != MDT_HEAD_RAW) {
                 const float den = F * c_out + xin[r][c] * c_skip;
@@ -1532,7 +1547,7 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
             res[r * AMAX + c] = o;
         }
     }
-    float resy[PLAN ? RW * AMAX : 1];
+    float resy[PLAN ? RS * AMAX : 1];
     if constexpr (PLAN) {
         // sampler plan update: X' = sum cx R, Y' = cy[NREG] X' + sum cy R; lane c stores column c
         const mdt_sampler_eval& e = *pl->e;
@@ -1546,7 +1561,7 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
         const float* n0 = (e.noise[0] >= 0 && e.noise[0] < nn) ? pl->noise + e.noise[0] * nel : nullptr;
         const float* n1 = (e.noise[1] >= 0 && e.noise[1] < nn) ? pl->noise + e.noise[1] * nel : nullptr;
 #pragma unroll
-        for (int r = 0; r < RW; ++r)
+        for (int r = 0; r < RS; ++r)
 #pragma unroll
             for (int c = 0; c < AMAX; ++c) {
                 const int64_t k = row[r] * a.A + min(c, a.A - 1);
@@ -1580,20 +1595,20 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
     }
     // all lanes hold all results (xor-butterfly sums); lanes 0..A-1 store one each
 #pragma unroll
-    for (int r = 0; r < RW; ++r)
+    for (int r = 0; r < RS; ++r)
 #pragma unroll
         for (int c = 0; c < AMAX; ++c)
             if (c < a.A && lane == c && base + r < a.M) a.out[row[r] * a.A + c] = res[r * AMAX + c];
     if (a.y_next != nullptr) {
-        f32x4 acc[RW][2];
+        f32x4 acc[RS][2];
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
-            for (int r = 0; r < RW; ++r) acc[r][p] = ba4[p];
+            for (int r = 0; r < RS; ++r) acc[r][p] = ba4[p];
 #pragma unroll
         for (int c = 0; c < AMAX; ++c)
 #pragma unroll
-            for (int r = 0; r < RW; ++r) {
+            for (int r = 0; r < RS; ++r) {
                 float xv;
                 if constexpr (PLAN) xv = c < a.A ? resy[r * AMAX + c] * cin_next : 0.f;
                 else xv = c < a.A ? res[r * AMAX + c] * cin_next : 0.f;
@@ -1601,10 +1616,10 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
                 for (int p = 0; p < 2; ++p) acc[r][p] += xv * wa[c][p];
             }
 #pragma unroll
-        for (int r = 0; r < RW; ++r)
+        for (int r = 0; r < RW; ++r)  // GUIDE: the one embedding goes to both halves
 #pragma unroll
             for (int p = 0; p < 2; ++p)
-                if (cv[p] && base + r < a.M) *(f32x4*)(a.y_next + row[r] * a.D + cc[p]) = acc[r][p];
+                if (cv[p] && (GUIDE || base + r < a.M)) *(f32x4*)(a.y_next + yrow[r] * a.D + cc[p]) = acc[GUIDE ? 0 : r][p];
     }
 }
 

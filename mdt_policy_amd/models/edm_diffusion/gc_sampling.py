@@ -178,14 +178,15 @@ def _graph_wanted(model, state, action, goal, sigmas, tag=None) -> bool:
     return seen.get(key, 0) > _GRAPH_AUTO_AFTER
 
 
-def _graphed(model, state, action, goal, sigmas):
-    """One GraphedDDIM per (shapes, modality, state keys) of a model, kept on the model (at most four)."""
+def _graphed(model, state, action, goal, sigmas, cond_lambda=None):
+    """One GraphedDDIM per (shapes, modality, state keys, guidance weight) of a model, kept on the model (at most four)."""
     from .graphed import GraphedDDIM
     cache = model.__dict__.setdefault("_graphed_samplers", [])
     for gsamp in cache:
-        if gsamp.matches(state, action, goal, sigmas):
+        if gsamp.cond_lambda == cond_lambda and gsamp.matches(state, action, goal, sigmas):
             return gsamp(state, action, goal, sigmas)
-    gsamp = GraphedDDIM(model, state, action, goal, sigmas if torch.is_tensor(sigmas) else torch.as_tensor(sigmas))
+    gsamp = GraphedDDIM(model, state, action, goal, sigmas if torch.is_tensor(sigmas) else torch.as_tensor(sigmas),
+                        cond_lambda=cond_lambda)
     cache.append(gsamp)
     del cache[:-4]
     return gsamp(state, action, goal, sigmas)
@@ -198,8 +199,20 @@ def _graphed(model, state, action, goal, sigmas):
 # plan the call builds assumes what every get_sigmas_* guarantees -- all levels > 0 but a final 0 -- which a host schedule is
 # checked for (else: the host loop); a device schedule is read in place, unchecked.
 # ------------------------------------------------------------------------------------------------
+def _native_guidance(extra_args):
+    """(native, cond_lambda) for a sampler's ``extra_args``: no extra arguments -> (True, None); ``{"cond_lambda": lam}`` alone ->
+    (True, lam), or (True, None) when lam == 1 (the conditional model: today's unguided call); anything else -> (False, None),
+    the host loop, which hands extra_args to GCDenoiser.forward."""
+    if not extra_args:
+        return True, None
+    if set(extra_args) != {"cond_lambda"}:
+        return False, None
+    lam = float(extra_args["cond_lambda"])
+    return True, (None if lam == 1.0 else lam)
+
+
 def _native_ok(model, sigmas, scaler, callback, extra_args) -> bool:
-    if not isinstance(model, GCDenoiser) or callback is not None or extra_args or scaler is not None:
+    if not isinstance(model, GCDenoiser) or callback is not None or not _native_guidance(extra_args)[0] or scaler is not None:
         return False
     n = len(sigmas) - 1
     if n < 1 or n > _lib.SAMPLER_MAX_STEPS:
@@ -246,9 +259,13 @@ def _graphed_native(model, kind, params, state, action, goal, sigmas, noise, n_s
     return gsamp(state, action, goal, sigmas, noise=noise)
 
 
-def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, **params):
+def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, extra_args=None, **params):
     """The native call, replayed as a HIP graph by sample_ddim's rule (rollout-sized batches from the third identical call).
-    ``n_steps``: dpm_fast's evaluation count (its schedule is the two levels, which join the graph key with it)."""
+    ``n_steps``: dpm_fast's evaluation count (its schedule is the two levels, which join the graph key with it).  ``extra_args``:
+    the sampler's, which _native_ok admitted -- a guidance weight joins the parameters (and with them the graph key)."""
+    lam = _native_guidance(extra_args)[1]
+    if lam is not None:
+        params = dict(params, cond_lambda=lam)
     tag = (kind, tuple(sorted(params.items())))
     if n_steps is not None:
         tag += (n_steps, tuple(float(v) for v in sigmas))
@@ -275,7 +292,24 @@ def sample_ddim(model, state, action, goal, sigmas, scaler=None, extra_args=None
     `scaler` is accepted and never read, exactly as in the reference (its DDIM has no `clip_output` call), so a harness run
     with `use_scaler` (mdtv_agent.py:606-614) keeps the fused native loop; only `callback` / `extra_args` need the step loop."""
     extra_args = {} if extra_args is None else extra_args
-    if isinstance(model, GCDenoiser) and callback is None and not extra_args:
+    native, lam = _native_guidance(extra_args)
+    if isinstance(model, GCDenoiser) and callback is None and native:
+        if lam is not None:  # classifier-free guidance: the guided native call, its graphs keyed by the weight too
+            if not math.isfinite(lam):
+                raise ValueError(f"cond_lambda must be finite, got {lam}")
+            tag = ("ddim_guided", lam)
+            if _graph_wanted(model, state, action, goal, sigmas, tag=tag):
+                try:
+                    return _graphed(model, state, action, goal, sigmas, cond_lambda=lam)
+                except Exception as exc:  # noqa: BLE001 -- as below
+                    if _GRAPH_SAMPLER:
+                        raise
+                    model.__dict__.setdefault("_graph_failed", set()).add((tag,) + _graph_key(state, action, goal, sigmas))
+                    model.__dict__.pop("_graphed_samplers", None)
+                    import warnings
+                    warnings.warn(f"mdt_policy_amd: HIP-graph capture of guided sample_ddim failed ({exc!r}); this call shape stays eager")
+                    torch.cuda.synchronize()
+            return model.sample_ddim(state, action, goal, sigmas, cond_lambda=lam)
         if _graph_wanted(model, state, action, goal, sigmas):
             if _GRAPH_SAMPLER:
                 return _graphed(model, state, action, goal, sigmas)  # the same launches, replayed as a HIP graph
@@ -307,7 +341,7 @@ def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     """Karras Algorithm 2 without the 2nd-order correction (reference gc_sampling.py:164-209)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("euler", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
-                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise)
+                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -334,7 +368,7 @@ def sample_euler_ancestral(model, state, action, goal, sigmas, scaler=None, extr
     """Euler steps to sigma_down plus fresh noise sigma_up (reference gc_sampling.py:213-252)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         noise = _randn_rows(action, _ancestral_draws(sigmas, eta))
-        return _run_native("euler_ancestral", model, state, action, goal, sigmas, noise, eta=eta)
+        return _run_native("euler_ancestral", model, state, action, goal, sigmas, noise, eta=eta, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -359,7 +393,7 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
     (reference gc_sampling.py:256-312)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("heun", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
-                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise)
+                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -391,7 +425,7 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
 def sample_dpmpp_2m(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None):
     """DPM-Solver++(2M) multistep (reference gc_sampling.py:699-734)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
-        return _run_native("dpmpp_2m", model, state, action, goal, sigmas, None)
+        return _run_native("dpmpp_2m", model, state, action, goal, sigmas, None, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     old_denoised = None
@@ -417,7 +451,7 @@ def sample_dpmpp_2s(model, state, action, goal, sigmas, scaler=None, extra_args=
                     eta=1.):
     """DPM-Solver++(2S) single-step second order (reference gc_sampling.py:955-994)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
-        return _run_native("dpmpp_2s", model, state, action, goal, sigmas, None)
+        return _run_native("dpmpp_2s", model, state, action, goal, sigmas, None, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -446,7 +480,7 @@ def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     evaluation at the log-midpoint sigma, full step with the midpoint derivative; Euler on the last step."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("dpm_2", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
-                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise)
+                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -480,7 +514,7 @@ def sample_dpm_2_ancestral(model, state, action, goal, sigmas, scaler=None, extr
     """Ancestral sampling with DPM-Solver-2 midpoint steps (reference gc_sampling.py:374-407)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         noise = _randn_rows(action, _ancestral_draws(sigmas, eta))
-        return _run_native("dpm_2_ancestral", model, state, action, goal, sigmas, noise, eta=eta)
+        return _run_native("dpm_2_ancestral", model, state, action, goal, sigmas, noise, eta=eta, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -524,7 +558,7 @@ def linear_multistep_coeff(order, t, i, j):
 def sample_lms(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None, order=4):
     """Linear multistep (Adams-Bashforth in sigma) sampler (reference gc_sampling.py:425-460)."""
     if 1 <= order <= 4 and _native_ok(model, sigmas, scaler, callback, extra_args):
-        return _run_native("lms", model, state, action, goal, sigmas, None, order=order)
+        return _run_native("lms", model, state, action, goal, sigmas, None, order=order, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     sig_np = sig.numpy()
@@ -564,7 +598,8 @@ def sample_dpmpp_2s_ancestral(model, state, action, goal, sigmas, scaler=None, e
         else:
             sig = _host(sigmas)
             noise = _sampled_rows(action, [noise_sampler(sig[i], sig[i + 1]) for i in range(n)])
-        return _run_native("dpmpp_2s_ancestral", model, state, action, goal, sigmas, noise, eta=eta, s_noise=s_noise)
+        return _run_native("dpmpp_2s_ancestral", model, state, action, goal, sigmas, noise, eta=eta, s_noise=s_noise,
+                           extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
     sig = _host(sigmas)
@@ -722,10 +757,11 @@ def sample_dpm_fast(model, state, action, goal, sigma_min, sigma_max, n, scaler=
     if eta and not t_end > t_start:
         raise ValueError('eta must be 0 for reverse sampling')
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
-    if (isinstance(model, GCDenoiser) and callback is None and not extra_args and scaler is None
+    if (isinstance(model, GCDenoiser) and callback is None and _native_guidance(extra_args)[0] and scaler is None
             and 1 <= n <= _lib.SAMPLER_MAX_EVALS):
         return _run_native("dpm_fast", model, state, action, goal, [float(sigma_max), float(sigma_min)],
-                           _dpm_fast_noise(action, t_start, t_end, n, eta, noise_sampler), n_steps=n, eta=eta, s_noise=s_noise)
+                           _dpm_fast_noise(action, t_start, t_end, n, eta, noise_sampler), n_steps=n, eta=eta, s_noise=s_noise,
+                           extra_args=extra_args)
     with _hoist(model, state, goal):
         return _dpm_fast_run(_EpsEvaluator(model, state, goal, extra_args), action, t_start, t_end, n, eta, s_noise,
                              noise_sampler, callback)
@@ -780,11 +816,13 @@ def sample_dpm_adaptive(model, state, action, goal, sigma_min, sigma_max, extra_
     t_end = _t(torch.tensor(float(sigma_min))).to(torch.float32)
     if eta and not bool(t_end > t_start):
         raise ValueError('eta must be 0 for reverse sampling')
-    if (isinstance(model, GCDenoiser) and callback is None and not extra_args and not eta and action.device.type == "cuda"
+    native, lam = _native_guidance(extra_args)
+    if (isinstance(model, GCDenoiser) and callback is None and native and not eta and action.device.type == "cuda"
             and not torch.cuda.is_current_stream_capturing()):
+        kw = {} if lam is None else {"cond_lambda": lam}  # guidance: mdt_sample_dpm_adaptive_guided
         action, info = model.sample_dpm_adaptive_native(state, action, goal, float(sigma_min), float(sigma_max), order=order,
                                                         rtol=rtol, atol=atol, h_init=h_init, pcoeff=pcoeff, icoeff=icoeff,
-                                                        dcoeff=dcoeff, accept_safety=accept_safety)
+                                                        dcoeff=dcoeff, accept_safety=accept_safety, **kw)
         return (action, info) if return_info else action
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
     with _hoist(model, state, goal):
@@ -933,7 +971,7 @@ def sample_dpmpp_sde(model, state, action, goal, sigmas, extra_args=None, callba
             if _f(get_ancestral_step(_sigma(t), _sigma(t_next), eta)[1]) != 0:
                 values.append(noise_sampler(_sigma(t), _sigma(t_next)))
         return _run_native("dpmpp_sde", model, state, action, goal, sigmas, _sampled_rows(action, values), eta=eta,
-                           s_noise=s_noise, r=r)
+                           s_noise=s_noise, r=r, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     if noise_sampler is None:

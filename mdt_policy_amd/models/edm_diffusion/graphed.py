@@ -22,10 +22,12 @@ import torch
 
 
 class GraphedDDIM:
-    def __init__(self, model, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas: torch.Tensor):
+    def __init__(self, model, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas: torch.Tensor,
+                 cond_lambda: Optional[float] = None):
         if x_T.device.type != "cuda":
             raise RuntimeError("GraphedDDIM needs the model and its inputs on a ROCm GPU")
         self.model = model
+        self.cond_lambda = cond_lambda  # classifier-free guidance weight of the captured call (None: unguided)
         self.device = x_T.device
         self._static_state: Dict[str, object] = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in state.items()}
         self._x = x_T.detach().clone()
@@ -42,6 +44,8 @@ class GraphedDDIM:
         return self.model._engine(state=self._static_state)
 
     def _run(self):
+        if self.cond_lambda is not None:
+            return self.model.sample_ddim(self._static_state, self._x, self._goal, self._sig, cond_lambda=self.cond_lambda)
         return self.model.sample_ddim(self._static_state, self._x, self._goal, self._sig)
 
     def _extra_inputs(self, noise):

@@ -9,6 +9,7 @@ action-head kernels.
 from __future__ import annotations
 
 import importlib
+import math
 from contextlib import contextmanager
 
 import torch
@@ -30,6 +31,15 @@ def _staged_backward() -> bool:
         return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     except Exception:  # noqa: BLE001
         return False
+
+
+def _lambda(cond_lambda):
+    """A sampler's guidance weight as the engine takes it: None for the unguided call (none given, or exactly 1 -- the
+    conditional model, which then runs the unguided native call and gives its bits)."""
+    if cond_lambda is None:
+        return None
+    lam = float(cond_lambda)
+    return None if lam == 1.0 else lam
 
 
 def _instantiate(cfg):
@@ -100,8 +110,21 @@ class GCDenoiser(nn.Module):
                  if ("inner_model." + n) in eng._grad_layout and not (unused and n.startswith(unused))]
         return tok, tok2, g, B, [n for n, _ in named], [p for _, p in named]
 
-    def forward(self, state, action, goal, sigma, **kwargs):
-        """D(x; sigma) = F(x*c_in, sigma)*c_out + x*c_skip (reference score_wrappers.py:65-80)."""
+    def forward(self, state, action, goal, sigma, cond_lambda=1.0, **kwargs):
+        """D(x; sigma) = F(x*c_in, sigma)*c_out + x*c_skip (reference score_wrappers.py:65-80).
+
+        ``cond_lambda`` != 1: classifier-free guidance, D_lambda = D(x; sigma, 0) + lambda (D(x; sigma, g) - D(x; sigma, 0)) from the
+        conditional and the ``uncond`` evaluation (the latter first, so latent_encoder_emb ends as the conditional context)."""
+        lam = float(cond_lambda)
+        if lam != 1.0:
+            if not math.isfinite(lam):
+                raise ValueError(f"cond_lambda must be finite, got {lam}")
+            if kwargs.get("uncond", False):
+                raise ValueError("uncond=True and cond_lambda != 1 contradict each other")
+            kwargs = {k: v for k, v in kwargs.items() if k != "uncond"}
+            d_u = self.forward(state, action, goal, sigma, uncond=True, **kwargs)
+            d_g = self.forward(state, action, goal, sigma, **kwargs)
+            return d_u + lam * (d_g - d_u)
         im = self.inner_model
         eng = self._engine(state=state)
         goal = im._goals(goal, bool(kwargs.get("uncond", False)))
@@ -183,35 +206,41 @@ class GCDenoiser(nn.Module):
         return self._engine(state=state).denoise_vjp(state, action, im._goals(goal, False), sigma, v)
 
     @torch.no_grad()
-    def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, **params):
+    def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, cond_lambda=None, **params):
         """One of the other samplers (``kind``: 'euler', 'heun', 'dpmpp_2m', ... -- the gc_sampling function name without
         'sample_') as one enqueue on the current stream (mdt_sample).  ``noise``: None or (n_noise, B, Ta, A) in the Python loop's
         draw order -- raw randn draws (euler / heun / dpm_2 / the ancestral samplers) or the noise_sampler values (dpmpp_2s_ancestral,
         dpmpp_sde); s_noise and the step scales are applied inside.  ``params``: the sampler's keyword arguments (eta, s_churn,
         s_tmin, s_tmax, s_noise, r, order).  'dpm_fast': ``sigmas`` is [sigma_max, sigma_min] and ``n_steps`` the evaluation
-        count."""
+        count.  ``cond_lambda``: classifier-free guidance weight (None or 1: the unguided call; include/mdt_hip.h
+        mdt_sample_guided)."""
         from ... import _lib
         im = self.inner_model
         out, ctx = self._engine(state=state).sample_native(_lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action,
-                                                           im._goals(goal, False), sigmas, noise, n_steps=n_steps)
+                                                           im._goals(goal, False), sigmas, noise, n_steps=n_steps,
+                                                           cond_lambda=_lambda(cond_lambda))
         im.latent_encoder_emb = ctx
         return out
 
     @torch.no_grad()
-    def sample_dpm_adaptive_native(self, state, action, goal, sigma_min, sigma_max, **params):
+    def sample_dpm_adaptive_native(self, state, action, goal, sigma_min, sigma_max, cond_lambda=None, **params):
         """sample_dpm_adaptive with eta = 0 as one blocking call (mdt_sample_dpm_adaptive): ``params`` its keyword arguments
-        (order, rtol, atol, h_init, pcoeff, icoeff, dcoeff, accept_safety).  Returns (action, info)."""
+        (order, rtol, atol, h_init, pcoeff, icoeff, dcoeff, accept_safety).  Returns (action, info).  ``cond_lambda``:
+        classifier-free guidance weight (mdt_sample_dpm_adaptive_guided)."""
         from ... import _lib
         im = self.inner_model
         out, ctx, info = self._engine(state=state).sample_dpm_adaptive(_lib.dpm_adaptive_params(**params), state, action,
-                                                                       im._goals(goal, False), sigma_min, sigma_max)
+                                                                       im._goals(goal, False), sigma_min, sigma_max,
+                                                                       cond_lambda=_lambda(cond_lambda))
         im.latent_encoder_emb = ctx
         return out, info
 
     @torch.no_grad()
-    def sample_ddim(self, state, action, goal, sigmas):
-        """Whole DDIM loop (reference gc_sampling.py:922-951) as one enqueue on the current stream."""
+    def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None):
+        """Whole DDIM loop (reference gc_sampling.py:922-951) as one enqueue on the current stream.  ``cond_lambda``:
+        classifier-free guidance weight (None or 1: the unguided call; mdt_sample_ddim_guided)."""
         im = self.inner_model
-        out, ctx = self._engine(state=state).sample_ddim(state, action, im._goals(goal, False), sigmas)
+        out, ctx = self._engine(state=state).sample_ddim(state, action, im._goals(goal, False), sigmas,
+                                                         cond_lambda=_lambda(cond_lambda))
         im.latent_encoder_emb = ctx
         return out

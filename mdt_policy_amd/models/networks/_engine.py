@@ -14,6 +14,7 @@ configuration raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import operator
 from typing import Dict, Optional
 
@@ -27,6 +28,17 @@ from ._handle import grad_layout
 import os
 
 _RESYNC_EVERY = int(os.environ.get("MDT_HIP_PARAM_RESYNC", "0") or 0)
+
+
+def _guidance(cond_lambda) -> Optional[float]:
+    """The guidance weight of a sampler call as the C ABI takes it, or None for the unguided call (no weight given).  A weight
+    that is not a finite number raises ValueError, before anything is enqueued."""
+    if cond_lambda is None:
+        return None
+    lam = float(cond_lambda)
+    if not math.isfinite(lam):
+        raise ValueError(f"cond_lambda must be finite, got {lam}")
+    return lam
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -246,10 +258,12 @@ class HipEngine:
                                         _ptr(s), B, _ptr(out), _ptr(ctx), self._stream())
         return out, ctx
 
-    def sample_ddim(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas):
+    def sample_ddim(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, cond_lambda: Optional[float] = None):
         """Fused sampler call.  ``sigmas`` may live on the host (gc_sampling's default) or on the model's device --
         the agent builds its schedule there (mdtv_agent.py:660-667); a device schedule is consumed in place
-        (mdt_sample_ddim_dev): no copy to the host, no synchronisation."""
+        (mdt_sample_ddim_dev): no copy to the host, no synchronisation.  ``cond_lambda`` (not None): classifier-free guidance,
+        mdt_sample_ddim_guided / mdt_sample_ddim_dev_guided."""
+        lam = _guidance(cond_lambda)
         self.sync_params()
         tok, tok2, B = self._tokens(state)
         g, x_ = self._goal(goal, B), self._in(x_T, (B, self.Ta, self.A))
@@ -260,6 +274,10 @@ class HipEngine:
             n = sig.numel() - 1
             self._keep = sig  # the kernel that reads it is only enqueued: keep the (possibly converted) tensor alive
             self.ctx_generation += 1
+            if lam is not None:
+                _lib.call(self.lib.mdt_sample_ddim_dev_guided, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
+                          _ptr(x_), _ptr(sig), n, B, _ptr(out), _ptr(ctx), lam, self._stream())
+                return out, ctx
             _lib.call(self.lib.mdt_sample_ddim_dev, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
                                                     _ptr(x_), _ptr(sig), n, B, _ptr(out), _ptr(ctx), self._stream())
             return out, ctx
@@ -267,16 +285,21 @@ class HipEngine:
         n = len(sig) - 1
         arr = (C.c_float * len(sig))(*sig)
         self.ctx_generation += 1
+        if lam is not None:
+            _lib.call(self.lib.mdt_sample_ddim_guided, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
+                      _ptr(x_), arr, n, B, _ptr(out), _ptr(ctx), lam, self._stream())
+            return out, ctx
         _lib.call(self.lib.mdt_sample_ddim, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
                                             _ptr(x_), arr, n, B, _ptr(out), _ptr(ctx), self._stream())
         return out, ctx
 
     def sample_native(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
-                      noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None):
+                      noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cond_lambda: Optional[float] = None):
         """One call of another sampler (mdt_sample / mdt_sample_dev): ``kind`` an mdt_sampler_kind, ``params`` an
         _lib.SamplerParams, ``noise`` None or (n_noise, B, Ta, A) in the Python loop's draw order, ``n_steps`` None (one less
         than the levels) or dpm_fast's evaluation count.  Like sample_ddim, a device schedule is read in place (no copy, no
-        synchronisation)."""
+        synchronisation).  ``cond_lambda`` (not None): classifier-free guidance (mdt_sample_guided / mdt_sample_dev_guided)."""
+        lam = _guidance(cond_lambda)
         self.sync_params()
         tok, tok2, B = self._tokens(state)
         g, x_ = self._goal(goal, B), self._in(x_T, (B, self.Ta, self.A))
@@ -289,6 +312,11 @@ class HipEngine:
             n = sig.numel() - 1 if n_steps is None else int(n_steps)
             self._keep = (sig, nz)  # the kernels that read them are only enqueued: keep the tensors alive
             self.ctx_generation += 1
+            if lam is not None:
+                _lib.call(self.lib.mdt_sample_dev_guided, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
+                          _ptr(x_), int(kind), C.byref(params), _ptr(sig), n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), lam,
+                          self._stream())
+                return out, ctx
             _lib.call(self.lib.mdt_sample_dev, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_),
                       int(kind), C.byref(params), _ptr(sig), n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), self._stream())
             return out, ctx
@@ -297,13 +325,19 @@ class HipEngine:
         arr = (C.c_float * len(sig))(*sig)
         self._keep = nz
         self.ctx_generation += 1
+        if lam is not None:
+            _lib.call(self.lib.mdt_sample_guided, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_),
+                      int(kind), C.byref(params), arr, n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), lam, self._stream())
+            return out, ctx
         _lib.call(self.lib.mdt_sample, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_), int(kind),
                   C.byref(params), arr, n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), self._stream())
         return out, ctx
 
-    def sample_dpm_adaptive(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigma_min: float, sigma_max: float):
+    def sample_dpm_adaptive(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigma_min: float, sigma_max: float,
+                            cond_lambda: Optional[float] = None):
         """mdt_sample_dpm_adaptive (eta = 0): ``params`` an _lib.DpmAdaptiveParams.  Blocking: the call reads the step error
-        back every step.  Returns (out, ctx, info dict)."""
+        back every step.  Returns (out, ctx, info dict).  ``cond_lambda`` (not None): mdt_sample_dpm_adaptive_guided."""
+        lam = _guidance(cond_lambda)
         self.sync_params()
         tok, tok2, B = self._tokens(state)
         g, x_ = self._goal(goal, B), self._in(x_T, (B, self.Ta, self.A))
@@ -311,6 +345,11 @@ class HipEngine:
         ctx = torch.empty((B, self.Te, self.D), device=self.device, dtype=torch.float32)
         info = _lib.DpmAdaptiveInfo()
         self.ctx_generation += 1
+        if lam is not None:
+            _lib.call(self.lib.mdt_sample_dpm_adaptive_guided, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
+                      _ptr(x_), float(sigma_min), float(sigma_max), C.byref(params), B, _ptr(out), _ptr(ctx), lam, C.byref(info),
+                      self._stream())
+            return out, ctx, {k: int(getattr(info, k)) for k in ("steps", "nfe", "n_accept", "n_reject")}
         _lib.call(self.lib.mdt_sample_dpm_adaptive, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_),
                   float(sigma_min), float(sigma_max), C.byref(params), B, _ptr(out), _ptr(ctx), C.byref(info), self._stream())
         return out, ctx, {k: int(getattr(info, k)) for k in ("steps", "nfe", "n_accept", "n_reject")}
