@@ -144,16 +144,21 @@ struct mdt_head_plan {
     int32_t n_noise;            // rows of `noise`: a plan row at or beyond it reads as 0 (the device plan is never trusted
                                 // to stay inside the caller's buffer)
 };
-hipError_t mdt_launch_head_plan(const mdt_head_args& a, const mdt_head_plan& pl, hipStream_t s);
-// classifier-free guidance: the head (pl == nullptr) or the plan head on a.M state rows whose decoder rows are a.y's [0, M)
-// (conditional) and [M, 2M) (unconditional); F = F_u + lam (F_g - F_u); y_next (if any) receives 2M rows
-hipError_t mdt_launch_head_guided(const mdt_head_args& a, const mdt_head_plan* pl, float lam, hipStream_t s);
+// classifier-free guidance of a sampler call (mdt_sample_*_guided): `on` = the call runs the doubled batch, conditional samples
+// [0, B) and unconditional ones [B, 2B), and its heads combine the two halves with `lam`
+struct mdt_guide {
+    bool on = false;
+    float lam = 1.f;
+};
+// the action head on a.M rows: pl == nullptr the DDIM / denoiser head, else the plan head.  gd.on: the decoder rows of the a.M
+// state rows are a.y's [0, M) (conditional) and [M, 2M) (unconditional); F = F_u + lam (F_g - F_u); y_next (if any) receives 2M rows
+hipError_t mdt_launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, hipStream_t s);
+inline hipError_t mdt_launch_head(const mdt_head_args& a, hipStream_t s) { return mdt_launch_head(a, nullptr, mdt_guide(), s); }
 // the guided sampler's 2B encoder inputs (tokens and tokens2 twice, the goal then zeros) in one launch
 hipError_t mdt_launch_guide_stage(const float* tok, const float* tok2, const float* goal, float* tok_o, float* tok2_o, float* goal_o,
                                   int B, int w1, int w2, int G, hipStream_t s);
 hipError_t mdt_launch_action_embed(const float* x, const float* sigma, int64_t sstride, float sd, const float* Wa,
                                    const float* ba, float* y, int M, int A, int D, int rps, hipStream_t s);
-hipError_t mdt_launch_head(const mdt_head_args& a, hipStream_t s);
 hipError_t mdt_launch_noise_input(const float* act, const float* noise, const float* sigma, float* noised, int64_t n,
                                   int per_sample, hipStream_t s);
 constexpr int MDT_LOSS_PARTS = 1024;   // floats of scratch mdt_launch_loss_reduce wants (`part`)

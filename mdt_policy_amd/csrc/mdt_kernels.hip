@@ -1719,28 +1719,31 @@ __global__ __launch_bounds__(256) void k_head_plan_guided(mdt_head_args a, mdt_h
     head_rows<AMAX, false, XP, 2, true, true>(a, base, threadIdx.x & 63, zeros, &pl, lam);
 }
 
-// pl == nullptr: the DDIM / denoiser head (k_head_guided), else the plan head (k_head_plan_guided)
+// the kernel of a head launch: pl == nullptr the DDIM / denoiser head, else the plan head; gd.on the guided twin of either
 template <int AMAX, int XP>
-static void launch_head_guided(const mdt_head_args& a, const mdt_head_plan* pl, float lam, int grid, hipStream_t s) {
-    if (pl) hipLaunchKernelGGL((k_head_plan_guided<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, *pl, lam, g_zeros);
-    else hipLaunchKernelGGL((k_head_guided<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, lam, g_zeros);
+static void launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, int grid, hipStream_t s) {
+    if (gd.on && pl) hipLaunchKernelGGL((k_head_plan_guided<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, *pl, gd.lam, g_zeros);
+    else if (gd.on) hipLaunchKernelGGL((k_head_guided<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, gd.lam, g_zeros);
+    else if (pl) hipLaunchKernelGGL((k_head_plan<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, *pl, g_zeros);
+    else hipLaunchKernelGGL((k_head<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, g_zeros);
 }
 
-hipError_t mdt_launch_head_guided(const mdt_head_args& a, const mdt_head_plan* pl, float lam, hipStream_t s) {
+hipError_t mdt_launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, hipStream_t s) {
     hipError_t e = ensure_zeros();
     if (e != hipSuccess) return e;
-    const int grid = (a.M + 3) / 4;
-    if (a.y_parts > 1) {
+    const int grid = (a.M + 3) / 4;  // 4 waves x 1 row per workgroup
+    if (a.y_parts > 1) {  // rows = the sum of a fused MLP's slabs
         if (a.A > 8 || a.y_parts > 4) return hipErrorInvalidValue;
         switch (a.y_parts) {
-            case 2: launch_head_guided<8, 2>(a, pl, lam, grid, s); break;
-            case 3: launch_head_guided<8, 3>(a, pl, lam, grid, s); break;
-            default: launch_head_guided<8, 4>(a, pl, lam, grid, s); break;
+            case 2: launch_head<8, 2>(a, pl, gd, grid, s); break;
+            case 3: launch_head<8, 3>(a, pl, gd, grid, s); break;
+            default: launch_head<8, 4>(a, pl, gd, grid, s); break;
         }
-        return hipGetLastError();
+    } else if (a.A <= 8) {
+        launch_head<8, 1>(a, pl, gd, grid, s);
+    } else {
+        launch_head<16, 1>(a, pl, gd, grid, s);
     }
-    if (a.A <= 8) launch_head_guided<8, 1>(a, pl, lam, grid, s);
-    else launch_head_guided<16, 1>(a, pl, lam, grid, s);
     return hipGetLastError();
 }
 
@@ -1768,42 +1771,6 @@ hipError_t mdt_launch_guide_stage(const float* tok, const float* tok2, const flo
     if (n == 0) return hipSuccess;
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 2048);
     hipLaunchKernelGGL(k_guide_stage, dim3(grid), dim3(256), 0, s, tok, tok2, goal, tok_o, tok2_o, goal_o, B, w1, w2, G);
-    return hipGetLastError();
-}
-
-hipError_t mdt_launch_head_plan(const mdt_head_args& a, const mdt_head_plan& pl, hipStream_t s) {
-    hipError_t e = ensure_zeros();
-    if (e != hipSuccess) return e;
-    const int grid = (a.M + 3) / 4;
-    if (a.y_parts > 1) {
-        if (a.A > 8 || a.y_parts > 4) return hipErrorInvalidValue;
-        switch (a.y_parts) {
-            case 2: hipLaunchKernelGGL((k_head_plan<8, 2>), dim3(grid), dim3(256), 0, s, a, pl, g_zeros); break;
-            case 3: hipLaunchKernelGGL((k_head_plan<8, 3>), dim3(grid), dim3(256), 0, s, a, pl, g_zeros); break;
-            default: hipLaunchKernelGGL((k_head_plan<8, 4>), dim3(grid), dim3(256), 0, s, a, pl, g_zeros); break;
-        }
-        return hipGetLastError();
-    }
-    if (a.A <= 8) hipLaunchKernelGGL((k_head_plan<8, 1>), dim3(grid), dim3(256), 0, s, a, pl, g_zeros);
-    else hipLaunchKernelGGL((k_head_plan<16, 1>), dim3(grid), dim3(256), 0, s, a, pl, g_zeros);
-    return hipGetLastError();
-}
-
-hipError_t mdt_launch_head(const mdt_head_args& a, hipStream_t s) {
-    hipError_t e = ensure_zeros();
-    if (e != hipSuccess) return e;
-    const int grid = (a.M + 3) / 4;  // 4 waves x 1 row per workgroup
-    if (a.y_parts > 1) {  // rows = the sum of a fused MLP's slabs
-        if (a.A > 8 || a.y_parts > 4) return hipErrorInvalidValue;
-        switch (a.y_parts) {
-            case 2: hipLaunchKernelGGL((k_head<8, 2>), dim3(grid), dim3(256), 0, s, a, g_zeros); break;
-            case 3: hipLaunchKernelGGL((k_head<8, 3>), dim3(grid), dim3(256), 0, s, a, g_zeros); break;
-            default: hipLaunchKernelGGL((k_head<8, 4>), dim3(grid), dim3(256), 0, s, a, g_zeros); break;
-        }
-        return hipGetLastError();
-    }
-    if (a.A <= 8) hipLaunchKernelGGL((k_head<8, 1>), dim3(grid), dim3(256), 0, s, a, g_zeros);
-    else hipLaunchKernelGGL((k_head<16, 1>), dim3(grid), dim3(256), 0, s, a, g_zeros);
     return hipGetLastError();
 }
 

@@ -1095,24 +1095,16 @@ static mdt_head_args head_args(mdt_model* m, const float* y, int64_t B, const fl
     return h;
 }
 
-// The action head on the rows of `h.y`.  Linear head: ONE launch (decoder LN, action_pred, EDM combine, DDIM update,
-// next step's embedding).  MLP head (linear_output = 0): decoder LN -> action_pred.0 + GELU on the GEMM ->
-// action_pred.2 and the rest in the head kernel reading the hidden layer as it is; `scratch` holds M * (D + HP)
-// floats (the slice's MLP hidden buffer is free at this point); the next step's embedding is its own launch then.
-// Classifier-free guidance of a sampler call (mdt_sample_*_guided): `on` = the call runs the doubled batch, conditional samples
-// [0, B) and unconditional ones [B, 2B), and its heads combine the two halves with `lam`.
-struct Guide {
-    bool on = false;
-    float lam = 1.f;
-};
-
-// The guided MLP head's scratch and the unguided one's are the same buffer: 2 M (D + HP) floats of the 2B-sample slice's hidden
-// buffer (4 D floats per row, HP <= 3 D).
-static mdt_status run_head(mdt_model* m, mdt_head_args h, float* scratch, const float* sigma_next, hipStream_t s,
-                           Guide gd = Guide()) {
+// The action head on the rows of `h.y`: pl == nullptr the DDIM / denoiser head, else a sampler plan's update (MDT_HEAD_PLAN);
+// gd.on combines the conditional and the unconditional half (mdt_guide).  Linear head: ONE launch (decoder LN, action_pred, EDM
+// combine, state update, next input's embedding).  MLP head (linear_output = 0): decoder LN -> action_pred.0 + GELU on the GEMM
+// -> action_pred.2 and the rest in the head kernel reading the hidden layer as it is; `scratch` holds rows * (D + HP) floats
+// (the slice's MLP hidden buffer is free at this point: 4 D floats per decoder row, HP <= 3 D); the next input's embedding --
+// of the DDIM state h.out or of the plan's Y' (pl->y_out) -- is its own launch then.
+static mdt_status run_head(mdt_model* m, mdt_head_args h, const mdt_head_plan* pl, float* scratch, const float* sigma_next,
+                           hipStream_t s, mdt_guide gd) {
     if (m->HP == 0) {
-        if (gd.on) LAUNCH(mdt_launch_head_guided(h, nullptr, gd.lam, s));
-        else LAUNCH(mdt_launch_head(h, s));
+        LAUNCH(mdt_launch_head(h, pl, gd, s));
         return MDT_OK;
     }
     const int D = m->D, HP = m->HP;
@@ -1125,42 +1117,34 @@ static mdt_status run_head(mdt_model* m, mdt_head_args h, float* scratch, const 
     LAUNCH(mdt_launch_gemm(g, s));
     float* y_next = h.y_next;
     h.y = hh; h.D = HP; h.no_ln = 1; h.y_next = nullptr;
-    if (gd.on) LAUNCH(mdt_launch_head_guided(h, nullptr, gd.lam, s));
-    else LAUNCH(mdt_launch_head(h, s));
-    if (y_next) {
-        LAUNCH(mdt_launch_action_embed(h.out, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next, h.M, m->A, D,
-                                       m->Ta, s));
-        if (gd.on)  // the unconditional half embeds the same state
-            LAUNCH(mdt_launch_action_embed(h.out, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next + (int64_t)h.M * D, h.M,
-                                           m->A, D, m->Ta, s));
-    }
+    LAUNCH(mdt_launch_head(h, pl, gd, s));
+    const float* state = pl ? pl->y_out : h.out;
+    for (int half = 0; y_next && half < (gd.on ? 2 : 1); ++half)  // the unconditional half embeds the same state
+        LAUNCH(mdt_launch_action_embed(state, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next + (int64_t)half * h.M * D, h.M,
+                                       m->A, D, m->Ta, s));
     return MDT_OK;
+}
+
+// One network evaluation on the embedded input in V.y: the decoder blocks at nb samples (conditioning rows from mod_row), then
+// the head `h` on their rows -- summing the MLP's slabs itself when it is the one-launch head.  sigma_next (not null): the next
+// input is embedded into V.y.
+static mdt_status run_eval(mdt_model* m, const View& V, int64_t nb, const float* mod_row, int64_t mod_stride, mdt_head_args h,
+                           const mdt_head_plan* pl, const float* sigma_next, hipStream_t s, mdt_guide gd) {
+    Stream fin;
+    const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
+    MDT_TRY(run_decoder_blocks(m, V, nb, mod_row, mod_stride, s, head_sums ? &fin : nullptr));
+    if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
+    if (sigma_next) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
+    return run_head(m, h, pl, V.hid, sigma_next, s, gd);
 }
 
 // Validate lam and decide whether a guided entry point runs the doubled batch: lam == 1 and a model without a goal token
 // (m->g_row < 0: `uncond` changes nothing there) take the unguided implementation and give its exact bits.
-static mdt_status guide_of(const mdt_model* m, float lam, const char* who, Guide* gd) {
+static mdt_status guide_of(const mdt_model* m, float lam, const char* who, mdt_guide* gd) {
     if (!m) return fail(MDT_ERR_INVALID_ARG, "%s: null handle", who);
     if (!std::isfinite(lam)) return fail(MDT_ERR_INVALID_ARG, "%s: cond_lambda must be finite", who);
     gd->on = lam != 1.f && m->g_row >= 0;
     gd->lam = lam;
-    return MDT_OK;
-}
-
-// the guided call's encoder inputs in the handle's staging buffers (after mdt_reserve(2B)); the pointers are redirected there
-static mdt_status guide_stage(mdt_model* m, const float*& tokens, const float*& tokens2, const float*& goal, int64_t B,
-                              hipStream_t s) {
-    const int w1 = guide_w1(m), w2 = tokens2 ? guide_w2(m) : 0;
-    LAUNCH(mdt_launch_guide_stage(tokens, tokens2, goal, m->g_tok, m->g_tok2, m->g_goal, (int)B, w1, w2, m->G, s));
-    tokens = m->g_tok;
-    tokens2 = tokens2 ? m->g_tok2 : nullptr;
-    goal = m->g_goal;
-    return MDT_OK;
-}
-
-// the conditional half of the cached context -> ctx_out (what the unguided call writes there)
-static mdt_status guide_ctx_out(mdt_model* m, float* ctx_out, int64_t B, hipStream_t s) {
-    if (ctx_out) HIP_TRY(hipMemcpyAsync(ctx_out, m->ctx, (size_t)B * m->Te * m->D * sizeof(float), hipMemcpyDeviceToDevice, s));
     return MDT_OK;
 }
 
@@ -1182,17 +1166,12 @@ extern "C" mdt_status mdt_denoise_cached(mdt_model* m, const float* x, const flo
                     (long long)batch, (long long)m->cached_batch);
     hipStream_t s = (hipStream_t)stream;
     const bool scalar = (flags & MDT_SIGMA_SCALAR) != 0;
-    const int64_t modw = cond_width(m);
     const int64_t sst = scalar ? 0 : 1;  // stride of sigma / of the modulation rows across samples
     MDT_TRY(run_modulation(m, sigma, 1, scalar ? 1 : (int)batch, s));
     LAUNCH(mdt_launch_action_embed(x, (flags & MDT_RAW_INPUT) ? nullptr : sigma, sst, m->cfg.sigma_data, m->Wa, m->ba,
                                    m->y, (int)(batch * m->Ta), m->A, m->D, m->Ta, s));
-    Stream fin;
-    const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
-    MDT_TRY(run_decoder_blocks(m, decoder_view(m, 0), batch, cond_row(m, 0), scalar ? 0 : modw, s, head_sums ? &fin : nullptr));
     mdt_head_args h = head_args(m, m->y, batch, x, sigma, sst, out, (flags & MDT_RAW_OUTPUT) ? MDT_HEAD_RAW : MDT_HEAD_DENOISED);
-    if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
-    return run_head(m, h, m->hid, nullptr, s);
+    return run_eval(m, decoder_view(m, 0), batch, cond_row(m, 0), scalar ? 0 : cond_width(m), h, nullptr, nullptr, s, mdt_guide());
 }
 
 extern "C" mdt_status mdt_forward(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
@@ -1205,25 +1184,89 @@ extern "C" mdt_status mdt_forward(mdt_model* m, const float* tokens, const float
     return mdt_denoise_cached(m, x, sigma, batch, 0, out, stream);
 }
 
-// sigmas_host or sigmas_dev (exactly one non-null): the n_steps + 1 noise levels
-// gd.on (guided): the encoder and the decoder run 2B samples, the head combines the halves and updates B samples of state
-static mdt_status sample_ddim_impl(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
-                                   int32_t modality, const float* x_T, const float* sigmas, const float* sigmas_dev,
-                                   int32_t n_steps, int64_t batch, float* out, float* ctx_out, void* stream, Guide gd = Guide()) {
-    if (!m || !x_T || (!sigmas && !sigmas_dev) || !out || batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_ddim: bad argument");
-    if (n_steps < 1 || n_steps > MAX_STEPS) return fail(MDT_ERR_INVALID_ARG, "n_steps must be 1..%d", MAX_STEPS);
-    hipStream_t s = (hipStream_t)stream;
-    const int honour = m->cfg.arch == MDT_ARCH_MDTV;
-    const bool per_step_ctx = m->cond == COND_TOKEN;  // sigma is a context token: the encoder cannot be hoisted
-    MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));  // before anything is enqueued
-    MDT_TRY(check_loaded(m));
-    const int64_t nb = gd.on ? 2 * batch : batch;  // samples through the network
-    MDT_TRY(mdt_reserve(m, nb));
-    float* const ctx_user = ctx_out;
-    if (gd.on) {
-        MDT_TRY(guide_stage(m, tokens, tokens2, goal, batch, s));
-        ctx_out = nullptr;  // the encoder's second copy would hold 2B samples: the conditional half is copied at the end
+// ------------------------------------------------------------------------------------------------
+// Sampler calls.  Every entry point (the DDIM loop, the plan samplers, adaptive DPM-Solver, and the guided twin of each) fills
+// one SamplerArgs and calls its family's implementation, which checks its arguments (sampler_check, then the family's own),
+// opens the call (sampler_open), runs its evaluations and closes it (sampler_close).
+// ------------------------------------------------------------------------------------------------
+// the arguments every sampler entry point takes
+struct SamplerArgs {
+    const char* who;    // the entry point (error messages)
+    const float* lam;   // the guided twin's weight, or null
+    const float *tokens, *tokens2, *goal;
+    int32_t modality;
+    const float* x_T;
+    int64_t batch;
+    float* out;
+    float* ctx_out;
+    void* stream;
+};
+
+// a sampler call's noise levels: in host memory (they ride in the prep kernel's arguments) or on the device (read in place)
+struct Sched {
+    const float* levels;
+    bool dev;
+    const float* host() const { return dev ? nullptr : levels; }
+    const float* device() const { return dev ? levels : nullptr; }
+};
+
+// An open sampler call: the encoder's inputs -- a guided call's staged 2B-sample copies -- the samples through the network (nb:
+// 2B when guided), where the encoder's context goes (null when guided: sampler_close copies the conditional half to the
+// caller's ctx_out, where the unguided call writes it) and the guidance.
+struct SamplerCall {
+    const float *tokens, *tokens2, *goal;
+    int32_t modality;
+    int64_t batch, nb;
+    float* ctx_out;
+    float* ctx_user;
+    mdt_guide gd;
+    hipStream_t s;
+    mdt_status encode(mdt_model* m, const float* sigma, float* ctx) const {
+        return run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, nb, sigma, 0, ctx, s);
     }
+};
+
+// The first checks of every sampler call, in the order the entry points have always made them: a guided twin's handle and
+// weight (guide_of decides gd), the schedule (sched_ok), then the arguments all families share ("<family>: bad argument").
+static mdt_status sampler_check(const mdt_model* m, const SamplerArgs& a, const char* family, bool sched_ok, mdt_guide* gd) {
+    if (a.lam) MDT_TRY(guide_of(m, *a.lam, a.who, gd));
+    if (!sched_ok) return fail(MDT_ERR_INVALID_ARG, "%s: null sigmas", a.who);
+    if (!m || !a.x_T || !a.out || a.batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: bad argument", family);
+    return MDT_OK;
+}
+
+// The encoder arguments are checked and the parameters known loaded before anything is enqueued; the handle then holds nb
+// samples, and a guided call's encoder inputs are staged in the handle's buffers: tokens and tokens2 twice, the goal then zeros.
+static mdt_status sampler_open(mdt_model* m, const SamplerArgs& a, mdt_guide gd, SamplerCall* c) {
+    MDT_TRY(check_encode_args(m, a.tokens, a.tokens2, a.goal, a.ctx_out));
+    MDT_TRY(check_loaded(m));
+    *c = {a.tokens, a.tokens2, a.goal, a.modality, a.batch, gd.on ? 2 * a.batch : a.batch, a.ctx_out, a.ctx_out, gd,
+          (hipStream_t)a.stream};
+    MDT_TRY(mdt_reserve(m, c->nb));
+    if (!gd.on) return MDT_OK;
+    const int w1 = guide_w1(m), w2 = a.tokens2 ? guide_w2(m) : 0;
+    LAUNCH(mdt_launch_guide_stage(a.tokens, a.tokens2, a.goal, m->g_tok, m->g_tok2, m->g_goal, (int)a.batch, w1, w2, m->G, c->s));
+    c->tokens = m->g_tok;
+    c->tokens2 = a.tokens2 ? m->g_tok2 : nullptr;
+    c->goal = m->g_goal;
+    c->ctx_out = nullptr;  // the encoder's second copy would hold 2B samples
+    return MDT_OK;
+}
+
+static mdt_status sampler_close(mdt_model* m, const SamplerCall& c) {
+    if (c.gd.on && c.ctx_user)
+        HIP_TRY(hipMemcpyAsync(c.ctx_user, m->ctx, (size_t)c.batch * m->Te * m->D * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    return MDT_OK;
+}
+
+// gd.on (guided): the encoder and the decoder run 2B samples, the head combines the halves and updates B samples of state
+static mdt_status sample_ddim_impl(mdt_model* m, const SamplerArgs& a, Sched sc, int32_t n_steps) {
+    mdt_guide gd;
+    MDT_TRY(sampler_check(m, a, "mdt_sample_ddim", sc.levels != nullptr, &gd));
+    if (n_steps < 1 || n_steps > MAX_STEPS) return fail(MDT_ERR_INVALID_ARG, "n_steps must be 1..%d", MAX_STEPS);
+    SamplerCall c;
+    MDT_TRY(sampler_open(m, a, gd, &c));
+    const bool per_step_ctx = m->cond == COND_TOKEN;  // sigma is a context token: the encoder cannot be hoisted
     // per-step scalars, fp32 like the reference's 0-dim tensor math (gc_sampling.py:946-950):
     // t = -ln(sigma); ratio = exp(-t_next)/exp(-t); coef = -expm1(-(t_next - t)) -- by ONE routine (on the device)
     // whether the schedule arrives in host memory (the reference's CPU default) or on the device (mdtv_agent.py:660-667: no
@@ -1235,93 +1278,51 @@ static mdt_status sample_ddim_impl(mdt_model* m, const float* tokens, const floa
     // of the encoder's first small products (rollout batches; at large batches whatever the encoder did not take along is
     // launched behind it)
     const View V = decoder_view(m, 0);
-    LAUNCH(mdt_launch_sample_prep(sigmas_dev, sigmas_dev ? nullptr : sigmas, n_steps, m->steps, m->freqs,
-                                  m->cond == COND_TOKEN ? nullptr : m->sig_e, m->D, x_T, m->cfg.sigma_data, m->Wa, m->ba,
-                                  V.y, (int)(nb * m->Ta), m->A, s, (int)(batch * m->Ta)));
-    mdt_status ms = run_modulation(m, m->steps + 3, 4, n_steps, s, true, !per_step_ctx);  // one row of conditioning vectors per step
-    if (ms == MDT_OK && !per_step_ctx) ms = run_encode(m, tokens, tokens2, goal, modality, honour, nb, nullptr, 0, ctx_out, s);
+    LAUNCH(mdt_launch_sample_prep(sc.device(), sc.host(), n_steps, m->steps, m->freqs, m->cond == COND_TOKEN ? nullptr : m->sig_e,
+                                  m->D, a.x_T, m->cfg.sigma_data, m->Wa, m->ba, V.y, (int)(c.nb * m->Ta), m->A, c.s,
+                                  (int)(a.batch * m->Ta)));
+    mdt_status ms = run_modulation(m, m->steps + 3, 4, n_steps, c.s, true, !per_step_ctx);  // one row of conditioning vectors per step
+    if (ms == MDT_OK && !per_step_ctx) ms = c.encode(m, nullptr, c.ctx_out);
     if (ms != MDT_OK) { mdt_gemm_side_drop(); return ms; }
-    LAUNCH(mdt_gemm_side_flush(s));
+    LAUNCH(mdt_gemm_side_flush(c.s));
     for (int i = 0; i < n_steps; ++i) {
         const bool last = i == n_steps - 1;
+        const float* sigma = m->steps + 4 * i + 3;
         if (per_step_ctx)  // the reference leaves the LAST step's context in latent_encoder_emb
-            MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, honour, nb, m->steps + 4 * i + 3, 0,
-                               last ? ctx_out : nullptr, s));
-        Stream fin;
-        const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
-        MDT_TRY(run_decoder_blocks(m, V, nb, cond_row(m, i), 0, s, head_sums ? &fin : nullptr));
-        mdt_head_args h = head_args(m, V.y, batch, i == 0 ? x_T : m->xbuf, m->steps + 4 * i + 3, 0, last ? out : m->xbuf,
-                                    MDT_HEAD_DDIM);
-        if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
+            MDT_TRY(c.encode(m, sigma, last ? c.ctx_out : nullptr));
+        mdt_head_args h = head_args(m, V.y, a.batch, i == 0 ? a.x_T : m->xbuf, sigma, 0, last ? a.out : m->xbuf, MDT_HEAD_DDIM);
         h.step = m->steps + 4 * i;
-        if (!last) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
-        MDT_TRY(run_head(m, h, V.hid, m->steps + 4 * (i + 1) + 3, s, gd));
+        MDT_TRY(run_eval(m, V, c.nb, cond_row(m, i), 0, h, nullptr, last ? nullptr : sigma + 4, c.s, gd));
     }
-    if (gd.on) MDT_TRY(guide_ctx_out(m, ctx_user, batch, s));
-    return MDT_OK;
+    return sampler_close(m, c);
 }
 
 extern "C" mdt_status mdt_sample_ddim(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                       int32_t modality, const float* x_T, const float* sigmas, int32_t n_steps,
                                       int64_t batch, float* out, float* ctx_out, void* stream) {
-    if (!sigmas) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_ddim: null sigmas");
-    return sample_ddim_impl(m, tokens, tokens2, goal, modality, x_T, sigmas, nullptr, n_steps, batch, out, ctx_out, stream);
+    return sample_ddim_impl(m, {"mdt_sample_ddim", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream},
+                            {sigmas, false}, n_steps);
 }
 
 extern "C" mdt_status mdt_sample_ddim_dev(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                           int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
                                           int64_t batch, float* out, float* ctx_out, void* stream) {
-    if (!sigmas_dev) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_ddim_dev: null sigmas");
-    return sample_ddim_impl(m, tokens, tokens2, goal, modality, x_T, nullptr, sigmas_dev, n_steps, batch, out, ctx_out, stream);
+    return sample_ddim_impl(m, {"mdt_sample_ddim_dev", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream},
+                            {sigmas_dev, true}, n_steps);
 }
 
 extern "C" mdt_status mdt_sample_ddim_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                              int32_t modality, const float* x_T, const float* sigmas, int32_t n_steps,
                                              int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
-    Guide gd;
-    MDT_TRY(guide_of(m, cond_lambda, "mdt_sample_ddim_guided", &gd));
-    if (!sigmas) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_ddim_guided: null sigmas");
-    return sample_ddim_impl(m, tokens, tokens2, goal, modality, x_T, sigmas, nullptr, n_steps, batch, out, ctx_out, stream, gd);
+    return sample_ddim_impl(m, {"mdt_sample_ddim_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
+                                stream}, {sigmas, false}, n_steps);
 }
 
 extern "C" mdt_status mdt_sample_ddim_dev_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                                  int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
                                                  int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
-    Guide gd;
-    MDT_TRY(guide_of(m, cond_lambda, "mdt_sample_ddim_dev_guided", &gd));
-    if (!sigmas_dev) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_ddim_dev_guided: null sigmas");
-    return sample_ddim_impl(m, tokens, tokens2, goal, modality, x_T, nullptr, sigmas_dev, n_steps, batch, out, ctx_out, stream, gd);
-}
-
-// run_head with a sampler plan's update (MDT_HEAD_PLAN).  The MLP head embeds the next input Y' (pl.y_out) in a launch of
-// its own, as run_head embeds the DDIM state.
-static mdt_status run_head_plan(mdt_model* m, mdt_head_args h, const mdt_head_plan& pl, float* scratch, const float* sigma_next,
-                                hipStream_t s, Guide gd = Guide()) {
-    if (m->HP == 0) {
-        if (gd.on) LAUNCH(mdt_launch_head_guided(h, &pl, gd.lam, s));
-        else LAUNCH(mdt_launch_head_plan(h, pl, s));
-        return MDT_OK;
-    }
-    const int D = m->D, HP = m->HP;
-    const int rows = gd.on ? 2 * h.M : h.M;  // decoder rows (run_head)
-    float* ln = scratch;
-    float* hh = scratch + (int64_t)rows * D;
-    LAUNCH(mdt_launch_layernorm(h.y, m->dec_ln_w, m->dec_ln_b, ln, rows, D, s));
-    mdt_gemm_args g = gemm_args(ln, D, m->head0, hh, HP, rows);
-    g.act = MDT_ACT_GELU;
-    LAUNCH(mdt_launch_gemm(g, s));
-    float* y_next = h.y_next;
-    h.y = hh; h.D = HP; h.no_ln = 1; h.y_next = nullptr;
-    if (gd.on) LAUNCH(mdt_launch_head_guided(h, &pl, gd.lam, s));
-    else LAUNCH(mdt_launch_head_plan(h, pl, s));
-    if (y_next) {
-        LAUNCH(mdt_launch_action_embed(pl.y_out, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next, h.M, m->A, D,
-                                       m->Ta, s));
-        if (gd.on)
-            LAUNCH(mdt_launch_action_embed(pl.y_out, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next + (int64_t)h.M * D,
-                                           h.M, m->A, D, m->Ta, s));
-    }
-    return MDT_OK;
+    return sample_ddim_impl(m, {"mdt_sample_ddim_dev_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out,
+                                ctx_out, stream}, {sigmas_dev, true}, n_steps);
 }
 
 // MDT_PLAN_* -> mdt_status with the message of the failed check
@@ -1352,126 +1353,96 @@ extern "C" mdt_status mdt_sampler_plan(int32_t kind, const mdt_sampler_params* p
 
 // evaluation e of the plan in m->plan: (per evaluation for COND_TOKEN: the encoder with its sigma -> ctx_out), one decoder pass,
 // the plan head reading the state xs, writing X' to out and Y' to y_out; the next input is embedded unless `last`
-// gd.on: tokens / tokens2 / goal are the staged 2B-sample inputs and ctx_out is null (the caller copies the conditional half)
-static mdt_status run_plan_eval(mdt_model* m, const View& V, const float* tokens, const float* tokens2, const float* goal,
-                                int32_t modality, int64_t batch, int e, bool last, const float* xs, float* out, float* y_out,
-                                const float* noise, int32_t n_noise, float* ctx_out, hipStream_t s, Guide gd = Guide()) {
+static mdt_status run_plan_eval(mdt_model* m, const View& V, const SamplerCall& c, int e, bool last, const float* xs, float* out,
+                                float* y_out, const float* noise, int32_t n_noise, float* ctx_out) {
     mdt_sampler_eval* ev = m->plan->e;
-    const int64_t nb = gd.on ? 2 * batch : batch;
-    if (m->cond == COND_TOKEN)
-        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, nb, &ev[e].sigma, 0, ctx_out, s));
-    Stream fin;
-    const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
-    MDT_TRY(run_decoder_blocks(m, V, nb, cond_row(m, e), 0, s, head_sums ? &fin : nullptr));
-    mdt_head_args h = head_args(m, V.y, batch, m->ybuf, &ev[e].sigma, 0, out, MDT_HEAD_PLAN);
-    if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
-    if (!last) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
+    if (m->cond == COND_TOKEN) MDT_TRY(c.encode(m, &ev[e].sigma, ctx_out));
     mdt_head_plan pl;
     pl.e = &ev[e];
     pl.xs = xs;
     pl.hist = m->hist;
     pl.noise = noise;
     pl.y_out = y_out;
-    pl.nel = (int64_t)batch * m->Ta * m->A;
+    pl.nel = (int64_t)c.batch * m->Ta * m->A;
     pl.n_noise = noise ? n_noise : 0;
-    return run_head_plan(m, h, pl, V.hid, last ? nullptr : &ev[e].sigma_next, s, gd);
+    mdt_head_args h = head_args(m, V.y, c.batch, m->ybuf, &ev[e].sigma, 0, out, MDT_HEAD_PLAN);
+    return run_eval(m, V, c.nb, cond_row(m, e), 0, h, &pl, last ? nullptr : &ev[e].sigma_next, c.s, c.gd);
 }
 
-// sigmas_host or sigmas_dev (exactly one non-null): the n_steps + 1 noise levels.  The structure of sample_ddim_impl: the plan
-// and the sigma embeddings of every evaluation (one launch), the first input, the conditioning rows of every evaluation (their
-// GEMMs ride in the encoder's launches), the encoder and cross K/V once, then one decoder pass + plan head per evaluation.
-static mdt_status sample_plan_impl(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
-                                   const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas,
-                                   const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch,
-                                   float* out, float* ctx_out, void* stream, Guide gd = Guide()) {
-    if (!m || !x_T || (!sigmas && !sigmas_dev) || !out || batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_sample: bad argument");
+// The structure of sample_ddim_impl: the plan and the sigma embeddings of every evaluation (one launch), the first input, the
+// conditioning rows of every evaluation (their GEMMs ride in the encoder's launches), the encoder and cross K/V once, then one
+// decoder pass + plan head per evaluation.
+static mdt_status sample_plan_impl(mdt_model* m, const SamplerArgs& a, int32_t kind, const mdt_sampler_params* params, Sched sc,
+                                   int32_t n_steps, const float* noise, int32_t n_noise) {
+    mdt_guide gd;
+    MDT_TRY(sampler_check(m, a, "mdt_sample", sc.levels != nullptr, &gd));
     const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
     int E = 0, rows = 0;
     MDT_TRY(plan_fail(mdt_plan_shape(kind, p, n_steps, &E, &rows), "mdt_sample", kind));
-    if (sigmas) {  // a host schedule: the loop's exact draw count (a device schedule: the structural maximum)
-        MDT_TRY(plan_fail(mdt_plan_check_levels(kind, p, sigmas), "mdt_sample", kind));
+    if (sc.host()) {  // a host schedule: the loop's exact draw count (a device schedule: the structural maximum)
+        MDT_TRY(plan_fail(mdt_plan_check_levels(kind, p, sc.host()), "mdt_sample", kind));
         static thread_local mdt_sampler_plan_t hp;
-        mdt_build_sampler_plan(kind, p, sigmas, n_steps, &hp);
+        mdt_build_sampler_plan(kind, p, sc.host(), n_steps, &hp);
         rows = hp.n_noise;
     }
     if (!noise && mdt_plan_needs_noise(kind, p))
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample: this sampler and parameter set need the noise buffer (%d rows)", rows);
     if (noise && n_noise < rows)
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample: the noise buffer holds %d rows, the sampler reads %d", n_noise, rows);
-    if (misaligned(x_T) || misaligned(out) || misaligned(noise))
+    if (misaligned(a.x_T) || misaligned(a.out) || misaligned(noise))
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample: pointers must be 16-byte aligned");
     if (m->A > 16) return fail(MDT_ERR_UNSUPPORTED, "mdt_sample: action_dim must be <= 16");
-    hipStream_t s = (hipStream_t)stream;
-    const int honour = m->cfg.arch == MDT_ARCH_MDTV;
+    SamplerCall c;
+    MDT_TRY(sampler_open(m, a, gd, &c));
     const bool per_step_ctx = m->cond == COND_TOKEN;  // sigma is a context token: the encoder runs per evaluation
-    MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));  // before anything is enqueued
-    MDT_TRY(check_loaded(m));
-    const int64_t nb = gd.on ? 2 * batch : batch;  // samples through the network
-    MDT_TRY(mdt_reserve(m, nb));
-    float* const ctx_user = ctx_out;
-    if (gd.on) {
-        MDT_TRY(guide_stage(m, tokens, tokens2, goal, batch, s));
-        ctx_out = nullptr;
-    }
     const View V = decoder_view(m, 0);
-    const int M = (int)(batch * m->Ta);
     mdt_sampler_eval* ev = m->plan->e;
-    LAUNCH(mdt_launch_sampler_prep(sigmas_dev, sigmas_dev ? nullptr : sigmas, n_steps, kind, p, m->plan, m->freqs,
-                                   per_step_ctx ? nullptr : m->sig_e, m->D, x_T, noise, noise ? n_noise : 0, m->ybuf, m->hist,
-                                   m->cfg.sigma_data,
-                                   m->Wa, m->ba, V.y, (int)(nb * m->Ta), m->A, s, M));
+    LAUNCH(mdt_launch_sampler_prep(sc.device(), sc.host(), n_steps, kind, p, m->plan, m->freqs, per_step_ctx ? nullptr : m->sig_e,
+                                   m->D, a.x_T, noise, noise ? n_noise : 0, m->ybuf, m->hist, m->cfg.sigma_data, m->Wa, m->ba, V.y,
+                                   (int)(c.nb * m->Ta), m->A, c.s, (int)(a.batch * m->Ta)));
     const int stride = (int)(sizeof(mdt_sampler_eval) / sizeof(float));
-    mdt_status ms = run_modulation(m, &ev[0].sigma, stride, E, s, true, !per_step_ctx);  // one conditioning row per evaluation
-    if (ms == MDT_OK && !per_step_ctx) ms = run_encode(m, tokens, tokens2, goal, modality, honour, nb, nullptr, 0, ctx_out, s);
+    mdt_status ms = run_modulation(m, &ev[0].sigma, stride, E, c.s, true, !per_step_ctx);  // one conditioning row per evaluation
+    if (ms == MDT_OK && !per_step_ctx) ms = c.encode(m, nullptr, c.ctx_out);
     if (ms != MDT_OK) { mdt_gemm_side_drop(); return ms; }
-    LAUNCH(mdt_gemm_side_flush(s));
+    LAUNCH(mdt_gemm_side_flush(c.s));
     for (int e = 0; e < E; ++e) {
         const bool last = e == E - 1;
-        MDT_TRY(run_plan_eval(m, V, tokens, tokens2, goal, modality, batch, e, last, e == 0 ? x_T : m->xbuf, last ? out : m->xbuf,
-                              last ? nullptr : m->ybuf, noise, n_noise, last ? ctx_out : nullptr, s, gd));
+        MDT_TRY(run_plan_eval(m, V, c, e, last, e == 0 ? a.x_T : m->xbuf, last ? a.out : m->xbuf, last ? nullptr : m->ybuf, noise,
+                              n_noise, last ? c.ctx_out : nullptr));
     }
-    if (gd.on) MDT_TRY(guide_ctx_out(m, ctx_user, batch, s));
-    return MDT_OK;
+    return sampler_close(m, c);
 }
 
 extern "C" mdt_status mdt_sample(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
                                  const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas_host,
                                  int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, float* out, float* ctx_out,
                                  void* stream) {
-    if (!sigmas_host) return fail(MDT_ERR_INVALID_ARG, "mdt_sample: null sigmas");
-    return sample_plan_impl(m, tokens, tokens2, goal, modality, x_T, kind, params, sigmas_host, nullptr, n_steps, noise, n_noise,
-                            batch, out, ctx_out, stream);
+    return sample_plan_impl(m, {"mdt_sample", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream}, kind,
+                            params, {sigmas_host, false}, n_steps, noise, n_noise);
 }
 
 extern "C" mdt_status mdt_sample_dev(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                      int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
                                      const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
                                      int64_t batch, float* out, float* ctx_out, void* stream) {
-    if (!sigmas_dev) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dev: null sigmas");
-    return sample_plan_impl(m, tokens, tokens2, goal, modality, x_T, kind, params, nullptr, sigmas_dev, n_steps, noise, n_noise,
-                            batch, out, ctx_out, stream);
+    return sample_plan_impl(m, {"mdt_sample_dev", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream}, kind,
+                            params, {sigmas_dev, true}, n_steps, noise, n_noise);
 }
 
 extern "C" mdt_status mdt_sample_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                         int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
                                         const float* sigmas_host, int32_t n_steps, const float* noise, int32_t n_noise,
                                         int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
-    Guide gd;
-    MDT_TRY(guide_of(m, cond_lambda, "mdt_sample_guided", &gd));
-    if (!sigmas_host) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_guided: null sigmas");
-    return sample_plan_impl(m, tokens, tokens2, goal, modality, x_T, kind, params, sigmas_host, nullptr, n_steps, noise, n_noise,
-                            batch, out, ctx_out, stream, gd);
+    return sample_plan_impl(m, {"mdt_sample_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream},
+                            kind, params, {sigmas_host, false}, n_steps, noise, n_noise);
 }
 
 extern "C" mdt_status mdt_sample_dev_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                             int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
                                             const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
                                             int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
-    Guide gd;
-    MDT_TRY(guide_of(m, cond_lambda, "mdt_sample_dev_guided", &gd));
-    if (!sigmas_dev) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dev_guided: null sigmas");
-    return sample_plan_impl(m, tokens, tokens2, goal, modality, x_T, kind, params, nullptr, sigmas_dev, n_steps, noise, n_noise,
-                            batch, out, ctx_out, stream, gd);
+    return sample_plan_impl(m, {"mdt_sample_dev_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
+                                stream}, kind, params, {sigmas_dev, true}, n_steps, noise, n_noise);
 }
 
 extern "C" mdt_status mdt_dpm_control_init(mdt_dpm_control* c, double h, double pcoeff, double icoeff, double dcoeff,
@@ -1503,28 +1474,26 @@ struct DpmHost {
 // input (X at sigma(s)), the conditioning rows of its evaluations, one decoder pass + plan head per evaluation (the last writes
 // high -> hi and low -> lo), the error partials, one read-back and the controller.  Accepting swaps pointers: X <- high,
 // prev <- low.  Every scalar is the loop's: s and t in fp32, t = min / max(t_end, fp32(s + fp32(h))), the 1e-5 end test.
-static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
-                                           int32_t modality, const float* x_T, float sigma_min, float sigma_max,
-                                           const mdt_dpm_adaptive_params* params, int64_t batch, float* out, float* ctx_out,
-                                           mdt_dpm_adaptive_info* info, void* stream, Guide gd) {
-    if (!m || !x_T || !out || batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: bad argument");
+static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const SamplerArgs& a, float sigma_min, float sigma_max,
+                                           const mdt_dpm_adaptive_params* params, mdt_dpm_adaptive_info* info) {
+    mdt_guide gd;
+    MDT_TRY(sampler_check(m, a, "mdt_sample_dpm_adaptive", true, &gd));
     mdt_dpm_adaptive_params p = {3, 0.05, 0.0078, 0.05, 0.0, 1.0, 0.0, 0.81};
     if (params) p = *params;
     if (p.order != 2 && p.order != 3) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: order must be 2 or 3");
     if (!(sigma_min > 0.f) || !(sigma_max > 0.f))
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: sigma_min and sigma_max must be > 0");
-    if (misaligned(x_T) || misaligned(out)) return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: pointers must be 16-byte aligned");
+    if (misaligned(a.x_T) || misaligned(a.out))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: pointers must be 16-byte aligned");
     if (m->A > 16) return fail(MDT_ERR_UNSUPPORTED, "mdt_sample_dpm_adaptive: action_dim must be <= 16");
-    hipStream_t s = (hipStream_t)stream;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(s, &cs));
+    HIP_TRY(hipStreamIsCapturing((hipStream_t)a.stream, &cs));
     if (cs != hipStreamCaptureStatusNone)
         return fail(MDT_ERR_STATE, "mdt_sample_dpm_adaptive: the call synchronises every step and cannot be captured");
-    MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));
-    MDT_TRY(check_loaded(m));
-    const int64_t nb = gd.on ? 2 * batch : batch;  // samples through the network
-    MDT_TRY(mdt_reserve(m, nb));
-    const int M = (int)(batch * m->Ta);
+    SamplerCall c;
+    MDT_TRY(sampler_open(m, a, gd, &c));
+    hipStream_t s = c.s;
+    const int M = (int)(a.batch * m->Ta);
     const int64_t nel = (int64_t)M * m->A, nel4 = (nel + 3) & ~(int64_t)3;
     MDT_TRY(mdt_grow_carve(m->ad_ws, m->ad_cap, nel4, [&](Bump& b, int64_t cap) { (void)b.take(4 * cap + MDT_DPM_PARTS); }));
     if (!m->ad_host) HIP_TRY(hipHostMalloc(&m->ad_host, sizeof(DpmHost), hipHostMallocDefault));
@@ -1532,16 +1501,9 @@ static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const float* tokens, co
     float *X = m->ad_ws, *prev = X + m->ad_cap, *hi = prev + m->ad_cap, *lo = hi + m->ad_cap;
     float* part = m->ad_ws + 4 * m->ad_cap;
     const View V = decoder_view(m, 0);
-    const bool per_step_ctx = m->cond == COND_TOKEN;
-    HIP_TRY(hipMemcpyAsync(X, x_T, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipMemcpyAsync(prev, x_T, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
-    float* const ctx_user = ctx_out;
-    if (gd.on) {
-        MDT_TRY(guide_stage(m, tokens, tokens2, goal, batch, s));
-        ctx_out = nullptr;
-    }
-    if (!per_step_ctx)
-        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, nb, nullptr, 0, ctx_out, s));
+    HIP_TRY(hipMemcpyAsync(X, a.x_T, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(prev, a.x_T, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (m->cond != COND_TOKEN) MDT_TRY(c.encode(m, nullptr, c.ctx_out));
     const float t_start = mdt_plan_detail::dpm_t(sigma_max), t_end = mdt_plan_detail::dpm_t(sigma_min);
     const bool forward = t_end > t_start;
     mdt_dpm_control ctl;
@@ -1562,13 +1524,13 @@ static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const float* tokens, co
         const int E = hb->plan.n_evals;
         const size_t bytes = sizeof(mdt_sampler_plan_t) - (size_t)(MDT_SAMPLER_MAX_EVALS - E) * sizeof(mdt_sampler_eval);
         HIP_TRY(hipMemcpyAsync(m->plan, &hb->plan, bytes, hipMemcpyHostToDevice, s));
-        LAUNCH(mdt_launch_sampler_first(m->plan, X, nullptr, 0, m->ybuf, m->hist, m->cfg.sigma_data, m->Wa, m->ba, V.y, (int)(nb * m->Ta),
+        LAUNCH(mdt_launch_sampler_first(m->plan, X, nullptr, 0, m->ybuf, m->hist, m->cfg.sigma_data, m->Wa, m->ba, V.y, (int)(c.nb * m->Ta),
                                         m->A, m->D, s, M));
         MDT_TRY(run_modulation(m, &m->plan->e[0].sigma, stride, E, s));
         for (int e = 0; e < E; ++e) {
             const bool last = e == E - 1;
-            MDT_TRY(run_plan_eval(m, V, tokens, tokens2, goal, modality, batch, e, last, e == 0 ? X : m->xbuf,
-                                  last ? hi : m->xbuf, last ? lo : m->ybuf, nullptr, 0, ctx_out, s, gd));
+            MDT_TRY(run_plan_eval(m, V, c, e, last, e == 0 ? X : m->xbuf, last ? hi : m->xbuf, last ? lo : m->ybuf, nullptr, 0,
+                                  c.ctx_out));
         }
         LAUNCH(mdt_launch_dpm_error(lo, hi, prev, nel, (float)p.rtol, (float)p.atol, part, s));
         HIP_TRY(hipMemcpyAsync(hb->part, part, parts * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -1592,8 +1554,8 @@ static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const float* tokens, co
             inf.n_reject += 1;
         }
     }
-    HIP_TRY(hipMemcpyAsync(out, X, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (gd.on) MDT_TRY(guide_ctx_out(m, ctx_user, batch, s));
+    HIP_TRY(hipMemcpyAsync(a.out, X, nel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    MDT_TRY(sampler_close(m, c));
     if (info) *info = inf;
     return MDT_OK;
 }
@@ -1602,18 +1564,16 @@ extern "C" mdt_status mdt_sample_dpm_adaptive(mdt_model* m, const float* tokens,
                                               int32_t modality, const float* x_T, float sigma_min, float sigma_max,
                                               const mdt_dpm_adaptive_params* params, int64_t batch, float* out, float* ctx_out,
                                               mdt_dpm_adaptive_info* info, void* stream) {
-    return sample_dpm_adaptive_impl(m, tokens, tokens2, goal, modality, x_T, sigma_min, sigma_max, params, batch, out, ctx_out, info,
-                                    stream, Guide());
+    return sample_dpm_adaptive_impl(m, {"mdt_sample_dpm_adaptive", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
+                                        stream}, sigma_min, sigma_max, params, info);
 }
 
 extern "C" mdt_status mdt_sample_dpm_adaptive_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                                      int32_t modality, const float* x_T, float sigma_min, float sigma_max,
                                                      const mdt_dpm_adaptive_params* params, int64_t batch, float* out,
                                                      float* ctx_out, float cond_lambda, mdt_dpm_adaptive_info* info, void* stream) {
-    Guide gd;
-    MDT_TRY(guide_of(m, cond_lambda, "mdt_sample_dpm_adaptive_guided", &gd));
-    return sample_dpm_adaptive_impl(m, tokens, tokens2, goal, modality, x_T, sigma_min, sigma_max, params, batch, out, ctx_out, info,
-                                    stream, gd);
+    return sample_dpm_adaptive_impl(m, {"mdt_sample_dpm_adaptive_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch,
+                                        out, ctx_out, stream}, sigma_min, sigma_max, params, info);
 }
 
 extern "C" mdt_status mdt_loss_fwd(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,

@@ -23,6 +23,8 @@ import torch
 
 from . import utils
 from ... import _lib
+from ..networks._engine import guidance
+from .graphed import GraphedDDIM, GraphedSampler
 from .score_wrappers import GCDenoiser
 
 
@@ -178,18 +180,33 @@ def _graph_wanted(model, state, action, goal, sigmas, tag=None) -> bool:
     return seen.get(key, 0) > _GRAPH_AUTO_AFTER
 
 
-def _graphed(model, state, action, goal, sigmas, cond_lambda=None):
-    """One GraphedDDIM per (shapes, modality, state keys, guidance weight) of a model, kept on the model (at most four)."""
-    from .graphed import GraphedDDIM
-    cache = model.__dict__.setdefault("_graphed_samplers", [])
-    for gsamp in cache:
-        if gsamp.cond_lambda == cond_lambda and gsamp.matches(state, action, goal, sigmas):
-            return gsamp(state, action, goal, sigmas)
-    gsamp = GraphedDDIM(model, state, action, goal, sigmas if torch.is_tensor(sigmas) else torch.as_tensor(sigmas),
-                        cond_lambda=cond_lambda)
-    cache.append(gsamp)
-    del cache[:-4]
-    return gsamp(state, action, goal, sigmas)
+def _graph_route(model, cache, tag, key, state, action, goal, sigmas, make, what, noise=None):
+    """A native sampler call replayed as a HIP graph, or None: the eager call runs then.  The rule is _graph_wanted's, ``tag``
+    joining the call's graph key (None: unguided DDIM).  The graphs live on the model in the list ``cache`` (at most four) and
+    are found by GraphedDDIM.matches with ``key``; ``make(sigmas)`` captures a new one.  In auto mode a capture that fails
+    (another thread allocating / synchronising while torch's global capture mode is on, ...) must not break a rollout the eager
+    path would have served: that call shape stays eager, with a warning naming ``what``.  MDT_HIP_GRAPH=1 re-raises."""
+    if not _graph_wanted(model, state, action, goal, sigmas, tag=tag):
+        return None
+    try:
+        graphs = model.__dict__.setdefault(cache, [])
+        for gsamp in graphs:
+            if gsamp.matches(state, action, goal, sigmas, key=key, noise=noise):
+                return gsamp(state, action, goal, sigmas, noise=noise)
+        gsamp = make(sigmas if torch.is_tensor(sigmas) else torch.as_tensor(sigmas))
+        graphs.append(gsamp)
+        del graphs[:-4]
+        return gsamp(state, action, goal, sigmas, noise=noise)  # the same launches, replayed as a HIP graph
+    except Exception as exc:  # noqa: BLE001 -- whatever the capture raised, the eager launches still work
+        if _GRAPH_SAMPLER:
+            raise
+        failed = _graph_key(state, action, goal, sigmas)
+        model.__dict__.setdefault("_graph_failed", set()).add(failed if tag is None else (tag,) + failed)
+        model.__dict__.pop(cache, None)
+        import warnings
+        warnings.warn(f"mdt_policy_amd: HIP-graph capture of {what} failed ({exc!r}); this call shape stays eager")
+        torch.cuda.synchronize()
+        return None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -199,20 +216,8 @@ def _graphed(model, state, action, goal, sigmas, cond_lambda=None):
 # plan the call builds assumes what every get_sigmas_* guarantees -- all levels > 0 but a final 0 -- which a host schedule is
 # checked for (else: the host loop); a device schedule is read in place, unchecked.
 # ------------------------------------------------------------------------------------------------
-def _native_guidance(extra_args):
-    """(native, cond_lambda) for a sampler's ``extra_args``: no extra arguments -> (True, None); ``{"cond_lambda": lam}`` alone ->
-    (True, lam), or (True, None) when lam == 1 (the conditional model: today's unguided call); anything else -> (False, None),
-    the host loop, which hands extra_args to GCDenoiser.forward."""
-    if not extra_args:
-        return True, None
-    if set(extra_args) != {"cond_lambda"}:
-        return False, None
-    lam = float(extra_args["cond_lambda"])
-    return True, (None if lam == 1.0 else lam)
-
-
 def _native_ok(model, sigmas, scaler, callback, extra_args) -> bool:
-    if not isinstance(model, GCDenoiser) or callback is not None or not _native_guidance(extra_args)[0] or scaler is not None:
+    if not isinstance(model, GCDenoiser) or callback is not None or not guidance(**(extra_args or {}))[0] or scaler is not None:
         return False
     n = len(sigmas) - 1
     if n < 1 or n > _lib.SAMPLER_MAX_STEPS:
@@ -245,42 +250,21 @@ def _ancestral_draws(sigmas, eta):
     return sum(1 for i in range(n) if get_ancestral_step(sig[i], sig[i + 1], eta=eta)[0] > 0)
 
 
-def _graphed_native(model, kind, params, state, action, goal, sigmas, noise, n_steps=None):
-    """One GraphedSampler per (kind, parameters, shapes, modality, state keys) of a model, kept on the model (at most four)."""
-    from .graphed import GraphedSampler
-    cache = model.__dict__.setdefault("_graphed_native", [])
-    for gsamp in cache:
-        if gsamp.matches_sampler(kind, params, state, action, goal, sigmas, noise, n_steps):
-            return gsamp(state, action, goal, sigmas, noise=noise)
-    gsamp = GraphedSampler(model, kind, params, state, action, goal,
-                           sigmas if torch.is_tensor(sigmas) else torch.as_tensor(sigmas), noise, n_steps)
-    cache.append(gsamp)
-    del cache[:-4]
-    return gsamp(state, action, goal, sigmas, noise=noise)
-
-
 def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, extra_args=None, **params):
     """The native call, replayed as a HIP graph by sample_ddim's rule (rollout-sized batches from the third identical call).
     ``n_steps``: dpm_fast's evaluation count (its schedule is the two levels, which join the graph key with it).  ``extra_args``:
     the sampler's, which _native_ok admitted -- a guidance weight joins the parameters (and with them the graph key)."""
-    lam = _native_guidance(extra_args)[1]
+    lam = guidance(**(extra_args or {}))[1]
     if lam is not None:
         params = dict(params, cond_lambda=lam)
     tag = (kind, tuple(sorted(params.items())))
     if n_steps is not None:
         tag += (n_steps, tuple(float(v) for v in sigmas))
-    if _graph_wanted(model, state, action, goal, sigmas, tag=tag):
-        try:
-            return _graphed_native(model, kind, params, state, action, goal, sigmas, noise, n_steps)
-        except Exception as exc:  # noqa: BLE001 -- as in sample_ddim: a failed capture leaves this call shape eager
-            if _GRAPH_SAMPLER:
-                raise
-            key = (tag,) + _graph_key(state, action, goal, sigmas)
-            model.__dict__.setdefault("_graph_failed", set()).add(key)
-            model.__dict__.pop("_graphed_native", None)
-            import warnings
-            warnings.warn(f"mdt_policy_amd: HIP-graph capture of sample_{kind} failed ({exc!r}); this call shape stays eager")
-            torch.cuda.synchronize()
+    out = _graph_route(model, "_graphed_native", tag, (kind, params, n_steps), state, action, goal, sigmas,
+                       lambda sig: GraphedSampler(model, kind, params, state, action, goal, sig, noise, n_steps), f"sample_{kind}",
+                       noise=noise)
+    if out is not None:
+        return out
     return model.sample_native(kind, state, action, goal, sigmas, noise=noise, n_steps=n_steps, **params)
 
 
@@ -292,37 +276,16 @@ def sample_ddim(model, state, action, goal, sigmas, scaler=None, extra_args=None
     `scaler` is accepted and never read, exactly as in the reference (its DDIM has no `clip_output` call), so a harness run
     with `use_scaler` (mdtv_agent.py:606-614) keeps the fused native loop; only `callback` / `extra_args` need the step loop."""
     extra_args = {} if extra_args is None else extra_args
-    native, lam = _native_guidance(extra_args)
+    native, lam = guidance(**extra_args)
     if isinstance(model, GCDenoiser) and callback is None and native:
-        if lam is not None:  # classifier-free guidance: the guided native call, its graphs keyed by the weight too
-            if not math.isfinite(lam):
-                raise ValueError(f"cond_lambda must be finite, got {lam}")
-            tag = ("ddim_guided", lam)
-            if _graph_wanted(model, state, action, goal, sigmas, tag=tag):
-                try:
-                    return _graphed(model, state, action, goal, sigmas, cond_lambda=lam)
-                except Exception as exc:  # noqa: BLE001 -- as below
-                    if _GRAPH_SAMPLER:
-                        raise
-                    model.__dict__.setdefault("_graph_failed", set()).add((tag,) + _graph_key(state, action, goal, sigmas))
-                    model.__dict__.pop("_graphed_samplers", None)
-                    import warnings
-                    warnings.warn(f"mdt_policy_amd: HIP-graph capture of guided sample_ddim failed ({exc!r}); this call shape stays eager")
-                    torch.cuda.synchronize()
-            return model.sample_ddim(state, action, goal, sigmas, cond_lambda=lam)
-        if _graph_wanted(model, state, action, goal, sigmas):
-            if _GRAPH_SAMPLER:
-                return _graphed(model, state, action, goal, sigmas)  # the same launches, replayed as a HIP graph
-            try:  # auto mode: a capture that fails (another thread allocating / synchronising while torch's global capture
-                #   mode is on, ...) must not break a rollout the eager path would have served
-                return _graphed(model, state, action, goal, sigmas)
-            except Exception as exc:  # noqa: BLE001 -- whatever the capture raised, the eager launches below still work
-                model.__dict__.setdefault("_graph_failed", set()).add(_graph_key(state, action, goal, sigmas))
-                model.__dict__.pop("_graphed_samplers", None)
-                import warnings
-                warnings.warn(f"mdt_policy_amd: HIP-graph capture of sample_ddim failed ({exc!r}); this call shape stays eager")
-                torch.cuda.synchronize()
-        return model.sample_ddim(state, action, goal, sigmas)  # fused native loop
+        # guidance: the guided native call, its graphs keyed by the weight too
+        tag, kw = (None, {}) if lam is None else (("ddim_guided", lam), {"cond_lambda": lam})
+        out = _graph_route(model, "_graphed_samplers", tag, lam, state, action, goal, sigmas,
+                           lambda sig: GraphedDDIM(model, state, action, goal, sig, cond_lambda=lam),
+                           "sample_ddim" if lam is None else "guided sample_ddim")
+        if out is not None:
+            return out
+        return model.sample_ddim(state, action, goal, sigmas, **kw)  # fused native loop
     sig = _host(sigmas)
     with _hoist(model, state, goal):
         for i in range(len(sig) - 1):
@@ -757,7 +720,7 @@ def sample_dpm_fast(model, state, action, goal, sigma_min, sigma_max, n, scaler=
     if eta and not t_end > t_start:
         raise ValueError('eta must be 0 for reverse sampling')
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
-    if (isinstance(model, GCDenoiser) and callback is None and _native_guidance(extra_args)[0] and scaler is None
+    if (isinstance(model, GCDenoiser) and callback is None and guidance(**(extra_args or {}))[0] and scaler is None
             and 1 <= n <= _lib.SAMPLER_MAX_EVALS):
         return _run_native("dpm_fast", model, state, action, goal, [float(sigma_max), float(sigma_min)],
                            _dpm_fast_noise(action, t_start, t_end, n, eta, noise_sampler), n_steps=n, eta=eta, s_noise=s_noise,
@@ -816,7 +779,7 @@ def sample_dpm_adaptive(model, state, action, goal, sigma_min, sigma_max, extra_
     t_end = _t(torch.tensor(float(sigma_min))).to(torch.float32)
     if eta and not bool(t_end > t_start):
         raise ValueError('eta must be 0 for reverse sampling')
-    native, lam = _native_guidance(extra_args)
+    native, lam = guidance(**(extra_args or {}))
     if (isinstance(model, GCDenoiser) and callback is None and native and not eta and action.device.type == "cuda"
             and not torch.cuda.is_current_stream_capturing()):
         kw = {} if lam is None else {"cond_lambda": lam}  # guidance: mdt_sample_dpm_adaptive_guided

@@ -43,6 +43,12 @@ class GraphedDDIM:
     def _engine(self):
         return self.model._engine(state=self._static_state)
 
+    _noise = None  # the captured noise rows (GraphedSampler)
+
+    def _call_key(self):
+        """What besides the shapes a call must share with the captured one to replay it (matches)."""
+        return self.cond_lambda
+
     def _run(self):
         if self.cond_lambda is not None:
             return self.model.sample_ddim(self._static_state, self._x, self._goal, self._sig, cond_lambda=self.cond_lambda)
@@ -73,7 +79,14 @@ class GraphedDDIM:
             self._eng = eng
             self._eng_key = next(k for k, e in model.inner_model._engines.items() if e is eng)
 
-    def matches(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas) -> bool:
+    def matches(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, key=None,
+                noise: Optional[torch.Tensor] = None) -> bool:
+        """Whether this graph replays the call: the same shapes and noise rows, and ``key`` equal to the captured call's
+        (_call_key: the guidance weight, or GraphedSampler's kind, parameters and evaluation count)."""
+        if key != self._call_key() or (noise is None) != (self._noise is None):
+            return False
+        if noise is not None and noise.shape != self._noise.shape:
+            return False
         if x_T.shape != self._x.shape or goal.shape != self._goal.shape or len(sigmas) != self._sig.numel():
             return False
         for k, v in self._static_state.items():
@@ -153,6 +166,9 @@ class GraphedSampler(GraphedDDIM):
         self._noise = None if noise is None else noise.detach().clone()
         super().__init__(model, state, x_T, goal, sigmas)
 
+    def _call_key(self):
+        return (self.kind, self.params, self.n_steps)
+
     def _run(self):
         return self.model.sample_native(self.kind, self._static_state, self._x, self._goal, self._sig, noise=self._noise,
                                         n_steps=self.n_steps, **self.params)
@@ -161,11 +177,3 @@ class GraphedSampler(GraphedDDIM):
         if (noise is None) != (self._noise is None) or (noise is not None and noise.shape != self._noise.shape):
             raise ValueError("GraphedSampler: the noise rows must have the captured shape")
         return ([], []) if noise is None else ([self._noise], [noise])
-
-    def matches_sampler(self, kind: str, params: dict, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
-                        noise: Optional[torch.Tensor], n_steps: Optional[int] = None) -> bool:
-        if kind != self.kind or params != self.params or n_steps != self.n_steps or (noise is None) != (self._noise is None):
-            return False
-        if noise is not None and noise.shape != self._noise.shape:
-            return False
-        return self.matches(state, x_T, goal, sigmas)

@@ -33,15 +33,6 @@ def _staged_backward() -> bool:
         return False
 
 
-def _lambda(cond_lambda):
-    """A sampler's guidance weight as the engine takes it: None for the unguided call (none given, or exactly 1 -- the
-    conditional model, which then runs the unguided native call and gives its bits)."""
-    if cond_lambda is None:
-        return None
-    lam = float(cond_lambda)
-    return None if lam == 1.0 else lam
-
-
 def _instantiate(cfg):
     """hydra.utils.instantiate when Hydra is installed, else the same thing for a flat kwargs mapping."""
     if isinstance(cfg, nn.Module):
@@ -213,12 +204,12 @@ class GCDenoiser(nn.Module):
         dpmpp_sde); s_noise and the step scales are applied inside.  ``params``: the sampler's keyword arguments (eta, s_churn,
         s_tmin, s_tmax, s_noise, r, order).  'dpm_fast': ``sigmas`` is [sigma_max, sigma_min] and ``n_steps`` the evaluation
         count.  ``cond_lambda``: classifier-free guidance weight (None or 1: the unguided call; include/mdt_hip.h
-        mdt_sample_guided)."""
+        mdt_sample_guided; _engine.guidance reads it)."""
         from ... import _lib
         im = self.inner_model
         out, ctx = self._engine(state=state).sample_native(_lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action,
                                                            im._goals(goal, False), sigmas, noise, n_steps=n_steps,
-                                                           cond_lambda=_lambda(cond_lambda))
+                                                           cond_lambda=cond_lambda)
         im.latent_encoder_emb = ctx
         return out
 
@@ -231,7 +222,7 @@ class GCDenoiser(nn.Module):
         im = self.inner_model
         out, ctx, info = self._engine(state=state).sample_dpm_adaptive(_lib.dpm_adaptive_params(**params), state, action,
                                                                        im._goals(goal, False), sigma_min, sigma_max,
-                                                                       cond_lambda=_lambda(cond_lambda))
+                                                                       cond_lambda=cond_lambda)
         im.latent_encoder_emb = ctx
         return out, info
 
@@ -241,6 +232,6 @@ class GCDenoiser(nn.Module):
         classifier-free guidance weight (None or 1: the unguided call; mdt_sample_ddim_guided)."""
         im = self.inner_model
         out, ctx = self._engine(state=state).sample_ddim(state, action, im._goals(goal, False), sigmas,
-                                                         cond_lambda=_lambda(cond_lambda))
+                                                         cond_lambda=cond_lambda)
         im.latent_encoder_emb = ctx
         return out

@@ -30,15 +30,28 @@ import os
 _RESYNC_EVERY = int(os.environ.get("MDT_HIP_PARAM_RESYNC", "0") or 0)
 
 
-def _guidance(cond_lambda) -> Optional[float]:
-    """The guidance weight of a sampler call as the C ABI takes it, or None for the unguided call (no weight given).  A weight
-    that is not a finite number raises ValueError, before anything is enqueued."""
+def guidance(cond_lambda=None, **other):
+    """The one reading of a guidance weight: ``guidance(**extra_args)`` for a sampler's ``extra_args``, ``guidance(cond_lambda)`` for
+    a weight.  Returns (native, lam).  native is False when there is more than the weight: the host loop runs then, and hands
+    the arguments to GCDenoiser.forward.  lam is the weight as the C ABI takes it, or None for the unguided call.  No weight and
+    exactly 1 both give None: the conditional model's unguided call gives the same bits.  A weight that is not a finite number
+    raises ValueError, before anything is enqueued."""
+    if other:
+        return False, None
     if cond_lambda is None:
-        return None
+        return True, None
     lam = float(cond_lambda)
     if not math.isfinite(lam):
         raise ValueError(f"cond_lambda must be finite, got {lam}")
-    return lam
+    return True, (None if lam == 1.0 else lam)
+
+
+# the C entry points of each sampler family as [device schedule][guided]
+_SAMPLER_ENTRIES = {
+    "ddim": (("mdt_sample_ddim", "mdt_sample_ddim_guided"), ("mdt_sample_ddim_dev", "mdt_sample_ddim_dev_guided")),
+    "plan": (("mdt_sample", "mdt_sample_guided"), ("mdt_sample_dev", "mdt_sample_dev_guided")),
+    "dpm_adaptive": (("mdt_sample_dpm_adaptive", "mdt_sample_dpm_adaptive_guided"),),
+}
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -74,6 +87,7 @@ class HipEngine:
         self.Te = int(self.sigma_in_context) + int(self.has_goal_token) + (cfg.n_obs_token if cfg.arch == 0 else 2) + \
             int(self.proprio)
         self.Ta, self.A, self.D = cfg.action_seq_len, cfg.action_dim, cfg.embed_dim
+        self._entries = {fam: tuple(tuple(getattr(self.lib, n) for n in pair) for pair in e) for fam, e in _SAMPLER_ENTRIES.items()}
 
     def __del__(self):
         try:
@@ -258,100 +272,61 @@ class HipEngine:
                                         _ptr(s), B, _ptr(out), _ptr(ctx), self._stream())
         return out, ctx
 
-    def sample_ddim(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, cond_lambda: Optional[float] = None):
-        """Fused sampler call.  ``sigmas`` may live on the host (gc_sampling's default) or on the model's device --
-        the agent builds its schedule there (mdtv_agent.py:660-667); a device schedule is consumed in place
-        (mdt_sample_ddim_dev): no copy to the host, no synchronisation.  ``cond_lambda`` (not None): classifier-free guidance,
-        mdt_sample_ddim_guided / mdt_sample_ddim_dev_guided."""
-        lam = _guidance(cond_lambda)
+    def _sample(self, family: str, state: dict, x_T: torch.Tensor, goal: torch.Tensor, cond_lambda, lead=(), sigmas=None,
+                n_steps: Optional[int] = None, noise: Optional[torch.Tensor] = None, rows: bool = False, tail=()):
+        """The steps every sampler call shares: the inputs, the outputs, the schedule and the entry point of ``family``
+        (_SAMPLER_ENTRIES).  The C arguments are the inputs, ``lead``, the schedule (if ``sigmas`` is given) and its count (one less
+        than the levels, or ``n_steps``), the noise rows (``rows``: None or (n_noise, B, Ta, A)), B, out, ctx, the weight of a
+        guided call, ``tail`` and the stream.  A device schedule is read in place (no copy to the host, no synchronisation)."""
+        lam = guidance(cond_lambda)[1]
         self.sync_params()
         tok, tok2, B = self._tokens(state)
         g, x_ = self._goal(goal, B), self._in(x_T, (B, self.Ta, self.A))
+        nz = None if noise is None else self._in(noise, (-1, B, self.Ta, self.A))
         out = torch.empty((B, self.Ta, self.A), device=self.device, dtype=torch.float32)
         ctx = torch.empty((B, self.Te, self.D), device=self.device, dtype=torch.float32)
-        if torch.is_tensor(sigmas) and sigmas.device.type == "cuda":
-            sig = self._in(sigmas.reshape(-1))
-            n = sig.numel() - 1
-            self._keep = sig  # the kernel that reads it is only enqueued: keep the (possibly converted) tensor alive
-            self.ctx_generation += 1
-            if lam is not None:
-                _lib.call(self.lib.mdt_sample_ddim_dev_guided, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
-                          _ptr(x_), _ptr(sig), n, B, _ptr(out), _ptr(ctx), lam, self._stream())
-                return out, ctx
-            _lib.call(self.lib.mdt_sample_ddim_dev, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
-                                                    _ptr(x_), _ptr(sig), n, B, _ptr(out), _ptr(ctx), self._stream())
-            return out, ctx
-        sig = [float(v) for v in (sigmas.detach().tolist() if torch.is_tensor(sigmas) else sigmas)]
-        n = len(sig) - 1
-        arr = (C.c_float * len(sig))(*sig)
+        dev = False
+        if sigmas is not None:
+            dev = torch.is_tensor(sigmas) and sigmas.device.type == "cuda"
+            if dev:
+                sig = self._in(sigmas.reshape(-1))
+                levels, arg = sig.numel(), sig.data_ptr()
+            else:
+                vals = [float(v) for v in (sigmas.detach().tolist() if torch.is_tensor(sigmas) else sigmas)]
+                levels = len(vals)
+                sig = arg = (C.c_float * levels)(*vals)
+            lead += (arg, levels - 1 if n_steps is None else int(n_steps))
+            self._keep = (sig, nz)  # the kernels that read them are only enqueued: keep the (possibly converted) inputs alive
+        if rows:
+            lead += (_ptr(nz), 0 if nz is None else nz.shape[0])
+        fn = self._entries[family][dev][lam is not None]
         self.ctx_generation += 1
-        if lam is not None:
-            _lib.call(self.lib.mdt_sample_ddim_guided, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
-                      _ptr(x_), arr, n, B, _ptr(out), _ptr(ctx), lam, self._stream())
-            return out, ctx
-        _lib.call(self.lib.mdt_sample_ddim, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
-                                            _ptr(x_), arr, n, B, _ptr(out), _ptr(ctx), self._stream())
+        _lib.call(fn, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_), *lead, B, _ptr(out), _ptr(ctx),
+                  *(() if lam is None else (lam,)), *tail, self._stream())
         return out, ctx
+
+    def sample_ddim(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, cond_lambda: Optional[float] = None):
+        """Fused sampler call.  ``sigmas`` may live on the host (gc_sampling's default) or on the model's device --
+        the agent builds its schedule there (mdtv_agent.py:660-667); a device schedule is consumed in place
+        (mdt_sample_ddim_dev): no copy to the host, no synchronisation.  ``cond_lambda`` (not None or 1): classifier-free
+        guidance, mdt_sample_ddim_guided / mdt_sample_ddim_dev_guided."""
+        return self._sample("ddim", state, x_T, goal, cond_lambda, sigmas=sigmas)
 
     def sample_native(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
                       noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cond_lambda: Optional[float] = None):
         """One call of another sampler (mdt_sample / mdt_sample_dev): ``kind`` an mdt_sampler_kind, ``params`` an
         _lib.SamplerParams, ``noise`` None or (n_noise, B, Ta, A) in the Python loop's draw order, ``n_steps`` None (one less
         than the levels) or dpm_fast's evaluation count.  Like sample_ddim, a device schedule is read in place (no copy, no
-        synchronisation).  ``cond_lambda`` (not None): classifier-free guidance (mdt_sample_guided / mdt_sample_dev_guided)."""
-        lam = _guidance(cond_lambda)
-        self.sync_params()
-        tok, tok2, B = self._tokens(state)
-        g, x_ = self._goal(goal, B), self._in(x_T, (B, self.Ta, self.A))
-        nz = None if noise is None else self._in(noise, (-1, B, self.Ta, self.A))
-        n_noise = 0 if nz is None else nz.shape[0]
-        out = torch.empty((B, self.Ta, self.A), device=self.device, dtype=torch.float32)
-        ctx = torch.empty((B, self.Te, self.D), device=self.device, dtype=torch.float32)
-        if torch.is_tensor(sigmas) and sigmas.device.type == "cuda":
-            sig = self._in(sigmas.reshape(-1))
-            n = sig.numel() - 1 if n_steps is None else int(n_steps)
-            self._keep = (sig, nz)  # the kernels that read them are only enqueued: keep the tensors alive
-            self.ctx_generation += 1
-            if lam is not None:
-                _lib.call(self.lib.mdt_sample_dev_guided, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
-                          _ptr(x_), int(kind), C.byref(params), _ptr(sig), n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), lam,
-                          self._stream())
-                return out, ctx
-            _lib.call(self.lib.mdt_sample_dev, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_),
-                      int(kind), C.byref(params), _ptr(sig), n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), self._stream())
-            return out, ctx
-        sig = [float(v) for v in (sigmas.detach().tolist() if torch.is_tensor(sigmas) else sigmas)]
-        n = len(sig) - 1 if n_steps is None else int(n_steps)
-        arr = (C.c_float * len(sig))(*sig)
-        self._keep = nz
-        self.ctx_generation += 1
-        if lam is not None:
-            _lib.call(self.lib.mdt_sample_guided, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_),
-                      int(kind), C.byref(params), arr, n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), lam, self._stream())
-            return out, ctx
-        _lib.call(self.lib.mdt_sample, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_), int(kind),
-                  C.byref(params), arr, n, _ptr(nz), n_noise, B, _ptr(out), _ptr(ctx), self._stream())
-        return out, ctx
+        synchronisation).  ``cond_lambda`` (not None or 1): classifier-free guidance (mdt_sample_guided / mdt_sample_dev_guided)."""
+        return self._sample("plan", state, x_T, goal, cond_lambda, (int(kind), C.byref(params)), sigmas, n_steps, noise, rows=True)
 
     def sample_dpm_adaptive(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigma_min: float, sigma_max: float,
                             cond_lambda: Optional[float] = None):
         """mdt_sample_dpm_adaptive (eta = 0): ``params`` an _lib.DpmAdaptiveParams.  Blocking: the call reads the step error
-        back every step.  Returns (out, ctx, info dict).  ``cond_lambda`` (not None): mdt_sample_dpm_adaptive_guided."""
-        lam = _guidance(cond_lambda)
-        self.sync_params()
-        tok, tok2, B = self._tokens(state)
-        g, x_ = self._goal(goal, B), self._in(x_T, (B, self.Ta, self.A))
-        out = torch.empty((B, self.Ta, self.A), device=self.device, dtype=torch.float32)
-        ctx = torch.empty((B, self.Te, self.D), device=self.device, dtype=torch.float32)
+        back every step.  Returns (out, ctx, info dict).  ``cond_lambda`` (not None or 1): mdt_sample_dpm_adaptive_guided."""
         info = _lib.DpmAdaptiveInfo()
-        self.ctx_generation += 1
-        if lam is not None:
-            _lib.call(self.lib.mdt_sample_dpm_adaptive_guided, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state),
-                      _ptr(x_), float(sigma_min), float(sigma_max), C.byref(params), B, _ptr(out), _ptr(ctx), lam, C.byref(info),
-                      self._stream())
-            return out, ctx, {k: int(getattr(info, k)) for k in ("steps", "nfe", "n_accept", "n_reject")}
-        _lib.call(self.lib.mdt_sample_dpm_adaptive, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_),
-                  float(sigma_min), float(sigma_max), C.byref(params), B, _ptr(out), _ptr(ctx), C.byref(info), self._stream())
+        out, ctx = self._sample("dpm_adaptive", state, x_T, goal, cond_lambda, (float(sigma_min), float(sigma_max), C.byref(params)),
+                                tail=(C.byref(info),))
         return out, ctx, {k: int(getattr(info, k)) for k in ("steps", "nfe", "n_accept", "n_reject")}
 
     def loss_fwd(self, state: dict, action: torch.Tensor, goal: torch.Tensor, noise: torch.Tensor, sigma: torch.Tensor):
