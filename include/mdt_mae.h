@@ -11,7 +11,8 @@
  *
  * The host mirror (mdt_policy_amd/models/img_generation/masked_transformer_decoder.py) runs every Linear on the fp32-MFMA
  * GEMM (mdt_op_gemm forward, mdt_op_linear_bwd backward) and the row / token kernels below; gathers, residual adds and
- * the loss are PyTorch-ROCm glue.  fp32, row-major, device pointers 16-byte aligned.
+ * the loss are PyTorch-ROCm glue.  fp32, row-major, device pointers 16-byte aligned.  Its self-attention runs on
+ * mdt_op_attn_mid_* up to 128 tokens (the shipped 102) and on mdt_op_attn_long_* above that, up to 4096.
  */
 #ifndef MDT_MAE_H
 #define MDT_MAE_H
@@ -72,6 +73,21 @@ mdt_status mdt_op_attn_mid_fwd(const float *qkv, int64_t ld_qkv, float *out, int
 mdt_status mdt_op_attn_mid_bwd(const float *qkv, int64_t ld_qkv, const float *out, int64_t ld_out, const float *d_out,
                                int64_t ld_do, float *d_qkv, int64_t ld_dqkv, int64_t B, int32_t H, int32_t hd, int32_t T,
                                float scale, void *stream);
+
+/* The same attention over 1 <= T <= 4096 tokens, flash-style (the decoder above 112 x 112 / 16: 132 tokens at 128 / 16, 396 at
+ * 224 / 16 or 112 / 8, 1572 at 224 / 8).  Same qkv / out layout and head dims as mdt_op_attn_mid_*; row strides multiples of
+ * 4, pointers 16-byte aligned.  No T x T matrix exists: per (sample, head, 64-query block) the keys are streamed through LDS in
+ * stages of 64 with an online softmax; the forward also writes lse (B, H, T) fp32, the natural log-sum-exp of each row of
+ * scores (scale * q k^T), which the backward needs.  The backward recomputes the probabilities from qkv and lse; dK / dV and
+ * dQ are each written by the one workgroup that owns them (no atomics: bitwise reproducible).  scratch:
+ * mdt_op_attn_long_bwd_scratch(B, H, T) floats.  T > 4096, another head dim, misaligned pointers or odd strides: non-zero
+ * status, nothing launched.  The caller's stream, no host synchronisation, no allocation. */
+mdt_status mdt_op_attn_long_fwd(const float *qkv, int64_t ld_qkv, float *out, int64_t ld_out, float *lse, int64_t B, int32_t H,
+                                int32_t hd, int32_t T, float scale, void *stream);
+int64_t mdt_op_attn_long_bwd_scratch(int64_t B, int32_t H, int32_t T);
+mdt_status mdt_op_attn_long_bwd(const float *qkv, int64_t ld_qkv, const float *out, int64_t ld_out, const float *lse,
+                                const float *d_out, int64_t ld_do, float *d_qkv, int64_t ld_dqkv, int64_t B, int32_t H,
+                                int32_t hd, int32_t T, float scale, float *scratch, void *stream);
 
 /* compute_loss of the decoder (masked_transformer_decoder.py:228-262, symmetric mask) in one pass each way:
  *   loss = 1/2 sum_{x in {0,1}} [ sum_{b,n} mask[b][n] * mean_e (rec[b][x][n][e] - target[b][x][n][e])^2 ] / sum(mask)

@@ -345,6 +345,9 @@ SYMBOLS = [
     ("mdt_op_swiglu_bwd", _I32, [_VP, _VP, _VP, _I64, _I32, _VP]),
     ("mdt_op_attn_mid_fwd", _I32, [_VP, _I64, _VP, _I64, _I64, _I32, _I32, _I32, _F, _VP]),
     ("mdt_op_attn_mid_bwd", _I32, [_VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _I64, _I32, _I32, _I32, _F, _VP]),
+    ("mdt_op_attn_long_fwd", _I32, [_VP, _I64, _VP, _I64, _VP, _I64, _I32, _I32, _I32, _F, _VP]),
+    ("mdt_op_attn_long_bwd_scratch", _I64, [_I64, _I32, _I32]),
+    ("mdt_op_attn_long_bwd", _I32, [_VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _I64, _I64, _I32, _I32, _I32, _F, _VP, _VP]),
     ("mdt_op_patch_mse_fwd", _I32, [_VP, _VP, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _I32, _I32, _VP]),
     ("mdt_op_patch_mse_bwd", _I32, [_VP, _VP, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _I32, _I32, _VP]),
     ("mdt_op_infonce_scratch", _I64, [_I64, _I64]),

@@ -1,5 +1,6 @@
 // mdt_mae.hip -- op-level kernels of the masked generative foresight head (include/mdt_mae.h): unmasked multi-head
-// self-attention over ~100 tokens with its backward, and the exported RMSNorm / SwishGLU row ops.
+// self-attention over ~100 tokens with its backward, its flash-style form for 129 .. 4096 tokens (further down), and the
+// exported RMSNorm / SwishGLU row ops.
 //
 // The attention of the shipped decoder is 102 tokens x 8 heads of 24 (masked_transformer_decoder.py:68-121 builds
 // voltron Blocks of d = 192).  One workgroup of 8 waves per (sample, head) keeps q / k / v (and dO, O) and the T x T scores
@@ -1039,6 +1040,498 @@ extern "C" mdt_status mdt_op_attn_mid_bwd(const float* qkv, int64_t ld_qkv, cons
         case 48: LAUNCH(launch_bwd<48>(qkv, ld_qkv, out, ld_out, d_out, ld_do, d_qkv, ld_dqkv, B, H, T, scale, s)); break;
         case 64: LAUNCH(launch_bwd<64>(qkv, ld_qkv, out, ld_out, d_out, ld_do, d_qkv, ld_dqkv, B, H, T, scale, s)); break;
         default: return mdt_fail(MDT_ERR_UNSUPPORTED, "mdt_op_attn_mid_bwd: head dim %d (supported 16/24/32/48/64)", hd);
+    }
+    return MDT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Long self-attention (129 .. 4096 tokens: the decoder at resolutions above 112 pixels or patches below 16), flash-style.
+// Nothing of size T x T exists anywhere: the scores of a 16-query tile against one 64-key stage live in MFMA accumulators.
+//   forward   one workgroup of 4 waves per (sample, head, 64-query block), a wave per 16-query tile; the workgroup walks the
+//             keys in stages of 64 (K rows and V transposed in LDS, two buffers: the next stage's rows are fetched into
+//             registers before the current stage's products and written to the other buffer after them, one barrier per
+//             stage).  Scores are computed TRANSPOSED as in k_attn_mid_fwd2 (acc[tj][r] = S[query m][key 16 tj + 4 g + r]),
+//             so the probabilities are the A operand of P V without leaving the registers; online softmax with a running
+//             max and a lane-partial running sum per query; writes O and the row's natural log-sum-exp.
+//   backward  delta_i = dO_i . O_i (scratch), then two passes that each OWN their outputs (no atomics: bit-reproducible):
+//             dK / dV by key blocks (a wave per 16-key tile, keys on the lane, the queries streamed through LDS in stages of
+//             64) and dQ by query blocks (a wave per 16-query tile, the keys streamed).  P is recomputed from Q, K and the LSE.
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr int LONG_TMAX = 4096, LB = 64, LNT = 256;   // tokens; rows per LDS stage and per workgroup (4 tiles of 16); threads
+constexpr float LOG2E = 1.44269504088896341f, LN2 = 0.693147180559945309f;
+
+template <int HD>
+struct LongCfg {
+    static constexpr int ST = HD + 4, H4 = HD / 4, N4 = LB * H4, U = (N4 + LNT - 1) / LNT, C16 = HD / 16, REM8 = (HD % 16) == 8,
+                         NC = (HD + 15) / 16, HDP = 16 * NC, VS = LB + 4;
+};
+
+// rows r0 .. r0 + LB - 1 of a (T, HD) head slice -> registers, U 16-byte pieces per thread (rows >= T re-read row T - 1)
+template <int HD>
+__device__ __forceinline__ void long_fetch(f32x4 (&v)[LongCfg<HD>::U], const float* src, int64_t ld, int r0, int T, int tid) {
+    using C_ = LongCfg<HD>;
+#pragma unroll
+    for (int u = 0; u < C_::U; ++u) {
+        const int i = min(tid + u * LNT, C_::N4 - 1), t = i / C_::H4, c = i - t * C_::H4;
+        v[u] = ldg4(src + (int64_t)min(r0 + t, T - 1) * ld + 4 * c);
+    }
+}
+// ... registers -> LDS: rows [LB][ST], or (TRANS) the slice transposed [HD][VS]; rows >= T are written as zeros
+template <int HD, bool TRANS>
+__device__ __forceinline__ void long_commit(const f32x4 (&v)[LongCfg<HD>::U], float* dst, int r0, int T, int tid) {
+    using C_ = LongCfg<HD>;
+#pragma unroll
+    for (int u = 0; u < C_::U; ++u) {
+        const int i = tid + u * LNT, t = i / C_::H4, c = i - t * C_::H4;
+        if (i < C_::N4) {
+            const f32x4 x = r0 + t < T ? v[u] : (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (TRANS) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dst[(4 * c + e) * C_::VS + t] = x[e];
+            } else {
+                *(f32x4*)(dst + t * C_::ST + 4 * c) = x;
+            }
+        }
+    }
+}
+
+// a 16-row tile a wave keeps in registers for the whole kernel, as the MFMA's lane-side operand: lane (row m, d = 16 c + 4 g + e)
+// (and the 8-wide remainder of hd = 24 as two pairs, d = 16 C16 + 2 g + e)
+template <int HD>
+struct LongFrag {
+    f32x4 v[LongCfg<HD>::C16];
+    f32x2 r2;
+    __device__ __forceinline__ void load(const float* row, int g, float s) {   // row m of the tile (global or LDS), scaled by s
+        using C_ = LongCfg<HD>;
+#pragma unroll
+        for (int c = 0; c < C_::C16; ++c) v[c] = *(const f32x4*)(row + 16 * c + 4 * g) * s;
+        r2 = C_::REM8 ? *(const f32x2*)(row + 16 * C_::C16 + 2 * g) * s : (f32x2){0.f, 0.f};
+    }
+};
+// acc[r] = sum_d A[4 g + r][d] F[m][d]  (A: LDS rows, stride any, `ar` at row m; F: the register fragment) -- the fragment on the
+// lane (B operand)
+template <int HD>
+__device__ __forceinline__ f32x4 long_dot_rows_frag(const float* ar, const LongFrag<HD>& f, int g) {
+    using C_ = LongCfg<HD>;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < C_::C16; ++c) {
+        const f32x4 a = *(const f32x4*)(ar + 16 * c + 4 * g);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], f.v[c][e], acc, 0, 0, 0);
+    }
+    if (C_::REM8) {
+        const f32x2 a = *(const f32x2*)(ar + 16 * C_::C16 + 2 * g);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, f.r2.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, f.r2.y, acc, 0, 0, 0);
+    }
+    return acc;
+}
+// out[c] += sum over the 16 reduction rows i of  w[e of row 4 g + e] * X[16 t0 + 4 g + e][16 c + m]  -- an accumulator of
+// reduction index 4 g + e (lane m = output row) times 16 LDS rows of X (stride ST) read by columns: dV = P^T dO, dK = dS^T Q,
+// dQ = dS K.  Columns >= HD read column HD - 1 (their outputs are never stored).
+template <int HD>
+__device__ __forceinline__ void long_acc_cols(const f32x4& w, const float* xrows, int g, int m, f32x4 (&out)[LongCfg<HD>::NC]) {
+    using C_ = LongCfg<HD>;
+#pragma unroll
+    for (int c = 0; c < C_::NC; ++c) {
+        const float* xp = xrows + (4 * g) * C_::ST + min(16 * c + m, HD - 1);
+        const f32x4 x = {xp[0], xp[C_::ST], xp[2 * C_::ST], xp[3 * C_::ST]};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[e], x[e], out[c], 0, 0, 0);
+    }
+}
+
+// (sample, head, block) of a flattened grid, block fastest: neighbouring workgroups share a head's rows in L2
+struct LongIdx {
+    int64_t b;
+    int h, blk;
+    __device__ __forceinline__ LongIdx(int H, int nb) {
+        const int64_t x = blockIdx.x, bh = x / nb;
+        blk = (int)(x - bh * nb);
+        h = (int)(bh % H);
+        b = bh / H;
+    }
+};
+
+template <int HD>
+__global__ __launch_bounds__(LNT) void k_attn_long_fwd(const float* __restrict__ qkv, int64_t ld, float* __restrict__ out, int64_t ldo,
+                                                     float* __restrict__ lse, int H, int T, float scale) {
+    using C_ = LongCfg<HD>;
+    constexpr int ST = C_::ST, VS = C_::VS, NC = C_::NC, U = C_::U, BUF = LB * ST + C_::HDP * VS;   // K rows | V transposed
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, g = lane >> 4, D = H * HD;
+    const int nb = (T + LB - 1) / LB;
+    const LongIdx ix(H, nb);
+    const float* base = qkv + ix.b * T * ld + ix.h * HD;
+    const float sl2 = scale * LOG2E;   // softmax in base 2
+    const int ti = ix.blk * 4 + wave;  // this wave's query tile
+    const bool active = 16 * ti < T;
+    LongFrag<HD> qf;                   // query m as the column operand, scaled by scale * log2 e
+    qf.load(base + (int64_t)min(16 * ti + m, T - 1) * ld, g, sl2);
+    f32x4 rk[U], rv[U];
+    long_fetch<HD>(rk, base + D, ld, 0, T, tid);
+    long_fetch<HD>(rv, base + 2 * D, ld, 0, T, tid);
+    long_commit<HD, false>(rk, lds, 0, T, tid);
+    long_commit<HD, true>(rv, lds + LB * ST, 0, T, tid);
+    __syncthreads();
+    float mrun = -INFINITY, lpart = 0.f;   // running max of query m (every lane of column m); this lane's share of the sum
+    f32x4 oacc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) oacc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < nb; ++j) {
+        const int k0 = j * LB;
+        const bool next = j + 1 < nb;
+        if (next) {
+            long_fetch<HD>(rk, base + D, ld, k0 + LB, T, tid);
+            long_fetch<HD>(rv, base + 2 * D, ld, k0 + LB, T, tid);
+        }
+        const float* ks = lds + (j & 1) * BUF;
+        const float* vt = ks + LB * ST;
+        if (active) {
+            f32x4 acc[4];
+#pragma unroll
+            for (int tj = 0; tj < 4; ++tj) acc[tj] = long_dot_rows_frag<HD>(ks + (16 * tj + m) * ST, qf, g);   // keys on the register axis
+            float bm = -INFINITY;
+            const bool tail = k0 + LB > T;
+#pragma unroll
+            for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (tail && k0 + 16 * tj + 4 * g + r >= T) acc[tj][r] = -INFINITY;
+                    bm = fmaxf(bm, acc[tj][r]);
+                }
+            const float mnew = fmaxf(mrun, xrow_max(bm));   // key k0 is live: finite
+            const float alpha = __builtin_amdgcn_exp2f(mrun - mnew);   // 0 on the first stage
+            mrun = mnew;
+            float s = 0.f;
+#pragma unroll
+            for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    acc[tj][r] = __builtin_amdgcn_exp2f(acc[tj][r] - mnew);
+                    s += acc[tj][r];
+                }
+            lpart = lpart * alpha + s;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float ar = __shfl(alpha, 4 * g + r, 64);   // the factor of output row 4 g + r lives in column 4 g + r
+#pragma unroll
+                for (int c = 0; c < NC; ++c) oacc[c][r] *= ar;
+            }
+#pragma unroll
+            for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    const f32x4 vv = *(const f32x4*)(vt + (16 * c + m) * VS + 16 * tj + 4 * g);   // lane = (d, keys 4 g .. + 3)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) oacc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(acc[tj][e], vv[e], oacc[c], 0, 0, 0);
+                }
+        }
+        if (next) {
+            float* nk = lds + ((j + 1) & 1) * BUF;
+            long_commit<HD, false>(rk, nk, k0 + LB, T, tid);
+            long_commit<HD, true>(rv, nk + LB * ST, k0 + LB, T, tid);
+        }
+        __syncthreads();
+    }
+    if (active) {
+        const float l = xrow_sum(lpart), inv = 1.0f / l;
+        float* o = out + ix.b * T * ldo + ix.h * HD;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float ir = __shfl(inv, 4 * g + r, 64);
+            const int q = 16 * ti + 4 * g + r;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int d = 16 * c + m;
+                if (d < HD && q < T) o[(int64_t)q * ldo + d] = oacc[c][r] * ir;
+            }
+        }
+        const int q = 16 * ti + m;
+        if (g == 0 && q < T) lse[(ix.b * H + ix.h) * T + q] = (mrun + __log2f(l)) * LN2;
+    }
+}
+
+// delta[(b, h), t] = dO . O over the head's hd columns: one thread per (row, head)
+template <int HD>
+__global__ __launch_bounds__(256) void k_attn_long_delta(const float* __restrict__ d_out, int64_t ldd, const float* __restrict__ o,
+                                                       int64_t ldo, float* __restrict__ delta, int64_t rows, int H, int T) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * H) return;
+    const int64_t row = i / H, b = row / T;
+    const int h = (int)(i - row * H), t = (int)(row - b * T);
+    const float* a = d_out + row * ldd + h * HD;
+    const float* c = o + row * ldo + h * HD;
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < HD / 4; ++k) {
+        const f32x4 x = ldg4(a + 4 * k), y = ldg4(c + 4 * k);
+        acc += (x.x * y.x + x.y * y.y) + (x.z * y.z + x.w * y.w);
+    }
+    delta[(b * H + h) * T + t] = acc;
+}
+
+// dK, dV: a wave per 16-key tile (its K and V rows in registers); the workgroup streams Q, dO, the LSE and delta of all queries
+// through LDS in stages of 64 (two buffers, as the forward).  With the queries on the register axis and the keys on the lane,
+// S = Q K^T and dP = dO V^T come out as acc[r] = X[query 4 g + r][key m]: the A operand of dV = P^T dO and dK = dS^T Q as they
+// are.  Query rows >= T are zero with LSE +inf: P = 0, dS = 0.
+template <int HD>
+__global__ __launch_bounds__(LNT) void k_attn_long_bwd_kv(const float* __restrict__ qkv, int64_t ld, const float* __restrict__ d_out,
+                                                        int64_t ldd, const float* __restrict__ lse, const float* __restrict__ delta,
+                                                        float* __restrict__ d_qkv, int64_t ldg, int H, int T, float scale) {
+    using C_ = LongCfg<HD>;
+    constexpr int ST = C_::ST, NC = C_::NC, U = C_::U, BUF = 2 * LB * ST + 2 * LB;   // Q rows | dO rows | LSE * log2 e | delta
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, g = lane >> 4, D = H * HD;
+    const int nb = (T + LB - 1) / LB;
+    const LongIdx ix(H, nb);
+    const float* base = qkv + ix.b * T * ld + ix.h * HD;
+    const float* dob = d_out + ix.b * T * ldd + ix.h * HD;
+    const int64_t bh = ix.b * H + ix.h;
+    const float sl2 = scale * LOG2E;
+    const int kt = ix.blk * 4 + wave;   // this wave's key tile
+    const bool active = 16 * kt < T;
+    LongFrag<HD> kf, vf;
+    {
+        const int64_t kr = min(16 * kt + m, T - 1);
+        kf.load(base + D + kr * ld, g, 1.f);
+        vf.load(base + 2 * D + kr * ld, g, 1.f);
+    }
+    f32x4 rq[U], rd[U];
+    float rl = 0.f, rdl = 0.f;
+    auto fetch = [&](int r0) {
+        long_fetch<HD>(rq, base, ld, r0, T, tid);
+        long_fetch<HD>(rd, dob, ldd, r0, T, tid);
+        if (tid < LB) {
+            const int q = min(r0 + tid, T - 1);
+            rl = lse[bh * T + q];
+            rdl = delta[bh * T + q];
+        }
+    };
+    auto commit = [&](float* buf, int r0) {
+        long_commit<HD, false>(rq, buf, r0, T, tid);
+        long_commit<HD, false>(rd, buf + LB * ST, r0, T, tid);
+        if (tid < LB) {
+            const bool live = r0 + tid < T;
+            buf[2 * LB * ST + tid] = live ? rl * LOG2E : INFINITY;
+            buf[2 * LB * ST + LB + tid] = live ? rdl : 0.f;
+        }
+    };
+    fetch(0);
+    commit(lds, 0);
+    __syncthreads();
+    f32x4 dK[NC], dV[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { dK[c] = (f32x4){0.f, 0.f, 0.f, 0.f}; dV[c] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+    for (int j = 0; j < nb; ++j) {
+        const bool next = j + 1 < nb;
+        if (next) fetch((j + 1) * LB);
+        const float* qs = lds + (j & 1) * BUF;
+        const float* dos = qs + LB * ST;
+        const float* l2 = dos + LB * ST;
+        const float* dl = l2 + LB;
+        if (active) {
+#pragma unroll
+            for (int tq = 0; tq < 4; ++tq) {
+                const f32x4 s = long_dot_rows_frag<HD>(qs + (16 * tq + m) * ST, kf, g);    // S[query 4 g + r][key m]
+                const f32x4 dp = long_dot_rows_frag<HD>(dos + (16 * tq + m) * ST, vf, g);  // dP, same layout
+                const f32x4 lq = *(const f32x4*)(l2 + 16 * tq + 4 * g), dq = *(const f32x4*)(dl + 16 * tq + 4 * g);
+                f32x4 p, ds;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    p[r] = __builtin_amdgcn_exp2f(fmaf(s[r], sl2, -lq[r]));
+                    ds[r] = p[r] * (dp[r] - dq[r]) * scale;
+                }
+                long_acc_cols<HD>(p, dos + 16 * tq * ST, g, m, dV);    // dV += P^T dO
+                long_acc_cols<HD>(ds, qs + 16 * tq * ST, g, m, dK);    // dK += dS^T Q
+            }
+        }
+        if (next) commit(lds + ((j + 1) & 1) * BUF, (j + 1) * LB);
+        __syncthreads();
+    }
+    if (active) {
+        float* gk = d_qkv + ix.b * T * ldg + D + ix.h * HD;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = 16 * kt + 4 * g + r;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int d = 16 * c + m;
+                if (d < HD && k < T) {
+                    gk[(int64_t)k * ldg + d] = dK[c][r];
+                    gk[(int64_t)k * ldg + D + d] = dV[c][r];
+                }
+            }
+        }
+    }
+}
+
+// dQ: a wave per 16-query tile (its Q, dO, LSE and delta in registers), the keys streamed through LDS in stages of 64.  Scores
+// transposed as in the forward, acc[r] = X[query m][key 4 g + r]: dS is the A operand of dQ = dS K as it is.
+template <int HD>
+__global__ __launch_bounds__(LNT) void k_attn_long_bwd_q(const float* __restrict__ qkv, int64_t ld, const float* __restrict__ d_out,
+                                                       int64_t ldd, const float* __restrict__ lse, const float* __restrict__ delta,
+                                                       float* __restrict__ d_qkv, int64_t ldg, int H, int T, float scale) {
+    using C_ = LongCfg<HD>;
+    constexpr int ST = C_::ST, NC = C_::NC, U = C_::U, BUF = 2 * LB * ST;   // K rows | V rows
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, g = lane >> 4, D = H * HD;
+    const int nb = (T + LB - 1) / LB;
+    const LongIdx ix(H, nb);
+    const float* base = qkv + ix.b * T * ld + ix.h * HD;
+    const int64_t bh = ix.b * H + ix.h;
+    const float sl2 = scale * LOG2E;
+    const int ti = ix.blk * 4 + wave;
+    const bool active = 16 * ti < T;
+    LongFrag<HD> qf, df;
+    const int qr = min(16 * ti + m, T - 1);
+    qf.load(base + (int64_t)qr * ld, g, sl2);
+    df.load(d_out + ix.b * T * ldd + ix.h * HD + (int64_t)qr * ldd, g, 1.f);
+    const float l2 = lse[bh * T + qr] * LOG2E, dlt = delta[bh * T + qr];
+    f32x4 rk[U], rv[U];
+    long_fetch<HD>(rk, base + D, ld, 0, T, tid);
+    long_fetch<HD>(rv, base + 2 * D, ld, 0, T, tid);
+    long_commit<HD, false>(rk, lds, 0, T, tid);
+    long_commit<HD, false>(rv, lds + LB * ST, 0, T, tid);
+    __syncthreads();
+    f32x4 dQ[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) dQ[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < nb; ++j) {
+        const int k0 = j * LB;
+        const bool next = j + 1 < nb;
+        if (next) {
+            long_fetch<HD>(rk, base + D, ld, k0 + LB, T, tid);
+            long_fetch<HD>(rv, base + 2 * D, ld, k0 + LB, T, tid);
+        }
+        const float* ks = lds + (j & 1) * BUF;
+        const float* vs = ks + LB * ST;
+        if (active) {
+            const bool tail = k0 + LB > T;
+#pragma unroll
+            for (int tj = 0; tj < 4; ++tj) {
+                const f32x4 s = long_dot_rows_frag<HD>(ks + (16 * tj + m) * ST, qf, g);   // S[query m][key 4 g + r], base 2
+                const f32x4 dp = long_dot_rows_frag<HD>(vs + (16 * tj + m) * ST, df, g);
+                f32x4 ds;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const bool live = !tail || k0 + 16 * tj + 4 * g + r < T;
+                    const float p = live ? __builtin_amdgcn_exp2f(s[r] - l2) : 0.f;
+                    ds[r] = p * (dp[r] - dlt) * scale;
+                }
+                long_acc_cols<HD>(ds, ks + 16 * tj * ST, g, m, dQ);   // dQ += dS K
+            }
+        }
+        if (next) {
+            float* nk = lds + ((j + 1) & 1) * BUF;
+            long_commit<HD, false>(rk, nk, k0 + LB, T, tid);
+            long_commit<HD, false>(rv, nk + LB * ST, k0 + LB, T, tid);
+        }
+        __syncthreads();
+    }
+    if (active) {
+        float* gq = d_qkv + ix.b * T * ldg + ix.h * HD;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int q = 16 * ti + 4 * g + r;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const int d = 16 * c + m;
+                if (d < HD && q < T) gq[(int64_t)q * ldg + d] = dQ[c][r];
+            }
+        }
+    }
+}
+
+template <int HD>
+size_t long_lds(int which) {   // 0 forward, 1 dK / dV, 2 dQ: two stage buffers each
+    using C_ = LongCfg<HD>;
+    const size_t buf = which == 0 ? LB * C_::ST + C_::HDP * C_::VS : which == 1 ? 2 * LB * C_::ST + 2 * LB : 2 * LB * C_::ST;
+    return 2 * buf * sizeof(float);
+}
+
+template <typename K>
+hipError_t long_launch_setup(K kern, size_t lds) {
+    return lds > 64 * 1024 ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+}
+
+template <int HD>
+hipError_t launch_long_fwd(const float* qkv, int64_t ld, float* out, int64_t ldo, float* lse, int64_t B, int H, int T, float scale,
+                           hipStream_t s) {
+    const size_t lds = long_lds<HD>(0);
+    hipError_t e = long_launch_setup(k_attn_long_fwd<HD>, lds);
+    if (e != hipSuccess) return e;
+    const int64_t nwg = B * H * ((T + LB - 1) / LB);
+    hipLaunchKernelGGL((k_attn_long_fwd<HD>), dim3((unsigned)nwg), dim3(LNT), lds, s, qkv, ld, out, ldo, lse, H, T, scale);
+    return hipGetLastError();
+}
+
+template <int HD>
+hipError_t launch_long_bwd(const float* qkv, int64_t ld, const float* o, int64_t ldo, const float* lse, const float* d_out, int64_t ldd,
+                           float* d_qkv, int64_t ldg, int64_t B, int H, int T, float scale, float* delta, hipStream_t s) {
+    const int64_t rows = B * T, nwg = B * H * ((T + LB - 1) / LB);
+    hipLaunchKernelGGL((k_attn_long_delta<HD>), dim3((unsigned)((rows * H + 255) / 256)), dim3(256), 0, s, d_out, ldd, o, ldo, delta,
+                       rows, H, T);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const size_t l1 = long_lds<HD>(1), l2 = long_lds<HD>(2);
+    if ((e = long_launch_setup(k_attn_long_bwd_kv<HD>, l1)) != hipSuccess) return e;
+    if ((e = long_launch_setup(k_attn_long_bwd_q<HD>, l2)) != hipSuccess) return e;
+    hipLaunchKernelGGL((k_attn_long_bwd_kv<HD>), dim3((unsigned)nwg), dim3(LNT), l1, s, qkv, ld, d_out, ldd, lse, delta, d_qkv, ldg, H, T,
+                       scale);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL((k_attn_long_bwd_q<HD>), dim3((unsigned)nwg), dim3(LNT), l2, s, qkv, ld, d_out, ldd, lse, delta, d_qkv, ldg, H, T,
+                       scale);
+    return hipGetLastError();
+}
+
+// the checks both directions share; 0 = fine
+mdt_status long_check(const char* what, int64_t B, int32_t H, int32_t hd, int32_t T, bool ptrs_ok, bool aligned_ok) {
+    if (!ptrs_ok || B < 1 || H < 1 || T < 1) return mdt_fail(MDT_ERR_INVALID_ARG, "%s: bad argument", what);
+    if (T > LONG_TMAX) return mdt_fail(MDT_ERR_UNSUPPORTED, "%s: T must be <= %d", what, LONG_TMAX);
+    if (hd != 16 && hd != 24 && hd != 32 && hd != 48 && hd != 64)
+        return mdt_fail(MDT_ERR_UNSUPPORTED, "%s: head dim %d (supported 16/24/32/48/64)", what, hd);
+    if (!aligned_ok) return mdt_fail(MDT_ERR_INVALID_ARG, "%s: pointers 16-byte aligned, strides multiples of 4", what);
+    if (B * H * ((T + LB - 1) / LB) > 0x7fffffffll)
+        return mdt_fail(MDT_ERR_UNSUPPORTED, "%s: batch too large", what);
+    return MDT_OK;
+}
+}  // namespace
+
+extern "C" mdt_status mdt_op_attn_long_fwd(const float* qkv, int64_t ld_qkv, float* out, int64_t ld_out, float* lse, int64_t B, int32_t H,
+                                           int32_t hd, int32_t T, float scale, void* stream) {
+    const mdt_status st = long_check("mdt_op_attn_long_fwd", B, H, hd, T, qkv && out && lse,
+                                     aligned16(qkv) && aligned16(out) && ld_qkv % 4 == 0 && ld_out % 4 == 0);
+    if (st != MDT_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    switch (hd) {
+        case 16: LAUNCH(launch_long_fwd<16>(qkv, ld_qkv, out, ld_out, lse, B, H, T, scale, s)); break;
+        case 24: LAUNCH(launch_long_fwd<24>(qkv, ld_qkv, out, ld_out, lse, B, H, T, scale, s)); break;
+        case 32: LAUNCH(launch_long_fwd<32>(qkv, ld_qkv, out, ld_out, lse, B, H, T, scale, s)); break;
+        case 48: LAUNCH(launch_long_fwd<48>(qkv, ld_qkv, out, ld_out, lse, B, H, T, scale, s)); break;
+        case 64: LAUNCH(launch_long_fwd<64>(qkv, ld_qkv, out, ld_out, lse, B, H, T, scale, s)); break;
+    }
+    return MDT_OK;
+}
+
+extern "C" int64_t mdt_op_attn_long_bwd_scratch(int64_t B, int32_t H, int32_t T) { return B * H * (int64_t)T; }
+
+extern "C" mdt_status mdt_op_attn_long_bwd(const float* qkv, int64_t ld_qkv, const float* out, int64_t ld_out, const float* lse,
+                                           const float* d_out, int64_t ld_do, float* d_qkv, int64_t ld_dqkv, int64_t B, int32_t H,
+                                           int32_t hd, int32_t T, float scale, float* scratch, void* stream) {
+    const mdt_status st = long_check("mdt_op_attn_long_bwd", B, H, hd, T, qkv && out && lse && d_out && d_qkv && scratch,
+                                     aligned16(qkv) && aligned16(out) && aligned16(d_out) && aligned16(d_qkv) && ld_qkv % 4 == 0 &&
+                                         ld_out % 4 == 0 && ld_do % 4 == 0 && ld_dqkv % 4 == 0);
+    if (st != MDT_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    switch (hd) {
+        case 16: LAUNCH(launch_long_bwd<16>(qkv, ld_qkv, out, ld_out, lse, d_out, ld_do, d_qkv, ld_dqkv, B, H, T, scale, scratch, s)); break;
+        case 24: LAUNCH(launch_long_bwd<24>(qkv, ld_qkv, out, ld_out, lse, d_out, ld_do, d_qkv, ld_dqkv, B, H, T, scale, scratch, s)); break;
+        case 32: LAUNCH(launch_long_bwd<32>(qkv, ld_qkv, out, ld_out, lse, d_out, ld_do, d_qkv, ld_dqkv, B, H, T, scale, scratch, s)); break;
+        case 48: LAUNCH(launch_long_bwd<48>(qkv, ld_qkv, out, ld_out, lse, d_out, ld_do, d_qkv, ld_dqkv, B, H, T, scale, scratch, s)); break;
+        case 64: LAUNCH(launch_long_bwd<64>(qkv, ld_qkv, out, ld_out, lse, d_out, ld_do, d_qkv, ld_dqkv, B, H, T, scale, scratch, s)); break;
     }
     return MDT_OK;
 }

@@ -1,5 +1,5 @@
 """HIP-backed autograd functions of the masked-image decoder: every Linear on the fp32-MFMA GEMM (mdt_op_gemm forward,
-mdt_op_linear_bwd backward), RMSNorm / SwishGLU row kernels and the mid-length self-attention (include/mdt_mae.h).
+mdt_op_linear_bwd backward), RMSNorm / SwishGLU row kernels and the mid-length / long self-attention (include/mdt_mae.h).
 No eager fallback: CPU tensors or a missing library raise."""
 from __future__ import annotations
 
@@ -519,8 +519,14 @@ class HipPatchMSE(torch.autograd.Function):
         return d, None, None, None
 
 
+MID_TMAX = 128    # mdt_op_attn_mid_*: a whole (sample, head) in one workgroup's registers and LDS
+LONG_TMAX = 4096  # mdt_op_attn_long_*: flash-style, keys streamed through LDS
+
+
 class HipSelfAttention(torch.autograd.Function):
-    """qkv (B, T, 3 D) = q | k | v -> softmax(q k^T * scale) v (B, T, D), H heads, unmasked, T <= 128."""
+    """qkv (B, T, 3 D) = q | k | v -> softmax(q k^T * scale) v (B, T, D), H heads, unmasked.  T <= 128 runs the mid-length op
+    (the shipped 102-token head), 128 < T <= 4096 the flash-style long op, which also keeps the rows' log-sum-exp for the
+    backward."""
 
     @staticmethod
     def forward(ctx, qkv, n_heads: int, scale: float):
@@ -529,20 +535,31 @@ class HipSelfAttention(torch.autograd.Function):
         D = D3 // 3
         q = _c(qkv)
         out = torch.empty((B, T, D), device=q.device, dtype=torch.float32)
-        _lib.check(lib.mdt_op_attn_mid_fwd(q.data_ptr(), D3, out.data_ptr(), D, B, n_heads, D // n_heads, T, float(scale), _stream(q)))
-        ctx.save_for_backward(q, out)  # the output is kept anyway (input of the projection that follows)
+        if T <= MID_TMAX:
+            _lib.check(lib.mdt_op_attn_mid_fwd(q.data_ptr(), D3, out.data_ptr(), D, B, n_heads, D // n_heads, T, float(scale), _stream(q)))
+            ctx.save_for_backward(q, out)  # the output is kept anyway (input of the projection that follows)
+        else:
+            lse = torch.empty((B, n_heads, T), device=q.device, dtype=torch.float32)
+            _lib.check(lib.mdt_op_attn_long_fwd(q.data_ptr(), D3, out.data_ptr(), D, lse.data_ptr(), B, n_heads, D // n_heads, T,
+                                                float(scale), _stream(q)))
+            ctx.save_for_backward(q, out, lse)
         ctx.cfg = (n_heads, float(scale))
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         lib = _lib.load()
-        q, out = ctx.saved_tensors
+        q, out, *lse = ctx.saved_tensors
         n_heads, scale = ctx.cfg
         B, T, D3 = q.shape
         D = D3 // 3
         d = _c(d_out)
         dq = torch.empty_like(q)
-        _lib.check(lib.mdt_op_attn_mid_bwd(q.data_ptr(), D3, out.data_ptr(), D, d.data_ptr(), D, dq.data_ptr(), D3, B, n_heads,
-                                           D // n_heads, T, scale, _stream(d)))
+        if not lse:
+            _lib.check(lib.mdt_op_attn_mid_bwd(q.data_ptr(), D3, out.data_ptr(), D, d.data_ptr(), D, dq.data_ptr(), D3, B, n_heads,
+                                               D // n_heads, T, scale, _stream(d)))
+        else:
+            scratch = torch.empty(lib.mdt_op_attn_long_bwd_scratch(B, n_heads, T), device=q.device, dtype=torch.float32)
+            _lib.check(lib.mdt_op_attn_long_bwd(q.data_ptr(), D3, out.data_ptr(), D, lse[0].data_ptr(), d.data_ptr(), D,
+                                                dq.data_ptr(), D3, B, n_heads, D // n_heads, T, scale, scratch.data_ptr(), _stream(d)))
         return dq, None, None

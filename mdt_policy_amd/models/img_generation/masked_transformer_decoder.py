@@ -230,9 +230,17 @@ class MaskedTransformerImgDecoder(nn.Module):
         B = context.shape[0]
         if X != 2 or target_images.shape[1] != 2:
             raise NotImplementedError("the decoder pairs frame 0 and frame K (num_images = 2), as the reference's forward does")
-        if context.shape[1] + X * n > 128:
-            raise NotImplementedError(f"{context.shape[1] + X * n} decoder tokens: the HIP attention covers up to 128 "
-                                      "(the shipped 112 x 112 / 16 configuration has 102)")
+        T = context.shape[1] + X * n
+        if T > ops.LONG_TMAX:
+            raise NotImplementedError(f"{T} decoder tokens: the HIP attention covers up to {ops.LONG_TMAX} (224 x 224 / 8 has "
+                                      "1572; the shipped 112 x 112 / 16 configuration has 102)")
+        # the row kernels and GEMMs address a tensor's elements with 32-bit indices / byte offsets in places: refuse a batch whose
+        # widest activation (the SwishGLU input, B T x 2 hidden) would not fit rather than let an index wrap
+        glu = self.decoder_blocks[0].mlp[0].project.out_features if len(self.decoder_blocks) else 0
+        widest = B * T * max(glu, 3 * d, self.patch_size ** 2 * self.in_channels)
+        if widest >= 2 ** 31:
+            raise ValueError(f"batch {B} x {T} decoder tokens: the widest activation would hold {widest} elements, the HIP head "
+                             f"supports fewer than 2^31 (split the batch)")
         # every Linear's packed images (and, under autograd, the W^T images of the backward) in one launch
         self._packs.refresh([m.weight for m in self.modules() if isinstance(m, (nn.Linear, nn.Conv2d))],
                             need_t=torch.is_grad_enabled())
