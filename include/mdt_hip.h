@@ -345,6 +345,60 @@ mdt_status mdt_sample_dpm_adaptive_guided(mdt_model *m, const float *tokens, con
                                           const mdt_dpm_adaptive_params *params, int64_t batch, float *out, float *ctx_out,
                                           float cond_lambda, mdt_dpm_adaptive_info *info, void *stream);
 
+/* Brownian-tree noise: the default noise sampler of sample_dpmpp_sde (the reference's BrownianTreeNoiseSampler) without
+ * torchsde.  A virtual Brownian tree (Levy midpoint construction, csrc/mdt_brownian.h) on [lo, hi] (lo < hi; W(lo) = 0) whose
+ * value at any point is a pure function of (seed, element, point), walked in double until the interval is <= tol (at most 62
+ * levels; a tol that needs more is MDT_ERR_INVALID_ARG; the reference's 1e-6 takes 27 levels on [0.001, 80]).  The normals are
+ * Box-Muller on the library's Philox4x32-10 keyed by the seed.  The noise value of a query (from, to) is
+ *     (W(to) - W(from)) / sqrt(|to - from|)          (double, rounded once to fp32; points clamped to [lo, hi])
+ * Seeds: n_seeds == 1: one tree per element of the whole (batch, per_row) tensor (element = its flat index); n_seeds == batch:
+ * sample b uses seeds[b] and the element index inside its row, so a sample's noise does not depend on the rest of the batch.
+ * Bit parity with torchsde is not a goal (another algorithm); the law is the same. */
+enum { MDT_BROWNIAN_MAX_PAIRS = 64 };
+/* mdt_brownian_noise: out (n_q, batch, per_row) on the device for n_q <= MDT_BROWNIAN_MAX_PAIRS HOST pairs
+ * (pairs[2 q], pairs[2 q + 1]) = (from, to); seeds: n_seeds device keys.  One launch, capture-safe, never synchronises (the
+ * pairs ride in the kernel's arguments).  mdt_brownian_noise_host: the same values from the same routine on host memory (seeds
+ * and out on the host, any n_q, no GPU work). */
+mdt_status mdt_brownian_noise(const uint64_t *seeds, int32_t n_seeds, double lo, double hi, double tol, const double *pairs,
+                              int32_t n_q, int64_t batch, int64_t per_row, float *out, void *stream);
+mdt_status mdt_brownian_noise_host(const uint64_t *seeds, int32_t n_seeds, double lo, double hi, double tol, const double *pairs,
+                                   int32_t n_q, int64_t batch, int64_t per_row, float *out);
+
+/* The tree of a dpmpp_sde call that draws its noise inside the call (mdt_sample_sde_tree*).  lo < hi: the tree's interval (a
+ * noise sampler built with its own sigma_min / sigma_max); lo == hi == 0: the schedule's smallest positive and largest level,
+ * the reference's default, taken on the device for a device schedule. */
+typedef struct mdt_brownian_source {
+    const uint64_t *seeds;           /* device: n_seeds keys                                                           */
+    int32_t n_seeds;                 /* 1 or batch (see mdt_brownian_noise)                                            */
+    int32_t pad;
+    double lo, hi;                   /* the tree's interval, or 0, 0: the schedule's                                   */
+    double tol;                      /* the walk's resolution (reference default 1e-6)                                 */
+} mdt_brownian_source;
+
+/* sample_dpmpp_sde (MDT_SAMPLER_DPMPP_SDE) with the noise of the reference's default noise sampler -- the Brownian tree of
+ * `tree` -- drawn inside the call instead of read from a noise buffer: the arguments of mdt_sample / mdt_sample_dev /
+ * mdt_sample_guided / mdt_sample_dev_guided without kind, noise and n_noise, plus `tree`.  The plan kernel records the
+ * (from, to) points of every noise row -- (sigma(t), sigma(s)) then (sigma(t), sigma(t_next)), each where sigma_up != 0, t =
+ * -ln(sigma) as the Python loop forms them -- and one more launch before the first evaluation writes every row into a
+ * handle-owned buffer from the tree; the evaluations then read it as they read a caller's noise (the same bits as passing those
+ * rows to mdt_sample).  A device schedule is read in place (interval and points included): capture-safe, no synchronisation.
+ * The first call at a larger batch or step count grows the buffer (synchronising, and a new mdt_ws_generation): make one eager
+ * call before capturing.  With eta == 0 or s_noise == 0 the tree is not read. */
+mdt_status mdt_sample_sde_tree(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                               const float *x_T, const mdt_sampler_params *params, const float *sigmas_host, int32_t n_steps,
+                               const mdt_brownian_source *tree, int64_t batch, float *out, float *ctx_out, void *stream);
+mdt_status mdt_sample_sde_tree_dev(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                                   const float *x_T, const mdt_sampler_params *params, const float *sigmas_dev, int32_t n_steps,
+                                   const mdt_brownian_source *tree, int64_t batch, float *out, float *ctx_out, void *stream);
+mdt_status mdt_sample_sde_tree_guided(mdt_model *m, const float *tokens, const float *tokens2, const float *goal,
+                                      int32_t modality, const float *x_T, const mdt_sampler_params *params,
+                                      const float *sigmas_host, int32_t n_steps, const mdt_brownian_source *tree, int64_t batch,
+                                      float *out, float *ctx_out, float cond_lambda, void *stream);
+mdt_status mdt_sample_sde_tree_dev_guided(mdt_model *m, const float *tokens, const float *tokens2, const float *goal,
+                                          int32_t modality, const float *x_T, const mdt_sampler_params *params,
+                                          const float *sigmas_dev, int32_t n_steps, const mdt_brownian_source *tree,
+                                          int64_t batch, float *out, float *ctx_out, float cond_lambda, void *stream);
+
 /* GCDenoiser.loss(state, action, goal, noise, sigma) forward value, eval mode (reference
  * score_wrappers.py:45-63): noised = a + n*sigma; F = inner(noised*c_in); target = (a - c_skip*noised)/c_out;
  * loss = mean((F - target)^2) over all B*Ta*A elements.  loss_out: 1 float (device); model_output: (B,Ta,A). */

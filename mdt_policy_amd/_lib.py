@@ -87,6 +87,15 @@ class SamplerEval(C.Structure):
                 ("step", C.c_int32), ("t", C.c_float), ("pad", C.c_int32 * 3)]
 
 
+class BrownianSource(C.Structure):
+    """mdt_brownian_source (include/mdt_hip.h): the tree of a tree-noise dpmpp_sde call."""
+    _fields_ = [("seeds", C.c_void_p), ("n_seeds", C.c_int32), ("pad", C.c_int32), ("lo", C.c_double), ("hi", C.c_double),
+                ("tol", C.c_double)]
+
+
+BROWNIAN_MAX_PAIRS = 64  # MDT_BROWNIAN_MAX_PAIRS
+
+
 class SamplerPlan(C.Structure):
     """mdt_sampler_plan_t (include/mdt_hip.h)."""
     _fields_ = [("n_evals", C.c_int32), ("n_noise", C.c_int32), ("y0_noise", C.c_int32), ("y0_cn", C.c_float),
@@ -229,6 +238,16 @@ SYMBOLS = [
                                  _I32, _I64, _VP, _VP, _F, _VP]),
     ("mdt_sample_dev_guided", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), _VP, _I32, _VP, _I32, _I64,
                                      _VP, _VP, _F, _VP]),
+    ("mdt_brownian_noise", _I32, [_VP, _I32, C.c_double, C.c_double, C.c_double, _VP, _I32, _I64, _I64, _VP, _VP]),
+    ("mdt_brownian_noise_host", _I32, [_VP, _I32, C.c_double, C.c_double, C.c_double, _VP, _I32, _I64, _I64, _VP]),
+    ("mdt_sample_sde_tree", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32,
+                                   C.POINTER(BrownianSource), _I64, _VP, _VP, _VP]),
+    ("mdt_sample_sde_tree_dev", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(SamplerParams), _VP, _I32, C.POINTER(BrownianSource),
+                                       _I64, _VP, _VP, _VP]),
+    ("mdt_sample_sde_tree_guided", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32,
+                                          C.POINTER(BrownianSource), _I64, _VP, _VP, _F, _VP]),
+    ("mdt_sample_sde_tree_dev_guided", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(SamplerParams), _VP, _I32,
+                                              C.POINTER(BrownianSource), _I64, _VP, _VP, _F, _VP]),
     ("mdt_sample_dpm_adaptive_guided", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.c_float, C.c_float, C.POINTER(DpmAdaptiveParams),
                                               _I64, _VP, _VP, _F, C.POINTER(DpmAdaptiveInfo), _VP]),
     ("mdt_dpm_control_init", _I32, [C.POINTER(DpmControl)] + [C.c_double] * 6),
@@ -423,6 +442,18 @@ def sampler_plan(kind, sigmas, n_steps=None, **params) -> SamplerPlan:
     n = len(sig) - 1 if n_steps is None else int(n_steps)
     check(load().mdt_sampler_plan(kind, C.byref(sampler_params(**params)), arr, n, C.byref(plan)))
     return plan
+
+
+def brownian_noise_host(seeds, lo, hi, tol, pairs, batch, per_row):
+    """mdt_brownian_noise_host: a (len(pairs), batch, per_row) float32 numpy array of the tree's noise values for the (from, to)
+    ``pairs``; ``seeds`` one int (the whole tensor) or ``batch`` ints (one tree per sample)."""
+    import numpy as np
+    sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).reshape(-1))
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.float64).reshape(-1, 2))
+    out = np.empty((pr.shape[0], int(batch), int(per_row)), dtype=np.float32)
+    check(load().mdt_brownian_noise_host(sd.ctypes.data, len(sd), float(lo), float(hi), float(tol), pr.ctypes.data, pr.shape[0],
+                                         int(batch), int(per_row), out.ctypes.data))
+    return out
 
 
 def dpm_adaptive_params(order=3, rtol=0.05, atol=0.0078, h_init=0.05, pcoeff=0., icoeff=1., dcoeff=0.,

@@ -207,7 +207,8 @@ __device__ __forceinline__ float xrow_sum(float v) {
 // idx & 3 of block idx >> 2 (round 6; rounds 1-5 ran a whole block per element and kept one word: ~100 integer instructions per
 // dropped-out value, as much as the branch-merge kernels' memory time), so 16-byte accesses pay one block per four elements.
 struct philox4_t { uint32_t w[4]; };
-__device__ __forceinline__ philox4_t philox4(uint64_t seed, uint32_t site, uint64_t ctr) {
+// (host and device: the Brownian tree of mdt_brownian.h evaluates the same normals on both)
+__host__ __device__ __forceinline__ philox4_t philox4(uint64_t seed, uint32_t site, uint64_t ctr) {
     uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = site, c3 = 0x9e3779b9u;
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll

@@ -119,11 +119,19 @@ hipError_t mdt_launch_sample_prep(const float* sigmas_dev, const float* sigmas_h
 // (Mx: rows of x; 0 = M.  The guided sampler passes M = 2 Mx: the embedding goes to both halves of y)
 // the other samplers' once-per-call work (mdt_kernels.hip: k_sampler_plan + k_sampler_first): the plan of mdt_sampler_plan.h
 // built on the device, the sigma embeddings of every evaluation (sig_e == nullptr: none), the first input Y_0 -> y0 (M, A), the
-// four history slots hist (4, M, A) zeroed, and Y_0's action embedding -> y
+// four history slots hist (4, M, A) zeroed, and Y_0's action embedding -> y.  tq: nullptr, or (dpmpp_sde with tree noise) where
+// the plan records its noise rows' points and the schedule's interval (mdt_sampler_plan.h)
+struct mdt_tree_q;
+// the tree of a tree-noise sampler call, checked before anything is enqueued (mdt_brownian.hip)
+mdt_status mdt_check_brownian_source(const char* who, const mdt_brownian_source* src, int64_t batch, int64_t per_row);
 hipError_t mdt_launch_sampler_prep(const float* sigmas_dev, const float* sigmas_host, int n_steps, int kind,
                                    const mdt_sampler_params& prm, mdt_sampler_plan_t* plan, const float* freqs, float* sig_e,
                                    int D, const float* x, const float* noise, int n_noise, float* y0, float* hist, float sd, const float* Wa,
-                                   const float* ba, float* y, int M, int A, hipStream_t s, int Mx = 0);
+                                   const float* ba, float* y, int M, int A, hipStream_t s, int Mx = 0, mdt_tree_q* tq = nullptr);
+// the tree-noise rows of a dpmpp_sde call (mdt_brownian.hip: k_brownian_fill): rows (max_rows, nel) of the points the plan kernel
+// recorded in tq (rows beyond tq->n are not written), from the trees of src (lo >= hi: tq's interval)
+hipError_t mdt_launch_brownian_fill(const mdt_tree_q* tq, const mdt_brownian_source& src, int max_rows, int64_t nel, int64_t per_row,
+                                    float* out, hipStream_t s);
 // k_sampler_first alone (the adaptive DPM-Solver's per-attempt first input, from a plan uploaded by the host)
 hipError_t mdt_launch_sampler_first(const mdt_sampler_plan_t* plan, const float* x, const float* noise, int n_noise, float* y0,
                                     float* hist, float sd, const float* Wa, const float* ba, float* y, int M, int A, int D,

@@ -1556,11 +1556,13 @@ hipError_t mdt_launch_sample_prep(const float* sigmas_dev, const float* sigmas_h
 // The once-per-call scalar work of the other samplers (mdt_sample): ONE workgroup builds the plan (mdt_sampler_plan.h) from
 // the schedule -- by value from the host or read in place from the device -- in LDS, copies it out and writes the sinusoidal
 // sigma embeddings of every evaluation (k_sigma_emb's arithmetic).  k_sampler_first then forms the first input
-// Y_0 = x_T + y0_cn N[y0_noise], zeroes the history slots and embeds Y_0 with c_in(sigma of evaluation 0).
+// Y_0 = x_T + y0_cn N[y0_noise], zeroes the history slots and embeds Y_0 with c_in(sigma of evaluation 0).  tq (dpmpp_sde
+// with tree noise): the plan's noise-row points and the schedule's interval go there too (mdt_tree_q).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sampler_plan(const float* __restrict__ sig_dev, mdt_sched_arg sv, int n_steps, int kind,
                                                       mdt_sampler_params prm, mdt_sampler_plan_t* __restrict__ plan,
-                                                      const float* __restrict__ freqs, float* __restrict__ sig_e, int D) {
+                                                      const float* __restrict__ freqs, float* __restrict__ sig_e, int D,
+                                                      mdt_tree_q* __restrict__ tq) {
     __shared__ float ss[MDT_SCHED_MAX + 1];
     __shared__ mdt_sampler_plan_t sp;
     __shared__ float lms[4 * MDT_SCHED_MAX];
@@ -1571,7 +1573,13 @@ __global__ __launch_bounds__(256) void k_sampler_plan(const float* __restrict__ 
     // the LMS quadratures (double) one step per thread: serially they were 85 us of a 20-step call
     if (is_lms && threadIdx.x < n_steps) mdt_lms_step_coeffs(prm.order, ss, threadIdx.x, lms + 4 * threadIdx.x);
     if (is_lms) __syncthreads();
-    if (threadIdx.x == 0) mdt_build_sampler_plan(kind, prm, ss, n_steps, &sp, is_lms ? lms : nullptr);  // host checked the args
+    if (threadIdx.x == 0) {  // host checked the args
+        mdt_build_sampler_plan(kind, prm, ss, n_steps, &sp, is_lms ? lms : nullptr, tq ? tq->q : nullptr);
+        if (tq) {
+            mdt_tree_interval(ss, levels, &tq->lo, &tq->hi);
+            tq->n = sp.n_noise;
+        }
+    }
     __syncthreads();
     const int E = sp.n_evals;
     const int words = (int)((sizeof(mdt_sampler_plan_t) - (MDT_SAMPLER_MAX_EVALS - E) * sizeof(mdt_sampler_eval)) / 4);
@@ -1623,14 +1631,14 @@ __global__ __launch_bounds__(256) void k_sampler_first(const mdt_sampler_plan_t*
 hipError_t mdt_launch_sampler_prep(const float* sigmas_dev, const float* sigmas_host, int n_steps, int kind,
                                    const mdt_sampler_params& prm, mdt_sampler_plan_t* plan, const float* freqs, float* sig_e,
                                    int D, const float* x, const float* noise, int n_noise, float* y0, float* hist, float sd, const float* Wa,
-                                   const float* ba, float* y, int M, int A, hipStream_t s, int Mx) {
+                                   const float* ba, float* y, int M, int A, hipStream_t s, int Mx, mdt_tree_q* tq) {
     const int levels = mdt_plan_levels(kind, n_steps);
     if (n_steps < 1 || n_steps > MDT_SAMPLER_MAX_EVALS || levels > MDT_SCHED_MAX + 1 || (!sigmas_dev) == (!sigmas_host) || (D & 3))
         return hipErrorInvalidValue;
     mdt_sched_arg sv;
     memset(&sv, 0, sizeof sv);
     if (sigmas_host) memcpy(sv.s, sigmas_host, (size_t)levels * sizeof(float));
-    hipLaunchKernelGGL(k_sampler_plan, dim3(1), dim3(256), 0, s, sigmas_dev, sv, n_steps, kind, prm, plan, freqs, sig_e, D);
+    hipLaunchKernelGGL(k_sampler_plan, dim3(1), dim3(256), 0, s, sigmas_dev, sv, n_steps, kind, prm, plan, freqs, sig_e, D, tq);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return mdt_launch_sampler_first(plan, x, noise, n_noise, y0, hist, sd, Wa, ba, y, M, A, D, s, Mx);

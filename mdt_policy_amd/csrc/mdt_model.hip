@@ -415,6 +415,7 @@ extern "C" mdt_status mdt_destroy(mdt_model* m) {
     }
     if (m->ev_tab_use) (void)hipEventDestroy(m->ev_tab_use);
     (void)mdt_dev_free(m->ad_ws);
+    (void)mdt_dev_free(m->tr_ws);
     if (m->ad_host) (void)hipHostFree(m->ad_host);
     delete m;
     return MDT_OK;
@@ -1372,20 +1373,47 @@ static mdt_status run_plan_eval(mdt_model* m, const View& V, const SamplerCall& 
 // The structure of sample_ddim_impl: the plan and the sigma embeddings of every evaluation (one launch), the first input, the
 // conditioning rows of every evaluation (their GEMMs ride in the encoder's launches), the encoder and cross K/V once, then one
 // decoder pass + plan head per evaluation.
+// tree (dpmpp_sde with tree noise, mdt_sample_sde_tree*): `noise` is null and the rows come from the tree -- the plan kernel records
+// their points, k_brownian_fill writes them into the handle's tr_noise before the first evaluation, which then reads them as a
+// caller's buffer.
 static mdt_status sample_plan_impl(mdt_model* m, const SamplerArgs& a, int32_t kind, const mdt_sampler_params* params, Sched sc,
-                                   int32_t n_steps, const float* noise, int32_t n_noise) {
+                                   int32_t n_steps, const float* noise, int32_t n_noise, const mdt_brownian_source* tree = nullptr) {
     mdt_guide gd;
     MDT_TRY(sampler_check(m, a, "mdt_sample", sc.levels != nullptr, &gd));
     const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
     int E = 0, rows = 0;
     MDT_TRY(plan_fail(mdt_plan_shape(kind, p, n_steps, &E, &rows), "mdt_sample", kind));
+    const int max_rows = rows;
     if (sc.host()) {  // a host schedule: the loop's exact draw count (a device schedule: the structural maximum)
         MDT_TRY(plan_fail(mdt_plan_check_levels(kind, p, sc.host()), "mdt_sample", kind));
         static thread_local mdt_sampler_plan_t hp;
         mdt_build_sampler_plan(kind, p, sc.host(), n_steps, &hp);
         rows = hp.n_noise;
     }
-    if (!noise && mdt_plan_needs_noise(kind, p))
+    const bool use_tree = tree && mdt_plan_needs_noise(kind, p) && max_rows > 0;
+    if (tree) {
+        const int64_t per_row = (int64_t)m->Ta * m->A;
+        MDT_TRY(mdt_check_brownian_source(a.who, tree, a.batch, per_row));
+        if (sc.host() && tree->lo == 0.0 && tree->hi == 0.0) {
+            double lo = 0.0, hi = 0.0;
+            mdt_tree_interval(sc.host(), n_steps + 1, &lo, &hi);
+            mdt_brownian_source t = *tree;
+            t.lo = lo; t.hi = hi;
+            MDT_TRY(mdt_check_brownian_source(a.who, &t, a.batch, per_row));
+        }
+        if (use_tree) {  // (a grown buffer moves: captured graphs that read the old one are stale, as after mdt_reserve)
+            const int64_t held_rows = m->tr_rows, held_nel = m->tr_nel;
+            MDT_TRY(mdt_grow_carve(m->tr_ws, m->tr_rows, m->tr_nel, max_rows, a.batch * per_row,
+                                   [&](Bump& b, int64_t r, int64_t nel) {
+                                       m->tr_q = (mdt_tree_q*)b.take((sizeof(mdt_tree_q) + 3) / 4);
+                                       m->tr_noise = b.take(r * nel);
+                                   }));
+            if (m->tr_rows != held_rows || m->tr_nel != held_nel) ++m->ws_generation;
+            noise = m->tr_noise;
+            n_noise = max_rows;
+        }
+    }
+    if (!noise && !tree && mdt_plan_needs_noise(kind, p))
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample: this sampler and parameter set need the noise buffer (%d rows)", rows);
     if (noise && n_noise < rows)
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample: the noise buffer holds %d rows, the sampler reads %d", n_noise, rows);
@@ -1399,7 +1427,9 @@ static mdt_status sample_plan_impl(mdt_model* m, const SamplerArgs& a, int32_t k
     mdt_sampler_eval* ev = m->plan->e;
     LAUNCH(mdt_launch_sampler_prep(sc.device(), sc.host(), n_steps, kind, p, m->plan, m->freqs, per_step_ctx ? nullptr : m->sig_e,
                                    m->D, a.x_T, noise, noise ? n_noise : 0, m->ybuf, m->hist, m->cfg.sigma_data, m->Wa, m->ba, V.y,
-                                   (int)(c.nb * m->Ta), m->A, c.s, (int)(a.batch * m->Ta)));
+                                   (int)(c.nb * m->Ta), m->A, c.s, (int)(a.batch * m->Ta), use_tree ? m->tr_q : nullptr));
+    if (use_tree)  // every noise row from the tree, before the first evaluation reads one
+        LAUNCH(mdt_launch_brownian_fill(m->tr_q, *tree, max_rows, a.batch * m->Ta * m->A, (int64_t)m->Ta * m->A, m->tr_noise, c.s));
     const int stride = (int)(sizeof(mdt_sampler_eval) / sizeof(float));
     mdt_status ms = run_modulation(m, &ev[0].sigma, stride, E, c.s, true, !per_step_ctx);  // one conditioning row per evaluation
     if (ms == MDT_OK && !per_step_ctx) ms = c.encode(m, nullptr, c.ctx_out);
@@ -1443,6 +1473,44 @@ extern "C" mdt_status mdt_sample_dev_guided(mdt_model* m, const float* tokens, c
                                             int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
     return sample_plan_impl(m, {"mdt_sample_dev_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
                                 stream}, kind, params, {sigmas_dev, true}, n_steps, noise, n_noise);
+}
+
+static const mdt_brownian_source k_null_tree = {};  // a null `tree` argument: refused by the checks
+
+extern "C" mdt_status mdt_sample_sde_tree(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                          int32_t modality, const float* x_T, const mdt_sampler_params* params,
+                                          const float* sigmas_host, int32_t n_steps, const mdt_brownian_source* tree, int64_t batch,
+                                          float* out, float* ctx_out, void* stream) {
+    return sample_plan_impl(m, {"mdt_sample_sde_tree", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream},
+                            MDT_SAMPLER_DPMPP_SDE, params, {sigmas_host, false}, n_steps, nullptr, 0,
+                            tree ? tree : &k_null_tree);
+}
+
+extern "C" mdt_status mdt_sample_sde_tree_dev(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                              int32_t modality, const float* x_T, const mdt_sampler_params* params,
+                                              const float* sigmas_dev, int32_t n_steps, const mdt_brownian_source* tree,
+                                              int64_t batch, float* out, float* ctx_out, void* stream) {
+    return sample_plan_impl(m, {"mdt_sample_sde_tree_dev", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
+                                stream}, MDT_SAMPLER_DPMPP_SDE, params, {sigmas_dev, true}, n_steps, nullptr, 0,
+                            tree ? tree : &k_null_tree);
+}
+
+extern "C" mdt_status mdt_sample_sde_tree_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                                 int32_t modality, const float* x_T, const mdt_sampler_params* params,
+                                                 const float* sigmas_host, int32_t n_steps, const mdt_brownian_source* tree,
+                                                 int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
+    return sample_plan_impl(m, {"mdt_sample_sde_tree_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
+                                stream}, MDT_SAMPLER_DPMPP_SDE, params, {sigmas_host, false}, n_steps, nullptr, 0,
+                            tree ? tree : &k_null_tree);
+}
+
+extern "C" mdt_status mdt_sample_sde_tree_dev_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                                     int32_t modality, const float* x_T, const mdt_sampler_params* params,
+                                                     const float* sigmas_dev, int32_t n_steps, const mdt_brownian_source* tree,
+                                                     int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
+    return sample_plan_impl(m, {"mdt_sample_sde_tree_dev_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out,
+                                ctx_out, stream}, MDT_SAMPLER_DPMPP_SDE, params, {sigmas_dev, true}, n_steps, nullptr, 0,
+                            tree ? tree : &k_null_tree);
 }
 
 extern "C" mdt_status mdt_dpm_control_init(mdt_dpm_control* c, double h, double pcoeff, double icoeff, double dcoeff,

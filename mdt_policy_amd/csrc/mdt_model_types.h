@@ -97,6 +97,12 @@ struct mdt_model {
     float* ad_ws = nullptr;
     int64_t ad_cap = 0;
     void* ad_host = nullptr;
+    // mdt_sample_sde_tree*: the plan's noise-row points (mdt_tree_q) and the rows (tr_rows, tr_nel) k_brownian_fill writes, grown by
+    // mdt_grow_carve
+    float* tr_ws = nullptr;
+    int64_t tr_rows = 0, tr_nel = 0;
+    mdt_tree_q* tr_q = nullptr;
+    float* tr_noise = nullptr;
     float* cmod = nullptr;  // COND_NOISE: rows of [c | ones(D)], read as (shift, scale) by the LayerNorm prologue
     int64_t cached_batch = 0;  // batch of the context currently cached by mdt_encode (0 = none)
     // collapsed cross-attention (k_xattn_fold / k_xattn_apply): folded projections per sample and decoder block

@@ -118,6 +118,7 @@ MDT_HD inline float lms_coeff(int order, const float* t, int i, int j) {
 struct Builder {
     mdt_sampler_plan_t* P;
     int rows = 0;  // noise rows drawn so far (the loop's order)
+    float* q = nullptr;  // dpmpp_sde with tree noise: the (from, to) points of every row (mdt_tree_q::q), or null
     MDT_HD mdt_sampler_eval& add(float sigma, int step) {
         mdt_sampler_eval& e = P->e[P->n_evals++];
         memset(&e, 0, sizeof e);
@@ -151,6 +152,17 @@ struct Builder {
         c.cx[MDT_R_X] = 1.f;
     }
 };
+
+// the points of dpmpp_sde's noise_sampler calls at step i as the host loop forms them from 0-dim fp32 tensors: sigma(t),
+// sigma(t + h r), sigma(t_next), t = -ln(sigma), with ln / exp rounded once from double (dpm_t / dpm_s below: the correctly
+// rounded fp32 results but in rare last-place cases, on the host and the device alike)
+MDT_HD inline float dpm_t(float s);
+MDT_HD inline float dpm_s(float t);
+MDT_HD inline void sde_points(float s, float sn, float r, float* from, float* mid, float* next) {
+#pragma clang fp contract(off)
+    const float t = dpm_t(s), tn = dpm_t(sn), h = tn - t, sm = t + h * r;
+    *from = dpm_s(t); *mid = dpm_s(sm); *next = dpm_s(tn);
+}
 
 // torch.linspace(t0, t1, m + 1)[i] in fp32 as torch's CPU kernel computes it: from the nearer end
 MDT_HD inline float dpm_grid(float t0, float t1, int m, int i) {
@@ -287,9 +299,10 @@ MDT_HD inline void mdt_lms_step_coeffs(int order, const float* sig, int i, float
 }
 
 // sig: mdt_plan_levels(kind, n) levels.  lms: nullptr, or the n x 4 table of mdt_lms_step_coeffs (the same values, computed beforehand).
+// queries: nullptr, or (dpmpp_sde) 2 floats per noise row that receive the row's (from, to) points (sde_points).
 // Returns MDT_PLAN_*.
 MDT_HD inline int mdt_build_sampler_plan(int kind, const mdt_sampler_params& p, const float* sig, int n, mdt_sampler_plan_t* P,
-                                         const float* lms = nullptr) {
+                                         const float* lms = nullptr, float* queries = nullptr) {
     using namespace mdt_plan_detail;
     int n_evals = 0, n_noise = 0;
     const int st = mdt_plan_shape(kind, p, n, &n_evals, &n_noise);
@@ -301,6 +314,7 @@ MDT_HD inline int mdt_build_sampler_plan(int kind, const mdt_sampler_params& p, 
     P->y0_draws = 0;
     P->pad[0] = P->pad[1] = P->pad[2] = 0;
     Builder b{P};
+    b.q = queries;
     if (kind == MDT_SAMPLER_DPM_FAST) dpm_fast(b, p, sig, n);
     for (int i = 0; i < n && kind != MDT_SAMPLER_DPM_FAST; ++i) {
         const float s = sig[i], sn = sig[i + 1];
@@ -405,14 +419,24 @@ MDT_HD inline int mdt_build_sampler_plan(int kind, const mdt_sampler_params& p, 
                 const float s1 = t_of(a1.down);
                 a.cx[MDT_R_Y] = 1.f; a.push = MDT_PUSH_D;
                 a.cy[MDT_SAMPLER_NREG] = 0.f; a.cy[MDT_R_Y] = s_of(s1) / s_of(t); a.cy[MDT_R_D] = -expm1f(t - s1);
-                if (a1.up != 0.f) a.cy[Builder::slot(a, b.draw())] = p.s_noise * a1.up;
+                float qf = 0.f, qm = 0.f, qn = 0.f;
+                if (b.q) sde_points(s, sn, p.r, &qf, &qm, &qn);
+                if (a1.up != 0.f) {
+                    const int row = b.draw();
+                    a.cy[Builder::slot(a, row)] = p.s_noise * a1.up;
+                    if (b.q) { b.q[2 * row] = qf; b.q[2 * row + 1] = qm; }
+                }
                 mdt_sampler_eval& c = b.add(s_of(sm), i);
                 const Anc a2 = ancestral(s_of(t), s_of(tn), p.eta);
                 const float t2 = t_of(a2.down), em = expm1f(t - t2);
                 c.cx[MDT_R_X] = s_of(t2) / s_of(t);
                 c.cx[MDT_R_H0] = -em * (1.f - fac);
                 c.cx[MDT_R_D] = -em * fac;
-                if (a2.up != 0.f) c.cx[Builder::slot(c, b.draw())] = p.s_noise * a2.up;
+                if (a2.up != 0.f) {
+                    const int row = b.draw();
+                    c.cx[Builder::slot(c, row)] = p.s_noise * a2.up;
+                    if (b.q) { b.q[2 * row] = qf; b.q[2 * row + 1] = qn; }
+                }
                 break;
             }
         }
@@ -422,4 +446,22 @@ MDT_HD inline int mdt_build_sampler_plan(int kind, const mdt_sampler_params& p, 
     mdt_sampler_eval& z = P->e[P->n_evals - 1];
     for (int k = 0; k <= MDT_SAMPLER_NREG; ++k) z.cy[k] = 0.f;  // nothing follows the last evaluation
     return MDT_PLAN_OK;
+}
+
+// The tree-noise rows of a dpmpp_sde call (mdt_sample_sde_tree*): the plan records the (from, to) points of every noise row,
+// and the schedule's interval, beside the plan in device memory; k_brownian_fill (mdt_brownian.hip) reads them.
+struct mdt_tree_q {
+    double lo, hi;                        // the schedule's smallest positive and largest level
+    int32_t n, pad;                       // noise rows of the plan
+    float q[2 * MDT_SAMPLER_MAX_EVALS];   // (from, to) of row r at q[2 r], q[2 r + 1]
+};
+
+// lo / hi of a schedule of `levels` levels (the reference's sigma_min = smallest positive level, sigma_max = largest)
+MDT_HD inline void mdt_tree_interval(const float* sig, int levels, double* lo, double* hi) {
+    float l = INFINITY, h = -INFINITY;
+    for (int i = 0; i < levels; ++i) {
+        if (sig[i] > 0.f && sig[i] < l) l = sig[i];
+        if (sig[i] > h) h = sig[i];
+    }
+    *lo = l; *hi = h;
 }

@@ -14,6 +14,7 @@ callback=None, disable=None, ...)``.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 from contextlib import nullcontext
@@ -250,21 +251,31 @@ def _ancestral_draws(sigmas, eta):
     return sum(1 for i in range(n) if get_ancestral_step(sig[i], sig[i + 1], eta=eta)[0] > 0)
 
 
-def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, extra_args=None, **params):
+def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, extra_args=None, tree=None, **params):
     """The native call, replayed as a HIP graph by sample_ddim's rule (rollout-sized batches from the third identical call).
     ``n_steps``: dpm_fast's evaluation count (its schedule is the two levels, which join the graph key with it).  ``extra_args``:
-    the sampler's, which _native_ok admitted -- a guidance weight joins the parameters (and with them the graph key)."""
+    the sampler's, which _native_ok admitted -- a guidance weight joins the parameters (and with them the graph key).  ``tree``
+    (dpmpp_sde, in place of ``noise``): (seeds, tol, lo, hi) of the Brownian tree the call draws from; (tol, lo, hi) join the
+    graph key and the seeds are the graph's per-call input."""
     lam = guidance(**(extra_args or {}))[1]
     if lam is not None:
         params = dict(params, cond_lambda=lam)
     tag = (kind, tuple(sorted(params.items())))
     if n_steps is not None:
         tag += (n_steps, tuple(float(v) for v in sigmas))
-    out = _graph_route(model, "_graphed_native", tag, (kind, params, n_steps), state, action, goal, sigmas,
-                       lambda sig: GraphedSampler(model, kind, params, state, action, goal, sig, noise, n_steps), f"sample_{kind}",
-                       noise=noise)
+    key = (kind, params, n_steps)
+    meta = None
+    if tree is not None:
+        noise, meta = tree[0], tuple(float(v) for v in tree[1:])
+        tag += (("tree",) + meta,)
+        key += (("tree",) + meta,)
+    out = _graph_route(model, "_graphed_native", tag, key, state, action, goal, sigmas,
+                       lambda sig: GraphedSampler(model, kind, params, state, action, goal, sig, noise, n_steps, tree=meta),
+                       f"sample_{kind}", noise=noise)
     if out is not None:
         return out
+    if tree is not None:
+        return model.sample_native(kind, state, action, goal, sigmas, tree=tree, **params)
     return model.sample_native(kind, state, action, goal, sigmas, noise=noise, n_steps=n_steps, **params)
 
 
@@ -590,17 +601,88 @@ def sample_dpmpp_2s_ancestral(model, state, action, goal, sigmas, scaler=None, e
 # ------------------------------------------------------------------------------------------------
 # DPM-Solver (fixed-step "fast" and adaptive) and DPM-Solver++ SDE      (reference gc_sampling.py:495-690,737-790,834-870)
 # ------------------------------------------------------------------------------------------------
+def _identity(x):
+    return x
+
+
+def _torchsde_available() -> bool:
+    import importlib.util
+    return importlib.util.find_spec("torchsde") is not None
+
+
+class NativeBrownianTreeNoiseSampler:
+    """The noise sampler of ``BrownianTreeNoiseSampler`` without torchsde: the library's virtual Brownian tree (include/mdt_hip.h
+    mdt_brownian_noise; the definition is in csrc/mdt_brownian.h), on the GPU for a GPU ``x`` and on the host for a CPU one.  The
+    reference's constructor and call: ``seed`` None draws one ``torch.randint(0, 2**63 - 1, [])`` from the default generator, an
+    int gives one tree for the whole tensor, a list of B ints one tree per sample (a sample's noise does not then depend on the
+    rest of the batch).  A call returns (W(to) - W(from)) / sqrt(|to - from|) of the transformed points, shaped like ``x``.  The
+    law is torchsde's; the values are not (another construction).  sample_dpmpp_sde runs such a sampler with the identity
+    ``transform`` inside its native call."""
+
+    def __init__(self, x, sigma_min, sigma_max, seed=None, transform=_identity, tol=1e-6):
+        self.transform = transform
+        t0, t1 = self._point(sigma_min), self._point(sigma_max)
+        self.sign = 1 if t0 < t1 else -1
+        self.lo, self.hi = (t0, t1) if t0 < t1 else (t1, t0)
+        seeds = [torch.randint(0, 2 ** 63 - 1, []).item()] if seed is None else ([seed] if isinstance(seed, int) else list(seed))
+        self.batched = not (seed is None or isinstance(seed, int))
+        self.seeds = [int(s) for s in seeds]
+        self.tol = float(tol)
+        self.shape, self.dtype, self.device = tuple(x.shape), x.dtype, x.device
+        if self.batched and (x.ndim == 0 or len(self.seeds) != x.shape[0]):
+            raise ValueError(f"NativeBrownianTreeNoiseSampler: {len(self.seeds)} seeds for a batch of {tuple(x.shape)[:1]}")
+        if any(not 0 <= s < 2 ** 64 for s in self.seeds):
+            raise ValueError("NativeBrownianTreeNoiseSampler: seeds must be in [0, 2**64)")
+        self.batch = len(self.seeds) if self.batched else 1
+        self.per_row = max(1, x.numel() // self.batch)
+        self._dev_seeds = None
+        _lib.brownian_noise_host(self.seeds, self.lo, self.hi, self.tol, [], self.batch, self.per_row)  # the checks, no values
+
+    def _point(self, v):
+        return float(self.transform(torch.as_tensor(v)))
+
+    def seeds_on(self, device):
+        """The seeds as the int64 device tensor the library reads (bit pattern of the unsigned keys)."""
+        if self._dev_seeds is None or self._dev_seeds.device != device:
+            vals = [s - 2 ** 64 if s >= 2 ** 63 else s for s in self.seeds]
+            self._dev_seeds = torch.tensor(vals, dtype=torch.int64, device=device)
+        return self._dev_seeds
+
+    def native_tree(self, device):
+        """(seeds, tol, lo, hi) for GCDenoiser.sample_native's ``tree``, or None where the call cannot walk this sampler's trees
+        (a transform other than the identity, a reversed interval, another device)."""
+        if self.transform is not _identity or self.sign != 1 or torch.device(device) != self.device:
+            return None
+        return self.seeds_on(self.device), self.tol, self.lo, self.hi
+
+    def __call__(self, sigma, sigma_next):
+        pair = [self._point(sigma), self._point(sigma_next)]
+        if self.device.type == "cuda":
+            lib = _lib.load()
+            out = torch.empty((1, self.batch, self.per_row), device=self.device, dtype=torch.float32)
+            pr = (ctypes.c_double * 2)(*pair)
+            _lib.check(lib.mdt_brownian_noise(self.seeds_on(self.device).data_ptr(), len(self.seeds), self.lo, self.hi, self.tol,
+                                              pr, 1, self.batch, self.per_row, out.data_ptr(),
+                                              torch.cuda.current_stream(self.device).cuda_stream))
+        else:
+            out = torch.from_numpy(_lib.brownian_noise_host(self.seeds, self.lo, self.hi, self.tol, [pair], self.batch,
+                                                            self.per_row))
+        out = out.view(self.shape)
+        return (out if self.sign == 1 else -out).to(self.dtype)
+
+
 class BrownianTreeNoiseSampler:
     """Noise sampler backed by torchsde.BrownianTree (reference gc_sampling.py:112-160), the default of
-    ``sample_dpmpp_sde``.  torchsde is an optional dependency, exactly as in the reference: without it, pass your own
-    ``noise_sampler(sigma, sigma_next)``."""
+    ``sample_dpmpp_sde``.  torchsde is an optional dependency, as in the reference; without it the constructor returns a
+    ``NativeBrownianTreeNoiseSampler`` (the same law from the library's own tree)."""
 
-    def __init__(self, x, sigma_min, sigma_max, seed=None, transform=lambda x: x):
-        try:
-            import torchsde
-        except ImportError as e:  # pragma: no cover - environment dependent
-            raise ImportError("BrownianTreeNoiseSampler needs torchsde (as the reference does); pass noise_sampler=... "
-                              "to sample_dpmpp_sde instead") from e
+    def __new__(cls, x, sigma_min, sigma_max, seed=None, transform=_identity):
+        if not _torchsde_available():
+            return NativeBrownianTreeNoiseSampler(x, sigma_min, sigma_max, seed=seed, transform=transform)
+        return super().__new__(cls)
+
+    def __init__(self, x, sigma_min, sigma_max, seed=None, transform=_identity):
+        import torchsde
         self.transform = transform
         t0, t1 = self.transform(torch.as_tensor(sigma_min)), self.transform(torch.as_tensor(sigma_max))
         self.sign = 1 if t0 < t1 else -1
@@ -920,8 +1002,20 @@ class DPMSolver(torch.nn.Module):
 def sample_dpmpp_sde(model, state, action, goal, sigmas, extra_args=None, callback=None, disable=None, eta=1., s_noise=1.,
                      scaler=None, noise_sampler=None, r=1 / 2):
     """DPM-Solver++ (stochastic) (reference gc_sampling.py:737-790): a midpoint evaluation at s = t + r h, ancestral
-    noise at both sub-steps from ``noise_sampler(sigma, sigma_next)`` (default: a torchsde Brownian tree)."""
+    noise at both sub-steps from ``noise_sampler(sigma, sigma_next)`` (default: a torchsde Brownian tree, or without torchsde
+    the library's own, NativeBrownianTreeNoiseSampler).  On the native path that tree -- the default without torchsde, or a
+    NativeBrownianTreeNoiseSampler with the identity transform on the model's device -- is walked inside the call
+    (mdt_sample_sde_tree): no noise on the host and no read-back of a device schedule."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
+        tree = None
+        if noise_sampler is None and not _torchsde_available():  # the default's one seed draw, as its constructor makes it
+            seed = torch.randint(0, 2 ** 63 - 1, []).item()
+            tree = (torch.tensor([seed], dtype=torch.int64, device=action.device), 1e-6, 0., 0.)
+        elif isinstance(noise_sampler, NativeBrownianTreeNoiseSampler):
+            tree = noise_sampler.native_tree(action.device)
+        if tree is not None:
+            return _run_native("dpmpp_sde", model, state, action, goal, sigmas, None, eta=eta, s_noise=s_noise, r=r,
+                               extra_args=extra_args, tree=tree)
         sig = _host(sigmas)  # the noise sampler takes host values (a device schedule is read back for it)
         if noise_sampler is None:
             noise_sampler = BrownianTreeNoiseSampler(action, sig[sig > 0].min(), sig.max())

@@ -161,15 +161,21 @@ class GraphedSampler(GraphedDDIM):
     the other inputs, so a replay consumes the same random stream as the eager call."""
 
     def __init__(self, model, kind: str, params: dict, state: dict, x_T: torch.Tensor, goal: torch.Tensor,
-                 sigmas: torch.Tensor, noise: Optional[torch.Tensor], n_steps: Optional[int] = None):
+                 sigmas: torch.Tensor, noise: Optional[torch.Tensor], n_steps: Optional[int] = None, tree: Optional[tuple] = None):
         self.kind, self.params, self.n_steps = kind, dict(params), n_steps  # n_steps: dpm_fast's evaluation count
+        # tree: (tol, lo, hi) of a dpmpp_sde call that draws Brownian-tree noise inside (GCDenoiser.sample_native's ``tree``); its
+        # seeds are then the static input `noise` -- copied in per call, so that a replay walks the new call's trees
+        self.tree = None if tree is None else tuple(float(v) for v in tree)
         self._noise = None if noise is None else noise.detach().clone()
         super().__init__(model, state, x_T, goal, sigmas)
 
     def _call_key(self):
-        return (self.kind, self.params, self.n_steps)
+        return (self.kind, self.params, self.n_steps) + (() if self.tree is None else (("tree",) + self.tree,))
 
     def _run(self):
+        if self.tree is not None:
+            return self.model.sample_native(self.kind, self._static_state, self._x, self._goal, self._sig,
+                                            tree=(self._noise,) + self.tree, **self.params)
         return self.model.sample_native(self.kind, self._static_state, self._x, self._goal, self._sig, noise=self._noise,
                                         n_steps=self.n_steps, **self.params)
 

@@ -197,16 +197,26 @@ class GCDenoiser(nn.Module):
         return self._engine(state=state).denoise_vjp(state, action, im._goals(goal, False), sigma, v)
 
     @torch.no_grad()
-    def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, cond_lambda=None, **params):
+    def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, cond_lambda=None, tree=None, **params):
         """One of the other samplers (``kind``: 'euler', 'heun', 'dpmpp_2m', ... -- the gc_sampling function name without
         'sample_') as one enqueue on the current stream (mdt_sample).  ``noise``: None or (n_noise, B, Ta, A) in the Python loop's
         draw order -- raw randn draws (euler / heun / dpm_2 / the ancestral samplers) or the noise_sampler values (dpmpp_2s_ancestral,
         dpmpp_sde); s_noise and the step scales are applied inside.  ``params``: the sampler's keyword arguments (eta, s_churn,
         s_tmin, s_tmax, s_noise, r, order).  'dpm_fast': ``sigmas`` is [sigma_max, sigma_min] and ``n_steps`` the evaluation
         count.  ``cond_lambda``: classifier-free guidance weight (None or 1: the unguided call; include/mdt_hip.h
-        mdt_sample_guided; _engine.guidance reads it)."""
+        mdt_sample_guided; _engine.guidance reads it).  ``tree`` ('dpmpp_sde' only, in place of ``noise``): (seeds, tol) or
+        (seeds, tol, lo, hi) -- the Brownian tree the call draws its noise rows from (mdt_sample_sde_tree): ``seeds`` an int64
+        tensor of 1 or B keys on the model's device, ``lo`` < ``hi`` the tree's interval (default: the schedule's)."""
         from ... import _lib
         im = self.inner_model
+        if tree is not None:
+            if kind != "dpmpp_sde" or noise is not None or n_steps is not None:
+                raise ValueError("sample_native: tree noise is for 'dpmpp_sde' and takes no noise rows")
+            seeds, tol, lo, hi = (tuple(tree) + (0., 0.))[:4]
+            out, ctx = self._engine(state=state).sample_sde_tree(_lib.sampler_params(**params), state, action, im._goals(goal, False),
+                                                                 sigmas, seeds, tol, lo, hi, cond_lambda=cond_lambda)
+            im.latent_encoder_emb = ctx
+            return out
         out, ctx = self._engine(state=state).sample_native(_lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action,
                                                            im._goals(goal, False), sigmas, noise, n_steps=n_steps,
                                                            cond_lambda=cond_lambda)

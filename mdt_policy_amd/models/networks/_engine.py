@@ -51,6 +51,7 @@ _SAMPLER_ENTRIES = {
     "ddim": (("mdt_sample_ddim", "mdt_sample_ddim_guided"), ("mdt_sample_ddim_dev", "mdt_sample_ddim_dev_guided")),
     "plan": (("mdt_sample", "mdt_sample_guided"), ("mdt_sample_dev", "mdt_sample_dev_guided")),
     "dpm_adaptive": (("mdt_sample_dpm_adaptive", "mdt_sample_dpm_adaptive_guided"),),
+    "sde_tree": (("mdt_sample_sde_tree", "mdt_sample_sde_tree_guided"), ("mdt_sample_sde_tree_dev", "mdt_sample_sde_tree_dev_guided")),
 }
 
 
@@ -273,11 +274,11 @@ class HipEngine:
         return out, ctx
 
     def _sample(self, family: str, state: dict, x_T: torch.Tensor, goal: torch.Tensor, cond_lambda, lead=(), sigmas=None,
-                n_steps: Optional[int] = None, noise: Optional[torch.Tensor] = None, rows: bool = False, tail=()):
+                n_steps: Optional[int] = None, noise: Optional[torch.Tensor] = None, rows: bool = False, tail=(), tree=None):
         """The steps every sampler call shares: the inputs, the outputs, the schedule and the entry point of ``family``
         (_SAMPLER_ENTRIES).  The C arguments are the inputs, ``lead``, the schedule (if ``sigmas`` is given) and its count (one less
-        than the levels, or ``n_steps``), the noise rows (``rows``: None or (n_noise, B, Ta, A)), B, out, ctx, the weight of a
-        guided call, ``tail`` and the stream.  A device schedule is read in place (no copy to the host, no synchronisation)."""
+        than the levels, or ``n_steps``), the noise rows (``rows``: None or (n_noise, B, Ta, A)) or the tree (``tree``: an
+        _lib.BrownianSource), B, out, ctx, the weight of a guided call, ``tail`` and the stream.  A device schedule is read in place (no copy to the host, no synchronisation)."""
         lam = guidance(cond_lambda)[1]
         self.sync_params()
         tok, tok2, B = self._tokens(state)
@@ -299,6 +300,8 @@ class HipEngine:
             self._keep = (sig, nz)  # the kernels that read them are only enqueued: keep the (possibly converted) inputs alive
         if rows:
             lead += (_ptr(nz), 0 if nz is None else nz.shape[0])
+        if tree is not None:
+            lead += (C.byref(tree),)
         fn = self._entries[family][dev][lam is not None]
         self.ctx_generation += 1
         _lib.call(fn, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_), *lead, B, _ptr(out), _ptr(ctx),
@@ -319,6 +322,18 @@ class HipEngine:
         than the levels) or dpm_fast's evaluation count.  Like sample_ddim, a device schedule is read in place (no copy, no
         synchronisation).  ``cond_lambda`` (not None or 1): classifier-free guidance (mdt_sample_guided / mdt_sample_dev_guided)."""
         return self._sample("plan", state, x_T, goal, cond_lambda, (int(kind), C.byref(params)), sigmas, n_steps, noise, rows=True)
+
+    def sample_sde_tree(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, seeds: torch.Tensor, tol: float,
+                        lo: float = 0., hi: float = 0., cond_lambda: Optional[float] = None):
+        """dpmpp_sde with Brownian-tree noise drawn inside the call (mdt_sample_sde_tree / _dev / _guided / _dev_guided):
+        ``seeds`` an int64 tensor of 1 or B keys on the device, ``tol`` the tree's resolution, ``lo`` < ``hi`` its interval (0, 0:
+        the schedule's smallest positive and largest level).  Capture-safe like sample_native."""
+        if seeds.device != self.device or seeds.dtype != torch.int64 or not seeds.is_contiguous():
+            raise ValueError("sample_sde_tree: seeds must be a contiguous int64 tensor on the model's device")
+        src = _lib.BrownianSource(seeds.data_ptr(), int(seeds.numel()), 0, float(lo), float(hi), float(tol))
+        out = self._sample("sde_tree", state, x_T, goal, cond_lambda, (C.byref(params),), sigmas, tree=src)
+        self._keep = self._keep + (seeds, src)
+        return out
 
     def sample_dpm_adaptive(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigma_min: float, sigma_max: float,
                             cond_lambda: Optional[float] = None):
