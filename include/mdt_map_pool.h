@@ -47,7 +47,17 @@ mdt_status mdt_map_pool_load_param(mdt_map_pool *p, const char *name, const floa
 
 /* MAPBlock.forward(x) (transformer_blocks.py:787-791):
  *   x   : (B, N, embed_dim) tokens to pool, N <= 16
- *   out : (B, n_latents, output_dim)   (the reference squeezes dim 1 when n_latents == 1: same memory) */
+ *   out : (B, n_latents, output_dim)   (the reference squeezes dim 1 when n_latents == 1: same memory)
+ *
+ * How many tokens a call may have.  The attention runs one workgroup per sample with the sample's queries, keys,
+ * values and scores in LDS, within a 64 KiB budget.  With Q = n_latents, D = output_dim, H = 2 * n_heads, in bytes:
+ *   inference (mdt_map_pool_forward)       : 4 * (Q*D + 2*N*D + Q*H*N)        q, k|v, scores
+ *   training  (mdt_map_pool_forward_train) : 4 * (2*Q*D + 2*N*D + 2*Q*H*N)    + dO and dS for the backward
+ * A call whose budget exceeds 65536 bytes returns MDT_ERR_UNSUPPORTED before anything is enqueued.  The training
+ * budget is the larger one, so a shape can be ACCEPTED FOR INFERENCE AND REFUSED FOR TRAINING.  Example: n_latents 16,
+ * output_dim 256, n_heads 8, N = 16 needs exactly 65536 bytes for inference (accepted) and 98304 for training
+ * (refused); n_latents 16, output_dim 512, N = 16 is refused for both.  ClipStyleProjection's shape (one latent, 384
+ * channels, n_heads 8) fits with 16 tokens in both: 51712 and 54272 bytes. */
 mdt_status mdt_map_pool_forward(mdt_map_pool *p, const float *x, int64_t batch, int32_t n_tokens, float *out,
                                 void *stream);
 

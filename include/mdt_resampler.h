@@ -51,9 +51,21 @@ mdt_status mdt_resampler_load_param(mdt_resampler *r, const char *name, const fl
                                     void *stream);
 
 /* PerceiverResampler.forward(x_f, mask) (perceiver_resampler.py:124-162).
- *   x_f  : (B, T, n, dim) media tokens, T <= num_time_embeds frames of n tokens each; T*n + num_latents <= 4096
+ *   x_f  : (B, T, n, dim) media tokens, T <= num_time_embeds frames of n tokens each
  *   mask : (B, T) bytes (torch.bool) or NULL -- scales the frame's time embedding, as the reference does
- *   out  : (B, num_latents, dim) */
+ *   out  : (B, num_latents, dim)
+ *
+ * How many keys a call may have.  The attention runs one workgroup per (sample, head) with every score of that head
+ * in LDS, so the key count Tk = T*n + num_latents is bounded by 4096 AND by a 160 KiB LDS budget that depends on
+ * Q = num_latents, hd = dim_head and Tkp = Tk rounded up to a multiple of 4.  In bytes:
+ *   inference (mdt_resampler_forward)       : 4 * (Q*hd + Q*Tkp + 16 + 256*Q)        queries, scores, 1/sum, P.V partials
+ *   training  (mdt_resampler_forward_train) : 4 * (2*Q*hd + 2*Q*Tkp + 16 + 256*Q)    + dO and dS for the backward
+ * A call whose budget exceeds 163840 bytes returns MDT_ERR_UNSUPPORTED before anything is enqueued.  The training
+ * budget is the larger one, so a shape can be ACCEPTED FOR INFERENCE AND REFUSED FOR TRAINING: the taped forward
+ * refuses what its backward could not run.  Examples:
+ *   Q = 16, hd = 64 : inference up to 2236 keys, training up to 1084 keys
+ *   Q =  3, hd = 64 : 4096 keys in both (inference 52 KiB, training 101 KiB)
+ *   Q =  1          : 4096 keys in both */
 mdt_status mdt_resampler_forward(mdt_resampler *r, const float *x_f, const uint8_t *mask, int64_t batch,
                                  int32_t n_frames, int32_t n_tokens, float *out, void *stream);
 

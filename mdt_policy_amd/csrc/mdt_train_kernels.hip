@@ -1787,13 +1787,14 @@ hipError_t mdt_launch_attention_long_bwd(const float* q, int64_t ldq, const floa
 }
 
 // time_pos_emb gradient: out[t][d] = sum_{b, n} mask[b][t] * dxf[b][t][n][d], in two deterministic stages:
-//   partial[b*T + t][d] = mask * sum_n dxf[b][t][n][d]   (one workgroup per frame and 64 columns, 4 row groups)
+//   partial[b*T + t][d] = mask * sum_n dxf[b][t][n][d]   (one workgroup per frame and 64 columns, 4 row groups; the
+//                                                          frame on grid x: B*T may pass the 65536 a device reports for grid y)
 //   out[t][d] (+)= sum_b partial[b*T + t][d]              (k_colsum over the B rows of frame t, stride T*D)
 __global__ __launch_bounds__(256) void k_frame_sums(const float* __restrict__ dxf, const uint8_t* __restrict__ mask,
                                                     float* __restrict__ partial, int n, int D) {
     __shared__ float part[4][64];
-    const int64_t frame = blockIdx.y;
-    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
+    const int64_t frame = blockIdx.x;
+    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, c = blockIdx.y * 64 + cl;
     float acc = 0.f;
     if (c < D && (!mask || mask[frame])) {
         const float* base = dxf + frame * (int64_t)n * D + c;
@@ -1805,7 +1806,7 @@ __global__ __launch_bounds__(256) void k_frame_sums(const float* __restrict__ dx
 }
 hipError_t mdt_launch_time_emb_grad(const float* dxf, const uint8_t* mask, float* out, float* partial, int64_t B, int T, int n,
                                     int D, int accumulate, hipStream_t s) {
-    hipLaunchKernelGGL(k_frame_sums, dim3((D + 63) / 64, (unsigned)(B * T)), dim3(256), 0, s, dxf, mask, partial, n, D);
+    hipLaunchKernelGGL(k_frame_sums, dim3((unsigned)(B * T), (D + 63) / 64), dim3(256), 0, s, dxf, mask, partial, n, D);
     hipError_t e = hipGetLastError();
     for (int t = 0; t < T && e == hipSuccess; ++t)
         e = mdt_launch_colsum(partial + (int64_t)t * D, (int64_t)T * D, (int)B, D, out + (int64_t)t * D, accumulate, s);

@@ -1,7 +1,12 @@
 """Model configurations at the edges of what mdt_create accepts (embed_dim a multiple of 16 up to 512, head dims 16 / 32 / 48 /
 64, action_dim and action_seq_len 1..16, up to 16 context tokens, RoPE from head dim 32, both architectures).  Shared by the
 GPU envelope test (tests/test_gpu_config_envelope.py) and the CPU check that mdt_create's validation accepts every one of
-them (tests/test_cpu_abi.py)."""
+them (tests/test_cpu_abi.py).
+
+RESAMPLER_ENVELOPE and MAP_ENVELOPE do the same for the two other handle modules, the Perceiver resampler (mdt_resampler_*)
+and the MAP pooling block (mdt_map_pool_*): tests/test_gpu_module_envelope.py runs them, tests/test_cpu_abi.py checks the
+constructors' validation, tests/golden/make_golden.py g18 records the reference's results for the cases named in
+RESAMPLER_GOLDEN / MAP_GOLDEN."""
 from mdt_policy_amd import configs
 
 
@@ -31,3 +36,134 @@ ENVELOPE = {
     # the proprioceptive row at the context limit: goal + 14 state tokens + proprio = 16
     "proprio_ctx16": _case(configs.mdtv_default(proprio_dim=16, n_obs_token=14), proprio=True),
 }
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Perceiver resampler and MAP block.  The LDS budgets are restated here from the headers' text (include/mdt_resampler.h,
+# include/mdt_map_pool.h), NOT read from the library: a boundary the two disagree on is a finding.
+# ------------------------------------------------------------------------------------------------------------------
+RESAMPLER_LDS_BUDGET = 160 * 1024
+MAP_LDS_BUDGET = 64 * 1024
+
+
+def resampler_lds_bytes(num_latents, dim_head, keys, train):
+    """LDS of one (sample, head) workgroup of the resampler's attention: scaled queries (Q, hd), scores (Q, keys rounded up to
+    4), 16 reciprocal sums, (256 / hd) partial P.V sums of (Q, hd) = 256 * Q floats; training keeps dO beside the queries and
+    dS beside the scores."""
+    kp = (keys + 3) // 4 * 4
+    k = 2 if train else 1
+    return 4 * (k * num_latents * dim_head + k * num_latents * kp + 16 + 256 * num_latents)
+
+
+def map_lds_bytes(n_latents, output_dim, n_heads, tokens, train):
+    """LDS of one sample's workgroup of the MAP attention (2 * n_heads heads): q (Q, D), k|v (N, 2D), scores (Q, H, N);
+    training keeps dO beside q and dS beside the scores."""
+    H = 2 * n_heads
+    k = 2 if train else 1
+    return 4 * (k * n_latents * output_dim + 2 * tokens * output_dim + k * n_latents * H * tokens)
+
+
+def resampler_mask(kind, B, T):
+    """None, or a (B, T) list of 0/1.  "mixed": a pattern that differs per sample and frame, frame 2 masked in EVERY sample
+    (its time_pos_emb row gets an exactly zero gradient) and -- from two samples on -- sample 1 with every frame masked."""
+    if kind is None:
+        return None
+    assert kind == "mixed"
+    m = [[int((5 * b + 3 * t) % 4 != 0) for t in range(T)] for b in range(B)]
+    for b in range(B):
+        if T > 2:
+            m[b][2] = 0
+    if B > 1:
+        m[1] = [0] * T
+    return m
+
+
+def _r(dim, dim_head, heads, latents, T, n, batches, train_b, depth=1, ff_mult=1, time_embeds=None, mask=None, infer=True,
+       train=True):
+    """kwargs of PerceiverResampler; the (T frames, n tokens) to run; inference batches; the batch of the training step;
+    infer / train False: that entry point must refuse the shape (LDS budget)."""
+    kw = dict(dim=dim, depth=depth, dim_head=dim_head, heads=heads, num_latents=latents, num_time_embeds=time_embeds or T,
+              ff_mult=ff_mult)
+    return dict(kwargs=kw, T=T, n=n, batches=batches, train_b=train_b, mask=mask, infer=infer, train=train)
+
+
+_WIDE = dict(dim=512, dim_head=64, heads=2, latents=16, time_embeds=4)  # one model (16 latents x dim_head 64), many key counts
+
+RESAMPLER_ENVELOPE = {
+    # the smallest model: 2 keys (one media token + the latent), every loop at its first trip; B = 8200: media GEMM >= 8192 rows
+    "r_min_2keys": _r(16, 16, 1, 1, 1, 1, [1, 70, 8200], 3),
+    # inner = 48 < dim = 80, K|V product 96 wide, 7 latents, 262 keys (2 mod 4, one full stride + a clamped tail of 6), a frame
+    # masked everywhere and a sample masked entirely, more time embeddings than frames; B = 33: 8415 media / 231 latent rows
+    "r_inner_lt_dim": _r(80, 16, 3, 7, 5, 51, [1, 4, 33], 4, depth=2, ff_mult=3, time_embeds=6, mask="mixed"),
+    # dim 400: LayerNorm prologue at K not a multiple of 64 / 128, k_frame_sums' c < D guard (400 = 6 * 64 + 16); three unmasked
+    # frames of five time embeddings
+    "r_d400_hd32": _r(400, 32, 5, 4, 3, 37, [1, 5], 3, ff_mult=2, time_embeds=5),
+    # dim 208 = 3 * 64 + 16 with 9 latents (three queries per wave and one left over), masked
+    "r_d208_hd32": _r(208, 32, 2, 9, 4, 30, [1, 6], 3, ff_mult=3, mask="mixed"),
+    # 16 latents x dim_head 64 around the 256-key stride: 255 (3 mod 4, one short stride), 256 (exactly one), 257 (1 mod 4, a
+    # second stride of one key), 258 (2 mod 4), 512 (two full strides)
+    "r_wide_k255": _r(T=1, n=239, batches=[1, 3], train_b=2, **_WIDE),
+    "r_wide_k256": _r(T=2, n=120, batches=[1, 3], train_b=2, **_WIDE),
+    "r_wide_k257": _r(T=1, n=241, batches=[1, 3], train_b=2, **_WIDE),
+    "r_wide_k258": _r(T=2, n=121, batches=[1, 3], train_b=2, **_WIDE),
+    "r_wide_k512": _r(T=4, n=124, batches=[1, 3], train_b=2, **_WIDE),
+    # above 64 KiB of LDS in forward (83 KiB) and backward (149 KiB): 16 latents x 1000 keys, 8 heads, two layers, masked
+    "r_lds_k1000": _r(512, 64, 8, 16, 3, 328, [1, 3], 2, depth=2, mask="mixed"),
+    # the training boundary of (16 latents, dim_head 64): 1084 keys is the last shape the backward's budget holds ...
+    "r_wide_k1084_train_edge": _r(T=2, n=534, batches=[1, 2], train_b=2, **_WIDE),
+    # ... 1085 keys is refused for training and still runs (and is checked) for inference
+    "r_wide_k1085_infer_only": _r(T=1, n=1069, batches=[1, 2], train_b=2, train=False, **_WIDE),
+    # the inference boundary: 2236 keys is the last shape the forward's budget holds, 2237 is refused by both entry points
+    "r_wide_k2236_infer_edge": _r(T=1, n=2220, batches=[1, 2], train_b=1, train=False, **_WIDE),
+    "r_wide_k2237_refused": _r(T=1, n=2221, batches=[1], train_b=1, infer=False, train=False, **_WIDE),
+    # the top of the key range: 4096 keys x 3 latents; the forward stays under 64 KiB (52), only the backward (101 KiB) raises
+    # the limit; 4093 media tokens: 16 strides, the last clamped
+    "r_q3_k4096": _r(128, 64, 2, 3, 1, 4093, [1, 2], 2),
+}
+
+# recorded from the reference by make_golden.py g18: name -> batch of the fixture
+RESAMPLER_GOLDEN = {"r_min_2keys": 3, "r_inner_lt_dim": 4, "r_d400_hd32": 2, "r_wide_k257": 2, "r_lds_k1000": 2, "r_q3_k4096": 2}
+
+
+def _m(n_latents, embed_dim, n_heads, output_dim, mlp_ratio, tokens, batches, train_b, infer=True, train=True):
+    kw = dict(n_latents=n_latents, embed_dim=embed_dim, n_heads=n_heads, output_dim=output_dim, mlp_ratio=mlp_ratio)
+    return dict(kwargs=kw, N=tokens, batches=batches, train_b=train_b, infer=infer, train=train)
+
+
+MAP_ENVELOPE = {
+    # 16 latents x 16 tokens, no squeeze, 2 heads of 24 channels, embed_dim != output_dim, a fractional mlp_ratio that int()
+    # truncates (2.34 * 48 = 112.32 -> 112 = 7 * 16); B = 520: 8320 token rows and 8320 latent rows.
+    # (The ratio 2.5 gives mlp_hidden = 120, not a multiple of 16: that shape is MAP_REFUSED_AT_CREATE below.)
+    "m_q16_e96_d48": _m(16, 96, 1, 48, 2.34, 16, [1, 40, 520], 5),
+    # embed_dim 1024 > 512 into 48 channels, ONE token (softmax over a single key), 5 latents, 6 heads of 8
+    "m_q5_e1024_n1": _m(5, 1024, 3, 48, 1.0, 1, [1, 50, 330], 6),
+    # the smallest block: 16 channels everywhere, 2 latents, 7 tokens
+    "m_q2_min": _m(2, 16, 1, 16, 1.0, 7, [1, 33, 1200], 7),
+    # 64 heads of 8 channels at the width limit, mlp_hidden = 256 < output_dim, 3 latents x 9 tokens
+    "m_q3_e640_h32": _m(3, 640, 32, 512, 0.5, 9, [1, 24, 310], 4),
+    # head dim 3 (48 / 16 heads): channel loops that are not a multiple of 4
+    "m_hd3": _m(4, 64, 8, 48, 2.0, 5, [1, 30, 400], 5),
+    # head dim 1 (16 / 16 heads), 16 tokens
+    "m_hd1": _m(3, 32, 8, 16, 3.0, 16, [1, 30, 600], 5),
+    # exactly 65536 bytes of LDS for inference (accepted by <=), 98304 for training (refused)
+    "m_lds_edge_infer_only": _m(16, 256, 8, 256, 4.0, 16, [1, 20], 2, train=False),
+    # 16 latents x 512 channels x 16 tokens: 114688 bytes, refused for inference too
+    "m_refused": _m(16, 512, 8, 512, 1.0, 16, [1], 1, infer=False, train=False),
+}
+
+MAP_GOLDEN = {"m_q16_e96_d48": 3, "m_q5_e1024_n1": 4, "m_q2_min": 5, "m_q3_e640_h32": 3, "m_hd3": 3, "m_hd1": 3}
+
+# constructor arguments the libraries document as refused (include/mdt_resampler.h, include/mdt_map_pool.h) -> status
+# (1 = MDT_ERR_INVALID_ARG, 2 = MDT_ERR_UNSUPPORTED)
+_RBASE = dict(dim=64, depth=1, dim_head=16, heads=4, num_latents=2, num_time_embeds=1, ff_mult=4, activation=0)
+RESAMPLER_REFUSED_AT_CREATE = [
+    (dict(_RBASE, dim=24), 2), (dict(_RBASE, dim=528), 2), (dict(_RBASE, dim_head=48), 2), (dict(_RBASE, num_latents=0), 2),
+    (dict(_RBASE, num_latents=17), 2), (dict(_RBASE, activation=1), 2), (dict(_RBASE, ff_mult=0), 1),
+]
+_MBASE = dict(n_latents=1, embed_dim=128, output_dim=128, n_heads=8, mlp_hidden=512)
+MAP_REFUSED_AT_CREATE = [
+    (dict(_MBASE, output_dim=528, n_heads=1), 2), (dict(_MBASE, output_dim=48, n_heads=5), 1), (dict(_MBASE, mlp_hidden=120), 2),
+    # MAPBlock(16, 96, 1, 48, mlp_ratio=2.5): int(2.5 * 48) = 120
+    (dict(n_latents=16, embed_dim=96, output_dim=48, n_heads=1, mlp_hidden=120), 2),
+    (dict(_MBASE, n_latents=0), 2), (dict(_MBASE, n_latents=17), 2), (dict(_MBASE, embed_dim=100), 2),
+]

@@ -766,6 +766,72 @@ def g17():
         save(f"g17_loglik_{name}.npz", meta, ll=ll.numpy(), v=v.numpy())
 
 
+def save_fixed(name, meta, **arrays):
+    """save() with the archive's timestamps pinned, so that the same results give the same bytes."""
+    import io
+    import zipfile
+    path = os.path.join(HERE, name)
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k, v in [("meta", np.array(json.dumps(meta, sort_keys=True)))] + sorted(arrays.items()):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, v if np.ndim(v) == 0 else np.ascontiguousarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+    print(f"  wrote {name}: " + ", ".join(f"{k}{tuple(np.shape(v))}" for k, v in sorted(arrays.items())))
+
+
+def _grad_summaries(m):
+    grads = {}
+    for k, p in m.named_parameters():
+        g = p.grad.detach().double()
+        grads[k] = [float(g.norm()), float(g.sum())] + [float(v) for v in g.flatten()[:6]]
+    return grads
+
+
+def g18():
+    """The module envelope (tests/envelope_configs.py RESAMPLER_GOLDEN / MAP_GOLDEN): the reference's PerceiverResampler and
+    MAPBlock (constructed directly, not through ClipStyleProjection) at the edges of what the HIP modules accept.  Stored as
+    in g9 / g14: outputs, per-parameter gradient summaries, the head of the input gradient (all of it for the MAP block)."""
+    from mdt.models.networks.transformers.perceiver_resampler import PerceiverResampler
+    from mdt.models.networks.transformers.transformer_blocks import MAPBlock
+    from tests import envelope_configs as E
+
+    for name, B in E.RESAMPLER_GOLDEN.items():
+        c = E.RESAMPLER_ENVELOPE[name]
+        kw, T, n = c["kwargs"], c["T"], c["n"]
+        m = PerceiverResampler(**kw).eval()
+        sd = m.state_dict()
+        new = synthetic.fill_state_dict([(k, tuple(v.shape)) for k, v in sd.items()], 181, "rich")
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in new.items()}, strict=True)
+        x = torch.from_numpy(synthetic.normal("media", (B, T, n, kw["dim"]), 182)).requires_grad_()
+        mask = E.resampler_mask(c["mask"], B, T)
+        out = m(x, None if mask is None else torch.tensor(mask, dtype=torch.bool))
+        cot = torch.from_numpy(synthetic.normal("cotangent", tuple(out.shape), 183))
+        (out * cot).sum().backward()
+        dx = x.grad.detach()
+        meta = dict(kwargs=kw, B=B, T=T, n=n, mask=mask, weight_seed=181, input_seed=182, cot_seed=183, profile="rich",
+                    grads=_grad_summaries(m), d_x_summary=[float(dx.double().norm()), float(dx.double().sum())],
+                    state_dict=[[k, list(v.shape)] for k, v in sd.items()])
+        save_fixed(f"g18_resampler_{name}.npz", meta, out=out.detach().numpy(), d_x_head=dx[:, :, :4, :].numpy())
+
+    for name, B in E.MAP_GOLDEN.items():
+        c = E.MAP_ENVELOPE[name]
+        kw, N = c["kwargs"], c["N"]
+        m = MAPBlock(**kw)
+        sd = m.state_dict()
+        new = synthetic.fill_state_dict([(k, tuple(v.shape)) for k, v in sd.items()], 184, "rich")
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in new.items()}, strict=True)
+        x = torch.from_numpy(synthetic.normal("ctx", (B, N, kw["embed_dim"]), 185)).requires_grad_()
+        out = m(x)
+        cot = torch.from_numpy(synthetic.normal("cotangent", tuple(out.shape), 186))
+        (out * cot).sum().backward()
+        meta = dict(kwargs=kw, B=B, N=N, weight_seed=184, input_seed=185, cot_seed=186, profile="rich", grads=_grad_summaries(m),
+                    state_dict=[[k, list(v.shape)] for k, v in sd.items()])
+        save_fixed(f"g18_map_{name}.npz", meta, out=out.detach().numpy(), d_x=x.grad.numpy())
+
+
 def manifest():
     """state_dict names + shapes IN ORDER (the checkpoint / positional-EMA contract, evaluation/utils.py:98)."""
     out = {}
@@ -788,7 +854,7 @@ if __name__ == "__main__":
     assert os.path.isdir(REF), "this script needs the reference checkout at /root/reference"
     install_stubs()
     torch.manual_seed(0)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g10b", "g11", "g13", "g14", "g15", "g16", "g17", "manifest"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9", "g10", "g10b", "g11", "g13", "g14", "g15", "g16", "g17", "g18", "manifest"]
     for w in which:
         print(w)
         globals()[w]()

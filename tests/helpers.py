@@ -86,3 +86,40 @@ def perceiver_case(name):
                                           meta["input_seed"]))
     mask = None if meta["mask"] is None else torch.tensor(meta["mask"], dtype=torch.bool)
     return meta, fx, P, x, mask
+
+
+def envelope_params(shapes, seed):
+    return {k: torch.from_numpy(v) for k, v in synthetic.fill_state_dict([(k, tuple(s)) for k, s in shapes], seed, "rich").items()}
+
+
+def resampler_envelope_fixture(name):
+    """(meta, fixture arrays, params, media tokens, mask, cotangent) of a g18 resampler fixture (tests/envelope_configs.py)."""
+    meta, fx = load_fixture(f"g18_resampler_{name}.npz")
+    P = envelope_params(meta["state_dict"], meta["weight_seed"])
+    x = torch.from_numpy(synthetic.normal("media", (meta["B"], meta["T"], meta["n"], meta["kwargs"]["dim"]), meta["input_seed"]))
+    mask = None if meta["mask"] is None else torch.tensor(meta["mask"], dtype=torch.bool)
+    cot = torch.from_numpy(synthetic.normal("cotangent", tuple(fx["out"].shape), meta["cot_seed"]))
+    return meta, fx, P, x, mask, cot
+
+
+def map_envelope_fixture(name):
+    """(meta, fixture arrays, params, tokens, cotangent) of a g18 MAPBlock fixture."""
+    meta, fx = load_fixture(f"g18_map_{name}.npz")
+    P = envelope_params(meta["state_dict"], meta["weight_seed"])
+    x = torch.from_numpy(synthetic.normal("ctx", (meta["B"], meta["N"], meta["kwargs"]["embed_dim"]), meta["input_seed"]))
+    cot = torch.from_numpy(synthetic.normal("cotangent", tuple(fx["out"].shape), meta["cot_seed"]))
+    return meta, fx, P, x, cot
+
+
+def grad_summary(g):
+    g = g.detach().double().cpu()
+    return [float(g.norm()), float(g.sum())] + [float(v) for v in g.flatten()[:6]]
+
+
+def check_grad_summaries(named_grads, want, what):
+    """The oracle-vs-reference gate of test_perceiver.py / test_cla.py: each summary to 2e-3 of the gradient's norm."""
+    assert set(named_grads) == set(want), what
+    for k, w in want.items():
+        g, w = np.array(grad_summary(named_grads[k])), np.array(w)
+        tol = 2e-3 * abs(w[0]) + 1e-6
+        assert np.all(np.abs(g - w) <= tol), f"{what} {k}: {g} vs {w}"

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from mdt_policy_amd import _lib, configs
+from tests import envelope_configs as EC
 from tests.envelope_configs import ENVELOPE
 from tests.helpers import MANIFEST, load_fixture
 
@@ -67,6 +68,83 @@ def test_create_accepts_every_envelope_configuration(name):
     st = lib.mdt_create(C.byref(cfg), C.byref(h))
     assert st == 4 and not h.value, (name, st, lib.mdt_last_error())
     assert b"hipMalloc" in lib.mdt_last_error()
+
+
+
+def _resampler_config(kw):
+    from mdt_policy_amd.models.networks.transformers.perceiver_resampler import PerceiverResampler
+    return _lib.ResamplerConfig(**PerceiverResampler(**kw)._cfg)
+
+
+def _map_config(kw):
+    from mdt_policy_amd.models.networks.transformers.map_pool import MAPBlock
+    return _lib.MapPoolConfig(**MAPBlock(**kw)._cfg)
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="checks behaviour WITHOUT a GPU")
+@pytest.mark.parametrize("name", sorted(EC.RESAMPLER_ENVELOPE))
+def test_resampler_create_accepts_every_envelope_configuration(name):
+    """As above for mdt_resampler_create, with the config the facade builds from the case's constructor kwargs."""
+    lib = _lib.load()
+    cfg = _resampler_config(EC.RESAMPLER_ENVELOPE[name]["kwargs"])
+    h = C.c_void_p()
+    st = lib.mdt_resampler_create(C.byref(cfg), C.byref(h))
+    assert st == 4 and not h.value, (name, st, lib.mdt_last_error())
+    assert b"hipMalloc" in lib.mdt_last_error()
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="checks behaviour WITHOUT a GPU")
+@pytest.mark.parametrize("name", sorted(EC.MAP_ENVELOPE))
+def test_map_pool_create_accepts_every_envelope_configuration(name):
+    """As above for mdt_map_pool_create (the over-budget cases too: the LDS budget is a property of a call, not of the
+    constructor)."""
+    lib = _lib.load()
+    cfg = _map_config(EC.MAP_ENVELOPE[name]["kwargs"])
+    h = C.c_void_p()
+    st = lib.mdt_map_pool_create(C.byref(cfg), C.byref(h))
+    assert st == 4 and not h.value, (name, st, lib.mdt_last_error())
+    assert b"hipMalloc" in lib.mdt_last_error()
+
+
+def test_resampler_and_map_pool_create_refuse_what_their_headers_exclude_before_touching_the_device():
+    """Each documented constructor refusal comes back as MDT_ERR_INVALID_ARG / MDT_ERR_UNSUPPORTED (never 4 = MDT_ERR_HIP: the
+    validation runs before any allocation, with or without a GPU).  ff_mult * dim is a multiple of 16 whenever dim is, so the
+    only ff_mult the constructor can refuse is one below 1."""
+    lib = _lib.load()
+    for bad, status in EC.RESAMPLER_REFUSED_AT_CREATE:
+        h = C.c_void_p()
+        cfg = _lib.ResamplerConfig(**bad)
+        assert lib.mdt_resampler_create(C.byref(cfg), C.byref(h)) == status and not h.value, bad
+        assert lib.mdt_last_error()
+    for bad, status in EC.MAP_REFUSED_AT_CREATE:
+        h = C.c_void_p()
+        cfg = _lib.MapPoolConfig(**bad)
+        assert lib.mdt_map_pool_create(C.byref(cfg), C.byref(h)) == status and not h.value, bad
+        assert lib.mdt_last_error()
+    assert lib.mdt_resampler_create(None, None) == 1 and lib.mdt_map_pool_create(None, None) == 1
+    # the facade maps MAPBlock(16, 96, 1, 48, mlp_ratio=2.5) onto the refused mlp_hidden = 120
+    assert _map_config(dict(n_latents=16, embed_dim=96, n_heads=1, output_dim=48, mlp_ratio=2.5)).mlp_hidden == 120
+    from mdt_policy_amd.models.networks.transformers.perceiver_resampler import PerceiverResampler
+    with pytest.raises(NotImplementedError):
+        PerceiverResampler(dim=64, depth=1, activation="relu")
+
+
+@pytest.mark.parametrize("name", sorted(EC.RESAMPLER_GOLDEN))
+def test_resampler_facade_state_dict_matches_the_reference_at_the_envelope(name):
+    from mdt_policy_amd.models.networks.transformers.perceiver_resampler import PerceiverResampler
+    meta, _ = load_fixture(f"g18_resampler_{name}.npz")
+    m = PerceiverResampler(**meta["kwargs"])
+    assert [[k, list(v.shape)] for k, v in m.state_dict().items()] == meta["state_dict"]
+    assert [k for k, _ in m.named_parameters()] == [k for k, _ in meta["state_dict"]]
+
+
+@pytest.mark.parametrize("name", sorted(EC.MAP_GOLDEN))
+def test_map_block_facade_state_dict_matches_the_reference_at_the_envelope(name):
+    from mdt_policy_amd.models.networks.transformers.map_pool import MAPBlock
+    meta, _ = load_fixture(f"g18_map_{name}.npz")
+    m = MAPBlock(**meta["kwargs"])
+    assert [[k, list(v.shape)] for k, v in m.state_dict().items()] == meta["state_dict"]
+    assert [k for k, _ in m.named_parameters()] == [k for k, _ in meta["state_dict"]]
 
 
 def test_create_rejects_unsupported_configurations_before_touching_the_device():
