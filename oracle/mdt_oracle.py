@@ -106,11 +106,20 @@ def apply_rotary(t: Tensor, rot_dim: int) -> Tensor:
     return torch.cat((tr * cos + half * sin, rest), dim=-1)
 
 
+def _m(mask: Tensor, like: Tensor) -> Tensor:
+    return mask.to(device=like.device, dtype=like.dtype)
+
+
 def attention(P: Params, pre: str, x: Tensor, ctx: Optional[Tensor], n_heads: int, causal: bool,
-              use_rot: bool = False, trace: Optional[dict] = None) -> Tensor:
+              use_rot: bool = False, trace: Optional[dict] = None, masks=None, blk: int = 0) -> Tensor:
     """transformer_blocks.py:119-158.  q/k/v Linear with bias, heads split, softmax(q k^T / sqrt(hd) + mask),
     heads merged, c_proj (bias-less when cfg bias=False).  ``causal`` reproduces SDPA's is_causal=True,
-    i.e. a TOP-LEFT aligned lower-triangular mask even when Tq != Tk (cross attention, :204 + :142)."""
+    i.e. a TOP-LEFT aligned lower-triangular mask even when Tq != Tk (cross attention, :204 + :142).
+
+    ``masks`` (train mode; None: eval, nothing below changes): an object that hands out the dropout multipliers (0 or
+    1 / (1 - p)) of block ``blk`` -- attn / xattn(blk, B, Tq, Tk) -> (B, H, Tq, Tk) on the probabilities after the softmax
+    (SDPA's dropout_p, :142; attn_dropout, :152) and resid / xresid(blk, B, T) -> (B, T, C) on the c_proj output
+    (resid_dropout, :157); the x-forms belong to the cross attention."""
     B, T, C = x.shape
     src = x if ctx is None else ctx
     hd = C // n_heads
@@ -125,34 +134,43 @@ def attention(P: Params, pre: str, x: Tensor, ctx: Optional[Tensor], n_heads: in
         Tk = k.shape[-2]
         keep = torch.ones(T, Tk, dtype=torch.bool, device=att.device).tril()
         att = att.masked_fill(~keep, float("-inf"))
-    y = att.softmax(dim=-1) @ v
+    prob = att.softmax(dim=-1)
+    if masks is not None:
+        prob = prob * _m((masks.attn if ctx is None else masks.xattn)(blk, B, T, k.shape[-2]), prob)
+    y = prob @ v
     y = y.transpose(1, 2).reshape(B, T, C)
-    return _lin(P, pre + ".c_proj", y)
+    y = _lin(P, pre + ".c_proj", y)
+    if masks is not None:
+        y = y * _m((masks.resid if ctx is None else masks.xresid)(blk, B, T), y)
+    return y
 
 
-def mlp(P: Params, pre: str, x: Tensor) -> Tensor:
-    """transformer_blocks.py:161-180: c_fc -> exact-erf GELU -> c_proj."""
-    return _lin(P, pre + ".c_proj", F.gelu(_lin(P, pre + ".c_fc", x)))
+def mlp(P: Params, pre: str, x: Tensor, masks=None, blk: int = 0) -> Tensor:
+    """transformer_blocks.py:161-180: c_fc -> exact-erf GELU -> c_proj -> dropout (:179; ``masks``.mlp(blk, B, T))."""
+    y = _lin(P, pre + ".c_proj", F.gelu(_lin(P, pre + ".c_fc", x)))
+    if masks is not None:
+        y = y * _m(masks.mlp(blk, x.shape[0], x.shape[1]), y)
+    return y
 
 
-def block(P: Params, pre: str, x: Tensor, n_heads: int, use_rot: bool) -> Tensor:
+def block(P: Params, pre: str, x: Tensor, n_heads: int, use_rot: bool, masks=None, blk: int = 0) -> Tensor:
     """Encoder Block.forward (transformer_blocks.py:209-214), non-causal, no cross attention."""
-    x = x + attention(P, pre + ".attn", _ln(P, pre + ".ln_1", x), None, n_heads, False, use_rot)
-    x = x + mlp(P, pre + ".mlp", _ln(P, pre + ".ln_2", x))
+    x = x + attention(P, pre + ".attn", _ln(P, pre + ".ln_1", x), None, n_heads, False, use_rot, masks=masks, blk=blk)
+    x = x + mlp(P, pre + ".mlp", _ln(P, pre + ".ln_2", x), masks, blk)
     return x
 
 
 def conditioned_block(P: Params, pre: str, x: Tensor, c: Tensor, ctx: Tensor, n_heads: int, use_rot: bool,
-                      trace: Optional[dict] = None) -> Tensor:
+                      trace: Optional[dict] = None, masks=None, blk: int = 0) -> Tensor:
     """ConditionedBlock.forward (transformer_blocks.py:291-309) with AdaLNZero (:245-260) and
     modulate = shift + x*scale (:262, no '1 +')."""
     mod = F.linear(F.silu(c), P[pre + ".adaLN_zero.modulation.1.weight"], P[pre + ".adaLN_zero.modulation.1.bias"])
     sh1, sc1, g1, sh2, sc2, g2 = mod.chunk(6, dim=-1)
-    a = attention(P, pre + ".attn", sh1 + _ln(P, pre + ".ln_1", x) * sc1, None, n_heads, True, use_rot)
+    a = attention(P, pre + ".attn", sh1 + _ln(P, pre + ".ln_1", x) * sc1, None, n_heads, True, use_rot, masks=masks, blk=blk)
     x = x + g1 * a
-    xa = attention(P, pre + ".cross_att", _ln(P, pre + ".ln3", x), ctx, n_heads, True, use_rot)
+    xa = attention(P, pre + ".cross_att", _ln(P, pre + ".ln3", x), ctx, n_heads, True, use_rot, masks=masks, blk=blk)
     x = x + xa
-    m = mlp(P, pre + ".mlp", sh2 + _ln(P, pre + ".ln_2", x) * sc2)
+    m = mlp(P, pre + ".mlp", sh2 + _ln(P, pre + ".ln_2", x) * sc2, masks, blk)
     if trace is not None:
         trace[pre + ".mod"] = mod
         trace[pre + ".attn"] = a
@@ -164,20 +182,22 @@ def conditioned_block(P: Params, pre: str, x: Tensor, c: Tensor, ctx: Tensor, n_
     return x
 
 
-def noise_block(P: Params, pre: str, x: Tensor, c: Tensor, ctx: Tensor, n_heads: int, use_rot: bool) -> Tensor:
+def noise_block(P: Params, pre: str, x: Tensor, c: Tensor, ctx: Tensor, n_heads: int, use_rot: bool, masks=None,
+                blk: int = 0) -> Tensor:
     """NoiseBlock.forward (transformer_blocks.py:335-341): the sigma embedding is ADDED to the normalised input of
     the self- and cross-attention; the MLP branch is unconditioned; no gates."""
-    x = x + attention(P, pre + ".attn", _ln(P, pre + ".ln_1", x) + c, None, n_heads, True, use_rot)
-    x = x + attention(P, pre + ".cross_att", _ln(P, pre + ".ln3", x) + c, ctx, n_heads, True, use_rot)
-    x = x + mlp(P, pre + ".mlp", _ln(P, pre + ".ln_2", x))
+    x = x + attention(P, pre + ".attn", _ln(P, pre + ".ln_1", x) + c, None, n_heads, True, use_rot, masks=masks, blk=blk)
+    x = x + attention(P, pre + ".cross_att", _ln(P, pre + ".ln3", x) + c, ctx, n_heads, True, use_rot, masks=masks, blk=blk)
+    x = x + mlp(P, pre + ".mlp", _ln(P, pre + ".ln_2", x), masks, blk)
     return x
 
 
-def plain_decoder_block(P: Params, pre: str, x: Tensor, ctx: Tensor, n_heads: int, use_rot: bool) -> Tensor:
+def plain_decoder_block(P: Params, pre: str, x: Tensor, ctx: Tensor, n_heads: int, use_rot: bool, masks=None,
+                        blk: int = 0) -> Tensor:
     """Block.forward with cross attention, causal (TransformerDecoder, transformer_blocks.py:209-214,460-506)."""
-    x = x + attention(P, pre + ".attn", _ln(P, pre + ".ln_1", x), None, n_heads, True, use_rot)
-    x = x + attention(P, pre + ".cross_att", _ln(P, pre + ".ln3", x), ctx, n_heads, True, use_rot)
-    x = x + mlp(P, pre + ".mlp", _ln(P, pre + ".ln_2", x))
+    x = x + attention(P, pre + ".attn", _ln(P, pre + ".ln_1", x), None, n_heads, True, use_rot, masks=masks, blk=blk)
+    x = x + attention(P, pre + ".cross_att", _ln(P, pre + ".ln3", x), ctx, n_heads, True, use_rot, masks=masks, blk=blk)
+    x = x + mlp(P, pre + ".mlp", _ln(P, pre + ".ln_2", x), masks, blk)
     return x
 
 
@@ -206,12 +226,18 @@ def _prep_goal(cfg: dict, goal: Tensor, states_len: int) -> Tensor:
 
 
 def encode(P: Params, cfg: dict, state: dict, goal: Tensor, arch: str = "mdtv", entry: str = "forward",
-           trace: Optional[dict] = None, sigma: Optional[Tensor] = None) -> Tensor:
+           trace: Optional[dict] = None, sigma: Optional[Tensor] = None, masks=None) -> Tensor:
     """MDT-V: forward_enc_only (mdtv_transformer.py:213-222).  MDT: enc_only_forward (mdt_transformer.py:211-229,
     always goal_emb) when entry == 'forward', forward_enc_only (:257-281, honours modality) otherwise.
-    adaLN variants only (use_ada_conditioning=True): the encoder sees neither sigma nor the actions."""
+    adaLN variants only (use_ada_conditioning=True): the encoder sees neither sigma nor the actions.
+
+    ``masks`` (train mode): encoder block l is block l; the embedding dropout self.drop is masks.embed_ctx(B, Te, drop_lo)
+    -> (B, Te, D), Te counting every context row and the rows below drop_lo kept: MDT drops every embedded goal / state token
+    (mdt_transformer.py:220-224,320-321) but never the sigma token, MDT-V only the goal token it appends without goal
+    conditioning (mdtv_transformer.py:293-294)."""
     ada = cfg.get("use_ada_conditioning", False)
     assert ada or sigma is not None, "without adaLN conditioning the encoder needs sigma (its first token)"
+    t0 = 0 if ada else 1  # context rows in front of the embedded tokens: the sigma token
     modality = state.get("modality", "vis")
     H, rot = cfg["n_heads"], cfg.get("use_rot_embed", False)
     if arch == "mdtv":
@@ -227,6 +253,9 @@ def encode(P: Params, cfg: dict, state: dict, goal: Tensor, arch: str = "mdtv", 
             pe = _lin(P, "inner_model.proprio_emb.0", state["state_obs"].to(s.dtype))
             parts.append(_lin(P, "inner_model.proprio_emb.2", F.mish(pe)))
         elif not cfg.get("goal_conditioned", True):
+            if masks is not None:
+                Te = t0 + s.shape[1] + 1
+                g = g * _m(masks.embed_ctx(g.shape[0], Te, Te - 1)[:, Te - 1:], g)
             parts.append(g)
         h = torch.cat(parts, dim=1)
     else:
@@ -242,12 +271,14 @@ def encode(P: Params, cfg: dict, state: dict, goal: Tensor, arch: str = "mdtv", 
             s = s + pos[:, cfg["goal_seq_len"]: cfg["goal_seq_len"] + 1, :]
         # concatenate_inputs (mdt_transformer.py:326-334): without goal conditioning the goal never enters
         h = torch.cat([g, s], dim=1) if cfg.get("goal_conditioned", True) else s
+        if masks is not None:
+            h = h * _m(masks.embed_ctx(h.shape[0], t0 + h.shape[1], t0)[:, t0:], h)
     if not ada:  # concatenate_inputs: the sigma embedding is the FIRST encoder token (mdtv_transformer.py:296-297)
         h = torch.cat([sigma_embedding(P, cfg, sigma), h], dim=1)
     if trace is not None:
         trace["goal_embed"], trace["state_embed"] = g, s
     for l in range(cfg["n_enc_layers"]):
-        h = block(P, f"inner_model.encoder.blocks.{l}", h, H, rot)
+        h = block(P, f"inner_model.encoder.blocks.{l}", h, H, rot, masks, l)
         if trace is not None:
             trace[f"inner_model.encoder.blocks.{l}"] = h
     ctx = _ln(P, "inner_model.encoder.ln", h)
@@ -268,22 +299,27 @@ def sigma_embedding(P: Params, cfg: dict, sigma: Tensor) -> Tensor:
     return c[:, None, :]
 
 
-def decode(P: Params, cfg: dict, ctx: Tensor, x_in: Tensor, sigma: Tensor, trace: Optional[dict] = None) -> Tensor:
+def decode(P: Params, cfg: dict, ctx: Tensor, x_in: Tensor, sigma: Tensor, trace: Optional[dict] = None,
+           masks=None) -> Tensor:
     """forward_dec_only (mdtv_transformer.py:224-236; identical in mdt_transformer.py:231-242):
-    no positional embedding on the action tokens, TransformerFiLMDecoder (transformer_blocks.py:509-569)."""
+    no positional embedding on the action tokens, TransformerFiLMDecoder (transformer_blocks.py:509-569).
+    ``masks`` (train mode): self.drop on the embedded actions (mdtv_transformer.py:227, mdt_transformer.py:234) is
+    masks.embed_action(B, Ta); decoder block l is block n_enc_layers + l."""
     H, rot = cfg["n_heads"], cfg.get("use_rot_embed", False)
     c = sigma_embedding(P, cfg, sigma)
     y = _lin(P, "inner_model.action_emb", x_in)
+    if masks is not None:
+        y = y * _m(masks.embed_action(y.shape[0], y.shape[1]), y)
     if trace is not None:
         trace["sigma_emb"], trace["action_emb"] = c, y
     for l in range(cfg["n_dec_layers"]):
-        pre = f"inner_model.decoder.blocks.{l}"
+        pre, blk = f"inner_model.decoder.blocks.{l}", cfg["n_enc_layers"] + l
         if not cfg.get("use_ada_conditioning", False):
-            y = plain_decoder_block(P, pre, y, ctx, H, rot)
+            y = plain_decoder_block(P, pre, y, ctx, H, rot, masks, blk)
         elif cfg.get("use_noise_encoder", False):
-            y = noise_block(P, pre, y, c, ctx, H, rot)
+            y = noise_block(P, pre, y, c, ctx, H, rot, masks, blk)
         else:
-            y = conditioned_block(P, pre, y, c, ctx, H, rot, trace)
+            y = conditioned_block(P, pre, y, c, ctx, H, rot, trace, masks, blk)
     y = _ln(P, "inner_model.decoder.ln", y)
     if cfg.get("linear_output", True):
         out = _lin(P, "inner_model.action_pred", y)
@@ -318,20 +354,21 @@ def denoise(P: Params, cfg: dict, state: dict, x: Tensor, goal: Tensor, sigma: T
 
 
 def loss(P: Params, cfg: dict, state: dict, action: Tensor, goal: Tensor, noise: Tensor, sigma: Tensor,
-         sigma_data: float = 0.5, arch: str = "mdtv"):
-    """GCDenoiser.loss (score_wrappers.py:45-63), eval mode (no dropout / goal masking)."""
+         sigma_data: float = 0.5, arch: str = "mdtv", masks=None):
+    """GCDenoiser.loss (score_wrappers.py:45-63); eval mode (no dropout) unless ``masks`` hands out the multipliers of a
+    train-mode forward (see attention / encode / decode).  Goal masking (mask_cond) is the caller's: pass the masked goal."""
     c_skip, c_out, c_in = [s[:, None, None] for s in get_scalings(sigma, sigma_data)]
     noised = action + noise * sigma[:, None, None]
-    ctx = encode(P, cfg, state, goal, arch, "forward", sigma=sigma)
-    model_output = decode(P, cfg, ctx, noised * c_in, sigma)
+    ctx = encode(P, cfg, state, goal, arch, "forward", sigma=sigma, masks=masks)
+    model_output = decode(P, cfg, ctx, noised * c_in, sigma, masks=masks)
     target = (action - c_skip * noised) / c_out
     return (model_output - target).pow(2).flatten(1).mean(), model_output
 
 
 def forward_context_only(P: Params, cfg: dict, state: dict, goal: Tensor, arch: str = "mdtv",
-                         sigma: Optional[Tensor] = None) -> Tensor:
+                         sigma: Optional[Tensor] = None, masks=None) -> Tensor:
     """GCDenoiser.forward_context_only (score_wrappers.py:82-97) -> inner_model.forward_enc_only."""
-    return encode(P, cfg, state, goal, arch, "forward_enc_only", sigma=sigma)
+    return encode(P, cfg, state, goal, arch, "forward_enc_only", sigma=sigma, masks=masks)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -9,30 +9,8 @@ import pytest
 import torch
 
 from mdt_policy_amd import _lib
+from tests.dropout_masks import philox4
 from tests.helpers import load_fixture
-
-M32 = np.uint64(0xFFFFFFFF)
-
-
-def philox4(seed, site, ctr):
-    """The library's philox4(seed, site, ctr) (csrc/mdt_device.h) in uint64 arithmetic: Philox4x32-10 with counter
-    (ctr lo, ctr hi, site, 0x9e3779b9) and key (seed lo, seed hi).  ``site`` may be an array."""
-    site = np.asarray(site, dtype=np.uint64)
-    seed, ctr = np.uint64(seed), np.uint64(ctr)
-    c0 = np.full(site.shape, ctr & M32, dtype=np.uint64)
-    c1 = np.full(site.shape, ctr >> np.uint64(32), dtype=np.uint64)
-    c2 = site & M32
-    c3 = np.full(site.shape, 0x9E3779B9, dtype=np.uint64)
-    k0, k1 = seed & M32, seed >> np.uint64(32)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        n0 = (p1 >> np.uint64(32)) ^ c1 ^ k0
-        n2 = (p0 >> np.uint64(32)) ^ c3 ^ k1
-        c1, c3, c0, c2 = p1 & M32, p0 & M32, n0, n2
-        k0 = (k0 + np.uint64(0x9E3779B9)) & M32
-        k1 = (k1 + np.uint64(0xBB67AE85)) & M32
-    return c0, c1, c2, c3
 
 
 def normal(seed, e, node):

@@ -5,14 +5,16 @@ GPU's fp64 units; the oracles are the checkers, never the thing measured) and to
 
 B = 1024 reaches code the B <= 96 tests never do: 104 448 decoder rows of the head (other split-K slice counts, the 32 x 192
 tiles chosen for training-sized row counts, k_gemm_tn's deep reductions), 10 240 action rows of the denoiser, and the
-encoder gradient that arrives from BOTH losses through latent_encoder_emb.  Dropout is off (eval mode): the oracle has no
-counterpart of the library's Philox streams; everything else is the bench's step."""
+encoder gradient that arrives from BOTH losses through latent_encoder_emb.  The combined step runs twice: in eval mode, and in
+train mode with the shipped dropouts (what bench.py times), where the oracle replays the library's Philox masks
+(tests/dropout_masks.py) from the seed of every step."""
 import pytest
 import torch
 
 from mdt_policy_amd import synthetic
 from oracle import mae_oracle as MO
 from oracle import mdt_oracle as O
+from tests import dropout_masks as DM
 from tests.helpers import assert_close, cfg_of, inputs_of, load_fixture, params_of
 
 pytestmark = pytest.mark.gpu
@@ -85,6 +87,16 @@ def test_combined_c3_step_follows_the_oracles_for_three_adamw_steps():
     """(ii) the bench's step_c3, three times: losses of every step, every gradient of the first step (both modules: the
     encoder receives d_context from both losses), and the weights after three FusedAdamW steps against torch.optim.AdamW
     on the float64 oracles."""
+    _combined_c3_step("eval")
+
+
+def test_combined_c3_step_in_train_mode_follows_the_masked_oracles_for_three_adamw_steps():
+    """The same with model.train(): a fresh dropout seed per step (recorded from train_dropout), the denoiser's oracle
+    multiplying with the replayed masks of that seed in loss and context; same assertions, same tolerances."""
+    _combined_c3_step("train")
+
+
+def _combined_c3_step(mode):
     from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
     from mdt_policy_amd.optim import FusedAdamW
     meta, fx = load_fixture("g11_grads_mdtv_default.npz")
@@ -98,7 +110,15 @@ def test_combined_c3_step_follows_the_oracles_for_three_adamw_steps():
 
     model = GCDenoiser(cfg, 0.5)
     model.load_state_dict(params_of(meta))
-    model = model.cuda().eval()
+    model = model.cuda().train(mode == "train")
+    seeds, draw = [], model.inner_model.train_dropout
+
+    def train_dropout():   # the seed of every train-mode forward, in call order (None in eval mode)
+        d = draw()
+        seeds.append(int(d.seed) if d is not None else None)
+        return d
+
+    model.inner_model.train_dropout = train_dropout
     gen = _facade_head(kw, PH)
     opt = FusedAdamW(list(model.parameters()) + list(gen.parameters()), lr=lr, weight_decay=wd)
     gstate = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in state.items()}
@@ -127,8 +147,10 @@ def test_combined_c3_step_follows_the_oracles_for_three_adamw_steps():
         assert _hip_ops.SIDE_LAUNCHES > side0, step
 
         opt64.zero_grad(set_to_none=True)
-        lo, _ = O.loss(PD, cfg, st64, l64["actions"], g64, l64["noise_train"], l64["sigma"], arch=meta["arch"])
-        c64 = O.encode(PD, cfg, st64, g64, meta["arch"], "forward", sigma=l64["sigma"])
+        assert len(seeds) == step + 1 and (seeds[step] is None) == (mode == "eval")
+        masks = DM.Masks.of(seeds[step], cfg) if mode == "train" else None
+        lo, _ = O.loss(PD, cfg, st64, l64["actions"], g64, l64["noise_train"], l64["sigma"], arch=meta["arch"], masks=masks)
+        c64 = O.encode(PD, cfg, st64, g64, meta["arch"], "forward", sigma=l64["sigma"], masks=masks)
         r64, m64, _, _ = MO.forward(P64, kw, c64, i64, torch.argsort(noises[step], dim=1).to(dev))
         ao = MO.compute_loss(kw, i64, r64, m64)
         (lo + ao).backward()

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import dropout_masks as DM
 from tests.helpers import assert_close
 from tests.test_gpu_ops import dev, expected_pack, stream
 
@@ -517,3 +518,188 @@ def test_linear_backward_through_the_forward_gemm(lib, M, N, K):
     assert_close(dW.cpu() - dW0, ref_dW, what="dW", **tol)
     assert_close(dX.cpu() - dX0, ref_dX, what="dX", rtol=1e-3, atol=1e-4)
     assert_close(db.cpu(), dY.double().sum(0), what="dbias", rtol=1e-3, atol=1e-4 * max(1.0, (M / 64) ** 0.5))
+
+
+# ------------------------------------------------------------------------------------------------
+# the kernels' dropout masks against the restatement of tests/dropout_masks.py: the mask comes from numpy, never out of the
+# kernel under test, and the 0 / kept pattern is compared for equality (the keep rule is exact in fp32)
+# ------------------------------------------------------------------------------------------------
+MASK_SHAPES = [(64, 10, 384), (1024, 10, 384), (3, 7, 30), (2, 401, 384), (5, 7, 64), (2, 3, 1024)]   # (3, 7, 30): the scalar route
+MASK_SITES = [DM.site_id(0, DM.RESID), DM.site_id(9, DM.XRESID)]
+MASK_SEEDS = [123456789, 2 ** 40 + 12345]
+
+
+def assert_mask_equal(got, want, p, what):
+    """got: fp32 multipliers out of a kernel; want: float64 restatement.  Same zeros, kept value 1 / (1 - p) to fp32 rounding."""
+    got, want = got.detach().cpu().double(), torch.as_tensor(want).double().reshape(got.shape)
+    assert torch.equal(got != 0, want != 0), f"{what}: {int(((got != 0) != (want != 0)).sum())} of {got.numel()} mask elements differ"
+    kept = got[want != 0]
+    v = 1.0 / (1.0 - float(np.float32(p)))
+    assert kept.numel() > 0 and float((kept - v).abs().max()) <= 2.0 ** -23 * v, what
+
+
+@pytest.mark.parametrize("p", [0.05, 0.1])
+@pytest.mark.parametrize("B,rps,D", MASK_SHAPES)
+def test_merge_forward_mask_is_the_restated_mask(lib, B, rps, D, p):
+    zeros, ones = torch.zeros(B * rps, D, device="cuda"), torch.ones(B * rps, D, device="cuda")
+    seen = []
+    for site in MASK_SITES:
+        for seed in MASK_SEEDS:
+            out = torch.full((B * rps, D), float("nan"), device="cuda")
+            merge(lib, "mdt_op_merge_fwd", zeros, ones, None, out, None, B, rps, D, p=p, site=site, seed=seed)
+            assert_mask_equal(out, DM.scale(seed, site, (B * rps, D), p), p, f"site {site} seed {seed}")
+            seen.append(out.cpu() != 0)
+    assert not any(torch.equal(seen[0], o) for o in seen[1:])       # four different masks
+
+
+@pytest.mark.parametrize("p", [0.05, 0.1])
+@pytest.mark.parametrize("B,rps,D", MASK_SHAPES)
+def test_merge_backward_against_float64_with_the_restated_mask(lib, B, rps, D, p):
+    """mdt_op_merge_bwd: d_a = mask / (1 - p) * gate * d_x and d_gate = sum over the sample's rows of d_x * dropout(a)."""
+    site, seed = MASK_SITES[1], MASK_SEEDS[1]
+    x, a, gate, dx = rnd(B * rps, D, seed=81), rnd(B * rps, D, seed=82), rnd(B, D, seed=83), rnd(B * rps, D, seed=84)
+    mask = torch.from_numpy(DM.scale(seed, site, (B * rps, D), p))
+    a64, g64 = a.double().requires_grad_(), gate.double().requires_grad_()
+    y = x.double() + g64.repeat_interleave(rps, 0) * (a64 * mask)
+    y.backward(dx.double())
+    out, da, dg = (torch.full(t.shape, float("nan"), device="cuda") for t in (x, x, gate))
+    merge(lib, "mdt_op_merge_fwd", dev(x), dev(a), dev(gate), out, None, B, rps, D, p=p, site=site, seed=seed, ld=D)
+    merge(lib, "mdt_op_merge_bwd", dev(dx), dev(a), dev(gate), da, dg, B, rps, D, p=p, site=site, seed=seed, ld=D)
+    assert_close(out.cpu(), y.detach(), what="x + g drop(a)")
+    assert_close(da.cpu(), a64.grad, what="d_a", **G_TOL)
+    assert torch.equal(da.cpu() != 0, (a64.grad != 0))             # dropped elements get exactly no gradient
+    # (a sum of rps products of unit-variance values in fp32: the floor grows with sqrt(rps), as in the vector-kernel test above)
+    assert_close(dg.cpu(), g64.grad, rtol=1e-3, atol=2e-5 * max(1.0, (rps / 10) ** 0.5), what="d_gate")
+
+
+@pytest.mark.parametrize("p", [0.05, 0.1])
+@pytest.mark.parametrize("B,rps,D", MASK_SHAPES + [(2, 3, 512)])
+def test_fused_merge_layernorm_pair_against_float64_with_the_restated_mask(lib, B, rps, D, p):
+    """mdt_op_merge_ln_fwd and mdt_op_ln_bwd_merge (k_merge_ln_fwd4, k_ln_bwd4<true>; D = 30: the two-launch route inside them):
+    the merged rows, the LayerNorm output, the gradient of the merged rows and d_a / d_gate against float64 autograd.
+    The LayerNorm kernels hold a row in registers up to D = 512 (include/mdt_hip_train.h): D = 1024, which the merges alone take,
+    must be refused by both fused entry points with nothing written; (2, 3, 512) is the widest row they accept."""
+    L = lib.load()
+    M, site, seed = B * rps, MASK_SITES[0], MASK_SEEDS[1]
+    x, a, gate = rnd(M, D, seed=91), rnd(M, D, seed=92), rnd(B, D, seed=93)
+    w, b = 1 + 0.1 * rnd(D, seed=94), 0.1 * rnd(D, seed=95)
+    dh, dx0 = rnd(M, D, seed=96), rnd(M, D, seed=97)
+    mask = torch.from_numpy(DM.scale(seed, site, (M, D), p))
+    a64, g64 = a.double().requires_grad_(), gate.double().requires_grad_()
+    x1 = x.double() + g64.repeat_interleave(rps, 0) * (a64 * mask)
+    x1.retain_grad()
+    h = F.layer_norm(x1, (D,), w.double(), b.double(), 1e-5)
+    ((h * dh.double()).sum() + (x1 * dx0.double()).sum()).backward()     # dx0: the gradient the residual path already left on x1
+    xd, ad, gd, wd, bd = dev(x), dev(a), dev(gate), dev(w), dev(b)
+    x1d, hd_, st = (torch.full((M, n), float("nan"), device="cuda") for n in (D, D, 2))
+
+    def margs(xin, out, dgate=None):
+        return lib.MergeArgs(x=xin.data_ptr(), a=ad.data_ptr(), gate=gd.data_ptr(), gate_stride=D, out=out.data_ptr(),
+                             dgate=dgate.data_ptr() if dgate is not None else None, dgate_stride=D, B=B, rows_per_sample=rps, D=D,
+                             p=p, site=site, seed=seed)
+
+    mf = margs(xd, x1d)
+    lf = lib.LnTrainArgs(x=xd.data_ptr(), w=wd.data_ptr(), b=bd.data_ptr(), mod=None, mod_stride=0, shift_off=-1, scale_off=-1,
+                         rows_per_sample=rps, out=hd_.data_ptr(), stats=st.data_ptr(), M=M, D=D)
+    if D > 512:
+        dx, da = dev(dx0).clone(), torch.full((M, D), float("nan"), device="cuda")
+        g = lib.LnBwdArgs(x=xd.data_ptr(), stats=st.data_ptr(), w=wd.data_ptr(), b=bd.data_ptr(), mod=None, mod_stride=0, shift_off=-1,
+                          scale_off=-1, dh=dev(dh).data_ptr(), ld_dh=D, dx=dx.data_ptr(), accumulate=1, d_mod=None, d_mod_stride=0,
+                          pw=x1d.data_ptr(), pb=None, B=B, rows_per_sample=rps, D=D, row_chunks=0)
+        mg = margs(dx, da)
+        with pytest.raises(lib.MDTHipError, match="invalid argument"):
+            lib.check(L.mdt_op_merge_ln_fwd(C.byref(mf), C.byref(lf), stream()))
+        with pytest.raises(lib.MDTHipError, match="invalid argument"):
+            lib.check(L.mdt_op_ln_bwd_merge(C.byref(g), C.byref(mg), stream()))
+        torch.cuda.synchronize()
+        assert bool(x1d.isnan().all()) and bool(hd_.isnan().all()) and bool(da.isnan().all()) and torch.equal(dx.cpu(), dx0)
+        return
+    lib.check(L.mdt_op_merge_ln_fwd(C.byref(mf), C.byref(lf), stream()))
+    assert_close(x1d.cpu(), x1.detach(), what="merged rows")
+    assert_close(hd_.cpu(), h.detach(), what="LayerNorm of the merged rows")
+    dhd, dx = dev(dh), dev(dx0).clone()
+    da, dg = torch.full((M, D), float("nan"), device="cuda"), torch.full((B, D), float("nan"), device="cuda")
+    pw, pb = torch.empty(B, D, device="cuda"), torch.empty(B, D, device="cuda")
+    g = lib.LnBwdArgs(x=x1d.data_ptr(), stats=st.data_ptr(), w=wd.data_ptr(), b=bd.data_ptr(), mod=None, mod_stride=0, shift_off=-1,
+                      scale_off=-1, dh=dhd.data_ptr(), ld_dh=D, dx=dx.data_ptr(), accumulate=1, d_mod=None, d_mod_stride=0,
+                      pw=pw.data_ptr(), pb=pb.data_ptr(), B=B, rows_per_sample=rps, D=D, row_chunks=0)
+    mg = margs(dx, da, dg)
+    lib.check(L.mdt_op_ln_bwd_merge(C.byref(g), C.byref(mg), stream()))
+    assert_close(dx.cpu(), x1.grad, what="d_x1", **G_TOL)
+    assert_close(da.cpu(), a64.grad, what="d_a", **G_TOL)
+    assert torch.equal(da.cpu() != 0, (a64.grad != 0))
+    assert_close(dg.cpu(), g64.grad, rtol=1e-3, atol=2e-5 * max(1.0, (rps / 10) ** 0.5), what="d_gate")
+
+
+# Which kernel a case takes is decided by attn_train_mfma_group(hd, H, rope) (csrc/mdt_train_kernels.hip), not by the batch:
+# RoPE -> the scalar form k_attn_fwd_train / k_attn_bwd; otherwise the MFMA form with 4 heads per workgroup when H % 4 == 0, 2
+# when H % 2 == 0, else 1.          hd,  H, Tq, Tk, causal, rope
+MASKED_ATTN_CASES = [(48, 8, 10, 10, 1, 0),    # MFMA, 4 heads (the shipped model's self-attention)
+                     (48, 8, 10, 4, 1, 0),     # MFMA, 4 heads, rectangular (the shipped cross-attention)
+                     (16, 4, 4, 4, 0, 0),      # MFMA, 4 heads
+                     (32, 6, 10, 4, 1, 0),     # MFMA, 2 heads, rectangular
+                     (48, 8, 10, 10, 1, 1),    # scalar (RoPE)
+                     (32, 4, 10, 4, 1, 1),     # scalar (RoPE), rectangular
+                     (64, 2, 5, 16, 0, 1),     # scalar (RoPE), Tq < Tk
+                     # TRAIN_ATTN_EDGES: H odd -> MFMA 1 head; H = 6, 10 -> MFMA 2 heads; H = 32, 24, 16 -> MFMA 4 heads;
+                     # its last three (rope = 1) -> scalar
+                     ] + TRAIN_ATTN_EDGES
+assert {(r, 0 if r else (4 if H % 4 == 0 else 2 if H % 2 == 0 else 1)) for _, H, _, _, _, r in MASKED_ATTN_CASES} == \
+    {(1, 0), (0, 1), (0, 2), (0, 4)}
+assert all(any(r == rope and (Tq, Tk) == (10, 4) for _, _, Tq, Tk, _, r in MASKED_ATTN_CASES) for rope in (0, 1))
+
+
+@pytest.mark.parametrize("B", [5, 1024])
+@pytest.mark.parametrize("hd,H,Tq,Tk,causal,rope", MASKED_ATTN_CASES)
+def test_attention_dropout_against_float64_with_the_restated_mask(lib, hd, H, Tq, Tk, causal, rope, B):
+    """mdt_op_attn_fwd_train / mdt_op_attn_bwd at p = 0.3 with the (B, H, Tq, Tk) mask of the documented element index
+    ((b H + h) Tq + i) Tk + j: forward, dq, dk, dv against float64 attention.  B = 1024 is the grid of the benchmark's step."""
+    Dm, p, seed, site = H * hd, 0.3, 2 ** 41 + 987654321, DM.site_id(3, DM.XATTN)
+    L = lib.load()
+    rc, rs = _rope_tables()
+    q, kv, do = rnd(B * Tq, Dm, seed=51), rnd(B * Tk, 2 * Dm, seed=52), rnd(B * Tq, Dm, seed=53)
+    mask = torch.from_numpy(DM.scale(seed, site, (B, H, Tq, Tk), p))
+    split = lambda t, T: t.view(B, T, H, hd).transpose(1, 2)
+    q64 = q.double().requires_grad_()
+    k64, v64 = kv[:, :Dm].double().requires_grad_(), kv[:, Dm:].double().requires_grad_()
+    att = _rot(split(q64, Tq), rope) @ _rot(split(k64, Tk), rope).transpose(-1, -2) / hd ** 0.5
+    if causal:
+        att = att.masked_fill(~torch.ones(Tq, Tk, dtype=torch.bool).tril(), float("-inf"))
+    y = ((att.softmax(-1) * mask) @ split(v64, Tk)).transpose(1, 2).reshape(B * Tq, Dm)
+    y.backward(do.double())
+    qd, kvd, dod = dev(q), dev(kv), dev(do)
+    out = torch.full((B * Tq, Dm), float("nan"), device="cuda")
+    a = lib.AttnTrainArgs(q=qd.data_ptr(), ldq=Dm, k=kvd.data_ptr(), v=kvd.data_ptr() + 4 * Dm, ldkv=2 * Dm, out=out.data_ptr(),
+                          ldo=Dm, B=B, H=H, hd=hd, Tq=Tq, Tk=Tk, causal=causal, p=p, site=site, seed=seed, rope=rope,
+                          rope_cos=rc.data_ptr(), rope_sin=rs.data_ptr())
+    lib.check(L.mdt_op_attn_fwd_train(C.byref(a), stream()))
+    assert_close(out.cpu(), y.detach(), what="attention with dropout")
+    dq, dkv = torch.zeros(B * Tq, Dm, device="cuda"), torch.zeros(B * Tk, 2 * Dm, device="cuda")
+    g = lib.AttnBwdArgs(q=qd.data_ptr(), ldq=Dm, k=kvd.data_ptr(), v=kvd.data_ptr() + 4 * Dm, ldkv=2 * Dm, d_out=dod.data_ptr(),
+                        ld_do=Dm, dq=dq.data_ptr(), ld_dq=Dm, dk=dkv.data_ptr(), dv=dkv.data_ptr() + 4 * Dm, ld_dkv=2 * Dm,
+                        accumulate_kv=0, B=B, H=H, hd=hd, Tq=Tq, Tk=Tk, causal=causal, p=p, site=site, seed=seed, rope=rope,
+                        rope_cos=rc.data_ptr(), rope_sin=rs.data_ptr())
+    lib.check(L.mdt_op_attn_bwd(C.byref(g), stream()))
+    assert_close(dq.cpu(), q64.grad, what="dq", **G_TOL)
+    assert_close(dkv[:, :Dm].cpu(), k64.grad, what="dk", **G_TOL)
+    assert_close(dkv[:, Dm:].cpu(), v64.grad, what="dv", **G_TOL)
+
+
+@pytest.mark.parametrize("hd,H,Tq,Tk,rope", [(48, 8, 10, 4, 0), (32, 6, 10, 4, 0), (48, 5, 10, 4, 0), (32, 4, 10, 4, 1), (16, 4, 16, 16, 0)])
+def test_attention_mask_pattern_is_the_restated_mask(lib, hd, H, Tq, Tk, rope):
+    """The 0 / kept pattern itself, exactly: with every score equal (q = 0, no causal mask) and one-hot values, output column j
+    of head h and query i is mask[b, h, i, j] / Tk.  The expected pattern is the restatement's; nothing is read back to build it."""
+    B, Dm, p, seed, site = 64, H * hd, 0.3, 2 ** 33 + 5, DM.site_id(1, DM.ATTN)
+    rc, rs = _rope_tables()
+    kv = torch.zeros(B * Tk, 2 * Dm)
+    kv[:, Dm:] = torch.eye(Tk, hd).repeat(B, H)
+    qd, kvd = torch.zeros(B * Tq, Dm, device="cuda"), dev(kv)
+    out = torch.full((B * Tq, Dm), float("nan"), device="cuda")
+    a = lib.AttnTrainArgs(q=qd.data_ptr(), ldq=Dm, k=kvd.data_ptr(), v=kvd.data_ptr() + 4 * Dm, ldkv=2 * Dm, out=out.data_ptr(),
+                          ldo=Dm, B=B, H=H, hd=hd, Tq=Tq, Tk=Tk, causal=0, p=p, site=site, seed=seed, rope=rope,
+                          rope_cos=rc.data_ptr(), rope_sin=rs.data_ptr())
+    lib.check(lib.load().mdt_op_attn_fwd_train(C.byref(a), stream()))
+    got = out.cpu().view(B, Tq, H, hd)[..., :Tk].permute(0, 2, 1, 3) * Tk          # (B, H, Tq, Tk) multipliers
+    want = DM.scale(seed, site, (B, H, Tq, Tk), p)
+    assert torch.equal(got != 0, torch.from_numpy(want) != 0)
+    assert_close(got, want, rtol=1e-5, atol=0, what="kept probabilities")
