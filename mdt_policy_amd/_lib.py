@@ -320,6 +320,9 @@ SYMBOLS = [
     ("mdt_op_linear_bwd_scratch_exact", _I64, [_I64, _I64, _I64]),
     ("mdt_op_multi_adamw", _I32, [C.POINTER(OptTensor), _I32, _F, _F, _F, _F, _F, _I64, _VP]),
     ("mdt_op_multi_ema", _I32, [C.POINTER(OptTensor), _I32, _F, _VP]),
+    ("mdt_op_multi_sumsq_scratch", _I64, [C.POINTER(OptTensor), _I32]),
+    ("mdt_op_multi_sumsq", _I32, [C.POINTER(OptTensor), _I32, _I32, _VP, _VP, _I64, _VP]),
+    ("mdt_op_multi_adamw_dev", _I32, [C.POINTER(OptTensor), _I32, _F, _F, _F, _F, _F, _VP, _VP, _VP, _VP, _F, _VP, _VP]),
     # include/mdt_resampler.h
     ("mdt_resampler_create", _I32, [C.POINTER(ResamplerConfig), C.POINTER(_VP)]),
     ("mdt_resampler_destroy", _I32, [_VP]),

@@ -288,6 +288,14 @@ hipError_t mdt_launch_multi_adamw(const mdt_opt_tensor* tab, const int2* blocks,
                                   float beta2, float eps, float wd, float bc1, float bc2_sqrt, hipStream_t s);
 hipError_t mdt_launch_multi_axpby(const mdt_opt_tensor* tab, const int2* blocks, int n_blocks, float a, float b,
                                   hipStream_t s);
+// partial: 2 * n_blocks floats; out[0] = sum of squares of the g (which = 0) or p (1) members, out[1] = non-finite count
+hipError_t mdt_launch_multi_sumsq(const mdt_opt_tensor* tab, const int2* blocks, int n_blocks, int which, float* partial,
+                                  float* out, hipStream_t s);
+// k_opt_ctl writes ctl (4 floats, 16-byte aligned) from the device scalars, k_multi_adamw_dev reads it
+hipError_t mdt_launch_multi_adamw_dev(const mdt_opt_tensor* tab, const int2* blocks, int n_blocks, float lr, float beta1,
+                                      float beta2, float eps, float wd, float* step, const float* grad_scale,
+                                      const float* found_inf, const float* grad_sumsq, float max_norm, float* ctl,
+                                      float* grad_norm, hipStream_t s);
 // RMSNorm / SwishGLU row kernels (mdt_map_pool.hip), shared with the masked-image decoder's ops (mdt_mae.hip)
 hipError_t mdt_launch_rms_fwd(const float* x, const float* g, float* out, int64_t M, int D, float eps, hipStream_t s);
 hipError_t mdt_launch_rms_bwd(const float* x, const float* g, const float* dy, float* dx, int accumulate, float* pg, int64_t M,

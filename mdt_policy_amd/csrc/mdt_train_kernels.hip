@@ -1900,6 +1900,152 @@ hipError_t mdt_launch_multi_axpby(const mdt_opt_tensor* tab, const int2* blocks,
     return hipGetLastError();
 }
 
+// Sum of squares and non-finite count of the g (which = 0) or p (which = 1) members of a tensor list, without atomics:
+// k_multi_sumsq leaves one fp32 partial and one count per chunk (each thread its 16 elements in order, lane shuffles, then
+// the four waves through LDS), k_sumsq_finish adds them in a fixed order in double.  The same bits on every run.
+__global__ __launch_bounds__(256) void k_multi_sumsq(const mdt_opt_tensor* __restrict__ tab, const int2* __restrict__ blocks,
+                                                     int which, float* __restrict__ partial, int n_blocks) {
+    const int2 blk = blocks[blockIdx.x];
+    const mdt_opt_tensor t = tab[blk.x];
+    const float* __restrict__ x = which ? t.p : t.g;
+    const int64_t end = min((int64_t)blk.y + OPT_CHUNK, t.numel);
+    float acc = 0.f, bad = 0.f;  // at most 4096 per chunk: exact in fp32
+    auto add = [&](float v) {
+        acc = fmaf(v, v, acc);
+        bad += (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u ? 1.f : 0.f;  // inf or nan
+    };
+    if (end - blk.y == OPT_CHUNK && ((uintptr_t)x & 15) == 0) {
+        const f32x4* x4 = (const f32x4*)(x + blk.y);
+        f32x4 xv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) xv[k] = x4[threadIdx.x + 256 * k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) add(xv[k][e]);
+    } else {
+        for (int64_t i = (int64_t)blk.y + threadIdx.x; i < end; i += 256) add(x[i]);
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        acc += __shfl_down(acc, off, 64);
+        bad += __shfl_down(bad, off, 64);
+    }
+    __shared__ float part[2][4];
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = acc; part[1][threadIdx.x >> 6] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
+        partial[n_blocks + blockIdx.x] = (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]);
+    }
+}
+
+// out[0] = sum of the n_blocks partials, out[1] = sum of the counts: thread i adds entries i, i + 256, ... in index order,
+// then a fixed binary tree over the 256 threads, all in double
+__global__ __launch_bounds__(256) void k_sumsq_finish(const float* __restrict__ partial, int n_blocks, float* __restrict__ out) {
+    __shared__ double s[2][256];
+    double a = 0.0, b = 0.0;
+    for (int i = threadIdx.x; i < n_blocks; i += 256) { a += (double)partial[i]; b += (double)partial[n_blocks + i]; }
+    s[0][threadIdx.x] = a; s[1][threadIdx.x] = b;
+    __syncthreads();
+    for (int w = 128; w; w >>= 1) {
+        if ((int)threadIdx.x < w) { s[0][threadIdx.x] += s[0][threadIdx.x + w]; s[1][threadIdx.x] += s[1][threadIdx.x + w]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { out[0] = (float)s[0][0]; out[1] = (float)s[1][0]; }
+}
+
+hipError_t mdt_launch_multi_sumsq(const mdt_opt_tensor* tab, const int2* blocks, int n_blocks, int which, float* partial,
+                                  float* out, hipStream_t s) {
+    if (n_blocks > 0) hipLaunchKernelGGL(k_multi_sumsq, dim3(n_blocks), dim3(256), 0, s, tab, blocks, which, partial, n_blocks);
+    hipLaunchKernelGGL(k_sumsq_finish, dim3(1), dim3(256), 0, s, partial, n_blocks, out);
+    return hipGetLastError();
+}
+
+// The control block of one mdt_op_multi_adamw_dev call, ctl = {skip, bc1, sqrt(bc2), g_mult}, from device scalars: the AMP
+// protocol's found_inf / grad_scale, the step counter (advanced here unless the step is skipped) and the sum of squares of the
+// still-scaled gradients.  One thread; the bias corrections in double as mdt_op_multi_adamw forms them on the host, the
+// clip factor as torch.nn.utils.clip_grad_norm_ does.
+__global__ void k_opt_ctl(float* __restrict__ step, const float* __restrict__ grad_scale, const float* __restrict__ found_inf,
+                          const float* __restrict__ grad_sumsq, float max_norm, float beta1, float beta2,
+                          float* __restrict__ ctl, float* __restrict__ grad_norm) {
+    if (threadIdx.x != 0) return;
+    const bool skip = found_inf != nullptr && !(*found_inf == 0.f);
+    const float t = skip ? *step : *step + 1.0f;
+    const float inv_scale = grad_scale ? (float)(1.0 / (double)*grad_scale) : 1.0f;
+    double coef = 1.0;
+    if (grad_sumsq) {
+        const double norm = sqrt((double)*grad_sumsq) * (double)inv_scale;  // of the unscaled gradients
+        if (grad_norm) *grad_norm = (float)norm;
+        if (max_norm > 0.f) coef = fmin(1.0, (double)max_norm / (norm + 1e-6));
+    }
+    const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
+    f32x4 c;
+    c[0] = skip ? 1.f : 0.f; c[1] = (float)bc1; c[2] = (float)sqrt(bc2); c[3] = (float)((double)inv_scale * coef);
+    *(f32x4*)ctl = c;
+    if (!skip) *step = t;
+}
+
+// k_multi_adamw with g * g_mult in place of g and the bias corrections from the control block; nothing is written when
+// ctl says skip.  Reads ctl only, never the step counter k_opt_ctl stores to.
+__global__ __launch_bounds__(256) void k_multi_adamw_dev(const mdt_opt_tensor* __restrict__ tab, const int2* __restrict__ blocks,
+                                                         float lr, float beta1, float beta2, float eps, float wd,
+                                                         const float* __restrict__ ctl) {
+    const f32x4 c = *(const f32x4*)ctl;
+    if (c[0] != 0.f) return;  // uniform over the grid
+    const float bc1 = c[1], bc2_sqrt = c[2], g_mult = c[3];
+    const int2 blk = blocks[blockIdx.x];
+    const mdt_opt_tensor t = tab[blk.x];
+    const int64_t end = min((int64_t)blk.y + OPT_CHUNK, t.numel);
+    const float step_size = lr / bc1;
+    if (end - blk.y == OPT_CHUNK && ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15) == 0)) {
+        f32x4 *p4 = (f32x4*)(t.p + blk.y), *m4 = (f32x4*)(t.m + blk.y), *v4 = (f32x4*)(t.v + blk.y);
+        const f32x4* g4 = (const f32x4*)(t.g + blk.y);
+        f32x4 pv[4], gv[4], mv[4], vv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = threadIdx.x + 256 * k;
+            pv[k] = p4[i]; gv[k] = g4[i]; mv[k] = m4[i]; vv[k] = v4[i];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = threadIdx.x + 256 * k;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float g = gv[k][e] * g_mult;
+                float p = pv[k][e] * (1.0f - lr * wd);
+                const float m = fmaf(beta1, mv[k][e], (1.0f - beta1) * g);
+                const float v = fmaf(beta2, vv[k][e], (1.0f - beta2) * g * g);
+                p -= step_size * (m / (sqrtf(v) / bc2_sqrt + eps));
+                pv[k][e] = p; mv[k][e] = m; vv[k][e] = v;
+            }
+            p4[i] = pv[k]; m4[i] = mv[k]; v4[i] = vv[k];
+        }
+        return;
+    }
+    for (int64_t i = (int64_t)blk.y + threadIdx.x; i < end; i += 256) {
+        const float g = t.g[i] * g_mult;
+        float p = t.p[i] * (1.0f - lr * wd);
+        const float m = fmaf(beta1, t.m[i], (1.0f - beta1) * g);
+        const float v = fmaf(beta2, t.v[i], (1.0f - beta2) * g * g);
+        const float denom = sqrtf(v) / bc2_sqrt + eps;
+        p -= step_size * (m / denom);
+        t.m[i] = m; t.v[i] = v; t.p[i] = p;
+    }
+}
+
+hipError_t mdt_launch_multi_adamw_dev(const mdt_opt_tensor* tab, const int2* blocks, int n_blocks, float lr, float beta1,
+                                      float beta2, float eps, float wd, float* step, const float* grad_scale,
+                                      const float* found_inf, const float* grad_sumsq, float max_norm, float* ctl,
+                                      float* grad_norm, hipStream_t s) {
+    // the prologue runs for an empty list too: the step counter belongs to the call, not to its tensors
+    hipLaunchKernelGGL(k_opt_ctl, dim3(1), dim3(64), 0, s, step, grad_scale, found_inf, grad_sumsq, max_norm, beta1, beta2, ctl,
+                       grad_norm);
+    if (n_blocks > 0)
+        hipLaunchKernelGGL(k_multi_adamw_dev, dim3(n_blocks), dim3(256), 0, s, tab, blocks, lr, beta1, beta2, eps, wd, ctl);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // k_gemm_tn: the weight gradient  dW[n][k] = sum_m dY[m][n] * X[m][k]  straight from the two row-major operands --
 // no transposed copy of dY, no packed copy of X^T (those were 0.64 ms of a 12.7 ms B = 1024 step and 6 ms of the

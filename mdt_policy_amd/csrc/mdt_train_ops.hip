@@ -302,6 +302,7 @@ struct OptSlot {
     bool busy = false;
     std::vector<char> key;    // the caller's table bytes this slot holds
     size_t tab_bytes = 0;
+    size_t ctl_off = 0;       // 16 bytes behind table and block list: the control block of mdt_op_multi_adamw_dev
     int n_blocks = 0;
     uint64_t last_use = 0;
 };
@@ -309,6 +310,12 @@ struct OptTable {  // one per device: the tables live in that device's memory
     std::mutex mu;
     OptSlot slots[16];
     uint64_t clock = 0;
+    // the per-chunk partials of mdt_op_multi_sumsq for callers that bring none: grown on demand, never shrunk
+    float* partial = nullptr;
+    size_t partial_cap = 0;   // floats
+    hipEvent_t partial_ev = nullptr;  // behind the last k_sumsq_finish that read it, on partial_stream
+    hipStream_t partial_stream = nullptr;
+    bool partial_busy = false;
 };
 OptTable g_opt_dev[32];
 }  // namespace
@@ -335,7 +342,8 @@ static mdt_status upload_opt_table(OptTable& g_opt, const mdt_opt_tensor* tensor
         for (int64_t off = 0; off < tensors[i].numel; off += CH) blocks.push_back(make_int2(i, (int)off));
     }
     const size_t tab_bytes = (key_bytes + 255) & ~(size_t)255;
-    const size_t total = tab_bytes + blocks.size() * sizeof(int2);
+    const size_t data_bytes = tab_bytes + blocks.size() * sizeof(int2);
+    const size_t total = ((data_bytes + 15) & ~(size_t)15) + 16;  // + the control block (device only, never copied)
     OptSlot* lru = &g_opt.slots[0];
     for (OptSlot& c : g_opt.slots)
         if (c.last_use < lru->last_use) lru = &c;
@@ -353,9 +361,10 @@ static mdt_status upload_opt_table(OptTable& g_opt, const mdt_opt_tensor* tensor
     }
     memcpy(sl.host, tensors, key_bytes);
     memcpy((char*)sl.host + tab_bytes, blocks.data(), blocks.size() * sizeof(int2));
-    HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, total, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(sl.dev, sl.host, data_bytes, hipMemcpyHostToDevice, s));
     sl.key.assign((const char*)tensors, (const char*)tensors + key_bytes);
     sl.tab_bytes = tab_bytes;
+    sl.ctl_off = total - 16;
     sl.n_blocks = (int)blocks.size();
     *d_tab = (const mdt_opt_tensor*)sl.dev;
     *d_blocks = (const int2*)((const char*)sl.dev + tab_bytes);
@@ -475,6 +484,86 @@ extern "C" mdt_status mdt_op_multi_ema(const mdt_opt_tensor* tensors, int32_t n,
     OptSlot* slot = nullptr;
     MDT_TRY(upload_opt_table(g_opt, tensors, n, &tab, &blocks, &nb, &slot, s));
     LAUNCH(mdt_launch_multi_axpby(tab, blocks, nb, decay, 1.0f - decay, s));
+    HIP_TRY(hipEventRecord(slot->ev, s));
+    slot->busy = true;
+    slot->stream = s;
+    return MDT_OK;
+}
+
+extern "C" int64_t mdt_op_multi_sumsq_scratch(const mdt_opt_tensor* tensors, int32_t n) {
+    if (!tensors || n < 0) return 0;
+    int64_t nb = 0;
+    for (int i = 0; i < n; ++i)
+        if (tensors[i].numel > 0) nb += (tensors[i].numel + 4095) / 4096;  // OPT_CHUNK of the kernels
+    return 2 * nb;
+}
+
+extern "C" mdt_status mdt_op_multi_sumsq(const mdt_opt_tensor* tensors, int32_t n, int32_t which, float* out, float* partials,
+                                         int64_t partials_numel, void* stream) {
+    if (!tensors || n < 0 || !out || (which != 0 && which != 1) || partials_numel < 0)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_multi_sumsq: bad argument");
+    for (int i = 0; i < n; ++i)
+        if (tensors[i].numel != 0 && !(which ? (const float*)tensors[i].p : tensors[i].g))  // an empty tensor has no storage
+            return fail(MDT_ERR_INVALID_ARG, "mdt_op_multi_sumsq: tensor %d lacks %s", i, which ? "p" : "g");
+    const int64_t need = mdt_op_multi_sumsq_scratch(tensors, n);
+    if (partials && partials_numel < need)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_multi_sumsq: %lld floats of partials given, %lld needed", (long long)partials_numel,
+                    (long long)need);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 32) return fail(MDT_ERR_INVALID_ARG, "device index %d out of range", dev);
+    OptTable& g_opt = g_opt_dev[dev];
+    std::lock_guard<std::mutex> lock(g_opt.mu);
+    hipStream_t s = (hipStream_t)stream;
+    const mdt_opt_tensor* tab; const int2* blocks; int nb;
+    OptSlot* slot = nullptr;
+    MDT_TRY(upload_opt_table(g_opt, tensors, n, &tab, &blocks, &nb, &slot, s));
+    const bool own = partials == nullptr && need > 0;
+    if (own) {
+        if (!g_opt.partial_ev) HIP_TRY(hipEventCreateWithFlags(&g_opt.partial_ev, hipEventDisableTiming));
+        if ((size_t)need > g_opt.partial_cap) {
+            if (g_opt.partial_busy) HIP_TRY(hipEventSynchronize(g_opt.partial_ev));  // its last reader (long done in practice)
+            if (g_opt.partial) HIP_TRY(mdt_dev_free(g_opt.partial));
+            g_opt.partial = nullptr; g_opt.partial_cap = 0; g_opt.partial_busy = false;
+            HIP_TRY(mdt_dev_malloc((void**)&g_opt.partial, (size_t)need * 2 * sizeof(float)));
+            g_opt.partial_cap = (size_t)need * 2;
+        }
+        if (g_opt.partial_busy && g_opt.partial_stream != s) HIP_TRY(hipStreamWaitEvent(s, g_opt.partial_ev, 0));
+        partials = g_opt.partial;
+    }
+    LAUNCH(mdt_launch_multi_sumsq(tab, blocks, nb, which, partials, out, s));
+    HIP_TRY(hipEventRecord(slot->ev, s));
+    slot->busy = true;
+    slot->stream = s;
+    if (own) {
+        HIP_TRY(hipEventRecord(g_opt.partial_ev, s));
+        g_opt.partial_busy = true;
+        g_opt.partial_stream = s;
+    }
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_multi_adamw_dev(const mdt_opt_tensor* tensors, int32_t n, float lr, float beta1, float beta2,
+                                             float eps, float weight_decay, float* step, const float* grad_scale,
+                                             const float* found_inf, const float* grad_sumsq, float max_norm, float* grad_norm,
+                                             void* stream) {
+    if (!tensors || n < 0 || !step || max_norm != max_norm || (max_norm > 0.f && !grad_sumsq))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_multi_adamw_dev: bad argument");
+    for (int i = 0; i < n; ++i)
+        if (!tensors[i].p || !tensors[i].g || !tensors[i].m || !tensors[i].v)
+            return fail(MDT_ERR_INVALID_ARG, "mdt_op_multi_adamw_dev: tensor %d lacks p / g / m / v", i);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 32) return fail(MDT_ERR_INVALID_ARG, "device index %d out of range", dev);
+    OptTable& g_opt = g_opt_dev[dev];
+    std::lock_guard<std::mutex> lock(g_opt.mu);
+    hipStream_t s = (hipStream_t)stream;
+    const mdt_opt_tensor* tab; const int2* blocks; int nb;
+    OptSlot* slot = nullptr;
+    MDT_TRY(upload_opt_table(g_opt, tensors, n, &tab, &blocks, &nb, &slot, s));
+    float* ctl = (float*)((char*)slot->dev + slot->ctl_off);
+    LAUNCH(mdt_launch_multi_adamw_dev(tab, blocks, nb, lr, beta1, beta2, eps, weight_decay, step, grad_scale, found_inf, grad_sumsq,
+                                      max_norm, ctl, grad_norm, s));
     HIP_TRY(hipEventRecord(slot->ev, s));
     slot->busy = true;
     slot->stream = s;
