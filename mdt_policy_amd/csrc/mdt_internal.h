@@ -252,10 +252,15 @@ hipError_t mdt_launch_attn_bwd(const mdt_attn_bwd_args& a, hipStream_t s);
 hipError_t mdt_launch_loss_grad(const float* F, const float* act, const float* noised, const float* sigma, float sd,
                                 int64_t n, int per_sample, const float* gscale, float* dF, hipStream_t s);
 hipError_t mdt_launch_narrow_dx(const float* G, const float* W, float* out, int M, int A, int D, hipStream_t s);
-hipError_t mdt_launch_vjp_seed(const float* F, const float* x, const float* sigma, const float* v, float sd, int64_t n,
-                               int per_sample, float* den, float* dF, hipStream_t s);
-hipError_t mdt_launch_vjp_finish(const float* dxin, const float* sigma, const float* v, float sd, int64_t n, int per_sample,
-                                 float* out, hipStream_t s);
+// D = c_skip x + c_out F (den; may be nullptr) and the backward's seed dF = c_out g (g / dF; may be nullptr); its end
+// out = c_in dxin + c_skip g; and d_sigma per sample (k_denoise_dsigma; d_e == nullptr: no sigma-embedding path)
+hipError_t mdt_launch_denoise_seed(const float* F, const float* x, const float* sigma, const float* g, float sd, int64_t n,
+                                   int per_sample, float* den, float* dF, hipStream_t s);
+hipError_t mdt_launch_denoise_finish(const float* dxin, const float* sigma, const float* g, float sd, int64_t n, int per_sample,
+                                     float* out, hipStream_t s);
+hipError_t mdt_launch_denoise_dsigma(const float* g, const float* x, const float* F, const float* xin, const float* dxin,
+                                     const float* e, const float* d_e, const float* freqs, const float* sigma, float sd, int B,
+                                     int per_sample, int D, float* out, hipStream_t s);
 // out[m][n] = act(b[n] + sum_a X[m][a] WT[a][n]), A <= 16; pre (optional): the pre-activation rows
 hipError_t mdt_launch_narrow_linear(const float* X, const float* WT, const float* b, float* pre, float* out, int M, int A,
                                     int N, int act, hipStream_t s);

@@ -34,6 +34,7 @@ struct BlockTape {  // one transformer block; rows M = B*T
 
 struct Tape : TapeBase {
     bool has_decoder = false;
+    bool dec_only = false;  // mdt_train_denoise_fwd: the decoder against a context the caller gave (no encoder activations)
     int64_t B = 0, cap = 0;
     int lang = 0;  // 1: the goal went through lang_emb
     mdt_dropout drop = {0.f, 0.f, 0.f, 0.f, 0};
@@ -283,6 +284,7 @@ static mdt_status acquire_tape(mdt_model* m, int64_t B, mdt_tape_id* id, hipStre
     Tape& t = m->train->tapes[*id];
     t.B = B;
     t.has_decoder = false;
+    t.dec_only = false;
     return MDT_OK;
 }
 
@@ -886,17 +888,18 @@ static mdt_status block_bwd(mdt_model* m, float* grads, const EncBlock& e, const
     return MDT_OK;
 }
 
-// backward of sigma_fwd given d(c) (B, D) in `dc` (consumed); sigma itself takes no gradient
+// backward of sigma_fwd given d(c) (B, D) in `dc` (consumed); d_e (optional): receives the gradient of the sinusoidal
+// features (B, D), from which mdt_train_denoise_bwd forms d_sigma -- sigma takes no gradient anywhere else
 // tmp (B, 2D) / scratch: the caller's own buffers when this runs beside the chain (else the shared ones)
 static mdt_status sigma_bwd(mdt_model* m, Tape& t, float* grads, float* dc, hipStream_t s, float* tmp = nullptr,
-                            float* scratch = nullptr) {
+                            float* scratch = nullptr, float* d_e = nullptr) {
     mdt_train_state* ts = m->train;
     const int D = m->D;
     const int64_t B = t.B;
     if (!tmp) tmp = ts->t_d2;
     MDT_TRY(lin_bwd(m, grads, m->sig3, t.sig_t, 2 * D, dc, D, (int)B, tmp, 2 * D, 0, s, nullptr, 0, false, scratch));
     LAUNCH(mdt_launch_act_bwd(t.sig_tpre, tmp, tmp, B * 2 * D, MDT_ACT_MISH, s));
-    MDT_TRY(lin_bwd(m, grads, m->sig1, t.sig_e, D, tmp, 2 * D, (int)B, nullptr, 0, 0, s, nullptr, 0, false, scratch));
+    if (grads || d_e) MDT_TRY(lin_bwd(m, grads, m->sig1, t.sig_e, D, tmp, 2 * D, (int)B, d_e, D, 0, s, nullptr, 0, false, scratch));
     return MDT_OK;
 }
 
@@ -998,6 +1001,7 @@ extern "C" mdt_status mdt_train_encode_bwd(mdt_model* m, mdt_tape_id tape, const
     Tape* t;
     MDT_TRY(get_tape(m, tape, &t));
     if (!g_ctx || !grads) return fail(MDT_ERR_INVALID_ARG, "mdt_train_encode_bwd: null argument");
+    if (t->dec_only) return fail(MDT_ERR_STATE, "tape %d holds a decoder-only forward: use mdt_train_denoise_bwd", tape);
     hipStream_t s = (hipStream_t)stream;
     t->stream = s;
     MDT_TRY(scratch_enter(m, s));
@@ -1071,12 +1075,14 @@ static mdt_status dec_bwd_block(mdt_model* m, Tape& t, float* grads, int l, hipS
 // the cross K|V Linear and the encoder -- reads them or the buffers they come from (ts->dx, ts->d_mod are final).  With the
 // weight gradients beside the chain (MDT_HIP_DW_STREAM) the whole tail therefore runs on the side stream, with its own scratch,
 // while the chain goes on into the encoder (~0.25 ms of small launches at B = 1024).
-static mdt_status dec_bwd_tail(mdt_model* m, Tape& t, float* grads, hipStream_t s) {
+// in_chain: everything stays in `s` on the shared scratch -- mdt_train_denoise_bwd reads ts->dx (d y0) and d_e behind it;
+// d_e (B, D; optional): the gradient of the sigma embedding's sinusoidal features (sigma_bwd), formed with or without `grads`.
+static mdt_status dec_bwd_tail(mdt_model* m, Tape& t, float* grads, hipStream_t s, bool in_chain = false, float* d_e = nullptr) {
     mdt_train_state* ts = m->train;
     const int D = m->D, Ta = m->Ta, A = m->A;
     const int64_t B = t.B, Ma = B * Ta;
     const DecCond dc = dec_cond(m);
-    const bool beside = grads && ts->dy_arena && ts->small2;
+    const bool beside = !in_chain && grads && ts->dy_arena && ts->small2;
     float *narrow = ts->narrow, *small = ts->small, *tmp = nullptr, *scratch = nullptr;
     if (beside) {
         MDT_TRY(side_fork(ts, 0, s, &s));  // from here on `s` is the side stream
@@ -1086,18 +1092,20 @@ static mdt_status dec_bwd_tail(mdt_model* m, Tape& t, float* grads, hipStream_t 
     // ---- action embedding: y0 = drop(action_emb(xin)); no gradient flows to the noisy actions
     LAUNCH(mdt_launch_dropout_rows(ts->dx, Ma, D, Ta, 0, t.drop.embed_p, site_id(m->Le + m->Ld, SITE_EMBED_ACTION), t.drop.seed,
                                    s));
-    if (!grads) return MDT_OK;
-    LAUNCH(mdt_launch_colsum(ts->dx, D, (int)Ma, D, grad_of(m, grads, m->ba), 1, s));
-    LAUNCH(mdt_launch_narrow_dw(t.xin, ts->dx, D, narrow, NARROW_SLICES, (int)Ma, A, D, 1, s));
-    LAUNCH(mdt_launch_colsum(narrow, (int64_t)A * D, NARROW_SLICES, A * D, grad_of(m, grads, m->Wa), 1, s));
+    if (!grads && !d_e) return MDT_OK;
+    if (grads) {
+        LAUNCH(mdt_launch_colsum(ts->dx, D, (int)Ma, D, grad_of(m, grads, m->ba), 1, s));
+        LAUNCH(mdt_launch_narrow_dw(t.xin, ts->dx, D, narrow, NARROW_SLICES, (int)Ma, A, D, 1, s));
+        LAUNCH(mdt_launch_colsum(narrow, (int64_t)A * D, NARROW_SLICES, A * D, grad_of(m, grads, m->Wa), 1, s));
+    }
     // ---- sigma path.  adaLN: mod = modulation(silu(c)), c = sigma_emb(sigma); NoiseBlock: the rows are c itself;
     //      sigma token: its gradient arrives with the context's (enc_bwd)
     if (m->cond == COND_ADALN) {
         MDT_TRY(lin_bwd(m, grads, m->mod_all, t.sig_s, D, ts->d_mod, dc.modw, (int)B, small, D, 0, s, nullptr, 0, false, scratch));
         LAUNCH(mdt_launch_act_bwd(t.sig_cpre, small, small, B * D, MDT_ACT_SILU, s));
-        MDT_TRY(sigma_bwd(m, t, grads, small, s, tmp, scratch));
+        MDT_TRY(sigma_bwd(m, t, grads, small, s, tmp, scratch, d_e));
     } else if (m->cond == COND_NOISE) {
-        MDT_TRY(sigma_bwd(m, t, grads, ts->d_mod, s, tmp, scratch));
+        MDT_TRY(sigma_bwd(m, t, grads, ts->d_mod, s, tmp, scratch, d_e));
     }
     return MDT_OK;
 }
@@ -1127,6 +1135,7 @@ static mdt_status loss_bwd_stage_impl(mdt_model* m, mdt_tape_id tape, int32_t st
     Tape& t = *tp;
     if (!grads) return fail(MDT_ERR_INVALID_ARG, "mdt_train_loss_bwd: null gradient buffer");
     if (!t.has_decoder) return fail(MDT_ERR_STATE, "tape %d holds an encoder-only forward: use mdt_train_encode_bwd", tape);
+    if (t.dec_only) return fail(MDT_ERR_STATE, "tape %d holds a decoder-only forward: use mdt_train_denoise_bwd", tape);
     hipStream_t s = (hipStream_t)stream;
     mdt_train_state* ts = m->train;
     const int Ld = m->Ld, Le = m->Le, n = Ld + Le + 2;
@@ -1206,6 +1215,84 @@ extern "C" int32_t mdt_train_param_stage(const mdt_model* m, int64_t i) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// D(x; sigma) against a given context, differentiable in everything it reads (include/mdt_hip_train.h): what GCDenoiser.forward
+// is to torch.autograd on the reference modules (score_wrappers.py:65-80), split at the context so that several evaluations --
+// unrolled solver steps, the two halves of classifier-free guidance -- share one encoder forward / backward
+// (mdt_train_encode_fwd / _bwd).  The forward is dec_fwd on a tape without encoder activations; the backward is the loss
+// path's decoder backward (dec_bwd_head / _block / _tail, the stacked K|V lin_bwd) between a seed for an arbitrary upstream
+// gradient and the input gradients the loss path never forms: d_x, d_sigma, d_ctx.
+// ------------------------------------------------------------------------------------------------
+extern "C" mdt_status mdt_train_denoise_fwd(mdt_model* m, const float* ctx, const float* x, const float* sigma, int64_t batch,
+                                            const mdt_dropout* drop, float* denoised, mdt_tape_id* tape, void* stream) {
+    MDT_TRY(check_ready(m));
+    if (!ctx || !x || !sigma || !denoised || !tape || batch < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_train_denoise_fwd: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    MDT_TRY(check_dropout(drop));
+    MDT_TRY(acquire_tape(m, batch, tape, s));
+    Tape& t = m->train->tapes[*tape];
+    t.drop = effective_dropout(drop);
+    t.dec_only = true;
+    const int64_t n = batch * m->Ta * m->A;
+    mdt_status st = MDT_OK;
+    auto hip = [&](hipError_t e, const char* what) { if (st == MDT_OK && e != hipSuccess) st = fail(MDT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
+    hip(hipMemcpyAsync(t.ctx, ctx, (size_t)batch * m->Te * m->D * sizeof(float), hipMemcpyDeviceToDevice, s), "context copy");
+    // with the sigma token the encoder ran the sigma MLP (the context carries it); the decoder still reads sigma for the scalings
+    if (m->cond == COND_TOKEN) hip(hipMemcpyAsync(t.sigma, sigma, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, s), "sigma copy");
+    // action := x, no noise: the tape's "noised" rows are x itself, F the raw network output
+    if (st == MDT_OK) st = dec_fwd(m, t, x, nullptr, sigma, nullptr, nullptr, s);
+    if (st == MDT_OK) hip(mdt_launch_denoise_seed(t.F, t.noised, t.sigma, nullptr, m->cfg.sigma_data, n, m->Ta * m->A, denoised, nullptr, s), "denoise launch");
+    if (st != MDT_OK) t.in_use = false;
+    return st;
+}
+
+extern "C" mdt_status mdt_train_denoise_bwd(mdt_model* m, mdt_tape_id tape, const float* g_denoised, float* grads, float* d_ctx,
+                                            float* d_x, float* d_sigma, void* stream) {
+    if (!m) return fail(MDT_ERR_INVALID_ARG, "mdt_train_denoise_bwd: null handle");
+    Tape* tp;
+    MDT_TRY(get_tape(m, tape, &tp));
+    Tape& t = *tp;
+    if (!g_denoised) return fail(MDT_ERR_INVALID_ARG, "mdt_train_denoise_bwd: null upstream gradient");
+    if (!t.has_decoder || !t.dec_only)
+        return fail(MDT_ERR_STATE, "tape %d was not written by mdt_train_denoise_fwd", tape);
+    if (d_sigma && m->cond == COND_TOKEN)
+        return fail(MDT_ERR_UNSUPPORTED, "mdt_train_denoise_bwd: d_sigma is not formed for use_ada_conditioning=False models "
+                                         "(sigma is a context token there: its gradient would have to come through the encoder)");
+    hipStream_t s = (hipStream_t)stream;
+    mdt_train_state* ts = m->train;
+    // the chain's buffers (ts->dx, ts->gm, the dY arena) carry a staged loss backward from stage to stage: not between its stages.
+    // bwd_next == -1 (a stage failed: that run is over, only a new stage 0 leaves the state) is no such run: this call rewrites
+    // every buffer it reads, clears the deferred sums and joins whatever side stream the failed stage left marked as used.
+    if (ts->bwd_next > 0)
+        return fail(MDT_ERR_STATE, "mdt_train_denoise_bwd: a staged loss backward of tape %d is under way on this handle (stage %d is next)",
+                    ts->bwd_tape, ts->bwd_next);
+    t.stream = s;
+    MDT_TRY(scratch_enter(m, s));
+    MDT_TRY(reserve_scratch(m, t.B));
+    ts->deferred.clear(); ts->defer_off = 0; ts->dy_off = 0;
+    const int D = m->D, Ta = m->Ta, A = m->A, per = Ta * A;
+    const int64_t B = t.B, Ma = B * Ta, Me = B * m->Te;
+    LAUNCH(mdt_launch_denoise_seed(t.F, t.noised, t.sigma, g_denoised, m->cfg.sigma_data, Ma * A, per, nullptr, ts->dF, s));
+    MDT_TRY(dec_bwd_head(m, t, grads, s));
+    for (int l = m->Ld - 1; l >= 0; --l) MDT_TRY(dec_bwd_block(m, t, grads, l, s));
+    // the tail in the chain: ts->dx leaves it as d y0, ts->t_d as the gradient of the sigma embedding's sinusoidal features
+    float* d_e = d_sigma ? ts->t_d : nullptr;
+    MDT_TRY(dec_bwd_tail(m, t, grads, s, true, d_e));
+    if (d_x || d_sigma) {
+        // y0 = action_emb(c_in x): d x_in = d y0 . Wa;  d x = c_in d x_in + c_skip g
+        float* dxin = ts->t_4d;
+        LAUNCH(mdt_launch_narrow_out(ts->dx, D, m->Wa, dxin, (int)Ma, A, D, s));
+        if (d_x) LAUNCH(mdt_launch_denoise_finish(dxin, t.sigma, g_denoised, m->cfg.sigma_data, Ma * A, per, d_x, s));
+        if (d_sigma)
+            LAUNCH(mdt_launch_denoise_dsigma(g_denoised, t.noised, t.F, t.xin, dxin, t.sig_e, d_e, m->freqs, t.sigma, m->cfg.sigma_data,
+                                             (int)B, per, D, d_sigma, s));
+    }
+    // the context: K|V projections of all blocks
+    if (grads || d_ctx)
+        MDT_TRY(lin_bwd(m, grads, m->kv_all, t.ctx, D, ts->d_kvx, (int64_t)m->Ld * 2 * D, (int)Me, d_ctx, D, 0, s));
+    return flush_deferred(m, s);
+}
+
+// ------------------------------------------------------------------------------------------------
 // vector-Jacobian product of the denoiser w.r.t. its noisy-action input (what log_likelihood differentiates,
 // gc_sampling.py:469-487: torch.autograd.grad((d * v).sum(), action) with d = (action - D(action; sigma)) / sigma)
 // ------------------------------------------------------------------------------------------------
@@ -1233,13 +1320,13 @@ extern "C" mdt_status mdt_denoise_vjp(mdt_model* m, const float* tokens, const f
         const int64_t n = batch * m->Ta * m->A;
         const int per = m->Ta * m->A;
         // D = c_skip x + c_out F;  dF = c_out v
-        hipError_t e = mdt_launch_vjp_seed(t.F, t.noised, t.sigma, v, m->cfg.sigma_data, n, per, denoised, ts->dF, s);
+        hipError_t e = mdt_launch_denoise_seed(t.F, t.noised, t.sigma, v, m->cfg.sigma_data, n, per, denoised, ts->dF, s);
         if (e != hipSuccess) st = fail(MDT_ERR_HIP, "vjp seed launch failed: %s", hipGetErrorString(e));
         if (st == MDT_OK) st = dec_bwd(m, t, nullptr, s);
         if (st == MDT_OK) {
             // y0 = action_emb(c_in x): d x = c_in (d y0 . Wa) + c_skip v
             e = mdt_launch_narrow_out(ts->dx, m->D, m->Wa, ts->small, (int)(batch * m->Ta), m->A, m->D, s);
-            if (e == hipSuccess) e = mdt_launch_vjp_finish(ts->small, t.sigma, v, m->cfg.sigma_data, n, per, vjp, s);
+            if (e == hipSuccess) e = mdt_launch_denoise_finish(ts->small, t.sigma, v, m->cfg.sigma_data, n, per, vjp, s);
             if (e != hipSuccess) st = fail(MDT_ERR_HIP, "vjp finish launch failed: %s", hipGetErrorString(e));
         }
     }

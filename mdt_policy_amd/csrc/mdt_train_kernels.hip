@@ -1439,35 +1439,80 @@ hipError_t mdt_launch_loss_grad(const float* F, const float* act, const float* n
     return hipGetLastError();
 }
 
-// mdt_denoise_vjp: D = c_skip x + c_out F (score_wrappers.py:65-80) and the seed of its backward, dF = c_out v
-__global__ void k_vjp_seed(const float* __restrict__ F, const float* __restrict__ x, const float* __restrict__ sigma,
-                           const float* __restrict__ v, float sd, int64_t n, int per_sample, float* __restrict__ den,
-                           float* __restrict__ dF) {
+// D(x; sigma) = c_skip x + c_out F (score_wrappers.py:65-80) and the seed of its backward for an upstream gradient g:
+// dF = c_out g.  Either half may be absent (den == nullptr / g == nullptr): mdt_denoise_vjp runs both in one launch (g = v),
+// mdt_train_denoise_fwd the first, mdt_train_denoise_bwd the second.
+__global__ void k_denoise_seed(const float* __restrict__ F, const float* __restrict__ x, const float* __restrict__ sigma,
+                               const float* __restrict__ g, float sd, int64_t n, int per_sample, float* __restrict__ den,
+                               float* __restrict__ dF) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float sg = sigma[i / per_sample];
     const float den2 = sg * sg + sd * sd;
     const float c_skip = sd * sd / den2, c_out = sg * sd / sqrtf(den2);
-    den[i] = fmaf(F[i], c_out, x[i] * c_skip);
-    dF[i] = c_out * v[i];
+    if (den) den[i] = fmaf(F[i], c_out, x[i] * c_skip);
+    if (g) dF[i] = c_out * g[i];
 }
-hipError_t mdt_launch_vjp_seed(const float* F, const float* x, const float* sigma, const float* v, float sd, int64_t n,
-                               int per_sample, float* den, float* dF, hipStream_t s) {
-    hipLaunchKernelGGL(k_vjp_seed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, F, x, sigma, v, sd, n, per_sample, den, dF);
+hipError_t mdt_launch_denoise_seed(const float* F, const float* x, const float* sigma, const float* g, float sd, int64_t n,
+                                   int per_sample, float* den, float* dF, hipStream_t s) {
+    hipLaunchKernelGGL(k_denoise_seed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, F, x, sigma, g, sd, n, per_sample, den, dF);
     return hipGetLastError();
 }
-// ... and its end: the network saw c_in x, the skip connection c_skip x
-__global__ void k_vjp_finish(const float* __restrict__ dxin, const float* __restrict__ sigma, const float* __restrict__ v,
-                             float sd, int64_t n, int per_sample, float* __restrict__ out) {
+// ... and its end: the network saw c_in x, the skip connection c_skip x: d_x = c_in (d y0 . Wa) + c_skip g
+__global__ void k_denoise_finish(const float* __restrict__ dxin, const float* __restrict__ sigma, const float* __restrict__ g,
+                                 float sd, int64_t n, int per_sample, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float sg = sigma[i / per_sample];
     const float den2 = sg * sg + sd * sd;
-    out[i] = fmaf(dxin[i], 1.0f / sqrtf(den2), v[i] * (sd * sd / den2));
+    out[i] = fmaf(dxin[i], 1.0f / sqrtf(den2), g[i] * (sd * sd / den2));
 }
-hipError_t mdt_launch_vjp_finish(const float* dxin, const float* sigma, const float* v, float sd, int64_t n, int per_sample,
-                                 float* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_vjp_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dxin, sigma, v, sd, n, per_sample, out);
+hipError_t mdt_launch_denoise_finish(const float* dxin, const float* sigma, const float* g, float sd, int64_t n, int per_sample,
+                                     float* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_denoise_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dxin, sigma, g, sd, n, per_sample, out);
+    return hipGetLastError();
+}
+
+// d_sigma of D(x; sigma) for an upstream gradient g, one wavefront per sample ("d_sigma"):
+//   sum over the sample's chunk of  g (c_skip' x + c_out' F)  +  c_in'/c_in d_xin x_in          (the three scalings)
+//   + 1/(4 sigma) sum_j f_j (d_e[j] cos(s f_j) - d_e[half + j] sin(s f_j))                      (the sigma embedding's input)
+// with c_skip' = -2 sigma sd^2 / (sigma^2 + sd^2)^2, c_out' = sd^3 / (sigma^2 + sd^2)^(3/2), c_in'/c_in = -sigma / (sigma^2 + sd^2),
+// s = c_noise = ln(sigma) / 4 (d c_noise / d sigma = 1 / (4 sigma)), e = [sin(s f) | cos(s f)] the features the forward kept and
+// d_e the input gradient of sigma_emb's first Linear (nullptr: that path is absent).  Lanes stride over the elements, the
+// wavefront's sums run as shuffles in a fixed order, lane 0 stores: the same bits on every run.
+__global__ __launch_bounds__(256) void k_denoise_dsigma(const float* __restrict__ g, const float* __restrict__ x,
+                                                        const float* __restrict__ F, const float* __restrict__ xin,
+                                                        const float* __restrict__ dxin, const float* __restrict__ e,
+                                                        const float* __restrict__ d_e, const float* __restrict__ freqs,
+                                                        const float* __restrict__ sigma, float sd, int B, int per_sample, int D,
+                                                        float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const float sg = sigma[b];
+    const float den2 = sg * sg + sd * sd;
+    const float r = 1.0f / sqrtf(den2);
+    const float dskip = -2.0f * sg * sd * sd / (den2 * den2), dout = sd * sd * sd * r / den2, din = -sg / den2;
+    const int64_t o = (int64_t)b * per_sample;
+    float acc = 0.f;
+    for (int i = lane; i < per_sample; i += 64)
+        acc += g[o + i] * fmaf(dskip, x[o + i], dout * F[o + i]) + din * (dxin[o + i] * xin[o + i]);
+    float emb = 0.f;
+    if (d_e) {
+        const int half = D >> 1;
+        const float* eb = e + (int64_t)b * D;
+        const float* db = d_e + (int64_t)b * D;
+        for (int j = lane; j < half; j += 64) emb += freqs[j] * (db[j] * eb[half + j] - db[half + j] * eb[j]);
+    }
+    const float v = wave_sum(acc) + wave_sum(emb) / (4.0f * sg);
+    if (lane == 0) out[b] = v;
+}
+hipError_t mdt_launch_denoise_dsigma(const float* g, const float* x, const float* F, const float* xin, const float* dxin,
+                                     const float* e, const float* d_e, const float* freqs, const float* sigma, float sd, int B,
+                                     int per_sample, int D, float* out, hipStream_t s) {
+    if (B < 1 || per_sample < 1 || (d_e && (!e || !freqs || D < 2))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_denoise_dsigma, dim3((B + 3) / 4), dim3(256), 0, s, g, x, F, xin, dxin, e, d_e, freqs, sigma, sd, B,
+                       per_sample, D, out);
     return hipGetLastError();
 }
 

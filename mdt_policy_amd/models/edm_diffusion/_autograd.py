@@ -169,3 +169,29 @@ class HipContextOnly(torch.autograd.Function):
         grads, d_tok, d_tok2, d_goal = eng.train_encode_bwd(ctx.tape.id, g_ctx, tok, tok2, goal, ctx.needs)
         ctx.tape.release()
         return (None, None, d_tok, d_tok2, d_goal, None, None, None, None, *eng.param_grads(grads, ctx.named, ctx.unused))
+
+
+class HipDenoise(torch.autograd.Function):
+    """denoised = D(x; sigma) against a context tensor (GCDenoiser.denoise_grad): differentiable in the context, the noisy
+    actions, sigma (where it conditions the decoder) and the decoder-side parameters.  Encoder parameters get their gradient
+    from the node that made the context (HipContextOnly), fed by this node's d_ctx."""
+
+    @staticmethod
+    def forward(ctx, eng, context, x, sigma, drop, names, *params):
+        B = x.shape[0]
+        out, tape = eng.train_denoise_fwd(eng._in(context), eng._in(x, (B, eng.Ta, eng.A)), eng._in(sigma, (B,)), drop)
+        ctx.eng, ctx.tape, ctx.B = eng, LibTape(tape, eng.tape_release), B
+        ctx.named = list(zip(names, params))
+        ctx.needs = _needs(context, x, sigma)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        eng = ctx.eng
+        if ctx.tape.id is None:
+            raise RuntimeError("the HIP training tape of this forward was already consumed (no retain_graph support)")
+        want = any(p.requires_grad for _, p in ctx.named)
+        grads, d_ctx, d_x, d_sigma = eng.train_denoise_bwd(ctx.tape.id, g, ctx.B, ctx.needs, want)
+        ctx.tape.release()
+        pg = eng.param_grads(grads, ctx.named) if want else [None] * len(ctx.named)
+        return (None, d_ctx, d_x, d_sigma, None, None, *pg)

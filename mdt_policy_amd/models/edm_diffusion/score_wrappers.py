@@ -166,6 +166,83 @@ class GCDenoiser(nn.Module):
     def get_params(self):
         return self.inner_model.parameters()
 
+    def _context_engine(self, state, context):
+        """The handle a given context tensor belongs to: the one ``state`` selects or, where its context layout has another
+        token count (MDT-V with / without the proprioceptive token; ``state`` may be None), the other layout's."""
+        eng = self._engine(allow_grad=True, state=state)
+        if self.inner_model._arch == "mdtv" and context.dim() == 3 and context.shape[1] != eng.Te:
+            other = {} if eng.proprio else {"state_obs": None}  # hip_engine keys on the presence of 'state_obs' alone
+            try:
+                alt = self._engine(allow_grad=True, state=other)
+            except Exception:  # noqa: BLE001 -- a model without that layout: the shape error below names the mismatch
+                return eng
+            if context.shape[1] == alt.Te:
+                return alt
+        return eng
+
+    def denoise_grad(self, state, action, goal, sigma, cond_lambda=1.0, context=None, uncond=False):
+        """``forward`` recorded by torch.autograd: D(x; sigma), differentiable in the parameters, the state tokens, the goal,
+        the noisy ``action`` and ``sigma`` -- custom objectives on the denoised chunk, guidance gradients, hand-unrolled solver
+        steps.  The implicit call ``self(...)`` stays inference-only; this is the opt-in.
+
+        ``context``: None -- the encoder runs as a differentiable node of its own (as ``forward`` runs it; latent_encoder_emb is
+        set); or a context tensor, e.g. one ``forward_context_only`` under autograd, against which only the decoder runs: several
+        evaluations then share one encoder forward and backward (``goal`` is not read, ``state`` may be None: the handle is the one
+        whose context layout has the tensor's token count, with or without the proprioceptive token; with
+        use_ada_conditioning=False the context must have been encoded with this ``sigma``).  ``cond_lambda`` != 1 composes
+        d_u + lambda (d_g - d_u) from two evaluations as ``forward`` does (needs ``context`` None).  In train() mode the shipped
+        dropouts apply, a fresh seed per evaluation, as in ``loss``.  Under torch.no_grad(), or when nothing requires grad, this
+        is ``forward``.  ``sigma.requires_grad`` on a use_ada_conditioning=False model raises: sigma is a context token there
+        and its gradient through the encoder is not formed."""
+        lam = float(cond_lambda)
+        if lam != 1.0:
+            if not math.isfinite(lam):
+                raise ValueError(f"cond_lambda must be finite, got {lam}")
+            if uncond:
+                raise ValueError("uncond=True and cond_lambda != 1 contradict each other")
+            if context is not None:
+                raise ValueError("cond_lambda != 1 encodes the goal and the zeroed goal itself: it takes no context")
+            d_u = self.denoise_grad(state, action, goal, sigma, uncond=True)
+            d_g = self.denoise_grad(state, action, goal, sigma)
+            return d_u + lam * (d_g - d_u)
+        im = self.inner_model
+        tensors = [goal, action, sigma, context] + ([v for v in state.values() if torch.is_tensor(v)] if context is None else [])
+        if not self._wants_grad(*tensors):
+            if context is None:
+                return self.forward(state, action, goal, sigma, uncond=uncond)
+            eng = self._context_engine(state, context)  # a given context: the taped decoder forward, its tape handed back
+            B = action.shape[0]
+            sg = sigma.reshape(-1).expand(B) if sigma.numel() == 1 and B > 1 else sigma
+            out, tape = eng.train_denoise_fwd(eng._in(context), eng._in(action, (B, eng.Ta, eng.A)), eng._in(sg, (B,)),
+                                              im.train_dropout())
+            eng.tape_release(tape)
+            return out
+        from ._autograd import HipContextOnly, HipDenoise
+        eng = self._engine(allow_grad=True, state=state) if context is None else self._context_engine(state, context)
+        if eng.sigma_in_context and torch.is_tensor(sigma) and sigma.requires_grad:
+            raise NotImplementedError("use_ada_conditioning=False: sigma is a context token and its gradient through the encoder "
+                                      "is not formed (d_sigma exists for adaLN-Zero and NoiseBlock conditioning only)")
+        B = action.shape[0]
+        drop = im.train_dropout()  # one seed for the encoder's and the decoder's sites, as in loss
+        # float32 (B,) / (B, Ta, A) views by differentiable torch ops: the node sees the layout the C ABI takes
+        sg = sigma.to(torch.float32).reshape(-1)
+        sg = sg.expand(B) if sg.numel() == 1 and B > 1 else sg
+        x = action.to(torch.float32).reshape(B, eng.Ta, eng.A)
+        if context is None:
+            tok, tok2, g, Bs, names, params = self._train_inputs(eng, state, goal, im._arch == "mdtv", uncond)
+            if Bs != B:
+                raise ValueError(f"state holds {Bs} samples, action {B}")
+            s_tok = eng._in(sg, (B,)) if eng.sigma_in_context else None  # the sigma token leads the context
+            enc = [(n, p) for n, p in zip(names, params) if not eng.decoder_side(n)]  # the decoder's get theirs from the node below
+            context = HipContextOnly.apply(eng, state, tok, tok2, g, im._arch == "mdtv", drop, s_tok, [n for n, _ in enc],
+                                           *[p for _, p in enc])
+            im.latent_encoder_emb = context
+        else:
+            eng.train_prepare()
+            context = context.to(torch.float32)
+        named = [(n, p) for n, p in im.named_parameters() if ("inner_model." + n) in eng._grad_layout and eng.decoder_side(n)]
+        return HipDenoise.apply(eng, context, x, sg, drop, [n for n, _ in named], *[p for _, p in named])
+
     # -- additions ---------------------------------------------------------------------------
     @contextmanager
     def cached_context(self, state, goal):

@@ -444,6 +444,37 @@ class HipEngine:
                                                  _ptr(d_goal), self._stream())
         return grads, d_tok, d_tok2, d_goal
 
+    def decoder_side(self, name: str) -> bool:
+        """Whether the decoder half (mdt_train_denoise_fwd) reads parameter ``name`` (module-relative): the action embedding and
+        head, the decoder blocks, and the sigma embedding where sigma conditions the decoder -- as a context token it is the
+        encoder's."""
+        return name.startswith(("decoder.", "action_pred.", "action_emb.")) or \
+            (name.startswith("sigma_emb.") and not self.sigma_in_context)
+
+    def train_denoise_fwd(self, ctx: torch.Tensor, x: torch.Tensor, sigma: torch.Tensor, drop=None):
+        """D(x; sigma) against the context tensor ``ctx`` with a tape (mdt_train_denoise_fwd); inputs as ``_in`` leaves them."""
+        self.train_prepare()
+        self.sync_params()
+        B = x.shape[0]
+        if tuple(ctx.shape) != (B, self.Te, self.D):
+            raise ValueError(f"context must be ({B},{self.Te},{self.D}), got {tuple(ctx.shape)}")
+        out = torch.empty((B, self.Ta, self.A), device=self.device, dtype=torch.float32)
+        tape = C.c_int32(-1)  # (the call writes its tape only: the handle's cached context, and ctx_generation, stay)
+        _lib.call(self.lib.mdt_train_denoise_fwd, self.handle, _ptr(ctx), _ptr(x), _ptr(sigma), B,
+                                                  None if drop is None else C.byref(drop), _ptr(out), C.byref(tape), self._stream())
+        return out, int(tape.value)
+
+    def train_denoise_bwd(self, tape: int, g: torch.Tensor, B: int, needs, want_params: bool):
+        """mdt_train_denoise_bwd: (flat gradient buffer or None, d_ctx, d_x, d_sigma), each None unless ``needs`` asks for it."""
+        grads = torch.zeros(self._grad_numel, device=self.device, dtype=torch.float32) if want_params else None
+        d_ctx = torch.empty((B, self.Te, self.D), device=self.device, dtype=torch.float32) if needs[0] else None
+        d_x = torch.empty((B, self.Ta, self.A), device=self.device, dtype=torch.float32) if needs[1] else None
+        d_sigma = torch.empty((B,), device=self.device, dtype=torch.float32) if needs[2] else None
+        g_ = self._in(g, (B, self.Ta, self.A))
+        _lib.call(self.lib.mdt_train_denoise_bwd, self.handle, tape, _ptr(g_), _ptr(grads), _ptr(d_ctx), _ptr(d_x), _ptr(d_sigma),
+                                                  self._stream())
+        return grads, d_ctx, d_x, d_sigma
+
     def denoise_vjp(self, state: dict, x: torch.Tensor, goal: torch.Tensor, sigma: torch.Tensor, v: torch.Tensor):
         """(D(x; sigma), (dD/dx)^T v): the eval-mode denoiser and its vector-Jacobian product w.r.t. the noisy actions
         (mdt_denoise_vjp: a tape-keeping forward plus an input-gradient-only backward)."""
@@ -575,7 +606,8 @@ class HipScoreNetwork(nn.Module):
             # forward values are exact, but no autograd graph is recorded
             raise NotImplementedError(
                 "autograd through the HIP denoiser is not implemented yet (SURVEY.md 8(f) item 1); wrap the call "
-                "in torch.no_grad() for inference / loss evaluation")
+                "in torch.no_grad() for inference / loss evaluation.  GCDenoiser.denoise_grad is the explicit, "
+                "differentiable form of this call (autograd through D(x; sigma) on the HIP path)")
 
     # -- reference API ---------------------------------------------------------------------------
     def _goals(self, goals: torch.Tensor, uncond: bool) -> torch.Tensor:
