@@ -12,7 +12,8 @@
  * The host mirror (mdt_policy_amd/models/img_generation/masked_transformer_decoder.py) runs every Linear on the fp32-MFMA
  * GEMM (mdt_op_gemm forward, mdt_op_linear_bwd backward) and the row / token kernels below; gathers, residual adds and
  * the loss are PyTorch-ROCm glue.  fp32, row-major, device pointers 16-byte aligned.  Its self-attention runs on
- * mdt_op_attn_mid_* up to 128 tokens (the shipped 102) and on mdt_op_attn_long_* above that, up to 4096.
+ * mdt_op_attn_mid_* up to 128 tokens (the shipped 102) wherever the LDS rule below holds the shape in every direction
+ * that will run, and on mdt_op_attn_long_* otherwise, up to 4096 tokens.
  */
 #ifndef MDT_MAE_H
 #define MDT_MAE_H
@@ -65,7 +66,16 @@ mdt_status mdt_op_scale_residual_rms_bwd(const float *x_new, const float *g_norm
 
 /* Unmasked multi-head self-attention over T <= 128 tokens (voltron Attention.forward):
  *   qkv (B*T, 3*H*hd) = q | k | v column blocks (row stride ld_qkv), head h at columns h*hd;
- *   out (B*T, H*hd) = softmax(q k^T * scale) v.   hd in {16, 24, 32, 48, 64}.  One workgroup per (sample, head). */
+ *   out (B*T, H*hd) = softmax(q k^T * scale) v.   hd in {16, 24, 32, 48, 64}.  One workgroup per (sample, head).
+ *
+ * LDS rule (one workgroup holds a whole (sample, head); the limit is 160 KiB = 163840 bytes).  With T16 = T rounded up to a
+ * multiple of 16, the ops refuse (MDT_ERR_UNSUPPORTED, "does not fit LDS", nothing launched) a shape whose need exceeds it:
+ *   forward   4 * (3 * T16 * (hd + 4) + 64 * (T16 + 4) + 16)       bytes   (q, k, v rows; four waves' probability tiles)
+ *   backward  4 * (5 * T16 * (hd + 4) + T16 * (T16 + 4) + 144)     bytes   (q, k, v, dO, dQ rows; one T16 x T16 matrix)
+ * The forward holds every head dim up to T = 128.  The backward holds hd 16 / 24 / 32 up to T = 128, hd 48 up to T = 96
+ * (138816 bytes; T = 97: 169024) and hd 64 up to T = 80 (136256 bytes; T = 81: 169536).  A caller that will differentiate
+ * a shape the backward refuses runs mdt_op_attn_long_* in BOTH directions (the long backward needs the forward's lse): the
+ * host mirror's attention_route() does. */
 mdt_status mdt_op_attn_mid_fwd(const float *qkv, int64_t ld_qkv, float *out, int64_t ld_out, int64_t B, int32_t H,
                                int32_t hd, int32_t T, float scale, void *stream);
 /* d_qkv (B*T, 3*H*hd; same layout, overwritten) from d_out; the probabilities are recomputed from qkv, `out` is the

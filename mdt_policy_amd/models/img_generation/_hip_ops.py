@@ -293,16 +293,17 @@ class HipLinear(torch.autograd.Function):
         lib = _lib.load()
         w2d = weight.reshape(weight.shape[0], -1)
         N, K = w2d.shape
-        x2 = _c(x).reshape(-1, K)
+        x2 = _c(x).reshape(x.numel() // K, K)
         M = x2.shape[0]
         need_t = x.requires_grad
         wp, wt = packs.get(w2d, weight, need_t)
         out = torch.empty((M, N), device=x2.device, dtype=torch.float32)
-        a = _lib.GemmArgs()
-        a.A, a.lda, a.Wp, a.out, a.ldo, a.M, a.N, a.K = x2.data_ptr(), K, wp.data_ptr(), out.data_ptr(), N, M, N, K
-        a.bias = None if bias is None else _c(bias).data_ptr()
-        a.shift_off, a.scale_off, a.gate_off, a.rows_per_sample, a.gin, a.gout, a.goff = -1, -1, -1, 1, 1, 1, 0
-        _lib.check(lib.mdt_op_gemm(C.byref(a), _stream(x2)))
+        if M:  # no rows (a mask that keeps no patch): nothing to launch, the output is empty
+            a = _lib.GemmArgs()
+            a.A, a.lda, a.Wp, a.out, a.ldo, a.M, a.N, a.K = x2.data_ptr(), K, wp.data_ptr(), out.data_ptr(), N, M, N, K
+            a.bias = None if bias is None else _c(bias).data_ptr()
+            a.shift_off, a.scale_off, a.gate_off, a.rows_per_sample, a.gin, a.gout, a.goff = -1, -1, -1, 1, 1, 1, 0
+            _lib.check(lib.mdt_op_gemm(C.byref(a), _stream(x2)))
         ctx.save_for_backward(x2, weight, bias)
         ctx.packs, ctx.xshape = packs, x.shape
         _count_uses(ctx, ((weight, 1), (bias, 2)))
@@ -317,6 +318,10 @@ class HipLinear(torch.autograd.Function):
         M = x2.shape[0]
         dY = _c(g).reshape(M, N)
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], bias is not None and ctx.needs_input_grad[2]
+        if M == 0:  # the sums over no rows: zero weight and bias gradients, an empty input gradient, no launch
+            _arm_reset()
+            return (g.new_zeros(ctx.xshape) if need_x else None, torch.zeros_like(weight) if need_w else None,
+                    torch.zeros_like(bias) if need_b else None, None)
         wt = ctx.packs.get(w2d, weight, True)[1] if need_x else None
         dX, dW, db = _linear_bwd(lib, x2, dY, N, K, wt, need_x, need_w, need_b, beside=_dw_beside((weight, bias)))
         return (None if dX is None else dX.reshape(ctx.xshape), None if dW is None else dW.reshape(weight.shape), db, None)
@@ -521,12 +526,37 @@ class HipPatchMSE(torch.autograd.Function):
 
 MID_TMAX = 128    # mdt_op_attn_mid_*: a whole (sample, head) in one workgroup's registers and LDS
 LONG_TMAX = 4096  # mdt_op_attn_long_*: flash-style, keys streamed through LDS
+MID_LDS_BUDGET = 160 * 1024
+HEAD_DIMS = (16, 24, 32, 48, 64)
+ATTN_LAUNCHES = {"mid": 0, "long": 0}  # forwards of HipSelfAttention per op (tests pin the routing with it, as SIDE_LAUNCHES)
+
+
+def mid_attention_lds_bytes(hd: int, T: int, backward: bool) -> int:
+    """LDS of one (sample, head) workgroup of mdt_op_attn_mid_fwd / _bwd as include/mdt_mae.h states it, T16 = T rounded up
+    to a multiple of 16: forward q, k, v rows of hd + 4 floats and four waves' 16 x (T16 + 4) probability tiles; backward
+    q, k, v, dO, dQ rows and one T16 x (T16 + 4) matrix.  The op refuses a shape above MID_LDS_BUDGET."""
+    T16 = (T + 15) // 16 * 16
+    if backward:
+        return 4 * (5 * T16 * (hd + 4) + T16 * (T16 + 4) + 144)
+    return 4 * (3 * T16 * (hd + 4) + 64 * (T16 + 4) + 16)
+
+
+def attention_route(hd: int, T: int, needs_grad: bool) -> str:
+    """Which op HipSelfAttention runs: "mid" up to MID_TMAX tokens while the mid op's LDS holds the shape -- its forward, and,
+    when a gradient can be asked for, its backward too (the backward of a head dim above 32 keeps a T x T matrix in LDS: hd 48
+    up to 96 tokens, hd 64 up to 80) --, else "long" (1 <= T <= LONG_TMAX).  The forward decides for both directions: the long
+    backward needs the log-sum-exp its forward saves."""
+    if T > MID_TMAX or mid_attention_lds_bytes(hd, T, False) > MID_LDS_BUDGET:
+        return "long"
+    if needs_grad and mid_attention_lds_bytes(hd, T, True) > MID_LDS_BUDGET:
+        return "long"
+    return "mid"
 
 
 class HipSelfAttention(torch.autograd.Function):
-    """qkv (B, T, 3 D) = q | k | v -> softmax(q k^T * scale) v (B, T, D), H heads, unmasked.  T <= 128 runs the mid-length op
-    (the shipped 102-token head), 128 < T <= 4096 the flash-style long op, which also keeps the rows' log-sum-exp for the
-    backward."""
+    """qkv (B, T, 3 D) = q | k | v -> softmax(q k^T * scale) v (B, T, D), H heads, unmasked.  ``attention_route`` picks the op:
+    the mid-length one up to 128 tokens (the shipped 102-token head) where its LDS holds the shape in the directions that will
+    run, else the flash-style long op (up to 4096 tokens), which also keeps the rows' log-sum-exp for the backward."""
 
     @staticmethod
     def forward(ctx, qkv, n_heads: int, scale: float):
@@ -535,7 +565,8 @@ class HipSelfAttention(torch.autograd.Function):
         D = D3 // 3
         q = _c(qkv)
         out = torch.empty((B, T, D), device=q.device, dtype=torch.float32)
-        if T <= MID_TMAX:
+        route = attention_route(D // n_heads, T, bool(ctx.needs_input_grad[0]))
+        if route == "mid":
             _lib.check(lib.mdt_op_attn_mid_fwd(q.data_ptr(), D3, out.data_ptr(), D, B, n_heads, D // n_heads, T, float(scale), _stream(q)))
             ctx.save_for_backward(q, out)  # the output is kept anyway (input of the projection that follows)
         else:
@@ -543,6 +574,7 @@ class HipSelfAttention(torch.autograd.Function):
             _lib.check(lib.mdt_op_attn_long_fwd(q.data_ptr(), D3, out.data_ptr(), D, lse.data_ptr(), B, n_heads, D // n_heads, T,
                                                 float(scale), _stream(q)))
             ctx.save_for_backward(q, out, lse)
+        ATTN_LAUNCHES[route] += 1
         ctx.cfg = (n_heads, float(scale))
         return out
 

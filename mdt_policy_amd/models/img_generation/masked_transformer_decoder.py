@@ -14,6 +14,11 @@ What runs where: every Linear (context projection, patch embedding of the VISIBL
 project / mlp.1 of the 6 blocks, patch prediction -- 98 % of the FLOPs) on the fp32-MFMA GEMM, RMSNorm / SwishGLU / the
 102-token attention on their HIP kernels; the random mask, gathers, residual adds and the loss are PyTorch-ROCm glue, as in
 the agent's own loss code.  No eager fallback: CPU tensors raise.
+
+Accepted: decoder_embed_dim a multiple of 16 up to 512, head dims 16 / 24 / 32 / 48 / 64, hidden width, context_dim and
+patch_size^2 * in_channels multiples of 16, any depth (0: the decoder norm alone), num_images = 2, up to 4096 decoder tokens, a
+mask that keeps no patch.  The constructor builds the reference's parameter tree for any arguments; ``forward`` raises
+NotImplementedError naming the limit for a configuration outside this envelope.
 """
 from __future__ import annotations
 
@@ -116,10 +121,29 @@ class MaskedTransformerImgDecoder(nn.Module):
         self.decoder_norm = RMSNorm(decoder_embed_dim)
         self.decoder_patch_prediction = nn.Linear(decoder_embed_dim, (patch_size ** 2) * in_channels, bias=True)
         self.video_gen = video_gen
+        self._refusal = self._outside_the_envelope(context_dim)
         self._packs = ops.PackedWeights()
         from ...utils import weight_cache
         weight_cache.track(self)
         self.initialize_weights()
+
+    def _outside_the_envelope(self, context_dim: int) -> Optional[str]:
+        """None, or why the HIP kernels cannot run this configuration (the constructor itself accepts what the reference's
+        does: the parameter tree exists either way; ``forward`` raises with this text)."""
+        d, H, E = self.decoder_embed_dim, self.decoder_n_heads, self.patch_size ** 2 * self.in_channels
+        hidden = int(self.mlp_ratio * d)
+        if d % 16 or not 16 <= d <= 512:
+            return f"decoder_embed_dim {d}: the HIP norms and GEMM operands take a multiple of 16 from 16 to 512"
+        if d % H or d // H not in ops.HEAD_DIMS:
+            return (f"decoder_embed_dim {d} / decoder_n_heads {H}: the HIP attention covers head dims "
+                    f"{' / '.join(map(str, ops.HEAD_DIMS))}")
+        if self.decoder_depth and (hidden < 16 or hidden % 16):
+            return f"mlp hidden width int(mlp_ratio * decoder_embed_dim) = {hidden}: the SwishGLU GEMMs take a multiple of 16"
+        if E % 16:
+            return f"patch_size^2 * in_channels = {E} values per patch: the patch GEMMs take a multiple of 16"
+        if context_dim % 16:
+            return f"context_dim {context_dim}: the context projection takes a multiple of 16"
+        return None
 
     # -- initialisation (reference :176-203) ---------------------------------------------------------
     def initialize_weights(self) -> None:
@@ -224,12 +248,23 @@ class MaskedTransformerImgDecoder(nn.Module):
     # -- reference API -------------------------------------------------------------------------------
     def forward(self, context, target_images, img_gen_frame_diff: int = 3, noise: Optional[torch.Tensor] = None):
         """-> (reconstructions (B, num_images, n_patches, p*p*C), mask, restore_idxs, visible_patches) (reference :215-283)."""
+        uses = dict(ops._USES)
+        try:
+            return self._forward(context, target_images, noise)
+        except BaseException:  # a forward that raised half-way leaves no node to run: its parameter uses are not uses
+            ops._USES.clear()
+            ops._USES.update(uses)
+            raise
+
+    def _forward(self, context, target_images, noise: Optional[torch.Tensor]):
         if context.device.type != "cuda":
             raise RuntimeError("MaskedTransformerImgDecoder runs only on a ROCm GPU; there is no CPU execution path in mdt_policy_amd")
         d, X, n = self.decoder_embed_dim, self.num_images, self.num_patches
         B = context.shape[0]
         if X != 2 or target_images.shape[1] != 2:
             raise NotImplementedError("the decoder pairs frame 0 and frame K (num_images = 2), as the reference's forward does")
+        if self._refusal:
+            raise NotImplementedError(self._refusal)
         T = context.shape[1] + X * n
         if T > ops.LONG_TMAX:
             raise NotImplementedError(f"{T} decoder tokens: the HIP attention covers up to {ops.LONG_TMAX} (224 x 224 / 8 has "

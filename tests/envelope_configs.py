@@ -6,7 +6,10 @@ them (tests/test_cpu_abi.py).
 RESAMPLER_ENVELOPE and MAP_ENVELOPE do the same for the two other handle modules, the Perceiver resampler (mdt_resampler_*)
 and the MAP pooling block (mdt_map_pool_*): tests/test_gpu_module_envelope.py runs them, tests/test_cpu_abi.py checks the
 constructors' validation, tests/golden/make_golden.py g18 records the reference's results for the cases named in
-RESAMPLER_GOLDEN / MAP_GOLDEN."""
+RESAMPLER_GOLDEN / MAP_GOLDEN.
+
+MAE_ENVELOPE is the same for the masked-image head (MaskedTransformerImgDecoder): tests/test_mae_envelope.py (CPU) and
+tests/test_gpu_mae_envelope.py run it, make_golden.py g15 records the reference's results for the cases in MAE_GOLDEN."""
 from mdt_policy_amd import configs
 
 
@@ -167,3 +170,102 @@ MAP_REFUSED_AT_CREATE = [
     (dict(n_latents=16, embed_dim=96, output_dim=48, n_heads=1, mlp_hidden=120), 2),
     (dict(_MBASE, n_latents=0), 2), (dict(_MBASE, n_latents=17), 2), (dict(_MBASE, embed_dim=100), 2),
 ]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Masked-image head.  The mid attention's LDS rule is restated here from the text of include/mdt_mae.h, NOT read from the
+# library or from the Python routing function: a boundary on which they disagree is a finding.
+# ------------------------------------------------------------------------------------------------------------------
+MAE_MID_LDS_BUDGET = 160 * 1024
+MAE_MID_TMAX, MAE_LONG_TMAX = 128, 4096
+
+
+def mae_mid_lds_bytes(hd, T, backward):
+    """include/mdt_mae.h: T16 = T rounded up to 16; forward (3 T16 (hd + 4) + 64 (T16 + 4) + 16) floats, backward
+    (5 T16 (hd + 4) + T16 (T16 + 4) + 144) floats."""
+    T16 = -(-T // 16) * 16
+    floats = 5 * T16 * (hd + 4) + T16 * (T16 + 4) + 144 if backward else 3 * T16 * (hd + 4) + 64 * (T16 + 4) + 16
+    return 4 * floats
+
+
+def mae_route(hd, T, train):
+    """The op the head's attention must run ("mid" / "long") as the header documents it."""
+    if T > MAE_MID_TMAX or mae_mid_lds_bytes(hd, T, False) > MAE_MID_LDS_BUDGET:
+        return "long"
+    return "long" if train and mae_mid_lds_bytes(hd, T, True) > MAE_MID_LDS_BUDGET else "mid"
+
+
+# the shipped head (conf/model/img_gen/masked_transformer.yaml at gen_img_res 112) and the `tiny` fixture's kwargs
+MAE_SHIPPED = dict(resolution=112, patch_size=16, decoder_depth=6, decoder_embed_dim=192, decoder_n_heads=8, context_dim=384,
+                   mlp_ratio=4, in_channels=3, norm_pixel_loss=True, num_images=2, mask_ratio=0.75, symmetric_mask=True,
+                   img_gen_frame_diff=3)
+MAE_TINY = dict(MAE_SHIPPED, resolution=64, decoder_depth=2, decoder_embed_dim=64, decoder_n_heads=4, context_dim=128, mask_ratio=0.5)
+
+
+def _e(base=MAE_TINY, ctx=4, batches=(1, 3), train_b=2, n_keep=None, T=None, refused=None, seed=301, **over):
+    """kwargs of MaskedTransformerImgDecoder; context tokens; inference batches; the batch of the training step; the number of
+    visible patches per frame and of decoder tokens the comment claims (checked by the CPU tier); refused: (exception type name,
+    pattern its message must match) when the call must raise; seed: of the inputs (weights: 151, "rich")."""
+    return dict(kwargs=dict(base, **over), ctx=ctx, batches=list(batches), train_b=train_b, n_keep=n_keep, T=T, refused=refused,
+                seed=seed)
+
+
+def _w(d, heads, **over):
+    return dict(decoder_embed_dim=d, decoder_n_heads=heads, context_dim=over.pop("context_dim", 64), decoder_depth=over.pop("decoder_depth", 2), **over)
+
+
+MAE_ENVELOPE = {
+    # every loop at its first trip: d 16, one head of 16, 8/4 (n = 4, E = 16), one channel, one block, hidden 16, one context
+    # token; mask 0.5 keeps 2: T = 1 + 2 * 4 = 9
+    "e_min": _e(ctx=1, n_keep=2, T=9, resolution=8, patch_size=4, in_channels=1, mlp_ratio=1, mask_ratio=0.5,
+                **_w(16, 1, context_dim=16, decoder_depth=1)),
+    # the shipped head twice as wide: 8 heads of 48 at 102 tokens -- the mid backward holds hd 48 up to 96 (training: long op)
+    "e_d384_hd48_t102": _e(MAE_SHIPPED, n_keep=12, T=102, **_w(384, 8)),
+    # 8 heads of 64 at 102 tokens (mid backward up to 80); SwishGLU epilogues at K = 512, the limit of aux_mode (one K chunk:
+    # mdt_gemm_kchunk splits only above 512), the backward's dx_act_u at N = 512, row kernels at the D limit (all column groups live)
+    "e_d512_hd64_t102": _e(MAE_SHIPPED, n_keep=12, T=102, mlp_ratio=2, **_w(512, 8)),
+    # hd 64: 80 tokens is the last shape on the mid backward, 81 the first off it (96/16: n = 36, + 8 / 9 context tokens)
+    "e_hd64_t80": _e(ctx=8, n_keep=18, T=80, resolution=96, **_w(128, 2)),
+    "e_hd64_t81": _e(ctx=9, n_keep=18, T=81, resolution=96, **_w(128, 2)),
+    # hd 48: 96 | 97
+    "e_hd48_t96": _e(ctx=24, n_keep=18, T=96, resolution=96, **_w(96, 2)),
+    "e_hd48_t97": _e(ctx=25, n_keep=18, T=97, resolution=96, **_w(96, 2)),
+    # the hand-over between the two ops inside the head: 128 tokens (mid, 8 tiles) | 129 (long); 112/16 + 30 / 31 context tokens
+    "e_t128": _e(ctx=30, n_keep=24, T=128, resolution=112, **_w(96, 4)),
+    "e_t129": _e(ctx=31, n_keep=24, T=129, resolution=112, **_w(96, 4)),
+    # 32 heads of 16 at d 512 (64/16: T = 36, three tiles); the forward walks hpw heads per workgroup once B * H / hpw reaches
+    # 1024 workgroups: B = 3 hpw 1 (96 workgroups), B = 64 hpw 2 (1024), B = 130 hpw 4 (1040)
+    "e_h32_d512": _e(batches=(1, 3, 64, 130), n_keep=8, T=36, mlp_ratio=1, **_w(512, 32)),
+    # one channel, 32/8 (n = 16, E = 64): channel stride 1 in the patch loss's image index
+    "e_c1_p8": _e(n_keep=8, T=36, resolution=32, patch_size=8, in_channels=1, **_w(64, 4)),
+    # four channels, 16/4 (n = 16, E = 64), the reference's other masking branch, 2 heads of 24
+    "e_c4_p4_asym": _e(n_keep=8, T=36, resolution=16, patch_size=4, in_channels=4, symmetric_mask=False, **_w(48, 2)),
+    # 64/32 (n = 4): the patch embedding is a product with K = 3072 (deep-K pipe), the prediction one with N = 3072
+    "e_p32": _e(n_keep=2, T=12, resolution=64, patch_size=32, **_w(64, 4)),
+    # no blocks: the plain HipRMSNorm branch of forward
+    "e_depth0": _e(n_keep=8, T=36, **_w(64, 4, decoder_depth=0)),
+    # hidden 240, 2H = 480: SwishGLU forward tiling <2,2,4,3> (N % 32 only), backward <2,2,4,4> (240 % 192 != 0)
+    "e_ratio_2p5": _e(n_keep=8, T=36, mlp_ratio=2.5, **_w(96, 4)),
+    # 2H = 1024: SwishGLU forward tiling <2,4,4,3> away from K = 192
+    "e_glu256_d128": _e(n_keep=8, T=36, mlp_ratio=4, **_w(128, 4)),
+    # the constructor's default mask_ratio at the shipped shape: int(49 * (1 - 0.9)) = 4 visible patches
+    "e_shipped_mask09": _e(MAE_SHIPPED, n_keep=4, T=102, mask_ratio=0.9),
+    # 32/16 (n = 4), mask 0.25: one patch removed per sample, mask.sum() = B
+    "e_one_masked": _e(n_keep=3, T=12, resolution=32, mask_ratio=0.25, **_w(64, 4)),
+    # 48/16 (n = 9) at the default mask 0.9: int(9 * 0.1) = 0 visible patches -- an empty patch-embedding product, zero
+    # gradients for patch2embed (the reference embeds all patches and gathers none)
+    "e_keep0": _e(n_keep=0, T=22, resolution=48, mask_ratio=0.9, **_w(64, 4)),
+    # the tiny kwargs at B = 240: 240 * 36 = 8640 decoder rows, the >= 8192-row GEMM dispatch at K = 64 / 256 and the
+    # bf16-split dW products
+    "e_rows8192": _e(batches=(240,), train_b=240, n_keep=8, T=36),
+    # ---- refused: a Python exception that names the limit
+    "x_d528": _e(refused=("NotImplementedError", "512"), **_w(528, 11)),                       # norms stop at 512
+    "x_hd12": _e(refused=("NotImplementedError", "head dim"), **_w(48, 4)),                    # 4 heads of 12
+    "x_hidden120": _e(refused=("NotImplementedError", "120"), mlp_ratio=1.5, **_w(80, 5)),     # int(1.5 * 80) = 120
+    "x_num_images3": _e(refused=("NotImplementedError", "num_images"), num_images=3),
+    "x_tokens_8196": _e(MAE_SHIPPED, refused=("NotImplementedError", "4096"), resolution=512, patch_size=8, decoder_depth=1),
+}
+
+# recorded from the reference by make_golden.py g15 at B = 2 (tests/golden/g15_mae_<name>.npz)
+MAE_GOLDEN = ["e_min", "e_c1_p8", "e_c4_p4_asym", "e_p32", "e_keep0", "e_one_masked", "e_depth0"]
+MAE_GOLDEN_B = 2

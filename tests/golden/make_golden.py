@@ -622,19 +622,16 @@ def install_voltron_stand_in():
         stub("PIL", Image=None)
 
 
-def g15():
-    """Masked generative foresight head: the reference's MaskedTransformerImgDecoder.forward + compute_loss (+ gradients)
-    around stood-in Voltron blocks (see install_voltron_stand_in)."""
-    install_voltron_stand_in()
+def _g15_cases(cases, writer):
     from mdt.models.img_generation.masked_transformer_decoder import MaskedTransformerImgDecoder
 
-    for name, (kw, B, Tc) in G15_MAE.items():
+    for name, (kw, B, Tc) in cases.items():
         m = MaskedTransformerImgDecoder(**kw)
         sd = m.state_dict()
         new = synthetic.fill_state_dict([(k, tuple(v.shape)) for k, v in sd.items() if k != "decoder_pe"], 151, "rich")
         m.load_state_dict({**{k: torch.from_numpy(v) for k, v in new.items()}, "decoder_pe": sd["decoder_pe"]}, strict=True)
         ctx = torch.from_numpy(synthetic.normal("ctx", (B, Tc, kw["context_dim"]), 152)).requires_grad_()
-        img = torch.from_numpy(synthetic.normal("img", (B, 2, 3, kw["resolution"], kw["resolution"]), 153))
+        img = torch.from_numpy(synthetic.normal("img", (B, 2, kw["in_channels"], kw["resolution"], kw["resolution"]), 153))
         torch.manual_seed(154)
         rec, mask, restore, visible = m(ctx, img)
         loss = m.compute_loss(img, rec, mask, restore)
@@ -647,9 +644,25 @@ def g15():
             grads[k] = [float(g.norm()), float(g.sum())] + [float(v) for v in g.flatten()[:6]]
         meta = dict(kwargs=kw, B=B, Tc=Tc, weight_seed=151, ctx_seed=152, img_seed=153, profile="rich", grads=grads,
                     state_dict=[[k, list(v.shape)] for k, v in sd.items()], named_parameters=[k for k, _ in m.named_parameters()])
-        save(f"g15_mae_{name}.npz", meta, rec=rec.detach().numpy(), mask=mask.numpy(), restore=restore.numpy(),
-             visible=visible.detach().numpy(), loss=np.array(loss.item(), np.float32), d_ctx=ctx.grad.numpy(),
-             decoder_pe=sd["decoder_pe"].numpy())
+        writer(f"g15_mae_{name}.npz", meta, rec=rec.detach().numpy(), mask=mask.numpy(), restore=restore.numpy(),
+               visible=visible.detach().numpy(), loss=np.array(loss.item(), np.float32), d_ctx=ctx.grad.numpy(),
+               decoder_pe=sd["decoder_pe"].numpy())
+
+
+def g15_envelope():
+    """The cases of tests/envelope_configs.py MAE_GOLDEN (other in_channels, patch sizes, context lengths, n_keep 0, one
+    removed patch, no blocks) through the same reference calls, the same arrays per file."""
+    install_voltron_stand_in()
+    from tests import envelope_configs as E
+    _g15_cases({n: (E.MAE_ENVELOPE[n]["kwargs"], E.MAE_GOLDEN_B, E.MAE_ENVELOPE[n]["ctx"]) for n in E.MAE_GOLDEN}, save_fixed)
+
+
+def g15():
+    """Masked generative foresight head: the reference's MaskedTransformerImgDecoder.forward + compute_loss (+ gradients)
+    around stood-in Voltron blocks (see install_voltron_stand_in); then the envelope cases (g15_envelope)."""
+    install_voltron_stand_in()
+    _g15_cases(G15_MAE, save)
+    g15_envelope()
 
 
 G16_PROPRIO = {

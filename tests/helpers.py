@@ -123,3 +123,33 @@ def check_grad_summaries(named_grads, want, what):
         g, w = np.array(grad_summary(named_grads[k])), np.array(w)
         tol = 2e-3 * abs(w[0]) + 1e-6
         assert np.all(np.abs(g - w) <= tol), f"{what} {k}: {g} vs {w}"
+
+
+def mae_inputs(kw, B, n_ctx, seed):
+    """(context, images, mask noise) of a masked-image head case from the deterministic generator."""
+    n = (kw["resolution"] // kw["patch_size"]) ** 2
+    ctx = torch.from_numpy(synthetic.normal("ctx", (B, n_ctx, kw["context_dim"]), seed))
+    img = torch.from_numpy(synthetic.normal("img", (B, 2, kw["in_channels"], kw["resolution"], kw["resolution"]), seed + 1))
+    noise = torch.from_numpy(synthetic.uniform("mask_noise", (B, n) if kw["symmetric_mask"] else (B, 2, n), seed + 2))
+    return ctx, img, noise
+
+
+def mae_params(state_dict_shapes, kw, seed=151, profile="rich"):
+    """{state_dict name: tensor} of a head: the generator's values, decoder_pe from the oracle's position table."""
+    from oracle import mae_oracle as O
+    shapes = [(k, tuple(s)) for k, s in state_dict_shapes if k != "decoder_pe"]
+    P = {k: torch.from_numpy(v) for k, v in synthetic.fill_state_dict(shapes, seed, profile).items()}
+    table = O.position_table(kw["decoder_embed_dim"], kw["resolution"] // kw["patch_size"])
+    P["decoder_pe"] = torch.from_numpy(table).float().unsqueeze(0)
+    return P
+
+
+def mae_envelope_fixture(name):
+    """(meta, fixture arrays, params, context, images, shuffle) of a g15 envelope fixture (tests/envelope_configs.py MAE_GOLDEN)."""
+    meta, fx = load_fixture(f"g15_mae_{name}.npz")
+    kw = meta["kwargs"]
+    P = mae_params(meta["state_dict"], kw, meta["weight_seed"], meta["profile"])
+    ctx = torch.from_numpy(synthetic.normal("ctx", (meta["B"], meta["Tc"], kw["context_dim"]), meta["ctx_seed"]))
+    img = torch.from_numpy(synthetic.normal("img", (meta["B"], 2, kw["in_channels"], kw["resolution"], kw["resolution"]), meta["img_seed"]))
+    shuffle = torch.argsort(torch.from_numpy(fx["restore"]), dim=1)
+    return meta, fx, P, ctx, img, shuffle
