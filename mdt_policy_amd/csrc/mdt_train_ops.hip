@@ -109,13 +109,24 @@ int64_t mdt_linear_bwd_scratch(int64_t M, int64_t N, int64_t K) {
 
 mdt_status mdt_linear_bwd(const mdt_linear_bwd_args& a, hipStream_t s, mdt_colsum_entry* defer_bias, float* bias_space) {
     if (a.M < 1 || a.N < 1 || a.K < 1 || (a.K % 16)) return fail(MDT_ERR_INVALID_ARG, "linear_bwd: bad shape");
+    // every refusal comes before the first launch: a refused call has enqueued nothing, so a caller may correct its arguments
+    // and call again without counting a gradient twice
+    if (a.dW && (a.N % 16)) return fail(MDT_ERR_INVALID_ARG, "linear_bwd: N must be a multiple of 16 for dW");
+    if (a.dX) {
+        if (!a.Wt || (a.N % 16)) return fail(MDT_ERR_INVALID_ARG, "linear_bwd: dX needs the packed W^T and N % 16 == 0");
+        if (a.dx_act_u) {
+            if (a.accumulate_dx || a.N > 512) return fail(MDT_ERR_INVALID_ARG, "linear_bwd: dx_act_u needs accumulate_dx = 0 and N <= 512");
+            if (a.dx_act == MDT_ACT_SWIGLU && a.ldxo < 2 * (int64_t)a.K)
+                return fail(MDT_ERR_INVALID_ARG, "linear_bwd: SwishGLU backward writes 2 K columns (ldxo >= 2 K)");
+        }
+    }
     if (defer_bias) defer_bias->src = nullptr;
     // the bias gradient rides on the transpose the dW path needs anyway (per-32-row column partials)
     const bool bias_from_partials = a.dbias && a.dW && !(a.N % 16);
     if (a.dbias && !bias_from_partials) LAUNCH(mdt_launch_colsum(a.dY, a.ldy, a.M, a.N, a.dbias, a.accumulate_dw, s));
     // (bias_from_partials: the dW path below also leaves the bias gradient -- per-slice column sums of dY from k_gemm_tn,
     //  or per-32-row partials from the transpose of the older path)
-    if (a.dW && !(a.N % 16) && !(a.ldy % 4) && !(a.ldx % 4)) {
+    if (a.dW && !(a.ldy % 4) && !(a.ldx % 4)) {
         // dW straight from dY and X (k_gemm_tn): S slices of the row reduction as one batched launch, partial products and
         // the bias gradient's per-slice column sums added up in a fixed order afterwards
         int S, L;
@@ -148,7 +159,6 @@ mdt_status mdt_linear_bwd(const mdt_linear_bwd_args& a, hipStream_t s, mdt_colsu
         if (defer) *defer_bias = mdt_colsum_entry{bpart, a.dbias, (int64_t)a.N, S, a.N, a.accumulate_dw};
         else if (a.dbias) LAUNCH(mdt_launch_colsum(bpart, a.N, S, a.N, a.dbias, a.accumulate_dw, s));
     } else if (a.dW) {
-        if (a.N % 16) return fail(MDT_ERR_INVALID_ARG, "linear_bwd: N must be a multiple of 16 for dW");
         int S, L;
         split_rows(a.M, a.N, a.K, &S, &L);
         const int64_t Mp = (int64_t)S * L;
@@ -175,16 +185,13 @@ mdt_status mdt_linear_bwd(const mdt_linear_bwd_args& a, hipStream_t s, mdt_colsu
         if (S > 1) LAUNCH(mdt_launch_colsum(parts, (int64_t)a.N * a.K, S, a.N * a.K, a.dW, a.accumulate_dw, s));
     }
     if (a.dX) {
-        if (!a.Wt || (a.N % 16)) return fail(MDT_ERR_INVALID_ARG, "linear_bwd: dX needs the packed W^T and N % 16 == 0");
         Lin w;
         w.wp = const_cast<float*>(a.Wt); w.bias = nullptr; w.N = a.K; w.K = a.N;
         mdt_gemm_args g = gemm_args(a.dY, a.ldy, w, a.dX, a.ldxo, a.M);
         g.residual = a.accumulate_dx;
         if (a.dx_act_u) {  // dX = (dY W) * act'(u): the activation's backward rides on this product's epilogue
-            if (a.accumulate_dx || a.N > 512) return fail(MDT_ERR_INVALID_ARG, "linear_bwd: dx_act_u needs accumulate_dx = 0 and N <= 512");
             g.aux = a.dx_act_u; g.aux_mode = 2; g.act = a.dx_act;
             if (a.dx_act == MDT_ACT_SWIGLU) {  // dX (M, 2K; ldxo) from d = dY W (M, K) and u (M, 2K; ldxo)
-                if (a.ldxo < 2 * (int64_t)a.K) return fail(MDT_ERR_INVALID_ARG, "linear_bwd: SwishGLU backward writes 2 K columns (ldxo >= 2 K)");
                 g.aux_mode = 4; g.act = MDT_ACT_NONE;
             }
         }
