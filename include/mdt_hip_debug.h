@@ -1,0 +1,95 @@
+/*
+ * mdt_hip_debug.h -- process-global test and measurement hooks of libmdt_hip.so.
+ *
+ * NOT part of the product boundary (mdt_hip.h and the operator headers): every setter here flips a launch choice for EVERY handle
+ * of the process, none is needed to run the model, and a host that binds the library should leave them alone.  The parity tests
+ * use them to pin one kernel form against another, bench.py and tools/ to measure one.  All of them write one table inside the
+ * library (csrc/mdt_internal.h: mdt_switches); a negative argument restores the default unless a hook says otherwise.  No other
+ * header includes this one.
+ */
+#ifndef MDT_HIP_DEBUG_H
+#define MDT_HIP_DEBUG_H
+
+#include <stdint.h>
+#include "mdt_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The split forms of mdt_op_mlp_split and of the wide LayerNorm-prologue products (mdt_gemm_args.Wp_split): 0 = the fp32 launches
+ * everywhere, 1 = on, negative = default (MDT_HIP_MLP_SPLIT from the environment; unset = 1). */
+void mdt_op_set_mlp_split(int32_t on);
+/* The model-level entry points run the MLP sublayer through mdt_op_mlp from `rows` rows (B * horizon) on; 0 = never (the two-GEMM
+ * sequence), -1 = default (1401; 768 where the split form applies).  The split form always needs 768 rows: below them a setting
+ * runs the fp32 form. */
+void mdt_op_set_mlp_fuse_min(int32_t rows);
+/* Rollout-sized model-level calls queue the products that do not depend on their neighbours in the launch chain (the sigma-MLP /
+ * adaLN table of mdt_sample_ddim, the MDTV token embedding) and let each ride as extra workgroups in the next split-K small-M
+ * launch.  0 = every product its own launch, 1 = on, -1 = default (on).  Same tiles, same order inside each product: results are
+ * bit-identical either way.
+ * mdt_op_side_jobs_paired: how many launches of this process have taken such a product along so far. */
+void mdt_op_set_side_jobs(int32_t on);
+int64_t mdt_op_side_jobs_paired(void);
+/* 1 = the K = 384 products that take the weight-stationary body (from 8192 rows on: the training step at B = 1024) run its
+ * THREE-WAY bf16 SPLIT form -- every fp32 operand as three bf16 parts, six v_mfma_f32_16x16x32_bf16 products per k32 step with fp32
+ * accumulation: fp32's product accuracy (not its bits) at 2.7x the fp32 matrix rate; 0 = the fp32 MFMA form; negative = default
+ * (MDT_HIP_WS_SPLIT from the environment; unset = 1). */
+void mdt_op_set_ws_split(int32_t on);
+/* 1 = from 8192 rows on the weight-gradient product dW = dY^T X (mdt_op_linear_bwd) runs as three-way bf16 splits of both operands;
+ * 0 = the fp32 MFMA kernel everywhere; negative = default (MDT_HIP_TN_SPLIT from the environment; unset = 1). */
+void mdt_op_set_tn_split(int32_t on);
+
+/* Wave schedule inside mdt_op_mlp's kernel.  Low byte = number of k-steps the second wave of every SIMD starts behind the first
+ * (0 = lockstep with a workgroup barrier between the two products), | 256 = MFMA loops at raised issue priority; -1 = default
+ * (18 | 256).  Every setting produces the same bits (the K order of both products does not depend on it). */
+void mdt_op_set_mlp_skew(int32_t v);
+
+/* Force the workgroup geometry of every following GEMM launch in this process.
+ * 0 = heuristic (default): up to 15 rows the split-K small-M kernel -- one workgroup per 16 columns, K divided between its
+ * 8 waves --; up to 512 rows the same kernel for the products whose half-height tiling would have fewer than 60 (LayerNorm
+ * prologue) / 100 (plain, <= 192 rows) / 160 (plain, <= 512 rows) tiles; up to 1400 rows the half-height tiled geometry 6;
+ * beyond, the widest row-tile geometry that still fills the chip;
+ * 1 = 4 waves 32x64; 2 = 8 waves 32x128; 3 = 8 waves 32x384; 4 = 8 waves 32x512; 5 = 4 waves 32x128; 6 = 4 waves 16x64;
+ * 7 = 4 waves 64x128; 8 = 4 waves 32x256; 9 = 4 waves 32x192;
+ * 10 / 12 / 16 = the TALL body (128-row tiles, both operands staged in LDS by LDS-DMA; plain prologue, K % 32 == 0;
+ * anything else falls back to the heuristic): 4 waves 128x128 / 128x64 / 128x96; 23 = 128x64 with a loader wave, 3 stages;
+ * -1 = the split-K small-M kernel wherever it applies.
+ * 30 = the weight-stationary body wherever it is supported, whatever the row count.
+ * Row-tile, tall and (fp32 form, mdt_op_set_ws_split(0)) weight-stationary geometries compute bit-identical results (same k order
+ * per output element); the small-M kernel and the weight-stationary body's bf16 split form (the default) agree to fp32 rounding. */
+void mdt_op_set_gemm_geometry(int32_t geometry);
+
+/* The model-level entry points compute the self-attention of a LARGE batch in the prologue of its output projection
+ * (mdt_op_attn_proj's contract on 32-row tiles, k_attn_proj_wide) from `rows` rows on: 0 = never (attention launch + projection
+ * GEMM; also switches off the one-workgroup-per-sample form, mdt_op_attn_xattn), -1 = default 1401. */
+void mdt_op_set_attn_wide_min(int32_t rows);
+
+/* Measurement hook: bracket every fused-MLP launch of the model-level calls that follow (mdt_sample_ddim, mdt_forward, ...)
+ * with a pair of HIP events on its stream; mdt_op_trace_mlp_read waits for them, writes up to `cap` durations in
+ * MICROSECONDS (launch order) to `us`, releases the events and returns how many it wrote.  The duration of the dominant
+ * kernel inside its launch chain, as a kernel trace reports it (bench.py's roofline.dominant_kernel).  Process-wide; not
+ * for use under stream capture. */
+void mdt_op_trace_mlp(int32_t enable);
+int32_t mdt_op_trace_mlp_read(float *us, int32_t cap);
+/* Behind every traced launch the hook also brackets NOTHING with a second pair of events: mdt_op_trace_mlp_read_empty returns
+ * those empty brackets (microseconds; same order and count as the last mdt_op_trace_mlp_read) -- what the bracket itself costs
+ * on the stream.  Launch bracket minus empty bracket = the kernel as a kernel trace's row reports it. */
+int32_t mdt_op_trace_mlp_read_empty(float *us, int32_t cap);
+/* Measurement hook: in stream order, one wave per XCD writes {shader-clock counter (s_memtime), constant 100 MHz counter
+ * (s_memrealtime)} to out16[2 x + 0 .. 1] (device memory, 16 values, zero them first; x = the XCD the wave ran on: the shader-clock
+ * counters of the eight XCDs are not synchronised).  Two stamps around a span of launches give, XCD by XCD, the average shader clock
+ * the chip sustained over it: (d memtime / d memrealtime) x 100 MHz -- what bench.py reports as roofline.sustained_mhz beside the
+ * 2.4 GHz the peak is quoted at. */
+mdt_status mdt_op_clock_stamp(uint64_t *out16, void *stream);
+
+/* Only a library built with -DMDT_DEBUG_TIMING (the phase-timing variant that the phase tools under tools/ build beside the product library)
+ * also exports
+ *     int mdt_debug_set_timing_buffer(unsigned long long *stamps);
+ * which points the kernels' phase stamps at a device buffer (NULL: off).  The product library does not have the symbol, so it is
+ * named here and declared by the tools that load that variant. */
+
+#ifdef __cplusplus
+}
+#endif
+#endif

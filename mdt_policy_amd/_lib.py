@@ -253,12 +253,6 @@ SYMBOLS = [
     ("mdt_dpm_control_init", _I32, [C.POINTER(DpmControl)] + [C.c_double] * 6),
     ("mdt_dpm_control_update", _I32, [C.POINTER(DpmControl), C.c_float, C.POINTER(C.c_int32)]),
     ("mdt_dpm_adaptive_plan", _I32, [_I32, C.c_float, C.c_float, C.POINTER(SamplerPlan)]),
-    ("mdt_op_trace_mlp", None, [_I32]),
-    ("mdt_op_trace_mlp_read", _I32, [_VP, _I32]),
-    ("mdt_op_trace_mlp_read_empty", _I32, [_VP, _I32]),
-    ("mdt_op_clock_stamp", _I32, [_VP, _VP]),
-    ("mdt_op_set_ws_split", None, [_I32]),
-    ("mdt_op_set_tn_split", None, [_I32]),
     ("mdt_loss_fwd", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP]),
     ("mdt_flops_per_chunk", C.c_double, [_VP, _I32]),
     ("mdt_fnv1_32", C.c_uint32, [C.c_char_p, C.c_uint64, C.c_uint32]),
@@ -270,13 +264,6 @@ SYMBOLS = [
     ("mdt_op_pack_weight_split", _I32, [_VP, _I64, _I64, _VP, _VP]),
     ("mdt_op_pack_weight_split_rows", _I32, [_VP, _I64, _I64, _VP, _I64, _VP]),
     ("mdt_op_mlp_split", _I32, [C.POINTER(GemmArgs), C.POINTER(GemmArgs), _VP, _VP, _VP, _I64, C.POINTER(_I32), _VP]),
-    ("mdt_op_set_mlp_split", None, [_I32]),
-    ("mdt_op_set_gemm_geometry", None, [_I32]),
-    ("mdt_op_set_mlp_fuse_min", None, [_I32]),
-    ("mdt_op_set_side_jobs", None, [_I32]),
-    ("mdt_op_side_jobs_paired", _I64, []),
-    ("mdt_op_set_mlp_skew", None, [_I32]),
-    ("mdt_op_set_attn_wide_min", None, [_I32]),
     ("mdt_op_attention", _I32, [C.POINTER(AttnArgs), _VP]),
     ("mdt_op_attn_proj", _I32, [C.POINTER(GemmArgs), _VP, _I64, _I32, _I32, _I32, _VP]),
     ("mdt_op_xattn_fold", _I32, [C.POINTER(XFoldArgs), _VP]),
@@ -286,6 +273,20 @@ SYMBOLS = [
     ("mdt_op_layernorm", _I32, [_VP, _VP, _VP, _VP, _I64, _I32, _VP]),
     ("mdt_op_head", _I32, [C.POINTER(HeadArgs), _VP]),
     ("mdt_op_action_embed", _I32, [_VP, _VP, _I64, _F, _VP, _VP, _VP, _I64, _I32, _I32, _I32, _VP]),
+    # include/mdt_hip_debug.h (process-global test and measurement hooks)
+    ("mdt_op_set_mlp_split", None, [_I32]),
+    ("mdt_op_set_gemm_geometry", None, [_I32]),
+    ("mdt_op_set_mlp_fuse_min", None, [_I32]),
+    ("mdt_op_set_side_jobs", None, [_I32]),
+    ("mdt_op_side_jobs_paired", _I64, []),
+    ("mdt_op_set_mlp_skew", None, [_I32]),
+    ("mdt_op_set_attn_wide_min", None, [_I32]),
+    ("mdt_op_trace_mlp", None, [_I32]),
+    ("mdt_op_trace_mlp_read", _I32, [_VP, _I32]),
+    ("mdt_op_trace_mlp_read_empty", _I32, [_VP, _I32]),
+    ("mdt_op_clock_stamp", _I32, [_VP, _VP]),
+    ("mdt_op_set_ws_split", None, [_I32]),
+    ("mdt_op_set_tn_split", None, [_I32]),
     # include/mdt_hip_train.h
     ("mdt_train_prepare", _I32, [_VP]),
     ("mdt_grad_numel", _I64, [_VP]),

@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <atomic>
+
 #include "mdt_hip.h"
 #include "mdt_hip_ops.h"
 #include "mdt_resampler.h"
@@ -63,6 +65,28 @@ static inline mdt_gemm_args gemm_args(const float* A, int64_t lda, const Lin& w,
     g.gin = 1; g.gout = 1; g.goff = 0;
     return g;
 }
+
+// ---- the process-global test and measurement switches (setters: include/mdt_hip_debug.h, each a one-line write) ----
+// One table, defined in mdt_kernels.hip and hidden from the library's dynamic symbols.  -1 = "the default" in every field but gemm_geometry, whose setter documents 0 as the
+// heuristic and -1 as a geometry of its own.  Atomics: host threads may drive different handles side by side.
+struct mdt_switches {
+    std::atomic<int> attn_wide_min{-1};  // mdt_op_set_attn_wide_min: rows; 0 = never (and no k_attn_xattn either)
+    std::atomic<int> mlp_fuse_min{-1};   // mdt_op_set_mlp_fuse_min: rows; 0 = never
+    std::atomic<int> mlp_skew{-1};       // mdt_op_set_mlp_skew
+    std::atomic<int> gemm_geometry{0};   // mdt_op_set_gemm_geometry
+    std::atomic<int> trace_mlp{-1};      // mdt_op_trace_mlp: 1 = on
+    std::atomic<int> side_jobs{-1};      // mdt_op_set_side_jobs: 0 = off
+    // ... and the ones an environment variable fills the first time they are read (mdt_switch_env)
+    std::atomic<int> ws_split{-1};       // MDT_HIP_WS_SPLIT / mdt_op_set_ws_split
+    std::atomic<int> mlp_split{-1};      // MDT_HIP_MLP_SPLIT / mdt_op_set_mlp_split
+    std::atomic<int> tn_split{-1};       // MDT_HIP_TN_SPLIT / mdt_op_set_tn_split
+    std::atomic<int> dw_stream{-1};      // MDT_HIP_DW_STREAM (mdt_train.hip)
+    std::atomic<int> xfold{-1};          // MDT_HIP_XFOLD (mdt_create)
+};
+extern mdt_switches g_mdt_sw __attribute__((visibility("hidden")));
+// a field with an environment variable: its value if set (>= 0), else the variable's integer (unset: dflt), which `latch` keeps in
+// the field.  xfold is read without latch: mdt_create looks at the environment every time, and a test flips it between two handles.
+__attribute__((visibility("hidden"))) int mdt_switch_env(std::atomic<int>& field, const char* var, int dflt, bool latch = true);
 
 // batch-sized buffers (workspace, tapes, backward scratch): through the installed allocator (mdt_set_allocator) or hipMalloc
 hipError_t mdt_dev_malloc(void** p, size_t bytes);

@@ -26,6 +26,8 @@
 #include <vector>
 
 #include "mdt_internal.h"
+#include "mdt_hip_debug.h"
+#include "mdt_launch.h"
 
 #include "mdt_device.h"
 
@@ -432,21 +434,14 @@ __global__ __launch_bounds__(512) void k_attn_xattn(mdt_gemm_args a, mdt_attn_pr
 // 256 KiB of zeros per device: stands in for absent bias / rowvec / LayerNorm-bias vectors.  ensure_zeros() points
 // g_zeros at the CURRENT device's buffer (a process normally drives one GPU; a second one gets its own buffer).
 static const int ZEROS_FLOATS = 65536;
-static const int MAX_DEVICES = 32;
-static float* g_zeros_dev[MAX_DEVICES] = {nullptr};
+static float* g_zeros_dev[MDT_MAX_DEVICES] = {nullptr};
 static thread_local float* g_zeros = nullptr;
-
-static int current_device() {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return 0;
-    return dev;
-}
 
 static hipError_t ensure_zeros() {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= MAX_DEVICES) return hipErrorInvalidDevice;
+    if (dev < 0 || dev >= MDT_MAX_DEVICES) return hipErrorInvalidDevice;
     if (g_zeros_dev[dev] == nullptr) {
         static std::mutex mu;
         std::lock_guard<std::mutex> lock(mu);
@@ -465,22 +460,21 @@ static hipError_t ensure_zeros() {
 
 const float* mdt_zeros() { return ensure_zeros() == hipSuccess ? g_zeros : nullptr; }
 
+// f(std::integral_constant<int, PRO_*>()) for the prologue kind (mdt_tiles.h) a product's arguments ask for; Lo = the first kind
+// the caller's kernel is instantiated for (PRO_PLAIN, or PRO_LN where a LayerNorm prologue is a condition of the launch)
+template <int Lo, class F>
+static hipError_t mdt_with_pro(const mdt_gemm_args& a, F f) {
+    const int pro = !a.ln ? PRO_PLAIN : (a.mod != nullptr && a.shift_off >= 0) ? (a.mod_stride == 0 ? PRO_LN_MOD_BCAST : PRO_LN_MOD_ROWS) : PRO_LN;
+    return mdt_with_const<Lo, PRO_LN_MOD_ROWS>(pro, f);
+}
+
 template <int MTILES, int NTW, int NWAVES, int PRO, bool RES>
 static hipError_t launch_gemm_r(const mdt_gemm_args& a, int kchunk, hipStream_t s) {
     const int MT = MTILES * 16, NTC = NWAVES * NTW * 16;
     const int gn = (a.N + NTC - 1) / NTC, gm = (a.M + MT - 1) / MT;
     const size_t lds = (size_t)MT * (kchunk + 4) * sizeof(float);
-    static size_t lds_attr_dev[MAX_DEVICES] = {0};  // per instantiation and per device (function attributes are per device)
-    size_t& lds_attr = lds_attr_dev[current_device()];
-    if (lds > lds_attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm<MTILES, NTW, NWAVES, PRO, RES>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_attr = lds;
-    }
-    hipLaunchKernelGGL((k_gemm<MTILES, NTW, NWAVES, PRO, RES>), dim3(gn * gm, 1, a.batch > 1 ? a.batch : 1), dim3(64 * NWAVES),
-                       lds, s, a, kchunk, gn, g_zeros);
-    return hipGetLastError();
+    return mdt_launch_lds<k_gemm<MTILES, NTW, NWAVES, PRO, RES>>(dim3(gn * gm, 1, a.batch > 1 ? a.batch : 1), dim3(64 * NWAVES), lds, s,
+                                                                 a, kchunk, gn, g_zeros);
 }
 
 template <int MTILES, int NTW, int NWAVES, int GLU>
@@ -488,15 +482,7 @@ static hipError_t launch_gemm_glu(const mdt_gemm_args& a, int kchunk, hipStream_
     const int MT = MTILES * 16, NTC = NWAVES * NTW * 16;
     const int gn = (a.N + NTC - 1) / NTC, gm = (a.M + MT - 1) / MT;
     const size_t lds = (size_t)MT * (kchunk + 4) * sizeof(float);
-    static size_t lds_attr_dev[MAX_DEVICES] = {0};
-    size_t& lds_attr = lds_attr_dev[current_device()];
-    if (lds > lds_attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_glu<MTILES, NTW, NWAVES, GLU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_attr = lds;
-    }
-    hipLaunchKernelGGL((k_gemm_glu<MTILES, NTW, NWAVES, GLU>), dim3(gn * gm), dim3(64 * NWAVES), lds, s, a, kchunk, gn, g_zeros);
-    return hipGetLastError();
+    return mdt_launch_lds<k_gemm_glu<MTILES, NTW, NWAVES, GLU>>(dim3(gn * gm), dim3(64 * NWAVES), lds, s, a, kchunk, gn, g_zeros);
 }
 
 template <int MTILES, int NTW, int NWAVES, int LW, bool RES>
@@ -504,17 +490,8 @@ static hipError_t launch_gemm_pipe_r(const mdt_gemm_args& a, int kchunk, hipStre
     const int MT = MTILES * 16, NTC = NWAVES * NTW * 16;
     const int gn = (a.N + NTC - 1) / NTC, gm = (a.M + MT - 1) / MT;
     const size_t lds = (size_t)2 * MT * (kchunk + 4) * sizeof(float);  // double-buffered activation chunk
-    static size_t lds_attr_dev[MAX_DEVICES] = {0};
-    size_t& lds_attr = lds_attr_dev[current_device()];
-    if (lds > lds_attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_pipe<MTILES, NTW, NWAVES, LW, RES>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_attr = lds;
-    }
-    hipLaunchKernelGGL((k_gemm_pipe<MTILES, NTW, NWAVES, LW, RES>), dim3(gn * gm, 1, a.batch > 1 ? a.batch : 1),
-                       dim3(64 * (NWAVES + LW)), lds, s, a, kchunk, gn, g_zeros);
-    return hipGetLastError();
+    return mdt_launch_lds<k_gemm_pipe<MTILES, NTW, NWAVES, LW, RES>>(dim3(gn * gm, 1, a.batch > 1 ? a.batch : 1),
+                                                                     dim3(64 * (NWAVES + LW)), lds, s, a, kchunk, gn, g_zeros);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -540,15 +517,7 @@ static hipError_t launch_gemm_tall_r(const mdt_gemm_args& a, hipStream_t s) {
     constexpr int BM = WM * 64, BN = WN * NT * 16;
     const int gn = (a.N + BN - 1) / BN, gm = (a.M + BM - 1) / BM;
     const size_t lds = (size_t)NS * (BM + BN) * MDT_TALL_BK * sizeof(float);
-    static bool attr_dev[MAX_DEVICES] = {false};
-    bool& done = attr_dev[current_device()];
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_tall<WM, WN, NT, NS, RES, LW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done = true;
-    }
-    hipLaunchKernelGGL((k_gemm_tall<WM, WN, NT, NS, RES, LW>), dim3(gn * gm), dim3(64 * (WM * WN + LW)), lds, s, a, gn, g_zeros);
-    return hipGetLastError();
+    return mdt_launch_lds<k_gemm_tall<WM, WN, NT, NS, RES, LW>>(dim3(gn * gm), dim3(64 * (WM * WN + LW)), lds, s, a, gn, g_zeros);
 }
 template <int WM, int WN, int NT, int NS, int LW = 0>
 static hipError_t launch_gemm_tall(const mdt_gemm_args& a, hipStream_t s) {
@@ -603,12 +572,8 @@ static int ws_shape(const mdt_gemm_args& a) {
     return a.N % 256 == 0 ? 8 : 0;
 }
 // the three-way bf16 split of the weight-stationary body (mdt_ws.h): K = 384, 128-column panels (8 waves, one column tile each)
-static int g_ws_split = -1;
-static bool ws_split_on() {
-    if (g_ws_split < 0) { const char* e = getenv("MDT_HIP_WS_SPLIT"); g_ws_split = e ? atoi(e) : 1; }
-    return g_ws_split != 0;
-}
-extern "C" void mdt_op_set_ws_split(int32_t on) { g_ws_split = on < 0 ? -1 : (on != 0); }
+static bool ws_split_on() { return mdt_switch_env(g_mdt_sw.ws_split, "MDT_HIP_WS_SPLIT", 1) != 0; }
+extern "C" void mdt_op_set_ws_split(int32_t on) { g_mdt_sw.ws_split = on < 0 ? -1 : (on != 0); }
 // split form only: plain K = 192 products whose N is a multiple of 192 but not of 256 (the masked-image head's qkv and output
 // projections, N = 576 / 192) -- twelve waves (three per SIMD) x one column tile.  (Their fp32 form was measured and dropped, above: no gain over the
 // tall body; the split form is 1.4x.)
@@ -630,30 +595,14 @@ static hipError_t launch_gemm_ws_t(const mdt_gemm_args& a, hipStream_t s) {
     const int groups = std::max(1, std::min(256 / (8 * panels), (ntiles + 7) / 8));
     const int chunks = 8 * groups, tiles = (ntiles + chunks - 1) / chunks;
     const size_t lds = (size_t)2 * 32 * (K16 * 16 + 4) * sizeof(float);
-    static bool attr_dev[MAX_DEVICES] = {false};
-    bool& done = attr_dev[current_device()];
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_ws<K16, NTW, NW, GLU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done = true;
-    }
-    hipLaunchKernelGGL((k_gemm_ws<K16, NTW, NW, GLU>), dim3(chunks * panels), dim3(64 * NW), lds, s, a, tiles, panels, g_zeros);
-    return hipGetLastError();
+    return mdt_launch_lds<k_gemm_ws<K16, NTW, NW, GLU>>(dim3(chunks * panels), dim3(64 * NW), lds, s, a, tiles, panels, g_zeros);
 }
 template <int K16, int NTW, int GLU, int NW = 8>
 static hipError_t launch_gemm_ws_split(const mdt_gemm_args& a, hipStream_t s) {
     const int panels = a.N / (NW * NTW * 16), ntiles = (a.M + 31) / 32;
     const int chunks = std::max(1, std::min(256 / panels, ntiles)), tiles = (ntiles + chunks - 1) / chunks;
     const size_t lds = (size_t)2 * 3 * 32 * (2 * K16 * 16 + 32);
-    static bool attr_dev[MAX_DEVICES] = {false};
-    bool& done = attr_dev[current_device()];
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_ws_split<K16, NTW, NW, GLU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        done = true;
-    }
-    hipLaunchKernelGGL((k_gemm_ws_split<K16, NTW, NW, GLU>), dim3(256), dim3(64 * NW), lds, s, a, tiles, panels, g_zeros);
-    return hipGetLastError();
+    return mdt_launch_lds<k_gemm_ws_split<K16, NTW, NW, GLU>>(dim3(256), dim3(64 * NW), lds, s, a, tiles, panels, g_zeros);
 }
 static hipError_t launch_gemm_ws(const mdt_gemm_args& a, hipStream_t s) {
     if (ws_split_on() && a.K == 384 && a.N % 128 == 0 && a.N / 128 <= 32) {
@@ -749,14 +698,19 @@ int mdt_gemm_kchunk(int K, int ln, int cap) {
 
 template <int MTILES, int NTW, int NWAVES>
 static hipError_t launch_gemm_pro(const mdt_gemm_args& a, int kchunk, hipStream_t s) {
-    if (!a.ln) return launch_gemm_t<MTILES, NTW, NWAVES, PRO_PLAIN>(a, kchunk, s);
-    if (a.mod != nullptr && a.shift_off >= 0)
-        return a.mod_stride == 0 ? launch_gemm_t<MTILES, NTW, NWAVES, PRO_LN_MOD_BCAST>(a, kchunk, s)
-                                 : launch_gemm_t<MTILES, NTW, NWAVES, PRO_LN_MOD_ROWS>(a, kchunk, s);
-    return launch_gemm_t<MTILES, NTW, NWAVES, PRO_LN>(a, kchunk, s);
+    return mdt_with_pro<PRO_PLAIN>(a, [&](auto pro) { return launch_gemm_t<MTILES, NTW, NWAVES, decltype(pro)::value>(a, kchunk, s); });
 }
 
-int g_mdt_gemm_force = 0;  // tuning hook: 0 = heuristic, 1.. selects a geometry below, -1 = the split-K small-M kernel
+// the switch table (mdt_internal.h) and its environment helper
+mdt_switches g_mdt_sw;
+int mdt_switch_env(std::atomic<int>& field, const char* var, int dflt, bool latch) {
+    int v = field;
+    if (v >= 0) return v;
+    const char* e = getenv(var);
+    v = e ? atoi(e) : dflt;
+    if (latch) field = v;
+    return v;
+}
 
 // WStream (mdt_tiles.h) addresses a weight image with 32-bit byte offsets from its base: every launcher that feeds one checks
 // the image size (mdt_launch_gemm does for the GEMMs; the fused MLP and attn_xattn tiles bound N and K by their shape rules)
@@ -775,16 +729,8 @@ bool mdt_attn_proj_supported(const mdt_gemm_args& p, int H, int hd, int T, int r
 template <int HD>
 static hipError_t launch_attn_proj_t(const mdt_gemm_args& p, const float* qkv, int64_t ldq, int T, int causal, hipStream_t s) {
     const size_t lds = (size_t)8 * 3 * T * (HD + 4) * sizeof(float);
-    static size_t lds_attr_dev[MAX_DEVICES] = {0};
-    size_t& lds_attr = lds_attr_dev[current_device()];
-    if (lds > 48 * 1024 && lds > lds_attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_proj_smallm<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_attr = lds;
-    }
-    hipLaunchKernelGGL((k_attn_proj_smallm<HD>), dim3(p.N >> 4, p.M / T), dim3(512), lds, s, p, qkv, ldq, T, causal,
-                       1.0f / sqrtf((float)HD), g_zeros);
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn_proj_smallm<HD>>(dim3(p.N >> 4, p.M / T), dim3(512), lds, s, p, qkv, ldq, T, causal,
+                                                  1.0f / sqrtf((float)HD), g_zeros);
 }
 
 hipError_t mdt_launch_attn_proj(const mdt_gemm_args& p, const float* qkv, int64_t ldq, int H, int hd, int T, int causal,
@@ -814,15 +760,7 @@ template <int HD, int TKC>
 static hipError_t launch_attn_proj_wide_t(const mdt_gemm_args& p, const mdt_attn_pro& ap, hipStream_t s) {
     const int gn = (p.N + 127) / 128, gm = (p.M + 31) / 32;
     const size_t lds = ((size_t)32 * (p.K + 4) + (size_t)(32 + 2 * 48) * (4 * HD + 16)) * sizeof(float);
-    static size_t lds_attr_dev[MAX_DEVICES] = {0};
-    size_t& lds_attr = lds_attr_dev[current_device()];
-    if (lds > lds_attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_proj_wide<HD, TKC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_attr = lds;
-    }
-    hipLaunchKernelGGL((k_attn_proj_wide<HD, TKC>), dim3(gn * gm), dim3(512), lds, s, p, ap, gn, g_zeros);
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn_proj_wide<HD, TKC>>(dim3(gn * gm), dim3(512), lds, s, p, ap, gn, g_zeros);
 }
 
 hipError_t mdt_launch_attn_proj_wide(const mdt_gemm_args& p, const float* qkv, int64_t ldq, int H, int hd, int T, hipStream_t s) {
@@ -853,15 +791,7 @@ template <int HD, int TKC>
 static hipError_t launch_attn_xattn_t(const mdt_gemm_args& p, const mdt_attn_pro& at, const mdt_xapply_args& x, hipStream_t s) {
     const int D = 8 * HD;
     const size_t lds = ((size_t)16 * (D + 4) + (size_t)48 * (D + 16)) * sizeof(float);
-    static bool attr_dev[MAX_DEVICES] = {false};
-    bool& attr = attr_dev[current_device()];
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_xattn<HD, TKC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    hipLaunchKernelGGL((k_attn_xattn<HD, TKC>), dim3(x.B), dim3(512), lds, s, p, at, x, g_zeros);
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn_xattn<HD, TKC>>(dim3(x.B), dim3(512), lds, s, p, at, x, g_zeros);
 }
 
 hipError_t mdt_launch_attn_xattn(const mdt_gemm_args& p, const float* qkv, int64_t ldq, const mdt_xapply_args& x, int H, int hd,
@@ -885,12 +815,9 @@ static bool smallm_shape_ok(const mdt_gemm_args& a) {
            a.N <= ZEROS_FLOATS && a.K <= ZEROS_FLOATS && !(a.N & 15) && (int64_t)a.N * a.K < ((int64_t)1 << 30);
 }
 // process-wide (the queue itself is per host thread): atomics, host threads may drive different handles side by side
-static std::atomic<int> g_side_override{-1};     // mdt_op_set_side_jobs (tests): 0 = off, 1 = on, -1 = the default (on)
 static std::atomic<int64_t> g_side_paired{0};    // launches that took a side job along (mdt_op_side_jobs_paired)
-static bool side_enabled() {
-    return g_side_override.load(std::memory_order_relaxed) != 0 && g_mdt_gemm_force == 0;
-}
-extern "C" void mdt_op_set_side_jobs(int32_t on) { g_side_override.store(on < 0 ? -1 : (on != 0)); }
+static bool side_enabled() { return g_mdt_sw.side_jobs != 0 && g_mdt_sw.gemm_geometry == 0; }
+extern "C" void mdt_op_set_side_jobs(int32_t on) { g_mdt_sw.side_jobs = on < 0 ? -1 : (on != 0); }
 extern "C" int64_t mdt_op_side_jobs_paired(void) { return g_side_paired.load(); }
 hipError_t mdt_gemm_side_push(const mdt_gemm_args& a, hipStream_t s) {
     if (!side_enabled() || !smallm_shape_ok(a)) return mdt_launch_gemm(a, s);
@@ -930,6 +857,7 @@ hipError_t mdt_gemm_side_flush(hipStream_t s) {
 }
 
 hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
+    const int force = g_mdt_sw.gemm_geometry;   // mdt_op_set_gemm_geometry
     if (a.N > ZEROS_FLOATS || a.K > ZEROS_FLOATS) return hipErrorInvalidValue;
     // the weight stream is addressed with 32-bit byte offsets from the image's base (buffer loads, mdt_tiles.h: WStream)
     if ((int64_t)a.N * a.K >= ((int64_t)1 << 30)) return hipErrorInvalidValue;
@@ -944,7 +872,7 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
             return hipErrorInvalidValue;
         // from 8192 rows on, K = 192: the weight-stationary body (mdt_ws.h) with the same epilogues -- round 5.  The masked-image
         // head's two SwishGLU products at B = 1024 (104448 rows).
-        if (a.M >= 8192 && g_mdt_gemm_force <= 0 && mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
+        if (a.M >= 8192 && force <= 0 && mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
         const int kc = mdt_gemm_kchunk(a.K, 0, 384);
         if (a.aux_mode == 3)
             return (a.N % 256 == 0) ? launch_gemm_glu<2, 4, 4, 3>(a, kc, s) : launch_gemm_glu<2, 2, 4, 3>(a, kc, s);
@@ -960,7 +888,7 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
     const int64_t tiles6 = (int64_t)((a.M + 15) / 16) * ((a.N + 63) / 64);
     const bool few_tiles = a.M <= GEMM_SMALLM_ROWS && tiles6 < (a.ln ? 60 : (a.M <= 192 ? 100 : 160));
     // (geometry hook -1: the split-K kernel wherever it applies -- tests that pin it against its fused variants)
-    if ((a.M <= GEMM_SMALLM_MAX || few_tiles || g_mdt_gemm_force < 0) && g_mdt_gemm_force <= 0 && (!a.ln || a.K <= 512) && a.batch <= 1 && a.K <= 4096 && !a.aux_mode) {
+    if ((a.M <= GEMM_SMALLM_MAX || few_tiles || force < 0) && force <= 0 && (!a.ln || a.K <= 512) && a.batch <= 1 && a.K <= 4096 && !a.aux_mode) {
         if (g_side_next < g_side_jobs.size() && a.batch <= 1 && a.M <= 16 * 64) {  // a queued side job rides in this launch
             const mdt_gemm_args b = g_side_jobs[g_side_next++];
             ++g_side_paired;
@@ -1022,10 +950,10 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
     // profiles/r04_gemm_train_shapes.txt: 104448 x 576 x 192 249 -> 213-231 us, 104448 x 192 x 768 290 -> 263-270,
     // 10240 x 384 x 1536 124 -> 105-112, 10240 x 1152 x 384 94 -> 88-92; 10240 x 384 x 384 unchanged, 4096 rows lose)
     // ... and the K = 192 products among them whose column count is a multiple of 256 on the weight-stationary body (mdt_ws.h)
-    if (a.M >= 8192 && (a.aux_mode == 0 || a.K == 384) && g_mdt_gemm_force <= 0 && mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
+    if (a.M >= 8192 && (a.aux_mode == 0 || a.K == 384) && force <= 0 && mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
     if (a.M >= 8192 && a.N % 64 == 0 && (a.N > 384 || a.K > 384) && a.batch <= 1 && mdt_gemm_tall_supported(a)) geo = 23;
     if (a.batch > 1) geo = 5;  // split-K partial products (deep reductions): geometry chosen for those
-    if (g_mdt_gemm_force > 0) geo = g_mdt_gemm_force;
+    if (force > 0) geo = force;
     if (geo == 30) {  // forced: the weight-stationary body (tests pin it against the other bodies)
         if (mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
         geo = 0;
@@ -1065,7 +993,7 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
     }
 }
 
-extern "C" void mdt_op_set_gemm_geometry(int32_t geo) { g_mdt_gemm_force = geo; }
+extern "C" void mdt_op_set_gemm_geometry(int32_t geo) { g_mdt_sw.gemm_geometry = geo; }
 
 // ---- fused MLP sublayer (k_mlp) ----
 bool mdt_mlp_supported(const mdt_gemm_args& f, const mdt_gemm_args& p) {
@@ -1079,42 +1007,24 @@ int mdt_mlp_slices(int D) { return 4 * D / 512; }
 // mlp_tile's wave schedule: low byte = k-steps the second wave of a SIMD starts behind the first (0: lockstep, workgroup
 // barrier between the two products), | 256 = MFMA loops at raised issue priority.  Measured at B = 256 (
 // profiles/r03_mlp_skew_ab.txt): 0 -> 4.89, 6 -> 4.86, 18 | 256 -> 4.82 ms per sampler call.  The hook: tests.
-static int g_mlp_skew = -1;
-static int mlp_skew() { return g_mlp_skew < 0 ? 18 | 256 : g_mlp_skew; }
-extern "C" void mdt_op_set_mlp_skew(int32_t v) { g_mlp_skew = v < 0 ? -1 : (v & 0x1ff); }
+static int mlp_skew() { const int v = g_mdt_sw.mlp_skew; return v < 0 ? 18 | 256 : v; }
+extern "C" void mdt_op_set_mlp_skew(int32_t v) { g_mdt_sw.mlp_skew = v < 0 ? -1 : (v & 0x1ff); }
 
 template <int NTW2, int PRO>
 static hipError_t launch_mlp_t(const mdt_gemm_args& f, const mdt_gemm_args& p, float* parts, int64_t part_stride, hipStream_t s) {
     const int S = mdt_mlp_slices(f.K), gm = (f.M + 31) / 32;
     const size_t lds = (size_t)32 * (f.K + 4 + 516) * sizeof(float) + 16 * sizeof(int);  // + the wave flags of mlp_tile
-    const int skew = mlp_skew();
-    static size_t lds_attr_dev[MAX_DEVICES] = {0};
-    size_t& lds_attr = lds_attr_dev[current_device()];
-    if (lds > lds_attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_mlp<NTW2, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_attr = lds;
-    }
-    hipLaunchKernelGGL((k_mlp<NTW2, PRO>), dim3(gm * S), dim3(512), lds, s, f, p, parts, part_stride, S, g_zeros, skew);
-    return hipGetLastError();
-}
-template <int NTW2>
-static hipError_t launch_mlp_pro(const mdt_gemm_args& f, const mdt_gemm_args& p, float* parts, int64_t part_stride, hipStream_t s) {
-    if (f.mod != nullptr && f.shift_off >= 0)
-        return f.mod_stride == 0 ? launch_mlp_t<NTW2, PRO_LN_MOD_BCAST>(f, p, parts, part_stride, s)
-                                 : launch_mlp_t<NTW2, PRO_LN_MOD_ROWS>(f, p, parts, part_stride, s);
-    return launch_mlp_t<NTW2, PRO_LN>(f, p, parts, part_stride, s);
+    return mdt_launch_lds<k_mlp<NTW2, PRO>>(dim3(gm * S), dim3(512), lds, s, f, p, parts, part_stride, S, g_zeros, mlp_skew());
 }
 hipError_t mdt_launch_mlp(const mdt_gemm_args& f, const mdt_gemm_args& p, float* parts, int64_t part_stride, hipStream_t s) {
     if (!mdt_mlp_supported(f, p)) return hipErrorInvalidValue;
     hipError_t ze = ensure_zeros();
     if (ze != hipSuccess) return ze;
-    switch (f.K / 128) {
-        case 1: return launch_mlp_pro<1>(f, p, parts, part_stride, s);
-        case 2: return launch_mlp_pro<2>(f, p, parts, part_stride, s);
-        case 3: return launch_mlp_pro<3>(f, p, parts, part_stride, s);
-        default: return launch_mlp_pro<4>(f, p, parts, part_stride, s);
-    }
+    return mdt_with_const<1, 4>(std::min(f.K / 128, 4), [&](auto ntw2) {
+        return mdt_with_pro<PRO_LN>(f, [&](auto pro) {
+            return launch_mlp_t<decltype(ntw2)::value, decltype(pro)::value>(f, p, parts, part_stride, s);
+        });
+    });
 }
 
 // ---- the LayerNorm-prologue product on the wide tiles in the split form (gemm_ln_split_tile) ----
@@ -1129,37 +1039,21 @@ template <int ND, int NTW, int PRO, int XP>
 static hipError_t launch_gemm_ln_split_t(const mdt_gemm_args& a, hipStream_t s) {
     const int gn = a.N / (8 * NTW * 16), gm = (a.M + 31) / 32;
     const int lds = 3 * 32 * (2 * 128 * ND + 32);
-    static bool attr_dev[MAX_DEVICES] = {false};
-    bool& done = attr_dev[current_device()];
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_ln_split<ND, NTW, PRO, XP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        done = true;
-    }
-    hipLaunchKernelGGL((k_gemm_ln_split<ND, NTW, PRO, XP>), dim3(gn * gm), dim3(512), lds, s, a, gn, g_zeros);
-    return hipGetLastError();
-}
-template <int ND, int NTW, int PRO>
-static hipError_t launch_gemm_ln_split_x(const mdt_gemm_args& a, hipStream_t s) {
-    switch (a.a_parts) {
-        case 2: return launch_gemm_ln_split_t<ND, NTW, PRO, 2>(a, s);
-        case 3: return launch_gemm_ln_split_t<ND, NTW, PRO, 3>(a, s);
-        case 4: return launch_gemm_ln_split_t<ND, NTW, PRO, 4>(a, s);
-        default: return launch_gemm_ln_split_t<ND, NTW, PRO, 1>(a, s);
-    }
+    return mdt_launch_lds<k_gemm_ln_split<ND, NTW, PRO, XP>>(dim3(gn * gm), dim3(512), lds, s, a, gn, g_zeros);
 }
 template <int ND, int NTW>
 static hipError_t launch_gemm_ln_split_pro(const mdt_gemm_args& a, hipStream_t s) {
-    if (a.mod != nullptr && a.shift_off >= 0)
-        return a.mod_stride == 0 ? launch_gemm_ln_split_x<ND, NTW, PRO_LN_MOD_BCAST>(a, s) : launch_gemm_ln_split_x<ND, NTW, PRO_LN_MOD_ROWS>(a, s);
-    return launch_gemm_ln_split_x<ND, NTW, PRO_LN>(a, s);
+    const int xp = a.a_parts >= 2 && a.a_parts <= 4 ? a.a_parts : 1;   // one array, or the sum of 2..4 slabs
+    return mdt_with_pro<PRO_LN>(a, [&](auto pro) {
+        return mdt_with_const<1, 4>(xp, [&](auto x) { return launch_gemm_ln_split_t<ND, NTW, decltype(pro)::value, decltype(x)::value>(a, s); });
+    });
 }
 // which products take it: the split image is there, LayerNorm prologue over whole rows of K = 384, column count a multiple of the
 // 384-wide panels, plain output rows, and enough rows that the wide tiles are the choice anyway (the fused MLP's threshold)
 static bool gemm_ln_split_applies(const mdt_gemm_args& a) {
     return a.Wp_split != nullptr && mdt_mlp_split_enabled() && a.ln && (a.K == 384 || a.K == 512) && a.N % 384 == 0 &&
            a.M >= mdt_split_min_rows() && a.batch <= 1 && !a.residual && a.gin == 1 && a.gout == 1 && a.goff == 0 && a.rowvec == nullptr && !a.aux_mode &&
-           a.a_parts <= 4 && (a.lda & 3) == 0 && (a.ldo & 3) == 0 && g_mdt_gemm_force == 0;
+           a.a_parts <= 4 && (a.lda & 3) == 0 && (a.ldo & 3) == 0 && g_mdt_sw.gemm_geometry == 0;
 }
 static hipError_t launch_gemm_ln_split(const mdt_gemm_args& a, hipStream_t s) {
     // (the tile is written for any D <= 512 and 256-wide panels too; instantiated for the two shipped widths: MDT-V d = 384, MDT d = 512)
@@ -1167,12 +1061,9 @@ static hipError_t launch_gemm_ln_split(const mdt_gemm_args& a, hipStream_t s) {
 }
 
 // ---- the fused MLP sublayer in the three-way bf16 split form (k_mlp_split) ----
-static int g_mlp_split = -1;   // MDT_HIP_MLP_SPLIT / mdt_op_set_mlp_split: 0 = the fp32 launch everywhere
-bool mdt_mlp_split_enabled() {
-    if (g_mlp_split < 0) { const char* e = getenv("MDT_HIP_MLP_SPLIT"); g_mlp_split = e ? atoi(e) : 1; }
-    return g_mlp_split != 0;
-}
-extern "C" void mdt_op_set_mlp_split(int32_t on) { g_mlp_split = on < 0 ? -1 : (on != 0); }
+// MDT_HIP_MLP_SPLIT / mdt_op_set_mlp_split: 0 = the fp32 launch everywhere
+bool mdt_mlp_split_enabled() { return mdt_switch_env(g_mdt_sw.mlp_split, "MDT_HIP_MLP_SPLIT", 1) != 0; }
+extern "C" void mdt_op_set_mlp_split(int32_t on) { g_mdt_sw.mlp_split = on < 0 ? -1 : (on != 0); }
 int mdt_split_min_rows() { return 768; }
 bool mdt_mlp_split_supported(const mdt_gemm_args& f, const mdt_gemm_args& p) {
     return mdt_mlp_supported(f, p);
@@ -1182,37 +1073,20 @@ static hipError_t launch_mlp_split_t(const mdt_gemm_args& f, const mdt_gemm_args
                                      int64_t part_stride, hipStream_t s) {
     const int S = mdt_mlp_slices(f.K), gm = (f.M + 31) / 32;
     const int lds = mlp_split_lds_bytes(128 * NTW2);
-    static bool attr_dev[MAX_DEVICES] = {false};
-    bool& done = attr_dev[current_device()];
-    if (!done) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_mlp_split<NTW2, PRO>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        done = true;
-    }
     const int per = (gm * S + 7) / 8;
-    hipLaunchKernelGGL((k_mlp_split<NTW2, PRO>), dim3(8 * per), dim3(512), lds, s, f, p, (const char*)w1s, (const char*)w2s, parts,
-                       part_stride, S, gm, g_zeros);
-    return hipGetLastError();
-}
-template <int NTW2>
-static hipError_t launch_mlp_split_pro(const mdt_gemm_args& f, const mdt_gemm_args& p, const void* w1s, const void* w2s, float* parts,
-                                       int64_t part_stride, hipStream_t s) {
-    if (f.mod != nullptr && f.shift_off >= 0)
-        return f.mod_stride == 0 ? launch_mlp_split_t<NTW2, PRO_LN_MOD_BCAST>(f, p, w1s, w2s, parts, part_stride, s)
-                                 : launch_mlp_split_t<NTW2, PRO_LN_MOD_ROWS>(f, p, w1s, w2s, parts, part_stride, s);
-    return launch_mlp_split_t<NTW2, PRO_LN>(f, p, w1s, w2s, parts, part_stride, s);
+    return mdt_launch_lds<k_mlp_split<NTW2, PRO>>(dim3(8 * per), dim3(512), lds, s, f, p, (const char*)w1s, (const char*)w2s, parts,
+                                                  part_stride, S, gm, g_zeros);
 }
 hipError_t mdt_launch_mlp_split(const mdt_gemm_args& f, const mdt_gemm_args& p, const void* w1s, const void* w2s, float* parts,
                                 int64_t part_stride, hipStream_t s) {
     if (!mdt_mlp_split_supported(f, p) || !w1s || !w2s) return hipErrorInvalidValue;
     hipError_t ze = ensure_zeros();
     if (ze != hipSuccess) return ze;
-    switch (f.K / 128) {
-        case 1: return launch_mlp_split_pro<1>(f, p, w1s, w2s, parts, part_stride, s);
-        case 2: return launch_mlp_split_pro<2>(f, p, w1s, w2s, parts, part_stride, s);
-        case 3: return launch_mlp_split_pro<3>(f, p, w1s, w2s, parts, part_stride, s);
-        default: return launch_mlp_split_pro<4>(f, p, w1s, w2s, parts, part_stride, s);
-    }
+    return mdt_with_const<1, 4>(std::min(f.K / 128, 4), [&](auto ntw2) {
+        return mdt_with_pro<PRO_LN>(f, [&](auto pro) {
+            return launch_mlp_split_t<decltype(ntw2)::value, decltype(pro)::value>(f, p, w1s, w2s, parts, part_stride, s);
+        });
+    });
 }
 
 // a LayerNorm-prologue GEMM whose rows are the sum of a.a_parts slabs (2..4): wide tiles only
@@ -1221,30 +1095,13 @@ static hipError_t launch_gemm_merge_t(const mdt_gemm_args& a, hipStream_t s) {
     const int NTC = 8 * NTW * 16;
     const int gn = (a.N + NTC - 1) / NTC, gm = (a.M + 31) / 32;
     const size_t lds = (size_t)32 * (a.K + 4) * sizeof(float);
-    static size_t lds_attr_dev[MAX_DEVICES] = {0};
-    size_t& lds_attr = lds_attr_dev[current_device()];
-    if (lds > lds_attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_merge<NTW, PRO, XP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_attr = lds;
-    }
-    hipLaunchKernelGGL((k_gemm_merge<NTW, PRO, XP>), dim3(gn * gm), dim3(512), lds, s, a, a.K, gn, g_zeros);
-    return hipGetLastError();
-}
-template <int NTW, int PRO>
-static hipError_t launch_gemm_merge_x(const mdt_gemm_args& a, hipStream_t s) {
-    switch (a.a_parts) {
-        case 2: return launch_gemm_merge_t<NTW, PRO, 2>(a, s);
-        case 3: return launch_gemm_merge_t<NTW, PRO, 3>(a, s);
-        case 4: return launch_gemm_merge_t<NTW, PRO, 4>(a, s);
-        default: return hipErrorInvalidValue;
-    }
+    return mdt_launch_lds<k_gemm_merge<NTW, PRO, XP>>(dim3(gn * gm), dim3(512), lds, s, a, a.K, gn, g_zeros);
 }
 template <int NTW>
 static hipError_t launch_gemm_merge_pro(const mdt_gemm_args& a, hipStream_t s) {
-    if (a.mod != nullptr && a.shift_off >= 0)
-        return a.mod_stride == 0 ? launch_gemm_merge_x<NTW, PRO_LN_MOD_BCAST>(a, s) : launch_gemm_merge_x<NTW, PRO_LN_MOD_ROWS>(a, s);
-    return launch_gemm_merge_x<NTW, PRO_LN>(a, s);
+    return mdt_with_pro<PRO_LN>(a, [&](auto pro) {   // (a_parts outside 2..4 is refused)
+        return mdt_with_const<2, 4>(a.a_parts, [&](auto x) { return launch_gemm_merge_t<NTW, decltype(pro)::value, decltype(x)::value>(a, s); });
+    });
 }
 static hipError_t launch_gemm_merge(const mdt_gemm_args& a, hipStream_t s) {
     if (!a.ln || a.K > 512 || a.residual || a.batch > 1 || a.aux_mode || a.a_parts > 4 || (a.N & 15)) return hipErrorInvalidValue;
@@ -1289,16 +1146,7 @@ static hipError_t launch_attn_tt(const mdt_attn_args& a, const float* rc, const 
     const int hs = attn_head_split(a.H, a.Tq, HD, a.B);
     const int Hl = a.H / hs;
     const size_t lds = ((size_t)(a.Tq + 2 * a.Tk) * Hl * HD + (size_t)Hl * a.Tq * 16 * LP) * sizeof(float);
-    static size_t lds_attr_dev[MAX_DEVICES] = {0};
-    size_t& lds_attr = lds_attr_dev[current_device()];
-    if (lds > lds_attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn<HD, TKC, ROPE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return e;
-        lds_attr = lds;
-    }
-    hipLaunchKernelGGL((k_attn<HD, TKC, ROPE>), dim3(a.B, hs), dim3(256), lds, s, a, rc, rs, 1.0f / sqrtf((float)HD));
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn<HD, TKC, ROPE>>(dim3(a.B, hs), dim3(256), lds, s, a, rc, rs, 1.0f / sqrtf((float)HD));
 }
 
 template <int HD>
@@ -1962,15 +1810,8 @@ bool mdt_xattn_gemm_supported(const mdt_xapply_args& x, const mdt_gemm_args& g) 
 template <int NPP>
 static hipError_t launch_xattn_gemm_t(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s) {
     const size_t lds = ((size_t)16 * (x.D + 4) + mdt_xattn_lds_floats(x.D, x.H)) * sizeof(float);
-    static size_t lds_attr_dev[MAX_DEVICES] = {0};
-    size_t& lds_attr = lds_attr_dev[current_device()];
-    if (lds > lds_attr) {  // up to 78 KB of dynamic LDS at d = 512
-        hipError_t e = hipFuncSetAttribute((const void*)k_xattn_gemm_smallm<NPP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_attr = lds;
-    }
-    hipLaunchKernelGGL((k_xattn_gemm_smallm<NPP>), dim3(g.N >> 4, x.B), dim3(512), lds, s, x, g, g_zeros);
-    return hipGetLastError();
+    // (up to 78 KB of dynamic LDS at d = 512)
+    return mdt_launch_lds<k_xattn_gemm_smallm<NPP>>(dim3(g.N >> 4, x.B), dim3(512), lds, s, x, g, g_zeros);
 }
 hipError_t mdt_launch_xattn_gemm(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s) {
     if (!mdt_xattn_gemm_supported(x, g)) return hipErrorInvalidValue;
@@ -2210,13 +2051,7 @@ template <int HD>
 static hipError_t launch_attn_long_t(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
                                      float* out, int64_t ldo, int B, int H, int Tq, int Tk, float scale, hipStream_t s) {
     const size_t lds = attn_long_lds(HD, Tq, Tk);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_long<HD>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((k_attn_long<HD>), dim3(B, H), dim3(256), lds, s, q, ldq, k, v, ldkv, out, ldo, Tq, Tk, scale);
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn_long<HD>>(dim3(B, H), dim3(256), lds, s, q, ldq, k, v, ldkv, out, ldo, Tq, Tk, scale);
 }
 
 hipError_t mdt_launch_attention_long(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,

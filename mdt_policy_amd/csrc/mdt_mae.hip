@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "mdt_internal.h"
+#include "mdt_launch.h"
 #include "mdt_device.h"
 
 namespace {
@@ -813,23 +814,15 @@ hipError_t launch_fwd(const float* qkv, int64_t ld, float* out, int64_t ldo, int
         int hpw = H;
         while (hpw > 1 && (B * (H / hpw) < 256 * per_cu || H % hpw)) --hpw;
         const dim3 grid((unsigned)B, H / hpw);
-#define MDT_FWD2(N_)                                                                                                              \
-    case N_: {                                                                                                                    \
-        hipError_t e2 = hipFuncSetAttribute((const void*)k_attn_mid_fwd2<HD, N_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-        if (e2 != hipSuccess) return e2;                                                                                          \
-        hipLaunchKernelGGL((k_attn_mid_fwd2<HD, N_>), grid, dim3(N_ > 4 ? 512 : 256), lds2, s, qkv, ld, out, ldo, H, T, scale, hpw); \
-        return hipGetLastError();                                                                                                 \
-    }
+#define MDT_FWD2(N_) \
+    case N_: return mdt_launch_lds<k_attn_mid_fwd2<HD, N_>>(grid, dim3(N_ > 4 ? 512 : 256), lds2, s, qkv, ld, out, ldo, H, T, scale, hpw);
         switch (n) {
             MDT_FWD2(1) MDT_FWD2(2) MDT_FWD2(3) MDT_FWD2(4) MDT_FWD2(5) MDT_FWD2(6) MDT_FWD2(7) MDT_FWD2(8)
         }
 #undef MDT_FWD2
     }
     const size_t lds = attn_mid_lds(HD, T, false);
-    hipError_t e = hipFuncSetAttribute((const void*)k_attn_mid_fwd<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_attn_mid_fwd<HD>), dim3((unsigned)B, H), dim3(256), lds, s, qkv, ld, out, ldo, H, T, scale);
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn_mid_fwd<HD>>(dim3((unsigned)B, H), dim3(256), lds, s, qkv, ld, out, ldo, H, T, scale);
 }
 template <int HD>
 hipError_t launch_bwd(const float* qkv, int64_t ld, const float* fo, int64_t ldf, const float* d_out, int64_t ldd, float* d_qkv,
@@ -837,25 +830,16 @@ hipError_t launch_bwd(const float* qkv, int64_t ld, const float* fo, int64_t ldf
     // the second form where it applies, else the first (T x T matrices in LDS, five phases): hd > 32, T > 128
     if constexpr (HD <= 32) {  // (hd 48 / 64: the T16 x hd accumulators of dK and dV no longer fit the registers)
         const size_t lds2 = attn_mid_lds2(HD, T);
-#define MDT_BWD2(N_)                                                                                                              \
-    case N_: {                                                                                                                    \
-        hipError_t e2 = hipFuncSetAttribute((const void*)k_attn_mid_bwd2<HD, N_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-        if (e2 != hipSuccess) return e2;                                                                                          \
-        hipLaunchKernelGGL((k_attn_mid_bwd2<HD, N_>), dim3((unsigned)B, H), dim3(256), lds2, s, qkv, ld, fo, ldf, d_out, ldd, d_qkv, ldg, \
-                           H, T, scale);                                                                                          \
-        return hipGetLastError();                                                                                                 \
-    }
+#define MDT_BWD2(N_)                                                                                                          \
+    case N_: return mdt_launch_lds<k_attn_mid_bwd2<HD, N_>>(dim3((unsigned)B, H), dim3(256), lds2, s, qkv, ld, fo, ldf, d_out, ldd, d_qkv, \
+                                                            ldg, H, T, scale);
         switch ((T + 15) >> 4) {
             MDT_BWD2(1) MDT_BWD2(2) MDT_BWD2(3) MDT_BWD2(4) MDT_BWD2(5) MDT_BWD2(6) MDT_BWD2(7) MDT_BWD2(8)
         }
 #undef MDT_BWD2
     }
     const size_t lds = attn_mid_lds(HD, T, true);
-    hipError_t e = hipFuncSetAttribute((const void*)k_attn_mid_bwd<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_attn_mid_bwd<HD>), dim3((unsigned)B, H), dim3(512), lds, s, qkv, ld, fo, ldf, d_out, ldd, d_qkv, ldg, H, T,
-                       scale);
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn_mid_bwd<HD>>(dim3((unsigned)B, H), dim3(512), lds, s, qkv, ld, fo, ldf, d_out, ldd, d_qkv, ldg, H, T, scale);
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -1452,20 +1436,12 @@ size_t long_lds(int which) {   // 0 forward, 1 dK / dV, 2 dQ: two stage buffers 
     return 2 * buf * sizeof(float);
 }
 
-template <typename K>
-hipError_t long_launch_setup(K kern, size_t lds) {
-    return lds > 64 * 1024 ? hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
-}
-
 template <int HD>
 hipError_t launch_long_fwd(const float* qkv, int64_t ld, float* out, int64_t ldo, float* lse, int64_t B, int H, int T, float scale,
                            hipStream_t s) {
     const size_t lds = long_lds<HD>(0);
-    hipError_t e = long_launch_setup(k_attn_long_fwd<HD>, lds);
-    if (e != hipSuccess) return e;
     const int64_t nwg = B * H * ((T + LB - 1) / LB);
-    hipLaunchKernelGGL((k_attn_long_fwd<HD>), dim3((unsigned)nwg), dim3(LNT), lds, s, qkv, ld, out, ldo, lse, H, T, scale);
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn_long_fwd<HD>>(dim3((unsigned)nwg), dim3(LNT), lds, s, qkv, ld, out, ldo, lse, H, T, scale);
 }
 
 template <int HD>
@@ -1477,14 +1453,9 @@ hipError_t launch_long_bwd(const float* qkv, int64_t ld, const float* o, int64_t
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const size_t l1 = long_lds<HD>(1), l2 = long_lds<HD>(2);
-    if ((e = long_launch_setup(k_attn_long_bwd_kv<HD>, l1)) != hipSuccess) return e;
-    if ((e = long_launch_setup(k_attn_long_bwd_q<HD>, l2)) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_attn_long_bwd_kv<HD>), dim3((unsigned)nwg), dim3(LNT), l1, s, qkv, ld, d_out, ldd, lse, delta, d_qkv, ldg, H, T,
-                       scale);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_attn_long_bwd_q<HD>), dim3((unsigned)nwg), dim3(LNT), l2, s, qkv, ld, d_out, ldd, lse, delta, d_qkv, ldg, H, T,
-                       scale);
-    return hipGetLastError();
+    e = mdt_launch_lds<k_attn_long_bwd_kv<HD>>(dim3((unsigned)nwg), dim3(LNT), l1, s, qkv, ld, d_out, ldd, lse, delta, d_qkv, ldg, H, T, scale);
+    if (e != hipSuccess) return e;
+    return mdt_launch_lds<k_attn_long_bwd_q<HD>>(dim3((unsigned)nwg), dim3(LNT), l2, s, qkv, ld, d_out, ldd, lse, delta, d_qkv, ldg, H, T, scale);
 }
 
 // the checks both directions share; 0 = fine

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "mdt_internal.h"
+#include "mdt_hip_debug.h"
 #include "mdt_sampler_plan.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -396,7 +397,7 @@ extern "C" mdt_status mdt_create(const mdt_config* cfg, mdt_model** out) {
     if (e != hipSuccess) { (void)hipFree(m->arena); delete m; return fail(MDT_ERR_HIP, "hipMalloc(staging) failed: %s", hipGetErrorString(e)); }
     // the collapsed cross-attention needs a step-independent context and an unconditioned query input
     m->xfold = cond == COND_ADALN && !c.use_rot_embed && mdt_xattn_apply_supported(m->D, m->H, m->Te, m->Ta);
-    if (const char* x = getenv("MDT_HIP_XFOLD")) m->xfold = m->xfold && atoi(x) != 0;
+    m->xfold = m->xfold && mdt_switch_env(g_mdt_sw.xfold, "MDT_HIP_XFOLD", 1, false) != 0;
     *out = m;
     return MDT_OK;
 }
@@ -656,11 +657,11 @@ struct Stream {
 };
 
 // row count from which the self-attention runs in the prologue of its output projection
-static int g_attn_wide_override = -1;  // mdt_op_set_attn_wide_min (tests): 0 disables, -1 = the default
 static int g_attn_wide_min_rows() {
-    return g_attn_wide_override >= 0 ? (g_attn_wide_override == 0 ? 1 << 30 : g_attn_wide_override) : 1401;
+    const int v = g_mdt_sw.attn_wide_min;
+    return v >= 0 ? (v == 0 ? 1 << 30 : v) : 1401;
 }
-extern "C" void mdt_op_set_attn_wide_min(int32_t rows) { g_attn_wide_override = rows; }
+extern "C" void mdt_op_set_attn_wide_min(int32_t rows) { g_mdt_sw.attn_wide_min = rows; }
 
 // row count from which (and batch up to which: two rounds of one workgroup per CU) one workgroup per sample runs self-attention,
 // projection AND the collapsed cross-attention (k_attn_xattn); mdt_op_set_attn_wide_min(0) switches it off too
@@ -668,7 +669,7 @@ static int g_attn_xattn_min_rows() {
     // (round 3 started it where the fused MLP launch starts, 1401 rows; measured down the batch sizes in round 4 -- tools/latency.py,
     //  profiles/r04_lowbatch.txt -- it beats k_attn + projection + k_xattn_apply from 200 rows on: B = 20 2.03 -> 1.99 ms, 32 2.13 -> 2.09,
     //  40 2.48 -> 2.35, 80 3.12 -> 3.03, 100 3.26 -> 3.17, 128 3.62 -> 3.52, 140 4.33 -> 4.14; at 160 rows it loses, 1.71 -> 1.75)
-    return g_attn_wide_override == 0 ? 1 << 30 : 200;
+    return g_mdt_sw.attn_wide_min == 0 ? 1 << 30 : 200;
 }
 static constexpr int64_t ATTN_XATTN_MAX_BATCH = 512;
 
@@ -704,7 +705,7 @@ static mdt_status run_self_attn(mdt_model* m, const EncBlock& e, const View& V, 
     // (up to one workgroup per CU: its 156 KB of LDS allow no second one, so beyond 256 tiles -- B > 272 -- the workgroups
     //  queue up behind each other while the plain projection keeps three per CU in flight: B = 512 10.35 vs 10.13 ms)
     const int64_t wide_tiles = (int64_t)((M + 31) / 32) * ((D + 127) / 128);
-    if (M >= g_attn_wide_min_rows() && (wide_tiles <= 256 || g_attn_wide_override > 0) &&
+    if (M >= g_attn_wide_min_rows() && (wide_tiles <= 256 || g_mdt_sw.attn_wide_min > 0) &&
         mdt_attn_proj_wide_supported(p, m->H, m->hd, T, causal, m->cfg.use_rot_embed)) {
         // large batch: the causal attention of each 32-row tile in the projection's prologue (no attention launch, no
         // round trip of the attention output)
@@ -723,25 +724,24 @@ static mdt_status run_self_attn(mdt_model* m, const EncBlock& e, const View& V, 
 
 // row count from which the MLP sublayer runs as ONE launch (k_mlp) that leaves partial slabs instead of the residual
 // stream: below it the wide tiles do not fill the chip
-static int g_mlp_fuse_override = -1;  // mdt_op_set_mlp_fuse_min (tests): 0 disables, -1 = the default
 // (`split`: the launch would run in its bf16 split form, which pays from fewer rows -- mdt_split_min_rows(), B = 128: 1280 rows
 // per call 3.42 -> 2.96 ms with the qkv products split too (mdt_internal.h); a setting made with the hook is taken as it is)
 static int g_mlp_fuse_min_rows(bool split = false) {
-    if (g_mlp_fuse_override >= 0) return g_mlp_fuse_override == 0 ? 1 << 30 : g_mlp_fuse_override;
+    const int v = g_mdt_sw.mlp_fuse_min;
+    if (v >= 0) return v == 0 ? 1 << 30 : v;
     return split ? mdt_split_min_rows() : 1401;
 }
-extern "C" void mdt_op_set_mlp_fuse_min(int32_t rows) { g_mlp_fuse_override = rows; }
+extern "C" void mdt_op_set_mlp_fuse_min(int32_t rows) { g_mdt_sw.mlp_fuse_min = rows; }
 
 // mdt_op_trace_mlp: every fused-MLP launch (k_mlp, the dominant kernel of the B = 256 sampler call) of the model-level calls
 // that follow is bracketed by a pair of HIP events on its stream -- the kernel's duration INSIDE the launch chain (the
 // preceding kernel's tail and the launch gap included, like a kernel-trace row), which 200 back-to-back launches of the
 // kernel alone do not give (bench.py).  mdt_op_trace_mlp_read synchronises the events, returns the
 // durations in microseconds (at most `cap`) and releases them.
-static bool g_trace_mlp = false;
 struct TraceEv { hipEvent_t e0, e1, e2; };   // e0 .. e1 bracket the launch; e1 .. e2 bracket NOTHING (the cost of a bracket itself)
 static std::vector<TraceEv> g_trace_mlp_events;
 static std::vector<float> g_trace_mlp_empty;
-extern "C" void mdt_op_trace_mlp(int32_t enable) { g_trace_mlp = enable != 0; }
+extern "C" void mdt_op_trace_mlp(int32_t enable) { g_mdt_sw.trace_mlp = enable != 0; }
 extern "C" int32_t mdt_op_trace_mlp_read(float* us, int32_t cap) {
     int32_t n = 0;
     g_trace_mlp_empty.clear();
@@ -827,7 +827,7 @@ static mdt_status run_mlp(mdt_model* m, const EncBlock& e, const View& V, int64_
         // the hidden buffer (M x 4D) is free in this form: it holds the S <= 4 slabs of (M x D)
         p.ldo = D;
         const int64_t stride = (int64_t)M * D;
-        if (g_trace_mlp) {  // measurement hook (mdt_op_trace_mlp): this launch between its own pair of HIP events, inside the chain
+        if (g_mdt_sw.trace_mlp > 0) {  // measurement hook (mdt_op_trace_mlp): this launch between its own pair of HIP events, inside the chain
             TraceEv ev;
             HIP_TRY(hipEventCreate(&ev.e0)); HIP_TRY(hipEventCreate(&ev.e1)); HIP_TRY(hipEventCreate(&ev.e2));
             HIP_TRY(hipEventRecord(ev.e0, s));

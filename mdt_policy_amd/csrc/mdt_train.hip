@@ -99,9 +99,7 @@ struct mdt_train_state {
 // MDT_HIP_DW_STREAM = number of side streams the blocks' weight gradients rotate over (0: everything in the chain's stream, as in
 // rounds 1-5; default 1; measured at B = 1024, train mode: 0 -> 9.43 ms per step, 1 -> 9.15)
 static int dw_stream_mode() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MDT_HIP_DW_STREAM"); v = e ? atoi(e) : 1; v = v < 0 ? 0 : (v > mdt_train_state::MAX_SIDE ? mdt_train_state::MAX_SIDE : v); }
-    return v;
+    return std::min(std::max(mdt_switch_env(g_mdt_sw.dw_stream, "MDT_HIP_DW_STREAM", 1), 0), (int)mdt_train_state::MAX_SIDE);
 }
 static mdt_status side_fork(mdt_train_state* ts, int q, hipStream_t s, hipStream_t* out);  // (defined with the backward)
 // a dY buffer of n floats: its own piece of the arena when the weight gradients run beside the chain, else `shared`

@@ -14,6 +14,8 @@
 #include <unordered_map>
 
 #include "mdt_internal.h"
+#include "mdt_hip_debug.h"
+#include "mdt_launch.h"
 
 #include "mdt_device.h"
 
@@ -1214,31 +1216,13 @@ template <int HD, int HG>
 static hipError_t launch_attn_fwd_mfma(const mdt_attn_train_args& a, float scale, hipStream_t s) {
     using AM = AttnMfma<HD, HG>;
     const size_t lds = ((size_t)(a.Tq + 2 * a.Tk) * AM::RS + (size_t)HG * 16 * 17) * sizeof(float);
-    static bool attr_dev[32] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) dev = 0;
-    if (!attr_dev[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_fwd_train_mfma<HD, HG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_dev[dev] = true;
-    }
-    hipLaunchKernelGGL((k_attn_fwd_train_mfma<HD, HG>), dim3(a.B, a.H / HG), dim3(64 * HG), lds, s, a, scale);
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn_fwd_train_mfma<HD, HG>>(dim3(a.B, a.H / HG), dim3(64 * HG), lds, s, a, scale);
 }
 template <int HD, int HG>
 static hipError_t launch_attn_bwd_mfma(const mdt_attn_bwd_args& a, float scale, hipStream_t s) {
     using AM = AttnMfma<HD, HG>;
     const size_t lds = ((size_t)(2 * a.Tq + 2 * a.Tk) * AM::RS + (size_t)HG * (16 * 17 + 2 * 16 * 20)) * sizeof(float);
-    static bool attr_dev[32] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) dev = 0;
-    if (!attr_dev[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_bwd_mfma<HD, HG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_dev[dev] = true;
-    }
-    hipLaunchKernelGGL((k_attn_bwd_mfma<HD, HG>), dim3(a.B, a.H / HG), dim3(64 * HG), lds, s, a, scale);
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn_bwd_mfma<HD, HG>>(dim3(a.B, a.H / HG), dim3(64 * HG), lds, s, a, scale);
 }
 bool mdt_attn_train_mfma_supported(int hd, int H, int rope) { return attn_train_mfma_group(hd, H, rope) != 0; }
 #define ATTN_MFMA_DISPATCH(FN, a, scale, s, hg)                                                         \
@@ -1809,13 +1793,8 @@ static hipError_t launch_attn_long_bwd_t(const float* q, int64_t ldq, const floa
                                          int64_t ld_dkv, int B, int H, int Tq, int Tk, float scale, hipStream_t s, float* dkl,
                                          int F) {
     const size_t lds = attn_long_bwd_lds(HD, Tq, Tk);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_attn_long_bwd<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((k_attn_long_bwd<HD>), dim3(B, H), dim3(256), lds, s, q, ldq, k, v, ldkv, d_out, ld_do, dq, ld_dq, dk,
-                       dv, ld_dkv, Tq, Tk, scale, dkl, F);
-    return hipGetLastError();
+    return mdt_launch_lds<k_attn_long_bwd<HD>>(dim3(B, H), dim3(256), lds, s, q, ldq, k, v, ldkv, d_out, ld_do, dq, ld_dq, dk, dv,
+                                               ld_dkv, Tq, Tk, scale, dkl, F);
 }
 
 hipError_t mdt_launch_attention_long_bwd(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
@@ -2419,12 +2398,9 @@ __global__ __launch_bounds__(TNW == 2 ? 512 : 384) void k_gemm_tn_split(const fl
         }
     }
 }
-static int g_tn_split = -1;   // MDT_HIP_TN_SPLIT / mdt_op_set_tn_split: 0 = the fp32 MFMA kernel everywhere
-bool mdt_gemm_tn_split_on() {
-    if (g_tn_split < 0) { const char* e = getenv("MDT_HIP_TN_SPLIT"); g_tn_split = e ? atoi(e) : 1; }
-    return g_tn_split != 0;
-}
-extern "C" void mdt_op_set_tn_split(int32_t on) { g_tn_split = on < 0 ? -1 : (on != 0); }
+// MDT_HIP_TN_SPLIT / mdt_op_set_tn_split: 0 = the fp32 MFMA kernel everywhere
+bool mdt_gemm_tn_split_on() { return mdt_switch_env(g_mdt_sw.tn_split, "MDT_HIP_TN_SPLIT", 1) != 0; }
+extern "C" void mdt_op_set_tn_split(int32_t on) { g_mdt_sw.tn_split = on < 0 ? -1 : (on != 0); }
 // k-tile of the split kernel for a K-column product: 192 where that pads K less
 int mdt_gemm_tn_split_ktile(int K) { return (K + 191) / 192 * 192 < (K + 127) / 128 * 128 ? 192 : 128; }
 // tile of the split kernel for an (N, K) product: (n, k) = 192 x 128 where 128-wide n-tiles would pad N by more than an eighth and
@@ -2439,17 +2415,8 @@ static hipError_t launch_gemm_tn_split_t(const float* dY, int64_t ldy, const flo
                                          int N, int K, int S, int L, int accumulate, float* bpart, hipStream_t s) {
     constexpr int NWV = TNW == 2 ? 8 : 6, TN_ = 64 * TNW, TK = 16 * KTW * (NWV / TNW);
     constexpr size_t lds = (size_t)2 * 3 * (TN_ + TK) * 80;
-    static bool attr_dev[32] = {false};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) dev = 0;
-    if (!attr_dev[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_tn_split<KTW, TNW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_dev[dev] = true;
-    }
-    hipLaunchKernelGGL((k_gemm_tn_split<KTW, TNW>), dim3(((N + TN_ - 1) / TN_) * ((K + TK - 1) / TK), 1, S), dim3(64 * NWV), lds, s, dY, ldy, X,
-                       ldx, out, slice_stride, M, N, K, L, accumulate, bpart, S > 1 ? 1 : 0);
-    return hipGetLastError();
+    return mdt_launch_lds<k_gemm_tn_split<KTW, TNW>>(dim3(((N + TN_ - 1) / TN_) * ((K + TK - 1) / TK), 1, S), dim3(64 * NWV), lds, s, dY, ldy,
+                                                     X, ldx, out, slice_stride, M, N, K, L, accumulate, bpart, S > 1 ? 1 : 0);
 }
 hipError_t mdt_launch_gemm_tn_split(const float* dY, int64_t ldy, const float* X, int64_t ldx, float* out, int64_t slice_stride, int M, int N,
                                     int K, int S, int L, int accumulate, float* bpart, hipStream_t s) {
@@ -2483,17 +2450,8 @@ static hipError_t launch_gemm_tn_t(const float* dY, int64_t ldy, const float* X,
                                    int N, int K, int S, int L, int accumulate, float* bpart, hipStream_t s) {
     constexpr int TN_ = 64 * WN, TK = 64 * KT;
     constexpr size_t lds = (size_t)2 * 32 * ((TN_ + 4) + (TK + 4)) * sizeof(float);
-    static bool attr_dev[32] = {false};  // per instantiation AND per device: function attributes are per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) dev = 0;
-    if (!attr_dev[dev] && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_gemm_tn<KT, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_dev[dev] = true;
-    }
-    hipLaunchKernelGGL((k_gemm_tn<KT, WN>), dim3(((N + TN_ - 1) / TN_) * ((K + TK - 1) / TK), 1, S), dim3(256 * WN), lds, s, dY, ldy, X, ldx,
-                       out, slice_stride, M, N, K, L, accumulate, bpart, S > 1 ? 1 : 0);
-    return hipGetLastError();
+    return mdt_launch_lds<k_gemm_tn<KT, WN>>(dim3(((N + TN_ - 1) / TN_) * ((K + TK - 1) / TK), 1, S), dim3(256 * WN), lds, s, dY, ldy, X, ldx,
+                                             out, slice_stride, M, N, K, L, accumulate, bpart, S > 1 ? 1 : 0);
 }
 hipError_t mdt_launch_gemm_tn(const float* dY, int64_t ldy, const float* X, int64_t ldx, float* out, int64_t slice_stride, int M, int N,
                               int K, int S, int L, int accumulate, float* bpart, hipStream_t s) {
