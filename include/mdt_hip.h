@@ -240,7 +240,11 @@ typedef struct mdt_sampler_eval {
     int32_t draws;                   /* noise rows the Python loop draws from this evaluation up to the next one      */
     int32_t step;                    /* the sampler step this evaluation belongs to                                   */
     float t;                         /* DPM-Solver kinds: t = -ln(sigma) of this evaluation as the Python loop has it   */
-    int32_t pad[3];
+    int32_t ends_step;               /* 1 on the last evaluation of its sampler step: X' is the step's result (where a loop
+                                        that clips runs scaler.clip_output); a step's pass evaluation is its last          */
+    int32_t begins_step;             /* 1 on the first evaluation of its step: its input and denoised output are what the
+                                        Python loop hands to `callback`                                                   */
+    int32_t pad[1];
 } mdt_sampler_eval;
 
 typedef struct mdt_sampler_plan_t {
@@ -276,6 +280,38 @@ mdt_status mdt_sample_dev(mdt_model *m, const float *tokens, const float *tokens
                           const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_dev,
                           int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out, float *ctx_out,
                           void *stream);
+
+/* mdt_sample / mdt_sample_dev (and their guided and tree-noise twins) with the options a harness run adds, still ONE enqueue
+ * with the launches of the call it extends: action bounds (MDTVAgent.sample_loop's use_scaler) and a per-step record (what a
+ * `callback` would see).
+ *   lo, hi : the bounds of scaler.clip_output, x <- min(max(x, lo), hi) per action dimension as torch.clamp computes it (NaN
+ *            stays NaN; lo > hi gives hi), applied in the head of every evaluation that ends a step of a loop that clips there:
+ *            after every step of euler, euler_ancestral, heun, dpm_2, dpm_2_ancestral, lms, dpmpp_2s, dpmpp_2s_ancestral; after
+ *            every step but the final one of dpmpp_sde; never in dpmpp_2m and dpm_fast (the reference's loops take a scaler
+ *            there and do not read it).  +-inf bounds leave every bit as it is.
+ *   record : one row pair per sampler step i -- n_steps of them, n_steps // 3 + 1 (the solver steps) for MDT_SAMPLER_DPM_FAST --
+ *            [i][0] the input of the step's first evaluation in action units (after the sigma_hat churn: the loop's 'x'),
+ *            [i][1] its denoised output (the guided call: the combined D_lambda).
+ *   tree   : the noise of mdt_sample_sde_tree (kind must be MDT_SAMPLER_DPMPP_SDE; `noise` is then not read).
+ * opts == NULL or {sizeof(mdt_sample_opts), 1.0f, NULL, NULL, NULL, NULL} enqueues exactly what mdt_sample / mdt_sample_dev do.
+ * Checked before anything is enqueued (MDT_ERR_INVALID_ARG, the message names the field): size != sizeof(mdt_sample_opts),
+ * exactly one of lo / hi, a non-finite cond_lambda, tree with another kind.  lo, hi and record need no more than a float's
+ * alignment (the head reads and writes them element by element): a slice of a larger statistics tensor will do. */
+typedef struct mdt_sample_opts {
+    int32_t size;                    /* sizeof(mdt_sample_opts): lets the struct grow                                   */
+    float cond_lambda;               /* 1.0f: the unguided call; anything else: the doubled-batch guided call           */
+    const float *lo, *hi;            /* (A,) device; both NULL: no bounds                                               */
+    float *record;                   /* NULL or (steps, 2, B, Ta, A) device: [i][0] = x, [i][1] = denoised               */
+    const struct mdt_brownian_source *tree; /* NULL, or dpmpp_sde's tree noise as in mdt_sample_sde_tree (below)         */
+} mdt_sample_opts;
+mdt_status mdt_sample_opt(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                          const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_host,
+                          int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out, float *ctx_out,
+                          const mdt_sample_opts *opts, void *stream);
+mdt_status mdt_sample_dev_opt(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                              const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_dev,
+                              int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out, float *ctx_out,
+                              const mdt_sample_opts *opts, void *stream);
 
 /* sample_dpm_adaptive (eta = 0): DPM-Solver-12 / -23 with the PID step-size control of _StepControl, as ONE blocking call.
  * Every attempted step runs its 2 or 3 denoiser evaluations; the head of the last one writes both the order-k ("high") and the

@@ -84,7 +84,8 @@ class SamplerEval(C.Structure):
     """mdt_sampler_eval (include/mdt_hip.h): one denoiser evaluation of a sampler plan."""
     _fields_ = [("sigma", C.c_float), ("sigma_next", C.c_float), ("cx", C.c_float * SAMPLER_NREG),
                 ("cy", C.c_float * (SAMPLER_NREG + 1)), ("push", C.c_int32), ("noise", C.c_int32 * 2), ("draws", C.c_int32),
-                ("step", C.c_int32), ("t", C.c_float), ("pad", C.c_int32 * 3)]
+                ("step", C.c_int32), ("t", C.c_float), ("ends_step", C.c_int32), ("begins_step", C.c_int32),
+                ("pad", C.c_int32 * 1)]
 
 
 class BrownianSource(C.Structure):
@@ -94,6 +95,12 @@ class BrownianSource(C.Structure):
 
 
 BROWNIAN_MAX_PAIRS = 64  # MDT_BROWNIAN_MAX_PAIRS
+
+
+class SampleOpts(C.Structure):
+    """mdt_sample_opts (include/mdt_hip.h): bounds, record, guidance and tree noise of mdt_sample_opt / mdt_sample_dev_opt."""
+    _fields_ = [("size", C.c_int32), ("cond_lambda", C.c_float), ("lo", C.c_void_p), ("hi", C.c_void_p), ("record", C.c_void_p),
+                ("tree", C.POINTER(BrownianSource))]
 
 
 class SamplerPlan(C.Structure):
@@ -229,6 +236,10 @@ SYMBOLS = [
                           _I64, _VP, _VP, _VP]),
     ("mdt_sample_dev", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), _VP, _I32, _VP, _I32, _I64, _VP,
                               _VP, _VP]),
+    ("mdt_sample_opt", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, _VP, _I32,
+                              _I64, _VP, _VP, C.POINTER(SampleOpts), _VP]),
+    ("mdt_sample_dev_opt", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), _VP, _I32, _VP, _I32, _I64, _VP,
+                                  _VP, C.POINTER(SampleOpts), _VP]),
     ("mdt_sampler_plan", _I32, [_I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, C.POINTER(SamplerPlan)]),
     ("mdt_sample_dpm_adaptive", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.c_float, C.c_float, C.POINTER(DpmAdaptiveParams), _I64,
                                        _VP, _VP, C.POINTER(DpmAdaptiveInfo), _VP]),

@@ -175,6 +175,9 @@ struct mdt_head_plan {
     int64_t nel;                // M * A
     int32_t n_noise;            // rows of `noise`: a plan row at or beyond it reads as 0 (the device plan is never trusted
                                 // to stay inside the caller's buffer)
+    // mdt_sample_opts (both pairs null: the epilogue as it was)
+    const float *lo = nullptr, *hi = nullptr;      // (A,) bounds, both or neither: X' is clamped where e->ends_step
+    float *rec_x = nullptr, *rec_d = nullptr;      // (M, A) both or neither: receive Y and D where e->begins_step
 };
 // classifier-free guidance of a sampler call (mdt_sample_*_guided): `on` = the call runs the doubled batch, conditional samples
 // [0, B) and unconditional ones [B, 2B), and its heads combine the two halves with `lam`

@@ -1354,8 +1354,11 @@ extern "C" mdt_status mdt_sampler_plan(int32_t kind, const mdt_sampler_params* p
 
 // evaluation e of the plan in m->plan: (per evaluation for COND_TOKEN: the encoder with its sigma -> ctx_out), one decoder pass,
 // the plan head reading the state xs, writing X' to out and Y' to y_out; the next input is embedded unless `last`
+// bounds (lo, hi: the head clamps X' where the evaluation ends a step) and rec (two (M, A) rows: the head stores Y and D where the
+// evaluation begins a step): mdt_sample_opts' operands for this evaluation, or null
 static mdt_status run_plan_eval(mdt_model* m, const View& V, const SamplerCall& c, int e, bool last, const float* xs, float* out,
-                                float* y_out, const float* noise, int32_t n_noise, float* ctx_out) {
+                                float* y_out, const float* noise, int32_t n_noise, float* ctx_out, const float* lo = nullptr,
+                                const float* hi = nullptr, float* rec = nullptr) {
     mdt_sampler_eval* ev = m->plan->e;
     if (m->cond == COND_TOKEN) MDT_TRY(c.encode(m, &ev[e].sigma, ctx_out));
     mdt_head_plan pl;
@@ -1366,6 +1369,10 @@ static mdt_status run_plan_eval(mdt_model* m, const View& V, const SamplerCall& 
     pl.y_out = y_out;
     pl.nel = (int64_t)c.batch * m->Ta * m->A;
     pl.n_noise = noise ? n_noise : 0;
+    pl.lo = lo;
+    pl.hi = hi;
+    pl.rec_x = rec;
+    pl.rec_d = rec ? rec + pl.nel : nullptr;
     mdt_head_args h = head_args(m, V.y, c.batch, m->ybuf, &ev[e].sigma, 0, out, MDT_HEAD_PLAN);
     return run_eval(m, V, c.nb, cond_row(m, e), 0, h, &pl, last ? nullptr : &ev[e].sigma_next, c.s, c.gd);
 }
@@ -1376,10 +1383,15 @@ static mdt_status run_plan_eval(mdt_model* m, const View& V, const SamplerCall& 
 // tree (dpmpp_sde with tree noise, mdt_sample_sde_tree*): `noise` is null and the rows come from the tree -- the plan kernel records
 // their points, k_brownian_fill writes them into the handle's tr_noise before the first evaluation, which then reads them as a
 // caller's buffer.
+// bounds / record (mdt_sample_opt): lo and hi go to the heads of the evaluations whose step the kind's loop clips
+// (mdt_plan_loop_clips; the head applies them where the plan says the step ends), the record's row pair of step i to the heads of
+// step i's evaluations (the head stores where the plan says the step begins) -- no launch and no buffer of the call's own.
 static mdt_status sample_plan_impl(mdt_model* m, const SamplerArgs& a, int32_t kind, const mdt_sampler_params* params, Sched sc,
-                                   int32_t n_steps, const float* noise, int32_t n_noise, const mdt_brownian_source* tree = nullptr) {
+                                   int32_t n_steps, const float* noise, int32_t n_noise, const mdt_brownian_source* tree = nullptr,
+                                   const float* lo = nullptr, const float* hi = nullptr, float* record = nullptr) {
     mdt_guide gd;
     MDT_TRY(sampler_check(m, a, "mdt_sample", sc.levels != nullptr, &gd));
+    // (lo, hi and record are read and written one element at a time: any float alignment will do, e.g. a slice of a larger tensor)
     const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
     int E = 0, rows = 0;
     MDT_TRY(plan_fail(mdt_plan_shape(kind, p, n_steps, &E, &rows), "mdt_sample", kind));
@@ -1389,6 +1401,10 @@ static mdt_status sample_plan_impl(mdt_model* m, const SamplerArgs& a, int32_t k
         static thread_local mdt_sampler_plan_t hp;
         mdt_build_sampler_plan(kind, p, sc.host(), n_steps, &hp);
         rows = hp.n_noise;
+        for (int e = 0; record && e < hp.n_evals; ++e)  // the record's rows are placed by the structure: it must be the plan's
+            if (hp.e[e].step != mdt_plan_step_of(kind, n_steps, e))
+                return fail(MDT_ERR_STATE, "mdt_sample: evaluation %d is in step %d of the plan, %d by its structure", e, hp.e[e].step,
+                            mdt_plan_step_of(kind, n_steps, e));
     }
     const bool use_tree = tree && mdt_plan_needs_noise(kind, p) && max_rows > 0;
     if (tree) {
@@ -1435,10 +1451,12 @@ static mdt_status sample_plan_impl(mdt_model* m, const SamplerArgs& a, int32_t k
     if (ms == MDT_OK && !per_step_ctx) ms = c.encode(m, nullptr, c.ctx_out);
     if (ms != MDT_OK) { mdt_gemm_side_drop(); return ms; }
     LAUNCH(mdt_gemm_side_flush(c.s));
+    const int64_t rec_stride = 2 * a.batch * m->Ta * m->A;
     for (int e = 0; e < E; ++e) {
-        const bool last = e == E - 1;
+        const bool last = e == E - 1, clips = lo && mdt_plan_loop_clips(kind, last);
         MDT_TRY(run_plan_eval(m, V, c, e, last, e == 0 ? a.x_T : m->xbuf, last ? a.out : m->xbuf, last ? nullptr : m->ybuf, noise,
-                              n_noise, last ? c.ctx_out : nullptr));
+                              n_noise, last ? c.ctx_out : nullptr, clips ? lo : nullptr, clips ? hi : nullptr,
+                              record ? record + mdt_plan_step_of(kind, n_steps, e) * rec_stride : nullptr));
     }
     return sampler_close(m, c);
 }
@@ -1473,6 +1491,46 @@ extern "C" mdt_status mdt_sample_dev_guided(mdt_model* m, const float* tokens, c
                                             int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
     return sample_plan_impl(m, {"mdt_sample_dev_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
                                 stream}, kind, params, {sigmas_dev, true}, n_steps, noise, n_noise);
+}
+
+// mdt_sample_opt / mdt_sample_dev_opt: the options checked (nothing is enqueued before sample_plan_impl's own checks pass), then
+// the call path of mdt_sample and its guided and tree-noise twins
+static mdt_status sample_opt_impl(mdt_model* m, const char* who, const float* tokens, const float* tokens2, const float* goal,
+                                  int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params, Sched sc,
+                                  int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, float* out, float* ctx_out,
+                                  const mdt_sample_opts* opts, void* stream) {
+    mdt_sample_opts o = {(int32_t)sizeof(mdt_sample_opts), 1.f, nullptr, nullptr, nullptr, nullptr};
+    if (opts) {
+        if (opts->size != (int32_t)sizeof(mdt_sample_opts))
+            return fail(MDT_ERR_INVALID_ARG, "%s: opts.size is %d, sizeof(mdt_sample_opts) is %d", who, opts->size,
+                        (int)sizeof(mdt_sample_opts));
+        o = *opts;
+    }
+    if (!std::isfinite(o.cond_lambda)) return fail(MDT_ERR_INVALID_ARG, "%s: opts.cond_lambda must be finite", who);
+    if ((o.lo == nullptr) != (o.hi == nullptr))
+        return fail(MDT_ERR_INVALID_ARG, "%s: opts.lo and opts.hi must both be set or both be null", who);
+    if (o.tree && kind != MDT_SAMPLER_DPMPP_SDE)
+        return fail(MDT_ERR_INVALID_ARG, "%s: opts.tree is the noise of MDT_SAMPLER_DPMPP_SDE (kind %d)", who, kind);
+    const bool guided = o.cond_lambda != 1.f;  // lambda == 1 is the unguided call (mdt_sample_guided gives its bits there too)
+    return sample_plan_impl(m, {who, guided ? &o.cond_lambda : nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
+                                stream}, kind, params, sc, n_steps, o.tree ? nullptr : noise, o.tree ? 0 : n_noise, o.tree, o.lo, o.hi,
+                            o.record);
+}
+
+extern "C" mdt_status mdt_sample_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
+                                     const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas_host,
+                                     int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, float* out,
+                                     float* ctx_out, const mdt_sample_opts* opts, void* stream) {
+    return sample_opt_impl(m, "mdt_sample_opt", tokens, tokens2, goal, modality, x_T, kind, params, {sigmas_host, false}, n_steps,
+                           noise, n_noise, batch, out, ctx_out, opts, stream);
+}
+
+extern "C" mdt_status mdt_sample_dev_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                         int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
+                                         const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
+                                         int64_t batch, float* out, float* ctx_out, const mdt_sample_opts* opts, void* stream) {
+    return sample_opt_impl(m, "mdt_sample_dev_opt", tokens, tokens2, goal, modality, x_T, kind, params, {sigmas_dev, true}, n_steps,
+                           noise, n_noise, batch, out, ctx_out, opts, stream);
 }
 
 static const mdt_brownian_source k_null_tree = {};  // a null `tree` argument: refused by the checks

@@ -84,7 +84,40 @@ MDT_HD inline bool mdt_plan_needs_noise(int kind, const mdt_sampler_params& p) {
     }
 }
 
+// The sampler step evaluation e belongs to, from the structure alone (mdt_sampler_eval::step of any plan of this kind and n): the
+// host places a call's per-step record rows with it without reading a device plan.
+MDT_HD inline int mdt_plan_step_of(int kind, int n, int e) {
+    if (kind == MDT_SAMPLER_DPM_FAST) {  // orders 3 .. 3 then 2, 1 (3 | n) or n % 3: one evaluation per order
+        const int m = n / 3 + 1;
+        for (int i = 0, k = 0; i < m; ++i) {
+            k += n % 3 == 0 ? (i < m - 2 ? 3 : i == m - 2 ? 2 : 1) : (i < m - 1 ? 3 : n % 3);
+            if (e < k) return i;
+        }
+        return m - 1;
+    }
+    int evals = 0, rows = 0;
+    mdt_plan_shape(kind, mdt_sampler_defaults(), n, &evals, &rows);
+    return evals == n ? e : e / 2;  // two evaluations per step but the last
+}
+
+// Whether the reference's loop of this kind runs scaler.clip_output on the result of the step that evaluation e ends (`last`:
+// e is the plan's final evaluation).  sample_dpmpp_2m and sample_dpm_fast take a scaler and never read it, and
+// sample_dpmpp_sde leaves its final Euler step through `continue`, in front of the clip (reference gc_sampling.py:699-734,
+// 673-697, 770-792); every other loop clips after every step.
+MDT_HD inline bool mdt_plan_loop_clips(int kind, bool last) {
+    if (kind == MDT_SAMPLER_DPMPP_2M || kind == MDT_SAMPLER_DPM_FAST) return false;
+    return !(kind == MDT_SAMPLER_DPMPP_SDE && last);
+}
+
 namespace mdt_plan_detail {
+
+// begins_step / ends_step of every evaluation, from its neighbours' `step`
+MDT_HD inline void mark_steps(mdt_sampler_plan_t* P) {
+    for (int k = 0; k < P->n_evals; ++k) {
+        P->e[k].begins_step = k == 0 || P->e[k - 1].step != P->e[k].step;
+        P->e[k].ends_step = k + 1 == P->n_evals || P->e[k + 1].step != P->e[k].step;
+    }
+}
 
 struct Anc { float down, up; };
 // get_ancestral_step (gc_sampling.py:97-103)
@@ -248,6 +281,7 @@ MDT_HD inline void mdt_dpm_adaptive_step_plan(int order, float s, float t, mdt_s
     Builder b{P};
     mdt_sampler_eval& z = dpm_step(b, s, t, order, 0);
     for (int k = 0; k < P->n_evals; ++k) P->e[k].sigma_next = k + 1 < P->n_evals ? P->e[k + 1].sigma : 0.f;
+    mark_steps(P);
     const float h = t - s, sn = dpm_s(t), em = dpm_expm1(h), c0 = sn * em;
     for (int k = 0; k <= MDT_SAMPLER_NREG; ++k) z.cy[k] = 0.f;
     z.cy[MDT_R_X] = 1.f;
@@ -443,6 +477,7 @@ MDT_HD inline int mdt_build_sampler_plan(int kind, const mdt_sampler_params& p, 
     }
     P->n_noise = b.rows;
     for (int k = 0; k < P->n_evals; ++k) P->e[k].sigma_next = k + 1 < P->n_evals ? P->e[k + 1].sigma : 0.f;
+    mark_steps(P);
     mdt_sampler_eval& z = P->e[P->n_evals - 1];
     for (int k = 0; k <= MDT_SAMPLER_NREG; ++k) z.cy[k] = 0.f;  // nothing follows the last evaluation
     return MDT_PLAN_OK;

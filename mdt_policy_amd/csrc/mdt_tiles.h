@@ -1404,7 +1404,10 @@ __device__ __forceinline__ float edm_c_in(float sigma, float sd) { return 1.0f /
 // four rows per wave 4.705).
 // PLAN: the MDT_HEAD_PLAN epilogue -- the per-element update of a sampler plan (mdt_sampler_plan.h) on the registers X, Y, D,
 // d = (Y - D) / sigma, H0..H3, N0, N1; writes X' to a.out, Y' to pl->y_out, shifts the history and embeds Y' (not X') as the next
-// input.  The instantiations without it are the DDIM / denoiser heads as they were.
+// input.  The instantiations without it are the DDIM / denoiser heads as they were.  With pl->lo / pl->hi (kernel arguments: the
+// tests are scalar, one per wave) X' is clamped on the evaluation that ends a step, before Y' is formed from it; with pl->rec_x
+// the evaluation that begins a step also stores Y and D (the guided head: D_lambda).  The bounds are requested with the other
+// operands; without them no load, compare or store is added.
 // GUIDE (classifier-free guidance, RW = 2): a.M counts the rows of STATE; the wave reads the conditional row base of a.y and the
 // unconditional row base + a.M, combines their action_pred outputs F = F_u + lam (F_g - F_u) per element (fp32, before the EDM
 // output scaling), runs the epilogue on state row base and writes the next input's embedding to y_next rows base and base + a.M.
@@ -1470,6 +1473,15 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
         for (int p = 0; p < 2; ++p) wa[c][p] = ldg4(Wa + (int64_t)min(c, a.A - 1) * a.D + cc[p]);
 #pragma unroll
     for (int p = 0; p < 2; ++p) ba4[p] = ldg4(bap + cc[p]);
+    float blo[PLAN ? AMAX : 1], bhi[PLAN ? AMAX : 1];
+    if constexpr (PLAN) {
+#pragma unroll
+        for (int c = 0; c < AMAX; ++c) { blo[c] = 0.f; bhi[c] = 0.f; }
+        if (pl->lo != nullptr) {
+#pragma unroll
+            for (int c = 0; c < AMAX; ++c) { blo[c] = pl->lo[min(c, a.A - 1)]; bhi[c] = pl->hi[min(c, a.A - 1)]; }
+        }
+    }
     float ratio = 0.f, coef = 0.f, sig_next = 1.f;
     if (a.mode == MDT_HEAD_DDIM) {
         ratio = a.step[0];
@@ -1556,6 +1568,8 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
         for (int k = 0; k < MDT_SAMPLER_NREG; ++k) { cx[k] = e.cx[k]; cy[k] = e.cy[k]; }
         cy[MDT_SAMPLER_NREG] = e.cy[MDT_SAMPLER_NREG];
         const int push = e.push;
+        const bool clip = pl->lo != nullptr && e.ends_step != 0;       // wave-uniform, like rec
+        const bool rec = pl->rec_x != nullptr && e.begins_step != 0;
         const int64_t nel = pl->nel;
         const int nn = pl->noise != nullptr ? pl->n_noise : 0;  // rows outside [0, n_noise) read as 0
         const float* n0 = (e.noise[0] >= 0 && e.noise[0] < nn) ? pl->noise + e.noise[0] * nel : nullptr;
@@ -1577,6 +1591,10 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
                 float xn = 0.f, yn = 0.f;
 #pragma unroll
                 for (int q = 0; q < MDT_SAMPLER_NREG; ++q) xn += cx[q] * R[q];
+                if (clip) {  // torch.clamp: ordered compares keep a NaN, and lo > hi gives hi
+                    xn = xn < blo[c] ? blo[c] : xn;
+                    xn = xn > bhi[c] ? bhi[c] : xn;
+                }
                 yn = cy[MDT_SAMPLER_NREG] * xn;
 #pragma unroll
                 for (int q = 0; q < MDT_SAMPLER_NREG; ++q) yn += cy[q] * R[q];
@@ -1584,6 +1602,7 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
                 resy[r * AMAX + c] = yn;
                 if (c < a.A && lane == c && base + r < a.M) {
                     if (pl->y_out != nullptr) pl->y_out[k] = yn;
+                    if (rec) { pl->rec_x[k] = R[MDT_R_Y]; pl->rec_d[k] = R[MDT_R_D]; }
                     if (push != MDT_PUSH_NONE) {
                         pl->hist[3 * nel + k] = R[MDT_R_H0 + 2];
                         pl->hist[2 * nel + k] = R[MDT_R_H0 + 1];

@@ -4,7 +4,8 @@
 libmdt_hip.so when ``model`` is this package's GCDenoiser and no Python hooks are requested: encoder and
 cross-attention K/V once, adaLN vectors of all steps once, the DDIM update fused into the action-head kernel.
 The other fixed-step samplers (euler, heun, the ancestral ones, dpm_2, lms, dpmpp_2m / 2s / sde) run the same way --
-one call, ``GCDenoiser.sample_native`` -> mdt_sample -- under the same condition plus ``scaler=None``, and so does
+one call, ``GCDenoiser.sample_native`` -> mdt_sample -- under the same condition and with ``scaler`` None or an object that
+exposes its bounds (``clip_bounds``, utils/action_bounds.py ActionBounds: the call clamps inside), and so does
 sample_dpm_fast (1..128 evaluations); sample_dpm_adaptive with eta = 0 on the GPU is one blocking call
 (``GCDenoiser.sample_dpm_adaptive_native`` -> mdt_sample_dpm_adaptive).  Otherwise they are host loops over
 ``model(state, x, goal, sigma)`` (the HIP denoiser step) with the sigma-independent encoder hoisted out of the loop.
@@ -181,23 +182,25 @@ def _graph_wanted(model, state, action, goal, sigmas, tag=None) -> bool:
     return seen.get(key, 0) > _GRAPH_AUTO_AFTER
 
 
-def _graph_route(model, cache, tag, key, state, action, goal, sigmas, make, what, noise=None):
+def _graph_route(model, cache, tag, key, state, action, goal, sigmas, make, what, noise=None, bounds=None):
     """A native sampler call replayed as a HIP graph, or None: the eager call runs then.  The rule is _graph_wanted's, ``tag``
     joining the call's graph key (None: unguided DDIM).  The graphs live on the model in the list ``cache`` (at most four) and
     are found by GraphedDDIM.matches with ``key``; ``make(sigmas)`` captures a new one.  In auto mode a capture that fails
     (another thread allocating / synchronising while torch's global capture mode is on, ...) must not break a rollout the eager
-    path would have served: that call shape stays eager, with a warning naming ``what``.  MDT_HIP_GRAPH=1 re-raises."""
+    path would have served: that call shape stays eager, with a warning naming ``what``.  MDT_HIP_GRAPH=1 re-raises.
+    ``bounds``: the call's (lo, hi) action bounds (a graph captured with bounds copies them in before it replays)."""
     if not _graph_wanted(model, state, action, goal, sigmas, tag=tag):
         return None
+    kw = {} if bounds is None else {"bounds": bounds}
     try:
         graphs = model.__dict__.setdefault(cache, [])
         for gsamp in graphs:
             if gsamp.matches(state, action, goal, sigmas, key=key, noise=noise):
-                return gsamp(state, action, goal, sigmas, noise=noise)
+                return gsamp(state, action, goal, sigmas, noise=noise, **kw)
         gsamp = make(sigmas if torch.is_tensor(sigmas) else torch.as_tensor(sigmas))
         graphs.append(gsamp)
         del graphs[:-4]
-        return gsamp(state, action, goal, sigmas, noise=noise)  # the same launches, replayed as a HIP graph
+        return gsamp(state, action, goal, sigmas, noise=noise, **kw)  # the same launches, replayed as a HIP graph
     except Exception as exc:  # noqa: BLE001 -- whatever the capture raised, the eager launches still work
         if _GRAPH_SAMPLER:
             raise
@@ -212,13 +215,22 @@ def _graph_route(model, cache, tag, key, state, action, goal, sigmas, make, what
 
 # ------------------------------------------------------------------------------------------------
 # The other samplers' native path (GCDenoiser.sample_native -> mdt_sample): the whole loop as one enqueue, under the condition
-# sample_ddim uses plus scaler=None (clip_output is not linear).  The noise is drawn here, by torch, with the shapes, count and
+# sample_ddim uses.  clip_output is not linear, so it cannot ride in the plan's coefficients: a scaler that exposes its bounds
+# (a callable ``clip_bounds(device)`` -> (lo, hi), ActionBounds) has them applied by the plan head on the evaluation that ends
+# a step (mdt_sample_opt); any other scaler object keeps the host loop.  The noise is drawn here, by torch, with the shapes, count and
 # order of the host loop, so a seeded call gives the loop's result and leaves the generator where the loop leaves it.  The
 # plan the call builds assumes what every get_sigmas_* guarantees -- all levels > 0 but a final 0 -- which a host schedule is
 # checked for (else: the host loop); a device schedule is read in place, unchecked.
 # ------------------------------------------------------------------------------------------------
+def _scaler_native(scaler) -> bool:
+    """Whether a sampler's ``scaler`` leaves the native call possible: none, or one whose bounds the call can apply itself."""
+    return scaler is None or callable(getattr(scaler, "clip_bounds", None))
+
+
 def _native_ok(model, sigmas, scaler, callback, extra_args) -> bool:
-    if not isinstance(model, GCDenoiser) or callback is not None or not guidance(**(extra_args or {}))[0] or scaler is not None:
+    if not isinstance(model, GCDenoiser) or callback is not None or not guidance(**(extra_args or {}))[0]:
+        return False
+    if not _scaler_native(scaler):
         return False
     n = len(sigmas) - 1
     if n < 1 or n > _lib.SAMPLER_MAX_STEPS:
@@ -251,12 +263,16 @@ def _ancestral_draws(sigmas, eta):
     return sum(1 for i in range(n) if get_ancestral_step(sig[i], sig[i + 1], eta=eta)[0] > 0)
 
 
-def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, extra_args=None, tree=None, **params):
+def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, extra_args=None, tree=None, scaler=None,
+                **params):
     """The native call, replayed as a HIP graph by sample_ddim's rule (rollout-sized batches from the third identical call).
     ``n_steps``: dpm_fast's evaluation count (its schedule is the two levels, which join the graph key with it).  ``extra_args``:
     the sampler's, which _native_ok admitted -- a guidance weight joins the parameters (and with them the graph key).  ``tree``
     (dpmpp_sde, in place of ``noise``): (seeds, tol, lo, hi) of the Brownian tree the call draws from; (tol, lo, hi) join the
-    graph key and the seeds are the graph's per-call input."""
+    graph key and the seeds are the graph's per-call input.  ``scaler``: None or the sampler's, which _native_ok admitted -- its
+    bounds ride in the call; a graph holds them in static buffers refreshed before every replay, so only their presence joins the
+    graph key."""
+    bounds = None if scaler is None else scaler.clip_bounds(action.device)
     lam = guidance(**(extra_args or {}))[1]
     if lam is not None:
         params = dict(params, cond_lambda=lam)
@@ -269,14 +285,28 @@ def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, e
         noise, meta = tree[0], tuple(float(v) for v in tree[1:])
         tag += (("tree",) + meta,)
         key += (("tree",) + meta,)
+    if bounds is not None:
+        tag += ("bounds",)
+        key += ("bounds",)
     out = _graph_route(model, "_graphed_native", tag, key, state, action, goal, sigmas,
-                       lambda sig: GraphedSampler(model, kind, params, state, action, goal, sig, noise, n_steps, tree=meta),
-                       f"sample_{kind}", noise=noise)
+                       lambda sig: GraphedSampler(model, kind, params, state, action, goal, sig, noise, n_steps, tree=meta,
+                                                  bounds=bounds),
+                       f"sample_{kind}", noise=noise, bounds=bounds)
     if out is not None:
         return out
+    kw = {} if bounds is None else {"bounds": bounds}
     if tree is not None:
-        return model.sample_native(kind, state, action, goal, sigmas, tree=tree, **params)
-    return model.sample_native(kind, state, action, goal, sigmas, noise=noise, n_steps=n_steps, **params)
+        return model.sample_native(kind, state, action, goal, sigmas, tree=tree, **kw, **params)
+    return model.sample_native(kind, state, action, goal, sigmas, noise=noise, n_steps=n_steps, **kw, **params)
+
+
+def replay_callback(rec, callback):
+    """Feed the record of ``GCDenoiser.sample_native(..., record=True)`` to a sampler ``callback``: one call per step with the dict
+    the loops pass -- {'x', 'i', 'sigma', 'sigma_hat', 'denoised'} -- for a hook that wants the trajectory of the native call.
+    (A ``callback`` passed to ``sample_*`` itself keeps the host loop, which calls it between the steps.)"""
+    for i in range(rec["x"].shape[0]):
+        callback({'x': rec["x"][i], 'i': i, 'sigma': rec["sigma"][i], 'sigma_hat': rec["sigma_hat"][i],
+                  'denoised': rec["denoised"][i]})
 
 
 @torch.no_grad()
@@ -315,7 +345,7 @@ def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     """Karras Algorithm 2 without the 2nd-order correction (reference gc_sampling.py:164-209)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("euler", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
-                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args)
+                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -342,7 +372,8 @@ def sample_euler_ancestral(model, state, action, goal, sigmas, scaler=None, extr
     """Euler steps to sigma_down plus fresh noise sigma_up (reference gc_sampling.py:213-252)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         noise = _randn_rows(action, _ancestral_draws(sigmas, eta))
-        return _run_native("euler_ancestral", model, state, action, goal, sigmas, noise, eta=eta, extra_args=extra_args)
+        return _run_native("euler_ancestral", model, state, action, goal, sigmas, noise, eta=eta, extra_args=extra_args,
+                           scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -367,7 +398,7 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
     (reference gc_sampling.py:256-312)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("heun", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
-                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args)
+                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -399,6 +430,7 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
 def sample_dpmpp_2m(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None):
     """DPM-Solver++(2M) multistep (reference gc_sampling.py:699-734)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
+        # (the loop below never reads `scaler`, as in the reference: no bounds to pass)
         return _run_native("dpmpp_2m", model, state, action, goal, sigmas, None, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
@@ -425,7 +457,7 @@ def sample_dpmpp_2s(model, state, action, goal, sigmas, scaler=None, extra_args=
                     eta=1.):
     """DPM-Solver++(2S) single-step second order (reference gc_sampling.py:955-994)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
-        return _run_native("dpmpp_2s", model, state, action, goal, sigmas, None, extra_args=extra_args)
+        return _run_native("dpmpp_2s", model, state, action, goal, sigmas, None, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -454,7 +486,7 @@ def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     evaluation at the log-midpoint sigma, full step with the midpoint derivative; Euler on the last step."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("dpm_2", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
-                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args)
+                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -488,7 +520,8 @@ def sample_dpm_2_ancestral(model, state, action, goal, sigmas, scaler=None, extr
     """Ancestral sampling with DPM-Solver-2 midpoint steps (reference gc_sampling.py:374-407)."""
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         noise = _randn_rows(action, _ancestral_draws(sigmas, eta))
-        return _run_native("dpm_2_ancestral", model, state, action, goal, sigmas, noise, eta=eta, extra_args=extra_args)
+        return _run_native("dpm_2_ancestral", model, state, action, goal, sigmas, noise, eta=eta, extra_args=extra_args,
+                           scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -532,7 +565,7 @@ def linear_multistep_coeff(order, t, i, j):
 def sample_lms(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None, order=4):
     """Linear multistep (Adams-Bashforth in sigma) sampler (reference gc_sampling.py:425-460)."""
     if 1 <= order <= 4 and _native_ok(model, sigmas, scaler, callback, extra_args):
-        return _run_native("lms", model, state, action, goal, sigmas, None, order=order, extra_args=extra_args)
+        return _run_native("lms", model, state, action, goal, sigmas, None, order=order, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     sig_np = sig.numpy()
@@ -573,7 +606,7 @@ def sample_dpmpp_2s_ancestral(model, state, action, goal, sigmas, scaler=None, e
             sig = _host(sigmas)
             noise = _sampled_rows(action, [noise_sampler(sig[i], sig[i + 1]) for i in range(n)])
         return _run_native("dpmpp_2s_ancestral", model, state, action, goal, sigmas, noise, eta=eta, s_noise=s_noise,
-                           extra_args=extra_args)
+                           extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
     sig = _host(sigmas)
@@ -802,8 +835,8 @@ def sample_dpm_fast(model, state, action, goal, sigma_min, sigma_max, n, scaler=
     if eta and not t_end > t_start:
         raise ValueError('eta must be 0 for reverse sampling')
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
-    if (isinstance(model, GCDenoiser) and callback is None and guidance(**(extra_args or {}))[0] and scaler is None
-            and 1 <= n <= _lib.SAMPLER_MAX_EVALS):
+    if (isinstance(model, GCDenoiser) and callback is None and guidance(**(extra_args or {}))[0] and _scaler_native(scaler)
+            and 1 <= n <= _lib.SAMPLER_MAX_EVALS):  # (the solver never reads `scaler`, here as in the reference: no bounds to pass)
         return _run_native("dpm_fast", model, state, action, goal, [float(sigma_max), float(sigma_min)],
                            _dpm_fast_noise(action, t_start, t_end, n, eta, noise_sampler), n_steps=n, eta=eta, s_noise=s_noise,
                            extra_args=extra_args)
@@ -1015,7 +1048,7 @@ def sample_dpmpp_sde(model, state, action, goal, sigmas, extra_args=None, callba
             tree = noise_sampler.native_tree(action.device)
         if tree is not None:
             return _run_native("dpmpp_sde", model, state, action, goal, sigmas, None, eta=eta, s_noise=s_noise, r=r,
-                               extra_args=extra_args, tree=tree)
+                               extra_args=extra_args, tree=tree, scaler=scaler)
         sig = _host(sigmas)  # the noise sampler takes host values (a device schedule is read back for it)
         if noise_sampler is None:
             noise_sampler = BrownianTreeNoiseSampler(action, sig[sig > 0].min(), sig.max())
@@ -1028,7 +1061,7 @@ def sample_dpmpp_sde(model, state, action, goal, sigmas, extra_args=None, callba
             if _f(get_ancestral_step(_sigma(t), _sigma(t_next), eta)[1]) != 0:
                 values.append(noise_sampler(_sigma(t), _sigma(t_next)))
         return _run_native("dpmpp_sde", model, state, action, goal, sigmas, _sampled_rows(action, values), eta=eta,
-                           s_noise=s_noise, r=r, extra_args=extra_args)
+                           s_noise=s_noise, r=r, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     if noise_sampler is None:

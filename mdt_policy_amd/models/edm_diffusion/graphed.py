@@ -44,6 +44,7 @@ class GraphedDDIM:
         return self.model._engine(state=self._static_state)
 
     _noise = None  # the captured noise rows (GraphedSampler)
+    _lo = _hi = None  # the static action bounds of a call captured with bounds (GraphedSampler)
 
     def _call_key(self):
         """What besides the shapes a call must share with the captured one to replay it (matches)."""
@@ -54,7 +55,7 @@ class GraphedDDIM:
             return self.model.sample_ddim(self._static_state, self._x, self._goal, self._sig, cond_lambda=self.cond_lambda)
         return self.model.sample_ddim(self._static_state, self._x, self._goal, self._sig)
 
-    def _extra_inputs(self, noise):
+    def _extra_inputs(self, noise, bounds=None):
         return [], []
 
     def _capture(self) -> None:
@@ -100,7 +101,7 @@ class GraphedDDIM:
 
     @torch.no_grad()
     def __call__(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas=None, fresh: bool = True,
-                 noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 noise: Optional[torch.Tensor] = None, bounds=None) -> torch.Tensor:
         """Same result as ``model.sample_ddim(state, x_T, goal, sigmas)``, including ``inner_model.latent_encoder_emb``: both are
         fresh tensors the next call does not touch.  ``fresh=False`` hands out the graph's own static buffers instead (valid
         until the next call; one copy launch less)."""
@@ -120,7 +121,7 @@ class GraphedDDIM:
             if torch.is_tensor(v):
                 dst.append(v); src.append(state[k])
         dst += [self._x, self._goal]; src += [x_T, goal]
-        d2, s2 = self._extra_inputs(noise)
+        d2, s2 = self._extra_inputs(noise, bounds)
         dst += d2; src += s2
         if sigmas is not None:
             # n + 1 floats: never skipped on identity -- a caller may rewrite its schedule tensor in place (same object, new values).
@@ -161,7 +162,13 @@ class GraphedSampler(GraphedDDIM):
     the other inputs, so a replay consumes the same random stream as the eager call."""
 
     def __init__(self, model, kind: str, params: dict, state: dict, x_T: torch.Tensor, goal: torch.Tensor,
-                 sigmas: torch.Tensor, noise: Optional[torch.Tensor], n_steps: Optional[int] = None, tree: Optional[tuple] = None):
+                 sigmas: torch.Tensor, noise: Optional[torch.Tensor], n_steps: Optional[int] = None, tree: Optional[tuple] = None,
+                 bounds: Optional[tuple] = None):
+        # bounds: (lo, hi) action bounds of the captured call (GCDenoiser.sample_native's ``bounds``).  The graph reads them from
+        # static (A,) buffers that every call fills with ITS bounds before the replay: the values are not part of the graph, only
+        # their presence is (_call_key)
+        if bounds is not None:
+            self._lo, self._hi = (torch.as_tensor(b).detach().to(x_T.device, torch.float32).reshape(-1).clone() for b in bounds)
         self.kind, self.params, self.n_steps = kind, dict(params), n_steps  # n_steps: dpm_fast's evaluation count
         # tree: (tol, lo, hi) of a dpmpp_sde call that draws Brownian-tree noise inside (GCDenoiser.sample_native's ``tree``); its
         # seeds are then the static input `noise` -- copied in per call, so that a replay walks the new call's trees
@@ -170,16 +177,23 @@ class GraphedSampler(GraphedDDIM):
         super().__init__(model, state, x_T, goal, sigmas)
 
     def _call_key(self):
-        return (self.kind, self.params, self.n_steps) + (() if self.tree is None else (("tree",) + self.tree,))
+        return ((self.kind, self.params, self.n_steps) + (() if self.tree is None else (("tree",) + self.tree,))
+                + (() if self._lo is None else ("bounds",)))
 
     def _run(self):
+        kw = {} if self._lo is None else {"bounds": (self._lo, self._hi)}
         if self.tree is not None:
             return self.model.sample_native(self.kind, self._static_state, self._x, self._goal, self._sig,
-                                            tree=(self._noise,) + self.tree, **self.params)
+                                            tree=(self._noise,) + self.tree, **kw, **self.params)
         return self.model.sample_native(self.kind, self._static_state, self._x, self._goal, self._sig, noise=self._noise,
-                                        n_steps=self.n_steps, **self.params)
+                                        n_steps=self.n_steps, **kw, **self.params)
 
-    def _extra_inputs(self, noise):
+    def _extra_inputs(self, noise, bounds=None):
         if (noise is None) != (self._noise is None) or (noise is not None and noise.shape != self._noise.shape):
             raise ValueError("GraphedSampler: the noise rows must have the captured shape")
-        return ([], []) if noise is None else ([self._noise], [noise])
+        if (bounds is None) != (self._lo is None):
+            raise ValueError("GraphedSampler: a graph captured with action bounds replays calls with bounds, and only those")
+        dst, src = ([], []) if noise is None else ([self._noise], [noise])
+        if bounds is not None:
+            dst += [self._lo, self._hi]; src += [bounds[0], bounds[1]]
+        return dst, src

@@ -46,6 +46,29 @@ def _instantiate(cfg):
         return getattr(importlib.import_module(module), cls)(**kwargs)
 
 
+def _record_sigmas(kind, sigmas, n_steps, params):
+    """(sigma, sigma_hat) of every step of a native sampler call, as its Python loop hands them to ``callback``: from
+    mdt_sampler_plan for a host schedule (CPU tensors), computed with torch in place for a device one (no read-back)."""
+    from ... import _lib
+    if not (torch.is_tensor(sigmas) and sigmas.device.type == "cuda"):
+        sig = [float(v) for v in sigmas]
+        plan = _lib.sampler_plan(kind, sig, n_steps, **params)
+        first = [plan.e[k] for k in range(plan.n_evals) if plan.e[k].begins_step]
+        hat = torch.tensor([e.sigma for e in first], dtype=torch.float32)
+        return (hat.clone() if kind == "dpm_fast" else torch.tensor(sig[:len(first)], dtype=torch.float32)), hat
+    sig = sigmas.detach().to(torch.float32).reshape(-1)
+    if kind == "dpm_fast":  # the solver steps' left ends on the uniform grid in t = -ln(sigma)
+        m = int(n_steps) // 3 + 1
+        t = torch.stack([torch.lerp(-sig[0].log(), -sig[1].log(), i / m) for i in range(m)])
+        return t.neg().exp(), t.neg().exp()
+    sigma = sig[:-1]
+    if kind in ("euler", "heun", "dpm_2") and params.get("s_churn", 0.):
+        gamma = min(params["s_churn"] / sigma.numel(), 2 ** 0.5 - 1)
+        inside = (sigma >= params.get("s_tmin", 0.)) & (sigma <= params.get("s_tmax", float("inf")))
+        return sigma, sigma * (1 + gamma * inside.to(sigma.dtype))
+    return sigma, sigma.clone()
+
+
 class GCDenoiser(nn.Module):
     """Karras et al. (2022) preconditioner around the MI355X-native score network."""
 
@@ -274,7 +297,8 @@ class GCDenoiser(nn.Module):
         return self._engine(state=state).denoise_vjp(state, action, im._goals(goal, False), sigma, v)
 
     @torch.no_grad()
-    def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, cond_lambda=None, tree=None, **params):
+    def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, cond_lambda=None, tree=None, bounds=None,
+                      record=False, **params):
         """One of the other samplers (``kind``: 'euler', 'heun', 'dpmpp_2m', ... -- the gc_sampling function name without
         'sample_') as one enqueue on the current stream (mdt_sample).  ``noise``: None or (n_noise, B, Ta, A) in the Python loop's
         draw order -- raw randn draws (euler / heun / dpm_2 / the ancestral samplers) or the noise_sampler values (dpmpp_2s_ancestral,
@@ -283,9 +307,31 @@ class GCDenoiser(nn.Module):
         count.  ``cond_lambda``: classifier-free guidance weight (None or 1: the unguided call; include/mdt_hip.h
         mdt_sample_guided; _engine.guidance reads it).  ``tree`` ('dpmpp_sde' only, in place of ``noise``): (seeds, tol) or
         (seeds, tol, lo, hi) -- the Brownian tree the call draws its noise rows from (mdt_sample_sde_tree): ``seeds`` an int64
-        tensor of 1 or B keys on the model's device, ``lo`` < ``hi`` the tree's interval (default: the schedule's)."""
+        tensor of 1 or B keys on the model's device, ``lo`` < ``hi`` the tree's interval (default: the schedule's).
+        ``bounds``: an ``ActionBounds`` (utils/action_bounds.py) or a (lo, hi) pair of length-A sequences / tensors -- what the
+        loop's ``scaler.clip_output`` clamps to, applied inside the call where the reference's loop of this kind clips (after
+        every step; dpmpp_sde: not after the last; dpmpp_2m and dpm_fast: never -- include/mdt_hip.h mdt_sample_opts).
+        ``record=True``: returns (actions, rec) with rec = {'x', 'denoised': (n_steps, B, Ta, A), 'sigma', 'sigma_hat':
+        (n_steps,)}, what a ``callback`` of the loop sees per step (dpm_fast: per solver step); gc_sampling.replay_callback feeds
+        it to one.  The actions are those of the call without ``record``, bit for bit."""
         from ... import _lib
         im = self.inner_model
+        if bounds is not None or record:
+            if bounds is not None:
+                pair = bounds.clip_bounds(action.device) if callable(getattr(bounds, "clip_bounds", None)) else bounds
+                bounds = tuple(torch.as_tensor(b, dtype=torch.float32).to(action.device) for b in pair)
+            if tree is not None:
+                if kind != "dpmpp_sde" or noise is not None or n_steps is not None:
+                    raise ValueError("sample_native: tree noise is for 'dpmpp_sde' and takes no noise rows")
+                tree = (tuple(tree) + (0., 0.))[:4]
+            out, ctx, rec = self._engine(state=state).sample_native_opt(
+                _lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action, im._goals(goal, False), sigmas, noise,
+                n_steps=n_steps, cond_lambda=cond_lambda, tree=tree, bounds=bounds, record=record)
+            im.latent_encoder_emb = ctx
+            if not record:
+                return out
+            sigma, sigma_hat = _record_sigmas(kind, sigmas, n_steps, params)
+            return out, {"x": rec[:, 0], "denoised": rec[:, 1], "sigma": sigma, "sigma_hat": sigma_hat}
         if tree is not None:
             if kind != "dpmpp_sde" or noise is not None or n_steps is not None:
                 raise ValueError("sample_native: tree noise is for 'dpmpp_sde' and takes no noise rows")
@@ -314,9 +360,12 @@ class GCDenoiser(nn.Module):
         return out, info
 
     @torch.no_grad()
-    def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None):
+    def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None, bounds=None, record=False):
         """Whole DDIM loop (reference gc_sampling.py:922-951) as one enqueue on the current stream.  ``cond_lambda``:
-        classifier-free guidance weight (None or 1: the unguided call; mdt_sample_ddim_guided)."""
+        classifier-free guidance weight (None or 1: the unguided call; mdt_sample_ddim_guided).  ``bounds`` is accepted and not
+        read, as the reference's DDIM accepts a scaler and never clips; the DDIM head keeps no per-step record."""
+        if record:
+            raise NotImplementedError("sample_ddim keeps no per-step record; run the host loop with a callback")
         im = self.inner_model
         out, ctx = self._engine(state=state).sample_ddim(state, action, im._goals(goal, False), sigmas,
                                                          cond_lambda=cond_lambda)

@@ -50,6 +50,7 @@ def guidance(cond_lambda=None, **other):
 _SAMPLER_ENTRIES = {
     "ddim": (("mdt_sample_ddim", "mdt_sample_ddim_guided"), ("mdt_sample_ddim_dev", "mdt_sample_ddim_dev_guided")),
     "plan": (("mdt_sample", "mdt_sample_guided"), ("mdt_sample_dev", "mdt_sample_dev_guided")),
+    "plan_opt": (("mdt_sample_opt",), ("mdt_sample_dev_opt",)),  # the guidance weight rides in mdt_sample_opts
     "dpm_adaptive": (("mdt_sample_dpm_adaptive", "mdt_sample_dpm_adaptive_guided"),),
     "sde_tree": (("mdt_sample_sde_tree", "mdt_sample_sde_tree_guided"), ("mdt_sample_sde_tree_dev", "mdt_sample_sde_tree_dev_guided")),
 }
@@ -322,6 +323,33 @@ class HipEngine:
         than the levels) or dpm_fast's evaluation count.  Like sample_ddim, a device schedule is read in place (no copy, no
         synchronisation).  ``cond_lambda`` (not None or 1): classifier-free guidance (mdt_sample_guided / mdt_sample_dev_guided)."""
         return self._sample("plan", state, x_T, goal, cond_lambda, (int(kind), C.byref(params)), sigmas, n_steps, noise, rows=True)
+
+    def sample_native_opt(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
+                          noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None,
+                          cond_lambda: Optional[float] = None, tree=None, bounds=None, record: bool = False):
+        """sample_native / sample_sde_tree with action bounds and / or a per-step record (mdt_sample_opt / mdt_sample_dev_opt):
+        ``bounds`` None or (lo, hi), fp32 (A,) tensors on the device, read when the kernels run (a captured call reads what they
+        hold at replay); ``record``: the call also returns the (steps, 2, B, Ta, A) record -- [i][0] the input of step i's first
+        evaluation, [i][1] its denoised output; ``tree``: None or (seeds, tol, lo, hi) as in sample_sde_tree.  Returns
+        (out, ctx, record or None).  Capture-safe like sample_native."""
+        lam = guidance(cond_lambda)[1]
+        lo = hi = rec = src = None
+        if bounds is not None:
+            lo, hi = (self._in(b, (self.A,)) for b in bounds)
+        if tree is not None:
+            seeds = tree[0]
+            if seeds.device != self.device or seeds.dtype != torch.int64 or not seeds.is_contiguous():
+                raise ValueError("sample_native_opt: seeds must be a contiguous int64 tensor on the model's device")
+            src = _lib.BrownianSource(seeds.data_ptr(), int(seeds.numel()), 0, float(tree[2]), float(tree[3]), float(tree[1]))
+        if record:
+            steps = len(sigmas) - 1 if n_steps is None else int(n_steps) // 3 + 1  # n_steps: dpm_fast's evaluation count
+            rec = torch.empty((steps, 2, x_T.shape[0], self.Ta, self.A), device=self.device, dtype=torch.float32)
+        opts = _lib.SampleOpts(C.sizeof(_lib.SampleOpts), 1.0 if lam is None else lam, _ptr(lo), _ptr(hi), _ptr(rec),
+                               None if src is None else C.pointer(src))
+        out, ctx = self._sample("plan_opt", state, x_T, goal, None, (int(kind), C.byref(params)), sigmas, n_steps, noise, rows=True,
+                                tail=(C.byref(opts),))
+        self._keep = self._keep + (lo, hi, src, None if tree is None else tree[0])
+        return out, ctx, rec
 
     def sample_sde_tree(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, seeds: torch.Tensor, tol: float,
                         lo: float = 0., hi: float = 0., cond_lambda: Optional[float] = None):

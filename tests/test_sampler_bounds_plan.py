@@ -1,0 +1,188 @@
+"""Step marks of the sampler plans, ActionBounds and the routing of a scaler, without a GPU: the plan says on which evaluation
+a sampler step begins (what a ``callback`` sees) and ends (where ``scaler.clip_output`` runs), the C structs keep their sizes,
+``ActionBounds.clip_output`` is ``torch.clamp``, and a scaler that exposes its bounds keeps the native call."""
+import ctypes as C
+import math
+
+import pytest
+import torch
+
+from mdt_policy_amd import _lib
+from mdt_policy_amd.utils.action_bounds import ActionBounds
+
+KINDS = ["euler", "euler_ancestral", "heun", "dpm_2", "dpm_2_ancestral", "lms", "dpmpp_2s", "dpmpp_2s_ancestral", "dpmpp_2m",
+         "dpmpp_sde"]
+VARIANTS = {"euler": [{}, dict(s_churn=2.0)], "heun": [{}, dict(s_churn=2.0)], "dpm_2": [{}, dict(s_churn=2.0)],
+            "euler_ancestral": [{}, dict(eta=0.)], "dpm_2_ancestral": [{}, dict(eta=0.)], "dpmpp_2s_ancestral": [{}, dict(eta=0.)],
+            "dpmpp_sde": [{}, dict(eta=0.)], "dpm_fast": [{}, dict(eta=0.5)]}
+
+
+def gs():
+    from mdt_policy_amd.models.edm_diffusion import gc_sampling
+    return gc_sampling
+
+
+def test_the_plan_structs_keep_their_sizes():
+    assert C.sizeof(_lib.SamplerEval) == 128  # 32 words
+    assert C.sizeof(_lib.SamplerPlan) == 32 + 128 * _lib.SAMPLER_MAX_EVALS
+    assert _lib.SamplerEval.ends_step.offset == 116 and _lib.SamplerEval.begins_step.offset == 120
+    # the library writes the same layout: the last evaluation of a 64-step heun plan (evaluation 126) is marked, the unused
+    # evaluation after it and the bytes after the struct are untouched
+    buf = (C.c_char * (C.sizeof(_lib.SamplerPlan) + 64))(*([0x5a] * (C.sizeof(_lib.SamplerPlan) + 64)))
+    plan = _lib.SamplerPlan.from_buffer(buf)
+    sig = gs().get_sigmas_exponential(64, 0.001, 80.0)
+    arr = (C.c_float * 65)(*[float(v) for v in sig])
+    _lib.check(_lib.load().mdt_sampler_plan(_lib.SAMPLER_KIND["heun"], None, arr, 64, C.byref(plan)))
+    assert plan.n_evals == 127 and plan.e[126].ends_step == 1 and plan.e[126].step == 63
+    assert bytes(buf[C.sizeof(_lib.SamplerPlan):]) == b"\x5a" * 64
+    assert bytes(buf[32 + 127 * 128:32 + 128 * 128]) == b"\x5a" * 128
+
+
+def _check_marks(plan, steps, what):
+    ev = [plan.e[k] for k in range(plan.n_evals)]
+    assert [e.step for e in ev] == sorted(e.step for e in ev), what
+    for i in range(steps):
+        mine = [e for e in ev if e.step == i]
+        assert mine, f"{what}: step {i} has no evaluation"
+        assert [e.begins_step for e in mine] == [1] + [0] * (len(mine) - 1), f"{what}: begins_step of step {i}"
+        assert [e.ends_step for e in mine] == [0] * (len(mine) - 1) + [1], f"{what}: ends_step of step {i}"
+    assert {e.step for e in ev} == set(range(steps)), what
+    assert ev[-1].ends_step == 1, what
+    assert all(e.pad[0] == 0 for e in ev), what
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 5])
+@pytest.mark.parametrize("kind", KINDS)
+def test_every_step_has_one_first_and_one_last_evaluation(kind, n):
+    sig = gs().get_sigmas_exponential(n, 0.001, 80.0)
+    for kw in VARIANTS.get(kind, [{}]):
+        _check_marks(_lib.sampler_plan(kind, sig, **kw), n, f"{kind} n={n} {kw}")
+
+
+@pytest.mark.parametrize("kind", ["dpm_2_ancestral", "dpmpp_2s_ancestral"])
+def test_a_pass_evaluation_is_the_last_of_its_step(kind):
+    """A step whose sigma_down rounds to 0 before the last one (a steep schedule) skips its second evaluation in the loop; the
+    plan pads it with a pass evaluation, which carries the step's ends_step."""
+    sig = [80.0, 1e-30, 1e-31, 0.0]
+    plan = _lib.sampler_plan(kind, sig, eta=1.0)
+    _check_marks(plan, 3, kind)
+    padded = [k for k in range(plan.n_evals - 1) if plan.e[k].begins_step and plan.e[k + 1].step == plan.e[k].step
+              and plan.e[k + 1].cx[0] == 1.0 and not any(plan.e[k + 1].cx[1:])]
+    assert padded, "the schedule produced no pass evaluation: the case checks nothing"
+    for k in padded:
+        assert plan.e[k].ends_step == 0 and plan.e[k + 1].ends_step == 1 and plan.e[k + 1].begins_step == 0
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 7])
+def test_dpm_fast_marks_follow_its_solver_steps(n):
+    for kw in VARIANTS["dpm_fast"]:
+        plan = _lib.sampler_plan("dpm_fast", [80.0, 0.001], n, **kw)
+        assert plan.n_evals == n
+        _check_marks(plan, n // 3 + 1, f"dpm_fast n={n} {kw}")
+        assert sum(plan.e[k].begins_step for k in range(n)) == n // 3 + 1
+        assert sum(plan.e[k].ends_step for k in range(n)) == n // 3 + 1
+
+
+@pytest.mark.parametrize("order", [2, 3])
+def test_an_adaptive_attempt_is_one_step(order):
+    plan = _lib.SamplerPlan()
+    _lib.check(_lib.load().mdt_dpm_adaptive_plan(order, -4.0, -3.5, C.byref(plan)))
+    assert plan.n_evals == order
+    _check_marks(plan, 1, f"adaptive order {order}")
+
+
+# ---- ActionBounds ------------------------------------------------------------------------------------------------------------
+def test_clip_output_is_torch_clamp_bit_for_bit():
+    lo = [-1.0, -0.5, -math.inf, 0.25, -2.0, -1e-3, 0.0]
+    hi = [1.0, 0.5, 0.0, 0.25, math.inf, 1e-3, 3.0]
+    b = ActionBounds(lo, hi)
+    torch.manual_seed(0)
+    x = torch.randn(5, 10, 7) * 2
+    x[0, 0, :] = float("nan")
+    x[1, 1, 2], x[1, 2, 4], x[2, 0, 0], x[2, 0, 1] = math.inf, -math.inf, -0.0, 0.5
+    want = torch.clamp(x, torch.tensor(lo), torch.tensor(hi))
+    got = b.clip_output(x)
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    assert torch.isnan(got[0, 0]).all()
+    lo_t, hi_t = b.clip_bounds("cpu")
+    assert lo_t.dtype == torch.float32 and lo_t.shape == (7,) and lo_t is b.clip_bounds(torch.device("cpu"))[0]
+    assert torch.equal(lo_t, torch.tensor(lo)) and torch.equal(hi_t, torch.tensor(hi))
+
+
+def test_the_constructor_refuses_what_it_cannot_clamp_to():
+    with pytest.raises(ValueError, match="NaN"):
+        ActionBounds([0.0, float("nan")], [1.0, 1.0])
+    with pytest.raises(ValueError, match="NaN"):
+        ActionBounds([0.0, 0.0], [1.0, float("nan")])
+    with pytest.raises(ValueError, match="exceed"):
+        ActionBounds([0.0, 2.0], [1.0, 1.0])
+    with pytest.raises(ValueError, match="values each"):
+        ActionBounds([0.0, 0.0, 0.0], [1.0, 1.0])
+    with pytest.raises(ValueError, match="values each"):
+        ActionBounds([0.0] * 6, [1.0] * 6, action_dim=7)
+    ActionBounds([-math.inf] * 7, [math.inf] * 7, action_dim=7)  # no bounds at all is legal
+    ActionBounds(torch.zeros(7), torch.zeros(7, dtype=torch.float64))  # lo == hi too
+
+
+def test_from_statistics_applies_the_margin():
+    b = ActionBounds.from_statistics([-1.0, 0.0, 2.0], [1.0, 4.0, 2.0], margin=0.25)
+    assert torch.equal(b.lo, torch.tensor([-1.5, -1.0, 2.0])) and torch.equal(b.hi, torch.tensor([1.5, 5.0, 2.0]))
+    b0 = ActionBounds.from_statistics(torch.tensor([-1.0, 0.0]), torch.tensor([1.0, 4.0]))
+    assert torch.equal(b0.lo, torch.tensor([-1.0, 0.0])) and torch.equal(b0.hi, torch.tensor([1.0, 4.0]))
+    with pytest.raises(ValueError):
+        ActionBounds.from_statistics([0.0], [1.0], margin=-0.1)
+    with pytest.raises(ValueError):
+        ActionBounds.from_statistics([0.0, 0.0], [1.0])
+
+
+# ---- routing -----------------------------------------------------------------------------------------------------------------
+class _ClampOnly:
+    """A scaler as any harness may bring it: clip_output and nothing else."""
+
+    def __init__(self, lo, hi):
+        self.lo, self.hi = lo, hi
+
+    def clip_output(self, x):
+        return torch.clamp(x, self.lo.to(x.device), self.hi.to(x.device))
+
+
+def _denoiser():
+    from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
+    return GCDenoiser.__new__(GCDenoiser)  # _native_ok reads the type alone
+
+
+def test_a_scaler_with_bounds_keeps_the_native_call():
+    g = gs()
+    sig = g.get_sigmas_exponential(4, 0.001, 80.0)
+    model = _denoiser()
+    assert g._native_ok(model, sig, None, None, None)
+    assert g._native_ok(model, sig, ActionBounds([-1.0] * 7, [1.0] * 7), None, None)
+    assert not g._native_ok(model, sig, _ClampOnly(-torch.ones(7), torch.ones(7)), None, None)
+    assert not g._native_ok(model, sig, ActionBounds([-1.0] * 7, [1.0] * 7), lambda d: None, None)  # a callback: the host loop
+    assert not g._native_ok(lambda *a: None, sig, ActionBounds([-1.0] * 7, [1.0] * 7), None, None)
+
+
+def test_replay_callback_hands_out_the_loops_dicts():
+    rec = {"x": torch.arange(24.).view(3, 2, 2, 2), "denoised": -torch.arange(24.).view(3, 2, 2, 2),
+           "sigma": torch.tensor([3.0, 2.0, 1.0]), "sigma_hat": torch.tensor([3.5, 2.0, 1.0])}
+    seen = []
+    gs().replay_callback(rec, seen.append)
+    assert [d["i"] for d in seen] == [0, 1, 2]
+    for i, d in enumerate(seen):
+        assert set(d) == {"x", "i", "sigma", "sigma_hat", "denoised"}
+        assert torch.equal(d["x"], rec["x"][i]) and torch.equal(d["denoised"], rec["denoised"][i])
+        assert float(d["sigma"]) == float(rec["sigma"][i]) and float(d["sigma_hat"]) == float(rec["sigma_hat"][i])
+
+
+def test_record_sigmas_of_a_host_schedule_are_the_loops():
+    from mdt_policy_amd.models.edm_diffusion.score_wrappers import _record_sigmas
+    sig = gs().get_sigmas_exponential(4, 0.01, 80.0)
+    s, h = _record_sigmas("heun", sig, None, dict(s_churn=2.0))
+    assert torch.equal(s, sig[:-1])
+    gamma = min(2.0 / 4, 2 ** 0.5 - 1)
+    assert torch.allclose(h, sig[:-1] * (gamma + 1), rtol=1e-6)
+    s, h = _record_sigmas("lms", sig, None, {})
+    assert torch.equal(s, sig[:-1]) and torch.equal(h, sig[:-1])
+    s, h = _record_sigmas("dpm_fast", [80.0, 0.01], 7, {})
+    grid = torch.linspace(-math.log(80.0), -math.log(0.01), 4)[:3]
+    assert s.shape == (3,) and torch.allclose(s, grid.neg().exp(), rtol=1e-5) and torch.equal(s, h)
