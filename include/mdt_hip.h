@@ -293,16 +293,32 @@ mdt_status mdt_sample_dev(mdt_model *m, const float *tokens, const float *tokens
  *            [i][0] the input of the step's first evaluation in action units (after the sigma_hat churn: the loop's 'x'),
  *            [i][1] its denoised output (the guided call: the combined D_lambda).
  *   tree   : the noise of mdt_sample_sde_tree (kind must be MDT_SAMPLER_DPMPP_SDE; `noise` is then not read).
- * opts == NULL or {sizeof(mdt_sample_opts), 1.0f, NULL, NULL, NULL, NULL} enqueues exactly what mdt_sample / mdt_sample_dev do.
- * Checked before anything is enqueued (MDT_ERR_INVALID_ARG, the message names the field): size != sizeof(mdt_sample_opts),
- * exactly one of lo / hi, a non-finite cond_lambda, tree with another kind.  lo, hi and record need no more than a float's
- * alignment (the head reads and writes them element by element): a slice of a larger statistics tensor will do. */
+ *   pin_known, pin_keep : pinned actions (chunk inpainting: receding-horizon replanning with overlap, way-points, "first action =
+ *            current pose").  Both (B, Ta, A), keep in [0, 1].  The pin is an argument of the denoiser:
+ *                D'(x; sigma) = keep * known + (1 - keep) * D(x; sigma)
+ *            per element in fp32 as D + keep (known - D), with selects at both ends: keep == 0 gives the bits of D, keep == 1 the
+ *            bits of known.  With guidance D is the combined D_lambda (guide first, then pin).  The head applies it right after
+ *            the EDM combine, so every sampler uses D' wherever it used D: its update, its derivative d = (x - D') / sigma, its
+ *            history slots and the `denoised` of the record.  Bounds clamp x where they did; x_T stays the caller's.  Under every
+ *            kind whose schedule ends at sigma = 0 the elements with keep == 1 arrive at `known` to rounding; MDT_SAMPLER_DPM_FAST
+ *            stops at sigma_min and arrives within O(sigma_min); 0 < keep < 1 blends the prediction toward `known` at every step.
+ *            Values outside [0, 1] are not checked here (the Python facade's ActionPin refuses them).
+ * opts == NULL or {sizeof(mdt_sample_opts), 1.0f, NULL, NULL, NULL, NULL} enqueues exactly what mdt_sample / mdt_sample_dev do: a
+ * call without a pin launches the kernels it launched before the pin existed.
+ * `size` is sizeof(mdt_sample_opts), or the struct's size before pin_known / pin_keep were appended (40 on LP64): the two fields
+ * then read as NULL, so a client compiled against the earlier header keeps working.
+ * Checked before anything is enqueued (MDT_ERR_INVALID_ARG, the message names the field): any other size, exactly one of lo / hi,
+ * exactly one of pin_known / pin_keep, a non-finite cond_lambda, tree with another kind.  lo, hi, record, pin_known and pin_keep
+ * need no more than a float's alignment (the head reads and writes them element by element): a slice of a larger tensor will do.
+ * mdt_sample_dpm_adaptive takes no options and no pin: a pinned adaptive run is the Python host loop (sample_dpm_adaptive with
+ * extra_args = {"pin": ...}), which applies the pin in GCDenoiser.forward. */
 typedef struct mdt_sample_opts {
     int32_t size;                    /* sizeof(mdt_sample_opts): lets the struct grow                                   */
     float cond_lambda;               /* 1.0f: the unguided call; anything else: the doubled-batch guided call           */
     const float *lo, *hi;            /* (A,) device; both NULL: no bounds                                               */
     float *record;                   /* NULL or (steps, 2, B, Ta, A) device: [i][0] = x, [i][1] = denoised               */
     const struct mdt_brownian_source *tree; /* NULL, or dpmpp_sde's tree noise as in mdt_sample_sde_tree (below)         */
+    const float *pin_known, *pin_keep; /* both NULL, or both (B, Ta, A) device: D' = keep known + (1 - keep) D             */
 } mdt_sample_opts;
 mdt_status mdt_sample_opt(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
                           const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_host,
@@ -312,6 +328,17 @@ mdt_status mdt_sample_dev_opt(mdt_model *m, const float *tokens, const float *to
                               const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_dev,
                               int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out, float *ctx_out,
                               const mdt_sample_opts *opts, void *stream);
+
+/* mdt_sample_ddim / mdt_sample_ddim_dev with options: cond_lambda (1.0f: unguided; anything else: mdt_sample_ddim_guided's call)
+ * and pin_known / pin_keep (above).  lo and hi are accepted and not read -- the reference's DDIM takes a scaler and never clips;
+ * record and tree are MDT_ERR_INVALID_ARG (the message names the field): the DDIM head keeps no per-step record and draws no
+ * noise.  opts == NULL enqueues exactly what mdt_sample_ddim / mdt_sample_ddim_dev do. */
+mdt_status mdt_sample_ddim_opt(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                               const float *x_T, const float *sigmas_host, int32_t n_steps, int64_t batch, float *out,
+                               float *ctx_out, const mdt_sample_opts *opts, void *stream);
+mdt_status mdt_sample_ddim_dev_opt(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                                   const float *x_T, const float *sigmas_dev, int32_t n_steps, int64_t batch, float *out,
+                                   float *ctx_out, const mdt_sample_opts *opts, void *stream);
 
 /* sample_dpm_adaptive (eta = 0): DPM-Solver-12 / -23 with the PID step-size control of _StepControl, as ONE blocking call.
  * Every attempted step runs its 2 or 3 denoiser evaluations; the head of the last one writes both the order-k ("high") and the

@@ -98,9 +98,10 @@ BROWNIAN_MAX_PAIRS = 64  # MDT_BROWNIAN_MAX_PAIRS
 
 
 class SampleOpts(C.Structure):
-    """mdt_sample_opts (include/mdt_hip.h): bounds, record, guidance and tree noise of mdt_sample_opt / mdt_sample_dev_opt."""
+    """mdt_sample_opts (include/mdt_hip.h): bounds, record, guidance, tree noise and pinned actions of mdt_sample_opt /
+    mdt_sample_dev_opt / mdt_sample_ddim_opt / mdt_sample_ddim_dev_opt."""
     _fields_ = [("size", C.c_int32), ("cond_lambda", C.c_float), ("lo", C.c_void_p), ("hi", C.c_void_p), ("record", C.c_void_p),
-                ("tree", C.POINTER(BrownianSource))]
+                ("tree", C.POINTER(BrownianSource)), ("pin_known", C.c_void_p), ("pin_keep", C.c_void_p)]
 
 
 class SamplerPlan(C.Structure):
@@ -240,6 +241,9 @@ SYMBOLS = [
                               _I64, _VP, _VP, C.POINTER(SampleOpts), _VP]),
     ("mdt_sample_dev_opt", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), _VP, _I32, _VP, _I32, _I64, _VP,
                                   _VP, C.POINTER(SampleOpts), _VP]),
+    ("mdt_sample_ddim_opt", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(C.c_float), _I32, _I64, _VP, _VP, C.POINTER(SampleOpts),
+                                   _VP]),
+    ("mdt_sample_ddim_dev_opt", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _I64, _VP, _VP, C.POINTER(SampleOpts), _VP]),
     ("mdt_sampler_plan", _I32, [_I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, C.POINTER(SamplerPlan)]),
     ("mdt_sample_dpm_adaptive", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.c_float, C.c_float, C.POINTER(DpmAdaptiveParams), _I64,
                                        _VP, _VP, C.POINTER(DpmAdaptiveInfo), _VP]),

@@ -185,9 +185,15 @@ struct mdt_guide {
     bool on = false;
     float lam = 1.f;
 };
+// pinned actions of a sampler call (mdt_sample_opts.pin_known / pin_keep): both (M, A) device rows, both or neither.  The head
+// turns its denoised value D into keep == 0 ? D : keep == 1 ? known : D + keep (known - D) before anything else reads it
+struct mdt_head_pin {
+    const float *known = nullptr, *keep = nullptr;
+};
 // the action head on a.M rows: pl == nullptr the DDIM / denoiser head, else the plan head.  gd.on: the decoder rows of the a.M
 // state rows are a.y's [0, M) (conditional) and [M, 2M) (unconditional); F = F_u + lam (F_g - F_u); y_next (if any) receives 2M rows
-hipError_t mdt_launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, hipStream_t s);
+// pn: the call's pinned actions (the default: none)
+hipError_t mdt_launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, hipStream_t s, mdt_head_pin pn = {});
 inline hipError_t mdt_launch_head(const mdt_head_args& a, hipStream_t s) { return mdt_launch_head(a, nullptr, mdt_guide(), s); }
 // the guided sampler's 2B encoder inputs (tokens and tokens2 twice, the goal then zeros) in one launch
 hipError_t mdt_launch_guide_stage(const float* tok, const float* tok2, const float* goal, float* tok_o, float* tok2_o, float* goal_o,

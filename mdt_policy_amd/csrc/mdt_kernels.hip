@@ -1542,63 +1542,65 @@ hipError_t mdt_launch_dpm_error(const float* lo, const float* hi, const float* p
 // action head: decoder LN -> action_pred -> EDM combine -> (DDIM update) -> (next step's embedding)
 // one wave per action-token row; A <= 16
 // ------------------------------------------------------------------------------------------------
-// body in mdt_tiles.h (head_rows): each wave handles ONE row
+// body in mdt_tiles.h (head_rows): each wave handles ONE row; pn: the call's pinned actions (null pointers: none)
 template <int AMAX, int XP>
-__global__ __launch_bounds__(256) void k_head(mdt_head_args a, const float* __restrict__ zeros) {
+__global__ __launch_bounds__(256) void k_head(mdt_head_args a, mdt_head_pin pn, const float* __restrict__ zeros) {
     const int base = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (base >= a.M) return;  // wave-uniform
-    head_rows<AMAX, false, XP, 1>(a, base, threadIdx.x & 63, zeros);
+    head_rows<AMAX, false, XP, 1>(a, base, threadIdx.x & 63, zeros, nullptr, 1.f, pn);
 }
 
 // the same head with a sampler plan's update (MDT_HEAD_PLAN, mdt_tiles.h: head_rows' PLAN epilogue)
 template <int AMAX, int XP>
-__global__ __launch_bounds__(256) void k_head_plan(mdt_head_args a, mdt_head_plan pl, const float* __restrict__ zeros) {
+__global__ __launch_bounds__(256) void k_head_plan(mdt_head_args a, mdt_head_plan pl, mdt_head_pin pn,
+                                                   const float* __restrict__ zeros) {
     const int base = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (base >= a.M) return;  // wave-uniform
-    head_rows<AMAX, false, XP, 1, true>(a, base, threadIdx.x & 63, zeros, &pl);
+    head_rows<AMAX, false, XP, 1, true>(a, base, threadIdx.x & 63, zeros, &pl, 1.f, pn);
 }
 
 // classifier-free guidance (mdt_tiles.h: head_rows GUIDE): a.M rows of state, a.y holds 2 a.M rows -- conditional [0, M),
 // unconditional [M, 2M) -- and the next input's embedding goes to both halves of a.y_next.  One wave per state row.
 template <int AMAX, int XP>
-__global__ __launch_bounds__(256) void k_head_guided(mdt_head_args a, float lam, const float* __restrict__ zeros) {
+__global__ __launch_bounds__(256) void k_head_guided(mdt_head_args a, mdt_head_pin pn, float lam, const float* __restrict__ zeros) {
     const int base = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (base >= a.M) return;  // wave-uniform
-    head_rows<AMAX, false, XP, 2, false, true>(a, base, threadIdx.x & 63, zeros, nullptr, lam);
+    head_rows<AMAX, false, XP, 2, false, true>(a, base, threadIdx.x & 63, zeros, nullptr, lam, pn);
 }
 
 template <int AMAX, int XP>
-__global__ __launch_bounds__(256) void k_head_plan_guided(mdt_head_args a, mdt_head_plan pl, float lam,
+__global__ __launch_bounds__(256) void k_head_plan_guided(mdt_head_args a, mdt_head_plan pl, mdt_head_pin pn, float lam,
                                                           const float* __restrict__ zeros) {
     const int base = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (base >= a.M) return;  // wave-uniform
-    head_rows<AMAX, false, XP, 2, true, true>(a, base, threadIdx.x & 63, zeros, &pl, lam);
+    head_rows<AMAX, false, XP, 2, true, true>(a, base, threadIdx.x & 63, zeros, &pl, lam, pn);
 }
 
 // the kernel of a head launch: pl == nullptr the DDIM / denoiser head, else the plan head; gd.on the guided twin of either
 template <int AMAX, int XP>
-static void launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, int grid, hipStream_t s) {
-    if (gd.on && pl) hipLaunchKernelGGL((k_head_plan_guided<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, *pl, gd.lam, g_zeros);
-    else if (gd.on) hipLaunchKernelGGL((k_head_guided<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, gd.lam, g_zeros);
-    else if (pl) hipLaunchKernelGGL((k_head_plan<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, *pl, g_zeros);
-    else hipLaunchKernelGGL((k_head<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, g_zeros);
+static void launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, mdt_head_pin pn, int grid, hipStream_t s) {
+    if (gd.on && pl) hipLaunchKernelGGL((k_head_plan_guided<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, *pl, pn, gd.lam, g_zeros);
+    else if (gd.on) hipLaunchKernelGGL((k_head_guided<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, pn, gd.lam, g_zeros);
+    else if (pl) hipLaunchKernelGGL((k_head_plan<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, *pl, pn, g_zeros);
+    else hipLaunchKernelGGL((k_head<AMAX, XP>), dim3(grid), dim3(256), 0, s, a, pn, g_zeros);
 }
 
-hipError_t mdt_launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, hipStream_t s) {
+hipError_t mdt_launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, hipStream_t s, mdt_head_pin pn) {
+    if ((pn.known == nullptr) != (pn.keep == nullptr)) return hipErrorInvalidValue;
     hipError_t e = ensure_zeros();
     if (e != hipSuccess) return e;
     const int grid = (a.M + 3) / 4;  // 4 waves x 1 row per workgroup
     if (a.y_parts > 1) {  // rows = the sum of a fused MLP's slabs
         if (a.A > 8 || a.y_parts > 4) return hipErrorInvalidValue;
         switch (a.y_parts) {
-            case 2: launch_head<8, 2>(a, pl, gd, grid, s); break;
-            case 3: launch_head<8, 3>(a, pl, gd, grid, s); break;
-            default: launch_head<8, 4>(a, pl, gd, grid, s); break;
+            case 2: launch_head<8, 2>(a, pl, gd, pn, grid, s); break;
+            case 3: launch_head<8, 3>(a, pl, gd, pn, grid, s); break;
+            default: launch_head<8, 4>(a, pl, gd, pn, grid, s); break;
         }
     } else if (a.A <= 8) {
-        launch_head<8, 1>(a, pl, gd, grid, s);
+        launch_head<8, 1>(a, pl, gd, pn, grid, s);
     } else {
-        launch_head<16, 1>(a, pl, gd, grid, s);
+        launch_head<16, 1>(a, pl, gd, pn, grid, s);
     }
     return hipGetLastError();
 }

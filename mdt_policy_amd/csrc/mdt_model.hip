@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1101,11 +1102,11 @@ static mdt_head_args head_args(mdt_model* m, const float* y, int64_t B, const fl
 // combine, state update, next input's embedding).  MLP head (linear_output = 0): decoder LN -> action_pred.0 + GELU on the GEMM
 // -> action_pred.2 and the rest in the head kernel reading the hidden layer as it is; `scratch` holds rows * (D + HP) floats
 // (the slice's MLP hidden buffer is free at this point: 4 D floats per decoder row, HP <= 3 D); the next input's embedding --
-// of the DDIM state h.out or of the plan's Y' (pl->y_out) -- is its own launch then.
+// of the DDIM state h.out or of the plan's Y' (pl->y_out) -- is its own launch then.  pn: the call's pinned actions, if any.
 static mdt_status run_head(mdt_model* m, mdt_head_args h, const mdt_head_plan* pl, float* scratch, const float* sigma_next,
-                           hipStream_t s, mdt_guide gd) {
+                           hipStream_t s, mdt_guide gd, mdt_head_pin pn = {}) {
     if (m->HP == 0) {
-        LAUNCH(mdt_launch_head(h, pl, gd, s));
+        LAUNCH(mdt_launch_head(h, pl, gd, s, pn));
         return MDT_OK;
     }
     const int D = m->D, HP = m->HP;
@@ -1118,7 +1119,7 @@ static mdt_status run_head(mdt_model* m, mdt_head_args h, const mdt_head_plan* p
     LAUNCH(mdt_launch_gemm(g, s));
     float* y_next = h.y_next;
     h.y = hh; h.D = HP; h.no_ln = 1; h.y_next = nullptr;
-    LAUNCH(mdt_launch_head(h, pl, gd, s));
+    LAUNCH(mdt_launch_head(h, pl, gd, s, pn));
     const float* state = pl ? pl->y_out : h.out;
     for (int half = 0; y_next && half < (gd.on ? 2 : 1); ++half)  // the unconditional half embeds the same state
         LAUNCH(mdt_launch_action_embed(state, sigma_next, 0, m->cfg.sigma_data, m->Wa, m->ba, y_next + (int64_t)half * h.M * D, h.M,
@@ -1130,13 +1131,13 @@ static mdt_status run_head(mdt_model* m, mdt_head_args h, const mdt_head_plan* p
 // the head `h` on their rows -- summing the MLP's slabs itself when it is the one-launch head.  sigma_next (not null): the next
 // input is embedded into V.y.
 static mdt_status run_eval(mdt_model* m, const View& V, int64_t nb, const float* mod_row, int64_t mod_stride, mdt_head_args h,
-                           const mdt_head_plan* pl, const float* sigma_next, hipStream_t s, mdt_guide gd) {
+                           const mdt_head_plan* pl, const float* sigma_next, hipStream_t s, mdt_guide gd, mdt_head_pin pn = {}) {
     Stream fin;
     const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
     MDT_TRY(run_decoder_blocks(m, V, nb, mod_row, mod_stride, s, head_sums ? &fin : nullptr));
     if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
     if (sigma_next) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
-    return run_head(m, h, pl, V.hid, sigma_next, s, gd);
+    return run_head(m, h, pl, V.hid, sigma_next, s, gd, pn);
 }
 
 // Validate lam and decide whether a guided entry point runs the doubled batch: lam == 1 and a model without a goal token
@@ -1201,6 +1202,7 @@ struct SamplerArgs {
     float* out;
     float* ctx_out;
     void* stream;
+    mdt_head_pin pin = {};  // pinned actions (mdt_sample_opts.pin_known / pin_keep), both (B, Ta, A) or both null
 };
 
 // a sampler call's noise levels: in host memory (they ride in the prep kernel's arguments) or on the device (read in place)
@@ -1222,6 +1224,7 @@ struct SamplerCall {
     float* ctx_user;
     mdt_guide gd;
     hipStream_t s;
+    mdt_head_pin pin;
     mdt_status encode(mdt_model* m, const float* sigma, float* ctx) const {
         return run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, nb, sigma, 0, ctx, s);
     }
@@ -1242,7 +1245,7 @@ static mdt_status sampler_open(mdt_model* m, const SamplerArgs& a, mdt_guide gd,
     MDT_TRY(check_encode_args(m, a.tokens, a.tokens2, a.goal, a.ctx_out));
     MDT_TRY(check_loaded(m));
     *c = {a.tokens, a.tokens2, a.goal, a.modality, a.batch, gd.on ? 2 * a.batch : a.batch, a.ctx_out, a.ctx_out, gd,
-          (hipStream_t)a.stream};
+          (hipStream_t)a.stream, a.pin};
     MDT_TRY(mdt_reserve(m, c->nb));
     if (!gd.on) return MDT_OK;
     const int w1 = guide_w1(m), w2 = a.tokens2 ? guide_w2(m) : 0;
@@ -1293,7 +1296,7 @@ static mdt_status sample_ddim_impl(mdt_model* m, const SamplerArgs& a, Sched sc,
             MDT_TRY(c.encode(m, sigma, last ? c.ctx_out : nullptr));
         mdt_head_args h = head_args(m, V.y, a.batch, i == 0 ? a.x_T : m->xbuf, sigma, 0, last ? a.out : m->xbuf, MDT_HEAD_DDIM);
         h.step = m->steps + 4 * i;
-        MDT_TRY(run_eval(m, V, c.nb, cond_row(m, i), 0, h, nullptr, last ? nullptr : sigma + 4, c.s, gd));
+        MDT_TRY(run_eval(m, V, c.nb, cond_row(m, i), 0, h, nullptr, last ? nullptr : sigma + 4, c.s, gd, c.pin));
     }
     return sampler_close(m, c);
 }
@@ -1374,7 +1377,7 @@ static mdt_status run_plan_eval(mdt_model* m, const View& V, const SamplerCall& 
     pl.rec_x = rec;
     pl.rec_d = rec ? rec + pl.nel : nullptr;
     mdt_head_args h = head_args(m, V.y, c.batch, m->ybuf, &ev[e].sigma, 0, out, MDT_HEAD_PLAN);
-    return run_eval(m, V, c.nb, cond_row(m, e), 0, h, &pl, last ? nullptr : &ev[e].sigma_next, c.s, c.gd);
+    return run_eval(m, V, c.nb, cond_row(m, e), 0, h, &pl, last ? nullptr : &ev[e].sigma_next, c.s, c.gd, c.pin);
 }
 
 // The structure of sample_ddim_impl: the plan and the sigma embeddings of every evaluation (one launch), the first input, the
@@ -1493,28 +1496,68 @@ extern "C" mdt_status mdt_sample_dev_guided(mdt_model* m, const float* tokens, c
                                 stream}, kind, params, {sigmas_dev, true}, n_steps, noise, n_noise);
 }
 
+// mdt_sample_opts as a call reads it: NULL gives the defaults, `size` may be the struct's size before pin_known / pin_keep were
+// appended (they read as NULL then) or today's; the checks that need no more than the struct itself
+constexpr int32_t OPTS_SIZE_V1 = (int32_t)offsetof(mdt_sample_opts, pin_known);
+static mdt_status read_opts(const char* who, const mdt_sample_opts* opts, mdt_sample_opts* o) {
+    *o = {(int32_t)sizeof(mdt_sample_opts), 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (opts) {
+        if (opts->size != (int32_t)sizeof(mdt_sample_opts) && opts->size != OPTS_SIZE_V1)
+            return fail(MDT_ERR_INVALID_ARG, "%s: opts.size is %d, sizeof(mdt_sample_opts) is %d (%d without the pin)", who,
+                        opts->size, (int)sizeof(mdt_sample_opts), (int)OPTS_SIZE_V1);
+        memcpy(o, opts, (size_t)opts->size);
+    }
+    if (!std::isfinite(o->cond_lambda)) return fail(MDT_ERR_INVALID_ARG, "%s: opts.cond_lambda must be finite", who);
+    if ((o->lo == nullptr) != (o->hi == nullptr))
+        return fail(MDT_ERR_INVALID_ARG, "%s: opts.lo and opts.hi must both be set or both be null", who);
+    if ((o->pin_known == nullptr) != (o->pin_keep == nullptr))
+        return fail(MDT_ERR_INVALID_ARG, "%s: opts.%s is set and opts.%s is null: a pin needs both", who,
+                    o->pin_known ? "pin_known" : "pin_keep", o->pin_known ? "pin_keep" : "pin_known");
+    return MDT_OK;
+}
+
 // mdt_sample_opt / mdt_sample_dev_opt: the options checked (nothing is enqueued before sample_plan_impl's own checks pass), then
 // the call path of mdt_sample and its guided and tree-noise twins
 static mdt_status sample_opt_impl(mdt_model* m, const char* who, const float* tokens, const float* tokens2, const float* goal,
                                   int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params, Sched sc,
                                   int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, float* out, float* ctx_out,
                                   const mdt_sample_opts* opts, void* stream) {
-    mdt_sample_opts o = {(int32_t)sizeof(mdt_sample_opts), 1.f, nullptr, nullptr, nullptr, nullptr};
-    if (opts) {
-        if (opts->size != (int32_t)sizeof(mdt_sample_opts))
-            return fail(MDT_ERR_INVALID_ARG, "%s: opts.size is %d, sizeof(mdt_sample_opts) is %d", who, opts->size,
-                        (int)sizeof(mdt_sample_opts));
-        o = *opts;
-    }
-    if (!std::isfinite(o.cond_lambda)) return fail(MDT_ERR_INVALID_ARG, "%s: opts.cond_lambda must be finite", who);
-    if ((o.lo == nullptr) != (o.hi == nullptr))
-        return fail(MDT_ERR_INVALID_ARG, "%s: opts.lo and opts.hi must both be set or both be null", who);
+    mdt_sample_opts o;
+    MDT_TRY(read_opts(who, opts, &o));
     if (o.tree && kind != MDT_SAMPLER_DPMPP_SDE)
         return fail(MDT_ERR_INVALID_ARG, "%s: opts.tree is the noise of MDT_SAMPLER_DPMPP_SDE (kind %d)", who, kind);
     const bool guided = o.cond_lambda != 1.f;  // lambda == 1 is the unguided call (mdt_sample_guided gives its bits there too)
     return sample_plan_impl(m, {who, guided ? &o.cond_lambda : nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
-                                stream}, kind, params, sc, n_steps, o.tree ? nullptr : noise, o.tree ? 0 : n_noise, o.tree, o.lo, o.hi,
-                            o.record);
+                                stream, {o.pin_known, o.pin_keep}}, kind, params, sc, n_steps, o.tree ? nullptr : noise,
+                            o.tree ? 0 : n_noise, o.tree, o.lo, o.hi, o.record);
+}
+
+// mdt_sample_ddim_opt / mdt_sample_ddim_dev_opt: cond_lambda and the pin; lo / hi are accepted and not read (the reference's DDIM
+// never clips), record and tree are refused
+static mdt_status sample_ddim_opt_impl(mdt_model* m, const char* who, const float* tokens, const float* tokens2, const float* goal,
+                                       int32_t modality, const float* x_T, Sched sc, int32_t n_steps, int64_t batch, float* out,
+                                       float* ctx_out, const mdt_sample_opts* opts, void* stream) {
+    mdt_sample_opts o;
+    MDT_TRY(read_opts(who, opts, &o));
+    if (o.record) return fail(MDT_ERR_INVALID_ARG, "%s: opts.record: the DDIM head keeps no per-step record", who);
+    if (o.tree) return fail(MDT_ERR_INVALID_ARG, "%s: opts.tree is the noise of MDT_SAMPLER_DPMPP_SDE; DDIM draws none", who);
+    const bool guided = o.cond_lambda != 1.f;
+    return sample_ddim_impl(m, {who, guided ? &o.cond_lambda : nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
+                                stream, {o.pin_known, o.pin_keep}}, sc, n_steps);
+}
+
+extern "C" mdt_status mdt_sample_ddim_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                          int32_t modality, const float* x_T, const float* sigmas_host, int32_t n_steps,
+                                          int64_t batch, float* out, float* ctx_out, const mdt_sample_opts* opts, void* stream) {
+    return sample_ddim_opt_impl(m, "mdt_sample_ddim_opt", tokens, tokens2, goal, modality, x_T, {sigmas_host, false}, n_steps, batch,
+                                out, ctx_out, opts, stream);
+}
+
+extern "C" mdt_status mdt_sample_ddim_dev_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                              int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
+                                              int64_t batch, float* out, float* ctx_out, const mdt_sample_opts* opts, void* stream) {
+    return sample_ddim_opt_impl(m, "mdt_sample_ddim_dev_opt", tokens, tokens2, goal, modality, x_T, {sigmas_dev, true}, n_steps,
+                                batch, out, ctx_out, opts, stream);
 }
 
 extern "C" mdt_status mdt_sample_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,

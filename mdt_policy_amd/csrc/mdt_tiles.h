@@ -1411,9 +1411,15 @@ __device__ __forceinline__ float edm_c_in(float sigma, float sd) { return 1.0f /
 // GUIDE (classifier-free guidance, RW = 2): a.M counts the rows of STATE; the wave reads the conditional row base of a.y and the
 // unconditional row base + a.M, combines their action_pred outputs F = F_u + lam (F_g - F_u) per element (fp32, before the EDM
 // output scaling), runs the epilogue on state row base and writes the next input's embedding to y_next rows base and base + a.M.
+// pn (chunk inpainting, mdt_sample_opts.pin_known / pin_keep; kernel arguments: the null test is scalar, one per wave): known and
+// keep are (M, A) rows.  Lane c requests element c of its row with the other operands -- two registers per row, not 2 AMAX --
+// and each element's pair reaches every lane through a readlane where it is used: the denoised value becomes
+// D' = keep == 0 ? D : keep == 1 ? known : D + keep (known - D) right after the EDM combine (the guided head: after the lambda
+// combination), so the DDIM update, R_D / R_DD, the record and the history push all see D'.  Without a pin no load, compare or
+// store is added.
 template <int AMAX, bool COH, int XP = 1, int RW = 2, bool PLAN = false, bool GUIDE = false>
 __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int lane, const float* __restrict__ zeros,
-                                          const mdt_head_plan* pl = nullptr, float lam = 1.f) {
+                                          const mdt_head_plan* pl = nullptr, float lam = 1.f, mdt_head_pin pn = {}) {
     static_assert(!GUIDE || RW == 2, "the guided head reads one conditional and one unconditional row per wave");
     constexpr int RS = GUIDE ? 1 : RW;  // rows of state the wave updates
     const int n4 = a.D >> 2;
@@ -1435,6 +1441,7 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
     // ---- every global operand is requested up front (clamped addresses, no load behind a branch) ----
     f32x4 v[RW][2], w[2], bb[2], wp[AMAX][2];
     float xin[RW][AMAX], bpv[AMAX], sigma[RW];
+    float pkn[RS], pkp[RS];  // lane c: known and keep of element c of the row
     const float* lnb = a.ln_b != nullptr ? a.ln_b : zeros;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
@@ -1460,6 +1467,16 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
 #pragma unroll
         for (int r = 0; r < RS; ++r) xin[r][c] = LX.ld1(row[r] * a.A + ce);
         bpv[c] = a.bp[ce];
+    }
+#pragma unroll
+    for (int r = 0; r < RS; ++r) { pkn[r] = 0.f; pkp[r] = 0.f; }
+    if (pn.known != nullptr) {
+#pragma unroll
+        for (int r = 0; r < RS; ++r) {
+            const int64_t k = row[r] * a.A + min(lane, a.A - 1);
+            pkn[r] = pn.known[k];
+            pkp[r] = pn.keep[k];
+        }
     }
 #pragma unroll
     for (int r = 0; r < RS; ++r) sigma[r] = a.sigma[(row[r] / a.rows_per_sample) * a.sigma_stride];
@@ -1553,7 +1570,12 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
             const float F = GUIDE ? res[r * AMAX + c] : res[r * AMAX + c] + bpv[c];
             float o = F;
             if (a.mode != MDT_HEAD_RAW) {
-                const float den = F * c_out + xin[r][c] * c_skip;
+                float den = F * c_out + xin[r][c] * c_skip;
+                if (pn.known != nullptr) {  // selects at both ends: no 0 * inf, no sign-of-zero change
+                    const float kn = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pkn[r]), c));
+                    const float kp = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pkp[r]), c));
+                    den = kp == 0.f ? den : (kp == 1.f ? kn : den + kp * (kn - den));
+                }
                 o = a.mode == MDT_HEAD_DDIM ? ratio * xin[r][c] + coef * den : den;
             }
             res[r * AMAX + c] = o;

@@ -25,7 +25,7 @@ import torch
 
 from . import utils
 from ... import _lib
-from ..networks._engine import guidance
+from ..networks._engine import rollout_controls
 from .graphed import GraphedDDIM, GraphedSampler
 from .score_wrappers import GCDenoiser
 
@@ -182,16 +182,19 @@ def _graph_wanted(model, state, action, goal, sigmas, tag=None) -> bool:
     return seen.get(key, 0) > _GRAPH_AUTO_AFTER
 
 
-def _graph_route(model, cache, tag, key, state, action, goal, sigmas, make, what, noise=None, bounds=None):
+def _graph_route(model, cache, tag, key, state, action, goal, sigmas, make, what, noise=None, bounds=None, pin=None):
     """A native sampler call replayed as a HIP graph, or None: the eager call runs then.  The rule is _graph_wanted's, ``tag``
     joining the call's graph key (None: unguided DDIM).  The graphs live on the model in the list ``cache`` (at most four) and
     are found by GraphedDDIM.matches with ``key``; ``make(sigmas)`` captures a new one.  In auto mode a capture that fails
     (another thread allocating / synchronising while torch's global capture mode is on, ...) must not break a rollout the eager
     path would have served: that call shape stays eager, with a warning naming ``what``.  MDT_HIP_GRAPH=1 re-raises.
-    ``bounds``: the call's (lo, hi) action bounds (a graph captured with bounds copies them in before it replays)."""
+    ``bounds``: the call's (lo, hi) action bounds (a graph captured with bounds copies them in before it replays); ``pin``: its
+    (known, keep) pinned actions, handled the same way."""
     if not _graph_wanted(model, state, action, goal, sigmas, tag=tag):
         return None
     kw = {} if bounds is None else {"bounds": bounds}
+    if pin is not None:
+        kw["pin"] = pin
     try:
         graphs = model.__dict__.setdefault(cache, [])
         for gsamp in graphs:
@@ -228,7 +231,7 @@ def _scaler_native(scaler) -> bool:
 
 
 def _native_ok(model, sigmas, scaler, callback, extra_args) -> bool:
-    if not isinstance(model, GCDenoiser) or callback is not None or not guidance(**(extra_args or {}))[0]:
+    if not isinstance(model, GCDenoiser) or callback is not None or not rollout_controls(**(extra_args or {}))[0]:
         return False
     if not _scaler_native(scaler):
         return False
@@ -271,9 +274,11 @@ def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, e
     (dpmpp_sde, in place of ``noise``): (seeds, tol, lo, hi) of the Brownian tree the call draws from; (tol, lo, hi) join the
     graph key and the seeds are the graph's per-call input.  ``scaler``: None or the sampler's, which _native_ok admitted -- its
     bounds ride in the call; a graph holds them in static buffers refreshed before every replay, so only their presence joins the
-    graph key."""
+    graph key.  A pin among the ``extra_args`` (an ActionPin) rides in the call the same way."""
     bounds = None if scaler is None else scaler.clip_bounds(action.device)
-    lam = guidance(**(extra_args or {}))[1]
+    _, lam, pin = rollout_controls(**(extra_args or {}))
+    if pin is not None:
+        pin = pin.on(action.device, action.shape)
     if lam is not None:
         params = dict(params, cond_lambda=lam)
     tag = (kind, tuple(sorted(params.items())))
@@ -288,13 +293,18 @@ def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, e
     if bounds is not None:
         tag += ("bounds",)
         key += ("bounds",)
+    if pin is not None:
+        tag += ("pin",)
+        key += ("pin",)
     out = _graph_route(model, "_graphed_native", tag, key, state, action, goal, sigmas,
                        lambda sig: GraphedSampler(model, kind, params, state, action, goal, sig, noise, n_steps, tree=meta,
-                                                  bounds=bounds),
-                       f"sample_{kind}", noise=noise, bounds=bounds)
+                                                  bounds=bounds, pin=pin),
+                       f"sample_{kind}", noise=noise, bounds=bounds, pin=pin)
     if out is not None:
         return out
     kw = {} if bounds is None else {"bounds": bounds}
+    if pin is not None:
+        kw["pin"] = pin
     if tree is not None:
         return model.sample_native(kind, state, action, goal, sigmas, tree=tree, **kw, **params)
     return model.sample_native(kind, state, action, goal, sigmas, noise=noise, n_steps=n_steps, **kw, **params)
@@ -315,15 +325,20 @@ def sample_ddim(model, state, action, goal, sigmas, scaler=None, extra_args=None
     """DPM-Solver-1 / DDIM (reference gc_sampling.py:922-951):
     x <- (sigma_{i+1}/sigma_i) x - expm1(-(t_{i+1} - t_i)) D(x; sigma_i),  t = -ln sigma.
     `scaler` is accepted and never read, exactly as in the reference (its DDIM has no `clip_output` call), so a harness run
-    with `use_scaler` (mdtv_agent.py:606-614) keeps the fused native loop; only `callback` / `extra_args` need the step loop."""
+    with `use_scaler` (mdtv_agent.py:606-614) keeps the fused native loop; only `callback` / `extra_args` need the step loop
+    (a guidance weight and pinned actions, ``extra_args={"cond_lambda": lam, "pin": ActionPin(...)}``, ride in the native call)."""
     extra_args = {} if extra_args is None else extra_args
-    native, lam = guidance(**extra_args)
+    native, lam, pin = rollout_controls(**extra_args)
     if isinstance(model, GCDenoiser) and callback is None and native:
-        # guidance: the guided native call, its graphs keyed by the weight too
+        # guidance: the guided native call, its graphs keyed by the weight too; a pin: by its presence (the values are copied in)
         tag, kw = (None, {}) if lam is None else (("ddim_guided", lam), {"cond_lambda": lam})
-        out = _graph_route(model, "_graphed_samplers", tag, lam, state, action, goal, sigmas,
-                           lambda sig: GraphedDDIM(model, state, action, goal, sig, cond_lambda=lam),
-                           "sample_ddim" if lam is None else "guided sample_ddim")
+        key = lam
+        if pin is not None:
+            pin = pin.on(action.device, action.shape)
+            tag, key, kw = ("ddim_pin", lam), (lam, "pin"), dict(kw, pin=pin)
+        out = _graph_route(model, "_graphed_samplers", tag, key, state, action, goal, sigmas,
+                           lambda sig: GraphedDDIM(model, state, action, goal, sig, cond_lambda=lam, pin=pin),
+                           "sample_ddim" if lam is None else "guided sample_ddim", pin=pin)
         if out is not None:
             return out
         return model.sample_ddim(state, action, goal, sigmas, **kw)  # fused native loop
@@ -835,7 +850,7 @@ def sample_dpm_fast(model, state, action, goal, sigma_min, sigma_max, n, scaler=
     if eta and not t_end > t_start:
         raise ValueError('eta must be 0 for reverse sampling')
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
-    if (isinstance(model, GCDenoiser) and callback is None and guidance(**(extra_args or {}))[0] and _scaler_native(scaler)
+    if (isinstance(model, GCDenoiser) and callback is None and rollout_controls(**(extra_args or {}))[0] and _scaler_native(scaler)
             and 1 <= n <= _lib.SAMPLER_MAX_EVALS):  # (the solver never reads `scaler`, here as in the reference: no bounds to pass)
         return _run_native("dpm_fast", model, state, action, goal, [float(sigma_max), float(sigma_min)],
                            _dpm_fast_noise(action, t_start, t_end, n, eta, noise_sampler), n_steps=n, eta=eta, s_noise=s_noise,
@@ -894,7 +909,8 @@ def sample_dpm_adaptive(model, state, action, goal, sigma_min, sigma_max, extra_
     t_end = _t(torch.tensor(float(sigma_min))).to(torch.float32)
     if eta and not bool(t_end > t_start):
         raise ValueError('eta must be 0 for reverse sampling')
-    native, lam = guidance(**(extra_args or {}))
+    native, lam, pin = rollout_controls(**(extra_args or {}))
+    native = native and pin is None  # mdt_sample_dpm_adaptive takes no pin: the host loop applies it through forward
     if (isinstance(model, GCDenoiser) and callback is None and native and not eta and action.device.type == "cuda"
             and not torch.cuda.is_current_stream_capturing()):
         kw = {} if lam is None else {"cond_lambda": lam}  # guidance: mdt_sample_dpm_adaptive_guided

@@ -23,9 +23,13 @@ import torch
 
 class GraphedDDIM:
     def __init__(self, model, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas: torch.Tensor,
-                 cond_lambda: Optional[float] = None):
+                 cond_lambda: Optional[float] = None, pin: Optional[tuple] = None):
         if x_T.device.type != "cuda":
             raise RuntimeError("GraphedDDIM needs the model and its inputs on a ROCm GPU")
+        # pin: (known, keep) of a call captured with pinned actions.  Like the bounds of GraphedSampler the graph reads them from
+        # static buffers that every call fills with ITS pin before the replay: only their presence is part of the graph (_call_key)
+        if pin is not None:
+            self._pin = tuple(t.detach().to(x_T.device, torch.float32).reshape(x_T.shape).clone() for t in pin)
         self.model = model
         self.cond_lambda = cond_lambda  # classifier-free guidance weight of the captured call (None: unguided)
         self.device = x_T.device
@@ -45,18 +49,22 @@ class GraphedDDIM:
 
     _noise = None  # the captured noise rows (GraphedSampler)
     _lo = _hi = None  # the static action bounds of a call captured with bounds (GraphedSampler)
+    _pin = None  # the static (known, keep) of a call captured with pinned actions
 
     def _call_key(self):
         """What besides the shapes a call must share with the captured one to replay it (matches)."""
-        return self.cond_lambda
+        return self.cond_lambda if self._pin is None else (self.cond_lambda, "pin")
 
     def _run(self):
+        kw = {} if self._pin is None else {"pin": self._pin}
         if self.cond_lambda is not None:
-            return self.model.sample_ddim(self._static_state, self._x, self._goal, self._sig, cond_lambda=self.cond_lambda)
-        return self.model.sample_ddim(self._static_state, self._x, self._goal, self._sig)
+            kw["cond_lambda"] = self.cond_lambda
+        return self.model.sample_ddim(self._static_state, self._x, self._goal, self._sig, **kw)
 
-    def _extra_inputs(self, noise, bounds=None):
-        return [], []
+    def _extra_inputs(self, noise, bounds=None, pin=None):
+        if (pin is None) != (self._pin is None):
+            raise ValueError("a graph captured with pinned actions replays calls with a pin, and only those")
+        return ([], []) if pin is None else (list(self._pin), [pin[0], pin[1]])
 
     def _capture(self) -> None:
         model = self.model
@@ -101,7 +109,7 @@ class GraphedDDIM:
 
     @torch.no_grad()
     def __call__(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas=None, fresh: bool = True,
-                 noise: Optional[torch.Tensor] = None, bounds=None) -> torch.Tensor:
+                 noise: Optional[torch.Tensor] = None, bounds=None, pin=None) -> torch.Tensor:
         """Same result as ``model.sample_ddim(state, x_T, goal, sigmas)``, including ``inner_model.latent_encoder_emb``: both are
         fresh tensors the next call does not touch.  ``fresh=False`` hands out the graph's own static buffers instead (valid
         until the next call; one copy launch less)."""
@@ -121,7 +129,7 @@ class GraphedDDIM:
             if torch.is_tensor(v):
                 dst.append(v); src.append(state[k])
         dst += [self._x, self._goal]; src += [x_T, goal]
-        d2, s2 = self._extra_inputs(noise, bounds)
+        d2, s2 = self._extra_inputs(noise, bounds, pin)
         dst += d2; src += s2
         if sigmas is not None:
             # n + 1 floats: never skipped on identity -- a caller may rewrite its schedule tensor in place (same object, new values).
@@ -163,7 +171,7 @@ class GraphedSampler(GraphedDDIM):
 
     def __init__(self, model, kind: str, params: dict, state: dict, x_T: torch.Tensor, goal: torch.Tensor,
                  sigmas: torch.Tensor, noise: Optional[torch.Tensor], n_steps: Optional[int] = None, tree: Optional[tuple] = None,
-                 bounds: Optional[tuple] = None):
+                 bounds: Optional[tuple] = None, pin: Optional[tuple] = None):
         # bounds: (lo, hi) action bounds of the captured call (GCDenoiser.sample_native's ``bounds``).  The graph reads them from
         # static (A,) buffers that every call fills with ITS bounds before the replay: the values are not part of the graph, only
         # their presence is (_call_key)
@@ -174,21 +182,23 @@ class GraphedSampler(GraphedDDIM):
         # seeds are then the static input `noise` -- copied in per call, so that a replay walks the new call's trees
         self.tree = None if tree is None else tuple(float(v) for v in tree)
         self._noise = None if noise is None else noise.detach().clone()
-        super().__init__(model, state, x_T, goal, sigmas)
+        super().__init__(model, state, x_T, goal, sigmas, pin=pin)
 
     def _call_key(self):
         return ((self.kind, self.params, self.n_steps) + (() if self.tree is None else (("tree",) + self.tree,))
-                + (() if self._lo is None else ("bounds",)))
+                + (() if self._lo is None else ("bounds",)) + (() if self._pin is None else ("pin",)))
 
     def _run(self):
         kw = {} if self._lo is None else {"bounds": (self._lo, self._hi)}
+        if self._pin is not None:
+            kw["pin"] = self._pin
         if self.tree is not None:
             return self.model.sample_native(self.kind, self._static_state, self._x, self._goal, self._sig,
                                             tree=(self._noise,) + self.tree, **kw, **self.params)
         return self.model.sample_native(self.kind, self._static_state, self._x, self._goal, self._sig, noise=self._noise,
                                         n_steps=self.n_steps, **kw, **self.params)
 
-    def _extra_inputs(self, noise, bounds=None):
+    def _extra_inputs(self, noise, bounds=None, pin=None):
         if (noise is None) != (self._noise is None) or (noise is not None and noise.shape != self._noise.shape):
             raise ValueError("GraphedSampler: the noise rows must have the captured shape")
         if (bounds is None) != (self._lo is None):
@@ -196,4 +206,5 @@ class GraphedSampler(GraphedDDIM):
         dst, src = ([], []) if noise is None else ([self._noise], [noise])
         if bounds is not None:
             dst += [self._lo, self._hi]; src += [bounds[0], bounds[1]]
-        return dst, src
+        d2, s2 = super()._extra_inputs(noise, bounds, pin)
+        return dst + d2, src + s2

@@ -124,11 +124,15 @@ class GCDenoiser(nn.Module):
                  if ("inner_model." + n) in eng._grad_layout and not (unused and n.startswith(unused))]
         return tok, tok2, g, B, [n for n, _ in named], [p for _, p in named]
 
-    def forward(self, state, action, goal, sigma, cond_lambda=1.0, **kwargs):
+    def forward(self, state, action, goal, sigma, cond_lambda=1.0, pin=None, **kwargs):
         """D(x; sigma) = F(x*c_in, sigma)*c_out + x*c_skip (reference score_wrappers.py:65-80).
 
         ``cond_lambda`` != 1: classifier-free guidance, D_lambda = D(x; sigma, 0) + lambda (D(x; sigma, g) - D(x; sigma, 0)) from the
-        conditional and the ``uncond`` evaluation (the latter first, so latent_encoder_emb ends as the conditional context)."""
+        conditional and the ``uncond`` evaluation (the latter first, so latent_encoder_emb ends as the conditional context).
+        ``pin`` (an ActionPin, utils/action_pin.py): pinned actions, D' = keep * known + (1 - keep) * D, applied after the
+        guidance -- what the native samplers compute in their action head."""
+        if pin is not None:
+            return pin.apply(self.forward(state, action, goal, sigma, cond_lambda=cond_lambda, **kwargs))
         lam = float(cond_lambda)
         if lam != 1.0:
             if not math.isfinite(lam):
@@ -298,7 +302,7 @@ class GCDenoiser(nn.Module):
 
     @torch.no_grad()
     def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, cond_lambda=None, tree=None, bounds=None,
-                      record=False, **params):
+                      record=False, pin=None, **params):
         """One of the other samplers (``kind``: 'euler', 'heun', 'dpmpp_2m', ... -- the gc_sampling function name without
         'sample_') as one enqueue on the current stream (mdt_sample).  ``noise``: None or (n_noise, B, Ta, A) in the Python loop's
         draw order -- raw randn draws (euler / heun / dpm_2 / the ancestral samplers) or the noise_sampler values (dpmpp_2s_ancestral,
@@ -313,10 +317,15 @@ class GCDenoiser(nn.Module):
         every step; dpmpp_sde: not after the last; dpmpp_2m and dpm_fast: never -- include/mdt_hip.h mdt_sample_opts).
         ``record=True``: returns (actions, rec) with rec = {'x', 'denoised': (n_steps, B, Ta, A), 'sigma', 'sigma_hat':
         (n_steps,)}, what a ``callback`` of the loop sees per step (dpm_fast: per solver step); gc_sampling.replay_callback feeds
-        it to one.  The actions are those of the call without ``record``, bit for bit."""
+        it to one.  The actions are those of the call without ``record``, bit for bit.
+        ``pin``: an ``ActionPin`` (utils/action_pin.py) or its (known, keep) pair of (B, Ta, A) device tensors -- pinned actions:
+        every evaluation's denoised value becomes keep * known + (1 - keep) * D inside the action head (mdt_sample_opts.pin_known /
+        pin_keep), for every kind, guided or not, with bounds, record and tree noise as without it."""
         from ... import _lib
         im = self.inner_model
-        if bounds is not None or record:
+        if pin is not None and callable(getattr(pin, "on", None)):
+            pin = pin.on(action.device, action.shape)
+        if bounds is not None or record or pin is not None:
             if bounds is not None:
                 pair = bounds.clip_bounds(action.device) if callable(getattr(bounds, "clip_bounds", None)) else bounds
                 bounds = tuple(torch.as_tensor(b, dtype=torch.float32).to(action.device) for b in pair)
@@ -326,7 +335,7 @@ class GCDenoiser(nn.Module):
                 tree = (tuple(tree) + (0., 0.))[:4]
             out, ctx, rec = self._engine(state=state).sample_native_opt(
                 _lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action, im._goals(goal, False), sigmas, noise,
-                n_steps=n_steps, cond_lambda=cond_lambda, tree=tree, bounds=bounds, record=record)
+                n_steps=n_steps, cond_lambda=cond_lambda, tree=tree, bounds=bounds, record=record, pin=pin)
             im.latent_encoder_emb = ctx
             if not record:
                 return out
@@ -360,14 +369,19 @@ class GCDenoiser(nn.Module):
         return out, info
 
     @torch.no_grad()
-    def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None, bounds=None, record=False):
+    def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None, bounds=None, record=False, pin=None):
         """Whole DDIM loop (reference gc_sampling.py:922-951) as one enqueue on the current stream.  ``cond_lambda``:
         classifier-free guidance weight (None or 1: the unguided call; mdt_sample_ddim_guided).  ``bounds`` is accepted and not
-        read, as the reference's DDIM accepts a scaler and never clips; the DDIM head keeps no per-step record."""
+        read, as the reference's DDIM accepts a scaler and never clips; the DDIM head keeps no per-step record.  ``pin``: an
+        ``ActionPin`` or its (known, keep) pair of (B, Ta, A) device tensors -- pinned actions (mdt_sample_ddim_opt): every step's
+        denoised value becomes keep * known + (1 - keep) * D inside the action head."""
         if record:
             raise NotImplementedError("sample_ddim keeps no per-step record; run the host loop with a callback")
         im = self.inner_model
+        kw = {}
+        if pin is not None:
+            kw["pin"] = pin.on(action.device, action.shape) if callable(getattr(pin, "on", None)) else pin
         out, ctx = self._engine(state=state).sample_ddim(state, action, im._goals(goal, False), sigmas,
-                                                         cond_lambda=cond_lambda)
+                                                         cond_lambda=cond_lambda, **kw)
         im.latent_encoder_emb = ctx
         return out

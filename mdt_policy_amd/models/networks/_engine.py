@@ -46,11 +46,24 @@ def guidance(cond_lambda=None, **other):
     return True, (None if lam == 1.0 else lam)
 
 
+def rollout_controls(cond_lambda=None, pin=None, **other):
+    """``guidance`` for a sampler's ``extra_args`` that may also carry pinned actions (``pin``: an ActionPin,
+    utils/action_pin.py): ``rollout_controls(**extra_args)`` returns (native, lam, pin).  The weight and the pin both ride inside
+    the native call; any further key keeps the host loop, which hands all of them to GCDenoiser.forward.  ``extra_args`` reach
+    ``forward`` too, which applies the pin through ``ActionPin.apply``: a bare (known, keep) pair (what ``sample_native(pin=)``
+    also takes) is a TypeError here, before anything is enqueued."""
+    if pin is not None and not (callable(getattr(pin, "on", None)) and callable(getattr(pin, "apply", None))):
+        raise TypeError(f"extra_args['pin'] must be an ActionPin (ActionPin(known, keep)), got {type(pin).__name__}")
+    native, lam = guidance(cond_lambda, **other)
+    return native, lam, pin
+
+
 # the C entry points of each sampler family as [device schedule][guided]
 _SAMPLER_ENTRIES = {
     "ddim": (("mdt_sample_ddim", "mdt_sample_ddim_guided"), ("mdt_sample_ddim_dev", "mdt_sample_ddim_dev_guided")),
     "plan": (("mdt_sample", "mdt_sample_guided"), ("mdt_sample_dev", "mdt_sample_dev_guided")),
     "plan_opt": (("mdt_sample_opt",), ("mdt_sample_dev_opt",)),  # the guidance weight rides in mdt_sample_opts
+    "ddim_opt": (("mdt_sample_ddim_opt",), ("mdt_sample_ddim_dev_opt",)),
     "dpm_adaptive": (("mdt_sample_dpm_adaptive", "mdt_sample_dpm_adaptive_guided"),),
     "sde_tree": (("mdt_sample_sde_tree", "mdt_sample_sde_tree_guided"), ("mdt_sample_sde_tree_dev", "mdt_sample_sde_tree_dev_guided")),
 }
@@ -309,12 +322,35 @@ class HipEngine:
                   *(() if lam is None else (lam,)), *tail, self._stream())
         return out, ctx
 
-    def sample_ddim(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, cond_lambda: Optional[float] = None):
+    def _pin(self, pin, B: int):
+        """A pin's (known, keep) as the C ABI takes them: contiguous fp32 (B, Ta, A) on the device (a float's alignment will do)."""
+        out = []
+        for t in pin:
+            if t.device != self.device:
+                raise RuntimeError(f"pin tensor on {t.device}, model on {self.device}")
+            if tuple(t.shape) != (B, self.Ta, self.A):
+                raise ValueError(f"pin tensors must be ({B},{self.Ta},{self.A}), got {tuple(t.shape)}")
+            t = t.detach()
+            out.append(t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous())
+        return tuple(out)
+
+    def sample_ddim(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, cond_lambda: Optional[float] = None,
+                    pin=None):
         """Fused sampler call.  ``sigmas`` may live on the host (gc_sampling's default) or on the model's device --
         the agent builds its schedule there (mdtv_agent.py:660-667); a device schedule is consumed in place
         (mdt_sample_ddim_dev): no copy to the host, no synchronisation.  ``cond_lambda`` (not None or 1): classifier-free
-        guidance, mdt_sample_ddim_guided / mdt_sample_ddim_dev_guided."""
-        return self._sample("ddim", state, x_T, goal, cond_lambda, sigmas=sigmas)
+        guidance, mdt_sample_ddim_guided / mdt_sample_ddim_dev_guided.  ``pin``: None or (known, keep), fp32 (B, Ta, A) tensors on
+        the device, read when the kernels run -- pinned actions, mdt_sample_ddim_opt / mdt_sample_ddim_dev_opt; without one the
+        call is the one it was."""
+        if pin is None:
+            return self._sample("ddim", state, x_T, goal, cond_lambda, sigmas=sigmas)
+        lam = guidance(cond_lambda)[1]
+        known, keep = self._pin(pin, x_T.shape[0])
+        opts = _lib.SampleOpts(C.sizeof(_lib.SampleOpts), 1.0 if lam is None else lam, None, None, None, None, _ptr(known),
+                               _ptr(keep))
+        out = self._sample("ddim_opt", state, x_T, goal, None, sigmas=sigmas, tail=(C.byref(opts),))
+        self._keep = self._keep + (known, keep)
+        return out
 
     def sample_native(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
                       noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cond_lambda: Optional[float] = None):
@@ -326,14 +362,18 @@ class HipEngine:
 
     def sample_native_opt(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
                           noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None,
-                          cond_lambda: Optional[float] = None, tree=None, bounds=None, record: bool = False):
+                          cond_lambda: Optional[float] = None, tree=None, bounds=None, record: bool = False, pin=None):
         """sample_native / sample_sde_tree with action bounds and / or a per-step record (mdt_sample_opt / mdt_sample_dev_opt):
         ``bounds`` None or (lo, hi), fp32 (A,) tensors on the device, read when the kernels run (a captured call reads what they
         hold at replay); ``record``: the call also returns the (steps, 2, B, Ta, A) record -- [i][0] the input of step i's first
-        evaluation, [i][1] its denoised output; ``tree``: None or (seeds, tol, lo, hi) as in sample_sde_tree.  Returns
-        (out, ctx, record or None).  Capture-safe like sample_native."""
+        evaluation, [i][1] its denoised output; ``tree``: None or (seeds, tol, lo, hi) as in sample_sde_tree; ``pin``: None or
+        (known, keep), fp32 (B, Ta, A) tensors on the device, read when the kernels run -- the denoised value of every evaluation
+        becomes keep * known + (1 - keep) * D (the record then holds that).  Returns (out, ctx, record or None).  Capture-safe
+        like sample_native."""
         lam = guidance(cond_lambda)[1]
-        lo = hi = rec = src = None
+        lo = hi = rec = src = known = keep = None
+        if pin is not None:
+            known, keep = self._pin(pin, x_T.shape[0])
         if bounds is not None:
             lo, hi = (self._in(b, (self.A,)) for b in bounds)
         if tree is not None:
@@ -345,10 +385,10 @@ class HipEngine:
             steps = len(sigmas) - 1 if n_steps is None else int(n_steps) // 3 + 1  # n_steps: dpm_fast's evaluation count
             rec = torch.empty((steps, 2, x_T.shape[0], self.Ta, self.A), device=self.device, dtype=torch.float32)
         opts = _lib.SampleOpts(C.sizeof(_lib.SampleOpts), 1.0 if lam is None else lam, _ptr(lo), _ptr(hi), _ptr(rec),
-                               None if src is None else C.pointer(src))
+                               None if src is None else C.pointer(src), _ptr(known), _ptr(keep))
         out, ctx = self._sample("plan_opt", state, x_T, goal, None, (int(kind), C.byref(params)), sigmas, n_steps, noise, rows=True,
                                 tail=(C.byref(opts),))
-        self._keep = self._keep + (lo, hi, src, None if tree is None else tree[0])
+        self._keep = self._keep + (lo, hi, src, None if tree is None else tree[0], known, keep)
         return out, ctx, rec
 
     def sample_sde_tree(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, seeds: torch.Tensor, tol: float,
