@@ -179,10 +179,9 @@ mdt_status mdt_sample_ddim(mdt_model *m, const float *tokens, const float *token
                            int32_t modality, const float *x_T, const float *sigmas_host, int32_t n_steps,
                            int64_t batch, float *out, float *ctx_out, void *stream);
 
-/* The same call with the noise schedule in DEVICE memory, as MDTVAgent.get_noise_schedule builds it
- * (mdtv_agent.py:660-667: `get_sigmas_*(..., self.device)`): the per-step scalars t = -ln(sigma), h, sigma ratio and
- * -expm1(-h) (gc_sampling.py:946-950) are computed by a device kernel, nothing is copied to the host and the call never
- * synchronises.  sigmas_dev: n_steps + 1 floats on the model's device. */
+/* The same call with the noise schedule in DEVICE memory, as MDTVAgent.get_noise_schedule builds it (mdtv_agent.py:660-667):
+ * the per-step scalars t = -ln(sigma), h, sigma ratio and -expm1(-h) (gc_sampling.py:946-950) are computed by a device kernel,
+ * nothing is copied to the host and the call never synchronises.  sigmas_dev: n_steps + 1 floats on the model's device. */
 mdt_status mdt_sample_ddim_dev(mdt_model *m, const float *tokens, const float *tokens2, const float *goal,
                                int32_t modality, const float *x_T, const float *sigmas_dev, int32_t n_steps,
                                int64_t batch, float *out, float *ctx_out, void *stream);
@@ -281,9 +280,10 @@ mdt_status mdt_sample_dev(mdt_model *m, const float *tokens, const float *tokens
                           int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out, float *ctx_out,
                           void *stream);
 
-/* mdt_sample / mdt_sample_dev (and their guided and tree-noise twins) with the options a harness run adds, still ONE enqueue
- * with the launches of the call it extends: action bounds (MDTVAgent.sample_loop's use_scaler) and a per-step record (what a
- * `callback` would see).
+/* The full form of the plan-sampler call; every other fixed-schedule entry of this family is it with named defaults:
+ *   mdt_sample / mdt_sample_dev: opts = NULL;  mdt_sample_guided / _dev_guided: opts = {cond_lambda};
+ *   mdt_sample_sde_tree*: kind = MDT_SAMPLER_DPMPP_SDE, noise = NULL, opts = {cond_lambda (1.0f unless _guided), tree}.
+ * Still ONE enqueue, with the launches of the call it extends.
  *   lo, hi : the bounds of scaler.clip_output, x <- min(max(x, lo), hi) per action dimension as torch.clamp computes it (NaN
  *            stays NaN; lo > hi gives hi), applied in the head of every evaluation that ends a step of a loop that clips there:
  *            after every step of euler, euler_ancestral, heun, dpm_2, dpm_2_ancestral, lms, dpmpp_2s, dpmpp_2s_ancestral; after
@@ -303,8 +303,7 @@ mdt_status mdt_sample_dev(mdt_model *m, const float *tokens, const float *tokens
  *            kind whose schedule ends at sigma = 0 the elements with keep == 1 arrive at `known` to rounding; MDT_SAMPLER_DPM_FAST
  *            stops at sigma_min and arrives within O(sigma_min); 0 < keep < 1 blends the prediction toward `known` at every step.
  *            Values outside [0, 1] are not checked here (the Python facade's ActionPin refuses them).
- * opts == NULL or {sizeof(mdt_sample_opts), 1.0f, NULL, NULL, NULL, NULL} enqueues exactly what mdt_sample / mdt_sample_dev do: a
- * call without a pin launches the kernels it launched before the pin existed.
+ * opts == NULL is {sizeof(mdt_sample_opts), 1.0f, NULL, NULL, NULL, NULL}; a call without a pin launches what it did before pins.
  * `size` is sizeof(mdt_sample_opts), or the struct's size before pin_known / pin_keep were appended (40 on LP64): the two fields
  * then read as NULL, so a client compiled against the earlier header keeps working.
  * Checked before anything is enqueued (MDT_ERR_INVALID_ARG, the message names the field): any other size, exactly one of lo / hi,
@@ -329,10 +328,9 @@ mdt_status mdt_sample_dev_opt(mdt_model *m, const float *tokens, const float *to
                               int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, float *out, float *ctx_out,
                               const mdt_sample_opts *opts, void *stream);
 
-/* mdt_sample_ddim / mdt_sample_ddim_dev with options: cond_lambda (1.0f: unguided; anything else: mdt_sample_ddim_guided's call)
- * and pin_known / pin_keep (above).  lo and hi are accepted and not read -- the reference's DDIM takes a scaler and never clips;
- * record and tree are MDT_ERR_INVALID_ARG (the message names the field): the DDIM head keeps no per-step record and draws no
- * noise.  opts == NULL enqueues exactly what mdt_sample_ddim / mdt_sample_ddim_dev do. */
+/* The full form of the DDIM call: mdt_sample_ddim / _dev are it with opts = NULL, mdt_sample_ddim_guided / _dev_guided with
+ * opts = {cond_lambda}.  It reads cond_lambda and pin_known / pin_keep (above); lo and hi are accepted and not read -- the
+ * reference's DDIM takes a scaler and never clips; record and tree are MDT_ERR_INVALID_ARG (the message names the field). */
 mdt_status mdt_sample_ddim_opt(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
                                const float *x_T, const float *sigmas_host, int32_t n_steps, int64_t batch, float *out,
                                float *ctx_out, const mdt_sample_opts *opts, void *stream);
@@ -381,14 +379,15 @@ mdt_status mdt_sample_dpm_adaptive(mdt_model *m, const float *tokens, const floa
  * accepted; NaN / +-Inf give MDT_ERR_INVALID_ARG before anything is enqueued.  c_skip x is the same in both branches, so the
  * calls combine the network outputs instead, F = F_0 + lambda (F_g - F_0) in fp32 per element before the output scaling.
  *
- * Each call takes the arguments of its unguided twin plus `cond_lambda`.  At lambda == 1, and on a model without a goal token
- * (goal_conditioned=False with MDT, or with MDT-V and use_proprio: there `uncond` changes nothing), it runs the unguided call
- * and gives its bits.  Otherwise ONE call runs the sampler loop over 2B samples: [0, B) conditional, [B, 2B) the same state
- * tokens with a zero goal (and the same `modality` embedder).  The 2B encoder inputs are staged inside the stream (handle-owned
- * buffers, no host synchronisation: capture-safe like the unguided calls); the encoder, the cross-attention K/V and every
- * decoder pass run at 2B; each action head reads rows r and r + B Ta, combines them and updates the B samples of state.  The
- * noise rows are those of the unguided call at B (the host loop's draws).  ctx_out receives the conditional context (B, Te, d).
- * The workspace grows for 2B samples: mdt_reserve(m, 2 B) before capturing a guided call. */
+ * Each call is its family's full form with opts = {cond_lambda} (mdt_sample_dpm_adaptive_guided: its unguided twin plus
+ * `cond_lambda`). At lambda == 1, and on a model without a goal token (goal_conditioned=False with MDT, or with MDT-V and
+ * use_proprio: there `uncond` changes nothing), it runs the unguided call and gives its bits. Otherwise ONE call runs the
+ * sampler loop over 2B samples: [0, B) conditional, [B, 2B) the same state tokens with a zero goal (and the same `modality`
+ * embedder). The 2B encoder inputs are staged inside the stream (handle-owned buffers, no host synchronisation: capture-safe
+ * like the unguided calls); the encoder, the cross-attention K/V and every decoder pass run at 2B; each action head reads rows
+ * r and r + B Ta, combines them and updates the B samples of state. The noise rows are those of the unguided call at B (the
+ * host loop's draws). ctx_out receives the conditional context (B, Te, d). The workspace grows for 2B samples: mdt_reserve(m,
+ * 2 B) before capturing a guided call. */
 mdt_status mdt_sample_ddim_guided(mdt_model *m, const float *tokens, const float *tokens2, const float *goal,
                                   int32_t modality, const float *x_T, const float *sigmas_host, int32_t n_steps,
                                   int64_t batch, float *out, float *ctx_out, float cond_lambda, void *stream);
@@ -439,14 +438,14 @@ typedef struct mdt_brownian_source {
 } mdt_brownian_source;
 
 /* sample_dpmpp_sde (MDT_SAMPLER_DPMPP_SDE) with the noise of the reference's default noise sampler -- the Brownian tree of
- * `tree` -- drawn inside the call instead of read from a noise buffer: the arguments of mdt_sample / mdt_sample_dev /
- * mdt_sample_guided / mdt_sample_dev_guided without kind, noise and n_noise, plus `tree`.  The plan kernel records the
- * (from, to) points of every noise row -- (sigma(t), sigma(s)) then (sigma(t), sigma(t_next)), each where sigma_up != 0, t =
- * -ln(sigma) as the Python loop forms them -- and one more launch before the first evaluation writes every row into a
- * handle-owned buffer from the tree; the evaluations then read it as they read a caller's noise (the same bits as passing those
- * rows to mdt_sample).  A device schedule is read in place (interval and points included): capture-safe, no synchronisation.
- * The first call at a larger batch or step count grows the buffer (synchronising, and a new mdt_ws_generation): make one eager
- * call before capturing.  With eta == 0 or s_noise == 0 the tree is not read. */
+ * `tree` -- drawn inside the call instead of read from a noise buffer (mdt_sample_opt / mdt_sample_dev_opt with opts.tree; a
+ * NULL `tree` is MDT_ERR_INVALID_ARG). The plan kernel records the (from, to) points of every noise row -- (sigma(t),
+ * sigma(s)) then (sigma(t), sigma(t_next)), each where sigma_up != 0, t = -ln(sigma) as the Python loop forms them -- and one
+ * more launch before the first evaluation writes every row into a handle-owned buffer from the tree; the evaluations then read
+ * it as they read a caller's noise (the same bits as passing those rows to mdt_sample). A device schedule is read in place
+ * (interval and points included): capture-safe, no synchronisation. The first call at a larger batch or step count grows the
+ * buffer (synchronising, and a new mdt_ws_generation): make one eager call before capturing. With eta == 0 or s_noise == 0 the
+ * tree is not read. */
 mdt_status mdt_sample_sde_tree(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
                                const float *x_T, const mdt_sampler_params *params, const float *sigmas_host, int32_t n_steps,
                                const mdt_brownian_source *tree, int64_t batch, float *out, float *ctx_out, void *stream);

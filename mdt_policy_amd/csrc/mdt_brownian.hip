@@ -62,6 +62,7 @@ hipError_t launch_fill(const BtArgs& a, hipStream_t s) {
 // the checks both entry points share
 mdt_status check_tree(const char* who, const void* seeds, int32_t n_seeds, double lo, double hi, double tol, int64_t batch,
                       int64_t per_row) {
+    // (sample_plan_impl, mdt_model.hip, gives a tree entry without its tree this text too: change both together)
     if (!seeds || batch < 1 || per_row < 1 || (n_seeds != 1 && n_seeds != batch))
         return mdt_fail(MDT_ERR_INVALID_ARG, "%s: bad argument (seeds, n_seeds = 1 or batch, batch, per_row)", who);
     if (batch * per_row > (int64_t)UINT32_MAX) return mdt_fail(MDT_ERR_INVALID_ARG, "%s: more than 2^32 - 1 elements", who);

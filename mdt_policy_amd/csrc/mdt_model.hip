@@ -1187,30 +1187,63 @@ extern "C" mdt_status mdt_forward(mdt_model* m, const float* tokens, const float
 }
 
 // ------------------------------------------------------------------------------------------------
-// Sampler calls.  Every entry point (the DDIM loop, the plan samplers, adaptive DPM-Solver, and the guided twin of each) fills
-// one SamplerArgs and calls its family's implementation, which checks its arguments (sampler_check, then the family's own),
-// opens the call (sampler_open), runs its evaluations and closes it (sampler_close).
+// Sampler calls.  Every entry point (the DDIM loop, the plan samplers, adaptive DPM-Solver; plain, guided, with options, with tree
+// noise) is an adapter: it fills one SamplerRequest and calls its family's implementation, which checks the request
+// (sampler_check, then the family's own), opens the call (sampler_open), runs its evaluations and closes it (sampler_close).
+// mdt_sample_opt and mdt_sample_ddim_opt state every field; the other entries are those calls with defaults.
 // ------------------------------------------------------------------------------------------------
-// the arguments every sampler entry point takes
-struct SamplerArgs {
-    const char* who;    // the entry point (error messages)
-    const float* lam;   // the guided twin's weight, or null
+// mdt_sample_opts as a call reads it: NULL gives the defaults, `size` may be the struct's size before pin_known / pin_keep were
+// appended (they read as NULL then) or today's; the checks that need no more than the struct itself
+constexpr int32_t OPTS_SIZE_V1 = (int32_t)offsetof(mdt_sample_opts, pin_known);
+constexpr mdt_sample_opts k_default_opts = {(int32_t)sizeof(mdt_sample_opts), 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+static mdt_status read_opts(const char* who, const mdt_sample_opts* opts, mdt_sample_opts* o) {
+    *o = k_default_opts;
+    if (opts) {
+        if (opts->size != (int32_t)sizeof(mdt_sample_opts) && opts->size != OPTS_SIZE_V1)
+            return fail(MDT_ERR_INVALID_ARG, "%s: opts.size is %d, sizeof(mdt_sample_opts) is %d (%d without the pin)", who,
+                        opts->size, (int)sizeof(mdt_sample_opts), (int)OPTS_SIZE_V1);
+        memcpy(o, opts, (size_t)opts->size);
+    }
+    if (!std::isfinite(o->cond_lambda)) return fail(MDT_ERR_INVALID_ARG, "%s: opts.cond_lambda must be finite", who);
+    if ((o->lo == nullptr) != (o->hi == nullptr))
+        return fail(MDT_ERR_INVALID_ARG, "%s: opts.lo and opts.hi must both be set or both be null", who);
+    if ((o->pin_known == nullptr) != (o->pin_keep == nullptr))
+        return fail(MDT_ERR_INVALID_ARG, "%s: opts.%s is set and opts.%s is null: a pin needs both", who,
+                    o->pin_known ? "pin_known" : "pin_keep", o->pin_known ? "pin_keep" : "pin_known");
+    return MDT_OK;
+}
+
+// One sampler call.  The first ten fields are the arguments every entry takes; the rest default to the plain call.
+struct SamplerRequest {
+    const char* who;  // the entry point (error messages)
     const float *tokens, *tokens2, *goal;
     int32_t modality;
     const float* x_T;
     int64_t batch;
-    float* out;
-    float* ctx_out;
+    float *out, *ctx_out;
     void* stream;
-    mdt_head_pin pin = {};  // pinned actions (mdt_sample_opts.pin_known / pin_keep), both (B, Ta, A) or both null
-};
+    const float* sigmas = nullptr;  // the noise levels: in host memory (they ride in the prep kernel's arguments) or on the device
+    bool sigmas_dev = false;        // (read in place)
+    int32_t n_steps = 0;
+    int32_t kind = 0;  // the plan family: kind, params and the caller's noise rows (not read when o.tree draws them)
+    const mdt_sampler_params* params = nullptr;
+    const float* noise = nullptr;
+    int32_t n_noise = 0;
+    mdt_sample_opts o = k_default_opts;  // as read_opts leaves them; o.cond_lambda != 1 is the guided call
+    bool weight_given = false;  // a *_guided entry: guide_of's handle and weight checks come first, at lambda == 1 too
+    bool tree_entry = false;    // mdt_sample_sde_tree*: o.tree is the entry's `tree` argument, refused when null
 
-// a sampler call's noise levels: in host memory (they ride in the prep kernel's arguments) or on the device (read in place)
-struct Sched {
-    const float* levels;
-    bool dev;
-    const float* host() const { return dev ? nullptr : levels; }
-    const float* device() const { return dev ? levels : nullptr; }
+    SamplerRequest& schedule(const float* levels, bool dev, int32_t n) { sigmas = levels; sigmas_dev = dev; n_steps = n; return *this; }
+    SamplerRequest& plan(int32_t k, const mdt_sampler_params* p, const float* rows, int32_t n) {
+        kind = k; params = p; noise = rows; n_noise = n; return *this;
+    }
+    SamplerRequest& weight(float lam) { o.cond_lambda = lam; weight_given = true; return *this; }
+    SamplerRequest& tree(const mdt_sampler_params* p, const mdt_brownian_source* t) {
+        kind = MDT_SAMPLER_DPMPP_SDE; params = p; o.tree = t; tree_entry = true; return *this;
+    }
+    bool guided() const { return weight_given || o.cond_lambda != 1.f; }
+    const float* host_sigmas() const { return sigmas_dev ? nullptr : sigmas; }
+    const float* dev_sigmas() const { return sigmas_dev ? sigmas : nullptr; }
 };
 
 // An open sampler call: the encoder's inputs -- a guided call's staged 2B-sample copies -- the samples through the network (nb:
@@ -1232,8 +1265,8 @@ struct SamplerCall {
 
 // The first checks of every sampler call, in the order the entry points have always made them: a guided twin's handle and
 // weight (guide_of decides gd), the schedule (sched_ok), then the arguments all families share ("<family>: bad argument").
-static mdt_status sampler_check(const mdt_model* m, const SamplerArgs& a, const char* family, bool sched_ok, mdt_guide* gd) {
-    if (a.lam) MDT_TRY(guide_of(m, *a.lam, a.who, gd));
+static mdt_status sampler_check(const mdt_model* m, const SamplerRequest& a, const char* family, bool sched_ok, mdt_guide* gd) {
+    if (a.guided()) MDT_TRY(guide_of(m, a.o.cond_lambda, a.who, gd));
     if (!sched_ok) return fail(MDT_ERR_INVALID_ARG, "%s: null sigmas", a.who);
     if (!m || !a.x_T || !a.out || a.batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: bad argument", family);
     return MDT_OK;
@@ -1241,11 +1274,11 @@ static mdt_status sampler_check(const mdt_model* m, const SamplerArgs& a, const 
 
 // The encoder arguments are checked and the parameters known loaded before anything is enqueued; the handle then holds nb
 // samples, and a guided call's encoder inputs are staged in the handle's buffers: tokens and tokens2 twice, the goal then zeros.
-static mdt_status sampler_open(mdt_model* m, const SamplerArgs& a, mdt_guide gd, SamplerCall* c) {
+static mdt_status sampler_open(mdt_model* m, const SamplerRequest& a, mdt_guide gd, SamplerCall* c) {
     MDT_TRY(check_encode_args(m, a.tokens, a.tokens2, a.goal, a.ctx_out));
     MDT_TRY(check_loaded(m));
     *c = {a.tokens, a.tokens2, a.goal, a.modality, a.batch, gd.on ? 2 * a.batch : a.batch, a.ctx_out, a.ctx_out, gd,
-          (hipStream_t)a.stream, a.pin};
+          (hipStream_t)a.stream, {a.o.pin_known, a.o.pin_keep}};
     MDT_TRY(mdt_reserve(m, c->nb));
     if (!gd.on) return MDT_OK;
     const int w1 = guide_w1(m), w2 = a.tokens2 ? guide_w2(m) : 0;
@@ -1264,9 +1297,14 @@ static mdt_status sampler_close(mdt_model* m, const SamplerCall& c) {
 }
 
 // gd.on (guided): the encoder and the decoder run 2B samples, the head combines the halves and updates B samples of state
-static mdt_status sample_ddim_impl(mdt_model* m, const SamplerArgs& a, Sched sc, int32_t n_steps) {
+// Of the options DDIM takes cond_lambda and the pin; lo / hi are accepted and not read (the reference's DDIM never clips), record
+// and tree are refused.
+static mdt_status sample_ddim_impl(mdt_model* m, const SamplerRequest& a) {
+    if (a.o.record) return fail(MDT_ERR_INVALID_ARG, "%s: opts.record: the DDIM head keeps no per-step record", a.who);
+    if (a.o.tree) return fail(MDT_ERR_INVALID_ARG, "%s: opts.tree is the noise of MDT_SAMPLER_DPMPP_SDE; DDIM draws none", a.who);
+    const int32_t n_steps = a.n_steps;
     mdt_guide gd;
-    MDT_TRY(sampler_check(m, a, "mdt_sample_ddim", sc.levels != nullptr, &gd));
+    MDT_TRY(sampler_check(m, a, "mdt_sample_ddim", a.sigmas != nullptr, &gd));
     if (n_steps < 1 || n_steps > MAX_STEPS) return fail(MDT_ERR_INVALID_ARG, "n_steps must be 1..%d", MAX_STEPS);
     SamplerCall c;
     MDT_TRY(sampler_open(m, a, gd, &c));
@@ -1282,7 +1320,7 @@ static mdt_status sample_ddim_impl(mdt_model* m, const SamplerArgs& a, Sched sc,
     // of the encoder's first small products (rollout batches; at large batches whatever the encoder did not take along is
     // launched behind it)
     const View V = decoder_view(m, 0);
-    LAUNCH(mdt_launch_sample_prep(sc.device(), sc.host(), n_steps, m->steps, m->freqs, m->cond == COND_TOKEN ? nullptr : m->sig_e,
+    LAUNCH(mdt_launch_sample_prep(a.dev_sigmas(), a.host_sigmas(), n_steps, m->steps, m->freqs, m->cond == COND_TOKEN ? nullptr : m->sig_e,
                                   m->D, a.x_T, m->cfg.sigma_data, m->Wa, m->ba, V.y, (int)(c.nb * m->Ta), m->A, c.s,
                                   (int)(a.batch * m->Ta)));
     mdt_status ms = run_modulation(m, m->steps + 3, 4, n_steps, c.s, true, !per_step_ctx);  // one row of conditioning vectors per step
@@ -1301,32 +1339,49 @@ static mdt_status sample_ddim_impl(mdt_model* m, const SamplerArgs& a, Sched sc,
     return sampler_close(m, c);
 }
 
-extern "C" mdt_status mdt_sample_ddim(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
-                                      int32_t modality, const float* x_T, const float* sigmas, int32_t n_steps,
-                                      int64_t batch, float* out, float* ctx_out, void* stream) {
-    return sample_ddim_impl(m, {"mdt_sample_ddim", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream},
-                            {sigmas, false}, n_steps);
-}
-
-extern "C" mdt_status mdt_sample_ddim_dev(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
-                                          int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
-                                          int64_t batch, float* out, float* ctx_out, void* stream) {
-    return sample_ddim_impl(m, {"mdt_sample_ddim_dev", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream},
-                            {sigmas_dev, true}, n_steps);
+extern "C" mdt_status mdt_sample_ddim(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
+                                      const float* x_T, const float* sigmas, int32_t n_steps, int64_t batch, float* out,
+                                      float* ctx_out, void* stream) {
+    SamplerRequest r = {"mdt_sample_ddim", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_ddim_impl(m, r.schedule(sigmas, false, n_steps));
 }
 
 extern "C" mdt_status mdt_sample_ddim_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                              int32_t modality, const float* x_T, const float* sigmas, int32_t n_steps,
                                              int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
-    return sample_ddim_impl(m, {"mdt_sample_ddim_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
-                                stream}, {sigmas, false}, n_steps);
+    SamplerRequest r = {"mdt_sample_ddim_guided", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_ddim_impl(m, r.schedule(sigmas, false, n_steps).weight(cond_lambda));
+}
+
+extern "C" mdt_status mdt_sample_ddim_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                          int32_t modality, const float* x_T, const float* sigmas_host, int32_t n_steps,
+                                          int64_t batch, float* out, float* ctx_out, const mdt_sample_opts* opts, void* stream) {
+    SamplerRequest r = {"mdt_sample_ddim_opt", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_ddim_impl(m, r.schedule(sigmas_host, false, n_steps));
+}
+
+extern "C" mdt_status mdt_sample_ddim_dev(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                          int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
+                                          int64_t batch, float* out, float* ctx_out, void* stream) {
+    SamplerRequest r = {"mdt_sample_ddim_dev", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_ddim_impl(m, r.schedule(sigmas_dev, true, n_steps));
 }
 
 extern "C" mdt_status mdt_sample_ddim_dev_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                                  int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
                                                  int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
-    return sample_ddim_impl(m, {"mdt_sample_ddim_dev_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out,
-                                ctx_out, stream}, {sigmas_dev, true}, n_steps);
+    SamplerRequest r = {"mdt_sample_ddim_dev_guided", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_ddim_impl(m, r.schedule(sigmas_dev, true, n_steps).weight(cond_lambda));
+}
+
+extern "C" mdt_status mdt_sample_ddim_dev_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                              int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
+                                              int64_t batch, float* out, float* ctx_out, const mdt_sample_opts* opts,
+                                              void* stream) {
+    SamplerRequest r = {"mdt_sample_ddim_dev_opt", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_ddim_impl(m, r.schedule(sigmas_dev, true, n_steps));
 }
 
 // MDT_PLAN_* -> mdt_status with the message of the failed check
@@ -1355,67 +1410,76 @@ extern "C" mdt_status mdt_sampler_plan(int32_t kind, const mdt_sampler_params* p
     return plan_fail(st, "mdt_sampler_plan", kind);
 }
 
-// evaluation e of the plan in m->plan: (per evaluation for COND_TOKEN: the encoder with its sigma -> ctx_out), one decoder pass,
-// the plan head reading the state xs, writing X' to out and Y' to y_out; the next input is embedded unless `last`
-// bounds (lo, hi: the head clamps X' where the evaluation ends a step) and rec (two (M, A) rows: the head stores Y and D where the
-// evaluation begins a step): mdt_sample_opts' operands for this evaluation, or null
-static mdt_status run_plan_eval(mdt_model* m, const View& V, const SamplerCall& c, int e, bool last, const float* xs, float* out,
-                                float* y_out, const float* noise, int32_t n_noise, float* ctx_out, const float* lo = nullptr,
-                                const float* hi = nullptr, float* rec = nullptr) {
+// what one evaluation of a plan reads and writes: the state xs, X' -> out, Y' -> y_out, the next input embedded unless `last`,
+// the caller's noise rows, where a COND_TOKEN model's per-evaluation encoder leaves its context, and mdt_sample_opts' operands for
+// this evaluation or null: the bounds (the head clamps X' where the evaluation ends a step) and the record's two (M, A) rows (the
+// head stores Y and D where the evaluation begins a step)
+struct PlanEvalIo {
+    bool last;
+    const float* xs;
+    float *out, *y_out;
+    const float* noise;
+    int32_t n_noise;
+    float* ctx_out;
+    const float *lo, *hi;
+    float* rec;
+};
+
+// evaluation e of the plan in m->plan: (per evaluation for COND_TOKEN: the encoder with its sigma), one decoder pass, the plan head
+static mdt_status run_plan_eval(mdt_model* m, const View& V, const SamplerCall& c, int e, const PlanEvalIo& io) {
     mdt_sampler_eval* ev = m->plan->e;
-    if (m->cond == COND_TOKEN) MDT_TRY(c.encode(m, &ev[e].sigma, ctx_out));
-    mdt_head_plan pl;
-    pl.e = &ev[e];
-    pl.xs = xs;
-    pl.hist = m->hist;
-    pl.noise = noise;
-    pl.y_out = y_out;
-    pl.nel = (int64_t)c.batch * m->Ta * m->A;
-    pl.n_noise = noise ? n_noise : 0;
-    pl.lo = lo;
-    pl.hi = hi;
-    pl.rec_x = rec;
-    pl.rec_d = rec ? rec + pl.nel : nullptr;
-    mdt_head_args h = head_args(m, V.y, c.batch, m->ybuf, &ev[e].sigma, 0, out, MDT_HEAD_PLAN);
-    return run_eval(m, V, c.nb, cond_row(m, e), 0, h, &pl, last ? nullptr : &ev[e].sigma_next, c.s, c.gd, c.pin);
+    if (m->cond == COND_TOKEN) MDT_TRY(c.encode(m, &ev[e].sigma, io.ctx_out));
+    const int64_t nel = (int64_t)c.batch * m->Ta * m->A;
+    const mdt_head_plan pl = {&ev[e], io.xs, m->hist, io.noise, io.y_out, nel, io.noise ? io.n_noise : 0, io.lo, io.hi, io.rec,
+                              io.rec ? io.rec + nel : nullptr};
+    mdt_head_args h = head_args(m, V.y, c.batch, m->ybuf, &ev[e].sigma, 0, io.out, MDT_HEAD_PLAN);
+    return run_eval(m, V, c.nb, cond_row(m, e), 0, h, &pl, io.last ? nullptr : &ev[e].sigma_next, c.s, c.gd, c.pin);
 }
 
 // The structure of sample_ddim_impl: the plan and the sigma embeddings of every evaluation (one launch), the first input, the
 // conditioning rows of every evaluation (their GEMMs ride in the encoder's launches), the encoder and cross K/V once, then one
 // decoder pass + plan head per evaluation.
-// tree (dpmpp_sde with tree noise, mdt_sample_sde_tree*): `noise` is null and the rows come from the tree -- the plan kernel records
-// their points, k_brownian_fill writes them into the handle's tr_noise before the first evaluation, which then reads them as a
-// caller's buffer.
-// bounds / record (mdt_sample_opt): lo and hi go to the heads of the evaluations whose step the kind's loop clips
+// o.tree (dpmpp_sde with tree noise; the `tree` argument of mdt_sample_sde_tree*): the request's noise rows are not read and the
+// rows come from the tree -- the plan kernel records their points, k_brownian_fill writes them into the handle's tr_noise before
+// the first evaluation, which then reads them as a caller's buffer.
+// o.lo, o.hi / o.record: lo and hi go to the heads of the evaluations whose step the kind's loop clips
 // (mdt_plan_loop_clips; the head applies them where the plan says the step ends), the record's row pair of step i to the heads of
 // step i's evaluations (the head stores where the plan says the step begins) -- no launch and no buffer of the call's own.
-static mdt_status sample_plan_impl(mdt_model* m, const SamplerArgs& a, int32_t kind, const mdt_sampler_params* params, Sched sc,
-                                   int32_t n_steps, const float* noise, int32_t n_noise, const mdt_brownian_source* tree = nullptr,
-                                   const float* lo = nullptr, const float* hi = nullptr, float* record = nullptr) {
+static mdt_status sample_plan_impl(mdt_model* m, const SamplerRequest& a) {
+    const int32_t kind = a.kind, n_steps = a.n_steps;
+    const float* host = a.host_sigmas();
+    const mdt_brownian_source* tree = a.o.tree;
+    if (tree && kind != MDT_SAMPLER_DPMPP_SDE)
+        return fail(MDT_ERR_INVALID_ARG, "%s: opts.tree is the noise of MDT_SAMPLER_DPMPP_SDE (kind %d)", a.who, kind);
+    const bool wants_tree = tree || a.tree_entry;
+    const float* noise = wants_tree ? nullptr : a.noise;
+    int32_t n_noise = wants_tree ? 0 : a.n_noise;
     mdt_guide gd;
-    MDT_TRY(sampler_check(m, a, "mdt_sample", sc.levels != nullptr, &gd));
-    // (lo, hi and record are read and written one element at a time: any float alignment will do, e.g. a slice of a larger tensor)
-    const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
+    MDT_TRY(sampler_check(m, a, "mdt_sample", a.sigmas != nullptr, &gd));
+    // (o.lo, o.hi and o.record are read and written one element at a time: any float alignment will do, e.g. a slice of a larger tensor)
+    const mdt_sampler_params p = a.params ? *a.params : mdt_sampler_defaults();
     int E = 0, rows = 0;
     MDT_TRY(plan_fail(mdt_plan_shape(kind, p, n_steps, &E, &rows), "mdt_sample", kind));
     const int max_rows = rows;
-    if (sc.host()) {  // a host schedule: the loop's exact draw count (a device schedule: the structural maximum)
-        MDT_TRY(plan_fail(mdt_plan_check_levels(kind, p, sc.host()), "mdt_sample", kind));
+    if (host) {  // a host schedule: the loop's exact draw count (a device schedule: the structural maximum)
+        MDT_TRY(plan_fail(mdt_plan_check_levels(kind, p, host), "mdt_sample", kind));
         static thread_local mdt_sampler_plan_t hp;
-        mdt_build_sampler_plan(kind, p, sc.host(), n_steps, &hp);
+        mdt_build_sampler_plan(kind, p, host, n_steps, &hp);
         rows = hp.n_noise;
-        for (int e = 0; record && e < hp.n_evals; ++e)  // the record's rows are placed by the structure: it must be the plan's
+        for (int e = 0; a.o.record && e < hp.n_evals; ++e)  // the record's rows are placed by the structure: it must be the plan's
             if (hp.e[e].step != mdt_plan_step_of(kind, n_steps, e))
                 return fail(MDT_ERR_STATE, "mdt_sample: evaluation %d is in step %d of the plan, %d by its structure", e, hp.e[e].step,
                             mdt_plan_step_of(kind, n_steps, e));
     }
     const bool use_tree = tree && mdt_plan_needs_noise(kind, p) && max_rows > 0;
-    if (tree) {
+    if (wants_tree) {
         const int64_t per_row = (int64_t)m->Ta * m->A;
+        if (!tree)  // a tree entry without its tree: what a tree without seeds is told (check_tree, mdt_brownian.hip)
+            return fail(MDT_ERR_INVALID_ARG, "%s: bad argument (seeds, n_seeds = 1 or batch, batch, per_row)", a.who);
         MDT_TRY(mdt_check_brownian_source(a.who, tree, a.batch, per_row));
-        if (sc.host() && tree->lo == 0.0 && tree->hi == 0.0) {
+        if (host && tree->lo == 0.0 && tree->hi == 0.0) {
             double lo = 0.0, hi = 0.0;
-            mdt_tree_interval(sc.host(), n_steps + 1, &lo, &hi);
+            mdt_tree_interval(host, n_steps + 1, &lo, &hi);
             mdt_brownian_source t = *tree;
             t.lo = lo; t.hi = hi;
             MDT_TRY(mdt_check_brownian_source(a.who, &t, a.batch, per_row));
@@ -1444,7 +1508,7 @@ static mdt_status sample_plan_impl(mdt_model* m, const SamplerArgs& a, int32_t k
     const bool per_step_ctx = m->cond == COND_TOKEN;  // sigma is a context token: the encoder runs per evaluation
     const View V = decoder_view(m, 0);
     mdt_sampler_eval* ev = m->plan->e;
-    LAUNCH(mdt_launch_sampler_prep(sc.device(), sc.host(), n_steps, kind, p, m->plan, m->freqs, per_step_ctx ? nullptr : m->sig_e,
+    LAUNCH(mdt_launch_sampler_prep(a.dev_sigmas(), host, n_steps, kind, p, m->plan, m->freqs, per_step_ctx ? nullptr : m->sig_e,
                                    m->D, a.x_T, noise, noise ? n_noise : 0, m->ybuf, m->hist, m->cfg.sigma_data, m->Wa, m->ba, V.y,
                                    (int)(c.nb * m->Ta), m->A, c.s, (int)(a.batch * m->Ta), use_tree ? m->tr_q : nullptr));
     if (use_tree)  // every noise row from the tree, before the first evaluation reads one
@@ -1456,10 +1520,10 @@ static mdt_status sample_plan_impl(mdt_model* m, const SamplerArgs& a, int32_t k
     LAUNCH(mdt_gemm_side_flush(c.s));
     const int64_t rec_stride = 2 * a.batch * m->Ta * m->A;
     for (int e = 0; e < E; ++e) {
-        const bool last = e == E - 1, clips = lo && mdt_plan_loop_clips(kind, last);
-        MDT_TRY(run_plan_eval(m, V, c, e, last, e == 0 ? a.x_T : m->xbuf, last ? a.out : m->xbuf, last ? nullptr : m->ybuf, noise,
-                              n_noise, last ? c.ctx_out : nullptr, clips ? lo : nullptr, clips ? hi : nullptr,
-                              record ? record + mdt_plan_step_of(kind, n_steps, e) * rec_stride : nullptr));
+        const bool last = e == E - 1, clips = a.o.lo && mdt_plan_loop_clips(kind, last);
+        MDT_TRY(run_plan_eval(m, V, c, e, {last, e == 0 ? a.x_T : m->xbuf, last ? a.out : m->xbuf, last ? nullptr : m->ybuf, noise,
+                                           n_noise, last ? c.ctx_out : nullptr, clips ? a.o.lo : nullptr, clips ? a.o.hi : nullptr,
+                                           a.o.record ? a.o.record + mdt_plan_step_of(kind, n_steps, e) * rec_stride : nullptr}));
     }
     return sampler_close(m, c);
 }
@@ -1468,150 +1532,82 @@ extern "C" mdt_status mdt_sample(mdt_model* m, const float* tokens, const float*
                                  const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas_host,
                                  int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, float* out, float* ctx_out,
                                  void* stream) {
-    return sample_plan_impl(m, {"mdt_sample", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream}, kind,
-                            params, {sigmas_host, false}, n_steps, noise, n_noise);
-}
-
-extern "C" mdt_status mdt_sample_dev(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
-                                     int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
-                                     const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
-                                     int64_t batch, float* out, float* ctx_out, void* stream) {
-    return sample_plan_impl(m, {"mdt_sample_dev", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream}, kind,
-                            params, {sigmas_dev, true}, n_steps, noise, n_noise);
+    SamplerRequest r = {"mdt_sample", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_plan_impl(m, r.schedule(sigmas_host, false, n_steps).plan(kind, params, noise, n_noise));
 }
 
 extern "C" mdt_status mdt_sample_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                         int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
                                         const float* sigmas_host, int32_t n_steps, const float* noise, int32_t n_noise,
                                         int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
-    return sample_plan_impl(m, {"mdt_sample_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream},
-                            kind, params, {sigmas_host, false}, n_steps, noise, n_noise);
-}
-
-extern "C" mdt_status mdt_sample_dev_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
-                                            int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
-                                            const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
-                                            int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
-    return sample_plan_impl(m, {"mdt_sample_dev_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
-                                stream}, kind, params, {sigmas_dev, true}, n_steps, noise, n_noise);
-}
-
-// mdt_sample_opts as a call reads it: NULL gives the defaults, `size` may be the struct's size before pin_known / pin_keep were
-// appended (they read as NULL then) or today's; the checks that need no more than the struct itself
-constexpr int32_t OPTS_SIZE_V1 = (int32_t)offsetof(mdt_sample_opts, pin_known);
-static mdt_status read_opts(const char* who, const mdt_sample_opts* opts, mdt_sample_opts* o) {
-    *o = {(int32_t)sizeof(mdt_sample_opts), 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (opts) {
-        if (opts->size != (int32_t)sizeof(mdt_sample_opts) && opts->size != OPTS_SIZE_V1)
-            return fail(MDT_ERR_INVALID_ARG, "%s: opts.size is %d, sizeof(mdt_sample_opts) is %d (%d without the pin)", who,
-                        opts->size, (int)sizeof(mdt_sample_opts), (int)OPTS_SIZE_V1);
-        memcpy(o, opts, (size_t)opts->size);
-    }
-    if (!std::isfinite(o->cond_lambda)) return fail(MDT_ERR_INVALID_ARG, "%s: opts.cond_lambda must be finite", who);
-    if ((o->lo == nullptr) != (o->hi == nullptr))
-        return fail(MDT_ERR_INVALID_ARG, "%s: opts.lo and opts.hi must both be set or both be null", who);
-    if ((o->pin_known == nullptr) != (o->pin_keep == nullptr))
-        return fail(MDT_ERR_INVALID_ARG, "%s: opts.%s is set and opts.%s is null: a pin needs both", who,
-                    o->pin_known ? "pin_known" : "pin_keep", o->pin_known ? "pin_keep" : "pin_known");
-    return MDT_OK;
-}
-
-// mdt_sample_opt / mdt_sample_dev_opt: the options checked (nothing is enqueued before sample_plan_impl's own checks pass), then
-// the call path of mdt_sample and its guided and tree-noise twins
-static mdt_status sample_opt_impl(mdt_model* m, const char* who, const float* tokens, const float* tokens2, const float* goal,
-                                  int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params, Sched sc,
-                                  int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, float* out, float* ctx_out,
-                                  const mdt_sample_opts* opts, void* stream) {
-    mdt_sample_opts o;
-    MDT_TRY(read_opts(who, opts, &o));
-    if (o.tree && kind != MDT_SAMPLER_DPMPP_SDE)
-        return fail(MDT_ERR_INVALID_ARG, "%s: opts.tree is the noise of MDT_SAMPLER_DPMPP_SDE (kind %d)", who, kind);
-    const bool guided = o.cond_lambda != 1.f;  // lambda == 1 is the unguided call (mdt_sample_guided gives its bits there too)
-    return sample_plan_impl(m, {who, guided ? &o.cond_lambda : nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
-                                stream, {o.pin_known, o.pin_keep}}, kind, params, sc, n_steps, o.tree ? nullptr : noise,
-                            o.tree ? 0 : n_noise, o.tree, o.lo, o.hi, o.record);
-}
-
-// mdt_sample_ddim_opt / mdt_sample_ddim_dev_opt: cond_lambda and the pin; lo / hi are accepted and not read (the reference's DDIM
-// never clips), record and tree are refused
-static mdt_status sample_ddim_opt_impl(mdt_model* m, const char* who, const float* tokens, const float* tokens2, const float* goal,
-                                       int32_t modality, const float* x_T, Sched sc, int32_t n_steps, int64_t batch, float* out,
-                                       float* ctx_out, const mdt_sample_opts* opts, void* stream) {
-    mdt_sample_opts o;
-    MDT_TRY(read_opts(who, opts, &o));
-    if (o.record) return fail(MDT_ERR_INVALID_ARG, "%s: opts.record: the DDIM head keeps no per-step record", who);
-    if (o.tree) return fail(MDT_ERR_INVALID_ARG, "%s: opts.tree is the noise of MDT_SAMPLER_DPMPP_SDE; DDIM draws none", who);
-    const bool guided = o.cond_lambda != 1.f;
-    return sample_ddim_impl(m, {who, guided ? &o.cond_lambda : nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
-                                stream, {o.pin_known, o.pin_keep}}, sc, n_steps);
-}
-
-extern "C" mdt_status mdt_sample_ddim_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
-                                          int32_t modality, const float* x_T, const float* sigmas_host, int32_t n_steps,
-                                          int64_t batch, float* out, float* ctx_out, const mdt_sample_opts* opts, void* stream) {
-    return sample_ddim_opt_impl(m, "mdt_sample_ddim_opt", tokens, tokens2, goal, modality, x_T, {sigmas_host, false}, n_steps, batch,
-                                out, ctx_out, opts, stream);
-}
-
-extern "C" mdt_status mdt_sample_ddim_dev_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
-                                              int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
-                                              int64_t batch, float* out, float* ctx_out, const mdt_sample_opts* opts, void* stream) {
-    return sample_ddim_opt_impl(m, "mdt_sample_ddim_dev_opt", tokens, tokens2, goal, modality, x_T, {sigmas_dev, true}, n_steps,
-                                batch, out, ctx_out, opts, stream);
+    SamplerRequest r = {"mdt_sample_guided", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_plan_impl(m, r.schedule(sigmas_host, false, n_steps).plan(kind, params, noise, n_noise).weight(cond_lambda));
 }
 
 extern "C" mdt_status mdt_sample_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
                                      const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas_host,
                                      int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, float* out,
                                      float* ctx_out, const mdt_sample_opts* opts, void* stream) {
-    return sample_opt_impl(m, "mdt_sample_opt", tokens, tokens2, goal, modality, x_T, kind, params, {sigmas_host, false}, n_steps,
-                           noise, n_noise, batch, out, ctx_out, opts, stream);
+    SamplerRequest r = {"mdt_sample_opt", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_plan_impl(m, r.schedule(sigmas_host, false, n_steps).plan(kind, params, noise, n_noise));
+}
+
+extern "C" mdt_status mdt_sample_dev(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
+                                     const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas_dev,
+                                     int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, float* out,
+                                     float* ctx_out, void* stream) {
+    SamplerRequest r = {"mdt_sample_dev", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_plan_impl(m, r.schedule(sigmas_dev, true, n_steps).plan(kind, params, noise, n_noise));
+}
+
+extern "C" mdt_status mdt_sample_dev_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                            int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
+                                            const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
+                                            int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
+    SamplerRequest r = {"mdt_sample_dev_guided", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_plan_impl(m, r.schedule(sigmas_dev, true, n_steps).plan(kind, params, noise, n_noise).weight(cond_lambda));
 }
 
 extern "C" mdt_status mdt_sample_dev_opt(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                          int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
                                          const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
                                          int64_t batch, float* out, float* ctx_out, const mdt_sample_opts* opts, void* stream) {
-    return sample_opt_impl(m, "mdt_sample_dev_opt", tokens, tokens2, goal, modality, x_T, kind, params, {sigmas_dev, true}, n_steps,
-                           noise, n_noise, batch, out, ctx_out, opts, stream);
+    SamplerRequest r = {"mdt_sample_dev_opt", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_plan_impl(m, r.schedule(sigmas_dev, true, n_steps).plan(kind, params, noise, n_noise));
 }
-
-static const mdt_brownian_source k_null_tree = {};  // a null `tree` argument: refused by the checks
 
 extern "C" mdt_status mdt_sample_sde_tree(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                           int32_t modality, const float* x_T, const mdt_sampler_params* params,
                                           const float* sigmas_host, int32_t n_steps, const mdt_brownian_source* tree, int64_t batch,
                                           float* out, float* ctx_out, void* stream) {
-    return sample_plan_impl(m, {"mdt_sample_sde_tree", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream},
-                            MDT_SAMPLER_DPMPP_SDE, params, {sigmas_host, false}, n_steps, nullptr, 0,
-                            tree ? tree : &k_null_tree);
-}
-
-extern "C" mdt_status mdt_sample_sde_tree_dev(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
-                                              int32_t modality, const float* x_T, const mdt_sampler_params* params,
-                                              const float* sigmas_dev, int32_t n_steps, const mdt_brownian_source* tree,
-                                              int64_t batch, float* out, float* ctx_out, void* stream) {
-    return sample_plan_impl(m, {"mdt_sample_sde_tree_dev", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
-                                stream}, MDT_SAMPLER_DPMPP_SDE, params, {sigmas_dev, true}, n_steps, nullptr, 0,
-                            tree ? tree : &k_null_tree);
+    SamplerRequest r = {"mdt_sample_sde_tree", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_plan_impl(m, r.schedule(sigmas_host, false, n_steps).tree(params, tree));
 }
 
 extern "C" mdt_status mdt_sample_sde_tree_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                                  int32_t modality, const float* x_T, const mdt_sampler_params* params,
                                                  const float* sigmas_host, int32_t n_steps, const mdt_brownian_source* tree,
                                                  int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
-    return sample_plan_impl(m, {"mdt_sample_sde_tree_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
-                                stream}, MDT_SAMPLER_DPMPP_SDE, params, {sigmas_host, false}, n_steps, nullptr, 0,
-                            tree ? tree : &k_null_tree);
+    SamplerRequest r = {"mdt_sample_sde_tree_guided", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_plan_impl(m, r.schedule(sigmas_host, false, n_steps).tree(params, tree).weight(cond_lambda));
+}
+
+extern "C" mdt_status mdt_sample_sde_tree_dev(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                              int32_t modality, const float* x_T, const mdt_sampler_params* params,
+                                              const float* sigmas_dev, int32_t n_steps, const mdt_brownian_source* tree,
+                                              int64_t batch, float* out, float* ctx_out, void* stream) {
+    SamplerRequest r = {"mdt_sample_sde_tree_dev", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_plan_impl(m, r.schedule(sigmas_dev, true, n_steps).tree(params, tree));
 }
 
 extern "C" mdt_status mdt_sample_sde_tree_dev_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                                      int32_t modality, const float* x_T, const mdt_sampler_params* params,
                                                      const float* sigmas_dev, int32_t n_steps, const mdt_brownian_source* tree,
                                                      int64_t batch, float* out, float* ctx_out, float cond_lambda, void* stream) {
-    return sample_plan_impl(m, {"mdt_sample_sde_tree_dev_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch, out,
-                                ctx_out, stream}, MDT_SAMPLER_DPMPP_SDE, params, {sigmas_dev, true}, n_steps, nullptr, 0,
-                            tree ? tree : &k_null_tree);
+    SamplerRequest r = {"mdt_sample_sde_tree_dev_guided", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_plan_impl(m, r.schedule(sigmas_dev, true, n_steps).tree(params, tree).weight(cond_lambda));
 }
 
 extern "C" mdt_status mdt_dpm_control_init(mdt_dpm_control* c, double h, double pcoeff, double icoeff, double dcoeff,
@@ -1643,7 +1639,7 @@ struct DpmHost {
 // input (X at sigma(s)), the conditioning rows of its evaluations, one decoder pass + plan head per evaluation (the last writes
 // high -> hi and low -> lo), the error partials, one read-back and the controller.  Accepting swaps pointers: X <- high,
 // prev <- low.  Every scalar is the loop's: s and t in fp32, t = min / max(t_end, fp32(s + fp32(h))), the 1e-5 end test.
-static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const SamplerArgs& a, float sigma_min, float sigma_max,
+static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const SamplerRequest& a, float sigma_min, float sigma_max,
                                            const mdt_dpm_adaptive_params* params, mdt_dpm_adaptive_info* info) {
     mdt_guide gd;
     MDT_TRY(sampler_check(m, a, "mdt_sample_dpm_adaptive", true, &gd));
@@ -1698,8 +1694,8 @@ static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const SamplerArgs& a, f
         MDT_TRY(run_modulation(m, &m->plan->e[0].sigma, stride, E, s));
         for (int e = 0; e < E; ++e) {
             const bool last = e == E - 1;
-            MDT_TRY(run_plan_eval(m, V, c, e, last, e == 0 ? X : m->xbuf, last ? hi : m->xbuf, last ? lo : m->ybuf, nullptr, 0,
-                                  c.ctx_out));
+            MDT_TRY(run_plan_eval(m, V, c, e, {last, e == 0 ? X : m->xbuf, last ? hi : m->xbuf, last ? lo : m->ybuf, nullptr, 0,
+                                               c.ctx_out, nullptr, nullptr, nullptr}));
         }
         LAUNCH(mdt_launch_dpm_error(lo, hi, prev, nel, (float)p.rtol, (float)p.atol, part, s));
         HIP_TRY(hipMemcpyAsync(hb->part, part, parts * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -1733,16 +1729,16 @@ extern "C" mdt_status mdt_sample_dpm_adaptive(mdt_model* m, const float* tokens,
                                               int32_t modality, const float* x_T, float sigma_min, float sigma_max,
                                               const mdt_dpm_adaptive_params* params, int64_t batch, float* out, float* ctx_out,
                                               mdt_dpm_adaptive_info* info, void* stream) {
-    return sample_dpm_adaptive_impl(m, {"mdt_sample_dpm_adaptive", nullptr, tokens, tokens2, goal, modality, x_T, batch, out, ctx_out,
-                                        stream}, sigma_min, sigma_max, params, info);
+    SamplerRequest r = {"mdt_sample_dpm_adaptive", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_dpm_adaptive_impl(m, r, sigma_min, sigma_max, params, info);
 }
 
 extern "C" mdt_status mdt_sample_dpm_adaptive_guided(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
                                                      int32_t modality, const float* x_T, float sigma_min, float sigma_max,
                                                      const mdt_dpm_adaptive_params* params, int64_t batch, float* out,
                                                      float* ctx_out, float cond_lambda, mdt_dpm_adaptive_info* info, void* stream) {
-    return sample_dpm_adaptive_impl(m, {"mdt_sample_dpm_adaptive_guided", &cond_lambda, tokens, tokens2, goal, modality, x_T, batch,
-                                        out, ctx_out, stream}, sigma_min, sigma_max, params, info);
+    SamplerRequest r = {"mdt_sample_dpm_adaptive_guided", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    return sample_dpm_adaptive_impl(m, r.weight(cond_lambda), sigma_min, sigma_max, params, info);
 }
 
 extern "C" mdt_status mdt_loss_fwd(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,

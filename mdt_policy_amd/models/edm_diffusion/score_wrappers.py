@@ -325,35 +325,21 @@ class GCDenoiser(nn.Module):
         im = self.inner_model
         if pin is not None and callable(getattr(pin, "on", None)):
             pin = pin.on(action.device, action.shape)
-        if bounds is not None or record or pin is not None:
-            if bounds is not None:
-                pair = bounds.clip_bounds(action.device) if callable(getattr(bounds, "clip_bounds", None)) else bounds
-                bounds = tuple(torch.as_tensor(b, dtype=torch.float32).to(action.device) for b in pair)
-            if tree is not None:
-                if kind != "dpmpp_sde" or noise is not None or n_steps is not None:
-                    raise ValueError("sample_native: tree noise is for 'dpmpp_sde' and takes no noise rows")
-                tree = (tuple(tree) + (0., 0.))[:4]
-            out, ctx, rec = self._engine(state=state).sample_native_opt(
-                _lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action, im._goals(goal, False), sigmas, noise,
-                n_steps=n_steps, cond_lambda=cond_lambda, tree=tree, bounds=bounds, record=record, pin=pin)
-            im.latent_encoder_emb = ctx
-            if not record:
-                return out
-            sigma, sigma_hat = _record_sigmas(kind, sigmas, n_steps, params)
-            return out, {"x": rec[:, 0], "denoised": rec[:, 1], "sigma": sigma, "sigma_hat": sigma_hat}
+        if bounds is not None:
+            pair = bounds.clip_bounds(action.device) if callable(getattr(bounds, "clip_bounds", None)) else bounds
+            bounds = tuple(torch.as_tensor(b, dtype=torch.float32).to(action.device) for b in pair)
         if tree is not None:
             if kind != "dpmpp_sde" or noise is not None or n_steps is not None:
                 raise ValueError("sample_native: tree noise is for 'dpmpp_sde' and takes no noise rows")
-            seeds, tol, lo, hi = (tuple(tree) + (0., 0.))[:4]
-            out, ctx = self._engine(state=state).sample_sde_tree(_lib.sampler_params(**params), state, action, im._goals(goal, False),
-                                                                 sigmas, seeds, tol, lo, hi, cond_lambda=cond_lambda)
-            im.latent_encoder_emb = ctx
-            return out
-        out, ctx = self._engine(state=state).sample_native(_lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action,
-                                                           im._goals(goal, False), sigmas, noise, n_steps=n_steps,
-                                                           cond_lambda=cond_lambda)
+            tree = (tuple(tree) + (0., 0.))[:4]
+        out, ctx, rec = self._engine(state=state).sample_native(
+            _lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action, im._goals(goal, False), sigmas, noise,
+            n_steps=n_steps, cond_lambda=cond_lambda, tree=tree, bounds=bounds, record=record, pin=pin)
         im.latent_encoder_emb = ctx
-        return out
+        if not record:
+            return out
+        sigma, sigma_hat = _record_sigmas(kind, sigmas, n_steps, params)
+        return out, {"x": rec[:, 0], "denoised": rec[:, 1], "sigma": sigma, "sigma_hat": sigma_hat}
 
     @torch.no_grad()
     def sample_dpm_adaptive_native(self, state, action, goal, sigma_min, sigma_max, cond_lambda=None, **params):
@@ -378,10 +364,9 @@ class GCDenoiser(nn.Module):
         if record:
             raise NotImplementedError("sample_ddim keeps no per-step record; run the host loop with a callback")
         im = self.inner_model
-        kw = {}
-        if pin is not None:
-            kw["pin"] = pin.on(action.device, action.shape) if callable(getattr(pin, "on", None)) else pin
-        out, ctx = self._engine(state=state).sample_ddim(state, action, im._goals(goal, False), sigmas,
-                                                         cond_lambda=cond_lambda, **kw)
+        if pin is not None and callable(getattr(pin, "on", None)):
+            pin = pin.on(action.device, action.shape)
+        out, ctx = self._engine(state=state).sample_ddim(state, action, im._goals(goal, False), sigmas, cond_lambda=cond_lambda,
+                                                         pin=pin)
         im.latent_encoder_emb = ctx
         return out

@@ -16,6 +16,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import operator
+from types import SimpleNamespace
 from typing import Dict, Optional
 
 import torch
@@ -58,17 +59,6 @@ def rollout_controls(cond_lambda=None, pin=None, **other):
     return native, lam, pin
 
 
-# the C entry points of each sampler family as [device schedule][guided]
-_SAMPLER_ENTRIES = {
-    "ddim": (("mdt_sample_ddim", "mdt_sample_ddim_guided"), ("mdt_sample_ddim_dev", "mdt_sample_ddim_dev_guided")),
-    "plan": (("mdt_sample", "mdt_sample_guided"), ("mdt_sample_dev", "mdt_sample_dev_guided")),
-    "plan_opt": (("mdt_sample_opt",), ("mdt_sample_dev_opt",)),  # the guidance weight rides in mdt_sample_opts
-    "ddim_opt": (("mdt_sample_ddim_opt",), ("mdt_sample_ddim_dev_opt",)),
-    "dpm_adaptive": (("mdt_sample_dpm_adaptive", "mdt_sample_dpm_adaptive_guided"),),
-    "sde_tree": (("mdt_sample_sde_tree", "mdt_sample_sde_tree_guided"), ("mdt_sample_sde_tree_dev", "mdt_sample_sde_tree_dev_guided")),
-}
-
-
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -102,7 +92,6 @@ class HipEngine:
         self.Te = int(self.sigma_in_context) + int(self.has_goal_token) + (cfg.n_obs_token if cfg.arch == 0 else 2) + \
             int(self.proprio)
         self.Ta, self.A, self.D = cfg.action_seq_len, cfg.action_dim, cfg.embed_dim
-        self._entries = {fam: tuple(tuple(getattr(self.lib, n) for n in pair) for pair in e) for fam, e in _SAMPLER_ENTRIES.items()}
 
     def __del__(self):
         try:
@@ -287,40 +276,54 @@ class HipEngine:
                                         _ptr(s), B, _ptr(out), _ptr(ctx), self._stream())
         return out, ctx
 
-    def _sample(self, family: str, state: dict, x_T: torch.Tensor, goal: torch.Tensor, cond_lambda, lead=(), sigmas=None,
-                n_steps: Optional[int] = None, noise: Optional[torch.Tensor] = None, rows: bool = False, tail=(), tree=None):
-        """The steps every sampler call shares: the inputs, the outputs, the schedule and the entry point of ``family``
-        (_SAMPLER_ENTRIES).  The C arguments are the inputs, ``lead``, the schedule (if ``sigmas`` is given) and its count (one less
-        than the levels, or ``n_steps``), the noise rows (``rows``: None or (n_noise, B, Ta, A)) or the tree (``tree``: an
-        _lib.BrownianSource), B, out, ctx, the weight of a guided call, ``tail`` and the stream.  A device schedule is read in place (no copy to the host, no synchronisation)."""
-        lam = guidance(cond_lambda)[1]
+    # -- the sampler calls: one path to C.  mdt_sample_opt / mdt_sample_ddim_opt (and their _dev forms) state every other entry --
+    def _sampler_inputs(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas=None, n_steps: Optional[int] = None,
+                        noise: Optional[torch.Tensor] = None):
+        """What every sampler call starts from, once: the parameters in sync, the inputs as the C ABI takes them (tok, tok2, g,
+        x, and nz: ``noise`` as (n_noise, B, Ta, A) or None), the outputs (out, ctx) and the schedule -- sig, its C argument
+        sig_arg, dev (on the device: read in place, no copy to the host, no synchronisation) and n (one less than the levels, or
+        ``n_steps``).  The caller holds the result until its C call has returned: a converted input lives nowhere else, and
+        what the enqueued kernels read must not go back to the allocator before they are enqueued.  Bumps ctx_generation."""
         self.sync_params()
-        tok, tok2, B = self._tokens(state)
-        g, x_ = self._goal(goal, B), self._in(x_T, (B, self.Ta, self.A))
-        nz = None if noise is None else self._in(noise, (-1, B, self.Ta, self.A))
-        out = torch.empty((B, self.Ta, self.A), device=self.device, dtype=torch.float32)
-        ctx = torch.empty((B, self.Te, self.D), device=self.device, dtype=torch.float32)
-        dev = False
+        p = SimpleNamespace(modality=self._modality(state), sig=None, sig_arg=None, dev=False, n=None)
+        p.tok, p.tok2, p.B = self._tokens(state)
+        p.g, p.x = self._goal(goal, p.B), self._in(x_T, (p.B, self.Ta, self.A))
+        p.nz = None if noise is None else self._in(noise, (-1, p.B, self.Ta, self.A))
+        p.out = torch.empty((p.B, self.Ta, self.A), device=self.device, dtype=torch.float32)
+        p.ctx = torch.empty((p.B, self.Te, self.D), device=self.device, dtype=torch.float32)
         if sigmas is not None:
-            dev = torch.is_tensor(sigmas) and sigmas.device.type == "cuda"
-            if dev:
-                sig = self._in(sigmas.reshape(-1))
-                levels, arg = sig.numel(), sig.data_ptr()
+            p.dev = torch.is_tensor(sigmas) and sigmas.device.type == "cuda"
+            if p.dev:
+                p.sig = self._in(sigmas.reshape(-1))
+                levels, p.sig_arg = p.sig.numel(), p.sig.data_ptr()
             else:
                 vals = [float(v) for v in (sigmas.detach().tolist() if torch.is_tensor(sigmas) else sigmas)]
                 levels = len(vals)
-                sig = arg = (C.c_float * levels)(*vals)
-            lead += (arg, levels - 1 if n_steps is None else int(n_steps))
-            self._keep = (sig, nz)  # the kernels that read them are only enqueued: keep the (possibly converted) inputs alive
-        if rows:
-            lead += (_ptr(nz), 0 if nz is None else nz.shape[0])
-        if tree is not None:
-            lead += (C.byref(tree),)
-        fn = self._entries[family][dev][lam is not None]
+                p.sig = p.sig_arg = (C.c_float * levels)(*vals)
+            p.n = levels - 1 if n_steps is None else int(n_steps)
         self.ctx_generation += 1
-        _lib.call(fn, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_), *lead, B, _ptr(out), _ptr(ctx),
-                  *(() if lam is None else (lam,)), *tail, self._stream())
-        return out, ctx
+        return p
+
+    def _opts(self, B: int, cond_lambda=None, bounds=None, record=None, tree=None, pin=None):
+        """mdt_sample_opts of a call as (the C argument, what it points to).  Nothing asked for: (None, ()), the entries' NULL --
+        the plain call, and no struct is built for it.  ``bounds`` (lo, hi): fp32 (A,) tensors on the device; ``record``: the
+        (steps, 2, B, Ta, A) tensor to fill; ``tree``: (seeds, tol, lo, hi); ``pin``: (known, keep), fp32 (B, Ta, A) on the device."""
+        lam = guidance(cond_lambda)[1]
+        if lam is None and bounds is None and record is None and tree is None and pin is None:
+            return None, ()
+        lo = hi = src = seeds = known = keep = None
+        if pin is not None:
+            known, keep = self._pin(pin, B)
+        if bounds is not None:
+            lo, hi = (self._in(b, (self.A,)) for b in bounds)
+        if tree is not None:
+            seeds = tree[0]
+            if seeds.device != self.device or seeds.dtype != torch.int64 or not seeds.is_contiguous():
+                raise ValueError("sample_native: seeds must be a contiguous int64 tensor on the model's device")
+            src = _lib.BrownianSource(seeds.data_ptr(), int(seeds.numel()), 0, float(tree[2]), float(tree[3]), float(tree[1]))
+        opts = _lib.SampleOpts(C.sizeof(_lib.SampleOpts), 1.0 if lam is None else lam, _ptr(lo), _ptr(hi), _ptr(record),
+                               None if src is None else C.pointer(src), _ptr(known), _ptr(keep))
+        return C.byref(opts), (opts, lo, hi, src, seeds, known, keep)
 
     def _pin(self, pin, B: int):
         """A pin's (known, keep) as the C ABI takes them: contiguous fp32 (B, Ta, A) on the device (a float's alignment will do)."""
@@ -336,81 +339,58 @@ class HipEngine:
 
     def sample_ddim(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, cond_lambda: Optional[float] = None,
                     pin=None):
-        """Fused sampler call.  ``sigmas`` may live on the host (gc_sampling's default) or on the model's device --
-        the agent builds its schedule there (mdtv_agent.py:660-667); a device schedule is consumed in place
-        (mdt_sample_ddim_dev): no copy to the host, no synchronisation.  ``cond_lambda`` (not None or 1): classifier-free
-        guidance, mdt_sample_ddim_guided / mdt_sample_ddim_dev_guided.  ``pin``: None or (known, keep), fp32 (B, Ta, A) tensors on
-        the device, read when the kernels run -- pinned actions, mdt_sample_ddim_opt / mdt_sample_ddim_dev_opt; without one the
-        call is the one it was."""
-        if pin is None:
-            return self._sample("ddim", state, x_T, goal, cond_lambda, sigmas=sigmas)
-        lam = guidance(cond_lambda)[1]
-        known, keep = self._pin(pin, x_T.shape[0])
-        opts = _lib.SampleOpts(C.sizeof(_lib.SampleOpts), 1.0 if lam is None else lam, None, None, None, None, _ptr(known),
-                               _ptr(keep))
-        out = self._sample("ddim_opt", state, x_T, goal, None, sigmas=sigmas, tail=(C.byref(opts),))
-        self._keep = self._keep + (known, keep)
-        return out
+        """Fused sampler call (mdt_sample_ddim_opt / mdt_sample_ddim_dev_opt).  ``sigmas`` may live on the host (gc_sampling's
+        default) or on the model's device -- the agent builds its schedule there (mdtv_agent.py:660-667); a device schedule is
+        consumed in place: no copy to the host, no synchronisation.  ``cond_lambda`` (not None or 1): classifier-free guidance.
+        ``pin``: None or (known, keep), fp32 (B, Ta, A) tensors on the device, read when the kernels run -- pinned actions.
+        Without either the call passes no options: the plain mdt_sample_ddim call."""
+        opts, held = self._opts(x_T.shape[0], cond_lambda, pin=pin)
+        p = self._sampler_inputs(state, x_T, goal, sigmas)
+        self._keep = (p.sig, None) + held  # the kernels that read them are only enqueued
+        _lib.call(self.lib.mdt_sample_ddim_dev_opt if p.dev else self.lib.mdt_sample_ddim_opt, self.handle, _ptr(p.tok),
+                  _ptr(p.tok2), _ptr(p.g), p.modality, _ptr(p.x), p.sig_arg, p.n, p.B, _ptr(p.out), _ptr(p.ctx), opts, self._stream())
+        return p.out, p.ctx
 
     def sample_native(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
-                      noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cond_lambda: Optional[float] = None):
-        """One call of another sampler (mdt_sample / mdt_sample_dev): ``kind`` an mdt_sampler_kind, ``params`` an
+                      noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cond_lambda: Optional[float] = None,
+                      tree=None, bounds=None, record: bool = False, pin=None):
+        """One call of another sampler (mdt_sample_opt / mdt_sample_dev_opt): ``kind`` an mdt_sampler_kind, ``params`` an
         _lib.SamplerParams, ``noise`` None or (n_noise, B, Ta, A) in the Python loop's draw order, ``n_steps`` None (one less
         than the levels) or dpm_fast's evaluation count.  Like sample_ddim, a device schedule is read in place (no copy, no
-        synchronisation).  ``cond_lambda`` (not None or 1): classifier-free guidance (mdt_sample_guided / mdt_sample_dev_guided)."""
-        return self._sample("plan", state, x_T, goal, cond_lambda, (int(kind), C.byref(params)), sigmas, n_steps, noise, rows=True)
-
-    def sample_native_opt(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
-                          noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None,
-                          cond_lambda: Optional[float] = None, tree=None, bounds=None, record: bool = False, pin=None):
-        """sample_native / sample_sde_tree with action bounds and / or a per-step record (mdt_sample_opt / mdt_sample_dev_opt):
-        ``bounds`` None or (lo, hi), fp32 (A,) tensors on the device, read when the kernels run (a captured call reads what they
-        hold at replay); ``record``: the call also returns the (steps, 2, B, Ta, A) record -- [i][0] the input of step i's first
-        evaluation, [i][1] its denoised output; ``tree``: None or (seeds, tol, lo, hi) as in sample_sde_tree; ``pin``: None or
-        (known, keep), fp32 (B, Ta, A) tensors on the device, read when the kernels run -- the denoised value of every evaluation
-        becomes keep * known + (1 - keep) * D (the record then holds that).  Returns (out, ctx, record or None).  Capture-safe
-        like sample_native."""
-        lam = guidance(cond_lambda)[1]
-        lo = hi = rec = src = known = keep = None
-        if pin is not None:
-            known, keep = self._pin(pin, x_T.shape[0])
-        if bounds is not None:
-            lo, hi = (self._in(b, (self.A,)) for b in bounds)
-        if tree is not None:
-            seeds = tree[0]
-            if seeds.device != self.device or seeds.dtype != torch.int64 or not seeds.is_contiguous():
-                raise ValueError("sample_native_opt: seeds must be a contiguous int64 tensor on the model's device")
-            src = _lib.BrownianSource(seeds.data_ptr(), int(seeds.numel()), 0, float(tree[2]), float(tree[3]), float(tree[1]))
+        synchronisation).  ``cond_lambda`` (not None or 1): classifier-free guidance.  ``tree``: None or (seeds, tol, lo, hi) --
+        dpmpp_sde with Brownian-tree noise drawn inside the call: ``seeds`` an int64 tensor of 1 or B keys on the device, ``tol``
+        the tree's resolution, ``lo`` < ``hi`` its interval (0, 0: the schedule's smallest positive and largest level).
+        ``bounds``: None or (lo, hi), fp32 (A,) tensors on the device, read when the kernels run (a captured call reads what they
+        hold at replay); ``record``: the call also fills the (steps, 2, B, Ta, A) record -- [i][0] the input of step i's first
+        evaluation, [i][1] its denoised output; ``pin``: None or (known, keep), fp32 (B, Ta, A) tensors on the device, read when
+        the kernels run -- the denoised value of every evaluation becomes keep * known + (1 - keep) * D (the record then holds
+        that).  Returns (out, ctx, record or None).  Capture-safe."""
+        rec = None
         if record:
             steps = len(sigmas) - 1 if n_steps is None else int(n_steps) // 3 + 1  # n_steps: dpm_fast's evaluation count
             rec = torch.empty((steps, 2, x_T.shape[0], self.Ta, self.A), device=self.device, dtype=torch.float32)
-        opts = _lib.SampleOpts(C.sizeof(_lib.SampleOpts), 1.0 if lam is None else lam, _ptr(lo), _ptr(hi), _ptr(rec),
-                               None if src is None else C.pointer(src), _ptr(known), _ptr(keep))
-        out, ctx = self._sample("plan_opt", state, x_T, goal, None, (int(kind), C.byref(params)), sigmas, n_steps, noise, rows=True,
-                                tail=(C.byref(opts),))
-        self._keep = self._keep + (lo, hi, src, None if tree is None else tree[0], known, keep)
-        return out, ctx, rec
-
-    def sample_sde_tree(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, seeds: torch.Tensor, tol: float,
-                        lo: float = 0., hi: float = 0., cond_lambda: Optional[float] = None):
-        """dpmpp_sde with Brownian-tree noise drawn inside the call (mdt_sample_sde_tree / _dev / _guided / _dev_guided):
-        ``seeds`` an int64 tensor of 1 or B keys on the device, ``tol`` the tree's resolution, ``lo`` < ``hi`` its interval (0, 0:
-        the schedule's smallest positive and largest level).  Capture-safe like sample_native."""
-        if seeds.device != self.device or seeds.dtype != torch.int64 or not seeds.is_contiguous():
-            raise ValueError("sample_sde_tree: seeds must be a contiguous int64 tensor on the model's device")
-        src = _lib.BrownianSource(seeds.data_ptr(), int(seeds.numel()), 0, float(lo), float(hi), float(tol))
-        out = self._sample("sde_tree", state, x_T, goal, cond_lambda, (C.byref(params),), sigmas, tree=src)
-        self._keep = self._keep + (seeds, src)
-        return out
+        opts, held = self._opts(x_T.shape[0], cond_lambda, bounds, rec, tree, pin)
+        p = self._sampler_inputs(state, x_T, goal, sigmas, n_steps, noise)
+        self._keep = (p.sig, p.nz) + held  # the kernels that read them are only enqueued
+        _lib.call(self.lib.mdt_sample_dev_opt if p.dev else self.lib.mdt_sample_opt, self.handle, _ptr(p.tok), _ptr(p.tok2),
+                  _ptr(p.g), p.modality, _ptr(p.x), int(kind), C.byref(params), p.sig_arg, p.n, _ptr(p.nz),
+                  0 if p.nz is None else p.nz.shape[0], p.B, _ptr(p.out), _ptr(p.ctx), opts, self._stream())
+        return p.out, p.ctx, rec
 
     def sample_dpm_adaptive(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigma_min: float, sigma_max: float,
                             cond_lambda: Optional[float] = None):
         """mdt_sample_dpm_adaptive (eta = 0): ``params`` an _lib.DpmAdaptiveParams.  Blocking: the call reads the step error
         back every step.  Returns (out, ctx, info dict).  ``cond_lambda`` (not None or 1): mdt_sample_dpm_adaptive_guided."""
+        lam = guidance(cond_lambda)[1]
         info = _lib.DpmAdaptiveInfo()
-        out, ctx = self._sample("dpm_adaptive", state, x_T, goal, cond_lambda, (float(sigma_min), float(sigma_max), C.byref(params)),
-                                tail=(C.byref(info),))
-        return out, ctx, {k: int(getattr(info, k)) for k in ("steps", "nfe", "n_accept", "n_reject")}
+        p = self._sampler_inputs(state, x_T, goal)
+        args = (self.handle, _ptr(p.tok), _ptr(p.tok2), _ptr(p.g), p.modality, _ptr(p.x), float(sigma_min), float(sigma_max),
+                C.byref(params), p.B, _ptr(p.out), _ptr(p.ctx))
+        if lam is None:
+            _lib.call(self.lib.mdt_sample_dpm_adaptive, *args, C.byref(info), self._stream())
+        else:
+            _lib.call(self.lib.mdt_sample_dpm_adaptive_guided, *args, lam, C.byref(info), self._stream())
+        return p.out, p.ctx, {k: int(getattr(info, k)) for k in ("steps", "nfe", "n_accept", "n_reject")}
 
     def loss_fwd(self, state: dict, action: torch.Tensor, goal: torch.Tensor, noise: torch.Tensor, sigma: torch.Tensor):
         self.sync_params()

@@ -19,6 +19,7 @@ import torch
 
 from mdt_policy_amd import _lib
 from mdt_policy_amd.utils.action_pin import ActionPin
+from tests import raw_sampler as raw
 from tests import test_action_pin as cpu
 from tests import test_gpu_guidance as guid
 from tests.helpers import ATOL, RTOL, assert_close, inputs_of
@@ -155,14 +156,21 @@ def test_device_schedule_with_a_pin(name, monkeypatch):
 
 
 # ---- 7: no pin in effect -> the bits of the call without -------------------------------------------------------------------------
-def _raw(model, state, x, goal, family, lead, opts, sig=None):
-    eng = model._engine(state=state)
-    return eng._sample(family, state, x, model.inner_model._goals(goal, False), None, lead, sched() if sig is None else sig, None,
-                       None, rows=family == "plan_opt", tail=(None if opts is None else C.byref(opts),))[0]
+def _raw(model, state, x, goal, family, lead, opts):
+    """The ``_opt`` entry of a family with ``opts`` (None: NULL); ``lead``: the plan family's kind and parameters."""
+    return raw.run({"ddim_opt": "mdt_sample_ddim_opt", "plan_opt": "mdt_sample_opt"}[family], model, state, x, goal, sched(),
+                   opts=opts, **lead)
+
+
+def _legacy(model, state, x, goal, name):
+    """The entry without options (mdt_sample_ddim / mdt_sample): what an ``_opt`` entry without a pin must equal, bit for bit."""
+    if name == "ddim":
+        return raw.run("mdt_sample_ddim", model, state, x, goal, sched())
+    return raw.run("mdt_sample", model, state, x, goal, sched(), **_plan_lead(name))
 
 
 def _plan_lead(name):
-    return (_lib.SAMPLER_KIND[name], C.byref(_lib.sampler_params(**KINDS[name])))
+    return dict(kind=name, params=KINDS[name])
 
 
 @pytest.mark.parametrize("name", ["ddim", "lms", "dpmpp_2m"])
@@ -171,16 +179,18 @@ def test_a_zero_keep_and_an_absent_pin_change_no_bit(name):
     zero = ActionPin(pin.known, torch.zeros(x.shape[1]))
     size = C.sizeof(_lib.SampleOpts)
     with torch.no_grad():
+        base = _legacy(model, state, x, goal, name)
         if name == "ddim":
-            base = model.sample_ddim(state, x, goal, sched())                  # mdt_sample_ddim: today's entry point
+            plain = model.sample_ddim(state, x, goal, sched())
             none = model.sample_ddim(state, x, goal, sched(), pin=zero)
-            null = _raw(model, state, x, goal, "ddim_opt", (), None)
-            empty = _raw(model, state, x, goal, "ddim_opt", (), _lib.SampleOpts(size, 1.0, None, None, None, None, None, None))
+            null = _raw(model, state, x, goal, "ddim_opt", {}, None)
+            empty = _raw(model, state, x, goal, "ddim_opt", {}, _lib.SampleOpts(size, 1.0, None, None, None, None, None, None))
         else:
-            base = model.sample_native(name, state, x, goal, sched(), **KINDS[name])   # mdt_sample
+            plain = model.sample_native(name, state, x, goal, sched(), **KINDS[name])
             none = model.sample_native(name, state, x, goal, sched(), pin=zero, **KINDS[name])
             null = _raw(model, state, x, goal, "plan_opt", _plan_lead(name), None)
             empty = _raw(model, state, x, goal, "plan_opt", _plan_lead(name), _lib.SampleOpts(size, 1.0, None, None, None, None))
+    assert torch.equal(plain, base), "the facade without a pin is not the plain entry"
     assert torch.equal(none, base), "an all-zero keep changed the result"
     assert torch.equal(null, base) and torch.equal(empty, base), "the opts entry without a pin is not the plain call"
 
@@ -293,7 +303,7 @@ def test_bad_pin_options_are_refused_and_the_handle_keeps_working():
            "opts.size": Opts(size - 8, 1.0, None, None, None, None, known.data_ptr(), keep.data_ptr())}
     good = Opts(size, 1.0, None, None, None, None, known.data_ptr(), keep.data_ptr())
     for field, opts in bad.items():
-        for family, lead in (("ddim_opt", ()), ("plan_opt", _plan_lead("lms"))):
+        for family, lead in (("ddim_opt", {}), ("plan_opt", _plan_lead("lms"))):
             if family == "plan_opt" and field in ("opts.record", "opts.tree"):
                 continue  # the plan entry takes a record; its tree refusal is test_gpu_sampler_bounds'
             with pytest.raises(_lib.MDTHipError) as err:
@@ -301,14 +311,13 @@ def test_bad_pin_options_are_refused_and_the_handle_keeps_working():
                     _raw(model, state, x, goal, family, lead, opts)
             assert err.value.status == 1 and field in str(err.value), f"{family} {field}: {err.value}"
         with torch.no_grad():
-            got = _raw(model, state, x, goal, "ddim_opt", (), good)
+            got = _raw(model, state, x, goal, "ddim_opt", {}, good)
         assert_close(got.cpu(), want.cpu(), what=f"ddim after the refused {field}")
     # the struct's size before the pin was appended: accepted, the two fields read as NULL whatever lies behind
     old = Opts(Opts.pin_known.offset, 1.0, None, None, None, None, 0xdead0, 0xbeef0)
     with torch.no_grad():
-        assert torch.equal(_raw(model, state, x, goal, "ddim_opt", (), old), model.sample_ddim(state, x, goal, sched()))
-        assert torch.equal(_raw(model, state, x, goal, "plan_opt", _plan_lead("lms"), old),
-                           model.sample_native("lms", state, x, goal, sched()))
+        assert torch.equal(_raw(model, state, x, goal, "ddim_opt", {}, old), _legacy(model, state, x, goal, "ddim"))
+        assert torch.equal(_raw(model, state, x, goal, "plan_opt", _plan_lead("lms"), old), _legacy(model, state, x, goal, "lms"))
         kl, ql = pin_l.on(x.device, x.shape)
         got = _raw(model, state, x, goal, "plan_opt", _plan_lead("lms"), Opts(size, 1.0, None, None, None, None, kl.data_ptr(),
                                                                               ql.data_ptr()))
@@ -316,7 +325,7 @@ def test_bad_pin_options_are_refused_and_the_handle_keeps_working():
     # lo / hi on the DDIM entry are accepted and not read
     lo = torch.zeros(x.shape[-1], device="cuda")
     with torch.no_grad():
-        got = _raw(model, state, x, goal, "ddim_opt", (), Opts(size, 1.0, lo.data_ptr(), lo.data_ptr(), None, None, known.data_ptr(),
+        got = _raw(model, state, x, goal, "ddim_opt", {}, Opts(size, 1.0, lo.data_ptr(), lo.data_ptr(), None, None, known.data_ptr(),
                                                                 keep.data_ptr()))
     assert_close(got.cpu(), want.cpu(), what="ddim, bounds not read")
 
@@ -330,7 +339,7 @@ def test_a_pin_may_be_a_slice_of_a_larger_tensor():
     opts = _lib.SampleOpts(C.sizeof(_lib.SampleOpts), 1.0, None, None, None, None, both.data_ptr() + 4,
                            both.data_ptr() + 4 + 4 * known.numel())
     with torch.no_grad():
-        got = _raw(model, state, x, goal, "ddim_opt", (), opts)
+        got = _raw(model, state, x, goal, "ddim_opt", {}, opts)
     assert_close(got.cpu(), want.cpu(), what="ddim, pin in a slice")
 
 

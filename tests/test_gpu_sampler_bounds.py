@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from mdt_policy_amd import _lib
+from tests import raw_sampler as raw
 from tests.helpers import ATOL, RTOL, assert_close, cfg_of, inputs_of, load_fixture, params_of
 
 pytestmark = pytest.mark.gpu
@@ -160,12 +161,11 @@ def test_infinite_bounds_and_null_opts_change_no_bit(name):
     sig, noise, kw = sched(), _rows(name, x), KINDS[name]
     inf = torch.full((x.shape[-1],), math.inf)
     with torch.no_grad():
-        base = model.sample_native(name, state, x, goal, sig, noise=noise, **kw)
+        base = raw.run("mdt_sample", model, state, x, goal, sig, kind=name, params=kw, noise=noise)  # the entry without options
+        plain = model.sample_native(name, state, x, goal, sig, noise=noise, **kw)
         wide = model.sample_native(name, state, x, goal, sig, noise=noise, bounds=(-inf, inf), **kw)
-        eng = model._engine(state=state)
-        null_opts, _ = eng._sample("plan_opt", state, x, model.inner_model._goals(goal, False), None,
-                                   (_lib.SAMPLER_KIND[name], C.byref(_lib.sampler_params(**kw))), sig, None, noise, rows=True,
-                                   tail=(None,))
+        null_opts = raw.run("mdt_sample_opt", model, state, x, goal, sig, kind=name, params=kw, noise=noise, opts=None)
+    assert torch.equal(plain, base), "sample_native without options is not mdt_sample"
     assert torch.equal(wide, base), "bounds of (-inf, +inf) changed the result"
     assert torch.equal(null_opts, base), "mdt_sample_opt(opts = NULL) is not mdt_sample"
 
@@ -312,10 +312,7 @@ def test_guided_record_holds_the_combined_denoiser():
 
 # ---- 9: refusals ------------------------------------------------------------------------------------------------------------
 def _raw(model, state, x, goal, kind, opts):
-    eng = model._engine(state=state)
-    return eng._sample("plan_opt", state, x, model.inner_model._goals(goal, False), None,
-                       (_lib.SAMPLER_KIND[kind], C.byref(_lib.sampler_params())), sched(), None, None, rows=True,
-                       tail=(C.byref(opts),))[0]
+    return raw.run("mdt_sample_opt", model, state, x, goal, sched(), kind=kind, opts=opts)
 
 
 def test_bad_options_are_refused_and_the_handle_keeps_working():

@@ -1,6 +1,7 @@
 """Cost of pinned actions on the GPU, in one process: ms per host-synchronised call of 10-step sample_ddim (MDT-V d = 384,
-synthetic 'rich' weights) at B = 1 (rollout size, graph-replayed from the third identical call on, calls back to back) and at
-B = 256, without a pin and with one (extra_args={"pin": ActionPin.overlap(...)}: 2 B Ta A floats more read per step).
+synthetic 'rich' weights) at B = 1 (rollout size, graph-replayed from the third identical call on, calls back to back; and
+eager, GCDenoiser.sample_ddim itself, where the host's work per call shows) and at B = 256, without a pin and with one
+(extra_args={"pin": ActionPin.overlap(...)}: 2 B Ta A floats more read per step).
 
     python tools/pin_latency.py [--iters 400] [--passes 3]
 The unpinned legs run on a tree without the feature too (the pinned legs are skipped there), which is how a commit is compared
@@ -49,36 +50,53 @@ def main():
                     if int(st[0, x, 1]) and int(st[1, x, 1]) and int(st[1, x, 1] - st[0, x, 1]) > 0))
         return round(v[len(v) // 2]) if v else None
 
-    def timed(B, iters, pinned):
+    def timed(B, iters, pinned, eager=False):
         state, x, goal = inputs(B)
         kw = {"extra_args": {"pin": ActionPin.overlap(x / 80.0, executed=4, hard=2, soft=3)}} if pinned else {}
+        call = (lambda: model.sample_ddim(state, x, goal, sig)) if eager else (lambda: gs.sample_ddim(model, state, x, goal, sig, **kw))
         with torch.no_grad():
             for _ in range(5):  # warm-up: the auto rule captures the graph on the third identical call
-                gs.sample_ddim(model, state, x, goal, sig, **kw)
+                call()
             stamps = torch.zeros(2, 16, dtype=torch.int64, device="cuda")
             stream = torch.cuda.current_stream().cuda_stream
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             _lib.check(_lib.load().mdt_op_clock_stamp(stamps[0].data_ptr(), stream))
             for _ in range(iters):
-                gs.sample_ddim(model, state, x, goal, sig, **kw)
+                call()
             _lib.check(_lib.load().mdt_op_clock_stamp(stamps[1].data_ptr(), stream))
             torch.cuda.synchronize()
         return (time.perf_counter() - t0) / iters * 1e3, mhz(stamps)
 
-    legs = [("b1_unpinned", 1, args.iters, False), ("b256_unpinned", 256, max(10, args.iters // 4), False)]
+    def host_us(iters):
+        """The eager B = 1 call's host path alone: the stream is drained before every call and only the call's own return is
+        timed (Python, ctypes and the enqueue; nothing of the GPU's).  The median over the calls, in microseconds."""
+        state, x, goal = inputs(1)
+        ts = []
+        with torch.no_grad():
+            for i in range(iters + 20):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                model.sample_ddim(state, x, goal, sig)
+                ts.append(time.perf_counter() - t0)
+        return round(sorted(ts[20:])[iters // 2] * 1e6, 1)
+
+    legs = [("b1_unpinned", 1, args.iters, False), ("b1_eager", 1, args.iters, False, True),
+            ("b256_unpinned", 256, max(10, args.iters // 4), False)]
     if ActionPin is not None:
         legs += [("b1_pinned", 1, args.iters, True), ("b256_pinned", 256, max(10, args.iters // 4), True)]
     res = {name: [] for name, *_ in legs}
     clk = {name: [] for name, *_ in legs}
     for _ in range(args.passes):  # the legs alternate: other work shares the host
-        for name, B, n, pinned in legs:
-            ms, f = timed(B, n, pinned)
+        for name, *leg in legs:
+            ms, f = timed(*leg)
             res[name].append(round(ms, 4))
             clk[name].append(f)
     for k, v in res.items():
         print(f"{k:16s} " + " ".join(f"{ms:8.4f}" for ms in v) + " ms per call   " + " ".join(str(f) for f in clk[k]) + " MHz")
-    print(json.dumps(dict(res, mhz=clk)))
+    host = [host_us(max(100, args.iters // 5)) for _ in range(args.passes)]
+    print("b1_eager_host    " + " ".join(f"{us:8.1f}" for us in host) + " us of host time per call (stream drained before each)")
+    print(json.dumps(dict(res, mhz=clk, b1_eager_host_us=host)))
 
 
 if __name__ == "__main__":
