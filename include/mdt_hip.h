@@ -120,7 +120,9 @@ mdt_status mdt_load_param(mdt_model *m, const char *name, const float *src, int6
 mdt_status mdt_load_params(mdt_model *m, int32_t n, const char *const *names, const float *const *srcs,
                            const int64_t *numels, void *stream);
 
-/* Pre-size the workspace for batches up to max_batch (avoids hipMalloc later, e.g. before graph capture). */
+/* Pre-size the workspace for batches up to max_batch (avoids hipMalloc later, e.g. before graph capture).  A sampler call needs
+ * its decoder samples: batch, 2 * batch when guided; a *_multi call (below) batch * candidates chunks, 2 * batch * candidates when
+ * guided -- reserve that before capturing one. */
 mdt_status mdt_reserve(mdt_model *m, int64_t max_batch);
 
 /* Number of times the workspace was (re)allocated.  A captured HIP graph of a sampler call holds workspace addresses: it
@@ -337,6 +339,38 @@ mdt_status mdt_sample_ddim_opt(mdt_model *m, const float *tokens, const float *t
 mdt_status mdt_sample_ddim_dev_opt(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
                                    const float *x_T, const float *sigmas_dev, int32_t n_steps, int64_t batch, float *out,
                                    float *ctx_out, const mdt_sample_opts *opts, void *stream);
+
+/* Several action chunks per observation from one shared context: the *_opt call of each family with `candidates` = K >= 1 chunks
+ * for each of the `batch` = B observations (best-of-N with a critic, the chunk most coherent with a pinned one, the spread over
+ * chunks as an uncertainty signal).  Still ONE enqueue.  What does not depend on the noisy actions -- the guide staging, the
+ * encoder, the stacked cross K|V product, the fold of the collapsed cross-attention -- runs on the B observations (2B when
+ * guided); the decoder blocks and every head run on the B * K chunks (2 B K decoder samples when guided).
+ * Layout, observation-major: chunk k of observation b is sample b * K + k.
+ *   per chunk       : x_T and out (B * K, Ta, A); the noise rows (n_noise, B * K, Ta, A); opts.pin_known / pin_keep (B * K, Ta, A);
+ *                     opts.record (steps, 2, B * K, Ta, A); opts.tree's seeds (n_seeds = 1 or B * K)
+ *   per observation : tokens, tokens2, goal; ctx_out (B, Te, d)
+ * Guided, the decoder runs [B K conditional | B K unconditional] samples over the contexts [B conditional | B unconditional]:
+ * decoder sample s reads context s / K in either half.  Every option means what it means in the *_opt call, per chunk.
+ * candidates == 1 enqueues exactly the launches of the *_opt entry and gives its bits.  Before anything is enqueued,
+ * MDT_ERR_INVALID_ARG with the entry and the field in the message: candidates < 1; a batch * candidates (doubled when guided)
+ * beyond what the decoder's row counts hold.  The workspace grows for the decoder samples: a caller who captures the call
+ * reserves B * K first, 2 * B * K when guided (mdt_reserve).  The per-context buffers are carved at that size too and the call
+ * uses their first B (2B) entries.
+ * mdt_sample_dpm_adaptive has no such form (the Python facade's host loop expands the observations instead). */
+mdt_status mdt_sample_multi(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                            const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_host,
+                            int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, int32_t candidates, float *out,
+                            float *ctx_out, const mdt_sample_opts *opts, void *stream);
+mdt_status mdt_sample_dev_multi(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                                const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_dev,
+                                int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, int32_t candidates,
+                                float *out, float *ctx_out, const mdt_sample_opts *opts, void *stream);
+mdt_status mdt_sample_ddim_multi(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                                 const float *x_T, const float *sigmas_host, int32_t n_steps, int64_t batch, int32_t candidates,
+                                 float *out, float *ctx_out, const mdt_sample_opts *opts, void *stream);
+mdt_status mdt_sample_ddim_dev_multi(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                                     const float *x_T, const float *sigmas_dev, int32_t n_steps, int64_t batch,
+                                     int32_t candidates, float *out, float *ctx_out, const mdt_sample_opts *opts, void *stream);
 
 /* sample_dpm_adaptive (eta = 0): DPM-Solver-12 / -23 with the PID step-size control of _StepControl, as ONE blocking call.
  * Every attempted step runs its 2 or 3 denoiser evaluations; the head of the last one writes both the order-k ("high") and the

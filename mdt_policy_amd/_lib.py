@@ -244,6 +244,14 @@ SYMBOLS = [
     ("mdt_sample_ddim_opt", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(C.c_float), _I32, _I64, _VP, _VP, C.POINTER(SampleOpts),
                                    _VP]),
     ("mdt_sample_ddim_dev_opt", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _I64, _VP, _VP, C.POINTER(SampleOpts), _VP]),
+    # the *_opt calls with `candidates` chunks per observation, after `batch`
+    ("mdt_sample_multi", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, _VP, _I32,
+                                _I64, _I32, _VP, _VP, C.POINTER(SampleOpts), _VP]),
+    ("mdt_sample_dev_multi", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), _VP, _I32, _VP, _I32, _I64, _I32,
+                                    _VP, _VP, C.POINTER(SampleOpts), _VP]),
+    ("mdt_sample_ddim_multi", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(C.c_float), _I32, _I64, _I32, _VP, _VP,
+                                     C.POINTER(SampleOpts), _VP]),
+    ("mdt_sample_ddim_dev_multi", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _I64, _I32, _VP, _VP, C.POINTER(SampleOpts), _VP]),
     ("mdt_sampler_plan", _I32, [_I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, C.POINTER(SamplerPlan)]),
     ("mdt_sample_dpm_adaptive", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.c_float, C.c_float, C.POINTER(DpmAdaptiveParams), _I64,
                                        _VP, _VP, C.POINTER(DpmAdaptiveInfo), _VP]),

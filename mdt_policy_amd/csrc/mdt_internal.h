@@ -110,7 +110,10 @@ hipError_t mdt_launch_mlp_split(const mdt_gemm_args& fc, const mdt_gemm_args& pr
 hipError_t mdt_launch_pack_weight_split(const float* w, int n_rows, int K, void* image, hipStream_t s, int n_off = 0);
 // the same image from the fp32 fragment image of the weight (mdt_launch_pack_weight's output for the whole (N, K) matrix)
 hipError_t mdt_launch_split_from_packed(const float* wp, int N, int K, void* image, hipStream_t s);
-hipError_t mdt_launch_attention(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s);
+// ctx_div (here and in the three cross-attention launchers below; 1 = the plain launch): the launch's a.B samples are decoder
+// samples of which ctx_div consecutive ones share a context -- the candidates of a sampler call -- so sample b reads the k / v
+// rows (the folded operands U, Wf, c) of context b / ctx_div.  The public argument structs keep their layout.
+hipError_t mdt_launch_attention(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s, int ctx_div = 1);
 // one sample's self-attention fused into its output projection p (rollout batch 1); see mdt_kernels.hip
 bool mdt_attn_proj_supported(const mdt_gemm_args& p, int H, int hd, int T, int rope);
 hipError_t mdt_launch_attn_proj(const mdt_gemm_args& p, const float* qkv, int64_t ldq, int H, int hd, int T, int causal,
@@ -121,7 +124,7 @@ hipError_t mdt_launch_attn_proj_wide(const mdt_gemm_args& p, const float* qkv, i
 // one workgroup per sample: self-attention -> projection -> collapsed cross-attention (k_attn_xattn); x.y == p.out
 bool mdt_attn_xattn_supported(const mdt_gemm_args& p, const mdt_xapply_args& x, int H, int hd, int T, int causal, int rope);
 hipError_t mdt_launch_attn_xattn(const mdt_gemm_args& p, const float* qkv, int64_t ldq, const mdt_xapply_args& x, int H, int hd,
-                                 int T, hipStream_t s);
+                                 int T, hipStream_t s, int ctx_div = 1);
 // side jobs (mdt_kernels.hip): small-M products that ride in the launches of the small-M products that follow them
 hipError_t mdt_gemm_side_push(const mdt_gemm_args& a, hipStream_t s);
 hipError_t mdt_gemm_side_push_front(const mdt_gemm_args& a, hipStream_t s);
@@ -222,10 +225,10 @@ hipError_t mdt_launch_multi_load(const mdt_load_entry* tab, const int2* blocks, 
 hipError_t mdt_launch_transpose(const float* src, float* dst, int R, int Cc, hipStream_t s);
 hipError_t mdt_launch_xattn_fold(const mdt_xfold_args& a, hipStream_t s);
 hipError_t mdt_launch_xattn_fold_n(const mdt_xfold_args* sets, int n, hipStream_t s);  // equal shapes; one launch per 8 sets
-hipError_t mdt_launch_xattn_apply(const mdt_xapply_args& a, hipStream_t s);
+hipError_t mdt_launch_xattn_apply(const mdt_xapply_args& a, hipStream_t s, int ctx_div = 1);
 // the collapsed cross-attention + the LayerNorm-prologue Linear on its output rows in one launch (k_xattn_gemm_smallm)
 bool mdt_xattn_gemm_supported(const mdt_xapply_args& x, const mdt_gemm_args& g);
-hipError_t mdt_launch_xattn_gemm(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s);
+hipError_t mdt_launch_xattn_gemm(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s, int ctx_div = 1);
 bool mdt_xattn_apply_supported(int D, int H, int Te, int Ta);
 size_t mdt_xattn_lds_floats(int D, int H);  // LDS floats of the collapsed cross-attention body (xattn_tile)
 // ---- Perceiver resampler kernels ----

@@ -425,10 +425,15 @@ __global__ __launch_bounds__(512) void k_attn_proj_wide(mdt_gemm_args a, mdt_att
 // k_attn_xattn: one workgroup per SAMPLE through self-attention, its output projection and the collapsed cross-attention
 // (mdt_tiles.h: attn_xattn_tile) -- replaces k_attn_proj_wide + k_xattn_apply for batches of at most one sample per CU.
 // ------------------------------------------------------------------------------------------------
-template <int HD, int TKC>
-__global__ __launch_bounds__(512) void k_attn_xattn(mdt_gemm_args a, mdt_attn_pro at, mdt_xapply_args x, const float* __restrict__ zeros) {
+// CD (here and in the other kernels that read per-context operands): ctx_div decoder samples share one context -- the candidates
+// of a sampler call -- so sample b reads the operands of context b / ctx_div (ctx_context below).  The plain launch is the
+// CD = false instantiation, the code it has always been: it never reads ctx_div.
+template <int HD, int TKC, bool CD>
+__global__ __launch_bounds__(512) void k_attn_xattn(mdt_gemm_args a, mdt_attn_pro at, mdt_xapply_args x, const float* __restrict__ zeros,
+                                                    int ctx_div) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    attn_xattn_tile<HD, TKC, 32>(a, at, x, xcd_remap(blockIdx.x, gridDim.x), lds, zeros, threadIdx.x);
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    attn_xattn_tile<HD, TKC, 32>(a, at, x, b, ctx_context<CD>(b, ctx_div), lds, zeros, threadIdx.x);
 }
 
 // 256 KiB of zeros per device: stands in for absent bias / rowvec / LayerNorm-bias vectors.  ensure_zeros() points
@@ -673,14 +678,14 @@ static constexpr int GEMM_MID_MAX = 1400;  // rows up to which the 16 x 64 tiled
 // LayerNorm + modulate -> Linear that follows (mlp.c_fc) -- rollout batches: the cross-attention launch (one workgroup, 6.5 us
 // of latency per decoder block at B = 1) disappears into the c_fc launch, whose 96 workgroups each repeat it on the MFMA pipe
 // (48 MFMAs per wave, the sample's 98 KB of folded operands from L2); workgroup 0 writes the residual stream.
-template <int NPP>
-__global__ __launch_bounds__(512) void k_xattn_gemm_smallm(mdt_xapply_args x, mdt_gemm_args a, const float* __restrict__ zeros) {
+template <int NPP, bool CD>
+__global__ __launch_bounds__(512) void k_xattn_gemm_smallm(mdt_xapply_args x, mdt_gemm_args a, const float* __restrict__ zeros, int ctx_div) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float s_stat[32];
     __shared__ __attribute__((aligned(16))) float red[8 * 64 * 4];
     const int b = blockIdx.y, ys = x.D + 4;
     float* yo = lds;                       // [16][D + 4]: the sample's rows after the cross-attention
-    xattn_tile<NPP, false, false, 512, 0, true>(x, b, lds + 16 * ys, zeros, threadIdx.x, nullptr, 0, nullptr, yo, ys, blockIdx.x == 0);
+    xattn_tile<NPP, false, false, 512, 0, true>(x, b, ctx_context<CD>(b, ctx_div), lds + 16 * ys, zeros, threadIdx.x, nullptr, 0, nullptr, yo, ys, blockIdx.x == 0);
     __syncthreads();
     gemm_smallm_tile<false, true>(a, blockIdx.x, b * x.Ta, s_stat, red, zeros, threadIdx.x, yo, ys, x.Ta);
 }
@@ -788,20 +793,21 @@ bool mdt_attn_xattn_supported(const mdt_gemm_args& p, const mdt_xapply_args& x, 
 }
 
 template <int HD, int TKC>
-static hipError_t launch_attn_xattn_t(const mdt_gemm_args& p, const mdt_attn_pro& at, const mdt_xapply_args& x, hipStream_t s) {
+static hipError_t launch_attn_xattn_t(const mdt_gemm_args& p, const mdt_attn_pro& at, const mdt_xapply_args& x, hipStream_t s, int ctx_div) {
     const int D = 8 * HD;
     const size_t lds = ((size_t)16 * (D + 4) + (size_t)48 * (D + 16)) * sizeof(float);
-    return mdt_launch_lds<k_attn_xattn<HD, TKC>>(dim3(x.B), dim3(512), lds, s, p, at, x, g_zeros);
+    if (ctx_div > 1) return mdt_launch_lds<k_attn_xattn<HD, TKC, true>>(dim3(x.B), dim3(512), lds, s, p, at, x, g_zeros, ctx_div);
+    return mdt_launch_lds<k_attn_xattn<HD, TKC, false>>(dim3(x.B), dim3(512), lds, s, p, at, x, g_zeros, 1);
 }
 
 hipError_t mdt_launch_attn_xattn(const mdt_gemm_args& p, const float* qkv, int64_t ldq, const mdt_xapply_args& x, int H, int hd,
-                                 int T, hipStream_t s) {
-    if (!mdt_attn_xattn_supported(p, x, H, hd, T, 1, 0) || ldq != 3 * (int64_t)p.K) return hipErrorInvalidValue;
+                                 int T, hipStream_t s, int ctx_div) {
+    if (!mdt_attn_xattn_supported(p, x, H, hd, T, 1, 0) || ldq != 3 * (int64_t)p.K || ctx_div < 1) return hipErrorInvalidValue;
     hipError_t ze = ensure_zeros();
     if (ze != hipSuccess) return ze;
     mdt_attn_pro at;
     at.qkv = qkv; at.ldq = ldq; at.T = T; at.scale = 1.0f / sqrtf((float)hd);
-    return T <= 10 ? launch_attn_xattn_t<48, 10>(p, at, x, s) : launch_attn_xattn_t<48, 16>(p, at, x, s);
+    return T <= 10 ? launch_attn_xattn_t<48, 10>(p, at, x, s, ctx_div) : launch_attn_xattn_t<48, 16>(p, at, x, s, ctx_div);
 }
 
 // Side jobs: products that do not depend on the launches they are queued beside (and that nothing launched before
@@ -1115,14 +1121,15 @@ static hipError_t launch_gemm_merge(const mdt_gemm_args& a, hipStream_t s) {
 // registers.  10x10 / 10x4 / 4x4 score matrices are 0.1 % of the FLOPs, so this stays on the VALU.
 // ------------------------------------------------------------------------------------------------
 // body in mdt_tiles.h (attn_tile); gridDim.y workgroups share a sample, each taking H / gridDim.y heads
-template <int HD, int TKC, bool ROPE>
+// CD: the k / v rows are those of context b / ctx_div (cross-attention of a sampler call with candidates; see k_attn_xattn)
+template <int HD, int TKC, bool ROPE, bool CD>
 __global__ __launch_bounds__(256) void k_attn(mdt_attn_args a, const float* __restrict__ rope_cos,
-                                              const float* __restrict__ rope_sin, float scale) {
+                                              const float* __restrict__ rope_sin, float scale, int ctx_div) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // sample -> XCD as the GEMMs map row tiles -> XCD (xcd_remap): the q/k/v rows this workgroup reads were written
     // by GEMM tiles of the same XCD and the rows it writes are read there again (speed only)
     const int b = xcd_remap(blockIdx.x, gridDim.x);
-    attn_tile<HD, TKC, ROPE, false>(a, rope_cos, rope_sin, scale, b, blockIdx.y, gridDim.y, lds, threadIdx.x);
+    attn_tile<HD, TKC, ROPE, false>(a, rope_cos, rope_sin, scale, b, ctx_context<CD>(b, ctx_div), blockIdx.y, gridDim.y, lds, threadIdx.x);
 }
 
 // lanes per (head, query row): one per 16 (hd 16, 48) or 32 (hd 32, 64) dims of the head
@@ -1141,40 +1148,42 @@ static int attn_head_split(int H, int Tq, int hd, int B) {
 }
 
 template <int HD, int TKC, bool ROPE>
-static hipError_t launch_attn_tt(const mdt_attn_args& a, const float* rc, const float* rs, hipStream_t s) {
+static hipError_t launch_attn_tt(const mdt_attn_args& a, const float* rc, const float* rs, hipStream_t s, int ctx_div) {
     constexpr int LP = HD == 48 ? 3 : (HD >= 32 ? 2 : 1);
     const int hs = attn_head_split(a.H, a.Tq, HD, a.B);
     const int Hl = a.H / hs;
     const size_t lds = ((size_t)(a.Tq + 2 * a.Tk) * Hl * HD + (size_t)Hl * a.Tq * 16 * LP) * sizeof(float);
-    return mdt_launch_lds<k_attn<HD, TKC, ROPE>>(dim3(a.B, hs), dim3(256), lds, s, a, rc, rs, 1.0f / sqrtf((float)HD));
+    if (ctx_div > 1)
+        return mdt_launch_lds<k_attn<HD, TKC, ROPE, true>>(dim3(a.B, hs), dim3(256), lds, s, a, rc, rs, 1.0f / sqrtf((float)HD), ctx_div);
+    return mdt_launch_lds<k_attn<HD, TKC, ROPE, false>>(dim3(a.B, hs), dim3(256), lds, s, a, rc, rs, 1.0f / sqrtf((float)HD), 1);
 }
 
 template <int HD>
-static hipError_t launch_attn_t(const mdt_attn_args& a, const float* rc, const float* rs, hipStream_t s) {
+static hipError_t launch_attn_t(const mdt_attn_args& a, const float* rc, const float* rs, hipStream_t s, int ctx_div) {
     if constexpr (HD >= 32) {
         if (a.rope) {
-            if (a.Tk <= 4) return launch_attn_tt<HD, 4, true>(a, rc, rs, s);
-            if (a.Tk <= 10) return launch_attn_tt<HD, 10, true>(a, rc, rs, s);
-            return launch_attn_tt<HD, 16, true>(a, rc, rs, s);
+            if (a.Tk <= 4) return launch_attn_tt<HD, 4, true>(a, rc, rs, s, ctx_div);
+            if (a.Tk <= 10) return launch_attn_tt<HD, 10, true>(a, rc, rs, s, ctx_div);
+            return launch_attn_tt<HD, 16, true>(a, rc, rs, s, ctx_div);
         }
     }
-    if (a.Tk <= 4) return launch_attn_tt<HD, 4, false>(a, rc, rs, s);
-    if (a.Tk <= 10) return launch_attn_tt<HD, 10, false>(a, rc, rs, s);
-    return launch_attn_tt<HD, 16, false>(a, rc, rs, s);
+    if (a.Tk <= 4) return launch_attn_tt<HD, 4, false>(a, rc, rs, s, ctx_div);
+    if (a.Tk <= 10) return launch_attn_tt<HD, 10, false>(a, rc, rs, s, ctx_div);
+    return launch_attn_tt<HD, 16, false>(a, rc, rs, s, ctx_div);
 }
 
 hipError_t mdt_launch_attention(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin,
-                                hipStream_t s) {
-    if (a.H < 1 || a.Tq < 1 || a.Tq > 16 || a.Tk < 1 || a.Tk > 16) return hipErrorInvalidValue;
+                                hipStream_t s, int ctx_div) {
+    if (a.H < 1 || a.Tq < 1 || a.Tq > 16 || a.Tk < 1 || a.Tk > 16 || ctx_div < 1) return hipErrorInvalidValue;
     const int lp = attn_lanes(a.hd);
     const int Hl = a.H / attn_head_split(a.H, a.Tq, a.hd, a.B);  // heads of one workgroup
     const size_t need = ((size_t)(a.Tq + 2 * a.Tk) * Hl * a.hd + (size_t)Hl * a.Tq * 16 * lp) * sizeof(float);
     if (Hl * a.Tq * lp > 256 || need > 160 * 1024) return hipErrorInvalidValue;
     switch (a.hd) {
-        case 16: return launch_attn_t<16>(a, rope_cos, rope_sin, s);
-        case 32: return launch_attn_t<32>(a, rope_cos, rope_sin, s);
-        case 48: return launch_attn_t<48>(a, rope_cos, rope_sin, s);
-        case 64: return launch_attn_t<64>(a, rope_cos, rope_sin, s);
+        case 16: return launch_attn_t<16>(a, rope_cos, rope_sin, s, ctx_div);
+        case 32: return launch_attn_t<32>(a, rope_cos, rope_sin, s, ctx_div);
+        case 48: return launch_attn_t<48>(a, rope_cos, rope_sin, s, ctx_div);
+        case 64: return launch_attn_t<64>(a, rope_cos, rope_sin, s, ctx_div);
         default: return hipErrorInvalidValue;
     }
 }
@@ -1784,10 +1793,11 @@ hipError_t mdt_launch_xattn_fold_n(const mdt_xfold_args* sets, int n, hipStream_
 hipError_t mdt_launch_xattn_fold(const mdt_xfold_args& a, hipStream_t s) { return mdt_launch_xattn_fold_n(&a, 1, s); }
 
 // One workgroup (512 threads) per sample; body in mdt_tiles.h (xattn_tile)
-template <int NPP>
-__global__ __launch_bounds__(512) void k_xattn_apply(mdt_xapply_args a, const float* __restrict__ zeros) {
+template <int NPP, bool CD>
+__global__ __launch_bounds__(512) void k_xattn_apply(mdt_xapply_args a, const float* __restrict__ zeros, int ctx_div) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    xattn_tile<NPP, false>(a, xcd_remap(blockIdx.x, gridDim.x), lds, zeros, threadIdx.x);
+    const int b = xcd_remap(blockIdx.x, gridDim.x);
+    xattn_tile<NPP, false>(a, b, ctx_context<CD>(b, ctx_div), lds, zeros, threadIdx.x);
 }
 
 // which configurations the collapsed path covers (others keep the q GEMM + attention + c_proj GEMM sequence)
@@ -1810,25 +1820,29 @@ bool mdt_xattn_gemm_supported(const mdt_xapply_args& x, const mdt_gemm_args& g) 
            g.gout == 1 && g.goff == 0 && g.rows_per_sample == x.Ta;
 }
 template <int NPP>
-static hipError_t launch_xattn_gemm_t(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s) {
+static hipError_t launch_xattn_gemm_t(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s, int ctx_div) {
     const size_t lds = ((size_t)16 * (x.D + 4) + mdt_xattn_lds_floats(x.D, x.H)) * sizeof(float);
     // (up to 78 KB of dynamic LDS at d = 512)
-    return mdt_launch_lds<k_xattn_gemm_smallm<NPP>>(dim3(g.N >> 4, x.B), dim3(512), lds, s, x, g, g_zeros);
+    if (ctx_div > 1) return mdt_launch_lds<k_xattn_gemm_smallm<NPP, true>>(dim3(g.N >> 4, x.B), dim3(512), lds, s, x, g, g_zeros, ctx_div);
+    return mdt_launch_lds<k_xattn_gemm_smallm<NPP, false>>(dim3(g.N >> 4, x.B), dim3(512), lds, s, x, g, g_zeros, 1);
 }
-hipError_t mdt_launch_xattn_gemm(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s) {
-    if (!mdt_xattn_gemm_supported(x, g)) return hipErrorInvalidValue;
+hipError_t mdt_launch_xattn_gemm(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s, int ctx_div) {
+    if (!mdt_xattn_gemm_supported(x, g) || ctx_div < 1) return hipErrorInvalidValue;
     hipError_t e = ensure_zeros();
     if (e != hipSuccess) return e;
-    return x.H == 8 ? launch_xattn_gemm_t<32>(x, g, s) : launch_xattn_gemm_t<16>(x, g, s);
+    return x.H == 8 ? launch_xattn_gemm_t<32>(x, g, s, ctx_div) : launch_xattn_gemm_t<16>(x, g, s, ctx_div);
 }
 
-hipError_t mdt_launch_xattn_apply(const mdt_xapply_args& a, hipStream_t s) {
-    if (!mdt_xattn_apply_supported(a.D, a.H, a.Te, a.Ta)) return hipErrorInvalidValue;
+hipError_t mdt_launch_xattn_apply(const mdt_xapply_args& a, hipStream_t s, int ctx_div) {
+    if (!mdt_xattn_apply_supported(a.D, a.H, a.Te, a.Ta) || ctx_div < 1) return hipErrorInvalidValue;
     hipError_t e = ensure_zeros();
     if (e != hipSuccess) return e;
     const size_t lds = mdt_xattn_lds_floats(a.D, a.H) * sizeof(float);
-    if (a.H == 8) hipLaunchKernelGGL((k_xattn_apply<32>), dim3(a.B), dim3(512), lds, s, a, g_zeros);
-    else hipLaunchKernelGGL((k_xattn_apply<16>), dim3(a.B), dim3(512), lds, s, a, g_zeros);
+    if (ctx_div > 1) {
+        if (a.H == 8) hipLaunchKernelGGL((k_xattn_apply<32, true>), dim3(a.B), dim3(512), lds, s, a, g_zeros, ctx_div);
+        else hipLaunchKernelGGL((k_xattn_apply<16, true>), dim3(a.B), dim3(512), lds, s, a, g_zeros, ctx_div);
+    } else if (a.H == 8) hipLaunchKernelGGL((k_xattn_apply<32, false>), dim3(a.B), dim3(512), lds, s, a, g_zeros, 1);
+    else hipLaunchKernelGGL((k_xattn_apply<16, false>), dim3(a.B), dim3(512), lds, s, a, g_zeros, 1);
     return hipGetLastError();
 }
 

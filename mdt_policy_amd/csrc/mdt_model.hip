@@ -675,10 +675,10 @@ static int g_attn_xattn_min_rows() {
 static constexpr int64_t ATTN_XATTN_MAX_BATCH = 512;
 
 // `fx` (optional): the collapsed cross-attention that follows on the same rows; when the one-sample-per-workgroup kernel takes
-// both, *fused is set and the caller skips its own launch.
+// both, *fused is set and the caller skips its own launch.  ctx_div: how many consecutive samples share one of fx's contexts.
 static mdt_status run_self_attn(mdt_model* m, const EncBlock& e, const View& V, int64_t B, int T, bool causal,
                                 ModRef mr, hipStream_t s, Stream in = Stream(), const mdt_xapply_args* fx = nullptr,
-                                bool* fused = nullptr) {
+                                bool* fused = nullptr, int ctx_div = 1) {
     float* x = V.y;
     const int D = m->D, M = (int)(B * T);
     mdt_gemm_args g = gemm_args(x, D, e.qkv, V.qkv, 3 * D, M);
@@ -699,7 +699,7 @@ static mdt_status run_self_attn(mdt_model* m, const EncBlock& e, const View& V, 
     }
     if (fx && fused && M >= g_attn_xattn_min_rows() && B <= ATTN_XATTN_MAX_BATCH &&
         mdt_attn_xattn_supported(p, *fx, m->H, m->hd, T, causal, m->cfg.use_rot_embed)) {
-        LAUNCH(mdt_launch_attn_xattn(p, V.qkv, 3 * D, *fx, m->H, m->hd, T, s));
+        LAUNCH(mdt_launch_attn_xattn(p, V.qkv, 3 * D, *fx, m->H, m->hd, T, s, ctx_div));
         *fused = true;
         return MDT_OK;
     }
@@ -806,9 +806,9 @@ static inline mdt_status split_ready(mdt_model* m, int64_t rows, hipStream_t s) 
 // `out` (optional): when given and the fused launch applies, the sublayer's output is left as slabs in V.hid (described in
 // *out) and V.y is NOT updated -- the caller hands *out to the next reader; otherwise V.y is updated in place.
 // `pre_x` (optional; rollout batches): the collapsed cross-attention that is still to run on these rows -- it goes into the
-// c_fc launch (k_xattn_gemm_smallm); the caller has checked mdt_xattn_gemm_supported.
+// c_fc launch (k_xattn_gemm_smallm); the caller has checked mdt_xattn_gemm_supported.  ctx_div: samples per context of pre_x.
 static mdt_status run_mlp(mdt_model* m, const EncBlock& e, const View& V, int64_t B, int T, ModRef mr, hipStream_t s,
-                          Stream* out = nullptr, const mdt_xapply_args* pre_x = nullptr) {
+                          Stream* out = nullptr, const mdt_xapply_args* pre_x = nullptr, int ctx_div = 1) {
     float* x = V.y;
     const int D = m->D, M = (int)(B * T);
     mdt_gemm_args g = gemm_args(x, D, e.fc, V.hid, 4 * D, M);
@@ -845,7 +845,7 @@ static mdt_status run_mlp(mdt_model* m, const EncBlock& e, const View& V, int64_
         out->base = V.hid; out->parts = mdt_mlp_slices(D); out->stride = stride;
         return MDT_OK;
     }
-    if (pre_x) LAUNCH(mdt_launch_xattn_gemm(*pre_x, g, s));
+    if (pre_x) LAUNCH(mdt_launch_xattn_gemm(*pre_x, g, s, ctx_div));
     else LAUNCH(mdt_launch_gemm(g, s));
     LAUNCH(mdt_launch_gemm(p, s));
     return MDT_OK;
@@ -1015,8 +1015,11 @@ static int64_t cond_width(const mdt_model* m) {
 // (:335-341) or the plain cross-attending Block (:209-214), by m->cond
 // `fin` (optional): the caller's next reader (the action head) can sum MLP slabs itself; then the last block may leave its
 // output as slabs, described in *fin.  Without it the residual stream ends in V.y.
+// ctx_div (a sampler call with candidates; 1 otherwise): the B samples are chunks of which ctx_div consecutive ones share an
+// observation, and the encoder ran on the B / ctx_div contexts only -- sample b's cross-attention reads the K|V rows and the
+// folded operands of context b / ctx_div.  Everything else in a block is per row.
 static mdt_status run_decoder_blocks(mdt_model* m, const View& V, int64_t B, const float* mod_row, int64_t mod_stride,
-                                     hipStream_t s, Stream* fin = nullptr) {
+                                     hipStream_t s, Stream* fin = nullptr, int ctx_div = 1) {
     const int D = m->D, Ta = m->Ta, M = (int)(B * Ta);
     View W = V;  // W.y / W.att trade places whenever a block's cross-attention runs inside its c_fc launch (rollout batches)
     Stream cur;  // where the residual stream lives between blocks
@@ -1055,12 +1058,12 @@ static mdt_status run_decoder_blocks(mdt_model* m, const View& V, int64_t B, con
             if (!x_in_fc) x.y_out = nullptr;
         }
         bool xdone = false;
-        MDT_TRY(run_self_attn(m, d, W, B, Ta, true, ma, s, cur, m->xfold ? &x : nullptr, &xdone));
+        MDT_TRY(run_self_attn(m, d, W, B, Ta, true, ma, s, cur, m->xfold ? &x : nullptr, &xdone, ctx_div));
         cur = Stream();
         if (xdone) {
             // self-attention, projection and cross-attention went as one launch (one workgroup per sample)
         } else if (m->xfold) {
-            if (!x_in_fc) LAUNCH(mdt_launch_xattn_apply(x, s));
+            if (!x_in_fc) LAUNCH(mdt_launch_xattn_apply(x, s, ctx_div));
         } else {
             mdt_gemm_args q = gemm_args(W.y, D, d.xq, W.qx, D, M);
             q.ln = 1; q.ln_w = d.ln3_w; q.ln_b = d.ln3_b; q.rows_per_sample = Ta;
@@ -1073,13 +1076,13 @@ static mdt_status run_decoder_blocks(mdt_model* m, const View& V, int64_t B, con
             a.out = W.att; a.ldo = D; a.B = (int)B; a.H = m->H; a.hd = m->hd; a.Tq = Ta; a.Tk = m->Te;
             a.causal = 1;  // SDPA is_causal on a Ta x Te matrix: top-left aligned (transformer_blocks.py:204,142)
             a.rope = m->cfg.use_rot_embed;
-            LAUNCH(mdt_launch_attention(a, m->rope_cos, m->rope_sin, s));
+            LAUNCH(mdt_launch_attention(a, m->rope_cos, m->rope_sin, s, ctx_div));
             mdt_gemm_args p = gemm_args(W.att, D, d.xproj, W.y, D, M);
             p.residual = 1; p.rows_per_sample = Ta;
             LAUNCH(mdt_launch_gemm(p, s));
         }
         const bool last = l == m->Ld - 1;
-        MDT_TRY(run_mlp(m, d, W, B, Ta, mm, s, (!last || fin) ? &cur : nullptr, x_in_fc ? &x : nullptr));
+        MDT_TRY(run_mlp(m, d, W, B, Ta, mm, s, (!last || fin) ? &cur : nullptr, x_in_fc ? &x : nullptr, ctx_div));
         if (x_in_fc) std::swap(W.y, W.att);
     }
     if (fin) *fin = cur;
@@ -1129,12 +1132,13 @@ static mdt_status run_head(mdt_model* m, mdt_head_args h, const mdt_head_plan* p
 
 // One network evaluation on the embedded input in V.y: the decoder blocks at nb samples (conditioning rows from mod_row), then
 // the head `h` on their rows -- summing the MLP's slabs itself when it is the one-launch head.  sigma_next (not null): the next
-// input is embedded into V.y.
+// input is embedded into V.y.  ctx_div: samples per encoded context (run_decoder_blocks).
 static mdt_status run_eval(mdt_model* m, const View& V, int64_t nb, const float* mod_row, int64_t mod_stride, mdt_head_args h,
-                           const mdt_head_plan* pl, const float* sigma_next, hipStream_t s, mdt_guide gd, mdt_head_pin pn = {}) {
+                           const mdt_head_plan* pl, const float* sigma_next, hipStream_t s, mdt_guide gd, mdt_head_pin pn = {},
+                           int ctx_div = 1) {
     Stream fin;
     const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
-    MDT_TRY(run_decoder_blocks(m, V, nb, mod_row, mod_stride, s, head_sums ? &fin : nullptr));
+    MDT_TRY(run_decoder_blocks(m, V, nb, mod_row, mod_stride, s, head_sums ? &fin : nullptr, ctx_div));
     if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
     if (sigma_next) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
     return run_head(m, h, pl, V.hid, sigma_next, s, gd, pn);
@@ -1232,34 +1236,45 @@ struct SamplerRequest {
     mdt_sample_opts o = k_default_opts;  // as read_opts leaves them; o.cond_lambda != 1 is the guided call
     bool weight_given = false;  // a *_guided entry: guide_of's handle and weight checks come first, at lambda == 1 too
     bool tree_entry = false;    // mdt_sample_sde_tree*: o.tree is the entry's `tree` argument, refused when null
+    int32_t cand = 1;           // a *_multi entry: action chunks per observation (x_T, out, the noise rows, the pin, the record and the
+    bool cand_given = false;    // tree's seeds are per chunk, batch * cand of them; tokens, goal and ctx_out per observation)
 
     SamplerRequest& schedule(const float* levels, bool dev, int32_t n) { sigmas = levels; sigmas_dev = dev; n_steps = n; return *this; }
     SamplerRequest& plan(int32_t k, const mdt_sampler_params* p, const float* rows, int32_t n) {
         kind = k; params = p; noise = rows; n_noise = n; return *this;
     }
+    SamplerRequest& candidates(int32_t k) { cand = k; cand_given = true; return *this; }
     SamplerRequest& weight(float lam) { o.cond_lambda = lam; weight_given = true; return *this; }
     SamplerRequest& tree(const mdt_sampler_params* p, const mdt_brownian_source* t) {
         kind = MDT_SAMPLER_DPMPP_SDE; params = p; o.tree = t; tree_entry = true; return *this;
     }
     bool guided() const { return weight_given || o.cond_lambda != 1.f; }
+    int64_t chunks() const { return batch * cand; }  // (after sampler_check)
     const float* host_sigmas() const { return sigmas_dev ? nullptr : sigmas; }
     const float* dev_sigmas() const { return sigmas_dev ? sigmas : nullptr; }
 };
 
-// An open sampler call: the encoder's inputs -- a guided call's staged 2B-sample copies -- the samples through the network (nb:
-// 2B when guided), where the encoder's context goes (null when guided: sampler_close copies the conditional half to the
-// caller's ctx_out, where the unguided call writes it) and the guidance.
+// An open sampler call: the encoder's inputs -- a guided call's staged 2B-sample copies -- its two counts, where the encoder's
+// context goes (null when guided: sampler_close copies the conditional half to the caller's ctx_out, where the unguided call
+// writes it) and the guidance.
+// The counts: `batch` observations make nctx encoded contexts (2 batch when guided: the conditional ones, then the
+// unconditional ones) and, at `cand` chunks each, `chunks` = batch * cand states through nb = nctx * cand decoder samples (the
+// conditional chunks, then the unconditional ones): decoder sample s reads context s / cand in either half.  The guide staging,
+// the encoder, the stacked cross K|V product, the fold and sampler_close's copy run on contexts; the prep kernels, the decoder
+// blocks, every head, the tree's noise rows and the record on chunks / decoder samples.
 struct SamplerCall {
     const float *tokens, *tokens2, *goal;
     int32_t modality;
-    int64_t batch, nb;
+    int64_t batch, nctx;
+    int32_t cand;
+    int64_t chunks, nb;
     float* ctx_out;
     float* ctx_user;
     mdt_guide gd;
     hipStream_t s;
     mdt_head_pin pin;
     mdt_status encode(mdt_model* m, const float* sigma, float* ctx) const {
-        return run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, nb, sigma, 0, ctx, s);
+        return run_encode(m, tokens, tokens2, goal, modality, m->cfg.arch == MDT_ARCH_MDTV, nctx, sigma, 0, ctx, s);
     }
 };
 
@@ -1269,15 +1284,24 @@ static mdt_status sampler_check(const mdt_model* m, const SamplerRequest& a, con
     if (a.guided()) MDT_TRY(guide_of(m, a.o.cond_lambda, a.who, gd));
     if (!sched_ok) return fail(MDT_ERR_INVALID_ARG, "%s: null sigmas", a.who);
     if (!m || !a.x_T || !a.out || a.batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: bad argument", family);
+    if (a.cand_given) {  // a *_multi entry: its own argument, then the decoder's row counts (int) at what mdt_reserve will be asked for
+        if (a.cand < 1) return fail(MDT_ERR_INVALID_ARG, "%s: candidates is %d, must be >= 1", a.who, (int)a.cand);
+        const int64_t limit = ((int64_t)1 << 24) / std::max(m->Te, m->Ta) / (gd->on ? 2 : 1);
+        if (a.batch > limit / a.cand)
+            return fail(MDT_ERR_INVALID_ARG, "%s: batch * candidates = %lld * %d%s is more than the decoder's %lld samples", a.who,
+                        (long long)a.batch, (int)a.cand, gd->on ? ", doubled by the guidance," : "",
+                        (long long)(((int64_t)1 << 24) / std::max(m->Te, m->Ta)));
+    }
     return MDT_OK;
 }
 
 // The encoder arguments are checked and the parameters known loaded before anything is enqueued; the handle then holds nb
-// samples, and a guided call's encoder inputs are staged in the handle's buffers: tokens and tokens2 twice, the goal then zeros.
+// samples (every buffer is sized by decoder samples, the per-context ones too: a candidates call uses their first nctx), and a guided call's encoder inputs are staged in the handle's buffers: tokens and tokens2 twice, the goal then zeros.
 static mdt_status sampler_open(mdt_model* m, const SamplerRequest& a, mdt_guide gd, SamplerCall* c) {
     MDT_TRY(check_encode_args(m, a.tokens, a.tokens2, a.goal, a.ctx_out));
     MDT_TRY(check_loaded(m));
-    *c = {a.tokens, a.tokens2, a.goal, a.modality, a.batch, gd.on ? 2 * a.batch : a.batch, a.ctx_out, a.ctx_out, gd,
+    const int64_t nctx = gd.on ? 2 * a.batch : a.batch;
+    *c = {a.tokens, a.tokens2, a.goal, a.modality, a.batch, nctx, a.cand, a.chunks(), nctx * a.cand, a.ctx_out, a.ctx_out, gd,
           (hipStream_t)a.stream, {a.o.pin_known, a.o.pin_keep}};
     MDT_TRY(mdt_reserve(m, c->nb));
     if (!gd.on) return MDT_OK;
@@ -1296,7 +1320,7 @@ static mdt_status sampler_close(mdt_model* m, const SamplerCall& c) {
     return MDT_OK;
 }
 
-// gd.on (guided): the encoder and the decoder run 2B samples, the head combines the halves and updates B samples of state
+// gd.on (guided): the encoder runs 2B contexts and the decoder twice the chunks, the head combines the halves and updates the chunks' state
 // Of the options DDIM takes cond_lambda and the pin; lo / hi are accepted and not read (the reference's DDIM never clips), record
 // and tree are refused.
 static mdt_status sample_ddim_impl(mdt_model* m, const SamplerRequest& a) {
@@ -1322,7 +1346,7 @@ static mdt_status sample_ddim_impl(mdt_model* m, const SamplerRequest& a) {
     const View V = decoder_view(m, 0);
     LAUNCH(mdt_launch_sample_prep(a.dev_sigmas(), a.host_sigmas(), n_steps, m->steps, m->freqs, m->cond == COND_TOKEN ? nullptr : m->sig_e,
                                   m->D, a.x_T, m->cfg.sigma_data, m->Wa, m->ba, V.y, (int)(c.nb * m->Ta), m->A, c.s,
-                                  (int)(a.batch * m->Ta)));
+                                  (int)(c.chunks * m->Ta)));
     mdt_status ms = run_modulation(m, m->steps + 3, 4, n_steps, c.s, true, !per_step_ctx);  // one row of conditioning vectors per step
     if (ms == MDT_OK && !per_step_ctx) ms = c.encode(m, nullptr, c.ctx_out);
     if (ms != MDT_OK) { mdt_gemm_side_drop(); return ms; }
@@ -1332,9 +1356,9 @@ static mdt_status sample_ddim_impl(mdt_model* m, const SamplerRequest& a) {
         const float* sigma = m->steps + 4 * i + 3;
         if (per_step_ctx)  // the reference leaves the LAST step's context in latent_encoder_emb
             MDT_TRY(c.encode(m, sigma, last ? c.ctx_out : nullptr));
-        mdt_head_args h = head_args(m, V.y, a.batch, i == 0 ? a.x_T : m->xbuf, sigma, 0, last ? a.out : m->xbuf, MDT_HEAD_DDIM);
+        mdt_head_args h = head_args(m, V.y, c.chunks, i == 0 ? a.x_T : m->xbuf, sigma, 0, last ? a.out : m->xbuf, MDT_HEAD_DDIM);
         h.step = m->steps + 4 * i;
-        MDT_TRY(run_eval(m, V, c.nb, cond_row(m, i), 0, h, nullptr, last ? nullptr : sigma + 4, c.s, gd, c.pin));
+        MDT_TRY(run_eval(m, V, c.nb, cond_row(m, i), 0, h, nullptr, last ? nullptr : sigma + 4, c.s, gd, c.pin, c.cand));
     }
     return sampler_close(m, c);
 }
@@ -1384,6 +1408,25 @@ extern "C" mdt_status mdt_sample_ddim_dev_opt(mdt_model* m, const float* tokens,
     return sample_ddim_impl(m, r.schedule(sigmas_dev, true, n_steps));
 }
 
+// The *_multi entries: the *_opt call with `candidates` chunks per observation (include/mdt_hip.h).
+extern "C" mdt_status mdt_sample_ddim_multi(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                            int32_t modality, const float* x_T, const float* sigmas_host, int32_t n_steps,
+                                            int64_t batch, int32_t candidates, float* out, float* ctx_out,
+                                            const mdt_sample_opts* opts, void* stream) {
+    SamplerRequest r = {"mdt_sample_ddim_multi", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_ddim_impl(m, r.schedule(sigmas_host, false, n_steps).candidates(candidates));
+}
+
+extern "C" mdt_status mdt_sample_ddim_dev_multi(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                                int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
+                                                int64_t batch, int32_t candidates, float* out, float* ctx_out,
+                                                const mdt_sample_opts* opts, void* stream) {
+    SamplerRequest r = {"mdt_sample_ddim_dev_multi", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_ddim_impl(m, r.schedule(sigmas_dev, true, n_steps).candidates(candidates));
+}
+
 // MDT_PLAN_* -> mdt_status with the message of the failed check
 static mdt_status plan_fail(int st, const char* who, int kind) {
     switch (st) {
@@ -1429,11 +1472,11 @@ struct PlanEvalIo {
 static mdt_status run_plan_eval(mdt_model* m, const View& V, const SamplerCall& c, int e, const PlanEvalIo& io) {
     mdt_sampler_eval* ev = m->plan->e;
     if (m->cond == COND_TOKEN) MDT_TRY(c.encode(m, &ev[e].sigma, io.ctx_out));
-    const int64_t nel = (int64_t)c.batch * m->Ta * m->A;
+    const int64_t nel = (int64_t)c.chunks * m->Ta * m->A;
     const mdt_head_plan pl = {&ev[e], io.xs, m->hist, io.noise, io.y_out, nel, io.noise ? io.n_noise : 0, io.lo, io.hi, io.rec,
                               io.rec ? io.rec + nel : nullptr};
-    mdt_head_args h = head_args(m, V.y, c.batch, m->ybuf, &ev[e].sigma, 0, io.out, MDT_HEAD_PLAN);
-    return run_eval(m, V, c.nb, cond_row(m, e), 0, h, &pl, io.last ? nullptr : &ev[e].sigma_next, c.s, c.gd, c.pin);
+    mdt_head_args h = head_args(m, V.y, c.chunks, m->ybuf, &ev[e].sigma, 0, io.out, MDT_HEAD_PLAN);
+    return run_eval(m, V, c.nb, cond_row(m, e), 0, h, &pl, io.last ? nullptr : &ev[e].sigma_next, c.s, c.gd, c.pin, c.cand);
 }
 
 // The structure of sample_ddim_impl: the plan and the sigma embeddings of every evaluation (one launch), the first input, the
@@ -1472,21 +1515,22 @@ static mdt_status sample_plan_impl(mdt_model* m, const SamplerRequest& a) {
                             mdt_plan_step_of(kind, n_steps, e));
     }
     const bool use_tree = tree && mdt_plan_needs_noise(kind, p) && max_rows > 0;
+    const int64_t chunks = a.chunks();  // the states: x_T, out, the noise rows, the record and the tree's seeds are per chunk
     if (wants_tree) {
         const int64_t per_row = (int64_t)m->Ta * m->A;
         if (!tree)  // a tree entry without its tree: what a tree without seeds is told (check_tree, mdt_brownian.hip)
             return fail(MDT_ERR_INVALID_ARG, "%s: bad argument (seeds, n_seeds = 1 or batch, batch, per_row)", a.who);
-        MDT_TRY(mdt_check_brownian_source(a.who, tree, a.batch, per_row));
+        MDT_TRY(mdt_check_brownian_source(a.who, tree, chunks, per_row));
         if (host && tree->lo == 0.0 && tree->hi == 0.0) {
             double lo = 0.0, hi = 0.0;
             mdt_tree_interval(host, n_steps + 1, &lo, &hi);
             mdt_brownian_source t = *tree;
             t.lo = lo; t.hi = hi;
-            MDT_TRY(mdt_check_brownian_source(a.who, &t, a.batch, per_row));
+            MDT_TRY(mdt_check_brownian_source(a.who, &t, chunks, per_row));
         }
         if (use_tree) {  // (a grown buffer moves: captured graphs that read the old one are stale, as after mdt_reserve)
             const int64_t held_rows = m->tr_rows, held_nel = m->tr_nel;
-            MDT_TRY(mdt_grow_carve(m->tr_ws, m->tr_rows, m->tr_nel, max_rows, a.batch * per_row,
+            MDT_TRY(mdt_grow_carve(m->tr_ws, m->tr_rows, m->tr_nel, max_rows, chunks * per_row,
                                    [&](Bump& b, int64_t r, int64_t nel) {
                                        m->tr_q = (mdt_tree_q*)b.take((sizeof(mdt_tree_q) + 3) / 4);
                                        m->tr_noise = b.take(r * nel);
@@ -1510,15 +1554,15 @@ static mdt_status sample_plan_impl(mdt_model* m, const SamplerRequest& a) {
     mdt_sampler_eval* ev = m->plan->e;
     LAUNCH(mdt_launch_sampler_prep(a.dev_sigmas(), host, n_steps, kind, p, m->plan, m->freqs, per_step_ctx ? nullptr : m->sig_e,
                                    m->D, a.x_T, noise, noise ? n_noise : 0, m->ybuf, m->hist, m->cfg.sigma_data, m->Wa, m->ba, V.y,
-                                   (int)(c.nb * m->Ta), m->A, c.s, (int)(a.batch * m->Ta), use_tree ? m->tr_q : nullptr));
+                                   (int)(c.nb * m->Ta), m->A, c.s, (int)(chunks * m->Ta), use_tree ? m->tr_q : nullptr));
     if (use_tree)  // every noise row from the tree, before the first evaluation reads one
-        LAUNCH(mdt_launch_brownian_fill(m->tr_q, *tree, max_rows, a.batch * m->Ta * m->A, (int64_t)m->Ta * m->A, m->tr_noise, c.s));
+        LAUNCH(mdt_launch_brownian_fill(m->tr_q, *tree, max_rows, chunks * m->Ta * m->A, (int64_t)m->Ta * m->A, m->tr_noise, c.s));
     const int stride = (int)(sizeof(mdt_sampler_eval) / sizeof(float));
     mdt_status ms = run_modulation(m, &ev[0].sigma, stride, E, c.s, true, !per_step_ctx);  // one conditioning row per evaluation
     if (ms == MDT_OK && !per_step_ctx) ms = c.encode(m, nullptr, c.ctx_out);
     if (ms != MDT_OK) { mdt_gemm_side_drop(); return ms; }
     LAUNCH(mdt_gemm_side_flush(c.s));
-    const int64_t rec_stride = 2 * a.batch * m->Ta * m->A;
+    const int64_t rec_stride = 2 * chunks * m->Ta * m->A;
     for (int e = 0; e < E; ++e) {
         const bool last = e == E - 1, clips = a.o.lo && mdt_plan_loop_clips(kind, last);
         MDT_TRY(run_plan_eval(m, V, c, e, {last, e == 0 ? a.x_T : m->xbuf, last ? a.out : m->xbuf, last ? nullptr : m->ybuf, noise,
@@ -1576,6 +1620,25 @@ extern "C" mdt_status mdt_sample_dev_opt(mdt_model* m, const float* tokens, cons
     SamplerRequest r = {"mdt_sample_dev_opt", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
     MDT_TRY(read_opts(r.who, opts, &r.o));
     return sample_plan_impl(m, r.schedule(sigmas_dev, true, n_steps).plan(kind, params, noise, n_noise));
+}
+
+extern "C" mdt_status mdt_sample_multi(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
+                                       const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas_host,
+                                       int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, int32_t candidates,
+                                       float* out, float* ctx_out, const mdt_sample_opts* opts, void* stream) {
+    SamplerRequest r = {"mdt_sample_multi", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_plan_impl(m, r.schedule(sigmas_host, false, n_steps).plan(kind, params, noise, n_noise).candidates(candidates));
+}
+
+extern "C" mdt_status mdt_sample_dev_multi(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                           int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
+                                           const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
+                                           int64_t batch, int32_t candidates, float* out, float* ctx_out,
+                                           const mdt_sample_opts* opts, void* stream) {
+    SamplerRequest r = {"mdt_sample_dev_multi", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_plan_impl(m, r.schedule(sigmas_dev, true, n_steps).plan(kind, params, noise, n_noise).candidates(candidates));
 }
 
 extern "C" mdt_status mdt_sample_sde_tree(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,

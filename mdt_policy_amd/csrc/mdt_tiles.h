@@ -24,6 +24,15 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
+// The context of decoder sample b where ctx_div consecutive samples share one (the candidates of a sampler call): b and ctx_div
+// are workgroup-uniform, so this is one scalar division per workgroup in front of every load, none of which it gates.
+// CD = false is the plain launch: b itself, ctx_div never read.
+template <bool CD>
+__device__ __forceinline__ int ctx_context(int b, int ctx_div) {
+    if constexpr (CD) return (int)((unsigned)b / (unsigned)ctx_div);
+    else return b;
+}
+
 // ---- activation loader ----
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 template <bool COH>
@@ -1242,7 +1251,8 @@ __device__ __forceinline__ void attn_proj_tile(const mdt_gemm_args& a, const flo
 // small attention tile: sample b, head group hg of nhg (Hl = H / nhg heads, a contiguous column range of q/k/v).  The
 // rows (all Hl heads) are staged in LDS with batched 16-byte loads, then thread (head, query row) runs
 // softmax(q k^T) v out of LDS with the scores in registers.  10x10 / 10x4 / 4x4 score matrices are 0.1 % of the FLOPs,
-// so this stays on the VALU.  256 threads (tid 0..255); `lds` is this group's own region; `sync` is the barrier the 256
+// so this stays on the VALU.  The q rows and the output rows are sample b's, the k / v rows sample bkv's (b itself, or the
+// context that several decoder samples share: candidates).  256 threads (tid 0..255); `lds` is this group's own region; `sync` is the barrier the 256
 // threads share with whoever else runs the same code (a workgroup barrier).
 // TKC: compile-time bound on the number of keys (4 / 10 / 16, the smallest >= Tk), ROPE: rotary embedding on q/k.
 // With both fixed the score / softmax / PV loops are straight-line code over clamped rows with select masks, so the
@@ -1250,8 +1260,8 @@ __device__ __forceinline__ void attn_proj_tile(const mdt_gemm_args& a, const flo
 // ------------------------------------------------------------------------------------------------
 template <int HD, int TKC, bool ROPE, bool COH>
 __device__ __forceinline__ void attn_tile(const mdt_attn_args& a, const float* __restrict__ rope_cos,
-                                          const float* __restrict__ rope_sin, float scale, int b, int hg, int nhg, float* lds,
-                                          int tid) {
+                                          const float* __restrict__ rope_sin, float scale, int b, int bkv, int hg, int nhg,
+                                          float* lds, int tid) {
     MDT_TS(0)
     MDT_TS_HWID()
     constexpr int ROT = 32;  // rotary dims (position_embeddings.py / transformer_blocks.py:108)
@@ -1279,10 +1289,10 @@ __device__ __forceinline__ void attn_tile(const mdt_attn_args& a, const float* _
                 src = oq + (int64_t)(b * a.Tq + r) * a.ldq + coff + 4 * (idx - r * d4);
             } else if (idx < nq + nkv) {
                 const int i2 = idx - nq, r = i2 / d4;
-                src = ok + (int64_t)(b * a.Tk + r) * a.ldkv + coff + 4 * (i2 - r * d4);
+                src = ok + (int64_t)(bkv * a.Tk + r) * a.ldkv + coff + 4 * (i2 - r * d4);
             } else {
                 const int i2 = idx - nq - nkv, r = i2 / d4;
-                src = ov + (int64_t)(b * a.Tk + r) * a.ldkv + coff + 4 * (i2 - r * d4);
+                src = ov + (int64_t)(bkv * a.Tk + r) * a.ldkv + coff + 4 * (i2 - r * d4);
             }
             t[u] = LQ.ld4(src);
         }
@@ -1695,24 +1705,26 @@ struct mdt_xattn_req {
     f32x4 bo[NTWMAX];              // output bias at the lane's output columns
 };
 // DX: 0 = D is a.D (run time); otherwise D == DX == DMAX is known at compile time (attn_xattn_tile: all offsets fold)
+// bc: the context whose folded operands decoder sample b reads -- b itself, or b / candidates where several chunks share one
+// observation (workgroup-uniform, worked out once by the kernel; the rows stay sample b's)
 template <int NPP, int DMAX, int DX = 0>
-__device__ __forceinline__ void xattn_request_u(const mdt_xapply_args& a, int b, int tid, mdt_xattn_req<NPP, DMAX>& q) {
+__device__ __forceinline__ void xattn_request_u(const mdt_xapply_args& a, int bc, int tid, mdt_xattn_req<NPP, DMAX>& q) {
     constexpr int NTU = NPP / 16, KS = 8 / NTU, KLMAX = DMAX / 16 / KS;
     const int lane = tid & 63, wave = tid >> 6;
     const int D = DX ? DX : a.D, K16 = D >> 4, KL = K16 / KS;
-    const float* Ub = a.U + (int64_t)b * NPP * D;
+    const float* Ub = a.U + (int64_t)bc * NPP * D;
     const int ntu = wave % NTU, ks = wave / NTU;
 #pragma unroll
     for (int kk = 0; kk < KLMAX; ++kk)
         q.u[kk] = ldg4(Ub + ((int64_t)(ntu * K16 + min(ks * KL + kk, K16 - 1)) * 64 + lane) * 4);
-    q.cb = ldg4(a.c + (int64_t)b * NPP + 4 * min(tid >> 4, NPP / 4 - 1));   // softmax thread (t, h) = (tid % 16, tid / 16)
+    q.cb = ldg4(a.c + (int64_t)bc * NPP + 4 * min(tid >> 4, NPP / 4 - 1));   // softmax thread (t, h) = (tid % 16, tid / 16)
 }
 template <int NPP, int DMAX, int DX = 0>
-__device__ __forceinline__ void xattn_request_wf(const mdt_xapply_args& a, int b, int tid, mdt_xattn_req<NPP, DMAX>& q) {
+__device__ __forceinline__ void xattn_request_wf(const mdt_xapply_args& a, int bc, int tid, mdt_xattn_req<NPP, DMAX>& q) {
     constexpr int KP16 = NPP / 16, NTWMAX = DMAX / 128;
     const int lane = tid & 63, wave = tid >> 6;
     const int D = DX ? DX : a.D, N16 = D >> 4, NTW = D >> 7;
-    const float* Wb = a.Wf + (int64_t)b * NPP * D;
+    const float* Wb = a.Wf + (int64_t)bc * NPP * D;
 #pragma unroll
     for (int j = 0; j < NTWMAX; ++j)
 #pragma unroll
@@ -1740,7 +1752,7 @@ __device__ __forceinline__ void xattn_request_vec(const mdt_xapply_args& a, cons
 // OL: the new rows ALSO go to LDS (`yo`, row stride `yos`: k_xattn_gemm_smallm multiplies them on the spot) and reach a.y only
 // if `wr` (one workgroup of those that repeat the sample's cross-attention writes it).
 template <int NPP, bool COH, bool YL = false, int DMAX = 512, int DX = 0, bool OL = false>
-__device__ __forceinline__ void xattn_tile(const mdt_xapply_args& a, int b, float* lds, const float* __restrict__ zeros, int tid,
+__device__ __forceinline__ void xattn_tile(const mdt_xapply_args& a, int b, int bc, float* lds, const float* __restrict__ zeros, int tid,
                                            const float* yl = nullptr, int yls = 0, const mdt_xattn_req<NPP, DMAX>* pre = nullptr,
                                            float* yo = nullptr, int yos = 0, bool wr = true) {
     constexpr int NTU = NPP / 16, KS = 8 / NTU, KP16 = NPP / 16, PS = NPP + 4;
@@ -1785,8 +1797,8 @@ __device__ __forceinline__ void xattn_tile(const mdt_xapply_args& a, int b, floa
     if constexpr (YL) q = *pre;
     else {
         xattn_request_vec<NPP, DMAX, DX>(a, zeros, tid, q);
-        xattn_request_u<NPP, DMAX, DX>(a, b, tid, q);
-        xattn_request_wf<NPP, DMAX, DX>(a, b, tid, q);
+        xattn_request_u<NPP, DMAX, DX>(a, bc, tid, q);
+        xattn_request_wf<NPP, DMAX, DX>(a, bc, tid, q);
     }
     const int ntu = wave % NTU, ks = wave / NTU;
     // old rows at this lane's output position: row lane % 16, columns tile * 16 + 4 (lane / 16) .. + 3
@@ -1900,7 +1912,7 @@ __device__ __forceinline__ void xattn_tile(const mdt_xapply_args& a, int b, floa
 // ------------------------------------------------------------------------------------------------
 template <int HD, int TKC, int NPP>
 __device__ __forceinline__ void attn_xattn_tile(const mdt_gemm_args& a, const mdt_attn_pro& at, const mdt_xapply_args& x, int b,
-                                                float* lds, const float* __restrict__ zeros, int tid) {
+                                                int bc, float* lds, const float* __restrict__ zeros, int tid) {
     constexpr int MTILES = 1, NTW = HD / 16, D = 8 * HD, K16 = D / 16;
     constexpr bool KSTEP_PRIO = false;
     constexpr int R = NTW == 1 ? 6 : (NTW == 2 ? 4 : 3);   // deeper rings change nothing here (measured: R = 4, 6)
@@ -1955,7 +1967,7 @@ __device__ __forceinline__ void attn_xattn_tile(const mdt_gemm_args& a, const md
     // one step ago: 25 MB per launch).  Requested at entry they held the q / k / v rows back (rows in LDS after 13.7 k cycles
     // instead of 7.6 k: the whole chip asks for 41 MB at once); requested here, the score half travels under the projection
     // (vmcnt retires in order: the k loop's first fragment waits ~1 k cycles behind it) ...
-    xattn_request_u<NPP, D, D>(x, b, tid, xq);
+    xattn_request_u<NPP, D, D>(x, bc, tid, xq);
 
     // ---- projection: 16 x D x D, transposed-form MFMA k-steps on the ring ----
     {
@@ -1980,7 +1992,7 @@ __device__ __forceinline__ void attn_xattn_tile(const mdt_gemm_args& a, const md
     MDT_TS(3)
     // ... and the combination half + the ln3 / bias vectors behind the k loop's last weight fragment: nothing queues behind
     // them, and they have the epilogue, ln3, the scores and the softmax to arrive
-    xattn_request_wf<NPP, D, D>(x, b, tid, xq);
+    xattn_request_wf<NPP, D, D>(x, bc, tid, xq);
     xattn_request_vec<NPP, D, D>(x, zeros, tid, xq);
     // ---- epilogue: out = old + gate * (acc + bias) -> LDS rows (lane holds row lane % 16, columns ncol .. ncol + 3) ----
 #pragma unroll
@@ -1992,5 +2004,5 @@ __device__ __forceinline__ void attn_xattn_tile(const mdt_gemm_args& a, const md
     __syncthreads();
     MDT_TS(4)
     // ---- ln3 -> scores against U -> masked softmax -> Wf combination -> residual -> x.y ----
-    xattn_tile<NPP, false, true, D, D>(x, b, xscr, zeros, tid, yl, stride, &xq);
+    xattn_tile<NPP, false, true, D, D>(x, b, bc, xscr, zeros, tid, yl, stride, &xq);
 }

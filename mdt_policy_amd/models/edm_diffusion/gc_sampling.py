@@ -25,7 +25,7 @@ import torch
 
 from . import utils
 from ... import _lib
-from ..networks._engine import rollout_controls
+from ..networks._engine import chunk_rows, rollout_controls, take_candidates
 from .graphed import GraphedDDIM, GraphedSampler
 from .score_wrappers import GCDenoiser
 
@@ -230,8 +230,27 @@ def _scaler_native(scaler) -> bool:
     return scaler is None or callable(getattr(scaler, "clip_bounds", None))
 
 
+def _controls(extra_args):
+    """(native, lam, pin, K) of a sampler's ``extra_args``: ``candidates`` = K comes off first (take_candidates), the rest is
+    rollout_controls'.  K chunks per observation ride in the native call with a weight and a pin; any further key keeps the host
+    loop, whose ``model(...)`` calls get all of them -- GCDenoiser.forward expands the observations there."""
+    K, rest = take_candidates(extra_args)
+    return rollout_controls(**rest) + (K,)
+
+
+def _chunk_view(state, action, noise, K):
+    """A candidates call's ``action`` as its (B*K, Ta, A) chunks (chunk_rows checks the leading size) and its noise rows to match."""
+    if K == 1 and action.dim() != 4:
+        return action, noise
+    B = next(v for v in state.values() if torch.is_tensor(v)).shape[0]
+    rows = chunk_rows(action, B, K)
+    if noise is not None and noise.dim() == action.dim() + 1:
+        noise = noise.reshape((noise.shape[0],) + tuple(rows.shape))
+    return rows, noise
+
+
 def _native_ok(model, sigmas, scaler, callback, extra_args) -> bool:
-    if not isinstance(model, GCDenoiser) or callback is not None or not rollout_controls(**(extra_args or {}))[0]:
+    if not isinstance(model, GCDenoiser) or callback is not None or not _controls(extra_args)[0]:
         return False
     if not _scaler_native(scaler):
         return False
@@ -274,13 +293,20 @@ def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, e
     (dpmpp_sde, in place of ``noise``): (seeds, tol, lo, hi) of the Brownian tree the call draws from; (tol, lo, hi) join the
     graph key and the seeds are the graph's per-call input.  ``scaler``: None or the sampler's, which _native_ok admitted -- its
     bounds ride in the call; a graph holds them in static buffers refreshed before every replay, so only their presence joins the
-    graph key.  A pin among the ``extra_args`` (an ActionPin) rides in the call the same way."""
+    graph key.  A pin among the ``extra_args`` (an ActionPin) rides in the call the same way; ``candidates`` joins the parameters
+    as the weight does, and the "rollout-sized" rule then counts chunks."""
     bounds = None if scaler is None else scaler.clip_bounds(action.device)
-    _, lam, pin = rollout_controls(**(extra_args or {}))
+    _, lam, pin, K = _controls(extra_args)
+    shape = action.shape
+    action, noise_rows = _chunk_view(state, action, None if tree is not None else noise, K)
+    if tree is None:
+        noise = noise_rows
     if pin is not None:
-        pin = pin.on(action.device, action.shape)
+        pin = pin.on(action.device, action.shape, K)
     if lam is not None:
         params = dict(params, cond_lambda=lam)
+    if K != 1:
+        params = dict(params, candidates=K)
     tag = (kind, tuple(sorted(params.items())))
     if n_steps is not None:
         tag += (n_steps, tuple(float(v) for v in sigmas))
@@ -301,13 +327,13 @@ def _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=None, e
                                                   bounds=bounds, pin=pin),
                        f"sample_{kind}", noise=noise, bounds=bounds, pin=pin)
     if out is not None:
-        return out
+        return out.reshape(shape)
     kw = {} if bounds is None else {"bounds": bounds}
     if pin is not None:
         kw["pin"] = pin
     if tree is not None:
-        return model.sample_native(kind, state, action, goal, sigmas, tree=tree, **kw, **params)
-    return model.sample_native(kind, state, action, goal, sigmas, noise=noise, n_steps=n_steps, **kw, **params)
+        return model.sample_native(kind, state, action, goal, sigmas, tree=tree, **kw, **params).reshape(shape)
+    return model.sample_native(kind, state, action, goal, sigmas, noise=noise, n_steps=n_steps, **kw, **params).reshape(shape)
 
 
 def replay_callback(rec, callback):
@@ -326,22 +352,28 @@ def sample_ddim(model, state, action, goal, sigmas, scaler=None, extra_args=None
     x <- (sigma_{i+1}/sigma_i) x - expm1(-(t_{i+1} - t_i)) D(x; sigma_i),  t = -ln sigma.
     `scaler` is accepted and never read, exactly as in the reference (its DDIM has no `clip_output` call), so a harness run
     with `use_scaler` (mdtv_agent.py:606-614) keeps the fused native loop; only `callback` / `extra_args` need the step loop
-    (a guidance weight and pinned actions, ``extra_args={"cond_lambda": lam, "pin": ActionPin(...)}``, ride in the native call)."""
+    (a guidance weight, pinned actions and a candidate count, ``extra_args={"cond_lambda": lam, "pin": ActionPin(...),
+    "candidates": K}``, ride in the native call: K chunks per observation of ``state`` / ``goal`` from one encoded context,
+    ``action`` (B*K, Ta, A) or (B, K, Ta, A))."""
     extra_args = {} if extra_args is None else extra_args
-    native, lam, pin = rollout_controls(**extra_args)
+    native, lam, pin, K = _controls(extra_args)
     if isinstance(model, GCDenoiser) and callback is None and native:
         # guidance: the guided native call, its graphs keyed by the weight too; a pin: by its presence (the values are copied in)
         tag, kw = (None, {}) if lam is None else (("ddim_guided", lam), {"cond_lambda": lam})
         key = lam
+        shape = action.shape
+        action = _chunk_view(state, action, None, K)[0]
         if pin is not None:
-            pin = pin.on(action.device, action.shape)
+            pin = pin.on(action.device, action.shape, K)
             tag, key, kw = ("ddim_pin", lam), (lam, "pin"), dict(kw, pin=pin)
+        if K != 1:  # the candidate count: part of the graph key (GraphedDDIM._call_key)
+            tag, key, kw = (tag, ("candidates", K)), (key, ("candidates", K)), dict(kw, candidates=K)
         out = _graph_route(model, "_graphed_samplers", tag, key, state, action, goal, sigmas,
-                           lambda sig: GraphedDDIM(model, state, action, goal, sig, cond_lambda=lam, pin=pin),
+                           lambda sig: GraphedDDIM(model, state, action, goal, sig, cond_lambda=lam, pin=pin, candidates=K),
                            "sample_ddim" if lam is None else "guided sample_ddim", pin=pin)
         if out is not None:
-            return out
-        return model.sample_ddim(state, action, goal, sigmas, **kw)  # fused native loop
+            return out.reshape(shape)
+        return model.sample_ddim(state, action, goal, sigmas, **kw).reshape(shape)  # fused native loop
     sig = _host(sigmas)
     with _hoist(model, state, goal):
         for i in range(len(sig) - 1):
@@ -850,7 +882,7 @@ def sample_dpm_fast(model, state, action, goal, sigma_min, sigma_max, n, scaler=
     if eta and not t_end > t_start:
         raise ValueError('eta must be 0 for reverse sampling')
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
-    if (isinstance(model, GCDenoiser) and callback is None and rollout_controls(**(extra_args or {}))[0] and _scaler_native(scaler)
+    if (isinstance(model, GCDenoiser) and callback is None and _controls(extra_args)[0] and _scaler_native(scaler)
             and 1 <= n <= _lib.SAMPLER_MAX_EVALS):  # (the solver never reads `scaler`, here as in the reference: no bounds to pass)
         return _run_native("dpm_fast", model, state, action, goal, [float(sigma_max), float(sigma_min)],
                            _dpm_fast_noise(action, t_start, t_end, n, eta, noise_sampler), n_steps=n, eta=eta, s_noise=s_noise,
@@ -909,8 +941,9 @@ def sample_dpm_adaptive(model, state, action, goal, sigma_min, sigma_max, extra_
     t_end = _t(torch.tensor(float(sigma_min))).to(torch.float32)
     if eta and not bool(t_end > t_start):
         raise ValueError('eta must be 0 for reverse sampling')
-    native, lam, pin = rollout_controls(**(extra_args or {}))
-    native = native and pin is None  # mdt_sample_dpm_adaptive takes no pin: the host loop applies it through forward
+    native, lam, pin, K = _controls(extra_args)
+    # mdt_sample_dpm_adaptive takes no pin and no candidates: the host loop hands both to forward
+    native = native and pin is None and K == 1
     if (isinstance(model, GCDenoiser) and callback is None and native and not eta and action.device.type == "cuda"
             and not torch.cuda.is_current_stream_capturing()):
         kw = {} if lam is None else {"cond_lambda": lam}  # guidance: mdt_sample_dpm_adaptive_guided

@@ -23,7 +23,7 @@ import torch
 
 class GraphedDDIM:
     def __init__(self, model, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas: torch.Tensor,
-                 cond_lambda: Optional[float] = None, pin: Optional[tuple] = None):
+                 cond_lambda: Optional[float] = None, pin: Optional[tuple] = None, candidates: int = 1):
         if x_T.device.type != "cuda":
             raise RuntimeError("GraphedDDIM needs the model and its inputs on a ROCm GPU")
         # pin: (known, keep) of a call captured with pinned actions.  Like the bounds of GraphedSampler the graph reads them from
@@ -31,6 +31,7 @@ class GraphedDDIM:
         if pin is not None:
             self._pin = tuple(t.detach().to(x_T.device, torch.float32).reshape(x_T.shape).clone() for t in pin)
         self.model = model
+        self.candidates = int(candidates)  # chunks per observation of the captured call: part of the graph (_call_key)
         self.cond_lambda = cond_lambda  # classifier-free guidance weight of the captured call (None: unguided)
         self.device = x_T.device
         self._static_state: Dict[str, object] = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in state.items()}
@@ -53,12 +54,15 @@ class GraphedDDIM:
 
     def _call_key(self):
         """What besides the shapes a call must share with the captured one to replay it (matches)."""
-        return self.cond_lambda if self._pin is None else (self.cond_lambda, "pin")
+        key = self.cond_lambda if self._pin is None else (self.cond_lambda, "pin")
+        return key if self.candidates == 1 else (key, ("candidates", self.candidates))
 
     def _run(self):
         kw = {} if self._pin is None else {"pin": self._pin}
         if self.cond_lambda is not None:
             kw["cond_lambda"] = self.cond_lambda
+        if self.candidates != 1:
+            kw["candidates"] = self.candidates
         return self.model.sample_ddim(self._static_state, self._x, self._goal, self._sig, **kw)
 
     def _extra_inputs(self, noise, bounds=None, pin=None):
@@ -71,7 +75,7 @@ class GraphedDDIM:
         with torch.no_grad():
             eng = self._engine()
             eng.sync_params()
-            eng.reserve(self._x.shape[0])
+            eng.reserve(self._x.shape[0])  # chunks; a guided call's warm-up below grows the workspace to twice that before the capture
             side = torch.cuda.Stream(self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(side):  # warm-up on a side stream, as torch's graph capture wants it
@@ -166,8 +170,9 @@ class GraphedDDIM:
 
 class GraphedSampler(GraphedDDIM):
     """The same for one of the other samplers (``GCDenoiser.sample_native``): one graph per sampler kind, parameter set and
-    shapes.  The noise rows of a call (drawn by the caller in the Python loop's order) are copied into a static buffer with
-    the other inputs, so a replay consumes the same random stream as the eager call."""
+    shapes (``candidates`` rides among ``params``, as a guidance weight does).  The noise rows of a call (drawn by the caller in
+    the Python loop's order) are copied into a static buffer with the other inputs, so a replay consumes the same random stream
+    as the eager call."""
 
     def __init__(self, model, kind: str, params: dict, state: dict, x_T: torch.Tensor, goal: torch.Tensor,
                  sigmas: torch.Tensor, noise: Optional[torch.Tensor], n_steps: Optional[int] = None, tree: Optional[tuple] = None,

@@ -15,7 +15,7 @@ from contextlib import contextmanager
 import torch
 from torch import nn
 
-from ..networks._engine import HipScoreNetwork
+from ..networks._engine import HipScoreNetwork, candidate_count, chunk_rows
 
 
 def _staged_backward() -> bool:
@@ -124,13 +124,29 @@ class GCDenoiser(nn.Module):
                  if ("inner_model." + n) in eng._grad_layout and not (unused and n.startswith(unused))]
         return tok, tok2, g, B, [n for n, _ in named], [p for _, p in named]
 
-    def forward(self, state, action, goal, sigma, cond_lambda=1.0, pin=None, **kwargs):
+    def forward(self, state, action, goal, sigma, cond_lambda=1.0, pin=None, candidates=None, **kwargs):
         """D(x; sigma) = F(x*c_in, sigma)*c_out + x*c_skip (reference score_wrappers.py:65-80).
 
         ``cond_lambda`` != 1: classifier-free guidance, D_lambda = D(x; sigma, 0) + lambda (D(x; sigma, g) - D(x; sigma, 0)) from the
         conditional and the ``uncond`` evaluation (the latter first, so latent_encoder_emb ends as the conditional context).
         ``pin`` (an ActionPin, utils/action_pin.py): pinned actions, D' = keep * known + (1 - keep) * D, applied after the
-        guidance -- what the native samplers compute in their action head."""
+        guidance -- what the native samplers compute in their action head.
+        ``candidates`` = K: ``action`` holds K chunks for each of the B observations of ``state`` and ``goal``, (B*K, Ta, A) or
+        (B, K, Ta, A), chunk k of observation b at row b*K + k; the observations are expanded with ``repeat_interleave`` and the
+        call runs at batch B*K (the samplers' host loops; the native samplers encode each observation once instead).  A pin
+        given per observation goes to each of its chunks; latent_encoder_emb stays (B, Te, d)."""
+        K = candidate_count(candidates)
+        if K != 1 or (candidates is not None and action.dim() == 4):
+            B = next(v for v in state.values() if torch.is_tensor(v)).shape[0]
+            rows = chunk_rows(action, B, K)
+            wide = {k: (v.repeat_interleave(K, 0) if torch.is_tensor(v) else v) for k, v in state.items()}
+            out = self.forward(wide, rows, goal.repeat_interleave(K, 0), sigma, cond_lambda=cond_lambda, **kwargs)  # sigma: 1 or B*K values
+            im = self.inner_model
+            if torch.is_tensor(im.latent_encoder_emb) and im.latent_encoder_emb.shape[0] == B * K:
+                im.latent_encoder_emb = im.latent_encoder_emb[::K]
+            if pin is not None:
+                out = pin.apply(out, K)
+            return out.reshape(action.shape)
         if pin is not None:
             return pin.apply(self.forward(state, action, goal, sigma, cond_lambda=cond_lambda, **kwargs))
         lam = float(cond_lambda)
@@ -302,7 +318,7 @@ class GCDenoiser(nn.Module):
 
     @torch.no_grad()
     def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, cond_lambda=None, tree=None, bounds=None,
-                      record=False, pin=None, **params):
+                      record=False, pin=None, candidates=None, **params):
         """One of the other samplers (``kind``: 'euler', 'heun', 'dpmpp_2m', ... -- the gc_sampling function name without
         'sample_') as one enqueue on the current stream (mdt_sample).  ``noise``: None or (n_noise, B, Ta, A) in the Python loop's
         draw order -- raw randn draws (euler / heun / dpm_2 / the ancestral samplers) or the noise_sampler values (dpmpp_2s_ancestral,
@@ -320,11 +336,17 @@ class GCDenoiser(nn.Module):
         it to one.  The actions are those of the call without ``record``, bit for bit.
         ``pin``: an ``ActionPin`` (utils/action_pin.py) or its (known, keep) pair of (B, Ta, A) device tensors -- pinned actions:
         every evaluation's denoised value becomes keep * known + (1 - keep) * D inside the action head (mdt_sample_opts.pin_known /
-        pin_keep), for every kind, guided or not, with bounds, record and tree noise as without it."""
+        pin_keep), for every kind, guided or not, with bounds, record and tree noise as without it.
+        ``candidates`` = K (an int >= 1): K action chunks for each of the B observations of ``state`` and ``goal`` from ONE encoded
+        context (mdt_sample_multi): the encoder, the cross K|V product and the cross-attention fold run on B samples, the decoder on
+        B*K.  ``action`` is (B*K, Ta, A) or (B, K, Ta, A), chunk k of observation b at row b*K + k, and the result has its shape;
+        ``noise``, the record, ``tree``'s seeds and a per-chunk pin count chunks the same way; a pin given per observation,
+        (B, Ta, A), goes to each of its K chunks; latent_encoder_emb is (B, Te, d).  A leading size other than B*K raises ValueError."""
         from ... import _lib
         im = self.inner_model
+        K = candidate_count(candidates)
         if pin is not None and callable(getattr(pin, "on", None)):
-            pin = pin.on(action.device, action.shape)
+            pin = pin.on(action.device, (action.numel() // (action.shape[-2] * action.shape[-1]),) + tuple(action.shape[-2:]), K)
         if bounds is not None:
             pair = bounds.clip_bounds(action.device) if callable(getattr(bounds, "clip_bounds", None)) else bounds
             bounds = tuple(torch.as_tensor(b, dtype=torch.float32).to(action.device) for b in pair)
@@ -334,7 +356,7 @@ class GCDenoiser(nn.Module):
             tree = (tuple(tree) + (0., 0.))[:4]
         out, ctx, rec = self._engine(state=state).sample_native(
             _lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action, im._goals(goal, False), sigmas, noise,
-            n_steps=n_steps, cond_lambda=cond_lambda, tree=tree, bounds=bounds, record=record, pin=pin)
+            n_steps=n_steps, cond_lambda=cond_lambda, tree=tree, bounds=bounds, record=record, pin=pin, candidates=K)
         im.latent_encoder_emb = ctx
         if not record:
             return out
@@ -355,18 +377,20 @@ class GCDenoiser(nn.Module):
         return out, info
 
     @torch.no_grad()
-    def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None, bounds=None, record=False, pin=None):
+    def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None, bounds=None, record=False, pin=None, candidates=None):
         """Whole DDIM loop (reference gc_sampling.py:922-951) as one enqueue on the current stream.  ``cond_lambda``:
         classifier-free guidance weight (None or 1: the unguided call; mdt_sample_ddim_guided).  ``bounds`` is accepted and not
         read, as the reference's DDIM accepts a scaler and never clips; the DDIM head keeps no per-step record.  ``pin``: an
         ``ActionPin`` or its (known, keep) pair of (B, Ta, A) device tensors -- pinned actions (mdt_sample_ddim_opt): every step's
-        denoised value becomes keep * known + (1 - keep) * D inside the action head."""
+        denoised value becomes keep * known + (1 - keep) * D inside the action head.  ``candidates`` = K: K chunks per
+        observation from one encoded context (mdt_sample_ddim_multi), with the shapes ``sample_native`` documents."""
         if record:
             raise NotImplementedError("sample_ddim keeps no per-step record; run the host loop with a callback")
         im = self.inner_model
+        K = candidate_count(candidates)
         if pin is not None and callable(getattr(pin, "on", None)):
-            pin = pin.on(action.device, action.shape)
+            pin = pin.on(action.device, (action.numel() // (action.shape[-2] * action.shape[-1]),) + tuple(action.shape[-2:]), K)
         out, ctx = self._engine(state=state).sample_ddim(state, action, im._goals(goal, False), sigmas, cond_lambda=cond_lambda,
-                                                         pin=pin)
+                                                         pin=pin, candidates=K)
         im.latent_encoder_emb = ctx
         return out

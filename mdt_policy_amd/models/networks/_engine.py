@@ -59,6 +59,36 @@ def rollout_controls(cond_lambda=None, pin=None, **other):
     return native, lam, pin
 
 
+def candidate_count(candidates=None) -> int:
+    """The one reading of ``candidates``: action chunks per observation as an int >= 1 (None: 1).  Anything else raises ValueError,
+    before anything is enqueued."""
+    if candidates is None:
+        return 1
+    if isinstance(candidates, bool) or not isinstance(candidates, int) or candidates < 1:
+        raise ValueError(f"candidates must be an int >= 1, got {candidates!r}")
+    return candidates
+
+
+def take_candidates(extra_args):
+    """(K, the other keys) of a sampler's ``extra_args``: ``candidates`` comes off in front of ``rollout_controls`` and ``guidance``,
+    which keep their signatures -- alone or with a weight and / or a pin it rides in the native call."""
+    rest = dict(extra_args or {})
+    return candidate_count(rest.pop("candidates", None)), rest
+
+
+def chunk_rows(action: torch.Tensor, B: int, K: int) -> torch.Tensor:
+    """``action`` of a call with K candidates for each of B observations, (B*K, Ta, A) or (B, K, Ta, A), as its (B*K, Ta, A)
+    chunks (observation-major: chunk k of observation b is row b*K + k).  A leading size that is not B*K raises ValueError."""
+    if action.dim() == 4:
+        if tuple(action.shape[:2]) != (B, K):
+            raise ValueError(f"action is {tuple(action.shape)}: {B} observations at candidates={K} take ({B}, {K}, Ta, A) "
+                             f"or ({B * K}, Ta, A)")
+        return action.reshape((B * K,) + tuple(action.shape[2:]))
+    if action.shape[0] != B * K:
+        raise ValueError(f"action holds {action.shape[0]} chunks, {B} observations at candidates={K} take {B * K}")
+    return action
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -278,18 +308,24 @@ class HipEngine:
 
     # -- the sampler calls: one path to C.  mdt_sample_opt / mdt_sample_ddim_opt (and their _dev forms) state every other entry --
     def _sampler_inputs(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas=None, n_steps: Optional[int] = None,
-                        noise: Optional[torch.Tensor] = None):
+                        noise: Optional[torch.Tensor] = None, candidates: int = 1):
         """What every sampler call starts from, once: the parameters in sync, the inputs as the C ABI takes them (tok, tok2, g,
         x, and nz: ``noise`` as (n_noise, B, Ta, A) or None), the outputs (out, ctx) and the schedule -- sig, its C argument
         sig_arg, dev (on the device: read in place, no copy to the host, no synchronisation) and n (one less than the levels, or
-        ``n_steps``).  The caller holds the result until its C call has returned: a converted input lives nowhere else, and
+        ``n_steps``).  ``candidates`` = K: p.B observations, p.K and p.N = B*K chunks -- x, nz and out are per chunk (out in the
+        shape x_T came in, (B*K, Ta, A) or (B, K, Ta, A)), tok, tok2, g and ctx per observation.  The caller holds the result until its C call has returned: a converted input lives nowhere else, and
         what the enqueued kernels read must not go back to the allocator before they are enqueued.  Bumps ctx_generation."""
         self.sync_params()
         p = SimpleNamespace(modality=self._modality(state), sig=None, sig_arg=None, dev=False, n=None)
         p.tok, p.tok2, p.B = self._tokens(state)
-        p.g, p.x = self._goal(goal, p.B), self._in(x_T, (p.B, self.Ta, self.A))
-        p.nz = None if noise is None else self._in(noise, (-1, p.B, self.Ta, self.A))
-        p.out = torch.empty((p.B, self.Ta, self.A), device=self.device, dtype=torch.float32)
+        p.K = candidate_count(candidates)
+        p.N = p.B * p.K
+        if p.K != 1 or x_T.dim() == 4:
+            chunk_rows(x_T, p.B, p.K)
+        p.g, p.x = self._goal(goal, p.B), self._in(x_T, (p.N, self.Ta, self.A))
+        p.nz = None if noise is None else self._in(noise, (-1, p.N, self.Ta, self.A))
+        p.out = torch.empty((p.B, p.K, self.Ta, self.A) if x_T.dim() == 4 else (p.N, self.Ta, self.A), device=self.device,
+                            dtype=torch.float32)
         p.ctx = torch.empty((p.B, self.Te, self.D), device=self.device, dtype=torch.float32)
         if sigmas is not None:
             p.dev = torch.is_tensor(sigmas) and sigmas.device.type == "cuda"
@@ -304,16 +340,20 @@ class HipEngine:
         self.ctx_generation += 1
         return p
 
-    def _opts(self, B: int, cond_lambda=None, bounds=None, record=None, tree=None, pin=None):
+    def _chunks(self, x_T: torch.Tensor) -> int:
+        return x_T.numel() // (self.Ta * self.A)
+
+    def _opts(self, B: int, cond_lambda=None, bounds=None, record=None, tree=None, pin=None, candidates: int = 1):
         """mdt_sample_opts of a call as (the C argument, what it points to).  Nothing asked for: (None, ()), the entries' NULL --
         the plain call, and no struct is built for it.  ``bounds`` (lo, hi): fp32 (A,) tensors on the device; ``record``: the
-        (steps, 2, B, Ta, A) tensor to fill; ``tree``: (seeds, tol, lo, hi); ``pin``: (known, keep), fp32 (B, Ta, A) on the device."""
+        (steps, 2, B, Ta, A) tensor to fill; ``tree``: (seeds, tol, lo, hi); ``pin``: (known, keep), fp32 (B, Ta, A) on the device.  ``B`` counts chunks; with
+        ``candidates`` = K > 1 a pin of (B / K, Ta, A) is per observation and goes to each of its K chunks."""
         lam = guidance(cond_lambda)[1]
         if lam is None and bounds is None and record is None and tree is None and pin is None:
             return None, ()
         lo = hi = src = seeds = known = keep = None
         if pin is not None:
-            known, keep = self._pin(pin, B)
+            known, keep = self._pin(pin, B, candidates)
         if bounds is not None:
             lo, hi = (self._in(b, (self.A,)) for b in bounds)
         if tree is not None:
@@ -325,12 +365,16 @@ class HipEngine:
                                None if src is None else C.pointer(src), _ptr(known), _ptr(keep))
         return C.byref(opts), (opts, lo, hi, src, seeds, known, keep)
 
-    def _pin(self, pin, B: int):
+    def _pin(self, pin, B: int, candidates: int = 1):
         """A pin's (known, keep) as the C ABI takes them: contiguous fp32 (B, Ta, A) on the device (a float's alignment will do)."""
         out = []
         for t in pin:
             if t.device != self.device:
                 raise RuntimeError(f"pin tensor on {t.device}, model on {self.device}")
+            if candidates > 1 and tuple(t.shape) == (B // candidates, candidates, self.Ta, self.A):
+                t = t.reshape(B, self.Ta, self.A)
+            elif candidates > 1 and tuple(t.shape) == (B // candidates, self.Ta, self.A):
+                t = t.repeat_interleave(candidates, 0)  # per observation: the same pin for each of its chunks
             if tuple(t.shape) != (B, self.Ta, self.A):
                 raise ValueError(f"pin tensors must be ({B},{self.Ta},{self.A}), got {tuple(t.shape)}")
             t = t.detach()
@@ -338,23 +382,30 @@ class HipEngine:
         return tuple(out)
 
     def sample_ddim(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, cond_lambda: Optional[float] = None,
-                    pin=None):
-        """Fused sampler call (mdt_sample_ddim_opt / mdt_sample_ddim_dev_opt).  ``sigmas`` may live on the host (gc_sampling's
+                    pin=None, candidates: int = 1):
+        """Fused sampler call (mdt_sample_ddim_opt / mdt_sample_ddim_dev_opt; ``candidates`` = K > 1: mdt_sample_ddim_multi /
+        _dev_multi -- K chunks per observation from one encoded context, x_T (B*K, Ta, A) or (B, K, Ta, A)).  ``sigmas`` may live on the host (gc_sampling's
         default) or on the model's device -- the agent builds its schedule there (mdtv_agent.py:660-667); a device schedule is
         consumed in place: no copy to the host, no synchronisation.  ``cond_lambda`` (not None or 1): classifier-free guidance.
         ``pin``: None or (known, keep), fp32 (B, Ta, A) tensors on the device, read when the kernels run -- pinned actions.
         Without either the call passes no options: the plain mdt_sample_ddim call."""
-        opts, held = self._opts(x_T.shape[0], cond_lambda, pin=pin)
-        p = self._sampler_inputs(state, x_T, goal, sigmas)
+        K = candidate_count(candidates)
+        opts, held = self._opts(self._chunks(x_T), cond_lambda, pin=pin, candidates=K)
+        p = self._sampler_inputs(state, x_T, goal, sigmas, candidates=K)
         self._keep = (p.sig, None) + held  # the kernels that read them are only enqueued
-        _lib.call(self.lib.mdt_sample_ddim_dev_opt if p.dev else self.lib.mdt_sample_ddim_opt, self.handle, _ptr(p.tok),
-                  _ptr(p.tok2), _ptr(p.g), p.modality, _ptr(p.x), p.sig_arg, p.n, p.B, _ptr(p.out), _ptr(p.ctx), opts, self._stream())
+        head = (self.handle, _ptr(p.tok), _ptr(p.tok2), _ptr(p.g), p.modality, _ptr(p.x), p.sig_arg, p.n, p.B)
+        tail = (_ptr(p.out), _ptr(p.ctx), opts, self._stream())
+        if K == 1:
+            _lib.call(self.lib.mdt_sample_ddim_dev_opt if p.dev else self.lib.mdt_sample_ddim_opt, *head, *tail)
+        else:
+            _lib.call(self.lib.mdt_sample_ddim_dev_multi if p.dev else self.lib.mdt_sample_ddim_multi, *head, K, *tail)
         return p.out, p.ctx
 
     def sample_native(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
                       noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cond_lambda: Optional[float] = None,
-                      tree=None, bounds=None, record: bool = False, pin=None):
-        """One call of another sampler (mdt_sample_opt / mdt_sample_dev_opt): ``kind`` an mdt_sampler_kind, ``params`` an
+                      tree=None, bounds=None, record: bool = False, pin=None, candidates: int = 1):
+        """One call of another sampler (mdt_sample_opt / mdt_sample_dev_opt; ``candidates`` = K > 1: mdt_sample_multi / _dev_multi,
+        where x_T, the noise rows, the pin, the record and the tree's seeds are per chunk, B*K of them): ``kind`` an mdt_sampler_kind, ``params`` an
         _lib.SamplerParams, ``noise`` None or (n_noise, B, Ta, A) in the Python loop's draw order, ``n_steps`` None (one less
         than the levels) or dpm_fast's evaluation count.  Like sample_ddim, a device schedule is read in place (no copy, no
         synchronisation).  ``cond_lambda`` (not None or 1): classifier-free guidance.  ``tree``: None or (seeds, tol, lo, hi) --
@@ -368,13 +419,18 @@ class HipEngine:
         rec = None
         if record:
             steps = len(sigmas) - 1 if n_steps is None else int(n_steps) // 3 + 1  # n_steps: dpm_fast's evaluation count
-            rec = torch.empty((steps, 2, x_T.shape[0], self.Ta, self.A), device=self.device, dtype=torch.float32)
-        opts, held = self._opts(x_T.shape[0], cond_lambda, bounds, rec, tree, pin)
-        p = self._sampler_inputs(state, x_T, goal, sigmas, n_steps, noise)
+            rec = torch.empty((steps, 2) + tuple(x_T.shape[:-2]) + (self.Ta, self.A), device=self.device, dtype=torch.float32)
+        K = candidate_count(candidates)
+        opts, held = self._opts(self._chunks(x_T), cond_lambda, bounds, rec, tree, pin, candidates=K)
+        p = self._sampler_inputs(state, x_T, goal, sigmas, n_steps, noise, candidates=K)
         self._keep = (p.sig, p.nz) + held  # the kernels that read them are only enqueued
-        _lib.call(self.lib.mdt_sample_dev_opt if p.dev else self.lib.mdt_sample_opt, self.handle, _ptr(p.tok), _ptr(p.tok2),
-                  _ptr(p.g), p.modality, _ptr(p.x), int(kind), C.byref(params), p.sig_arg, p.n, _ptr(p.nz),
-                  0 if p.nz is None else p.nz.shape[0], p.B, _ptr(p.out), _ptr(p.ctx), opts, self._stream())
+        head = (self.handle, _ptr(p.tok), _ptr(p.tok2), _ptr(p.g), p.modality, _ptr(p.x), int(kind), C.byref(params), p.sig_arg, p.n,
+                _ptr(p.nz), 0 if p.nz is None else p.nz.shape[0], p.B)
+        tail = (_ptr(p.out), _ptr(p.ctx), opts, self._stream())
+        if K == 1:
+            _lib.call(self.lib.mdt_sample_dev_opt if p.dev else self.lib.mdt_sample_opt, *head, *tail)
+        else:
+            _lib.call(self.lib.mdt_sample_dev_multi if p.dev else self.lib.mdt_sample_multi, *head, K, *tail)
         return p.out, p.ctx, rec
 
     def sample_dpm_adaptive(self, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigma_min: float, sigma_max: float,

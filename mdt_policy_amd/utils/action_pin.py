@@ -70,8 +70,10 @@ class ActionPin:
             keep[j] = 1.0 if j < hard else 1.0 - (j - hard + 1) / (soft + 1)
         return cls(known, keep.to(prev.device))
 
-    def on(self, device, shape) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(known, keep) as contiguous fp32 tensors of ``shape`` = (B, Ta, A) on ``device``."""
+    def on(self, device, shape, candidates: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(known, keep) as contiguous fp32 tensors of ``shape`` = (B, Ta, A) on ``device``.  ``candidates`` = K > 1: the B chunks
+        are K per observation (chunk k of observation b is row b*K + k); a pin that fits (B, Ta, A) is per chunk and passes
+        through, one that fits (B / K, Ta, A) is per observation and goes to each of that observation's K chunks."""
         shape = tuple(int(v) for v in shape)
         if len(shape) != 3:
             raise ValueError(f"ActionPin: the action chunk must be (B, Ta, A), got {shape}")
@@ -79,13 +81,17 @@ class ActionPin:
             known = torch.broadcast_to(self.known.to(device), shape)
             keep = torch.broadcast_to(self.keep.to(device), shape)
         except RuntimeError as exc:
+            if candidates > 1 and shape[0] % candidates == 0:
+                known, keep = self.on(device, (shape[0] // candidates,) + shape[1:])
+                return known.repeat_interleave(candidates, 0), keep.repeat_interleave(candidates, 0)
             raise ValueError(f"ActionPin: known {tuple(self.known.shape)} / keep {tuple(self.keep.shape)} do not fit an action "
                              f"chunk of {shape}") from exc
         return known.contiguous(), keep.contiguous()
 
-    def apply(self, denoised: torch.Tensor) -> torch.Tensor:
-        """D' of a denoised chunk D, by the rule above (what GCDenoiser.forward and the host loops compute)."""
-        known, keep = self.on(denoised.device, denoised.shape)
+    def apply(self, denoised: torch.Tensor, candidates: int = 1) -> torch.Tensor:
+        """D' of a denoised chunk D, by the rule above (what GCDenoiser.forward and the host loops compute).  ``candidates``: as
+        in ``on``."""
+        known, keep = self.on(denoised.device, denoised.shape, candidates)
         known, keep = known.to(denoised.dtype), keep.to(denoised.dtype)
         return torch.where(keep == 0, denoised, torch.where(keep == 1, known, denoised + keep * (known - denoised)))
 
