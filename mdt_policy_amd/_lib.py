@@ -130,6 +130,17 @@ class DpmControl(C.Structure):
 DPM_REJECT, DPM_ACCEPT, DPM_STOP = 0, 1, 2
 
 
+class LoglikParams(C.Structure):
+    """mdt_loglik_params (include/mdt_hip_train.h)."""
+    _fields_ = [("size", C.c_int32), ("probes", C.c_int32), ("rtol", C.c_double), ("atol", C.c_double),
+                ("max_steps", C.c_int32), ("pad", C.c_int32)]
+
+
+class LoglikInfo(C.Structure):
+    """mdt_loglik_info (include/mdt_hip_train.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("fevals", "steps", "n_accept", "n_reject")]
+
+
 class LnTrainArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("b", C.c_void_p), ("mod", C.c_void_p), ("mod_stride", C.c_int64),
                 ("shift_off", C.c_int32), ("scale_off", C.c_int32), ("rows_per_sample", C.c_int32),
@@ -325,6 +336,11 @@ SYMBOLS = [
     ("mdt_train_encode_bwd", _I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("mdt_tape_release", _I32, [_VP, _I32]),
     ("mdt_denoise_vjp", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _I64, _VP, _VP, _VP]),
+    ("mdt_log_likelihood", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _F, _F, _I64, _I32, C.POINTER(LoglikParams), _VP, _VP, _VP,
+                                  C.POINTER(LoglikInfo), _VP]),
+    ("mdt_dopri5_h0", C.c_double, [C.c_double, C.c_double]),
+    ("mdt_dopri5_h1", C.c_double, [C.c_double, C.c_double, C.c_double]),
+    ("mdt_dopri5_next", C.c_double, [C.c_double, C.c_double, C.POINTER(_I32)]),
     ("mdt_train_denoise_fwd", _I32, [_VP, _VP, _VP, _VP, _I64, C.POINTER(Dropout), _VP, C.POINTER(_I32), _VP]),
     ("mdt_train_denoise_bwd", _I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("mdt_op_pack_weight_t", _I32, [_VP, _I64, _I64, _I64, _VP, _I64, _I64, _VP]),
@@ -496,6 +512,27 @@ def dpm_adaptive_plan(order, s, t) -> SamplerPlan:
     plan = SamplerPlan()
     check(load().mdt_dpm_adaptive_plan(int(order), float(s), float(t), C.byref(plan)))
     return plan
+
+
+def loglik_params(probes=1, rtol=1e-4, atol=1e-4, max_steps=10000) -> LoglikParams:
+    """mdt_loglik_params with log_likelihood's defaults."""
+    return LoglikParams(C.sizeof(LoglikParams), int(probes), float(rtol), float(atol), int(max_steps), 0)
+
+
+def dopri5_start(d0, d1):
+    """mdt_dopri5_h0: the first guess of _dopri5's starting step."""
+    return load().mdt_dopri5_h0(float(d0), float(d1))
+
+
+def dopri5_start_refine(h0, d1, d2):
+    """mdt_dopri5_h1: the starting step from the guess h0 and the probe evaluation's norm d2 (not yet divided by h0)."""
+    return load().mdt_dopri5_h1(float(h0), float(d1), float(d2))
+
+
+def dopri5_next(h, ratio):
+    """mdt_dopri5_next: (the next step size, whether the attempt at ``h`` with scaled error ``ratio`` is accepted)."""
+    acc = C.c_int32()
+    return load().mdt_dopri5_next(float(h), float(ratio), C.byref(acc)), bool(acc.value)
 
 
 class DpmController:

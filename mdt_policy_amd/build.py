@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(CSRC, "libmdt_hip.so")
-SOURCES = ["mdt_kernels.hip", "mdt_model.hip", "mdt_brownian.hip", "mdt_resampler.hip", "mdt_map_pool.hip", "mdt_mae.hip", "mdt_infonce.hip", "mdt_train_kernels.hip", "mdt_train_ops.hip", "mdt_train.hip"]
+SOURCES = ["mdt_kernels.hip", "mdt_model.hip", "mdt_brownian.hip", "mdt_resampler.hip", "mdt_map_pool.hip", "mdt_mae.hip", "mdt_infonce.hip", "mdt_train_kernels.hip", "mdt_train_ops.hip", "mdt_train.hip", "mdt_loglik.hip"]
 ARCH = "gfx950"
 
 
@@ -25,7 +25,7 @@ def _hipcc() -> str:
     return exe
 
 
-HEADERS = ["mdt_internal.h", "mdt_launch.h", "mdt_handle.h", "mdt_device.h", "mdt_model_types.h", "mdt_tiles.h", "mdt_tall.h", "mdt_ws.h", "mdt_mlp_split.h", "mdt_sampler_plan.h", "mdt_brownian.h"]
+HEADERS = ["mdt_internal.h", "mdt_launch.h", "mdt_handle.h", "mdt_device.h", "mdt_model_types.h", "mdt_tiles.h", "mdt_tall.h", "mdt_ws.h", "mdt_mlp_split.h", "mdt_sampler_plan.h", "mdt_brownian.h", "mdt_loglik.h"]
 PUBLIC_HEADERS = ["mdt_hip.h", "mdt_hip_ops.h", "mdt_resampler.h", "mdt_map_pool.h", "mdt_hip_train.h", "mdt_mae.h", "mdt_hip_debug.h"]
 
 

@@ -97,6 +97,11 @@ struct mdt_model {
     float* ad_ws = nullptr;
     int64_t ad_cap = 0;
     void* ad_host = nullptr;
+    // mdt_log_likelihood (mdt_loglik.hip): the integrator's state, stage and probe buffers at (rows, probes), grown by
+    // mdt_grow_carve, and the pinned host block its norm partials come back into
+    float* ll_ws = nullptr;
+    int64_t ll_rows = 0, ll_probes = 0;
+    void* ll_host = nullptr;
     // mdt_sample_sde_tree*: the plan's noise-row points (mdt_tree_q) and the rows (tr_rows, tr_nel) k_brownian_fill writes, grown by
     // mdt_grow_carve
     float* tr_ws = nullptr;

@@ -20,6 +20,7 @@
 #include <utility>
 #include <vector>
 
+#include "mdt_loglik.h"
 #include "mdt_model_types.h"
 
 #define fail mdt_fail
@@ -590,7 +591,7 @@ static mdt_status dec_fwd_pre(mdt_model* m, Tape& t, const float* action, const 
 }
 
 static mdt_status dec_fwd(mdt_model* m, Tape& t, const float* action, const float* noise, const float* sigma, float* loss_out,
-                          float* model_output, hipStream_t s, bool pre_done = false) {
+                          float* model_output, hipStream_t s, bool pre_done = false, bool kv_done = false) {
     const int D = m->D, Ta = m->Ta, A = m->A;
     const int64_t B = t.B, Ma = B * Ta;
     // conditioning rows of the decoder blocks: adaLN-Zero (B, Ld*6D), NoiseBlock (B, D) = c, sigma token: none
@@ -598,8 +599,8 @@ static mdt_status dec_fwd(mdt_model* m, Tape& t, const float* action, const floa
     const int64_t mod_blk = m->cond == COND_ADALN ? 6 * D : 0;  // a block's offset in the row
     if (!pre_done) MDT_TRY(dec_fwd_pre(m, t, action, noise, sigma, s));
     const int per = Ta * A;
-    // cross-attention K|V of all decoder blocks
-    LAUNCH(mdt_launch_gemm(gemm_args(t.ctx, D, m->kv_all, t.kvx, (int64_t)m->Ld * 2 * D, (int)(B * m->Te)), s));
+    // cross-attention K|V of all decoder blocks (kv_done: the caller staged t.kvx -- mdt_ll_context, once for many forwards)
+    if (!kv_done) LAUNCH(mdt_launch_gemm(gemm_args(t.ctx, D, m->kv_all, t.kvx, (int64_t)m->Ld * 2 * D, (int)(B * m->Te)), s));
     for (int l = 0; l < m->Ld; ++l) t.dec[l].x_in = l == 0 ? t.y0 : t.dec[l - 1].x3;
     float* xl = t.dec[m->Ld - 1].x3;
     const mdt_ln_train_args lh = ln_args(xl, m->dec_ln_w, m->dec_ln_b, t.lnout, t.st_h, (int)Ma, D);
@@ -1330,5 +1331,74 @@ extern "C" mdt_status mdt_denoise_vjp(mdt_model* m, const float* tokens, const f
     }
     (void)mdt_tape_release(m, id);
     if (st == MDT_OK) st = scratch_leave(m, s);
+    return st;
+}
+
+// ------------------------------------------------------------------------------------------------
+// mdt_log_likelihood's pieces of this path (mdt_loglik.h; the integrator and the entry point are in mdt_loglik.hip): the encoder
+// and the stacked cross K|V product on the B observations, the decoder forward on the R = B*K chunks against K|V rows staged
+// once, and mdt_denoise_vjp's backward as often as there are probes over that one tape -- it reads the tape and writes only the
+// handle's backward scratch.
+// ------------------------------------------------------------------------------------------------
+mdt_status mdt_ll_check(mdt_model* m, const char* fn) {
+    MDT_TRY(check_ready(m));
+    const mdt_train_state* ts = m->train;
+    if (ts->bwd_next > 0)
+        return fail(MDT_ERR_STATE, "%s: a staged loss backward of tape %d is under way on this handle (stage %d is next)", fn,
+                    ts->bwd_tape, ts->bwd_next);
+    return MDT_OK;
+}
+
+mdt_status mdt_ll_open(mdt_model* m, int64_t B, int K, hipStream_t s, mdt_ll_run* r) {
+    r->B = B; r->K = K; r->enc = r->dec = -1;
+    MDT_TRY(acquire_tape(m, B, &r->enc, s));
+    m->train->tapes[r->enc].drop = effective_dropout(nullptr);  // eval-mode forward: D(x; sigma) itself
+    MDT_TRY(acquire_tape(m, B * K, &r->dec, s));
+    m->train->tapes[r->dec].drop = effective_dropout(nullptr);
+    m->train->tapes[r->dec].dec_only = true;
+    MDT_TRY(scratch_enter(m, s));
+    return reserve_scratch(m, B * K);
+}
+
+mdt_status mdt_ll_context(mdt_model* m, const mdt_ll_run& r, const float* tokens, const float* tokens2, const float* goal,
+                          int modality, const float* sigma, hipStream_t s) {
+    Tape &te = m->train->tapes[r.enc], &td = m->train->tapes[r.dec];
+    const int honour = m->cfg.arch == MDT_ARCH_MDTV;
+    const int64_t w = (int64_t)m->Ld * 2 * m->D;
+    MDT_TRY(enc_fwd(m, te, tokens, tokens2, goal, modality, honour, sigma, nullptr, s));
+    float* kv = r.K == 1 ? td.kvx : te.kvx;
+    LAUNCH(mdt_launch_gemm(gemm_args(te.ctx, m->D, m->kv_all, kv, w, (int)(r.B * m->Te)), s));
+    if (r.K > 1) LAUNCH(mdt_launch_ll_repeat_rows(te.kvx, td.kvx, r.B, r.K, (int64_t)m->Te * w, s));
+    return MDT_OK;
+}
+
+mdt_status mdt_ll_forward(mdt_model* m, const mdt_ll_run& r, const float* x, const float* sigma, hipStream_t s) {
+    Tape& t = m->train->tapes[r.dec];
+    // with the sigma token the encoder ran the sigma MLP on its own tape; the decoder still reads sigma for the scalings
+    if (m->cond == COND_TOKEN) HIP_TRY(hipMemcpyAsync(t.sigma, sigma, (size_t)t.B * sizeof(float), hipMemcpyDeviceToDevice, s));
+    // action := x, no noise: the tape's "noised" rows are x itself, F the raw network output
+    return dec_fwd(m, t, x, nullptr, sigma, nullptr, nullptr, s, false, true);
+}
+
+mdt_status mdt_ll_vjp(mdt_model* m, const mdt_ll_run& r, const float* v, float* denoised, float* vjp, hipStream_t s) {
+    Tape& t = m->train->tapes[r.dec];
+    mdt_train_state* ts = m->train;
+    const int64_t n = t.B * m->Ta * m->A;
+    const int per = m->Ta * m->A;
+    ts->dy_off = 0;
+    // D = c_skip x + c_out F;  dF = c_out v
+    LAUNCH(mdt_launch_denoise_seed(t.F, t.noised, t.sigma, v, m->cfg.sigma_data, n, per, denoised, ts->dF, s));
+    MDT_TRY(dec_bwd(m, t, nullptr, s));
+    // y0 = action_emb(c_in x): d x = c_in (d y0 . Wa) + c_skip v
+    LAUNCH(mdt_launch_narrow_out(ts->dx, m->D, m->Wa, ts->small, (int)(t.B * m->Ta), m->A, m->D, s));
+    LAUNCH(mdt_launch_denoise_finish(ts->small, t.sigma, v, m->cfg.sigma_data, n, per, vjp, s));
+    return MDT_OK;
+}
+
+mdt_status mdt_ll_close(mdt_model* m, const mdt_ll_run& r, hipStream_t s) {
+    mdt_status st = MDT_OK;
+    for (mdt_tape_id id : {r.dec, r.enc})
+        if (id >= 0 && m->train->tapes[id].in_use && m->train->tapes[id].release() != MDT_OK) st = MDT_ERR_HIP;
+    if (r.dec >= 0 && scratch_leave(m, s) != MDT_OK) st = MDT_ERR_HIP;
     return st;
 }

@@ -9,6 +9,8 @@ exposes its bounds (``clip_bounds``, utils/action_bounds.py ActionBounds: the ca
 sample_dpm_fast (1..128 evaluations); sample_dpm_adaptive with eta = 0 on the GPU is one blocking call
 (``GCDenoiser.sample_dpm_adaptive_native`` -> mdt_sample_dpm_adaptive).  Otherwise they are host loops over
 ``model(state, x, goal, sigma)`` (the HIP denoiser step) with the sigma-independent encoder hoisted out of the loop.
+``log_likelihood`` with this package's GCDenoiser is one blocking call too (``GCDenoiser.log_likelihood`` ->
+mdt_log_likelihood), for K chunks per observation and P probes; ``best_candidates`` picks from its result.
 
 Signatures follow the reference: ``sample_*(model, state, action, goal, sigmas, scaler=None, extra_args=None,
 callback=None, disable=None, ...)``.
@@ -25,7 +27,7 @@ import torch
 
 from . import utils
 from ... import _lib
-from ..networks._engine import chunk_rows, rollout_controls, take_candidates
+from ..networks._engine import candidate_count, chunk_rows, rollout_controls, take_candidates
 from .graphed import GraphedDDIM, GraphedSampler
 from .score_wrappers import GCDenoiser
 
@@ -1169,12 +1171,12 @@ def _scaled_rms(parts, scale_parts):
     return math.sqrt(num / sum(p.numel() for p in parts))
 
 
-def _dopri5(fn, y0, t0, t1, rtol, atol, max_steps=10000):
+def _dopri5(fn, y0, t0, t1, rtol, atol, max_steps=10000, stats=None):
     """Adaptive Dormand-Prince 5(4) integration of y' = fn(t, y) from t0 to t1 for a tuple of tensors ``y0``: embedded
     error estimate in a mixed absolute / relative norm, first-same-as-last stage reuse, step controller
     h <- h * clip(0.9 * err^(-1/5), 0.2, 10), Hairer's starting step; the last step is shortened to end on t1.  The role
     torchdiffeq.odeint(..., method='dopri5') plays in the reference (gc_sampling.py:486) -- that package is not a
-    dependency here."""
+    dependency here.  ``stats``: a dict whose 'steps' / 'n_accept' / 'n_reject' count the attempted steps."""
     y = tuple(y0)
     t, direction = float(t0), (1.0 if t1 >= t0 else -1.0)
     k1 = fn(t, y)
@@ -1198,6 +1200,9 @@ def _dopri5(fn, y0, t0, t1, rtol, atol, max_steps=10000):
         err = tuple(h * sum(e * k[j] for e, k in zip(_DP_E, ks) if e != 0.0) for j in range(len(y)))
         scale = tuple(atol + rtol * torch.maximum(p.abs(), q.abs()) for p, q in zip(y, y_new))
         ratio = _scaled_rms(err, scale)
+        if stats is not None:
+            stats['steps'] += 1
+            stats['n_accept' if ratio <= 1.0 else 'n_reject'] += 1
         if ratio <= 1.0:  # accept
             t = t1 if h >= abs(t1 - t) else t + direction * h
             y, k1 = y_new, ks[6]
@@ -1210,36 +1215,90 @@ def _probe_signs(action):
     return torch.randint_like(action, 2) * 2 - 1
 
 
+def _probes(action, probes):
+    """The probe tensors (P, *action.shape) of log_likelihood's ``extra_args['probes']``: an int P >= 1 -- P = 1 is one
+    ``_probe_signs(action)`` draw, as without the key; P > 1 draws all P * action.numel() signs in one call, probe-major -- or
+    the caller's own tensor of that shape, used as given."""
+    if torch.is_tensor(probes):
+        if probes.dim() != action.dim() + 1 or probes.shape[0] < 1 or tuple(probes.shape[1:]) != tuple(action.shape):
+            raise ValueError(f"probes is {tuple(probes.shape)}: {action.shape[0]} chunks take (P, {', '.join(map(str, action.shape))})")
+        return probes.to(device=action.device, dtype=action.dtype)
+    if isinstance(probes, bool) or not isinstance(probes, int) or probes < 1:
+        raise ValueError(f"probes must be an int >= 1 or a tensor of probes, got {probes!r}")
+    if probes == 1:
+        return _probe_signs(action)[None]
+    return _probe_signs(action.new_empty((probes,) + tuple(action.shape)))
+
+
+def best_candidates(chunks, scores, K):
+    """The step after scoring K candidate chunks per observation: (best (B, Ta, A), index (B,)) by per-observation argmax of
+    ``scores`` -- (B*K,) or (B, K), e.g. log_likelihood's -- over ``chunks`` -- (B*K, Ta, A) or (B, K, Ta, A), chunk k of
+    observation b at row b*K + k.  Ties go to the lowest index, NaN scores lose; on the tensors' device, no read-back."""
+    K = candidate_count(K)
+    if scores.numel() % K or chunks.numel() % max(scores.numel(), 1) or chunks.dim() < 3:
+        raise ValueError(f"scores {tuple(scores.shape)} and chunks {tuple(chunks.shape)} do not hold K = {K} candidates per observation")
+    sc = torch.nan_to_num(scores.reshape(-1, K), nan=float("-inf"))
+    B = sc.shape[0]
+    if chunks.numel() // (chunks.shape[-2] * chunks.shape[-1]) != B * K:
+        raise ValueError(f"chunks {tuple(chunks.shape)} hold no {B} x {K} chunks")
+    ks = torch.arange(K, device=sc.device).expand(B, K)
+    index = torch.where(sc == sc.max(1, keepdim=True).values, ks, K - 1).min(1).values
+    rows = chunks.reshape((B, K) + tuple(chunks.shape[-2:]))
+    return rows[torch.arange(B, device=rows.device), index.to(rows.device)], index
+
+
 @torch.no_grad()
 def log_likelihood(model, state, action, goal, sigma_min, sigma_max, extra_args=None, atol=1e-4, rtol=1e-4):
     """log p(action | state, goal) by integrating the probability-flow ODE dx/dsigma = (x - D(x; sigma)) / sigma from
-    sigma_min to sigma_max together with its divergence, estimated with one Rademacher probe v as v^T (d f / d x) v
-    (reference gc_sampling.py:468-490).  Returns (log-likelihood per sample, {'fevals': n}).
+    sigma_min to sigma_max together with its divergence, estimated with Rademacher probes v as v^T (d f / d x) v
+    (reference gc_sampling.py:468-490).  Returns (log-likelihood per sample, {'fevals', 'steps', 'n_accept', 'n_reject'}).
 
-    With this package's GCDenoiser the denoiser value and the vector-Jacobian product (dD/dx)^T v come from one HIP
-    forward + input-gradient-only backward (``mdt_denoise_vjp``); any other model is differentiated with
-    torch.autograd, as in the reference."""
-    extra_args = {} if extra_args is None else extra_args
-    v = _probe_signs(action)
-    fevals = 0
-    hip = isinstance(model, GCDenoiser) and not extra_args
+    ``extra_args`` keys read here:
+      'probes'     -- an int P >= 1 (default 1, the reference's single draw) or a tensor (P, *action.shape) of the caller's own
+                      probes: the divergence estimate is the mean over the P probes.
+      'candidates' -- K chunks for each of the B observations of ``state`` / ``goal``: ``action`` is (B*K, Ta, A) or
+                      (B, K, Ta, A), chunk k of observation b at row b*K + k, and the result is (B*K,) or (B, K) to match
+                      (``best_candidates`` picks from it).  A leading size other than B*K raises ValueError.
+
+    With this package's GCDenoiser the whole integration is one blocking native call (``GCDenoiser.log_likelihood`` ->
+    mdt_log_likelihood): the encoder runs once on the B observations, each evaluation is a decoder forward on the B*K chunks
+    and one input-gradient-only backward per probe, and the Dormand-Prince loop reads one number back per attempted step.  One
+    step size serves the whole call, so a chunk's value depends on its batch-mates at the integrator's tolerance.  Any further
+    key (cond_lambda, pin) raises NotImplementedError.  Any other model is differentiated with torch.autograd in the host
+    loop, as in the reference, and gets the other keys; it has no shared context to exploit, so 'candidates' raises
+    ValueError."""
+    rest = dict(extra_args or {})
+    has_k = "candidates" in rest
+    K, rest = take_candidates(rest)
+    probes = rest.pop("probes", 1)
+    if isinstance(model, GCDenoiser):
+        if rest:
+            raise NotImplementedError(f"log_likelihood: extra_args[{sorted(rest)[0]!r}] is not supported with GCDenoiser "
+                                      "(the native call scores the unguided, unpinned model; keys read: 'candidates', 'probes')")
+        rows, _ = _chunk_view(state, action, None, K)
+        ll, _, _, info = model.log_likelihood(state, rows, goal, _probes(rows, probes), sigma_min, sigma_max, candidates=K,
+                                              rtol=rtol, atol=atol)
+        return ll.reshape(action.shape[:-2]), info
+    if has_k:
+        raise ValueError("log_likelihood: 'candidates' needs this package's GCDenoiser (a foreign model has no shared context to "
+                         "exploit): expand the observations and score the chunks as a batch")
+    v = _probes(action, probes)
+    P = v.shape[0]
+    info = {'fevals': 0, 'steps': 0, 'n_accept': 0, 'n_reject': 0}
 
     def flow(sigma, y):
-        nonlocal fevals
-        x = y[0]
-        fevals += 1
-        if hip:
-            sg = torch.full((x.shape[0],), sigma, device=x.device, dtype=x.dtype)
-            denoised, jtv = model.denoise_vjp(state, x, goal, sg, v)
-            grad = (v - jtv) / sigma  # d/dx of sum(((x - D(x)) / sigma) * v)
-        else:
-            with torch.enable_grad():
-                x = x.detach().requires_grad_()
-                denoised = model(state, x, goal, x.new_full((x.shape[0],), sigma), **extra_args)
-                grad = torch.autograd.grad((to_d(x, sigma, denoised) * v).sum(), x)[0]
-        return to_d(x, sigma, denoised).detach(), (v * grad).flatten(1).sum(1)
+        info['fevals'] += 1
+        with torch.enable_grad():
+            x = y[0].detach().requires_grad_()
+            denoised = model(state, x, goal, x.new_full((x.shape[0],), sigma), **rest)
+            d = to_d(x, sigma, denoised)
+            div = 0
+            for p in range(P):
+                grad = torch.autograd.grad((d * v[p]).sum(), x, retain_graph=p + 1 < P)[0]
+                div = div + (v[p] * grad).flatten(1).sum(1)
+        return d.detach(), (div if P == 1 else div / P)
 
     latent, delta_ll = _dopri5(flow, (action, action.new_zeros([action.shape[0]])), float(sigma_min), float(sigma_max),
-                               rtol, atol)
+                               rtol, atol, stats=info)
     ll_prior = torch.distributions.Normal(0, sigma_max).log_prob(latent).flatten(1).sum(1)
-    return ll_prior + delta_ll, {'fevals': fevals}
+    return ll_prior + delta_ll, info

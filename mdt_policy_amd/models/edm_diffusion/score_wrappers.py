@@ -317,6 +317,19 @@ class GCDenoiser(nn.Module):
         return self._engine(state=state).denoise_vjp(state, action, im._goals(goal, False), sigma, v)
 
     @torch.no_grad()
+    def log_likelihood(self, state, action, goal, v, sigma_min, sigma_max, candidates=None, rtol=1e-4, atol=1e-4, max_steps=10000):
+        """gc_sampling.log_likelihood's integration as one blocking native call (mdt_log_likelihood): the encoder and the cross
+        K|V product once on the B observations of ``state`` / ``goal``, every evaluation one decoder forward on the B*K chunks of
+        ``action`` -- (B*K, Ta, A) or (B, K, Ta, A), ``candidates`` = K -- and one input-gradient-only backward per probe tensor
+        of ``v`` (P, B*K, Ta, A).  Returns (ll (B*K,), latent (B*K, Ta, A), delta (B*K,), info) with info = {'fevals', 'steps',
+        'n_accept', 'n_reject'}.  One step size serves the whole call: a chunk's value depends on its batch-mates at the
+        integrator's tolerance."""
+        im = self.inner_model
+        return self._engine(state=state).log_likelihood(state, action, im._goals(goal, False), v, float(sigma_min), float(sigma_max),
+                                                        candidates=candidate_count(candidates), rtol=rtol, atol=atol,
+                                                        max_steps=max_steps)
+
+    @torch.no_grad()
     def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, cond_lambda=None, tree=None, bounds=None,
                       record=False, pin=None, candidates=None, **params):
         """One of the other samplers (``kind``: 'euler', 'heun', 'dpmpp_2m', ... -- the gc_sampling function name without

@@ -595,6 +595,33 @@ class HipEngine:
                                             _ptr(s), _ptr(v_), B, _ptr(den), _ptr(vjp), self._stream())
         return den, vjp
 
+    def log_likelihood(self, state: dict, x: torch.Tensor, goal: torch.Tensor, v: torch.Tensor, sigma_min: float, sigma_max: float,
+                       candidates: int = 1, rtol: float = 1e-4, atol: float = 1e-4, max_steps: int = 10000):
+        """mdt_log_likelihood: gc_sampling.log_likelihood's probability-flow integration as one blocking call.  ``state`` and
+        ``goal`` carry B observations, ``x`` the B*K chunks as (B*K, Ta, A) or (B, K, Ta, A) (chunk k of observation b at row
+        b*K + k), ``v`` the probe tensors (P, B*K, Ta, A).  Returns (ll (B*K,), latent (B*K, Ta, A), delta (B*K,), info dict)."""
+        self.train_prepare()
+        self.sync_params()
+        tok, tok2, B = self._tokens(state)
+        K = candidate_count(candidates)
+        R = B * K
+        chunk_rows(x, B, K)
+        g = self._goal(goal, B)
+        x_ = self._in(x, (R, self.Ta, self.A))
+        if v.dim() < 1 or v.numel() == 0 or v.numel() % x_.numel():
+            raise ValueError(f"probes hold {v.numel()} values, {R} chunks take (P, {R}, {self.Ta}, {self.A})")
+        v_ = self._in(v, (-1, R, self.Ta, self.A))
+        params = _lib.loglik_params(probes=v_.shape[0], rtol=rtol, atol=atol, max_steps=max_steps)
+        ll = torch.empty((R,), device=self.device, dtype=torch.float32)
+        latent = torch.empty((R, self.Ta, self.A), device=self.device, dtype=torch.float32)
+        delta = torch.empty((R,), device=self.device, dtype=torch.float32)
+        info = _lib.LoglikInfo()
+        self.ctx_generation += 1
+        _lib.call(self.lib.mdt_log_likelihood, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_), _ptr(v_),
+                                               float(sigma_min), float(sigma_max), B, K, C.byref(params), _ptr(ll), _ptr(latent),
+                                               _ptr(delta), C.byref(info), self._stream())
+        return ll, latent, delta, {k: int(getattr(info, k)) for k in ("fevals", "steps", "n_accept", "n_reject")}
+
     def tape_release(self, tape: int) -> None:
         _lib.check(self.lib.mdt_tape_release(self.handle, tape))
 
