@@ -23,6 +23,20 @@ mdt_status mdt_ll_context(mdt_model* m, const mdt_ll_run& r, const float* tokens
 mdt_status mdt_ll_forward(mdt_model* m, const mdt_ll_run& r, const float* x, const float* sigma, hipStream_t s);
 // over that tape: denoised = D(x; sigma) (optional) and vjp = (dD/dx)^T v; the tape is only read
 mdt_status mdt_ll_vjp(mdt_model* m, const mdt_ll_run& r, const float* v, float* denoised, float* vjp, hipStream_t s);
+// mdt_ll_vjp's backward between a seed and a finish launch of the caller's (mdt_steer.hip swaps both for its own): over the
+// R * Ta * A = n elements, the seed reads the tape (F the raw network output, x the forward's input, sigma per row) and leaves the
+// upstream gradient of F in dF; the finish reads small = d y0 . Wa, the gradient at the network's input c_in x
+struct mdt_ll_io {
+    const float *F, *x, *sigma;
+    float *dF, *small;
+    int64_t n;
+    int per;  // Ta * A
+    float sd;
+};
+typedef hipError_t (*mdt_ll_launch)(const mdt_ll_io& io, void* arg, hipStream_t s);
+mdt_status mdt_ll_backward(mdt_model* m, const mdt_ll_run& r, mdt_ll_launch seed, mdt_ll_launch finish, void* arg, hipStream_t s);
+// the B observations' context (B, Te, D) on the encoder tape, as mdt_ll_context left it
+const float* mdt_ll_ctx(mdt_model* m, const mdt_ll_run& r);
 // tapes released, scratch handed back; safe after a failed open (ids < 0 are skipped)
 mdt_status mdt_ll_close(mdt_model* m, const mdt_ll_run& r, hipStream_t s);
 

@@ -420,6 +420,7 @@ extern "C" mdt_status mdt_destroy(mdt_model* m) {
     (void)mdt_dev_free(m->tr_ws);
     if (m->ad_host) (void)hipHostFree(m->ad_host);
     (void)mdt_dev_free(m->ll_ws);
+    (void)mdt_dev_free(m->st_ws);
     if (m->ll_host) (void)hipHostFree(m->ll_host);
     delete m;
     return MDT_OK;

@@ -1,0 +1,205 @@
+// mdt_steer.hip -- mdt_sample_ddim_steer (include/mdt_hip_train.h): DDIM steered toward known actions through the denoiser's
+// Jacobian, as one enqueue.
+//
+// A steer is (known, weight, beta).  Wherever the sampler used D(x; sigma) it uses
+//     D'(x; sigma) = D + s(sigma) J^T (weight . (known - D)),   J = dD/dx,   s(sigma) = min(beta, 1 + sigma^2 / sigma_data^2)
+// (pseudo-inverse guidance as real-time chunking clips it; e = weight . (known - D) is a constant of the step).  The denoiser and
+// its vector-Jacobian product are the training path's, shared with mdt_log_likelihood (mdt_loglik.h): the encoder and the cross
+// K|V once per call on the B observations (once per step where sigma is a context token), per step one tape-keeping decoder
+// forward on the R = B * K chunks and one input-gradient-only backward over that tape.  This file holds the two kernels that
+// stand where mdt_ll_vjp's seed and finish launches stand -- the seed forms D and e on the way, the finish the steered DDIM
+// update -- and the host loop.  Neither kernel uses atomics, LDS or scratch; every element is written by one thread.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "mdt_hip_train.h"
+#include "mdt_launch.h"
+#include "mdt_loglik.h"
+
+#define fail mdt_fail
+
+namespace {
+
+// Both kernels: 256 threads (four wave64), grid-stride over the N = R * Ta * A elements.  Ta * A = 70 is no multiple of 64 and N
+// rarely one of 256: the bound is per element, and no lane cooperates with another, so a partly filled wave just idles its tail.
+constexpr int STEER_THREADS = 256;
+constexpr int STEER_MAX_BLOCKS = 1024;
+
+unsigned steer_grid(int64_t n) {
+    const int64_t g = (n + STEER_THREADS - 1) / STEER_THREADS;
+    return (unsigned)(g < 1 ? 1 : (g > STEER_MAX_BLOCKS ? STEER_MAX_BLOCKS : g));
+}
+
+// The seed of the backward and the constraint error in one pass over the tape's F and x (k_denoise_seed's arithmetic, sigma
+// shared by all rows): D = c_skip x + c_out F;  e = weight (known - D);  dF = c_out e.
+__global__ __launch_bounds__(STEER_THREADS) void k_steer_seed(const float* __restrict__ F, const float* __restrict__ x,
+                                                              const float* __restrict__ known, const float* __restrict__ weight,
+                                                              float sg, float sd, int64_t N, float* __restrict__ D,
+                                                              float* __restrict__ e, float* __restrict__ dF) {
+    const float den2 = sg * sg + sd * sd;
+    const float c_skip = sd * sd / den2, c_out = sg * sd / sqrtf(den2);
+    for (int64_t i = (int64_t)blockIdx.x * STEER_THREADS + threadIdx.x; i < N; i += (int64_t)gridDim.x * STEER_THREADS) {
+        const float d = fmaf(F[i], c_out, x[i] * c_skip);
+        const float ev = weight[i] * (known[i] - d);
+        D[i] = d;
+        e[i] = ev;
+        dF[i] = c_out * ev;
+    }
+}
+
+// The end of the backward and the steered DDIM step over the N elements, the R per-row sigma entries behind them
+// (k_denoise_finish's arithmetic): g = c_in small + c_skip e;  D' = D + scale g;  x_out = ratio x_in + coef D', clamped to
+// [lo, hi] per action dimension as torch.clamp does (NaN stays, lo > hi gives hi) where bounds are given;  sig_rows = the next
+// forward's sigma.  x_in and x_out may be the same buffer (each element is read and written by its own thread), so neither is
+// __restrict__; x_in is only read.  N == 0: only the sigma rows (the first forward's).
+__global__ __launch_bounds__(STEER_THREADS) void k_steer_step(const float* __restrict__ small, const float* __restrict__ e,
+                                                              const float* __restrict__ D, const float* x_in, float sg, float sd,
+                                                              float scale, float ratio, float coef, const float* __restrict__ lo,
+                                                              const float* __restrict__ hi, int A, float sigma_next, int64_t N,
+                                                              int64_t R, float* x_out, float* __restrict__ sig_rows) {
+    const float den2 = sg * sg + sd * sd;
+    const float c_in = 1.0f / sqrtf(den2), c_skip = sd * sd / den2;
+    for (int64_t i = (int64_t)blockIdx.x * STEER_THREADS + threadIdx.x; i < N + R; i += (int64_t)gridDim.x * STEER_THREADS) {
+        if (i < N) {
+            const float g = fmaf(small[i], c_in, e[i] * c_skip);
+            const float dp = D[i] + scale * g;
+            float v = ratio * x_in[i] + coef * dp;
+            if (lo) {
+                const int a = (int)(i % A);
+                const float l = lo[a], h = hi[a];
+                v = v < l ? l : v;
+                v = v > h ? h : v;
+            }
+            x_out[i] = v;
+        } else {
+            sig_rows[i - N] = sigma_next;
+        }
+    }
+}
+
+// the call's buffers over one device block
+struct SteerBufs {
+    float *x, *D, *e, *sig;
+};
+
+void carve(Bump& b, int64_t rows, int per, SteerBufs* o) {
+    SteerBufs t;
+    t.x = b.take(rows * per); t.D = b.take(rows * per); t.e = b.take(rows * per); t.sig = b.take(rows);
+    if (o) *o = t;
+}
+
+struct Call {
+    mdt_model* m;
+    mdt_ll_run run;
+    hipStream_t s;
+    const float *tokens, *tokens2, *goal, *known, *weight, *lo, *hi;
+    int modality;
+    int64_t R, N;
+    SteerBufs b;
+    // the step under way
+    float sg, scale, ratio, coef, sigma_next;
+    const float* x_in;
+    float* x_out;
+};
+
+hipError_t steer_seed(const mdt_ll_io& io, void* arg, hipStream_t s) {
+    const Call& c = *(const Call*)arg;
+    return mdt_launch_lds<k_steer_seed>(dim3(steer_grid(c.N)), dim3(STEER_THREADS), 0, s, io.F, io.x, c.known, c.weight, c.sg, io.sd,
+                                        c.N, c.b.D, c.b.e, io.dF);
+}
+
+hipError_t steer_step(const mdt_ll_io& io, void* arg, hipStream_t s) {
+    const Call& c = *(const Call*)arg;
+    return mdt_launch_lds<k_steer_step>(dim3(steer_grid(c.N + c.R)), dim3(STEER_THREADS), 0, s, (const float*)io.small,
+                                        (const float*)c.b.e, (const float*)c.b.D, c.x_in, c.sg, io.sd, c.scale, c.ratio, c.coef,
+                                        c.lo, c.hi, c.m->A, c.sigma_next, c.N, c.R, c.x_out, c.b.sig);
+}
+
+// the rows' sigma for the first forward (k_steer_step over no elements)
+mdt_status fill_sigma(Call& c, float sigma) {
+    LAUNCH(mdt_launch_lds<k_steer_step>(dim3(steer_grid(c.R)), dim3(STEER_THREADS), 0, c.s, (const float*)nullptr,
+                                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 1.f, 1.f, 0.f, 0.f, 0.f,
+                                        (const float*)nullptr, (const float*)nullptr, 1, sigma, (int64_t)0, c.R, (float*)nullptr,
+                                        c.b.sig));
+    return MDT_OK;
+}
+
+mdt_status run(Call& c, const float* x_T, const float* sig, int n, float beta, float* out, float* ctx_out) {
+    mdt_model* m = c.m;
+    const float sd = m->cfg.sigma_data;
+    MDT_TRY(fill_sigma(c, sig[0]));
+    if (m->cond != COND_TOKEN) MDT_TRY(mdt_ll_context(m, c.run, c.tokens, c.tokens2, c.goal, c.modality, nullptr, c.s));
+    for (int i = 0; i < n; ++i) {
+        // the DDIM coefficients as the native sampler forms them (k_sample_prep): t = -ln sigma, exp(-t') / exp(-t), -expm1(-(t' - t))
+        const float t = -logf(sig[i]), tn = -logf(sig[i + 1]);
+        c.sg = sig[i];
+        c.ratio = expf(-tn) / expf(-t);
+        c.coef = -expm1f(-(tn - t));
+        c.scale = fminf(beta, 1.f + (sig[i] * sig[i]) / (sd * sd));
+        c.sigma_next = sig[i + 1];
+        c.x_in = i == 0 ? x_T : c.b.x;       // x_T is only read
+        c.x_out = i == n - 1 ? out : c.b.x;
+        if (m->cond == COND_TOKEN)  // sigma is a context token: the context is this step's, still on the B observations
+            MDT_TRY(mdt_ll_context(m, c.run, c.tokens, c.tokens2, c.goal, c.modality, c.b.sig, c.s));
+        MDT_TRY(mdt_ll_forward(m, c.run, c.x_in, c.b.sig, c.s));
+        MDT_TRY(mdt_ll_backward(m, c.run, steer_seed, steer_step, &c, c.s));
+    }
+    if (ctx_out)
+        HIP_TRY(hipMemcpyAsync(ctx_out, mdt_ll_ctx(m, c.run), (size_t)c.run.B * m->Te * m->D * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    return MDT_OK;
+}
+
+}  // namespace
+
+extern "C" mdt_status mdt_sample_ddim_steer(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                            int32_t modality, const float* x_T, const float* sigmas, int32_t n_steps,
+                                            int64_t batch, int32_t candidates, const float* known, const float* weight, float beta,
+                                            const float* lo, const float* hi, float* out, float* ctx_out, void* stream) {
+    const char* fn = "mdt_sample_ddim_steer";
+    if (!m) return fail(MDT_ERR_INVALID_ARG, "%s: null handle", fn);
+    if (!tokens) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens", fn);
+    if (!goal) return fail(MDT_ERR_INVALID_ARG, "%s: null goal", fn);
+    if (!x_T) return fail(MDT_ERR_INVALID_ARG, "%s: null x_T", fn);
+    if (!sigmas) return fail(MDT_ERR_INVALID_ARG, "%s: null sigmas", fn);
+    if (!known) return fail(MDT_ERR_INVALID_ARG, "%s: null known", fn);
+    if (!weight) return fail(MDT_ERR_INVALID_ARG, "%s: null weight", fn);
+    if (!out) return fail(MDT_ERR_INVALID_ARG, "%s: null out", fn);
+    if (batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: batch is %lld, must be >= 1", fn, (long long)batch);
+    if (candidates < 1) return fail(MDT_ERR_INVALID_ARG, "%s: candidates is %d, must be >= 1", fn, candidates);
+    if (n_steps < 1 || n_steps > MDT_SAMPLER_MAX_STEPS)
+        return fail(MDT_ERR_INVALID_ARG, "%s: n_steps is %d, must be in [1, %d]", fn, n_steps, (int)MDT_SAMPLER_MAX_STEPS);
+    if (!std::isfinite(beta) || !(beta > 0.f)) return fail(MDT_ERR_INVALID_ARG, "%s: beta is %g, must be finite and > 0", fn, beta);
+    for (int i = 0; i < n_steps; ++i)
+        if (!std::isfinite(sigmas[i]) || !(sigmas[i] > 0.f))
+            return fail(MDT_ERR_INVALID_ARG, "%s: sigmas[%d] is %g: the schedule must be finite and > 0, then end in 0", fn, i, sigmas[i]);
+    if (sigmas[n_steps] != 0.f)
+        return fail(MDT_ERR_INVALID_ARG, "%s: sigmas[%d] is %g: the schedule must be finite and > 0, then end in 0", fn, n_steps,
+                    sigmas[n_steps]);
+    if ((!lo) != (!hi)) return fail(MDT_ERR_INVALID_ARG, "%s: null %s: the bounds lo and hi come together", fn, lo ? "hi" : "lo");
+    if (m->cfg.arch == MDT_ARCH_MDT && !tokens2) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: MDT needs the gripper tokens", fn);
+    MDT_TRY(mdt_ll_check(m, fn));
+    if (m->p_row >= 0 && !tokens2)
+        return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: this handle was created with use_proprio and needs state_obs", fn);
+    const int64_t R = batch * candidates, limit = ((int64_t)1 << 24) / std::max(m->Te, m->Ta);  // the decoder's row counts (int)
+    if (batch > limit / candidates)
+        return fail(MDT_ERR_INVALID_ARG, "%s: batch * candidates = %lld * %d is more than the decoder's %lld samples", fn,
+                    (long long)batch, candidates, (long long)limit);
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(s, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+        return fail(MDT_ERR_STATE, "%s: the tape path is not capture-safe and the call cannot be captured", fn);
+
+    Call c;
+    c.m = m; c.s = s; c.tokens = tokens; c.tokens2 = tokens2; c.goal = goal; c.known = known; c.weight = weight; c.lo = lo; c.hi = hi;
+    c.modality = modality; c.R = R; c.N = R * m->Ta * m->A;
+    const int per = m->Ta * m->A;
+    MDT_TRY(mdt_grow_carve(m->st_ws, m->st_rows, R, [&](Bump& b, int64_t rows) { carve(b, rows, per, b.base ? &c.b : nullptr); }));
+    mdt_status st = mdt_ll_open(m, batch, candidates, s, &c.run);
+    if (st == MDT_OK) st = run(c, x_T, sigmas, n_steps, beta, out, ctx_out);
+    // on every path: the tapes released, the scratch handed back (a failure above keeps its own message)
+    const mdt_status closed = mdt_ll_close(m, c.run, s);
+    return st != MDT_OK ? st : closed;
+}

@@ -1335,7 +1335,8 @@ extern "C" mdt_status mdt_denoise_vjp(mdt_model* m, const float* tokens, const f
 }
 
 // ------------------------------------------------------------------------------------------------
-// mdt_log_likelihood's pieces of this path (mdt_loglik.h; the integrator and the entry point are in mdt_loglik.hip): the encoder
+// mdt_log_likelihood's and mdt_sample_ddim_steer's pieces of this path (mdt_loglik.h; the integrator and its entry point are in
+// mdt_loglik.hip, the steered DDIM loop in mdt_steer.hip): the encoder
 // and the stacked cross K|V product on the B observations, the decoder forward on the R = B*K chunks against K|V rows staged
 // once, and mdt_denoise_vjp's backward as often as there are probes over that one tape -- it reads the tape and writes only the
 // handle's backward scratch.
@@ -1380,20 +1381,44 @@ mdt_status mdt_ll_forward(mdt_model* m, const mdt_ll_run& r, const float* x, con
     return dec_fwd(m, t, x, nullptr, sigma, nullptr, nullptr, s, false, true);
 }
 
-mdt_status mdt_ll_vjp(mdt_model* m, const mdt_ll_run& r, const float* v, float* denoised, float* vjp, hipStream_t s) {
+// the input-gradient-only backward over the decoder tape, between the caller's two elementwise launches: mdt_ll_vjp's (below:
+// k_denoise_seed / _finish) or mdt_sample_ddim_steer's (mdt_steer.hip: the seed forms the constraint error, the finish the update)
+mdt_status mdt_ll_backward(mdt_model* m, const mdt_ll_run& r, mdt_ll_launch seed, mdt_ll_launch finish, void* arg, hipStream_t s) {
     Tape& t = m->train->tapes[r.dec];
     mdt_train_state* ts = m->train;
-    const int64_t n = t.B * m->Ta * m->A;
-    const int per = m->Ta * m->A;
+    const mdt_ll_io io = {t.F, t.noised, t.sigma, ts->dF, ts->small, t.B * m->Ta * m->A, m->Ta * m->A, m->cfg.sigma_data};
     ts->dy_off = 0;
-    // D = c_skip x + c_out F;  dF = c_out v
-    LAUNCH(mdt_launch_denoise_seed(t.F, t.noised, t.sigma, v, m->cfg.sigma_data, n, per, denoised, ts->dF, s));
+    LAUNCH(seed(io, arg, s));
     MDT_TRY(dec_bwd(m, t, nullptr, s));
-    // y0 = action_emb(c_in x): d x = c_in (d y0 . Wa) + c_skip v
+    // y0 = action_emb(c_in x): d x_in = d y0 . Wa
     LAUNCH(mdt_launch_narrow_out(ts->dx, m->D, m->Wa, ts->small, (int)(t.B * m->Ta), m->A, m->D, s));
-    LAUNCH(mdt_launch_denoise_finish(ts->small, t.sigma, v, m->cfg.sigma_data, n, per, vjp, s));
+    LAUNCH(finish(io, arg, s));
     return MDT_OK;
 }
+
+namespace {
+struct VjpArg {
+    const float* v;
+    float *denoised, *vjp;
+};
+// D = c_skip x + c_out F;  dF = c_out v
+hipError_t vjp_seed(const mdt_ll_io& io, void* arg, hipStream_t s) {
+    const VjpArg& a = *(const VjpArg*)arg;
+    return mdt_launch_denoise_seed(io.F, io.x, io.sigma, a.v, io.sd, io.n, io.per, a.denoised, io.dF, s);
+}
+// d x = c_in (d y0 . Wa) + c_skip v
+hipError_t vjp_finish(const mdt_ll_io& io, void* arg, hipStream_t s) {
+    const VjpArg& a = *(const VjpArg*)arg;
+    return mdt_launch_denoise_finish(io.small, io.sigma, a.v, io.sd, io.n, io.per, a.vjp, s);
+}
+}  // namespace
+
+mdt_status mdt_ll_vjp(mdt_model* m, const mdt_ll_run& r, const float* v, float* denoised, float* vjp, hipStream_t s) {
+    VjpArg a = {v, denoised, vjp};
+    return mdt_ll_backward(m, r, vjp_seed, vjp_finish, &a, s);
+}
+
+const float* mdt_ll_ctx(mdt_model* m, const mdt_ll_run& r) { return m->train->tapes[r.enc].ctx; }
 
 mdt_status mdt_ll_close(mdt_model* m, const mdt_ll_run& r, hipStream_t s) {
     mdt_status st = MDT_OK;

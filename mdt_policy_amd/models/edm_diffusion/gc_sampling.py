@@ -9,6 +9,9 @@ exposes its bounds (``clip_bounds``, utils/action_bounds.py ActionBounds: the ca
 sample_dpm_fast (1..128 evaluations); sample_dpm_adaptive with eta = 0 on the GPU is one blocking call
 (``GCDenoiser.sample_dpm_adaptive_native`` -> mdt_sample_dpm_adaptive).  Otherwise they are host loops over
 ``model(state, x, goal, sigma)`` (the HIP denoiser step) with the sigma-independent encoder hoisted out of the loop.
+Every sampler takes ``extra_args={"steer": ActionSteer}`` (utils/action_steer.py: D' = D + s(sigma) J^T (weight (known - D)));
+sample_ddim, and sample_euler without churn, then run as one native call (``GCDenoiser.sample_steered`` -> mdt_sample_ddim_steer),
+the others as host loops whose ``model(...)`` calls get the key.
 ``log_likelihood`` with this package's GCDenoiser is one blocking call too (``GCDenoiser.log_likelihood`` ->
 mdt_log_likelihood), for K chunks per observation and P probes; ``best_candidates`` picks from its result.
 
@@ -27,7 +30,7 @@ import torch
 
 from . import utils
 from ... import _lib
-from ..networks._engine import candidate_count, chunk_rows, rollout_controls, take_candidates
+from ..networks._engine import candidate_count, chunk_rows, rollout_controls, steer_alone, take_candidates, take_steer
 from .graphed import GraphedDDIM, GraphedSampler
 from .score_wrappers import GCDenoiser
 
@@ -240,6 +243,55 @@ def _controls(extra_args):
     return rollout_controls(**rest) + (K,)
 
 
+class _SteeredModel:
+    """A foreign denoiser (any callable that is no GCDenoiser) under a steer: D' = D + s(sigma) J^T (weight (known - D)) with
+    J^T e from torch.autograd inside torch.enable_grad(), as log_likelihood differentiates such a model.  sigma_data is the
+    model's own attribute of that name, 1 without one."""
+
+    def __init__(self, model, steer):
+        self.model, self.steer = model, steer
+        self.sigma_data = float(getattr(model, "sigma_data", 1.0))
+
+    def __call__(self, state, x, goal, sigma, **kw):
+        with torch.enable_grad():
+            xg = x.detach().requires_grad_()
+            den = self.model(state, xg, goal, sigma, **kw)
+            e = self.steer.error(den.detach(), candidate_count(kw.get("candidates")))
+            jte, = torch.autograd.grad((den * e).sum(), xg)
+        sig = torch.as_tensor(sigma, dtype=x.dtype, device=x.device).reshape(-1)
+        return den.detach() + utils.append_dims(self.steer.scale(sig, self.sigma_data), x.ndim) * jte
+
+
+def _steer(model, extra_args):
+    """(model, extra_args, steer) of a sampler call: ``extra_args['steer']`` (an ActionSteer) read once, in front of every other
+    key.  No steer, or one whose weight is all zero: the key is dropped and the call is the call without it.  An active steer
+    with a pin or a guidance weight raises NotImplementedError.  With this package's GCDenoiser the key stays: the host loops
+    hand it to ``forward``, and ``_steer_native`` decides whether the call is the native one instead.  Any other model is
+    wrapped (``_SteeredModel``) and the key comes off."""
+    if not extra_args or "steer" not in extra_args:
+        return model, extra_args, None
+    steer, rest = take_steer(extra_args)
+    if steer is None:
+        return model, rest, None
+    steer_alone(cond_lambda=rest.get("cond_lambda"), pin=rest.get("pin"))
+    if isinstance(model, GCDenoiser):
+        return model, extra_args, steer
+    return _SteeredModel(model, steer), rest, steer
+
+
+def _steer_native(model, sigmas, scaler, callback, extra_args) -> bool:
+    """Whether a steered sample_ddim / churn-free sample_euler call is the native one (mdt_sample_ddim_steer): ``_native_ok`` says
+    yes to the call without the steer, and the only other key is ``candidates``.  Steered calls are never graphed."""
+    rest = take_steer(extra_args)[1]
+    return set(rest) <= {"candidates"} and _native_ok(model, sigmas, scaler, callback, rest)
+
+
+def _run_steer(model, state, action, goal, sigmas, steer, extra_args, scaler=None):
+    K = take_candidates(take_steer(extra_args)[1])[0]
+    rows = _chunk_view(state, action, None, K)[0]
+    return model.sample_steered(state, rows, goal, sigmas, steer, candidates=K, bounds=scaler).reshape(action.shape)
+
+
 def _chunk_view(state, action, noise, K):
     """A candidates call's ``action`` as its (B*K, Ta, A) chunks (chunk_rows checks the leading size) and its noise rows to match."""
     if K == 1 and action.dim() != 4:
@@ -356,8 +408,13 @@ def sample_ddim(model, state, action, goal, sigmas, scaler=None, extra_args=None
     with `use_scaler` (mdtv_agent.py:606-614) keeps the fused native loop; only `callback` / `extra_args` need the step loop
     (a guidance weight, pinned actions and a candidate count, ``extra_args={"cond_lambda": lam, "pin": ActionPin(...),
     "candidates": K}``, ride in the native call: K chunks per observation of ``state`` / ``goal`` from one encoded context,
-    ``action`` (B*K, Ta, A) or (B, K, Ta, A))."""
+    ``action`` (B*K, Ta, A) or (B, K, Ta, A)).  ``extra_args={"steer": ActionSteer(...)}`` (utils/action_steer.py) steers every
+    step's denoised value through the denoiser's Jacobian; alone or with ``candidates`` it is one native call of its own
+    (mdt_sample_ddim_steer), eager, never a graph."""
+    model, extra_args, steer = _steer(model, extra_args)
     extra_args = {} if extra_args is None else extra_args
+    if steer is not None and _steer_native(model, sigmas, None, callback, extra_args):
+        return _run_steer(model, state, action, goal, sigmas, steer, extra_args)  # one native call, eager (never a graph)
     native, lam, pin, K = _controls(extra_args)
     if isinstance(model, GCDenoiser) and callback is None and native:
         # guidance: the guided native call, its graphs keyed by the weight too; a pin: by its presence (the values are copied in)
@@ -391,7 +448,13 @@ def sample_ddim(model, state, action, goal, sigmas, scaler=None, extra_args=None
 @torch.no_grad()
 def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None,
                  s_churn=0., s_tmin=0., s_tmax=float('inf'), s_noise=1.):
-    """Karras Algorithm 2 without the 2nd-order correction (reference gc_sampling.py:164-209)."""
+    """Karras Algorithm 2 without the 2nd-order correction (reference gc_sampling.py:164-209).  Steered
+    (``extra_args={"steer": ActionSteer}``) and without churn it is sample_ddim's update and runs as that native call, the scaler's
+    bounds inside."""
+    model, extra_args, steer = _steer(model, extra_args)
+    if steer is not None and s_churn == 0 and _steer_native(model, sigmas, scaler, callback, extra_args):
+        _randn_rows(action, len(sigmas) - 1)  # the loop's draws: a seeded call leaves the generator where the loop leaves it
+        return _run_steer(model, state, action, goal, sigmas, steer, extra_args, scaler=scaler)
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("euler", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
                            s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
@@ -419,6 +482,7 @@ def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=Non
 def sample_euler_ancestral(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None,
                            disable=None, eta=1.):
     """Euler steps to sigma_down plus fresh noise sigma_up (reference gc_sampling.py:213-252)."""
+    model, extra_args, steer = _steer(model, extra_args)
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         noise = _randn_rows(action, _ancestral_draws(sigmas, eta))
         return _run_native("euler_ancestral", model, state, action, goal, sigmas, noise, eta=eta, extra_args=extra_args,
@@ -445,6 +509,7 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
                 s_churn=0., s_tmin=0., s_tmax=float('inf'), s_noise=1.):
     """Karras Algorithm 2 with Heun's trapezoidal correction; plain Euler on the final step to sigma = 0
     (reference gc_sampling.py:256-312)."""
+    model, extra_args, steer = _steer(model, extra_args)
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("heun", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
                            s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
@@ -478,6 +543,7 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
 @torch.no_grad()
 def sample_dpmpp_2m(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None):
     """DPM-Solver++(2M) multistep (reference gc_sampling.py:699-734)."""
+    model, extra_args, steer = _steer(model, extra_args)
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         # (the loop below never reads `scaler`, as in the reference: no bounds to pass)
         return _run_native("dpmpp_2m", model, state, action, goal, sigmas, None, extra_args=extra_args)
@@ -505,6 +571,7 @@ def sample_dpmpp_2m(model, state, action, goal, sigmas, scaler=None, extra_args=
 def sample_dpmpp_2s(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None,
                     eta=1.):
     """DPM-Solver++(2S) single-step second order (reference gc_sampling.py:955-994)."""
+    model, extra_args, steer = _steer(model, extra_args)
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("dpmpp_2s", model, state, action, goal, sigmas, None, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
@@ -533,6 +600,7 @@ def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=Non
                  s_churn=0., s_tmin=0., s_tmax=float('inf'), s_noise=1.):
     """DPM-Solver-2 flavoured midpoint steps (reference gc_sampling.py:315-371): derivative at sigma_hat, a second
     evaluation at the log-midpoint sigma, full step with the midpoint derivative; Euler on the last step."""
+    model, extra_args, steer = _steer(model, extra_args)
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("dpm_2", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
                            s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
@@ -567,6 +635,7 @@ def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=Non
 def sample_dpm_2_ancestral(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None,
                            disable=None, eta=1.):
     """Ancestral sampling with DPM-Solver-2 midpoint steps (reference gc_sampling.py:374-407)."""
+    model, extra_args, steer = _steer(model, extra_args)
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         noise = _randn_rows(action, _ancestral_draws(sigmas, eta))
         return _run_native("dpm_2_ancestral", model, state, action, goal, sigmas, noise, eta=eta, extra_args=extra_args,
@@ -613,6 +682,7 @@ def linear_multistep_coeff(order, t, i, j):
 @torch.no_grad()
 def sample_lms(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None, order=4):
     """Linear multistep (Adams-Bashforth in sigma) sampler (reference gc_sampling.py:425-460)."""
+    model, extra_args, steer = _steer(model, extra_args)
     if 1 <= order <= 4 and _native_ok(model, sigmas, scaler, callback, extra_args):
         return _run_native("lms", model, state, action, goal, sigmas, None, order=order, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
@@ -647,6 +717,7 @@ def sample_dpmpp_2_with_lms(model, state, action, goal, sigmas, scaler=None, ext
 def sample_dpmpp_2s_ancestral(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None,
                               disable=None, eta=1., s_noise=1., noise_sampler=None):
     """Ancestral sampling with DPM-Solver++(2S) steps (reference gc_sampling.py:864-907)."""
+    model, extra_args, steer = _steer(model, extra_args)
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         n = len(sigmas) - 1
         if noise_sampler is None:
@@ -879,6 +950,7 @@ def sample_dpm_fast(model, state, action, goal, sigma_min, sigma_max, n, scaler=
     floor(n/3)+1 uniform steps in t, third order except for the tail (.., 2, 1 when 3 | n, else .., n mod 3).
     (The reference builds its default noise sampler from an undefined name, :600, so it only runs with an explicit one;
     the default here is the action-shaped Gaussian sampler it meant.)"""
+    model, extra_args, steer = _steer(model, extra_args)
     _check_sigma_range(sigma_min, sigma_max)
     t_start, t_end = _t(torch.tensor(float(sigma_max))), _t(torch.tensor(float(sigma_min)))
     if eta and not t_end > t_start:
@@ -936,6 +1008,7 @@ def sample_dpm_adaptive(model, state, action, goal, sigma_min, sigma_max, extra_
     (order-1, order) shares its stage evaluations -- the order-2 estimate of the 23 pair uses r_1 = 1/3, the first node
     of the order-3 step -- and the scaled difference of the two drives the step-size control.
     (The reference reads `noise_sampler` before assigning it, :633: its adaptive solver cannot run.  Parity unpinned.)"""
+    model, extra_args, steer = _steer(model, extra_args)
     _check_sigma_range(sigma_min, sigma_max)
     if order not in (2, 3):
         raise ValueError('order should be 2 or 3')
@@ -1090,6 +1163,7 @@ def sample_dpmpp_sde(model, state, action, goal, sigmas, extra_args=None, callba
     the library's own, NativeBrownianTreeNoiseSampler).  On the native path that tree -- the default without torchsde, or a
     NativeBrownianTreeNoiseSampler with the identity transform on the model's device -- is walked inside the call
     (mdt_sample_sde_tree): no noise on the host and no read-back of a device schedule."""
+    model, extra_args, steer = _steer(model, extra_args)
     if _native_ok(model, sigmas, scaler, callback, extra_args):
         tree = None
         if noise_sampler is None and not _torchsde_available():  # the default's one seed draw, as its constructor makes it

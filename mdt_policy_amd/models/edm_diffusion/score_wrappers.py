@@ -15,7 +15,7 @@ from contextlib import contextmanager
 import torch
 from torch import nn
 
-from ..networks._engine import HipScoreNetwork, candidate_count, chunk_rows
+from ..networks._engine import HipScoreNetwork, candidate_count, chunk_rows, steer_alone, take_steer
 
 
 def _staged_backward() -> bool:
@@ -124,7 +124,7 @@ class GCDenoiser(nn.Module):
                  if ("inner_model." + n) in eng._grad_layout and not (unused and n.startswith(unused))]
         return tok, tok2, g, B, [n for n, _ in named], [p for _, p in named]
 
-    def forward(self, state, action, goal, sigma, cond_lambda=1.0, pin=None, candidates=None, **kwargs):
+    def forward(self, state, action, goal, sigma, cond_lambda=1.0, pin=None, candidates=None, steer=None, **kwargs):
         """D(x; sigma) = F(x*c_in, sigma)*c_out + x*c_skip (reference score_wrappers.py:65-80).
 
         ``cond_lambda`` != 1: classifier-free guidance, D_lambda = D(x; sigma, 0) + lambda (D(x; sigma, g) - D(x; sigma, 0)) from the
@@ -134,7 +134,14 @@ class GCDenoiser(nn.Module):
         ``candidates`` = K: ``action`` holds K chunks for each of the B observations of ``state`` and ``goal``, (B*K, Ta, A) or
         (B, K, Ta, A), chunk k of observation b at row b*K + k; the observations are expanded with ``repeat_interleave`` and the
         call runs at batch B*K (the samplers' host loops; the native samplers encode each observation once instead).  A pin
-        given per observation goes to each of its chunks; latent_encoder_emb stays (B, Te, d)."""
+        given per observation goes to each of its chunks; latent_encoder_emb stays (B, Te, d).
+        ``steer`` (an ActionSteer, utils/action_steer.py): D' = D + s(sigma) J^T (weight (known - D)) from one taped decoder forward
+        and one input-gradient-only backward over it; with ``candidates`` the observations are encoded once.  Together with
+        ``cond_lambda`` != 1 or ``pin`` it raises NotImplementedError.  A steer whose weight is all zero is no steer."""
+        steer = take_steer({"steer": steer})[0]
+        if steer is not None:
+            steer_alone(cond_lambda=cond_lambda, pin=pin)
+            return self._steered(state, action, goal, sigma, steer, candidates, **kwargs)
         K = candidate_count(candidates)
         if K != 1 or (candidates is not None and action.dim() == 4):
             B = next(v for v in state.values() if torch.is_tensor(v)).shape[0]
@@ -169,6 +176,33 @@ class GCDenoiser(nn.Module):
         out, ctx = eng.forward(state, action, goal, sigma)
         im.latent_encoder_emb = ctx
         return out
+
+    def _steered(self, state, action, goal, sigma, steer, candidates=None, **kwargs):
+        """``forward`` with an active steer: the context of the B observations (the one ``cached_context`` holds, where it is
+        this call's), the taped decoder forward on the B*K chunks, e = weight (known - D), the backward for d_x alone."""
+        im = self.inner_model
+        K = candidate_count(candidates)
+        eng = self._engine(state=state)
+        g = im._goals(goal, bool(kwargs.get("uncond", False)))
+        B = next(v for v in state.values() if torch.is_tensor(v)).shape[0]
+        rows = chunk_rows(action, B, K) if (K != 1 or action.dim() == 4) else action
+        R = rows.shape[0]
+        sg = sigma.to(device=rows.device, dtype=torch.float32).reshape(-1)
+        if sg.numel() not in (1, R):
+            raise ValueError(f"sigma holds {sg.numel()} values, {R} chunks take 1 or {R}")
+        if self._ctx_key is not None and self._ctx_key == (id(state), id(g), B, eng.ctx_generation):
+            ctx = im.latent_encoder_emb  # inside cached_context(): encoder hoisted
+        else:  # (sigma is read by use_ada_conditioning=False models only: one value per observation)
+            ctx = eng.encode(state, g, honour_modality=im._arch == "mdtv", sigma=sg if sg.numel() == 1 else sg[::K])
+            im.latent_encoder_emb = ctx
+        sg = sg.expand(R) if sg.numel() == 1 else sg
+        den, tape = eng.train_denoise_fwd(eng._in(ctx if K == 1 else ctx.repeat_interleave(K, 0)),
+                                          eng._in(rows, (R, eng.Ta, eng.A)), eng._in(sg, (R,)))
+        try:
+            jte = eng.train_denoise_bwd(tape, steer.error(den, K), R, (False, True, False), False)[2]
+        finally:
+            eng.tape_release(tape)
+        return (den + steer.scale(sg, self.sigma_data).reshape(R, 1, 1) * jte).reshape(action.shape)
 
     def loss(self, state, action, goal, noise, sigma, **kwargs):
         """Denoising score-matching loss, forward value (reference score_wrappers.py:45-63)."""
@@ -390,13 +424,37 @@ class GCDenoiser(nn.Module):
         return out, info
 
     @torch.no_grad()
-    def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None, bounds=None, record=False, pin=None, candidates=None):
+    def sample_steered(self, state, action, goal, sigmas, steer, candidates=None, bounds=None):
+        """The steered DDIM loop as one enqueue (mdt_sample_ddim_steer): what ``sample_ddim(..., steer=steer)`` runs, and with
+        ``bounds`` -- an ``ActionBounds`` or a (lo, hi) pair, x clamped after every step -- what gc_sampling.sample_euler without
+        churn runs under a clipping scaler (the same update)."""
+        im = self.inner_model
+        if bounds is not None:
+            pair = bounds.clip_bounds(action.device) if callable(getattr(bounds, "clip_bounds", None)) else bounds
+            bounds = tuple(torch.as_tensor(b, dtype=torch.float32).to(action.device) for b in pair)
+        out, ctx = self._engine(state=state).sample_ddim_steer(state, action, im._goals(goal, False), sigmas, steer,
+                                                               candidates=candidate_count(candidates), bounds=bounds)
+        im.latent_encoder_emb = ctx
+        return out
+
+    @torch.no_grad()
+    def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None, bounds=None, record=False, pin=None, candidates=None,
+                    steer=None):
         """Whole DDIM loop (reference gc_sampling.py:922-951) as one enqueue on the current stream.  ``cond_lambda``:
         classifier-free guidance weight (None or 1: the unguided call; mdt_sample_ddim_guided).  ``bounds`` is accepted and not
         read, as the reference's DDIM accepts a scaler and never clips; the DDIM head keeps no per-step record.  ``pin``: an
         ``ActionPin`` or its (known, keep) pair of (B, Ta, A) device tensors -- pinned actions (mdt_sample_ddim_opt): every step's
         denoised value becomes keep * known + (1 - keep) * D inside the action head.  ``candidates`` = K: K chunks per
-        observation from one encoded context (mdt_sample_ddim_multi), with the shapes ``sample_native`` documents."""
+        observation from one encoded context (mdt_sample_ddim_multi), with the shapes ``sample_native`` documents.  ``steer``: an
+        ``ActionSteer`` (utils/action_steer.py) -- every step's denoised value becomes D + s(sigma) J^T (weight (known - D))
+        (mdt_sample_ddim_steer: per step one taped decoder forward and one input-gradient-only backward; eager, never a graph);
+        with ``cond_lambda`` != 1 or ``pin`` it raises NotImplementedError; a steer whose weight is all zero is no steer."""
+        steer = take_steer({"steer": steer})[0]
+        if steer is not None:
+            steer_alone(cond_lambda=cond_lambda, pin=pin)
+            if record:
+                raise NotImplementedError("sample_ddim keeps no per-step record; run the host loop with a callback")
+            return self.sample_steered(state, action, goal, sigmas, steer, candidates=candidates)
         if record:
             raise NotImplementedError("sample_ddim keeps no per-step record; run the host loop with a callback")
         im = self.inner_model

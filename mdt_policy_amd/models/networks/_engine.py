@@ -76,6 +76,30 @@ def take_candidates(extra_args):
     return candidate_count(rest.pop("candidates", None)), rest
 
 
+def take_steer(extra_args):
+    """(steer, the other keys) of a sampler's ``extra_args``: ``steer`` (an ActionSteer, utils/action_steer.py) comes off in front
+    of ``take_candidates`` and ``rollout_controls``.  A steer whose weight is all zero comes back as None -- it is treated as
+    absent everywhere, so the call is the call without it.  Anything that is no ActionSteer is a TypeError, before anything is
+    enqueued."""
+    rest = dict(extra_args or {})
+    steer = rest.pop("steer", None)
+    if steer is None:
+        return None, rest
+    if not (callable(getattr(steer, "on", None)) and callable(getattr(steer, "scale", None)) and hasattr(steer, "active")):
+        raise TypeError(f"extra_args['steer'] must be an ActionSteer (ActionSteer(known, weight, beta)), got {type(steer).__name__}")
+    return (steer if steer.active else None), rest
+
+
+def steer_alone(cond_lambda=None, pin=None):
+    """What an active steer does not combine with yet: the Jacobian of the guided call's doubled batch, and the order of pin
+    against steer.  Raises NotImplementedError naming the key."""
+    if pin is not None:
+        raise NotImplementedError("'steer' together with 'pin' is not implemented (the order of pin against steer is not defined yet)")
+    if cond_lambda is not None and float(cond_lambda) != 1.0:
+        raise NotImplementedError("'steer' together with 'cond_lambda' != 1 is not implemented (the Jacobian of the guided call's "
+                                  "doubled batch is not formed)")
+
+
 def chunk_rows(action: torch.Tensor, B: int, K: int) -> torch.Tensor:
     """``action`` of a call with K candidates for each of B observations, (B*K, Ta, A) or (B, K, Ta, A), as its (B*K, Ta, A)
     chunks (observation-major: chunk k of observation b is row b*K + k).  A leading size that is not B*K raises ValueError."""
@@ -399,6 +423,27 @@ class HipEngine:
             _lib.call(self.lib.mdt_sample_ddim_dev_opt if p.dev else self.lib.mdt_sample_ddim_opt, *head, *tail)
         else:
             _lib.call(self.lib.mdt_sample_ddim_dev_multi if p.dev else self.lib.mdt_sample_ddim_multi, *head, K, *tail)
+        return p.out, p.ctx
+
+    def sample_ddim_steer(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, steer, candidates: int = 1, bounds=None):
+        """mdt_sample_ddim_steer: DDIM with every step's denoised value steered through the denoiser's Jacobian, D' = D + s(sigma)
+        J^T (weight (known - D)), as one enqueue -- the observations encoded once, per step one taped decoder forward on the B*K
+        chunks and one input-gradient-only backward.  ``steer``: an ActionSteer, per chunk or per observation; ``x_T``
+        (B*K, Ta, A) or (B, K, Ta, A); ``bounds``: None or (lo, hi), fp32 (A,) device tensors -- x is clamped after every step
+        (sample_euler's clip; sample_ddim passes none).  The schedule goes to the host (a device schedule is read back).  Not
+        capture-safe: on a capturing stream the library refuses with MDT_ERR_STATE and enqueues nothing."""
+        self.train_prepare()
+        K = candidate_count(candidates)
+        host = sigmas.detach().to("cpu") if torch.is_tensor(sigmas) else sigmas
+        p = self._sampler_inputs(state, x_T, goal, host, candidates=K)
+        known, weight = steer.on(self.device, (p.N, self.Ta, self.A), K)
+        lo = hi = None
+        if bounds is not None:
+            lo, hi = (self._in(b, (self.A,)) for b in bounds)
+        self._keep = (p.sig, known, weight, lo, hi)  # the kernels that read them are only enqueued
+        _lib.call(self.lib.mdt_sample_ddim_steer, self.handle, _ptr(p.tok), _ptr(p.tok2), _ptr(p.g), p.modality, _ptr(p.x),
+                  C.cast(p.sig, C.c_void_p), p.n, p.B, K, _ptr(known), _ptr(weight), float(steer.beta), _ptr(lo), _ptr(hi),
+                  _ptr(p.out), _ptr(p.ctx), self._stream())
         return p.out, p.ctx
 
     def sample_native(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,

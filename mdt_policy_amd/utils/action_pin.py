@@ -15,7 +15,8 @@ toward ``known`` at every step.
 
 Hand it to a sampler as ``extra_args={"pin": pin}`` (gc_sampling.sample_*: the native call stays native, include/mdt_hip.h
 mdt_sample_opts.pin_known / pin_keep), to ``GCDenoiser.sample_ddim / sample_native(..., pin=pin)`` or to
-``GCDenoiser.forward(..., pin=pin)``.
+``GCDenoiser.forward(..., pin=pin)``.  A steer (utils/action_steer.py, ``ActionSteer``) moves the whole chunk instead: it sends the
+same error, known - D, back through the denoiser's Jacobian, so the tokens that are not pinned follow the known part.
 """
 from __future__ import annotations
 
