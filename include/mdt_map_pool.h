@@ -85,7 +85,9 @@ typedef struct {
     const float *image_features;  /* (batch, dim)                                                   */
     const float *lang_features;   /* (batch, dim)                                                   */
     const float *logit_scale;     /* device scalar: the log temperature parameter (mdtv_agent.py:140) */
-    int32_t batch, dim;           /* dim: multiple of 16; batch 1..32768 (the GLOBAL batch after the gather) */
+    int32_t batch, dim;           /* dim: multiple of 16, at most 65536; batch 1..32768 (the GLOBAL batch after the gather);
+                                   * ceil16(batch) * dim < 2^30.  Anything else: MDT_ERR_UNSUPPORTED / MDT_ERR_INVALID_ARG
+                                   * before anything is enqueued */
     int32_t mode;                 /* MDT_INFONCE_*                                                    */
     float *loss;                  /* device scalar out                                                */
     float *d_image, *d_lang;      /* (batch, dim) out, or all three NULL                              */

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void k_rownorm_fwd(const float* __restrict__ x
     if (lane == 0) inv[row] = r;
 }
 
-// dx = (dn - xn (xn . dn)) * inv   (rows whose norm was clamped never occur for non-zero embeddings)
+// dx = (dn - xn (xn . dn)) * inv   (a zero row: xn = 0, dx = dn / eps as F.normalize's autograd -- tests/infonce_cases.py (d))
 __global__ __launch_bounds__(256) void k_rownorm_bwd(const float* __restrict__ xn, const float* __restrict__ inv,
                                                      const float* __restrict__ dn, float* __restrict__ dx, int M, int D) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -152,11 +152,18 @@ extern "C" int64_t mdt_op_infonce_scratch(int64_t batch, int64_t dim) {
 }
 
 extern "C" mdt_status mdt_op_infonce(const mdt_infonce_args* a, void* stream) {
-    if (!a || !a->image_features || !a->lang_features || !a->logit_scale || !a->loss || !a->scratch)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_infonce: null argument");
+    if (!a) return fail(MDT_ERR_INVALID_ARG, "mdt_op_infonce: null args");
+    const char* null_field = !a->image_features ? "image_features" : !a->lang_features ? "lang_features" : !a->logit_scale ? "logit_scale"
+                           : !a->loss ? "loss" : !a->scratch ? "scratch" : nullptr;
+    if (null_field) return fail(MDT_ERR_INVALID_ARG, "mdt_op_infonce: null %s", null_field);
     const int B = a->batch, D = a->dim;
     if (B < 1 || B > 32768) return fail(MDT_ERR_INVALID_ARG, "mdt_op_infonce: batch must be 1..32768");
     if (D < 16 || D % 16) return fail(MDT_ERR_UNSUPPORTED, "mdt_op_infonce: dim must be a multiple of 16");
+    // what the three GEMM calls below accept (mdt_launch_gemm: N, K <= 65536 and N * K < 2^30 for the 32-bit weight offsets),
+    // refused here so that nothing is enqueued before the refusal
+    if (D > 65536) return fail(MDT_ERR_UNSUPPORTED, "mdt_op_infonce: dim is %d, must be at most 65536", D);
+    if ((((int64_t)B + 15) & ~(int64_t)15) * D >= ((int64_t)1 << 30))
+        return fail(MDT_ERR_UNSUPPORTED, "mdt_op_infonce: batch %d (padded to a multiple of 16) times dim %d must be below 2^30", B, D);
     float w_r, w_c;
     switch (a->mode) {
         case MDT_INFONCE_SYMMETRIC: w_r = 0.5f; w_c = 0.5f; break;
