@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-/* The split forms of mdt_op_mlp_split and of the wide LayerNorm-prologue products (mdt_gemm_args.Wp_split): 0 = the fp32 launches
+/* The split forms of the model's fused MLP launch and of the wide LayerNorm-prologue products (mdt_gemm_args.Wp_split / Wp_pair): 0 = the fp32 launches
  * everywhere, 1 = on, negative = default (MDT_HIP_MLP_SPLIT from the environment; unset = 1). */
 void mdt_op_set_mlp_split(int32_t on);
 /* The model-level entry points run the MLP sublayer through mdt_op_mlp from `rows` rows (B * horizon) on; 0 = never (the two-GEMM

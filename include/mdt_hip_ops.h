@@ -95,6 +95,9 @@ typedef struct {
      * plain output rows) multiply in the split form -- six bf16 MFMA products per 32-deep step, fp32
      * accumulation: fp32's product accuracy, not the fp32 form's bits -- unless mdt_op_set_mlp_split(0).  NULL: the fp32 form. */
     const void *Wp_split;
+    /* optional: the fp16 pair image of the same weight (mdt_op_pack_weight_pair).  Takes the same products as Wp_split (which wins
+     * where both are given) through the two-way fp16 pair split described at mdt_op_pack_weight_pair. */
+    const void *Wp_pair;
 } mdt_gemm_args;
 
 mdt_status mdt_op_gemm(const mdt_gemm_args *args, void *stream);
@@ -122,6 +125,36 @@ mdt_status mdt_op_pack_weight_split(const float *w, int64_t n_rows, int64_t K, v
 mdt_status mdt_op_pack_weight_split_rows(const float *w, int64_t n_rows, int64_t K, void *image, int64_t n_off, void *stream);
 mdt_status mdt_op_mlp_split(const mdt_gemm_args *fc, const mdt_gemm_args *proj, const void *fc_split, const void *proj_split,
                             float *parts, int64_t part_stride, int32_t *n_parts, void *stream);
+
+/* The same launches in the two-way fp16 PAIR split -- the form the model's own launches take from 768 rows on (the three-way bf16
+ * entries above keep their behaviour bit for bit).
+ * Numerics.  An operand element x of a scale group is stored as h1 + h2 = x s:  h1 = fp16(x s), h2 = fp16(x s - h1), both rounded to
+ * nearest (the subtraction is exact in fp32) -- 22 significand bits.  s is a power of two that brings the group's largest |x| into
+ * [2^14, 2^15) (exponent clamped to +-126; a zero group gets 2^126), below fp16's 65504 with room for rounding, so no finite fp32
+ * operand -- a hidden activation above 65504, an all-zero row or tile, a tile of fp32 subnormals -- turns into Inf or NaN.  Groups: one
+ * scale per activation ROW (computed in the launch: the LayerNorm prologue's rows, the GELU epilogue's 512-wide hidden slices) and
+ * one per 16-row TILE of the (N, K) weight (= one MFMA column tile; made by the pack kernel, no global reduction).  A k32 step is
+ * three v_mfma_f32_16x16x32_f16 products, x2 w1, x1 w2, x1 w1, fp32 accumulation; the epilogue multiplies each accumulator by the
+ * exact reciprocal of (row scale x tile scale) (one v_ldexp_f32) before bias, activation and gate.  Elements more than 2^-14 below
+ * their group's maximum lose low bits of h2 to fp16's subnormal range -- below 2^-28 of the maximum, whether or not the MFMA keeps
+ * fp16 subnormals.  A row or tile that holds Inf or NaN gets a NaN scale: the outputs that depend on it are NaN, no others.
+ * Against float64 the error stays within 1.5x the fp32 launches' (tests/test_gpu_f16_pair.py); not their bits.
+ * Image of an (N, K) weight, N % 16 == 0, K % 32 == 0: column tile nt at nt * (K / 32 * 2048 + 16) bytes = K / 32 steps x 2 parts x
+ * 1 KiB fragments (step kk, part p at (2 kk + p) * 1024; lane l's 16 bytes = the part's eight fp16 of
+ * W[16 nt + l % 16][32 kk + 16 h + 4 (l / 16) + e] at slot 4 h + e), then a 16-byte trailer {fp32 s, 0, 0, 0}.
+ * mdt_op_pair_image_bytes = 4 N K + N bytes (-1: bad shape).
+ * mdt_op_pack_weight_pair: rows [0, n_rows) of w (n_rows, K) -> column tiles n_off / 16 .. of the image (n_rows, n_off multiples of
+ * 16: stacked weights are packed row range by row range).  mdt_op_pair_from_packed: the same image, bit for bit, from the fp32
+ * fragment image of the whole weight (mdt_op_pack_weight).
+ * mdt_op_mlp_pair: mdt_op_mlp_split on pair images.  mdt_op_gemm_ln_pair: the wide LayerNorm-prologue product on args->Wp_pair
+ * (K = 384 or 512, N a multiple of 384, plain output rows, a_parts <= 4; Wp is not read) at ANY row count and whatever the
+ * switches say; mdt_op_gemm takes the same launch from 768 rows on where Wp_pair is given and Wp_split is not. */
+int64_t mdt_op_pair_image_bytes(int64_t n_rows, int64_t K);
+mdt_status mdt_op_pack_weight_pair(const float *w, int64_t n_rows, int64_t K, void *image, int64_t n_off, void *stream);
+mdt_status mdt_op_pair_from_packed(const float *packed, int64_t N, int64_t K, void *image, void *stream);
+mdt_status mdt_op_mlp_pair(const mdt_gemm_args *fc, const mdt_gemm_args *proj, const void *fc_pair, const void *proj_pair,
+                           float *parts, int64_t part_stride, int32_t *n_parts, void *stream);
+mdt_status mdt_op_gemm_ln_pair(const mdt_gemm_args *args, void *stream);
 
 /* From 8192 rows on, mdt_op_gemm's K = 384 products that take the weight-stationary body run the same three-way bf16 split form
  * (fp32's product accuracy, not its bits, at 2.7x the fp32 matrix rate) unless MDT_HIP_WS_SPLIT=0.

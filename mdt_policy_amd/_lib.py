@@ -38,7 +38,7 @@ class GemmArgs(C.Structure):
         ("residual", C.c_int32), ("gate_off", C.c_int32), ("gin", C.c_int32), ("gout", C.c_int32),
         ("goff", C.c_int32), ("rowvec", C.c_void_p), ("batch", C.c_int32), ("bs_a", C.c_int64), ("bs_w", C.c_int64),
         ("bs_out", C.c_int64), ("aux", C.c_void_p), ("aux_mode", C.c_int32), ("a_parts", C.c_int32),
-        ("a_part_stride", C.c_int64), ("a_merged", C.c_void_p), ("Wp_split", C.c_void_p)]
+        ("a_part_stride", C.c_int64), ("a_merged", C.c_void_p), ("Wp_split", C.c_void_p), ("Wp_pair", C.c_void_p)]
 
 
 class AttnArgs(C.Structure):
@@ -298,6 +298,11 @@ SYMBOLS = [
     ("mdt_op_pack_weight_split", _I32, [_VP, _I64, _I64, _VP, _VP]),
     ("mdt_op_pack_weight_split_rows", _I32, [_VP, _I64, _I64, _VP, _I64, _VP]),
     ("mdt_op_mlp_split", _I32, [C.POINTER(GemmArgs), C.POINTER(GemmArgs), _VP, _VP, _VP, _I64, C.POINTER(_I32), _VP]),
+    ("mdt_op_pair_image_bytes", _I64, [_I64, _I64]),
+    ("mdt_op_pack_weight_pair", _I32, [_VP, _I64, _I64, _VP, _I64, _VP]),
+    ("mdt_op_pair_from_packed", _I32, [_VP, _I64, _I64, _VP, _VP]),
+    ("mdt_op_mlp_pair", _I32, [C.POINTER(GemmArgs), C.POINTER(GemmArgs), _VP, _VP, _VP, _I64, C.POINTER(_I32), _VP]),
+    ("mdt_op_gemm_ln_pair", _I32, [C.POINTER(GemmArgs), _VP]),
     ("mdt_op_attention", _I32, [C.POINTER(AttnArgs), _VP]),
     ("mdt_op_attn_proj", _I32, [C.POINTER(GemmArgs), _VP, _I64, _I32, _I32, _I32, _VP]),
     ("mdt_op_xattn_fold", _I32, [C.POINTER(XFoldArgs), _VP]),

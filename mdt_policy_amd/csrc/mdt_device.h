@@ -253,6 +253,55 @@ __device__ __forceinline__ void split3_bf16(const f32x4& x, mdt_bf16x4& p1, mdt_
     }
 }
 
+// ---- two-way fp16 split of SCALED fp32 operands (the pair form: mdt_mlp_split.h) ----
+// One power-of-two scale s per group (an activation row, a 16-column weight tile) brings the group's largest |x| into [2^14, 2^15),
+// below fp16's 65504 with room for rounding; x s = h1 + h2 with h1 = fp16(x s) and h2 = fp16(x s - h1), both rounded to nearest
+// (v_cvt_f16_f32; the subtraction is exact): 22 significand bits.  Elements more than 2^-14 below the group's maximum lose low bits
+// of h2 to fp16's subnormal range (or all of h2 if the MFMA flushes them): below 2^-28 of the maximum either way.
+// The scale travels as its exponent: the epilogue undoes (row scale x tile scale) with one v_ldexp_f32, exact over the whole range.
+typedef _Float16 mdt_f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 mdt_f16x4 __attribute__((ext_vector_type(4)));
+enum { MDT_SPLIT_NONE = 0, MDT_SPLIT_BF16X3 = 1, MDT_SPLIT_F16X2 = 2 };   // the split schemes (gemm_stage_tile, SplitRing, ...)
+
+// |x| as ordered bits: finite < Inf < NaN, so an unsigned maximum carries a group's Inf / NaN to its scale
+__device__ __forceinline__ unsigned pair_absbits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+__device__ __forceinline__ unsigned pair_absbits4(const f32x4& x) {
+    return max(max(pair_absbits(x[0]), pair_absbits(x[1])), max(pair_absbits(x[2]), pair_absbits(x[3])));
+}
+// exponent e of the scale 2^e for a group whose largest |x| has the bits mx: max |x| 2^e in [2^14, 2^15) for normal maxima, e
+// clamped to [-126, 126] (a zero or subnormal group: 2^126, still finite and its reciprocal normal).  Inf / NaN group: 0 (pair_scale
+// then makes the scale itself NaN).
+__device__ __forceinline__ int pair_scale_exp(unsigned mx) {
+    const int ex = (int)(mx >> 23);
+    return ex == 255 ? 0 : min(126, max(-126, 141 - ex));
+}
+__device__ __forceinline__ float pair_scale(unsigned mx) {
+    return (mx >> 23) == 255 ? __uint_as_float(0x7fc00000u) : __uint_as_float((unsigned)(pair_scale_exp(mx) + 127) << 23);
+}
+__device__ __forceinline__ void split2_f16(const f32x4& x, float s, mdt_f16x4& p1, mdt_f16x4& p2) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float v = x[e] * s;
+        const _Float16 a = (_Float16)v;
+        p1[e] = a; p2[e] = (_Float16)(v - (float)a);
+    }
+}
+// acc 2^-e, one rounding at most (v_ldexp_f32)
+__device__ __forceinline__ f32x4 pair_unscale(const f32x4& acc, int e) {
+    return (f32x4){__builtin_ldexpf(acc[0], -e), __builtin_ldexpf(acc[1], -e), __builtin_ldexpf(acc[2], -e), __builtin_ldexpf(acc[3], -e)};
+}
+__device__ __forceinline__ unsigned wave_max_u32(unsigned u) {   // wave_max on ordered bits
+    float v = __uint_as_float(u);
+    auto mx = [](float a, float b) { return __uint_as_float(max(__float_as_uint(a), __float_as_uint(b))); };
+    v = mx(v, dpp_keep<0xB1, 0xf>(v));
+    v = mx(v, dpp_keep<0x4E, 0xf>(v));
+    v = mx(v, dpp_keep<0x141, 0xf>(v));
+    v = mx(v, dpp_keep<0x140, 0xf>(v));
+    v = mx(v, dpp_keep<0x142, 0xa>(v));
+    v = mx(v, dpp_keep<0x143, 0xc>(v));
+    return (unsigned)__builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63);
+}
+
 // byte offset of the four values at columns c .. c + 3 of a row inside one part of a split tile (row stride rowb bytes): slots
 // (half, 0 .. 3) = ((c % 32) / 16, ..) of lane group (c % 16) / 4 in k32 step c / 32 -- the order v_mfma_f32_16x16x32_bf16 reads
 // with one ds_read_b128 per part, row tile and k32 step

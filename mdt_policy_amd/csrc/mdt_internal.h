@@ -42,7 +42,7 @@ struct Lin {
     float* bias = nullptr;  // (N) or nullptr
     int N = 0, K = 0;
     float* wt = nullptr;    // training only: fragment-packed image of W^T (N' = K, K' = N), for dX = dY W
-    void* ws = nullptr;     // the MLP's two Linears: three-way bf16 split fragment image (6 N K bytes; mdt_mlp_split.h)
+    void* ws = nullptr;     // the MLP's two Linears and the stacked q|k|v: fp16 pair fragment image (4 N K + N bytes; mdt_mlp_split.h)
 };
 
 // bump allocator over one hipMalloc'ed block (count pass with base == nullptr, then the real pass)
@@ -59,7 +59,7 @@ struct Bump {
 static inline mdt_gemm_args gemm_args(const float* A, int64_t lda, const Lin& w, float* out, int64_t ldo, int M) {
     mdt_gemm_args g;
     memset(&g, 0, sizeof g);
-    g.A = A; g.lda = lda; g.Wp = w.wp; g.Wp_split = w.ws; g.bias = w.bias; g.out = out; g.ldo = ldo;
+    g.A = A; g.lda = lda; g.Wp = w.wp; g.Wp_pair = w.ws; g.bias = w.bias; g.out = out; g.ldo = ldo;
     g.M = M; g.N = w.N; g.K = w.K;
     g.shift_off = -1; g.scale_off = -1; g.gate_off = -1; g.rows_per_sample = 1;
     g.gin = 1; g.gout = 1; g.goff = 0;
@@ -106,6 +106,17 @@ bool mdt_mlp_split_enabled();
 int mdt_split_min_rows();   // rows from which the split forms of the sampler's launches are used (768: B = 80 2.97 -> 2.89 ms per call, 96 3.08 -> 2.93, 120 3.54 -> 2.96, 128 3.42 -> 2.96; B = 64 loses, 2.44 -> 2.90)
 hipError_t mdt_launch_mlp_split(const mdt_gemm_args& fc, const mdt_gemm_args& proj, const void* w1s, const void* w2s, float* parts,
                                 int64_t part_stride, hipStream_t s);
+// ... and on fp16 pair images (the form the model's launches take)
+hipError_t mdt_launch_mlp_pair(const mdt_gemm_args& fc, const mdt_gemm_args& proj, const void* w1p, const void* w2p, float* parts,
+                               int64_t part_stride, hipStream_t s);
+// (n_rows, K) row-major fp32 -> column tiles n_off / 16 .. of the fp16 pair image (n_rows, n_off % 16 == 0, K % 32 == 0); the same
+// image from the fp32 fragment image of the whole (N, K) weight.  mdt_pair_image_bytes (mdt_mlp_split.h) = 4 N K + N
+// the wide LayerNorm-prologue product (K = 384 / 512, N a multiple of 384, plain output rows) in the pair form on a.Wp_pair
+bool mdt_gemm_ln_pair_supported(const mdt_gemm_args& a);
+hipError_t mdt_launch_gemm_ln_pair(const mdt_gemm_args& a, hipStream_t s);
+constexpr int64_t mdt_pair_image_bytes(int64_t N, int64_t K) { return (N / 16) * ((K / 32) * 2048 + 16); }
+hipError_t mdt_launch_pack_weight_pair(const float* w, int n_rows, int K, void* image, hipStream_t s, int n_off = 0);
+hipError_t mdt_launch_pair_from_packed(const float* wp, int N, int K, void* image, hipStream_t s);
 // (n_rows, K) row-major fp32 -> split image of 6 n_rows K bytes (n_rows % 16 == 0, K % 32 == 0)
 hipError_t mdt_launch_pack_weight_split(const float* w, int n_rows, int K, void* image, hipStream_t s, int n_off = 0);
 // the same image from the fp32 fragment image of the weight (mdt_launch_pack_weight's output for the whole (N, K) matrix)
@@ -212,7 +223,8 @@ hipError_t mdt_launch_pack_weight(const float* w, int n_rows, int K, float* pack
 hipError_t mdt_launch_pack_weight_glu(const float* w, int H, int K, float* packed, hipStream_t s);
 // one move of a batched parameter upload (k_multi_load): src is (rows, K) row-major on the device
 enum { MDT_LOAD_RAW = 0, MDT_LOAD_PACK = 1, MDT_LOAD_PACK_T = 2, MDT_LOAD_TRANSPOSE = 3, MDT_LOAD_PAD_COLS = 4,
-       MDT_LOAD_PACK_SPLIT = 5 };  // PACK_SPLIT: the three-way bf16 split fragment image (mdt_mlp_split.h); dst is a byte image of 6 rows K bytes
+       MDT_LOAD_PACK_SPLIT = 5,    // PACK_SPLIT: the three-way bf16 split fragment image (mdt_mlp_split.h); dst is a byte image of 6 rows K bytes
+       MDT_LOAD_PACK_PAIR = 6 };   // PACK_PAIR: the fp16 pair image; ONE block per 16 source rows (its chunk index = the tile), p0 = n_off
 struct mdt_load_entry {
     const float* src;
     float* dst;

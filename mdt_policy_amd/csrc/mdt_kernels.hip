@@ -115,6 +115,73 @@ hipError_t mdt_launch_split_from_packed(const float* wp, int N, int K, void* ima
     return hipGetLastError();
 }
 
+// ---- the fp16 PAIR image (mdt_mlp_split.h: column tile = K / 32 steps x 2 parts x 1 KiB + a 16-byte trailer with the tile's scale) ----
+// One workgroup of 256 threads per column tile: the tile's largest |w| (ordered bits, so Inf / NaN reach the scale), the power-of-two
+// scale of mdt_device.h, then the two parts of every quad.  No global reduction: a tile is 16 rows of the source.
+__device__ __forceinline__ unsigned block_max_u32(unsigned mx, unsigned* red4, int tid) {   // 256 threads; every thread gets the maximum
+    mx = wave_max_u32(mx);
+    __syncthreads();                                  // (red4 may still be read from an earlier call)
+    if ((tid & 63) == 0) red4[tid >> 6] = mx;
+    __syncthreads();
+    return max(max(red4[0], red4[1]), max(red4[2], red4[3]));
+}
+// rows [16 t, 16 t + 16) of the (., K) row-major source -> column tile t + n_off / 16 of the image
+__device__ __forceinline__ void pack_pair_tile(const float* __restrict__ src, char* __restrict__ image, int t, int K, int n_off,
+                                               unsigned* red4, int tid) {
+    const int K4 = K >> 2, K32 = K >> 5;
+    const float* rows = src + (int64_t)t * 16 * K;
+    unsigned mx = 0u;
+    for (int i = tid; i < 16 * K4; i += 256) mx = max(mx, pair_absbits4(*(const f32x4*)(rows + 4 * i)));
+    mx = block_max_u32(mx, red4, tid);
+    const float sc = pair_scale(mx);
+    char* tile = image + (int64_t)(t + (n_off >> 4)) * ((int64_t)K32 * 2048 + 16);
+    for (int i = tid; i < 16 * K4; i += 256) {
+        const int r = i / K4, c = 4 * (i - r * K4);
+        mdt_f16x4 p1, p2;
+        split2_f16(*(const f32x4*)(rows + (int64_t)r * K + c), sc, p1, p2);
+        char* q = tile + (c >> 5) * 2048 + (r + 16 * ((c & 15) >> 2)) * 16 + ((c & 31) >> 4) * 8;
+        *(mdt_f16x4*)q = p1;
+        *(mdt_f16x4*)(q + 1024) = p2;
+    }
+    if (tid == 0) *(f32x4*)(tile + (int64_t)K32 * 2048) = (f32x4){sc, 0.f, 0.f, 0.f};
+}
+__global__ __launch_bounds__(256) void k_pack_weight_pair(const float* __restrict__ w, int K, char* __restrict__ image, int n_off) {
+    __shared__ unsigned red4[4];
+    pack_pair_tile(w, image, blockIdx.x, K, n_off, red4, threadIdx.x);
+}
+hipError_t mdt_launch_pack_weight_pair(const float* w, int n_rows, int K, void* image, hipStream_t s, int n_off) {
+    if (n_rows <= 0 || n_rows % 16 || n_off % 16 || K % 32) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pack_weight_pair, dim3((unsigned)(n_rows / 16)), dim3(256), 0, s, w, K, (char*)image, n_off);
+    return hipGetLastError();
+}
+// the same image from the fp32 fragment image of the weight (column tile nt = 16 K consecutive floats of it): same maximum, same
+// scale, same parts -- bit for bit what k_pack_weight_pair makes from the raw weight
+__global__ __launch_bounds__(256) void k_pair_from_packed(const float* __restrict__ wp, int K32, char* __restrict__ image) {
+    __shared__ unsigned red4[4];
+    const int tid = threadIdx.x;
+    const float* src = wp + (int64_t)blockIdx.x * K32 * 512;
+    unsigned mx = 0u;
+    for (int i = tid; i < K32 * 128; i += 256) mx = max(mx, pair_absbits4(*(const f32x4*)(src + 4 * i)));
+    mx = block_max_u32(mx, red4, tid);
+    const float sc = pair_scale(mx);
+    char* tile = image + (int64_t)blockIdx.x * ((int64_t)K32 * 2048 + 16);
+    for (int i = tid; i < K32 * 64; i += 256) {
+        const int kk = i >> 6, lane = i & 63;
+        mdt_f16x4 l1, l2, h1, h2;
+        split2_f16(*(const f32x4*)(src + ((2 * kk) * 64 + lane) * 4), sc, l1, l2);
+        split2_f16(*(const f32x4*)(src + ((2 * kk + 1) * 64 + lane) * 4), sc, h1, h2);
+        char* q = tile + kk * 2048 + lane * 16;
+        *(mdt_f16x8*)q = __builtin_shufflevector(l1, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+        *(mdt_f16x8*)(q + 1024) = __builtin_shufflevector(l2, h2, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+    if (tid == 0) *(f32x4*)(tile + (int64_t)K32 * 2048) = (f32x4){sc, 0.f, 0.f, 0.f};
+}
+hipError_t mdt_launch_pair_from_packed(const float* wp, int N, int K, void* image, hipStream_t s) {
+    if (N <= 0 || N % 16 || K % 32) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pair_from_packed, dim3((unsigned)(N / 16)), dim3(256), 0, s, wp, K / 32, (char*)image);
+    return hipGetLastError();
+}
+
 // Every parameter image of one load_state_dict / optimizer step in ONE launch (mdt_load_params): a table of moves --
 // raw copies, fragment packs, transposed fragment packs (training), transposes, column pads -- and a (move, chunk) list,
 // one workgroup per 1024 source elements.  The per-parameter launches this replaces (~230 of 3-6 us for MDT-V) were
@@ -123,6 +190,11 @@ __global__ __launch_bounds__(256) void k_multi_load(const mdt_load_entry* __rest
     const int2 bk = blocks[blockIdx.x];
     const mdt_load_entry e = tab[bk.x];
     const int64_t n = (int64_t)e.rows * e.K;
+    if (e.kind == MDT_LOAD_PACK_PAIR) {   // one workgroup per 16-row column tile (bk.y) of the fp16 pair image
+        __shared__ unsigned red4[4];
+        pack_pair_tile(e.src, (char*)e.dst, bk.y, e.K, e.p0, red4, threadIdx.x);
+        return;
+    }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int64_t idx = (int64_t)bk.y * 1024 + threadIdx.x + 256 * u;
@@ -234,7 +306,8 @@ __global__ __launch_bounds__(512) void k_mlp(mdt_gemm_args f, mdt_gemm_args p, f
 // k_mlp_split: the same launch in the three-way bf16 split form (mdt_mlp_split.h).  Workgroups in SLICE-major order, XCD x taking a
 // contiguous range of it (block b runs on XCD b % 8): an XCD's L2 then holds one or two slices of the split weight images (2.4 MB
 // each at d = 384) instead of all of them.  grid = 8 * ceil(tiles * slices / 8).
-template <int NTW2, int PRO>
+// SCH: the split scheme (mdt_mlp_split.h): the three-way bf16 split, or the two-way fp16 pair split the model's launches use
+template <int NTW2, int PRO, int SCH = MDT_SPLIT_BF16X3>
 __global__ __launch_bounds__(512) void k_mlp_split(mdt_gemm_args f, mdt_gemm_args p, const char* __restrict__ w1s, const char* __restrict__ w2s,
                                                    float* __restrict__ parts, int64_t part_stride, int n_slices, int gm,
                                                    const float* __restrict__ zeros) {
@@ -243,7 +316,7 @@ __global__ __launch_bounds__(512) void k_mlp_split(mdt_gemm_args f, mdt_gemm_arg
     const int i = blockIdx.x >> 3, w = (blockIdx.x & 7) * per + i;
     if (i >= per || w >= total) return;
     const int s = w / gm, by = w - s * gm;
-    mlp_split_tile<NTW2, PRO>(f, p, w1s, w2s, parts, part_stride, by, s, lds_c, zeros, threadIdx.x);
+    mlp_split_tile<NTW2, PRO, SCH>(f, p, w1s, w2s, parts, part_stride, by, s, lds_c, zeros, threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -884,7 +957,7 @@ hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
             return (a.N % 256 == 0) ? launch_gemm_glu<2, 4, 4, 3>(a, kc, s) : launch_gemm_glu<2, 2, 4, 3>(a, kc, s);
         return (a.N % 192 == 0) ? launch_gemm_glu<2, 3, 4, 4>(a, kc, s) : launch_gemm_glu<2, 2, 4, 4>(a, kc, s);
     }
-    if (gemm_ln_split_applies(a)) return launch_gemm_ln_split(a, s);   // the wide LayerNorm-prologue products in the bf16 split form
+    if (gemm_ln_split_applies(a)) return launch_gemm_ln_split(a, s);   // the wide LayerNorm-prologue products in a split form (Wp_split: bf16 x 3, Wp_pair: fp16 x 2)
     if (a.a_parts > 1) return launch_gemm_merge(a, s);
     // ... and beyond one row tile, the products whose half-height (16 x 64) tiling would leave most of the chip empty keep the
     // split-K kernel, which has 4x the workgroups: fewer than 60 tiles behind a LayerNorm prologue (every 16-column workgroup
@@ -1034,36 +1107,52 @@ hipError_t mdt_launch_mlp(const mdt_gemm_args& f, const mdt_gemm_args& p, float*
 }
 
 // ---- the LayerNorm-prologue product on the wide tiles in the split form (gemm_ln_split_tile) ----
-template <int ND, int NTW, int PRO, int XP>
+template <int ND, int NTW, int PRO, int XP, int SCH = MDT_SPLIT_BF16X3>
 __global__ __launch_bounds__(512) void k_gemm_ln_split(mdt_gemm_args a, int grid_n, const float* __restrict__ zeros) {
     extern __shared__ __attribute__((aligned(16))) char lds_c[];
     const int logical = xcd_remap(blockIdx.x, gridDim.x);   // the column panels of a row tile are neighbours: they share the rows' L2
     const int by = logical / grid_n, bx = logical - by * grid_n;
-    gemm_ln_split_tile<ND, NTW, PRO, XP>(a, by, bx, lds_c, zeros, threadIdx.x);
+    gemm_ln_split_tile<ND, NTW, PRO, XP, SCH>(a, by, bx, lds_c, zeros, threadIdx.x);
 }
-template <int ND, int NTW, int PRO, int XP>
+template <int ND, int NTW, int PRO, int XP, int SCH>
 static hipError_t launch_gemm_ln_split_t(const mdt_gemm_args& a, hipStream_t s) {
     const int gn = a.N / (8 * NTW * 16), gm = (a.M + 31) / 32;
-    const int lds = 3 * 32 * (2 * 128 * ND + 32);
-    return mdt_launch_lds<k_gemm_ln_split<ND, NTW, PRO, XP>>(dim3(gn * gm), dim3(512), lds, s, a, gn, g_zeros);
+    const int lds = gemm_ln_split_lds_bytes(128 * ND, SCH);
+    return mdt_launch_lds<k_gemm_ln_split<ND, NTW, PRO, XP, SCH>>(dim3(gn * gm), dim3(512), lds, s, a, gn, g_zeros);
 }
-template <int ND, int NTW>
+template <int ND, int NTW, int SCH>
 static hipError_t launch_gemm_ln_split_pro(const mdt_gemm_args& a, hipStream_t s) {
     const int xp = a.a_parts >= 2 && a.a_parts <= 4 ? a.a_parts : 1;   // one array, or the sum of 2..4 slabs
     return mdt_with_pro<PRO_LN>(a, [&](auto pro) {
-        return mdt_with_const<1, 4>(xp, [&](auto x) { return launch_gemm_ln_split_t<ND, NTW, decltype(pro)::value, decltype(x)::value>(a, s); });
+        return mdt_with_const<1, 4>(xp, [&](auto x) { return launch_gemm_ln_split_t<ND, NTW, decltype(pro)::value, decltype(x)::value, SCH>(a, s); });
     });
 }
 // which products take it: the split image is there, LayerNorm prologue over whole rows of K = 384, column count a multiple of the
 // 384-wide panels, plain output rows, and enough rows that the wide tiles are the choice anyway (the fused MLP's threshold)
+static bool gemm_ln_split_shape(const mdt_gemm_args& a) {
+    return a.ln && (a.K == 384 || a.K == 512) && a.N % 384 == 0 && a.M >= 1 &&
+           a.batch <= 1 && !a.residual && a.gin == 1 && a.gout == 1 && a.goff == 0 && a.rowvec == nullptr && !a.aux_mode &&
+           a.a_parts <= 4 && (a.lda & 3) == 0 && (a.ldo & 3) == 0;
+}
 static bool gemm_ln_split_applies(const mdt_gemm_args& a) {
-    return a.Wp_split != nullptr && mdt_mlp_split_enabled() && a.ln && (a.K == 384 || a.K == 512) && a.N % 384 == 0 &&
-           a.M >= mdt_split_min_rows() && a.batch <= 1 && !a.residual && a.gin == 1 && a.gout == 1 && a.goff == 0 && a.rowvec == nullptr && !a.aux_mode &&
-           a.a_parts <= 4 && (a.lda & 3) == 0 && (a.ldo & 3) == 0 && g_mdt_sw.gemm_geometry == 0;
+    return (a.Wp_split != nullptr || a.Wp_pair != nullptr) && mdt_mlp_split_enabled() && gemm_ln_split_shape(a) &&
+           a.M >= mdt_split_min_rows() && g_mdt_sw.gemm_geometry == 0;
 }
 static hipError_t launch_gemm_ln_split(const mdt_gemm_args& a, hipStream_t s) {
     // (the tile is written for any D <= 512 and 256-wide panels too; instantiated for the two shipped widths: MDT-V d = 384, MDT d = 512)
-    return a.K == 512 ? launch_gemm_ln_split_pro<4, 3>(a, s) : launch_gemm_ln_split_pro<3, 3>(a, s);
+    // (Wp_split, where given, keeps its three-way bf16 form; the fp16 pair image otherwise)
+    if (a.Wp_split == nullptr)
+        return a.K == 512 ? launch_gemm_ln_split_pro<4, 3, MDT_SPLIT_F16X2>(a, s) : launch_gemm_ln_split_pro<3, 3, MDT_SPLIT_F16X2>(a, s);
+    return a.K == 512 ? launch_gemm_ln_split_pro<4, 3, MDT_SPLIT_BF16X3>(a, s) : launch_gemm_ln_split_pro<3, 3, MDT_SPLIT_BF16X3>(a, s);
+}
+
+// the pair form on its own, at any row count and whatever the switches say (mdt_op_gemm_ln_pair)
+bool mdt_gemm_ln_pair_supported(const mdt_gemm_args& a) { return a.Wp_pair != nullptr && gemm_ln_split_shape(a); }
+hipError_t mdt_launch_gemm_ln_pair(const mdt_gemm_args& a, hipStream_t s) {
+    if (!mdt_gemm_ln_pair_supported(a)) return hipErrorInvalidValue;
+    hipError_t ze = ensure_zeros();
+    if (ze != hipSuccess) return ze;
+    return a.K == 512 ? launch_gemm_ln_split_pro<4, 3, MDT_SPLIT_F16X2>(a, s) : launch_gemm_ln_split_pro<3, 3, MDT_SPLIT_F16X2>(a, s);
 }
 
 // ---- the fused MLP sublayer in the three-way bf16 split form (k_mlp_split) ----
@@ -1074,13 +1163,13 @@ int mdt_split_min_rows() { return 768; }
 bool mdt_mlp_split_supported(const mdt_gemm_args& f, const mdt_gemm_args& p) {
     return mdt_mlp_supported(f, p);
 }
-template <int NTW2, int PRO>
+template <int NTW2, int PRO, int SCH>
 static hipError_t launch_mlp_split_t(const mdt_gemm_args& f, const mdt_gemm_args& p, const void* w1s, const void* w2s, float* parts,
                                      int64_t part_stride, hipStream_t s) {
     const int S = mdt_mlp_slices(f.K), gm = (f.M + 31) / 32;
-    const int lds = mlp_split_lds_bytes(128 * NTW2);
+    const int lds = mlp_split_lds_bytes(128 * NTW2, SCH);
     const int per = (gm * S + 7) / 8;
-    return mdt_launch_lds<k_mlp_split<NTW2, PRO>>(dim3(8 * per), dim3(512), lds, s, f, p, (const char*)w1s, (const char*)w2s, parts,
+    return mdt_launch_lds<k_mlp_split<NTW2, PRO, SCH>>(dim3(8 * per), dim3(512), lds, s, f, p, (const char*)w1s, (const char*)w2s, parts,
                                                   part_stride, S, gm, g_zeros);
 }
 hipError_t mdt_launch_mlp_split(const mdt_gemm_args& f, const mdt_gemm_args& p, const void* w1s, const void* w2s, float* parts,
@@ -1090,7 +1179,19 @@ hipError_t mdt_launch_mlp_split(const mdt_gemm_args& f, const mdt_gemm_args& p, 
     if (ze != hipSuccess) return ze;
     return mdt_with_const<1, 4>(std::min(f.K / 128, 4), [&](auto ntw2) {
         return mdt_with_pro<PRO_LN>(f, [&](auto pro) {
-            return launch_mlp_split_t<decltype(ntw2)::value, decltype(pro)::value>(f, p, w1s, w2s, parts, part_stride, s);
+            return launch_mlp_split_t<decltype(ntw2)::value, decltype(pro)::value, MDT_SPLIT_BF16X3>(f, p, w1s, w2s, parts, part_stride, s);
+        });
+    });
+}
+// the same launch on fp16 pair images (mdt_launch_pack_weight_pair) of fc / proj
+hipError_t mdt_launch_mlp_pair(const mdt_gemm_args& f, const mdt_gemm_args& p, const void* w1p, const void* w2p, float* parts,
+                               int64_t part_stride, hipStream_t s) {
+    if (!mdt_mlp_split_supported(f, p) || !w1p || !w2p) return hipErrorInvalidValue;
+    hipError_t ze = ensure_zeros();
+    if (ze != hipSuccess) return ze;
+    return mdt_with_const<1, 4>(std::min(f.K / 128, 4), [&](auto ntw2) {
+        return mdt_with_pro<PRO_LN>(f, [&](auto pro) {
+            return launch_mlp_split_t<decltype(ntw2)::value, decltype(pro)::value, MDT_SPLIT_F16X2>(f, p, w1p, w2p, parts, part_stride, s);
         });
     });
 }

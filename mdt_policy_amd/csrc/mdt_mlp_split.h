@@ -1,4 +1,5 @@
-// mdt_mlp_split.h -- the fused MLP launch (mdt_tiles.h mlp_tile) in the THREE-WAY bf16 SPLIT form (round 6).
+// mdt_mlp_split.h -- the fused MLP launch (mdt_tiles.h mlp_tile) in its SPLIT forms: the THREE-WAY bf16 split (round 6; DESIGN.md section
+// 5a (h)), described first, and the TWO-WAY fp16 PAIR split the model's launches take (5a (i); `split_scheme` below).
 //
 // Same work per workgroup as mlp_tile -- row tile `by` (32 rows) x hidden slice `s` (512 of the 4 D hidden columns):
 //   x + gate * (act(prologue(x) W1^T + b1) W2^T + b2),  partial slab s of the second product to parts + s * part_stride --
@@ -28,14 +29,41 @@
 #include "mdt_tiles.h"
 #include "mdt_ws.h"   // mdt_bf16x8 / mdt_bf16x4, split3_bf16
 
+#include <type_traits>
+
+// ---- the split SCHEME of every body below (template parameter SCH) ----
+//   MDT_SPLIT_BF16X3  three bf16 parts per operand, six products per k32 step, 6 bytes per weight (everything written above);
+//   MDT_SPLIT_F16X2   the PAIR form: two fp16 parts of the SCALED operand (mdt_device.h split2_f16: 22 significand bits), THREE
+//                     v_mfma_f32_16x16x32_f16 products per k32 step (x2 w1, x1 w2, x1 w1), 4 bytes per weight -- half the matrix-pipe
+//                     clocks and two thirds of the weight stream, the two co-limits of these launches.  One power-of-two scale per
+//                     activation row (LayerNorm prologue: a wave reduction; hidden slice: an LDS maximum written before the barrier
+//                     that separates the products anyway) and one per 16-column weight tile (made by the pack kernel); the epilogue
+//                     undoes both with one v_ldexp_f32 per value before bias, activation and gate.
+// Pair image of an (N, K) weight: column tile nt = K / 32 steps x 2 parts x 1 KiB fragments (lane / slot order as above) followed by
+// a 16-byte trailer {fp32 scale, 0, 0, 0}: tile stride K / 32 * 2048 + 16 bytes, image size 4 N K + N bytes.
+template <int SCH> struct split_scheme {
+    static constexpr int P = SCH == MDT_SPLIT_F16X2 ? 2 : 3;                 // parts per operand
+    static constexpr int FRAG = P * 1024;                                    // bytes of one (column tile, k32 step)
+    static constexpr int TRAILER = SCH == MDT_SPLIT_F16X2 ? 16 : 0;          // bytes behind a column tile's fragments
+    using frag_t = std::conditional_t<SCH == MDT_SPLIT_F16X2, mdt_f16x8, mdt_bf16x8>;
+    __host__ __device__ static constexpr int64_t tile_stride(int K32) { return (int64_t)K32 * FRAG + TRAILER; }
+};
+// exponent of column tile nt's scale (pair images)
+__device__ __forceinline__ int pair_tile_exp(const char* image, int64_t tile_stride, int nt) {
+    const unsigned b = __float_as_uint(*(const float*)(image + (nt + 1) * tile_stride - 16));
+    return (int)((b >> 23) & 255u) - 127;
+}
+
 // ring of R k32 steps x NT column tiles x 3 parts of weight fragments.  Fragment (j, kk, p) of the wave sits at byte
 // base + j * tile_stride + (kk * 3 + p) * 1024 of the image, lane l's 16 bytes at l * 16.  BUFFER loads (resource = the image, one
 // 32-bit per-lane offset per column tile, the step / part offset in the scalar operand): a global_load sends 64 x 8 bytes of address
 // through the SIMD's register read path, 33 clocks of matrix-pipe time against 17.7 (mdt_tiles.h WStream) -- and this form requests
 // 1.5x the fragments of the fp32 one per step.
-template <int NT, int R>
+template <int NT, int R, int SCH = MDT_SPLIT_BF16X3>
 struct SplitRing {
-    mdt_bf16x8 w[R][NT][3];
+    static constexpr int P = split_scheme<SCH>::P;
+    using frag_t = typename split_scheme<SCH>::frag_t;
+    frag_t w[R][NT][P];
     __amdgpu_buffer_rsrc_t rs;
     unsigned voff[NT];
     __device__ __forceinline__ void open(const void* image, int64_t first_byte, int64_t tile_stride, int lane) {
@@ -47,17 +75,56 @@ struct SplitRing {
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
-            for (int p = 0; p < 3; ++p)
-                w[slot][j][p] = __builtin_bit_cast(mdt_bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff[j], (kk * 3 + p) * 1024, 0));
+            for (int p = 0; p < P; ++p)
+                w[slot][j][p] = __builtin_bit_cast(frag_t, __builtin_amdgcn_raw_buffer_load_b128(rs, voff[j], (kk * P + p) * 1024, 0));
     }
 };
 
 // one product phase: acc[i][j] += sum over K32 k32 steps; ring slots 0 .. R - 2 hold steps 0 .. R - 2 on entry (requested by the
 // caller, early); activations from the split tile at `xa` (row stride rowb, part
 // stride part)
-template <int NT, int K32, int R>
-__device__ __forceinline__ void split_phase(SplitRing<NT, R>& ring, const char* xa, int rowb, int part, int lane, f32x4 (&acc)[2][NT]) {
+template <int NT, int K32, int R, int SCH>
+__device__ __forceinline__ void split_phase(SplitRing<NT, R, SCH>& ring, const char* xa, int rowb, int part, int lane, f32x4 (&acc)[2][NT]) {
     const int aoff = (lane & 15) * rowb + (lane >> 4) * 16;
+    if constexpr (SCH == MDT_SPLIT_F16X2) {
+        mdt_f16x8 x1[2], x2[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const char* q = xa + aoff + i * 16 * rowb;
+            x1[i] = *(const mdt_f16x8*)q; x2[i] = *(const mdt_f16x8*)(q + part);
+        }
+#pragma unroll
+        for (int kk = 0; kk < K32; ++kk) {
+            const int u = kk % R, un = (kk + R - 1) % R;
+            const bool nx = kk + 1 < K32;
+            if (kk + R - 1 < K32) ring.request(un, kk + R - 1);
+            const char* p0 = xa + aoff + (kk + 1) * 64;
+            const char* p1 = p0 + 16 * rowb;
+            MDT_SCHED_PIN
+            // the three products of this k32 step, smallest first; same pinned order as the six of the bf16 form below
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][0], x2[0], acc[0][j], 0, 0, 0);
+                acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][0], x2[1], acc[1][j], 0, 0, 0);
+            }
+            MDT_SCHED_PIN
+            if (nx) { x2[0] = *(const mdt_f16x8*)(p0 + part); x2[1] = *(const mdt_f16x8*)(p1 + part); }
+            MDT_SCHED_PIN
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][1], x1[0], acc[0][j], 0, 0, 0);
+                acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][1], x1[1], acc[1][j], 0, 0, 0);
+            }
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][0], x1[0], acc[0][j], 0, 0, 0);
+                acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][0], x1[1], acc[1][j], 0, 0, 0);
+            }
+            MDT_SCHED_PIN
+            if (nx) { x1[0] = *(const mdt_f16x8*)p0; x1[1] = *(const mdt_f16x8*)p1; }
+            MDT_SCHED_PIN
+        }
+    } else {
     mdt_bf16x8 x1[2], x2[2], x3[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -114,15 +181,18 @@ __device__ __forceinline__ void split_phase(SplitRing<NT, R>& ring, const char* 
         if (nx) { x1[0] = *(const mdt_bf16x8*)p0; x1[1] = *(const mdt_bf16x8*)p1; }
         MDT_SCHED_PIN
     }
+    }
 }
 
-// LDS bytes of mlp_split_tile at model width D
-__host__ __device__ constexpr int mlp_split_lds_bytes(int D) {
-    const int xs = 3 * 32 * (2 * D + 32), hs = 3 * 32 * (2 * 512 + 32);
-    return xs > hs ? xs : hs;
+// LDS bytes of mlp_split_tile at model width D (pair form: two parts -- 67.6 KB for D <= 512 -- + the rows' 32 scale exponents of
+// the first product and the 32 maxima of the hidden rows)
+__host__ __device__ constexpr int mlp_split_lds_bytes(int D, int sch = MDT_SPLIT_BF16X3) {
+    const int P = sch == MDT_SPLIT_F16X2 ? 2 : 3;
+    const int xs = P * 32 * (2 * D + 32), hs = P * 32 * (2 * 512 + 32);
+    return (xs > hs ? xs : hs) + (sch == MDT_SPLIT_F16X2 ? 256 : 0);
 }
 
-template <int NTW2, int PRO>
+template <int NTW2, int PRO, int SCH = MDT_SPLIT_BF16X3>
 __device__ __forceinline__ void mlp_split_tile(const mdt_gemm_args& f, const mdt_gemm_args& p, const char* __restrict__ w1s,
                                                const char* __restrict__ w2s, float* __restrict__ parts, int64_t part_stride, int by,
                                                int s, char* lds, const float* __restrict__ zeros, int tid) {
@@ -130,17 +200,26 @@ __device__ __forceinline__ void mlp_split_tile(const mdt_gemm_args& f, const mdt
     constexpr int D = 128 * NTW2, K32a = D / 32, K32b = HS / 32;
     constexpr int ROWB1 = 2 * D + 32, PART1 = MT * ROWB1, ROWB2 = 2 * HS + 32, PART2 = MT * ROWB2;
     static_assert(NTW2 >= 1 && NTW2 <= 4, "D <= 512");
+    using SS = split_scheme<SCH>;
+    constexpr bool PAIR = SCH == MDT_SPLIT_F16X2;
+    constexpr int FRAG = SS::FRAG;
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int lane = tid & 63, wave = tid >> 6;
     const int m0 = by * MT;
     const int nq = 4 * (lane >> 4);
-    char* xs = lds;                                   // split x tile: 3 parts x [32][ROWB1]
-    char* hs = lds;                                   // split hidden slice: 3 parts x [32][ROWB2] (after the first product)
+    char* xs = lds;                                   // split x tile: P parts x [32][ROWB1]
+    char* hs = lds;                                   // split hidden slice: P parts x [32][ROWB2] (after the first product)
+    // pair form, behind both tiles: ordered bits of the hidden rows' largest |value|, scale exponents of the x rows
+    unsigned* hmax = (unsigned*)(lds + mlp_split_lds_bytes(D, SCH) - 256);
+    int* xexp = (int*)(hmax + 32);
+    if constexpr (PAIR) {
+        if (tid < 32) hmax[tid] = 0u;                 // (the barrier behind the prologue orders this before the first maximum)
+    }
 
     // ---- first product's operands: the ring's first step and the bias travel under the prologue ----
     const int nt1 = (s * NWAVES + wave) * NTW1;       // hidden column tiles of this wave (global)
-    SplitRing<NTW1, R> ring1;
-    ring1.open(w1s, (int64_t)nt1 * K32a * 3072, (int64_t)K32a * 3072, lane);
+    SplitRing<NTW1, R, SCH> ring1;
+    ring1.open(w1s, nt1 * SS::tile_stride(K32a), SS::tile_stride(K32a), lane);
 #pragma unroll
     for (int u = 0; u < R - 1; ++u) ring1.request(u, u);
     f32x4 b1[NTW1];
@@ -150,20 +229,20 @@ __device__ __forceinline__ void mlp_split_tile(const mdt_gemm_args& f, const mdt
         for (int j = 0; j < NTW1; ++j) b1[j] = ldg4(bp + (nt1 + j) * 16 + nq);
     }
     // LayerNorm (+ modulate) of the tile's rows, stored as their split in MFMA slot order
-    gemm_stage_tile<MTILES, NWAVES, PRO, false, 1, 2, true>(f, (float*)xs, ROWB1, m0, 0, D, zeros, tid, lane, wave);
+    gemm_stage_tile<MTILES, NWAVES, PRO, false, 1, 2, SCH>(f, (float*)xs, ROWB1, m0, 0, D, zeros, tid, lane, wave, nullptr, xexp);
     __syncthreads();
     f32x4 acc1[MTILES][NTW1];
 #pragma unroll
     for (int i = 0; i < MTILES; ++i)
 #pragma unroll
         for (int j = 0; j < NTW1; ++j) acc1[i][j] = zero4;
-    split_phase<NTW1, K32a, R>(ring1, xs, ROWB1, PART1, lane, acc1);
+    split_phase<NTW1, K32a, R, SCH>(ring1, xs, ROWB1, PART1, lane, acc1);
 
     // ---- second product's operands, requested before the activation epilogue so that they travel while it runs: the first
     //      fragments of W2's K slice [512 s, 512 s + 512), then bias / gate / residual rows of the output tile ----
     const int K32p = p.K >> 5;                        // k32 steps of the whole second product (4 D / 32)
-    SplitRing<NTW2, R> ring2;
-    ring2.open(w2s, ((int64_t)(wave * NTW2) * K32p + (int64_t)s * K32b) * 3072, (int64_t)K32p * 3072, lane);
+    SplitRing<NTW2, R, SCH> ring2;
+    ring2.open(w2s, (wave * NTW2) * SS::tile_stride(K32p) + (int64_t)s * K32b * FRAG, SS::tile_stride(K32p), lane);
 #pragma unroll
     for (int u = 0; u < R - 1; ++u) ring2.request(u, u);
     // (d = 512, four column tiles per wave: gate and residual rows are requested behind the second product instead -- 64 registers
@@ -198,21 +277,48 @@ __device__ __forceinline__ void mlp_split_tile(const mdt_gemm_args& f, const mdt
             for (int j = 0; j < NTW2; ++j) acc2[i][j] = zero4;
         if constexpr (EARLY) load_gate_res();
     }
+    int he[MTILES] = {0, 0};                          // (pair) scale exponents of the lane's two hidden rows
+    if constexpr (PAIR) {
+        // activation in place, each hidden row's largest |value| over the 512-wide slice into LDS BEFORE the barrier
+        int et1[NTW1];
+#pragma unroll
+        for (int j = 0; j < NTW1; ++j) et1[j] = pair_tile_exp(w1s, SS::tile_stride(K32a), nt1 + j);
+#pragma unroll
+        for (int i = 0; i < MTILES; ++i) {
+            const int xe = xexp[i * 16 + (lane & 15)];
+            unsigned mx = 0u;
+#pragma unroll
+            for (int j = 0; j < NTW1; ++j) {
+                acc1[i][j] = apply_act(pair_unscale(acc1[i][j], xe + et1[j]) + b1[j], f.act);
+                mx = max(mx, pair_absbits4(acc1[i][j]));
+            }
+            atomicMax(&hmax[i * 16 + (lane & 15)], mx);
+        }
+    }
     __syncthreads();                                  // everybody has read the x tile: the hidden slice overwrites it
     // ---- activation epilogue of the first product -> split hidden slice (lane holds hidden[16 i + lane % 16][tile * 16 + nq .. + 3]) ----
 #pragma unroll
     for (int i = 0; i < MTILES; ++i)
 #pragma unroll
         for (int j = 0; j < NTW1; ++j) {
-            mdt_bf16x4 p1, p2, p3;
-            split3_bf16(apply_act(acc1[i][j] + b1[j], f.act), p1, p2, p3);
             char* q = hs + split_slot(i * 16 + (lane & 15), (wave * NTW1 + j) * 16 + nq, ROWB2);
-            *(mdt_bf16x4*)q = p1;
-            *(mdt_bf16x4*)(q + PART2) = p2;
-            *(mdt_bf16x4*)(q + 2 * PART2) = p3;
+            if constexpr (PAIR) {
+                const unsigned mx = hmax[i * 16 + (lane & 15)];
+                he[i] = pair_scale_exp(mx);
+                mdt_f16x4 p1, p2;
+                split2_f16(acc1[i][j], pair_scale(mx), p1, p2);
+                *(mdt_f16x4*)q = p1;
+                *(mdt_f16x4*)(q + PART2) = p2;
+            } else {
+                mdt_bf16x4 p1, p2, p3;
+                split3_bf16(apply_act(acc1[i][j] + b1[j], f.act), p1, p2, p3);
+                *(mdt_bf16x4*)q = p1;
+                *(mdt_bf16x4*)(q + PART2) = p2;
+                *(mdt_bf16x4*)(q + 2 * PART2) = p3;
+            }
         }
     __syncthreads();
-    split_phase<NTW2, K32b, R>(ring2, hs, ROWB2, PART2, lane, acc2);
+    split_phase<NTW2, K32b, R, SCH>(ring2, hs, ROWB2, PART2, lane, acc2);
 
     if constexpr (!EARLY) load_gate_res();
     float* out = parts + (int64_t)s * part_stride;
@@ -221,7 +327,9 @@ __device__ __forceinline__ void mlp_split_tile(const mdt_gemm_args& f, const mdt
         const int m = m0 + i * 16 + (lane & 15);
 #pragma unroll
         for (int j = 0; j < NTW2; ++j) {
-            f32x4 v = acc2[i][j] + b2[j];
+            f32x4 v = acc2[i][j];
+            if constexpr (PAIR) v = pair_unscale(v, he[i] + pair_tile_exp(w2s, SS::tile_stride(K32p), wave * NTW2 + j));
+            v = v + b2[j];
             v = res_v[i][j] + (gated ? gate_v[i][j] * v : v);
             if (m < f.M) st4(out + (int64_t)m * p.ldo + ncol[j], v);
         }
@@ -235,8 +343,14 @@ __device__ __forceinline__ void mlp_split_tile(const mdt_gemm_args& f, const mdt
 // in a.a_merged).  The first half of mlp_split_tile with a plain epilogue: out = act(product + bias), plain output rows.
 // LDS: the split x tile (76.8 KB at D = 384).
 // ------------------------------------------------------------------------------------------------
-template <int ND, int NTW, int PRO, int XP>
+// Pair form (SCH = MDT_SPLIT_F16X2): the image is a.Wp_pair, LDS = the two-part x tile (51.2 KB at D = 384) + the rows' 32 scale exponents.
+__host__ __device__ constexpr int gemm_ln_split_lds_bytes(int D, int sch = MDT_SPLIT_BF16X3) {
+    return sch == MDT_SPLIT_F16X2 ? 2 * 32 * (2 * D + 32) + 128 : 3 * 32 * (2 * D + 32);
+}
+template <int ND, int NTW, int PRO, int XP, int SCH = MDT_SPLIT_BF16X3>
 __device__ __forceinline__ void gemm_ln_split_tile(const mdt_gemm_args& a, int by, int bx, char* lds, const float* __restrict__ zeros, int tid) {
+    using SS = split_scheme<SCH>;
+    constexpr bool PAIR = SCH == MDT_SPLIT_F16X2;
     constexpr int MTILES = 2, NWAVES = 8, MT = 32, R = 2;
     constexpr int D = 128 * ND, K32 = D / 32, ROWB = 2 * D + 32, PART = MT * ROWB;
     static_assert(ND >= 1 && ND <= 4, "D <= 512");
@@ -245,8 +359,10 @@ __device__ __forceinline__ void gemm_ln_split_tile(const mdt_gemm_args& a, int b
     const int m0 = by * MT, nq = 4 * (lane >> 4);
     char* xs = lds;
     const int nt0 = (bx * NWAVES + wave) * NTW;       // N is a multiple of the panel width: every wave has NTW real column tiles
-    SplitRing<NTW, R> ring;
-    ring.open(a.Wp_split, (int64_t)nt0 * K32 * 3072, (int64_t)K32 * 3072, lane);
+    SplitRing<NTW, R, SCH> ring;
+    const char* image = (const char*)(PAIR ? a.Wp_pair : a.Wp_split);
+    int* xexp = (int*)(lds + 2 * PART);               // (pair) scale exponents of the tile's rows
+    ring.open(image, nt0 * SS::tile_stride(K32), SS::tile_stride(K32), lane);
 #pragma unroll
     for (int u = 0; u < R - 1; ++u) ring.request(u, u);
     f32x4 bias_v[NTW];
@@ -255,20 +371,24 @@ __device__ __forceinline__ void gemm_ln_split_tile(const mdt_gemm_args& a, int b
 #pragma unroll
         for (int j = 0; j < NTW; ++j) bias_v[j] = ldg4(bp + (nt0 + j) * 16 + nq);
     }
-    gemm_stage_tile<MTILES, NWAVES, PRO, false, XP, (NTW <= 3 && XP <= 3) ? 1 : 2, true>(a, (float*)xs, ROWB, m0, 0, D, zeros, tid, lane, wave,
-                                                                                         bx == 0 ? a.a_merged : nullptr);
+    gemm_stage_tile<MTILES, NWAVES, PRO, false, XP, (NTW <= 3 && XP <= 3) ? 1 : 2, SCH>(a, (float*)xs, ROWB, m0, 0, D, zeros, tid, lane, wave,
+                                                                                        bx == 0 ? a.a_merged : nullptr, xexp);
     __syncthreads();
     f32x4 acc[MTILES][NTW];
 #pragma unroll
     for (int i = 0; i < MTILES; ++i)
 #pragma unroll
         for (int j = 0; j < NTW; ++j) acc[i][j] = zero4;
-    split_phase<NTW, K32, R>(ring, xs, ROWB, PART, lane, acc);
+    split_phase<NTW, K32, R, SCH>(ring, xs, ROWB, PART, lane, acc);
 #pragma unroll
     for (int i = 0; i < MTILES; ++i) {
         const int m = m0 + i * 16 + (lane & 15);
+        const int xe = PAIR ? xexp[i * 16 + (lane & 15)] : 0;
 #pragma unroll
-        for (int j = 0; j < NTW; ++j)
-            if (m < a.M) st4(a.out + (int64_t)m * a.ldo + (nt0 + j) * 16 + nq, apply_act(acc[i][j] + bias_v[j], a.act));
+        for (int j = 0; j < NTW; ++j) {
+            f32x4 v = acc[i][j];
+            if constexpr (PAIR) v = pair_unscale(v, xe + pair_tile_exp(image, SS::tile_stride(K32), nt0 + j));
+            if (m < a.M) st4(a.out + (int64_t)m * a.ldo + (nt0 + j) * 16 + nq, apply_act(v + bias_v[j], a.act));
+        }
     }
 }

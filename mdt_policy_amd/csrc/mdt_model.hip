@@ -208,8 +208,8 @@ static void build_params(mdt_model* m, Bump& b, bool fill_slots) {
         lin_part(qkv, pre + ".key", D, D, true);
         lin_part(qkv, pre + ".query", D, 0, true);
         lin_part(qkv, pre + ".value", D, 2 * D, true);
-        if (D % 128 == 0 && D <= 512) {   // the split form of the LayerNorm-prologue product (mdt_mlp_split.h): 6 bytes per weight
-            qkv.ws = b.take((size_t)3 * D * D * 6 / 4);
+        if (D % 128 == 0 && D <= 512) {   // the pair form of the LayerNorm-prologue product (mdt_mlp_split.h): 4 bytes per weight
+            qkv.ws = b.take((size_t)mdt_pair_image_bytes(3 * D, D) / 4);
             add_extra(pre + ".key.weight", (int64_t)D * D, SLOT_PACK_SPLIT, (float*)qkv.ws, D, D, D);
             add_extra(pre + ".query.weight", (int64_t)D * D, SLOT_PACK_SPLIT, (float*)qkv.ws, D, D, 0);
             add_extra(pre + ".value.weight", (int64_t)D * D, SLOT_PACK_SPLIT, (float*)qkv.ws, D, D, 2 * D);
@@ -229,9 +229,9 @@ static void build_params(mdt_model* m, Bump& b, bool fill_slots) {
         lin_part(e.fc, pre + ".mlp.c_fc", 4 * D, 0, xb);
         lin_begin(e.proj2, D, 4 * D, xb);
         lin_part(e.proj2, pre + ".mlp.c_proj", D, 0, xb);
-        if (D % 128 == 0 && D <= 512) {   // the fused MLP launch's split form (mdt_mlp_split.h): 6 bytes per weight
-            e.fc.ws = b.take((size_t)4 * D * D * 6 / 4);
-            e.proj2.ws = b.take((size_t)4 * D * D * 6 / 4);
+        if (D % 128 == 0 && D <= 512) {   // the fused MLP launch's pair form (mdt_mlp_split.h): 4 bytes per weight
+            e.fc.ws = b.take((size_t)mdt_pair_image_bytes(4 * D, D) / 4);
+            e.proj2.ws = b.take((size_t)mdt_pair_image_bytes(D, 4 * D) / 4);
             add_extra(pre + ".mlp.c_fc.weight", (int64_t)4 * D * D, SLOT_PACK_SPLIT, (float*)e.fc.ws, 4 * D, D);
             add_extra(pre + ".mlp.c_proj.weight", (int64_t)4 * D * D, SLOT_PACK_SPLIT, (float*)e.proj2.ws, D, 4 * D);
         }
@@ -465,7 +465,7 @@ extern "C" mdt_status mdt_load_param(mdt_model* m, const char* name, const float
             mark_split_stale(m);   // training: re-made on demand (mdt_model_types.h)
         } else {
             MDT_TRY(mdt_stage_source(src, numel, m->staging, s, &dev_src));
-            HIP_TRY(mdt_launch_pack_weight_split(dev_src, t->rows, t->K, t->dst, s, t->n_off));
+            HIP_TRY(mdt_launch_pack_weight_pair(dev_src, t->rows, t->K, t->dst, s, t->n_off));
         }
     }
     slot->loaded = true;
@@ -486,7 +486,8 @@ extern "C" mdt_status mdt_load_params(mdt_model* m, int32_t n, const char* const
         mdt_load_entry e;
         memset(&e, 0, sizeof e);
         e.src = src; e.dst = dst; e.kind = kind; e.rows = rows; e.K = K; e.p0 = p0; e.p1 = p1;
-        const int64_t work = kind == MDT_LOAD_PACK_T ? (int64_t)((rows + 3) / 4) * K
+        const int64_t work = kind == MDT_LOAD_PACK_PAIR ? (int64_t)(rows / 16) * 1024   // one block per column tile
+                             : kind == MDT_LOAD_PACK_T ? (int64_t)((rows + 3) / 4) * K
                              : (kind == MDT_LOAD_PACK || kind == MDT_LOAD_PACK_SPLIT) ? (int64_t)rows * (K / 4) : (int64_t)rows * K;
         for (int64_t c = 0; c * 1024 < work; ++c) blocks.push_back(make_int2((int)tab.size(), (int)c));
         tab.push_back(e);
@@ -520,7 +521,7 @@ extern "C" mdt_status mdt_load_params(mdt_model* m, int32_t n, const char* const
             else if (t->kind == SLOT_PACK_T) add(srcs[i], t->dst, MDT_LOAD_PACK_T, t->rows, t->K, 0, t->rows / 16);
             else if (t->kind == SLOT_PACK_SPLIT) {
                 if (m->train) mark_split_stale(m);   // training: re-made on demand (mdt_model_types.h)
-                else add(srcs[i], t->dst, MDT_LOAD_PACK_SPLIT, t->rows, t->K, t->n_off, 0);
+                else add(srcs[i], t->dst, MDT_LOAD_PACK_PAIR, t->rows, t->K, t->n_off, 0);
             }
             else {
                 add(srcs[i], t->dst, MDT_LOAD_PACK, t->rows, t->K, t->n_off, 0);
@@ -728,7 +729,7 @@ static mdt_status run_self_attn(mdt_model* m, const EncBlock& e, const View& V, 
 
 // row count from which the MLP sublayer runs as ONE launch (k_mlp) that leaves partial slabs instead of the residual
 // stream: below it the wide tiles do not fill the chip
-// (`split`: the launch would run in its bf16 split form, which pays from fewer rows -- mdt_split_min_rows(), B = 128: 1280 rows
+// (`split`: the launch would run in its split form (fp16 pairs, mdt_mlp_split.h), which pays from fewer rows -- mdt_split_min_rows(), B = 128: 1280 rows
 // per call 3.42 -> 2.96 ms with the qkv products split too (mdt_internal.h); a setting made with the hook is taken as it is)
 static int g_mlp_fuse_min_rows(bool split = false) {
     const int v = g_mdt_sw.mlp_fuse_min;
@@ -790,10 +791,10 @@ extern "C" mdt_status mdt_op_clock_stamp(uint64_t* out16, void* stream) {
     return MDT_OK;
 }
 
-// the split images of every block, re-made from the fp32 fragment images (after parameter loads that skipped them: split_stale)
+// the split (fp16 pair) images of every block, re-made from the fp32 fragment images (after parameter loads that skipped them: split_stale)
 static mdt_status refresh_split(mdt_model* m, hipStream_t s) {
     auto one = [&](const Lin& l) -> mdt_status {
-        if (l.ws) LAUNCH(mdt_launch_split_from_packed(l.wp, l.N, l.K, l.ws, s));
+        if (l.ws) LAUNCH(mdt_launch_pair_from_packed(l.wp, l.N, l.K, l.ws, s));
         return MDT_OK;
     };
     for (const EncBlock& e : m->enc) { MDT_TRY(one(e.qkv)); MDT_TRY(one(e.fc)); MDT_TRY(one(e.proj2)); }
@@ -823,7 +824,7 @@ static mdt_status run_mlp(mdt_model* m, const EncBlock& e, const View& V, int64_
     if (mr.mod && mr.gate >= 0) { p.mod = mr.mod; p.mod_stride = mr.stride; p.gate_off = mr.gate; }
     if (out) *out = Stream();
     // (never with `pre_x`: the caller skipped its own cross-attention launch because the c_fc launch was to run it)
-    // the three-way bf16 split form of the launch (mdt_mlp_split.h) wherever its images exist and it is not switched off; it pays
+    // the fp16 pair split form of the launch (mdt_mlp_split.h) wherever its images exist and it is not switched off; it pays
     // from fewer rows than the fp32 launch (g_mlp_fuse_min_rows).  The row condition is split_ready's: below it the images may
     // be stale (a training state's optimizer steps refresh them only for the launches that read them)
     const bool split = e.fc.ws && e.proj2.ws && mdt_mlp_split_enabled() && M >= mdt_split_min_rows() && mdt_mlp_split_supported(g, p);
@@ -835,13 +836,13 @@ static mdt_status run_mlp(mdt_model* m, const EncBlock& e, const View& V, int64_
             TraceEv ev;
             HIP_TRY(hipEventCreate(&ev.e0)); HIP_TRY(hipEventCreate(&ev.e1)); HIP_TRY(hipEventCreate(&ev.e2));
             HIP_TRY(hipEventRecord(ev.e0, s));
-            if (split) LAUNCH(mdt_launch_mlp_split(g, p, e.fc.ws, e.proj2.ws, V.hid, stride, s));
+            if (split) LAUNCH(mdt_launch_mlp_pair(g, p, e.fc.ws, e.proj2.ws, V.hid, stride, s));
             else LAUNCH(mdt_launch_mlp(g, p, V.hid, stride, s));
             HIP_TRY(hipEventRecord(ev.e1, s));
             HIP_TRY(hipEventRecord(ev.e2, s));
             g_trace_mlp_events.push_back(ev);
         } else if (split) {
-            LAUNCH(mdt_launch_mlp_split(g, p, e.fc.ws, e.proj2.ws, V.hid, stride, s));
+            LAUNCH(mdt_launch_mlp_pair(g, p, e.fc.ws, e.proj2.ws, V.hid, stride, s));
         } else {
             LAUNCH(mdt_launch_mlp(g, p, V.hid, stride, s));
         }
@@ -1922,6 +1923,59 @@ extern "C" mdt_status mdt_op_mlp_split(const mdt_gemm_args* fc, const mdt_gemm_a
         return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp_split: pointers must be 16-byte aligned");
     LAUNCH(mdt_launch_mlp_split(*fc, *proj, fc_split, proj_split, parts, part_stride, (hipStream_t)stream));
     if (n_parts) *n_parts = mdt_mlp_slices(fc->K);
+    return MDT_OK;
+}
+
+extern "C" int64_t mdt_op_pair_image_bytes(int64_t n_rows, int64_t K) {
+    return (n_rows < 16 || n_rows % 16 || K < 32 || K % 32) ? -1 : mdt_pair_image_bytes(n_rows, K);
+}
+
+extern "C" mdt_status mdt_op_pack_weight_pair(const float* w, int64_t n_rows, int64_t K, void* image, int64_t n_off, void* stream) {
+    if (!w || !image) return fail(MDT_ERR_INVALID_ARG, "mdt_op_pack_weight_pair: null pointer");
+    if (n_rows < 16 || n_rows % 16 || n_off < 0 || n_off % 16 || K < 32 || K % 32 || (n_rows + n_off) * K >= ((int64_t)1 << 29))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_pack_weight_pair: n_rows and n_off multiples of 16, K a multiple of 32");
+    if (misaligned(w) || misaligned(image)) return fail(MDT_ERR_INVALID_ARG, "mdt_op_pack_weight_pair: pointers must be 16-byte aligned");
+    LAUNCH(mdt_launch_pack_weight_pair(w, (int)n_rows, (int)K, image, (hipStream_t)stream, (int)n_off));
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_pair_from_packed(const float* packed, int64_t N, int64_t K, void* image, void* stream) {
+    if (!packed || !image) return fail(MDT_ERR_INVALID_ARG, "mdt_op_pair_from_packed: null pointer");
+    if (N < 16 || N % 16 || K < 32 || K % 32 || N * K >= ((int64_t)1 << 29))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_pair_from_packed: N a multiple of 16, K a multiple of 32");
+    if (misaligned(packed) || misaligned(image)) return fail(MDT_ERR_INVALID_ARG, "mdt_op_pair_from_packed: pointers must be 16-byte aligned");
+    LAUNCH(mdt_launch_pair_from_packed(packed, (int)N, (int)K, image, (hipStream_t)stream));
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_mlp_pair(const mdt_gemm_args* fc, const mdt_gemm_args* proj, const void* fc_pair, const void* proj_pair,
+                                      float* parts, int64_t part_stride, int32_t* n_parts, void* stream) {
+    if (!fc || !proj || !fc->A || !fc_pair || !proj_pair || !parts || !fc->ln_w)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp_pair: null pointer");
+    if (!mdt_mlp_split_supported(*fc, *proj))
+        return fail(MDT_ERR_UNSUPPORTED, "mdt_op_mlp_pair: needs D = fc.K a multiple of 128 (<= 512), fc.N = proj.K = 4 D, proj.N = D, "
+                                         "a LayerNorm prologue and plain output rows");
+    if (fc->lda % 4 || proj->ldo % 4 || proj->ldo < proj->N || part_stride < (int64_t)fc->M * proj->ldo)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp_pair: lda / ldo multiples of 4, part_stride >= M * ldo required");
+    if (misaligned(fc->A) || misaligned(fc_pair) || misaligned(proj_pair) || misaligned(parts) || misaligned(fc->bias) ||
+        misaligned(proj->bias) || misaligned(fc->mod) || misaligned(proj->mod) || (part_stride & 3))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp_pair: pointers must be 16-byte aligned");
+    LAUNCH(mdt_launch_mlp_pair(*fc, *proj, fc_pair, proj_pair, parts, part_stride, (hipStream_t)stream));
+    if (n_parts) *n_parts = mdt_mlp_slices(fc->K);
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_gemm_ln_pair(const mdt_gemm_args* a, void* stream) {
+    if (!a || !a->A || !a->Wp_pair || !a->out || !a->ln_w) return fail(MDT_ERR_INVALID_ARG, "mdt_op_gemm_ln_pair: null pointer");
+    if (!mdt_gemm_ln_pair_supported(*a))
+        return fail(MDT_ERR_UNSUPPORTED, "mdt_op_gemm_ln_pair: needs a LayerNorm prologue over K = 384 or 512, N a multiple of 384, "
+                                         "plain output rows, at most 4 slabs, lda / ldo multiples of 4");
+    if (a->ldo < a->N || a->rows_per_sample < 1 || (a->a_parts >= 2 && (a->a_part_stride & 3)))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_gemm_ln_pair: ldo >= N, a_part_stride a multiple of 4 required");
+    if (misaligned(a->A) || misaligned(a->Wp_pair) || misaligned(a->out) || misaligned(a->bias) || misaligned(a->ln_w) ||
+        misaligned(a->ln_b) || misaligned(a->mod) || misaligned(a->a_merged) || (a->mod && a->shift_off >= 0 && ((a->mod_stride | a->shift_off | a->scale_off) & 3)))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_gemm_ln_pair: pointers must be 16-byte aligned");
+    LAUNCH(mdt_launch_gemm_ln_pair(*a, (hipStream_t)stream));
     return MDT_OK;
 }
 

@@ -185,10 +185,13 @@ __device__ unsigned long long* g_dbg_ts = nullptr;
 // SPLIT (round 6, LayerNorm prologues only): the rows are stored as their three-way bf16 split in MFMA slot order (mdt_device.h
 // split3_bf16 / split_slot: part q at (char*)lds + q * MT * stride, `stride` = the split tile's row stride in BYTES) instead of fp32
 // rows of `stride` floats -- the staged tile of mdt_mlp_split.h without an fp32 copy in LDS and a pass over it.
-template <int MTILES, int NWAVES, int PRO, bool COH, int XP = 1, int XB = 2, bool SPLIT = false>
+// SPLIT == MDT_SPLIT_F16X2: the two-way fp16 pair split instead (mdt_device.h split2_f16), two parts; each row is scaled by its own
+// power of two -- the wave holds whole rows, so the row's largest |y| is one more wave reduction -- whose exponent goes to
+// row_exp[row of the tile] (LDS, MT ints) for the product's epilogue.
+template <int MTILES, int NWAVES, int PRO, bool COH, int XP = 1, int XB = 2, int SPLIT = MDT_SPLIT_NONE>
 __device__ __forceinline__ void gemm_stage_tile(const mdt_gemm_args& a, float* lds, int stride, int m0, int k0, int klen,
                                                 const float* __restrict__ zeros, int tid, int lane, int wave,
-                                                float* merge_out = nullptr) {
+                                                float* merge_out = nullptr, int* row_exp = nullptr) {
     static_assert(!SPLIT || PRO != PRO_PLAIN, "the split store belongs to the LayerNorm prologues");
     constexpr int MT = MTILES * 16;
     constexpr int NT = 64 * NWAVES;
@@ -304,10 +307,12 @@ __device__ __forceinline__ void gemm_stage_tile(const mdt_gemm_args& a, float* l
             }
         }
         wave_sum_n<RPW>(red);
+        unsigned ymax[RPW];   // (pair split) ordered bits of the row's largest |y| among this lane's columns
 #pragma unroll
         for (int r = 0; r < RPW; ++r) {
             const int m = m0 + r0 + r;
             const float rstd = 1.0f / sqrtf(red[r] * inv_k + 1e-5f);
+            ymax[r] = 0u;
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
                 f32x4 y = v[r][p] * rstd * w[p] + bb[p];
@@ -324,7 +329,10 @@ __device__ __forceinline__ void gemm_stage_tile(const mdt_gemm_args& a, float* l
                     y = shv + y * scv;
                 }
                 y = sel4(m < a.M, y, zero4);
-                if constexpr (SPLIT) {
+                if constexpr (SPLIT == MDT_SPLIT_F16X2) {
+                    v[r][p] = y;
+                    if (cv[p]) ymax[r] = max(ymax[r], pair_absbits4(y));
+                } else if constexpr (SPLIT == MDT_SPLIT_BF16X3) {
                     if (cv[p]) {
                         mdt_bf16x4 p1, p2, p3;
                         split3_bf16(y, p1, p2, p3);
@@ -336,6 +344,23 @@ __device__ __forceinline__ void gemm_stage_tile(const mdt_gemm_args& a, float* l
                 } else {
                     if (cv[p]) *(f32x4*)(lds + (r0 + r) * stride + cc[p]) = y;
                 }
+            }
+        }
+        if constexpr (SPLIT == MDT_SPLIT_F16X2) {
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) {
+                const unsigned mx = wave_max_u32(ymax[r]);
+                const float rs = pair_scale(mx);
+                if (lane == 0) row_exp[r0 + r] = pair_scale_exp(mx);
+#pragma unroll
+                for (int p = 0; p < 2; ++p)
+                    if (cv[p]) {
+                        mdt_f16x4 p1, p2;
+                        split2_f16(v[r][p], rs, p1, p2);
+                        char* q = (char*)lds + split_slot(r0 + r, cc[p], stride);
+                        *(mdt_f16x4*)q = p1;
+                        *(mdt_f16x4*)(q + MT * stride) = p2;
+                    }
             }
         }
     } else {

@@ -338,6 +338,161 @@ void run32(const char* name, const char* w1, float* out, int phases) {
     printf("%-78s %7.2f us per launch (back to back)\n", name, ms * 1e3 / n);
 }
 
+// variant D: two fp16 parts (22 significand bits), THREE products per k32 step (x2 w1, x1 w2, x1 w1) on v_mfma_f32_16x16x32_f16 and a
+// 4-byte-per-weight image: half the MFMAs AND two thirds of the bytes of variant A, same launch shape.  The fp16 range needs one
+// power-of-two scale per activation row: the GELU epilogue takes the row maximum over the 512-wide hidden slice with an LDS max on the
+// non-negative float bits, written BEFORE the barrier that separates the products anyway; the split follows that barrier.
+// MI355X: 20.8 us against A's 29.0-29.6 in the same run (profiles/f16_pair_probe.txt).
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f16x8 ldh(const char* p) { return __builtin_bit_cast(f16x8, *(const f32x4*)p); }
+template <int NT, int K32, int R, int MT = 2>
+__device__ __forceinline__ void phase_h(const char* __restrict__ wimg, int64_t tile_stride, const char* lds_a, int rowb, int part, int lane,
+                                        f32x4 (&acc)[MT][NT]) {
+    // fragment (column tile j, step kk, part p): 1 KiB at wimg + j * tile_stride + (kk * 2 + p) * 1024, lane's 16 bytes at lane * 16
+    f16x8 w[R][NT][2];
+#pragma unroll
+    for (int u = 0; u < R - 1; ++u)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) w[u][j][p] = ldh(wimg + j * tile_stride + (u * 2 + p) * 1024 + lane * 16);
+    const int aoff = (lane & 15) * rowb + (lane >> 4) * 16;
+    f16x8 x1[MT], x2[MT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+        const char* q = lds_a + aoff + i * 16 * rowb;
+        x1[i] = *(const f16x8*)q; x2[i] = *(const f16x8*)(q + part);
+    }
+#pragma unroll
+    for (int kk = 0; kk < K32; ++kk) {
+        const int u = kk % R, un = (kk + R - 1) % R;
+        const bool nx = kk + 1 < K32;
+        if (kk + R - 1 < K32) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int p = 0; p < 2; ++p) w[un][j][p] = ldh(wimg + j * tile_stride + ((kk + R - 1) * 2 + p) * 1024 + lane * 16);
+        }
+        const char* p0 = lds_a + aoff + (kk + 1) * 64;
+        PIN
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+#pragma unroll
+            for (int i = 0; i < MT; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[u][j][0], x2[i], acc[i][j], 0, 0, 0);
+        }
+        PIN
+        if (nx) {
+#pragma unroll
+            for (int i = 0; i < MT; ++i) x2[i] = *(const f16x8*)(p0 + i * 16 * rowb + part);
+        }
+        PIN
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+#pragma unroll
+            for (int i = 0; i < MT; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[u][j][1], x1[i], acc[i][j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+#pragma unroll
+            for (int i = 0; i < MT; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[u][j][0], x1[i], acc[i][j], 0, 0, 0);
+        }
+        PIN
+        if (nx) {
+#pragma unroll
+            for (int i = 0; i < MT; ++i) x1[i] = *(const f16x8*)(p0 + i * 16 * rowb);
+        }
+        PIN
+    }
+}
+template <int R1, int R2>
+__global__ __launch_bounds__(512) void k_probe_h(const char* __restrict__ w1, const char* __restrict__ w2, const float* __restrict__ wsc,
+                                                 float* __restrict__ out, int phases) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    constexpr int ROWB1 = 2 * 384 + 32, PART1 = 32 * ROWB1, ROWB2 = 2 * 512 + 32, PART2 = 32 * ROWB2;
+    unsigned* rowmax = (unsigned*)(lds + 2 * PART2);          // 32 entries behind the tile: float bits of the hidden rows' max |v|
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int b = blockIdx.x;
+    b = (b & 7) * 30 + (b >> 3);
+    const int s = b / 80, by = b - s * 80;
+    for (int i = tid; i < (2 * PART2) / 16; i += 512) ((f32x4*)lds)[i] = (f32x4){1.f + i * 1e-6f, 0.5f, 0.25f, 0.125f};
+    if (tid < 32) rowmax[tid] = 0u;
+    __syncthreads();
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc1[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc1[i][j] = zero4;
+    if (phases & 1) phase_h<4, 12, R1>(w1 + (int64_t)((s * 8 + wave) * 4) * 12 * 2048, 12 * 2048, lds, ROWB1, PART1, lane, acc1);
+    // ---- rescale (row scale x column-tile scale), bias, GELU in place; the rows' maxima into LDS before the barrier ----
+    if (phases & 4) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float m = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float cs = wsc[(s * 8 + wave) * 4 + j];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { const float v = gelu(acc1[i][j][e] * cs + 0.1f); acc1[i][j][e] = v; m = fmaxf(m, fabsf(v)); }
+            }
+            atomicMax(&rowmax[16 * i + (lane & 15)], __float_as_uint(m));
+        }
+    }
+    __syncthreads();                                 // everybody has read the x tile: the hidden slice may overwrite it
+    if (phases & 4) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            // power-of-two scale that puts the row's maximum into [2^14, 2^15); a zero row keeps scale 1
+            const unsigned ex = rowmax[16 * i + (lane & 15)] >> 23;
+            const float sc = ex ? __uint_as_float((unsigned)max(1, min(254, 268 - (int)ex)) << 23) : 1.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                f16x4 p1, p2;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float v = acc1[i][j][e] * sc;
+                    const _Float16 a = (_Float16)v;
+                    p1[e] = a; p2[e] = (_Float16)(v - (float)a);
+                }
+                const int c = (4 * wave + j) * 16 + 4 * (lane >> 4);
+                char* q = lds + (16 * i + (lane & 15)) * ROWB2 + (c >> 5) * 64 + ((c & 15) >> 2) * 16 + ((c & 31) >> 4) * 8;
+                *(f16x4*)q = p1; *(f16x4*)(q + PART2) = p2;
+            }
+        }
+    }
+    __syncthreads();
+    f32x4 acc2[2][3];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc2[i][j] = zero4;
+    if (phases & 2) phase_h<3, 16, R2>(w2 + ((int64_t)(3 * wave) * 48 + 16 * s) * 2048, 48 * 2048, lds, ROWB2, PART2, lane, acc2);
+    float* o = out + ((int64_t)s * 2560 + by * 32) * 384;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const unsigned ex = rowmax[16 * i + (lane & 15)] >> 23;
+        const float rs = ex ? __uint_as_float((unsigned)max(1, min(254, (int)ex - 14)) << 23) : 1.f;   // 1 / row scale, exact
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            *(f32x4*)(o + (16 * i + (lane & 15)) * 384 + (3 * wave + j) * 16 + 4 * (lane >> 4)) = acc2[i][j] * (rs * wsc[96 + 3 * wave + j]) + acc1[i][j];
+    }
+}
+template <int R1, int R2>
+void run_h(const char* name, const char* w1, const char* w2, const float* wsc, float* out, int phases) {
+    const size_t ldsb = 2 * 32 * (2 * 512 + 32) + 128;
+    hipFuncSetAttribute((const void*)k_probe_h<R1, R2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
+    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((k_probe_h<R1, R2>), dim3(240), dim3(512), ldsb, 0, w1, w2, wsc, out, phases);
+    hipDeviceSynchronize();
+    hipEventRecord(e0);
+    const int n = 50;
+    for (int i = 0; i < n; ++i) hipLaunchKernelGGL((k_probe_h<R1, R2>), dim3(240), dim3(512), ldsb, 0, w1, w2, wsc, out, phases);
+    hipEventRecord(e1); hipEventSynchronize(e1);
+    float ms; hipEventElapsedTime(&ms, e0, e1);
+    printf("%-78s %7.2f us per launch (back to back)\n", name, ms * 1e3 / n);
+}
+
 template <int R1, int R2, int XCD>
 void run(const char* name, const char* w1, const char* w2, float* out, int phases) {
     const size_t ldsb = 3 * 32 * (2 * 512 + 32);
@@ -372,5 +527,14 @@ int main() {
     run32<2>("C: first product only on v_mfma_f32_32x32x16_bf16", w1, out, 1);
     run32<3>("C: ... ring 3", w1, out, 1);
     run32<2>("C: nothing", w1, out, 0);
+    float* wsc; hipMalloc(&wsc, 128 * 4); hipMemset(wsc, 0x3c, 128 * 4);
+    run<2, 2, 1>("A again, beside D: both phases + activation, ring 2 / 2", w1, w2, out, 7);
+    run_h<2, 2>("D: two fp16 parts, three products, 4-byte image: both phases + activation", w1, w2, wsc, out, 7);
+    run_h<3, 3>("D: ... ring 3 / 3", w1, w2, wsc, out, 7);
+    run_h<2, 2>("D: phase 1 only", w1, w2, wsc, out, 1);
+    run_h<2, 2>("D: phase 2 only", w1, w2, wsc, out, 2);
+    run_h<2, 2>("D: activation + row max + re-split only", w1, w2, wsc, out, 4);
+    run_h<2, 2>("D: nothing", w1, w2, wsc, out, 0);
+    run<2, 2, 1>("A once more", w1, w2, out, 7);
     return 0;
 }
