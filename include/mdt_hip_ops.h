@@ -55,8 +55,8 @@ typedef struct {
     int32_t ln;            /* 0 = plain A, 1 = layer_norm(A) * ln_w (+ ln_b)                          */
     const float *ln_w, *ln_b;
     const float *mod;      /* NULL, or modulation table: row (m / rows_per_sample) * mod_stride       */
-    int64_t mod_stride;    /* 0 broadcasts one row to the whole batch                                 */
-    int32_t shift_off, scale_off;
+    int64_t mod_stride;    /* 0 broadcasts one row to the whole batch; like shift_off, scale_off and  */
+    int32_t shift_off, scale_off;   /* gate_off a multiple of 4 floats (the rows are read 16 bytes at a time) */
     int32_t rows_per_sample;
     /* epilogue                                                                                        */
     int32_t act;           /* MDT_ACT_*  applied after bias                                           */
@@ -226,7 +226,7 @@ typedef struct {
     float *U, *Wf;                 /* out: B images of 4 H * D floats each, opaque: MFMA weight-fragment order, every head */
                                    /* padded to 4 context tokens (row p = 4 h + j; mdt_kernels.hip "Collapsed ...")        */
     float *c;                      /* out: (B, 4 H)                                                                        */
-    int32_t B, H, hd, D, Te;       /* H in {4, 8}, D = H * hd <= 512 a multiple of 128, 1 <= Te <= 4                       */
+    int32_t B, H, hd, D, Te;       /* H in {4, 8}, hd in {16, 32, 48, 64}, D = H * hd a multiple of 128, 1 <= Te <= 4      */
 } mdt_xfold_args;
 mdt_status mdt_op_xattn_fold(const mdt_xfold_args *args, void *stream);
 
