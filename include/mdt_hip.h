@@ -62,7 +62,7 @@ typedef struct {
     int32_t goal_dim;             /* multiple of 16                                                 */
     int32_t n_obs_token;          /* MDT-V: state tokens per sample (3); MDT: ignored (static+gripper) */
     int32_t goal_seq_len;         /* 1                                                              */
-    int32_t action_seq_len;       /* Ta <= 16                                                       */
+    int32_t action_seq_len;       /* Ta <= 16; 17..64 at head dim 32 / 48 / 64                      */
     int32_t use_mlp_goal;         /* goal_emb / lang_emb are Linear-GELU-Linear                     */
     int32_t use_modality_encoder; /* separate lang_emb                                              */
     int32_t use_abs_pos_emb;      /* MDT only: pos_emb added to the encoder tokens                  */

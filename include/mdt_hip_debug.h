@@ -12,6 +12,7 @@
 
 #include <stdint.h>
 #include "mdt_hip.h"
+#include "mdt_hip_ops.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -64,6 +65,11 @@ void mdt_op_set_gemm_geometry(int32_t geometry);
  * (mdt_op_attn_proj's contract on 32-row tiles, k_attn_proj_wide) from `rows` rows on: 0 = never (attention launch + projection
  * GEMM; also switches off the one-workgroup-per-sample form, mdt_op_attn_xattn), -1 = default 1401. */
 void mdt_op_set_attn_wide_min(int32_t rows);
+
+/* mdt_op_attention (mdt_hip_ops.h) as a sampler call with candidates launches it: the args->B query samples are chunks of which
+ * ctx_div consecutive ones share a context, so sample b reads the k / v rows of context b / ctx_div (k / v hold B / ctx_div * Tk
+ * rows; B a multiple of ctx_div).  ctx_div = 1 is mdt_op_attention. */
+mdt_status mdt_op_attention_shared(const mdt_attn_args *args, int32_t ctx_div, void *stream);
 
 /* Measurement hook: bracket every fused-MLP launch of the model-level calls that follow (mdt_sample_ddim, mdt_forward, ...)
  * with a pair of HIP events on its stream; mdt_op_trace_mlp_read waits for them, writes up to `cap` durations in

@@ -167,7 +167,7 @@ typedef struct {
     const float *k; const float *v;    /* (B*Tk, ...) key / value rows                                */
     int64_t ldkv;
     float *out; int64_t ldo;           /* (B*Tq, H*hd)                                                */
-    int32_t B, H, hd, Tq, Tk;          /* hd in {16,32,48,64}; Tq, Tk <= 16                           */
+    int32_t B, H, hd, Tq, Tk;          /* hd in {16,32,48,64}; Tq, Tk <= 16, or <= 64 at hd >= 32     */
     int32_t causal;                    /* 1: key j visible to query i iff j <= i (top-left aligned)   */
     int32_t rope;                      /* 1: rotate q by its position 0..Tq-1 and k by 0..Tk-1        */
 } mdt_attn_args;

@@ -320,6 +320,7 @@ SYMBOLS = [
     ("mdt_op_side_jobs_paired", _I64, []),
     ("mdt_op_set_mlp_skew", None, [_I32]),
     ("mdt_op_set_attn_wide_min", None, [_I32]),
+    ("mdt_op_attention_shared", _I32, [C.POINTER(AttnArgs), _I32, _VP]),
     ("mdt_op_trace_mlp", None, [_I32]),
     ("mdt_op_trace_mlp_read", _I32, [_VP, _I32]),
     ("mdt_op_trace_mlp_read_empty", _I32, [_VP, _I32]),

@@ -125,6 +125,14 @@ hipError_t mdt_launch_split_from_packed(const float* wp, int N, int K, void* ima
 // samples of which ctx_div consecutive ones share a context -- the candidates of a sampler call -- so sample b reads the k / v
 // rows (the folded operands U, Wf, c) of context b / ctx_div.  The public argument structs keep their layout.
 hipError_t mdt_launch_attention(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s, int ctx_div = 1);
+// chunks of 17 .. 64 rows (mdt_attn_chunk.hip): where mdt_launch_attention, mdt_launch_attn_fwd_train and mdt_launch_attn_bwd go
+// once max(Tq, Tk) > 16 -- head dim 32 / 48 / 64, Tq, Tk <= 64; rotary tables of max(Tq, Tk) positions x 16 frequencies
+constexpr int MDT_ROPE_POSITIONS = 64;   // rows of a handle's rotary tables
+bool mdt_attn_chunk_supported(int hd, int Tq, int Tk);
+size_t mdt_attn_chunk_lds(int hd, int Tq, int Tk, bool bwd);   // bytes of dynamic LDS of one workgroup
+hipError_t mdt_launch_attn_chunk(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s, int ctx_div);
+hipError_t mdt_launch_attn_chunk_fwd_train(const mdt_attn_train_args& a, hipStream_t s);
+hipError_t mdt_launch_attn_chunk_bwd(const mdt_attn_bwd_args& a, hipStream_t s);
 // one sample's self-attention fused into its output projection p (rollout batch 1); see mdt_kernels.hip
 bool mdt_attn_proj_supported(const mdt_gemm_args& p, int H, int hd, int T, int rope);
 hipError_t mdt_launch_attn_proj(const mdt_gemm_args& p, const float* qkv, int64_t ldq, int H, int hd, int T, int causal,

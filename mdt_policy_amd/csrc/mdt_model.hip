@@ -295,8 +295,8 @@ static void build_params(mdt_model* m, Bump& b, bool fill_slots) {
     }
     // constant tables
     m->freqs = b.take(D / 2);
-    m->rope_cos = b.take(16 * 16);
-    m->rope_sin = b.take(16 * 16);
+    m->rope_cos = b.take(MDT_ROPE_POSITIONS * 16);   // (positions, frequencies)
+    m->rope_sin = b.take(MDT_ROPE_POSITIONS * 16);
 }
 
 static bool is_ignored_param(const mdt_model* m, const std::string& name) {
@@ -330,7 +330,9 @@ extern "C" mdt_status mdt_create(const mdt_config* cfg, mdt_model** out) {
         return fail(MDT_ERR_UNSUPPORTED, "goal_dim == 2*obs_dim triggers the reference's goal truncation "
                                          "(mdtv_transformer.py:252-253); not implemented");
     if (c.action_dim < 1 || c.action_dim > 16) return fail(MDT_ERR_UNSUPPORTED, "action_dim must be 1..16");
-    if (c.action_seq_len < 1 || c.action_seq_len > 16) return fail(MDT_ERR_UNSUPPORTED, "action_seq_len must be 1..16");
+    if (c.action_seq_len < 1 || c.action_seq_len > MDT_ROPE_POSITIONS || (c.action_seq_len > 16 && hd < 32))
+        return fail(MDT_ERR_UNSUPPORTED, "action_seq_len %d at head dim %d: action_seq_len 17..64 needs head dim 32 / 48 / 64; head dim 16 "
+                                         "takes 1..16 (action_seq_len must be >= 1 and <= 64)", c.action_seq_len, hd);
     const int n_tok = c.arch == MDT_ARCH_MDTV ? c.n_obs_token : 2;
     // use_noise_encoder only selects the block type of the adaLN-style decoder (TransformerFiLMDecoder); without
     // use_ada_conditioning the reference builds a plain TransformerDecoder and the flag is never read
@@ -376,19 +378,20 @@ extern "C" mdt_status mdt_create(const mdt_config* cfg, mdt_model** out) {
 
     // constant tables (host fp32 math mirroring the reference's torch fp32 expressions)
     const int half = m->D / 2;
-    std::vector<float> fr(half), rc(256), rs(256);
+    constexpr int RP = MDT_ROPE_POSITIONS;
+    std::vector<float> fr(half), rc(RP * 16), rs(RP * 16);
     const float step = (float)(-(std::log(10000.0) / (double)(half - 1)));  // mdtv_transformer.py:21-22
     for (int j = 0; j < half; ++j) fr[j] = expf((float)j * step);
     for (int i = 0; i < 16; ++i) {  // position_embeddings.py:104: theta ** -(arange(0,32,2)/32)
         const float f = 1.0f / powf(10000.0f, (float)(2 * i) / 32.0f);
-        for (int p = 0; p < 16; ++p) {
+        for (int p = 0; p < RP; ++p) {
             rc[p * 16 + i] = cosf((float)p * f);
             rs[p * 16 + i] = sinf((float)p * f);
         }
     }
     (void)hipMemcpy(m->freqs, fr.data(), half * sizeof(float), hipMemcpyHostToDevice);
-    (void)hipMemcpy(m->rope_cos, rc.data(), 256 * sizeof(float), hipMemcpyHostToDevice);
-    e = hipMemcpy(m->rope_sin, rs.data(), 256 * sizeof(float), hipMemcpyHostToDevice);
+    (void)hipMemcpy(m->rope_cos, rc.data(), rc.size() * sizeof(float), hipMemcpyHostToDevice);
+    e = hipMemcpy(m->rope_sin, rs.data(), rs.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(m->arena); delete m; return fail(MDT_ERR_HIP, "table upload failed: %s", hipGetErrorString(e)); }
 
     size_t mx = 0;
@@ -1979,30 +1982,39 @@ extern "C" mdt_status mdt_op_gemm_ln_pair(const mdt_gemm_args* a, void* stream) 
     return MDT_OK;
 }
 
-extern "C" mdt_status mdt_op_attention(const mdt_attn_args* a, void* stream) {
+static mdt_status op_attention(const mdt_attn_args* a, int ctx_div, void* stream) {
     if (!a || !a->q || !a->k || !a->v || !a->out) return fail(MDT_ERR_INVALID_ARG, "mdt_op_attention: null pointer");
-    if (a->Tq < 1 || a->Tq > 16 || a->Tk < 1 || a->Tk > 16) return fail(MDT_ERR_UNSUPPORTED, "Tq, Tk must be 1..16");
+    if (a->Tq < 1 || a->Tq > 64 || a->Tk < 1 || a->Tk > 64) return fail(MDT_ERR_UNSUPPORTED, "Tq, Tk must be 1..64");
     if (a->hd != 16 && a->hd != 32 && a->hd != 48 && a->hd != 64) return fail(MDT_ERR_UNSUPPORTED, "hd must be 16/32/48/64");
+    if ((a->Tq > 16 || a->Tk > 16) && a->hd < 32)
+        return fail(MDT_ERR_UNSUPPORTED, "Tq / Tk 17..64 need head dim 32 / 48 / 64; head dim 16 takes 1..16");
     if (a->rope) {
         if (a->hd < 32) return fail(MDT_ERR_INVALID_ARG, "rope needs hd >= 32");
         // stand-alone op calls build the rotary tables on the fly
         static float *cs = nullptr, *sn = nullptr;
         if (!cs) {
-            std::vector<float> rc(256), rs(256);
+            constexpr int RP = MDT_ROPE_POSITIONS;
+            std::vector<float> rc(RP * 16), rs(RP * 16);
             for (int i = 0; i < 16; ++i) {
                 const float f = 1.0f / powf(10000.0f, (float)(2 * i) / 32.0f);
-                for (int p = 0; p < 16; ++p) { rc[p * 16 + i] = cosf((float)p * f); rs[p * 16 + i] = sinf((float)p * f); }
+                for (int p = 0; p < RP; ++p) { rc[p * 16 + i] = cosf((float)p * f); rs[p * 16 + i] = sinf((float)p * f); }
             }
-            HIP_TRY(hipMalloc((void**)&cs, 256 * sizeof(float)));
-            HIP_TRY(hipMalloc((void**)&sn, 256 * sizeof(float)));
-            HIP_TRY(hipMemcpy(cs, rc.data(), 256 * sizeof(float), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(sn, rs.data(), 256 * sizeof(float), hipMemcpyHostToDevice));
+            HIP_TRY(hipMalloc((void**)&cs, rc.size() * sizeof(float)));
+            HIP_TRY(hipMalloc((void**)&sn, rs.size() * sizeof(float)));
+            HIP_TRY(hipMemcpy(cs, rc.data(), rc.size() * sizeof(float), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(sn, rs.data(), rs.size() * sizeof(float), hipMemcpyHostToDevice));
         }
-        LAUNCH(mdt_launch_attention(*a, cs, sn, (hipStream_t)stream));
+        LAUNCH(mdt_launch_attention(*a, cs, sn, (hipStream_t)stream, ctx_div));
         return MDT_OK;
     }
-    LAUNCH(mdt_launch_attention(*a, nullptr, nullptr, (hipStream_t)stream));
+    LAUNCH(mdt_launch_attention(*a, nullptr, nullptr, (hipStream_t)stream, ctx_div));
     return MDT_OK;
+}
+extern "C" mdt_status mdt_op_attention(const mdt_attn_args* a, void* stream) { return op_attention(a, 1, stream); }
+// test hook (mdt_hip_debug.h): the launch a sampler call with candidates makes -- sample b reads the k / v rows of context b / ctx_div
+extern "C" mdt_status mdt_op_attention_shared(const mdt_attn_args* a, int32_t ctx_div, void* stream) {
+    if (ctx_div < 1 || (a && a->B % ctx_div)) return fail(MDT_ERR_INVALID_ARG, "mdt_op_attention_shared: B must be a multiple of ctx_div >= 1");
+    return op_attention(a, ctx_div, stream);
 }
 
 extern "C" mdt_status mdt_op_xattn_fold(const mdt_xfold_args* a, void* stream) {
