@@ -57,7 +57,7 @@ typedef struct {
     int32_t n_heads;              /* head dim d/n_heads in {16,32,48,64}                            */
     int32_t n_enc_layers;
     int32_t n_dec_layers;
-    int32_t action_dim;           /* <= 16                                                          */
+    int32_t action_dim;           /* 1..64 (17..64: the tiled action head and narrow gradients)     */
     int32_t obs_dim;              /* multiple of 16                                                 */
     int32_t goal_dim;             /* multiple of 16                                                 */
     int32_t n_obs_token;          /* MDT-V: state tokens per sample (3); MDT: ignored (static+gripper) */

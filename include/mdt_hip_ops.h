@@ -196,7 +196,7 @@ typedef struct {
     const float *y;            /* (M, D) decoder residual stream                                      */
     const float *ln_w;         /* decoder.ln.weight (D), ln_b optional                                */
     const float *ln_b;
-    const float *Wp, *bp;      /* action_pred.weight (A, D) row-major UNPACKED, bias (A)              */
+    const float *Wp, *bp;      /* action_pred.weight (A, D) row-major UNPACKED, bias (A); A <= 64     */
     const float *x;            /* (M, A) current noisy actions                                        */
     const float *sigma;        /* sigma of sample b at sigma[b * sigma_stride]                        */
     int64_t sigma_stride;
@@ -210,10 +210,13 @@ typedef struct {
     const float *Wa, *ba;      /* action_emb.weight TRANSPOSED to (A, D) row-major, bias (D)          */
     int32_t no_ln;             /* 1: y is used as it is (the MLP head's hidden layer), ln_w / ln_b only have to be
                                 * readable for D floats                                                */
-    int32_t y_parts;           /* >= 2: the rows are the sum of y_parts arrays y, y + y_part_stride, ... (the slabs  */
+    int32_t y_parts;           /* >= 2 (A <= 8 only): the rows are the sum of y_parts arrays y, y + y_part_stride, ... (the slabs */
     int64_t y_part_stride;     /* mdt_op_mlp left), added in that order; 0 / 1 = plain y                             */
 } mdt_head_args;
 
+/* A <= 16: one wave per row (A <= 8 and A > 8 instantiations).  17 <= A <= 64: one workgroup per 16 rows, both products as
+ * 16 x 16 tiles of v_mfma_f32_16x16x4_f32 (the same modes and operands; dynamic LDS 4 (16 (ceil16(D) + 4) + 16 (ceil16(A) + 4))
+ * bytes).  D % 4 == 0, D <= 512. */
 mdt_status mdt_op_head(const mdt_head_args *args, void *stream);
 
 /* Collapsed cross-attention (see mdt_kernels.hip): fold the sigma-independent context K|V into the query and

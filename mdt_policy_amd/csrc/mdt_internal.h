@@ -217,6 +217,12 @@ struct mdt_head_pin {
 // pn: the call's pinned actions (the default: none)
 hipError_t mdt_launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, hipStream_t s, mdt_head_pin pn = {});
 inline hipError_t mdt_launch_head(const mdt_head_args& a, hipStream_t s) { return mdt_launch_head(a, nullptr, mdt_guide(), s); }
+// action vectors of 17 .. 64 elements (mdt_head_wide.hip): where mdt_launch_head goes once a.A > 16 -- the same launch in every
+// mode, on 16-row MFMA tiles; D % 4 == 0, D <= 512, no slab input (y_parts <= 1).  mdt_head_wide_lds: bytes of dynamic LDS of one
+// workgroup, checked against the 160 KiB of a workgroup before the launch (hipErrorInvalidValue, nothing enqueued)
+constexpr int MDT_ACTION_DIM_MAX = 64;
+size_t mdt_head_wide_lds(int D, int A, bool guided);
+hipError_t mdt_launch_head_wide(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, hipStream_t s, mdt_head_pin pn = {});
 // the guided sampler's 2B encoder inputs (tokens and tokens2 twice, the goal then zeros) in one launch
 hipError_t mdt_launch_guide_stage(const float* tok, const float* tok2, const float* goal, float* tok_o, float* tok2_o, float* goal_o,
                                   int B, int w1, int w2, int G, hipStream_t s);

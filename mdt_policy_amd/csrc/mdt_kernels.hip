@@ -1651,7 +1651,7 @@ hipError_t mdt_launch_dpm_error(const float* lo, const float* hi, const float* p
 
 // ------------------------------------------------------------------------------------------------
 // action head: decoder LN -> action_pred -> EDM combine -> (DDIM update) -> (next step's embedding)
-// one wave per action-token row; A <= 16
+// one wave per action-token row; A <= 16 (17 .. 64: mdt_head_wide.hip, behind the same launcher)
 // ------------------------------------------------------------------------------------------------
 // body in mdt_tiles.h (head_rows): each wave handles ONE row; pn: the call's pinned actions (null pointers: none)
 template <int AMAX, int XP>
@@ -1698,6 +1698,7 @@ static void launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_gui
 
 hipError_t mdt_launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, hipStream_t s, mdt_head_pin pn) {
     if ((pn.known == nullptr) != (pn.keep == nullptr)) return hipErrorInvalidValue;
+    if (a.A > 16) return mdt_launch_head_wide(a, pl, gd, s, pn);  // 17 .. 64 elements: the tiled head (mdt_head_wide.hip)
     hipError_t e = ensure_zeros();
     if (e != hipSuccess) return e;
     const int grid = (a.M + 3) / 4;  // 4 waves x 1 row per workgroup

@@ -329,7 +329,8 @@ extern "C" mdt_status mdt_create(const mdt_config* cfg, mdt_model** out) {
     if (c.goal_dim == 2 * c.obs_dim)
         return fail(MDT_ERR_UNSUPPORTED, "goal_dim == 2*obs_dim triggers the reference's goal truncation "
                                          "(mdtv_transformer.py:252-253); not implemented");
-    if (c.action_dim < 1 || c.action_dim > 16) return fail(MDT_ERR_UNSUPPORTED, "action_dim must be 1..16");
+    if (c.action_dim < 1 || c.action_dim > MDT_ACTION_DIM_MAX)  // one wavefront's lanes carry a row's elements; four MFMA column tiles
+        return fail(MDT_ERR_UNSUPPORTED, "action_dim %d: supported 1..%d", c.action_dim, MDT_ACTION_DIM_MAX);
     if (c.action_seq_len < 1 || c.action_seq_len > MDT_ROPE_POSITIONS || (c.action_seq_len > 16 && hd < 32))
         return fail(MDT_ERR_UNSUPPORTED, "action_seq_len %d at head dim %d: action_seq_len 17..64 needs head dim 32 / 48 / 64; head dim 16 "
                                          "takes 1..16 (action_seq_len must be >= 1 and <= 64)", c.action_seq_len, hd);
@@ -1553,7 +1554,7 @@ static mdt_status sample_plan_impl(mdt_model* m, const SamplerRequest& a) {
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample: the noise buffer holds %d rows, the sampler reads %d", n_noise, rows);
     if (misaligned(a.x_T) || misaligned(a.out) || misaligned(noise))
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample: pointers must be 16-byte aligned");
-    if (m->A > 16) return fail(MDT_ERR_UNSUPPORTED, "mdt_sample: action_dim must be <= 16");
+    if (m->A > MDT_ACTION_DIM_MAX) return fail(MDT_ERR_UNSUPPORTED, "mdt_sample: action_dim must be <= %d", MDT_ACTION_DIM_MAX);
     SamplerCall c;
     MDT_TRY(sampler_open(m, a, gd, &c));
     const bool per_step_ctx = m->cond == COND_TOKEN;  // sigma is a context token: the encoder runs per evaluation
@@ -1720,7 +1721,8 @@ static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const SamplerRequest& a
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: sigma_min and sigma_max must be > 0");
     if (misaligned(a.x_T) || misaligned(a.out))
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: pointers must be 16-byte aligned");
-    if (m->A > 16) return fail(MDT_ERR_UNSUPPORTED, "mdt_sample_dpm_adaptive: action_dim must be <= 16");
+    if (m->A > MDT_ACTION_DIM_MAX)
+        return fail(MDT_ERR_UNSUPPORTED, "mdt_sample_dpm_adaptive: action_dim must be <= %d", MDT_ACTION_DIM_MAX);
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing((hipStream_t)a.stream, &cs));
     if (cs != hipStreamCaptureStatusNone)
@@ -2093,7 +2095,7 @@ extern "C" mdt_status mdt_op_layernorm(const float* in, const float* w, const fl
 }
 
 extern "C" mdt_status mdt_op_head(const mdt_head_args* a, void* stream) {
-    if (!a || !a->y || !a->out || a->A < 1 || a->A > 16 || a->D % 4 || a->D > 512 || a->mode == MDT_HEAD_PLAN)
+    if (!a || !a->y || !a->out || a->A < 1 || a->A > MDT_ACTION_DIM_MAX || a->D % 4 || a->D > 512 || a->mode == MDT_HEAD_PLAN)
         return fail(MDT_ERR_INVALID_ARG, "mdt_op_head: bad argument");
     LAUNCH(mdt_launch_head(*a, (hipStream_t)stream));
     return MDT_OK;

@@ -1429,6 +1429,50 @@ __device__ __forceinline__ void attn_tile(const mdt_attn_args& a, const float* _
 __device__ __forceinline__ float edm_c_in(float sigma, float sd) { return 1.0f / sqrtf(sigma * sigma + sd * sd); }
 
 // ------------------------------------------------------------------------------------------------
+// One element of a sampler plan's update (MDT_HEAD_PLAN; mdt_sampler_plan.h), shared by head_rows (A <= 16) and the tiled head of
+// mdt_head_wide.hip (A 17 .. 64): element k = row * A + column of the (M, A) operands, the evaluation's input Y, the denoised
+// value D (after the pin) and the row's sigma in registers.  X' = sum cx R (clamped to [lo, hi] where `clip`), Y' = cy[NREG] X'
+// + sum cy R.  `own`: this lane is the element's one owner and the element exists -- it stores Y', the record and the history
+// shift; every lane may evaluate the arithmetic on a clamped k.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void head_plan_elem(const mdt_head_plan* pl, const float (&cx)[MDT_SAMPLER_NREG],
+                                               const float (&cy)[MDT_SAMPLER_NREG + 1], int push, bool clip, bool rec, int64_t nel,
+                                               const float* n0, const float* n1, int64_t k, float Y, float D, float sigma, float lo,
+                                               float hi, bool own, float& x_new, float& y_new) {
+    float R[MDT_SAMPLER_NREG];
+    R[MDT_R_X] = pl->xs[k];
+    R[MDT_R_Y] = Y;
+    R[MDT_R_D] = D;
+    R[MDT_R_DD] = (R[MDT_R_Y] - R[MDT_R_D]) / sigma;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) R[MDT_R_H0 + h] = pl->hist[h * nel + k];
+    R[MDT_R_N0] = n0 != nullptr ? n0[k] : 0.f;
+    R[MDT_R_N1] = n1 != nullptr ? n1[k] : 0.f;
+    float xn = 0.f, yn = 0.f;
+#pragma unroll
+    for (int q = 0; q < MDT_SAMPLER_NREG; ++q) xn += cx[q] * R[q];
+    if (clip) {  // torch.clamp: ordered compares keep a NaN, and lo > hi gives hi
+        xn = xn < lo ? lo : xn;
+        xn = xn > hi ? hi : xn;
+    }
+    yn = cy[MDT_SAMPLER_NREG] * xn;
+#pragma unroll
+    for (int q = 0; q < MDT_SAMPLER_NREG; ++q) yn += cy[q] * R[q];
+    x_new = xn;
+    y_new = yn;
+    if (own) {
+        if (pl->y_out != nullptr) pl->y_out[k] = yn;
+        if (rec) { pl->rec_x[k] = R[MDT_R_Y]; pl->rec_d[k] = R[MDT_R_D]; }
+        if (push != MDT_PUSH_NONE) {
+            pl->hist[3 * nel + k] = R[MDT_R_H0 + 2];
+            pl->hist[2 * nel + k] = R[MDT_R_H0 + 1];
+            pl->hist[nel + k] = R[MDT_R_H0];
+            pl->hist[k] = push == MDT_PUSH_D ? R[MDT_R_D] : R[MDT_R_DD];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // action head rows: decoder LN -> action_pred -> EDM combine -> (DDIM update) -> (next step's embedding) for rows
 // base .. base + RW - 1 (RW = 2: the action_pred / action_emb weight fragments a wave fetches are used
 // twice); AMAX (8 or 16) bounds the action dimension at compile time so no load sits behind a branch.
@@ -1636,37 +1680,8 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
 #pragma unroll
             for (int c = 0; c < AMAX; ++c) {
                 const int64_t k = row[r] * a.A + min(c, a.A - 1);
-                float R[MDT_SAMPLER_NREG];
-                R[MDT_R_X] = pl->xs[k];
-                R[MDT_R_Y] = xin[r][c];
-                R[MDT_R_D] = res[r * AMAX + c];
-                R[MDT_R_DD] = (R[MDT_R_Y] - R[MDT_R_D]) / sigma[r];
-#pragma unroll
-                for (int h = 0; h < 4; ++h) R[MDT_R_H0 + h] = pl->hist[h * nel + k];
-                R[MDT_R_N0] = n0 != nullptr ? n0[k] : 0.f;
-                R[MDT_R_N1] = n1 != nullptr ? n1[k] : 0.f;
-                float xn = 0.f, yn = 0.f;
-#pragma unroll
-                for (int q = 0; q < MDT_SAMPLER_NREG; ++q) xn += cx[q] * R[q];
-                if (clip) {  // torch.clamp: ordered compares keep a NaN, and lo > hi gives hi
-                    xn = xn < blo[c] ? blo[c] : xn;
-                    xn = xn > bhi[c] ? bhi[c] : xn;
-                }
-                yn = cy[MDT_SAMPLER_NREG] * xn;
-#pragma unroll
-                for (int q = 0; q < MDT_SAMPLER_NREG; ++q) yn += cy[q] * R[q];
-                res[r * AMAX + c] = xn;
-                resy[r * AMAX + c] = yn;
-                if (c < a.A && lane == c && base + r < a.M) {
-                    if (pl->y_out != nullptr) pl->y_out[k] = yn;
-                    if (rec) { pl->rec_x[k] = R[MDT_R_Y]; pl->rec_d[k] = R[MDT_R_D]; }
-                    if (push != MDT_PUSH_NONE) {
-                        pl->hist[3 * nel + k] = R[MDT_R_H0 + 2];
-                        pl->hist[2 * nel + k] = R[MDT_R_H0 + 1];
-                        pl->hist[nel + k] = R[MDT_R_H0];
-                        pl->hist[k] = push == MDT_PUSH_D ? R[MDT_R_D] : R[MDT_R_DD];
-                    }
-                }
+                head_plan_elem(pl, cx, cy, push, clip, rec, nel, n0, n1, k, xin[r][c], res[r * AMAX + c], sigma[r], blo[c], bhi[c],
+                               c < a.A && lane == c && base + r < a.M, res[r * AMAX + c], resy[r * AMAX + c]);
             }
     }
     // all lanes hold all results (xor-butterfly sums); lanes 0..A-1 store one each

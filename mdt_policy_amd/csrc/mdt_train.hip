@@ -311,7 +311,9 @@ static void carve_scratch(const mdt_model* m, Bump& b, mdt_train_state* ts, int6
         ts->defer_cap = (int64_t)(2 * m->Le + 3 * m->Ld + 2) * 2 * B * D + (int64_t)m->parts.size() * 256 * widest + 1024;
         ts->defer_buf = b.take(ts->defer_cap);
     }
-    ts->narrow = b.take((size_t)NARROW_SLICES * 16 * std::max({D, m->HP, m->p_row >= 0 ? 2 * D : 0}));
+    // slices of an (A16, .) weight gradient: A16 = the action width rounded up to 16 (the proprio width is at most 16)
+    const size_t narrow_len = (size_t)NARROW_SLICES * ((m->A + 15) / 16 * 16) * std::max({D, m->HP, m->p_row >= 0 ? 2 * D : 0});
+    ts->narrow = b.take(narrow_len);
     // Linear backward scratch: the largest need over every (rows, N, K) this model's backward runs
     int64_t need = 0;
     for (int64_t rows : {Ma, Me}) {
@@ -330,7 +332,7 @@ static void carve_scratch(const mdt_model* m, Bump& b, mdt_train_state* ts, int6
         // every dY of every block once: (3 + dec) x (M, D) merged gradients / dq, (M, 4D), (M, 3D) per block
         ts->dy_cap = (int64_t)m->Le * Me * (3 + 4 + 3) * D + (int64_t)m->Ld * Ma * (4 + 4 + 3) * D + 64 * (int64_t)(m->Le + m->Ld) * 8 + 1024;
         ts->dy_arena = b.take(ts->dy_cap);
-        ts->narrow2 = b.take((size_t)NARROW_SLICES * 16 * std::max({D, m->HP, m->p_row >= 0 ? 2 * D : 0}));
+        ts->narrow2 = b.take(narrow_len);
         ts->small2 = b.take(B * 3 * D + 64);
     } else {
         ts->narrow2 = ts->small2 = nullptr;
@@ -338,7 +340,9 @@ static void carve_scratch(const mdt_model* m, Bump& b, mdt_train_state* ts, int6
         ts->dy_arena = nullptr; ts->dy_cap = 0;
     }
     ts->dF = b.take(Ma * m->A);
-    ts->small = b.take(std::max<int64_t>({B * 2 * D, Mx * (int64_t)std::max(m->O, m->G), (int64_t)16 * m->HP}));
+    // (Ma * A: d x of denoise_grad, steer and log_likelihood lands here; below max(O, G) columns only while A is)
+    ts->small = b.take(std::max<int64_t>({B * 2 * D, Mx * (int64_t)std::max(m->O, m->G), (int64_t)((m->A + 15) / 16 * 16) * m->HP,
+                                          Ma * (int64_t)m->A}));
 }
 
 static mdt_status reserve_scratch(mdt_model* m, int64_t B) {

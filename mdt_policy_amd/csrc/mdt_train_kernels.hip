@@ -1519,7 +1519,7 @@ hipError_t mdt_launch_narrow_dx(const float* G, const float* W, float* out, int 
     return hipGetLastError();
 }
 
-// out[m][a] = sum_d G[m][d] * WT[a][d]   (A <= 16): one wavefront per row m, lanes stride over d
+// out[m][a] = sum_d G[m][d] * WT[a][d]   (A <= 16; wider: k_narrow_out_wide): one wavefront per row m, lanes stride over d
 __global__ __launch_bounds__(256) void k_narrow_out(const float* __restrict__ G, int64_t ldg, const float* __restrict__ WT,
                                                     float* __restrict__ out, int M, int A, int D) {
     const int lane = threadIdx.x & 63;
@@ -1542,8 +1542,37 @@ __global__ __launch_bounds__(256) void k_narrow_out(const float* __restrict__ G,
         }
     }
 }
+// the same for 17 <= A <= 64: blockIdx.y = the 16-column tile a0 / 16 of the result; one wavefront per (row m, column tile), each
+// element summed in k_narrow_out's order
+__global__ __launch_bounds__(256) void k_narrow_out_wide(const float* __restrict__ G, int64_t ldg, const float* __restrict__ WT,
+                                                         float* __restrict__ out, int M, int A, int D) {
+    const int lane = threadIdx.x & 63;
+    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int a0 = blockIdx.y * 16;
+    if (m >= M) return;
+    float acc[16];
+#pragma unroll
+    for (int a = 0; a < 16; ++a) acc[a] = 0.f;
+    for (int d = lane; d < D; d += 64) {
+        const float g = G[(int64_t)m * ldg + d];
+#pragma unroll
+        for (int a = 0; a < 16; ++a)
+            if (a0 + a < A) acc[a] = fmaf(g, WT[(int64_t)(a0 + a) * D + d], acc[a]);
+    }
+#pragma unroll
+    for (int a = 0; a < 16; ++a) {
+        if (a0 + a < A) {
+            const float v = wave_sum(acc[a]);
+            if (lane == 0) out[(int64_t)m * A + a0 + a] = v;
+        }
+    }
+}
 hipError_t mdt_launch_narrow_out(const float* G, int64_t ldg, const float* WT, float* out, int M, int A, int D, hipStream_t s) {
-    if (A < 1 || A > 16) return hipErrorInvalidValue;
+    if (A < 1 || A > MDT_ACTION_DIM_MAX) return hipErrorInvalidValue;
+    if (A > 16) {
+        hipLaunchKernelGGL(k_narrow_out_wide, dim3((M + 3) / 4, (A + 15) / 16), dim3(256), 0, s, G, ldg, WT, out, M, A, D);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_narrow_out, dim3((M + 3) / 4), dim3(256), 0, s, G, ldg, WT, out, M, A, D);
     return hipGetLastError();
 }
@@ -1582,9 +1611,49 @@ __global__ __launch_bounds__(256) void k_narrow_dw(const float* __restrict__ G, 
             if (a < A) p[transposed ? d * A + a : a * D + d] = acc[a];
     }
 }
+// the same for 17 <= A <= 64: blockIdx.z = the 16-column tile a0 / 16 of G; every element of `partial` keeps one owner and
+// k_narrow_dw's order over the slice's rows
+__global__ __launch_bounds__(256) void k_narrow_dw_wide(const float* __restrict__ G, const float* __restrict__ Y, int64_t ldy,
+                                                        float* __restrict__ partial, int M, int A, int D, int transposed) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    const int ny = gridDim.y, y = blockIdx.y;
+    const int a0 = blockIdx.z * 16;
+    const int m0 = (int)((int64_t)M * y / ny), m1 = (int)((int64_t)M * (y + 1) / ny);
+    float acc[16];
+#pragma unroll
+    for (int a = 0; a < 16; ++a) acc[a] = 0.f;
+    if (d < D) {
+        int m = m0;
+        for (; m + 4 <= m1; m += 4) {  // four rows' loads in flight per trip
+            float yv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) yv[u] = Y[(int64_t)(m + u) * ldy + d];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int a = 0; a < 16; ++a)
+                    if (a0 + a < A) acc[a] = fmaf(G[(int64_t)(m + u) * A + a0 + a], yv[u], acc[a]);
+        }
+        for (; m < m1; ++m) {
+            const float yv = Y[(int64_t)m * ldy + d];
+#pragma unroll
+            for (int a = 0; a < 16; ++a)
+                if (a0 + a < A) acc[a] = fmaf(G[(int64_t)m * A + a0 + a], yv, acc[a]);
+        }
+        float* p = partial + (int64_t)y * A * D;
+#pragma unroll
+        for (int a = 0; a < 16; ++a)
+            if (a0 + a < A) p[transposed ? (int64_t)d * A + a0 + a : (int64_t)(a0 + a) * D + d] = acc[a];
+    }
+}
 hipError_t mdt_launch_narrow_dw(const float* G, const float* Y, int64_t ldy, float* partial, int n_slices, int M, int A,
                                 int D, int transposed, hipStream_t s) {
-    if (A < 1 || A > 16) return hipErrorInvalidValue;
+    if (A < 1 || A > MDT_ACTION_DIM_MAX) return hipErrorInvalidValue;
+    if (A > 16) {
+        hipLaunchKernelGGL(k_narrow_dw_wide, dim3((D + 255) / 256, n_slices, (A + 15) / 16), dim3(256), 0, s, G, Y, ldy, partial, M,
+                           A, D, transposed);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_narrow_dw, dim3((D + 255) / 256, n_slices), dim3(256), 0, s, G, Y, ldy, partial, M, A, D,
                        transposed);
     return hipGetLastError();
