@@ -263,6 +263,15 @@ mdt_status mdt_op_xattn_gemm(const mdt_xapply_args *x, const mdt_gemm_args *g, v
 mdt_status mdt_op_attn_xattn(const mdt_gemm_args *proj, const float *qkv, int64_t ldq, const mdt_xapply_args *x, int32_t hd,
                              int32_t T, void *stream);
 
+/* The same launch with the output projection on fp16 pair splits: proj->Wp_pair (required; proj->Wp is ignored) is the image
+ * mdt_op_pack_weight_pair makes of c_proj.weight (mdt_op_pair_image_bytes(384, 384) bytes, 16-byte aligned).  The attention output
+ * gets one power-of-two scale per row and is multiplied as two fp16 parts, three v_mfma_f32_16x16x32_f16 per 32 columns of K
+ * instead of eight v_mfma_f32_16x16x4_f32; everything behind the projection is mdt_op_attn_xattn's.  fp32-grade results, not
+ * its bits.  An Inf / NaN in a sample's attention output reaches that sample's rows only.  The model-level entry points use it
+ * from 768 rows on (mdt_op_set_mlp_split(0) restores the fp32 launch). */
+mdt_status mdt_op_attn_xattn_pair(const mdt_gemm_args *proj, const float *qkv, int64_t ldq, const mdt_xapply_args *x, int32_t hd,
+                                  int32_t T, void *stream);
+
 /* y = (x * c_in(sigma)) Wa^T + ba   (c_in omitted when sigma == NULL); WaT = action_emb.weight transposed to (A, D) */
 mdt_status mdt_op_action_embed(const float *x, const float *sigma, int64_t sigma_stride, float sigma_data,
                                const float *WaT, const float *ba, float *y, int64_t M, int32_t A, int32_t D,

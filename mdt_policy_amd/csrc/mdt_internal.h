@@ -42,7 +42,7 @@ struct Lin {
     float* bias = nullptr;  // (N) or nullptr
     int N = 0, K = 0;
     float* wt = nullptr;    // training only: fragment-packed image of W^T (N' = K, K' = N), for dX = dY W
-    void* ws = nullptr;     // the MLP's two Linears and the stacked q|k|v: fp16 pair fragment image (4 N K + N bytes; mdt_mlp_split.h)
+    void* ws = nullptr;     // the MLP's two Linears, the stacked q|k|v and the decoder's attention c_proj: fp16 pair fragment image (4 N K + N bytes; mdt_mlp_split.h)
 };
 
 // bump allocator over one hipMalloc'ed block (count pass with base == nullptr, then the real pass)
@@ -143,7 +143,7 @@ hipError_t mdt_launch_attn_proj_wide(const mdt_gemm_args& p, const float* qkv, i
 // one workgroup per sample: self-attention -> projection -> collapsed cross-attention (k_attn_xattn); x.y == p.out
 bool mdt_attn_xattn_supported(const mdt_gemm_args& p, const mdt_xapply_args& x, int H, int hd, int T, int causal, int rope);
 hipError_t mdt_launch_attn_xattn(const mdt_gemm_args& p, const float* qkv, int64_t ldq, const mdt_xapply_args& x, int H, int hd,
-                                 int T, hipStream_t s, int ctx_div = 1);
+                                 int T, hipStream_t s, int ctx_div = 1, bool pair = false);   // pair: the projection on p.Wp_pair (fp16 pairs)
 // side jobs (mdt_kernels.hip): small-M products that ride in the launches of the small-M products that follow them
 hipError_t mdt_gemm_side_push(const mdt_gemm_args& a, hipStream_t s);
 hipError_t mdt_gemm_side_push_front(const mdt_gemm_args& a, hipStream_t s);

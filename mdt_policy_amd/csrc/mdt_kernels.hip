@@ -501,12 +501,13 @@ __global__ __launch_bounds__(512) void k_attn_proj_wide(mdt_gemm_args a, mdt_att
 // CD (here and in the other kernels that read per-context operands): ctx_div decoder samples share one context -- the candidates
 // of a sampler call -- so sample b reads the operands of context b / ctx_div (ctx_context below).  The plain launch is the
 // CD = false instantiation, the code it has always been: it never reads ctx_div.
-template <int HD, int TKC, bool CD>
+// PAIR: the output projection on the fp16 pair image a.Wp_pair (three v_mfma_f32_16x16x32_f16 per k32 step) instead of a.Wp
+template <int HD, int TKC, bool CD, bool PAIR = false>
 __global__ __launch_bounds__(512) void k_attn_xattn(mdt_gemm_args a, mdt_attn_pro at, mdt_xapply_args x, const float* __restrict__ zeros,
                                                     int ctx_div) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b = xcd_remap(blockIdx.x, gridDim.x);
-    attn_xattn_tile<HD, TKC, 32>(a, at, x, b, ctx_context<CD>(b, ctx_div), lds, zeros, threadIdx.x);
+    attn_xattn_tile<HD, TKC, 32, PAIR>(a, at, x, b, ctx_context<CD>(b, ctx_div), lds, zeros, threadIdx.x);
 }
 
 // 256 KiB of zeros per device: stands in for absent bias / rowvec / LayerNorm-bias vectors.  ensure_zeros() points
@@ -865,22 +866,27 @@ bool mdt_attn_xattn_supported(const mdt_gemm_args& p, const mdt_xapply_args& x, 
            mdt_xattn_apply_supported(x.D, x.H, x.Te, x.Ta);
 }
 
-template <int HD, int TKC>
+// (both forms: 101 632 B at d = 384 -- the pair form keeps its 25.6 KB two-part activation tile inside xattn_tile's scratch and
+//  uses 64 B of the fp32 tile's place for the rows' maxima)
+template <int HD, int TKC, bool PAIR>
 static hipError_t launch_attn_xattn_t(const mdt_gemm_args& p, const mdt_attn_pro& at, const mdt_xapply_args& x, hipStream_t s, int ctx_div) {
-    const int D = 8 * HD;
-    const size_t lds = ((size_t)16 * (D + 4) + (size_t)48 * (D + 16)) * sizeof(float);
-    if (ctx_div > 1) return mdt_launch_lds<k_attn_xattn<HD, TKC, true>>(dim3(x.B), dim3(512), lds, s, p, at, x, g_zeros, ctx_div);
-    return mdt_launch_lds<k_attn_xattn<HD, TKC, false>>(dim3(x.B), dim3(512), lds, s, p, at, x, g_zeros, 1);
+    constexpr int D = 8 * HD;
+    constexpr size_t lds = ((size_t)16 * (D + 4) + (size_t)48 * (D + 16)) * sizeof(float);
+    if (ctx_div > 1) return mdt_launch_lds<k_attn_xattn<HD, TKC, true, PAIR>>(dim3(x.B), dim3(512), lds, s, p, at, x, g_zeros, ctx_div);
+    return mdt_launch_lds<k_attn_xattn<HD, TKC, false, PAIR>>(dim3(x.B), dim3(512), lds, s, p, at, x, g_zeros, 1);
 }
 
+// pair: the projection reads p.Wp_pair (mdt_pair_image_bytes(N, K) bytes, 16-byte aligned) instead of p.Wp
 hipError_t mdt_launch_attn_xattn(const mdt_gemm_args& p, const float* qkv, int64_t ldq, const mdt_xapply_args& x, int H, int hd,
-                                 int T, hipStream_t s, int ctx_div) {
+                                 int T, hipStream_t s, int ctx_div, bool pair) {
     if (!mdt_attn_xattn_supported(p, x, H, hd, T, 1, 0) || ldq != 3 * (int64_t)p.K || ctx_div < 1) return hipErrorInvalidValue;
+    if (pair && p.Wp_pair == nullptr) return hipErrorInvalidValue;
     hipError_t ze = ensure_zeros();
     if (ze != hipSuccess) return ze;
     mdt_attn_pro at;
     at.qkv = qkv; at.ldq = ldq; at.T = T; at.scale = 1.0f / sqrtf((float)hd);
-    return T <= 10 ? launch_attn_xattn_t<48, 10>(p, at, x, s, ctx_div) : launch_attn_xattn_t<48, 16>(p, at, x, s, ctx_div);
+    if (pair) return T <= 10 ? launch_attn_xattn_t<48, 10, true>(p, at, x, s, ctx_div) : launch_attn_xattn_t<48, 16, true>(p, at, x, s, ctx_div);
+    return T <= 10 ? launch_attn_xattn_t<48, 10, false>(p, at, x, s, ctx_div) : launch_attn_xattn_t<48, 16, false>(p, at, x, s, ctx_div);
 }
 
 // Side jobs: products that do not depend on the launches they are queued beside (and that nothing launched before

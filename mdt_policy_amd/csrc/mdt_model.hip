@@ -252,6 +252,10 @@ static void build_params(mdt_model* m, Bump& b, bool fill_slots) {
         const std::string pre = P + "decoder.blocks." + std::to_string(l);
         DecBlock& d = m->dec[l];
         block_common_a(d, pre);
+        if (D % 128 == 0 && D <= 512) {   // the pair form of k_attn_xattn's output projection (decoder blocks only reach that kernel)
+            d.proj.ws = b.take((size_t)mdt_pair_image_bytes(D, D) / 4);
+            add_extra(pre + ".attn.c_proj.weight", (int64_t)D * D, SLOT_PACK_SPLIT, (float*)d.proj.ws, D, D);
+        }
         lin_part(m->kv_all, pre + ".cross_att.key", D, l * 2 * D, true);
         lin_begin(d.xq, D, D, true);
         lin_part(d.xq, pre + ".cross_att.query", D, 0, true);
@@ -707,7 +711,9 @@ static mdt_status run_self_attn(mdt_model* m, const EncBlock& e, const View& V, 
     }
     if (fx && fused && M >= g_attn_xattn_min_rows() && B <= ATTN_XATTN_MAX_BATCH &&
         mdt_attn_xattn_supported(p, *fx, m->H, m->hd, T, causal, m->cfg.use_rot_embed)) {
-        LAUNCH(mdt_launch_attn_xattn(p, V.qkv, 3 * D, *fx, m->H, m->hd, T, s, ctx_div));
+        // the projection on its fp16 pair image under the row condition of split_ready (below it the image may be stale), as run_mlp
+        const bool pair = e.proj.ws && mdt_mlp_split_enabled() && M >= mdt_split_min_rows();
+        LAUNCH(mdt_launch_attn_xattn(p, V.qkv, 3 * D, *fx, m->H, m->hd, T, s, ctx_div, pair));
         *fused = true;
         return MDT_OK;
     }
@@ -802,7 +808,7 @@ static mdt_status refresh_split(mdt_model* m, hipStream_t s) {
         return MDT_OK;
     };
     for (const EncBlock& e : m->enc) { MDT_TRY(one(e.qkv)); MDT_TRY(one(e.fc)); MDT_TRY(one(e.proj2)); }
-    for (const DecBlock& d : m->dec) { MDT_TRY(one(d.qkv)); MDT_TRY(one(d.fc)); MDT_TRY(one(d.proj2)); }
+    for (const DecBlock& d : m->dec) { MDT_TRY(one(d.qkv)); MDT_TRY(one(d.proj)); MDT_TRY(one(d.fc)); MDT_TRY(one(d.proj2)); }
     m->split_stale = false;
     return MDT_OK;
 }
@@ -2084,6 +2090,21 @@ extern "C" mdt_status mdt_op_attn_xattn(const mdt_gemm_args* proj, const float* 
                                          "on M = x->B * T rows, T = x->Ta <= 16, x->y == proj->out and a (D, H, Te, Ta) "
                                          "mdt_op_xattn_apply supports");
     LAUNCH(mdt_launch_attn_xattn(*proj, qkv, ldq, *x, 8, hd, T, (hipStream_t)stream));
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_attn_xattn_pair(const mdt_gemm_args* proj, const float* qkv, int64_t ldq, const mdt_xapply_args* x,
+                                             int32_t hd, int32_t T, void* stream) {
+    if (!proj || !qkv || !x || !proj->Wp_pair || !proj->out || !x->ln_w || !x->U || !x->Wf || !x->c)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_xattn_pair: null argument");
+    if (misaligned(qkv) || misaligned(proj->Wp_pair) || misaligned(proj->out) || misaligned(proj->bias) || misaligned(proj->mod) ||
+        misaligned(x->U) || misaligned(x->Wf) || (ldq & 3))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_xattn_pair: pointers must be 16-byte aligned, ldq a multiple of 4");
+    if (!mdt_attn_xattn_supported(*proj, *x, 8, hd, T, 1, 0) || ldq != 3 * (int64_t)proj->K)
+        return fail(MDT_ERR_UNSUPPORTED, "mdt_op_attn_xattn_pair: needs 8 heads of 48 (K = N = ldo = 384, ldq = 3 K), a gated / residual "
+                                         "projection on M = x->B * T rows, T = x->Ta <= 16, x->y == proj->out and a (D, H, Te, Ta) "
+                                         "mdt_op_xattn_apply supports");
+    LAUNCH(mdt_launch_attn_xattn(*proj, qkv, ldq, *x, 8, hd, T, (hipStream_t)stream, 1, true));
     return MDT_OK;
 }
 

@@ -16,6 +16,7 @@
 
 #include "mdt_internal.h"
 #include "mdt_device.h"
+#include "mdt_split_ring.h"   // SplitRing / split_phase_one: attn_xattn_tile's pair form
 
 // XCD-aware block id: the dispatcher places block b on XCD b % 8 (speed-only assumption); give every XCD a
 // contiguous range of logical tiles so the row tiles it touches stay in its private L2.  Bijective for any n.
@@ -509,7 +510,7 @@ __device__ __forceinline__ void attn_stage_tile(const mdt_gemm_args& a, const md
 }
 
 // ------------------------------------------------------------------------------------------------
-// ONE sample's causal self-attention (8 heads of HD, T <= TKC <= 16 rows) -> xa (rows >= T zero): the attention stage of
+// ONE sample's causal self-attention (8 heads of HD, T <= TKC <= 16 rows) -> `out` (rows >= T zero): the attention stage of
 // attn_xattn_tile.  q | k | v of a row are adjacent (ldq == 3 D), so the sample's rows are ONE contiguous block of T * 3 D
 // floats: thread t requests float4 items t, t + 512, ... of it and puts them at the same (row, column) in LDS -- no division,
 // no 64-bit arithmetic per request (the general stage above spends ~1100 integer instructions per thread on its 9 + 28
@@ -517,9 +518,10 @@ __device__ __forceinline__ void attn_stage_tile(const mdt_gemm_args& a, const md
 // 16 (mod 64) floats.  Wave = head: both attention products on the MFMA pipe (below).  512 threads = 8 heads.
 //   scratch: 16 * (3 D + 16) floats.  `after_loads`: see attn_stage_tile.
 // ------------------------------------------------------------------------------------------------
-template <int HD, int TKC, class F>
-__device__ __forceinline__ void attn_sample_tile(const mdt_attn_pro& ap, float* xa, int stride, int m0, float* scratch, int tid,
-                                                 F after_loads) {
+//   `out(nt, row, column, o)`: what becomes of the lane's four output features [column, column + 4) of query `row` (already zero for
+//   rows >= T), nt = 0 .. HD / 16 - 1 -- attn_xattn_tile stores them into its activation tile, or keeps them for its pair split.
+template <int HD, int TKC, class F, class O>
+__device__ __forceinline__ void attn_sample_tile(const mdt_attn_pro& ap, int m0, float* scratch, int tid, F after_loads, O out) {
     constexpr int D = 8 * HD, R4 = 3 * D / 4, ST3 = 3 * D + 16;
     constexpr int NL = (TKC * R4 + 511) / 512;          // 6 float4 per thread for 10 rows of d = 384, 9 for 16
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -593,7 +595,7 @@ __device__ __forceinline__ void attn_sample_tile(const mdt_attn_pro& ap, float* 
         f32x4 o = zero4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[nt][e], pr[e], o, 0, 0, 0);
-        *(f32x4*)(xa + m * stride + h * HD + 16 * nt + 4 * g) = valid ? o : zero4;
+        out(nt, m, h * HD + 16 * nt + 4 * g, valid ? o : zero4);
     }
 }
 
@@ -1949,13 +1951,29 @@ __device__ __forceinline__ void xattn_tile(const mdt_xapply_args& a, int b, int 
 //   attention's arguments (x.y == a.out).  512 threads; D = 8 * HD.
 //   the q | k | v rows of the sample are one contiguous block (at.ldq == 3 D).
 //   lds: 16 * (D + 4) + 48 * (D + 16) floats (the attention's rows; afterwards the projected rows + xattn_tile's scratch).
+// PAIR (what the model launches from 768 rows on): the projection on the fp16 pair image a.Wp_pair -- the
+//   attention output gets one power-of-two scale per row (maximum over all 8 heads: ds_max_u32 in front of the barrier) and goes to LDS
+//   as two fp16 parts, ONE more barrier; three v_mfma_f32_16x16x32_f16 per k32 step and column tile (split_phase_one) instead of eight
+//   v_mfma_f32_16x16x4_f32, same weight bytes.  Measured at B = 256 (profiles/attn_xattn_pair_bench_ab.txt): 19.92 -> 16.94 us per
+//   launch, 23 040 -> 8 064 MFMA-busy cycles per SIMD, 44.2 k -> 37.2 k cycles per workgroup, sampler call 3.042 -> 2.932 ms (estimated
+//   beforehand: 0.16-0.19 ms; the added barrier + split and ~1 k cycles more in front of the attention's barrier took the rest).
+//   204 VGPRs, no scratch; same LDS bytes (the pair tile sits behind yl, inside xattn_tile's scratch).
 // ------------------------------------------------------------------------------------------------
-template <int HD, int TKC, int NPP>
+template <int HD, int TKC, int NPP, bool PAIR = false>
 __device__ __forceinline__ void attn_xattn_tile(const mdt_gemm_args& a, const mdt_attn_pro& at, const mdt_xapply_args& x, int b,
                                                 int bc, float* lds, const float* __restrict__ zeros, int tid) {
     constexpr int MTILES = 1, NTW = HD / 16, D = 8 * HD, K16 = D / 16;
     constexpr bool KSTEP_PRIO = false;
     constexpr int R = NTW == 1 ? 6 : (NTW == 2 ? 4 : 3);   // deeper rings change nothing here (measured: R = 4, 6)
+    // pair form: k32 steps, the ring's depth in k32 steps, row / part stride of the two-part activation tile in bytes
+    // EARLY: steps requested inside the attention's callback, behind the q | k | v requests -- ONE (6 KB per wave, the bytes of the
+    // fp32 ring's first fragments there); the other RP - 2 follow behind the attention.  Measured at B = 256, sampler call against the
+    // parent's 3.04-3.07 ms: all three early 2.947-2.963, two 2.938-2.960, one 2.911-2.935, none 2.921-2.942 (18 KB per wave asked
+    // for beside the rows hold the rows back, section 4.6); rings of 3 / 5 / 6 steps 2.950-2.975 / 2.925-2.926 / 2.913-2.926.
+    constexpr int K32 = D / 32, RP = 4, EARLY = 1, ROWB = 2 * D + 32, PARTB = 16 * ROWB;
+    using SS = split_scheme<MDT_SPLIT_F16X2>;
+    static_assert(!PAIR || (D % 32 == 0 && 2 * PARTB <= (int)sizeof(float) * (48 * (D + 16) - 16 * (D + 4)) && RP - 1 <= K32),
+                  "pair tile: behind yl, inside xattn_tile's scratch");
     MDT_TS(0)
     MDT_TS_HWID()
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1966,28 +1984,47 @@ __device__ __forceinline__ void attn_xattn_tile(const mdt_gemm_args& a, const md
     float* scr = xa + 16 * stride;         // 16 x (3 D + 16): q | k | v rows; then yl [16][stride] and xattn_tile's scratch
     float* yl = scr;
     float* xscr = scr + 16 * stride;
+    // pair form: xa holds only the 16 row maxima (ordered bits of the largest |attention output| of a row, all 8 heads); the
+    // activation tile is two fp16 parts [16][ROWB] bytes BEHIND yl -- an early wave's epilogue writes yl while late waves still read
+    // activations -- where xattn_tile's scratch begins (first written behind the barrier that follows the epilogue)
+    unsigned* rmax = (unsigned*)xa;
+    char* pt = (char*)xscr;
 
     const int nt0 = wave * NTW;
     WStream wp[NTW];
-#pragma unroll
-    for (int j = 0; j < NTW; ++j) wp[j] = wstream(a.Wp, (int64_t)(nt0 + j) * K16 * 256 + lane * 4);
     f32x4 ring[R][NTW];
+    SplitRing<NTW, RP, MDT_SPLIT_F16X2> pring;
+    const char* image = (const char*)a.Wp_pair;
+    if constexpr (PAIR) {
+        pring.open(image, nt0 * SS::tile_stride(K32), SS::tile_stride(K32), lane);
+    } else {
+#pragma unroll
+        for (int j = 0; j < NTW; ++j) wp[j] = wstream(a.Wp, (int64_t)(nt0 + j) * K16 * 256 + lane * 4);
+    }
     f32x4 acc[MTILES][NTW];
 #pragma unroll
     for (int j = 0; j < NTW; ++j) acc[0][j] = zero4;
     const int nq = 4 * (lane >> 4);
     const bool gated = a.gate_off >= 0;
     int ncol[NTW];
+    int et[NTW];                           // (pair) scale exponents of the wave's column tiles
     f32x4 bias_v[NTW], gate_v[NTW], res_v[NTW];
+    f32x4 ov[NTW];                         // (pair) the lane's attention outputs: row lane % 16, head `wave`
     mdt_xattn_req<NPP, D> xq;
 
     // ---- the sample's causal self-attention -> xa (rows >= T zero).  Behind its q / k / v requests: the projection's first
     //      weight fragments and its epilogue operands ----
-    attn_sample_tile<HD, TKC>(at, xa, stride, m0, scr, tid, [&]() {
+    attn_sample_tile<HD, TKC>(at, m0, scr, tid, [&]() {
+        if constexpr (PAIR) {
 #pragma unroll
-        for (int u = 0; u < R - 1; ++u)
+            for (int u = 0; u < EARLY; ++u) pring.request(u, u);
+            if (tid < 16) rmax[tid] = 0u;  // (the barrier behind the q | k | v stores orders this before the first maximum)
+        } else {
 #pragma unroll
-            for (int j = 0; j < NTW; ++j) ring[u][j] = wld4(wp[j] + min(u, K16 - 1) * 256);
+            for (int u = 0; u < R - 1; ++u)
+#pragma unroll
+                for (int j = 0; j < NTW; ++j) ring[u][j] = wld4(wp[j] + min(u, K16 - 1) * 256);
+        }
         const float* biasp = a.bias != nullptr ? a.bias : zeros;
         const int m = min(m0 + min(lane & 15, T - 1), a.M - 1);
         const float* gp = zeros;
@@ -1998,19 +2035,50 @@ __device__ __forceinline__ void attn_xattn_tile(const mdt_gemm_args& a, const md
             bias_v[j] = ldg4(biasp + ncol[j]);
             gate_v[j] = ldg4(gp + ncol[j]);
             res_v[j] = ldg4(a.out + (int64_t)m * a.ldo + ncol[j]);
+            if constexpr (PAIR) et[j] = pair_tile_exp(image, SS::tile_stride(K32), nt0 + j);
         }
+    }, [&](int nt, int row, int col, const f32x4& o) {
+        if constexpr (PAIR) ov[nt] = o;
+        else *(f32x4*)(xa + row * stride + col) = o;
     });
+    if constexpr (PAIR) {
+#pragma unroll
+        for (int u = EARLY; u < RP - 1; ++u) pring.request(u, u);
+        // a row's maximum spans all 8 heads (= waves): ds_max_u32 in front of the barrier that the fp32 form has here too
+        unsigned mx = 0u;
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt) mx = max(mx, pair_absbits4(ov[nt]));
+        atomicMax(&rmax[lane & 15], mx);
+    }
     MDT_TS(1)
     __syncthreads();
-    MDT_TS(2)
+    if constexpr (!PAIR) { MDT_TS(2) } else { MDT_TS(7) }
     // The cross-attention's fragments of the sample's folded operands are cold (98 KB per sample that another workgroup used
     // one step ago: 25 MB per launch).  Requested at entry they held the q / k / v rows back (rows in LDS after 13.7 k cycles
     // instead of 7.6 k: the whole chip asks for 41 MB at once); requested here, the score half travels under the projection
     // (vmcnt retires in order: the k loop's first fragment waits ~1 k cycles behind it) ...
     xattn_request_u<NPP, D, D>(x, bc, tid, xq);
 
+    int xe = 0;                            // (pair) scale exponent of the lane's row
+    if constexpr (PAIR) {
+        // ---- the attention output as its pair split, one power-of-two scale per row, in MFMA slot order (split_slot) ----
+        const unsigned mx = rmax[lane & 15];
+        xe = pair_scale_exp(mx);
+        const float rs = pair_scale(mx);
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt) {
+            mdt_f16x4 p1, p2;
+            split2_f16(ov[nt], rs, p1, p2);
+            char* q = pt + split_slot(lane & 15, wave * HD + 16 * nt + nq, ROWB);
+            *(mdt_f16x4*)q = p1;
+            *(mdt_f16x4*)(q + PARTB) = p2;
+        }
+        __syncthreads();
+        MDT_TS(2)
+        // ---- projection: 16 x D x D as three v_mfma_f32_16x16x32_f16 per k32 step and column tile ----
+        split_phase_one<NTW, K32, RP>(pring, pt, ROWB, PARTB, lane, acc[0]);
+    } else {
     // ---- projection: 16 x D x D, transposed-form MFMA k-steps on the ring ----
-    {
         int kg = 0;
         const int nk = K16;
         const float* ap = xa + (lane & 15) * stride + 4 * (lane >> 4);
@@ -2037,7 +2105,9 @@ __device__ __forceinline__ void attn_xattn_tile(const mdt_gemm_args& a, const md
     // ---- epilogue: out = old + gate * (acc + bias) -> LDS rows (lane holds row lane % 16, columns ncol .. ncol + 3) ----
 #pragma unroll
     for (int j = 0; j < NTW; ++j) {
-        f32x4 v = acc[0][j] + bias_v[j];
+        f32x4 v = acc[0][j];
+        if constexpr (PAIR) v = pair_unscale(v, xe + et[j]);
+        v = v + bias_v[j];
         v = res_v[j] + (gated ? gate_v[j] * v : v);
         *(f32x4*)(yl + (lane & 15) * stride + ncol[j]) = v;
     }
