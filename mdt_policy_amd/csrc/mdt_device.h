@@ -286,6 +286,24 @@ __device__ __forceinline__ void split2_f16(const f32x4& x, float s, mdt_f16x4& p
         p1[e] = a; p2[e] = (_Float16)(v - (float)a);
     }
 }
+// the parts of v (pair form: of v * scale) as 8-byte stores one part stride apart: part p at q + p * part_stride.  (Three sites keep
+// the split and its stores written out -- gemm_stage_tile, gemm_ws_split_tile's commit, k_gemm_tn_split's stash: there the address
+// is computed behind the split, and a helper that takes it as an argument moves it in front and changes the kernels' schedules.)
+template <int SCH>
+__device__ __forceinline__ void store_split(char* q, int part_stride, const f32x4& v, float scale = 1.f) {
+    if constexpr (SCH == MDT_SPLIT_F16X2) {
+        mdt_f16x4 p1, p2;
+        split2_f16(v, scale, p1, p2);
+        *(mdt_f16x4*)q = p1;
+        *(mdt_f16x4*)(q + part_stride) = p2;
+    } else {
+        mdt_bf16x4 p1, p2, p3;
+        split3_bf16(v, p1, p2, p3);
+        *(mdt_bf16x4*)q = p1;
+        *(mdt_bf16x4*)(q + part_stride) = p2;
+        *(mdt_bf16x4*)(q + 2 * part_stride) = p3;
+    }
+}
 // acc 2^-e, one rounding at most (v_ldexp_f32)
 __device__ __forceinline__ f32x4 pair_unscale(const f32x4& acc, int e) {
     return (f32x4){__builtin_ldexpf(acc[0], -e), __builtin_ldexpf(acc[1], -e), __builtin_ldexpf(acc[2], -e), __builtin_ldexpf(acc[3], -e)};

@@ -1,8 +1,10 @@
 // mdt_kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of the MDT action-denoising hot path.
 //
 // Design:
-//   * every dense contraction runs on v_mfma_f32_16x16x4_f32 (exact fp32 MFMA; bf16/fp16 operands fail
-//     the 1e-3 parity gate) in the TRANSPOSED form  D[n][m] = sum_k W[n][k] * X[m][k]:
+//   * every dense contraction keeps fp32's product accuracy (plain bf16/fp16 operands fail the 1e-3 parity gate, SURVEY.md
+//     section 0): v_mfma_f32_16x16x4_f32, or -- the MLP, qkv, weight-stationary and attn_xattn launches -- split operands on
+//     v_mfma_f32_16x16x32_bf16 / _f16 (three bf16 parts or two scaled fp16 parts per operand; mdt_split_ring.h, DESIGN.md
+//     section 5a).  Both in the TRANSPOSED form  D[n][m] = sum_k W[n][k] * X[m][k]:
 //     the weight fragment is the MFMA "A" operand and the activation fragment the "B" operand, so that a
 //     lane ends up with 4 CONSECUTIVE output columns of one row -> 16-byte epilogue loads/stores.
 //   * weights are pre-packed once (k_pack_weight) into fragment-major order: one 16(n) x 16(k) block is
@@ -36,7 +38,7 @@
 #include "mdt_sampler_plan.h"
 #include "mdt_tall.h"  // the tall LDS-staged GEMM body (round 4)
 #include "mdt_ws.h"    // the weight-stationary GEMM body (round 5)
-#include "mdt_mlp_split.h"  // the fused MLP launch in the three-way bf16 split form (round 6)
+#include "mdt_mlp_split.h"  // the fused MLP launch and the LayerNorm-prologue products in the split forms (bf16 x 3, fp16 x 2)
 
 // ------------------------------------------------------------------------------------------------
 // weight packing
@@ -70,13 +72,9 @@ hipError_t mdt_launch_pack_weight_glu(const float* w, int H, int K, float* packe
 // three-way bf16 split fragment image (mdt_mlp_split.h): thread = 4 consecutive k of one row -> eight bytes in each of the three
 // parts of fragment (row tile r / 16, k32 step c / 32): lane (r % 16) + 16 ((c % 16) / 4), half (c % 32) / 16
 __device__ __forceinline__ void pack_split_quad(const float* __restrict__ src, char* __restrict__ image, int rs, int c, int K, int n_off) {
-    mdt_bf16x4 p1, p2, p3;
-    split3_bf16(*(const f32x4*)(src + (int64_t)rs * K + c), p1, p2, p3);
     const int r = rs + n_off;   // row of the image
     char* q = image + (((int64_t)(r >> 4) * (K >> 5) + (c >> 5)) * 3) * 1024 + ((r & 15) + 16 * ((c & 15) >> 2)) * 16 + ((c & 31) >> 4) * 8;
-    *(mdt_bf16x4*)q = p1;
-    *(mdt_bf16x4*)(q + 1024) = p2;
-    *(mdt_bf16x4*)(q + 2048) = p3;
+    store_split<MDT_SPLIT_BF16X3>(q, 1024, *(const f32x4*)(src + (int64_t)rs * K + c));
 }
 __global__ void k_pack_weight_split(const float* __restrict__ w, int n_rows, int K, char* __restrict__ image, int n_off) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -137,11 +135,8 @@ __device__ __forceinline__ void pack_pair_tile(const float* __restrict__ src, ch
     char* tile = image + (int64_t)(t + (n_off >> 4)) * ((int64_t)K32 * 2048 + 16);
     for (int i = tid; i < 16 * K4; i += 256) {
         const int r = i / K4, c = 4 * (i - r * K4);
-        mdt_f16x4 p1, p2;
-        split2_f16(*(const f32x4*)(rows + (int64_t)r * K + c), sc, p1, p2);
         char* q = tile + (c >> 5) * 2048 + (r + 16 * ((c & 15) >> 2)) * 16 + ((c & 31) >> 4) * 8;
-        *(mdt_f16x4*)q = p1;
-        *(mdt_f16x4*)(q + 1024) = p2;
+        store_split<MDT_SPLIT_F16X2>(q, 1024, *(const f32x4*)(rows + (int64_t)r * K + c), sc);
     }
     if (tid == 0) *(f32x4*)(tile + (int64_t)K32 * 2048) = (f32x4){sc, 0.f, 0.f, 0.f};
 }
@@ -303,7 +298,7 @@ __global__ __launch_bounds__(512) void k_mlp(mdt_gemm_args f, mdt_gemm_args p, f
     mlp_tile<NTW2, PRO>(f, p, parts, part_stride, by, s, lds, zeros, threadIdx.x, skew);
 }
 
-// k_mlp_split: the same launch in the three-way bf16 split form (mdt_mlp_split.h).  Workgroups in SLICE-major order, XCD x taking a
+// k_mlp_split: the same launch in the split forms (mdt_mlp_split.h; SCH below).  Workgroups in SLICE-major order, XCD x taking a
 // contiguous range of it (block b runs on XCD b % 8): an XCD's L2 then holds one or two slices of the split weight images (2.4 MB
 // each at d = 384) instead of all of them.  grid = 8 * ceil(tiles * slices / 8).
 // SCH: the split scheme (mdt_mlp_split.h): the three-way bf16 split, or the two-way fp16 pair split the model's launches use
@@ -1161,7 +1156,7 @@ hipError_t mdt_launch_gemm_ln_pair(const mdt_gemm_args& a, hipStream_t s) {
     return a.K == 512 ? launch_gemm_ln_split_pro<4, 3, MDT_SPLIT_F16X2>(a, s) : launch_gemm_ln_split_pro<3, 3, MDT_SPLIT_F16X2>(a, s);
 }
 
-// ---- the fused MLP sublayer in the three-way bf16 split form (k_mlp_split) ----
+// ---- the fused MLP sublayer in the split forms (k_mlp_split: three-way bf16, or the two-way fp16 pair split) ----
 // MDT_HIP_MLP_SPLIT / mdt_op_set_mlp_split: 0 = the fp32 launch everywhere
 bool mdt_mlp_split_enabled() { return mdt_switch_env(g_mdt_sw.mlp_split, "MDT_HIP_MLP_SPLIT", 1) != 0; }
 extern "C" void mdt_op_set_mlp_split(int32_t on) { g_mdt_sw.mlp_split = on < 0 ? -1 : (on != 0); }

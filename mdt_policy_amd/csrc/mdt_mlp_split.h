@@ -1,24 +1,29 @@
-// mdt_mlp_split.h -- the fused MLP launch (mdt_tiles.h mlp_tile) in its SPLIT forms: the THREE-WAY bf16 split (round 6; DESIGN.md section
-// 5a (h)), described first, and the TWO-WAY fp16 PAIR split the model's launches take (5a (i); `split_scheme` below).
+// mdt_mlp_split.h -- the fused MLP launch (mdt_tiles.h mlp_tile) and the LayerNorm-prologue product in their SPLIT forms.  Template
+// parameter SCH (mdt_split_ring.h split_scheme): the THREE-WAY bf16 split, or the TWO-WAY fp16 PAIR split
+// of scaled operands that the model's launches take (5a (i)).
 //
 // Same work per workgroup as mlp_tile -- row tile `by` (32 rows) x hidden slice `s` (512 of the 4 D hidden columns):
 //   x + gate * (act(prologue(x) W1^T + b1) W2^T + b2),  partial slab s of the second product to parts + s * part_stride --
-// with every contraction as six v_mfma_f32_16x16x32_bf16 products per k32 step (x = x1 + x2 + x3, w = w1 + w2 + w3 in bf16,
-// products x3 w1, x2 w2, x2 w1, x1 w3, x1 w2, x1 w1, fp32 accumulation: fp32's product accuracy, mdt_ws.h) instead of eight
-// v_mfma_f32_16x16x4_f32: 96 matrix-pipe clocks per k32 step and accumulator instead of 256.
+// with every contraction as P (P + 1) / 2 products of operand parts per k32 step (x = x1 + .. + xP, w = w1 + .. + wP; order and
+// schedule: split_phase, mdt_split_ring.h; fp32 accumulation) instead of eight v_mfma_f32_16x16x4_f32: six
+// v_mfma_f32_16x16x32_bf16 (fp32's product accuracy, mdt_ws.h) = 96 matrix-pipe clocks per k32 step and accumulator instead of 256,
+// or three v_mfma_f32_16x16x32_f16 (22 significand bits after the row / tile scales) = 48.
 //
 // Where the operands come from:
-//   weights     PRE-SPLIT images (k_pack_weight_split: made wherever the fp32 fragment image is made -- mdt_load_param(s), i.e. also
-//               after every optimizer step): fragment (column tile nt, k32 step kk, part p) = 1 KiB at ((nt K32 + kk) 3 + p) 1024,
-//               lane l's 16 bytes = the part's eight bf16 of W[16 nt + l % 16][32 kk + 16 h + 4 (l / 16) + e], slot 4 h + e.  A wave
-//               streams its fragments L2 -> registers as mlp_tile does (ring of two k32 steps): 1.5x the bytes of the fp32 image in
-//               a third of the matrix-pipe time -- 49 B per clock and CU of the vector memory path's 64 at full rate (fp32: 14);
-//               tools/micro/mlp_split_probe.hip measured the two phases with this traffic at 31 us against k_mlp's 52-58.
+//   weights     PRE-SPLIT images (k_pack_weight_split / k_pack_weight_pair: made wherever the fp32 fragment image is made --
+//               mdt_load_param(s), i.e. also after every optimizer step): fragment (column tile nt, k32 step kk, part p) = 1 KiB at
+//               nt * tile_stride + (kk P + p) 1024, lane l's 16 bytes = the part's eight values of
+//               W[16 nt + l % 16][32 kk + 16 h + 4 (l / 16) + e], slot 4 h + e; pair images end each column tile with its scale
+//               (mdt_split_ring.h).  A wave streams its fragments L2 -> registers as mlp_tile does (SplitRing, two k32 steps):
+//               bf16 x 3 is 1.5x the bytes of the fp32 image in a third of the matrix-pipe time -- 49 B per clock and CU of the
+//               vector memory path's 64 at full rate (fp32: 14); tools/micro/mlp_split_probe.hip measured the two phases with this
+//               traffic at 31 us against k_mlp's 52-58.  The pair form streams the fp32 image's bytes.
 //   activations the LayerNorm (+ modulate) prologue of mlp_tile (gemm_stage_tile) stores its rows as their split, in the MFMA slot
-//               order of mdt_ws.h (one ds_read_b128 per part, row tile and k32 step);
-//   hidden      the activation epilogue of the first product splits its values on the way into LDS, same slot order.
-// LDS: split x tile 3 x 32 x (2 D + 32) B, overlaid after the first product by the split hidden slice 3 x 32 x 1056 B = 101 KB
-// (D <= 512: 101 KB either way).
+//               order of mdt_ws.h (one ds_read_b128 per part, row tile and k32 step); pair form: one power-of-two scale per row;
+//   hidden      the activation epilogue of the first product splits its values on the way into LDS, same slot order (pair form:
+//               scaled by the row's maximum over the 512-wide slice, gathered in LDS in front of the barrier).
+// LDS: split x tile P x 32 x (2 D + 32) B, overlaid after the first product by the split hidden slice P x 32 x 1056 B: 101 KB for
+// three parts, 67.6 KB + 256 B of row scales and maxima for two (D <= 512 either way).
 // No wave skew here (mlp_tile's flags): the hidden slice overlays the x tile, so the two products are separated by barriers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,118 +32,14 @@
 #include "mdt_device.h"
 #include "mdt_internal.h"
 #include "mdt_tiles.h"
-#include "mdt_ws.h"   // mdt_bf16x8 / mdt_bf16x4, split3_bf16
+#include "mdt_ws.h"
 
-// (the split schemes, split_scheme<SCH> and the weight-fragment ring SplitRing: mdt_split_ring.h, which mdt_tiles.h includes)
-
-// one product phase: acc[i][j] += sum over K32 k32 steps; ring slots 0 .. R - 2 hold steps 0 .. R - 2 on entry (requested by the
-// caller, early); activations from the split tile at `xa` (row stride rowb, part
-// stride part)
-template <int NT, int K32, int R, int SCH>
-__device__ __forceinline__ void split_phase(SplitRing<NT, R, SCH>& ring, const char* xa, int rowb, int part, int lane, f32x4 (&acc)[2][NT]) {
-    const int aoff = (lane & 15) * rowb + (lane >> 4) * 16;
-    if constexpr (SCH == MDT_SPLIT_F16X2) {
-        mdt_f16x8 x1[2], x2[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const char* q = xa + aoff + i * 16 * rowb;
-            x1[i] = *(const mdt_f16x8*)q; x2[i] = *(const mdt_f16x8*)(q + part);
-        }
-#pragma unroll
-        for (int kk = 0; kk < K32; ++kk) {
-            const int u = kk % R, un = (kk + R - 1) % R;
-            const bool nx = kk + 1 < K32;
-            if (kk + R - 1 < K32) ring.request(un, kk + R - 1);
-            const char* p0 = xa + aoff + (kk + 1) * 64;
-            const char* p1 = p0 + 16 * rowb;
-            MDT_SCHED_PIN
-            // the three products of this k32 step, smallest first; same pinned order as the six of the bf16 form below
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][0], x2[0], acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][0], x2[1], acc[1][j], 0, 0, 0);
-            }
-            MDT_SCHED_PIN
-            if (nx) { x2[0] = *(const mdt_f16x8*)(p0 + part); x2[1] = *(const mdt_f16x8*)(p1 + part); }
-            MDT_SCHED_PIN
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][1], x1[0], acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][1], x1[1], acc[1][j], 0, 0, 0);
-            }
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][0], x1[0], acc[0][j], 0, 0, 0);
-                acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ring.w[u][j][0], x1[1], acc[1][j], 0, 0, 0);
-            }
-            MDT_SCHED_PIN
-            if (nx) { x1[0] = *(const mdt_f16x8*)p0; x1[1] = *(const mdt_f16x8*)p1; }
-            MDT_SCHED_PIN
-        }
-    } else {
-    mdt_bf16x8 x1[2], x2[2], x3[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const char* q = xa + aoff + i * 16 * rowb;
-        x1[i] = *(const mdt_bf16x8*)q; x2[i] = *(const mdt_bf16x8*)(q + part); x3[i] = *(const mdt_bf16x8*)(q + 2 * part);
-    }
-#pragma unroll
-    for (int kk = 0; kk < K32; ++kk) {
-        const int u = kk % R, un = (kk + R - 1) % R;
-        const bool nx = kk + 1 < K32;
-        if (kk + R - 1 < K32) ring.request(un, kk + R - 1);
-        const char* p0 = xa + aoff + (kk + 1) * 64;
-        const char* p1 = p0 + 16 * rowb;
-        MDT_SCHED_PIN
-        // the six products of this k32 step, smallest first; each activation part of the NEXT step is read into this step's registers
-        // right behind its last use (mdt_ws.h)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][0], x3[0], acc[0][j], 0, 0, 0);
-            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][0], x3[1], acc[1][j], 0, 0, 0);
-        }
-        MDT_SCHED_PIN
-        if (nx) { x3[0] = *(const mdt_bf16x8*)(p0 + 2 * part); x3[1] = *(const mdt_bf16x8*)(p1 + 2 * part); }
-        MDT_SCHED_PIN
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][1], x2[0], acc[0][j], 0, 0, 0);
-            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][1], x2[1], acc[1][j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][0], x2[0], acc[0][j], 0, 0, 0);
-            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][0], x2[1], acc[1][j], 0, 0, 0);
-        }
-        MDT_SCHED_PIN
-        if (nx) { x2[0] = *(const mdt_bf16x8*)(p0 + part); x2[1] = *(const mdt_bf16x8*)(p1 + part); }
-        MDT_SCHED_PIN
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][2], x1[0], acc[0][j], 0, 0, 0);
-            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][2], x1[1], acc[1][j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][1], x1[0], acc[0][j], 0, 0, 0);
-            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][1], x1[1], acc[1][j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][0], x1[0], acc[0][j], 0, 0, 0);
-            acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ring.w[u][j][0], x1[1], acc[1][j], 0, 0, 0);
-        }
-        MDT_SCHED_PIN
-        if (nx) { x1[0] = *(const mdt_bf16x8*)p0; x1[1] = *(const mdt_bf16x8*)p1; }
-        MDT_SCHED_PIN
-    }
-    }
-}
+// (the split schemes, the weight-fragment ring SplitRing and the product loop split_phase: mdt_split_ring.h, which mdt_tiles.h includes)
 
 // LDS bytes of mlp_split_tile at model width D (pair form: two parts -- 67.6 KB for D <= 512 -- + the rows' 32 scale exponents of
 // the first product and the 32 maxima of the hidden rows)
 __host__ __device__ constexpr int mlp_split_lds_bytes(int D, int sch = MDT_SPLIT_BF16X3) {
-    const int P = sch == MDT_SPLIT_F16X2 ? 2 : 3;
+    const int P = split_parts(sch);
     const int xs = P * 32 * (2 * D + 32), hs = P * 32 * (2 * 512 + 32);
     return (xs > hs ? xs : hs) + (sch == MDT_SPLIT_F16X2 ? 256 : 0);
 }
@@ -256,16 +157,9 @@ __device__ __forceinline__ void mlp_split_tile(const mdt_gemm_args& f, const mdt
             if constexpr (PAIR) {
                 const unsigned mx = hmax[i * 16 + (lane & 15)];
                 he[i] = pair_scale_exp(mx);
-                mdt_f16x4 p1, p2;
-                split2_f16(acc1[i][j], pair_scale(mx), p1, p2);
-                *(mdt_f16x4*)q = p1;
-                *(mdt_f16x4*)(q + PART2) = p2;
+                store_split<SCH>(q, PART2, acc1[i][j], pair_scale(mx));
             } else {
-                mdt_bf16x4 p1, p2, p3;
-                split3_bf16(apply_act(acc1[i][j] + b1[j], f.act), p1, p2, p3);
-                *(mdt_bf16x4*)q = p1;
-                *(mdt_bf16x4*)(q + PART2) = p2;
-                *(mdt_bf16x4*)(q + 2 * PART2) = p3;
+                store_split<SCH>(q, PART2, apply_act(acc1[i][j] + b1[j], f.act));
             }
         }
     __syncthreads();
@@ -296,7 +190,7 @@ __device__ __forceinline__ void mlp_split_tile(const mdt_gemm_args& f, const mdt
 // ------------------------------------------------------------------------------------------------
 // Pair form (SCH = MDT_SPLIT_F16X2): the image is a.Wp_pair, LDS = the two-part x tile (51.2 KB at D = 384) + the rows' 32 scale exponents.
 __host__ __device__ constexpr int gemm_ln_split_lds_bytes(int D, int sch = MDT_SPLIT_BF16X3) {
-    return sch == MDT_SPLIT_F16X2 ? 2 * 32 * (2 * D + 32) + 128 : 3 * 32 * (2 * D + 32);
+    return split_parts(sch) * 32 * (2 * D + 32) + (sch == MDT_SPLIT_F16X2 ? 128 : 0);
 }
 template <int ND, int NTW, int PRO, int XP, int SCH = MDT_SPLIT_BF16X3>
 __device__ __forceinline__ void gemm_ln_split_tile(const mdt_gemm_args& a, int by, int bx, char* lds, const float* __restrict__ zeros, int tid) {
@@ -312,7 +206,7 @@ __device__ __forceinline__ void gemm_ln_split_tile(const mdt_gemm_args& a, int b
     const int nt0 = (bx * NWAVES + wave) * NTW;       // N is a multiple of the panel width: every wave has NTW real column tiles
     SplitRing<NTW, R, SCH> ring;
     const char* image = (const char*)(PAIR ? a.Wp_pair : a.Wp_split);
-    int* xexp = (int*)(lds + 2 * PART);               // (pair) scale exponents of the tile's rows
+    int* xexp = (int*)(lds + SS::P * PART);           // (pair) scale exponents of the tile's rows
     ring.open(image, nt0 * SS::tile_stride(K32), SS::tile_stride(K32), lane);
 #pragma unroll
     for (int u = 0; u < R - 1; ++u) ring.request(u, u);

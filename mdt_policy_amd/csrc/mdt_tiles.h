@@ -16,7 +16,7 @@
 
 #include "mdt_internal.h"
 #include "mdt_device.h"
-#include "mdt_split_ring.h"   // SplitRing / split_phase_one: attn_xattn_tile's pair form
+#include "mdt_split_ring.h"   // SplitRing / split_phase: attn_xattn_tile's pair form
 
 // XCD-aware block id: the dispatcher places block b on XCD b % 8 (speed-only assumption); give every XCD a
 // contiguous range of logical tiles so the row tiles it touches stay in its private L2.  Bijective for any n.
@@ -1953,7 +1953,7 @@ __device__ __forceinline__ void xattn_tile(const mdt_xapply_args& a, int b, int 
 //   lds: 16 * (D + 4) + 48 * (D + 16) floats (the attention's rows; afterwards the projected rows + xattn_tile's scratch).
 // PAIR (what the model launches from 768 rows on): the projection on the fp16 pair image a.Wp_pair -- the
 //   attention output gets one power-of-two scale per row (maximum over all 8 heads: ds_max_u32 in front of the barrier) and goes to LDS
-//   as two fp16 parts, ONE more barrier; three v_mfma_f32_16x16x32_f16 per k32 step and column tile (split_phase_one) instead of eight
+//   as two fp16 parts, ONE more barrier; three v_mfma_f32_16x16x32_f16 per k32 step and column tile (split_phase, one row tile) instead of eight
 //   v_mfma_f32_16x16x4_f32, same weight bytes.  Measured at B = 256 (profiles/attn_xattn_pair_bench_ab.txt): 19.92 -> 16.94 us per
 //   launch, 23 040 -> 8 064 MFMA-busy cycles per SIMD, 44.2 k -> 37.2 k cycles per workgroup, sampler call 3.042 -> 2.932 ms (estimated
 //   beforehand: 0.16-0.19 ms; the added barrier + split and ~1 k cycles more in front of the attention's barrier took the rest).
@@ -2066,17 +2066,12 @@ __device__ __forceinline__ void attn_xattn_tile(const mdt_gemm_args& a, const md
         xe = pair_scale_exp(mx);
         const float rs = pair_scale(mx);
 #pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) {
-            mdt_f16x4 p1, p2;
-            split2_f16(ov[nt], rs, p1, p2);
-            char* q = pt + split_slot(lane & 15, wave * HD + 16 * nt + nq, ROWB);
-            *(mdt_f16x4*)q = p1;
-            *(mdt_f16x4*)(q + PARTB) = p2;
-        }
+        for (int nt = 0; nt < NTW; ++nt)
+            store_split<MDT_SPLIT_F16X2>(pt + split_slot(lane & 15, wave * HD + 16 * nt + nq, ROWB), PARTB, ov[nt], rs);
         __syncthreads();
         MDT_TS(2)
         // ---- projection: 16 x D x D as three v_mfma_f32_16x16x32_f16 per k32 step and column tile ----
-        split_phase_one<NTW, K32, RP>(pring, pt, ROWB, PARTB, lane, acc[0]);
+        split_phase<NTW, K32, RP, MDT_SPLIT_F16X2>(pring, pt, ROWB, PARTB, lane, acc);
     } else {
     // ---- projection: 16 x D x D, transposed-form MFMA k-steps on the ring ----
         int kg = 0;

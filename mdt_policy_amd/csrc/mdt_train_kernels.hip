@@ -18,6 +18,7 @@
 #include "mdt_launch.h"
 
 #include "mdt_device.h"
+#include "mdt_split_ring.h"   // split_scheme, the order rule of the split products (k_gemm_tn_split)
 
 // ------------------------------------------------------------------------------------------------
 // packing the TRANSPOSE of a row-major (rows, cols) matrix part into a fragment-packed (N' = cols, K' = K16*16)
@@ -1519,36 +1520,14 @@ hipError_t mdt_launch_narrow_dx(const float* G, const float* W, float* out, int 
     return hipGetLastError();
 }
 
-// out[m][a] = sum_d G[m][d] * WT[a][d]   (A <= 16; wider: k_narrow_out_wide): one wavefront per row m, lanes stride over d
+// out[m][a] = sum_d G[m][d] * WT[a][d]: one wavefront per row m, lanes stride over d.  A <= 16, or WIDE (17 <= A <= 64): blockIdx.y =
+// the 16-column tile a0 / 16 of the result, one wavefront per (row m, column tile), each element summed in the same order
+template <bool WIDE>
 __global__ __launch_bounds__(256) void k_narrow_out(const float* __restrict__ G, int64_t ldg, const float* __restrict__ WT,
                                                     float* __restrict__ out, int M, int A, int D) {
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (m >= M) return;
-    float acc[16];
-#pragma unroll
-    for (int a = 0; a < 16; ++a) acc[a] = 0.f;
-    for (int d = lane; d < D; d += 64) {
-        const float g = G[(int64_t)m * ldg + d];
-#pragma unroll
-        for (int a = 0; a < 16; ++a)
-            if (a < A) acc[a] = fmaf(g, WT[(int64_t)a * D + d], acc[a]);
-    }
-#pragma unroll
-    for (int a = 0; a < 16; ++a) {
-        if (a < A) {
-            const float v = wave_sum(acc[a]);
-            if (lane == 0) out[(int64_t)m * A + a] = v;
-        }
-    }
-}
-// the same for 17 <= A <= 64: blockIdx.y = the 16-column tile a0 / 16 of the result; one wavefront per (row m, column tile), each
-// element summed in k_narrow_out's order
-__global__ __launch_bounds__(256) void k_narrow_out_wide(const float* __restrict__ G, int64_t ldg, const float* __restrict__ WT,
-                                                         float* __restrict__ out, int M, int A, int D) {
-    const int lane = threadIdx.x & 63;
-    const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int a0 = blockIdx.y * 16;
+    const int a0 = WIDE ? blockIdx.y * 16 : 0;
     if (m >= M) return;
     float acc[16];
 #pragma unroll
@@ -1570,54 +1549,23 @@ __global__ __launch_bounds__(256) void k_narrow_out_wide(const float* __restrict
 hipError_t mdt_launch_narrow_out(const float* G, int64_t ldg, const float* WT, float* out, int M, int A, int D, hipStream_t s) {
     if (A < 1 || A > MDT_ACTION_DIM_MAX) return hipErrorInvalidValue;
     if (A > 16) {
-        hipLaunchKernelGGL(k_narrow_out_wide, dim3((M + 3) / 4, (A + 15) / 16), dim3(256), 0, s, G, ldg, WT, out, M, A, D);
+        hipLaunchKernelGGL(k_narrow_out<true>, dim3((M + 3) / 4, (A + 15) / 16), dim3(256), 0, s, G, ldg, WT, out, M, A, D);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_narrow_out, dim3((M + 3) / 4), dim3(256), 0, s, G, ldg, WT, out, M, A, D);
+    hipLaunchKernelGGL(k_narrow_out<false>, dim3((M + 3) / 4), dim3(256), 0, s, G, ldg, WT, out, M, A, D);
     return hipGetLastError();
 }
 
-// partial[y][a][d] = sum_{m in slice y} G[m][a] * Y[m][d]   (A <= 16); summed over y by k_colsum.
+// partial[y][a][d] = sum_{m in slice y} G[m][a] * Y[m][d]; summed over y by k_colsum.  A <= 16, or WIDE (17 <= A <= 64): blockIdx.z =
+// the 16-column tile a0 / 16 of G; every element of `partial` keeps one owner and the same order over the slice's rows.
 //   transposed = 0: rows of the result are a (action_pred.weight (A, D));  1: result stored (D, A) (action_emb.weight)
+template <bool WIDE>
 __global__ __launch_bounds__(256) void k_narrow_dw(const float* __restrict__ G, const float* __restrict__ Y, int64_t ldy,
                                                    float* __restrict__ partial, int M, int A, int D, int transposed) {
+    using index_t = std::conditional_t<WIDE, int64_t, int>;   // of an element of a slice's (A, D) result
     const int d = blockIdx.x * 256 + threadIdx.x;
     const int ny = gridDim.y, y = blockIdx.y;
-    const int m0 = (int)((int64_t)M * y / ny), m1 = (int)((int64_t)M * (y + 1) / ny);
-    float acc[16];
-#pragma unroll
-    for (int a = 0; a < 16; ++a) acc[a] = 0.f;
-    if (d < D) {
-        int m = m0;
-        for (; m + 4 <= m1; m += 4) {  // four rows' loads in flight per trip
-            float yv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) yv[u] = Y[(int64_t)(m + u) * ldy + d];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int a = 0; a < 16; ++a)
-                    if (a < A) acc[a] = fmaf(G[(int64_t)(m + u) * A + a], yv[u], acc[a]);
-        }
-        for (; m < m1; ++m) {
-            const float yv = Y[(int64_t)m * ldy + d];
-#pragma unroll
-            for (int a = 0; a < 16; ++a)
-                if (a < A) acc[a] = fmaf(G[(int64_t)m * A + a], yv, acc[a]);
-        }
-        float* p = partial + (int64_t)y * A * D;
-#pragma unroll
-        for (int a = 0; a < 16; ++a)
-            if (a < A) p[transposed ? d * A + a : a * D + d] = acc[a];
-    }
-}
-// the same for 17 <= A <= 64: blockIdx.z = the 16-column tile a0 / 16 of G; every element of `partial` keeps one owner and
-// k_narrow_dw's order over the slice's rows
-__global__ __launch_bounds__(256) void k_narrow_dw_wide(const float* __restrict__ G, const float* __restrict__ Y, int64_t ldy,
-                                                        float* __restrict__ partial, int M, int A, int D, int transposed) {
-    const int d = blockIdx.x * 256 + threadIdx.x;
-    const int ny = gridDim.y, y = blockIdx.y;
-    const int a0 = blockIdx.z * 16;
+    const int a0 = WIDE ? blockIdx.z * 16 : 0;
     const int m0 = (int)((int64_t)M * y / ny), m1 = (int)((int64_t)M * (y + 1) / ny);
     float acc[16];
 #pragma unroll
@@ -1643,18 +1591,18 @@ __global__ __launch_bounds__(256) void k_narrow_dw_wide(const float* __restrict_
         float* p = partial + (int64_t)y * A * D;
 #pragma unroll
         for (int a = 0; a < 16; ++a)
-            if (a0 + a < A) p[transposed ? (int64_t)d * A + a0 + a : (int64_t)(a0 + a) * D + d] = acc[a];
+            if (a0 + a < A) p[transposed ? (index_t)d * A + a0 + a : (index_t)(a0 + a) * D + d] = acc[a];
     }
 }
 hipError_t mdt_launch_narrow_dw(const float* G, const float* Y, int64_t ldy, float* partial, int n_slices, int M, int A,
                                 int D, int transposed, hipStream_t s) {
     if (A < 1 || A > MDT_ACTION_DIM_MAX) return hipErrorInvalidValue;
     if (A > 16) {
-        hipLaunchKernelGGL(k_narrow_dw_wide, dim3((D + 255) / 256, n_slices, (A + 15) / 16), dim3(256), 0, s, G, Y, ldy, partial, M,
+        hipLaunchKernelGGL(k_narrow_dw<true>, dim3((D + 255) / 256, n_slices, (A + 15) / 16), dim3(256), 0, s, G, Y, ldy, partial, M,
                            A, D, transposed);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_narrow_dw, dim3((D + 255) / 256, n_slices), dim3(256), 0, s, G, Y, ldy, partial, M, A, D,
+    hipLaunchKernelGGL(k_narrow_dw<false>, dim3((D + 255) / 256, n_slices), dim3(256), 0, s, G, Y, ldy, partial, M, A, D,
                        transposed);
     return hipGetLastError();
 }
@@ -2328,7 +2276,7 @@ __global__ __launch_bounds__(TNW == 2 ? 512 : 384) void k_gemm_tn_split(const fl
                                                        float* __restrict__ out, int64_t slice_stride, int M, int N, int K, int L,
                                                        int accumulate, float* __restrict__ bpart, int xcd) {
     constexpr int NWV = TNW == 2 ? 8 : 6, NTH = 64 * NWV, WKG = NWV / TNW;   // waves, threads, k groups
-    constexpr int CM = 32, TN_ = 64 * TNW, TK = 16 * KTW * WKG, NC = TN_ + TK, S = 80, PART = NC * S, BUF = 3 * PART;
+    constexpr int CM = 32, TN_ = 64 * TNW, TK = 16 * KTW * WKG, NC = TN_ + TK, S = 80, PART = NC * S, BUF = split_scheme<MDT_SPLIT_BF16X3>::P * PART;
     constexpr int NQ = NC / 4, NI = NQ * 8, NU = (NI + NTH - 1) / NTH;   // column quads, staging items (quad, 4-row group), items per thread
     extern __shared__ __attribute__((aligned(16))) char tns_lds[];      // 2 buffers x 3 parts x NC columns x 80 bytes
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wk = wave % WKG, wn = wave / WKG;
@@ -2422,7 +2370,7 @@ __global__ __launch_bounds__(TNW == 2 ? 512 : 384) void k_gemm_tn_split(const fl
 #pragma unroll
             for (int j = 0; j < 4; ++j) yf[p][j] = *(const mdt_bf16x8*)(cur + p * PART + yoff + 16 * j * S);
         }
-        // the six products, smallest first: x3 y1, x2 y2, x2 y1, x1 y3, x1 y2, x1 y1
+        // the six products in the order of mdt_split_ring.h's rule, written out (both operands whole in registers: no reloads)
 #define MDT_TNS_PROD(PX, PY)                                                                                          \
     _Pragma("unroll") for (int i = 0; i < KTW; ++i)                                                                    \
         _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                  \

@@ -245,7 +245,7 @@ __device__ __forceinline__ void gemm_ws_split_tile(const mdt_gemm_args& a, int p
     static_assert(GLU != 3 || NTW % 2 == 0, "SwishGLU forward pairs tiles");
     static_assert(GLU != 1 || NTW == 1, "the activation hooks are written for one column tile");
     constexpr int K = K16 * 16, K32 = K16 / 2, K4 = K / 4, NT = 64 * NWAVES;
-    constexpr int ROWB = 2 * K + 32, PART = 32 * ROWB, TILEB = 3 * PART;       // bytes; + 32: ds_read_b128's 16-lane groups hit 64 banks
+    constexpr int ROWB = 2 * K + 32, PART = 32 * ROWB, TILEB = split_scheme<MDT_SPLIT_BF16X3>::P * PART;   // bytes; + 32: ds_read_b128's 16-lane groups hit 64 banks
     constexpr int NLD = (32 * K4 + NT - 1) / NT;
     static_assert(NLD <= K32, "one staged item per k32 step");
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -364,9 +364,8 @@ __device__ __forceinline__ void gemm_ws_split_tile(const mdt_gemm_args& a, int p
         }
 #pragma unroll
         for (int kk = 0; kk < K32; ++kk) {
-            // the six products of this k32 step, smallest first, row and column tiles alternating (a dependent MFMA sits at least two
-            // issue slots behind its producer); each part of the next step is read into the registers of this step's right behind its
-            // last use, so no second operand set is live (256 registers hold the 144 of the weights, the staged tile and this)
+            // one k32 step by the order rule of mdt_split_ring.h, hand-unrolled on the register-resident weights with this body's own
+            // loads behind the reloads (256 registers hold the 144 of the weights, the staged tile and one operand set)
             const bool nx = kk + 1 < K32;
             const char* p0 = cur + aoff + (kk + 1) * 64;
             const char* p1 = p0 + 16 * ROWB;
