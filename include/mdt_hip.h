@@ -60,7 +60,9 @@ typedef struct {
     int32_t action_dim;           /* 1..64 (17..64: the tiled action head and narrow gradients)     */
     int32_t obs_dim;              /* multiple of 16                                                 */
     int32_t goal_dim;             /* multiple of 16                                                 */
-    int32_t n_obs_token;          /* MDT-V: state tokens per sample (3); MDT: ignored (static+gripper) */
+    int32_t n_obs_token;          /* MDT-V: state tokens per sample (3); MDT: ignored (static+gripper).  The context is
+                                   * [sigma token] + goal + n_obs_token + [proprio token]: 1..16 tokens, 17..64 at head
+                                   * dim 32 / 48 / 64 */
     int32_t goal_seq_len;         /* 1                                                              */
     int32_t action_seq_len;       /* Ta <= 16; 17..64 at head dim 32 / 48 / 64                      */
     int32_t use_mlp_goal;         /* goal_emb / lang_emb are Linear-GELU-Linear                     */
@@ -143,7 +145,11 @@ int64_t mdt_ws_generation(const mdt_model *m);
  *   goal   : (B, 1, goal_dim)
  *   honour_modality: 1 = pick lang_emb when modality==LANG (MDT-V always; MDT forward_enc_only),
  *                    0 = always goal_emb (MDT.forward -> enc_only_forward, mdt_transformer.py:215)
- *   ctx_out: (B, Te, d) or NULL -- the value the reference caches as inner_model.latent_encoder_emb */
+ *   ctx_out: (B, Te, d) or NULL -- the value the reference caches as inner_model.latent_encoder_emb
+ * Te = [sigma token] + goal + state tokens + [proprio token] <= 64 (above 16: head dim 32 / 48 / 64).  The decoder's
+ * cross-attention is causal on its Ta x Te score matrix, top-left aligned: query row t sees context rows j <= t, so rows
+ * j >= Ta reach the decoder only through the encoder's self-attention (as in the reference), and above 16 tokens the
+ * cross-attention launches stage the first min(Ta, Te) K / V rows of a sample only. */
 mdt_status mdt_encode(mdt_model *m, const float *tokens, const float *tokens2, const float *goal,
                       int32_t modality, int32_t honour_modality, const float *sigma, int64_t batch,
                       float *ctx_out, void *stream);

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "mdt_hip.h"
 #include "mdt_hip_ops.h"
+#include "mdt_hip_train.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -70,6 +71,21 @@ void mdt_op_set_attn_wide_min(int32_t rows);
  * ctx_div consecutive ones share a context, so sample b reads the k / v rows of context b / ctx_div (k / v hold B / ctx_div * Tk
  * rows; B a multiple of ctx_div).  ctx_div = 1 is mdt_op_attention. */
 mdt_status mdt_op_attention_shared(const mdt_attn_args *args, int32_t ctx_div, void *stream);
+/* The three attention ops as the decoder's cross-attention launches them at contexts above 16 tokens: a causal launch (top-left
+ * aligned mask) with Tk > 16 stages and multiplies its first kv_rows keys only, min(Tq, Tk) <= kv_rows < Tk -- the keys some query
+ * sees.  Tk stays the k / v sample stride (sample b's rows start at row b * Tk) and the row length of the dropout index
+ * ((b H + h) Tq + i) Tk + j; k / v rows kv_rows .. Tk-1 are never read, and the backward writes rows kv_rows .. Tk-1 of dk / dv as
+ * zeros (accumulate_kv: leaves them as they are).  Results equal the full-key launch's.  kv_rows = 0 or Tk is that launch:
+ * mdt_op_attention_shared, mdt_op_attn_fwd_train, mdt_op_attn_bwd.  Anything else: MDT_ERR_INVALID_ARG. */
+mdt_status mdt_op_attention_prefix(const mdt_attn_args *args, int32_t ctx_div, int32_t kv_rows, void *stream);
+mdt_status mdt_op_attn_fwd_train_prefix(const mdt_attn_train_args *args, int32_t kv_rows, void *stream);
+mdt_status mdt_op_attn_bwd_prefix(const mdt_attn_bwd_args *args, int32_t kv_rows, void *stream);
+/* Bytes of dynamic LDS one workgroup of the attention kernels for Tq or Tk above 16 takes (one workgroup per (sample, head); the
+ * launch is refused above 160 KiB).  With T16 = T rounded up to a multiple of 16 and Tv = the keys the launch stages (kv_rows; Tk
+ * without a prefix):
+ *   forward   4 [(Tq16 + Tv16)(hd + 4) + hd (Tv16 + 4)]
+ *   backward  4 [(2 Tq16 + 2 Tv16)(hd + 4) + 2 Tq16 (Tv16 + 4)]  */
+int64_t mdt_op_attn_chunk_lds(int32_t hd, int32_t Tq, int32_t kv_rows, int32_t bwd);
 
 /* Measurement hook: bracket every fused-MLP launch of the model-level calls that follow (mdt_sample_ddim, mdt_forward, ...)
  * with a pair of HIP events on its stream; mdt_op_trace_mlp_read waits for them, writes up to `cap` durations in

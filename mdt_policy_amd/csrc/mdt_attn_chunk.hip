@@ -1,8 +1,12 @@
 // mdt_attn_chunk.hip -- softmax attention of action chunks of 17 .. 64 rows: the three kernels behind mdt_launch_attention,
 // mdt_launch_attn_fwd_train and mdt_launch_attn_bwd once max(Tq, Tk) > 16 (at most 16 rows keep their own kernels, bit for bit).
 //
-// Shapes: Tq, Tk <= 64, head dim 32 / 48 / 64 -- the decoder's causal self-attention (Tq = Tk = Ta) and its explicit
-// cross-attention (Tq = Ta, Tk = Te <= 16; the causal mask is top-left aligned, so a query row i >= Tk sees every key).
+// Shapes: Tq, Tk <= 64, head dim 32 / 48 / 64 -- the decoder's causal self-attention (Tq = Tk = Ta), the encoder's
+// non-causal one (Tq = Tk = Te) and the decoder's explicit cross-attention (Tq = Ta, Tk = Te; the causal mask is top-left
+// aligned, so a query row i >= Tk sees every key and no query sees a key j >= Tq).
+// The visible prefix (Tv): a causal launch whose keys j >= Tv = min(Tq, Tk) no query sees stages, sizes its LDS by and multiplies
+// the first Tv keys only.  Tk stays the K / V sample stride (b * Tk rows) and the row length of the dropout index
+// ((b H + h) Tq + i) Tk + j; the backward writes dk / dv rows Tv .. Tk-1 as zeros (accumulate_kv: leaves them as they are).
 // One workgroup of four waves per (sample, head); wave w owns the 16-row QUERY tile w.  Everything is 16 x 16 tiles of
 // v_mfma_f32_16x16x4_f32 on fp32 operands staged in LDS, modelled on k_attn_mid_fwd2 / k_attn_mid_bwd (mdt_mae.hip):
 //   forward   scores TRANSPOSED (keys as the row operand, queries as the column operand), so that the accumulator of key tile tj,
@@ -10,9 +14,9 @@
 //             dropout multipliers) stay in registers.  Causal: key tiles above the diagonal are skipped (wave uniform), the
 //             diagonal tile is masked per element.  V sits transposed in LDS.
 //   backward  P is recomputed the same way, dP = dO V^T beside it; (m P) and dS = P (m dP - delta) scale go through two
-//             Tq16 x Tk16 LDS matrices once, then dQ = dS K, dV = (m P)^T dO and dK = dS^T Q are row tiles dealt to the waves.
+//             Tq16 x Tv16 LDS matrices once, then dQ = dS K, dV = (m P)^T dO and dK = dS^T Q are row tiles dealt to the waves.
 //             RoPE is rotated back on the accumulators (a pair's two columns sit in neighbouring lanes).
-// Rows / keys past Tq / Tk inside the last tile are zero in LDS and masked in the softmax; their addresses are never formed.
+// Rows / keys past Tq / Tv inside the last tile are zero in LDS and masked in the softmax; their addresses are never formed.
 // No atomics: every output element has one owner, results repeat bit for bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -42,7 +46,7 @@ __device__ __forceinline__ f32x4 rope4(f32x4 v, const float* __restrict__ rc, co
 // Four loads per thread are requested from clamped rows before the first is consumed.
 // Item i -> (row t, float4 column c): row major for the row layout (a wave reads whole rows); for TRANS 16 consecutive lanes take
 // 16 consecutive rows of one column and the next 16 lanes the next column, so that a wave's four-byte stores of one feature go to
-// 64 different banks (the column pitch 4 vs is 16 banks for every vs = Tk16 + 4) while a row still gives 64 contiguous bytes.
+// 64 different banks (the column pitch 4 vs is 16 banks for every vs = Tv16 + 4) while a row still gives 64 contiguous bytes.
 template <int H4, bool TRANS>
 __device__ __forceinline__ void stage_item(int i, int& t, int& c) {
     if (TRANS) {
@@ -168,6 +172,7 @@ struct chunk_fwd_args {
     const float* k; const float* v; int64_t ldkv;
     float* out; int64_t ldo;
     int32_t H, Tq, Tk, causal, ctx_div;
+    int32_t Tv;                         // keys staged and multiplied (<= Tk; keys Tv .. Tk-1 are ones no query sees)
     const float *rc, *rs;               // rotary tables or nullptr
     float p; uint32_t site; uint64_t seed;
 };
@@ -179,13 +184,13 @@ __global__ __launch_bounds__(CHUNK_NT) void k_attn_chunk_fwd(chunk_fwd_args a, f
     constexpr int ST = HD + 4, C16 = HD / 16;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, g = lane >> 4;
     const int b = blockIdx.x, h = blockIdx.y, bkv = a.ctx_div > 1 ? b / a.ctx_div : b;
-    const int Tq = a.Tq, Tk = a.Tk, Tq16 = (Tq + 15) & ~15, Tk16 = (Tk + 15) & ~15, nq = Tq16 >> 4, nk = Tk16 >> 4, VS = Tk16 + 4;
+    const int Tq = a.Tq, Tk = a.Tk, Tv = a.Tv, Tq16 = (Tq + 15) & ~15, Tv16 = (Tv + 15) & ~15, nq = Tq16 >> 4, nk = Tv16 >> 4, VS = Tv16 + 4;
     float* qs = lds;                 // [Tq16][ST]
-    float* ks = qs + Tq16 * ST;      // [Tk16][ST]
-    float* vt = ks + Tk16 * ST;      // [HD][VS]: V transposed
+    float* ks = qs + Tq16 * ST;      // [Tv16][ST]
+    float* vt = ks + Tv16 * ST;      // [HD][VS]: V transposed
     stage_rows<HD, false>(a.q + (int64_t)b * Tq * a.ldq + h * HD, a.ldq, Tq, Tq16, qs, 0, a.rc, a.rs, tid);
-    stage_rows<HD, false>(a.k + (int64_t)bkv * Tk * a.ldkv + h * HD, a.ldkv, Tk, Tk16, ks, 0, a.rc, a.rs, tid);
-    stage_rows<HD, true>(a.v + (int64_t)bkv * Tk * a.ldkv + h * HD, a.ldkv, Tk, Tk16, vt, VS, nullptr, nullptr, tid);
+    stage_rows<HD, false>(a.k + (int64_t)bkv * Tk * a.ldkv + h * HD, a.ldkv, Tv, Tv16, ks, 0, a.rc, a.rs, tid);
+    stage_rows<HD, true>(a.v + (int64_t)bkv * Tk * a.ldkv + h * HD, a.ldkv, Tv, Tv16, vt, VS, nullptr, nullptr, tid);
     __syncthreads();
     const int ti = wave;
     if (ti >= nq) return;   // (no barrier below)
@@ -196,7 +201,7 @@ __global__ __launch_bounds__(CHUNK_NT) void k_attn_chunk_fwd(chunk_fwd_args a, f
     for (int c = 0; c < C16; ++c) qv[c] = *(const f32x4*)(qs + qi * ST + 16 * c + 4 * g);
     f32x4 pr[CHUNK_TILES];
     float inv;
-    chunk_probs<HD, false>(qv, ks, nkv, qi, Tk, a.causal != 0, sl2, m, g, pr, &inv);
+    chunk_probs<HD, false>(qv, ks, nkv, qi, Tv, a.causal != 0, sl2, m, g, pr, &inv);
     if (DROP) {
         const uint64_t base = (((uint64_t)b * a.H + h) * Tq + min(qi, Tq - 1)) * Tk;
 #pragma unroll
@@ -291,23 +296,23 @@ __device__ __forceinline__ void store_tile(f32x4 (&v)[HD / 16], float* dst, int6
 
 // backward: P is recomputed from q, k (nothing but the forward's inputs is read); dQ, dK, dV each written by one owner
 template <int HD, bool DROP>
-__global__ __launch_bounds__(CHUNK_NT) void k_attn_chunk_bwd(mdt_attn_bwd_args a, float scale) {
+__global__ __launch_bounds__(CHUNK_NT) void k_attn_chunk_bwd(mdt_attn_bwd_args a, float scale, int Tv) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int ST = HD + 4, C16 = HD / 16;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, m = lane & 15, g = lane >> 4;
     const int b = blockIdx.x, h = blockIdx.y;
-    const int Tq = a.Tq, Tk = a.Tk, Tq16 = (Tq + 15) & ~15, Tk16 = (Tk + 15) & ~15, nq = Tq16 >> 4, nk = Tk16 >> 4, SS = Tk16 + 4;
+    const int Tq = a.Tq, Tk = a.Tk, Tq16 = (Tq + 15) & ~15, Tv16 = (Tv + 15) & ~15, nq = Tq16 >> 4, nk = Tv16 >> 4, SS = Tv16 + 4;
     float* qs = lds;                  // [Tq16][ST] (rotated)
-    float* ks = qs + Tq16 * ST;       // [Tk16][ST] (rotated)
-    float* vs = ks + Tk16 * ST;       // [Tk16][ST]
-    float* os = vs + Tk16 * ST;       // [Tq16][ST]: dO
+    float* ks = qs + Tq16 * ST;       // [Tv16][ST] (rotated)
+    float* vs = ks + Tv16 * ST;       // [Tv16][ST]
+    float* os = vs + Tv16 * ST;       // [Tq16][ST]: dO
     float* Pm = os + Tq16 * ST;       // [Tq16][SS]: what multiplied V in the forward
     float* dS = Pm + Tq16 * SS;       // [Tq16][SS]
     const float* rc = a.rope ? a.rope_cos : nullptr;
     const float* rs = a.rope ? a.rope_sin : nullptr;
     stage_rows<HD, false>(a.q + (int64_t)b * Tq * a.ldq + h * HD, a.ldq, Tq, Tq16, qs, 0, rc, rs, tid);
-    stage_rows<HD, false>(a.k + (int64_t)b * Tk * a.ldkv + h * HD, a.ldkv, Tk, Tk16, ks, 0, rc, rs, tid);
-    stage_rows<HD, false>(a.v + (int64_t)b * Tk * a.ldkv + h * HD, a.ldkv, Tk, Tk16, vs, 0, nullptr, nullptr, tid);
+    stage_rows<HD, false>(a.k + (int64_t)b * Tk * a.ldkv + h * HD, a.ldkv, Tv, Tv16, ks, 0, rc, rs, tid);
+    stage_rows<HD, false>(a.v + (int64_t)b * Tk * a.ldkv + h * HD, a.ldkv, Tv, Tv16, vs, 0, nullptr, nullptr, tid);
     stage_rows<HD, false>(a.d_out + (int64_t)b * Tq * a.ld_do + h * HD, a.ld_do, Tq, Tq16, os, 0, nullptr, nullptr, tid);
     __syncthreads();
     if (wave < nq) {
@@ -321,7 +326,7 @@ __global__ __launch_bounds__(CHUNK_NT) void k_attn_chunk_bwd(mdt_attn_bwd_args a
         }
         f32x4 pr[CHUNK_TILES], dp[CHUNK_TILES], mk[CHUNK_TILES];
         float inv;
-        chunk_probs<HD, true>(qv, ks, nkv, qi, Tk, a.causal != 0, scale * LOG2E, m, g, pr, &inv);
+        chunk_probs<HD, true>(qv, ks, nkv, qi, Tv, a.causal != 0, scale * LOG2E, m, g, pr, &inv);
         const uint64_t base = (((uint64_t)b * a.H + h) * Tq + min(qi, Tq - 1)) * Tk;
         float part = 0.f;
 #pragma unroll
@@ -353,6 +358,16 @@ __global__ __launch_bounds__(CHUNK_NT) void k_attn_chunk_bwd(mdt_attn_bwd_args a
         }
     }
     __syncthreads();
+    // the keys no query sees (rows Tv .. Tk-1 of dk and dv): zeros, each float4 written by one thread
+    if (Tv < Tk && !a.accumulate_kv) {
+        constexpr int H4 = HD / 4;
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        for (int i = tid; i < (Tk - Tv) * H4; i += CHUNK_NT) {
+            const int64_t off = ((int64_t)b * Tk + Tv + i / H4) * a.ld_dkv + h * HD + 4 * (i % H4);
+            *(f32x4*)(a.dk + off) = z;
+            *(f32x4*)(a.dv + off) = z;
+        }
+    }
     // row tiles dealt to the waves: dQ = dS K (nq tiles), dV = (m P)^T dO and dK = dS^T Q (nk tiles each)
     for (int it = wave; it < nq + 2 * nk; it += CHUNK_NT / 64) {
         f32x4 acc[C16];
@@ -361,19 +376,21 @@ __global__ __launch_bounds__(CHUNK_NT) void k_attn_chunk_bwd(mdt_attn_bwd_args a
             store_tile<HD>(acc, a.dq + (int64_t)b * Tq * a.ld_dq + h * HD, a.ld_dq, Tq, it, m, g, rc, rs, false);
         } else if (it < nq + nk) {
             rows_tile<HD, true>(Pm, SS, os, nq, it - nq, m, g, acc);
-            store_tile<HD>(acc, a.dv + (int64_t)b * Tk * a.ld_dkv + h * HD, a.ld_dkv, Tk, it - nq, m, g, nullptr, nullptr, a.accumulate_kv != 0);
+            store_tile<HD>(acc, a.dv + (int64_t)b * Tk * a.ld_dkv + h * HD, a.ld_dkv, Tv, it - nq, m, g, nullptr, nullptr, a.accumulate_kv != 0);
         } else {
             rows_tile<HD, true>(dS, SS, qs, nq, it - nq - nk, m, g, acc);
-            store_tile<HD>(acc, a.dk + (int64_t)b * Tk * a.ld_dkv + h * HD, a.ld_dkv, Tk, it - nq - nk, m, g, rc, rs, a.accumulate_kv != 0);
+            store_tile<HD>(acc, a.dk + (int64_t)b * Tk * a.ld_dkv + h * HD, a.ld_dkv, Tv, it - nq - nk, m, g, rc, rs, a.accumulate_kv != 0);
         }
     }
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+int prefix_of(int Tk, int kv_rows) { return kv_rows > 0 ? kv_rows : Tk; }   // keys staged: kv_rows = 0 means every key
+
 template <int HD>
 hipError_t launch_fwd(const chunk_fwd_args& a, int B, hipStream_t s) {
-    const size_t lds = mdt_attn_chunk_lds(HD, a.Tq, a.Tk, false);
+    const size_t lds = mdt_attn_chunk_lds(HD, a.Tq, a.Tv, false);
     const float sl2 = LOG2E / sqrtf((float)HD);
     if (a.p > 0.f && a.seed != 0) return mdt_launch_lds<k_attn_chunk_fwd<HD, true>>(dim3(B, a.H), dim3(CHUNK_NT), lds, s, a, sl2);
     return mdt_launch_lds<k_attn_chunk_fwd<HD, false>>(dim3(B, a.H), dim3(CHUNK_NT), lds, s, a, sl2);
@@ -381,8 +398,9 @@ hipError_t launch_fwd(const chunk_fwd_args& a, int B, hipStream_t s) {
 
 hipError_t chunk_fwd(const chunk_fwd_args& a, int B, int hd, hipStream_t s) {
     if (!mdt_attn_chunk_supported(hd, a.Tq, a.Tk) || B < 1 || a.H < 1 || a.H > 65535 || a.ctx_div < 1) return hipErrorInvalidValue;
+    if (!mdt_prefix_rows_ok(a.Tq, a.Tk, a.causal, a.Tv)) return hipErrorInvalidValue;
     if (((a.ldq | a.ldkv | a.ldo) & 3) || !aligned16(a.q) || !aligned16(a.k) || !aligned16(a.v) || !aligned16(a.out)) return hipErrorInvalidValue;
-    if (mdt_attn_chunk_lds(hd, a.Tq, a.Tk, false) > 160 * 1024) return hipErrorInvalidValue;
+    if (mdt_attn_chunk_lds(hd, a.Tq, a.Tv, false) > 160 * 1024) return hipErrorInvalidValue;
     switch (hd) {
         case 32: return launch_fwd<32>(a, B, s);
         case 48: return launch_fwd<48>(a, B, s);
@@ -391,57 +409,71 @@ hipError_t chunk_fwd(const chunk_fwd_args& a, int B, int hd, hipStream_t s) {
 }
 
 template <int HD>
-hipError_t launch_bwd(const mdt_attn_bwd_args& a, hipStream_t s) {
-    const size_t lds = mdt_attn_chunk_lds(HD, a.Tq, a.Tk, true);
+hipError_t launch_bwd(const mdt_attn_bwd_args& a, int Tv, hipStream_t s) {
+    const size_t lds = mdt_attn_chunk_lds(HD, a.Tq, Tv, true);
     const float scale = 1.0f / sqrtf((float)HD);
-    if (a.p > 0.f && a.seed != 0) return mdt_launch_lds<k_attn_chunk_bwd<HD, true>>(dim3(a.B, a.H), dim3(CHUNK_NT), lds, s, a, scale);
-    return mdt_launch_lds<k_attn_chunk_bwd<HD, false>>(dim3(a.B, a.H), dim3(CHUNK_NT), lds, s, a, scale);
+    if (a.p > 0.f && a.seed != 0) return mdt_launch_lds<k_attn_chunk_bwd<HD, true>>(dim3(a.B, a.H), dim3(CHUNK_NT), lds, s, a, scale, Tv);
+    return mdt_launch_lds<k_attn_chunk_bwd<HD, false>>(dim3(a.B, a.H), dim3(CHUNK_NT), lds, s, a, scale, Tv);
 }
 
 }  // namespace
+
+// kv_rows a launch may stage: every key (0 or Tk), or a causal launch's prefix that holds every key some query sees -- key j is
+// seen by the queries i >= j only, so j < min(Tq, Tk) -- at Tk > 16 (the 16-row kernels have no such form)
+bool mdt_prefix_rows_ok(int Tq, int Tk, int causal, int kv_rows) {
+    return kv_rows == 0 || kv_rows == Tk || (causal && Tk > 16 && kv_rows >= (Tq < Tk ? Tq : Tk) && kv_rows < Tk);
+}
 
 bool mdt_attn_chunk_supported(int hd, int Tq, int Tk) {
     return (hd == 32 || hd == 48 || hd == 64) && Tq >= 1 && Tk >= 1 && Tq <= CHUNK_T && Tk <= CHUNK_T;
 }
 
-// bytes of dynamic LDS of the forward (q, k, V^T) or the backward (q, k, v, dO and the two Tq16 x Tk16 matrices)
-size_t mdt_attn_chunk_lds(int hd, int Tq, int Tk, bool bwd) {
-    const size_t Tq16 = (size_t)((Tq + 15) & ~15), Tk16 = (size_t)((Tk + 15) & ~15), st = (size_t)hd + 4;
-    if (bwd) return ((2 * Tq16 + 2 * Tk16) * st + 2 * Tq16 * (Tk16 + 4)) * sizeof(float);
-    return ((Tq16 + Tk16) * st + (size_t)hd * (Tk16 + 4)) * sizeof(float);
+// bytes of dynamic LDS of the forward (q, k, V^T) or the backward (q, k, v, dO and the two Tq16 x Tv16 matrices); Tv: the keys
+// the launch stages -- Tk, or the visible prefix
+size_t mdt_attn_chunk_lds(int hd, int Tq, int Tv, bool bwd) {
+    const size_t Tq16 = (size_t)((Tq + 15) & ~15), Tv16 = (size_t)((Tv + 15) & ~15), st = (size_t)hd + 4;
+    if (bwd) return ((2 * Tq16 + 2 * Tv16) * st + 2 * Tq16 * (Tv16 + 4)) * sizeof(float);
+    return ((Tq16 + Tv16) * st + (size_t)hd * (Tv16 + 4)) * sizeof(float);
 }
 
-hipError_t mdt_launch_attn_chunk(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s, int ctx_div) {
+// test hook (mdt_hip_debug.h)
+extern "C" int64_t mdt_op_attn_chunk_lds(int32_t hd, int32_t Tq, int32_t kv_rows, int32_t bwd) {
+    return (int64_t)mdt_attn_chunk_lds(hd, Tq, kv_rows, bwd != 0);
+}
+
+hipError_t mdt_launch_attn_chunk(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s, int ctx_div, int kv_rows) {
     if (a.rope && (!rope_cos || !rope_sin)) return hipErrorInvalidValue;
     chunk_fwd_args f;
     memset(&f, 0, sizeof f);
     f.q = a.q; f.ldq = a.ldq; f.k = a.k; f.v = a.v; f.ldkv = a.ldkv; f.out = a.out; f.ldo = a.ldo;
-    f.H = a.H; f.Tq = a.Tq; f.Tk = a.Tk; f.causal = a.causal; f.ctx_div = ctx_div;
+    f.H = a.H; f.Tq = a.Tq; f.Tk = a.Tk; f.causal = a.causal; f.ctx_div = ctx_div; f.Tv = prefix_of(a.Tk, kv_rows);
     f.rc = a.rope ? rope_cos : nullptr; f.rs = a.rope ? rope_sin : nullptr;
     return chunk_fwd(f, a.B, a.hd, s);
 }
 
-hipError_t mdt_launch_attn_chunk_fwd_train(const mdt_attn_train_args& a, hipStream_t s) {
+hipError_t mdt_launch_attn_chunk_fwd_train(const mdt_attn_train_args& a, hipStream_t s, int kv_rows) {
     if (a.rope && (!a.rope_cos || !a.rope_sin)) return hipErrorInvalidValue;
     chunk_fwd_args f;
     memset(&f, 0, sizeof f);
     f.q = a.q; f.ldq = a.ldq; f.k = a.k; f.v = a.v; f.ldkv = a.ldkv; f.out = a.out; f.ldo = a.ldo;
-    f.H = a.H; f.Tq = a.Tq; f.Tk = a.Tk; f.causal = a.causal; f.ctx_div = 1;
+    f.H = a.H; f.Tq = a.Tq; f.Tk = a.Tk; f.causal = a.causal; f.ctx_div = 1; f.Tv = prefix_of(a.Tk, kv_rows);
     f.rc = a.rope ? a.rope_cos : nullptr; f.rs = a.rope ? a.rope_sin : nullptr;
     f.p = a.p; f.site = a.site; f.seed = a.seed;
     return chunk_fwd(f, a.B, a.hd, s);
 }
 
-hipError_t mdt_launch_attn_chunk_bwd(const mdt_attn_bwd_args& a, hipStream_t s) {
+hipError_t mdt_launch_attn_chunk_bwd(const mdt_attn_bwd_args& a, hipStream_t s, int kv_rows) {
+    const int Tv = prefix_of(a.Tk, kv_rows);
     if (!mdt_attn_chunk_supported(a.hd, a.Tq, a.Tk) || a.B < 1 || a.H < 1 || a.H > 65535) return hipErrorInvalidValue;
+    if (!mdt_prefix_rows_ok(a.Tq, a.Tk, a.causal, Tv)) return hipErrorInvalidValue;
     if (((a.ldq | a.ld_do | a.ldkv | a.ld_dq | a.ld_dkv) & 3) || !aligned16(a.q) || !aligned16(a.k) || !aligned16(a.v) || !aligned16(a.d_out) ||
         !aligned16(a.dq) || !aligned16(a.dk) || !aligned16(a.dv))
         return hipErrorInvalidValue;
     if (a.rope && (!a.rope_cos || !a.rope_sin)) return hipErrorInvalidValue;
-    if (mdt_attn_chunk_lds(a.hd, a.Tq, a.Tk, true) > 160 * 1024) return hipErrorInvalidValue;
+    if (mdt_attn_chunk_lds(a.hd, a.Tq, Tv, true) > 160 * 1024) return hipErrorInvalidValue;
     switch (a.hd) {
-        case 32: return launch_bwd<32>(a, s);
-        case 48: return launch_bwd<48>(a, s);
-        default: return launch_bwd<64>(a, s);
+        case 32: return launch_bwd<32>(a, Tv, s);
+        case 48: return launch_bwd<48>(a, Tv, s);
+        default: return launch_bwd<64>(a, Tv, s);
     }
 }

@@ -124,15 +124,20 @@ hipError_t mdt_launch_split_from_packed(const float* wp, int N, int K, void* ima
 // ctx_div (here and in the three cross-attention launchers below; 1 = the plain launch): the launch's a.B samples are decoder
 // samples of which ctx_div consecutive ones share a context -- the candidates of a sampler call -- so sample b reads the k / v
 // rows (the folded operands U, Wf, c) of context b / ctx_div.  The public argument structs keep their layout.
-hipError_t mdt_launch_attention(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s, int ctx_div = 1);
+// kv_rows (here and in mdt_launch_attn_fwd_train / mdt_launch_attn_bwd; 0 or a.Tk = every key): a causal launch with Tk > 16 stages
+// and multiplies its first kv_rows >= min(Tq, Tk) keys only -- the keys some query sees under the top-left aligned mask; a.Tk stays
+// the K / V sample stride and the row length of the dropout index, and the backward leaves dk / dv rows kv_rows .. Tk-1 zero.
+hipError_t mdt_launch_attention(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s, int ctx_div = 1,
+                                int kv_rows = 0);
 // chunks of 17 .. 64 rows (mdt_attn_chunk.hip): where mdt_launch_attention, mdt_launch_attn_fwd_train and mdt_launch_attn_bwd go
 // once max(Tq, Tk) > 16 -- head dim 32 / 48 / 64, Tq, Tk <= 64; rotary tables of max(Tq, Tk) positions x 16 frequencies
+bool mdt_prefix_rows_ok(int Tq, int Tk, int causal, int kv_rows);   // the kv_rows the launchers (and the *_prefix hooks of mdt_hip_debug.h) accept
 constexpr int MDT_ROPE_POSITIONS = 64;   // rows of a handle's rotary tables
 bool mdt_attn_chunk_supported(int hd, int Tq, int Tk);
-size_t mdt_attn_chunk_lds(int hd, int Tq, int Tk, bool bwd);   // bytes of dynamic LDS of one workgroup
-hipError_t mdt_launch_attn_chunk(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s, int ctx_div);
-hipError_t mdt_launch_attn_chunk_fwd_train(const mdt_attn_train_args& a, hipStream_t s);
-hipError_t mdt_launch_attn_chunk_bwd(const mdt_attn_bwd_args& a, hipStream_t s);
+size_t mdt_attn_chunk_lds(int hd, int Tq, int Tv, bool bwd);   // bytes of dynamic LDS of one workgroup; Tv = the keys it stages
+hipError_t mdt_launch_attn_chunk(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s, int ctx_div, int kv_rows = 0);
+hipError_t mdt_launch_attn_chunk_fwd_train(const mdt_attn_train_args& a, hipStream_t s, int kv_rows = 0);
+hipError_t mdt_launch_attn_chunk_bwd(const mdt_attn_bwd_args& a, hipStream_t s, int kv_rows = 0);
 // one sample's self-attention fused into its output projection p (rollout batch 1); see mdt_kernels.hip
 bool mdt_attn_proj_supported(const mdt_gemm_args& p, int H, int hd, int T, int rope);
 hipError_t mdt_launch_attn_proj(const mdt_gemm_args& p, const float* qkv, int64_t ldq, int H, int hd, int T, int causal,
@@ -298,7 +303,7 @@ hipError_t mdt_launch_act_fwd(const float* u, float* out, int64_t n, int act, hi
 hipError_t mdt_launch_act_bwd(const float* u, const float* dy, float* du, int64_t n, int act, hipStream_t s);
 hipError_t mdt_launch_merge_fwd(const mdt_merge_args& a, hipStream_t s);
 hipError_t mdt_launch_merge_bwd(const mdt_merge_args& a, hipStream_t s);
-hipError_t mdt_launch_attn_fwd_train(const mdt_attn_train_args& a, hipStream_t s);
+hipError_t mdt_launch_attn_fwd_train(const mdt_attn_train_args& a, hipStream_t s, int kv_rows = 0);
 hipError_t mdt_launch_colsum(const float* X, int64_t ldx, int M, int N, float* out, int accumulate, hipStream_t s);
 // a table of independent column sums run as one launch: dst[n] (+)= sum_m src[m * ld + n], m < M, n < N
 struct mdt_colsum_entry {
@@ -310,7 +315,7 @@ struct mdt_colsum_entry {
 enum { MDT_COLSUM_TABLE = 80 };  // entries per launch (passed by value: 80 x 40 B of kernel arguments)
 struct mdt_colsum_table { mdt_colsum_entry e[MDT_COLSUM_TABLE]; };
 hipError_t mdt_launch_colsum_batched(const mdt_colsum_entry* entries, int n, hipStream_t s);
-hipError_t mdt_launch_attn_bwd(const mdt_attn_bwd_args& a, hipStream_t s);
+hipError_t mdt_launch_attn_bwd(const mdt_attn_bwd_args& a, hipStream_t s, int kv_rows = 0);
 hipError_t mdt_launch_loss_grad(const float* F, const float* act, const float* noised, const float* sigma, float sd,
                                 int64_t n, int per_sample, const float* gscale, float* dF, hipStream_t s);
 hipError_t mdt_launch_narrow_dx(const float* G, const float* W, float* out, int M, int A, int D, hipStream_t s);

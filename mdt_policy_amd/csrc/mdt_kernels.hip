@@ -1275,8 +1275,9 @@ static hipError_t launch_attn_t(const mdt_attn_args& a, const float* rc, const f
 }
 
 hipError_t mdt_launch_attention(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin,
-                                hipStream_t s, int ctx_div) {
-    if (a.Tq > 16 || a.Tk > 16) return mdt_launch_attn_chunk(a, rope_cos, rope_sin, s, ctx_div);   // 17 .. 64 rows: mdt_attn_chunk.hip
+                                hipStream_t s, int ctx_div, int kv_rows) {
+    if (a.Tq > 16 || a.Tk > 16) return mdt_launch_attn_chunk(a, rope_cos, rope_sin, s, ctx_div, kv_rows);   // 17 .. 64 rows: mdt_attn_chunk.hip
+    if (kv_rows != 0 && kv_rows != a.Tk) return hipErrorInvalidValue;   // the visible prefix is a form of the chunk kernels
     if (a.H < 1 || a.Tq < 1 || a.Tq > 16 || a.Tk < 1 || a.Tk > 16 || ctx_div < 1) return hipErrorInvalidValue;
     const int lp = attn_lanes(a.hd);
     const int Hl = a.H / attn_head_split(a.H, a.Tq, a.hd, a.B);  // heads of one workgroup

@@ -348,8 +348,12 @@ extern "C" mdt_status mdt_create(const mdt_config* cfg, mdt_model** out) {
         return fail(MDT_ERR_INVALID_ARG, "use_proprio: only MDTVTransformer reads state['state_obs'] "
                                          "(MDTTransformer.process_state_embeddings returns None, mdt_transformer.py:309-316)");
     if (prop && (c.proprio_dim < 1 || c.proprio_dim > 16)) return fail(MDT_ERR_UNSUPPORTED, "proprio_dim must be 1..16");
-    if (n_tok < 1 || sig_tok + 1 + n_tok + (prop ? 1 : 0) > 16)
-        return fail(MDT_ERR_UNSUPPORTED, "context length must be <= 16 tokens");
+    {   // the context: [sigma token] + goal + state tokens + [proprio token]; 64 = the chunk kernels' rows and the rotary tables' positions
+        const int ctx_len = sig_tok + 1 + n_tok + (prop ? 1 : 0);
+        if (n_tok < 1 || ctx_len > MDT_ROPE_POSITIONS || (ctx_len > 16 && hd < 32))
+            return fail(MDT_ERR_UNSUPPORTED, "context length %d tokens at head dim %d: a context of 17..64 tokens needs head dim 32 / 48 / 64; head dim 16 "
+                                             "takes 1..16 (sigma token + goal + n_obs_token + proprio token must be >= 1 and <= 64)", ctx_len, hd);
+    }
     const bool gc = c.no_goal_conditioning == 0;
     if (!gc && c.arch == MDT_ARCH_MDT && c.use_ada_conditioning)
         return fail(MDT_ERR_UNSUPPORTED, "MDTTransformer with goal_conditioned=False needs use_ada_conditioning=False "
@@ -1090,7 +1094,7 @@ static mdt_status run_decoder_blocks(mdt_model* m, const View& V, int64_t B, con
             a.out = W.att; a.ldo = D; a.B = (int)B; a.H = m->H; a.hd = m->hd; a.Tq = Ta; a.Tk = m->Te;
             a.causal = 1;  // SDPA is_causal on a Ta x Te matrix: top-left aligned (transformer_blocks.py:204,142)
             a.rope = m->cfg.use_rot_embed;
-            LAUNCH(mdt_launch_attention(a, m->rope_cos, m->rope_sin, s, ctx_div));
+            LAUNCH(mdt_launch_attention(a, m->rope_cos, m->rope_sin, s, ctx_div, mdt_visible_keys(m)));
             mdt_gemm_args p = gemm_args(W.att, D, d.xproj, W.y, D, M);
             p.residual = 1; p.rows_per_sample = Ta;
             LAUNCH(mdt_launch_gemm(p, s));
@@ -1990,7 +1994,7 @@ extern "C" mdt_status mdt_op_gemm_ln_pair(const mdt_gemm_args* a, void* stream) 
     return MDT_OK;
 }
 
-static mdt_status op_attention(const mdt_attn_args* a, int ctx_div, void* stream) {
+static mdt_status op_attention(const mdt_attn_args* a, int ctx_div, void* stream, int kv_rows = 0) {
     if (!a || !a->q || !a->k || !a->v || !a->out) return fail(MDT_ERR_INVALID_ARG, "mdt_op_attention: null pointer");
     if (a->Tq < 1 || a->Tq > 64 || a->Tk < 1 || a->Tk > 64) return fail(MDT_ERR_UNSUPPORTED, "Tq, Tk must be 1..64");
     if (a->hd != 16 && a->hd != 32 && a->hd != 48 && a->hd != 64) return fail(MDT_ERR_UNSUPPORTED, "hd must be 16/32/48/64");
@@ -2012,10 +2016,10 @@ static mdt_status op_attention(const mdt_attn_args* a, int ctx_div, void* stream
             HIP_TRY(hipMemcpy(cs, rc.data(), rc.size() * sizeof(float), hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(sn, rs.data(), rs.size() * sizeof(float), hipMemcpyHostToDevice));
         }
-        LAUNCH(mdt_launch_attention(*a, cs, sn, (hipStream_t)stream, ctx_div));
+        LAUNCH(mdt_launch_attention(*a, cs, sn, (hipStream_t)stream, ctx_div, kv_rows));
         return MDT_OK;
     }
-    LAUNCH(mdt_launch_attention(*a, nullptr, nullptr, (hipStream_t)stream, ctx_div));
+    LAUNCH(mdt_launch_attention(*a, nullptr, nullptr, (hipStream_t)stream, ctx_div, kv_rows));
     return MDT_OK;
 }
 extern "C" mdt_status mdt_op_attention(const mdt_attn_args* a, void* stream) { return op_attention(a, 1, stream); }
@@ -2023,6 +2027,13 @@ extern "C" mdt_status mdt_op_attention(const mdt_attn_args* a, void* stream) { r
 extern "C" mdt_status mdt_op_attention_shared(const mdt_attn_args* a, int32_t ctx_div, void* stream) {
     if (ctx_div < 1 || (a && a->B % ctx_div)) return fail(MDT_ERR_INVALID_ARG, "mdt_op_attention_shared: B must be a multiple of ctx_div >= 1");
     return op_attention(a, ctx_div, stream);
+}
+// test hook (mdt_hip_debug.h): the decoder's cross-attention at a context above 16 tokens -- the first kv_rows keys only
+extern "C" mdt_status mdt_op_attention_prefix(const mdt_attn_args* a, int32_t ctx_div, int32_t kv_rows, void* stream) {
+    if (ctx_div < 1 || (a && a->B % ctx_div)) return fail(MDT_ERR_INVALID_ARG, "mdt_op_attention_prefix: B must be a multiple of ctx_div >= 1");
+    if (a && !mdt_prefix_rows_ok(a->Tq, a->Tk, a->causal, kv_rows))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_attention_prefix: kv_rows %d: 0, Tk, or min(Tq, Tk) .. Tk - 1 of a causal launch with Tk > 16", kv_rows);
+    return op_attention(a, ctx_div, stream, kv_rows);
 }
 
 extern "C" mdt_status mdt_op_xattn_fold(const mdt_xfold_args* a, void* stream) {

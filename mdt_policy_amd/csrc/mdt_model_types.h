@@ -122,3 +122,8 @@ struct mdt_model {
     float *g_tok = nullptr, *g_tok2 = nullptr, *g_goal = nullptr;
 };
 
+// keys the decoder's cross-attention stages per (sample, head): the causal mask is top-left aligned on the Ta x Te matrix, so no
+// query sees a context row j >= Ta.  Above 16 tokens the chunk kernels take the visible prefix (mdt_launch_attention's kv_rows);
+// up to 16 tokens the launches are what they were (0 = every key).
+inline int mdt_visible_keys(const mdt_model* m) { return m->Te > 16 ? (m->Te < m->Ta ? m->Te : m->Ta) : 0; }
+

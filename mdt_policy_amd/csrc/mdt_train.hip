@@ -376,7 +376,7 @@ static mdt_merge_args merge_args(const float* x, const float* a, const float* ga
 }
 
 static mdt_status attn_fwd(mdt_model* m, const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, float* out,
-                           int64_t B, int Tq, int Tk, bool causal, const mdt_dropout& dr, uint32_t site, hipStream_t s) {
+                           int64_t B, int Tq, int Tk, bool causal, const mdt_dropout& dr, uint32_t site, hipStream_t s, int kv_rows = 0) {
     // (without dropout too where the MFMA form of the training kernel applies: it is the faster of the two at training batches)
     if ((dr.seed != 0 && dr.attn_p > 0.f) || mdt_attn_train_mfma_supported(m->hd, m->H, m->cfg.use_rot_embed)) {
         mdt_attn_train_args a;
@@ -385,7 +385,7 @@ static mdt_status attn_fwd(mdt_model* m, const float* q, int64_t ldq, const floa
         a.B = (int)B; a.H = m->H; a.hd = m->hd; a.Tq = Tq; a.Tk = Tk; a.causal = causal;
         a.p = dr.seed ? dr.attn_p : 0.f; a.site = site; a.seed = dr.seed;
         a.rope = m->cfg.use_rot_embed; a.rope_cos = m->rope_cos; a.rope_sin = m->rope_sin;
-        LAUNCH(mdt_launch_attn_fwd_train(a, s));
+        LAUNCH(mdt_launch_attn_fwd_train(a, s, kv_rows));
         return MDT_OK;
     }
     mdt_attn_args a;
@@ -393,7 +393,7 @@ static mdt_status attn_fwd(mdt_model* m, const float* q, int64_t ldq, const floa
     a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldkv = ldkv; a.out = out; a.ldo = m->D;
     a.B = (int)B; a.H = m->H; a.hd = m->hd; a.Tq = Tq; a.Tk = Tk; a.causal = causal;
     a.rope = m->cfg.use_rot_embed;
-    LAUNCH(mdt_launch_attention(a, m->rope_cos, m->rope_sin, s));
+    LAUNCH(mdt_launch_attention(a, m->rope_cos, m->rope_sin, s, 1, kv_rows));
     return MDT_OK;
 }
 
@@ -455,7 +455,7 @@ static mdt_status block_fwd(mdt_model* m, const EncBlock& e, const DecBlock* d, 
         }
         if (half == 1) return MDT_OK;
         // SDPA is_causal on a Ta x Te matrix: top-left aligned (transformer_blocks.py:204,142)
-        MDT_TRY(attn_fwd(m, t.q, D, kv, kv + D, (int64_t)m->Ld * 2 * D, t.att2, B, T, m->Te, true, dr, site_id(blk, SITE_XATTN), s));
+        MDT_TRY(attn_fwd(m, t.q, D, kv, kv + D, (int64_t)m->Ld * 2 * D, t.att2, B, T, m->Te, true, dr, site_id(blk, SITE_XATTN), s, mdt_visible_keys(m)));
         LAUNCH(mdt_launch_gemm(gemm_args(t.att2, D, d->xproj, t.a2, D, M), s));
         LAUNCH(mdt_launch_merge_ln_fwd(merge_args(t.x1, t.a2, nullptr, 0, t.x2, B, T, D, dr.resid_p, site_id(blk, SITE_XRESID), dr.seed), l2, s));
     } else {
@@ -874,7 +874,7 @@ static mdt_status block_bwd(mdt_model* m, float* grads, const EncBlock& e, const
         float* d_q = dy_take(ts, MD, ts->t_d2);
         LAUNCH(mdt_launch_attn_bwd(attn_bwd_args(m, t.q, D, kv, kv + D, (int64_t)m->Ld * 2 * D, ts->t_d, d_q, D, d_kv,
                                                  d_kv + D, (int64_t)m->Ld * 2 * D, B, T, m->Te, true, dr,
-                                                 site_id(blk, SITE_XATTN)), s));
+                                                 site_id(blk, SITE_XATTN)), s, mdt_visible_keys(m)));
         MDT_TRY(lin_bwd(m, grads, d->xq, t.h3, D, d_q, D, M, ts->t_d, D, 0, s, nullptr, 0, bs));
         MDT_TRY(ln_bwd(m, grads, t.x1, t.st3, d->ln3_w, d->ln3_b, mod, modw, c.sh3, -1, ts->t_d, dx, 1, d_mod, B, T, s, acc_dmod, &gs));
     } else {

@@ -1239,8 +1239,9 @@ bool mdt_attn_train_mfma_supported(int hd, int H, int rope) { return attn_train_
         default: break;                                                                                  \
     }
 
-hipError_t mdt_launch_attn_fwd_train(const mdt_attn_train_args& a, hipStream_t s) {
-    if (a.Tq > 16 || a.Tk > 16) return mdt_launch_attn_chunk_fwd_train(a, s);   // 17 .. 64 rows: mdt_attn_chunk.hip
+hipError_t mdt_launch_attn_fwd_train(const mdt_attn_train_args& a, hipStream_t s, int kv_rows) {
+    if (a.Tq > 16 || a.Tk > 16) return mdt_launch_attn_chunk_fwd_train(a, s, kv_rows);   // 17 .. 64 rows: mdt_attn_chunk.hip
+    if (kv_rows != 0 && kv_rows != a.Tk) return hipErrorInvalidValue;   // the visible prefix is a form of the chunk kernels
     if (a.Tq < 1 || a.Tq > 16 || a.Tk < 1 || a.Tk > 16) return hipErrorInvalidValue;
     if (((a.ldq | a.ldkv | a.ldo) & 3) || (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.out) & 15))
         return hipErrorInvalidValue;  // 16-byte loads / stores of the head slices
@@ -1384,8 +1385,9 @@ __global__ __launch_bounds__(64) void k_attn_bwd(mdt_attn_bwd_args a, float scal
     }
 }
 
-hipError_t mdt_launch_attn_bwd(const mdt_attn_bwd_args& a, hipStream_t s) {
-    if (a.Tq > 16 || a.Tk > 16) return mdt_launch_attn_chunk_bwd(a, s);   // 17 .. 64 rows: mdt_attn_chunk.hip
+hipError_t mdt_launch_attn_bwd(const mdt_attn_bwd_args& a, hipStream_t s, int kv_rows) {
+    if (a.Tq > 16 || a.Tk > 16) return mdt_launch_attn_chunk_bwd(a, s, kv_rows);   // 17 .. 64 rows: mdt_attn_chunk.hip
+    if (kv_rows != 0 && kv_rows != a.Tk) return hipErrorInvalidValue;   // the visible prefix is a form of the chunk kernels
     if (a.Tq < 1 || a.Tq > 16 || a.Tk < 1 || a.Tk > 16) return hipErrorInvalidValue;
     if (((a.ldq | a.ld_do | a.ldkv | a.ld_dq | a.ld_dkv) & 3) ||
         (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.d_out | (uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) & 15))

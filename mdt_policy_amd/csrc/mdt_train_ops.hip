@@ -236,6 +236,15 @@ extern "C" mdt_status mdt_op_attn_bwd(const mdt_attn_bwd_args* a, void* stream) 
     LAUNCH(mdt_launch_attn_bwd(*a, (hipStream_t)stream));
     return MDT_OK;
 }
+// test hook (mdt_hip_debug.h): the backward of the decoder's cross-attention at a context above 16 tokens
+extern "C" mdt_status mdt_op_attn_bwd_prefix(const mdt_attn_bwd_args* a, int32_t kv_rows, void* stream) {
+    if (!a || !a->q || !a->k || !a->v || !a->d_out || !a->dq || !a->dk || !a->dv)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_bwd_prefix: null argument");
+    if (!mdt_prefix_rows_ok(a->Tq, a->Tk, a->causal, kv_rows))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_bwd_prefix: kv_rows %d: 0, Tk, or min(Tq, Tk) .. Tk - 1 of a causal launch with Tk > 16", kv_rows);
+    LAUNCH(mdt_launch_attn_bwd(*a, (hipStream_t)stream, kv_rows));
+    return MDT_OK;
+}
 
 extern "C" mdt_status mdt_op_act_fwd(const float* u, float* out, int64_t n, int32_t act, void* stream) {
     if (!u || !out || n < 1) return fail(MDT_ERR_INVALID_ARG, "mdt_op_act_fwd: bad argument");
@@ -282,6 +291,14 @@ extern "C" mdt_status mdt_op_ln_bwd_merge(const mdt_ln_bwd_args* a, const mdt_me
 extern "C" mdt_status mdt_op_attn_fwd_train(const mdt_attn_train_args* a, void* stream) {
     if (!a || !a->q || !a->k || !a->v || !a->out) return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_fwd_train: null argument");
     LAUNCH(mdt_launch_attn_fwd_train(*a, (hipStream_t)stream));
+    return MDT_OK;
+}
+// test hook (mdt_hip_debug.h): the training forward of the decoder's cross-attention at a context above 16 tokens
+extern "C" mdt_status mdt_op_attn_fwd_train_prefix(const mdt_attn_train_args* a, int32_t kv_rows, void* stream) {
+    if (!a || !a->q || !a->k || !a->v || !a->out) return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_fwd_train_prefix: null argument");
+    if (!mdt_prefix_rows_ok(a->Tq, a->Tk, a->causal, kv_rows))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_fwd_train_prefix: kv_rows %d: 0, Tk, or min(Tq, Tk) .. Tk - 1 of a causal launch with Tk > 16", kv_rows);
+    LAUNCH(mdt_launch_attn_fwd_train(*a, (hipStream_t)stream, kv_rows));
     return MDT_OK;
 }
 
