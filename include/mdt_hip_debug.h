@@ -87,6 +87,20 @@ mdt_status mdt_op_attn_bwd_prefix(const mdt_attn_bwd_args *args, int32_t kv_rows
  *   backward  4 [(2 Tq16 + 2 Tv16)(hd + 4) + 2 Tq16 (Tv16 + 4)]  */
 int64_t mdt_op_attn_chunk_lds(int32_t hd, int32_t Tq, int32_t kv_rows, int32_t bwd);
 
+/* The two attention launches of the MAP pooling block (mdt_map_pool.h) on the caller's buffers, either kernel family:
+ * family 0 = one workgroup per sample (what the block runs at N <= 16; 1..16 tokens, refused above its 64 KiB LDS rule),
+ * family 1 = one workgroup per (sample, head group) (what the block runs at N 17..64; here reachable at N 1..64, so that the two
+ * can be compared at equal shapes).  q (Q, D): the seed queries, shared by the samples; kv (batch, N, 2 D): K | V rows;
+ * out (batch, Q, D); probs (batch, Q, H, N) or NULL in the forward.  The backward reads probs and d_out (batch, Q, D) and writes
+ * every element of dq_part (batch, Q, D) and d_kv (batch, N, 2 D) once (no accumulation, nothing to zero).  Q 1..16, D a multiple
+ * of 16 up to 512, H even and a divisor of D, 16-byte aligned pointers. */
+mdt_status mdt_op_map_attn_fwd(int32_t family, const float *q, const float *kv, float *out, float *probs, int64_t batch, int32_t Q,
+                               int32_t N, int32_t D, int32_t H, void *stream);
+mdt_status mdt_op_map_attn_bwd(int32_t family, const float *q, const float *kv, const float *probs, const float *d_out,
+                               float *dq_part, float *d_kv, int64_t batch, int32_t Q, int32_t N, int32_t D, int32_t H, void *stream);
+/* Bytes of dynamic LDS one workgroup of family 1 takes (the rule of mdt_map_pool.h); -1 for a shape that is none. */
+int64_t mdt_op_map_attn_lds(int32_t Q, int32_t N, int32_t D, int32_t H, int32_t bwd);
+
 /* Measurement hook: bracket every fused-MLP launch of the model-level calls that follow (mdt_sample_ddim, mdt_forward, ...)
  * with a pair of HIP events on its stream; mdt_op_trace_mlp_read waits for them, writes up to `cap` durations in
  * MICROSECONDS (launch order) to `us`, releases the events and returns how many it wrote.  The duration of the dominant

@@ -46,18 +46,34 @@ int64_t mdt_map_pool_param_numel(const mdt_map_pool *p, int64_t i);
 mdt_status mdt_map_pool_load_param(mdt_map_pool *p, const char *name, const float *src, int64_t numel, void *stream);
 
 /* MAPBlock.forward(x) (transformer_blocks.py:787-791):
- *   x   : (B, N, embed_dim) tokens to pool, N <= 16
+ *   x   : (B, N, embed_dim) tokens to pool, 1 <= N <= 64 (the denoiser's own context limit); N < 1 or N > 64 returns
+ *         MDT_ERR_UNSUPPORTED ("1..64 tokens per sample") before anything is enqueued
  *   out : (B, n_latents, output_dim)   (the reference squeezes dim 1 when n_latents == 1: same memory)
  *
- * How many tokens a call may have.  The attention runs one workgroup per sample with the sample's queries, keys,
- * values and scores in LDS, within a 64 KiB budget.  With Q = n_latents, D = output_dim, H = 2 * n_heads, in bytes:
+ * The attention is one of two kernel pairs, chosen by the token count alone.  With Q = n_latents, D = output_dim,
+ * H = 2 * n_heads, hd = D / H:
+ *
+ * N <= 16: one workgroup per sample with the sample's queries, keys, values and scores in LDS, within a 64 KiB budget.  Bytes:
  *   inference (mdt_map_pool_forward)       : 4 * (Q*D + 2*N*D + Q*H*N)        q, k|v, scores
  *   training  (mdt_map_pool_forward_train) : 4 * (2*Q*D + 2*N*D + 2*Q*H*N)    + dO and dS for the backward
- * A call whose budget exceeds 65536 bytes returns MDT_ERR_UNSUPPORTED before anything is enqueued.  The training
- * budget is the larger one, so a shape can be ACCEPTED FOR INFERENCE AND REFUSED FOR TRAINING.  Example: n_latents 16,
+ * A call whose budget exceeds 65536 bytes returns MDT_ERR_UNSUPPORTED ("LDS budget") before anything is enqueued.  The training
+ * budget is the larger one, so at N <= 16 a shape can be ACCEPTED FOR INFERENCE AND REFUSED FOR TRAINING.  Example: n_latents 16,
  * output_dim 256, n_heads 8, N = 16 needs exactly 65536 bytes for inference (accepted) and 98304 for training
  * (refused); n_latents 16, output_dim 512, N = 16 is refused for both.  ClipStyleProjection's shape (one latent, 384
- * channels, n_heads 8) fits with 16 tokens in both: 51712 and 54272 bytes. */
+ * channels, n_heads 8) fits with 16 tokens in both: 51712 and 54272 bytes.
+ *
+ * N 17..64: one workgroup per (sample, group of hg heads), which holds only the W = hg * hd channels of its heads and stages
+ * the K slice and the V slice of the sample one after the other in the same LDS rows:
+ *   hg = the largest divisor of H with hg <= 8 and hg * hd <= 128 (1 when there is none: hd > 64)
+ *   W  = hg * hd,   Wp = W | 1 (the staged rows have an odd stride)
+ *   inference : 4 * (Q*W + N*Wp + Q*hg*N)        q, K then V, scores
+ *   training  : 4 * (2*Q*W + N*Wp + 2*Q*hg*N)    + dO and dS for the backward
+ * The largest workgroups any accepted handle can ask for, at Q 16 and N 64: the widest single head, hd 256 (512 channels,
+ * n_heads 1), takes 86272 and 106752 bytes; eight heads of 16 (W = 128) take 73984 and 114944, the maximum of the rule.  All
+ * are inside the 160 KiB of a CU, so NOTHING IS REFUSED for LDS above 16 tokens, for inference or for training; the
+ * shipped head at 34 tokens takes 14120 / 15048 bytes.  The rule above 16 tokens is therefore the laxer one: 16 latents x 512
+ * channels is refused at 16 tokens and accepted at 17.  (Retiring the <= 16-token pair would lift that; its bits and its
+ * refusals are pinned by tests.)  mdt_op_map_attn_lds (mdt_hip_debug.h) returns the second rule's bytes. */
 mdt_status mdt_map_pool_forward(mdt_map_pool *p, const float *x, int64_t batch, int32_t n_tokens, float *out,
                                 void *stream);
 

@@ -326,6 +326,9 @@ SYMBOLS = [
     ("mdt_op_attn_fwd_train_prefix", _I32, [C.POINTER(AttnTrainArgs), _I32, _VP]),
     ("mdt_op_attn_bwd_prefix", _I32, [C.POINTER(AttnBwdArgs), _I32, _VP]),
     ("mdt_op_attn_chunk_lds", _I64, [_I32, _I32, _I32, _I32]),
+    ("mdt_op_map_attn_fwd", _I32, [_I32, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _I32, _I32, _VP]),
+    ("mdt_op_map_attn_bwd", _I32, [_I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _I32, _I32, _VP]),
+    ("mdt_op_map_attn_lds", _I64, [_I32, _I32, _I32, _I32, _I32]),
     ("mdt_op_trace_mlp", None, [_I32]),
     ("mdt_op_trace_mlp_read", _I32, [_VP, _I32]),
     ("mdt_op_trace_mlp_read_empty", _I32, [_VP, _I32]),

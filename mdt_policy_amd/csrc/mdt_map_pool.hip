@@ -7,9 +7,9 @@
 //   latents = rms(latents + proj(attn(q(latents), kv(projection(x)))))        seed vectors attend over the tokens
 //   latents = rms(latents + mlp.1(swish_glu(mlp.0.project(latents))))
 // runs here as the fp32-MFMA GEMMs of the denoiser (projection, kv, q, proj, mlp.0, mlp.1: bias / residual fused in
-// their epilogues) plus three small VALU kernels: seed-vector attention over <= 16 tokens (one workgroup per sample,
-// q / k / v of the sample in LDS), RMSNorm, SwishGLU.  The backward mirrors resampler / denoiser training: every dense
-// contraction through mdt_linear_bwd, the row-local pieces as VALU kernels.
+// their epilogues) plus small VALU kernels: seed-vector attention over <= 16 tokens (one workgroup per sample,
+// q / k / v of the sample in LDS) or over 17 .. 64 (one workgroup per sample and head group), RMSNorm, SwishGLU.  The backward
+// mirrors resampler / denoiser training: every dense contraction through mdt_linear_bwd, the row-local pieces as VALU kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +20,8 @@
 
 #include "mdt_device.h"
 #include "mdt_handle.h"
+#include "mdt_hip_debug.h"
+#include "mdt_launch.h"
 #include "mdt_map_pool.h"
 
 #define fail mdt_fail
@@ -117,6 +119,172 @@ __global__ __launch_bounds__(256) void k_map_attn_bwd(const float* __restrict__ 
         }
         d_kv[((int64_t)b * N + n) * 2 * D + c] = ak * scale;
         d_kv[((int64_t)b * N + n) * 2 * D + D + c] = av;
+    }
+}
+
+// ---- 17 .. 64 tokens: one workgroup per (sample, group of hg heads) -- include/mdt_map_pool.h has the rule ----
+// The workgroup owns the W = hg * hd channels of its heads: LDS holds q (Q, W), ONE of K / V of the slice at a time (N rows of
+// stride W | 1: odd, so the threads of consecutive keys hit different banks) and the scores (Q, hg, N).  Same arithmetic as the
+// pair above; a softmax row is reduced by 16 lanes instead of one thread, so the bits differ from that pair's.
+struct map_group { int hg, W, Wp; };
+static inline map_group map_group_of(int D, int H) {
+    const int hd = D / H;
+    int hg = 1;
+    for (int g = 2; g <= 8; ++g)
+        if (H % g == 0 && g * hd <= 128) hg = g;
+    return {hg, hg * hd, (hg * hd) | 1};
+}
+static inline size_t map_long_lds(int Q, int N, int D, int H, bool bwd) {
+    const map_group g = map_group_of(D, H);
+    const size_t k = bwd ? 2 : 1;
+    return sizeof(float) * (k * Q * g.W + (size_t)N * g.Wp + k * Q * g.hg * N);
+}
+
+// rows [0, N) x channels [c0, c0 + W) of a matrix of row stride ld -> dst (N, Wp), times mul; 16-byte loads when the slice allows
+__device__ __forceinline__ void map_stage(const float* __restrict__ src, int64_t ld, int c0, int N, int W, int Wp, float mul,
+                                          float* __restrict__ dst, int tid) {
+    if (((W | c0) & 3) == 0) {
+        const int W4 = W >> 2, total = N * W4;
+        for (int i0 = tid; i0 < total; i0 += 4 * 256) {  // four loads in flight per thread before the first LDS store
+            float4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = i0 + u * 256, n = i / W4, c = (i - n * W4) * 4;
+                if (i < total) v[u] = *reinterpret_cast<const float4*>(src + n * ld + c0 + c);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = i0 + u * 256, n = i / W4, c = (i - n * W4) * 4;
+                if (i >= total) continue;
+                float* d = dst + n * Wp + c;
+                d[0] = v[u].x * mul; d[1] = v[u].y * mul; d[2] = v[u].z * mul; d[3] = v[u].w * mul;
+            }
+        }
+    } else {
+        for (int i = tid; i < N * W; i += 256) {
+            const int n = i / W, c = i - n * W;
+            dst[n * Wp + c] = src[n * ld + c0 + c] * mul;
+        }
+    }
+}
+
+// sum / max over the 16 lanes of a quarter wave (every lane gets the result; the same tree for every row)
+__device__ __forceinline__ float q16_sum(float v) {
+    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
+    return v;
+}
+__device__ __forceinline__ float q16_max(float v) {
+    for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 16));
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_map_attn_long_fwd(const float* __restrict__ q, const float* __restrict__ kv,
+                                                           float* __restrict__ out, float* __restrict__ probs, int Q, int N, int D,
+                                                           int H, int hg, float scale) {
+    extern __shared__ float sm[];
+    const int b = blockIdx.x, tid = threadIdx.x, hd = D / H, W = hg * hd, Wp = W | 1, h0 = blockIdx.y * hg, c0 = h0 * hd;
+    float* qs = sm;
+    float* st = qs + Q * W;
+    float* sc = st + N * Wp;
+    const float* kvb = kv + (int64_t)b * N * 2 * D;
+    for (int i = tid; i < Q * W; i += 256) qs[i] = q[(i / W) * D + c0 + i % W];
+    map_stage(kvb, 2 * D, c0, N, W, Wp, scale, st, tid);  // the reference scales k, then q k^T
+    __syncthreads();
+    for (int i = tid; i < Q * hg * N; i += 256) {
+        const int n = i % N, h = (i / N) % hg, qi = i / (N * hg);
+        const float* qp = qs + qi * W + h * hd;
+        const float* kp = st + n * Wp + h * hd;
+        float s = 0.f;
+        for (int c = 0; c < hd; ++c) s = fmaf(qp[c], kp[c], s);
+        sc[i] = s;
+    }
+    __syncthreads();
+    map_stage(kvb, 2 * D, D + c0, N, W, Wp, 1.0f, st, tid);  // V takes K's place
+    for (int r = tid >> 4; r < Q * hg; r += 16) {             // 16 lanes per softmax row, up to 4 keys each
+        float* row = sc + r * N;
+        const int l = tid & 15;
+        float mx = -INFINITY;
+        for (int n = l; n < N; n += 16) mx = fmaxf(mx, row[n]);
+        mx = q16_max(mx);
+        float sum = 0.f;
+        for (int n = l; n < N; n += 16) { row[n] = expf(row[n] - mx); sum += row[n]; }
+        const float inv = 1.0f / q16_sum(sum);
+        const int qi = r / hg, h = r - qi * hg;
+        for (int n = l; n < N; n += 16) {
+            row[n] *= inv;
+            if (probs) probs[(((int64_t)b * Q + qi) * H + h0 + h) * N + n] = row[n];
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < Q * W; i += 256) {
+        const int c = i % W, qi = i / W, h = c / hd;
+        const float* row = sc + (qi * hg + h) * N;
+        float acc = 0.f;
+        for (int n = 0; n < N; ++n) acc = fmaf(row[n], st[n * Wp + c], acc);
+        out[((int64_t)b * Q + qi) * D + c0 + c] = acc;
+    }
+}
+
+// backward of k_map_attn_long_fwd: V is staged for dP, then K for dq; dk and dv need neither.  Every element of d_kv and of
+// dq_part is written once, by the workgroup that owns its channel: no atomics, nothing to zero first.
+__global__ __launch_bounds__(256) void k_map_attn_long_bwd(const float* __restrict__ q, const float* __restrict__ kv,
+                                                           const float* __restrict__ probs, const float* __restrict__ d_out,
+                                                           float* __restrict__ dq_part, float* __restrict__ d_kv, int Q, int N,
+                                                           int D, int H, int hg, float scale) {
+    extern __shared__ float sm[];
+    const int b = blockIdx.x, tid = threadIdx.x, hd = D / H, W = hg * hd, Wp = W | 1, h0 = blockIdx.y * hg, c0 = h0 * hd;
+    float* qs = sm;
+    float* dos = qs + Q * W;
+    float* st = dos + Q * W;
+    float* P = st + N * Wp;
+    float* dS = P + Q * hg * N;
+    const float* kvb = kv + (int64_t)b * N * 2 * D;
+    for (int i = tid; i < Q * W; i += 256) {
+        const int qi = i / W, c = i % W;
+        qs[i] = q[qi * D + c0 + c];
+        dos[i] = d_out[((int64_t)b * Q + qi) * D + c0 + c];
+    }
+    for (int i = tid; i < Q * hg * N; i += 256) {
+        const int n = i % N, h = (i / N) % hg, qi = i / (N * hg);
+        P[i] = probs[(((int64_t)b * Q + qi) * H + h0 + h) * N + n];
+    }
+    map_stage(kvb, 2 * D, D + c0, N, W, Wp, 1.0f, st, tid);
+    __syncthreads();
+    for (int i = tid; i < Q * hg * N; i += 256) {  // dP = dO . v
+        const int n = i % N, h = (i / N) % hg, qi = i / (N * hg);
+        const float* dp = dos + qi * W + h * hd;
+        const float* vp = st + n * Wp + h * hd;
+        float s = 0.f;
+        for (int c = 0; c < hd; ++c) s = fmaf(dp[c], vp[c], s);
+        dS[i] = s;
+    }
+    __syncthreads();
+    map_stage(kvb, 2 * D, c0, N, W, Wp, 1.0f, st, tid);  // K takes V's place
+    for (int r = tid >> 4; r < Q * hg; r += 16) {         // dS = P * (dP - sum_n P dP)
+        const int l = tid & 15;
+        float dot = 0.f;
+        for (int n = l; n < N; n += 16) dot = fmaf(P[r * N + n], dS[r * N + n], dot);
+        dot = q16_sum(dot);
+        for (int n = l; n < N; n += 16) dS[r * N + n] = P[r * N + n] * (dS[r * N + n] - dot);
+    }
+    __syncthreads();
+    for (int i = tid; i < Q * W; i += 256) {  // dq = scale * sum_n dS k
+        const int c = i % W, qi = i / W, h = c / hd;
+        const float* row = dS + (qi * hg + h) * N;
+        float acc = 0.f;
+        for (int n = 0; n < N; ++n) acc = fmaf(row[n], st[n * Wp + c], acc);
+        dq_part[((int64_t)b * Q + qi) * D + c0 + c] = acc * scale;
+    }
+    for (int i = tid; i < N * W; i += 256) {  // dk = scale * sum_q dS q ; dv = sum_q P dO
+        const int c = i % W, n = i / W, h = c / hd;
+        float ak = 0.f, av = 0.f;
+        for (int qi = 0; qi < Q; ++qi) {
+            ak = fmaf(dS[(qi * hg + h) * N + n], qs[qi * W + c], ak);
+            av = fmaf(P[(qi * hg + h) * N + n], dos[qi * W + c], av);
+        }
+        float* row = d_kv + ((int64_t)b * N + n) * 2 * D + c0 + c;
+        row[0] = ak * scale;
+        row[D] = av;
     }
 }
 
@@ -295,9 +463,71 @@ static void build(mdt_map_pool* p, Bump& b, bool fill) {
     p->qv = b.take((size_t)p->Q * p->D);
 }
 
-static size_t attn_lds_floats(const mdt_map_pool* p, int N, bool bwd) {
-    const size_t base = (size_t)p->Q * p->D + (size_t)N * 2 * p->D + (size_t)p->Q * p->H * N;
-    return bwd ? base + (size_t)p->Q * p->D + (size_t)p->Q * p->H * N : base;
+// bytes of LDS of the one-workgroup-per-sample pair (N <= 16)
+static size_t map_short_lds(int Q, int N, int D, int H, bool bwd) {
+    const size_t base = (size_t)Q * D + (size_t)N * 2 * D + (size_t)Q * H * N;
+    return sizeof(float) * (bwd ? base + (size_t)Q * D + (size_t)Q * H * N : base);
+}
+constexpr int MAP_SHORT_TOKENS = 16;
+constexpr size_t MAP_SHORT_LDS_BUDGET = 64 * 1024;
+
+// the attention launches: N <= 16 the one-workgroup-per-sample pair, above the (sample, head group) pair
+static hipError_t launch_map_attn_fwd(bool long_family, const float* q, const float* kv, float* out, float* probs, int64_t B, int Q,
+                                      int N, int D, int H, hipStream_t s) {
+    const float scale = 1.0f / sqrtf((float)(D / H));
+    if (!long_family)
+        return mdt_launch_lds<k_map_attn_fwd>(dim3((unsigned)B), dim3(256), map_short_lds(Q, N, D, H, false), s, q, kv, out, probs, Q,
+                                              N, D, H, scale);
+    const map_group g = map_group_of(D, H);
+    return mdt_launch_lds<k_map_attn_long_fwd>(dim3((unsigned)B, (unsigned)(H / g.hg)), dim3(256), map_long_lds(Q, N, D, H, false), s,
+                                               q, kv, out, probs, Q, N, D, H, g.hg, scale);
+}
+static hipError_t launch_map_attn_bwd(bool long_family, const float* q, const float* kv, const float* probs, const float* d_out,
+                                      float* dq_part, float* d_kv, int64_t B, int Q, int N, int D, int H, hipStream_t s) {
+    const float scale = 1.0f / sqrtf((float)(D / H));
+    if (!long_family)
+        return mdt_launch_lds<k_map_attn_bwd>(dim3((unsigned)B), dim3(256), map_short_lds(Q, N, D, H, true), s, q, kv, probs, d_out,
+                                              dq_part, d_kv, Q, N, D, H, scale);
+    const map_group g = map_group_of(D, H);
+    return mdt_launch_lds<k_map_attn_long_bwd>(dim3((unsigned)B, (unsigned)(H / g.hg)), dim3(256), map_long_lds(Q, N, D, H, true), s, q,
+                                               kv, probs, d_out, dq_part, d_kv, Q, N, D, H, g.hg, scale);
+}
+
+// ---- test hooks (mdt_hip_debug.h) ----
+static mdt_status check_map_op(const char* who, int family, int64_t B, int Q, int N, int D, int H, bool bwd) {
+    if (family != 0 && family != 1) return fail(MDT_ERR_INVALID_ARG, "%s: family %d: 0 (<= 16 tokens) or 1 (17..64 tokens)", who, family);
+    if (B < 1 || B > 65535 * 256 || Q < 1 || Q > 16 || D < 16 || D > 512 || D % 16 || H < 2 || H % 2 || D % H)
+        return fail(MDT_ERR_INVALID_ARG, "%s: batch >= 1, Q 1..16, D a multiple of 16 up to 512, H even and a divisor of D", who);
+    if (N < 1 || N > (family ? MDT_ROPE_POSITIONS : MAP_SHORT_TOKENS))
+        return fail(MDT_ERR_UNSUPPORTED, "%s: family %d takes 1..%d tokens, got %d", who, family, family ? MDT_ROPE_POSITIONS : MAP_SHORT_TOKENS, N);
+    if (!family && map_short_lds(Q, N, D, H, bwd) > MAP_SHORT_LDS_BUDGET)
+        return fail(MDT_ERR_UNSUPPORTED, "%s: %d latents x %d tokens x %d channels exceed the attention kernel's LDS budget", who, Q, N, D);
+    return MDT_OK;
+}
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+extern "C" mdt_status mdt_op_map_attn_fwd(int32_t family, const float* q, const float* kv, float* out, float* probs, int64_t batch,
+                                          int32_t Q, int32_t N, int32_t D, int32_t H, void* stream) {
+    if (!q || !kv || !out) return fail(MDT_ERR_INVALID_ARG, "mdt_op_map_attn_fwd: null argument");
+    if (!aligned16(q) || !aligned16(kv) || !aligned16(out) || !aligned16(probs))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_map_attn_fwd: pointers must be 16-byte aligned");
+    MDT_TRY(check_map_op("mdt_op_map_attn_fwd", family, batch, Q, N, D, H, false));
+    LAUNCH(launch_map_attn_fwd(family != 0, q, kv, out, probs, batch, Q, N, D, H, (hipStream_t)stream));
+    return MDT_OK;
+}
+extern "C" mdt_status mdt_op_map_attn_bwd(int32_t family, const float* q, const float* kv, const float* probs, const float* d_out,
+                                          float* dq_part, float* d_kv, int64_t batch, int32_t Q, int32_t N, int32_t D, int32_t H,
+                                          void* stream) {
+    if (!q || !kv || !probs || !d_out || !dq_part || !d_kv) return fail(MDT_ERR_INVALID_ARG, "mdt_op_map_attn_bwd: null argument");
+    if (!aligned16(q) || !aligned16(kv) || !aligned16(probs) || !aligned16(d_out) || !aligned16(dq_part) || !aligned16(d_kv))
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_map_attn_bwd: pointers must be 16-byte aligned");
+    MDT_TRY(check_map_op("mdt_op_map_attn_bwd", family, batch, Q, N, D, H, true));
+    LAUNCH(launch_map_attn_bwd(family != 0, q, kv, probs, d_out, dq_part, d_kv, batch, Q, N, D, H, (hipStream_t)stream));
+    return MDT_OK;
+}
+extern "C" int64_t mdt_op_map_attn_lds(int32_t Q, int32_t N, int32_t D, int32_t H, int32_t bwd) {
+    if (Q < 1 || N < 1 || D < 1 || H < 1 || D % H) return -1;
+    return (int64_t)map_long_lds(Q, N, D, H, bwd != 0);
 }
 
 extern "C" mdt_status mdt_map_pool_create(const mdt_map_pool_config* cfg, mdt_map_pool** out) {
@@ -344,10 +574,11 @@ extern "C" mdt_status mdt_map_pool_load_param(mdt_map_pool* p, const char* name,
 
 static mdt_status check_call(const mdt_map_pool* p, const float* x, const float* out, int64_t batch, int n_tokens, bool bwd) {
     if (!p || !x || !out || batch < 1) return fail(MDT_ERR_INVALID_ARG, "map pool: bad argument");
-    if (n_tokens < 1 || n_tokens > 16) return fail(MDT_ERR_UNSUPPORTED, "map pool: 1..16 tokens per sample, got %d", n_tokens);
+    if (n_tokens < 1 || n_tokens > MDT_ROPE_POSITIONS)
+        return fail(MDT_ERR_UNSUPPORTED, "map pool: 1..%d tokens per sample, got %d", MDT_ROPE_POSITIONS, n_tokens);
     if (((uintptr_t)x & 15) || ((uintptr_t)out & 15)) return fail(MDT_ERR_INVALID_ARG, "map pool: pointers must be 16-byte aligned");
     if (batch * n_tokens > ((int64_t)1 << 24)) return fail(MDT_ERR_INVALID_ARG, "map pool: batch too large");
-    if (attn_lds_floats(p, n_tokens, bwd) * sizeof(float) > 64 * 1024)
+    if (n_tokens <= MAP_SHORT_TOKENS && map_short_lds(p->Q, n_tokens, p->D, p->H, bwd) > MAP_SHORT_LDS_BUDGET)
         return fail(MDT_ERR_UNSUPPORTED, "map pool: %d latents x %d tokens x %d channels exceed the attention kernel's LDS budget",
                     p->Q, n_tokens, p->D);
     return mdt_check_loaded(p->slots, "map pool parameter");
@@ -362,10 +593,7 @@ static mdt_status run_forward(mdt_map_pool* p, const float* x, int64_t B, int N,
     LAUNCH(mdt_launch_gemm(gemm_args(x, p->Din, p->projection, w.xp, D, (int)rows), s));
     LAUNCH(mdt_launch_gemm(gemm_args(w.xp, D, p->kv, w.kv, 2 * D, (int)rows), s));
     LAUNCH(mdt_launch_gemm(gemm_args(p->latents, D, p->q, p->qv, D, Q), s));
-    const float scale = 1.0f / sqrtf((float)p->hd);
-    hipLaunchKernelGGL(k_map_attn_fwd, dim3((unsigned)B), dim3(256), attn_lds_floats(p, N, false) * sizeof(float), s, p->qv, w.kv,
-                       w.att, w.probs, Q, N, D, p->H, scale);
-    LAUNCH(hipGetLastError());
+    LAUNCH(launch_map_attn_fwd(N > MAP_SHORT_TOKENS, p->qv, w.kv, w.att, w.probs, B, Q, N, D, p->H, s));
     // x1 = latents + proj(att)
     LAUNCH(mdt_launch_bcast_rows(p->latents, w.x1, B, Q, D, s));
     mdt_gemm_args o = gemm_args(w.att, D, p->aproj, w.x1, D, (int)lr);
@@ -523,10 +751,7 @@ extern "C" mdt_status mdt_map_pool_backward(mdt_map_pool* p, int32_t tape, const
     float* g_lat = p->grad_of(grads, p->latents);
     LAUNCH(mdt_launch_colsum(p->g_b, (int64_t)Q * D, (int)B, Q * D, g_lat, 1, s));                 // latents were repeated
     MDT_TRY(m_lin_bwd(p, grads, p->aproj, t.att, D, p->g_b, D, lr, p->g_a, D, 0, s));             // g_a = d(att)
-    const float scale = 1.0f / sqrtf((float)p->hd);
-    hipLaunchKernelGGL(k_map_attn_bwd, dim3((unsigned)B), dim3(256), attn_lds_floats(p, N, true) * sizeof(float), s, p->qv, t.kv,
-                       t.probs, p->g_a, p->g_dq, p->g_dkv, Q, N, D, p->H, scale);
-    LAUNCH(hipGetLastError());
+    LAUNCH(launch_map_attn_bwd(N > MAP_SHORT_TOKENS, p->qv, t.kv, t.probs, p->g_a, p->g_dq, p->g_dkv, B, Q, N, D, p->H, s));
     // q = attn.q(latents): the same Q rows for every sample
     LAUNCH(mdt_launch_colsum(p->g_dq, (int64_t)Q * D, (int)B, Q * D, p->g_dqs, 0, s));
     MDT_TRY(m_lin_bwd(p, grads, p->q, p->latents, D, p->g_dqs, D, Q, g_lat, D, 1, s));

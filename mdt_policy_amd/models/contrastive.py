@@ -106,7 +106,8 @@ def compute_contrastive_loss(model, clip_proj, logit_scale, perceptual_emb, imag
                              modality_scope: str = "lang", use_distributed_clip: bool = True,
                              clip_loss_type: str = "symmetric", lang_text=None, group=None) -> torch.Tensor:
     """MDTVAgent.compute_contrastive_loss (mdtv_agent.py:440-484): call right after ``model.loss(...)`` of a
-    language-goal batch, whose context is ``model.inner_model.latent_encoder_emb``."""
+    language-goal batch, whose context is ``model.inner_model.latent_encoder_emb``.  The context may hold up to 64 tokens (what
+    the denoiser accepts); ``clip_proj`` pools all of them."""
     if "lang" not in modality_scope:
         return torch.tensor(0.0, device=actions.device)
     latent_language_embed = model.inner_model.latent_encoder_emb

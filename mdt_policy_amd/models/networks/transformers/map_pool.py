@@ -49,7 +49,9 @@ class MAPAttention(nn.Module):
 
 
 class MAPBlock(HandleModule):
-    """Multiheaded attention pooling block (reference transformer_blocks.py:746-791)."""
+    """Multiheaded attention pooling block (reference transformer_blocks.py:746-791).  Pools 1 .. 64 tokens per sample, the
+    denoiser's own context limit; the library picks the attention kernels by the token count (include/mdt_map_pool.h: up to 16
+    tokens a call can exceed the 64 KiB LDS rule of its kernels and raise, from 17 on nothing is refused for LDS)."""
 
     _prefix, _config, _what = "mdt_map_pool", _lib.MapPoolConfig, "MAPBlock"
     _no_cpu = ("MAPBlock runs only on a ROCm GPU (hand-written gfx950 kernels); move the module and its input with "
@@ -111,7 +113,8 @@ _CLIP_STYLES = {
 
 class ClipStyleProjection(nn.Module):
     """Pools the (B, tokens, d) context into the embedding the contrastive loss compares (reference
-    transformer_blocks.py:833-870: same constructor, same ``latent_proj`` sub-module per style, same outputs)."""
+    transformer_blocks.py:833-870: same constructor, same ``latent_proj`` sub-module per style, same outputs).  'map' and
+    'map_state_only' take a context of up to 64 tokens, e.g. the 34 of two cameras x 16 resampler latents, goal and proprio."""
 
     def __init__(self, clip_style, token_dim=384, clip_token_index=0, num_token=4):
         super().__init__()
