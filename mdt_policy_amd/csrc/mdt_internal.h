@@ -14,6 +14,7 @@
 #include "mdt_resampler.h"
 #include "mdt_hip_train.h"
 #include "mdt_mae.h"
+#include "mdt_route.h"   // which kernel a launch runs on: the shape rules, thresholds and *_supported predicates (host only)
 
 // ---- error plumbing: the message behind mdt_last_error() (thread local, defined in mdt_model.hip) ----
 mdt_status mdt_fail(mdt_status st, const char* fmt, ...);
@@ -92,18 +93,14 @@ __attribute__((visibility("hidden"))) int mdt_switch_env(std::atomic<int>& field
 hipError_t mdt_dev_malloc(void** p, size_t bytes);
 hipError_t mdt_dev_free(void* p);
 
-int mdt_gemm_kchunk(int K, int ln, int cap);
 // the current device's buffer of zeros (stands in for absent bias / LayerNorm-bias vectors); nullptr on failure
 const float* mdt_zeros();
+// the process switches a route (mdt_route.h) depends on, read once per launch; and whether a side job is queued on this host thread
+mdt_route_switches mdt_route_snapshot();
 hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s);
 // the MLP sublayer as one launch (k_mlp): S = mdt_mlp_slices(D) partial slabs at parts + s * part_stride
-bool mdt_mlp_supported(const mdt_gemm_args& fc, const mdt_gemm_args& proj);
-int mdt_mlp_slices(int D);
 hipError_t mdt_launch_mlp(const mdt_gemm_args& fc, const mdt_gemm_args& proj, float* parts, int64_t part_stride, hipStream_t s);
 // the same launch in the three-way bf16 split form (mdt_mlp_split.h): w1s / w2s = split images of fc / proj (mdt_launch_pack_weight_split)
-bool mdt_mlp_split_supported(const mdt_gemm_args& fc, const mdt_gemm_args& proj);
-bool mdt_mlp_split_enabled();
-int mdt_split_min_rows();   // rows from which the split forms of the sampler's launches are used (768: B = 80 2.97 -> 2.89 ms per call, 96 3.08 -> 2.93, 120 3.54 -> 2.96, 128 3.42 -> 2.96; B = 64 loses, 2.44 -> 2.90)
 hipError_t mdt_launch_mlp_split(const mdt_gemm_args& fc, const mdt_gemm_args& proj, const void* w1s, const void* w2s, float* parts,
                                 int64_t part_stride, hipStream_t s);
 // ... and on fp16 pair images (the form the model's launches take)
@@ -139,14 +136,11 @@ hipError_t mdt_launch_attn_chunk(const mdt_attn_args& a, const float* rope_cos, 
 hipError_t mdt_launch_attn_chunk_fwd_train(const mdt_attn_train_args& a, hipStream_t s, int kv_rows = 0);
 hipError_t mdt_launch_attn_chunk_bwd(const mdt_attn_bwd_args& a, hipStream_t s, int kv_rows = 0);
 // one sample's self-attention fused into its output projection p (rollout batch 1); see mdt_kernels.hip
-bool mdt_attn_proj_supported(const mdt_gemm_args& p, int H, int hd, int T, int rope);
 hipError_t mdt_launch_attn_proj(const mdt_gemm_args& p, const float* qkv, int64_t ldq, int H, int hd, int T, int causal,
                                 hipStream_t s);
 // the same for a LARGE batch: the causal attention of a 32-row tile computed in the projection's prologue (k_attn_proj_wide)
-bool mdt_attn_proj_wide_supported(const mdt_gemm_args& p, int H, int hd, int T, int causal, int rope);
 hipError_t mdt_launch_attn_proj_wide(const mdt_gemm_args& p, const float* qkv, int64_t ldq, int H, int hd, int T, hipStream_t s);
 // one workgroup per sample: self-attention -> projection -> collapsed cross-attention (k_attn_xattn); x.y == p.out
-bool mdt_attn_xattn_supported(const mdt_gemm_args& p, const mdt_xapply_args& x, int H, int hd, int T, int causal, int rope);
 hipError_t mdt_launch_attn_xattn(const mdt_gemm_args& p, const float* qkv, int64_t ldq, const mdt_xapply_args& x, int H, int hd,
                                  int T, hipStream_t s, int ctx_div = 1, bool pair = false);   // pair: the projection on p.Wp_pair (fp16 pairs)
 // side jobs (mdt_kernels.hip): small-M products that ride in the launches of the small-M products that follow them
@@ -258,9 +252,7 @@ hipError_t mdt_launch_xattn_fold(const mdt_xfold_args& a, hipStream_t s);
 hipError_t mdt_launch_xattn_fold_n(const mdt_xfold_args* sets, int n, hipStream_t s);  // equal shapes; one launch per 8 sets
 hipError_t mdt_launch_xattn_apply(const mdt_xapply_args& a, hipStream_t s, int ctx_div = 1);
 // the collapsed cross-attention + the LayerNorm-prologue Linear on its output rows in one launch (k_xattn_gemm_smallm)
-bool mdt_xattn_gemm_supported(const mdt_xapply_args& x, const mdt_gemm_args& g);
 hipError_t mdt_launch_xattn_gemm(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s, int ctx_div = 1);
-bool mdt_xattn_apply_supported(int D, int H, int Te, int Ta);
 size_t mdt_xattn_lds_floats(int D, int H);  // LDS floats of the collapsed cross-attention body (xattn_tile)
 // ---- Perceiver resampler kernels ----
 // media (B, T, n, D) + time_pos_emb[t] * mask[b][t] -> out (same shape); mask may be nullptr

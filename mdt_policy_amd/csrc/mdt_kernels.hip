@@ -507,7 +507,6 @@ __global__ __launch_bounds__(512) void k_attn_xattn(mdt_gemm_args a, mdt_attn_pr
 
 // 256 KiB of zeros per device: stands in for absent bias / rowvec / LayerNorm-bias vectors.  ensure_zeros() points
 // g_zeros at the CURRENT device's buffer (a process normally drives one GPU; a second one gets its own buffer).
-static const int ZEROS_FLOATS = 65536;
 static float* g_zeros_dev[MDT_MAX_DEVICES] = {nullptr};
 static thread_local float* g_zeros = nullptr;
 
@@ -534,38 +533,40 @@ static hipError_t ensure_zeros() {
 
 const float* mdt_zeros() { return ensure_zeros() == hipSuccess ? g_zeros : nullptr; }
 
+// the numbers mdt_route.h gives the prologue kinds and the split schemes are the kernels' template arguments
+static_assert(MDT_ROUTE_PRO_PLAIN == PRO_PLAIN && MDT_ROUTE_PRO_LN == PRO_LN && MDT_ROUTE_PRO_LN_MOD_BCAST == PRO_LN_MOD_BCAST &&
+              MDT_ROUTE_PRO_LN_MOD_ROWS == PRO_LN_MOD_ROWS && MDT_ROUTE_SCH_BF16X3 == MDT_SPLIT_BF16X3 && MDT_ROUTE_SCH_F16X2 == MDT_SPLIT_F16X2,
+              "mdt_route.h numbers the template arguments differently");
+
 // f(std::integral_constant<int, PRO_*>()) for the prologue kind (mdt_tiles.h) a product's arguments ask for; Lo = the first kind
 // the caller's kernel is instantiated for (PRO_PLAIN, or PRO_LN where a LayerNorm prologue is a condition of the launch)
 template <int Lo, class F>
 static hipError_t mdt_with_pro(const mdt_gemm_args& a, F f) {
-    const int pro = !a.ln ? PRO_PLAIN : (a.mod != nullptr && a.shift_off >= 0) ? (a.mod_stride == 0 ? PRO_LN_MOD_BCAST : PRO_LN_MOD_ROWS) : PRO_LN;
-    return mdt_with_const<Lo, PRO_LN_MOD_ROWS>(pro, f);
+    return mdt_with_const<Lo, PRO_LN_MOD_ROWS>(mdt_route_pro(a), f);
 }
 
-template <int MTILES, int NTW, int NWAVES, int PRO, bool RES>
-static hipError_t launch_gemm_r(const mdt_gemm_args& a, int kchunk, hipStream_t s) {
-    const int MT = MTILES * 16, NTC = NWAVES * NTW * 16;
-    const int gn = (a.N + NTC - 1) / NTC, gm = (a.M + MT - 1) / MT;
-    const size_t lds = (size_t)MT * (kchunk + 4) * sizeof(float);
-    return mdt_launch_lds<k_gemm<MTILES, NTW, NWAVES, PRO, RES>>(dim3(gn * gm, 1, a.batch > 1 ? a.batch : 1), dim3(64 * NWAVES), lds, s,
-                                                                 a, kchunk, gn, g_zeros);
+// ---- the GEMM bodies' launchers: grid, threads, LDS bytes and chunk length come with the route (mdt_route.h: mdt_route_gemm);
+// what is left here is what needs the template parameters ----
+static dim3 route_grid(const mdt_gemm_route& r) { return dim3(r.gx, r.gy, r.gz); }
+
+template <int MTILES, int NTW, int NWAVES>
+static hipError_t launch_gemm_tile(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {
+    return mdt_with_pro<PRO_PLAIN>(a, [&](auto pro) {
+        constexpr int PRO = decltype(pro)::value;
+        return r.res ? mdt_launch_lds<k_gemm<MTILES, NTW, NWAVES, PRO, true>>(route_grid(r), dim3(r.threads), r.lds, s, a, r.kchunk, r.grid_n, g_zeros)
+                     : mdt_launch_lds<k_gemm<MTILES, NTW, NWAVES, PRO, false>>(route_grid(r), dim3(r.threads), r.lds, s, a, r.kchunk, r.grid_n, g_zeros);
+    });
 }
 
-template <int MTILES, int NTW, int NWAVES, int GLU>
-static hipError_t launch_gemm_glu(const mdt_gemm_args& a, int kchunk, hipStream_t s) {
-    const int MT = MTILES * 16, NTC = NWAVES * NTW * 16;
-    const int gn = (a.N + NTC - 1) / NTC, gm = (a.M + MT - 1) / MT;
-    const size_t lds = (size_t)MT * (kchunk + 4) * sizeof(float);
-    return mdt_launch_lds<k_gemm_glu<MTILES, NTW, NWAVES, GLU>>(dim3(gn * gm), dim3(64 * NWAVES), lds, s, a, kchunk, gn, g_zeros);
+template <int NTW, int GLU>
+static hipError_t launch_gemm_glu(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {
+    return mdt_launch_lds<k_gemm_glu<2, NTW, 4, GLU>>(route_grid(r), dim3(r.threads), r.lds, s, a, r.kchunk, r.grid_n, g_zeros);
 }
 
-template <int MTILES, int NTW, int NWAVES, int LW, bool RES>
-static hipError_t launch_gemm_pipe_r(const mdt_gemm_args& a, int kchunk, hipStream_t s) {
-    const int MT = MTILES * 16, NTC = NWAVES * NTW * 16;
-    const int gn = (a.N + NTC - 1) / NTC, gm = (a.M + MT - 1) / MT;
-    const size_t lds = (size_t)2 * MT * (kchunk + 4) * sizeof(float);  // double-buffered activation chunk
-    return mdt_launch_lds<k_gemm_pipe<MTILES, NTW, NWAVES, LW, RES>>(dim3(gn * gm, 1, a.batch > 1 ? a.batch : 1),
-                                                                     dim3(64 * (NWAVES + LW)), lds, s, a, kchunk, gn, g_zeros);
+template <int MTILES, int NWAVES, int LW>
+static hipError_t launch_gemm_pipe(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {
+    return r.res ? mdt_launch_lds<k_gemm_pipe<MTILES, 1, NWAVES, LW, true>>(route_grid(r), dim3(r.threads), r.lds, s, a, r.kchunk, r.grid_n, g_zeros)
+                 : mdt_launch_lds<k_gemm_pipe<MTILES, 1, NWAVES, LW, false>>(route_grid(r), dim3(r.threads), r.lds, s, a, r.kchunk, r.grid_n, g_zeros);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -580,22 +581,9 @@ __global__ __launch_bounds__(64 * (WM * WN + LW)) void k_gemm_tall(mdt_gemm_args
     //  a stage changed nothing: profiles/r04_gemm_train_shapes.txt)
     gemm_tall_tile<WM, WN, NT, NS, RES, LW>(a, by, bx, lds, zeros, threadIdx.x);
 }
-bool mdt_gemm_tall_supported(const mdt_gemm_args& a) {
-    // (32-bit byte offsets from the operand bases: the activation block and the weight image each below 4 GiB)
-    if ((int64_t)a.M * a.lda >= ((int64_t)1 << 30) || (int64_t)a.N * a.K >= ((int64_t)1 << 30)) return false;
-    return !a.ln && a.a_parts <= 1 && a.batch <= 1 && a.K % MDT_TALL_BK == 0 && (a.N & 15) == 0 && a.M >= 1 && (a.lda & 3) == 0 &&
-           (a.aux_mode == 0 || ((a.aux_mode == 1 || a.aux_mode == 2) && !a.residual));
-}
-template <int WM, int WN, int NT, int NS, bool RES, int LW>
-static hipError_t launch_gemm_tall_r(const mdt_gemm_args& a, hipStream_t s) {
-    constexpr int BM = WM * 64, BN = WN * NT * 16;
-    const int gn = (a.N + BN - 1) / BN, gm = (a.M + BM - 1) / BM;
-    const size_t lds = (size_t)NS * (BM + BN) * MDT_TALL_BK * sizeof(float);
-    return mdt_launch_lds<k_gemm_tall<WM, WN, NT, NS, RES, LW>>(dim3(gn * gm), dim3(64 * (WM * WN + LW)), lds, s, a, gn, g_zeros);
-}
-template <int WM, int WN, int NT, int NS, int LW = 0>
-static hipError_t launch_gemm_tall(const mdt_gemm_args& a, hipStream_t s) {
-    return a.residual ? launch_gemm_tall_r<WM, WN, NT, NS, true, LW>(a, s) : launch_gemm_tall_r<WM, WN, NT, NS, false, LW>(a, s);
+static hipError_t launch_gemm_tall(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {   // 4 + 1 waves 128 x 64, 3 stages
+    return r.res ? mdt_launch_lds<k_gemm_tall<2, 2, 2, 3, true, 1>>(route_grid(r), dim3(r.threads), r.lds, s, a, r.grid_n, g_zeros)
+                 : mdt_launch_lds<k_gemm_tall<2, 2, 2, 3, false, 1>>(route_grid(r), dim3(r.threads), r.lds, s, a, r.grid_n, g_zeros);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -620,95 +608,43 @@ __global__ __launch_bounds__(64 * NWAVES) void k_gemm_ws_split(mdt_gemm_args a, 
     if (chunk * tiles >= ((a.M + 31) >> 5)) return;
     gemm_ws_split_tile<K16, NTW, NWAVES, GLU>(a, panel, chunk, tiles, lds_b, zeros, threadIdx.x);
 }
-// Workgroup = 8 waves x 2 column tiles (256-column panels), one per CU.  Measured and dropped (profiles/r05_ws_ab.txt): 4 waves x 2
-// tiles as two independent workgroups per CU (27.6 vs 27.5 ms per head step), 4 waves x 3 tiles for the N = 576 / 192 products
-// (272 VGPRs: qkv 225 -> 215 us against the tall body, c_proj 81.6 -> 81.0 against the row tiles: not worth a shape).
-static int ws_shape(const mdt_gemm_args& a) {
-    if (a.K == 384) {
-        // one column tile per wave: 128- (8 waves) or 192-column (12 waves) panels.  One round of one workgroup per CU either way;
-        // what differs is how evenly the row tiles divide: cost ~ tiles per workgroup x waves (a SIMD's waves share its matrix pipe).
-        // M = 10240: N = 384 -> 8 waves (3 panels x 80 chunks x 4 tiles), N = 1152 / 1536 -> 12 waves (6 x 40 x 8 / 8 x 32 x 10)
-        const int ntiles = (a.M + 31) / 32;
-        int best = 0, best_cost = 0;
-        for (int nw : {12, 8}) {
-            if (a.N % (nw * 16)) continue;
-            const int panels = a.N / (nw * 16), groups = std::max(1, std::min(256 / (8 * panels), (ntiles + 7) / 8));
-            if (8 * panels > 256) continue;
-            const int tiles = (ntiles + 8 * groups - 1) / (8 * groups), cost = tiles * nw;
-            if (!best || cost < best_cost) { best = nw; best_cost = cost; }
-        }
-        return best;
-    }
-    // 384-column panels, three waves per SIMD, 4 / 2 panels x 64 / 128 row chunks = 256 workgroups: the per-tile epilogue + barrier is
-    // amortised over 18.4 k instead of 12.3 k clocks of MFMA issue and all 256 CUs work (SwishGLU forward 601 -> 544 us, plain 272 -> 248).
-    // Not for the SwishGLU backward epilogue: at 168 VGPRs its u operands cannot be requested a tile ahead (348 -> 448 us)
-    if (a.N % 384 == 0 && a.aux_mode != 4) return 12;
-    return a.N % 256 == 0 ? 8 : 0;
-}
-// the three-way bf16 split of the weight-stationary body (mdt_ws.h): K = 384, 128-column panels (8 waves, one column tile each)
-static bool ws_split_on() { return mdt_switch_env(g_mdt_sw.ws_split, "MDT_HIP_WS_SPLIT", 1) != 0; }
 extern "C" void mdt_op_set_ws_split(int32_t on) { g_mdt_sw.ws_split = on < 0 ? -1 : (on != 0); }
-// split form only: plain K = 192 products whose N is a multiple of 192 but not of 256 (the masked-image head's qkv and output
-// projections, N = 576 / 192) -- twelve waves (three per SIMD) x one column tile.  (Their fp32 form was measured and dropped, above: no gain over the
-// tall body; the split form is 1.4x.)
-static bool ws_split_192(const mdt_gemm_args& a) {
-    return ws_split_on() && a.K == 192 && a.N % 192 == 0 && a.N % 256 != 0 && a.N / 192 <= 32 && a.aux_mode == 0 && a.act == MDT_ACT_NONE;
+// the instantiations the route's shapes name (mdt_route.h: ws_shape, mdt_route_detail::ws): <K16, NTW, NWAVES, GLU>
+static constexpr int ws_key(int k16, int ntw, int nw, int glu) { return ((k16 * 4 + ntw) * 16 + nw) * 8 + glu; }
+template <int K16, int NTW, int NW, int GLU>
+static hipError_t launch_gemm_ws_t(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {
+    return mdt_launch_lds<k_gemm_ws<K16, NTW, NW, GLU>>(route_grid(r), dim3(r.threads), r.lds, s, a, r.tiles, r.grid_n, g_zeros);
 }
-bool mdt_gemm_ws_supported(const mdt_gemm_args& a) {
-    const bool common = !a.ln && a.a_parts <= 1 && a.batch <= 1 && a.M >= 32 && (a.lda & 3) == 0 && (a.ldo & 3) == 0 && !a.residual &&
-                        a.gin == 1 && a.gout == 1 && a.goff == 0 && a.rowvec == nullptr && (int64_t)a.N * a.K < ((int64_t)1 << 30);
-    if (a.K == 384)   // plain rows, or an activation / the training hooks on the epilogue (GLU = 1 instantiation)
-        return common && (a.aux_mode == 0 || ((a.aux_mode == 1 || a.aux_mode == 2) && a.aux != nullptr)) && ws_shape(a) != 0;
-    const bool mode_ok = a.aux_mode == 0 || ((a.aux_mode == 3 || a.aux_mode == 4) && a.aux != nullptr);
-    return common && a.K == 192 && (ws_shape(a) != 0 || ws_split_192(a)) && a.act == MDT_ACT_NONE && mode_ok;
+template <int K16, int NTW, int NW, int GLU>
+static hipError_t launch_gemm_ws_split_t(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {
+    return mdt_launch_lds<k_gemm_ws_split<K16, NTW, NW, GLU>>(route_grid(r), dim3(r.threads), r.lds, s, a, r.tiles, r.grid_n, g_zeros);
 }
-template <int K16, int GLU, int NW, int NTW>
-static hipError_t launch_gemm_ws_t(const mdt_gemm_args& a, hipStream_t s) {
-    const int panels = a.N / (NW * NTW * 16), ntiles = (a.M + 31) / 32;
-    // one round of one workgroup per CU: 8 x panels x groups blocks
-    const int groups = std::max(1, std::min(256 / (8 * panels), (ntiles + 7) / 8));
-    const int chunks = 8 * groups, tiles = (ntiles + chunks - 1) / chunks;
-    const size_t lds = (size_t)2 * 32 * (K16 * 16 + 4) * sizeof(float);
-    return mdt_launch_lds<k_gemm_ws<K16, NTW, NW, GLU>>(dim3(chunks * panels), dim3(64 * NW), lds, s, a, tiles, panels, g_zeros);
-}
-template <int K16, int NTW, int GLU, int NW = 8>
-static hipError_t launch_gemm_ws_split(const mdt_gemm_args& a, hipStream_t s) {
-    const int panels = a.N / (NW * NTW * 16), ntiles = (a.M + 31) / 32;
-    const int chunks = std::max(1, std::min(256 / panels, ntiles)), tiles = (ntiles + chunks - 1) / chunks;
-    const size_t lds = (size_t)2 * 3 * 32 * (2 * K16 * 16 + 32);
-    return mdt_launch_lds<k_gemm_ws_split<K16, NTW, NW, GLU>>(dim3(256), dim3(64 * NW), lds, s, a, tiles, panels, g_zeros);
-}
-static hipError_t launch_gemm_ws(const mdt_gemm_args& a, hipStream_t s) {
-    if (ws_split_on() && a.K == 384 && a.N % 128 == 0 && a.N / 128 <= 32) {
-        const bool hooks = a.aux_mode != 0 || a.act != MDT_ACT_NONE;
-        return hooks ? launch_gemm_ws_split<24, 1, 1>(a, s) : launch_gemm_ws_split<24, 1, 0>(a, s);
+static hipError_t launch_gemm_ws(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {
+    switch (ws_key(r.mtiles, r.ntw, r.nwaves, r.glu)) {   // K = 384: GLU 1 = an activation / the training hooks on the epilogue
+        case ws_key(24, 1, 12, 0): return launch_gemm_ws_t<24, 1, 12, 0>(a, r, s);
+        case ws_key(24, 1, 12, 1): return launch_gemm_ws_t<24, 1, 12, 1>(a, r, s);
+        case ws_key(24, 1, 8, 0): return launch_gemm_ws_t<24, 1, 8, 0>(a, r, s);
+        case ws_key(24, 1, 8, 1): return launch_gemm_ws_t<24, 1, 8, 1>(a, r, s);
+        case ws_key(12, 2, 12, 0): return launch_gemm_ws_t<12, 2, 12, 0>(a, r, s);
+        case ws_key(12, 2, 12, 3): return launch_gemm_ws_t<12, 2, 12, 3>(a, r, s);
+        case ws_key(12, 2, 8, 0): return launch_gemm_ws_t<12, 2, 8, 0>(a, r, s);
+        case ws_key(12, 2, 8, 3): return launch_gemm_ws_t<12, 2, 8, 3>(a, r, s);
+        case ws_key(12, 2, 8, 4): return launch_gemm_ws_t<12, 2, 8, 4>(a, r, s);
+        default: return hipErrorInvalidValue;
     }
-    if (ws_split_on() && a.K == 192 && a.N % 256 == 0 && a.N / 256 <= 32 && a.act == MDT_ACT_NONE &&
-        (a.aux_mode == 0 || a.aux_mode == 3 || a.aux_mode == 4)) {
-        if (a.aux_mode == 3) return launch_gemm_ws_split<12, 2, 3>(a, s);
-        if (a.aux_mode == 4) return launch_gemm_ws_split<12, 2, 4>(a, s);
-        return launch_gemm_ws_split<12, 2, 0>(a, s);
+}
+static hipError_t launch_gemm_ws_split(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {
+    switch (ws_key(r.mtiles, r.ntw, r.nwaves, r.glu)) {
+        case ws_key(24, 1, 8, 0): return launch_gemm_ws_split_t<24, 1, 8, 0>(a, r, s);
+        case ws_key(24, 1, 8, 1): return launch_gemm_ws_split_t<24, 1, 8, 1>(a, r, s);
+        case ws_key(12, 2, 8, 0): return launch_gemm_ws_split_t<12, 2, 8, 0>(a, r, s);
+        case ws_key(12, 2, 8, 3): return launch_gemm_ws_split_t<12, 2, 8, 3>(a, r, s);
+        case ws_key(12, 2, 8, 4): return launch_gemm_ws_split_t<12, 2, 8, 4>(a, r, s);
+        case ws_key(12, 1, 12, 0): return launch_gemm_ws_split_t<12, 1, 12, 0>(a, r, s);
+        default: return hipErrorInvalidValue;
     }
-    if (ws_split_192(a)) return launch_gemm_ws_split<12, 1, 0, 12>(a, s);   // N = 192 / 576 ...: 192-column panels, twelve waves x one column tile
-    if (a.K == 384) {
-        const bool hooks = a.aux_mode != 0 || a.act != MDT_ACT_NONE;
-        if (ws_shape(a) == 12) return hooks ? launch_gemm_ws_t<24, 1, 12, 1>(a, s) : launch_gemm_ws_t<24, 0, 12, 1>(a, s);
-        return hooks ? launch_gemm_ws_t<24, 1, 8, 1>(a, s) : launch_gemm_ws_t<24, 0, 8, 1>(a, s);
-    }
-    if (ws_shape(a) == 12) return a.aux_mode == 3 ? launch_gemm_ws_t<12, 3, 12, 2>(a, s) : launch_gemm_ws_t<12, 0, 12, 2>(a, s);
-    if (a.aux_mode == 3) return launch_gemm_ws_t<12, 3, 8, 2>(a, s);
-    if (a.aux_mode == 4) return launch_gemm_ws_t<12, 4, 8, 2>(a, s);
-    return launch_gemm_ws_t<12, 0, 8, 2>(a, s);
 }
 
-template <int MTILES, int NTW, int NWAVES, int PRO>
-static hipError_t launch_gemm_t(const mdt_gemm_args& a, int kchunk, hipStream_t s) {
-    return a.residual ? launch_gemm_r<MTILES, NTW, NWAVES, PRO, true>(a, kchunk, s)
-                      : launch_gemm_r<MTILES, NTW, NWAVES, PRO, false>(a, kchunk, s);
-}
-
-// activation chunk length: whole K when it fits (always for the LayerNorm prologue), else the largest divisor of K
-// that is a multiple of 16 and <= cap (cap 768 = 97 KiB of LDS for the one-workgroup-per-CU wide tiles, else 384)
 // ------------------------------------------------------------------------------------------------
 // k_gemm_smallm: the same fused GEMM for FEW rows (rollout batches: B = 1 is M = 10 decoder / 4 encoder rows).
 // There the tiled kernel above has N/64 = 6 workgroups, each walking the whole K behind a 6 KB load window:
@@ -742,7 +678,6 @@ __global__ __launch_bounds__(512) void k_gemm_smallm2(mdt_gemm_args a, mdt_gemm_
     }
 }
 
-static constexpr int GEMM_MID_MAX = 1400;  // rows up to which the 16 x 64 tiled geometry is used
 // k_xattn_gemm_smallm: the collapsed cross-attention of sample b and, on its output rows, 16 columns (blockIdx.x) of the
 // LayerNorm + modulate -> Linear that follows (mlp.c_fc) -- rollout batches: the cross-attention launch (one workgroup, 6.5 us
 // of latency per decoder block at B = 1) disappears into the c_fc launch, whose 96 workgroups each repeat it on the MFMA pipe
@@ -759,22 +694,6 @@ __global__ __launch_bounds__(512) void k_xattn_gemm_smallm(mdt_xapply_args x, md
     gemm_smallm_tile<false, true>(a, blockIdx.x, b * x.Ta, s_stat, red, zeros, threadIdx.x, yo, ys, x.Ta);
 }
 
-// rows up to which k_gemm_smallm is used: one row tile; beyond it the tile-count rule in mdt_launch_gemm decides, up to
-// GEMM_SMALLM_ROWS rows (round 1 had 192 rows here, before the half-height tiles)
-static constexpr int GEMM_SMALLM_MAX = 15, GEMM_SMALLM_ROWS = 512;
-
-int mdt_gemm_kchunk(int K, int ln, int cap) {
-    if (ln || K <= 512) return K;
-    for (int c = cap; c >= 16; c -= 16)
-        if (K % c == 0) return c;
-    return 16;
-}
-
-template <int MTILES, int NTW, int NWAVES>
-static hipError_t launch_gemm_pro(const mdt_gemm_args& a, int kchunk, hipStream_t s) {
-    return mdt_with_pro<PRO_PLAIN>(a, [&](auto pro) { return launch_gemm_t<MTILES, NTW, NWAVES, decltype(pro)::value>(a, kchunk, s); });
-}
-
 // the switch table (mdt_internal.h) and its environment helper
 mdt_switches g_mdt_sw;
 int mdt_switch_env(std::atomic<int>& field, const char* var, int dflt, bool latch) {
@@ -786,20 +705,7 @@ int mdt_switch_env(std::atomic<int>& field, const char* var, int dflt, bool latc
     return v;
 }
 
-// WStream (mdt_tiles.h) addresses a weight image with 32-bit byte offsets from its base: every launcher that feeds one checks
-// the image size (mdt_launch_gemm does for the GEMMs; the fused MLP and attn_xattn tiles bound N and K by their shape rules)
-static bool w_image_ok(int64_t N, int64_t K) { return N * K < ((int64_t)1 << 30); }
-
-// Self-attention of ONE sample fused into its output projection (k_attn_proj_smallm).  `p` is the projection's GEMM
-// (A ignored: the attention output never reaches memory; M = the sample's T rows); q / k / v are the three column
-// blocks of the (T, 3 K) qkv rows.  Supported: 8 heads of 16 / 32 / 48 / 64, T <= 16, no RoPE, plain output rows.
-bool mdt_attn_proj_supported(const mdt_gemm_args& p, int H, int hd, int T, int rope) {
-    return w_image_ok(p.N, p.K) && H == 8 && (hd == 16 || hd == 32 || hd == 48 || hd == 64) && p.K == H * hd && T >= 1 && T <= 16 && p.M >= T &&
-           p.M % T == 0 && p.M / T <= 64 && (p.rows_per_sample == T || p.M == T) && !rope &&
-           !(p.N & 15) && p.gin == 1 && p.gout == 1 && p.goff == 0 && !p.ln && p.act == MDT_ACT_NONE && p.rowvec == nullptr &&
-           p.batch <= 1;
-}
-
+// Self-attention of ONE sample fused into its output projection (k_attn_proj_smallm; mdt_route.h: mdt_attn_proj_supported)
 template <int HD>
 static hipError_t launch_attn_proj_t(const mdt_gemm_args& p, const float* qkv, int64_t ldq, int T, int causal, hipStream_t s) {
     const size_t lds = (size_t)8 * 3 * T * (HD + 4) * sizeof(float);
@@ -820,16 +726,7 @@ hipError_t mdt_launch_attn_proj(const mdt_gemm_args& p, const float* qkv, int64_
     }
 }
 
-static hipError_t launch_gemm_merge(const mdt_gemm_args& a, hipStream_t s);
-static bool gemm_ln_split_applies(const mdt_gemm_args& a);
-static hipError_t launch_gemm_ln_split(const mdt_gemm_args& a, hipStream_t s);
-
-bool mdt_attn_proj_wide_supported(const mdt_gemm_args& p, int H, int hd, int T, int causal, int rope) {
-    return w_image_ok(p.N, p.K) && H == 8 && (hd == 16 || hd == 32 || hd == 48) && p.K == H * hd && T >= 1 && T <= 16 && causal && !rope && p.residual &&
-           p.M >= T && p.M % T == 0 && p.rows_per_sample == T && !(p.N & 15) && p.gin == 1 && p.gout == 1 && p.goff == 0 && !p.ln &&
-           p.act == MDT_ACT_NONE && p.rowvec == nullptr && p.batch <= 1 && !p.aux_mode;
-}
-
+// the same for a LARGE batch (k_attn_proj_wide; mdt_route.h: mdt_attn_proj_wide_supported)
 template <int HD, int TKC>
 static hipError_t launch_attn_proj_wide_t(const mdt_gemm_args& p, const mdt_attn_pro& ap, hipStream_t s) {
     const int gn = (p.N + 127) / 128, gm = (p.M + 31) / 32;
@@ -851,16 +748,7 @@ hipError_t mdt_launch_attn_proj_wide(const mdt_gemm_args& p, const float* qkv, i
     }
 }
 
-bool mdt_xattn_apply_supported(int D, int H, int Te, int Ta);
-
-// Self-attention + projection + collapsed cross-attention of one sample per workgroup: `p` = the projection's arguments
-// (as for mdt_launch_attn_proj_wide), `x` = the cross-attention's (x.y == p.out).  Head dimension 48 (d = 384).
-bool mdt_attn_xattn_supported(const mdt_gemm_args& p, const mdt_xapply_args& x, int H, int hd, int T, int causal, int rope) {
-    return mdt_attn_proj_wide_supported(p, H, hd, T, causal, rope) && hd == 48 && p.N == p.K && p.ldo == p.N && x.y == p.out &&
-           x.D == p.N && x.H == H && H == 8 && x.Ta == T && (int64_t)x.B * T == p.M &&
-           mdt_xattn_apply_supported(x.D, x.H, x.Te, x.Ta);
-}
-
+// Self-attention + projection + collapsed cross-attention of one sample per workgroup (mdt_route.h: mdt_attn_xattn_supported)
 // (both forms: 101 632 B at d = 384 -- the pair form keeps its 25.6 KB two-part activation tile inside xattn_tile's scratch and
 //  uses 64 B of the fp32 tile's place for the rows' maxima)
 template <int HD, int TKC, bool PAIR>
@@ -890,10 +778,6 @@ hipError_t mdt_launch_attn_xattn(const mdt_gemm_args& p, const float* qkv, int64
 // Only small-M products are accepted (M <= 16 rows, the small-M kernel's own shape rules); anything else is launched at once.
 static thread_local std::vector<mdt_gemm_args> g_side_jobs;
 static thread_local size_t g_side_next = 0;
-static bool smallm_shape_ok(const mdt_gemm_args& a) {
-    return a.M >= 1 && a.M <= 15 && (!a.ln || a.K <= 512) && a.batch <= 1 && a.K <= 4096 && !a.aux_mode && a.a_parts <= 1 &&
-           a.N <= ZEROS_FLOATS && a.K <= ZEROS_FLOATS && !(a.N & 15) && (int64_t)a.N * a.K < ((int64_t)1 << 30);
-}
 // process-wide (the queue itself is per host thread): atomics, host threads may drive different handles side by side
 static std::atomic<int64_t> g_side_paired{0};    // launches that took a side job along (mdt_op_side_jobs_paired)
 static bool side_enabled() { return g_mdt_sw.side_jobs != 0 && g_mdt_sw.gemm_geometry == 0; }
@@ -936,154 +820,7 @@ hipError_t mdt_gemm_side_flush(hipStream_t s) {
     return hipSuccess;
 }
 
-hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
-    const int force = g_mdt_sw.gemm_geometry;   // mdt_op_set_gemm_geometry
-    if (a.N > ZEROS_FLOATS || a.K > ZEROS_FLOATS) return hipErrorInvalidValue;
-    // the weight stream is addressed with 32-bit byte offsets from the image's base (buffer loads, mdt_tiles.h: WStream)
-    if ((int64_t)a.N * a.K >= ((int64_t)1 << 30)) return hipErrorInvalidValue;
-    hipError_t ze = ensure_zeros();
-    if (ze != hipSuccess) return ze;
-    // (not for the batched split-K products of the weight gradients: few output rows there come with a DEEP reduction --
-    // N = 192 layers of the masked-image decoder: 595 us as 16-column split-K tiles vs ~300 us tiled)
-    // the training hooks of the epilogue (aux) exist in the plain-prologue, non-residual tiled kernels only
-    if (a.aux_mode && (!a.aux || a.ln || a.residual || a.batch > 1 || a.K > 512)) return hipErrorInvalidValue;
-    if (a.aux_mode == 3 || a.aux_mode == 4) {  // SwishGLU on the epilogue: own kernels (4 waves; forward: pairs of column tiles per wave)
-        if ((a.N & (a.aux_mode == 3 ? 31 : 15)) || a.gin != 1 || a.gout != 1 || a.goff != 0 || a.act != MDT_ACT_NONE)
-            return hipErrorInvalidValue;
-        // from 8192 rows on, K = 192: the weight-stationary body (mdt_ws.h) with the same epilogues -- round 5.  The masked-image
-        // head's two SwishGLU products at B = 1024 (104448 rows).
-        if (a.M >= 8192 && force <= 0 && mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
-        const int kc = mdt_gemm_kchunk(a.K, 0, 384);
-        if (a.aux_mode == 3)
-            return (a.N % 256 == 0) ? launch_gemm_glu<2, 4, 4, 3>(a, kc, s) : launch_gemm_glu<2, 2, 4, 3>(a, kc, s);
-        return (a.N % 192 == 0) ? launch_gemm_glu<2, 3, 4, 4>(a, kc, s) : launch_gemm_glu<2, 2, 4, 4>(a, kc, s);
-    }
-    if (gemm_ln_split_applies(a)) return launch_gemm_ln_split(a, s);   // the wide LayerNorm-prologue products in a split form (Wp_split: bf16 x 3, Wp_pair: fp16 x 2)
-    if (a.a_parts > 1) return launch_gemm_merge(a, s);
-    // ... and beyond one row tile, the products whose half-height (16 x 64) tiling would leave most of the chip empty keep the
-    // split-K kernel, which has 4x the workgroups: fewer than 60 tiles behind a LayerNorm prologue (every 16-column workgroup
-    // repeats the row statistics), fewer than 100 / 160 (up to 192 / 512 rows) behind a plain one -- the two N = 384 residual
-    // projections of a block at B = 12 ... 32.  Measured per sampler call (tools/latency.py, profiles/r04_lowbatch.txt):
-    // B = 8 1.79 -> 1.69 ms, 10 2.06 -> 1.72, 16 2.43 -> 1.74, 19 2.93 -> 2.07, 24 2.36 -> 2.17, 32 2.39 -> 2.19.
-    const int64_t tiles6 = (int64_t)((a.M + 15) / 16) * ((a.N + 63) / 64);
-    const bool few_tiles = a.M <= GEMM_SMALLM_ROWS && tiles6 < (a.ln ? 60 : (a.M <= 192 ? 100 : 160));
-    // (geometry hook -1: the split-K kernel wherever it applies -- tests that pin it against its fused variants)
-    if ((a.M <= GEMM_SMALLM_MAX || few_tiles || force < 0) && force <= 0 && (!a.ln || a.K <= 512) && a.batch <= 1 && a.K <= 4096 && !a.aux_mode) {
-        if (g_side_next < g_side_jobs.size() && a.batch <= 1 && a.M <= 16 * 64) {  // a queued side job rides in this launch
-            const mdt_gemm_args b = g_side_jobs[g_side_next++];
-            ++g_side_paired;
-            const int nxa = a.N >> 4, nya = (a.M + 15) >> 4;
-            hipLaunchKernelGGL(k_gemm_smallm2, dim3(nxa * nya + (b.N >> 4) * ((b.M + 15) >> 4)), dim3(512), 0, s, a, b, nxa, nya, g_zeros);
-            return hipGetLastError();
-        }
-        hipLaunchKernelGGL(k_gemm_smallm, dim3(a.N >> 4, (a.M + 15) >> 4, a.batch > 1 ? a.batch : 1), dim3(512), 0, s, a, g_zeros);
-        return hipGetLastError();
-    }
-    // Geometry selection (rows are in tiles of 32).  The decoder at B = 256 has 80 row tiles for 256 CUs:
-    //   wide  (8 waves, 32 x 512 / 32 x 384): N >= 1024 -> 240 workgroups, each activation tile re-read 3x
-    //   mid   (8 waves, 32 x 128)           : N  < 1024 -> 240 workgroups for N = 384
-    //   small (4 waves, 32 x 64)            : few row tiles (small batches): more, smaller workgroups
-    const int gm = (a.M + 31) / 32;
-    // Pick the geometry with the best (wave fill) x (tile efficiency): workgroups run in waves of ~256 (one per CU), so
-    // a count just above a multiple of 256 wastes most of its last wave (M = 10240, N = 384 on 32x384 tiles: 320
-    // workgroups = 1.25 waves); wide tiles amortise the per-workgroup prologue / epilogue better than narrow ones.
-    const int tile_n[5] = {0, 64, 128, 384, 512};
-    const float eff[5] = {0.f, 0.85f, 0.92f, 1.0f, 1.0f};
-    int geo = 1;
-    float best = -1.f;
-    for (int g = 4; g >= 1; --g) {
-        const int cols = (a.N + tile_n[g] - 1) / tile_n[g];
-        const int cnt = gm * cols;
-        const float fill = (float)cnt / (float)(((cnt + 255) / 256) * 256);
-        const float used = (float)a.N / (float)(cols * tile_n[g]);   // columns of the last tile that are real work
-        const float score = fill * eff[g] * used;
-        if (score > best) { best = score; geo = g; }
-    }
-    // deep K in several LDS chunks (mlp.c_proj and its kin, K = 4d) at large row counts: co-resident 4-wave 32 x 128
-    // workgroups beat the 8-wave loader-wave kernel (tools/gemm_micro.py, N = 384, K = 1536: M = 10240 116 vs 131 us,
-    // M = 5120 60 vs 66 us; at M = 2560 the loader-wave kernel still wins, 37.7 vs 42.5 us)
-    if (geo == 2 && !a.ln && a.K > 512 && a.M >= 4096) geo = 5;
-    // mid-size row counts (batches of ~20..140 chunks, and the training path's 384..1536-row dW products): half-height
-    // tiles double the workgroup count; measured 4-17 % faster per sampler call up to M ~ 1400, slower beyond 2000
-    // ... unless the output is so wide that they would be thousands (the stacked adaLN projection of a training batch:
-    // 1024 x 9216 -> 9216 workgroups that each re-read their weight tile): then the scored choice stands
-    if (a.M <= GEMM_MID_MAX && (int64_t)((a.M + 15) / 16) * ((a.N + 63) / 64) <= 4096) {
-        geo = 6;
-        // ... except where 4-wave 32 x 192 tiles come out as (nearly) whole rounds of one workgroup per CU: the encoder's
-        // and the B ~ 120..140 decoder's wide products (tools/gemm_shapes.py: 1024 x 1536 22.0 -> 18.3 us, 1024 x 3072 33.7 ->
-        // 28.0, 1280 x 1152 21.6 -> 17.8; 1280 x 1536 -- 320 tiles -- 27.8 vs 28.5: stays; 1024 x 1152 -- 192 tiles -- wins
-        // alone, 18.9 -> 17.5, and loses inside the encoder, 18.1 -> 19.5: stays)
-        if (a.N % 192 == 0 && a.N >= 1152 && a.K <= 512 && a.batch <= 1) {
-            const int cnt9 = gm * (a.N / 192);
-            if ((float)cnt9 / (float)(((cnt9 + 255) / 256) * 256) >= 0.9f) geo = 9;
-        }
-    }
-    // training-sized row counts without a LayerNorm prologue (forward / input-gradient products of a B = 1024 step, the
-    // masked-image head's 104 k rows): 4 waves x 32 x 192 tiles -- two or three co-resident per CU, each weight fragment reused by
-    // one wave only -- beat every 8-wave geometry whenever N is a multiple of 192 (tools/gemm_train_shapes.py: 10240 x 1536 x 384
-    // 126 -> 107 us, 104448 x 192 x 768 372 -> 282 us, 104448 x 576 x 192 332 -> 233 us); N = 384 keeps the choices above
-    // (36.5 vs 38.4 us at K = 384, the co-resident 32 x 128 tiles at K = 1536)
-    if (!a.ln && a.M >= 4096 && a.N % 192 == 0 && a.N != 384 && a.batch <= 1) geo = 9;
-    // ... and from 8192 rows on the TALL body (mdt_tall.h: 128-row tiles, both operands staged in LDS by LDS-DMA, each staged
-    // element used by 2-4 waves) where the column count is a multiple of its 64-wide tiles: the forward / input-gradient
-    // products of a B = 1024 training step and the masked-image head's 104 k rows (tools/gemm_train_shapes.py,
-    // profiles/r04_gemm_train_shapes.txt: 104448 x 576 x 192 249 -> 213-231 us, 104448 x 192 x 768 290 -> 263-270,
-    // 10240 x 384 x 1536 124 -> 105-112, 10240 x 1152 x 384 94 -> 88-92; 10240 x 384 x 384 unchanged, 4096 rows lose)
-    // ... and the K = 192 products among them whose column count is a multiple of 256 on the weight-stationary body (mdt_ws.h)
-    if (a.M >= 8192 && (a.aux_mode == 0 || a.K == 384) && force <= 0 && mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
-    if (a.M >= 8192 && a.N % 64 == 0 && (a.N > 384 || a.K > 384) && a.batch <= 1 && mdt_gemm_tall_supported(a)) geo = 23;
-    if (a.batch > 1) geo = 5;  // split-K partial products (deep reductions): geometry chosen for those
-    if (force > 0) geo = force;
-    if (geo == 30) {  // forced: the weight-stationary body (tests pin it against the other bodies)
-        if (mdt_gemm_ws_supported(a)) return launch_gemm_ws(a, s);
-        geo = 0;
-    }
-    if (geo >= 10 && (geo != 23 || !mdt_gemm_tall_supported(a))) geo = 0;  // (forced geometry on a product the tall body does not take)
-    switch (geo) {
-        // the tall body (mdt_tall.h): 128-row tiles, operands by LDS-DMA, ONE loader wave issuing every DMA request of the workgroup.
-        // (Round 4 also carried 128 x 128 / 128 x 64 / 128 x 96 tiles without the loader wave -- geometries 10 / 12 / 16 -- which no
-        //  dispatcher rule reached after tools/gemm_train_shapes.py had measured them: pruned in round 5.)
-        case 23: return launch_gemm_tall<2, 2, 2, 3, 1>(a, s);  // 4 + 1 waves 128 x 64,  3 stages (72 KiB: two per CU)
-        case 1: return launch_gemm_pro<2, 1, 4>(a, mdt_gemm_kchunk(a.K, a.ln, 384), s);
-        case 2:
-            if (!a.ln && a.K > 512) {  // multi-chunk K: loader waves double-buffer the activation chunk
-                const int kc = mdt_gemm_kchunk(a.K, 0, 384);
-                return a.residual ? launch_gemm_pipe_r<2, 1, 8, 4, true>(a, kc, s)
-                                  : launch_gemm_pipe_r<2, 1, 8, 4, false>(a, kc, s);
-            }
-            return launch_gemm_pro<2, 1, 8>(a, mdt_gemm_kchunk(a.K, a.ln, 768), s);
-        case 3: return launch_gemm_pro<2, 3, 8>(a, mdt_gemm_kchunk(a.K, a.ln, 768), s);
-        case 4: return launch_gemm_pro<2, 4, 8>(a, mdt_gemm_kchunk(a.K, a.ln, 768), s);
-        case 6: {
-            // 4 waves 16 x 64.  Deep K (the encoder's / a mid batch's c_proj, K = 4d in four LDS chunks): with two LOADER waves that
-            // double-buffer the activation chunk -- as a single-buffer loop each chunk was a memory round trip of its own in front of
-            // its 24 k-steps, and half-height tiles have few workgroups per CU to hide it
-            // (up to one workgroup per CU: beyond that the co-resident workgroups hide each other's round trips -- the encoder's
-            //  1024-row c_proj, 384 workgroups, measured +0.1 % with the loader waves)
-            if (!a.ln && a.K > 512 && !a.aux_mode && (int64_t)((a.M + 15) / 16) * ((a.N + 63) / 64) <= 256) {
-                const int kc = mdt_gemm_kchunk(a.K, 0, 384);
-                return a.residual ? launch_gemm_pipe_r<1, 1, 4, 2, true>(a, kc, s) : launch_gemm_pipe_r<1, 1, 4, 2, false>(a, kc, s);
-            }
-            return launch_gemm_pro<1, 1, 4>(a, mdt_gemm_kchunk(a.K, a.ln, 384), s);
-        }
-        case 7: return launch_gemm_pro<4, 2, 4>(a, mdt_gemm_kchunk(a.K, a.ln, 384), s);  // 4 waves 64 x 128 (deep-K products)
-        case 8: return launch_gemm_pro<2, 4, 4>(a, mdt_gemm_kchunk(a.K, a.ln, 384), s);  // 4 waves 32 x 256: two workgroups per CU
-        case 9: return launch_gemm_pro<2, 3, 4>(a, mdt_gemm_kchunk(a.K, a.ln, 384), s);  // 4 waves 32 x 192
-        default: return launch_gemm_pro<2, 2, 4>(a, mdt_gemm_kchunk(a.K, a.ln, 384), s);
-    }
-}
-
-extern "C" void mdt_op_set_gemm_geometry(int32_t geo) { g_mdt_sw.gemm_geometry = geo; }
-
-// ---- fused MLP sublayer (k_mlp) ----
-bool mdt_mlp_supported(const mdt_gemm_args& f, const mdt_gemm_args& p) {
-    const int D = f.K;
-    return D >= 128 && D <= 512 && D % 128 == 0 && f.N == 4 * D && p.N == D && p.K == 4 * D && f.ln && f.batch <= 1 &&
-           f.gin == 1 && f.gout == 1 && f.goff == 0 && f.rowvec == nullptr && !f.aux_mode && f.a_parts <= 1 && f.M >= 1 &&
-           f.rows_per_sample >= 1 && p.rows_per_sample >= 1;
-}
-int mdt_mlp_slices(int D) { return 4 * D / 512; }
-
+// ---- fused MLP sublayer (k_mlp; mdt_route.h: mdt_mlp_supported, mdt_mlp_slices) ----
 // mlp_tile's wave schedule: low byte = k-steps the second wave of a SIMD starts behind the first (0: lockstep, workgroup
 // barrier between the two products), | 256 = MFMA loops at raised issue priority.  Measured at B = 256 (
 // profiles/r03_mlp_skew_ab.txt): 0 -> 4.89, 6 -> 4.86, 18 | 256 -> 4.82 ms per sampler call.  The hook: tests.
@@ -1115,36 +852,24 @@ __global__ __launch_bounds__(512) void k_gemm_ln_split(mdt_gemm_args a, int grid
     const int by = logical / grid_n, bx = logical - by * grid_n;
     gemm_ln_split_tile<ND, NTW, PRO, XP, SCH>(a, by, bx, lds_c, zeros, threadIdx.x);
 }
-template <int ND, int NTW, int PRO, int XP, int SCH>
-static hipError_t launch_gemm_ln_split_t(const mdt_gemm_args& a, hipStream_t s) {
-    const int gn = a.N / (8 * NTW * 16), gm = (a.M + 31) / 32;
-    const int lds = gemm_ln_split_lds_bytes(128 * ND, SCH);
-    return mdt_launch_lds<k_gemm_ln_split<ND, NTW, PRO, XP, SCH>>(dim3(gn * gm), dim3(512), lds, s, a, gn, g_zeros);
-}
-template <int ND, int NTW, int SCH>
-static hipError_t launch_gemm_ln_split_pro(const mdt_gemm_args& a, hipStream_t s) {
-    const int xp = a.a_parts >= 2 && a.a_parts <= 4 ? a.a_parts : 1;   // one array, or the sum of 2..4 slabs
+static_assert(mdt_route_ln_split_lds(384, MDT_ROUTE_SCH_F16X2) == (size_t)gemm_ln_split_lds_bytes(384, MDT_SPLIT_F16X2) &&
+              mdt_route_ln_split_lds(512, MDT_ROUTE_SCH_F16X2) == (size_t)gemm_ln_split_lds_bytes(512, MDT_SPLIT_F16X2) &&
+              mdt_route_ln_split_lds(384, MDT_ROUTE_SCH_BF16X3) == (size_t)gemm_ln_split_lds_bytes(384, MDT_SPLIT_BF16X3) &&
+              mdt_route_ln_split_lds(512, MDT_ROUTE_SCH_BF16X3) == (size_t)gemm_ln_split_lds_bytes(512, MDT_SPLIT_BF16X3),
+              "mdt_route.h sizes the split tile's LDS differently from the tile (mdt_mlp_split.h)");
+template <int ND, int SCH>
+static hipError_t launch_gemm_ln_split_t(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {
     return mdt_with_pro<PRO_LN>(a, [&](auto pro) {
-        return mdt_with_const<1, 4>(xp, [&](auto x) { return launch_gemm_ln_split_t<ND, NTW, decltype(pro)::value, decltype(x)::value, SCH>(a, s); });
+        return mdt_with_const<1, 4>(r.xp, [&](auto x) {
+            return mdt_launch_lds<k_gemm_ln_split<ND, 3, decltype(pro)::value, decltype(x)::value, SCH>>(route_grid(r), dim3(r.threads), r.lds, s, a,
+                                                                                                           r.grid_n, g_zeros);
+        });
     });
 }
-// which products take it: the split image is there, LayerNorm prologue over whole rows of K = 384, column count a multiple of the
-// 384-wide panels, plain output rows, and enough rows that the wide tiles are the choice anyway (the fused MLP's threshold)
-static bool gemm_ln_split_shape(const mdt_gemm_args& a) {
-    return a.ln && (a.K == 384 || a.K == 512) && a.N % 384 == 0 && a.M >= 1 &&
-           a.batch <= 1 && !a.residual && a.gin == 1 && a.gout == 1 && a.goff == 0 && a.rowvec == nullptr && !a.aux_mode &&
-           a.a_parts <= 4 && (a.lda & 3) == 0 && (a.ldo & 3) == 0;
-}
-static bool gemm_ln_split_applies(const mdt_gemm_args& a) {
-    return (a.Wp_split != nullptr || a.Wp_pair != nullptr) && mdt_mlp_split_enabled() && gemm_ln_split_shape(a) &&
-           a.M >= mdt_split_min_rows() && g_mdt_sw.gemm_geometry == 0;
-}
-static hipError_t launch_gemm_ln_split(const mdt_gemm_args& a, hipStream_t s) {
-    // (the tile is written for any D <= 512 and 256-wide panels too; instantiated for the two shipped widths: MDT-V d = 384, MDT d = 512)
-    // (Wp_split, where given, keeps its three-way bf16 form; the fp16 pair image otherwise)
-    if (a.Wp_split == nullptr)
-        return a.K == 512 ? launch_gemm_ln_split_pro<4, 3, MDT_SPLIT_F16X2>(a, s) : launch_gemm_ln_split_pro<3, 3, MDT_SPLIT_F16X2>(a, s);
-    return a.K == 512 ? launch_gemm_ln_split_pro<4, 3, MDT_SPLIT_BF16X3>(a, s) : launch_gemm_ln_split_pro<3, 3, MDT_SPLIT_BF16X3>(a, s);
+static hipError_t launch_gemm_ln_split(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {
+    if (r.sch == MDT_SPLIT_F16X2)
+        return r.mtiles == 4 ? launch_gemm_ln_split_t<4, MDT_SPLIT_F16X2>(a, r, s) : launch_gemm_ln_split_t<3, MDT_SPLIT_F16X2>(a, r, s);
+    return r.mtiles == 4 ? launch_gemm_ln_split_t<4, MDT_SPLIT_BF16X3>(a, r, s) : launch_gemm_ln_split_t<3, MDT_SPLIT_BF16X3>(a, r, s);
 }
 
 // the pair form on its own, at any row count and whatever the switches say (mdt_op_gemm_ln_pair)
@@ -1153,17 +878,15 @@ hipError_t mdt_launch_gemm_ln_pair(const mdt_gemm_args& a, hipStream_t s) {
     if (!mdt_gemm_ln_pair_supported(a)) return hipErrorInvalidValue;
     hipError_t ze = ensure_zeros();
     if (ze != hipSuccess) return ze;
-    return a.K == 512 ? launch_gemm_ln_split_pro<4, 3, MDT_SPLIT_F16X2>(a, s) : launch_gemm_ln_split_pro<3, 3, MDT_SPLIT_F16X2>(a, s);
+    mdt_gemm_route r;
+    r.pro = mdt_route_pro(a);
+    mdt_route_detail::ln_split(r, a, MDT_ROUTE_SCH_F16X2);
+    return launch_gemm_ln_split(a, r, s);
 }
 
 // ---- the fused MLP sublayer in the split forms (k_mlp_split: three-way bf16, or the two-way fp16 pair split) ----
 // MDT_HIP_MLP_SPLIT / mdt_op_set_mlp_split: 0 = the fp32 launch everywhere
-bool mdt_mlp_split_enabled() { return mdt_switch_env(g_mdt_sw.mlp_split, "MDT_HIP_MLP_SPLIT", 1) != 0; }
 extern "C" void mdt_op_set_mlp_split(int32_t on) { g_mdt_sw.mlp_split = on < 0 ? -1 : (on != 0); }
-int mdt_split_min_rows() { return 768; }
-bool mdt_mlp_split_supported(const mdt_gemm_args& f, const mdt_gemm_args& p) {
-    return mdt_mlp_supported(f, p);
-}
 template <int NTW2, int PRO, int SCH>
 static hipError_t launch_mlp_split_t(const mdt_gemm_args& f, const mdt_gemm_args& p, const void* w1s, const void* w2s, float* parts,
                                      int64_t part_stride, hipStream_t s) {
@@ -1173,49 +896,98 @@ static hipError_t launch_mlp_split_t(const mdt_gemm_args& f, const mdt_gemm_args
     return mdt_launch_lds<k_mlp_split<NTW2, PRO, SCH>>(dim3(8 * per), dim3(512), lds, s, f, p, (const char*)w1s, (const char*)w2s, parts,
                                                   part_stride, S, gm, g_zeros);
 }
-hipError_t mdt_launch_mlp_split(const mdt_gemm_args& f, const mdt_gemm_args& p, const void* w1s, const void* w2s, float* parts,
-                                int64_t part_stride, hipStream_t s) {
-    if (!mdt_mlp_split_supported(f, p) || !w1s || !w2s) return hipErrorInvalidValue;
+// w1 / w2: the images of fc / proj in the scheme SCH (mdt_launch_pack_weight_split, mdt_launch_pack_weight_pair)
+template <int SCH>
+static hipError_t launch_mlp_split_sch(const mdt_gemm_args& f, const mdt_gemm_args& p, const void* w1, const void* w2, float* parts,
+                                       int64_t part_stride, hipStream_t s) {
+    if (!mdt_mlp_split_supported(f, p) || !w1 || !w2) return hipErrorInvalidValue;
     hipError_t ze = ensure_zeros();
     if (ze != hipSuccess) return ze;
     return mdt_with_const<1, 4>(std::min(f.K / 128, 4), [&](auto ntw2) {
         return mdt_with_pro<PRO_LN>(f, [&](auto pro) {
-            return launch_mlp_split_t<decltype(ntw2)::value, decltype(pro)::value, MDT_SPLIT_BF16X3>(f, p, w1s, w2s, parts, part_stride, s);
+            return launch_mlp_split_t<decltype(ntw2)::value, decltype(pro)::value, SCH>(f, p, w1, w2, parts, part_stride, s);
         });
     });
+}
+hipError_t mdt_launch_mlp_split(const mdt_gemm_args& f, const mdt_gemm_args& p, const void* w1s, const void* w2s, float* parts,
+                                int64_t part_stride, hipStream_t s) {
+    return launch_mlp_split_sch<MDT_SPLIT_BF16X3>(f, p, w1s, w2s, parts, part_stride, s);
 }
 // the same launch on fp16 pair images (mdt_launch_pack_weight_pair) of fc / proj
 hipError_t mdt_launch_mlp_pair(const mdt_gemm_args& f, const mdt_gemm_args& p, const void* w1p, const void* w2p, float* parts,
                                int64_t part_stride, hipStream_t s) {
-    if (!mdt_mlp_split_supported(f, p) || !w1p || !w2p) return hipErrorInvalidValue;
-    hipError_t ze = ensure_zeros();
-    if (ze != hipSuccess) return ze;
-    return mdt_with_const<1, 4>(std::min(f.K / 128, 4), [&](auto ntw2) {
-        return mdt_with_pro<PRO_LN>(f, [&](auto pro) {
-            return launch_mlp_split_t<decltype(ntw2)::value, decltype(pro)::value, MDT_SPLIT_F16X2>(f, p, w1p, w2p, parts, part_stride, s);
+    return launch_mlp_split_sch<MDT_SPLIT_F16X2>(f, p, w1p, w2p, parts, part_stride, s);
+}
+
+// a LayerNorm-prologue GEMM whose rows are the sum of a.a_parts slabs (2..4): wide tiles only
+template <int NTW>
+static hipError_t launch_gemm_merge(const mdt_gemm_args& a, const mdt_gemm_route& r, hipStream_t s) {
+    return mdt_with_pro<PRO_LN>(a, [&](auto pro) {   // (a_parts outside 2..4 is refused)
+        return mdt_with_const<2, 4>(r.xp, [&](auto x) {
+            return mdt_launch_lds<k_gemm_merge<NTW, decltype(pro)::value, decltype(x)::value>>(route_grid(r), dim3(r.threads), r.lds, s, a, r.kchunk,
+                                                                                               r.grid_n, g_zeros);
         });
     });
 }
 
-// a LayerNorm-prologue GEMM whose rows are the sum of a.a_parts slabs (2..4): wide tiles only
-template <int NTW, int PRO, int XP>
-static hipError_t launch_gemm_merge_t(const mdt_gemm_args& a, hipStream_t s) {
-    const int NTC = 8 * NTW * 16;
-    const int gn = (a.N + NTC - 1) / NTC, gm = (a.M + 31) / 32;
-    const size_t lds = (size_t)32 * (a.K + 4) * sizeof(float);
-    return mdt_launch_lds<k_gemm_merge<NTW, PRO, XP>>(dim3(gn * gm), dim3(512), lds, s, a, a.K, gn, g_zeros);
+// ---- mdt_launch_gemm: snapshot, route, one switch from the route to the instantiation ----
+// the process switches a route depends on, read once (the two with an environment variable through mdt_switch_env), and whether a
+// side job is queued on this host thread
+mdt_route_switches mdt_route_snapshot() {
+    mdt_route_switches sw;
+    sw.gemm_geometry = g_mdt_sw.gemm_geometry;
+    sw.attn_wide_min = g_mdt_sw.attn_wide_min;
+    sw.mlp_fuse_min = g_mdt_sw.mlp_fuse_min;
+    sw.mlp_split = mdt_switch_env(g_mdt_sw.mlp_split, "MDT_HIP_MLP_SPLIT", 1) != 0;
+    sw.ws_split = mdt_switch_env(g_mdt_sw.ws_split, "MDT_HIP_WS_SPLIT", 1) != 0;
+    sw.side_pending = g_side_next < g_side_jobs.size();
+    return sw;
 }
-template <int NTW>
-static hipError_t launch_gemm_merge_pro(const mdt_gemm_args& a, hipStream_t s) {
-    return mdt_with_pro<PRO_LN>(a, [&](auto pro) {   // (a_parts outside 2..4 is refused)
-        return mdt_with_const<2, 4>(a.a_parts, [&](auto x) { return launch_gemm_merge_t<NTW, decltype(pro)::value, decltype(x)::value>(a, s); });
-    });
+
+hipError_t mdt_launch_gemm(const mdt_gemm_args& a, hipStream_t s) {
+    const mdt_gemm_route r = mdt_route_gemm(a, mdt_route_snapshot());
+    if (r.body == MDT_GEMM_REFUSED) return hipErrorInvalidValue;
+    hipError_t ze = ensure_zeros();
+    if (ze != hipSuccess) return ze;
+    const int shape = r.mtiles * 100 + r.ntw * 10 + r.nwaves;   // the tiled bodies' <MTILES, NTW, NWAVES>
+    switch (r.body) {
+        case MDT_GEMM_SMALLM:
+            hipLaunchKernelGGL(k_gemm_smallm, route_grid(r), dim3(r.threads), 0, s, a, g_zeros);
+            return hipGetLastError();
+        case MDT_GEMM_SMALLM_WITH_SIDE: {  // the head of the side queue rides in this launch, behind the product's own blocks
+            const mdt_gemm_args b = g_side_jobs[g_side_next++];
+            ++g_side_paired;
+            hipLaunchKernelGGL(k_gemm_smallm2, dim3(r.gx + (b.N >> 4) * ((b.M + 15) >> 4)), dim3(r.threads), 0, s, a, b, r.grid_n,
+                               (a.M + 15) >> 4, g_zeros);
+            return hipGetLastError();
+        }
+        case MDT_GEMM_TILE:
+            switch (shape) {
+                case 214: return launch_gemm_tile<2, 1, 4>(a, r, s);
+                case 218: return launch_gemm_tile<2, 1, 8>(a, r, s);
+                case 238: return launch_gemm_tile<2, 3, 8>(a, r, s);
+                case 248: return launch_gemm_tile<2, 4, 8>(a, r, s);
+                case 114: return launch_gemm_tile<1, 1, 4>(a, r, s);
+                case 424: return launch_gemm_tile<4, 2, 4>(a, r, s);
+                case 244: return launch_gemm_tile<2, 4, 4>(a, r, s);
+                case 234: return launch_gemm_tile<2, 3, 4>(a, r, s);
+                case 224: return launch_gemm_tile<2, 2, 4>(a, r, s);
+            }
+            break;
+        case MDT_GEMM_PIPE: return r.mtiles == 2 ? launch_gemm_pipe<2, 8, 4>(a, r, s) : launch_gemm_pipe<1, 4, 2>(a, r, s);
+        case MDT_GEMM_GLU:
+            if (r.glu == 3) return r.ntw == 4 ? launch_gemm_glu<4, 3>(a, r, s) : launch_gemm_glu<2, 3>(a, r, s);
+            return r.ntw == 3 ? launch_gemm_glu<3, 4>(a, r, s) : launch_gemm_glu<2, 4>(a, r, s);
+        case MDT_GEMM_MERGE: return r.ntw == 3 ? launch_gemm_merge<3>(a, r, s) : launch_gemm_merge<4>(a, r, s);
+        case MDT_GEMM_LN_SPLIT: return launch_gemm_ln_split(a, r, s);
+        case MDT_GEMM_WS: return launch_gemm_ws(a, r, s);
+        case MDT_GEMM_WS_SPLIT: return launch_gemm_ws_split(a, r, s);
+        case MDT_GEMM_TALL: return launch_gemm_tall(a, r, s);
+    }
+    return hipErrorInvalidValue;
 }
-static hipError_t launch_gemm_merge(const mdt_gemm_args& a, hipStream_t s) {
-    if (!a.ln || a.K > 512 || a.residual || a.batch > 1 || a.aux_mode || a.a_parts > 4 || (a.N & 15)) return hipErrorInvalidValue;
-    // 32 x 384 tiles when they divide N (qkv of d = 384: 1152), else 32 x 512
-    return (a.N % 384 == 0) ? launch_gemm_merge_pro<3>(a, s) : launch_gemm_merge_pro<4>(a, s);
-}
+
+extern "C" void mdt_op_set_gemm_geometry(int32_t geo) { g_mdt_sw.gemm_geometry = geo; }
 
 // ------------------------------------------------------------------------------------------------
 // small attention: one workgroup per sample.  The sample's q / k / v rows (all heads) are staged in LDS with
@@ -1276,7 +1048,7 @@ static hipError_t launch_attn_t(const mdt_attn_args& a, const float* rc, const f
 
 hipError_t mdt_launch_attention(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin,
                                 hipStream_t s, int ctx_div, int kv_rows) {
-    if (a.Tq > 16 || a.Tk > 16) return mdt_launch_attn_chunk(a, rope_cos, rope_sin, s, ctx_div, kv_rows);   // 17 .. 64 rows: mdt_attn_chunk.hip
+    if (mdt_route_attn_chunk(a.Tq, a.Tk)) return mdt_launch_attn_chunk(a, rope_cos, rope_sin, s, ctx_div, kv_rows);   // 17 .. 64 rows: mdt_attn_chunk.hip
     if (kv_rows != 0 && kv_rows != a.Tk) return hipErrorInvalidValue;   // the visible prefix is a form of the chunk kernels
     if (a.H < 1 || a.Tq < 1 || a.Tq > 16 || a.Tk < 1 || a.Tk > 16 || ctx_div < 1) return hipErrorInvalidValue;
     const int lp = attn_lanes(a.hd);
@@ -1700,7 +1472,7 @@ static void launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_gui
 
 hipError_t mdt_launch_head(const mdt_head_args& a, const mdt_head_plan* pl, mdt_guide gd, hipStream_t s, mdt_head_pin pn) {
     if ((pn.known == nullptr) != (pn.keep == nullptr)) return hipErrorInvalidValue;
-    if (a.A > 16) return mdt_launch_head_wide(a, pl, gd, s, pn);  // 17 .. 64 elements: the tiled head (mdt_head_wide.hip)
+    if (mdt_route_head_wide(a.A)) return mdt_launch_head_wide(a, pl, gd, s, pn);  // 17 .. 64 elements: the tiled head (mdt_head_wide.hip)
     hipError_t e = ensure_zeros();
     if (e != hipSuccess) return e;
     const int grid = (a.M + 3) / 4;  // 4 waves x 1 row per workgroup
@@ -1905,25 +1677,13 @@ __global__ __launch_bounds__(512) void k_xattn_apply(mdt_xapply_args a, const fl
     xattn_tile<NPP, false>(a, b, ctx_context<CD>(b, ctx_div), lds, zeros, threadIdx.x);
 }
 
-// which configurations the collapsed path covers (others keep the q GEMM + attention + c_proj GEMM sequence)
-bool mdt_xattn_apply_supported(int D, int H, int Te, int Ta) {
-    return D >= 128 && D <= 512 && D % 128 == 0 && (H == 4 || H == 8) && Te >= 1 && Te <= 4 && Ta >= 1 && Ta <= 16;
-}
 // floats of LDS xattn_tile needs
 size_t mdt_xattn_lds_floats(int D, int H) {
     const int npp = 4 * H, ks = 8 / (npp / 16);
     return (size_t)16 * (D + 4) + (size_t)(ks + 1) * 16 * (npp + 4);
 }
 
-// Cross-attention + the Linear behind it in one launch (rollout batches): `x` as for mdt_launch_xattn_apply with a SEPARATE
-// output array (x.y_out != x.y: the workgroups that repeat a sample's cross-attention read x.y while one of them writes), `g` =
-// the Linear on the same rows (g.A == x.y, LayerNorm prologue, K = x.D, M = x.B * x.Ta, no residual, plain row mapping).
-bool mdt_xattn_gemm_supported(const mdt_xapply_args& x, const mdt_gemm_args& g) {
-    return w_image_ok(g.N, g.K) && mdt_xattn_apply_supported(x.D, x.H, x.Te, x.Ta) && x.y_out != nullptr && x.y_out != x.y && g.ln && g.K == x.D && g.A == x.y &&
-           g.lda == x.D &&
-           g.M == x.B * x.Ta && !(g.N & 15) && !g.residual && g.batch <= 1 && !g.aux_mode && g.a_parts <= 1 && g.gin == 1 &&
-           g.gout == 1 && g.goff == 0 && g.rows_per_sample == x.Ta;
-}
+// Cross-attention + the Linear behind it in one launch (rollout batches; mdt_route.h: mdt_xattn_gemm_supported)
 template <int NPP>
 static hipError_t launch_xattn_gemm_t(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s, int ctx_div) {
     const size_t lds = ((size_t)16 * (x.D + 4) + mdt_xattn_lds_floats(x.D, x.H)) * sizeof(float);

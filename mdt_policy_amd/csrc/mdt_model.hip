@@ -658,13 +658,6 @@ struct ModRef {
     ModRef(const float* m_, int64_t st, int sh, int sc, int g) : mod(m_), stride(st), shift(sh), scale(sc), gate(g) {}
 };
 
-// largest batch whose self-attention runs fused into the projection (measured crossover)
-// (round 2, B = 2 / 4 / 8: 1.87 -> 1.71, 2.02 -> 1.85, 2.24 -> 2.07 ms; B = 16 lost then, 2.76 -> 2.83.  Round 5, with the fused
-//  kernel's attention on the MFMA pipe, its rows requested in one batch and its LDS cut to the T real rows -- two workgroups
-//  per CU: B = 12 / 16 / 20 / 24 / 32 1.653 / 1.649 / 1.918 / 2.006 / 2.017 -> 1.49 / 1.50 / 1.74 / 1.93 / 1.95 ms; B = 48 loses,
-//  2.30 -> 2.42)
-static constexpr int64_t ATTN_PROJ_MAX_BATCH = 32;
-
 // the residual stream as the previous sublayer left it: one array (parts <= 1: V.y) or the partial slabs of a fused MLP
 // launch, to be summed by whoever reads them next
 struct Stream {
@@ -673,22 +666,7 @@ struct Stream {
     int64_t stride = 0;
 };
 
-// row count from which the self-attention runs in the prologue of its output projection
-static int g_attn_wide_min_rows() {
-    const int v = g_mdt_sw.attn_wide_min;
-    return v >= 0 ? (v == 0 ? 1 << 30 : v) : 1401;
-}
 extern "C" void mdt_op_set_attn_wide_min(int32_t rows) { g_mdt_sw.attn_wide_min = rows; }
-
-// row count from which (and batch up to which: two rounds of one workgroup per CU) one workgroup per sample runs self-attention,
-// projection AND the collapsed cross-attention (k_attn_xattn); mdt_op_set_attn_wide_min(0) switches it off too
-static int g_attn_xattn_min_rows() {
-    // (round 3 started it where the fused MLP launch starts, 1401 rows; measured down the batch sizes in round 4 -- tools/latency.py,
-    //  profiles/r04_lowbatch.txt -- it beats k_attn + projection + k_xattn_apply from 200 rows on: B = 20 2.03 -> 1.99 ms, 32 2.13 -> 2.09,
-    //  40 2.48 -> 2.35, 80 3.12 -> 3.03, 100 3.26 -> 3.17, 128 3.62 -> 3.52, 140 4.33 -> 4.14; at 160 rows it loses, 1.71 -> 1.75)
-    return g_mdt_sw.attn_wide_min == 0 ? 1 << 30 : 200;
-}
-static constexpr int64_t ATTN_XATTN_MAX_BATCH = 512;
 
 // `fx` (optional): the collapsed cross-attention that follows on the same rows; when the one-sample-per-workgroup kernel takes
 // both, *fused is set and the caller skips its own launch.  ctx_div: how many consecutive samples share one of fx's contexts.
@@ -708,48 +686,32 @@ static mdt_status run_self_attn(mdt_model* m, const EncBlock& e, const View& V, 
     mdt_gemm_args p = gemm_args(V.att, D, e.proj, x, D, M);
     p.residual = 1; p.rows_per_sample = T;
     if (mr.mod && mr.gate >= 0) { p.mod = mr.mod; p.mod_stride = mr.stride; p.gate_off = mr.gate; }
-    if (B <= ATTN_PROJ_MAX_BATCH && mdt_attn_proj_supported(p, m->H, m->hd, T, m->cfg.use_rot_embed)) {
-        // rollout batch: attention and projection in one launch (the attention output never leaves the workgroup)
-        LAUNCH(mdt_launch_attn_proj(p, V.qkv, 3 * D, m->H, m->hd, T, causal, s));
-        return MDT_OK;
+    const int rope = m->cfg.use_rot_embed;
+    const mdt_attn_route r = mdt_route_self_attn(p, B, T, m->H, m->hd, causal, rope, fused ? fx : nullptr, e.proj.ws != nullptr, mdt_route_snapshot());
+    switch (r.form) {
+        case MDT_ATTN_PROJ_SMALL:   // the attention output never leaves the workgroup
+            LAUNCH(mdt_launch_attn_proj(p, V.qkv, 3 * D, m->H, m->hd, T, causal, s));
+            break;
+        case MDT_ATTN_XATTN:
+            LAUNCH(mdt_launch_attn_xattn(p, V.qkv, 3 * D, *fx, m->H, m->hd, T, s, ctx_div, r.pair));
+            *fused = true;
+            break;
+        case MDT_ATTN_PROJ_WIDE:    // no attention launch, no round trip of the attention output
+            LAUNCH(mdt_launch_attn_proj_wide(p, V.qkv, 3 * D, m->H, m->hd, T, s));
+            break;
+        default: {
+            mdt_attn_args a;
+            memset(&a, 0, sizeof a);
+            a.q = V.qkv; a.ldq = 3 * D; a.k = V.qkv + D; a.v = V.qkv + 2 * D; a.ldkv = 3 * D;
+            a.out = V.att; a.ldo = D; a.B = (int)B; a.H = m->H; a.hd = m->hd; a.Tq = T; a.Tk = T;
+            a.causal = causal; a.rope = rope;
+            LAUNCH(mdt_launch_attention(a, m->rope_cos, m->rope_sin, s));
+            LAUNCH(mdt_launch_gemm(p, s));
+        }
     }
-    if (fx && fused && M >= g_attn_xattn_min_rows() && B <= ATTN_XATTN_MAX_BATCH &&
-        mdt_attn_xattn_supported(p, *fx, m->H, m->hd, T, causal, m->cfg.use_rot_embed)) {
-        // the projection on its fp16 pair image under the row condition of split_ready (below it the image may be stale), as run_mlp
-        const bool pair = e.proj.ws && mdt_mlp_split_enabled() && M >= mdt_split_min_rows();
-        LAUNCH(mdt_launch_attn_xattn(p, V.qkv, 3 * D, *fx, m->H, m->hd, T, s, ctx_div, pair));
-        *fused = true;
-        return MDT_OK;
-    }
-    // (up to one workgroup per CU: its 156 KB of LDS allow no second one, so beyond 256 tiles -- B > 272 -- the workgroups
-    //  queue up behind each other while the plain projection keeps three per CU in flight: B = 512 10.35 vs 10.13 ms)
-    const int64_t wide_tiles = (int64_t)((M + 31) / 32) * ((D + 127) / 128);
-    if (M >= g_attn_wide_min_rows() && (wide_tiles <= 256 || g_mdt_sw.attn_wide_min > 0) &&
-        mdt_attn_proj_wide_supported(p, m->H, m->hd, T, causal, m->cfg.use_rot_embed)) {
-        // large batch: the causal attention of each 32-row tile in the projection's prologue (no attention launch, no
-        // round trip of the attention output)
-        LAUNCH(mdt_launch_attn_proj_wide(p, V.qkv, 3 * D, m->H, m->hd, T, s));
-        return MDT_OK;
-    }
-    mdt_attn_args a;
-    memset(&a, 0, sizeof a);
-    a.q = V.qkv; a.ldq = 3 * D; a.k = V.qkv + D; a.v = V.qkv + 2 * D; a.ldkv = 3 * D;
-    a.out = V.att; a.ldo = D; a.B = (int)B; a.H = m->H; a.hd = m->hd; a.Tq = T; a.Tk = T;
-    a.causal = causal; a.rope = m->cfg.use_rot_embed;
-    LAUNCH(mdt_launch_attention(a, m->rope_cos, m->rope_sin, s));
-    LAUNCH(mdt_launch_gemm(p, s));
     return MDT_OK;
 }
 
-// row count from which the MLP sublayer runs as ONE launch (k_mlp) that leaves partial slabs instead of the residual
-// stream: below it the wide tiles do not fill the chip
-// (`split`: the launch would run in its split form (fp16 pairs, mdt_mlp_split.h), which pays from fewer rows -- mdt_split_min_rows(), B = 128: 1280 rows
-// per call 3.42 -> 2.96 ms with the qkv products split too (mdt_internal.h); a setting made with the hook is taken as it is)
-static int g_mlp_fuse_min_rows(bool split = false) {
-    const int v = g_mdt_sw.mlp_fuse_min;
-    if (v >= 0) return v == 0 ? 1 << 30 : v;
-    return split ? mdt_split_min_rows() : 1401;
-}
 extern "C" void mdt_op_set_mlp_fuse_min(int32_t rows) { g_mdt_sw.mlp_fuse_min = rows; }
 
 // mdt_op_trace_mlp: every fused-MLP launch (k_mlp, the dominant kernel of the B = 256 sampler call) of the model-level calls
@@ -817,7 +779,7 @@ static mdt_status refresh_split(mdt_model* m, hipStream_t s) {
     return MDT_OK;
 }
 static inline mdt_status split_ready(mdt_model* m, int64_t rows, hipStream_t s) {
-    if (m->split_stale && mdt_mlp_split_enabled() && rows >= mdt_split_min_rows()) return refresh_split(m, s);
+    if (m->split_stale && mdt_route_reads_pair(mdt_route_snapshot(), rows)) return refresh_split(m, s);
     return MDT_OK;
 }
 
@@ -837,41 +799,39 @@ static mdt_status run_mlp(mdt_model* m, const EncBlock& e, const View& V, int64_
     p.residual = 1; p.rows_per_sample = T;
     if (mr.mod && mr.gate >= 0) { p.mod = mr.mod; p.mod_stride = mr.stride; p.gate_off = mr.gate; }
     if (out) *out = Stream();
-    // (never with `pre_x`: the caller skipped its own cross-attention launch because the c_fc launch was to run it)
-    // the fp16 pair split form of the launch (mdt_mlp_split.h) wherever its images exist and it is not switched off; it pays
-    // from fewer rows than the fp32 launch (g_mlp_fuse_min_rows).  The row condition is split_ready's: below it the images may
-    // be stale (a training state's optimizer steps refresh them only for the launches that read them)
-    const bool split = e.fc.ws && e.proj2.ws && mdt_mlp_split_enabled() && M >= mdt_split_min_rows() && mdt_mlp_split_supported(g, p);
-    if (out && !pre_x && M >= g_mlp_fuse_min_rows(split) && mdt_mlp_slices(D) >= 2 && mdt_mlp_supported(g, p)) {
-        // the hidden buffer (M x 4D) is free in this form: it holds the S <= 4 slabs of (M x D)
-        p.ldo = D;
-        const int64_t stride = (int64_t)M * D;
-        if (g_mdt_sw.trace_mlp > 0) {  // measurement hook (mdt_op_trace_mlp): this launch between its own pair of HIP events, inside the chain
+    const int form = mdt_route_mlp(g, p, out != nullptr, pre_x != nullptr, e.fc.ws && e.proj2.ws, mdt_route_snapshot());
+    switch (form) {
+        case MDT_MLP_FUSED_PAIR:
+        case MDT_MLP_FUSED_F32: {
+            // the hidden buffer (M x 4D) is free in this form: it holds the S <= 4 slabs of (M x D)
+            p.ldo = D;
+            const int64_t stride = (int64_t)M * D;
+            const bool trace = g_mdt_sw.trace_mlp > 0;  // measurement hook (mdt_op_trace_mlp): this launch between its own pair of HIP events, inside the chain
             TraceEv ev;
-            HIP_TRY(hipEventCreate(&ev.e0)); HIP_TRY(hipEventCreate(&ev.e1)); HIP_TRY(hipEventCreate(&ev.e2));
-            HIP_TRY(hipEventRecord(ev.e0, s));
-            if (split) LAUNCH(mdt_launch_mlp_pair(g, p, e.fc.ws, e.proj2.ws, V.hid, stride, s));
+            if (trace) {
+                HIP_TRY(hipEventCreate(&ev.e0)); HIP_TRY(hipEventCreate(&ev.e1)); HIP_TRY(hipEventCreate(&ev.e2));
+                HIP_TRY(hipEventRecord(ev.e0, s));
+            }
+            if (form == MDT_MLP_FUSED_PAIR) LAUNCH(mdt_launch_mlp_pair(g, p, e.fc.ws, e.proj2.ws, V.hid, stride, s));
             else LAUNCH(mdt_launch_mlp(g, p, V.hid, stride, s));
-            HIP_TRY(hipEventRecord(ev.e1, s));
-            HIP_TRY(hipEventRecord(ev.e2, s));
-            g_trace_mlp_events.push_back(ev);
-        } else if (split) {
-            LAUNCH(mdt_launch_mlp_pair(g, p, e.fc.ws, e.proj2.ws, V.hid, stride, s));
-        } else {
-            LAUNCH(mdt_launch_mlp(g, p, V.hid, stride, s));
+            if (trace) {
+                HIP_TRY(hipEventRecord(ev.e1, s));
+                HIP_TRY(hipEventRecord(ev.e2, s));
+                g_trace_mlp_events.push_back(ev);
+            }
+            out->base = V.hid; out->parts = mdt_mlp_slices(D); out->stride = stride;
+            break;
         }
-        out->base = V.hid; out->parts = mdt_mlp_slices(D); out->stride = stride;
-        return MDT_OK;
+        case MDT_MLP_XATTN_IN_FC:
+            LAUNCH(mdt_launch_xattn_gemm(*pre_x, g, s, ctx_div));
+            LAUNCH(mdt_launch_gemm(p, s));
+            break;
+        default:
+            LAUNCH(mdt_launch_gemm(g, s));
+            LAUNCH(mdt_launch_gemm(p, s));
     }
-    if (pre_x) LAUNCH(mdt_launch_xattn_gemm(*pre_x, g, s, ctx_div));
-    else LAUNCH(mdt_launch_gemm(g, s));
-    LAUNCH(mdt_launch_gemm(p, s));
     return MDT_OK;
 }
-
-// batch up to which the cross-attention of a decoder block runs inside the c_fc launch that follows it (rollout batches;
-// B = 4: 1.67 vs 1.58 ms per call)
-static constexpr int64_t XATTN_FC_MAX_BATCH = 2;
 
 // sigma_emb: sinusoidal(ln(sigma)/4) -> Linear -> Mish -> Linear for R sigmas (mdtv_transformer.py:105-110,282-288);
 // the second Linear's output rows go to out (leading dimension ldo, row r -> row r*gout) after `act`.
@@ -1072,7 +1032,7 @@ static mdt_status run_decoder_blocks(mdt_model* m, const View& V, int64_t B, con
             mdt_gemm_args gf = gemm_args(W.y, D, d.fc, W.hid, 4 * D, M);
             gf.ln = 1; gf.rows_per_sample = Ta;
             x.y_out = W.att;
-            x_in_fc = B <= XATTN_FC_MAX_BATCH && M <= 192 && m->Ld % 2 == 0 && mdt_xattn_gemm_supported(x, gf);
+            x_in_fc = mdt_route_x_in_fc(B, m->Ld, x, gf);
             if (!x_in_fc) x.y_out = nullptr;
         }
         bool xdone = false;
@@ -1155,7 +1115,7 @@ static mdt_status run_eval(mdt_model* m, const View& V, int64_t nb, const float*
                            const mdt_head_plan* pl, const float* sigma_next, hipStream_t s, mdt_guide gd, mdt_head_pin pn = {},
                            int ctx_div = 1) {
     Stream fin;
-    const bool head_sums = m->HP == 0 && m->A <= 8;  // the one-launch head adds MLP slabs itself
+    const bool head_sums = mdt_route_head_sums(m->HP, m->A);  // the one-launch head adds MLP slabs itself
     MDT_TRY(run_decoder_blocks(m, V, nb, mod_row, mod_stride, s, head_sums ? &fin : nullptr, ctx_div));
     if (fin.parts > 1) { h.y = fin.base; h.y_parts = fin.parts; h.y_part_stride = fin.stride; }
     if (sigma_next) { h.y_next = V.y; h.Wa = m->Wa; h.ba = m->ba; }
@@ -1889,18 +1849,24 @@ extern "C" mdt_status mdt_op_gemm(const mdt_gemm_args* a, void* stream) {
     return MDT_OK;
 }
 
+// the argument checks of the three fused-MLP ops; w1 / w2: the images of fc / proj the op reads
+static mdt_status check_mlp_op(const char* op, const mdt_gemm_args* fc, const mdt_gemm_args* proj, const void* w1, const void* w2,
+                               const float* parts, int64_t part_stride) {
+    if (!fc || !proj || !fc->A || !w1 || !w2 || !parts || !fc->ln_w) return fail(MDT_ERR_INVALID_ARG, "%s: null pointer", op);
+    if (!mdt_mlp_supported(*fc, *proj))
+        return fail(MDT_ERR_UNSUPPORTED, "%s: needs D = fc.K a multiple of 128 (<= 512), fc.N = proj.K = 4 D, proj.N = D, "
+                                         "a LayerNorm prologue and plain output rows", op);
+    if (fc->lda % 4 || proj->ldo % 4 || proj->ldo < proj->N || part_stride < (int64_t)fc->M * proj->ldo)
+        return fail(MDT_ERR_INVALID_ARG, "%s: lda / ldo multiples of 4, part_stride >= M * ldo required", op);
+    if (misaligned(fc->A) || misaligned(w1) || misaligned(w2) || misaligned(parts) || misaligned(fc->bias) ||
+        misaligned(proj->bias) || misaligned(fc->mod) || misaligned(proj->mod) || (part_stride & 3))
+        return fail(MDT_ERR_INVALID_ARG, "%s: pointers must be 16-byte aligned", op);
+    return MDT_OK;
+}
+
 extern "C" mdt_status mdt_op_mlp(const mdt_gemm_args* fc, const mdt_gemm_args* proj, float* parts, int64_t part_stride,
                                  int32_t* n_parts, void* stream) {
-    if (!fc || !proj || !fc->A || !fc->Wp || !proj->Wp || !parts || !fc->ln_w)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp: null pointer");
-    if (!mdt_mlp_supported(*fc, *proj))
-        return fail(MDT_ERR_UNSUPPORTED, "mdt_op_mlp: needs D = fc.K a multiple of 128 (<= 512), fc.N = proj.K = 4 D, proj.N = D, "
-                                         "a LayerNorm prologue and plain output rows");
-    if (fc->lda % 4 || proj->ldo % 4 || proj->ldo < proj->N || part_stride < (int64_t)fc->M * proj->ldo)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp: lda / ldo multiples of 4, part_stride >= M * ldo required");
-    if (misaligned(fc->A) || misaligned(fc->Wp) || misaligned(proj->Wp) || misaligned(parts) || misaligned(fc->bias) ||
-        misaligned(proj->bias) || misaligned(fc->mod) || misaligned(proj->mod) || (part_stride & 3))
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp: pointers must be 16-byte aligned");
+    MDT_TRY(check_mlp_op("mdt_op_mlp", fc, proj, fc ? fc->Wp : nullptr, proj ? proj->Wp : nullptr, parts, part_stride));
     LAUNCH(mdt_launch_mlp(*fc, *proj, parts, part_stride, (hipStream_t)stream));
     if (n_parts) *n_parts = mdt_mlp_slices(fc->K);
     return MDT_OK;
@@ -1926,16 +1892,7 @@ extern "C" mdt_status mdt_op_pack_weight_split_rows(const float* w, int64_t n_ro
 
 extern "C" mdt_status mdt_op_mlp_split(const mdt_gemm_args* fc, const mdt_gemm_args* proj, const void* fc_split, const void* proj_split,
                                        float* parts, int64_t part_stride, int32_t* n_parts, void* stream) {
-    if (!fc || !proj || !fc->A || !fc_split || !proj_split || !parts || !fc->ln_w)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp_split: null pointer");
-    if (!mdt_mlp_split_supported(*fc, *proj))
-        return fail(MDT_ERR_UNSUPPORTED, "mdt_op_mlp_split: needs D = fc.K a multiple of 128 (<= 512), fc.N = proj.K = 4 D, proj.N = D, "
-                                         "a LayerNorm prologue and plain output rows");
-    if (fc->lda % 4 || proj->ldo % 4 || proj->ldo < proj->N || part_stride < (int64_t)fc->M * proj->ldo)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp_split: lda / ldo multiples of 4, part_stride >= M * ldo required");
-    if (misaligned(fc->A) || misaligned(fc_split) || misaligned(proj_split) || misaligned(parts) || misaligned(fc->bias) ||
-        misaligned(proj->bias) || misaligned(fc->mod) || misaligned(proj->mod) || (part_stride & 3))
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp_split: pointers must be 16-byte aligned");
+    MDT_TRY(check_mlp_op("mdt_op_mlp_split", fc, proj, fc_split, proj_split, parts, part_stride));
     LAUNCH(mdt_launch_mlp_split(*fc, *proj, fc_split, proj_split, parts, part_stride, (hipStream_t)stream));
     if (n_parts) *n_parts = mdt_mlp_slices(fc->K);
     return MDT_OK;
@@ -1965,16 +1922,7 @@ extern "C" mdt_status mdt_op_pair_from_packed(const float* packed, int64_t N, in
 
 extern "C" mdt_status mdt_op_mlp_pair(const mdt_gemm_args* fc, const mdt_gemm_args* proj, const void* fc_pair, const void* proj_pair,
                                       float* parts, int64_t part_stride, int32_t* n_parts, void* stream) {
-    if (!fc || !proj || !fc->A || !fc_pair || !proj_pair || !parts || !fc->ln_w)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp_pair: null pointer");
-    if (!mdt_mlp_split_supported(*fc, *proj))
-        return fail(MDT_ERR_UNSUPPORTED, "mdt_op_mlp_pair: needs D = fc.K a multiple of 128 (<= 512), fc.N = proj.K = 4 D, proj.N = D, "
-                                         "a LayerNorm prologue and plain output rows");
-    if (fc->lda % 4 || proj->ldo % 4 || proj->ldo < proj->N || part_stride < (int64_t)fc->M * proj->ldo)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp_pair: lda / ldo multiples of 4, part_stride >= M * ldo required");
-    if (misaligned(fc->A) || misaligned(fc_pair) || misaligned(proj_pair) || misaligned(parts) || misaligned(fc->bias) ||
-        misaligned(proj->bias) || misaligned(fc->mod) || misaligned(proj->mod) || (part_stride & 3))
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_mlp_pair: pointers must be 16-byte aligned");
+    MDT_TRY(check_mlp_op("mdt_op_mlp_pair", fc, proj, fc_pair, proj_pair, parts, part_stride));
     LAUNCH(mdt_launch_mlp_pair(*fc, *proj, fc_pair, proj_pair, parts, part_stride, (hipStream_t)stream));
     if (n_parts) *n_parts = mdt_mlp_slices(fc->K);
     return MDT_OK;
@@ -2090,31 +2038,31 @@ extern "C" mdt_status mdt_op_xattn_gemm(const mdt_xapply_args* x, const mdt_gemm
     return MDT_OK;
 }
 
+// the argument checks of the two k_attn_xattn ops; w: the projection's image the op reads (pair: proj->Wp_pair, and the pair op
+// also holds the projection's bias and modulation rows to 16 bytes)
+static mdt_status check_attn_xattn_op(const char* op, const mdt_gemm_args* proj, const float* qkv, int64_t ldq, const mdt_xapply_args* x,
+                                      int32_t hd, int32_t T, const void* w, bool pair) {
+    if (!proj || !qkv || !x || !w || !proj->out || !x->ln_w || !x->U || !x->Wf || !x->c) return fail(MDT_ERR_INVALID_ARG, "%s: null argument", op);
+    if (misaligned(qkv) || misaligned(w) || misaligned(proj->out) || (pair && (misaligned(proj->bias) || misaligned(proj->mod))) ||
+        misaligned(x->U) || misaligned(x->Wf) || (ldq & 3))
+        return fail(MDT_ERR_INVALID_ARG, "%s: pointers must be 16-byte aligned, ldq a multiple of 4", op);
+    if (!mdt_attn_xattn_supported(*proj, *x, 8, hd, T, 1, 0) || ldq != 3 * (int64_t)proj->K)
+        return fail(MDT_ERR_UNSUPPORTED, "%s: needs 8 heads of 48 (K = N = ldo = 384, ldq = 3 K), a gated / residual projection "
+                                         "on M = x->B * T rows, T = x->Ta <= 16, x->y == proj->out and a (D, H, Te, Ta) "
+                                         "mdt_op_xattn_apply supports", op);
+    return MDT_OK;
+}
+
 extern "C" mdt_status mdt_op_attn_xattn(const mdt_gemm_args* proj, const float* qkv, int64_t ldq, const mdt_xapply_args* x,
                                         int32_t hd, int32_t T, void* stream) {
-    if (!proj || !qkv || !x || !proj->Wp || !proj->out || !x->ln_w || !x->U || !x->Wf || !x->c)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_xattn: null argument");
-    if (misaligned(qkv) || misaligned(proj->Wp) || misaligned(proj->out) || misaligned(x->U) || misaligned(x->Wf) || (ldq & 3))
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_xattn: pointers must be 16-byte aligned, ldq a multiple of 4");
-    if (!mdt_attn_xattn_supported(*proj, *x, 8, hd, T, 1, 0) || ldq != 3 * (int64_t)proj->K)
-        return fail(MDT_ERR_UNSUPPORTED, "mdt_op_attn_xattn: needs 8 heads of 48 (K = N = ldo = 384, ldq = 3 K), a gated / residual projection "
-                                         "on M = x->B * T rows, T = x->Ta <= 16, x->y == proj->out and a (D, H, Te, Ta) "
-                                         "mdt_op_xattn_apply supports");
+    MDT_TRY(check_attn_xattn_op("mdt_op_attn_xattn", proj, qkv, ldq, x, hd, T, proj ? proj->Wp : nullptr, false));
     LAUNCH(mdt_launch_attn_xattn(*proj, qkv, ldq, *x, 8, hd, T, (hipStream_t)stream));
     return MDT_OK;
 }
 
 extern "C" mdt_status mdt_op_attn_xattn_pair(const mdt_gemm_args* proj, const float* qkv, int64_t ldq, const mdt_xapply_args* x,
                                              int32_t hd, int32_t T, void* stream) {
-    if (!proj || !qkv || !x || !proj->Wp_pair || !proj->out || !x->ln_w || !x->U || !x->Wf || !x->c)
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_xattn_pair: null argument");
-    if (misaligned(qkv) || misaligned(proj->Wp_pair) || misaligned(proj->out) || misaligned(proj->bias) || misaligned(proj->mod) ||
-        misaligned(x->U) || misaligned(x->Wf) || (ldq & 3))
-        return fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_xattn_pair: pointers must be 16-byte aligned, ldq a multiple of 4");
-    if (!mdt_attn_xattn_supported(*proj, *x, 8, hd, T, 1, 0) || ldq != 3 * (int64_t)proj->K)
-        return fail(MDT_ERR_UNSUPPORTED, "mdt_op_attn_xattn_pair: needs 8 heads of 48 (K = N = ldo = 384, ldq = 3 K), a gated / residual "
-                                         "projection on M = x->B * T rows, T = x->Ta <= 16, x->y == proj->out and a (D, H, Te, Ta) "
-                                         "mdt_op_xattn_apply supports");
+    MDT_TRY(check_attn_xattn_op("mdt_op_attn_xattn_pair", proj, qkv, ldq, x, hd, T, proj ? proj->Wp_pair : nullptr, true));
     LAUNCH(mdt_launch_attn_xattn(*proj, qkv, ldq, *x, 8, hd, T, (hipStream_t)stream, 1, true));
     return MDT_OK;
 }

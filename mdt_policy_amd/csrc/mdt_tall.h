@@ -37,7 +37,7 @@
 #include "mdt_internal.h"
 #include "mdt_tiles.h"   // MDT_TS stamps (tuning builds), xcd_remap
 
-#define MDT_TALL_BK 32
+// (MDT_TALL_BK, the k step: mdt_route.h, with mdt_gemm_tall_supported)
 
 typedef __attribute__((address_space(3))) void mdt_lds_void;
 typedef __attribute__((address_space(1))) const void mdt_glb_cvoid;

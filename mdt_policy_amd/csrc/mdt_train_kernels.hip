@@ -308,10 +308,7 @@ hipError_t mdt_launch_merge_ln_fwd(const mdt_merge_args& g, const mdt_ln_train_a
 
 hipError_t mdt_launch_ln_fwd_train(const mdt_ln_train_args& a, hipStream_t s) {
     if (a.D > 64 * LN_MAXC || a.D < 1) return hipErrorInvalidValue;
-    auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (a.D % 4 == 0 && al(a.x) && al(a.w) && al(a.b) && al(a.out) &&
-        (!a.mod || (al(a.mod) && a.mod_stride % 4 == 0 && (a.shift_off < 0 || a.shift_off % 4 == 0) &&
-                    (a.scale_off < 0 || a.scale_off % 4 == 0)))) {
+    if (ln_fwd_vec_ok(a)) {
         hipLaunchKernelGGL(k_ln_fwd_train4, dim3((a.M + 3) / 4), dim3(256), 0, s, a.x, a.w, a.b, a.mod, a.mod_stride, a.shift_off,
                            a.scale_off, a.rows_per_sample > 0 ? a.rows_per_sample : 1, a.out, a.stats, a.M, a.D / 4);
         return hipGetLastError();

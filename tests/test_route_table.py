@@ -1,0 +1,78 @@
+"""Which kernel a shape takes: the host-only route functions (mdt_policy_amd/csrc/mdt_route.h) against the committed table.
+
+tests/c_client/route_table.cpp is a stand-alone program over the route header: no GPU, no library, nothing loaded into Python.  It is
+built with the address and undefined-behaviour sanitizers and its lines are compared, key by key, with
+tests/c_client/route_table.expected -- the kernel name with its template integers, grid, threads and dynamic LDS bytes of every
+GEMM case (each pair of cases straddles one rule of mdt_route_gemm), and the attention / MLP forms of a block at the batch sizes
+where they change.  The expected GEMM lines are the kernel-trace rows of the commit before the routes moved into the header
+(profiles/route_equivalence.txt); a pull request that moves a threshold changes this table on purpose or not at all."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "c_client", "route_table.cpp")
+EXPECTED = os.path.join(ROOT, "tests", "c_client", "route_table.expected")
+LDS_MAX = 160 * 1024  # bytes of LDS a workgroup can have on gfx950
+
+
+@pytest.fixture(scope="module")
+def table(tmp_path_factory):
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.fail("g++ not found: the route table program is plain C++17 and needs only a host compiler")
+    exe = str(tmp_path_factory.mktemp("route") / "route_table")
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    f"-I{os.path.join(ROOT, 'include')}", f"-I{os.path.join(ROOT, 'mdt_policy_amd', 'csrc')}", SRC, "-o", exe],
+                   check=True, capture_output=True, text=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True)
+    assert out.stderr == "", out.stderr  # a sanitizer report
+    return _parse(out.stdout)
+
+
+def _parse(text):
+    rows = {}
+    for line in text.splitlines():
+        if not line.strip() or line.startswith("#"):
+            continue
+        key, _, val = line.partition(": ")
+        assert key not in rows, f"duplicate key {key}"
+        rows[key] = val
+    return rows
+
+
+def test_every_route_is_the_committed_one(table):
+    with open(EXPECTED) as f:
+        want = _parse(f.read())
+    assert list(table) == list(want), "the program's cases and the committed table's differ (same keys, same order)"
+    wrong = {k: (table[k], want[k]) for k in want if table[k] != want[k]}
+    assert not wrong, "\n".join(f"{k}: got {g!r}, committed {w!r}" for k, (g, w) in wrong.items())
+
+
+def test_no_route_asks_for_more_lds_than_a_workgroup_has(table):
+    gemm = {k: v for k, v in table.items() if k.startswith("gemm/")}
+    assert len(gemm) >= 60
+    for key, val in gemm.items():
+        if val == "REFUSED":
+            continue
+        m = re.fullmatch(r"k_\w+(<[^>]*>)? grid=\((\d+),(\d+),(\d+)\) threads=(\d+) lds=(\d+)", val)
+        assert m, f"{key}: {val!r}"
+        assert int(m.group(6)) <= LDS_MAX, f"{key}: {val}"
+        assert 64 <= int(m.group(5)) <= 1024 and int(m.group(2)) >= 1, f"{key}: {val}"
+
+
+def test_the_table_agrees_with_the_outcomes_the_rules_comments_name(table):
+    # "M = 10240: N = 384 -> 8 waves, N = 1152 / 1536 -> 12 waves" (ws_shape)
+    assert "k_gemm_ws<24, 1, 8, 0>" in table["gemm/10240x384_ws_split0"]
+    assert "k_gemm_ws<24, 1, 12, 0>" in table["gemm/10240x1152_ws_split0"]
+    assert "k_gemm_ws<24, 1, 12, 0>" in table["gemm/10240x1536_ws_split0"]
+    # "1280 x 1536 -- 320 tiles -- ... stays" on the half-height tiles; 1024 x 1536 and 1280 x 1152 take the 32 x 192 tiles
+    assert table["gemm/ln_1280x1536"].startswith("k_gemm<1, 1, 4,")
+    assert table["gemm/ln_1024x1536"].startswith("k_gemm<2, 3, 4,") and table["gemm/ln_1280x1152"].startswith("k_gemm<2, 3, 4,")
+    # the tiled attention form up to 256 tiles: "B > 272" keeps the plain projection
+    assert "dec_attn=ATTN_PROJ_WIDE " in table["block/B272_no_fold"] and "dec_attn=ATTN_PLAIN " in table["block/B273_no_fold"]
+    # B = 77 is the first batch of the pair MLP (770 rows)
+    assert " mlp=MLP_TWO_GEMMS " in table["block/B76"] and " mlp=MLP_FUSED_PAIR " in table["block/B77"]
