@@ -409,32 +409,15 @@ hipError_t chunk_fwd(const chunk_fwd_args& a, int B, int hd, hipStream_t s) {
 }
 
 template <int HD>
-hipError_t launch_bwd(const mdt_attn_bwd_args& a, int Tv, hipStream_t s) {
-    const size_t lds = mdt_attn_chunk_lds(HD, a.Tq, Tv, true);
+hipError_t launch_bwd(const mdt_attn_bwd_args& a, const mdt_attn_train_route& r, hipStream_t s) {
     const float scale = 1.0f / sqrtf((float)HD);
-    if (a.p > 0.f && a.seed != 0) return mdt_launch_lds<k_attn_chunk_bwd<HD, true>>(dim3(a.B, a.H), dim3(CHUNK_NT), lds, s, a, scale, Tv);
-    return mdt_launch_lds<k_attn_chunk_bwd<HD, false>>(dim3(a.B, a.H), dim3(CHUNK_NT), lds, s, a, scale, Tv);
+    if (r.drop) return mdt_launch_lds<k_attn_chunk_bwd<HD, true>>(dim3(a.B, r.gy), dim3(r.threads), r.lds, s, a, scale, r.Tv);
+    return mdt_launch_lds<k_attn_chunk_bwd<HD, false>>(dim3(a.B, r.gy), dim3(r.threads), r.lds, s, a, scale, r.Tv);
 }
 
 }  // namespace
 
-// kv_rows a launch may stage: every key (0 or Tk), or a causal launch's prefix that holds every key some query sees -- key j is
-// seen by the queries i >= j only, so j < min(Tq, Tk) -- at Tk > 16 (the 16-row kernels have no such form)
-bool mdt_prefix_rows_ok(int Tq, int Tk, int causal, int kv_rows) {
-    return kv_rows == 0 || kv_rows == Tk || (causal && Tk > 16 && kv_rows >= (Tq < Tk ? Tq : Tk) && kv_rows < Tk);
-}
-
-bool mdt_attn_chunk_supported(int hd, int Tq, int Tk) {
-    return (hd == 32 || hd == 48 || hd == 64) && Tq >= 1 && Tk >= 1 && Tq <= CHUNK_T && Tk <= CHUNK_T;
-}
-
-// bytes of dynamic LDS of the forward (q, k, V^T) or the backward (q, k, v, dO and the two Tq16 x Tv16 matrices); Tv: the keys
-// the launch stages -- Tk, or the visible prefix
-size_t mdt_attn_chunk_lds(int hd, int Tq, int Tv, bool bwd) {
-    const size_t Tq16 = (size_t)((Tq + 15) & ~15), Tv16 = (size_t)((Tv + 15) & ~15), st = (size_t)hd + 4;
-    if (bwd) return ((2 * Tq16 + 2 * Tv16) * st + 2 * Tq16 * (Tv16 + 4)) * sizeof(float);
-    return ((Tq16 + Tv16) * st + (size_t)hd * (Tv16 + 4)) * sizeof(float);
-}
+static_assert(CHUNK_T == MDT_ATTN_CHUNK_T && CHUNK_NT == 256, "mdt_route_train.h: the chunk kernels' row limit and workgroup size");
 
 // test hook (mdt_hip_debug.h)
 extern "C" int64_t mdt_op_attn_chunk_lds(int32_t hd, int32_t Tq, int32_t kv_rows, int32_t bwd) {
@@ -451,29 +434,28 @@ hipError_t mdt_launch_attn_chunk(const mdt_attn_args& a, const float* rope_cos, 
     return chunk_fwd(f, a.B, a.hd, s);
 }
 
-hipError_t mdt_launch_attn_chunk_fwd_train(const mdt_attn_train_args& a, hipStream_t s, int kv_rows) {
-    if (a.rope && (!a.rope_cos || !a.rope_sin)) return hipErrorInvalidValue;
+// the training launches: mdt_launch_attn_fwd_train / mdt_launch_attn_bwd (mdt_train_kernels.hip) have checked the operands and
+// hand over their route (mdt_route_train.h: family CHUNK -- shape, prefix and LDS bytes accepted)
+hipError_t mdt_launch_attn_chunk_fwd_train(const mdt_attn_train_args& a, const mdt_attn_train_route& r, hipStream_t s) {
+    if (a.B < 1) return hipErrorInvalidValue;
     chunk_fwd_args f;
     memset(&f, 0, sizeof f);
     f.q = a.q; f.ldq = a.ldq; f.k = a.k; f.v = a.v; f.ldkv = a.ldkv; f.out = a.out; f.ldo = a.ldo;
-    f.H = a.H; f.Tq = a.Tq; f.Tk = a.Tk; f.causal = a.causal; f.ctx_div = 1; f.Tv = prefix_of(a.Tk, kv_rows);
+    f.H = a.H; f.Tq = a.Tq; f.Tk = a.Tk; f.causal = a.causal; f.ctx_div = 1; f.Tv = r.Tv;
     f.rc = a.rope ? a.rope_cos : nullptr; f.rs = a.rope ? a.rope_sin : nullptr;
     f.p = a.p; f.site = a.site; f.seed = a.seed;
-    return chunk_fwd(f, a.B, a.hd, s);
+    switch (r.hd) {
+        case 32: return launch_fwd<32>(f, a.B, s);
+        case 48: return launch_fwd<48>(f, a.B, s);
+        default: return launch_fwd<64>(f, a.B, s);
+    }
 }
 
-hipError_t mdt_launch_attn_chunk_bwd(const mdt_attn_bwd_args& a, hipStream_t s, int kv_rows) {
-    const int Tv = prefix_of(a.Tk, kv_rows);
-    if (!mdt_attn_chunk_supported(a.hd, a.Tq, a.Tk) || a.B < 1 || a.H < 1 || a.H > 65535) return hipErrorInvalidValue;
-    if (!mdt_prefix_rows_ok(a.Tq, a.Tk, a.causal, Tv)) return hipErrorInvalidValue;
-    if (((a.ldq | a.ld_do | a.ldkv | a.ld_dq | a.ld_dkv) & 3) || !aligned16(a.q) || !aligned16(a.k) || !aligned16(a.v) || !aligned16(a.d_out) ||
-        !aligned16(a.dq) || !aligned16(a.dk) || !aligned16(a.dv))
-        return hipErrorInvalidValue;
-    if (a.rope && (!a.rope_cos || !a.rope_sin)) return hipErrorInvalidValue;
-    if (mdt_attn_chunk_lds(a.hd, a.Tq, Tv, true) > 160 * 1024) return hipErrorInvalidValue;
-    switch (a.hd) {
-        case 32: return launch_bwd<32>(a, Tv, s);
-        case 48: return launch_bwd<48>(a, Tv, s);
-        default: return launch_bwd<64>(a, Tv, s);
+hipError_t mdt_launch_attn_chunk_bwd(const mdt_attn_bwd_args& a, const mdt_attn_train_route& r, hipStream_t s) {
+    if (a.B < 1) return hipErrorInvalidValue;
+    switch (r.hd) {
+        case 32: return launch_bwd<32>(a, r, s);
+        case 48: return launch_bwd<48>(a, r, s);
+        default: return launch_bwd<64>(a, r, s);
     }
 }

@@ -15,6 +15,7 @@
 #include "mdt_hip_train.h"
 #include "mdt_mae.h"
 #include "mdt_route.h"   // which kernel a launch runs on: the shape rules, thresholds and *_supported predicates (host only)
+#include "mdt_route_train.h"   // ... and the training path's: the Linear backward's plan, training attention, the row-wise kernels
 
 // ---- error plumbing: the message behind mdt_last_error() (thread local, defined in mdt_model.hip) ----
 mdt_status mdt_fail(mdt_status st, const char* fmt, ...);
@@ -128,13 +129,12 @@ hipError_t mdt_launch_attention(const mdt_attn_args& a, const float* rope_cos, c
                                 int kv_rows = 0);
 // chunks of 17 .. 64 rows (mdt_attn_chunk.hip): where mdt_launch_attention, mdt_launch_attn_fwd_train and mdt_launch_attn_bwd go
 // once max(Tq, Tk) > 16 -- head dim 32 / 48 / 64, Tq, Tk <= 64; rotary tables of max(Tq, Tk) positions x 16 frequencies
-bool mdt_prefix_rows_ok(int Tq, int Tk, int causal, int kv_rows);   // the kv_rows the launchers (and the *_prefix hooks of mdt_hip_debug.h) accept
+// (mdt_prefix_rows_ok -- the kv_rows the launchers and the *_prefix hooks of mdt_hip_debug.h accept --, mdt_attn_chunk_supported and
+// mdt_attn_chunk_lds -- bytes of dynamic LDS of one workgroup; Tv = the keys it stages --: mdt_route_train.h)
 constexpr int MDT_ROPE_POSITIONS = 64;   // rows of a handle's rotary tables
-bool mdt_attn_chunk_supported(int hd, int Tq, int Tk);
-size_t mdt_attn_chunk_lds(int hd, int Tq, int Tv, bool bwd);   // bytes of dynamic LDS of one workgroup; Tv = the keys it stages
 hipError_t mdt_launch_attn_chunk(const mdt_attn_args& a, const float* rope_cos, const float* rope_sin, hipStream_t s, int ctx_div, int kv_rows = 0);
-hipError_t mdt_launch_attn_chunk_fwd_train(const mdt_attn_train_args& a, hipStream_t s, int kv_rows = 0);
-hipError_t mdt_launch_attn_chunk_bwd(const mdt_attn_bwd_args& a, hipStream_t s, int kv_rows = 0);
+hipError_t mdt_launch_attn_chunk_fwd_train(const mdt_attn_train_args& a, const mdt_attn_train_route& r, hipStream_t s);   // r: family CHUNK
+hipError_t mdt_launch_attn_chunk_bwd(const mdt_attn_bwd_args& a, const mdt_attn_train_route& r, hipStream_t s);
 // one sample's self-attention fused into its output projection p (rollout batch 1); see mdt_kernels.hip
 hipError_t mdt_launch_attn_proj(const mdt_gemm_args& p, const float* qkv, int64_t ldq, int H, int hd, int T, int causal,
                                 hipStream_t s);
@@ -272,23 +272,18 @@ hipError_t mdt_launch_transpose_ld(const float* src, int64_t lds_, float* dst, i
                                    hipStream_t s, int slice_len = 0);
 // floats of scratch mdt_linear_bwd needs for an (M, N, K) layer
 int64_t mdt_linear_bwd_scratch(int64_t M, int64_t N, int64_t K);
-// dW[n][k] = sum_m dY[m][n] X[m][k] from the row-major operands (mdt_train_kernels.hip: k_gemm_tn), S row slices of L rows
+// dW[n][k] = sum_m dY[m][n] X[m][k] from the row-major operands (mdt_train_kernels.hip: k_gemm_tn), S row slices of L rows; the tile
+// is the route's (mdt_route_train.h: mdt_route_gemm_tn / mdt_route_gemm_tn_split)
 hipError_t mdt_launch_gemm_tn(const float* dY, int64_t ldy, const float* X, int64_t ldx, float* out, int64_t slice_stride, int M, int N,
                               int K, int S, int L, int accumulate, float* bpart, hipStream_t s);
-int mdt_gemm_tn_ktile(int K);  // 128 or 192: the k-tile width k_gemm_tn picks for K columns
 // the same product as three-way bf16 splits of both operands (k_gemm_tn_split: 128 x 128 / 128 x 192 tiles, 8 waves, 123 / 154 KB of LDS)
-bool mdt_gemm_tn_split_on();
-int mdt_gemm_tn_split_ktile(int K);
-void mdt_gemm_tn_split_tile(int N, int K, int* tn, int* tk);   // its (n, k) tile: 128 x 128 / 128 x 192 / 192 x 128
 hipError_t mdt_launch_gemm_tn_split(const float* dY, int64_t ldy, const float* X, int64_t ldx, float* out, int64_t slice_stride, int M, int N,
                                     int K, int S, int L, int accumulate, float* bpart, hipStream_t s);
-void mdt_gemm_tn_tile(int64_t M, int N, int K, int* tn, int* tk);  // its (n, k) tile for an M-deep product: n 64 / 128 / 192 (4 / 8 / 12 waves)
 hipError_t mdt_launch_colsum2(const float* X0, const float* X1, int64_t ldx, int M, int N, float* out0, float* out1,
                               int accumulate, hipStream_t s);
 hipError_t mdt_launch_ln_fwd_train(const mdt_ln_train_args& a, hipStream_t s);
 hipError_t mdt_launch_ln_bwd(const mdt_ln_bwd_args& a, hipStream_t s);
 // fused pairs of the training path (round 6): LayerNorm backward + the merge backward behind it; merge + the LayerNorm of its result
-bool mdt_attn_train_mfma_supported(int hd, int H, int rope);  // the MFMA form of the training attention kernels takes this shape
 hipError_t mdt_launch_ln_bwd_merge(const mdt_ln_bwd_args& a, const mdt_merge_args& g, hipStream_t s);
 hipError_t mdt_launch_merge_ln_fwd(const mdt_merge_args& g, const mdt_ln_train_args& l, hipStream_t s);
 hipError_t mdt_launch_act_fwd(const float* u, float* out, int64_t n, int act, hipStream_t s);

@@ -931,7 +931,7 @@ static hipError_t launch_gemm_merge(const mdt_gemm_args& a, const mdt_gemm_route
 }
 
 // ---- mdt_launch_gemm: snapshot, route, one switch from the route to the instantiation ----
-// the process switches a route depends on, read once (the two with an environment variable through mdt_switch_env), and whether a
+// the process switches a route depends on, read once (the three with an environment variable through mdt_switch_env), and whether a
 // side job is queued on this host thread
 mdt_route_switches mdt_route_snapshot() {
     mdt_route_switches sw;
@@ -940,6 +940,7 @@ mdt_route_switches mdt_route_snapshot() {
     sw.mlp_fuse_min = g_mdt_sw.mlp_fuse_min;
     sw.mlp_split = mdt_switch_env(g_mdt_sw.mlp_split, "MDT_HIP_MLP_SPLIT", 1) != 0;
     sw.ws_split = mdt_switch_env(g_mdt_sw.ws_split, "MDT_HIP_WS_SPLIT", 1) != 0;
+    sw.tn_split = mdt_switch_env(g_mdt_sw.tn_split, "MDT_HIP_TN_SPLIT", 1) != 0;
     sw.side_pending = g_side_next < g_side_jobs.size();
     return sw;
 }

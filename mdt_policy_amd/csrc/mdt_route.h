@@ -2,7 +2,8 @@
 // Plain C++17, host only: no HIP type, no atomics, no allocation -- a host compiler builds it alone (tests/c_client/route_table.cpp
 // prints the table tests/test_route_table.py pins).  The launchers (mdt_kernels.hip, mdt_model.hip) fill the snapshot once per
 // launch, ask the route, and hold one switch from the route to the instantiation; every threshold and shape rule of the forward
-// products lives here once, with the comment that carries its measurement.
+// products lives here once, with the comment that carries its measurement.  Its sibling mdt_route_train.h holds the training path's:
+// the Linear backward's plan (slices, kernel, scratch layout), the training attention kernels and the row-wise kernels' forms.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -19,6 +20,7 @@ struct mdt_route_switches {
     int mlp_fuse_min = -1;   // mdt_op_set_mlp_fuse_min: rows; 0 = never; < 0 = the default
     int mlp_split = 1;       // MDT_HIP_MLP_SPLIT / mdt_op_set_mlp_split, resolved: 0 = the fp32 launches everywhere
     int ws_split = 1;        // MDT_HIP_WS_SPLIT / mdt_op_set_ws_split, resolved
+    int tn_split = 1;        // MDT_HIP_TN_SPLIT / mdt_op_set_tn_split, resolved (mdt_route_train.h: the weight gradients)
     int side_pending = 0;    // a side job (mdt_gemm_side_push) is queued on this host thread
 };
 

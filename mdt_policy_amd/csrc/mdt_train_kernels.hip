@@ -284,34 +284,33 @@ __global__ __launch_bounds__(256) void k_merge_ln_fwd4(mdt_merge_args g, const f
     if (lane == 0 && stats) { stats[2 * row] = mean; stats[2 * row + 1] = rstd; }
 }
 
-static bool ln_fwd_vec_ok(const mdt_ln_train_args& a) {
-    auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    return a.D % 4 == 0 && al(a.x) && al(a.w) && al(a.b) && al(a.out) &&
-           (!a.mod || (al(a.mod) && a.mod_stride % 4 == 0 && (a.shift_off < 0 || a.shift_off % 4 == 0) &&
-                       (a.scale_off < 0 || a.scale_off % 4 == 0)));
-}
-static bool merge_vec_ok(const mdt_merge_args& a, bool bwd);
+// which form a row-wise launch takes (16-byte or 4-byte kernel, fused pair or two launches): mdt_route_train.h
+static_assert(MDT_LN_MAX_D == 64 * LN_MAXC, "mdt_route_train.h refuses rows wider than the kernels hold in registers");
 hipError_t mdt_launch_merge_fwd(const mdt_merge_args& a, hipStream_t s);
 // the merge g, then the LayerNorm l of its result (l.x is ignored): one launch where both take 16-byte accesses
 hipError_t mdt_launch_merge_ln_fwd(const mdt_merge_args& g, const mdt_ln_train_args& l, hipStream_t s) {
     mdt_ln_train_args ll = l;
     ll.x = g.out;
-    if (ll.D > 64 * LN_MAXC || ll.D < 1) return hipErrorInvalidValue;
-    if (ln_fwd_vec_ok(ll) && merge_vec_ok(g, false) && g.D == ll.D && (int64_t)g.B * g.rows_per_sample == ll.M && g.out != g.a) {
-        hipLaunchKernelGGL(k_merge_ln_fwd4, dim3((ll.M + 3) / 4), dim3(256), 0, s, g, ll.w, ll.b, ll.mod, ll.mod_stride, ll.shift_off,
-                           ll.scale_off, ll.rows_per_sample > 0 ? ll.rows_per_sample : 1, ll.out, ll.stats, ll.M, ll.D / 4);
-        return hipGetLastError();
+    switch (mdt_route_merge_ln_fwd(g, ll)) {
+        case MDT_ROW_REFUSED: return hipErrorInvalidValue;
+        case MDT_ROW_FUSED:
+            hipLaunchKernelGGL(k_merge_ln_fwd4, dim3((ll.M + 3) / 4), dim3(256), 0, s, g, ll.w, ll.b, ll.mod, ll.mod_stride, ll.shift_off,
+                               ll.scale_off, ll.rows_per_sample > 0 ? ll.rows_per_sample : 1, ll.out, ll.stats, ll.M, ll.D / 4);
+            return hipGetLastError();
+        default: break;
     }
     hipError_t e = mdt_launch_merge_fwd(g, s);
     return e != hipSuccess ? e : mdt_launch_ln_fwd_train(ll, s);
 }
 
 hipError_t mdt_launch_ln_fwd_train(const mdt_ln_train_args& a, hipStream_t s) {
-    if (a.D > 64 * LN_MAXC || a.D < 1) return hipErrorInvalidValue;
-    if (ln_fwd_vec_ok(a)) {
-        hipLaunchKernelGGL(k_ln_fwd_train4, dim3((a.M + 3) / 4), dim3(256), 0, s, a.x, a.w, a.b, a.mod, a.mod_stride, a.shift_off,
-                           a.scale_off, a.rows_per_sample > 0 ? a.rows_per_sample : 1, a.out, a.stats, a.M, a.D / 4);
-        return hipGetLastError();
+    switch (mdt_route_ln_fwd(a)) {
+        case MDT_ROW_REFUSED: return hipErrorInvalidValue;
+        case MDT_ROW_VEC4:
+            hipLaunchKernelGGL(k_ln_fwd_train4, dim3((a.M + 3) / 4), dim3(256), 0, s, a.x, a.w, a.b, a.mod, a.mod_stride, a.shift_off,
+                               a.scale_off, a.rows_per_sample > 0 ? a.rows_per_sample : 1, a.out, a.stats, a.M, a.D / 4);
+            return hipGetLastError();
+        default: break;
     }
     hipLaunchKernelGGL(k_ln_fwd_train, dim3((a.M + 3) / 4), dim3(256), 0, s, a.x, a.w, a.b, a.mod, a.mod_stride,
                        a.shift_off, a.scale_off, a.rows_per_sample > 0 ? a.rows_per_sample : 1, a.out, a.stats, a.M, a.D);
@@ -522,47 +521,29 @@ __global__ __launch_bounds__(256) void k_ln_bwd4(mdt_ln_bwd_args a, mdt_merge_ar
 }
 
 template <bool MG>
-static void launch_ln_bwd4(const mdt_ln_bwd_args& a, const mdt_merge_args& g, int chunks, hipStream_t s) {
-    // rows a wave keeps in flight: all of them, up to 3
-    const int per = (a.rows_per_sample + chunks - 1) / chunks;
-    const int rb = per <= 4 ? 1 : (per <= 8 ? 2 : 3);
-    const size_t lds = (size_t)4 * (MG ? 5 : 4) * a.D * sizeof(float);
-    if (rb == 1) hipLaunchKernelGGL((k_ln_bwd4<MG, 1>), dim3(a.B, chunks), dim3(256), lds, s, a, g);
-    else if (rb == 2) hipLaunchKernelGGL((k_ln_bwd4<MG, 2>), dim3(a.B, chunks), dim3(256), lds, s, a, g);
-    else hipLaunchKernelGGL((k_ln_bwd4<MG, 3>), dim3(a.B, chunks), dim3(256), lds, s, a, g);
-}
-
-static bool ln_bwd_vec_ok(const mdt_ln_bwd_args& a) {
-    auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    return a.D % 4 == 0 && a.ld_dh % 4 == 0 && al(a.x) && al(a.dh) && al(a.dx) && al(a.w) && al(a.b) &&
-           (!a.mod || (al(a.mod) && a.mod_stride % 4 == 0 && (a.scale_off < 0 || a.scale_off % 4 == 0)));
+static hipError_t launch_ln_bwd4(const mdt_ln_bwd_args& a, const mdt_merge_args& g, const mdt_ln_bwd_route& r, hipStream_t s) {
+    return mdt_with_const<1, 3>(r.rb, [&](auto rb) {
+        hipLaunchKernelGGL((k_ln_bwd4<MG, decltype(rb)::value>), dim3(a.B, r.chunks), dim3(256), r.lds, s, a, g);
+        return hipGetLastError();
+    });
 }
 hipError_t mdt_launch_ln_bwd(const mdt_ln_bwd_args& a, hipStream_t s) {
-    if (a.D > 64 * LN_MAXC || a.D < 1 || a.rows_per_sample < 1) return hipErrorInvalidValue;
-    const int chunks = a.row_chunks > 1 ? a.row_chunks : 1;
-    if (chunks > 1 && (a.d_mod || chunks > a.rows_per_sample)) return hipErrorInvalidValue;
-    if (ln_bwd_vec_ok(a)) {
-        launch_ln_bwd4<false>(a, mdt_merge_args{}, chunks, s);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_ln_bwd, dim3(a.B, chunks), dim3(256), (size_t)16 * a.D * sizeof(float), s, a);
+    const mdt_ln_bwd_route r = mdt_route_ln_bwd(a, nullptr);
+    if (r.form == MDT_ROW_REFUSED) return hipErrorInvalidValue;
+    if (r.form == MDT_ROW_VEC4) return launch_ln_bwd4<false>(a, mdt_merge_args{}, r, s);
+    hipLaunchKernelGGL(k_ln_bwd, dim3(a.B, r.chunks), dim3(256), r.lds, s, a);
     return hipGetLastError();
 }
 
-static bool merge_vec_ok(const mdt_merge_args& a, bool bwd);
 hipError_t mdt_launch_merge_bwd(const mdt_merge_args& a, hipStream_t s);
 // LayerNorm backward, then the backward of the branch merge `g` on the gradient it leaves in a.dx (g.x is ignored): one launch
 // where both take 16-byte accesses and a sample is one workgroup, else the two kernels one after the other
 hipError_t mdt_launch_ln_bwd_merge(const mdt_ln_bwd_args& a, const mdt_merge_args& g, hipStream_t s) {
     mdt_merge_args gg = g;
     gg.x = a.dx;
-    const int chunks = a.row_chunks > 1 ? a.row_chunks : 1;
-    if (a.D > 64 * LN_MAXC || a.D < 1 || a.rows_per_sample < 1) return hipErrorInvalidValue;
-    if (chunks == 1 && ln_bwd_vec_ok(a) && merge_vec_ok(gg, true) && gg.B == a.B && gg.rows_per_sample == a.rows_per_sample &&
-        gg.D == a.D) {
-        launch_ln_bwd4<true>(a, gg, 1, s);
-        return hipGetLastError();
-    }
+    const mdt_ln_bwd_route r = mdt_route_ln_bwd(a, &gg);
+    if (r.form == MDT_ROW_REFUSED) return hipErrorInvalidValue;
+    if (r.form == MDT_ROW_FUSED) return launch_ln_bwd4<true>(a, gg, r, s);
     hipError_t e = mdt_launch_ln_bwd(a, s);
     return e != hipSuccess ? e : mdt_launch_merge_bwd(gg, s);
 }
@@ -693,18 +674,13 @@ __global__ __launch_bounds__(256) void k_merge_bwd4(mdt_merge_args a) {
         *(f32x4*)(a.dgate + (int64_t)b * a.dgate_stride + 4 * c4) = acc;
     }
 }
-static bool merge_vec_ok(const mdt_merge_args& a, bool bwd) {
-    auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    return a.D % 4 == 0 && a.D >= 4 && a.D <= 1024 && al(a.x) && al(a.a) && al(a.out) &&
-           (!a.gate || (al(a.gate) && a.gate_stride % 4 == 0)) && (!bwd || !a.dgate || (al(a.dgate) && a.dgate_stride % 4 == 0));
-}
 hipError_t mdt_launch_merge_fwd(const mdt_merge_args& a, hipStream_t s) {
-    if (merge_vec_ok(a, false)) hipLaunchKernelGGL(k_merge_fwd4, dim3(a.B), dim3(256), 0, s, a);
+    if (mdt_merge_vec_ok(a, false)) hipLaunchKernelGGL(k_merge_fwd4, dim3(a.B), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_merge_fwd, dim3(a.B), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 hipError_t mdt_launch_merge_bwd(const mdt_merge_args& a, hipStream_t s) {
-    if (merge_vec_ok(a, true)) hipLaunchKernelGGL(k_merge_bwd4, dim3(a.B), dim3(256), 0, s, a);
+    if (mdt_merge_vec_ok(a, true)) hipLaunchKernelGGL(k_merge_bwd4, dim3(a.B), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_merge_bwd, dim3(a.B), dim3(256), 0, s, a);
     return hipGetLastError();
 }
@@ -810,7 +786,7 @@ hipError_t mdt_launch_colsum_batched(const mdt_colsum_entry* entries, int n, hip
 hipError_t mdt_launch_colsum(const float* X, int64_t ldx, int M, int N, float* out, int accumulate, hipStream_t s);
 hipError_t mdt_launch_colsum2(const float* X0, const float* X1, int64_t ldx, int M, int N, float* out0, float* out1,
                               int accumulate, hipStream_t s) {
-    if (M >= 512) {  // deep sums: the sliced two-stage reduction, once per operand (63 -> 2 x 9 us at M = 1024, N = 384)
+    if (M >= MDT_COLSUM_DEEP_ROWS) {  // deep sums: the sliced two-stage reduction, once per operand
         hipError_t e = mdt_launch_colsum(X0, ldx, M, N, out0, accumulate, s);
         return e != hipSuccess ? e : mdt_launch_colsum(X1, ldx, M, N, out1, accumulate, s);
     }
@@ -820,7 +796,7 @@ hipError_t mdt_launch_colsum2(const float* X0, const float* X1, int64_t ldx, int
 
 // 64 row slices x 4096 columns (1 MiB) of scratch PER STREAM: uses on one stream are ordered, two streams (two
 // handles training side by side) must not share it
-static const int CS_SLICES = 64, CS_MAXN = 4096;
+static const int CS_SLICES = MDT_COLSUM_SLICES, CS_MAXN = MDT_COLSUM_MAXN;   // (mdt_route_train.h: mdt_route_colsum)
 static std::mutex g_cs_mu;
 static std::unordered_map<hipStream_t, float*> g_cs_scratch;
 
@@ -864,11 +840,12 @@ __global__ __launch_bounds__(256) void k_colsum_wide4(const float* __restrict__ 
 }
 
 hipError_t mdt_launch_colsum(const float* X, int64_t ldx, int M, int N, float* out, int accumulate, hipStream_t s) {
-    if (N >= 16384 && N % 4 == 0 && ldx % 4 == 0 && (((uintptr_t)X | (uintptr_t)out) & 15) == 0) {
+    const int form = mdt_route_colsum(ldx, M, N, (((uintptr_t)X | (uintptr_t)out) & 15) == 0);
+    if (form == MDT_COLSUM_WIDE4) {
         hipLaunchKernelGGL(k_colsum_wide4, dim3((N / 4 + 63) / 64), dim3(256), 0, s, X, ldx / 4, M, N / 4, out, accumulate);
         return hipGetLastError();
     }
-    if (M >= 512 && N <= CS_MAXN) {  // 64 row slices in parallel, then their sum (a single stage runs on N / 64 workgroups)
+    if (form == MDT_COLSUM_SLICED) {  // 64 row slices in parallel, then their sum (a single stage runs on N / 64 workgroups)
         float* scratch = colsum_scratch(s);
         if (!scratch) return hipErrorOutOfMemory;
         hipLaunchKernelGGL(k_colsum, dim3((N + 63) / 64, CS_SLICES), dim3(256), 0, s, X, ldx, M, N, scratch, 0);
@@ -1205,55 +1182,35 @@ __global__ __launch_bounds__(64 * HG) void k_attn_bwd_mfma(mdt_attn_bwd_args a, 
     }
 }
 
-// which (hd, H) the MFMA kernels take (the others: the one-wave-per-head kernels)
-static int attn_train_mfma_group(int hd, int H, int rope) {
-    if (rope || (hd != 16 && hd != 32 && hd != 48 && hd != 64)) return 0;
-    return H % 4 == 0 ? 4 : (H % 2 == 0 ? 2 : 1);
+// The training attention launchers execute mdt_route_attn_train (mdt_route_train.h): family, template integers, grid, threads and
+// LDS bytes are the route's; here the operand checks (once for each argument struct) and one dispatch from route to instantiation.
+static_assert(AttnMfma<48, 4>::RS == 4 * 48 + 16, "mdt_route_attn_train's LDS bytes count AttnMfma::RS floats per row");
+// f(HD, HG) as integral constants for the route's MFMA instantiation: HD = 16 / 32 / 48 / 64, HG = 1 / 2 / 4
+template <class F>
+static hipError_t with_attn_mfma(const mdt_attn_train_route& r, F f) {
+    return mdt_with_const<1, 4>(r.hd / 16, [&](auto hd16) {
+        return mdt_with_const<0, 2>(r.hg >> 1, [&](auto lg) {
+            return f(std::integral_constant<int, 16 * decltype(hd16)::value>(), std::integral_constant<int, 1 << decltype(lg)::value>());
+        });
+    });
 }
-template <int HD, int HG>
-static hipError_t launch_attn_fwd_mfma(const mdt_attn_train_args& a, float scale, hipStream_t s) {
-    using AM = AttnMfma<HD, HG>;
-    const size_t lds = ((size_t)(a.Tq + 2 * a.Tk) * AM::RS + (size_t)HG * 16 * 17) * sizeof(float);
-    return mdt_launch_lds<k_attn_fwd_train_mfma<HD, HG>>(dim3(a.B, a.H / HG), dim3(64 * HG), lds, s, a, scale);
-}
-template <int HD, int HG>
-static hipError_t launch_attn_bwd_mfma(const mdt_attn_bwd_args& a, float scale, hipStream_t s) {
-    using AM = AttnMfma<HD, HG>;
-    const size_t lds = ((size_t)(2 * a.Tq + 2 * a.Tk) * AM::RS + (size_t)HG * (16 * 17 + 2 * 16 * 20)) * sizeof(float);
-    return mdt_launch_lds<k_attn_bwd_mfma<HD, HG>>(dim3(a.B, a.H / HG), dim3(64 * HG), lds, s, a, scale);
-}
-bool mdt_attn_train_mfma_supported(int hd, int H, int rope) { return attn_train_mfma_group(hd, H, rope) != 0; }
-#define ATTN_MFMA_DISPATCH(FN, a, scale, s, hg)                                                         \
-    switch ((a).hd * 8 + (hg)) {                                                                         \
-        case 16 * 8 + 4: return FN<16, 4>(a, scale, s); case 16 * 8 + 2: return FN<16, 2>(a, scale, s); \
-        case 16 * 8 + 1: return FN<16, 1>(a, scale, s);                                                  \
-        case 32 * 8 + 4: return FN<32, 4>(a, scale, s); case 32 * 8 + 2: return FN<32, 2>(a, scale, s); \
-        case 32 * 8 + 1: return FN<32, 1>(a, scale, s);                                                  \
-        case 48 * 8 + 4: return FN<48, 4>(a, scale, s); case 48 * 8 + 2: return FN<48, 2>(a, scale, s); \
-        case 48 * 8 + 1: return FN<48, 1>(a, scale, s);                                                  \
-        case 64 * 8 + 4: return FN<64, 4>(a, scale, s); case 64 * 8 + 2: return FN<64, 2>(a, scale, s); \
-        case 64 * 8 + 1: return FN<64, 1>(a, scale, s);                                                  \
-        default: break;                                                                                  \
-    }
 
 hipError_t mdt_launch_attn_fwd_train(const mdt_attn_train_args& a, hipStream_t s, int kv_rows) {
-    if (a.Tq > 16 || a.Tk > 16) return mdt_launch_attn_chunk_fwd_train(a, s, kv_rows);   // 17 .. 64 rows: mdt_attn_chunk.hip
-    if (kv_rows != 0 && kv_rows != a.Tk) return hipErrorInvalidValue;   // the visible prefix is a form of the chunk kernels
-    if (a.Tq < 1 || a.Tq > 16 || a.Tk < 1 || a.Tk > 16) return hipErrorInvalidValue;
-    if (((a.ldq | a.ldkv | a.ldo) & 3) || (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.out) & 15))
-        return hipErrorInvalidValue;  // 16-byte loads / stores of the head slices
-    if (a.rope && (a.hd < 32 || !a.rope_cos || !a.rope_sin)) return hipErrorInvalidValue;
+    const mdt_attn_train_route r = mdt_route_attn_train(a.hd, a.H, a.Tq, a.Tk, a.causal, a.rope, kv_rows, a.p > 0.f && a.seed != 0, false);
+    if (r.family == MDT_ATTN_TRAIN_REFUSED || !mdt_attn_train_operands_ok(a)) return hipErrorInvalidValue;
     const float scale = 1.0f / sqrtf((float)a.hd);
-    if (const int hg = attn_train_mfma_group(a.hd, a.H, a.rope)) { ATTN_MFMA_DISPATCH(launch_attn_fwd_mfma, a, scale, s, hg) }
-    const dim3 grid(a.B, a.H);
-    switch (a.hd) {
-        case 16: hipLaunchKernelGGL((k_attn_fwd_train<16>), grid, dim3(64), 0, s, a, scale); break;
-        case 32: hipLaunchKernelGGL((k_attn_fwd_train<32>), grid, dim3(64), 0, s, a, scale); break;
-        case 48: hipLaunchKernelGGL((k_attn_fwd_train<48>), grid, dim3(64), 0, s, a, scale); break;
-        case 64: hipLaunchKernelGGL((k_attn_fwd_train<64>), grid, dim3(64), 0, s, a, scale); break;
-        default: return hipErrorInvalidValue;
+    switch (r.family) {
+        case MDT_ATTN_TRAIN_CHUNK: return mdt_launch_attn_chunk_fwd_train(a, r, s);
+        case MDT_ATTN_TRAIN_MFMA:
+            return with_attn_mfma(r, [&](auto hd, auto hg) {
+                return mdt_launch_lds<k_attn_fwd_train_mfma<decltype(hd)::value, decltype(hg)::value>>(dim3(a.B, r.gy), dim3(r.threads), r.lds, s, a, scale);
+            });
+        default:
+            return mdt_with_const<1, 4>(r.hd / 16, [&](auto hd16) {
+                hipLaunchKernelGGL((k_attn_fwd_train<16 * decltype(hd16)::value>), dim3(a.B, r.gy), dim3(r.threads), 0, s, a, scale);
+                return hipGetLastError();
+            });
     }
-    return hipGetLastError();
 }
 
 template <int HD>
@@ -1383,24 +1340,21 @@ __global__ __launch_bounds__(64) void k_attn_bwd(mdt_attn_bwd_args a, float scal
 }
 
 hipError_t mdt_launch_attn_bwd(const mdt_attn_bwd_args& a, hipStream_t s, int kv_rows) {
-    if (a.Tq > 16 || a.Tk > 16) return mdt_launch_attn_chunk_bwd(a, s, kv_rows);   // 17 .. 64 rows: mdt_attn_chunk.hip
-    if (kv_rows != 0 && kv_rows != a.Tk) return hipErrorInvalidValue;   // the visible prefix is a form of the chunk kernels
-    if (a.Tq < 1 || a.Tq > 16 || a.Tk < 1 || a.Tk > 16) return hipErrorInvalidValue;
-    if (((a.ldq | a.ld_do | a.ldkv | a.ld_dq | a.ld_dkv) & 3) ||
-        (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.d_out | (uintptr_t)a.dq | (uintptr_t)a.dk | (uintptr_t)a.dv) & 15))
-        return hipErrorInvalidValue;  // 16-byte loads / stores of the head slices
-    if (a.rope && (a.hd < 32 || !a.rope_cos || !a.rope_sin)) return hipErrorInvalidValue;
+    const mdt_attn_train_route r = mdt_route_attn_train(a.hd, a.H, a.Tq, a.Tk, a.causal, a.rope, kv_rows, a.p > 0.f && a.seed != 0, true);
+    if (r.family == MDT_ATTN_TRAIN_REFUSED || !mdt_attn_train_operands_ok(a)) return hipErrorInvalidValue;
     const float scale = 1.0f / sqrtf((float)a.hd);
-    if (const int hg = attn_train_mfma_group(a.hd, a.H, a.rope)) { ATTN_MFMA_DISPATCH(launch_attn_bwd_mfma, a, scale, s, hg) }
-    const dim3 grid(a.B, a.H);
-    switch (a.hd) {
-        case 16: hipLaunchKernelGGL((k_attn_bwd<16>), grid, dim3(64), 0, s, a, scale); break;
-        case 32: hipLaunchKernelGGL((k_attn_bwd<32>), grid, dim3(64), 0, s, a, scale); break;
-        case 48: hipLaunchKernelGGL((k_attn_bwd<48>), grid, dim3(64), 0, s, a, scale); break;
-        case 64: hipLaunchKernelGGL((k_attn_bwd<64>), grid, dim3(64), 0, s, a, scale); break;
-        default: return hipErrorInvalidValue;
+    switch (r.family) {
+        case MDT_ATTN_TRAIN_CHUNK: return mdt_launch_attn_chunk_bwd(a, r, s);
+        case MDT_ATTN_TRAIN_MFMA:
+            return with_attn_mfma(r, [&](auto hd, auto hg) {
+                return mdt_launch_lds<k_attn_bwd_mfma<decltype(hd)::value, decltype(hg)::value>>(dim3(a.B, r.gy), dim3(r.threads), r.lds, s, a, scale);
+            });
+        default:
+            return mdt_with_const<1, 4>(r.hd / 16, [&](auto hd16) {
+                hipLaunchKernelGGL((k_attn_bwd<16 * decltype(hd16)::value>), dim3(a.B, r.gy), dim3(r.threads), 0, s, a, scale);
+                return hipGetLastError();
+            });
     }
-    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1547,8 +1501,8 @@ __global__ __launch_bounds__(256) void k_narrow_out(const float* __restrict__ G,
 }
 hipError_t mdt_launch_narrow_out(const float* G, int64_t ldg, const float* WT, float* out, int M, int A, int D, hipStream_t s) {
     if (A < 1 || A > MDT_ACTION_DIM_MAX) return hipErrorInvalidValue;
-    if (A > 16) {
-        hipLaunchKernelGGL(k_narrow_out<true>, dim3((M + 3) / 4, (A + 15) / 16), dim3(256), 0, s, G, ldg, WT, out, M, A, D);
+    if (const int tiles = mdt_route_narrow_tiles(A)) {
+        hipLaunchKernelGGL(k_narrow_out<true>, dim3((M + 3) / 4, tiles), dim3(256), 0, s, G, ldg, WT, out, M, A, D);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_narrow_out<false>, dim3((M + 3) / 4), dim3(256), 0, s, G, ldg, WT, out, M, A, D);
@@ -1596,8 +1550,8 @@ __global__ __launch_bounds__(256) void k_narrow_dw(const float* __restrict__ G, 
 hipError_t mdt_launch_narrow_dw(const float* G, const float* Y, int64_t ldy, float* partial, int n_slices, int M, int A,
                                 int D, int transposed, hipStream_t s) {
     if (A < 1 || A > MDT_ACTION_DIM_MAX) return hipErrorInvalidValue;
-    if (A > 16) {
-        hipLaunchKernelGGL(k_narrow_dw<true>, dim3((D + 255) / 256, n_slices, (A + 15) / 16), dim3(256), 0, s, G, Y, ldy, partial, M,
+    if (const int tiles = mdt_route_narrow_tiles(A)) {
+        hipLaunchKernelGGL(k_narrow_dw<true>, dim3((D + 255) / 256, n_slices, tiles), dim3(256), 0, s, G, Y, ldy, partial, M,
                            A, D, transposed);
         return hipGetLastError();
     }
@@ -2416,74 +2370,37 @@ __global__ __launch_bounds__(TNW == 2 ? 512 : 384) void k_gemm_tn_split(const fl
         }
     }
 }
-// MDT_HIP_TN_SPLIT / mdt_op_set_tn_split: 0 = the fp32 MFMA kernel everywhere
-bool mdt_gemm_tn_split_on() { return mdt_switch_env(g_mdt_sw.tn_split, "MDT_HIP_TN_SPLIT", 1) != 0; }
+// MDT_HIP_TN_SPLIT / mdt_op_set_tn_split: 0 = the fp32 MFMA kernel everywhere (read through mdt_route_snapshot)
 extern "C" void mdt_op_set_tn_split(int32_t on) { g_mdt_sw.tn_split = on < 0 ? -1 : (on != 0); }
-// k-tile of the split kernel for a K-column product: 192 where that pads K less
-int mdt_gemm_tn_split_ktile(int K) { return (K + 191) / 192 * 192 < (K + 127) / 128 * 128 ? 192 : 128; }
-// tile of the split kernel for an (N, K) product: (n, k) = 192 x 128 where 128-wide n-tiles would pad N by more than an eighth and
-// 192-wide ones do not (N = 192, 576 ...), else 128 x (192 where that pads K less, else 128)
-void mdt_gemm_tn_split_tile(int N, int K, int* tn, int* tk) {
-    const bool n192 = 8 * ((N + 127) / 128 * 128) > 9 * N && 8 * ((N + 191) / 192 * 192) <= 9 * N;
-    *tn = n192 ? 192 : 128;
-    *tk = n192 ? 128 : mdt_gemm_tn_split_ktile(K);
-}
-template <int KTW, int TNW>
-static hipError_t launch_gemm_tn_split_t(const float* dY, int64_t ldy, const float* X, int64_t ldx, float* out, int64_t slice_stride, int M,
-                                         int N, int K, int S, int L, int accumulate, float* bpart, hipStream_t s) {
-    constexpr int NWV = TNW == 2 ? 8 : 6, TN_ = 64 * TNW, TK = 16 * KTW * (NWV / TNW);
-    constexpr size_t lds = (size_t)2 * 3 * (TN_ + TK) * 80;
-    return mdt_launch_lds<k_gemm_tn_split<KTW, TNW>>(dim3(((N + TN_ - 1) / TN_) * ((K + TK - 1) / TK), 1, S), dim3(64 * NWV), lds, s, dY, ldy,
-                                                     X, ldx, out, slice_stride, M, N, K, L, accumulate, bpart, S > 1 ? 1 : 0);
-}
+
+// dW partials of S row slices of L rows: out + z * slice_stride is slice z's (N, K) product; N, K multiples of 16
+// (16-byte aligned rows).  bpart: nullptr or (S, N) per-slice column sums of dY.  Tile, grid, threads and LDS bytes are the
+// route's (mdt_route_train.h: mdt_route_gemm_tn / mdt_route_gemm_tn_split); here: one switch from it to the instantiation.
+#define TN_ARGS dY, ldy, X, ldx, out, slice_stride, M, N, K, L, accumulate, bpart, S > 1 ? 1 : 0
+#define TN_LAUNCH(KERNEL) mdt_launch_lds<KERNEL>(dim3(r.gx, 1, r.gz), dim3(r.threads), r.lds, s, TN_ARGS)
 hipError_t mdt_launch_gemm_tn_split(const float* dY, int64_t ldy, const float* X, int64_t ldx, float* out, int64_t slice_stride, int M, int N,
                                     int K, int S, int L, int accumulate, float* bpart, hipStream_t s) {
     if (M < 1 || N < 4 || K < 4 || (N & 3) || (K & 3) || (ldy & 3) || (ldx & 3) || S < 1) return hipErrorInvalidValue;
-    int tn, tk;
-    mdt_gemm_tn_split_tile(N, K, &tn, &tk);
-#define TNS_ARGS dY, ldy, X, ldx, out, slice_stride, M, N, K, S, L, accumulate, bpart, s
-    if (tn == 192) return launch_gemm_tn_split_t<4, 3>(TNS_ARGS);
-    return tk == 192 ? launch_gemm_tn_split_t<3, 2>(TNS_ARGS) : launch_gemm_tn_split_t<2, 2>(TNS_ARGS);
-#undef TNS_ARGS
-}
-
-// dW partials of S row slices of L rows: out + z * slice_stride is slice z's (N, K) product; N, K multiples of 16
-// (16-byte aligned rows).  bpart: nullptr or (S, N) per-slice column sums of dY.
-// (KT, WN) instantiation behind a shape.  n-tile: 192 wide (12 waves, needs N and K multiples of 192: every Linear of this model)
-// from 8192 reduction rows on for matrices of at least 576 x 192, else 128 wide where N is a multiple of 128, else 64; k-tile:
-// 192 with the 192-wide n-tile, else the one that pads K less.
-void mdt_gemm_tn_tile(int64_t M, int N, int K, int* tn, int* tk) {
-    const bool ok192 = N % 192 == 0 && K % 192 == 0, ok128 = N % 128 == 0;
-    // measured, product + sum of its slices (tools/dw_bench.py, us at 64 / 128 / 192): M = 104448: 1536 x 192 712 / 689 / 628,
-    // 192 x 768 357 / - / 307, 576 x 192 288 / - / 285, 192 x 192 115 / - / 139;  M = 10240: 1536 x 384 137 / 130 / 130,
-    // 384 x 1536 134 / 128 / 128, 1152 x 384 108 / 98 / 108, 384 x 384 51 / 48 / 63;  M = 4096: 64 wide or a tie
-    // (192 wide with ONE round of workgroups, split_rows_tn: 1536 x 192 597, 192 x 768 280, 576 x 192 263)
-    // M = 10240 with that slicing: 1536 x 384 119, 384 x 1536 118, 1152 x 384 97, 384 x 384 45 -- 192 wide everywhere it fits
-    const int w = ok192 && M >= 8192 && (int64_t)N * K >= 576 * 192 ? 192 : (ok128 && M >= 8192 ? 128 : 64);
-    *tn = w;
-    *tk = w == 192 ? 192 : mdt_gemm_tn_ktile(K);
-}
-template <int KT, int WN>
-static hipError_t launch_gemm_tn_t(const float* dY, int64_t ldy, const float* X, int64_t ldx, float* out, int64_t slice_stride, int M,
-                                   int N, int K, int S, int L, int accumulate, float* bpart, hipStream_t s) {
-    constexpr int TN_ = 64 * WN, TK = 64 * KT;
-    constexpr size_t lds = (size_t)2 * 32 * ((TN_ + 4) + (TK + 4)) * sizeof(float);
-    return mdt_launch_lds<k_gemm_tn<KT, WN>>(dim3(((N + TN_ - 1) / TN_) * ((K + TK - 1) / TK), 1, S), dim3(256 * WN), lds, s, dY, ldy, X, ldx,
-                                             out, slice_stride, M, N, K, L, accumulate, bpart, S > 1 ? 1 : 0);
+    mdt_linear_bwd_plan r;
+    mdt_route_gemm_tn_split(r, N, K, S);
+    switch (r.t0 * 10 + r.t1) {   // <KTW, TNW>
+        case 43: return TN_LAUNCH((k_gemm_tn_split<4, 3>));
+        case 32: return TN_LAUNCH((k_gemm_tn_split<3, 2>));
+        default: return TN_LAUNCH((k_gemm_tn_split<2, 2>));
+    }
 }
 hipError_t mdt_launch_gemm_tn(const float* dY, int64_t ldy, const float* X, int64_t ldx, float* out, int64_t slice_stride, int M, int N,
                               int K, int S, int L, int accumulate, float* bpart, hipStream_t s) {
     if (M < 1 || N < 4 || K < 4 || (N & 3) || (K & 3) || (ldy & 3) || (ldx & 3) || S < 1) return hipErrorInvalidValue;
-    int tn, tk;
-    mdt_gemm_tn_tile(M, N, K, &tn, &tk);
-#define TN_ARGS dY, ldy, X, ldx, out, slice_stride, M, N, K, S, L, accumulate, bpart, s
-    if (tn == 192) return launch_gemm_tn_t<3, 3>(TN_ARGS);
-    if (tk == 192) return tn == 128 ? launch_gemm_tn_t<3, 2>(TN_ARGS) : launch_gemm_tn_t<3, 1>(TN_ARGS);
-    return tn == 128 ? launch_gemm_tn_t<2, 2>(TN_ARGS) : launch_gemm_tn_t<2, 1>(TN_ARGS);
+    mdt_linear_bwd_plan r;
+    mdt_route_gemm_tn(r, M, N, K, S);
+    switch (r.t0 * 10 + r.t1) {   // <KT, WN>
+        case 33: return TN_LAUNCH((k_gemm_tn<3, 3>));
+        case 32: return TN_LAUNCH((k_gemm_tn<3, 2>));
+        case 31: return TN_LAUNCH((k_gemm_tn<3, 1>));
+        case 22: return TN_LAUNCH((k_gemm_tn<2, 2>));
+        default: return TN_LAUNCH((k_gemm_tn<2, 1>));
+    }
+}
+#undef TN_LAUNCH
 #undef TN_ARGS
-}
-// k-tile width k_gemm_tn uses for a K-column product: the one that pads K less (128 on a tie)
-int mdt_gemm_tn_ktile(int K) {
-    const int p128 = (K + 127) / 128 * 128, p192 = (K + 191) / 192 * 192;
-    return p192 < p128 ? 192 : 128;
-}

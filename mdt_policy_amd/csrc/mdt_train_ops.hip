@@ -17,95 +17,9 @@
 //              "weight" X^T packed as an (N' = K, K' = Mp) image: out'(N x K) = dY^T . (X^T)^T
 //   dX[m][k] = sum_n dY[m][n] W[n][k]  -> GEMM with row operand dY and the packed image of W^T (N' = K, K' = N)
 // Mp = M rounded up to 16; the pad columns / k-slices are zero, so they add nothing.
-// Split of the row reduction of dW = dY^T X into S parallel slices of L rows (multiples of 32), so that the product
-// fills the chip with WIDE tiles however small N x K is: slice s multiplies its own (N, L) piece of dY^T with its own
-// packed (K, L) piece of X^T in ONE batched launch (grid.z = S), and the S partial (N, K) products are summed in a
-// fixed order by a column sum -- deterministic, unlike atomics.  Only worth it for deep reductions.
-static void split_rows(int64_t M, int64_t N, int64_t K, int* S, int* L) {
-    const int64_t tiles = ((N + 31) / 32) * ((K + 127) / 128);   // 32 x 128 tiles of one product
-    constexpr int64_t target = 1000, min_depth = 512;  // workgroups aimed for, least slice depth
-    // measured (B = 1024 step): aiming for ~1000 workgroups of >= 512-deep slices instead of 400
-    // of >= 1024 is 11 % faster per step (several 4-wave workgroups share a CU); reductions under 4096 rows (B = 128:
-    // 1280 rows) were 2.6 % slower when cut in two, so they keep the 1024-row floor
-    const int64_t depth = M >= 4096 ? min_depth : std::max<int64_t>(min_depth, 1024);
-    int64_t s = std::max<int64_t>(1, std::min<int64_t>((target + tiles - 1) / tiles, M / depth));
-    s = std::min<int64_t>(s, 32);
-    int64_t l = ((M + s - 1) / s + 31) / 32 * 32;                // equal slices: at most 31 pad rows each
-    while (l > 16384) { ++s; l = ((M + s - 1) / s + 31) / 32 * 32; }  // keeps the GEMM's K' well inside its limit
-    *S = (int)((M + l - 1) / l);
-    *L = (int)l;
-}
-
-// The same for k_gemm_tn (64 x 128 tiles, no transposed / packed copies to amortise): ~6 workgroups per CU queued (3 resident), slices of at
-// least 128 rows -- small batches (B = 128: 1280 rows) need the split even more than large ones.
-static void split_rows_tn(int64_t M, int64_t N, int64_t K, int* S, int* L) {
-    int tn, tk;
-    mdt_gemm_tn_tile(M, (int)N, (int)K, &tn, &tk);
-    // in units of 64-column tiles whatever the n-tile: a 128- / 192-wide workgroup counts two / three times (it has as many waves)
-    const int64_t tiles = ((N + 63) / 64) * ((K + tk - 1) / tk);
-    constexpr int64_t target = 512;  // measured at B = 1024: round 2, everything in one stream: 768 -> 11.27 ms step / 42.1 ms head, 1536 -> 11.18 / 41.4, 2304 -> 11.22 / 41.4; round 6, the weight gradients beside the chain on a side stream: 1536 -> 9.34, 768 -> 9.25, 512 -> 9.23 (fewer, deeper slices: less partial-sum traffic beside the chain)
-    int64_t s = std::max<int64_t>(1, std::min<int64_t>((target + tiles - 1) / tiles, M / 128));
-    if (tn == 192) {
-        // twelve-wave workgroups, one per CU: ONE round of them (tools/dw_bench.py at M = 104448, us at 32 / 64 / 128 slices:
-        // 1536 x 192 (8 tiles) 597 / 624 / 616, 192 x 768 (4) 495 / 280 / 302, 576 x 192 (3) 483 / 263 / 281)
-        const int64_t tiles192 = (N / 192) * (K / 192);
-        constexpr int64_t round = 256;  // workgroups aimed for
-        s = std::max<int64_t>(1, std::min<int64_t>((round + tiles192 / 2) / tiles192, M / 128));
-    }
-    constexpr int64_t cap = 128;  // measured: masked-image head 37.7 ms (64) -> 37.2 (128) = (192, 256); denoiser step unchanged
-    s = std::min<int64_t>(s, cap);
-    if (tn != 192) {
-        // whole rounds of workgroups here too where that is within a factor 1.5 of the above (192 x 192 at M = 104448, three
-        // 64 x 192 tiles: 128 slices = 384 workgroups 118 us, 170 = 510 of the 512 that are resident at once 99 us, 256 108 us)
-        const int64_t tiles_wg = ((N + tn - 1) / tn) * ((K + tk - 1) / tk);
-        const int64_t slots = 256 * (tn == 64 ? (tk == 192 ? 2 : 3) : (tk == 192 ? 1 : 2));   // resident workgroups: LDS 51 / 68 / 68 / 84 KB
-        const int64_t rounds = std::max<int64_t>(1, (tiles_wg * s + slots / 2) / slots);
-        const int64_t s2 = std::min<int64_t>((rounds * slots) / tiles_wg, M / 128);
-        if (s2 >= 1 && 2 * s2 <= 3 * s && 3 * s2 >= 2 * s) s = s2;
-    }
-    const int64_t l = ((M + s - 1) / s + 31) / 32 * 32;
-    *S = (int)((M + l - 1) / l);
-    *L = (int)l;
-}
-
-// Floats of scratch ONE product of exactly M rows needs (what mdt_linear_bwd carves out of `scratch` for it).
-static int64_t linear_bwd_scratch_exact(int64_t M, int64_t N, int64_t K) {
-    int S, L, St, Lt;
-    split_rows(M, N, K, &S, &L);
-    split_rows_tn(M, N, K, &St, &Lt);
-    const int64_t Mp = (int64_t)S * L;
-    return std::max<int64_t>((N + K) * Mp + (int64_t)S * N * K + N * (Mp / 32 + 2), (int64_t)St * N * K + (int64_t)St * N + 64);
-}
-
-// Floats of scratch that serve EVERY row count up to M.  The callers size their scratch once, for the largest batch seen, and
-// reuse it for every smaller one -- and the slice count is not monotone in M (the n-tile changes at 8192 rows, the 192-wide tile
-// wants one round of workgroups, the narrower ones whole rounds of the resident workgroups: a smaller batch can be cut into MORE
-// slices than the capacity batch), so the exact figure at M is not enough.  Closed-form bounds of both paths:
-//   k_gemm_tn: S <= M / 128 always; S <= 3/2 x min(ceil(target / tiles), cap) for the 64- / 128-wide tiles (`tiles` counted with
-//              the k-tile that gives fewer of them), S <= (256 + t / 2) / t one-round slices for the 192-wide one;
-//   transposed-copy path (odd shapes): its slice count s only grows with M and Mp = S L <= M + 32 s.
-// tests/test_cpu_abi.py sweeps the exact need of every row count below a capacity against this bound.
-int64_t mdt_linear_bwd_scratch(int64_t M, int64_t N, int64_t K) {
-    if (M < 1) M = 1;
-    // k_gemm_tn
-    constexpr int64_t target = 1536, cap = 128;
-    const int64_t tiles_min = ((N + 63) / 64) * ((K + 191) / 192);
-    int64_t s_tn = (3 * std::min<int64_t>((target + tiles_min - 1) / tiles_min, cap) + 1) / 2;
-    if (N % 192 == 0 && K % 192 == 0) {
-        const int64_t t192 = (N / 192) * (K / 192);
-        s_tn = std::max<int64_t>(s_tn, (256 + t192 / 2) / t192);
-    }
-    s_tn = std::max<int64_t>(1, std::min<int64_t>(s_tn, M / 128));
-    const int64_t need_tn = s_tn * N * K + s_tn * N + 64;
-    // transposed-copy path: split_rows' slice count before it is rounded to whole slices -- non-decreasing in M
-    int S, L;
-    split_rows(M, N, K, &S, &L);
-    int64_t s_old = std::max<int64_t>(S, std::min<int64_t>(32, std::max<int64_t>(1, M / 512)));
-    while ((M + s_old - 1) / s_old > 16384) ++s_old;
-    const int64_t Mp = M + 32 * s_old;
-    const int64_t need_old = (N + K) * Mp + s_old * N * K + N * (Mp / 32 + 2);
-    return std::max(std::max(need_tn, need_old), linear_bwd_scratch_exact(M, N, K));
-}
+// The slicing of the row reduction, the kernel and the scratch layout of a call are ONE plan (mdt_route_train.h:
+// mdt_route_linear_bwd): mdt_linear_bwd executes it, and the two scratch sizes are read off the same function.
+int64_t mdt_linear_bwd_scratch(int64_t M, int64_t N, int64_t K) { return mdt_route_linear_bwd_scratch(M, N, K); }
 
 mdt_status mdt_linear_bwd(const mdt_linear_bwd_args& a, hipStream_t s, mdt_colsum_entry* defer_bias, float* bias_space) {
     if (a.M < 1 || a.N < 1 || a.K < 1 || (a.K % 16)) return fail(MDT_ERR_INVALID_ARG, "linear_bwd: bad shape");
@@ -121,52 +35,32 @@ mdt_status mdt_linear_bwd(const mdt_linear_bwd_args& a, hipStream_t s, mdt_colsu
         }
     }
     if (defer_bias) defer_bias->src = nullptr;
-    // the bias gradient rides on the transpose the dW path needs anyway (per-32-row column partials)
-    const bool bias_from_partials = a.dbias && a.dW && !(a.N % 16);
+    // the plan: which dW path, how many slices, where each region of `scratch` lies (mdt_route_train.h)
+    const mdt_linear_bwd_plan p = mdt_route_linear_bwd(a.M, a.N, a.K, !(a.ldy % 4) && !(a.ldx % 4), a.dW != nullptr, a.dbias != nullptr,
+                                                       mdt_route_snapshot());
+    const int S = p.S, L = p.L;
+    const bool bias_from_partials = p.bias_from_partials;   // the dW path also leaves the bias gradient's partial column sums
     if (a.dbias && !bias_from_partials) LAUNCH(mdt_launch_colsum(a.dY, a.ldy, a.M, a.N, a.dbias, a.accumulate_dw, s));
-    // (bias_from_partials: the dW path below also leaves the bias gradient -- per-slice column sums of dY from k_gemm_tn,
-    //  or per-32-row partials from the transpose of the older path)
-    if (a.dW && !(a.ldy % 4) && !(a.ldx % 4)) {
-        // dW straight from dY and X (k_gemm_tn): S slices of the row reduction as one batched launch, partial products and
-        // the bias gradient's per-slice column sums added up in a fixed order afterwards
-        int S, L;
-        split_rows_tn(a.M, a.N, a.K, &S, &L);
-        // from 8192 rows on: the bf16 split kernel, ONE round of its one-per-CU workgroups (never more slices than the fp32 tiling
-        // takes: the scratch bound is that tiling's)
-        // ... where its 128-wide n-tiles pad N by at most an eighth (tools/dw_bench.py, us fp32 / split: 12288 x 1536 x 384 127 / 101,
-        // x 384 x 1536 128 / 100, x 1152 x 384 105 / 80, x 384 x 384 47 / 36; 104448 x 1536 x 192 598 / 510, x 576 x 192 217 / 185;
-        // N = 192 -- a quarter of its second tile empty -- loses: x 192 x 768 286 / 311, x 192 x 1536 507 / 590)
-        int stn = 128, stk = 128;
-        mdt_gemm_tn_split_tile(a.N, a.K, &stn, &stk);
-        const bool tn_split = a.M >= 8192 && mdt_gemm_tn_split_on() && 8 * ((a.N + stn - 1) / stn * stn) <= 9 * a.N;
-        if (tn_split) {
-            const int64_t tiles = ((a.N + stn - 1) / stn) * ((a.K + stk - 1) / stk);
-            const int64_t s2 = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(256 / tiles, S), a.M / 256));   // never a second round
-            const int64_t l2 = ((a.M + s2 - 1) / s2 + 31) / 32 * 32;
-            S = (int)((a.M + l2 - 1) / l2);
-            L = (int)l2;
-        }
-        float* parts = a.scratch;                              // [S][N][K] (S > 1)
+    float* parts = a.scratch + p.parts;                          // [S][N][K] partial products (S > 1)
+    if (p.path == MDT_DW_TN || p.path == MDT_DW_TN_SPLIT) {
+        // dW straight from dY and X: one batched launch, then partial products and the bias gradient's per-slice column sums
+        // added up in a fixed order
         const bool defer = a.dbias && defer_bias && bias_space && S <= 256;
-        float* bpart = defer ? bias_space : parts + (int64_t)S * a.N * a.K;  // [S][N]
-        if (tn_split)
+        float* bpart = defer ? bias_space : a.scratch + p.bpart;   // [S][N]
+        if (p.path == MDT_DW_TN_SPLIT)
             LAUNCH(mdt_launch_gemm_tn_split(a.dY, a.ldy, a.X, a.ldx, S > 1 ? parts : a.dW, (int64_t)a.N * a.K, a.M, a.N, a.K, S, L,
                                             S > 1 ? 0 : a.accumulate_dw, a.dbias ? bpart : nullptr, s));
         else
-        LAUNCH(mdt_launch_gemm_tn(a.dY, a.ldy, a.X, a.ldx, S > 1 ? parts : a.dW, (int64_t)a.N * a.K, a.M, a.N, a.K, S, L,
-                                  S > 1 ? 0 : a.accumulate_dw, a.dbias ? bpart : nullptr, s));
+            LAUNCH(mdt_launch_gemm_tn(a.dY, a.ldy, a.X, a.ldx, S > 1 ? parts : a.dW, (int64_t)a.N * a.K, a.M, a.N, a.K, S, L,
+                                      S > 1 ? 0 : a.accumulate_dw, a.dbias ? bpart : nullptr, s));
         if (S > 1) LAUNCH(mdt_launch_colsum(parts, (int64_t)a.N * a.K, S, a.N * a.K, a.dW, a.accumulate_dw, s));
         if (defer) *defer_bias = mdt_colsum_entry{bpart, a.dbias, (int64_t)a.N, S, a.N, a.accumulate_dw};
         else if (a.dbias) LAUNCH(mdt_launch_colsum(bpart, a.N, S, a.N, a.dbias, a.accumulate_dw, s));
-    } else if (a.dW) {
-        int S, L;
-        split_rows(a.M, a.N, a.K, &S, &L);
-        const int64_t Mp = (int64_t)S * L;
-        float* dYt = a.scratch;                                  // [S][N][L]
-        float* Xt = dYt + (int64_t)a.N * Mp;                     // [S] packed (N' = K, K' = L)
-        float* parts = Xt + (int64_t)a.K * Mp;                   // [S][N][K] partial products (S > 1)
-        float* bpart = parts + (int64_t)S * a.N * a.K;           // (ceil(M/32), N) column partials of dY
-        if (Mp != a.M) {  // zero pad rows of the last slice
+    } else if (p.path == MDT_DW_COPY) {
+        float* dYt = a.scratch + p.dYt;                          // [S][N][L]
+        float* Xt = a.scratch + p.Xt;                            // [S] packed (N' = K, K' = L)
+        float* bpart = a.scratch + p.bpart;                      // (ceil(M/32), N) column partials of dY
+        if ((int64_t)S * L != a.M) {  // zero pad rows of the last slice
             HIP_TRY(hipMemsetAsync(dYt + (int64_t)(S - 1) * a.N * L, 0, (size_t)a.N * L * sizeof(float), s));
             HIP_TRY(hipMemsetAsync(Xt + (int64_t)(S - 1) * a.K * L, 0, (size_t)a.K * L * sizeof(float), s));
         }
@@ -201,7 +95,7 @@ mdt_status mdt_linear_bwd(const mdt_linear_bwd_args& a, hipStream_t s, mdt_colsu
 }
 
 extern "C" int64_t mdt_op_linear_bwd_scratch(int64_t M, int64_t N, int64_t K) { return mdt_linear_bwd_scratch(M, N, K); }
-extern "C" int64_t mdt_op_linear_bwd_scratch_exact(int64_t M, int64_t N, int64_t K) { return linear_bwd_scratch_exact(M, N, K); }
+extern "C" int64_t mdt_op_linear_bwd_scratch_exact(int64_t M, int64_t N, int64_t K) { return mdt_route_linear_bwd_scratch_exact(M, N, K); }
 
 extern "C" mdt_status mdt_op_linear_bwd(const mdt_linear_bwd_args* a, void* stream) {
     if (!a || !a->X || !a->dY || !a->scratch) return fail(MDT_ERR_INVALID_ARG, "mdt_op_linear_bwd: null argument");

@@ -1,15 +1,18 @@
 // route_table.cpp -- which kernel a shape takes, one line per case, from the host-only route functions of
-// mdt_policy_amd/csrc/mdt_route.h.  Stand-alone: no GPU, no library; tests/test_route_table.py builds it with the sanitizers and
-// compares its lines with route_table.expected beside it.
-//   route_table           the table:       <key>: <route>
-//   route_table --cases   the GEMM cases as numbers, for a driver that issues them on a GPU and compares a kernel trace:
+// mdt_policy_amd/csrc/mdt_route.h and mdt_route_train.h.  Stand-alone: no GPU, no library; tests/test_route_table.py builds it with
+// the sanitizers and compares its lines with route_table.expected beside it.
+//   route_table           the table:       <key>: <route>, then one `invariants: OK` line (or the first violation) of a sweep of
+//                         the Linear backward's plan
+//   route_table --cases   the cases as numbers, for a driver that issues them on a GPU and compares a kernel trace:
 //                         <key> M N K ln residual aux_mode a_parts batch image geometry mlp_split ws_split side
 //                         (image: 0 none, 1 Wp_pair, 2 Wp_split)
+//                         lin_bwd/<key> M N K aligned tn_split
+//                         attn_train/<key> hd H Tq Tk causal rope kv_rows dropout bwd
 // Each pair of GEMM cases straddles one rule of mdt_route_gemm.  N x K = 384 x 384 unless the key says otherwise.
 #include <stdio.h>
 #include <string.h>
 
-#include "mdt_route.h"
+#include "mdt_route_train.h"
 
 static bool g_cases = false;
 static const float* const SOME = (const float*)16;   // a non-null operand: routes look at pointers only to see whether they are there
@@ -97,6 +100,120 @@ static void block(const BlockCase& c) {
            mdt_attn_form_name(dec.form), dec.pair ? "+pair" : "", mdt_attn_form_name(enc.form),
            mdt_mlp_form_name(mdt_route_mlp(fc, pj, true, x_in_fc, true, c.sw)), mdt_mlp_form_name(mdt_route_mlp(fc, pj, false, x_in_fc, true, c.sw)),
            (int)x_in_fc, (int)mdt_route_head_sums(0, c.A), (int)mdt_route_head_wide(c.A), (int)mdt_route_attn_chunk(c.Ta, c.Te));
+}
+
+// ---- the training path (mdt_route_train.h) ----
+// One Linear backward with dW and dbias.  aligned = 0: a row stride that is no multiple of 4 floats (the transposed-copy path, whose
+// product is the batched forward GEMM: its route is printed behind the plan).
+static void lin_bwd(int M, int N, int K, bool aligned = true, bool tn_split = true) {
+    char key[64];
+    snprintf(key, sizeof key, "lin_bwd/%dx%dx%d%s%s", M, N, K, aligned ? "" : "_unaligned", tn_split ? "" : "_tn_split0");
+    if (g_cases) {
+        printf("%s %d %d %d %d %d\n", key, M, N, K, (int)aligned, (int)tn_split);
+        return;
+    }
+    mdt_route_switches sw;
+    sw.tn_split = tn_split;
+    const mdt_linear_bwd_plan p = mdt_route_linear_bwd(M, N, K, aligned, true, true, sw);
+    char text[256], gtext[160] = "";
+    mdt_route_text(p, text, sizeof text);
+    if (p.path == MDT_DW_COPY) {   // out'(N x K) = dY^T . (X^T)^T: S slices of L rows as one batched product
+        GemmCase c = gc("", N, K, p.L);
+        c.batch = p.S > 1 ? p.S : 0;
+        mdt_route_text(mdt_route_gemm(args_of(c), sw), gtext, sizeof gtext);
+    }
+    printf("%s: %s%s%s\n", key, text, gtext[0] ? " gemm: " : "", gtext);
+}
+static void attn_train(const char* key, int hd, int H, int Tq, int Tk, int causal = 0, int rope = 0, int kv_rows = 0, bool drop = false) {
+    for (int bwd = 0; bwd < 2; ++bwd) {
+        if (g_cases) {
+            printf("attn_train/%s_%s %d %d %d %d %d %d %d %d %d\n", key, bwd ? "bwd" : "fwd", hd, H, Tq, Tk, causal, rope, kv_rows, (int)drop, bwd);
+            continue;
+        }
+        char text[160];
+        mdt_route_text(mdt_route_attn_train(hd, H, Tq, Tk, causal, rope, kv_rows, drop, bwd != 0), text, sizeof text);
+        printf("attn_train/%s_%s: %s\n", key, bwd ? "bwd" : "fwd", text);
+    }
+}
+// LayerNorm forward / backward of B samples of rps rows, and the merge fused with each; off: bytes the activation pointers are off
+// a 16-byte boundary
+static void ln(const char* key, int D, int rps, int off = 0, int row_chunks = 0, bool out_is_a = false) {
+    if (g_cases) return;
+    float* const X = (float*)(uintptr_t)(4096 + off);
+    float* const Y = (float*)(uintptr_t)(8192 + off);
+    float* const Z = (float*)(uintptr_t)(12288 + off);
+    mdt_ln_train_args f;
+    memset(&f, 0, sizeof f);
+    f.x = X; f.w = SOME; f.b = SOME; f.out = Y; f.M = 8 * rps; f.D = D; f.rows_per_sample = rps; f.shift_off = f.scale_off = -1;
+    mdt_merge_args g;
+    memset(&g, 0, sizeof g);
+    g.x = Z; g.a = Y; g.out = out_is_a ? Y : X; g.B = 8; g.rows_per_sample = rps; g.D = D;
+    mdt_ln_train_args fl = f;
+    fl.x = g.out;
+    mdt_ln_bwd_args b;
+    memset(&b, 0, sizeof b);
+    b.x = X; b.stats = SOME; b.w = SOME; b.b = SOME; b.dh = Y; b.ld_dh = D; b.dx = Z; b.pw = (float*)SOME; b.B = 8; b.rows_per_sample = rps;
+    b.D = D; b.row_chunks = row_chunks; b.shift_off = b.scale_off = -1;
+    mdt_merge_args gb = g;
+    gb.x = b.dx; gb.out = Y;
+    const mdt_ln_bwd_route r = mdt_route_ln_bwd(b, nullptr), rm = mdt_route_ln_bwd(b, &gb);
+    printf("ln/%s: fwd=%s merge_ln_fwd=%s bwd=%s rb=%d chunks=%d lds=%zu ln_bwd_merge=%s rb=%d lds=%zu\n", key, mdt_rowwise_form_name(mdt_route_ln_fwd(f)),
+           mdt_rowwise_form_name(mdt_route_merge_ln_fwd(g, fl)), mdt_rowwise_form_name(r.form), r.rb, r.chunks, r.lds, mdt_rowwise_form_name(rm.form),
+           rm.rb, rm.lds);
+}
+static void colsum(int M, int N, bool aligned = true) {
+    if (g_cases) return;
+    printf("colsum/%dx%d%s: %s colsum2=%s\n", M, N, aligned ? "" : "_off4", mdt_colsum_form_name(mdt_route_colsum(N, M, N, aligned)),
+           M >= MDT_COLSUM_DEEP_ROWS ? "two colsums" : "k_colsum2");
+}
+
+// The plan's invariants over N, K in DIMS and every M up to 2048 plus the row counts where a rule changes: S L >= M, L % 32 == 0,
+// regions disjoint and inside the total, the split plan never more slices than the fp32 plan, and the total of every path inside
+// the bound mdt_route_linear_bwd_scratch gives for every capacity >= M of the sweep.
+static bool plan_ok(const mdt_linear_bwd_plan& p, int64_t M, int64_t N, int64_t K, const char* what) {
+    const int64_t Mp = (int64_t)p.S * p.L;
+    bool ok = p.S >= 1 && Mp >= M && p.L % 32 == 0;
+    if (p.path == MDT_DW_COPY)   // dYt [S][N][L], Xt [S][K][L], parts [S][N][K], bpart (ceil(M / 32), N)
+        ok = ok && p.dYt == 0 && p.dYt + N * Mp <= p.Xt && p.Xt + K * Mp <= p.parts && p.parts + (int64_t)p.S * N * K <= p.bpart &&
+             p.bpart + (M + 31) / 32 * N <= p.total;
+    else   // parts [S][N][K], bpart [S][N]
+        ok = ok && p.parts == 0 && p.parts + (int64_t)p.S * N * K <= p.bpart && p.bpart + (int64_t)p.S * N <= p.total &&
+             p.gz == (unsigned)p.S && (int)p.gx == ((N + p.tn - 1) / p.tn) * ((K + p.tk - 1) / p.tk) && p.lds <= MDT_LDS_MAX;
+    if (!ok) printf("invariants: VIOLATED by the %s plan at M=%lld N=%lld K=%lld (S=%d L=%d total=%lld)\n", what, (long long)M, (long long)N, (long long)K, p.S, p.L, (long long)p.total);
+    return ok;
+}
+static void invariants() {
+    if (g_cases) return;
+    const int DIMS[] = {16, 64, 80, 192, 208, 384, 576, 1152, 1536};
+    static int64_t rows[2048 + 6];
+    int n_rows = 0;
+    for (int m = 1; m <= 2048; ++m) rows[n_rows++] = m;
+    for (int64_t m : {8191, 8192, 8193, 10240, 50176, 104448}) rows[n_rows++] = m;
+    mdt_route_switches on, off;
+    off.tn_split = 0;
+    long points = 0;
+    for (int N : DIMS)
+        for (int K : DIMS) {
+            int64_t worst = 0;   // the largest total of any row count so far: every capacity from here on must cover it
+            for (int i = 0; i < n_rows; ++i) {
+                const int64_t M = rows[i];
+                const mdt_linear_bwd_plan split = mdt_route_linear_bwd(M, N, K, true, true, true, on), fp32 = mdt_route_linear_bwd(M, N, K, true, true, true, off),
+                                          copy = mdt_route_linear_bwd(M, N, K, false, true, true, on);
+                if (!plan_ok(split, M, N, K, "split") || !plan_ok(fp32, M, N, K, "fp32") || !plan_ok(copy, M, N, K, "copy")) return;
+                if (split.S > fp32.S || fp32.path != MDT_DW_TN || copy.path != MDT_DW_COPY) {
+                    printf("invariants: VIOLATED at M=%lld N=%d K=%d: %d split slices, %d fp32 slices\n", (long long)M, N, K, split.S, fp32.S);
+                    return;
+                }
+                worst = std::max(worst, std::max(std::max(split.total, fp32.total), copy.total));
+                if (std::max(fp32.total, copy.total) != mdt_route_linear_bwd_scratch_exact(M, N, K) || worst > mdt_route_linear_bwd_scratch(M, N, K)) {
+                    printf("invariants: VIOLATED at M=%lld N=%d K=%d: a row count up to here needs %lld floats, the bound is %lld\n", (long long)M, N, K,
+                           (long long)worst, (long long)mdt_route_linear_bwd_scratch(M, N, K));
+                    return;
+                }
+                ++points;
+            }
+        }
+    printf("invariants: OK (%ld points)\n", points);
 }
 
 int main(int argc, char** argv) {
@@ -230,6 +347,85 @@ int main(int argc, char** argv) {
         block(c);
         c.tag = "_Ta17"; c.A = 7; c.Ta = 17;
         block(c);
+    }
+
+    // ---- the Linear backward (dW and dbias): the small shapes of tests/linear_bwd_shapes.py, whose hand-worked slice counts
+    // tests/test_route_table.py asserts against these lines ----
+    for (int M : {1, 31, 32, 33, 127, 128, 129, 130}) lin_bwd(M, 64, 128);
+    for (int N : {16, 48, 80, 240}) lin_bwd(300, N, 128);
+    for (int K : {16, 80, 208, 192, 576}) lin_bwd(300, 64, K);
+    lin_bwd(1024, 16, 16);
+    lin_bwd(1000, 80, 208);
+    lin_bwd(300, 48, 80);
+    lin_bwd(257, 64, 128);
+    // 8192 rows: n-tile 64 -> 128, split off -> on
+    lin_bwd(8191, 384, 384);
+    lin_bwd(8192, 384, 384);
+    lin_bwd(8192, 1152, 384);
+    lin_bwd(8192, 192, 768);    // N = 192: the split kernel's 192 x 128 tile; its fp32 form: the 192-wide tile
+    lin_bwd(8192, 192, 768, true, false);
+    lin_bwd(8192, 192, 192);    // ... and the fp32 form below 576 x 192: 64 wide
+    lin_bwd(8192, 192, 192, true, false);
+    lin_bwd(10240, 640, 128);
+    for (int split = 1; split >= 0; --split) {
+        lin_bwd(12288, 1536, 384, true, split != 0);
+        lin_bwd(12288, 384, 1536, true, split != 0);
+    }
+    lin_bwd(33000, 768, 208);
+    lin_bwd(8223, 240, 80);
+    // the masked-image head's 104 k rows: the fp32 form runs one round of 192-wide workgroups
+    for (int split = 1; split >= 0; --split) {
+        lin_bwd(104448, 1536, 192, true, split != 0);
+        lin_bwd(104448, 576, 192, true, split != 0);
+    }
+    lin_bwd(104448, 192, 192);   // whole rounds of resident workgroups
+    // a row stride that is no multiple of 4 floats: transposed copies, S = 1 and S > 1
+    lin_bwd(300, 64, 128, false);
+    lin_bwd(5000, 384, 384, false);
+    invariants();
+
+    // ---- training attention, forward and backward ----
+    attn_train("hd64_H8", 64, 8, 10, 10);   // head groups 4 / 2 / 1
+    attn_train("hd64_H6", 64, 6, 10, 10);
+    attn_train("hd64_H7", 64, 7, 10, 10);
+    attn_train("hd16_H8", 16, 8, 10, 10);
+    attn_train("hd48_H8", 48, 8, 10, 10);
+    attn_train("hd64_H8_rope", 64, 8, 10, 10, 0, 1);   // one wave per head
+    attn_train("hd24_H8", 24, 8, 10, 10);              // refused
+    attn_train("hd48_16x16", 48, 8, 16, 16, 1);
+    attn_train("hd48_17x16", 48, 8, 17, 16, 1);        // the chunk kernels
+    attn_train("hd48_10x17", 48, 8, 10, 17, 1);
+    attn_train("hd48_64x64", 48, 8, 64, 64, 1);
+    attn_train("hd48_65x64", 48, 8, 65, 64, 1);        // refused
+    attn_train("hd16_17x17", 16, 8, 17, 17);           // refused: the chunk kernels take heads of 32 / 48 / 64
+    attn_train("hd48_10x20_kv10", 48, 8, 10, 20, 1, 0, 10);   // a causal prefix that holds every visible key
+    attn_train("hd48_10x20_kv9", 48, 8, 10, 20, 1, 0, 9);     // ... and one that does not
+    attn_train("hd48_10x10_kv5", 48, 8, 10, 10, 1, 0, 5);     // the 16-row kernels have no prefix form
+    attn_train("hd48_17x16_drop", 48, 8, 17, 16, 1, 0, 0, true);
+    attn_train("hd48_10x10_drop", 48, 8, 10, 10, 1, 0, 0, true);
+
+    // ---- the row-wise kernels ----
+    ln("D384", 384, 10);
+    ln("D384_off4", 384, 10, 4);
+    ln("D382", 382, 10);
+    ln("D384_rps4", 384, 4);     // rows a wave keeps in flight: 1 / 2 / 2 / 3
+    ln("D384_rps5", 384, 5);
+    ln("D384_rps8", 384, 8);
+    ln("D384_rps9", 384, 9);
+    ln("D384_chunks2", 384, 10, 0, 2);          // two workgroups per sample: the merge backward is a launch of its own
+    ln("D384_out_is_a", 384, 10, 0, 0, true);   // the merge writes over its branch input: not fused with the LayerNorm behind it
+    ln("D516", 516, 10);                        // wider than a row held in registers: refused
+    colsum(64, 16380);
+    colsum(64, 16384);
+    colsum(64, 16384, false);
+    colsum(511, 384);
+    colsum(512, 384);
+    colsum(1024, 4096);
+    colsum(1024, 4100);
+    for (int A : {16, 17}) {
+        if (g_cases) break;
+        printf("narrow/A%d: %s tiles=%d\n", A, mdt_route_narrow_tiles(A) ? "k_narrow_out<true> k_narrow_dw<true>" : "k_narrow_out<false> k_narrow_dw<false>",
+               mdt_route_narrow_tiles(A));
     }
     return 0;
 }

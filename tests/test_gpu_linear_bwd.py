@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.helpers import assert_close
+from tests.linear_bwd_shapes import SMALL_SHAPES
 from tests.test_gpu_ops import dev, stream
 from tests.test_gpu_train_ops import rnd
 
@@ -141,22 +142,11 @@ def tn_slices_written(r, N, K):
     return written // (N * K + N)
 
 
-# (M, N, K, S): S = the slices split_rows_tn cuts M rows into, worked out by hand from the host code.
-# mdt_op_linear_bwd_scratch_exact cannot confirm them: at every shape here it returns the need of the transposed-copy path,
-# (N + K) Mp + ..., which exceeds the straight path's S (N K + N) + 64.  The test reads S off the scratch instead
-# (tn_slices_written) and asserts it, so a retuned split that moves a shape off its edge shows here.
-M_EDGES = [(1, 64, 128, 1), (31, 64, 128, 1), (32, 64, 128, 1), (33, 64, 128, 1),    # one ragged / exactly full 32-row chunk
-           (127, 64, 128, 1), (128, 64, 128, 1), (129, 64, 128, 1),                  # the slice-count floor M / 128
-           (130, 64, 128, 1)]                                                        # a last chunk of 2 rows
-N_EDGES = [(300, 16, 128, 2), (300, 48, 128, 2), (300, 80, 128, 2), (300, 240, 128, 2)]   # a partly empty last 64-wide n-tile
-K_EDGES = [(300, 64, 16, 2),                       # smallest accepted
-           (300, 64, 80, 2), (300, 64, 208, 2),    # ragged last k-tile
-           (300, 64, 192, 2), (300, 64, 576, 2)]   # KT = 3: one tile, three tiles
-MANY_SLICES = [(1024, 16, 16, 8),      # 8 full slices of 128 rows
-               (1000, 80, 208, 7),     # slices of 160 rows, the last of 40
-               (300, 48, 80, 2),       # 160 + 140 rows
-               (257, 64, 128, 2)]      # 160 + 97 rows
-SMALL_SHAPES = M_EDGES + N_EDGES + K_EDGES + MANY_SLICES
+# M_EDGES, N_EDGES, K_EDGES, MANY_SLICES: (M, N, K, S) with S = the slices the straight path cuts M rows into, worked out by hand
+# (tests/linear_bwd_shapes.py).  mdt_op_linear_bwd_scratch_exact cannot confirm them -- at every shape there the transposed-copy
+# path's need is the larger -- so this test reads S off the scratch (tn_slices_written); the route table
+# (tests/c_client/route_table.cpp, the lin_bwd/ keys; tests/test_route_table.py) pins the plan's S, kernel and scratch layout for
+# the same shapes without a GPU.
 
 
 @pytest.mark.parametrize("M,N,K,S", SMALL_SHAPES)

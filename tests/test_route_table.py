@@ -1,17 +1,25 @@
-"""Which kernel a shape takes: the host-only route functions (mdt_policy_amd/csrc/mdt_route.h) against the committed table.
+"""Which kernel a shape takes: the host-only route functions (mdt_policy_amd/csrc/mdt_route.h, mdt_route_train.h) against the
+committed table.
 
 tests/c_client/route_table.cpp is a stand-alone program over the route header: no GPU, no library, nothing loaded into Python.  It is
 built with the address and undefined-behaviour sanitizers and its lines are compared, key by key, with
 tests/c_client/route_table.expected -- the kernel name with its template integers, grid, threads and dynamic LDS bytes of every
 GEMM case (each pair of cases straddles one rule of mdt_route_gemm), and the attention / MLP forms of a block at the batch sizes
 where they change.  The expected GEMM lines are the kernel-trace rows of the commit before the routes moved into the header
-(profiles/route_equivalence.txt); a pull request that moves a threshold changes this table on purpose or not at all."""
+(profiles/route_equivalence.txt); a pull request that moves a threshold changes this table on purpose or not at all.
+
+The training path's lines -- lin_bwd/ (the Linear backward's plan: path, kernel, grid, threads, LDS, slices S of L rows, scratch
+floats), attn_train/, ln/, colsum/, narrow/ -- are likewise those of the commit before mdt_route_train.h
+(profiles/train_route_equivalence.txt), and the program sweeps the plan's invariants (slices cover the rows, scratch regions
+disjoint and inside the total, every total inside the allocation bound of any larger capacity) into one `invariants` line."""
 import os
 import re
 import shutil
 import subprocess
 
 import pytest
+
+from tests.linear_bwd_shapes import SMALL_SHAPES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "c_client", "route_table.cpp")
@@ -62,6 +70,25 @@ def test_no_route_asks_for_more_lds_than_a_workgroup_has(table):
         assert m, f"{key}: {val!r}"
         assert int(m.group(6)) <= LDS_MAX, f"{key}: {val}"
         assert 64 <= int(m.group(5)) <= 1024 and int(m.group(2)) >= 1, f"{key}: {val}"
+    train = {k: v for k, v in table.items() if k.startswith(("lin_bwd/", "attn_train/")) and v != "REFUSED" and not v.startswith("copy ")}
+    assert len(train) >= 60
+    for key, val in train.items():
+        m = re.search(r" grid=\((B|\d+),(\d+)(,\d+)?\) threads=(\d+) lds=(\d+)", val)
+        assert m, f"{key}: {val!r}"
+        assert int(m.group(5)) <= LDS_MAX and 64 <= int(m.group(4)) <= 1024 and int(m.group(2)) >= 1, f"{key}: {val}"
+
+
+def test_the_plans_slices_are_the_hand_worked_ones(table):
+    """S of every (M, N, K, S) of tests/linear_bwd_shapes.py -- worked out by hand, and read back off the scratch on a GPU by
+    tests/test_gpu_linear_bwd.py -- is the S of the plan."""
+    assert len(SMALL_SHAPES) == 21
+    for M, N, K, S in SMALL_SHAPES:
+        val = table[f"lin_bwd/{M}x{N}x{K}"]
+        assert val.startswith("tn k_gemm_tn<") and re.search(rf" grid=\(\d+,1,{S}\) .* S={S} L=\d+ ", val), f"{M} x {N} x {K}: {S} slices by hand, {val}"
+
+
+def test_the_plans_invariants_hold_over_the_sweep(table):
+    assert table["invariants"].startswith("OK ("), table["invariants"]
 
 
 def test_the_table_agrees_with_the_outcomes_the_rules_comments_name(table):
@@ -74,5 +101,16 @@ def test_the_table_agrees_with_the_outcomes_the_rules_comments_name(table):
     assert table["gemm/ln_1024x1536"].startswith("k_gemm<2, 3, 4,") and table["gemm/ln_1280x1152"].startswith("k_gemm<2, 3, 4,")
     # the tiled attention form up to 256 tiles: "B > 272" keeps the plain projection
     assert "dec_attn=ATTN_PROJ_WIDE " in table["block/B272_no_fold"] and "dec_attn=ATTN_PLAIN " in table["block/B273_no_fold"]
+    # 8192 rows: "n-tile ... else 128 wide where N is a multiple of 128, else 64" and the bf16 split kernel "from 8192 rows on"
+    assert table["lin_bwd/8191x384x384"].startswith("tn k_gemm_tn<2, 1>") and table["lin_bwd/8192x384x384"].startswith("tn_split k_gemm_tn_split<2, 2>")
+    # "192 wide ... for matrices of at least 576 x 192", "ONE round of them": 8 tiles x 32 slices
+    assert table["lin_bwd/8192x192x768_tn_split0"].startswith("tn k_gemm_tn<3, 3>") and table["lin_bwd/8192x192x192_tn_split0"].startswith("tn k_gemm_tn<3, 1>")
+    assert " grid=(8,1,32) " in table["lin_bwd/104448x1536x192_tn_split0"]
+    # "170 = 510 of the 512 that are resident at once" (192 x 192 at M = 104448, fp32) is the split form's bound: never more slices
+    assert int(re.search(r" S=(\d+) ", table["lin_bwd/104448x192x192"]).group(1)) <= 170
+    # head groups 4 / 2 / 1; RoPE: one wave per head; rows a wave keeps in flight 1 / 2 / 2 / 3
+    assert [table[f"attn_train/hd64_H{h}_fwd"].split(">")[0][-1] for h in (8, 6, 7)] == ["4", "2", "1"]
+    assert table["attn_train/hd64_H8_rope_bwd"].startswith("k_attn_bwd<64> ")
+    assert [re.search(r"bwd=VEC4 rb=(\d)", table[f"ln/D384_rps{r}"]).group(1) for r in (4, 5, 8, 9)] == ["1", "2", "2", "3"]
     # B = 77 is the first batch of the pair MLP (770 rows)
     assert " mlp=MLP_TWO_GEMMS " in table["block/B76"] and " mlp=MLP_FUSED_PAIR " in table["block/B77"]
