@@ -101,6 +101,20 @@ mdt_status mdt_op_map_attn_bwd(int32_t family, const float *q, const float *kv, 
 /* Bytes of dynamic LDS one workgroup of family 1 takes (the rule of mdt_map_pool.h); -1 for a shape that is none. */
 int64_t mdt_op_map_attn_lds(int32_t Q, int32_t N, int32_t D, int32_t H, int32_t bwd);
 
+/* The narrow (A = 1..64 wide) linears around the action tokens, each as the training step launches it (A <= 16: one form; 17..64:
+ * 16-column tiles of A).  Dense fp32 rows unless a stride is named; every output element is written once, nothing accumulates.
+ *   mdt_op_narrow_dw : partial[y] = sum over the rows [M y / n_slices, M (y + 1) / n_slices) of G[m][a] Y[m][d] for y = 0 ..
+ *                      n_slices - 1 (a slice without rows: zeros); G (M, A), Y (M, D) with row stride ldy >= D, partial
+ *                      (n_slices, A, D), or (n_slices, D, A) when transposed.  The step runs 512 slices and sums them with
+ *                      mdt_op_colsum.
+ *   mdt_op_narrow_out: out (M, A) = G WT^T; G (M, D) with row stride ldg >= D, WT (A, D).
+ *   mdt_op_narrow_dx : out (M, D) = G W; G (M, A), W (A, D).
+ * A null pointer, M < 1, A outside 1..64, D < 1, n_slices outside 1..65535 or a stride below D: MDT_ERR_INVALID_ARG, nothing launched. */
+mdt_status mdt_op_narrow_dw(const float *G, const float *Y, int64_t ldy, float *partial, int32_t n_slices, int32_t M, int32_t A,
+                            int32_t D, int32_t transposed, void *stream);
+mdt_status mdt_op_narrow_out(const float *G, int64_t ldg, const float *WT, float *out, int32_t M, int32_t A, int32_t D, void *stream);
+mdt_status mdt_op_narrow_dx(const float *G, const float *W, float *out, int32_t M, int32_t A, int32_t D, void *stream);
+
 /* Measurement hook: bracket every fused-MLP launch of the model-level calls that follow (mdt_sample_ddim, mdt_forward, ...)
  * with a pair of HIP events on its stream; mdt_op_trace_mlp_read waits for them, writes up to `cap` durations in
  * MICROSECONDS (launch order) to `us`, releases the events and returns how many it wrote.  The duration of the dominant

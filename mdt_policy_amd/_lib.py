@@ -335,6 +335,9 @@ SYMBOLS = [
     ("mdt_op_clock_stamp", _I32, [_VP, _VP]),
     ("mdt_op_set_ws_split", None, [_I32]),
     ("mdt_op_set_tn_split", None, [_I32]),
+    ("mdt_op_narrow_dw", _I32, [_VP, _VP, _I64, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
+    ("mdt_op_narrow_out", _I32, [_VP, _I64, _VP, _VP, _I32, _I32, _I32, _VP]),
+    ("mdt_op_narrow_dx", _I32, [_VP, _VP, _VP, _I32, _I32, _I32, _VP]),
     # include/mdt_hip_train.h
     ("mdt_train_prepare", _I32, [_VP]),
     ("mdt_grad_numel", _I64, [_VP]),

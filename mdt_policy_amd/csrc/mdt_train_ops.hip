@@ -203,6 +203,33 @@ extern "C" mdt_status mdt_op_colsum(const float* X, int64_t ldx, int64_t M, int6
     return MDT_OK;
 }
 
+// test hooks (mdt_hip_debug.h): the narrow linears around the action tokens, each through the launcher the step calls
+extern "C" mdt_status mdt_op_narrow_dw(const float* G, const float* Y, int64_t ldy, float* partial, int32_t n_slices, int32_t M,
+                                       int32_t A, int32_t D, int32_t transposed, void* stream) {
+    if (!G || !Y || !partial) return fail(MDT_ERR_INVALID_ARG, "mdt_op_narrow_dw: null argument");
+    if (M < 1 || A < 1 || A > MDT_ACTION_DIM_MAX || D < 1 || n_slices < 1 || n_slices > 65535 || ldy < D)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_narrow_dw: M %d, A %d (1..%d), D %d, n_slices %d (1..65535), ldy %lld (>= D)", M, A,
+                    MDT_ACTION_DIM_MAX, D, n_slices, (long long)ldy);
+    LAUNCH(mdt_launch_narrow_dw(G, Y, ldy, partial, n_slices, M, A, D, transposed != 0, (hipStream_t)stream));
+    return MDT_OK;
+}
+extern "C" mdt_status mdt_op_narrow_out(const float* G, int64_t ldg, const float* WT, float* out, int32_t M, int32_t A, int32_t D,
+                                        void* stream) {
+    if (!G || !WT || !out) return fail(MDT_ERR_INVALID_ARG, "mdt_op_narrow_out: null argument");
+    if (M < 1 || A < 1 || A > MDT_ACTION_DIM_MAX || D < 1 || ldg < D)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_narrow_out: M %d, A %d (1..%d), D %d, ldg %lld (>= D)", M, A, MDT_ACTION_DIM_MAX, D,
+                    (long long)ldg);
+    LAUNCH(mdt_launch_narrow_out(G, ldg, WT, out, M, A, D, (hipStream_t)stream));
+    return MDT_OK;
+}
+extern "C" mdt_status mdt_op_narrow_dx(const float* G, const float* W, float* out, int32_t M, int32_t A, int32_t D, void* stream) {
+    if (!G || !W || !out) return fail(MDT_ERR_INVALID_ARG, "mdt_op_narrow_dx: null argument");
+    if (M < 1 || A < 1 || A > MDT_ACTION_DIM_MAX || D < 1)
+        return fail(MDT_ERR_INVALID_ARG, "mdt_op_narrow_dx: M %d, A %d (1..%d), D %d", M, A, MDT_ACTION_DIM_MAX, D);
+    LAUNCH(mdt_launch_narrow_dx(G, W, out, M, A, D, (hipStream_t)stream));
+    return MDT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // multi-tensor optimizer updates: the (tensor, chunk) table of a call lives in device memory.  A training loop passes the
 // same pointers step after step, so the tables are cached by content (16 slots per device, least recently used replaced -- the reference's

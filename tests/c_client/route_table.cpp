@@ -9,6 +9,7 @@
 //                         lin_bwd/<key> M N K aligned tn_split
 //                         attn_train/<key> hd H Tq Tk causal rope kv_rows dropout bwd
 // Each pair of GEMM cases straddles one rule of mdt_route_gemm.  N x K = 384 x 384 unless the key says otherwise.
+// The deep/ lines (table only) are whole training steps at the batches of tests/deep_row_configs.py.
 #include <stdio.h>
 #include <string.h>
 
@@ -165,6 +166,68 @@ static void colsum(int M, int N, bool aligned = true) {
     if (g_cases) return;
     printf("colsum/%dx%d%s: %s colsum2=%s\n", M, N, aligned ? "" : "_off4", mdt_colsum_form_name(mdt_route_colsum(N, M, N, aligned)),
            M >= MDT_COLSUM_DEEP_ROWS ? "two colsums" : "k_colsum2");
+}
+
+// ---- whole training steps at deep row counts (tests/deep_row_configs.py, tests/test_gpu_deep_row_training.py) ----
+// One line per product of a step of the model at batch B: <layer>.fwd the forward product (M, N, K), <layer>.bwd the plan of its
+// weight / bias gradient, <layer>.dx its input-gradient product (M, K, N).  enc.* run on the B Te encoder rows, dec.* on the B Ta
+// decoder rows, the rest on B rows (the token embedding: B n_tok).  A training step's products have no LayerNorm prologue (the
+// LayerNorm is a launch of its own); c_fc leaves its pre-activation (aux_mode 1), c_proj's input gradient applies the activation's
+// backward (aux_mode 2).
+struct StepCase {
+    const char* tag;
+    int B, Ta = 10, Te = 4, D = 384, H = 8, A = 7, Ld = 4, n_tok = 3, G = 512, O = 384, HP = 0;
+    bool proprio = false, mdt = false;
+    mdt_route_switches sw;
+};
+static void step_product(const StepCase& c, const char* layer, int M, int N, int K, int fwd_aux = 0, int dx_aux = 0) {
+    if (g_cases) return;
+    char text[256];
+    GemmCase f = gc("", M, N, K);
+    if (fwd_aux) f = with_aux(f, fwd_aux);
+    mdt_route_text(mdt_route_gemm(args_of(f), c.sw), text, sizeof text);
+    printf("deep/%s/%s.fwd: %dx%dx%d %s\n", c.tag, layer, M, N, K, text);
+    mdt_route_text(mdt_route_linear_bwd(M, N, K, true, true, true, c.sw), text, sizeof text);
+    printf("deep/%s/%s.bwd: %dx%dx%d %s\n", c.tag, layer, M, N, K, text);
+    GemmCase x = gc("", M, K, N);
+    if (dx_aux) x = with_aux(x, dx_aux);
+    mdt_route_text(mdt_route_gemm(args_of(x), c.sw), text, sizeof text);
+    printf("deep/%s/%s.dx: %dx%dx%d %s\n", c.tag, layer, M, K, N, text);
+}
+static void step(const StepCase& c) {
+    const int D = c.D, Me = c.B * c.Te, Md = c.B * c.Ta;
+    for (int dec = 0; dec < 2; ++dec) {
+        const int M = dec ? Md : Me;
+        char layer[32];
+        auto name = [&](const char* l) { snprintf(layer, sizeof layer, "%s.%s", dec ? "dec" : "enc", l); return layer; };
+        step_product(c, name("qkv"), M, 3 * D, D);
+        step_product(c, name("proj"), M, D, D);   // attn.c_proj; the decoder's cross_att.query and cross_att.c_proj have its shape
+        step_product(c, name("c_fc"), M, 4 * D, D, 1);
+        step_product(c, name("c_proj"), M, D, 4 * D, 0, 2);
+    }
+    step_product(c, "enc.kv_all", Me, c.Ld * 2 * D, D);   // every decoder block's cross-attention K | V from the context, stacked
+    if (c.HP) step_product(c, "dec.head0", Md, c.HP, D);
+    step_product(c, "mod_all", c.B, c.Ld * 6 * D, D);     // every decoder block's adaLN modulation, stacked
+    step_product(c, "sigma_emb.1", c.B, 2 * D, D);
+    step_product(c, "sigma_emb.3", c.B, D, 2 * D);
+    step_product(c, "goal_emb.0", c.B, 2 * D, c.G);
+    step_product(c, "goal_emb.2", c.B, D, 2 * D);
+    step_product(c, "tok_emb", c.mdt ? c.B : c.B * c.n_tok, D, c.O);   // MDT: the static and the gripper camera's, one row per sample each
+    if (c.proprio) step_product(c, "proprio_emb.2", c.B, D, 2 * D);
+    if (g_cases) return;
+    // the attention launches: encoder and decoder self-attention, the cross-attention (causal, top-left aligned: at a context above
+    // 16 tokens it stages the visible prefix)
+    const int H = c.H, hd = c.D / H;
+    const int kv = c.Te > 16 ? (c.Te < c.Ta ? c.Te : c.Ta) : 0;   // mdt_visible_keys
+    for (int bwd = 0; bwd < 2; ++bwd) {
+        char e[160], d[160], x[160];
+        mdt_route_text(mdt_route_attn_train(hd, H, c.Te, c.Te, 0, 0, 0, false, bwd != 0), e, sizeof e);
+        mdt_route_text(mdt_route_attn_train(hd, H, c.Ta, c.Ta, 1, 0, 0, false, bwd != 0), d, sizeof d);
+        mdt_route_text(mdt_route_attn_train(hd, H, c.Ta, c.Te, 1, 0, kv, false, bwd != 0), x, sizeof x);
+        printf("deep/%s/attn.%s: enc %dx%d %s | dec %dx%d %s | cross %dx%d kv_rows=%d %s\n", c.tag, bwd ? "bwd" : "fwd", c.Te, c.Te, e, c.Ta, c.Ta, d,
+               c.Ta, c.Te, kv, x);
+    }
+    printf("deep/%s/narrow: A=%d rows=%d slice_rows=%d..%d tiles=%d\n", c.tag, c.A, Md, Md / 512, (Md + 511) / 512, mdt_route_narrow_tiles(c.A));
 }
 
 // The plan's invariants over N, K in DIMS and every M up to 2048 plus the row counts where a rule changes: S L >= M, L % 32 == 0,
@@ -426,6 +489,49 @@ int main(int argc, char** argv) {
         if (g_cases) break;
         printf("narrow/A%d: %s tiles=%d\n", A, mdt_route_narrow_tiles(A) ? "k_narrow_out<true> k_narrow_dw<true>" : "k_narrow_out<false> k_narrow_dw<false>",
                mdt_route_narrow_tiles(A));
+    }
+
+    // ---- the whole steps of tests/deep_row_configs.py, batch by batch ----
+    // 4096 rows: geometry 9; 5120: geometry 5 at d = 384; 8128: the last batch below the 8192-row routes; 8192: on them
+    for (int B : {64, 80, 127, 128}) {
+        static char tags[4][24];
+        char* tag = tags[B == 64 ? 0 : (B == 80 ? 1 : B - 125)];
+        snprintf(tag, sizeof tags[0], "ta64_a64_B%d", B);
+        StepCase c;
+        c.tag = tag; c.B = B; c.Ta = 64; c.A = 64;
+        step(c);
+    }
+    {
+        StepCase c;
+        c.tag = "ta64_a64_B128_split0"; c.B = 128; c.Ta = 64; c.A = 64; c.sw.ws_split = 0; c.sw.tn_split = 0;
+        step(c);
+        c.tag = "ta64_a64_B105"; c.B = 105; c.sw = mdt_route_switches();   // the scratch-reuse test's smaller batch
+        step(c);
+        c.tag = "ta64_a64_d192_B128"; c.B = 128; c.D = c.O = 192; c.H = 4;
+        step(c);
+        c.tag = "ta64_a64_d256_B64"; c.B = 64; c.D = c.O = 256; c.H = 8; c.G = 384;   // geometries 5 and 9 at 4096 rows
+        step(c);
+    }
+    {
+        StepCase c;
+        c.tag = "ctx64_B128"; c.B = 128; c.Te = 64; c.n_tok = 63;
+        step(c);
+        c = StepCase();
+        c.tag = "a64_rows2600_B260"; c.B = 260; c.A = 64;
+        step(c);
+        c = StepCase();
+        c.tag = "a17_mlp_proprio_rows2600_B260"; c.B = 260; c.A = 17; c.HP = 112; c.Te = 5; c.proprio = true;
+        step(c);
+        c = StepCase();
+        c.tag = "mdt_ta40_B205"; c.B = 205; c.Ta = 40; c.Te = 3; c.D = c.O = 512; c.Ld = 6; c.mdt = true;
+        step(c);
+    }
+    if (!g_cases) {
+        // scratch reuse: S of the 384 x 384 weight gradients (attn.c_proj and its kin) at the smaller batch and at the capacity batch
+        mdt_route_switches sw;
+        const mdt_linear_bwd_plan small = mdt_route_linear_bwd(105 * 64, 384, 384, true, true, true, sw), cap = mdt_route_linear_bwd(128 * 64, 384, 384, true, true, true, sw);
+        printf("deep/scratch_reuse: B=105 rows=%d S=%d total=%lld | B=128 rows=%d S=%d total=%lld | bound_at_8192=%lld\n", 105 * 64, small.S, (long long)small.total,
+               128 * 64, cap.S, (long long)cap.total, (long long)mdt_route_linear_bwd_scratch(128 * 64, 384, 384));
     }
     return 0;
 }

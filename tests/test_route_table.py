@@ -11,7 +11,11 @@ where they change.  The expected GEMM lines are the kernel-trace rows of the com
 The training path's lines -- lin_bwd/ (the Linear backward's plan: path, kernel, grid, threads, LDS, slices S of L rows, scratch
 floats), attn_train/, ln/, colsum/, narrow/ -- are likewise those of the commit before mdt_route_train.h
 (profiles/train_route_equivalence.txt), and the program sweeps the plan's invariants (slices cover the rows, scratch regions
-disjoint and inside the total, every total inside the allocation bound of any larger capacity) into one `invariants` line."""
+disjoint and inside the total, every total inside the allocation bound of any larger capacity) into one `invariants` line.
+
+The deep/ lines are whole training steps: every forward product, Linear backward plan and input-gradient product, on encoder and on
+decoder rows, of each (configuration, batch) of tests/deep_row_configs.py.  The assertions at the end of this file name the route each
+of those batches is there for, so that tests/test_gpu_deep_row_training.py cannot drift off the kernels it means to run."""
 import os
 import re
 import shutil
@@ -114,3 +118,79 @@ def test_the_table_agrees_with_the_outcomes_the_rules_comments_name(table):
     assert [re.search(r"bwd=VEC4 rb=(\d)", table[f"ln/D384_rps{r}"]).group(1) for r in (4, 5, 8, 9)] == ["1", "2", "2", "3"]
     # B = 77 is the first batch of the pair MLP (770 rows)
     assert " mlp=MLP_TWO_GEMMS " in table["block/B76"] and " mlp=MLP_FUSED_PAIR " in table["block/B77"]
+
+
+# the GEMM geometries of mdt_op_set_gemm_geometry as the route text names them
+GEO5, GEO9 = " k_gemm<2, 2, 4, ", " k_gemm<2, 3, 4, "   # 4 waves 32 x 128, 4 waves 32 x 192
+
+
+def _deep(table, name, B, layer, tag=""):
+    return table[f"deep/{name}_B{B}{tag}/{layer}"]
+
+
+def test_every_deep_row_step_has_its_lines(table):
+    """The deep/ lines are the steps of tests/deep_row_configs.py, batch by batch, at the rows the configurations give."""
+    from tests.deep_row_configs import DEEP_DROPOUT, DEEP_REUSE, DEEP_SPLIT_OFF, DEEP_STEPS, rows_of
+    assert DEEP_DROPOUT in DEEP_STEPS and DEEP_SPLIT_OFF in DEEP_STEPS and DEEP_REUSE[:2] in DEEP_STEPS
+    for name, B in DEEP_STEPS + [(DEEP_REUSE[0], DEEP_REUSE[2])]:
+        Me, Md = rows_of(name, B)
+        assert _deep(table, name, B, "enc.qkv.fwd").startswith(f"{Me}x") and _deep(table, name, B, "dec.qkv.bwd").startswith(f"{Md}x"), (name, B)
+        assert f" rows={Md} " in _deep(table, name, B, "narrow")
+        assert "REFUSED" not in "".join(v for k, v in table.items() if k.startswith(f"deep/{name}_B{B}/")), (name, B)
+
+
+def test_the_deep_row_batches_reach_the_routes_they_are_there_for(table):
+    # geometries 5 and 9 at 4096 rows (d = 256: c_proj with its deep K on the 32 x 128 tiles, qkv on the 32 x 192 ones) ...
+    assert _deep(table, "ta64_a64_d256", 64, "dec.c_proj.fwd").startswith("4096x256x1024" + GEO5)
+    assert _deep(table, "ta64_a64_d256", 64, "dec.qkv.fwd").startswith("4096x768x256" + GEO9)
+    # ... geometry 9 at 4096 rows of the shipped width, where geometry 5 starts at 5120 rows
+    assert _deep(table, "ta64_a64", 64, "dec.qkv.fwd").startswith("4096x1152x384" + GEO9) and _deep(table, "ta64_a64", 64, "dec.c_fc.fwd").startswith("4096x1536x384" + GEO9)
+    assert _deep(table, "ta64_a64", 80, "dec.c_proj.fwd").startswith("5120x384x1536" + GEO5)
+    # B = 127 is the last batch below the 8192-row routes: tiled kernels, k_gemm_tn on its 64-wide tiles
+    for layer in ("qkv", "proj", "c_fc", "c_proj"):
+        for kind in ("fwd", "dx"):
+            assert " k_gemm<" in _deep(table, "ta64_a64", 127, f"dec.{layer}.{kind}"), (layer, kind)
+        assert " tn k_gemm_tn<2, 1> " in _deep(table, "ta64_a64", 127, f"dec.{layer}.bwd"), layer
+    # the tall body
+    assert _deep(table, "ta64_a64", 128, "dec.c_proj.fwd").startswith("8192x384x1536 k_gemm_tall<")
+    assert _deep(table, "ta64_a64", 128, "dec.qkv.dx").startswith("8192x384x1152 k_gemm_tall<")
+    assert _deep(table, "ctx64", 128, "enc.c_proj.fwd").startswith("8192x384x1536 k_gemm_tall<")
+    assert _deep(table, "mdt_ta40", 205, "dec.qkv.fwd").startswith("8200x1536x512 k_gemm_tall<")
+    # k_gemm_ws at K = 384: the fp32 body with the split forms off
+    for layer in ("qkv.fwd", "proj.fwd", "c_fc.fwd", "c_proj.dx"):
+        assert " k_gemm_ws<24, " in _deep(table, "ta64_a64", 128, f"dec.{layer}", "_split0"), layer
+    # k_gemm_ws at K = 192
+    assert " k_gemm_ws_split<12, " in _deep(table, "ta64_a64_d192", 128, "dec.qkv.fwd") and " k_gemm_ws_split<12, " in _deep(table, "ta64_a64_d192", 128, "dec.proj.fwd")
+    # the split form of k_gemm_ws, on decoder and on encoder rows
+    for name, side in (("ta64_a64", "dec"), ("ctx64", "enc")):
+        for layer in ("qkv.fwd", "proj.fwd", "c_fc.fwd", "c_proj.dx"):
+            assert " k_gemm_ws_split<24, " in _deep(table, name, 128, f"{side}.{layer}"), (name, layer)
+    assert " k_gemm_ws_split<24, " in _deep(table, "ctx64", 128, "enc.kv_all.fwd")
+    # k_gemm_tn_split, and its 192 x 128 tile at N = 192
+    for layer in ("qkv", "proj", "c_fc", "c_proj"):
+        assert " tn_split k_gemm_tn_split<2, 2> " in _deep(table, "ta64_a64", 128, f"dec.{layer}.bwd"), layer
+    assert " tn_split k_gemm_tn_split<4, 3> " in _deep(table, "ta64_a64_d192", 128, "dec.proj.bwd")
+    assert " tn_split k_gemm_tn_split<4, 3> " in _deep(table, "ta64_a64_d192", 128, "dec.c_proj.bwd")
+    # k_gemm_tn<3, ...>: the 192-wide fp32 tiles with the split forms off
+    for layer in ("qkv", "proj", "c_fc", "c_proj"):
+        assert " tn k_gemm_tn<3, 3> " in _deep(table, "ta64_a64", 128, f"dec.{layer}.bwd", "_split0"), layer
+    # chunk attention in those steps; the 64-token context's cross-attention stages the 10 visible keys
+    assert " dec 64x64 k_attn_chunk_bwd<48, false> " in _deep(table, "ta64_a64", 128, "attn.bwd")
+    assert "enc 64x64 k_attn_chunk_fwd<48, false> " in _deep(table, "ctx64", 128, "attn.fwd") and " cross 10x64 kv_rows=10 k_attn_chunk_bwd<48, false> " in _deep(table, "ctx64", 128, "attn.bwd")
+    # the narrow gradients' slices of 5 and 6 rows, in the wide form (4 and 2 column tiles)
+    assert _deep(table, "a64_rows2600", 260, "narrow") == "A=64 rows=2600 slice_rows=5..6 tiles=4"
+    assert _deep(table, "a17_mlp_proprio_rows2600", 260, "narrow") == "A=17 rows=2600 slice_rows=5..6 tiles=2"
+    assert _deep(table, "a17_mlp_proprio_rows2600", 260, "dec.head0.bwd").startswith("2600x112x384 ")
+
+
+def test_the_scratch_reuse_batch_has_more_slices_than_the_capacity_batch(table):
+    """tests/test_gpu_deep_row_training.py steps one model at B = 128 and at B = 105: the 384 x 384 weight gradients of the smaller
+    batch are cut into more slices and need more scratch than those of the capacity batch, inside the bound sized at 8192 rows."""
+    from tests.deep_row_configs import DEEP_REUSE
+    name, cap, small = DEEP_REUSE
+    m = re.fullmatch(r"B=(\d+) rows=(\d+) S=(\d+) total=(\d+) \| B=(\d+) rows=(\d+) S=(\d+) total=(\d+) \| bound_at_8192=(\d+)", table["deep/scratch_reuse"])
+    assert m, table["deep/scratch_reuse"]
+    b0, r0, s0, t0, b1, r1, s1, t1, bound = map(int, m.groups())
+    assert (b0, b1) == (small, cap) and r0 < r1 == 8192
+    assert s0 > s1 and t1 < t0 <= bound
+    assert f" S={s0} " in _deep(table, name, small, "dec.proj.bwd") and f" S={s1} " in _deep(table, name, cap, "dec.proj.bwd")
