@@ -14,6 +14,19 @@
  * the loss are PyTorch-ROCm glue.  fp32, row-major, device pointers 16-byte aligned.  Its self-attention runs on
  * mdt_op_attn_mid_* up to 128 tokens (the shipped 102) wherever the LDS rule below holds the shape in every direction
  * that will run, and on mdt_op_attn_long_* otherwise, up to 4096 tokens.
+ *
+ * Row and batch counts arrive as int64_t; the kernels index rows and workgroups with 32 bits.  What does not fit is refused
+ * with MDT_ERR_UNSUPPORTED and a message that names the limit, before anything is launched:
+ *   mdt_op_rms_*, mdt_op_swiglu_*, mdt_op_scale_residual_*     M <= 2^31 - 1 = 2147483647 rows
+ *   mdt_op_swiglu_*, in addition                                M * H <= 256 * (2^31 - 1) elements
+ *   mdt_op_attn_mid_*                                           B <= 2^31 - 1 samples
+ *   mdt_op_attn_long_*                                          B * H * ceil(T / 64) <= 2^31 - 1 workgroups
+ *   mdt_op_patch_mse_*                                          B * X * (R / P)^2 <= 2^31 - 1 patches (MDT_ERR_INVALID_ARG)
+ * The scratch sizes, in floats:
+ *   mdt_op_rms_bwd_scratch(M, D)                 = ceil(M / 4) * D
+ *   mdt_op_scale_residual_bwd_scratch(M, D)      = ceil(M / 64) * D
+ *   mdt_op_scale_residual_rms_bwd_scratch(M, D)  = 2 * ceil(M / 64) * D
+ *   mdt_op_attn_long_bwd_scratch(B, H, T)        = B * H * T
  */
 #ifndef MDT_MAE_H
 #define MDT_MAE_H

@@ -844,6 +844,15 @@ hipError_t launch_bwd(const float* qkv, int64_t ld, const float* fo, int64_t ldf
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// The row kernels (k_rms_*, k_sr_rms_*) take the row count as a 32-bit int, the column sums take the number of row slices as
+// one, and a grid dimension holds 2^31 - 1 workgroups: every row op refuses more rows than that before it launches anything
+// (include/mdt_mae.h states the limit).
+constexpr int64_t ROW_LIMIT = 0x7fffffffll;
+mdt_status rows_refused(const char* what, int64_t M) {
+    return mdt_fail(MDT_ERR_UNSUPPORTED, "%s: M = %lld rows, the limit is 2147483647 (2^31 - 1: 32-bit row indices)", what,
+                    (long long)M);
+}
+
 // LayerScale + residual: out = x + gamma * z over rows of D (voltron Block: x + layer_scale(branch(x))); one 16-byte column
 // group per thread, the row loop strided by the rows a workgroup holds at once.
 __global__ __launch_bounds__(256) void k_scale_residual_fwd(const float* __restrict__ x, const float* __restrict__ z,
@@ -919,7 +928,7 @@ __global__ __launch_bounds__(256) void k_sr_rms_bwd(const float* __restrict__ xn
                                                     float* __restrict__ pgam, int M, int D4, float eps) {
     __shared__ f32x4 red[2][4][64 * SRN_C4];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r0 = blockIdx.x * SRN_ROWS, r1 = min(r0 + SRN_ROWS, M);
+    const int r0 = blockIdx.x * SRN_ROWS, r1 = r0 + min(SRN_ROWS, M - r0);   // (r0 + SRN_ROWS may pass 2^31 - 1)
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     const float Df = (float)(4 * D4);
     f32x4 gnv[SRN_C4], gmv[SRN_C4], dgn[SRN_C4], dgm[SRN_C4];
@@ -990,7 +999,8 @@ extern "C" int mdt_mae_debug_wg(unsigned long long* out, int n_wg) {   // (start
 extern "C" mdt_status mdt_op_attn_mid_fwd(const float* qkv, int64_t ld_qkv, float* out, int64_t ld_out, int64_t B, int32_t H, int32_t hd,
                                           int32_t T, float scale, void* stream) {
     if (!qkv || !out || B < 1 || H < 1 || T < 1) return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_mid_fwd: bad argument");
-    if (T > TMAX || B > 65535 * 32768ll) return mdt_fail(MDT_ERR_UNSUPPORTED, "mdt_op_attn_mid_fwd: T must be <= %d", TMAX);
+    if (T > TMAX) return mdt_fail(MDT_ERR_UNSUPPORTED, "mdt_op_attn_mid_fwd: T must be <= %d", TMAX);
+    if (B > ROW_LIMIT) return mdt_fail(MDT_ERR_UNSUPPORTED, "mdt_op_attn_mid_fwd: B must be <= 2147483647 samples (one grid dimension)");
     if (!aligned16(qkv) || !aligned16(out) || ld_qkv % 4 || ld_out % 4)
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_mid_fwd: pointers 16-byte aligned, strides multiples of 4");
     if (attn_mid_lds(hd, T, false) > 160 * 1024) return mdt_fail(MDT_ERR_UNSUPPORTED, "mdt_op_attn_mid_fwd: (T, hd) does not fit LDS");
@@ -1012,6 +1022,7 @@ extern "C" mdt_status mdt_op_attn_mid_bwd(const float* qkv, int64_t ld_qkv, cons
     if (!qkv || !out || !d_out || !d_qkv || B < 1 || H < 1 || T < 1)
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_mid_bwd: bad argument");
     if (T > TMAX) return mdt_fail(MDT_ERR_UNSUPPORTED, "mdt_op_attn_mid_bwd: T must be <= %d", TMAX);
+    if (B > ROW_LIMIT) return mdt_fail(MDT_ERR_UNSUPPORTED, "mdt_op_attn_mid_bwd: B must be <= 2147483647 samples (one grid dimension)");
     if (!aligned16(qkv) || !aligned16(out) || !aligned16(d_out) || !aligned16(d_qkv) || ld_qkv % 4 || ld_out % 4 || ld_do % 4 ||
         ld_dqkv % 4)
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_attn_mid_bwd: pointers 16-byte aligned, strides multiples of 4");
@@ -1465,8 +1476,8 @@ mdt_status long_check(const char* what, int64_t B, int32_t H, int32_t hd, int32_
     if (hd != 16 && hd != 24 && hd != 32 && hd != 48 && hd != 64)
         return mdt_fail(MDT_ERR_UNSUPPORTED, "%s: head dim %d (supported 16/24/32/48/64)", what, hd);
     if (!aligned_ok) return mdt_fail(MDT_ERR_INVALID_ARG, "%s: pointers 16-byte aligned, strides multiples of 4", what);
-    if (B * H * ((T + LB - 1) / LB) > 0x7fffffffll)
-        return mdt_fail(MDT_ERR_UNSUPPORTED, "%s: batch too large", what);
+    if (B > 0x7fffffffll / ((int64_t)H * ((T + LB - 1) / LB)))   // (the product itself could pass 2^63)
+        return mdt_fail(MDT_ERR_UNSUPPORTED, "%s: batch too large (B * H * ceil(T / %d) must be <= 2147483647 workgroups)", what, LB);
     return MDT_OK;
 }
 }  // namespace
@@ -1509,6 +1520,7 @@ extern "C" mdt_status mdt_op_attn_long_bwd(const float* qkv, int64_t ld_qkv, con
 
 extern "C" mdt_status mdt_op_rms_fwd(const float* x, const float* g, float* out, int64_t M, int32_t D, float eps, void* stream) {
     if (!x || !g || !out || M < 1 || D < 1 || D > 512) return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_rms_fwd: bad argument (D <= 512)");
+    if (M > ROW_LIMIT) return rows_refused("mdt_op_rms_fwd", M);
     LAUNCH(mdt_launch_rms_fwd(x, g, out, M, D, eps, (hipStream_t)stream));
     return MDT_OK;
 }
@@ -1519,6 +1531,7 @@ extern "C" mdt_status mdt_op_rms_bwd(const float* x, const float* g, const float
                                      int32_t accumulate_dg, int64_t M, int32_t D, float eps, float* scratch, void* stream) {
     if (!x || !g || !dy || !dx || !scratch || M < 1 || D < 1 || D > 512)
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_rms_bwd: bad argument (D <= 512)");
+    if (M > ROW_LIMIT) return rows_refused("mdt_op_rms_bwd", M);
     hipStream_t s = (hipStream_t)stream;
     LAUNCH(mdt_launch_rms_bwd(x, g, dy, dx, accumulate_dx, scratch, M, D, eps, s));
     if (dg) LAUNCH(mdt_launch_colsum(scratch, D, (int)((M + 3) / 4), D, dg, accumulate_dg, s));
@@ -1529,6 +1542,7 @@ extern "C" mdt_status mdt_op_rms_bwd_res(const float* x, const float* g, const f
                                          int32_t accumulate_dg, int64_t M, int32_t D, float eps, float* scratch, void* stream) {
     if (!x || !g || !dy || !d_res || !dx || !scratch || M < 1 || D < 1 || D > 512)
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_rms_bwd_res: bad argument (D <= 512)");
+    if (M > ROW_LIMIT) return rows_refused("mdt_op_rms_bwd_res", M);
     hipStream_t s = (hipStream_t)stream;
     LAUNCH(mdt_launch_rms_bwd(x, g, dy, dx, 0, scratch, M, D, eps, s, d_res));
     if (dg) LAUNCH(mdt_launch_colsum(scratch, D, (int)((M + 3) / 4), D, dg, accumulate_dg, s));
@@ -1541,6 +1555,7 @@ extern "C" mdt_status mdt_op_scale_residual_fwd(const float* x, const float* z, 
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_scale_residual_fwd: bad argument (D a multiple of 4, <= 1024)");
     if (!aligned16(x) || !aligned16(z) || !aligned16(gamma) || !aligned16(out))
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_scale_residual_fwd: pointers must be 16-byte aligned");
+    if (M > ROW_LIMIT) return rows_refused("mdt_op_scale_residual_fwd", M);
     const int64_t n4 = M * (D / 4);
     hipLaunchKernelGGL(k_scale_residual_fwd, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, z, gamma, out,
                        n4, D / 4);
@@ -1554,6 +1569,7 @@ extern "C" mdt_status mdt_op_scale_residual_rms_fwd(const float* x, const float*
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_scale_residual_rms_fwd: bad argument (D a multiple of 4, <= 512)");
     if (!aligned16(x) || !aligned16(z) || !aligned16(gamma) || !aligned16(g_norm) || !aligned16(x_new) || !aligned16(h))
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_scale_residual_rms_fwd: pointers must be 16-byte aligned");
+    if (M > ROW_LIMIT) return rows_refused("mdt_op_scale_residual_rms_fwd", M);
     hipLaunchKernelGGL(k_sr_rms_fwd, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, z, gamma, g_norm, x_new, h, (int)M,
                        D / 4, eps);
     LAUNCH(hipGetLastError());
@@ -1571,6 +1587,7 @@ extern "C" mdt_status mdt_op_scale_residual_rms_bwd(const float* x_new, const fl
     if (!aligned16(x_new) || !aligned16(g_norm) || !aligned16(d_h) || !aligned16(d_res) || !aligned16(z) || !aligned16(gamma) ||
         !aligned16(d_x) || !aligned16(d_z) || !aligned16(scratch))
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_scale_residual_rms_bwd: pointers must be 16-byte aligned");
+    if (M > ROW_LIMIT) return rows_refused("mdt_op_scale_residual_rms_bwd", M);
     hipStream_t s = (hipStream_t)stream;
     const int64_t slices = (M + SRN_ROWS - 1) / SRN_ROWS;
     float* pgn = scratch;
@@ -1591,6 +1608,7 @@ extern "C" mdt_status mdt_op_scale_residual_bwd(const float* g, const float* z, 
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_scale_residual_bwd: bad argument (D a multiple of 4, <= 1024)");
     if (!aligned16(g) || !aligned16(z) || !aligned16(gamma) || !aligned16(dz) || !aligned16(scratch))
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_scale_residual_bwd: pointers must be 16-byte aligned");
+    if (M > ROW_LIMIT) return rows_refused("mdt_op_scale_residual_bwd", M);
     hipStream_t s = (hipStream_t)stream;
     const int64_t slices = (M + SR_ROWS - 1) / SR_ROWS;
     hipLaunchKernelGGL(k_scale_residual_bwd, dim3((unsigned)slices), dim3(256), 0, s, g, z, gamma, dz, scratch, M, D / 4);
@@ -1601,12 +1619,18 @@ extern "C" mdt_status mdt_op_scale_residual_bwd(const float* g, const float* z, 
 
 extern "C" mdt_status mdt_op_swiglu_fwd(const float* u, float* out, int64_t M, int32_t H, void* stream) {
     if (!u || !out || M < 1 || H < 1) return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_swiglu_fwd: bad argument");
+    if (M > ROW_LIMIT) return rows_refused("mdt_op_swiglu_fwd", M);
+    if ((M * H + 255) / 256 > ROW_LIMIT)
+        return mdt_fail(MDT_ERR_UNSUPPORTED, "mdt_op_swiglu_fwd: M * H = %lld elements, the limit is 256 * 2147483647 (one grid dimension)", (long long)(M * H));
     LAUNCH(mdt_launch_swiglu_fwd(u, out, M, H, (hipStream_t)stream));
     return MDT_OK;
 }
 
 extern "C" mdt_status mdt_op_swiglu_bwd(const float* u, const float* d_out, float* du, int64_t M, int32_t H, void* stream) {
     if (!u || !d_out || !du || M < 1 || H < 1) return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_swiglu_bwd: bad argument");
+    if (M > ROW_LIMIT) return rows_refused("mdt_op_swiglu_bwd", M);
+    if ((M * H + 255) / 256 > ROW_LIMIT)
+        return mdt_fail(MDT_ERR_UNSUPPORTED, "mdt_op_swiglu_bwd: M * H = %lld elements, the limit is 256 * 2147483647 (one grid dimension)", (long long)(M * H));
     LAUNCH(mdt_launch_swiglu_bwd(u, d_out, du, M, H, (hipStream_t)stream));
     return MDT_OK;
 }
@@ -1683,8 +1707,10 @@ extern "C" mdt_status mdt_op_patch_mse_fwd(const float* rec, const float* imgs, 
                                            float* mask_sum, int64_t B, int32_t X, int32_t C_, int32_t R, int32_t P, void* stream) {
     if (!rec || !imgs || !mask || !partial || !loss || !mask_sum || B < 1 || X < 1 || C_ < 1 || P < 1 || R < P || (R % P))
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_patch_mse_fwd: bad argument");
-    const int n = (R / P) * (R / P);
-    if (B * X * n > ((int64_t)1 << 31) - 1) return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_patch_mse_fwd: batch too large");
+    const int64_t n64 = (int64_t)(R / P) * (R / P);   // one workgroup per (b, x, patch)
+    if (n64 > ROW_LIMIT || X > ROW_LIMIT / n64 || B > ROW_LIMIT / (X * n64))
+        return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_patch_mse_fwd: batch too large (B * X * patches must be <= 2147483647)");
+    const int n = (int)n64;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_patch_mse_fwd, dim3((unsigned)(B * X * n)), dim3(256), 0, s, rec, imgs, mask, partial, X, n, C_, R, P);
     LAUNCH(hipGetLastError());
@@ -1698,8 +1724,10 @@ extern "C" mdt_status mdt_op_patch_mse_bwd(const float* rec, const float* imgs, 
                                            void* stream) {
     if (!rec || !imgs || !mask || !mask_sum || !g || !d_rec || B < 1 || X < 1 || C_ < 1 || P < 1 || R < P || (R % P))
         return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_patch_mse_bwd: bad argument");
-    const int n = (R / P) * (R / P);
-    if (B * X * n > ((int64_t)1 << 31) - 1) return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_patch_mse_bwd: batch too large");
+    const int64_t n64 = (int64_t)(R / P) * (R / P);   // one workgroup per (b, x, patch)
+    if (n64 > ROW_LIMIT || X > ROW_LIMIT / n64 || B > ROW_LIMIT / (X * n64))
+        return mdt_fail(MDT_ERR_INVALID_ARG, "mdt_op_patch_mse_bwd: batch too large (B * X * patches must be <= 2147483647)");
+    const int n = (int)n64;
     hipLaunchKernelGGL(k_patch_mse_bwd, dim3((unsigned)(B * X * n)), dim3(256), 0, (hipStream_t)stream, rec, imgs, mask, mask_sum, g,
                        d_rec, X, n, C_, R, P);
     LAUNCH(hipGetLastError());
