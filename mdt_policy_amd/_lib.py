@@ -356,6 +356,8 @@ SYMBOLS = [
     ("mdt_log_likelihood", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _F, _F, _I64, _I32, C.POINTER(LoglikParams), _VP, _VP, _VP,
                                   C.POINTER(LoglikInfo), _VP]),
     ("mdt_sample_ddim_steer", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _I64, _I32, _VP, _VP, _F, _VP, _VP, _VP, _VP, _VP]),
+    ("mdt_sample_steer", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, _VP, _I32,
+                                _I64, _I32, _VP, _VP, _F, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("mdt_dopri5_h0", C.c_double, [C.c_double, C.c_double]),
     ("mdt_dopri5_h1", C.c_double, [C.c_double, C.c_double, C.c_double]),
     ("mdt_dopri5_next", C.c_double, [C.c_double, C.c_double, C.POINTER(_I32)]),

@@ -102,8 +102,8 @@ struct mdt_model {
     float* ll_ws = nullptr;
     int64_t ll_rows = 0, ll_probes = 0;
     void* ll_host = nullptr;
-    // mdt_sample_ddim_steer (mdt_steer.hip): the working state, the denoised chunk, the constraint error and the rows' sigma at
-    // st_rows chunks, grown by mdt_grow_carve
+    // mdt_sample_ddim_steer / mdt_sample_steer (mdt_steer.hip): the working state, the denoised chunk, the constraint error, the
+    // rows' sigma and, for a plan call, the evaluation's input and the four history slots at st_rows chunks, grown by mdt_grow_carve
     float* st_ws = nullptr;
     int64_t st_rows = 0;
     // mdt_sample_sde_tree*: the plan's noise-row points (mdt_tree_q) and the rows (tr_rows, tr_nel) k_brownian_fill writes, grown by

@@ -1,5 +1,5 @@
-// mdt_steer.hip -- mdt_sample_ddim_steer (include/mdt_hip_train.h): DDIM steered toward known actions through the denoiser's
-// Jacobian, as one enqueue.
+// mdt_steer.hip -- mdt_sample_ddim_steer and mdt_sample_steer (include/mdt_hip_train.h): DDIM, and every sampler of a plan
+// (mdt_sampler_plan.h), steered toward known actions through the denoiser's Jacobian, as one enqueue.
 //
 // A steer is (known, weight, beta).  Wherever the sampler used D(x; sigma) it uses
 //     D'(x; sigma) = D + s(sigma) J^T (weight . (known - D)),   J = dD/dx,   s(sigma) = min(beta, 1 + sigma^2 / sigma_data^2)
@@ -8,21 +8,28 @@
 // K|V once per call on the B observations (once per step where sigma is a context token), per step one tape-keeping decoder
 // forward on the R = B * K chunks and one input-gradient-only backward over that tape.  This file holds the two kernels that
 // stand where mdt_ll_vjp's seed and finish launches stand -- the seed forms D and e on the way, the finish the steered DDIM
-// update -- and the host loop.  Neither kernel uses atomics, LDS or scratch; every element is written by one thread.
+// update -- and the host loop.  mdt_sample_steer runs a sampler plan the same way: per evaluation of the plan one forward on the
+// evaluation's input Y, the same seed at the evaluation's own sigma, and k_steer_plan as the finish -- D' and then the plan's
+// per-element update (head_plan_elem, the one the unsteered plan heads call) on X, Y, D', d = (Y - D') / sigma, H0..H3, N0, N1.
+// No kernel here uses atomics, LDS or scratch; every element is written by one thread.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 
 #include "mdt_hip_train.h"
+#include "mdt_internal.h"
 #include "mdt_launch.h"
+#include "mdt_device.h"
 #include "mdt_loglik.h"
+#include "mdt_sampler_plan.h"
+#include "mdt_tiles.h"
 
 #define fail mdt_fail
 
 namespace {
 
-// Both kernels: 256 threads (four wave64), grid-stride over the N = R * Ta * A elements.  Ta * A = 70 is no multiple of 64 and N
+// Every kernel: 256 threads (four wave64), grid-stride over the N = R * Ta * A elements.  Ta * A = 70 is no multiple of 64 and N
 // rarely one of 256: the bound is per element, and no lane cooperates with another, so a partly filled wave just idles its tail.
 constexpr int STEER_THREADS = 256;
 constexpr int STEER_MAX_BLOCKS = 1024;
@@ -79,14 +86,92 @@ __global__ __launch_bounds__(STEER_THREADS) void k_steer_step(const float* __res
     }
 }
 
-// the call's buffers over one device block
+
+// The first launch of a plan call over the N elements, the R sigma entries behind them (k_sampler_first's arithmetic without the
+// embedding): Y_0 = x_T + y0_cn N[y0_noise] (n0: that noise row or null), X = x_T, the four history slots zero -- a zero
+// coefficient does not neutralise what an earlier call left there -- and the rows' sigma for the first forward.  x_T is only read.
+__global__ __launch_bounds__(STEER_THREADS) void k_steer_first(const float* __restrict__ x_T, const float* __restrict__ n0, float cn,
+                                                               float sigma0, int64_t N, int64_t R, float* __restrict__ X,
+                                                               float* __restrict__ Y, float* __restrict__ hist,
+                                                               float* __restrict__ sig_rows) {
+    for (int64_t i = (int64_t)blockIdx.x * STEER_THREADS + threadIdx.x; i < N + R; i += (int64_t)gridDim.x * STEER_THREADS) {
+        if (i < N) {
+            float v = x_T[i];
+            if (n0 != nullptr && cn != 0.f) v = v + n0[i] * cn;
+            X[i] = x_T[i];
+            Y[i] = v;
+#pragma unroll
+            for (int h = 0; h < 4; ++h) hist[h * N + i] = 0.f;
+        } else {
+            sig_rows[i - N] = sigma0;
+        }
+    }
+}
+
+// what one evaluation of a steered plan call hands its finish launch: the evaluation's row of the plan by value (cx, cy, push,
+// the noise rows, the step marks, sigma_next), and the call's buffers
+struct SteerPlanArgs {
+    mdt_sampler_eval ev;
+    const float *small, *e, *D;  // the backward's result at the network's input, the seed's e and D
+    const float* Y;              // (N) this evaluation's input; y_out may be the same buffer
+    const float* X;              // (N) the state; x_out may be the same buffer
+    float *x_out, *y_out;        // X' (the call's `out` after the last evaluation);  Y' or null after the last evaluation
+    float* hist;                 // (4, N)
+    const float* noise;          // (n_noise, N) or null: every noise operand reads as 0
+    const float *lo, *hi;        // (A,) or null: where this evaluation's step is clipped at all (mdt_plan_loop_clips)
+    float* rec;                  // (2, N) this step's record rows or null
+    float* sig_rows;             // (R)
+    int64_t N, R;
+    float sd, scale;
+    int32_t n_noise, A;
+};
+
+// The end of the backward and one evaluation of a sampler plan over the N elements, the R per-row sigma entries behind them:
+// g = c_in small + c_skip e;  D' = D + scale g;  then head_plan_elem with D' as the denoised value -- X' = sum cx R clamped to
+// [lo, hi] where the evaluation ends a step, Y' = cy[NREG] X' + sum cy R, the record rows (Y, D') where it begins one, the history
+// shift -- and sig_rows = sigma_next.  X / x_out, Y / y_out and the history slots are read and written in place: each element by
+// its own thread, every read before the write, so none of them is __restrict__.
+__global__ __launch_bounds__(STEER_THREADS) void k_steer_plan(SteerPlanArgs a) {
+    const float sg = a.ev.sigma, den2 = sg * sg + a.sd * a.sd;
+    const float c_in = 1.0f / sqrtf(den2), c_skip = a.sd * a.sd / den2;
+    float cx[MDT_SAMPLER_NREG], cy[MDT_SAMPLER_NREG + 1];
+#pragma unroll
+    for (int k = 0; k < MDT_SAMPLER_NREG; ++k) { cx[k] = a.ev.cx[k]; cy[k] = a.ev.cy[k]; }
+    cy[MDT_SAMPLER_NREG] = a.ev.cy[MDT_SAMPLER_NREG];
+    const int push = a.ev.push;
+    const bool clip = a.lo != nullptr && a.ev.ends_step != 0;
+    const bool rec = a.rec != nullptr && a.ev.begins_step != 0;
+    const int nn = a.noise != nullptr ? a.n_noise : 0;  // rows outside [0, n_noise) read as 0
+    const float* n0 = (a.ev.noise[0] >= 0 && a.ev.noise[0] < nn) ? a.noise + a.ev.noise[0] * a.N : nullptr;
+    const float* n1 = (a.ev.noise[1] >= 0 && a.ev.noise[1] < nn) ? a.noise + a.ev.noise[1] * a.N : nullptr;
+    const mdt_head_plan pl = {nullptr, a.X, a.hist, a.noise, a.y_out, a.N, nn, a.lo, a.hi, a.rec, a.rec ? a.rec + a.N : nullptr};
+    for (int64_t i = (int64_t)blockIdx.x * STEER_THREADS + threadIdx.x; i < a.N + a.R; i += (int64_t)gridDim.x * STEER_THREADS) {
+        if (i < a.N) {
+            const float g = fmaf(a.small[i], c_in, a.e[i] * c_skip);
+            const float dp = a.D[i] + a.scale * g;
+            float l = 0.f, h = 0.f;
+            if (clip) {
+                const int c = (int)(i % a.A);
+                l = a.lo[c]; h = a.hi[c];
+            }
+            float xn, yn;
+            head_plan_elem(&pl, cx, cy, push, clip, rec, a.N, n0, n1, i, a.Y[i], dp, sg, l, h, true, xn, yn);
+            a.x_out[i] = xn;
+        } else {
+            a.sig_rows[i - a.N] = a.ev.sigma_next;
+        }
+    }
+}
+
+// the call's buffers over one device block (y and hist: the plan call's)
 struct SteerBufs {
-    float *x, *D, *e, *sig;
+    float *x, *D, *e, *sig, *y, *hist;
 };
 
 void carve(Bump& b, int64_t rows, int per, SteerBufs* o) {
     SteerBufs t;
     t.x = b.take(rows * per); t.D = b.take(rows * per); t.e = b.take(rows * per); t.sig = b.take(rows);
+    t.y = b.take(rows * per); t.hist = b.take(4 * rows * per);
     if (o) *o = t;
 }
 
@@ -102,6 +187,8 @@ struct Call {
     float sg, scale, ratio, coef, sigma_next;
     const float* x_in;
     float* x_out;
+    // the plan call: the evaluation under way
+    SteerPlanArgs pa;
 };
 
 hipError_t steer_seed(const mdt_ll_io& io, void* arg, hipStream_t s) {
@@ -115,6 +202,13 @@ hipError_t steer_step(const mdt_ll_io& io, void* arg, hipStream_t s) {
     return mdt_launch_lds<k_steer_step>(dim3(steer_grid(c.N + c.R)), dim3(STEER_THREADS), 0, s, (const float*)io.small,
                                         (const float*)c.b.e, (const float*)c.b.D, c.x_in, c.sg, io.sd, c.scale, c.ratio, c.coef,
                                         c.lo, c.hi, c.m->A, c.sigma_next, c.N, c.R, c.x_out, c.b.sig);
+}
+
+hipError_t steer_plan(const mdt_ll_io& io, void* arg, hipStream_t s) {
+    const Call& c = *(const Call*)arg;
+    SteerPlanArgs a = c.pa;
+    a.small = io.small;
+    return mdt_launch_lds<k_steer_plan>(dim3(steer_grid(c.N + c.R)), dim3(STEER_THREADS), 0, s, a);
 }
 
 // the rows' sigma for the first forward (k_steer_step over no elements)
@@ -145,6 +239,46 @@ mdt_status run(Call& c, const float* x_T, const float* sig, int n, float beta, f
             MDT_TRY(mdt_ll_context(m, c.run, c.tokens, c.tokens2, c.goal, c.modality, c.b.sig, c.s));
         MDT_TRY(mdt_ll_forward(m, c.run, c.x_in, c.b.sig, c.s));
         MDT_TRY(mdt_ll_backward(m, c.run, steer_seed, steer_step, &c, c.s));
+    }
+    if (ctx_out)
+        HIP_TRY(hipMemcpyAsync(ctx_out, mdt_ll_ctx(m, c.run), (size_t)c.run.B * m->Te * m->D * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    return MDT_OK;
+}
+
+// the plan's evaluations: (the context where sigma is a token,) forward on Y, backward between k_steer_seed and k_steer_plan
+mdt_status run_plan(Call& c, int kind, int n_steps, const mdt_sampler_plan_t& P, const float* x_T, const float* noise, int n_noise,
+                    float beta, float* record, float* out, float* ctx_out) {
+    mdt_model* m = c.m;
+    const float sd = m->cfg.sigma_data;
+    const int E = P.n_evals;
+    const float* y0n = (noise && P.y0_noise >= 0 && P.y0_noise < n_noise) ? noise + (int64_t)P.y0_noise * c.N : nullptr;
+    LAUNCH(mdt_launch_lds<k_steer_first>(dim3(steer_grid(c.N + c.R)), dim3(STEER_THREADS), 0, c.s, x_T, y0n, P.y0_cn, P.e[0].sigma,
+                                         c.N, c.R, c.b.x, c.b.y, c.b.hist, c.b.sig));
+    if (m->cond != COND_TOKEN) MDT_TRY(mdt_ll_context(m, c.run, c.tokens, c.tokens2, c.goal, c.modality, nullptr, c.s));
+    for (int e = 0; e < E; ++e) {
+        const bool last = e == E - 1, clips = c.lo && mdt_plan_loop_clips(kind, last);
+        const float sg = P.e[e].sigma;
+        c.sg = sg;
+        SteerPlanArgs& a = c.pa;
+        a.ev = P.e[e];
+        a.small = nullptr; a.e = c.b.e; a.D = c.b.D;
+        a.Y = c.b.y; a.X = c.b.x;
+        a.x_out = last ? out : c.b.x;
+        a.y_out = last ? nullptr : c.b.y;
+        a.hist = c.b.hist;
+        a.noise = noise;
+        a.lo = clips ? c.lo : nullptr; a.hi = clips ? c.hi : nullptr;
+        a.rec = record ? record + (int64_t)mdt_plan_step_of(kind, n_steps, e) * 2 * c.N : nullptr;
+        a.sig_rows = c.b.sig;
+        a.N = c.N; a.R = c.R;
+        a.sd = sd;
+        a.scale = fminf(beta, 1.f + (sg * sg) / (sd * sd));
+        a.n_noise = noise ? n_noise : 0;
+        a.A = m->A;
+        if (m->cond == COND_TOKEN)  // sigma is a context token: the context is this evaluation's, still on the B observations
+            MDT_TRY(mdt_ll_context(m, c.run, c.tokens, c.tokens2, c.goal, c.modality, c.b.sig, c.s));
+        MDT_TRY(mdt_ll_forward(m, c.run, c.b.y, c.b.sig, c.s));
+        MDT_TRY(mdt_ll_backward(m, c.run, steer_seed, steer_plan, &c, c.s));
     }
     if (ctx_out)
         HIP_TRY(hipMemcpyAsync(ctx_out, mdt_ll_ctx(m, c.run), (size_t)c.run.B * m->Te * m->D * sizeof(float), hipMemcpyDeviceToDevice, c.s));
@@ -199,6 +333,84 @@ extern "C" mdt_status mdt_sample_ddim_steer(mdt_model* m, const float* tokens, c
     MDT_TRY(mdt_grow_carve(m->st_ws, m->st_rows, R, [&](Bump& b, int64_t rows) { carve(b, rows, per, b.base ? &c.b : nullptr); }));
     mdt_status st = mdt_ll_open(m, batch, candidates, s, &c.run);
     if (st == MDT_OK) st = run(c, x_T, sigmas, n_steps, beta, out, ctx_out);
+    // on every path: the tapes released, the scratch handed back (a failure above keeps its own message)
+    const mdt_status closed = mdt_ll_close(m, c.run, s);
+    return st != MDT_OK ? st : closed;
+}
+
+extern "C" mdt_status mdt_sample_steer(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
+                                       const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas_host,
+                                       int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, int32_t candidates,
+                                       const float* known, const float* weight, float beta, const float* lo, const float* hi,
+                                       float* record, float* out, float* ctx_out, void* stream) {
+    const char* fn = "mdt_sample_steer";
+    if (!m) return fail(MDT_ERR_INVALID_ARG, "%s: null handle", fn);
+    if (!tokens) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens", fn);
+    if (!goal) return fail(MDT_ERR_INVALID_ARG, "%s: null goal", fn);
+    if (!x_T) return fail(MDT_ERR_INVALID_ARG, "%s: null x_T", fn);
+    if (!sigmas_host) return fail(MDT_ERR_INVALID_ARG, "%s: null sigmas_host", fn);
+    if (!known) return fail(MDT_ERR_INVALID_ARG, "%s: null known", fn);
+    if (!weight) return fail(MDT_ERR_INVALID_ARG, "%s: null weight", fn);
+    if (!out) return fail(MDT_ERR_INVALID_ARG, "%s: null out", fn);
+    if (batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: batch is %lld, must be >= 1", fn, (long long)batch);
+    if (candidates < 1) return fail(MDT_ERR_INVALID_ARG, "%s: candidates is %d, must be >= 1", fn, candidates);
+    if (!std::isfinite(beta) || !(beta > 0.f)) return fail(MDT_ERR_INVALID_ARG, "%s: beta is %g, must be finite and > 0", fn, beta);
+    const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
+    int E = 0, rows = 0;
+    switch (mdt_plan_shape(kind, p, n_steps, &E, &rows)) {
+        case MDT_PLAN_OK: break;
+        case MDT_PLAN_BAD_KIND:
+            return fail(MDT_ERR_INVALID_ARG, "%s: kind is %d, must be an mdt_sampler_kind in [0, %d)", fn, kind, (int)MDT_SAMPLER_COUNT);
+        case MDT_PLAN_BAD_STEPS:
+            return fail(MDT_ERR_INVALID_ARG, "%s: n_steps is %d, must be in [1, %d]%s", fn, n_steps, mdt_plan_max_n(kind),
+                        kind == MDT_SAMPLER_DPM_FAST ? " (dpm_fast's evaluations)" : "");
+        default:
+            return fail(MDT_ERR_INVALID_ARG, "%s: params.order is %d, lms takes 1..4", fn, p.order);
+    }
+    const int levels = mdt_plan_levels(kind, n_steps);
+    const char* rule = kind == MDT_SAMPLER_DPM_FAST ? "dpm_fast takes the two levels {sigma_max, sigma_min}, finite and > 0"
+                                                    : "the schedule must be finite and > 0, then end in 0";
+    for (int i = 0; i < levels; ++i) {
+        const bool zero = kind != MDT_SAMPLER_DPM_FAST && i == levels - 1;
+        const float v = sigmas_host[i];
+        if (zero ? v != 0.f : (!std::isfinite(v) || !(v > 0.f)))
+            return fail(MDT_ERR_INVALID_ARG, "%s: sigmas_host[%d] is %g: %s", fn, i, v, rule);
+    }
+    if (mdt_plan_check_levels(kind, p, sigmas_host) != MDT_PLAN_OK)
+        return fail(MDT_ERR_INVALID_ARG, "%s: params.eta is %g: dpm_fast with eta != 0 needs sigma_min < sigma_max (sigmas_host is {%g, %g})",
+                    fn, p.eta, sigmas_host[0], sigmas_host[1]);
+    if ((!lo) != (!hi)) return fail(MDT_ERR_INVALID_ARG, "%s: null %s: the bounds lo and hi come together", fn, lo ? "hi" : "lo");
+    static thread_local mdt_sampler_plan_t P;
+    MDT_TRY(mdt_sampler_plan(kind, &p, sigmas_host, n_steps, &P));
+    if (!noise && mdt_plan_needs_noise(kind, p))
+        return fail(MDT_ERR_INVALID_ARG, "%s: null noise: this sampler and parameter set read %d noise rows", fn, P.n_noise);
+    if (noise && n_noise < P.n_noise)
+        return fail(MDT_ERR_INVALID_ARG, "%s: n_noise is %d, the sampler reads %d noise rows", fn, n_noise, P.n_noise);
+    for (int e = 0; record && e < P.n_evals; ++e)  // the record's rows are placed by the structure: it must be the plan's
+        if (P.e[e].step != mdt_plan_step_of(kind, n_steps, e))
+            return fail(MDT_ERR_STATE, "%s: evaluation %d is in step %d of the plan, %d by its structure", fn, e, P.e[e].step,
+                        mdt_plan_step_of(kind, n_steps, e));
+    if (m->cfg.arch == MDT_ARCH_MDT && !tokens2) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: MDT needs the gripper tokens", fn);
+    MDT_TRY(mdt_ll_check(m, fn));
+    if (m->p_row >= 0 && !tokens2)
+        return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: this handle was created with use_proprio and needs state_obs", fn);
+    const int64_t R = batch * candidates, limit = ((int64_t)1 << 24) / std::max(m->Te, m->Ta);  // the decoder's row counts (int)
+    if (batch > limit / candidates)
+        return fail(MDT_ERR_INVALID_ARG, "%s: batch * candidates = %lld * %d is more than the decoder's %lld samples", fn,
+                    (long long)batch, candidates, (long long)limit);
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(s, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+        return fail(MDT_ERR_STATE, "%s: the tape path is not capture-safe and the call cannot be captured", fn);
+
+    Call c;
+    c.m = m; c.s = s; c.tokens = tokens; c.tokens2 = tokens2; c.goal = goal; c.known = known; c.weight = weight; c.lo = lo; c.hi = hi;
+    c.modality = modality; c.R = R; c.N = R * m->Ta * m->A;
+    const int per = m->Ta * m->A;
+    MDT_TRY(mdt_grow_carve(m->st_ws, m->st_rows, R, [&](Bump& b, int64_t rows_) { carve(b, rows_, per, b.base ? &c.b : nullptr); }));
+    mdt_status st = mdt_ll_open(m, batch, candidates, s, &c.run);
+    if (st == MDT_OK) st = run_plan(c, kind, n_steps, P, x_T, noise, n_noise, beta, record, out, ctx_out);
     // on every path: the tapes released, the scratch handed back (a failure above keeps its own message)
     const mdt_status closed = mdt_ll_close(m, c.run, s);
     return st != MDT_OK ? st : closed;

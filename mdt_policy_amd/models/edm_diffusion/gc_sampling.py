@@ -10,8 +10,10 @@ sample_dpm_fast (1..128 evaluations); sample_dpm_adaptive with eta = 0 on the GP
 (``GCDenoiser.sample_dpm_adaptive_native`` -> mdt_sample_dpm_adaptive).  Otherwise they are host loops over
 ``model(state, x, goal, sigma)`` (the HIP denoiser step) with the sigma-independent encoder hoisted out of the loop.
 Every sampler takes ``extra_args={"steer": ActionSteer}`` (utils/action_steer.py: D' = D + s(sigma) J^T (weight (known - D)));
-sample_ddim, and sample_euler without churn, then run as one native call (``GCDenoiser.sample_steered`` -> mdt_sample_ddim_steer),
-the others as host loops whose ``model(...)`` calls get the key.
+sample_ddim, and sample_euler without churn, then run as one native call (``GCDenoiser.sample_steered`` -> mdt_sample_ddim_steer)
+when the only other key is ``candidates``; with ``ActionSteer(..., plan_native=True)`` every other fixed-step sampler does too
+(-> mdt_sample_steer, with the noise rows its unsteered native call draws, on a host schedule).  Without that flag, and for
+sample_dpm_adaptive, a ``callback`` or a scaler without ``clip_bounds``, they are host loops whose ``model(...)`` calls get the key.
 ``log_likelihood`` with this package's GCDenoiser is one blocking call too (``GCDenoiser.log_likelihood`` ->
 mdt_log_likelihood), for K chunks per observation and P probes; ``best_candidates`` picks from its result.
 
@@ -279,17 +281,48 @@ def _steer(model, extra_args):
     return _SteeredModel(model, steer), rest, steer
 
 
-def _steer_native(model, sigmas, scaler, callback, extra_args) -> bool:
-    """Whether a steered sample_ddim / churn-free sample_euler call is the native one (mdt_sample_ddim_steer): ``_native_ok`` says
-    yes to the call without the steer, and the only other key is ``candidates``.  Steered calls are never graphed."""
+def _steer_native(model, sigmas, scaler, callback, extra_args, host_schedule=False) -> bool:
+    """Whether a steered sampler call is the native one (mdt_sample_ddim_steer for sample_ddim and churn-free sample_euler,
+    mdt_sample_steer for every other kind): ``_native_ok`` says yes to the call without the steer, and the only other key is
+    ``candidates``.  ``host_schedule``: the call takes a host schedule only (mdt_sample_steer; a device schedule keeps the host
+    loop).  Steered calls are never graphed."""
     rest = take_steer(extra_args)[1]
+    if host_schedule and torch.is_tensor(sigmas) and sigmas.device.type == "cuda":
+        return False
     return set(rest) <= {"candidates"} and _native_ok(model, sigmas, scaler, callback, rest)
 
 
-def _run_steer(model, state, action, goal, sigmas, steer, extra_args, scaler=None):
+def _plan_native(steer) -> bool:
+    """Whether a steer asks for the native call of the plan samplers (``ActionSteer(..., plan_native=True)``).  Without it a
+    steered call of those samplers is the host loop it has always been: the native route is there for the asking."""
+    return bool(getattr(steer, "plan_native", False))
+
+
+def _admits(model, sigmas, scaler, callback, extra_args, steer) -> bool:
+    """Whether a plan sampler's call is a native one: ``_native_ok`` without a steer; with one, the steer asks for it
+    (``_plan_native``) and ``_steer_native`` says yes on a host schedule."""
+    if steer is None:
+        return _native_ok(model, sigmas, scaler, callback, extra_args)
+    return _plan_native(steer) and _steer_native(model, sigmas, scaler, callback, extra_args, host_schedule=True)
+
+
+def _run_steer(model, state, action, goal, sigmas, steer, extra_args, scaler=None, kind=None, noise=None, n_steps=None, **params):
+    """The steered native call: DDIM's (``kind`` None) or the plan sampler ``kind``'s with its noise rows and parameters."""
     K = take_candidates(take_steer(extra_args)[1])[0]
-    rows = _chunk_view(state, action, None, K)[0]
-    return model.sample_steered(state, rows, goal, sigmas, steer, candidates=K, bounds=scaler).reshape(action.shape)
+    rows, noise = _chunk_view(state, action, noise, K)
+    kw = {} if kind is None else dict(params, kind=kind, noise=noise, n_steps=n_steps)
+    return model.sample_steered(state, rows, goal, sigmas, steer, candidates=K, bounds=scaler, **kw).reshape(action.shape)
+
+
+def _native(kind, model, state, action, goal, sigmas, noise, steer=None, n_steps=None, extra_args=None, tree=None, scaler=None,
+            **params):
+    """The native call of a plan sampler that ``_admits`` admitted: ``_run_native`` (graphs included), or under a steer the eager
+    steered call with the same noise rows and parameters."""
+    if steer is None:
+        return _run_native(kind, model, state, action, goal, sigmas, noise, n_steps=n_steps, extra_args=extra_args, tree=tree,
+                           scaler=scaler, **params)
+    return _run_steer(model, state, action, goal, sigmas, steer, extra_args, scaler=scaler, kind=kind, noise=noise,
+                      n_steps=n_steps, **params)
 
 
 def _chunk_view(state, action, noise, K):
@@ -455,9 +488,9 @@ def sample_euler(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     if steer is not None and s_churn == 0 and _steer_native(model, sigmas, scaler, callback, extra_args):
         _randn_rows(action, len(sigmas) - 1)  # the loop's draws: a seeded call leaves the generator where the loop leaves it
         return _run_steer(model, state, action, goal, sigmas, steer, extra_args, scaler=scaler)
-    if _native_ok(model, sigmas, scaler, callback, extra_args):
-        return _run_native("euler", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
-                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
+    if _admits(model, sigmas, scaler, callback, extra_args, steer):
+        return _native("euler", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), steer=steer,
+                       s_churn=s_churn, s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -483,10 +516,10 @@ def sample_euler_ancestral(model, state, action, goal, sigmas, scaler=None, extr
                            disable=None, eta=1.):
     """Euler steps to sigma_down plus fresh noise sigma_up (reference gc_sampling.py:213-252)."""
     model, extra_args, steer = _steer(model, extra_args)
-    if _native_ok(model, sigmas, scaler, callback, extra_args):
+    if _admits(model, sigmas, scaler, callback, extra_args, steer):
         noise = _randn_rows(action, _ancestral_draws(sigmas, eta))
-        return _run_native("euler_ancestral", model, state, action, goal, sigmas, noise, eta=eta, extra_args=extra_args,
-                           scaler=scaler)
+        return _native("euler_ancestral", model, state, action, goal, sigmas, noise, steer=steer, eta=eta, extra_args=extra_args,
+                       scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -510,9 +543,9 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
     """Karras Algorithm 2 with Heun's trapezoidal correction; plain Euler on the final step to sigma = 0
     (reference gc_sampling.py:256-312)."""
     model, extra_args, steer = _steer(model, extra_args)
-    if _native_ok(model, sigmas, scaler, callback, extra_args):
-        return _run_native("heun", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
-                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
+    if _admits(model, sigmas, scaler, callback, extra_args, steer):
+        return _native("heun", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), steer=steer,
+                       s_churn=s_churn, s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -544,9 +577,9 @@ def sample_heun(model, state, action, goal, sigmas, scaler=None, extra_args=None
 def sample_dpmpp_2m(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None):
     """DPM-Solver++(2M) multistep (reference gc_sampling.py:699-734)."""
     model, extra_args, steer = _steer(model, extra_args)
-    if _native_ok(model, sigmas, scaler, callback, extra_args):
+    if _admits(model, sigmas, scaler, callback, extra_args, steer):
         # (the loop below never reads `scaler`, as in the reference: no bounds to pass)
-        return _run_native("dpmpp_2m", model, state, action, goal, sigmas, None, extra_args=extra_args)
+        return _native("dpmpp_2m", model, state, action, goal, sigmas, None, steer=steer, extra_args=extra_args)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     old_denoised = None
@@ -572,8 +605,8 @@ def sample_dpmpp_2s(model, state, action, goal, sigmas, scaler=None, extra_args=
                     eta=1.):
     """DPM-Solver++(2S) single-step second order (reference gc_sampling.py:955-994)."""
     model, extra_args, steer = _steer(model, extra_args)
-    if _native_ok(model, sigmas, scaler, callback, extra_args):
-        return _run_native("dpmpp_2s", model, state, action, goal, sigmas, None, extra_args=extra_args, scaler=scaler)
+    if _admits(model, sigmas, scaler, callback, extra_args, steer):
+        return _native("dpmpp_2s", model, state, action, goal, sigmas, None, steer=steer, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -601,9 +634,9 @@ def sample_dpm_2(model, state, action, goal, sigmas, scaler=None, extra_args=Non
     """DPM-Solver-2 flavoured midpoint steps (reference gc_sampling.py:315-371): derivative at sigma_hat, a second
     evaluation at the log-midpoint sigma, full step with the midpoint derivative; Euler on the last step."""
     model, extra_args, steer = _steer(model, extra_args)
-    if _native_ok(model, sigmas, scaler, callback, extra_args):
-        return _run_native("dpm_2", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), s_churn=s_churn,
-                           s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
+    if _admits(model, sigmas, scaler, callback, extra_args, steer):
+        return _native("dpm_2", model, state, action, goal, sigmas, _randn_rows(action, len(sigmas) - 1), steer=steer,
+                       s_churn=s_churn, s_tmin=s_tmin, s_tmax=s_tmax, s_noise=s_noise, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     n = len(sig) - 1
@@ -636,10 +669,10 @@ def sample_dpm_2_ancestral(model, state, action, goal, sigmas, scaler=None, extr
                            disable=None, eta=1.):
     """Ancestral sampling with DPM-Solver-2 midpoint steps (reference gc_sampling.py:374-407)."""
     model, extra_args, steer = _steer(model, extra_args)
-    if _native_ok(model, sigmas, scaler, callback, extra_args):
+    if _admits(model, sigmas, scaler, callback, extra_args, steer):
         noise = _randn_rows(action, _ancestral_draws(sigmas, eta))
-        return _run_native("dpm_2_ancestral", model, state, action, goal, sigmas, noise, eta=eta, extra_args=extra_args,
-                           scaler=scaler)
+        return _native("dpm_2_ancestral", model, state, action, goal, sigmas, noise, steer=steer, eta=eta, extra_args=extra_args,
+                       scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     with _hoist(model, state, goal):
@@ -683,8 +716,9 @@ def linear_multistep_coeff(order, t, i, j):
 def sample_lms(model, state, action, goal, sigmas, scaler=None, extra_args=None, callback=None, disable=None, order=4):
     """Linear multistep (Adams-Bashforth in sigma) sampler (reference gc_sampling.py:425-460)."""
     model, extra_args, steer = _steer(model, extra_args)
-    if 1 <= order <= 4 and _native_ok(model, sigmas, scaler, callback, extra_args):
-        return _run_native("lms", model, state, action, goal, sigmas, None, order=order, extra_args=extra_args, scaler=scaler)
+    if 1 <= order <= 4 and _admits(model, sigmas, scaler, callback, extra_args, steer):
+        return _native("lms", model, state, action, goal, sigmas, None, steer=steer, order=order, extra_args=extra_args,
+                       scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     sig_np = sig.numpy()
@@ -718,15 +752,15 @@ def sample_dpmpp_2s_ancestral(model, state, action, goal, sigmas, scaler=None, e
                               disable=None, eta=1., s_noise=1., noise_sampler=None):
     """Ancestral sampling with DPM-Solver++(2S) steps (reference gc_sampling.py:864-907)."""
     model, extra_args, steer = _steer(model, extra_args)
-    if _native_ok(model, sigmas, scaler, callback, extra_args):
+    if _admits(model, sigmas, scaler, callback, extra_args, steer):
         n = len(sigmas) - 1
         if noise_sampler is None:
             noise = _randn_rows(action, n)  # default_noise_sampler: randn_like(action) per step
         else:
             sig = _host(sigmas)
             noise = _sampled_rows(action, [noise_sampler(sig[i], sig[i + 1]) for i in range(n)])
-        return _run_native("dpmpp_2s_ancestral", model, state, action, goal, sigmas, noise, eta=eta, s_noise=s_noise,
-                           extra_args=extra_args, scaler=scaler)
+        return _native("dpmpp_2s_ancestral", model, state, action, goal, sigmas, noise, steer=steer, eta=eta, s_noise=s_noise,
+                       extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
     sig = _host(sigmas)
@@ -956,11 +990,13 @@ def sample_dpm_fast(model, state, action, goal, sigma_min, sigma_max, n, scaler=
     if eta and not t_end > t_start:
         raise ValueError('eta must be 0 for reverse sampling')
     noise_sampler = default_noise_sampler(action) if noise_sampler is None else noise_sampler
-    if (isinstance(model, GCDenoiser) and callback is None and _controls(extra_args)[0] and _scaler_native(scaler)
+    rest = extra_args if steer is None else take_steer(extra_args)[1]  # a steer rides alone or with ``candidates``
+    if (isinstance(model, GCDenoiser) and callback is None and _controls(rest)[0] and _scaler_native(scaler)
+            and (steer is None or (_plan_native(steer) and set(rest) <= {"candidates"}))
             and 1 <= n <= _lib.SAMPLER_MAX_EVALS):  # (the solver never reads `scaler`, here as in the reference: no bounds to pass)
-        return _run_native("dpm_fast", model, state, action, goal, [float(sigma_max), float(sigma_min)],
-                           _dpm_fast_noise(action, t_start, t_end, n, eta, noise_sampler), n_steps=n, eta=eta, s_noise=s_noise,
-                           extra_args=extra_args)
+        return _native("dpm_fast", model, state, action, goal, [float(sigma_max), float(sigma_min)],
+                       _dpm_fast_noise(action, t_start, t_end, n, eta, noise_sampler), steer=steer, n_steps=n, eta=eta,
+                       s_noise=s_noise, extra_args=extra_args)
     with _hoist(model, state, goal):
         return _dpm_fast_run(_EpsEvaluator(model, state, goal, extra_args), action, t_start, t_end, n, eta, s_noise,
                              noise_sampler, callback)
@@ -1164,12 +1200,14 @@ def sample_dpmpp_sde(model, state, action, goal, sigmas, extra_args=None, callba
     NativeBrownianTreeNoiseSampler with the identity transform on the model's device -- is walked inside the call
     (mdt_sample_sde_tree): no noise on the host and no read-back of a device schedule."""
     model, extra_args, steer = _steer(model, extra_args)
-    if _native_ok(model, sigmas, scaler, callback, extra_args):
+    if _admits(model, sigmas, scaler, callback, extra_args, steer):
         tree = None
-        if noise_sampler is None and not _torchsde_available():  # the default's one seed draw, as its constructor makes it
+        # (the steered call takes noise rows, not a tree: they are read below from the sampler the host loop would construct, at
+        # the loop's points)
+        if steer is None and noise_sampler is None and not _torchsde_available():  # the default's one seed draw, as its constructor makes it
             seed = torch.randint(0, 2 ** 63 - 1, []).item()
             tree = (torch.tensor([seed], dtype=torch.int64, device=action.device), 1e-6, 0., 0.)
-        elif isinstance(noise_sampler, NativeBrownianTreeNoiseSampler):
+        elif steer is None and isinstance(noise_sampler, NativeBrownianTreeNoiseSampler):
             tree = noise_sampler.native_tree(action.device)
         if tree is not None:
             return _run_native("dpmpp_sde", model, state, action, goal, sigmas, None, eta=eta, s_noise=s_noise, r=r,
@@ -1185,8 +1223,8 @@ def sample_dpmpp_sde(model, state, action, goal, sigmas, extra_args=None, callba
                 values.append(noise_sampler(_sigma(t), _sigma(s)))
             if _f(get_ancestral_step(_sigma(t), _sigma(t_next), eta)[1]) != 0:
                 values.append(noise_sampler(_sigma(t), _sigma(t_next)))
-        return _run_native("dpmpp_sde", model, state, action, goal, sigmas, _sampled_rows(action, values), eta=eta,
-                           s_noise=s_noise, r=r, extra_args=extra_args, scaler=scaler)
+        return _native("dpmpp_sde", model, state, action, goal, sigmas, _sampled_rows(action, values), steer=steer, eta=eta,
+                       s_noise=s_noise, r=r, extra_args=extra_args, scaler=scaler)
     extra_args = {} if extra_args is None else extra_args
     sig = _host(sigmas)
     if noise_sampler is None:

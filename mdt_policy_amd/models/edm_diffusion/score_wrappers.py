@@ -424,18 +424,36 @@ class GCDenoiser(nn.Module):
         return out, info
 
     @torch.no_grad()
-    def sample_steered(self, state, action, goal, sigmas, steer, candidates=None, bounds=None):
-        """The steered DDIM loop as one enqueue (mdt_sample_ddim_steer): what ``sample_ddim(..., steer=steer)`` runs, and with
-        ``bounds`` -- an ``ActionBounds`` or a (lo, hi) pair, x clamped after every step -- what gc_sampling.sample_euler without
-        churn runs under a clipping scaler (the same update)."""
+    def sample_steered(self, state, action, goal, sigmas, steer, candidates=None, bounds=None, kind=None, noise=None, n_steps=None,
+                       record=False, **params):
+        """A steered sampler loop as one enqueue.  ``kind`` None: DDIM (mdt_sample_ddim_steer) -- what ``sample_ddim(...,
+        steer=steer)`` runs, and with ``bounds`` -- an ``ActionBounds`` or a (lo, hi) pair, x clamped after every step -- what
+        gc_sampling.sample_euler without churn runs under a clipping scaler (the same update).  ``kind`` a sampler name
+        ('euler', 'heun', 'dpmpp_2m', ...: mdt_sample_steer): that sampler in ``sample_native``'s conventions -- ``noise`` None or
+        (n_noise, B*K, Ta, A) in the Python loop's draw order, ``n_steps`` dpm_fast's evaluation count (``sigmas`` then
+        [sigma_max, sigma_min]), ``params`` the sampler's keyword arguments, ``bounds`` applied where the kind's loop clips,
+        ``record=True`` returning (actions, rec) with the dict ``gc_sampling.replay_callback`` takes, 'denoised' holding D'."""
+        from ... import _lib
         im = self.inner_model
         if bounds is not None:
             pair = bounds.clip_bounds(action.device) if callable(getattr(bounds, "clip_bounds", None)) else bounds
             bounds = tuple(torch.as_tensor(b, dtype=torch.float32).to(action.device) for b in pair)
-        out, ctx = self._engine(state=state).sample_ddim_steer(state, action, im._goals(goal, False), sigmas, steer,
-                                                               candidates=candidate_count(candidates), bounds=bounds)
+        K = candidate_count(candidates)
+        if kind is None:
+            if noise is not None or n_steps is not None or record or params:
+                raise ValueError("sample_steered: noise, n_steps, record and sampler parameters need a sampler kind")
+            out, ctx = self._engine(state=state).sample_ddim_steer(state, action, im._goals(goal, False), sigmas, steer,
+                                                                   candidates=K, bounds=bounds)
+            im.latent_encoder_emb = ctx
+            return out
+        out, ctx, rec = self._engine(state=state).sample_steer(
+            _lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action, im._goals(goal, False), sigmas, steer, noise=noise,
+            n_steps=n_steps, candidates=K, bounds=bounds, record=record)
         im.latent_encoder_emb = ctx
-        return out
+        if not record:
+            return out
+        sigma, sigma_hat = _record_sigmas(kind, sigmas, n_steps, params)
+        return out, {"x": rec[:, 0], "denoised": rec[:, 1], "sigma": sigma, "sigma_hat": sigma_hat}
 
     @torch.no_grad()
     def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None, bounds=None, record=False, pin=None, candidates=None,

@@ -446,6 +446,33 @@ class HipEngine:
                   _ptr(p.out), _ptr(p.ctx), self._stream())
         return p.out, p.ctx
 
+    def sample_steer(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, steer,
+                     noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, candidates: int = 1, bounds=None,
+                     record: bool = False):
+        """mdt_sample_steer: ``sample_native``'s sampler (``kind`` an mdt_sampler_kind, ``params`` an _lib.SamplerParams, ``noise``
+        None or (n_noise, B*K, Ta, A) in the Python loop's draw order, ``n_steps`` None or dpm_fast's evaluation count) with every
+        evaluation's denoised value steered as ``sample_ddim_steer`` steers DDIM's, as one enqueue.  ``bounds``: None or (lo, hi),
+        fp32 (A,) device tensors, applied where the kind's loop clips; ``record``: the call also fills the (steps, 2, B*K, Ta, A)
+        record, [i][1] holding D'.  The schedule goes to the host (a device schedule is read back).  Returns (out, ctx, record or
+        None).  Not capture-safe: on a capturing stream the library refuses with MDT_ERR_STATE and enqueues nothing."""
+        self.train_prepare()
+        K = candidate_count(candidates)
+        host = sigmas.detach().to("cpu") if torch.is_tensor(sigmas) else sigmas
+        p = self._sampler_inputs(state, x_T, goal, host, n_steps, noise, candidates=K)
+        known, weight = steer.on(self.device, (p.N, self.Ta, self.A), K)
+        rec = None
+        if record:
+            steps = len(host) - 1 if n_steps is None else int(n_steps) // 3 + 1  # n_steps: dpm_fast's evaluation count
+            rec = torch.empty((steps, 2) + tuple(p.out.shape), device=self.device, dtype=torch.float32)
+        lo = hi = None
+        if bounds is not None:
+            lo, hi = (self._in(b, (self.A,)) for b in bounds)
+        self._keep = (p.sig, p.nz, known, weight, lo, hi)  # the kernels that read them are only enqueued
+        _lib.call(self.lib.mdt_sample_steer, self.handle, _ptr(p.tok), _ptr(p.tok2), _ptr(p.g), p.modality, _ptr(p.x), int(kind),
+                  C.byref(params), p.sig_arg, p.n, _ptr(p.nz), 0 if p.nz is None else p.nz.shape[0], p.B, K, _ptr(known),
+                  _ptr(weight), float(steer.beta), _ptr(lo), _ptr(hi), _ptr(rec), _ptr(p.out), _ptr(p.ctx), self._stream())
+        return p.out, p.ctx, rec
+
     def sample_native(self, kind: int, params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas,
                       noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cond_lambda: Optional[float] = None,
                       tree=None, bounds=None, record: bool = False, pin=None, candidates: int = 1):

@@ -15,7 +15,8 @@ clipped at ``beta`` (real-time chunking's clip).  A steer is a triple (``known``
 (B, Ta, A), ``weight`` in [0, 1], and it is an argument of the denoiser: every sampler uses D' wherever it used D.
 
 Hand it to a sampler as ``extra_args={"steer": steer}`` (gc_sampling.sample_*: sample_ddim, and sample_euler without churn, stay
-one native call, include/mdt_hip_train.h mdt_sample_ddim_steer; the others run their host loops), to
+one native call, include/mdt_hip_train.h mdt_sample_ddim_steer; the others run their host loops unless the steer was built with
+``plan_native=True``, which makes every other fixed-step sampler one native call too, mdt_sample_steer), to
 ``GCDenoiser.sample_ddim(..., steer=steer)`` or to ``GCDenoiser.forward(..., steer=steer)``.  A steer whose weight is zero
 everywhere is no steer: the call is then, bit for bit, the call without it.
 """
@@ -32,9 +33,11 @@ from .action_pin import ActionPin
 class ActionSteer:
     """``known``: broadcastable to (B, Ta, A), finite.  ``weight``: (Ta,), (B, Ta), (B, Ta, 1) or (B, Ta, A), every value finite
     and in [0, 1].  ``beta``: finite and > 0.  The tensors are checked here, in one reduction (one read-back where they live on
-    a device), which also tells whether any weight is non-zero (``active``)."""
+    a device), which also tells whether any weight is non-zero (``active``).  ``plan_native``: whether the fixed-step samplers
+    other than sample_ddim and churn-free sample_euler run this steer as one native call (mdt_sample_steer) where they can; the
+    default keeps the host loops they have always run under a steer.  It changes where the work runs, not the rule."""
 
-    def __init__(self, known, weight, beta: float = 5.0):
+    def __init__(self, known, weight, beta: float = 5.0, plan_native: bool = False):
         beta = float(beta)
         if not math.isfinite(beta) or not beta > 0:
             raise ValueError(f"ActionSteer: beta must be finite and > 0, got {beta}")
@@ -59,9 +62,10 @@ class ActionSteer:
             raise ValueError("ActionSteer: known must be finite")
         self.known, self.weight, self.beta = known, weight, beta
         self.active = bool(flags & 2)
+        self.plan_native = bool(plan_native)
 
     @classmethod
-    def overlap(cls, prev_chunk, executed: int, hard: int, soft: int = 0, beta: float = 5.0):
+    def overlap(cls, prev_chunk, executed: int, hard: int, soft: int = 0, beta: float = 5.0, plan_native: bool = False):
         """The receding-horizon steer, with ``ActionPin.overlap``'s ramp as the weight: 1 on the first ``hard`` tokens of the new
         chunk, 1 - (j - hard + 1) / (soft + 1) for j in [hard, hard + soft), 0 behind them and wherever ``prev_chunk`` has no value;
         ``known`` is ``prev_chunk`` moved up by ``executed`` tokens."""
@@ -69,7 +73,7 @@ class ActionSteer:
             pin = ActionPin.overlap(prev_chunk, executed, hard, soft)
         except ValueError as exc:
             raise ValueError(str(exc).replace("ActionPin", "ActionSteer")) from None
-        return cls(pin.known, pin.keep, beta)
+        return cls(pin.known, pin.keep, beta, plan_native)
 
     def on(self, device, shape, candidates: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
         """(known, weight) as contiguous fp32 tensors of ``shape`` = (B, Ta, A) on ``device``.  ``candidates`` = K > 1: the B chunks

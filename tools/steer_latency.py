@@ -1,15 +1,16 @@
-"""What the native steered call buys on the GPU, in one process: ms per host-synchronised 10-step steered DDIM call (MDT-V d = 384,
+"""What the native steered call buys on the GPU, in one process: ms per host-synchronised 10-step steered sampler call (MDT-V d = 384,
 synthetic 'rich' weights, the exponential schedule 80 .. 0.001, an overlap steer with 3 hard and 2 soft tokens, beta = 5) for K
 action chunks per observation,
 
-  host   : the host loop over GCDenoiser.forward(..., steer=) -- what gc_sampling.sample_ddim runs with a callback: the observations
-           encoded once per call, per step a taped decoder forward, the error in torch, the input-gradient-only backward, the
-           update in torch
-  native : gs.sample_ddim(extra_args={"steer": steer, "candidates": K}) -> mdt_sample_ddim_steer, one enqueue
+  host   : the host loop over GCDenoiser.forward(..., steer=) -- what gc_sampling.sample_<kind> runs with a callback: the
+           observations encoded once per call, per evaluation a taped decoder forward, the error in torch, the
+           input-gradient-only backward, the update in torch
+  native : gs.sample_<kind>(extra_args={"steer": steer, "candidates": K}) -> mdt_sample_ddim_steer (ddim) or mdt_sample_steer (every
+           other fixed-schedule kind: heun, dpmpp_2m, lms, ...), one enqueue
 
 for every (B, K) of --legs.
 
-    python tools/steer_latency.py [--calls 20] [--warmup 3] [--steps 10] [--legs 1x1,1x8,64x1] [--out FILE]
+    python tools/steer_latency.py [--kind ddim] [--calls 20] [--warmup 3] [--steps 10] [--legs 1x1,1x8,64x1] [--out FILE]
 Every call sits between two device events and is waited for (what a controller waits for); the figure is the median over --calls
 calls after --warmup untimed ones, the forms alternating per leg.  Each timed loop also sits between two mdt_op_clock_stamp
 records: the shader clock the chip sustained over exactly those calls is printed beside the time.  Prints one line per leg, the
@@ -26,6 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", default="ddim", help="the gc_sampling function name without 'sample_' (fixed-schedule kinds)")
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--steps", type=int, default=10)
@@ -51,13 +53,15 @@ def main():
         t = {k: torch.from_numpy(v).cuda() for k, v in synthetic.sampler_inputs(B, cfg, seed=6).items()}
         prev = torch.from_numpy(synthetic.loss_inputs(B, cfg, 7)["actions"]).cuda()
         x = 80.0 * torch.from_numpy(synthetic.normal("steer_latency", (B * K,) + tuple(prev.shape[1:]), 8)).cuda()
-        return {"state_images": t["state_images"], "modality": "lang"}, x, t["goal"], ActionSteer.overlap(prev, 2, 3, 2)
+        return {"state_images": t["state_images"], "modality": "lang"}, x, t["goal"], ActionSteer.overlap(prev, 2, 3, 2, plan_native=True)
+
+    sample = getattr(gs, "sample_" + args.kind)
 
     def host(state, x, goal, steer, K):
-        return gs.sample_ddim(model, state, x, goal, sigmas, extra_args={"steer": steer, "candidates": K}, callback=lambda d: None)
+        return sample(model, state, x, goal, sigmas, extra_args={"steer": steer, "candidates": K}, callback=lambda d: None)
 
     def native(state, x, goal, steer, K):
-        return gs.sample_ddim(model, state, x, goal, sigmas, extra_args={"steer": steer, "candidates": K})
+        return sample(model, state, x, goal, sigmas, extra_args={"steer": steer, "candidates": K})
 
     def mhz(stamps):
         """Median over the XCDs of the shader clock between the two records (bench.py sustained_mhz)."""
@@ -93,7 +97,7 @@ def main():
         h_ms, h_min, h_clk, h_out = timed(host, a)
         n_ms, n_min, n_clk, n_out = timed(native, a)
         diff = float((h_out - n_out).abs().max())
-        rows.append(dict(B=B, K=K, steps=args.steps, host_ms=round(h_ms, 3), host_min_ms=round(h_min, 3), host_mhz=h_clk,
+        rows.append(dict(kind=args.kind, B=B, K=K, steps=args.steps, host_ms=round(h_ms, 3), host_min_ms=round(h_min, 3), host_mhz=h_clk,
                          native_ms=round(n_ms, 3), native_min_ms=round(n_min, 3), native_mhz=n_clk,
                          native_ms_per_step=round(n_ms / args.steps, 3), speedup=round(h_ms / n_ms, 2), max_diff=round(diff, 6)))
         print(f"({B:3d}, {K:2d}) host {h_ms:8.3f} ms ({h_clk} MHz)   native {n_ms:8.3f} ms ({n_clk} MHz, {n_ms / args.steps:.3f} ms / step)"
@@ -101,7 +105,7 @@ def main():
     table = ["| B | K | host loop ms | native ms | native ms / step | speed-up |", "|---|---|---|---|---|---|"]
     table += [f"| {r['B']} | {r['K']} | {r['host_ms']:.2f} | {r['native_ms']:.2f} | {r['native_ms_per_step']:.3f} | {r['speedup']:.2f}x |"
               for r in rows]
-    line = json.dumps({"calls": args.calls, "warmup": args.warmup, "rows": rows})
+    line = json.dumps({"kind": args.kind, "calls": args.calls, "warmup": args.warmup, "rows": rows})
     print("\n".join(table))
     print(line)
     if args.out:
