@@ -346,14 +346,7 @@ extern "C" mdt_status mdt_log_likelihood(mdt_model* m, const float* tokens, cons
                                          int64_t batch, int32_t candidates, const mdt_loglik_params* params, float* ll,
                                          float* latent, float* delta, mdt_loglik_info* info, void* stream) {
     const char* fn = "mdt_log_likelihood";
-    if (!m) return fail(MDT_ERR_INVALID_ARG, "%s: null handle", fn);
-    if (!tokens) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens", fn);
-    if (!goal) return fail(MDT_ERR_INVALID_ARG, "%s: null goal", fn);
-    if (!x) return fail(MDT_ERR_INVALID_ARG, "%s: null x", fn);
-    if (!v) return fail(MDT_ERR_INVALID_ARG, "%s: null v", fn);
-    if (!ll) return fail(MDT_ERR_INVALID_ARG, "%s: null ll", fn);
-    if (batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: batch is %lld, must be >= 1", fn, (long long)batch);
-    if (candidates < 1) return fail(MDT_ERR_INVALID_ARG, "%s: candidates is %d, must be >= 1", fn, candidates);
+    MDT_TRY(mdt_ll_check_head(fn, m, tokens, goal, {{x, "x"}, {v, "v"}, {ll, "ll"}}, batch, candidates));
     mdt_loglik_params p = {(int32_t)sizeof(mdt_loglik_params), 1, 1e-4, 1e-4, 10000, 0};
     if (params) {
         if (params->size != (int32_t)sizeof(mdt_loglik_params))
@@ -369,21 +362,11 @@ extern "C" mdt_status mdt_log_likelihood(mdt_model* m, const float* tokens, cons
     if (!std::isfinite(p.rtol) || !(p.rtol > 0)) return fail(MDT_ERR_INVALID_ARG, "%s: params.rtol is %g, must be finite and > 0", fn, p.rtol);
     if (!std::isfinite(p.atol) || !(p.atol > 0)) return fail(MDT_ERR_INVALID_ARG, "%s: params.atol is %g, must be finite and > 0", fn, p.atol);
     if (p.max_steps < 1) return fail(MDT_ERR_INVALID_ARG, "%s: params.max_steps is %d, must be >= 1", fn, p.max_steps);
-    if (m->cfg.arch == MDT_ARCH_MDT && !tokens2) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: MDT needs the gripper tokens", fn);
-    MDT_TRY(mdt_ll_check(m, fn));
-    if (m->p_row >= 0 && !tokens2)
-        return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: this handle was created with use_proprio and needs state_obs", fn);
-    const int64_t R = batch * candidates, limit = ((int64_t)1 << 24) / std::max(m->Te, m->Ta);  // the decoder's row counts (int)
-    if (batch > limit / candidates)
-        return fail(MDT_ERR_INVALID_ARG, "%s: batch * candidates = %lld * %d is more than the decoder's %lld samples", fn,
-                    (long long)batch, candidates, (long long)limit);
     hipStream_t s = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-        return fail(MDT_ERR_STATE, "%s: the call synchronises every step and cannot be captured", fn);
+    MDT_TRY(mdt_ll_check_tail(m, fn, tokens2, batch, candidates, s, "the call synchronises every step and"));
 
     Call c;
+    const int64_t R = batch * candidates;
     c.m = m; c.s = s; c.tokens = tokens; c.tokens2 = tokens2; c.goal = goal; c.v = v; c.modality = modality;
     c.P = p.probes; c.per = m->Ta * m->A; c.R = R; c.N = R * c.per;
     MDT_TRY(mdt_grow_carve(m->ll_ws, m->ll_rows, m->ll_probes, R, (int64_t)p.probes,
@@ -391,16 +374,12 @@ extern "C" mdt_status mdt_log_likelihood(mdt_model* m, const float* tokens, cons
     if (!m->ll_host) HIP_TRY(hipHostMalloc(&m->ll_host, sizeof(LLHost), hipHostMallocDefault));
     c.host = (LLHost*)m->ll_host;
     mdt_loglik_info inf = {0, 0, 0, 0};
-    mdt_status st = mdt_ll_open(m, batch, candidates, s, &c.run);
-    if (st == MDT_OK) st = integrate(c, x, (double)sigma_min, (double)sigma_max, p, &inf);
-    if (st == MDT_OK) {
+    const mdt_status st = mdt_ll_scoped(m, batch, candidates, s, &c.run, [&]() -> mdt_status {
+        MDT_TRY(integrate(c, x, (double)sigma_min, (double)sigma_max, p, &inf));
         hipError_t e = mdt_launch_lds<k_ll_finish>(dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, (const float*)c.b.x,
                                                    (const float*)c.b.d, sigma_max, c.per, R, ll, latent, delta);
-        if (e != hipSuccess) st = fail(MDT_ERR_HIP, "%s: finish launch failed: %s", fn, hipGetErrorString(e));
-    }
-    // on every path: the tapes released, the scratch handed back (a failure above keeps its own message)
-    const mdt_status closed = mdt_ll_close(m, c.run, s);
-    if (st == MDT_OK) st = closed;
+        return e == hipSuccess ? MDT_OK : fail(MDT_ERR_HIP, "%s: finish launch failed: %s", fn, hipGetErrorString(e));
+    });
     if (st == MDT_OK && info) *info = inf;
     return st;
 }

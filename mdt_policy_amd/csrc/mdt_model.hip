@@ -111,6 +111,7 @@ hipError_t mdt_dev_free(void* p) {
 extern "C" const char* mdt_version(void) { return "mdt_hip 0.1 (gfx950, v_mfma_f32_16x16x4_f32)"; }
 
 #include "mdt_model_types.h"
+#include "mdt_loglik.h"  // mdt_refuse_capture
 
 // workspace view of a contiguous slice of samples [b0, b0 + nb) for the decoder (Ta rows per sample)
 struct View {
@@ -1693,10 +1694,7 @@ static mdt_status sample_dpm_adaptive_impl(mdt_model* m, const SamplerRequest& a
         return fail(MDT_ERR_INVALID_ARG, "mdt_sample_dpm_adaptive: pointers must be 16-byte aligned");
     if (m->A > MDT_ACTION_DIM_MAX)
         return fail(MDT_ERR_UNSUPPORTED, "mdt_sample_dpm_adaptive: action_dim must be <= %d", MDT_ACTION_DIM_MAX);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing((hipStream_t)a.stream, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-        return fail(MDT_ERR_STATE, "mdt_sample_dpm_adaptive: the call synchronises every step and cannot be captured");
+    MDT_TRY(mdt_refuse_capture((hipStream_t)a.stream, "mdt_sample_dpm_adaptive", "the call synchronises every step and"));
     SamplerCall c;
     MDT_TRY(sampler_open(m, a, gd, &c));
     hipStream_t s = c.s;

@@ -6,15 +6,17 @@
 // (pseudo-inverse guidance as real-time chunking clips it; e = weight . (known - D) is a constant of the step).  The denoiser and
 // its vector-Jacobian product are the training path's, shared with mdt_log_likelihood (mdt_loglik.h): the encoder and the cross
 // K|V once per call on the B observations (once per step where sigma is a context token), per step one tape-keeping decoder
-// forward on the R = B * K chunks and one input-gradient-only backward over that tape.  This file holds the two kernels that
-// stand where mdt_ll_vjp's seed and finish launches stand -- the seed forms D and e on the way, the finish the steered DDIM
-// update -- and the host loop.  mdt_sample_steer runs a sampler plan the same way: per evaluation of the plan one forward on the
-// evaluation's input Y, the same seed at the evaluation's own sigma, and k_steer_plan as the finish -- D' and then the plan's
-// per-element update (head_plan_elem, the one the unsteered plan heads call) on X, Y, D', d = (Y - D') / sigma, H0..H3, N0, N1.
+// forward on the R = B * K chunks and one input-gradient-only backward over that tape.  This file holds the kernels that stand
+// where mdt_ll_vjp's seed and finish launches stand -- the seed forms D and e on the way, the finish the steered update -- and one
+// host loop, `evaluations`, that both entries run: per evaluation the context where sigma is a token, the forward, the backward
+// between the seed and the entry's finish.  An entry brings its first launch (the rows' sigma), a setter for what changes per
+// evaluation, and its finish: DDIM k_steer_step, with the coefficients formed on the host; mdt_sample_steer, per evaluation of a
+// sampler plan on the evaluation's input Y at its own sigma, k_steer_plan -- D' and then the plan's per-element update
+// (head_plan_elem, the one the unsteered plan heads call) on X, Y, D', d = (Y - D') / sigma, H0..H3, N0, N1.  Both entries stand
+// in mdt_loglik.h's frame: head checks, their own, tail checks, then mdt_ll_scoped around the loop.
 // No kernel here uses atomics, LDS or scratch; every element is written by one thread.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 
 #include "mdt_hip_train.h"
@@ -33,6 +35,7 @@ namespace {
 // rarely one of 256: the bound is per element, and no lane cooperates with another, so a partly filled wave just idles its tail.
 constexpr int STEER_THREADS = 256;
 constexpr int STEER_MAX_BLOCKS = 1024;
+constexpr const char* NOT_CAPTURE_SAFE = "the tape path is not capture-safe and the call";  // ... cannot be captured
 
 unsigned steer_grid(int64_t n) {
     const int64_t g = (n + STEER_THREADS - 1) / STEER_THREADS;
@@ -220,12 +223,29 @@ mdt_status fill_sigma(Call& c, float sigma) {
     return MDT_OK;
 }
 
-mdt_status run(Call& c, const float* x_T, const float* sig, int n, float beta, float* out, float* ctx_out) {
+// The evaluations of a steered call, after its first launch has filled the rows' sigma.  `set(i)` fills what evaluation i's seed
+// and finish launches read from `c` and returns the forward's input; the context is hoisted unless sigma is one of its tokens.
+template <class Set>
+mdt_status evaluations(Call& c, int n, Set set, mdt_ll_launch finish, float* ctx_out) {
     mdt_model* m = c.m;
-    const float sd = m->cfg.sigma_data;
-    MDT_TRY(fill_sigma(c, sig[0]));
     if (m->cond != COND_TOKEN) MDT_TRY(mdt_ll_context(m, c.run, c.tokens, c.tokens2, c.goal, c.modality, nullptr, c.s));
     for (int i = 0; i < n; ++i) {
+        const float* x = set(i);
+        if (m->cond == COND_TOKEN)  // sigma is a context token: the context is this evaluation's, still on the B observations
+            MDT_TRY(mdt_ll_context(m, c.run, c.tokens, c.tokens2, c.goal, c.modality, c.b.sig, c.s));
+        MDT_TRY(mdt_ll_forward(m, c.run, x, c.b.sig, c.s));
+        MDT_TRY(mdt_ll_backward(m, c.run, steer_seed, finish, &c, c.s));
+    }
+    if (ctx_out)
+        HIP_TRY(hipMemcpyAsync(ctx_out, mdt_ll_ctx(m, c.run), (size_t)c.run.B * m->Te * m->D * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    return MDT_OK;
+}
+
+// DDIM's steps: forward on x, backward between k_steer_seed and k_steer_step
+mdt_status run(Call& c, const float* x_T, const float* sig, int n, float beta, float* out, float* ctx_out) {
+    const float sd = c.m->cfg.sigma_data;
+    MDT_TRY(fill_sigma(c, sig[0]));
+    return evaluations(c, n, [&](int i) {
         // the DDIM coefficients as the native sampler forms them (k_sample_prep): t = -ln sigma, exp(-t') / exp(-t), -expm1(-(t' - t))
         const float t = -logf(sig[i]), tn = -logf(sig[i + 1]);
         c.sg = sig[i];
@@ -235,54 +255,49 @@ mdt_status run(Call& c, const float* x_T, const float* sig, int n, float beta, f
         c.sigma_next = sig[i + 1];
         c.x_in = i == 0 ? x_T : c.b.x;       // x_T is only read
         c.x_out = i == n - 1 ? out : c.b.x;
-        if (m->cond == COND_TOKEN)  // sigma is a context token: the context is this step's, still on the B observations
-            MDT_TRY(mdt_ll_context(m, c.run, c.tokens, c.tokens2, c.goal, c.modality, c.b.sig, c.s));
-        MDT_TRY(mdt_ll_forward(m, c.run, c.x_in, c.b.sig, c.s));
-        MDT_TRY(mdt_ll_backward(m, c.run, steer_seed, steer_step, &c, c.s));
-    }
-    if (ctx_out)
-        HIP_TRY(hipMemcpyAsync(ctx_out, mdt_ll_ctx(m, c.run), (size_t)c.run.B * m->Te * m->D * sizeof(float), hipMemcpyDeviceToDevice, c.s));
-    return MDT_OK;
+        return c.x_in;
+    }, steer_step, ctx_out);
 }
 
-// the plan's evaluations: (the context where sigma is a token,) forward on Y, backward between k_steer_seed and k_steer_plan
+// the plan's evaluations: forward on Y, backward between k_steer_seed and k_steer_plan
 mdt_status run_plan(Call& c, int kind, int n_steps, const mdt_sampler_plan_t& P, const float* x_T, const float* noise, int n_noise,
                     float beta, float* record, float* out, float* ctx_out) {
-    mdt_model* m = c.m;
-    const float sd = m->cfg.sigma_data;
+    const float sd = c.m->cfg.sigma_data;
     const int E = P.n_evals;
     const float* y0n = (noise && P.y0_noise >= 0 && P.y0_noise < n_noise) ? noise + (int64_t)P.y0_noise * c.N : nullptr;
     LAUNCH(mdt_launch_lds<k_steer_first>(dim3(steer_grid(c.N + c.R)), dim3(STEER_THREADS), 0, c.s, x_T, y0n, P.y0_cn, P.e[0].sigma,
                                          c.N, c.R, c.b.x, c.b.y, c.b.hist, c.b.sig));
-    if (m->cond != COND_TOKEN) MDT_TRY(mdt_ll_context(m, c.run, c.tokens, c.tokens2, c.goal, c.modality, nullptr, c.s));
-    for (int e = 0; e < E; ++e) {
+    SteerPlanArgs& a = c.pa;  // the call's buffers and sizes once, the evaluation's own fields in the setter
+    a.small = nullptr; a.e = c.b.e; a.D = c.b.D;
+    a.Y = c.b.y; a.X = c.b.x;
+    a.hist = c.b.hist;
+    a.noise = noise;
+    a.sig_rows = c.b.sig;
+    a.N = c.N; a.R = c.R;
+    a.sd = sd;
+    a.n_noise = noise ? n_noise : 0;
+    a.A = c.m->A;
+    return evaluations(c, E, [&](int e) {
         const bool last = e == E - 1, clips = c.lo && mdt_plan_loop_clips(kind, last);
         const float sg = P.e[e].sigma;
         c.sg = sg;
-        SteerPlanArgs& a = c.pa;
         a.ev = P.e[e];
-        a.small = nullptr; a.e = c.b.e; a.D = c.b.D;
-        a.Y = c.b.y; a.X = c.b.x;
         a.x_out = last ? out : c.b.x;
         a.y_out = last ? nullptr : c.b.y;
-        a.hist = c.b.hist;
-        a.noise = noise;
         a.lo = clips ? c.lo : nullptr; a.hi = clips ? c.hi : nullptr;
         a.rec = record ? record + (int64_t)mdt_plan_step_of(kind, n_steps, e) * 2 * c.N : nullptr;
-        a.sig_rows = c.b.sig;
-        a.N = c.N; a.R = c.R;
-        a.sd = sd;
         a.scale = fminf(beta, 1.f + (sg * sg) / (sd * sd));
-        a.n_noise = noise ? n_noise : 0;
-        a.A = m->A;
-        if (m->cond == COND_TOKEN)  // sigma is a context token: the context is this evaluation's, still on the B observations
-            MDT_TRY(mdt_ll_context(m, c.run, c.tokens, c.tokens2, c.goal, c.modality, c.b.sig, c.s));
-        MDT_TRY(mdt_ll_forward(m, c.run, c.b.y, c.b.sig, c.s));
-        MDT_TRY(mdt_ll_backward(m, c.run, steer_seed, steer_plan, &c, c.s));
-    }
-    if (ctx_out)
-        HIP_TRY(hipMemcpyAsync(ctx_out, mdt_ll_ctx(m, c.run), (size_t)c.run.B * m->Te * m->D * sizeof(float), hipMemcpyDeviceToDevice, c.s));
-    return MDT_OK;
+        return (const float*)c.b.y;
+    }, steer_plan, ctx_out);
+}
+
+// the call's arguments and, over the handle's steer block grown to R rows, its buffers
+mdt_status steer_call(Call& c, mdt_model* m, hipStream_t s, const float* tokens, const float* tokens2, const float* goal, int modality,
+                      int64_t R, const float* known, const float* weight, const float* lo, const float* hi) {
+    c.m = m; c.s = s; c.tokens = tokens; c.tokens2 = tokens2; c.goal = goal; c.known = known; c.weight = weight; c.lo = lo; c.hi = hi;
+    c.modality = modality; c.R = R; c.N = R * m->Ta * m->A;
+    const int per = m->Ta * m->A;
+    return mdt_grow_carve(m->st_ws, m->st_rows, R, [&](Bump& b, int64_t rows) { carve(b, rows, per, b.base ? &c.b : nullptr); });
 }
 
 }  // namespace
@@ -292,16 +307,8 @@ extern "C" mdt_status mdt_sample_ddim_steer(mdt_model* m, const float* tokens, c
                                             int64_t batch, int32_t candidates, const float* known, const float* weight, float beta,
                                             const float* lo, const float* hi, float* out, float* ctx_out, void* stream) {
     const char* fn = "mdt_sample_ddim_steer";
-    if (!m) return fail(MDT_ERR_INVALID_ARG, "%s: null handle", fn);
-    if (!tokens) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens", fn);
-    if (!goal) return fail(MDT_ERR_INVALID_ARG, "%s: null goal", fn);
-    if (!x_T) return fail(MDT_ERR_INVALID_ARG, "%s: null x_T", fn);
-    if (!sigmas) return fail(MDT_ERR_INVALID_ARG, "%s: null sigmas", fn);
-    if (!known) return fail(MDT_ERR_INVALID_ARG, "%s: null known", fn);
-    if (!weight) return fail(MDT_ERR_INVALID_ARG, "%s: null weight", fn);
-    if (!out) return fail(MDT_ERR_INVALID_ARG, "%s: null out", fn);
-    if (batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: batch is %lld, must be >= 1", fn, (long long)batch);
-    if (candidates < 1) return fail(MDT_ERR_INVALID_ARG, "%s: candidates is %d, must be >= 1", fn, candidates);
+    MDT_TRY(mdt_ll_check_head(fn, m, tokens, goal, {{x_T, "x_T"}, {sigmas, "sigmas"}, {known, "known"}, {weight, "weight"}, {out, "out"}},
+                              batch, candidates));
     if (n_steps < 1 || n_steps > MDT_SAMPLER_MAX_STEPS)
         return fail(MDT_ERR_INVALID_ARG, "%s: n_steps is %d, must be in [1, %d]", fn, n_steps, (int)MDT_SAMPLER_MAX_STEPS);
     if (!std::isfinite(beta) || !(beta > 0.f)) return fail(MDT_ERR_INVALID_ARG, "%s: beta is %g, must be finite and > 0", fn, beta);
@@ -312,30 +319,12 @@ extern "C" mdt_status mdt_sample_ddim_steer(mdt_model* m, const float* tokens, c
         return fail(MDT_ERR_INVALID_ARG, "%s: sigmas[%d] is %g: the schedule must be finite and > 0, then end in 0", fn, n_steps,
                     sigmas[n_steps]);
     if ((!lo) != (!hi)) return fail(MDT_ERR_INVALID_ARG, "%s: null %s: the bounds lo and hi come together", fn, lo ? "hi" : "lo");
-    if (m->cfg.arch == MDT_ARCH_MDT && !tokens2) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: MDT needs the gripper tokens", fn);
-    MDT_TRY(mdt_ll_check(m, fn));
-    if (m->p_row >= 0 && !tokens2)
-        return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: this handle was created with use_proprio and needs state_obs", fn);
-    const int64_t R = batch * candidates, limit = ((int64_t)1 << 24) / std::max(m->Te, m->Ta);  // the decoder's row counts (int)
-    if (batch > limit / candidates)
-        return fail(MDT_ERR_INVALID_ARG, "%s: batch * candidates = %lld * %d is more than the decoder's %lld samples", fn,
-                    (long long)batch, candidates, (long long)limit);
     hipStream_t s = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-        return fail(MDT_ERR_STATE, "%s: the tape path is not capture-safe and the call cannot be captured", fn);
+    MDT_TRY(mdt_ll_check_tail(m, fn, tokens2, batch, candidates, s, NOT_CAPTURE_SAFE));
 
     Call c;
-    c.m = m; c.s = s; c.tokens = tokens; c.tokens2 = tokens2; c.goal = goal; c.known = known; c.weight = weight; c.lo = lo; c.hi = hi;
-    c.modality = modality; c.R = R; c.N = R * m->Ta * m->A;
-    const int per = m->Ta * m->A;
-    MDT_TRY(mdt_grow_carve(m->st_ws, m->st_rows, R, [&](Bump& b, int64_t rows) { carve(b, rows, per, b.base ? &c.b : nullptr); }));
-    mdt_status st = mdt_ll_open(m, batch, candidates, s, &c.run);
-    if (st == MDT_OK) st = run(c, x_T, sigmas, n_steps, beta, out, ctx_out);
-    // on every path: the tapes released, the scratch handed back (a failure above keeps its own message)
-    const mdt_status closed = mdt_ll_close(m, c.run, s);
-    return st != MDT_OK ? st : closed;
+    MDT_TRY(steer_call(c, m, s, tokens, tokens2, goal, modality, batch * candidates, known, weight, lo, hi));
+    return mdt_ll_scoped(m, batch, candidates, s, &c.run, [&] { return run(c, x_T, sigmas, n_steps, beta, out, ctx_out); });
 }
 
 extern "C" mdt_status mdt_sample_steer(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
@@ -344,16 +333,9 @@ extern "C" mdt_status mdt_sample_steer(mdt_model* m, const float* tokens, const 
                                        const float* known, const float* weight, float beta, const float* lo, const float* hi,
                                        float* record, float* out, float* ctx_out, void* stream) {
     const char* fn = "mdt_sample_steer";
-    if (!m) return fail(MDT_ERR_INVALID_ARG, "%s: null handle", fn);
-    if (!tokens) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens", fn);
-    if (!goal) return fail(MDT_ERR_INVALID_ARG, "%s: null goal", fn);
-    if (!x_T) return fail(MDT_ERR_INVALID_ARG, "%s: null x_T", fn);
-    if (!sigmas_host) return fail(MDT_ERR_INVALID_ARG, "%s: null sigmas_host", fn);
-    if (!known) return fail(MDT_ERR_INVALID_ARG, "%s: null known", fn);
-    if (!weight) return fail(MDT_ERR_INVALID_ARG, "%s: null weight", fn);
-    if (!out) return fail(MDT_ERR_INVALID_ARG, "%s: null out", fn);
-    if (batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: batch is %lld, must be >= 1", fn, (long long)batch);
-    if (candidates < 1) return fail(MDT_ERR_INVALID_ARG, "%s: candidates is %d, must be >= 1", fn, candidates);
+    MDT_TRY(mdt_ll_check_head(fn, m, tokens, goal,
+                              {{x_T, "x_T"}, {sigmas_host, "sigmas_host"}, {known, "known"}, {weight, "weight"}, {out, "out"}}, batch,
+                              candidates));
     if (!std::isfinite(beta) || !(beta > 0.f)) return fail(MDT_ERR_INVALID_ARG, "%s: beta is %g, must be finite and > 0", fn, beta);
     const mdt_sampler_params p = params ? *params : mdt_sampler_defaults();
     int E = 0, rows = 0;
@@ -390,28 +372,11 @@ extern "C" mdt_status mdt_sample_steer(mdt_model* m, const float* tokens, const 
         if (P.e[e].step != mdt_plan_step_of(kind, n_steps, e))
             return fail(MDT_ERR_STATE, "%s: evaluation %d is in step %d of the plan, %d by its structure", fn, e, P.e[e].step,
                         mdt_plan_step_of(kind, n_steps, e));
-    if (m->cfg.arch == MDT_ARCH_MDT && !tokens2) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: MDT needs the gripper tokens", fn);
-    MDT_TRY(mdt_ll_check(m, fn));
-    if (m->p_row >= 0 && !tokens2)
-        return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: this handle was created with use_proprio and needs state_obs", fn);
-    const int64_t R = batch * candidates, limit = ((int64_t)1 << 24) / std::max(m->Te, m->Ta);  // the decoder's row counts (int)
-    if (batch > limit / candidates)
-        return fail(MDT_ERR_INVALID_ARG, "%s: batch * candidates = %lld * %d is more than the decoder's %lld samples", fn,
-                    (long long)batch, candidates, (long long)limit);
     hipStream_t s = (hipStream_t)stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(s, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-        return fail(MDT_ERR_STATE, "%s: the tape path is not capture-safe and the call cannot be captured", fn);
+    MDT_TRY(mdt_ll_check_tail(m, fn, tokens2, batch, candidates, s, NOT_CAPTURE_SAFE));
 
     Call c;
-    c.m = m; c.s = s; c.tokens = tokens; c.tokens2 = tokens2; c.goal = goal; c.known = known; c.weight = weight; c.lo = lo; c.hi = hi;
-    c.modality = modality; c.R = R; c.N = R * m->Ta * m->A;
-    const int per = m->Ta * m->A;
-    MDT_TRY(mdt_grow_carve(m->st_ws, m->st_rows, R, [&](Bump& b, int64_t rows_) { carve(b, rows_, per, b.base ? &c.b : nullptr); }));
-    mdt_status st = mdt_ll_open(m, batch, candidates, s, &c.run);
-    if (st == MDT_OK) st = run_plan(c, kind, n_steps, P, x_T, noise, n_noise, beta, record, out, ctx_out);
-    // on every path: the tapes released, the scratch handed back (a failure above keeps its own message)
-    const mdt_status closed = mdt_ll_close(m, c.run, s);
-    return st != MDT_OK ? st : closed;
+    MDT_TRY(steer_call(c, m, s, tokens, tokens2, goal, modality, batch * candidates, known, weight, lo, hi));
+    return mdt_ll_scoped(m, batch, candidates, s, &c.run,
+                         [&] { return run_plan(c, kind, n_steps, P, x_T, noise, n_noise, beta, record, out, ctx_out); });
 }

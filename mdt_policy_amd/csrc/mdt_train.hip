@@ -1339,10 +1339,11 @@ extern "C" mdt_status mdt_denoise_vjp(mdt_model* m, const float* tokens, const f
 }
 
 // ------------------------------------------------------------------------------------------------
-// mdt_log_likelihood's and mdt_sample_ddim_steer's pieces of this path (mdt_loglik.h; the integrator and its entry point are in
-// mdt_loglik.hip, the steered DDIM loop in mdt_steer.hip): the encoder
+// The tape-path calls' pieces of this path (mdt_loglik.h): mdt_log_likelihood (the integrator and its entry point are in
+// mdt_loglik.hip), mdt_sample_ddim_steer and mdt_sample_steer (the steered evaluation loop and both entry points are in
+// mdt_steer.hip; the frame all three entries stand in is inline in mdt_loglik.h): the encoder
 // and the stacked cross K|V product on the B observations, the decoder forward on the R = B*K chunks against K|V rows staged
-// once, and mdt_denoise_vjp's backward as often as there are probes over that one tape -- it reads the tape and writes only the
+// once, and mdt_denoise_vjp's backward as often as the caller asks over that one tape -- it reads the tape and writes only the
 // handle's backward scratch.
 // ------------------------------------------------------------------------------------------------
 mdt_status mdt_ll_check(mdt_model* m, const char* fn) {
@@ -1386,7 +1387,7 @@ mdt_status mdt_ll_forward(mdt_model* m, const mdt_ll_run& r, const float* x, con
 }
 
 // the input-gradient-only backward over the decoder tape, between the caller's two elementwise launches: mdt_ll_vjp's (below:
-// k_denoise_seed / _finish) or mdt_sample_ddim_steer's (mdt_steer.hip: the seed forms the constraint error, the finish the update)
+// k_denoise_seed / _finish) or the steered samplers' (mdt_steer.hip: the seed forms the constraint error, the finish the update)
 mdt_status mdt_ll_backward(mdt_model* m, const mdt_ll_run& r, mdt_ll_launch seed, mdt_ll_launch finish, void* arg, hipStream_t s) {
     Tape& t = m->train->tapes[r.dec];
     mdt_train_state* ts = m->train;

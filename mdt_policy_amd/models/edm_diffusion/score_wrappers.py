@@ -69,6 +69,24 @@ def _record_sigmas(kind, sigmas, n_steps, params):
     return sigma, sigma.clone()
 
 
+def _record_dict(rec, kind, sigmas, n_steps, params):
+    """A native call's (steps, 2, ...) record tensor as the dict a ``callback`` of the loop sees, step by step."""
+    sigma, sigma_hat = _record_sigmas(kind, sigmas, n_steps, params)
+    return {"x": rec[:, 0], "denoised": rec[:, 1], "sigma": sigma, "sigma_hat": sigma_hat}
+
+
+def _bounds_pair(bounds, device):
+    """An ``ActionBounds`` or a (lo, hi) pair as two fp32 tensors on ``device``; None as it came."""
+    pair = bounds.clip_bounds(device) if callable(getattr(bounds, "clip_bounds", None)) else bounds
+    return None if bounds is None else tuple(torch.as_tensor(b, dtype=torch.float32).to(device) for b in pair)
+
+
+def _pin_rows(pin, action, K):
+    """An ``ActionPin`` as its (known, keep) pair over the chunks of ``action``; a pair, or None, as it came."""
+    Ta, A = action.shape[-2:]
+    return pin.on(action.device, (action.numel() // (Ta * A), Ta, A), K) if callable(getattr(pin, "on", None)) else pin
+
+
 class GCDenoiser(nn.Module):
     """Karras et al. (2022) preconditioner around the MI355X-native score network."""
 
@@ -392,11 +410,8 @@ class GCDenoiser(nn.Module):
         from ... import _lib
         im = self.inner_model
         K = candidate_count(candidates)
-        if pin is not None and callable(getattr(pin, "on", None)):
-            pin = pin.on(action.device, (action.numel() // (action.shape[-2] * action.shape[-1]),) + tuple(action.shape[-2:]), K)
-        if bounds is not None:
-            pair = bounds.clip_bounds(action.device) if callable(getattr(bounds, "clip_bounds", None)) else bounds
-            bounds = tuple(torch.as_tensor(b, dtype=torch.float32).to(action.device) for b in pair)
+        pin = _pin_rows(pin, action, K)
+        bounds = _bounds_pair(bounds, action.device)
         if tree is not None:
             if kind != "dpmpp_sde" or noise is not None or n_steps is not None:
                 raise ValueError("sample_native: tree noise is for 'dpmpp_sde' and takes no noise rows")
@@ -405,10 +420,7 @@ class GCDenoiser(nn.Module):
             _lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action, im._goals(goal, False), sigmas, noise,
             n_steps=n_steps, cond_lambda=cond_lambda, tree=tree, bounds=bounds, record=record, pin=pin, candidates=K)
         im.latent_encoder_emb = ctx
-        if not record:
-            return out
-        sigma, sigma_hat = _record_sigmas(kind, sigmas, n_steps, params)
-        return out, {"x": rec[:, 0], "denoised": rec[:, 1], "sigma": sigma, "sigma_hat": sigma_hat}
+        return (out, _record_dict(rec, kind, sigmas, n_steps, params)) if record else out
 
     @torch.no_grad()
     def sample_dpm_adaptive_native(self, state, action, goal, sigma_min, sigma_max, cond_lambda=None, **params):
@@ -435,25 +447,19 @@ class GCDenoiser(nn.Module):
         ``record=True`` returning (actions, rec) with the dict ``gc_sampling.replay_callback`` takes, 'denoised' holding D'."""
         from ... import _lib
         im = self.inner_model
-        if bounds is not None:
-            pair = bounds.clip_bounds(action.device) if callable(getattr(bounds, "clip_bounds", None)) else bounds
-            bounds = tuple(torch.as_tensor(b, dtype=torch.float32).to(action.device) for b in pair)
+        bounds = _bounds_pair(bounds, action.device)
         K = candidate_count(candidates)
         if kind is None:
             if noise is not None or n_steps is not None or record or params:
                 raise ValueError("sample_steered: noise, n_steps, record and sampler parameters need a sampler kind")
             out, ctx = self._engine(state=state).sample_ddim_steer(state, action, im._goals(goal, False), sigmas, steer,
                                                                    candidates=K, bounds=bounds)
-            im.latent_encoder_emb = ctx
-            return out
-        out, ctx, rec = self._engine(state=state).sample_steer(
-            _lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action, im._goals(goal, False), sigmas, steer, noise=noise,
-            n_steps=n_steps, candidates=K, bounds=bounds, record=record)
+        else:
+            out, ctx, rec = self._engine(state=state).sample_steer(
+                _lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action, im._goals(goal, False), sigmas, steer,
+                noise=noise, n_steps=n_steps, candidates=K, bounds=bounds, record=record)
         im.latent_encoder_emb = ctx
-        if not record:
-            return out
-        sigma, sigma_hat = _record_sigmas(kind, sigmas, n_steps, params)
-        return out, {"x": rec[:, 0], "denoised": rec[:, 1], "sigma": sigma, "sigma_hat": sigma_hat}
+        return (out, _record_dict(rec, kind, sigmas, n_steps, params)) if record else out
 
     @torch.no_grad()
     def sample_ddim(self, state, action, goal, sigmas, cond_lambda=None, bounds=None, record=False, pin=None, candidates=None,
@@ -470,15 +476,13 @@ class GCDenoiser(nn.Module):
         steer = take_steer({"steer": steer})[0]
         if steer is not None:
             steer_alone(cond_lambda=cond_lambda, pin=pin)
-            if record:
-                raise NotImplementedError("sample_ddim keeps no per-step record; run the host loop with a callback")
-            return self.sample_steered(state, action, goal, sigmas, steer, candidates=candidates)
         if record:
             raise NotImplementedError("sample_ddim keeps no per-step record; run the host loop with a callback")
+        if steer is not None:
+            return self.sample_steered(state, action, goal, sigmas, steer, candidates=candidates)
         im = self.inner_model
         K = candidate_count(candidates)
-        if pin is not None and callable(getattr(pin, "on", None)):
-            pin = pin.on(action.device, (action.numel() // (action.shape[-2] * action.shape[-1]),) + tuple(action.shape[-2:]), K)
+        pin = _pin_rows(pin, action, K)
         out, ctx = self._engine(state=state).sample_ddim(state, action, im._goals(goal, False), sigmas, cond_lambda=cond_lambda,
                                                          pin=pin, candidates=K)
         im.latent_encoder_emb = ctx

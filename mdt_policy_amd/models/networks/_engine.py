@@ -425,6 +425,17 @@ class HipEngine:
             _lib.call(self.lib.mdt_sample_ddim_dev_multi if p.dev else self.lib.mdt_sample_ddim_multi, *head, K, *tail)
         return p.out, p.ctx
 
+    def _steered_inputs(self, state: dict, x_T, goal, sigmas, steer, bounds, n_steps=None, noise=None, candidates: int = 1):
+        """What both steered calls start from: the tapes prepared, the schedule on the host, ``_sampler_inputs`` on it, the steer
+        per chunk, the bounds as fp32 (A,) device tensors or None.  Holds what the enqueued kernels read in ``_keep``."""
+        self.train_prepare()
+        host = sigmas.detach().to("cpu") if torch.is_tensor(sigmas) else sigmas
+        p = self._sampler_inputs(state, x_T, goal, host, n_steps, noise, candidates=candidate_count(candidates))
+        known, weight = steer.on(self.device, (p.N, self.Ta, self.A), p.K)
+        lo, hi = (None, None) if bounds is None else (self._in(b, (self.A,)) for b in bounds)
+        self._keep = (p.sig, p.nz, known, weight, lo, hi)  # the kernels that read them are only enqueued
+        return p, host, known, weight, lo, hi
+
     def sample_ddim_steer(self, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, steer, candidates: int = 1, bounds=None):
         """mdt_sample_ddim_steer: DDIM with every step's denoised value steered through the denoiser's Jacobian, D' = D + s(sigma)
         J^T (weight (known - D)), as one enqueue -- the observations encoded once, per step one taped decoder forward on the B*K
@@ -432,17 +443,9 @@ class HipEngine:
         (B*K, Ta, A) or (B, K, Ta, A); ``bounds``: None or (lo, hi), fp32 (A,) device tensors -- x is clamped after every step
         (sample_euler's clip; sample_ddim passes none).  The schedule goes to the host (a device schedule is read back).  Not
         capture-safe: on a capturing stream the library refuses with MDT_ERR_STATE and enqueues nothing."""
-        self.train_prepare()
-        K = candidate_count(candidates)
-        host = sigmas.detach().to("cpu") if torch.is_tensor(sigmas) else sigmas
-        p = self._sampler_inputs(state, x_T, goal, host, candidates=K)
-        known, weight = steer.on(self.device, (p.N, self.Ta, self.A), K)
-        lo = hi = None
-        if bounds is not None:
-            lo, hi = (self._in(b, (self.A,)) for b in bounds)
-        self._keep = (p.sig, known, weight, lo, hi)  # the kernels that read them are only enqueued
+        p, _, known, weight, lo, hi = self._steered_inputs(state, x_T, goal, sigmas, steer, bounds, candidates=candidates)
         _lib.call(self.lib.mdt_sample_ddim_steer, self.handle, _ptr(p.tok), _ptr(p.tok2), _ptr(p.g), p.modality, _ptr(p.x),
-                  C.cast(p.sig, C.c_void_p), p.n, p.B, K, _ptr(known), _ptr(weight), float(steer.beta), _ptr(lo), _ptr(hi),
+                  C.cast(p.sig, C.c_void_p), p.n, p.B, p.K, _ptr(known), _ptr(weight), float(steer.beta), _ptr(lo), _ptr(hi),
                   _ptr(p.out), _ptr(p.ctx), self._stream())
         return p.out, p.ctx
 
@@ -455,21 +458,13 @@ class HipEngine:
         fp32 (A,) device tensors, applied where the kind's loop clips; ``record``: the call also fills the (steps, 2, B*K, Ta, A)
         record, [i][1] holding D'.  The schedule goes to the host (a device schedule is read back).  Returns (out, ctx, record or
         None).  Not capture-safe: on a capturing stream the library refuses with MDT_ERR_STATE and enqueues nothing."""
-        self.train_prepare()
-        K = candidate_count(candidates)
-        host = sigmas.detach().to("cpu") if torch.is_tensor(sigmas) else sigmas
-        p = self._sampler_inputs(state, x_T, goal, host, n_steps, noise, candidates=K)
-        known, weight = steer.on(self.device, (p.N, self.Ta, self.A), K)
+        p, host, known, weight, lo, hi = self._steered_inputs(state, x_T, goal, sigmas, steer, bounds, n_steps, noise, candidates)
         rec = None
         if record:
             steps = len(host) - 1 if n_steps is None else int(n_steps) // 3 + 1  # n_steps: dpm_fast's evaluation count
             rec = torch.empty((steps, 2) + tuple(p.out.shape), device=self.device, dtype=torch.float32)
-        lo = hi = None
-        if bounds is not None:
-            lo, hi = (self._in(b, (self.A,)) for b in bounds)
-        self._keep = (p.sig, p.nz, known, weight, lo, hi)  # the kernels that read them are only enqueued
         _lib.call(self.lib.mdt_sample_steer, self.handle, _ptr(p.tok), _ptr(p.tok2), _ptr(p.g), p.modality, _ptr(p.x), int(kind),
-                  C.byref(params), p.sig_arg, p.n, _ptr(p.nz), 0 if p.nz is None else p.nz.shape[0], p.B, K, _ptr(known),
+                  C.byref(params), p.sig_arg, p.n, _ptr(p.nz), 0 if p.nz is None else p.nz.shape[0], p.B, p.K, _ptr(known),
                   _ptr(weight), float(steer.beta), _ptr(lo), _ptr(hi), _ptr(rec), _ptr(p.out), _ptr(p.ctx), self._stream())
         return p.out, p.ctx, rec
 

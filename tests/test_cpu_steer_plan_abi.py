@@ -108,7 +108,8 @@ def test_the_messages_say_what_was_wrong():
     dict(kind="dpm_fast", sigmas=(80.0, 0.01), n_steps=6, params=dict(eta=1.0), noise=PTR, n_noise=3),
     dict(kind="dpm_fast", sigmas=(0.01, 80.0), n_steps=4, params=dict(eta=0.0)),
     dict(sigmas=tuple([1.0] * _lib.SAMPLER_MAX_STEPS) + (0.0,)), dict(lo=PTR, hi=PTR), dict(record=PTR),
-    dict(tokens2=PTR, handle=HANDLE_MDT)], ids=str)
+    dict(tokens2=PTR, handle=HANDLE_MDT)],
+    ids=lambda kw: str(kw).replace(str(HANDLE_MDT), "HANDLE_MDT").replace(str(PTR), "PTR"))  # no address in a test's name
 def test_good_arguments_pass_the_argument_checks(kw):
     """Every argument in order, on a handle without a training state: MDT_ERR_STATE from the guard mdt_log_likelihood has, still
     with nothing enqueued -- the argument checks, the plan's among them, are behind us."""
