@@ -115,6 +115,35 @@ mdt_status mdt_op_narrow_dw(const float *G, const float *Y, int64_t ldy, float *
 mdt_status mdt_op_narrow_out(const float *G, int64_t ldg, const float *WT, float *out, int32_t M, int32_t A, int32_t D, void *stream);
 mdt_status mdt_op_narrow_dx(const float *G, const float *W, float *out, int32_t M, int32_t A, int32_t D, void *stream);
 
+/* The four element-wise kernels of the steered samplers (mdt_sample_ddim_steer, mdt_sample_steer), each through the launch its
+ * entry point makes, on the caller's buffers.  Each is a grid-stride loop over N + R indices -- the N action elements, then the R
+ * per-row sigma entries -- of at most 1024 workgroups of 256 threads (mdt_op_steer_seed: the N elements only).  Dense fp32.
+ *   mdt_op_steer_seed : D = c_skip x + c_out F;  e = weight (known - D);  dF = c_out e  (the EDM scalings of sigma, sd).
+ *   mdt_op_steer_step : g = c_in small + c_skip e;  D' = D + scale g;  x_out = ratio x_in + coef D', clamped to [lo, hi] per
+ *                       column i % A where bounds are given;  sig_rows = sigma_next.  x_out may be x_in.  N = 0: the sigma rows
+ *                       only, every element pointer unused.
+ *   mdt_op_steer_first: X = x_T;  Y = x_T + cn n0 (n0 null or cn == 0: x_T's bits);  hist (4, N) = 0;  sig_rows = sigma0.
+ *   mdt_op_steer_plan : D' as above at ev->sigma, then one evaluation of a sampler plan (mdt_hip.h: mdt_sampler_eval) on the
+ *                       registers X, Y, D', d = (Y - D') / sigma, H0..H3, N0, N1: x_out = sum cx R, clamped where bounds are
+ *                       given and ev->ends_step;  y_out (or null) = cy[NREG] x_out + sum cy R;  rec (2, N) (or null) = Y, D'
+ *                       where ev->begins_step;  the history shift of ev->push;  sig_rows = ev->sigma_next.  noise (n_noise, N) or
+ *                       null: a row of ev->noise outside [0, n_noise), or any row of a null noise, reads as 0.  x_out may be X,
+ *                       y_out may be Y.
+ * Refused with MDT_ERR_INVALID_ARG and a text that names the hook and the field, nothing launched: a null required pointer
+ * (element operands where N > 0, sig_rows where R > 0); N < 0, R < 0 or N + R < 1 (seed: N < 1); A < 1, or bounds with N no
+ * multiple of A; lo without hi or hi without lo; n_noise < 0; sigma, sigma0 or sd not finite and > 0. */
+mdt_status mdt_op_steer_seed(const float *F, const float *x, const float *known, const float *weight, float sigma, float sd,
+                             int64_t N, float *D, float *e, float *dF, void *stream);
+mdt_status mdt_op_steer_step(const float *small, const float *e, const float *D, const float *x_in, float sigma, float sd, float scale,
+                             float ratio, float coef, const float *lo, const float *hi, int32_t A, float sigma_next, int64_t N,
+                             int64_t R, float *x_out, float *sig_rows, void *stream);
+mdt_status mdt_op_steer_first(const float *x_T, const float *n0, float cn, float sigma0, int64_t N, int64_t R, float *X, float *Y,
+                              float *hist, float *sig_rows, void *stream);
+mdt_status mdt_op_steer_plan(const mdt_sampler_eval *ev, const float *small, const float *e, const float *D, const float *Y,
+                             const float *X, float *x_out, float *y_out, float *hist, const float *noise, const float *lo,
+                             const float *hi, float *rec, float *sig_rows, int64_t N, int64_t R, float sd, float scale,
+                             int32_t n_noise, int32_t A, void *stream);
+
 /* Measurement hook: bracket every fused-MLP launch of the model-level calls that follow (mdt_sample_ddim, mdt_forward, ...)
  * with a pair of HIP events on its stream; mdt_op_trace_mlp_read waits for them, writes up to `cap` durations in
  * MICROSECONDS (launch order) to `us`, releases the events and returns how many it wrote.  The duration of the dominant

@@ -19,6 +19,7 @@
 
 #include <cmath>
 
+#include "mdt_hip_debug.h"
 #include "mdt_hip_train.h"
 #include "mdt_internal.h"
 #include "mdt_launch.h"
@@ -379,4 +380,113 @@ extern "C" mdt_status mdt_sample_steer(mdt_model* m, const float* tokens, const 
     MDT_TRY(steer_call(c, m, s, tokens, tokens2, goal, modality, batch * candidates, known, weight, lo, hi));
     return mdt_ll_scoped(m, batch, candidates, s, &c.run,
                          [&] { return run_plan(c, kind, n_steps, P, x_T, noise, n_noise, beta, record, out, ctx_out); });
+}
+
+// ------------------------------------------------------------------------------------------------
+// test hooks (mdt_hip_debug.h): the four kernels above on the caller's buffers, each through the launch its entry point makes --
+// steer_grid of what the entry passes, STEER_THREADS, mdt_launch_lds.  What a model call guarantees by construction is checked here.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct Named {
+    const void* p;
+    const char* name;
+};
+
+mdt_status hook_nulls(const char* fn, std::initializer_list<Named> ps) {
+    for (const Named& n : ps)
+        if (!n.p) return fail(MDT_ERR_INVALID_ARG, "%s: null %s", fn, n.name);
+    return MDT_OK;
+}
+
+mdt_status hook_sizes(const char* fn, int64_t N, int64_t R) {
+    if (N < 0) return fail(MDT_ERR_INVALID_ARG, "%s: N is %lld, must be >= 0", fn, (long long)N);
+    if (R < 0) return fail(MDT_ERR_INVALID_ARG, "%s: R is %lld, must be >= 0", fn, (long long)R);
+    if (N + R < 1) return fail(MDT_ERR_INVALID_ARG, "%s: N + R is 0: nothing to launch over", fn);
+    return MDT_OK;
+}
+
+mdt_status hook_positive(const char* fn, const char* name, float v) {
+    if (!std::isfinite(v) || !(v > 0.f)) return fail(MDT_ERR_INVALID_ARG, "%s: %s is %g, must be finite and > 0", fn, name, v);
+    return MDT_OK;
+}
+
+mdt_status hook_bounds(const char* fn, const float* lo, const float* hi, int32_t A, int64_t N) {
+    if (A < 1) return fail(MDT_ERR_INVALID_ARG, "%s: A is %d, must be >= 1", fn, A);
+    if ((!lo) != (!hi)) return fail(MDT_ERR_INVALID_ARG, "%s: null %s: the bounds lo and hi come together", fn, lo ? "hi" : "lo");
+    if (lo && N % A != 0)
+        return fail(MDT_ERR_INVALID_ARG, "%s: N is %lld, no multiple of A = %d: the bounds are per column of rows of A", fn,
+                    (long long)N, A);
+    return MDT_OK;
+}
+
+}  // namespace
+
+extern "C" mdt_status mdt_op_steer_seed(const float* F, const float* x, const float* known, const float* weight, float sigma, float sd,
+                                        int64_t N, float* D, float* e, float* dF, void* stream) {
+    const char* fn = "mdt_op_steer_seed";
+    MDT_TRY(hook_nulls(fn, {{F, "F"}, {x, "x"}, {known, "known"}, {weight, "weight"}, {D, "D"}, {e, "e"}, {dF, "dF"}}));
+    if (N < 1) return fail(MDT_ERR_INVALID_ARG, "%s: N is %lld, must be >= 1", fn, (long long)N);
+    MDT_TRY(hook_positive(fn, "sigma", sigma));
+    MDT_TRY(hook_positive(fn, "sd", sd));
+    LAUNCH(mdt_launch_lds<k_steer_seed>(dim3(steer_grid(N)), dim3(STEER_THREADS), 0, (hipStream_t)stream, F, x, known, weight, sigma, sd,
+                                        N, D, e, dF));
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_steer_step(const float* small, const float* e, const float* D, const float* x_in, float sigma, float sd,
+                                        float scale, float ratio, float coef, const float* lo, const float* hi, int32_t A,
+                                        float sigma_next, int64_t N, int64_t R, float* x_out, float* sig_rows, void* stream) {
+    const char* fn = "mdt_op_steer_step";
+    MDT_TRY(hook_sizes(fn, N, R));
+    if (N > 0) MDT_TRY(hook_nulls(fn, {{small, "small"}, {e, "e"}, {D, "D"}, {x_in, "x_in"}, {x_out, "x_out"}}));
+    if (R > 0) MDT_TRY(hook_nulls(fn, {{sig_rows, "sig_rows"}}));
+    MDT_TRY(hook_bounds(fn, lo, hi, A, N));
+    MDT_TRY(hook_positive(fn, "sigma", sigma));
+    MDT_TRY(hook_positive(fn, "sd", sd));
+    LAUNCH(mdt_launch_lds<k_steer_step>(dim3(steer_grid(N + R)), dim3(STEER_THREADS), 0, (hipStream_t)stream, small, e, D, x_in, sigma,
+                                        sd, scale, ratio, coef, lo, hi, (int)A, sigma_next, N, R, x_out, sig_rows));
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_steer_first(const float* x_T, const float* n0, float cn, float sigma0, int64_t N, int64_t R, float* X,
+                                         float* Y, float* hist, float* sig_rows, void* stream) {
+    const char* fn = "mdt_op_steer_first";
+    MDT_TRY(hook_sizes(fn, N, R));
+    if (N > 0) MDT_TRY(hook_nulls(fn, {{x_T, "x_T"}, {X, "X"}, {Y, "Y"}, {hist, "hist"}}));
+    if (R > 0) MDT_TRY(hook_nulls(fn, {{sig_rows, "sig_rows"}}));
+    MDT_TRY(hook_positive(fn, "sigma0", sigma0));
+    LAUNCH(mdt_launch_lds<k_steer_first>(dim3(steer_grid(N + R)), dim3(STEER_THREADS), 0, (hipStream_t)stream, x_T, n0, cn, sigma0, N, R,
+                                         X, Y, hist, sig_rows));
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_steer_plan(const mdt_sampler_eval* ev, const float* small, const float* e, const float* D, const float* Y,
+                                        const float* X, float* x_out, float* y_out, float* hist, const float* noise, const float* lo,
+                                        const float* hi, float* rec, float* sig_rows, int64_t N, int64_t R, float sd, float scale,
+                                        int32_t n_noise, int32_t A, void* stream) {
+    const char* fn = "mdt_op_steer_plan";
+    MDT_TRY(hook_nulls(fn, {{ev, "ev"}}));
+    MDT_TRY(hook_sizes(fn, N, R));
+    if (N > 0) MDT_TRY(hook_nulls(fn, {{small, "small"}, {e, "e"}, {D, "D"}, {Y, "Y"}, {X, "X"}, {x_out, "x_out"}, {hist, "hist"}}));
+    if (R > 0) MDT_TRY(hook_nulls(fn, {{sig_rows, "sig_rows"}}));
+    MDT_TRY(hook_bounds(fn, lo, hi, A, N));
+    if (n_noise < 0) return fail(MDT_ERR_INVALID_ARG, "%s: n_noise is %d, must be >= 0", fn, n_noise);
+    MDT_TRY(hook_positive(fn, "ev->sigma", ev->sigma));
+    MDT_TRY(hook_positive(fn, "sd", sd));
+    SteerPlanArgs a;
+    a.ev = *ev;
+    a.small = small; a.e = e; a.D = D;
+    a.Y = Y; a.X = X;
+    a.x_out = x_out; a.y_out = y_out;
+    a.hist = hist;
+    a.noise = noise;
+    a.lo = lo; a.hi = hi;
+    a.rec = rec;
+    a.sig_rows = sig_rows;
+    a.N = N; a.R = R;
+    a.sd = sd; a.scale = scale;
+    a.n_noise = n_noise; a.A = A;
+    LAUNCH(mdt_launch_lds<k_steer_plan>(dim3(steer_grid(N + R)), dim3(STEER_THREADS), 0, (hipStream_t)stream, a));
+    return MDT_OK;
 }

@@ -1,5 +1,6 @@
-"""Shared by tests/test_sampler_envelope.py (CPU) and tests/test_gpu_sampler_envelope.py: the sampler options -- pin, bounds and
-record, guidance, candidates, steer, denoise_vjp, log-likelihood -- on the configurations of tests/envelope_configs.ENVELOPE.
+"""Shared by tests/test_sampler_envelope.py (CPU), tests/test_gpu_sampler_envelope.py and tests/test_gpu_steer_plan_envelope.py:
+the sampler options -- pin, bounds and record, guidance, candidates, steer (DDIM's and, at the end of the file, every plan
+sampler's), denoise_vjp, log-likelihood -- on the configurations of tests/envelope_configs.ENVELOPE.
 
 The reference of every comparison is the package's own host loop in gc_sampling run on the CPU over ``EnvelopeOracle``, a float64
 denoiser built from oracle/mdt_oracle.py that composes the options the way GCDenoiser.forward does; it shares no kernel with the
@@ -328,4 +329,149 @@ def loglik_reference(name, monkeypatch, B=2, K=3):
             ll, info = gs.log_likelihood(oracle_of(name), wide(st), rows.double(), goal.repeat_interleave(K, 0).double(),
                                          LL_SMIN, LL_SMAX)
         _LOOPS[key] = (ll, kept["y"][0], kept["y"][1], dict(info))
+    return _LOOPS[key]
+
+
+# ---- the steered plan samplers (mdt_sample_steer) --------------------------------------------------------------------------------
+# (a) the kinds without noise rows, through gc_sampling's own loop: kind -> (sample_<kind>'s keyword arguments, steps of 80 -> 1)
+PLAN_KINDS = {"heun": (dict(s_churn=0.), N), "dpmpp_2m": ({}, N), "lms": (dict(order=4), 6), "dpmpp_sde": (dict(eta=1.), N)}
+PLAN_CASES = [(n, k) for k in ("heun", "dpmpp_2m") for n in NAMES] + [(n, k) for k in ("lms", "dpmpp_sde") for n in LL_NAMES]
+# (b) the kinds that read noise rows, through the plan interpreter: tag -> (kind, parameters, dpm_fast's evaluation count)
+NOISE_NAMES = ["h1_d64_min", "a16_ctx16", "mdt_h6_a12"]
+NOISE_KINDS = {"euler_churn": ("euler", dict(s_churn=1.0), None), "heun_churn": ("heun", dict(s_churn=1.0, s_noise=0.9), None),
+               "euler_ancestral": ("euler_ancestral", {}, None), "dpm_2_ancestral": ("dpm_2_ancestral", {}, None),
+               "dpmpp_2s_ancestral": ("dpmpp_2s_ancestral", {}, None), "dpm_fast_6": ("dpm_fast", {}, 6)}
+# (c) bounds: the kinds whose loops clip after every step, and the one that never reads its scaler
+CLIP_NAMES = ["a16_ctx16", "mdt_h6_a12"]
+CLIP_KINDS = {"heun": dict(s_churn=0.), "dpm_2": dict(s_churn=0.)}
+
+
+def plan_sched(kind):
+    return gs.get_sigmas_exponential(PLAN_KINDS[kind][1] if kind in PLAN_KINDS else N, SMIN, SMAX)
+
+
+def native_steer(steer):
+    """The same steer asking for the native plan call (mdt_sample_steer)."""
+    return ActionSteer(steer.known, steer.weight, steer.beta, plan_native=True)
+
+
+def steer_gate(want):
+    """The project's gate for steered trajectories, per element: (1 + beta) (ATOL + RTOL |want|)."""
+    return (1 + BETA) * (ATOL + RTOL * want.detach().double().abs())
+
+
+def werr_bound(steer, want):
+    """|E(native) - E(want)| <= sum W (2 |known - want| t + t^2), t the per-element gate (tests/test_gpu_steer_plan.py)."""
+    known, w = steer.on("cpu", tuple(want.shape))
+    t = steer_gate(want)
+    return float((w.double() * (2 * (known.double() - want).abs() * t + t * t)).sum())
+
+
+def run_plan_loop(kind, model, state, x, goal, fixed, sig, extra_args=None, scaler=None, callback=None, **params):
+    """gc_sampling's sample_<kind> (dpmpp_sde: the fixed noise tensor) with the given parameters."""
+    kw = dict(params)
+    if kind == "dpmpp_sde":
+        kw["noise_sampler"] = lambda s0, s1: fixed.to(device=x.device, dtype=x.dtype)
+    if scaler is not None:
+        kw["scaler"] = scaler
+    if callback is not None:
+        kw["callback"] = callback
+    with torch.no_grad():
+        return getattr(gs, "sample_" + kind)(model, state, x, goal, sig, extra_args=dict(extra_args or {}), **kw)
+
+
+def steered_plan(name, kind, B, x_scale=None):
+    """(steered, unsteered) float64 host loops of a noise-free kind under steer_of(name, B), computed once.  ``x_scale``: x_T is
+    multiplied by it and nothing is kept (the conditioning check of the CPU tier); only the steered result is returned."""
+    key = (name, "steer_plan", kind, B)
+    if key in _LOOPS and x_scale is None:
+        return _LOOPS[key]
+    model = oracle_of(name)
+    state, goal, x, fixed, _ = chunk_case(name, B)
+    state, goal, x, fixed = wide(state), wide(goal), wide(x), wide(fixed)
+    params, sig = (PLAN_KINDS[kind][0] if kind in PLAN_KINDS else CLIP_KINDS[kind]), plan_sched(kind)
+    ea = {"steer": steer_of(name, B)}
+    if x_scale is not None:
+        return run_plan_loop(kind, model, state, x * x_scale, goal, fixed, sig, ea, **params)
+    _LOOPS[key] = (run_plan_loop(kind, model, state, x, goal, fixed, sig, ea, **params),
+                   run_plan_loop(kind, model, state, x, goal, fixed, sig, **params))
+    return _LOOPS[key]
+
+
+class never_forward_steered:
+    """Inside: GCDenoiser._steered counts its calls; the native plan call makes none (tests/test_gpu_steer_plan.both_ways)."""
+
+    def __enter__(self):
+        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
+        self.cls, self.kept, self.calls = GCDenoiser, GCDenoiser._steered, []
+        kept, calls = self.kept, self.calls
+        GCDenoiser._steered = lambda this, *a, **k: calls.append(1) or kept(this, *a, **k)
+        return self
+
+    def __exit__(self, *exc):
+        self.cls._steered = self.kept
+        return False
+
+
+def noise_rows(tag, shape, n):
+    """(n,) + shape explicit noise rows of a case (b)."""
+    return torch.from_numpy(synthetic.normal("steer_plan_rows_" + tag, (n,) + tuple(shape), 35))
+
+
+def noise_plan(tag):
+    """(kind, parameters, n_steps for dpm_fast, host schedule, plan) of a kind that reads noise rows."""
+    from mdt_policy_amd import _lib
+    kind, params, n = NOISE_KINDS[tag]
+    sig = [SMAX, SMIN] if kind == "dpm_fast" else sched().tolist()
+    return kind, params, n, sig, _lib.sampler_plan(kind, sig, n_steps=n, **params)
+
+
+def chunk_steer(name, B, K):
+    """A per-chunk steer over the B * K rows: steer_of(name, B)'s known of the chunk's observation plus 0.1 N(0, 1) of its own."""
+    base = steer_of(name, B)
+    known = base.known.repeat_interleave(K, 0)
+    known = known + 0.1 * torch.from_numpy(synthetic.normal("steer_plan_chunks", tuple(known.shape), 36))
+    return ActionSteer(known, pattern(*known.shape, values=(1.0, 0.25, 0.0)), BETA)
+
+
+def interpreted(name, tag, B, K=1):
+    """(result, [(step, Y, D')] of the evaluations that begin a step, rows, steer) of the float64 plan interpreter
+    (tests/steer_ops_cases.apply_plan) with D' from EnvelopeOracle.steered on the expanded observations, computed once."""
+    key = (name, "steer_interp", tag, B, K)
+    if key not in _LOOPS:
+        from tests.steer_ops_cases import apply_plan
+        kind, params, n, sig, plan = noise_plan(tag)
+        model = oracle_of(name)
+        state, goal, x, _, _ = chunk_case(name, B, K)
+        if K != 1:
+            state = {k: (v.repeat_interleave(K, 0) if torch.is_tensor(v) else v) for k, v in state.items()}
+            goal = goal.repeat_interleave(K, 0)
+        state, goal = wide(state), wide(goal)
+        steer = steer_of(name, B) if K == 1 else chunk_steer(name, B, K)
+        rows = noise_rows(tag, x.shape, plan.n_noise)
+        R = x.shape[0]
+
+        def dprime(Y, sigma, k):
+            return model.steered(state, torch.from_numpy(Y), goal, torch.full((R,), float(sigma), dtype=torch.float64), steer)[0].numpy()
+        out, seen = apply_plan(plan, x.double().numpy(), rows.double().numpy(), dprime)
+        begins = [(plan.e[k].step, torch.from_numpy(seen[k][0]), torch.from_numpy(seen[k][1])) for k in range(plan.n_evals)
+                  if plan.e[k].begins_step]
+        _LOOPS[key] = (torch.from_numpy(out), begins, rows, steer)
+    return _LOOPS[key]
+
+
+def steered_bounded(name, kind, B):
+    """(lo, hi, clamped float64 steered loop, share changed per step, unclamped steered loop), computed once: the ``bounded``
+    pattern under steer_of(name, B), the bounds at the quantiles of the unclamped steered result."""
+    key = (name, "steer_bounds", kind, B)
+    if key not in _LOOPS:
+        model = oracle_of(name)
+        state, goal, x, fixed, _ = chunk_case(name, B)
+        state, goal, x, fixed = wide(state), wide(goal), wide(x), wide(fixed)
+        plain = steered_plan(name, kind, B)[0]
+        lo, hi = quantile_bounds(plain)
+        scaler = ClampOnly(lo, hi)
+        params = PLAN_KINDS[kind][0] if kind in PLAN_KINDS else CLIP_KINDS[kind]
+        want = run_plan_loop(kind, model, state, x, goal, fixed, plan_sched(kind), {"steer": steer_of(name, B)}, scaler=scaler, **params)
+        _LOOPS[key] = (lo, hi, want, list(scaler.changed), plain)
     return _LOOPS[key]

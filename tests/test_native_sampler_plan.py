@@ -8,6 +8,7 @@ import torch
 
 from mdt_policy_amd import _lib
 from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
+from tests.steer_ops_cases import apply_plan as interpret_plan
 
 B, TA, A = 2, 3, 4
 NREG = _lib.SAMPLER_NREG
@@ -35,22 +36,9 @@ def schedule(name, n):
 
 
 def apply_plan(plan, x_T, noise):
-    """The head kernel's per-element update (mdt_tiles.h, MDT_HEAD_PLAN) in float64."""
-    X = x_T.copy()
-    Y = X + (plan.y0_cn * noise[plan.y0_noise] if plan.y0_noise >= 0 else 0.0)
-    H = np.zeros((4,) + X.shape)
-    zero = np.zeros_like(X)
-    for k in range(plan.n_evals):
-        e = plan.e[k]
-        D = toy(Y, np.float64(e.sigma))
-        R = [X, Y, D, (Y - D) / np.float64(e.sigma), H[0], H[1], H[2], H[3],
-             noise[e.noise[0]] if e.noise[0] >= 0 else zero, noise[e.noise[1]] if e.noise[1] >= 0 else zero]
-        Xn = sum(np.float64(e.cx[q]) * R[q] for q in range(NREG))
-        Yn = np.float64(e.cy[NREG]) * Xn + sum(np.float64(e.cy[q]) * R[q] for q in range(NREG))
-        if e.push:
-            H = np.concatenate([(D if e.push == 1 else R[3])[None], H[:3]])
-        X, Y = Xn, Yn
-    return X
+    """The plan kernels' per-element update in float64 (tests/steer_ops_cases.apply_plan, shared with the steered plan tests) around
+    the toy denoiser."""
+    return interpret_plan(plan, x_T, noise, lambda y, s, k: toy(y, s))[0]
 
 
 class _Recorder:

@@ -29,7 +29,13 @@ Steer, weights (1, 0.25, 0), beta = 5, 3-step DDIM 80 -> 0.01 -> 0: the weighted
   sampler_envelope.steered_ddim.  One evaluation: s |J^T e| max is 730 .. 6900 tolerances at sigma = 1, 8 .. 81 at sigma = 80.
 Log-likelihood, (B, K) = (2, 3), sigma 0.001 .. 80, one sign probe: 74 evaluations in float64 (rope_ta16: 68); |ll| 0.06 .. 1.7
   at h1_d64_min (per = 1), 16 .. 147 elsewhere.
-The whole module takes about a minute at 8 threads.
+Steered plan samplers (mdt_sample_steer; tests/test_gpu_steer_plan_envelope.py), heun and dpmpp_2m on the nine configurations,
+  lms (six steps) and dpmpp_sde on LL_NAMES, under steer_of: a 2^-23 relative perturbation of x_T moves the float64 loop by
+  9.0e-7 .. 6.5e-4 of the gate (1 + beta) (ATOL + RTOL |want|) per element, against 1e-2; |steered - unsteered| max 0.98 .. 6.2
+  against 100 x the gate 0.54 .. 3.0 (at least 1.27 x that).  Bounds at the 0.3 / 0.7 quantiles of the steered result, heun and
+  dpm_2 on a16_ctx16 and mdt_h6_a12: clip_output changes 0.988 .. 0.992 of the elements at the first step, 0.38 .. 0.77 at the
+  others; dpmpp_2m never calls it.
+The whole module takes about a minute and a half at 8 threads.
 """
 import pytest
 import torch
@@ -180,3 +186,52 @@ def test_envelope_oracle_guided_ddim_equals_the_guidance_oracle(monkeypatch):
     # (the host loop forms its step scalars in float32, the guidance oracle in float64)
     assert_close(got, want, rtol=1e-5, atol=1e-6, what="guided DDIM")
     assert guid.tol(lam) == guided_tol()
+
+
+# ---- the steered plan samplers: what tests/test_gpu_steer_plan_envelope.py relies on ----------------------------------------------
+@pytest.mark.parametrize("name,kind", E.PLAN_CASES)
+def test_steered_plan_loops_are_well_conditioned_and_moved_by_the_steer(name, kind):
+    """The float64 steered loop moves by at most 1e-2 of the gate (1 + beta) (ATOL + RTOL |want|) under a 2^-23 relative
+    perturbation of x_T -- an fp32 run of the same loop has room inside the gate -- and steered and unsteered differ by more than
+    100 x the gate."""
+    steered, plain = E.steered_plan(name, kind, B)
+    moved = E.steered_plan(name, kind, B, x_scale=1.0 + 2.0 ** -23)
+    share = float(((moved - steered).abs() / E.steer_gate(steered)).max())
+    gap, tol = float((steered - plain).abs().max()), (1 + E.BETA) * E.tol_of(steered)
+    print(f"{name} {kind}: a 2^-23 perturbation of x_T moves the result by {share:.2e} of the gate; |steered - unsteered| max "
+          f"{gap:.4f} (100 tol {100 * tol:.4f}); weighted error {E.werr(E.steer_of(name, B), plain):.4e} -> "
+          f"{E.werr(E.steer_of(name, B), steered):.4e}")
+    assert bool(torch.isfinite(steered).all()) and steered.dtype == torch.float64
+    assert share < 1e-2, f"{name} {kind}: the float64 loop itself moves by {share:.3e} of the gate"
+    assert gap > 100 * tol, f"{name} {kind}: steered and unsteered differ by {gap:.3e} only"
+
+
+@pytest.mark.parametrize("tag", sorted(E.NOISE_KINDS))
+def test_the_noise_kinds_read_noise_rows_and_record_every_step(tag):
+    kind, params, n, sig, plan = E.noise_plan(tag)
+    coef = [abs(plan.e[k].cx[8 + j]) + abs(plan.e[k].cy[8 + j]) for k in range(plan.n_evals) for j in range(2) if plan.e[k].noise[j] >= 0]
+    assert plan.n_noise > 0 and (any(c > 0 for c in coef) or (plan.y0_noise >= 0 and plan.y0_cn != 0)), (tag, plan.n_noise)
+    steps = [plan.e[k].step for k in range(plan.n_evals) if plan.e[k].begins_step]
+    assert steps == list(range(len(steps))) and len(steps) >= 2
+
+
+@pytest.mark.parametrize("kind", sorted(E.CLIP_KINDS))
+@pytest.mark.parametrize("name", E.CLIP_NAMES)
+def test_steered_bounds_clip_a_share_of_the_elements_at_every_step(name, kind):
+    """Every clip_output call of the float64 steered loop changes between 0.1 and 0.9 of the elements -- but the first, which
+    changes nearly all and is held to that: after the first step x is still N(0, sigma_1^2)-sized, sigma_1 = 80^(2/3) = 18.6,
+    while lo and hi are quantiles of the final result, less than 2 apart, so an element stays inside with probability about
+    (hi - lo) / (sigma_1 sqrt(2 pi)) < 0.05.  (Measured: 0.988 .. 0.992 at the first step, 0.38 .. 0.77 at the others.)"""
+    lo, hi, want, changed, plain = E.steered_bounded(name, kind, B)
+    print(f"{name} steered {kind}: clip_output changed {[round(c, 3) for c in changed]}; |clamped - unclamped| max "
+          f"{float((want - plain).abs().max()):.4f}")
+    assert float((hi - lo).max()) < 2.0 and float(E.sched()[1]) > 18.0
+    assert len(changed) == E.N and 0.1 <= min(changed) and max(changed[1:]) <= 0.9 and 0.95 <= changed[0] < 1.0, changed
+    assert bool((want >= lo.double()).all()) and bool((want <= hi.double()).all())
+
+
+@pytest.mark.parametrize("name", E.CLIP_NAMES)
+def test_steered_dpmpp_2m_never_reads_its_scaler(name):
+    lo, hi, want, changed, plain = E.steered_bounded(name, "dpmpp_2m", B)
+    assert changed == [] and torch.equal(want, plain)
+    assert int(((plain < lo.double()) | (plain > hi.double())).sum()) > 0
