@@ -378,6 +378,32 @@ mdt_status mdt_sample_ddim_dev_multi(mdt_model *m, const float *tokens, const fl
                                      const float *x_T, const float *sigmas_dev, int32_t n_steps, int64_t batch,
                                      int32_t candidates, float *out, float *ctx_out, const mdt_sample_opts *opts, void *stream);
 
+/* Score action chunks by their denoising error: the step between mdt_sample*_multi and the selection, forwards only.  ONE enqueue
+ * on the inference path -- no mdt_train_prepare, no tape, no synchronisation, nothing read back -- and safe to capture into a
+ * graph once the workspace holds the call's rows (mdt_reserve(batch * candidates * n_levels * draws), or one eager call, first).
+ *     score[r] = - sum_s w_s (1 / M) sum_m sum_e q[r, s, m, e]^2,   q = (x0[r] - D(x0[r] + sigma_s n[s, m]; sigma_s, context(r / K))) / sigma_s
+ * for the R = B * K chunks x0 (R, Ta, A), chunk k of observation b at row b * K + k; S = n_levels levels sigmas_host (S,) and
+ * weights weights_host (S,), both in host memory and read before the call returns; M = draws noise rows per level, noise
+ * (S, M, Ta, A) on the device, the same rows for every chunk of every observation (antithetic pairs n, -n side by side cancel the
+ * part of the estimate that is odd in n).  By the pointwise I-MMSE relation this is log p(x0) up to a constant of the call for a
+ * denoiser that is the posterior mean, truncated to the range of the levels: higher is better, and score goes to a per-observation
+ * argmax as it is.  It ranks chunks; it is no calibrated likelihood.  weights_host == NULL: the trapezoid rule in ln sigma over the
+ * levels in the order given (w = 1 for a single level); the levels must then be strictly monotone.
+ * q is formed from the raw network output F without forming x0 - D: q = sigma / (sigma^2 + sd^2) x0 - c_skip n - sd / sqrt(sigma^2 + sd^2) F.
+ * The encoder, the stacked cross K|V product and the fold run once on the B observations (tokens, tokens2, goal as in
+ * mdt_sample_ddim_multi), the decoder blocks and the head once on B * S * K * M samples, each with its own sigma; with
+ * use_ada_conditioning = 0 sigma is a context token and the encoder runs on the B * S contexts.  ctx_out: NULL or (B, Te, d), the
+ * observations' context (sigma as a context token: at the last level).  A chunk's score does not depend on the other chunks of
+ * the call, and the sums have one fixed order: the same call gives the same bits.
+ * MDT_ERR_INVALID_ARG, "mdt_denoising_score: ..." naming the field, before anything is enqueued: a null handle or required
+ * pointer; batch or candidates < 1; n_levels or draws outside [1, 64]; a level that is not finite and > 0; a weight that is not
+ * finite and >= 0; weights_host == NULL with levels that are not strictly monotone; MDT, or a use_proprio handle, without tokens2;
+ * more rows batch * candidates * n_levels * draws than the decoder's 2^24 / max(Te, Ta) samples. */
+mdt_status mdt_denoising_score(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                               const float *x0, const float *sigmas_host, const float *weights_host, int32_t n_levels,
+                               const float *noise, int32_t draws, int64_t batch, int32_t candidates, float *score, float *ctx_out,
+                               void *stream);
+
 /* sample_dpm_adaptive (eta = 0): DPM-Solver-12 / -23 with the PID step-size control of _StepControl, as ONE blocking call.
  * Every attempted step runs its 2 or 3 denoiser evaluations; the head of the last one writes both the order-k ("high") and the
  * order-(k-1) ("low") result, one small kernel writes per-workgroup partial sums of the scaled error, and the host reads them

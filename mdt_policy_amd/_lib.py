@@ -263,6 +263,9 @@ SYMBOLS = [
     ("mdt_sample_ddim_multi", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(C.c_float), _I32, _I64, _I32, _VP, _VP,
                                      C.POINTER(SampleOpts), _VP]),
     ("mdt_sample_ddim_dev_multi", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _I64, _I32, _VP, _VP, C.POINTER(SampleOpts), _VP]),
+    # chunks scored by their denoising error: host levels and weights (or NULL), device noise rows (n_levels, draws, Ta, A)
+    ("mdt_denoising_score", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _VP, _I32, _I64,
+                                   _I32, _VP, _VP, _VP]),
     ("mdt_sampler_plan", _I32, [_I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, C.POINTER(SamplerPlan)]),
     ("mdt_sample_dpm_adaptive", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.c_float, C.c_float, C.POINTER(DpmAdaptiveParams), _I64,
                                        _VP, _VP, C.POINTER(DpmAdaptiveInfo), _VP]),

@@ -227,6 +227,19 @@ hipError_t mdt_launch_guide_stage(const float* tok, const float* tok2, const flo
                                   int B, int w1, int w2, int G, hipStream_t s);
 hipError_t mdt_launch_action_embed(const float* x, const float* sigma, int64_t sstride, float sd, const float* Wa,
                                    const float* ba, float* y, int M, int A, int D, int rps, hipStream_t s);
+// mdt_denoising_score (mdt_score.hip): the S levels and weights of a call by value; decoder sample ((b S + s) K + k) M + m is
+// chunk k of observation b at level s with noise row m.  prep: the embedded input y (rows, D), the noised rows (rows, A), the
+// samples' sigma (B S K M) and, where asked for, the contexts' (B S).  repeat: the encoder inputs of observation b at contexts
+// b S .. b S + S - 1 (w2 == 0: no tokens2).  reduce: score (B K) from the raw network output F of those samples.
+constexpr int MDT_SCORE_MAX = 64;
+struct mdt_score_levels { float sigma[MDT_SCORE_MAX], weight[MDT_SCORE_MAX]; };
+hipError_t mdt_launch_score_prep(const float* x0, const float* noise, const mdt_score_levels& lv, int64_t B, int S, int K, int M, int Ta,
+                                 int A, int D, float sd, const float* Wa, const float* ba, float* y, float* noised, float* sig_rows,
+                                 float* ctx_sig, hipStream_t s);
+hipError_t mdt_launch_score_repeat(const float* tok, const float* tok2, const float* goal, float* tok_o, float* tok2_o, float* goal_o,
+                                   int64_t B, int S, int w1, int w2, int wg, hipStream_t s);
+hipError_t mdt_launch_score_reduce(const float* F, const float* x0, const float* noise, const mdt_score_levels& lv, int64_t B, int S,
+                                   int K, int M, int E, float sd, float* score, hipStream_t s);
 hipError_t mdt_launch_noise_input(const float* act, const float* noise, const float* sigma, float* noised, int64_t n,
                                   int per_sample, hipStream_t s);
 constexpr int MDT_LOSS_PARTS = 1024;   // floats of scratch mdt_launch_loss_reduce wants (`part`)

@@ -1406,6 +1406,96 @@ extern "C" mdt_status mdt_sample_ddim_dev_multi(mdt_model* m, const float* token
     return sample_ddim_impl(m, r.schedule(sigmas_dev, true, n_steps).candidates(candidates));
 }
 
+// mdt_denoising_score (include/mdt_hip.h): the R = B * K chunks' likelihood-weighted denoising error from ONE decoder pass on the
+// inference path.  The decoder runs B * S * K * M samples, sample ((b S + s) K + k) M + m = chunk k of observation b at level s
+// with noise row m (mdt_score.hip), each with its own sigma as mdt_denoise_cached runs per-sample sigma: one conditioning row
+// per sample, stride cond_width.  The encoder, the stacked cross K|V product and the fold run on the B observations and S K M
+// consecutive samples read one context (ctx_div); where sigma is a context token they run on the B * S contexts (b, s), the
+// observation's inputs staged S times, and K M samples read one.  Every check comes before the first launch.
+extern "C" mdt_status mdt_denoising_score(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
+                                          const float* x0, const float* sigmas_host, const float* weights_host, int32_t n_levels,
+                                          const float* noise, int32_t draws, int64_t batch, int32_t candidates, float* score,
+                                          float* ctx_out, void* stream) {
+    const char* fn = "mdt_denoising_score";
+    if (!m) return fail(MDT_ERR_INVALID_ARG, "%s: null handle", fn);
+    const std::pair<const void*, const char*> need[] = {{tokens, "tokens"}, {goal, "goal"}, {x0, "x0"}, {sigmas_host, "sigmas"},
+                                                        {noise, "noise"}, {score, "score"}};
+    for (const auto& p : need)
+        if (!p.first) return fail(MDT_ERR_INVALID_ARG, "%s: null %s", fn, p.second);
+    if (batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: batch is %lld, must be >= 1", fn, (long long)batch);
+    if (candidates < 1) return fail(MDT_ERR_INVALID_ARG, "%s: candidates is %d, must be >= 1", fn, (int)candidates);
+    if (n_levels < 1 || n_levels > MDT_SCORE_MAX)
+        return fail(MDT_ERR_INVALID_ARG, "%s: n_levels is %d, must be in [1, %d]", fn, (int)n_levels, MDT_SCORE_MAX);
+    if (draws < 1 || draws > MDT_SCORE_MAX)
+        return fail(MDT_ERR_INVALID_ARG, "%s: draws is %d, must be in [1, %d]", fn, (int)draws, MDT_SCORE_MAX);
+    const int S = n_levels, K = candidates, M = draws;
+    mdt_score_levels lv;
+    memset(&lv, 0, sizeof lv);
+    for (int i = 0; i < S; ++i) {
+        if (!std::isfinite(sigmas_host[i]) || !(sigmas_host[i] > 0.f))
+            return fail(MDT_ERR_INVALID_ARG, "%s: sigmas[%d] is %g, must be finite and > 0", fn, i, (double)sigmas_host[i]);
+        lv.sigma[i] = sigmas_host[i];
+    }
+    if (weights_host) {
+        for (int i = 0; i < S; ++i) {
+            if (!std::isfinite(weights_host[i]) || !(weights_host[i] >= 0.f))
+                return fail(MDT_ERR_INVALID_ARG, "%s: weights[%d] is %g, must be finite and >= 0", fn, i, (double)weights_host[i]);
+            lv.weight[i] = weights_host[i];
+        }
+    } else {  // the trapezoid rule in ln sigma over the levels as given: half the distance to each neighbour; one level: 1
+        const bool up = S > 1 && sigmas_host[1] > sigmas_host[0];
+        for (int i = 1; i < S; ++i)
+            if (up ? !(sigmas_host[i] > sigmas_host[i - 1]) : !(sigmas_host[i] < sigmas_host[i - 1]))
+                return fail(MDT_ERR_INVALID_ARG, "%s: sigmas[%d] is %g after %g: without weights the levels must be strictly monotone "
+                                                 "(the default is the trapezoid rule in ln sigma)", fn, i, (double)sigmas_host[i],
+                            (double)sigmas_host[i - 1]);
+        for (int i = 0; i < S; ++i) {
+            const double l = std::log((double)sigmas_host[i]);
+            const double lo = i > 0 ? std::fabs(l - std::log((double)sigmas_host[i - 1])) : 0.0;
+            const double hi = i + 1 < S ? std::fabs(std::log((double)sigmas_host[i + 1]) - l) : 0.0;
+            lv.weight[i] = S == 1 ? 1.f : (float)(0.5 * (lo + hi));
+        }
+    }
+    if (m->cfg.arch == MDT_ARCH_MDT && !tokens2) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: MDT needs the gripper tokens", fn);
+    if (m->cfg.use_proprio && !tokens2)
+        return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: this handle was created with use_proprio and needs state_obs", fn);
+    const int64_t limit = ((int64_t)1 << 24) / std::max(1, std::max(m->Te, m->Ta));  // the decoder's row counts (int)
+    const int64_t per_obs = (int64_t)K * S * M;
+    if (per_obs > limit || batch > limit / per_obs)
+        return fail(MDT_ERR_INVALID_ARG, "%s: batch * candidates * n_levels * draws = %lld * %d * %d * %d rows is more than the "
+                                         "decoder's %lld samples", fn, (long long)batch, K, S, M, (long long)limit);
+    MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));
+    MDT_TRY(check_loaded(m));
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nb = batch * per_obs;
+    MDT_TRY(mdt_reserve(m, nb));
+    const bool sig_ctx = m->cond == COND_TOKEN;
+    const float sd = m->cfg.sigma_data;
+    const View V = decoder_view(m, 0);
+    float* sig_rows = m->xbuf;  // (nb): free on this path, like ybuf (the contexts' sigma) -- no sampler state lives here
+    LAUNCH(mdt_launch_score_prep(x0, noise, lv, batch, S, K, M, m->Ta, m->A, m->D, sd, m->Wa, m->ba, V.y, m->noised, sig_rows,
+                                 sig_ctx ? m->ybuf : nullptr, s));
+    const int honour = m->cfg.arch == MDT_ARCH_MDTV;
+    if (sig_ctx) {
+        const int w1 = guide_w1(m), w2 = tokens2 ? guide_w2(m) : 0;
+        LAUNCH(mdt_launch_score_repeat(tokens, tokens2, goal, m->g_tok, m->g_tok2, m->g_goal, batch, S, w1, w2, m->G, s));
+        MDT_TRY(run_encode(m, m->g_tok, w2 ? m->g_tok2 : nullptr, m->g_goal, modality, honour, batch * S, m->ybuf, 1, nullptr, s));
+        if (ctx_out) {  // the context of each observation at the last level, as the samplers leave the last step's
+            const size_t row = (size_t)m->Te * m->D * sizeof(float);
+            HIP_TRY(hipMemcpy2DAsync(ctx_out, row, m->ctx + (size_t)(S - 1) * m->Te * m->D, row * S, row, (size_t)batch,
+                                     hipMemcpyDeviceToDevice, s));
+        }
+    } else {
+        MDT_TRY(run_modulation(m, sig_rows, 1, (int)nb, s));
+        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, honour, batch, nullptr, 0, ctx_out, s));
+    }
+    mdt_head_args h = head_args(m, V.y, nb, m->noised, sig_rows, 1, m->Fbuf, MDT_HEAD_RAW);
+    const int64_t ctx_div = sig_ctx ? (int64_t)K * M : per_obs;
+    MDT_TRY(run_eval(m, V, nb, cond_row(m, 0), sig_ctx ? 0 : cond_width(m), h, nullptr, nullptr, s, mdt_guide(), {}, (int)ctx_div));
+    LAUNCH(mdt_launch_score_reduce(m->Fbuf, x0, noise, lv, batch, S, K, M, m->Ta * m->A, sd, score, s));
+    return MDT_OK;
+}
+
 // MDT_PLAN_* -> mdt_status with the message of the failed check
 static mdt_status plan_fail(int st, const char* who, int kind) {
     switch (st) {

@@ -16,6 +16,8 @@ when the only other key is ``candidates``; with ``ActionSteer(..., plan_native=T
 sample_dpm_adaptive, a ``callback`` or a scaler without ``clip_bounds``, they are host loops whose ``model(...)`` calls get the key.
 ``log_likelihood`` with this package's GCDenoiser is one blocking call too (``GCDenoiser.log_likelihood`` ->
 mdt_log_likelihood), for K chunks per observation and P probes; ``best_candidates`` picks from its result.
+``denoising_score`` is the forwards-only scorer beside it: the chunks' likelihood-weighted denoising error over a few noise
+levels as one enqueue (``GCDenoiser.denoising_score`` -> mdt_denoising_score), no tape, no read-back, capturable.
 
 Signatures follow the reference: ``sample_*(model, state, action, goal, sigmas, scaler=None, extra_args=None,
 callback=None, disable=None, ...)``.
@@ -1414,3 +1416,100 @@ def log_likelihood(model, state, action, goal, sigma_min, sigma_max, extra_args=
                                rtol, atol, stats=info)
     ll_prior = torch.distributions.Normal(0, sigma_max).log_prob(latent).flatten(1).sum(1)
     return ll_prior + delta_ll, info
+
+
+def _score_levels(sigmas, weights):
+    """The levels and weights of ``denoising_score`` as Python floats.  ``weights`` None: the trapezoid rule in ln sigma over the
+    levels in the order given -- half the distance to each neighbour, 1 for a single level -- which needs strictly monotone
+    levels.  What mdt_denoising_score checks and forms, in the same arithmetic (float64, rounded once)."""
+    levels = [float(v) for v in (sigmas.detach().reshape(-1).tolist() if torch.is_tensor(sigmas) else sigmas)]
+    S = len(levels)
+    if S < 1:
+        raise ValueError("denoising_score: sigmas must hold at least one level")
+    for i, v in enumerate(levels):
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError(f"denoising_score: sigmas[{i}] is {v}, must be finite and > 0")
+    if weights is not None:
+        w = [float(v) for v in (weights.detach().reshape(-1).tolist() if torch.is_tensor(weights) else weights)]
+        if len(w) != S:
+            raise ValueError(f"denoising_score: weights hold {len(w)} values, {S} levels take {S}")
+        for i, v in enumerate(w):
+            if not (math.isfinite(v) and v >= 0):
+                raise ValueError(f"denoising_score: weights[{i}] is {v}, must be finite and >= 0")
+        return levels, w
+    up = S > 1 and levels[1] > levels[0]
+    for i in range(1, S):
+        if not (levels[i] > levels[i - 1] if up else levels[i] < levels[i - 1]):
+            raise ValueError(f"denoising_score: sigmas[{i}] is {levels[i]} after {levels[i - 1]}: without weights the levels must be "
+                             "strictly monotone (the default is the trapezoid rule in ln sigma)")
+    ln = [math.log(v) for v in levels]
+    return levels, [1.0 if S == 1 else 0.5 * ((abs(ln[i] - ln[i - 1]) if i > 0 else 0.0) +
+                                              (abs(ln[i + 1] - ln[i]) if i + 1 < S else 0.0)) for i in range(S)]
+
+
+@torch.no_grad()
+def denoising_score(model, state, action, goal, sigmas, extra_args=None, draws=2, weights=None, noise=None, antithetic=True):
+    """Score action chunks by their likelihood-weighted denoising error, forwards only:
+
+        score = - sum_s w_s (1 / M) sum_m || (x0 - D(x0 + sigma_s n[s, m]; sigma_s)) / sigma_s ||^2
+
+    over the S levels ``sigmas`` (any order; host values) and M = ``draws`` noise rows per level, the same rows for every chunk.
+    By the pointwise I-MMSE relation this is log p(x0) up to a constant of the call for a denoiser that is the posterior mean,
+    truncated to the range of the levels.  Higher is better and ``best_candidates(chunks, score, K)`` takes it as it is; it ranks
+    chunks, it is no calibrated likelihood.  ``action`` is (B*K, Ta, A) or (B, K, Ta, A) and the result is shaped
+    ``action.shape[:-2]``.
+
+    ``weights``: None -- the trapezoid rule in ln sigma over the levels in the order given (they must then be strictly monotone; a
+    single level weighs 1) -- or S values >= 0.  ``noise``: None or the rows (S, M, Ta, A).  None draws ``torch.randn`` rows of the
+    action's dtype on its device in (S, M) order; with ``antithetic`` (the default) M / 2 rows per level, each followed directly
+    by its negative, which cancels the part of the estimate that is odd in n -- on a Gaussian-mixture toy 2 such draws at 16 levels
+    rank 8 candidates at Spearman 0.99 against the exact log p where 2 independent ones reach 0.75.  Odd ``draws`` then raise
+    ValueError.  ``extra_args`` reads 'candidates' = K only: K chunks for each of the B observations of ``state`` / ``goal``, chunk k
+    of observation b at row b*K + k.  Any other key raises NotImplementedError naming it.
+
+    With this package's GCDenoiser the score is one native enqueue (``GCDenoiser.denoising_score`` -> mdt_denoising_score): the
+    encoder once on the B observations, one decoder forward on B*K*S*M rows, one reduction -- no tape, no read-back, capturable.
+    It forms q from the network's raw output without the subtraction x0 - D.  Any other model runs a host loop over the levels
+    in its own dtype through ``model(state, x, goal, sigma)``; that loop uses the D form above as written, so in float32 its small
+    levels carry the cancellation of x0 - D.  It has no shared context to exploit: 'candidates' raises ValueError there."""
+    rest = dict(extra_args or {})
+    has_k = "candidates" in rest
+    K, rest = take_candidates(rest)
+    if rest:
+        raise NotImplementedError(f"denoising_score: extra_args[{sorted(rest)[0]!r}] is not supported (the score is that of the "
+                                  "unguided, unpinned model; key read: 'candidates')")
+    native = isinstance(model, GCDenoiser)
+    if has_k and not native:
+        raise ValueError("denoising_score: 'candidates' needs this package's GCDenoiser (a foreign model has no shared context to "
+                         "exploit): expand the observations and score the chunks as a batch")
+    levels, w = _score_levels(sigmas, weights)
+    S = len(levels)
+    Ta, A = action.shape[-2:]
+    if noise is None:
+        if isinstance(draws, bool) or not isinstance(draws, int) or draws < 1:
+            raise ValueError(f"denoising_score: draws must be an int >= 1, got {draws!r}")
+        if antithetic:
+            if draws % 2:
+                raise ValueError(f"denoising_score: draws is {draws}: antithetic pairs need an even count (or antithetic=False)")
+            half = torch.randn((S, draws // 2, Ta, A), dtype=action.dtype, device=action.device)
+            noise = torch.stack((half, -half), dim=2).reshape(S, draws, Ta, A)
+        else:
+            noise = torch.randn((S, draws, Ta, A), dtype=action.dtype, device=action.device)
+    elif noise.dim() != 4 or noise.shape[0] != S or noise.shape[1] < 1 or tuple(noise.shape[2:]) != (Ta, A):
+        raise ValueError(f"denoising_score: noise is {tuple(noise.shape)}: {S} levels take ({S}, draws, {Ta}, {A})")
+    if native:
+        rows, _ = _chunk_view(state, action, None, K)
+        return model.denoising_score(state, rows, goal, levels, noise, weights=None if weights is None else w,
+                                     candidates=K).reshape(action.shape[:-2])
+    rows = action.reshape(-1, Ta, A)
+    noise = noise.to(device=rows.device, dtype=rows.dtype)
+    M = noise.shape[1]
+    score = rows.new_zeros(rows.shape[0])
+    for s in range(S):
+        sigma = rows.new_full((rows.shape[0],), levels[s])
+        level = rows.new_zeros(rows.shape[0])
+        for m in range(M):
+            q = (rows - model(state, rows + levels[s] * noise[s, m], goal, sigma)) / levels[s]
+            level = level + (q * q).flatten(1).sum(1)
+        score = score - (w[s] / M) * level
+    return score.reshape(action.shape[:-2])

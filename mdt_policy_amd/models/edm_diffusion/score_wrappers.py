@@ -382,6 +382,20 @@ class GCDenoiser(nn.Module):
                                                         max_steps=max_steps)
 
     @torch.no_grad()
+    def denoising_score(self, state, rows, goal, sigmas, noise, weights=None, candidates=1):
+        """gc_sampling.denoising_score as one native enqueue (mdt_denoising_score): the encoder and the cross K|V product once on
+        the B observations of ``state`` / ``goal``, one decoder forward over B*K*S*M rows -- the chunks ``rows``, (B*K, Ta, A) or
+        (B, K, Ta, A) with ``candidates`` = K, at the S levels ``sigmas`` (host values) with the M noise rows per level of
+        ``noise`` (S, M, Ta, A) -- and one reduction.  ``weights``: None (trapezoid in ln sigma) or S host values.  Returns the
+        score (B*K,), higher is better; latent_encoder_emb is set to the observations' context.  No tape, no read-back, no
+        synchronisation: the call can be captured into a graph after one eager call has sized the workspace."""
+        im = self.inner_model
+        score, ctx = self._engine(state=state).denoising_score(state, rows, im._goals(goal, False), sigmas, noise, weights=weights,
+                                                               candidates=candidate_count(candidates))
+        im.latent_encoder_emb = ctx
+        return score
+
+    @torch.no_grad()
     def sample_native(self, kind, state, action, goal, sigmas, noise=None, n_steps=None, cond_lambda=None, tree=None, bounds=None,
                       record=False, pin=None, candidates=None, **params):
         """One of the other samplers (``kind``: 'euler', 'heun', 'dpmpp_2m', ... -- the gc_sampling function name without

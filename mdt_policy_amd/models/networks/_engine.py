@@ -689,6 +689,40 @@ class HipEngine:
                                                _ptr(delta), C.byref(info), self._stream())
         return ll, latent, delta, {k: int(getattr(info, k)) for k in ("fevals", "steps", "n_accept", "n_reject")}
 
+    def denoising_score(self, state: dict, x: torch.Tensor, goal: torch.Tensor, sigmas, noise: torch.Tensor, weights=None,
+                        candidates: int = 1):
+        """mdt_denoising_score: the B*K chunks ``x`` -- (B*K, Ta, A) or (B, K, Ta, A) -- scored by their weighted denoising error
+        over the S host levels ``sigmas`` with the noise rows ``noise`` (S, M, Ta, A), as one enqueue on the current stream: no
+        tape, no read-back, capturable once the workspace holds B*K*S*M rows.  ``weights``: None (trapezoid in ln sigma) or S
+        host values.  Returns (score (B*K,), the observations' context (B, Te, D))."""
+        self.sync_params()
+        tok, tok2, B = self._tokens(state)
+        K = candidate_count(candidates)
+        R = B * K
+        if K != 1 or x.dim() == 4:
+            chunk_rows(x, B, K)
+        g = self._goal(goal, B)
+        x_ = self._in(x, (R, self.Ta, self.A))
+        levels = [float(v) for v in (sigmas.detach().reshape(-1).tolist() if torch.is_tensor(sigmas) else sigmas)]
+        S = len(levels)
+        if noise.dim() != 4 or noise.shape[0] != S or tuple(noise.shape[2:]) != (self.Ta, self.A):
+            raise ValueError(f"noise is {tuple(noise.shape)}: {S} levels take ({S}, draws, {self.Ta}, {self.A})")
+        nz = self._in(noise)
+        sig = (C.c_float * max(S, 1))(*levels)
+        w = None
+        if weights is not None:
+            wl = [float(v) for v in (weights.detach().reshape(-1).tolist() if torch.is_tensor(weights) else weights)]
+            if len(wl) != S:
+                raise ValueError(f"weights hold {len(wl)} values, {S} levels take {S}")
+            w = (C.c_float * max(S, 1))(*wl)
+        score = torch.empty((R,), device=self.device, dtype=torch.float32)
+        ctx = torch.empty((B, self.Te, self.D), device=self.device, dtype=torch.float32)
+        self.ctx_generation += 1
+        _lib.call(self.lib.mdt_denoising_score, self.handle, _ptr(tok), _ptr(tok2), _ptr(g), self._modality(state), _ptr(x_), sig, w, S,
+                                                _ptr(nz), int(nz.shape[1]), B, K, _ptr(score), _ptr(ctx), self._stream())
+        self._keep = (tok, tok2, g, x_, nz)  # the kernels that read them are only enqueued
+        return score, ctx
+
     def tape_release(self, tape: int) -> None:
         _lib.check(self.lib.mdt_tape_release(self.handle, tape))
 
