@@ -144,6 +144,39 @@ mdt_status mdt_op_steer_plan(const mdt_sampler_eval *ev, const float *small, con
                              const float *hi, float *rec, float *sig_rows, int64_t N, int64_t R, float sd, float scale,
                              int32_t n_noise, int32_t A, void *stream);
 
+/* The three kernels of mdt_denoising_score (mdt_hip.h; csrc/mdt_score.hip), each through the launch the call makes, on the caller's
+ * buffers.  Dense fp32, 256 threads a workgroup.  B observations, K chunks each, S levels, M noise rows per level; decoder sample
+ * j = ((b S + s) K + k) M + m is chunk r = b K + k at level s with noise row i = s M + m.  sigmas (and weights) are HOST arrays of S
+ * floats and ride in the kernel arguments.  With den2 = sigma^2 + sd^2, c_in = 1 / sqrt(den2):
+ *   mdt_op_score_prep  : over the B S K M Ta decoder rows (sample j, step t), a grid-stride loop over rows * D / 4 threads of at most
+ *                        4096 workgroups.  x0 (B K, Ta, A), noise (S M, Ta, A), WaT (A, D), ba (D) are read;
+ *                        noised (rows, A) = x0[r, t] + sigma_s noise[i, t] (the product rounded, then the sum);
+ *                        y (rows, D) = ba + sum_c (noised[c] c_in(sigma_s)) WaT[c] -- mdt_op_action_embed's arithmetic on `noised`
+ *                        with the rows' sigma: c_in by its expression, the fma chain over c = 0 .. A-1 from the bias --;
+ *                        sig_rows (B S K M) = sigma_s per sample;  ctx_sig (B S) = sigma_s per (b, s), or NULL: not written.
+ *   mdt_op_score_repeat: row i of (B S) <- row i / S of the B rows, for three operands at once: tok -> tok_o (width w1), tok2 ->
+ *                        tok2_o (w2; w2 == 0: neither pointer is used), goal -> goal_o (wg); bits, a grid-stride loop over
+ *                        B S (w1 + w2 + wg) of at most 4096 workgroups.
+ *   mdt_op_score_reduce: score (B K), one workgroup per chunk r, F (B S K M, E) the network's raw output per decoder sample, x0
+ *                        (B K, E), noise (S M, E):
+ *                            q = sigma / den2 x0[r] - sd^2 / den2 noise[i] - sd / sqrt(den2) F[j],
+ *                            score[r] = - sum_s (weights[s] / M) sum_m sum_e q^2.
+ *                        Wave w of four takes the samples i with i % 4 == w in order, lane l the elements e = l, l + 64, ..: a
+ *                        sample's lane sum enters the lane's total by one fma with weights[s] / M; then the xor butterfly over the
+ *                        64 lanes (offsets 32 .. 1) and (p0 + p1) + (p2 + p3) over the waves.  One writer per element, no atomics: a
+ *                        call repeats bit for bit, and a chunk reads no other chunk's rows.
+ * Every output element is written once; inputs are only read.  Refused with MDT_ERR_INVALID_ARG and a text that names the hook and
+ * the field, nothing launched: a null required pointer (all but ctx_sig, and tok2 / tok2_o where w2 == 0); B, K, Ta, A, E, w1 or wg
+ * below 1; S or M outside [1, 64]; D below 4 or no multiple of 4; w2 < 0; sd or a level not finite and > 0; a weight not finite and
+ * >= 0; B * K above 2^31 - 1 (reduce: one workgroup per chunk). */
+mdt_status mdt_op_score_prep(const float *x0, const float *noise, const float *sigmas, int32_t S, int32_t K, int32_t M, int64_t B,
+                             int32_t Ta, int32_t A, int32_t D, float sd, const float *WaT, const float *ba, float *y, float *noised,
+                             float *sig_rows, float *ctx_sig, void *stream);
+mdt_status mdt_op_score_repeat(const float *tok, const float *tok2, const float *goal, int64_t B, int32_t S, int32_t w1, int32_t w2,
+                               int32_t wg, float *tok_o, float *tok2_o, float *goal_o, void *stream);
+mdt_status mdt_op_score_reduce(const float *F, const float *x0, const float *noise, const float *sigmas, const float *weights,
+                               int64_t B, int32_t S, int32_t K, int32_t M, int32_t E, float sd, float *score, void *stream);
+
 /* Measurement hook: bracket every fused-MLP launch of the model-level calls that follow (mdt_sample_ddim, mdt_forward, ...)
  * with a pair of HIP events on its stream; mdt_op_trace_mlp_read waits for them, writes up to `cap` durations in
  * MICROSECONDS (launch order) to `us`, releases the events and returns how many it wrote.  The duration of the dominant

@@ -346,6 +346,9 @@ SYMBOLS = [
     ("mdt_op_steer_first", _I32, [_VP, _VP, _F, _F, _I64, _I64, _VP, _VP, _VP, _VP, _VP]),
     ("mdt_op_steer_plan", _I32, [C.POINTER(SamplerEval), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I64,
                                  _F, _F, _I32, _I32, _VP]),
+    ("mdt_op_score_prep", _I32, [_VP, _VP, _VP, _I32, _I32, _I32, _I64, _I32, _I32, _I32, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("mdt_op_score_repeat", _I32, [_VP, _VP, _VP, _I64, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    ("mdt_op_score_reduce", _I32, [_VP, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _I32, _I32, _F, _VP, _VP]),
     # include/mdt_hip_train.h
     ("mdt_train_prepare", _I32, [_VP]),
     ("mdt_grad_numel", _I64, [_VP]),

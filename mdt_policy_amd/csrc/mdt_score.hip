@@ -14,7 +14,12 @@
 // beside the launches.  No atomics anywhere: every output element has one writer and the sums have one fixed order.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstring>
+#include <initializer_list>
+
 #include "mdt_device.h"
+#include "mdt_hip_debug.h"
 #include "mdt_internal.h"
 #include "mdt_launch.h"
 
@@ -51,12 +56,25 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_score_prep(const float* __res
         const int t = (int)(row - j * Ta);
         const ScoreIndex i = score_index(j, S, K, M);
         const float sg = lv.sigma[i.s];
-        const float cin = 1.0f / sqrtf(sg * sg + sd * sd);
+        float den2;  // both squares rounded, as k_action_embed's compiled form has them (sd * sd hoisted here invites an fma: one
+        {            // rounding fewer, and a c_in -- so a y -- one ulp off the embedding the decoder makes of the same rows).
+                     // edm_c_in itself is left to the compiler's contraction: if a compiler update fuses it there, the two part
+                     // again and only test_score_prep's bit comparison with mdt_op_action_embed shows it -- compiler drift, to
+                     // be settled in edm_c_in, not a regression of this kernel.
+#pragma clang fp contract(off)
+            den2 = sg * sg + sd * sd;
+        }
+        const float cin = 1.0f / sqrtf(den2);
         const float* xr = x0 + ((i.b * K + i.k) * Ta + t) * A;
         const float* nr = noise + (((int64_t)i.s * M + i.m) * Ta + t) * A;
         f32x4 acc = *(const f32x4*)(ba + n);
         for (int c = 0; c < A; ++c) {
-            const float xin = __fadd_rn(xr[c], __fmul_rn(sg, nr[c]));  // two roundings, as x0 + sigma * n is written everywhere else
+            float xin;  // two roundings, as x0 + sigma * n is written everywhere else: __fmul_rn is a plain product to the compiler,
+            {           // which contracts it into the sum unless told otherwise
+#pragma clang fp contract(off)
+                const float p = sg * nr[c];
+                xin = xr[c] + p;
+            }
             if (n == 0) noised[row * A + c] = xin;
             const float xv = xin * cin;
             const f32x4 w = *(const f32x4*)(WaT + (int64_t)c * D + n);
@@ -158,4 +176,109 @@ hipError_t mdt_launch_score_reduce(const float* F, const float* x0, const float*
                                    int K, int M, int E, float sd, float* score, hipStream_t s) {
     if (!score_shape_ok(B, S, K, M) || E < 1 || B * K > 0x7fffffff) return hipErrorInvalidValue;
     return mdt_launch_lds<k_score_reduce>(dim3((unsigned)(B * K)), dim3(SCORE_THREADS), 0, s, F, x0, noise, lv, S, K, M, E, sd, score);
+}
+
+// ------------------------------------------------------------------------------------------------
+// test hooks (mdt_hip_debug.h): the three kernels above on the caller's buffers, each through the launch mdt_denoising_score makes
+// (mdt_launch_score_*).  What the call guarantees by construction is checked here, before anything is launched.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct Named {
+    const void* p;
+    const char* name;
+};
+
+mdt_status hook_nulls(const char* fn, std::initializer_list<Named> ps) {
+    for (const Named& n : ps)
+        if (!n.p) return mdt_fail(MDT_ERR_INVALID_ARG, "%s: null %s", fn, n.name);
+    return MDT_OK;
+}
+
+mdt_status hook_at_least_1(const char* fn, const char* name, int64_t v) {
+    if (v < 1) return mdt_fail(MDT_ERR_INVALID_ARG, "%s: %s is %lld, must be >= 1", fn, name, (long long)v);
+    return MDT_OK;
+}
+
+mdt_status hook_up_to_max(const char* fn, const char* name, int32_t v) {
+    if (v < 1 || v > MDT_SCORE_MAX)
+        return mdt_fail(MDT_ERR_INVALID_ARG, "%s: %s is %d, must be in [1, %d]", fn, name, (int)v, MDT_SCORE_MAX);
+    return MDT_OK;
+}
+
+mdt_status hook_sd(const char* fn, float sd) {
+    if (!std::isfinite(sd) || !(sd > 0.f)) return mdt_fail(MDT_ERR_INVALID_ARG, "%s: sd is %g, must be finite and > 0", fn, (double)sd);
+    return MDT_OK;
+}
+
+// the S levels (and weights, or null: zeros) into the kernel argument; S is in [1, MDT_SCORE_MAX] here
+mdt_status hook_levels(const char* fn, const float* sigmas, const float* weights, int32_t S, mdt_score_levels* lv) {
+    memset(lv, 0, sizeof *lv);
+    for (int i = 0; i < S; ++i) {
+        if (!std::isfinite(sigmas[i]) || !(sigmas[i] > 0.f))
+            return mdt_fail(MDT_ERR_INVALID_ARG, "%s: sigmas[%d] is %g, must be finite and > 0", fn, i, (double)sigmas[i]);
+        lv->sigma[i] = sigmas[i];
+    }
+    for (int i = 0; weights && i < S; ++i) {
+        if (!std::isfinite(weights[i]) || !(weights[i] >= 0.f))
+            return mdt_fail(MDT_ERR_INVALID_ARG, "%s: weights[%d] is %g, must be finite and >= 0", fn, i, (double)weights[i]);
+        lv->weight[i] = weights[i];
+    }
+    return MDT_OK;
+}
+
+}  // namespace
+
+extern "C" mdt_status mdt_op_score_prep(const float* x0, const float* noise, const float* sigmas, int32_t S, int32_t K, int32_t M,
+                                        int64_t B, int32_t Ta, int32_t A, int32_t D, float sd, const float* WaT, const float* ba,
+                                        float* y, float* noised, float* sig_rows, float* ctx_sig, void* stream) {
+    const char* fn = "mdt_op_score_prep";
+    MDT_TRY(hook_nulls(fn, {{x0, "x0"}, {noise, "noise"}, {sigmas, "sigmas"}, {WaT, "WaT"}, {ba, "ba"}, {y, "y"}, {noised, "noised"},
+                            {sig_rows, "sig_rows"}}));
+    MDT_TRY(hook_at_least_1(fn, "B", B));
+    MDT_TRY(hook_at_least_1(fn, "K", K));
+    MDT_TRY(hook_up_to_max(fn, "S", S));
+    MDT_TRY(hook_up_to_max(fn, "M", M));
+    MDT_TRY(hook_at_least_1(fn, "Ta", Ta));
+    MDT_TRY(hook_at_least_1(fn, "A", A));
+    if (D < 4 || (D & 3)) return mdt_fail(MDT_ERR_INVALID_ARG, "%s: D is %d, must be a multiple of 4 and >= 4", fn, (int)D);
+    MDT_TRY(hook_sd(fn, sd));
+    mdt_score_levels lv;
+    MDT_TRY(hook_levels(fn, sigmas, nullptr, S, &lv));
+    LAUNCH(mdt_launch_score_prep(x0, noise, lv, B, S, K, M, Ta, A, D, sd, WaT, ba, y, noised, sig_rows, ctx_sig, (hipStream_t)stream));
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_score_repeat(const float* tok, const float* tok2, const float* goal, int64_t B, int32_t S, int32_t w1,
+                                          int32_t w2, int32_t wg, float* tok_o, float* tok2_o, float* goal_o, void* stream) {
+    const char* fn = "mdt_op_score_repeat";
+    MDT_TRY(hook_nulls(fn, {{tok, "tok"}, {goal, "goal"}, {tok_o, "tok_o"}, {goal_o, "goal_o"}}));
+    MDT_TRY(hook_at_least_1(fn, "B", B));
+    MDT_TRY(hook_up_to_max(fn, "S", S));
+    MDT_TRY(hook_at_least_1(fn, "w1", w1));
+    if (w2 < 0) return mdt_fail(MDT_ERR_INVALID_ARG, "%s: w2 is %d, must be >= 0", fn, (int)w2);
+    MDT_TRY(hook_at_least_1(fn, "wg", wg));
+    if (w2 > 0) MDT_TRY(hook_nulls(fn, {{tok2, "tok2"}, {tok2_o, "tok2_o"}}));
+    LAUNCH(mdt_launch_score_repeat(tok, tok2, goal, tok_o, tok2_o, goal_o, B, S, w1, w2, wg, (hipStream_t)stream));
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_score_reduce(const float* F, const float* x0, const float* noise, const float* sigmas,
+                                          const float* weights, int64_t B, int32_t S, int32_t K, int32_t M, int32_t E, float sd,
+                                          float* score, void* stream) {
+    const char* fn = "mdt_op_score_reduce";
+    MDT_TRY(hook_nulls(fn, {{F, "F"}, {x0, "x0"}, {noise, "noise"}, {sigmas, "sigmas"}, {weights, "weights"}, {score, "score"}}));
+    MDT_TRY(hook_at_least_1(fn, "B", B));
+    MDT_TRY(hook_up_to_max(fn, "S", S));
+    MDT_TRY(hook_at_least_1(fn, "K", K));
+    MDT_TRY(hook_up_to_max(fn, "M", M));
+    MDT_TRY(hook_at_least_1(fn, "E", E));
+    if (B > (int64_t)0x7fffffff / K)
+        return mdt_fail(MDT_ERR_INVALID_ARG, "%s: B * K is %lld * %d, more than 2147483647 chunks (one workgroup each)", fn, (long long)B,
+                        (int)K);
+    MDT_TRY(hook_sd(fn, sd));
+    mdt_score_levels lv;
+    MDT_TRY(hook_levels(fn, sigmas, weights, S, &lv));
+    LAUNCH(mdt_launch_score_reduce(F, x0, noise, lv, B, S, K, M, E, sd, score, (hipStream_t)stream));
+    return MDT_OK;
 }

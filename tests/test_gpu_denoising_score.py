@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from mdt_policy_amd import _lib, configs, synthetic
+from tests.envelope_configs import ENVELOPE
 from tests.guarded import GuardedSet, same_bits
 from tests.helpers import assert_close, cfg_of, load_fixture, params_of
 from tests.long_chunk_configs import LONG_ENVELOPE
@@ -54,7 +55,12 @@ def entry(name):
     if name.startswith("g11_"):  # the training fixtures' decoder variants, with their own weights
         meta, _ = load_fixture(f"g11_grads_{name[4:]}.npz")
         return cfg_of(meta), meta["arch"], False, params_of(meta)
-    for env in (LONG_ENVELOPE, WIDE_ENVELOPE, CTX_ENVELOPE):
+    if name.startswith("g16_proprio_"):  # the proprioceptive fixtures, with their own weights and state_obs
+        meta, _ = load_fixture(name + ".npz")
+        return cfg_of(meta), meta["arch"], True, params_of(meta)
+    if name == "mdtv_default_no_ada":  # sigma as a context token at the shipped width
+        return configs.mdtv_default(use_ada_conditioning=False), "mdtv", False, None
+    for env in (ENVELOPE, LONG_ENVELOPE, WIDE_ENVELOPE, CTX_ENVELOPE):
         if name in env:
             return env[name]["cfg"], env[name]["arch"], env[name]["proprio"], None
     raise KeyError(name)
