@@ -25,7 +25,7 @@ def _hipcc() -> str:
     return exe
 
 
-HEADERS = ["mdt_internal.h", "mdt_route.h", "mdt_route_train.h", "mdt_launch.h", "mdt_handle.h", "mdt_device.h", "mdt_model_types.h", "mdt_tiles.h", "mdt_split_ring.h", "mdt_tall.h", "mdt_ws.h", "mdt_mlp_split.h", "mdt_sampler_plan.h", "mdt_brownian.h", "mdt_loglik.h"]
+HEADERS = ["mdt_internal.h", "mdt_route.h", "mdt_route_train.h", "mdt_launch.h", "mdt_handle.h", "mdt_device.h", "mdt_model_types.h", "mdt_tiles.h", "mdt_split_ring.h", "mdt_tall.h", "mdt_ws.h", "mdt_mlp_split.h", "mdt_sampler_plan.h", "mdt_brownian.h", "mdt_loglik.h", "mdt_edm.h"]
 PUBLIC_HEADERS = ["mdt_hip.h", "mdt_hip_ops.h", "mdt_resampler.h", "mdt_map_pool.h", "mdt_hip_train.h", "mdt_mae.h", "mdt_hip_debug.h"]
 
 

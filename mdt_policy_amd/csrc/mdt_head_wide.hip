@@ -182,7 +182,7 @@ __global__ __launch_bounds__(HW_THREADS) void k_head_wide(mdt_head_args a, mdt_h
             }
         }
         const float sd = a.sigma_data;
-        const float cin_next = edm_c_in(sig_next, sd);
+        const float cin_next = edm_c_in(edm_den2_round_sd(sig_next, sd));
         float cx[MDT_SAMPLER_NREG], cy[MDT_SAMPLER_NREG + 1];
         int push = MDT_PUSH_NONE;
         bool clip = false, rec = false;
@@ -212,10 +212,9 @@ __global__ __launch_bounds__(HW_THREADS) void k_head_wide(mdt_head_args a, mdt_h
             }
             float o = F;
             if (a.mode != MDT_HEAD_RAW) {
-                const float den2 = sigma[r] * sigma[r] + sd * sd;
-                const float c_skip = sd * sd / den2;
-                const float c_out = sigma[r] * sd / sqrtf(den2);
-                float den = F * c_out + xin[r] * c_skip;
+                const float den2 = edm_den2_round_sd(sigma[r], sd);
+                const float c_skip = edm_c_skip(sd, den2), c_out = edm_c_out(sigma[r], sd, den2);
+                float den = edm_denoised_round_both(F, xin[r], c_out, c_skip);
                 if (pn.known != nullptr)  // selects at both ends: no 0 * inf, no sign-of-zero change
                     den = pkp[r] == 0.f ? den : (pkp[r] == 1.f ? pkn[r] : den + pkp[r] * (pkn[r] - den));
                 o = a.mode == MDT_HEAD_DDIM ? ratio * xin[r] + coef * den : den;

@@ -32,6 +32,7 @@
 #include "mdt_launch.h"
 
 #include "mdt_device.h"
+#include "mdt_edm.h"
 
 #define MDT_TILES_TIMING_OWNER  // this translation unit owns the -DMDT_DEBUG_TIMING stamp buffer
 #include "mdt_tiles.h"  // the tile bodies
@@ -1180,14 +1181,9 @@ __global__ __launch_bounds__(256) void k_action_embed(const float* __restrict__ 
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (int64_t)M * n4) return;
     const int m = (int)(idx / n4), n = (int)(idx % n4) * 4;
-    const float cin = sigma != nullptr ? edm_c_in(sigma[(int64_t)(m / rps) * sstride], sd) : 1.0f;
+    const float cin = sigma != nullptr ? edm_c_in(edm_den2_round_both(sigma[(int64_t)(m / rps) * sstride], sd)) : 1.0f;
     f32x4 acc = *(const f32x4*)(ba + n);
-    for (int c = 0; c < A; ++c) {
-        const float xv = x[(int64_t)m * A + c] * cin;
-        const f32x4 w = *(const f32x4*)(WaT + (int64_t)c * D + n);  // weight stored transposed: (A, D)
-        acc.x = fmaf(xv, w.x, acc.x); acc.y = fmaf(xv, w.y, acc.y);
-        acc.z = fmaf(xv, w.z, acc.z); acc.w = fmaf(xv, w.w, acc.w);
-    }
+    for (int c = 0; c < A; ++c) acc = action_embed_step(acc, x[(int64_t)m * A + c], cin, WaT + (int64_t)c * D + n);
     *(f32x4*)(y + (int64_t)m * D + n) = acc;
 }
 
@@ -1215,7 +1211,7 @@ hipError_t mdt_launch_action_embed(const float* x, const float* sigma, int64_t s
 // The once-per-call scalar work of the DDIM sampler as ONE launch (round 5; it was a host-to-device copy of the schedule +
 // k_ddim_steps + k_sigma_emb + k_action_embed: four dependent ~4.5 us launches in front of every sampler call, a tenth of a
 // rollout-sized call).  A host schedule travels in the kernel arguments; a device schedule is read in place.  Blocks
-// [0, n_act) embed the first noisy actions (k_action_embed's arithmetic with c_in(sigma_0)), blocks [n_act, n_act + n_emb) write
+// [0, n_act) embed the first noisy actions (action_embed_step over the A inputs, with c_in(sigma_0)), blocks [n_act, n_act + n_emb) write
 // the sinusoidal sigma embeddings of all steps (k_sigma_emb's), the last block the per-step DDIM scalars -- steps[i] =
 // {sigma_{i+1}/sigma_i as exp(-t')/exp(-t), -expm1(-h), sigma_{i+1}, sigma_i} with t = -ln sigma, h = t' - t (gc_sampling.py:946-950,
 // fp32 like the reference's tensors) -- each from the schedule itself, so nothing in the launch depends on anything else in it, and every value has the bits the
@@ -1235,14 +1231,9 @@ __global__ __launch_bounds__(256) void k_sample_prep(const float* __restrict__ s
         if (idx >= (int64_t)M * n4) return;
         const int m = (int)(idx / n4), n = (int)(idx % n4) * 4;
         const int mx = DUP && m >= Mx ? m - Mx : m;
-        const float cin = edm_c_in(sig_dev ? sig_dev[0] : sv.s[0], sd);
+        const float cin = edm_c_in(edm_den2_round_sigma(sig_dev ? sig_dev[0] : sv.s[0], sd));
         f32x4 acc = *(const f32x4*)(ba + n);
-        for (int c = 0; c < A; ++c) {
-            const float xv = x[(int64_t)mx * A + c] * cin;
-            const f32x4 w = *(const f32x4*)(WaT + (int64_t)c * D + n);
-            acc.x = fmaf(xv, w.x, acc.x); acc.y = fmaf(xv, w.y, acc.y);
-            acc.z = fmaf(xv, w.z, acc.z); acc.w = fmaf(xv, w.w, acc.w);
-        }
+        for (int c = 0; c < A; ++c) acc = action_embed_step(acc, x[(int64_t)mx * A + c], cin, WaT + (int64_t)c * D + n);
         *(f32x4*)(y + (int64_t)m * D + n) = acc;
     } else if (b < n_act + n_emb) {
         const int half = D >> 1;
@@ -1342,7 +1333,7 @@ __global__ __launch_bounds__(256) void k_sampler_first(const mdt_sampler_plan_t*
     const bool dup = DUP && m >= Mx;
     const int mx = dup ? m - Mx : m;
     const int64_t nel = (int64_t)Mx * A;
-    const float cin = edm_c_in(plan->e[0].sigma, sd);
+    const float cin = edm_c_in(edm_den2_round_sigma(plan->e[0].sigma, sd));
     const int row = (noise && plan->y0_noise < n_noise) ? plan->y0_noise : -1;  // a row outside the buffer reads as 0
     const float cn = plan->y0_cn;
     f32x4 acc = *(const f32x4*)(ba + n);
@@ -1354,10 +1345,7 @@ __global__ __launch_bounds__(256) void k_sampler_first(const mdt_sampler_plan_t*
             y0[k] = v;
             for (int h = 0; h < 4; ++h) hist[h * nel + k] = 0.f;
         }
-        const float xv = v * cin;
-        const f32x4 w = *(const f32x4*)(WaT + (int64_t)c * D + n);
-        acc.x = fmaf(xv, w.x, acc.x); acc.y = fmaf(xv, w.y, acc.y);
-        acc.z = fmaf(xv, w.z, acc.z); acc.w = fmaf(xv, w.w, acc.w);
+        acc = action_embed_step(acc, v, cin, WaT + (int64_t)c * D + n);
     }
     *(f32x4*)(y + (int64_t)m * D + n) = acc;
 }
@@ -1732,7 +1720,7 @@ __global__ __launch_bounds__(256) void k_loss_partial(const float* __restrict__ 
                                                       int n, int per_sample, int chunk, float* __restrict__ part) {
     __shared__ float red[4];
     const int lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
-    const float sd2 = sd * sd;
+    const float sd2 = sd * sd;  // hoisted by hand: c_skip below is edm_c_skip's expression on it
     float s = 0.f;
     for (int i0 = lo + threadIdx.x; i0 < hi; i0 += 1024) {
         float f[4], a[4], x[4], sg[4];
@@ -1743,7 +1731,7 @@ __global__ __launch_bounds__(256) void k_loss_partial(const float* __restrict__ 
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const float den2 = sg[u] * sg[u] + sd2;
+            const float den2 = edm_den2_round_sd(sg[u], sd);
             const float c_skip = sd2 / den2, inv_c_out = sqrtf(den2) / (sg[u] * sd);
             const float d = f[u] - (a[u] - c_skip * x[u]) * inv_c_out;
             if (i0 + 256 * u < hi) s = fmaf(d, d, s);

@@ -5,7 +5,7 @@
 // b at level s with noise row m: consecutive samples share a context (S K M of them the observation's; where sigma is a context
 // token K M of them the context of (b, s)), and the M draws of a chunk at one level lie side by side.
 //   k_score_prep    the decoder's input: x = x0 + sigma_s n[s, m] per element, the rows' sigma, and the action embedding of
-//                   x c_in(sigma_s) (k_action_embed's arithmetic: c_in by edm_c_in's expression, then the fma chain over A from the bias)
+//                   x c_in(sigma_s), by the functions k_action_embed calls (mdt_edm.h)
 //   k_score_repeat  where sigma is a context token: each observation's encoder inputs S times (context b S + s)
 //   k_score_reduce  the score from the network's raw output F, in the residual form
 //                       q = sigma / (sigma^2 + sd^2) x0 - c_skip n - sd / sqrt(sigma^2 + sd^2) F
@@ -19,6 +19,7 @@
 #include <initializer_list>
 
 #include "mdt_device.h"
+#include "mdt_edm.h"
 #include "mdt_hip_debug.h"
 #include "mdt_internal.h"
 #include "mdt_launch.h"
@@ -56,15 +57,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_score_prep(const float* __res
         const int t = (int)(row - j * Ta);
         const ScoreIndex i = score_index(j, S, K, M);
         const float sg = lv.sigma[i.s];
-        float den2;  // both squares rounded, as k_action_embed's compiled form has them (sd * sd hoisted here invites an fma: one
-        {            // rounding fewer, and a c_in -- so a y -- one ulp off the embedding the decoder makes of the same rows).
-                     // edm_c_in itself is left to the compiler's contraction: if a compiler update fuses it there, the two part
-                     // again and only test_score_prep's bit comparison with mdt_op_action_embed shows it -- compiler drift, to
-                     // be settled in edm_c_in, not a regression of this kernel.
-#pragma clang fp contract(off)
-            den2 = sg * sg + sd * sd;
-        }
-        const float cin = 1.0f / sqrtf(den2);
+        const float cin = edm_c_in(edm_den2_round_both(sg, sd));
         const float* xr = x0 + ((i.b * K + i.k) * Ta + t) * A;
         const float* nr = noise + (((int64_t)i.s * M + i.m) * Ta + t) * A;
         f32x4 acc = *(const f32x4*)(ba + n);
@@ -76,10 +69,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_score_prep(const float* __res
                 xin = xr[c] + p;
             }
             if (n == 0) noised[row * A + c] = xin;
-            const float xv = xin * cin;
-            const f32x4 w = *(const f32x4*)(WaT + (int64_t)c * D + n);
-            acc.x = fmaf(xv, w.x, acc.x); acc.y = fmaf(xv, w.y, acc.y);
-            acc.z = fmaf(xv, w.z, acc.z); acc.w = fmaf(xv, w.w, acc.w);
+            acc = action_embed_step(acc, xin, cin, WaT + (int64_t)c * D + n);
         }
         *(f32x4*)(y + row * D + n) = acc;
         if (n == 0 && t == 0) {
@@ -117,9 +107,9 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_score_reduce(const float* __r
     const int64_t r = blockIdx.x, b = r / K;
     const int k = (int)(r - b * K);
     if (tid < S) {
-        const float sg = lv.sigma[tid], den2 = sg * sg + sd * sd;
+        const float sg = lv.sigma[tid], den2 = edm_den2_round_both(sg, sd);
         c_x[tid] = sg / den2;
-        c_n[tid] = sd * sd / den2;
+        c_n[tid] = edm_c_skip(sd, den2);
         c_f[tid] = sd / sqrtf(den2);
         c_w[tid] = lv.weight[tid] / (float)M;
     }

@@ -24,6 +24,7 @@
 #include "mdt_internal.h"
 #include "mdt_launch.h"
 #include "mdt_device.h"
+#include "mdt_edm.h"
 #include "mdt_loglik.h"
 #include "mdt_sampler_plan.h"
 #include "mdt_tiles.h"
@@ -49,10 +50,10 @@ __global__ __launch_bounds__(STEER_THREADS) void k_steer_seed(const float* __res
                                                               const float* __restrict__ known, const float* __restrict__ weight,
                                                               float sg, float sd, int64_t N, float* __restrict__ D,
                                                               float* __restrict__ e, float* __restrict__ dF) {
-    const float den2 = sg * sg + sd * sd;
-    const float c_skip = sd * sd / den2, c_out = sg * sd / sqrtf(den2);
+    const float den2 = edm_den2_round_sd(sg, sd);
+    const float c_skip = edm_c_skip(sd, den2), c_out = edm_c_out(sg, sd, den2);
     for (int64_t i = (int64_t)blockIdx.x * STEER_THREADS + threadIdx.x; i < N; i += (int64_t)gridDim.x * STEER_THREADS) {
-        const float d = fmaf(F[i], c_out, x[i] * c_skip);
+        const float d = edm_denoised(F[i], x[i], c_out, c_skip);
         const float ev = weight[i] * (known[i] - d);
         D[i] = d;
         e[i] = ev;
@@ -70,8 +71,8 @@ __global__ __launch_bounds__(STEER_THREADS) void k_steer_step(const float* __res
                                                               float scale, float ratio, float coef, const float* __restrict__ lo,
                                                               const float* __restrict__ hi, int A, float sigma_next, int64_t N,
                                                               int64_t R, float* x_out, float* __restrict__ sig_rows) {
-    const float den2 = sg * sg + sd * sd;
-    const float c_in = 1.0f / sqrtf(den2), c_skip = sd * sd / den2;
+    const float den2 = edm_den2_round_sd(sg, sd);
+    const float c_in = edm_c_in(den2), c_skip = edm_c_skip(sd, den2);
     for (int64_t i = (int64_t)blockIdx.x * STEER_THREADS + threadIdx.x; i < N + R; i += (int64_t)gridDim.x * STEER_THREADS) {
         if (i < N) {
             const float g = fmaf(small[i], c_in, e[i] * c_skip);
@@ -136,8 +137,8 @@ struct SteerPlanArgs {
 // shift -- and sig_rows = sigma_next.  X / x_out, Y / y_out and the history slots are read and written in place: each element by
 // its own thread, every read before the write, so none of them is __restrict__.
 __global__ __launch_bounds__(STEER_THREADS) void k_steer_plan(SteerPlanArgs a) {
-    const float sg = a.ev.sigma, den2 = sg * sg + a.sd * a.sd;
-    const float c_in = 1.0f / sqrtf(den2), c_skip = a.sd * a.sd / den2;
+    const float sg = a.ev.sigma, den2 = edm_den2_round_sd(sg, a.sd);
+    const float c_in = edm_c_in(den2), c_skip = edm_c_skip(a.sd, den2);
     float cx[MDT_SAMPLER_NREG], cy[MDT_SAMPLER_NREG + 1];
 #pragma unroll
     for (int k = 0; k < MDT_SAMPLER_NREG; ++k) { cx[k] = a.ev.cx[k]; cy[k] = a.ev.cy[k]; }

@@ -16,6 +16,7 @@
 
 #include "mdt_internal.h"
 #include "mdt_device.h"
+#include "mdt_edm.h"
 #include "mdt_split_ring.h"   // SplitRing / split_phase: attn_xattn_tile's pair form
 
 // XCD-aware block id: the dispatcher places block b on XCD b % 8 (speed-only assumption); give every XCD a
@@ -1428,8 +1429,6 @@ __device__ __forceinline__ void attn_tile(const mdt_attn_args& a, const float* _
     MDT_TS(4)
 }
 
-__device__ __forceinline__ float edm_c_in(float sigma, float sd) { return 1.0f / sqrtf(sigma * sigma + sd * sd); }
-
 // ------------------------------------------------------------------------------------------------
 // One element of a sampler plan's update (MDT_HEAD_PLAN; mdt_sampler_plan.h), shared by head_rows (A <= 16) and the tiled head of
 // mdt_head_wide.hip (A 17 .. 64): element k = row * A + column of the (M, A) operands, the evaluation's input Y, the denoised
@@ -1633,7 +1632,7 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
         }
     wave_sum_n<RW * AMAX>(res);
     const float sd = a.sigma_data;
-    const float cin_next = edm_c_in(sig_next, sd);
+    const float cin_next = edm_c_in(edm_den2_round_sd(sig_next, sd));
     if constexpr (GUIDE) {
 #pragma unroll
         for (int c = 0; c < AMAX; ++c) {
@@ -1643,6 +1642,9 @@ __device__ __forceinline__ void head_rows(const mdt_head_args& a, int base, int 
     }
 #pragma unroll
     for (int r = 0; r < RS; ++r) {
+        // Not mdt_edm.h's functions: these five lines compile to edm_den2_round_sd and, in the unguided heads, to
+        // edm_denoised_round_both, but the guided heads fuse the combine of columns 1.. as fma(x, c_skip, rn(F c_out)), and the
+        // vectoriser drops that as soon as den2 alone comes from the header -- a change of bits.
         const float den2 = sigma[r] * sigma[r] + sd * sd;
         const float c_skip = sd * sd / den2;
         const float c_out = sigma[r] * sd / sqrtf(den2);

@@ -18,6 +18,7 @@
 #include "mdt_launch.h"
 
 #include "mdt_device.h"
+#include "mdt_edm.h"
 #include "mdt_split_ring.h"   // split_scheme, the order rule of the split products (k_gemm_tn_split)
 
 // ------------------------------------------------------------------------------------------------
@@ -1367,9 +1368,9 @@ __global__ void k_loss_grad(const float* __restrict__ F, const float* __restrict
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float sg = sigma[i / per_sample];
-    const float den2 = sg * sg + sd * sd;
-    const float c_skip = sd * sd / den2, c_out = sg * sd / sqrtf(den2);
-    const float tgt = (act[i] - c_skip * noised[i]) / c_out;
+    const float den2 = edm_den2_round_sd(sg, sd);
+    const float c_skip = edm_c_skip(sd, den2), c_out = edm_c_out(sg, sd, den2);
+    const float tgt = (act[i] - noised[i] * c_skip) / c_out;
     dF[i] = (gscale ? *gscale : 1.f) * 2.f * (F[i] - tgt) / (float)n;
 }
 hipError_t mdt_launch_loss_grad(const float* F, const float* act, const float* noised, const float* sigma, float sd,
@@ -1388,9 +1389,9 @@ __global__ void k_denoise_seed(const float* __restrict__ F, const float* __restr
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float sg = sigma[i / per_sample];
-    const float den2 = sg * sg + sd * sd;
-    const float c_skip = sd * sd / den2, c_out = sg * sd / sqrtf(den2);
-    if (den) den[i] = fmaf(F[i], c_out, x[i] * c_skip);
+    const float den2 = edm_den2_round_sd(sg, sd);
+    const float c_skip = edm_c_skip(sd, den2), c_out = edm_c_out(sg, sd, den2);
+    if (den) den[i] = edm_denoised(F[i], x[i], c_out, c_skip);
     if (g) dF[i] = c_out * g[i];
 }
 hipError_t mdt_launch_denoise_seed(const float* F, const float* x, const float* sigma, const float* g, float sd, int64_t n,
@@ -1404,8 +1405,8 @@ __global__ void k_denoise_finish(const float* __restrict__ dxin, const float* __
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float sg = sigma[i / per_sample];
-    const float den2 = sg * sg + sd * sd;
-    out[i] = fmaf(dxin[i], 1.0f / sqrtf(den2), g[i] * (sd * sd / den2));
+    const float den2 = edm_den2_round_both(sg, sd);
+    out[i] = fmaf(dxin[i], edm_c_in(den2), g[i] * edm_c_skip(sd, den2));
 }
 hipError_t mdt_launch_denoise_finish(const float* dxin, const float* sigma, const float* g, float sd, int64_t n, int per_sample,
                                      float* out, hipStream_t s) {
@@ -1430,8 +1431,8 @@ __global__ __launch_bounds__(256) void k_denoise_dsigma(const float* __restrict_
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
     const float sg = sigma[b];
-    const float den2 = sg * sg + sd * sd;
-    const float r = 1.0f / sqrtf(den2);
+    const float den2 = edm_den2_round_sd(sg, sd);
+    const float r = edm_c_in(den2);
     const float dskip = -2.0f * sg * sd * sd / (den2 * den2), dout = sd * sd * sd * r / den2, din = -sg / den2;
     const int64_t o = (int64_t)b * per_sample;
     float acc = 0.f;
@@ -1567,7 +1568,7 @@ __global__ void k_scaled_input(const float* __restrict__ x, const float* __restr
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float sg = sigma[i / per_sample];
-    out[i] = x[i] / sqrtf(sg * sg + sd * sd);
+    out[i] = x[i] / sqrtf(edm_den2_round_both(sg, sd));
 }
 hipError_t mdt_launch_scaled_input(const float* x, const float* sigma, float sd, int64_t n, int per_sample, float* out,
                                    hipStream_t s) {
