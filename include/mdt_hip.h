@@ -404,6 +404,58 @@ mdt_status mdt_denoising_score(mdt_model *m, const float *tokens, const float *t
                                const float *noise, int32_t draws, int64_t batch, int32_t candidates, float *score, float *ctx_out,
                                void *stream);
 
+/* Sample, score and select in ONE enqueue: the mdt_sample*_multi call of each family, mdt_denoising_score on its chunks and the
+ * per-observation selection, with nothing read back -- the replan-and-select loop of a controller as one call, capturable like its
+ * parts.  Each entry is its *_multi entry with `out` replaced by `best` (B, Ta, A), the winning chunk of every observation, and a
+ * `select` argument in front of `stream`:
+ *   sigmas_host, weights_host, n_levels, noise, draws : the score's levels, weights (NULL: the trapezoid rule in ln sigma), and
+ *            noise rows (n_levels, draws, Ta, A), as mdt_denoising_score takes them
+ *   chunks : (B * K, Ta, A), all the sampled chunks -- what the *_multi entry writes to `out`, bit for bit
+ *   scores : (B * K), what mdt_denoising_score gives on those chunks
+ *   index  : (B) int32, per observation the k of the largest score: ties go to the lowest k; a NaN score loses to every other,
+ *            -Inf included; an observation whose scores are all NaN selects 0.  (Exactly gc_sampling.best_candidates' index, whose
+ *            torch.nan_to_num reads +Inf as the largest finite float: +Inf ties with FLT_MAX.)  best[b] = chunks[b * K + index[b]].
+ * `opts` means what it means in the *_multi entry -- guidance, bounds, pin, record, tree -- and shapes the SAMPLING only: the score
+ * is that of the unguided, unpinned, unclamped conditional model on the final chunks, as mdt_denoising_score's is.  ctx_out is the
+ * sampler's.  candidates == 1 is legal: best is the chunk, index 0.
+ * Where the context does not depend on sigma (use_ada_conditioning = 1, the NoiseBlock decoder) the score phase runs no encoder: it
+ * reads the context, the cross K|V rows and the folded operands the sampler's prefix left for the B observations (a guided call's
+ * conditional half).  The unguided call's scores then have mdt_denoising_score's bits; a guided call's encoder ran 2B contexts
+ * where the stand-alone scorer runs B, which may route its products differently.  With sigma as a context token the score phase
+ * stages and encodes its B * n_levels contexts as mdt_denoising_score does.
+ * The workspace: max(the sampler's decoder samples, B * K * n_levels * draws), reserved once before the first launch; a caller who
+ * captures the call makes one eager call, or mdt_reserve of that maximum, first.
+ * MDT_ERR_INVALID_ARG before anything is enqueued, the message naming the entry and the field: a NULL select or a select.size that is
+ * not sizeof(mdt_select_spec); a NULL best, chunks, scores, index, sigmas_host or noise; whatever mdt_denoising_score refuses of
+ * n_levels, draws, the levels, the weights and batch * candidates * n_levels * draws; whatever the *_multi entry refuses.
+ * mdt_sample_dpm_adaptive and the steered calls have no such form. */
+typedef struct mdt_select_spec {
+    int32_t size;                             /* sizeof(mdt_select_spec): lets the struct grow                                  */
+    const float *sigmas_host, *weights_host;  /* (S,) host; weights NULL: trapezoid rule in ln sigma, as mdt_denoising_score    */
+    int32_t n_levels;
+    const float *noise; int32_t draws;        /* (S, M, Ta, A) device                                                           */
+    float *chunks;                            /* (B*K, Ta, A) device, required: all sampled chunks                              */
+    float *scores;                            /* (B*K) device, required                                                         */
+    int32_t *index;                           /* (B) device, required                                                           */
+} mdt_select_spec;
+mdt_status mdt_sample_select(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                             const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_host,
+                             int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, int32_t candidates, float *best,
+                             float *ctx_out, const mdt_sample_opts *opts, const mdt_select_spec *select, void *stream);
+mdt_status mdt_sample_dev_select(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                                 const float *x_T, int32_t kind, const mdt_sampler_params *params, const float *sigmas_dev,
+                                 int32_t n_steps, const float *noise, int32_t n_noise, int64_t batch, int32_t candidates,
+                                 float *best, float *ctx_out, const mdt_sample_opts *opts, const mdt_select_spec *select,
+                                 void *stream);
+mdt_status mdt_sample_ddim_select(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                                  const float *x_T, const float *sigmas_host, int32_t n_steps, int64_t batch, int32_t candidates,
+                                  float *best, float *ctx_out, const mdt_sample_opts *opts, const mdt_select_spec *select,
+                                  void *stream);
+mdt_status mdt_sample_ddim_dev_select(mdt_model *m, const float *tokens, const float *tokens2, const float *goal, int32_t modality,
+                                      const float *x_T, const float *sigmas_dev, int32_t n_steps, int64_t batch,
+                                      int32_t candidates, float *best, float *ctx_out, const mdt_sample_opts *opts,
+                                      const mdt_select_spec *select, void *stream);
+
 /* sample_dpm_adaptive (eta = 0): DPM-Solver-12 / -23 with the PID step-size control of _StepControl, as ONE blocking call.
  * Every attempted step runs its 2 or 3 denoiser evaluations; the head of the last one writes both the order-k ("high") and the
  * order-(k-1) ("low") result, one small kernel writes per-workgroup partial sums of the scaled error, and the host reads them

@@ -177,6 +177,17 @@ mdt_status mdt_op_score_repeat(const float *tok, const float *tok2, const float 
 mdt_status mdt_op_score_reduce(const float *F, const float *x0, const float *noise, const float *sigmas, const float *weights,
                                int64_t B, int32_t S, int32_t K, int32_t M, int32_t E, float sd, float *score, void *stream);
 
+/* The selection kernel of mdt_sample*_select (mdt_hip.h; csrc/mdt_score.hip), through the launch the call makes, on the caller's
+ * buffers: scores (B K) and chunks (B K, E) are read; index (B) int32 and best (B, E) are written, each element once.  One workgroup
+ * of 256 threads per observation: index[b] is the k that gc_sampling.best_candidates(chunks, scores, K) gives -- with the key of a
+ * score being the score, NaN read as -Inf, +Inf as the largest finite float and -Inf as the lowest (torch.nan_to_num(nan=-inf)), the
+ * largest key wins and ties go to the lowest k; K NaN scores select 0 -- and best[b] = chunks[b K + index[b]], bits.  Lane t scans
+ * k = t, t + 256, ..; the wave's 64 lanes and then the four waves reduce (key, k) in a fixed order; no atomics: a call repeats bit
+ * for bit.  Refused with MDT_ERR_INVALID_ARG, "mdt_op_score_select: ..." naming the field, nothing launched: a null pointer; B, K
+ * or E below 1; B above 2^31 - 1. */
+mdt_status mdt_op_score_select(const float *scores, const float *chunks, int64_t B, int32_t K, int32_t E, float *best, int32_t *index,
+                               void *stream);
+
 /* Measurement hook: bracket every fused-MLP launch of the model-level calls that follow (mdt_sample_ddim, mdt_forward, ...)
  * with a pair of HIP events on its stream; mdt_op_trace_mlp_read waits for them, writes up to `cap` durations in
  * MICROSECONDS (launch order) to `us`, releases the events and returns how many it wrote.  The duration of the dominant

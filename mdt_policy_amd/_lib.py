@@ -104,6 +104,14 @@ class SampleOpts(C.Structure):
                 ("tree", C.POINTER(BrownianSource)), ("pin_known", C.c_void_p), ("pin_keep", C.c_void_p)]
 
 
+class SelectSpec(C.Structure):
+    """mdt_select_spec (include/mdt_hip.h): the score and the selection of mdt_sample_select / _dev_select / mdt_sample_ddim_select /
+    _ddim_dev_select."""
+    _fields_ = [("size", C.c_int32), ("sigmas_host", C.POINTER(C.c_float)), ("weights_host", C.POINTER(C.c_float)),
+                ("n_levels", C.c_int32), ("noise", C.c_void_p), ("draws", C.c_int32), ("chunks", C.c_void_p),
+                ("scores", C.c_void_p), ("index", C.c_void_p)]
+
+
 class SamplerPlan(C.Structure):
     """mdt_sampler_plan_t (include/mdt_hip.h)."""
     _fields_ = [("n_evals", C.c_int32), ("n_noise", C.c_int32), ("y0_noise", C.c_int32), ("y0_cn", C.c_float),
@@ -266,6 +274,15 @@ SYMBOLS = [
     # chunks scored by their denoising error: host levels and weights (or NULL), device noise rows (n_levels, draws, Ta, A)
     ("mdt_denoising_score", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32, _VP, _I32, _I64,
                                    _I32, _VP, _VP, _VP]),
+    # the *_multi calls with `out` = the best chunk per observation and the score / selection spec in front of `stream`
+    ("mdt_sample_select", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, _VP, _I32,
+                                 _I64, _I32, _VP, _VP, C.POINTER(SampleOpts), C.POINTER(SelectSpec), _VP]),
+    ("mdt_sample_dev_select", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, C.POINTER(SamplerParams), _VP, _I32, _VP, _I32, _I64, _I32,
+                                     _VP, _VP, C.POINTER(SampleOpts), C.POINTER(SelectSpec), _VP]),
+    ("mdt_sample_ddim_select", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.POINTER(C.c_float), _I32, _I64, _I32, _VP, _VP,
+                                      C.POINTER(SampleOpts), C.POINTER(SelectSpec), _VP]),
+    ("mdt_sample_ddim_dev_select", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _I32, _I64, _I32, _VP, _VP, C.POINTER(SampleOpts),
+                                          C.POINTER(SelectSpec), _VP]),
     ("mdt_sampler_plan", _I32, [_I32, C.POINTER(SamplerParams), C.POINTER(C.c_float), _I32, C.POINTER(SamplerPlan)]),
     ("mdt_sample_dpm_adaptive", _I32, [_VP, _VP, _VP, _VP, _I32, _VP, C.c_float, C.c_float, C.POINTER(DpmAdaptiveParams), _I64,
                                        _VP, _VP, C.POINTER(DpmAdaptiveInfo), _VP]),
@@ -349,6 +366,7 @@ SYMBOLS = [
     ("mdt_op_score_prep", _I32, [_VP, _VP, _VP, _I32, _I32, _I32, _I64, _I32, _I32, _I32, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("mdt_op_score_repeat", _I32, [_VP, _VP, _VP, _I64, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
     ("mdt_op_score_reduce", _I32, [_VP, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _I32, _I32, _F, _VP, _VP]),
+    ("mdt_op_score_select", _I32, [_VP, _VP, _I64, _I32, _I32, _VP, _VP, _VP]),
     # include/mdt_hip_train.h
     ("mdt_train_prepare", _I32, [_VP]),
     ("mdt_grad_numel", _I64, [_VP]),

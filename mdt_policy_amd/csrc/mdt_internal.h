@@ -240,6 +240,9 @@ hipError_t mdt_launch_score_repeat(const float* tok, const float* tok2, const fl
                                    int64_t B, int S, int w1, int w2, int wg, hipStream_t s);
 hipError_t mdt_launch_score_reduce(const float* F, const float* x0, const float* noise, const mdt_score_levels& lv, int64_t B, int S,
                                    int K, int M, int E, float sd, float* score, hipStream_t s);
+// mdt_sample*_select: per observation the index best_candidates gives on score (B K) and that chunk of chunks (B K, E) -> best (B, E)
+hipError_t mdt_launch_score_select(const float* score, const float* chunks, int64_t B, int K, int E, float* best, int32_t* index,
+                                   hipStream_t s);
 hipError_t mdt_launch_noise_input(const float* act, const float* noise, const float* sigma, float* noised, int64_t n,
                                   int per_sample, hipStream_t s);
 constexpr int MDT_LOSS_PARTS = 1024;   // floats of scratch mdt_launch_loss_reduce wants (`part`)

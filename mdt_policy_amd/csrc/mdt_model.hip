@@ -1196,6 +1196,17 @@ static mdt_status read_opts(const char* who, const mdt_sample_opts* opts, mdt_sa
     return MDT_OK;
 }
 
+// The select phase of a *_select entry (include/mdt_hip.h), as read_select leaves it: the score's levels and weights, its noise rows
+// (S, M, Ta, A), and where the scores (B K), the winners' indices (B) and the winning chunks (B, Ta, A) go.  All the chunks go to
+// the request's `out`.
+struct SelectPhase {
+    mdt_score_levels lv;
+    int32_t S, M;
+    const float* noise;
+    float *best, *scores;
+    int32_t* index;
+};
+
 // One sampler call.  The first ten fields are the arguments every entry takes; the rest default to the plain call.
 struct SamplerRequest {
     const char* who;  // the entry point (error messages)
@@ -1217,6 +1228,7 @@ struct SamplerRequest {
     bool tree_entry = false;    // mdt_sample_sde_tree*: o.tree is the entry's `tree` argument, refused when null
     int32_t cand = 1;           // a *_multi entry: action chunks per observation (x_T, out, the noise rows, the pin, the record and the
     bool cand_given = false;    // tree's seeds are per chunk, batch * cand of them; tokens, goal and ctx_out per observation)
+    const SelectPhase* sel = nullptr;  // a *_select entry: `out` holds all the chunks, which are then scored and the best selected
 
     SamplerRequest& schedule(const float* levels, bool dev, int32_t n) { sigmas = levels; sigmas_dev = dev; n_steps = n; return *this; }
     SamplerRequest& plan(int32_t k, const mdt_sampler_params* p, const float* rows, int32_t n) {
@@ -1229,6 +1241,7 @@ struct SamplerRequest {
     }
     bool guided() const { return weight_given || o.cond_lambda != 1.f; }
     int64_t chunks() const { return batch * cand; }  // (after sampler_check)
+    int64_t score_rows() const { return sel ? chunks() * sel->S * sel->M : 0; }  // the select phase's decoder samples (after select_check)
     const float* host_sigmas() const { return sigmas_dev ? nullptr : sigmas; }
     const float* dev_sigmas() const { return sigmas_dev ? sigmas : nullptr; }
 };
@@ -1282,7 +1295,9 @@ static mdt_status sampler_open(mdt_model* m, const SamplerRequest& a, mdt_guide 
     const int64_t nctx = gd.on ? 2 * a.batch : a.batch;
     *c = {a.tokens, a.tokens2, a.goal, a.modality, a.batch, nctx, a.cand, a.chunks(), nctx * a.cand, a.ctx_out, a.ctx_out, gd,
           (hipStream_t)a.stream, {a.o.pin_known, a.o.pin_keep}};
-    MDT_TRY(mdt_reserve(m, c->nb));
+    // once, in front of the first launch: a select phase reads what the prefix leaves in the per-context buffers, and a growth
+    // between the two would move them
+    MDT_TRY(mdt_reserve(m, std::max(c->nb, a.score_rows())));
     if (!gd.on) return MDT_OK;
     const int w1 = guide_w1(m), w2 = a.tokens2 ? guide_w2(m) : 0;
     LAUNCH(mdt_launch_guide_stage(a.tokens, a.tokens2, a.goal, m->g_tok, m->g_tok2, m->g_goal, (int)a.batch, w1, w2, m->G, c->s));
@@ -1299,6 +1314,15 @@ static mdt_status sampler_close(mdt_model* m, const SamplerCall& c) {
     return MDT_OK;
 }
 
+// A *_select entry: the score's row count, checked in front of a family's own checks, and the phase behind sampler_close (below, beside
+// mdt_denoising_score, whose launches it makes).
+static mdt_status select_check(const mdt_model* m, const SamplerRequest& a);
+static mdt_status select_phase(mdt_model* m, const SamplerRequest& a);
+static mdt_status sampler_finish(mdt_model* m, const SamplerRequest& a, const SamplerCall& c) {
+    MDT_TRY(sampler_close(m, c));
+    return a.sel ? select_phase(m, a) : MDT_OK;
+}
+
 // gd.on (guided): the encoder runs 2B contexts and the decoder twice the chunks, the head combines the halves and updates the chunks' state
 // Of the options DDIM takes cond_lambda and the pin; lo / hi are accepted and not read (the reference's DDIM never clips), record
 // and tree are refused.
@@ -1307,6 +1331,7 @@ static mdt_status sample_ddim_impl(mdt_model* m, const SamplerRequest& a) {
     if (a.o.tree) return fail(MDT_ERR_INVALID_ARG, "%s: opts.tree is the noise of MDT_SAMPLER_DPMPP_SDE; DDIM draws none", a.who);
     const int32_t n_steps = a.n_steps;
     mdt_guide gd;
+    MDT_TRY(select_check(m, a));
     MDT_TRY(sampler_check(m, a, "mdt_sample_ddim", a.sigmas != nullptr, &gd));
     if (n_steps < 1 || n_steps > MAX_STEPS) return fail(MDT_ERR_INVALID_ARG, "n_steps must be 1..%d", MAX_STEPS);
     SamplerCall c;
@@ -1339,7 +1364,7 @@ static mdt_status sample_ddim_impl(mdt_model* m, const SamplerRequest& a) {
         h.step = m->steps + 4 * i;
         MDT_TRY(run_eval(m, V, c.nb, cond_row(m, i), 0, h, nullptr, last ? nullptr : sigma + 4, c.s, gd, c.pin, c.cand));
     }
-    return sampler_close(m, c);
+    return sampler_finish(m, a, c);
 }
 
 extern "C" mdt_status mdt_sample_ddim(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
@@ -1412,24 +1437,17 @@ extern "C" mdt_status mdt_sample_ddim_dev_multi(mdt_model* m, const float* token
 // per sample, stride cond_width.  The encoder, the stacked cross K|V product and the fold run on the B observations and S K M
 // consecutive samples read one context (ctx_div); where sigma is a context token they run on the B * S contexts (b, s), the
 // observation's inputs staged S times, and K M samples read one.  Every check comes before the first launch.
-extern "C" mdt_status mdt_denoising_score(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
-                                          const float* x0, const float* sigmas_host, const float* weights_host, int32_t n_levels,
-                                          const float* noise, int32_t draws, int64_t batch, int32_t candidates, float* score,
-                                          float* ctx_out, void* stream) {
-    const char* fn = "mdt_denoising_score";
-    if (!m) return fail(MDT_ERR_INVALID_ARG, "%s: null handle", fn);
-    const std::pair<const void*, const char*> need[] = {{tokens, "tokens"}, {goal, "goal"}, {x0, "x0"}, {sigmas_host, "sigmas"},
-                                                        {noise, "noise"}, {score, "score"}};
-    for (const auto& p : need)
-        if (!p.first) return fail(MDT_ERR_INVALID_ARG, "%s: null %s", fn, p.second);
-    if (batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: batch is %lld, must be >= 1", fn, (long long)batch);
-    if (candidates < 1) return fail(MDT_ERR_INVALID_ARG, "%s: candidates is %d, must be >= 1", fn, (int)candidates);
+// The checks and the launches are shared with the select phase of mdt_sample*_select (`fn`: the entry the messages name).
+
+// n_levels, draws, the levels and the weights (null: the trapezoid rule in ln sigma) into the kernel argument
+static mdt_status score_levels_of(const char* fn, const float* sigmas_host, const float* weights_host, int32_t n_levels, int32_t draws,
+                                  mdt_score_levels* out) {
     if (n_levels < 1 || n_levels > MDT_SCORE_MAX)
         return fail(MDT_ERR_INVALID_ARG, "%s: n_levels is %d, must be in [1, %d]", fn, (int)n_levels, MDT_SCORE_MAX);
     if (draws < 1 || draws > MDT_SCORE_MAX)
         return fail(MDT_ERR_INVALID_ARG, "%s: draws is %d, must be in [1, %d]", fn, (int)draws, MDT_SCORE_MAX);
-    const int S = n_levels, K = candidates, M = draws;
-    mdt_score_levels lv;
+    const int S = n_levels;
+    mdt_score_levels& lv = *out;
     memset(&lv, 0, sizeof lv);
     for (int i = 0; i < S; ++i) {
         if (!std::isfinite(sigmas_host[i]) || !(sigmas_host[i] > 0.f))
@@ -1456,19 +1474,28 @@ extern "C" mdt_status mdt_denoising_score(mdt_model* m, const float* tokens, con
             lv.weight[i] = S == 1 ? 1.f : (float)(0.5 * (lo + hi));
         }
     }
-    if (m->cfg.arch == MDT_ARCH_MDT && !tokens2) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: MDT needs the gripper tokens", fn);
-    if (m->cfg.use_proprio && !tokens2)
-        return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: this handle was created with use_proprio and needs state_obs", fn);
-    const int64_t limit = ((int64_t)1 << 24) / std::max(1, std::max(m->Te, m->Ta));  // the decoder's row counts (int)
+    return MDT_OK;
+}
+
+// batch * K * S * M decoder samples against the decoder's row counts (int)
+static mdt_status score_rows_check(const char* fn, const mdt_model* m, int64_t batch, int K, int S, int M) {
+    const int64_t limit = ((int64_t)1 << 24) / std::max(1, std::max(m->Te, m->Ta));
     const int64_t per_obs = (int64_t)K * S * M;
     if (per_obs > limit || batch > limit / per_obs)
         return fail(MDT_ERR_INVALID_ARG, "%s: batch * candidates * n_levels * draws = %lld * %d * %d * %d rows is more than the "
                                          "decoder's %lld samples", fn, (long long)batch, K, S, M, (long long)limit);
-    MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));
-    MDT_TRY(check_loaded(m));
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nb = batch * per_obs;
-    MDT_TRY(mdt_reserve(m, nb));
+    return MDT_OK;
+}
+
+// The launches of the score, the workspace holding batch * K * S * M samples.  shared_ctx (the select phase of a model whose context
+// does not depend on sigma): the encoder, the stacked cross K|V product and the fold are not run -- the context, K|V rows and folded
+// operands of the `batch` observations are the ones the sampler's prefix left in the workspace (a guided call's conditional half
+// comes first, and decoder sample j reads context j / ctx_div < batch).  The phase is mdt_denoising_score's otherwise: it reuses
+// xbuf / ybuf / noised / Fbuf, which the sampler has finished with, the chunks x0 being in the caller's buffer.
+static mdt_status score_run(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality, const float* x0,
+                            const mdt_score_levels& lv, int S, int K, int M, const float* noise, int64_t batch, float* score,
+                            float* ctx_out, hipStream_t s, bool shared_ctx) {
+    const int64_t per_obs = (int64_t)K * S * M, nb = batch * per_obs;
     const bool sig_ctx = m->cond == COND_TOKEN;
     const float sd = m->cfg.sigma_data;
     const View V = decoder_view(m, 0);
@@ -1487,13 +1514,98 @@ extern "C" mdt_status mdt_denoising_score(mdt_model* m, const float* tokens, con
         }
     } else {
         MDT_TRY(run_modulation(m, sig_rows, 1, (int)nb, s));
-        MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, honour, batch, nullptr, 0, ctx_out, s));
+        if (!shared_ctx) MDT_TRY(run_encode(m, tokens, tokens2, goal, modality, honour, batch, nullptr, 0, ctx_out, s));
     }
     mdt_head_args h = head_args(m, V.y, nb, m->noised, sig_rows, 1, m->Fbuf, MDT_HEAD_RAW);
     const int64_t ctx_div = sig_ctx ? (int64_t)K * M : per_obs;
     MDT_TRY(run_eval(m, V, nb, cond_row(m, 0), sig_ctx ? 0 : cond_width(m), h, nullptr, nullptr, s, mdt_guide(), {}, (int)ctx_div));
     LAUNCH(mdt_launch_score_reduce(m->Fbuf, x0, noise, lv, batch, S, K, M, m->Ta * m->A, sd, score, s));
     return MDT_OK;
+}
+
+extern "C" mdt_status mdt_denoising_score(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
+                                          const float* x0, const float* sigmas_host, const float* weights_host, int32_t n_levels,
+                                          const float* noise, int32_t draws, int64_t batch, int32_t candidates, float* score,
+                                          float* ctx_out, void* stream) {
+    const char* fn = "mdt_denoising_score";
+    if (!m) return fail(MDT_ERR_INVALID_ARG, "%s: null handle", fn);
+    const std::pair<const void*, const char*> need[] = {{tokens, "tokens"}, {goal, "goal"}, {x0, "x0"}, {sigmas_host, "sigmas"},
+                                                        {noise, "noise"}, {score, "score"}};
+    for (const auto& p : need)
+        if (!p.first) return fail(MDT_ERR_INVALID_ARG, "%s: null %s", fn, p.second);
+    if (batch < 1) return fail(MDT_ERR_INVALID_ARG, "%s: batch is %lld, must be >= 1", fn, (long long)batch);
+    if (candidates < 1) return fail(MDT_ERR_INVALID_ARG, "%s: candidates is %d, must be >= 1", fn, (int)candidates);
+    mdt_score_levels lv;
+    MDT_TRY(score_levels_of(fn, sigmas_host, weights_host, n_levels, draws, &lv));
+    const int S = n_levels, K = candidates, M = draws;
+    if (m->cfg.arch == MDT_ARCH_MDT && !tokens2) return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: MDT needs the gripper tokens", fn);
+    if (m->cfg.use_proprio && !tokens2)
+        return fail(MDT_ERR_INVALID_ARG, "%s: null tokens2: this handle was created with use_proprio and needs state_obs", fn);
+    MDT_TRY(score_rows_check(fn, m, batch, K, S, M));
+    MDT_TRY(check_encode_args(m, tokens, tokens2, goal, ctx_out));
+    MDT_TRY(check_loaded(m));
+    MDT_TRY(mdt_reserve(m, batch * K * S * M));
+    return score_run(m, tokens, tokens2, goal, modality, x0, lv, S, K, M, noise, batch, score, ctx_out, (hipStream_t)stream, false);
+}
+
+// The select phase of mdt_sample*_select, behind the sampler's last launch: the score of the chunks in `out` -- that of the unguided,
+// unpinned, unclamped conditional model, as mdt_denoising_score gives it; the request's weight, pin and bounds shaped the sampling
+// only -- then the selection.  The workspace holds the score's rows since sampler_open.  ctx_out stays the sampler's.
+static mdt_status select_check(const mdt_model* m, const SamplerRequest& a) {
+    if (!a.sel || !m || a.batch < 1 || a.cand < 1) return MDT_OK;  // (a null handle and the counts: the family's checks, next)
+    return score_rows_check(a.who, m, a.batch, a.cand, a.sel->S, a.sel->M);
+}
+
+static mdt_status select_phase(mdt_model* m, const SamplerRequest& a) {
+    const SelectPhase& p = *a.sel;
+    hipStream_t s = (hipStream_t)a.stream;
+    MDT_TRY(score_run(m, a.tokens, a.tokens2, a.goal, a.modality, a.out, p.lv, p.S, a.cand, p.M, p.noise, a.batch, p.scores, nullptr, s,
+                      m->cond != COND_TOKEN));
+    LAUNCH(mdt_launch_score_select(p.scores, a.out, a.batch, a.cand, m->Ta * m->A, p.best, p.index, s));
+    return MDT_OK;
+}
+
+// What a *_select entry checks of its own, before its family's checks: the spec, its size and its required pointers, `best`, then
+// what mdt_denoising_score checks of the levels, the weights and the draws.  The request then samples into spec.chunks.
+static mdt_status read_select(SamplerRequest* r, const mdt_select_spec* sp, float* best, SelectPhase* ph) {
+    const char* fn = r->who;
+    if (!sp) return fail(MDT_ERR_INVALID_ARG, "%s: null select", fn);
+    if (sp->size != (int32_t)sizeof(mdt_select_spec))
+        return fail(MDT_ERR_INVALID_ARG, "%s: select.size is %d, sizeof(mdt_select_spec) is %d", fn, sp->size, (int)sizeof(mdt_select_spec));
+    const std::pair<const void*, const char*> need[] = {{best, "best"}, {sp->chunks, "select.chunks"}, {sp->scores, "select.scores"},
+                                                        {sp->index, "select.index"}, {sp->sigmas_host, "select.sigmas_host"},
+                                                        {sp->noise, "select.noise"}};
+    for (const auto& p : need)
+        if (!p.first) return fail(MDT_ERR_INVALID_ARG, "%s: null %s", fn, p.second);
+    MDT_TRY(score_levels_of(fn, sp->sigmas_host, sp->weights_host, sp->n_levels, sp->draws, &ph->lv));
+    ph->S = sp->n_levels; ph->M = sp->draws; ph->noise = sp->noise;
+    ph->best = best; ph->scores = sp->scores; ph->index = sp->index;
+    r->out = sp->chunks;
+    r->sel = ph;
+    return MDT_OK;
+}
+
+// The *_select entries: the *_multi call into select.chunks, then the select phase (include/mdt_hip.h).
+extern "C" mdt_status mdt_sample_ddim_select(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                             int32_t modality, const float* x_T, const float* sigmas_host, int32_t n_steps,
+                                             int64_t batch, int32_t candidates, float* best, float* ctx_out,
+                                             const mdt_sample_opts* opts, const mdt_select_spec* select, void* stream) {
+    SamplerRequest r = {"mdt_sample_ddim_select", tokens, tokens2, goal, modality, x_T, batch, nullptr, ctx_out, stream};
+    SelectPhase ph;
+    MDT_TRY(read_select(&r, select, best, &ph));
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_ddim_impl(m, r.schedule(sigmas_host, false, n_steps).candidates(candidates));
+}
+
+extern "C" mdt_status mdt_sample_ddim_dev_select(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                                 int32_t modality, const float* x_T, const float* sigmas_dev, int32_t n_steps,
+                                                 int64_t batch, int32_t candidates, float* best, float* ctx_out,
+                                                 const mdt_sample_opts* opts, const mdt_select_spec* select, void* stream) {
+    SamplerRequest r = {"mdt_sample_ddim_dev_select", tokens, tokens2, goal, modality, x_T, batch, nullptr, ctx_out, stream};
+    SelectPhase ph;
+    MDT_TRY(read_select(&r, select, best, &ph));
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_ddim_impl(m, r.schedule(sigmas_dev, true, n_steps).candidates(candidates));
 }
 
 // MDT_PLAN_* -> mdt_status with the message of the failed check
@@ -1567,6 +1679,7 @@ static mdt_status sample_plan_impl(mdt_model* m, const SamplerRequest& a) {
     const float* noise = wants_tree ? nullptr : a.noise;
     int32_t n_noise = wants_tree ? 0 : a.n_noise;
     mdt_guide gd;
+    MDT_TRY(select_check(m, a));
     MDT_TRY(sampler_check(m, a, "mdt_sample", a.sigmas != nullptr, &gd));
     // (o.lo, o.hi and o.record are read and written one element at a time: any float alignment will do, e.g. a slice of a larger tensor)
     const mdt_sampler_params p = a.params ? *a.params : mdt_sampler_defaults();
@@ -1638,7 +1751,7 @@ static mdt_status sample_plan_impl(mdt_model* m, const SamplerRequest& a) {
                                            n_noise, last ? c.ctx_out : nullptr, clips ? a.o.lo : nullptr, clips ? a.o.hi : nullptr,
                                            a.o.record ? a.o.record + mdt_plan_step_of(kind, n_steps, e) * rec_stride : nullptr}));
     }
-    return sampler_close(m, c);
+    return sampler_finish(m, a, c);
 }
 
 extern "C" mdt_status mdt_sample(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
@@ -1706,6 +1819,30 @@ extern "C" mdt_status mdt_sample_dev_multi(mdt_model* m, const float* tokens, co
                                            int64_t batch, int32_t candidates, float* out, float* ctx_out,
                                            const mdt_sample_opts* opts, void* stream) {
     SamplerRequest r = {"mdt_sample_dev_multi", tokens, tokens2, goal, modality, x_T, batch, out, ctx_out, stream};
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_plan_impl(m, r.schedule(sigmas_dev, true, n_steps).plan(kind, params, noise, n_noise).candidates(candidates));
+}
+
+extern "C" mdt_status mdt_sample_select(mdt_model* m, const float* tokens, const float* tokens2, const float* goal, int32_t modality,
+                                        const float* x_T, int32_t kind, const mdt_sampler_params* params, const float* sigmas_host,
+                                        int32_t n_steps, const float* noise, int32_t n_noise, int64_t batch, int32_t candidates,
+                                        float* best, float* ctx_out, const mdt_sample_opts* opts, const mdt_select_spec* select,
+                                        void* stream) {
+    SamplerRequest r = {"mdt_sample_select", tokens, tokens2, goal, modality, x_T, batch, nullptr, ctx_out, stream};
+    SelectPhase ph;
+    MDT_TRY(read_select(&r, select, best, &ph));
+    MDT_TRY(read_opts(r.who, opts, &r.o));
+    return sample_plan_impl(m, r.schedule(sigmas_host, false, n_steps).plan(kind, params, noise, n_noise).candidates(candidates));
+}
+
+extern "C" mdt_status mdt_sample_dev_select(mdt_model* m, const float* tokens, const float* tokens2, const float* goal,
+                                            int32_t modality, const float* x_T, int32_t kind, const mdt_sampler_params* params,
+                                            const float* sigmas_dev, int32_t n_steps, const float* noise, int32_t n_noise,
+                                            int64_t batch, int32_t candidates, float* best, float* ctx_out,
+                                            const mdt_sample_opts* opts, const mdt_select_spec* select, void* stream) {
+    SamplerRequest r = {"mdt_sample_dev_select", tokens, tokens2, goal, modality, x_T, batch, nullptr, ctx_out, stream};
+    SelectPhase ph;
+    MDT_TRY(read_select(&r, select, best, &ph));
     MDT_TRY(read_opts(r.who, opts, &r.o));
     return sample_plan_impl(m, r.schedule(sigmas_dev, true, n_steps).plan(kind, params, noise, n_noise).candidates(candidates));
 }

@@ -10,6 +10,7 @@
 //   k_score_reduce  the score from the network's raw output F, in the residual form
 //                       q = sigma / (sigma^2 + sd^2) x0 - c_skip n - sd / sqrt(sigma^2 + sd^2) F
 //                   which never forms x0 - D, so nothing cancels at small sigma
+//   k_score_select  the selection behind the scores: per observation the index gc_sampling.best_candidates gives, and that chunk
 // The levels and the weights are host values and ride in the kernel arguments (mdt_score_levels): no copy, nothing to capture
 // beside the launches.  No atomics anywhere: every output element has one writer and the sums have one fixed order.
 #include <hip/hip_runtime.h>
@@ -135,6 +136,50 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_score_reduce(const float* __r
     if (tid == 0) score[r] = -((part[0] + part[1]) + (part[2] + part[3]));
 }
 
+// A score as the selection orders it: best_candidates' torch.nan_to_num(scores, nan=-inf) -- NaN below everything, and, by that
+// function's defaults, +Inf the largest finite float and -Inf the lowest (so +Inf ties with FLT_MAX, and -Inf beats NaN).
+__device__ __forceinline__ float select_key(float v) {
+    if (v != v) return -INFINITY;
+    return fminf(fmaxf(v, -3.402823466e+38f), 3.402823466e+38f);
+}
+// whether (v, k) goes before (bv, bk): the larger key, then the lower index -- a total order, the k being distinct
+__device__ __forceinline__ bool select_beats(float v, int k, float bv, int bk) { return v > bv || (v == bv && k < bk); }
+
+// One workgroup per observation b.  Lane t scans the keys of k = t, t + 256, .. and keeps its first largest; a lane without a k holds
+// (-Inf, INT_MAX), which loses every tie, so K all-NaN scores select k = 0.  Then the xor butterfly over the 64 lanes carrying
+// (key, k) -- the order is total, so every lane ends with the wave's winner -- and the four waves' winners from LDS in wave order,
+// by every thread alike.  The workgroup then copies the winner's E elements; thread 0 stores the index.  scores and chunks are only read.
+__global__ __launch_bounds__(SCORE_THREADS) void k_score_select(const float* __restrict__ score, const float* __restrict__ chunks, int K,
+                                                                 int E, float* __restrict__ best, int32_t* __restrict__ index) {
+    __shared__ float pv[SCORE_THREADS / 64];
+    __shared__ int pk[SCORE_THREADS / 64];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t b = blockIdx.x;
+    const float* sr = score + b * K;
+    float bv = -INFINITY;
+    int bk = 0x7fffffff;
+    for (int k = tid; k < K; k += SCORE_THREADS) {
+        const float v = select_key(sr[k]);
+        if (select_beats(v, k, bv, bk)) { bv = v; bk = k; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off, 64);
+        const int ok = __shfl_xor(bk, off, 64);
+        if (select_beats(ov, ok, bv, bk)) { bv = ov; bk = ok; }
+    }
+    if (lane == 0) { pv[wave] = bv; pk[wave] = bk; }
+    __syncthreads();
+    bv = pv[0]; bk = pk[0];
+#pragma unroll
+    for (int w = 1; w < SCORE_THREADS / 64; ++w)
+        if (select_beats(pv[w], pk[w], bv, bk)) { bv = pv[w]; bk = pk[w]; }
+    const float* src = chunks + (b * K + bk) * E;
+    float* dst = best + b * E;
+    for (int e = tid; e < E; e += SCORE_THREADS) dst[e] = src[e];
+    if (tid == 0) index[b] = bk;
+}
+
 unsigned score_grid(int64_t n) {
     const int64_t g = (n + SCORE_THREADS - 1) / SCORE_THREADS;
     return (unsigned)(g < 1 ? 1 : (g > SCORE_MAX_BLOCKS ? SCORE_MAX_BLOCKS : g));
@@ -168,9 +213,15 @@ hipError_t mdt_launch_score_reduce(const float* F, const float* x0, const float*
     return mdt_launch_lds<k_score_reduce>(dim3((unsigned)(B * K)), dim3(SCORE_THREADS), 0, s, F, x0, noise, lv, S, K, M, E, sd, score);
 }
 
+hipError_t mdt_launch_score_select(const float* score, const float* chunks, int64_t B, int K, int E, float* best, int32_t* index,
+                                   hipStream_t s) {
+    if (B < 1 || B > 0x7fffffff || K < 1 || E < 1) return hipErrorInvalidValue;
+    return mdt_launch_lds<k_score_select>(dim3((unsigned)B), dim3(SCORE_THREADS), 0, s, score, chunks, K, E, best, index);
+}
+
 // ------------------------------------------------------------------------------------------------
-// test hooks (mdt_hip_debug.h): the three kernels above on the caller's buffers, each through the launch mdt_denoising_score makes
-// (mdt_launch_score_*).  What the call guarantees by construction is checked here, before anything is launched.
+// test hooks (mdt_hip_debug.h): the kernels above on the caller's buffers, each through the launch mdt_denoising_score makes
+// or mdt_sample*_select makes (mdt_launch_score_*).  What the call guarantees by construction is checked here, before anything is launched.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -270,5 +321,18 @@ extern "C" mdt_status mdt_op_score_reduce(const float* F, const float* x0, const
     mdt_score_levels lv;
     MDT_TRY(hook_levels(fn, sigmas, weights, S, &lv));
     LAUNCH(mdt_launch_score_reduce(F, x0, noise, lv, B, S, K, M, E, sd, score, (hipStream_t)stream));
+    return MDT_OK;
+}
+
+extern "C" mdt_status mdt_op_score_select(const float* scores, const float* chunks, int64_t B, int32_t K, int32_t E, float* best,
+                                          int32_t* index, void* stream) {
+    const char* fn = "mdt_op_score_select";
+    MDT_TRY(hook_nulls(fn, {{scores, "scores"}, {chunks, "chunks"}, {best, "best"}, {index, "index"}}));
+    MDT_TRY(hook_at_least_1(fn, "B", B));
+    MDT_TRY(hook_at_least_1(fn, "K", K));
+    MDT_TRY(hook_at_least_1(fn, "E", E));
+    if (B > (int64_t)0x7fffffff)
+        return mdt_fail(MDT_ERR_INVALID_ARG, "%s: B is %lld, more than 2147483647 observations (one workgroup each)", fn, (long long)B);
+    LAUNCH(mdt_launch_score_select(scores, chunks, B, K, E, best, index, (hipStream_t)stream));
     return MDT_OK;
 }

@@ -35,8 +35,8 @@ import torch
 from . import utils
 from ... import _lib
 from ..networks._engine import candidate_count, chunk_rows, rollout_controls, steer_alone, take_candidates, take_steer
-from .graphed import GraphedDDIM, GraphedSampler
-from .score_wrappers import GCDenoiser
+from .graphed import GraphedDDIM, GraphedSampler, GraphedSelect
+from .score_wrappers import GCDenoiser, draw_score_noise
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1513,3 +1513,102 @@ def denoising_score(model, state, action, goal, sigmas, extra_args=None, draws=2
             level = level + (q * q).flatten(1).sum(1)
         score = score - (w[s] / M) * level
     return score.reshape(action.shape[:-2])
+
+
+# ------------------------------------------------------------------------------------------------
+# sample, score and select as one native call
+# ------------------------------------------------------------------------------------------------
+# The samplers sample_select runs inside the one call, with the draws their sample_<name> makes at its default parameters: None,
+# one randn per step ("steps": the churn's, drawn whether it is used or not), or one per step that adds noise ("ancestral").  Any
+# other sampler runs the three functions in sequence.
+_SELECT_DRAWS = {"ddim": None, "dpmpp_2m": None, "lms": None, "euler": "steps", "heun": "steps", "dpm_2": "steps",
+                 "euler_ancestral": "ancestral", "dpm_2_ancestral": "ancestral"}
+
+
+def _select_sequence(model, state, action, goal, sigmas, levels, sampler, scaler, extra_args, K, draws, weights, noise, antithetic):
+    """sample_select as its three functions: ``sample_<sampler>``, ``denoising_score``, ``best_candidates``."""
+    fn = globals().get("sample_" + sampler)
+    if fn is None or sampler in ("select", "dpm_fast"):
+        raise ValueError(f"sample_select: no sampler {sampler!r} that takes a schedule")
+    if sampler == "dpm_adaptive":  # the two ends of the schedule are its range
+        sig = [float(v) for v in sigmas if float(v) > 0]
+        chunks = fn(model, state, action, goal, min(sig), max(sig), extra_args=extra_args)
+    else:
+        chunks = fn(model, state, action, goal, sigmas, scaler=scaler, extra_args=extra_args)
+    has_k = extra_args is not None and "candidates" in extra_args
+    scores = denoising_score(model, state, chunks, goal, levels, extra_args={"candidates": K} if has_k else None, draws=draws,
+                             weights=weights, noise=noise, antithetic=antithetic)
+    if not has_k:  # a foreign model: every chunk its own observation
+        return chunks, torch.zeros(chunks.shape[:-2], dtype=torch.int64, device=chunks.device).reshape(-1), scores, chunks
+    best, index = best_candidates(chunks, scores, K)
+    return best, index, scores, chunks
+
+
+@torch.no_grad()
+def sample_select(model, state, action, goal, sigmas, levels, sampler="ddim", scaler=None, extra_args=None, draws=2, weights=None,
+                  noise=None, antithetic=True):
+    """The replan-and-select loop as one call: K candidate chunks per observation sampled from ``action`` by ``sample_<sampler>``
+    over ``sigmas``, scored by ``denoising_score`` over ``levels`` (``draws``, ``weights``, ``noise`` and ``antithetic`` are its
+    arguments: ``noise`` the score's rows (S, M, Ta, A)), and the best of each observation picked by ``best_candidates``.  Returns
+    (best (B, Ta, A), index (B,) int64, scores, chunks): ``chunks`` in ``action``'s shape -- (B*K, Ta, A) or (B, K, Ta, A) -- and
+    ``scores`` in ``action.shape[:-2]``.
+
+    ``extra_args`` reads 'candidates' = K (required with this package's GCDenoiser), 'cond_lambda' and 'pin'; any other key raises
+    NotImplementedError naming it.  The guidance weight, the pin and the scaler's bounds shape the sampling only: the score is that
+    of the unguided, unpinned model, as ``denoising_score``'s is.
+
+    With a GCDenoiser, a schedule and scaler the native samplers admit, and ``sampler`` one of ddim, euler, heun, dpm_2,
+    euler_ancestral, dpm_2_ancestral, lms, dpmpp_2m (at their default parameters) it is ONE native enqueue
+    (``GCDenoiser.sample_select`` -> mdt_sample_ddim_select / mdt_sample_select): where the context does not depend on sigma the
+    encoder runs once for both halves, the selection is one kernel, nothing is read back.  The sampler's noise rows and then the
+    score's are drawn as the three functions draw them, so a seeded call gives their result.  Rollout-sized calls (B*K <= 8) are
+    replayed as a HIP graph by ``sample_ddim``'s rule (MDT_HIP_GRAPH); the levels and weights are host values and belong to the
+    graph's key, the noise rows, the pin and the bounds sit in static buffers filled before every replay.
+
+    Anything else -- a foreign ``model``, a scaler without ``clip_bounds``, another ``sampler`` ('dpm_adaptive' reads the schedule's
+    largest and smallest positive level as its range) -- runs the three functions in sequence and returns the same tuple.  A
+    foreign model has no shared context: 'candidates' raises the ValueError ``denoising_score`` raises, and without it every chunk
+    is its own observation."""
+    rest = dict(extra_args or {})
+    for k in sorted(rest):
+        if k not in ("candidates", "cond_lambda", "pin"):
+            raise NotImplementedError(f"sample_select: extra_args[{k!r}] is not supported (keys read: 'candidates', 'cond_lambda', "
+                                      "'pin')")
+    ours = isinstance(model, GCDenoiser)
+    if "candidates" in rest and not ours:
+        raise ValueError("denoising_score: 'candidates' needs this package's GCDenoiser (a foreign model has no shared context to "
+                         "exploit): expand the observations and score the chunks as a batch")
+    if ours and "candidates" not in rest:
+        raise ValueError("sample_select: extra_args['candidates'] (chunks per observation) is required")
+    _, lam, pin, K = _controls(rest)
+    ddim = sampler == "ddim"
+    if not (ours and sampler in _SELECT_DRAWS and _native_ok(model, sigmas, None if ddim else scaler, None, rest)):
+        return _select_sequence(model, state, action, goal, sigmas, levels, sampler, scaler, extra_args, K, draws, weights, noise,
+                                antithetic)
+    lv, w = _score_levels(levels, weights)
+    S = len(lv)
+    Ta, A = action.shape[-2:]
+    if noise is not None and (noise.dim() != 4 or noise.shape[0] != S or noise.shape[1] < 1 or tuple(noise.shape[2:]) != (Ta, A)):
+        raise ValueError(f"sample_select: noise is {tuple(noise.shape)}: {S} levels take ({S}, draws, {Ta}, {A})")
+    rule = _SELECT_DRAWS[sampler]
+    rows_noise = None if rule is None else _randn_rows(action, len(sigmas) - 1 if rule == "steps" else _ancestral_draws(sigmas, 1.))
+    if noise is None:
+        noise = draw_score_noise("sample_select", S, draws, antithetic, Ta, A, action.dtype, action.device)
+    shape = action.shape
+    rows, rows_noise = _chunk_view(state, action, rows_noise, K)
+    bounds = None if scaler is None or ddim else scaler.clip_bounds(rows.device)
+    if pin is not None:
+        pin = pin.on(rows.device, rows.shape, K)
+    kind = None if ddim else sampler
+    wkey = None if weights is None else tuple(w)
+    key = ("select", sampler, K, tuple(lv), wkey, int(noise.shape[1]), lam, bounds is not None, pin is not None)
+    out = _graph_route(model, "_graphed_select", key, key, state, rows, goal, sigmas,
+                       lambda sig: GraphedSelect(model, kind, key, state, rows, goal, sig, (rows_noise, noise), lv,
+                                                 None if weights is None else w, K, cond_lambda=lam, bounds=bounds, pin=pin),
+                       f"sample_select({sampler})", noise=(rows_noise, noise), bounds=bounds, pin=pin)
+    if out is None:
+        kw = {} if lam is None else {"cond_lambda": lam}
+        out = model.sample_select(state, rows, goal, sigmas, lv, K, kind=kind, noise=rows_noise, pin=pin, bounds=bounds,
+                                  weights=None if weights is None else w, score_noise=noise, **kw)
+    best, index, scores, chunks = out
+    return best, index, scores.reshape(shape[:-2]), chunks.reshape(shape)

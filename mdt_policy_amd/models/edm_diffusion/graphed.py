@@ -213,3 +213,59 @@ class GraphedSampler(GraphedDDIM):
             dst += [self._lo, self._hi]; src += [bounds[0], bounds[1]]
         d2, s2 = super()._extra_inputs(noise, bounds, pin)
         return dst + d2, src + s2
+
+
+class GraphedSelect(GraphedSampler):
+    """The same for ``GCDenoiser.sample_select``: sample, score and select as one replay.  ``kind`` None is DDIM.  ``key`` is the
+    call's graph key as ``gc_sampling.sample_select`` forms it: the sampler, K, the score's levels and weights -- host values that
+    ride in kernel arguments and are therefore part of the graph -- its draw count, the guidance weight and the presence of bounds
+    and a pin.  ``noise`` is the pair (the sampler's noise rows or None, the score's noise rows): both sit in static buffers, with
+    the pin and the bounds, and are filled before every replay.  A call returns (best, index, scores, chunks) as fresh tensors."""
+
+    def __init__(self, model, kind: Optional[str], key, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas: torch.Tensor,
+                 noise: tuple, levels, weights, candidates: int, cond_lambda: Optional[float] = None,
+                 bounds: Optional[tuple] = None, pin: Optional[tuple] = None):
+        self._key = key
+        self._levels = [float(v) for v in levels]
+        self._weights = None if weights is None else [float(v) for v in weights]
+        self._K = int(candidates)
+        self._lam = cond_lambda
+        self._score_noise = noise[1].detach().clone()
+        self._sel = None
+        super().__init__(model, kind, {}, state, x_T, goal, sigmas, noise[0], bounds=bounds, pin=pin)
+
+    def _call_key(self):
+        return self._key
+
+    def _run(self):
+        kw = {} if self._lo is None else {"bounds": (self._lo, self._hi)}
+        if self._pin is not None:
+            kw["pin"] = self._pin
+        if self._lam is not None:
+            kw["cond_lambda"] = self._lam
+        self._sel = self.model.sample_select(self._static_state, self._x, self._goal, self._sig, self._levels, self._K,
+                                             kind=self.kind, noise=self._noise, weights=self._weights,
+                                             score_noise=self._score_noise, **kw)
+        return self._sel[0]
+
+    def matches(self, state, x_T, goal, sigmas, key=None, noise=None) -> bool:
+        if noise is None or noise[1].shape != self._score_noise.shape:
+            return False
+        return super().matches(state, x_T, goal, sigmas, key=key, noise=noise[0])
+
+    def _extra_inputs(self, noise, bounds=None, pin=None):
+        dst, src = super()._extra_inputs(noise[0], bounds, pin)
+        return dst + [self._score_noise], src + [noise[1]]
+
+    @torch.no_grad()
+    def __call__(self, state, x_T, goal, sigmas=None, noise=None, bounds=None, pin=None):
+        super().__call__(state, x_T, goal, sigmas, fresh=False, noise=noise, bounds=bounds, pin=pin)
+        best, index, scores, chunks = self._sel  # (captured in _capture; a re-capture renews them)
+        parts = (best, scores, chunks, self._ctx)
+        flat = torch.cat([t.reshape(-1) for t in parts])  # fresh tensors for the caller through ONE copy launch
+        views, at = [], 0
+        for t in parts:
+            views.append(flat[at:at + t.numel()].view(t.shape))
+            at += t.numel()
+        self.model.inner_model.latent_encoder_emb = views[3]
+        return views[0], index.clone(), views[1], views[2]

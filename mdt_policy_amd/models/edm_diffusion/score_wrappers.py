@@ -87,6 +87,20 @@ def _pin_rows(pin, action, K):
     return pin.on(action.device, (action.numel() // (Ta * A), Ta, A), K) if callable(getattr(pin, "on", None)) else pin
 
 
+def draw_score_noise(who, S, draws, antithetic, Ta, A, dtype, device):
+    """The noise rows (S, draws, Ta, A) of a denoising score whose caller gave none, by ``gc_sampling.denoising_score``'s rule:
+    ``torch.randn`` in (S, M) order; with ``antithetic`` draws / 2 rows per level, each followed directly by its negative, and an
+    odd ``draws`` raises ValueError."""
+    if isinstance(draws, bool) or not isinstance(draws, int) or draws < 1:
+        raise ValueError(f"{who}: draws must be an int >= 1, got {draws!r}")
+    if not antithetic:
+        return torch.randn((S, draws, Ta, A), dtype=dtype, device=device)
+    if draws % 2:
+        raise ValueError(f"{who}: draws is {draws}: antithetic pairs need an even count (or antithetic=False)")
+    half = torch.randn((S, draws // 2, Ta, A), dtype=dtype, device=device)
+    return torch.stack((half, -half), dim=2).reshape(S, draws, Ta, A)
+
+
 class GCDenoiser(nn.Module):
     """Karras et al. (2022) preconditioner around the MI355X-native score network."""
 
@@ -435,6 +449,35 @@ class GCDenoiser(nn.Module):
             n_steps=n_steps, cond_lambda=cond_lambda, tree=tree, bounds=bounds, record=record, pin=pin, candidates=K)
         im.latent_encoder_emb = ctx
         return (out, _record_dict(rec, kind, sigmas, n_steps, params)) if record else out
+
+    @torch.no_grad()
+    def sample_select(self, state, action, goal, sigmas, levels, candidates, kind=None, noise=None, n_steps=None, cond_lambda=1.0,
+                      pin=None, bounds=None, draws=2, weights=None, score_noise=None, antithetic=True, **params):
+        """Sample, score and select as one enqueue (mdt_sample_ddim_select, ``kind`` None; mdt_sample_select, ``kind`` a sampler
+        name): ``candidates`` = K chunks per observation sampled as ``sample_ddim`` / ``sample_native`` sample them (``sigmas``,
+        ``noise``, ``n_steps``, ``cond_lambda``, ``pin``, ``bounds`` and ``params`` are theirs), scored as ``denoising_score`` scores
+        them (``levels`` the S host levels, ``weights`` None or S values, ``score_noise`` (S, M, Ta, A) or None: ``draws`` rows per
+        level drawn here, in antithetic pairs by default), and per observation the chunk of the largest score selected by
+        ``gc_sampling.best_candidates``' rule.  The guidance weight, the pin and the bounds shape the sampling only: the score is
+        that of the unguided, unpinned model.  Where the context does not depend on sigma the score reads the context the sampler
+        encoded: the encoder runs once.  Returns (best (B, Ta, A), index (B,) int64, scores, chunks): ``chunks`` in ``action``'s
+        shape, (B*K, Ta, A) or (B, K, Ta, A), ``scores`` in ``action.shape[:-2]``.  No read-back, no synchronisation; capturable
+        after one eager call."""
+        from ... import _lib
+        im = self.inner_model
+        K = candidate_count(candidates)
+        Ta, A = action.shape[-2:]
+        S = int(levels.numel()) if torch.is_tensor(levels) else len(levels)
+        if score_noise is None:
+            score_noise = draw_score_noise("sample_select", S, draws, antithetic, Ta, A, action.dtype, action.device)
+        pin = _pin_rows(pin, action, K)
+        bounds = _bounds_pair(bounds, action.device)
+        best, index, scores, chunks, ctx = self._engine(state=state).sample_select(
+            None if kind is None else _lib.SAMPLER_KIND[kind], _lib.sampler_params(**params), state, action, im._goals(goal, False),
+            sigmas, levels, score_noise, K, weights=weights, noise=noise, n_steps=n_steps, cond_lambda=cond_lambda, bounds=bounds,
+            pin=pin)
+        im.latent_encoder_emb = ctx
+        return best, index.long(), scores.reshape(action.shape[:-2]), chunks
 
     @torch.no_grad()
     def sample_dpm_adaptive_native(self, state, action, goal, sigma_min, sigma_max, cond_lambda=None, **params):

@@ -723,6 +723,45 @@ class HipEngine:
         self._keep = (tok, tok2, g, x_, nz)  # the kernels that read them are only enqueued
         return score, ctx
 
+    def sample_select(self, kind: Optional[int], params, state: dict, x_T: torch.Tensor, goal: torch.Tensor, sigmas, levels,
+                      score_noise: torch.Tensor, candidates: int, weights=None, noise: Optional[torch.Tensor] = None,
+                      n_steps: Optional[int] = None, cond_lambda: Optional[float] = None, bounds=None, pin=None):
+        """mdt_sample_ddim_select / _dev_select (``kind`` None) or mdt_sample_select / _dev_select (``kind`` an mdt_sampler_kind,
+        ``params`` an _lib.SamplerParams): ``sample_ddim`` / ``sample_native`` with ``candidates`` = K chunks per observation, the
+        chunks scored as ``denoising_score`` scores them -- ``levels`` the S host levels, ``score_noise`` (S, M, Ta, A), ``weights``
+        None or S host values -- and the best of each observation selected, as ONE enqueue.  The other arguments are the sampler's.
+        Returns (best (B, Ta, A), index (B,) int32, scores (B*K,), chunks in the shape x_T came in, ctx).  Capture-safe once the
+        workspace holds max(the sampler's samples, B*K*S*M)."""
+        K = candidate_count(candidates)
+        opts, held = self._opts(self._chunks(x_T), cond_lambda, bounds, None, None, pin, candidates=K)
+        p = self._sampler_inputs(state, x_T, goal, sigmas, n_steps, noise, candidates=K)
+        lv = [float(v) for v in (levels.detach().reshape(-1).tolist() if torch.is_tensor(levels) else levels)]
+        S = len(lv)
+        if score_noise.dim() != 4 or score_noise.shape[0] != S or tuple(score_noise.shape[2:]) != (self.Ta, self.A):
+            raise ValueError(f"score noise is {tuple(score_noise.shape)}: {S} levels take ({S}, draws, {self.Ta}, {self.A})")
+        snz = self._in(score_noise)
+        sig = (C.c_float * max(S, 1))(*lv)
+        w = None
+        if weights is not None:
+            wl = [float(v) for v in (weights.detach().reshape(-1).tolist() if torch.is_tensor(weights) else weights)]
+            if len(wl) != S:
+                raise ValueError(f"weights hold {len(wl)} values, {S} levels take {S}")
+            w = (C.c_float * max(S, 1))(*wl)
+        best = torch.empty((p.B, self.Ta, self.A), device=self.device, dtype=torch.float32)
+        scores = torch.empty((p.N,), device=self.device, dtype=torch.float32)
+        index = torch.empty((p.B,), device=self.device, dtype=torch.int32)
+        spec = _lib.SelectSpec(C.sizeof(_lib.SelectSpec), sig, w, S, _ptr(snz), int(snz.shape[1]), _ptr(p.out), _ptr(scores),
+                               _ptr(index))
+        self._keep = (p.sig, p.nz, snz) + held  # the kernels that read them are only enqueued
+        tail = (p.B, K, _ptr(best), _ptr(p.ctx), opts, C.byref(spec), self._stream())
+        head = (self.handle, _ptr(p.tok), _ptr(p.tok2), _ptr(p.g), p.modality, _ptr(p.x))
+        if kind is None:
+            _lib.call(self.lib.mdt_sample_ddim_dev_select if p.dev else self.lib.mdt_sample_ddim_select, *head, p.sig_arg, p.n, *tail)
+        else:
+            _lib.call(self.lib.mdt_sample_dev_select if p.dev else self.lib.mdt_sample_select, *head, int(kind), C.byref(params),
+                      p.sig_arg, p.n, _ptr(p.nz), 0 if p.nz is None else p.nz.shape[0], *tail)
+        return best, index, scores, p.out, p.ctx
+
     def tape_release(self, tape: int) -> None:
         _lib.check(self.lib.mdt_tape_release(self.handle, tape))
 
