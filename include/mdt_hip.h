@@ -61,9 +61,12 @@ typedef struct {
     int32_t obs_dim;              /* multiple of 16                                                 */
     int32_t goal_dim;             /* multiple of 16                                                 */
     int32_t n_obs_token;          /* MDT-V: state tokens per sample (3); MDT: ignored (static+gripper).  The context is
-                                   * [sigma token] + goal + n_obs_token + [proprio token]: 1..16 tokens, 17..64 at head
-                                   * dim 32 / 48 / 64 */
-    int32_t goal_seq_len;         /* 1                                                              */
+                                   * [sigma token] + goal_seq_len + n_obs_token + [proprio token]: 1..16 tokens, 17..64 at
+                                   * head dim 32 / 48 / 64 */
+    int32_t goal_seq_len;         /* G >= 1: goal tokens per sample.  Every `goal` argument is (B, G, goal_dim); the G rows
+                                   * are embedded row by row and enter the context in order, bounded by the context rule
+                                   * above.  MDT with use_abs_pos_emb: goal token j adds pos_emb[:, j], the state rows
+                                   * pos_emb[:, G] */
     int32_t action_seq_len;       /* Ta <= 16; 17..64 at head dim 32 / 48 / 64                      */
     int32_t use_mlp_goal;         /* goal_emb / lang_emb are Linear-GELU-Linear                     */
     int32_t use_modality_encoder; /* separate lang_emb                                              */
@@ -78,8 +81,8 @@ typedef struct {
                                    * (MDTV, mdtv_transformer.py:178-185) / h = d (MDT, mdt_transformer.py:170-177) */
     int32_t bias;                 /* reference 'bias' flag: biases on c_proj / MLP / LayerNorms     */
     float   sigma_data;           /* GCDenoiser.sigma_data                                          */
-    int32_t no_goal_conditioning; /* 1: constructor kwarg goal_conditioned=False.  MDTV: the goal token FOLLOWS the
-                                     state tokens (mdtv_transformer.py:284-299); MDT: no goal token at all, which
+    int32_t no_goal_conditioning; /* 1: constructor kwarg goal_conditioned=False.  MDTV: the goal rows FOLLOW the
+                                     state tokens (mdtv_transformer.py:284-299); MDT: no goal rows at all, which
                                      the reference can only run with use_ada_conditioning=0 (mdt_transformer.py:326-334) */
     int32_t proprio_dim;          /* MDT-V: width of state['state_obs'] (1..16; conf/model/model/mdtv_transformer.yaml:11) */
     int32_t use_proprio;          /* MDT-V: 1 = every call carries state['state_obs'] (B, 1, proprio_dim), passed as
@@ -142,11 +145,11 @@ int64_t mdt_ws_generation(const mdt_model *m);
  *   tokens : MDT-V state['state_images'] (B, n_obs_token, obs_dim); MDT state['static'] (B,1,obs_dim)
  *   tokens2: MDT state['gripper'] (B,1,obs_dim); MDT-V: state['state_obs'] (B,1,proprio_dim) when the handle was
  *            created with use_proprio, else NULL
- *   goal   : (B, 1, goal_dim)
+ *   goal   : (B, goal_seq_len, goal_dim) -- here and in every entry point below that takes a goal
  *   honour_modality: 1 = pick lang_emb when modality==LANG (MDT-V always; MDT forward_enc_only),
  *                    0 = always goal_emb (MDT.forward -> enc_only_forward, mdt_transformer.py:215)
  *   ctx_out: (B, Te, d) or NULL -- the value the reference caches as inner_model.latent_encoder_emb
- * Te = [sigma token] + goal + state tokens + [proprio token] <= 64 (above 16: head dim 32 / 48 / 64).  The decoder's
+ * Te = [sigma token] + goal_seq_len goal rows + state tokens + [proprio token] <= 64 (above 16: head dim 32 / 48 / 64).  The decoder's
  * cross-attention is causal on its Ta x Te score matrix, top-left aligned: query row t sees context rows j <= t, so rows
  * j >= Ta reach the decoder only through the encoder's self-attention (as in the reference), and above 16 tokens the
  * cross-attention launches stage the first min(Ta, Te) K / V rows of a sample only. */
@@ -500,7 +503,7 @@ mdt_status mdt_sample_dpm_adaptive(mdt_model *m, const float *tokens, const floa
  * Each call is its family's full form with opts = {cond_lambda} (mdt_sample_dpm_adaptive_guided: its unguided twin plus
  * `cond_lambda`). At lambda == 1, and on a model without a goal token (goal_conditioned=False with MDT, or with MDT-V and
  * use_proprio: there `uncond` changes nothing), it runs the unguided call and gives its bits. Otherwise ONE call runs the
- * sampler loop over 2B samples: [0, B) conditional, [B, 2B) the same state tokens with a zero goal (and the same `modality`
+ * sampler loop over 2B samples: [0, B) conditional, [B, 2B) the same state tokens with every one of the goal_seq_len goal rows zero (and the same `modality`
  * embedder). The 2B encoder inputs are staged inside the stream (handle-owned buffers, no host synchronisation: capture-safe
  * like the unguided calls); the encoder, the cross-attention K/V and every decoder pass run at 2B; each action head reads rows
  * r and r + B Ta, combines them and updates the B samples of state. The noise rows are those of the unguided call at B (the

@@ -270,6 +270,8 @@ hipError_t mdt_launch_xattn_apply(const mdt_xapply_args& a, hipStream_t s, int c
 // the collapsed cross-attention + the LayerNorm-prologue Linear on its output rows in one launch (k_xattn_gemm_smallm)
 hipError_t mdt_launch_xattn_gemm(const mdt_xapply_args& x, const mdt_gemm_args& g, hipStream_t s, int ctx_div = 1);
 size_t mdt_xattn_lds_floats(int D, int H);  // LDS floats of the collapsed cross-attention body (xattn_tile)
+// x[(b * gout + goff + j)][:] += tab[j][:], j < gin, b < B: a (gin, D) table added to gin consecutive rows of every group of gout
+hipError_t mdt_launch_add_group_rows(float* x, const float* tab, int64_t B, int gin, int gout, int goff, int D, hipStream_t s);
 // ---- Perceiver resampler kernels ----
 // media (B, T, n, D) + time_pos_emb[t] * mask[b][t] -> out (same shape); mask may be nullptr
 hipError_t mdt_launch_add_time_emb(const float* media, const float* tpe, const uint8_t* mask, float* out, int64_t B,

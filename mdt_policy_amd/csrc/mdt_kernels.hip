@@ -1803,6 +1803,25 @@ __global__ void k_bcast_rows(const float* __restrict__ src, float* __restrict__ 
     st4(out + i * 4, ldg4(src + (i % per4) * 4));
 }
 
+// x[(b * gout + goff + j)][:] += tab[j][:] for j < gin: MDT's position rows of a goal of several tokens (the GEMM epilogues' rowvec
+// is one vector per launch).  n4 = B * gin * D / 4 float4s, d4 = D / 4.
+__global__ void k_add_group_rows(float* __restrict__ x, const float* __restrict__ tab, int64_t n4, int gin, int gout, int goff, int d4) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const int64_t row = i / d4;
+    const int c = (int)(i - row * d4), j = (int)(row % gin);
+    float* p = x + (((row / gin) * gout + goff + j) * d4 + c) * 4;
+    const f32x4 v = ldg4(p), e = ldg4(tab + ((int64_t)j * d4 + c) * 4);
+    st4(p, v + e);
+}
+
+hipError_t mdt_launch_add_group_rows(float* x, const float* tab, int64_t B, int gin, int gout, int goff, int D, hipStream_t s) {
+    if (!x || !tab || B < 1 || gin < 1 || goff < 0 || goff + gin > gout || D < 4 || (D & 3)) return hipErrorInvalidValue;
+    const int64_t n4 = B * gin * (D / 4);
+    hipLaunchKernelGGL(k_add_group_rows, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, x, tab, n4, gin, gout, goff, D / 4);
+    return hipGetLastError();
+}
+
 hipError_t mdt_launch_add_time_emb(const float* media, const float* tpe, const uint8_t* mask, float* out, int64_t B,
                                    int T, int n, int D, hipStream_t s) {
     const int64_t n4 = B * T * n * (D / 4);

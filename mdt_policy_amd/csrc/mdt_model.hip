@@ -320,7 +320,7 @@ extern "C" mdt_status mdt_create(const mdt_config* cfg, mdt_model** out) {
     if (!cfg || !out) return fail(MDT_ERR_INVALID_ARG, "mdt_create: null argument");
     const mdt_config& c = *cfg;
     if (c.arch != MDT_ARCH_MDTV && c.arch != MDT_ARCH_MDT) return fail(MDT_ERR_INVALID_ARG, "unknown arch %d", c.arch);
-    if (c.goal_seq_len != 1) return fail(MDT_ERR_UNSUPPORTED, "goal_seq_len must be 1");
+    if (c.goal_seq_len < 1) return fail(MDT_ERR_INVALID_ARG, "goal_seq_len %d: must be >= 1", c.goal_seq_len);
     if (c.embed_dim <= 0 || c.embed_dim % 16 || c.embed_dim > 512)
         return fail(MDT_ERR_UNSUPPORTED, "embed_dim %d: need a multiple of 16, <= 512", c.embed_dim);
     if (c.n_heads <= 0 || c.embed_dim % c.n_heads) return fail(MDT_ERR_INVALID_ARG, "embed_dim %% n_heads != 0");
@@ -349,12 +349,6 @@ extern "C" mdt_status mdt_create(const mdt_config* cfg, mdt_model** out) {
         return fail(MDT_ERR_INVALID_ARG, "use_proprio: only MDTVTransformer reads state['state_obs'] "
                                          "(MDTTransformer.process_state_embeddings returns None, mdt_transformer.py:309-316)");
     if (prop && (c.proprio_dim < 1 || c.proprio_dim > 16)) return fail(MDT_ERR_UNSUPPORTED, "proprio_dim must be 1..16");
-    {   // the context: [sigma token] + goal + state tokens + [proprio token]; 64 = the chunk kernels' rows and the rotary tables' positions
-        const int ctx_len = sig_tok + 1 + n_tok + (prop ? 1 : 0);
-        if (n_tok < 1 || ctx_len > MDT_ROPE_POSITIONS || (ctx_len > 16 && hd < 32))
-            return fail(MDT_ERR_UNSUPPORTED, "context length %d tokens at head dim %d: a context of 17..64 tokens needs head dim 32 / 48 / 64; head dim 16 "
-                                             "takes 1..16 (sigma token + goal + n_obs_token + proprio token must be >= 1 and <= 64)", ctx_len, hd);
-    }
     const bool gc = c.no_goal_conditioning == 0;
     if (!gc && c.arch == MDT_ARCH_MDT && c.use_ada_conditioning)
         return fail(MDT_ERR_UNSUPPORTED, "MDTTransformer with goal_conditioned=False needs use_ada_conditioning=False "
@@ -362,17 +356,28 @@ extern "C" mdt_status mdt_create(const mdt_config* cfg, mdt_model** out) {
     // MDT-V keeps the goal token of an un-conditioned model behind the state tokens -- unless the proprioceptive token
     // takes that place (concatenate_inputs, mdtv_transformer.py:291-294)
     const int has_goal = (gc || (c.arch == MDT_ARCH_MDTV && !prop)) ? 1 : 0;
+    const int Gs = c.goal_seq_len, n_goal = has_goal ? Gs : 0;
+    {   // the context: [sigma token] + goal rows + state tokens + [proprio token]; 64 = the chunk kernels' rows and the rotary tables' positions
+        // (the rule counts the goal's Gs rows for the layouts that drop them too, as it has always counted the one)
+        const int ctx_len = sig_tok + Gs + n_tok + (prop ? 1 : 0);
+        if (n_tok < 1 || ctx_len > MDT_ROPE_POSITIONS || (ctx_len > 16 && hd < 32))
+            return fail(MDT_ERR_UNSUPPORTED, "context length %d tokens at head dim %d (%d sigma + %d goal + %d state + %d proprio): a context of "
+                                             "17..64 tokens needs head dim 32 / 48 / 64; head dim 16 "
+                                             "takes 1..16 (sigma token + goal_seq_len + n_obs_token + proprio token must be >= 1 and <= 64)",
+                        ctx_len, hd, sig_tok, Gs, n_tok, prop ? 1 : 0);
+    }
     if (c.n_enc_layers < 0 || c.n_dec_layers < 1) return fail(MDT_ERR_INVALID_ARG, "bad layer counts");
     if (!(c.sigma_data > 0.f)) return fail(MDT_ERR_INVALID_ARG, "sigma_data must be > 0");
 
     mdt_model* m = new mdt_model();
     m->cfg = c;
     m->cond = cond; m->sig_tok = sig_tok;
-    m->D = c.embed_dim; m->H = c.n_heads; m->hd = hd; m->n_tok = n_tok; m->Te = sig_tok + has_goal + n_tok + (prop ? 1 : 0); m->Ta = c.action_seq_len;
+    m->D = c.embed_dim; m->H = c.n_heads; m->hd = hd; m->n_tok = n_tok; m->Te = sig_tok + n_goal + n_tok + (prop ? 1 : 0); m->Ta = c.action_seq_len;
+    m->Gs = Gs;
     m->Pd = prop ? c.proprio_dim : 0;
     m->p_row = prop ? m->Te - 1 : -1;
     m->g_row = !has_goal ? -1 : (gc ? sig_tok : sig_tok + n_tok);
-    m->tok_row = gc ? sig_tok + 1 : sig_tok;
+    m->tok_row = gc ? sig_tok + Gs : sig_tok;
     m->A = c.action_dim; m->Le = c.n_enc_layers; m->Ld = c.n_dec_layers; m->G = c.goal_dim; m->O = c.obs_dim;
 
     Bump count;
@@ -628,7 +633,7 @@ static void carve_ws(mdt_model* m, Bump& b, int64_t B) {
     }
     m->g_tok = b.take((size_t)B * guide_w1(m));
     m->g_tok2 = b.take((size_t)B * guide_w2(m));
-    m->g_goal = b.take((size_t)B * m->G);
+    m->g_goal = b.take((size_t)B * m->Gs * m->G);
 }
 
 extern "C" mdt_status mdt_reserve(mdt_model* m, int64_t max_batch) {
@@ -897,19 +902,23 @@ static mdt_status run_encode(mdt_model* m, const float* tokens, const float* tok
         a.gin = m->n_tok; a.gout = Te; a.goff = m->tok_row;
         LAUNCH(mdt_gemm_side_push_front(a, s));
     }
-    // goal token -> its row                                     (process_goal_embeddings, mdtv_transformer.py:268)
+    // goal rows -> their rows, Gs per sample                     (process_goal_embeddings, mdtv_transformer.py:268)
     if (m->g_row >= 0) {
+        const int Gs = m->Gs;
         const float* gin = goal;
         int64_t ld = m->G;
         if (c.use_mlp_goal) {
-            mdt_gemm_args a = gemm_args(goal, m->G, g0, m->hid, 2 * D, (int)B);
+            mdt_gemm_args a = gemm_args(goal, m->G, g0, m->hid, 2 * D, (int)(B * Gs));
             a.act = MDT_ACT_GELU;
             LAUNCH(mdt_launch_gemm(a, s));
             gin = m->hid; ld = 2 * D;
         }
-        mdt_gemm_args a = gemm_args(gin, ld, g2, m->h_enc, D, (int)B);
-        a.gin = 1; a.gout = Te; a.goff = m->g_row; a.rowvec = pos0;
+        mdt_gemm_args a = gemm_args(gin, ld, g2, m->h_enc, D, (int)(B * Gs));
+        a.gin = Gs; a.gout = Te; a.goff = m->g_row;
+        if (Gs == 1) a.rowvec = pos0;   // one position row for every row of the launch: it rides in the epilogue
         LAUNCH(mdt_launch_gemm(a, s));
+        // goal token j adds pos_emb[:, j]: one row-add launch over the B * Gs rows ("Goals of several tokens")
+        if (Gs > 1 && pos0) LAUNCH(mdt_launch_add_group_rows(m->h_enc, pos0, B, Gs, Te, m->g_row, D, s));
     }
     // The goal product above normally took the queued token embedding along.  Where it did not (a goal width or a geometry
     // override, mdt_op_set_gemm_geometry, that routes it away from the small-M kernel), the job must not stay at the head of
@@ -1300,7 +1309,7 @@ static mdt_status sampler_open(mdt_model* m, const SamplerRequest& a, mdt_guide 
     MDT_TRY(mdt_reserve(m, std::max(c->nb, a.score_rows())));
     if (!gd.on) return MDT_OK;
     const int w1 = guide_w1(m), w2 = a.tokens2 ? guide_w2(m) : 0;
-    LAUNCH(mdt_launch_guide_stage(a.tokens, a.tokens2, a.goal, m->g_tok, m->g_tok2, m->g_goal, (int)a.batch, w1, w2, m->G, c->s));
+    LAUNCH(mdt_launch_guide_stage(a.tokens, a.tokens2, a.goal, m->g_tok, m->g_tok2, m->g_goal, (int)a.batch, w1, w2, m->Gs * m->G, c->s));
     c->tokens = m->g_tok;
     c->tokens2 = a.tokens2 ? m->g_tok2 : nullptr;
     c->goal = m->g_goal;
@@ -1505,7 +1514,7 @@ static mdt_status score_run(mdt_model* m, const float* tokens, const float* toke
     const int honour = m->cfg.arch == MDT_ARCH_MDTV;
     if (sig_ctx) {
         const int w1 = guide_w1(m), w2 = tokens2 ? guide_w2(m) : 0;
-        LAUNCH(mdt_launch_score_repeat(tokens, tokens2, goal, m->g_tok, m->g_tok2, m->g_goal, batch, S, w1, w2, m->G, s));
+        LAUNCH(mdt_launch_score_repeat(tokens, tokens2, goal, m->g_tok, m->g_tok2, m->g_goal, batch, S, w1, w2, m->Gs * m->G, s));
         MDT_TRY(run_encode(m, m->g_tok, w2 ? m->g_tok2 : nullptr, m->g_goal, modality, honour, batch * S, m->ybuf, 1, nullptr, s));
         if (ctx_out) {  // the context of each observation at the last level, as the samplers leave the last step's
             const size_t row = (size_t)m->Te * m->D * sizeof(float);
@@ -2029,7 +2038,7 @@ extern "C" double mdt_flops_per_chunk(const mdt_model* m, int32_t n_steps) {
     if (!m) return 0.0;
     const double D = m->D, Te = m->Te, Ta = m->Ta, A = m->A, G = m->G, O = m->O;
     auto attn = [&](double Tq, double Tk) { return 2.0 * (2.0 * Tq * Tk * D); };
-    double goal = m->g_row < 0 ? 0.0 : (m->cfg.use_mlp_goal ? 2.0 * (G * 2 * D + 2 * D * D) : 2.0 * G * D);
+    double goal = m->g_row < 0 ? 0.0 : m->Gs * (m->cfg.use_mlp_goal ? 2.0 * (G * 2 * D + 2 * D * D) : 2.0 * G * D);
     double enc = goal + 2.0 * m->n_tok * O * D +
                  m->Le * (Te * 2.0 * (4 * D * D + 8 * D * D) + attn(Te, Te));
     double kv = m->Ld * Te * 2.0 * 2 * D * D;

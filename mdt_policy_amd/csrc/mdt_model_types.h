@@ -39,9 +39,11 @@ struct mdt_model {
     mdt_config cfg;
     int D, H, hd, Te, Ta, A, Le, Ld, G, O, n_tok;
     int cond = COND_ADALN;
-    int sig_tok = 0;  // 1 when the context starts with the sigma token (COND_TOKEN): Te = sig_tok + 1 + n_tok
-    // context rows: [sigma token] [goal] state tokens  (goal_conditioned, the default);
-    // goal_conditioned=False: MDTV [sigma] state tokens, goal ; MDT [sigma] state tokens (g_row = -1: no goal token)
+    int sig_tok = 0;  // 1 when the context starts with the sigma token (COND_TOKEN): Te = sig_tok + Gs + n_tok [+ 1 proprio]
+    int Gs = 1;       // cfg.goal_seq_len: goal rows per sample; the goal input is (B, Gs, G)
+    // context rows: [sigma token] [Gs goal rows] state tokens  (goal_conditioned, the default);
+    // goal_conditioned=False: MDTV [sigma] state tokens, Gs goal rows ; MDT [sigma] state tokens (g_row = -1: no goal rows)
+    // g_row: the first of the Gs consecutive goal rows
     int g_row = 0, tok_row = 1;
     // parameters
     float* arena = nullptr;

@@ -260,9 +260,9 @@ static void carve_tape(const mdt_model* m, Bump& b, Tape& t, int64_t B) {
     t.tokens = b.take(B * (m->cfg.arch == MDT_ARCH_MDTV ? m->n_tok : 1) * m->O);
     t.tokens2 = b.take(m->cfg.arch == MDT_ARCH_MDT ? B * m->O : B * m->Pd);  // MDT-V: state_obs (B, Pd) when use_proprio
     t.p_pre = b.take(m->p_row >= 0 ? B * 2 * D : 0); t.p_h = b.take(m->p_row >= 0 ? B * 2 * D : 0);
-    t.goal = b.take(B * m->G);
+    t.goal = b.take(B * m->Gs * m->G);
     t.action = b.take(Ma * m->A); t.noised = b.take(Ma * m->A); t.sigma = b.take(B); t.loss_part = b.take(MDT_LOSS_PARTS);
-    t.g_pre = b.take(B * 2 * D); t.g_h = b.take(B * 2 * D);
+    t.g_pre = b.take(B * m->Gs * 2 * D); t.g_h = b.take(B * m->Gs * 2 * D);
     t.enc.resize(m->Le);
     for (int l = 0; l < m->Le; ++l) carve_block(m, b, t.enc[l], Me, false);
     t.x_enc_out = b.take(Me * D);  // input of the first block / output chain starts here when Le == 0
@@ -325,6 +325,9 @@ static void carve_scratch(const mdt_model* m, Bump& b, mdt_train_state* ts, int6
                     std::pair<int, int>(2 * D, m->G), std::pair<int, int>(D, m->G), std::pair<int, int>(D, m->O)})
         need = std::max(need, mdt_linear_bwd_scratch(B, nk.first, nk.second));
     need = std::max(need, mdt_linear_bwd_scratch(B * m->n_tok, D, m->O));
+    if (m->Gs > 1)   // the goal embedder's layers at B * Gs rows
+        for (auto nk : {std::pair<int, int>(D, 2 * D), std::pair<int, int>(2 * D, m->G), std::pair<int, int>(D, m->G)})
+            need = std::max(need, mdt_linear_bwd_scratch(B * m->Gs, nk.first, nk.second));
     if (m->HP) need = std::max(need, mdt_linear_bwd_scratch(Ma, m->HP, D));
     ts->lin_scratch = b.take(need);
     if (dw_stream_mode()) {
@@ -341,7 +344,7 @@ static void carve_scratch(const mdt_model* m, Bump& b, mdt_train_state* ts, int6
     }
     ts->dF = b.take(Ma * m->A);
     // (Ma * A: d x of denoise_grad, steer and log_likelihood lands here; below max(O, G) columns only while A is)
-    ts->small = b.take(std::max<int64_t>({B * 2 * D, Mx * (int64_t)std::max(m->O, m->G), (int64_t)((m->A + 15) / 16 * 16) * m->HP,
+    ts->small = b.take(std::max<int64_t>({B * m->Gs * 2 * D, Mx * (int64_t)std::max(m->O, m->G), (int64_t)((m->A + 15) / 16 * 16) * m->HP,
                                           Ma * (int64_t)m->A}));
 }
 
@@ -514,7 +517,9 @@ static mdt_status enc_fwd(mdt_model* m, Tape& t, const float* tokens, const floa
         if (!tokens2) return fail(MDT_ERR_INVALID_ARG, "this handle was created with use_proprio: state_obs (tokens2) is required");
         HIP_TRY(hipMemcpyAsync(t.tokens2, tokens2, (size_t)B * m->Pd * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    HIP_TRY(hipMemcpyAsync(t.goal, goal, (size_t)B * m->G * sizeof(float), hipMemcpyDeviceToDevice, s));
+    const int Gs = m->Gs;
+    const int64_t Bg = B * Gs;  // goal rows of the batch
+    HIP_TRY(hipMemcpyAsync(t.goal, goal, (size_t)Bg * m->G * sizeof(float), hipMemcpyDeviceToDevice, s));
     t.lang = honour && c.use_modality_encoder && modality == MDT_MODALITY_LANG;
     const Lin& g0 = t.lang ? m->lang0 : m->goal0;
     const Lin& g2 = t.lang ? m->lang2 : m->goal2;
@@ -526,13 +531,15 @@ static mdt_status enc_fwd(mdt_model* m, Tape& t, const float* tokens, const floa
         const float* gin = t.goal;
         int64_t ld = m->G;
         if (c.use_mlp_goal) {
-            LAUNCH(mdt_launch_gemm(gemm_args(t.goal, m->G, g0, t.g_pre, 2 * D, (int)B), s));
-            LAUNCH(mdt_launch_act_fwd(t.g_pre, t.g_h, B * 2 * D, MDT_ACT_GELU, s));
+            LAUNCH(mdt_launch_gemm(gemm_args(t.goal, m->G, g0, t.g_pre, 2 * D, (int)Bg), s));
+            LAUNCH(mdt_launch_act_fwd(t.g_pre, t.g_h, Bg * 2 * D, MDT_ACT_GELU, s));
             gin = t.g_h; ld = 2 * D;
         }
-        mdt_gemm_args a = gemm_args(gin, ld, g2, x0, D, (int)B);
-        a.gin = 1; a.gout = Te; a.goff = m->g_row; a.rowvec = pos0;
+        mdt_gemm_args a = gemm_args(gin, ld, g2, x0, D, (int)Bg);
+        a.gin = Gs; a.gout = Te; a.goff = m->g_row;
+        if (Gs == 1) a.rowvec = pos0;
         LAUNCH(mdt_launch_gemm(a, s));
+        if (Gs > 1 && pos0) LAUNCH(mdt_launch_add_group_rows(x0, pos0, B, Gs, Te, m->g_row, D, s));  // goal token j adds pos_emb[:, j]
     }
     if (c.arch == MDT_ARCH_MDTV) {
         mdt_gemm_args a = gemm_args(t.tokens, m->O, m->tok, x0, D, (int)(B * m->n_tok));
@@ -950,21 +957,25 @@ static mdt_status enc_bwd_tail(mdt_model* m, Tape& t, float* grads, float* d_tok
     // token embeddings: the forward scattered their rows into the context
     const Lin& g0 = t.lang ? m->lang0 : m->goal0;
     const Lin& g2 = t.lang ? m->lang2 : m->goal2;
-    float* dg = ts->t_d;  // (B, D)
+    const int Gs = m->Gs;
+    const int64_t Bg = B * Gs;  // goal rows of the batch
+    float* dg = ts->t_d;  // (B * Gs, D)
     const bool has_goal = m->g_row >= 0;
-    if (has_goal) LAUNCH(mdt_launch_gather_rows(ts->dxe, dg, (int)B, D, 1, Te, m->g_row, s));
-    else if (d_goal) HIP_TRY(hipMemsetAsync(d_goal, 0, (size_t)B * m->G * sizeof(float), s));
+    if (has_goal) LAUNCH(mdt_launch_gather_rows(ts->dxe, dg, (int)Bg, D, Gs, Te, m->g_row, s));
+    else if (d_goal) HIP_TRY(hipMemsetAsync(d_goal, 0, (size_t)Bg * m->G * sizeof(float), s));
     const bool pos = c.arch == MDT_ARCH_MDT && c.use_abs_pos_emb;
     float* g_pos = pos ? grad_of(m, grads, m->pos_emb) : nullptr;
-    if (pos && has_goal) LAUNCH(mdt_launch_colsum(dg, D, (int)B, D, g_pos, 1, s));
+    // pos_emb row j: the column sum over the batch of goal row j (rows j, j + Gs, ... of dg: row stride Gs * D)
+    for (int j = 0; pos && has_goal && j < Gs; ++j)
+        LAUNCH(mdt_launch_colsum(dg + (int64_t)j * D, (int64_t)Gs * D, (int)B, D, g_pos + (int64_t)j * D, 1, s));
     if (!has_goal) {
         // goal_conditioned=False in MDTTransformer: the goal never enters the context
     } else if (c.use_mlp_goal) {
-        MDT_TRY(lin_bwd(m, grads, g2, t.g_h, 2 * D, dg, D, (int)B, ts->small, 2 * D, 0, s));
-        LAUNCH(mdt_launch_act_bwd(t.g_pre, ts->small, ts->small, B * 2 * D, MDT_ACT_GELU, s));
-        MDT_TRY(lin_bwd(m, grads, g0, t.goal, m->G, ts->small, 2 * D, (int)B, d_goal, m->G, 0, s));
+        MDT_TRY(lin_bwd(m, grads, g2, t.g_h, 2 * D, dg, D, (int)Bg, ts->small, 2 * D, 0, s));
+        LAUNCH(mdt_launch_act_bwd(t.g_pre, ts->small, ts->small, Bg * 2 * D, MDT_ACT_GELU, s));
+        MDT_TRY(lin_bwd(m, grads, g0, t.goal, m->G, ts->small, 2 * D, (int)Bg, d_goal, m->G, 0, s));
     } else {
-        MDT_TRY(lin_bwd(m, grads, g2, t.goal, m->G, dg, D, (int)B, d_goal, m->G, 0, s));
+        MDT_TRY(lin_bwd(m, grads, g2, t.goal, m->G, dg, D, (int)Bg, d_goal, m->G, 0, s));
     }
     if (m->p_row >= 0) {
         // proprio_emb: token = Linear2(mish(Linear0(state_obs))); the narrow first layer's weight gradient lands in the

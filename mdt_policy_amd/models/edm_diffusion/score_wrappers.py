@@ -367,7 +367,7 @@ class GCDenoiser(nn.Module):
         im.latent_encoder_emb = ctx
         B = ctx.shape[0]
         prev = self._ctx_key
-        # _goals() returns its argument unchanged for the usual (B,1,G) goal, so id(goal) identifies it
+        # _goals() returns its argument unchanged for the usual (B, goal_seq_len, goal_dim) goal, so id(goal) identifies it
         self._ctx_key = (id(state), id(g), B, eng.ctx_generation) if g is goal else None
         try:
             yield ctx

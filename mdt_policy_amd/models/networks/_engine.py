@@ -117,6 +117,14 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def check_goal_rows(goal: torch.Tensor, goal_seq_len: int) -> None:
+    """A goal holds goal_seq_len rows per sample: (B, goal_seq_len, goal_dim), or (B, goal_dim) where goal_seq_len is 1."""
+    rows = goal.shape[1] if goal.dim() >= 3 else 1
+    if goal_seq_len > 1 and rows != goal_seq_len:
+        raise ValueError(f"goal has {rows} token(s) per sample, shape {tuple(goal.shape)}; this model was built with "
+                         f"goal_seq_len={goal_seq_len} and takes (B,{goal_seq_len},goal_dim)")
+
+
 class HipEngine:
     def __init__(self, module: nn.Module, cfg: _lib.MDTConfig, device: torch.device):
         if device.type != "cuda":
@@ -139,12 +147,13 @@ class HipEngine:
         self._uploaded: Dict[str, tuple] = {}
         self.ctx_generation = 0  # bumped by every call that rewrites the handle's cached context (encoder output, K|V, folds)
         self.sigma_in_context = not cfg.use_ada_conditioning  # sigma embedding is the first context token
-        # goal_conditioned=False: MDTV keeps the goal token (behind the state tokens), MDT has none
+        # goal_conditioned=False: MDTV keeps the goal rows (behind the state tokens), MDT has none
         # (and MDTV gives it up when the proprioceptive token takes that place, mdtv_transformer.py:291-294)
         self.proprio = bool(cfg.use_proprio)
         self.has_goal_token = not (cfg.no_goal_conditioning and (cfg.arch == 1 or self.proprio))
-        self.Te = int(self.sigma_in_context) + int(self.has_goal_token) + (cfg.n_obs_token if cfg.arch == 0 else 2) + \
-            int(self.proprio)
+        self.goal_seq_len = int(cfg.goal_seq_len)  # goal rows per sample: the goal is (B, goal_seq_len, goal_dim)
+        self.Te = int(self.sigma_in_context) + int(self.has_goal_token) * self.goal_seq_len + \
+            (cfg.n_obs_token if cfg.arch == 0 else 2) + int(self.proprio)
         self.Ta, self.A, self.D = cfg.action_seq_len, cfg.action_dim, cfg.embed_dim
 
     def __del__(self):
@@ -279,9 +288,11 @@ class HipEngine:
         return st, gr, B
 
     def _goal(self, goal: torch.Tensor, B: int) -> torch.Tensor:
+        G = self.goal_seq_len
+        check_goal_rows(goal, G)
         g = self._in(goal)
-        if g.numel() != B * self.cfg.goal_dim:
-            raise ValueError(f"goal must hold (B,1,{self.cfg.goal_dim}) values, got {tuple(goal.shape)}")
+        if g.numel() != B * G * self.cfg.goal_dim:
+            raise ValueError(f"goal must hold (B,{G},{self.cfg.goal_dim}) values, got {tuple(goal.shape)}")
         return g
 
     def _modality(self, state: dict) -> int:
@@ -893,6 +904,7 @@ class HipScoreNetwork(nn.Module):
         states_length = self.n_obs_token if self._arch == "mdtv" else 1
         if goals.shape[1] == states_length and goals.shape[1] != 1 and self.goal_seq_len == 1:
             goals = goals[:, :1, :]
+        check_goal_rows(goals, self.goal_seq_len)  # a handle is built for one layout; checked before anything is enqueued
         goal_p = float(self._pdrops[4])
         if self.training and goal_p > 0.0:
             mask = torch.bernoulli(torch.ones(goals.shape, device=goals.device) * goal_p)

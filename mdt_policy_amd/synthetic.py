@@ -81,10 +81,11 @@ def fill_state_dict(named_shapes: Iterable[Tuple[str, Tuple[int, ...]]], seed: i
 
 
 def sampler_inputs(batch: int, cfg: dict, seed: int = 1, arch: str = "mdtv") -> Dict[str, np.ndarray]:
-    """Synthetic tokens of SURVEY.md 8(d): state ~ N(0,1), goal ~ N(0,1), noise ~ N(0,1)."""
+    """Synthetic tokens of SURVEY.md 8(d): state ~ N(0,1), goal ~ N(0,1), noise ~ N(0,1).  The goal is (batch, goal_seq_len,
+    goal_dim); with goal_seq_len = 1 its values are what they have always been."""
     d_obs = int(cfg["obs_dim"])
     out = {
-        "goal": normal("goal", (batch, 1, int(cfg["goal_dim"])), seed),
+        "goal": normal("goal", (batch, int(cfg.get("goal_seq_len", 1)), int(cfg["goal_dim"])), seed),
         "noise": normal("noise", (batch, int(cfg["action_seq_len"]), int(cfg["action_dim"])), seed),
     }
     if arch == "mdtv":
