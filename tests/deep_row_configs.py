@@ -3,8 +3,7 @@ kernels (mdt_policy_amd/csrc/mdt_route.h, mdt_route_train.h), in the style of te
 geometries 5 and 9), 8192 rows (the tall and weight-stationary bodies, k_gemm_tn's 192-wide tiles, k_gemm_tn_split) and the narrow
 weight gradients' 512 row slices at more than four rows each.  Shared by tests/test_gpu_deep_row_training.py and by
 tests/test_route_table.py, which ties every batch here to the route it is there for (tests/c_client/route_table.cpp: deep/ lines)."""
-from mdt_policy_amd import configs
-from tests.envelope_configs import _case
+from tests.envelope_configs import envelope_of
 
 # name -> (architecture, configs factory, overrides, proprio): the form the golden fixtures' meta records (tests/helpers.py: cfg_of)
 DEEP_SPEC = {
@@ -25,7 +24,7 @@ DEEP_SPEC = {
     "mdt_ta40": ("mdt", "mdt_default", dict(action_seq_len=40), False),
 }
 
-DEEP_ENVELOPE = {name: _case(configs.NAMED[factory](**ov), arch=arch, proprio=prop) for name, (arch, factory, ov, prop) in DEEP_SPEC.items()}
+DEEP_ENVELOPE = envelope_of(DEEP_SPEC)
 
 # name -> batches of the eval-mode step; rows: what the batch is there for (decoder rows B * action_seq_len unless it says encoder)
 DEEP_BATCHES = {

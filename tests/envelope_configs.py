@@ -17,6 +17,17 @@ def _case(cfg, arch="mdtv", proprio=False):
     return dict(cfg=cfg, arch=arch, proprio=proprio)
 
 
+def envelope_of(spec):
+    """{name: cfg, arch, proprio} of a SPEC table {name: (arch, factory of configs.NAMED, overrides, proprio)}."""
+    return {name: _case(configs.NAMED[factory](**ov), arch=arch, proprio=prop) for name, (arch, factory, ov, prop) in spec.items()}
+
+
+# the shipped MDT-V as mdt_config fields: what the *_REFUSED_AT_CREATE tables of the families vary
+SHIPPED_MDT_CONFIG = dict(arch=0, embed_dim=384, n_heads=8, n_enc_layers=1, n_dec_layers=2, action_dim=7, obs_dim=384, goal_dim=512, n_obs_token=3,
+                          goal_seq_len=1, action_seq_len=10, use_mlp_goal=1, use_modality_encoder=1, use_abs_pos_emb=1, use_rot_embed=0,
+                          use_ada_conditioning=1, use_noise_encoder=0, linear_output=1, bias=0, sigma_data=0.5)
+
+
 # name -> configuration, architecture, whether the calls carry state["state_obs"] (the proprioceptive token, switched on
 # at run time)
 ENVELOPE = {

@@ -3,8 +3,10 @@ goal is (B, G, goal_dim); its G embedded rows enter the encoder context: [sigma 
 token] (goal_conditioned=False: MDT-V keeps the G rows behind the state tokens).  Shared by the GPU tests
 (tests/test_gpu_goal_seq*.py), the CPU checks (tests/test_cpu_goal_seq.py, tests/test_goal_seq_golden.py) and the recorder
 tests/golden/make_golden_goal_seq.py."""
-from mdt_policy_amd import configs
-from tests.envelope_configs import _case
+import functools
+
+from tests import long_context_configs
+from tests.envelope_configs import SHIPPED_MDT_CONFIG as _BASE, envelope_of
 
 # name -> (architecture, configs factory, overrides, proprio): the form the golden fixtures' meta records (tests/helpers.py: cfg_of)
 GOAL_SPEC = {
@@ -34,18 +36,14 @@ GOAL_SPEC = {
     "mdt_g5_plain": ("mdt", "mdt_tiny", dict(goal_seq_len=5, use_ada_conditioning=False), False),
 }
 
-GOAL_ENVELOPE = {name: _case(configs.NAMED[factory](**ov), arch=arch, proprio=prop) for name, (arch, factory, ov, prop) in GOAL_SPEC.items()}
+GOAL_ENVELOPE = envelope_of(GOAL_SPEC)
 
 
 def goal_rows(name):
     return GOAL_ENVELOPE[name]["cfg"]["goal_seq_len"]
 
 
-def context_len(name):
-    """Te of a case: [sigma token] + G + state tokens (n_obs_token; MDT: static and gripper) + [proprio] -- every case keeps its goal."""
-    e = GOAL_ENVELOPE[name]
-    cfg = e["cfg"]
-    return int(not cfg["use_ada_conditioning"]) + cfg["goal_seq_len"] + (cfg["n_obs_token"] if e["arch"] == "mdtv" else 2) + int(e["proprio"])
+context_len = functools.partial(long_context_configs.context_len, envelope=GOAL_ENVELOPE)   # Te of a case of this table
 
 
 def goal_row0(name):
@@ -67,9 +65,6 @@ GOAL_GOLDEN = ["g2_shipped", "g14_tile", "g3_no_goal_cond", "g3_plain", "mdt_g3_
 GOAL_UNRECORDABLE = ["mdt_g3_pos"]
 GOAL_GOLDEN_B = 2
 
-_BASE = dict(arch=0, embed_dim=384, n_heads=8, n_enc_layers=1, n_dec_layers=2, action_dim=7, obs_dim=384, goal_dim=512, n_obs_token=3,
-             goal_seq_len=1, action_seq_len=10, use_mlp_goal=1, use_modality_encoder=1, use_abs_pos_emb=1, use_rot_embed=0,
-             use_ada_conditioning=1, use_noise_encoder=0, linear_output=1, bias=0, sigma_data=0.5)
 # mdt_config fields mdt_create refuses -> (status, what the message names); 1 = MDT_ERR_INVALID_ARG, 2 = MDT_ERR_UNSUPPORTED
 GOAL_REFUSED_AT_CREATE = [
     (dict(_BASE, goal_seq_len=0), 1, [b"goal_seq_len 0", b">= 1"]),

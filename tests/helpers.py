@@ -52,15 +52,49 @@ def params_of(meta, dtype=torch.float32):
     return {k: v.to(dtype) for k, v in P.items()}
 
 
-def inputs_of(meta, dtype=torch.float32, batch=None):
-    cfg = cfg_of(meta)
-    inp = synthetic.sampler_inputs(batch or meta["B"], cfg, meta["input_seed"], meta["arch"])
-    t = {k: torch.from_numpy(v).to(dtype) for k, v in inp.items()}
-    if meta["arch"] == "mdtv":
-        state = {"state_images": t["state_images"], "modality": meta["modality"]}
+def observation(cfg, arch, proprio, B, seed, dtype=torch.float32, obs_seed=None):
+    """(state, goal, noise) on the host from synthetic.sampler_inputs; with ``proprio`` also state_obs (B, 1, proprio_dim), drawn
+    at ``obs_seed`` (``seed`` when that is None)."""
+    t = {k: torch.from_numpy(v).to(dtype) for k, v in synthetic.sampler_inputs(B, cfg, seed, arch).items()}
+    if arch == "mdtv":
+        state = {"state_images": t["state_images"], "modality": "lang"}
     else:
-        state = {"static": t["static"], "gripper": t["gripper"], "modality": meta["modality"]}
+        state = {"static": t["static"], "gripper": t["gripper"], "modality": "lang"}
+    if proprio:
+        obs_seed = seed if obs_seed is None else obs_seed
+        state["state_obs"] = torch.from_numpy(synthetic.normal("state_obs", (B, 1, cfg["proprio_dim"]), obs_seed)).to(dtype)
     return state, t["goal"], t["noise"]
+
+
+def inputs_of(meta, dtype=torch.float32, batch=None):
+    state, goal, noise = observation(cfg_of(meta), meta["arch"], False, batch or meta["B"], meta["input_seed"], dtype)
+    return dict(state, modality=meta["modality"]), goal, noise
+
+
+def to(state, fn):
+    """The observation dict with ``fn`` applied to its tensors."""
+    return {k: (fn(v) if torch.is_tensor(v) else v) for k, v in state.items()}
+
+
+def cuda(t):
+    return to(t, torch.Tensor.cuda) if isinstance(t, dict) else t.cuda()
+
+
+def rich_weights(model, seed=5):
+    """Loads the 'rich' synthetic weights of the model's own state_dict() shapes (strict=False: rotary buffers as drawn, lang_emb
+    not aliased -- unlike params_of's recipe, which recorded fixtures rest on) and returns them, {name: float32 tensor}."""
+    shapes = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]
+    P = {k: torch.from_numpy(v) for k, v in synthetic.fill_state_dict(shapes, seed, "rich").items()}
+    model.load_state_dict(P, strict=False)
+    return P
+
+
+def rich_model(cfg):
+    """(GCDenoiser(cfg, 0.5) on the host with rich_weights, those weights); the caller moves it: ``.cuda().eval()``."""
+    from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
+    torch.manual_seed(0)
+    m = GCDenoiser(cfg, 0.5)
+    return m, rich_weights(m)
 
 
 RTOL, ATOL = 1e-3, 1e-4  # BASELINE.json north_star parity gate

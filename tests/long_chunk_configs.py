@@ -1,8 +1,7 @@
 """Model configurations with action chunks of 17 .. 64 steps (mdt_create accepts them at head dims 32 / 48 / 64), in the style of
 tests/envelope_configs.py.  Shared by the GPU tests (tests/test_gpu_long_chunks.py), the CPU check that mdt_create's
 validation accepts every one of them (tests/test_cpu_long_chunks_abi.py) and the recorder tests/golden/make_golden_long.py."""
-from mdt_policy_amd import configs
-from tests.envelope_configs import _case
+from tests.envelope_configs import SHIPPED_MDT_CONFIG as _BASE, envelope_of
 
 # name -> (architecture, configs factory, overrides, proprio): the form the golden fixtures' meta records (tests/helpers.py: cfg_of)
 LONG_SPEC = {
@@ -29,15 +28,12 @@ LONG_SPEC = {
     "ta20_mlp_head_proprio": ("mdtv", "mdtv_default", dict(linear_output=False, action_seq_len=20), True),
 }
 
-LONG_ENVELOPE = {name: _case(configs.NAMED[factory](**ov), arch=arch, proprio=prop) for name, (arch, factory, ov, prop) in LONG_SPEC.items()}
+LONG_ENVELOPE = envelope_of(LONG_SPEC)
 
 # recorded from the reference by tests/golden/make_golden_long.py at B = 2 (tests/golden/g19_long_<name>.npz)
 LONG_GOLDEN = ["ta17_hd48", "ta33_rope_hd64", "ta48_plain", "mdt_ta40_hd64"]
 LONG_GOLDEN_B = 2
 
-_BASE = dict(arch=0, embed_dim=384, n_heads=8, n_enc_layers=1, n_dec_layers=2, action_dim=7, obs_dim=384, goal_dim=512, n_obs_token=3,
-             goal_seq_len=1, action_seq_len=10, use_mlp_goal=1, use_modality_encoder=1, use_abs_pos_emb=1, use_rot_embed=0,
-             use_ada_conditioning=1, use_noise_encoder=0, linear_output=1, bias=0, sigma_data=0.5)
 # mdt_config fields mdt_create refuses -> status (1 = MDT_ERR_INVALID_ARG, 2 = MDT_ERR_UNSUPPORTED)
 LONG_REFUSED_AT_CREATE = [
     (dict(_BASE, embed_dim=128, obs_dim=128, action_seq_len=17), 2),                      # head dim 16 keeps 1..16

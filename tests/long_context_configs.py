@@ -2,8 +2,7 @@
 tests/long_chunk_configs.py.  The context of MDT-V is [sigma token] + goal + n_obs_token state tokens + [proprio token].  Shared by
 the GPU tests (tests/test_gpu_long_context.py, tests/test_gpu_long_context_options.py), the CPU check that mdt_create's validation
 accepts every one of them (tests/test_cpu_long_context_abi.py) and the recorder tests/golden/make_golden_ctx.py."""
-from mdt_policy_amd import configs
-from tests.envelope_configs import _case
+from tests.envelope_configs import SHIPPED_MDT_CONFIG as _BASE, envelope_of
 
 _ROPE_HD64 = dict(embed_dim=256, obs_dim=256, goal_dim=384, n_heads=4)   # goal_dim 384: 512 = 2 * obs_dim is the goal truncation mdt_create refuses
 
@@ -35,13 +34,15 @@ CTX_SPEC = {
     "ctx18_a64": ("mdtv", "mdtv_default", dict(action_dim=64, n_obs_token=17), False),
 }
 
-CTX_ENVELOPE = {name: _case(configs.NAMED[factory](**ov), arch=arch, proprio=prop) for name, (arch, factory, ov, prop) in CTX_SPEC.items()}
+CTX_ENVELOPE = envelope_of(CTX_SPEC)
 
 
-def context_len(name):
-    """Te of a case: [sigma token] + goal + n_obs_token + [proprio] (every case of the table keeps its goal token)."""
-    e = CTX_ENVELOPE[name]
-    return int(not e["cfg"]["use_ada_conditioning"]) + 1 + e["cfg"]["n_obs_token"] + int(e["proprio"])
+def context_len(name, envelope=CTX_ENVELOPE):
+    """Te of a case: [sigma token] + goal_seq_len + state tokens (n_obs_token; MDT: static and gripper) + [proprio] -- every case of
+    the tables keeps its goal."""
+    e = envelope[name]
+    cfg = e["cfg"]
+    return int(not cfg["use_ada_conditioning"]) + cfg["goal_seq_len"] + (cfg["n_obs_token"] if e["arch"] == "mdtv" else 2) + int(e["proprio"])
 
 
 # (Ta, Te, head dim) of every case
@@ -51,9 +52,6 @@ CTX_SHAPES = {name: (e["cfg"]["action_seq_len"], context_len(name), e["cfg"]["em
 CTX_GOLDEN = ["ctx17_hd48", "ctx33_rope_hd64", "ctx32_plain", "ctx40_ta48", "ctx40_no_goal"]
 CTX_GOLDEN_B = 2
 
-_BASE = dict(arch=0, embed_dim=384, n_heads=8, n_enc_layers=1, n_dec_layers=2, action_dim=7, obs_dim=384, goal_dim=512, n_obs_token=3,
-             goal_seq_len=1, action_seq_len=10, use_mlp_goal=1, use_modality_encoder=1, use_abs_pos_emb=1, use_rot_embed=0,
-             use_ada_conditioning=1, use_noise_encoder=0, linear_output=1, bias=0, sigma_data=0.5)
 # mdt_config fields mdt_create refuses -> status (1 = MDT_ERR_INVALID_ARG, 2 = MDT_ERR_UNSUPPORTED)
 CTX_REFUSED_AT_CREATE = [
     (dict(_BASE, embed_dim=128, obs_dim=128, n_obs_token=16), 2),                      # head dim 16 keeps 1..16 tokens

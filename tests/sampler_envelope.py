@@ -18,8 +18,7 @@ from mdt_policy_amd.utils.action_pin import ActionPin
 from mdt_policy_amd.utils.action_steer import ActionSteer
 from oracle import mdt_oracle as O
 from tests.envelope_configs import ENVELOPE
-from tests.helpers import ATOL, RTOL, assert_close
-from tests.test_gpu_config_envelope import inputs
+from tests.helpers import ATOL, RTOL, assert_close, observation, rich_model
 
 NAMES = sorted(ENVELOPE)
 GUIDED_NAMES = [n for n in NAMES if ENVELOPE[n]["cfg"].get("goal_conditioned", True)]
@@ -48,11 +47,7 @@ def shape_of(name):
 def params(name):
     """{state_dict name: float32 tensor}: test_gpu_config_envelope.model_of's weights, without a device."""
     if name not in _PARAMS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        torch.manual_seed(0)
-        m = GCDenoiser(ENVELOPE[name]["cfg"], SD)
-        shapes = [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
-        _PARAMS[name] = {k: torch.from_numpy(v) for k, v in synthetic.fill_state_dict(shapes, 5, "rich").items()}
+        _PARAMS[name] = rich_model(ENVELOPE[name]["cfg"])[1]
     return _PARAMS[name]
 
 
@@ -142,7 +137,8 @@ def oracle_of(name):
 
 def case(name, B, seed=SEED):
     """(state, goal, x_T, fixed noise) in float32 on the host; x_T = 80 noise."""
-    state, goal, noise = inputs(name, B, seed)
+    e = ENVELOPE[name]
+    state, goal, noise = observation(e["cfg"], e["arch"], e["proprio"], B, seed)
     fixed = torch.from_numpy(synthetic.normal("sde_noise", tuple(noise.shape), seed + 100))
     return state, goal, noise * SMAX, fixed
 

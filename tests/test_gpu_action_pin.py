@@ -111,7 +111,7 @@ def test_guided_native_call_with_a_pin_equals_the_guided_host_loop(name, monkeyp
 def test_dpmpp_sde_with_tree_noise_and_a_pin(monkeypatch):
     model, state, goal, x = inputs(2)
     sig = sched()
-    tree = gs().NativeBrownianTreeNoiseSampler(x, sig[sig > 0].min(), sig.max(), seed=[17, 18])
+    tree = gs.NativeBrownianTreeNoiseSampler(x, sig[sig > 0].min(), sig.max(), seed=[17, 18])
     model, state, goal, x, pin, want, _ = reference("dpmpp_sde", 2, noise_sampler=tree)
     no_forward(monkeypatch)
     got = cpu.run("dpmpp_sde", model, state, x, goal, extra_args={"pin": pin}, noise_sampler=tree)
@@ -129,7 +129,7 @@ def test_bounds_pin_and_record_together_on_euler():
     assert len(seen) == N and min(scaler.changed) >= 0.10, scaler.changed
     assert float((want - pinned).abs().max()) > 100 * (ATOL + RTOL * float(want.abs().max()))
     torch.manual_seed(11)  # run()'s seed: the rows the host loop drew
-    noise = gs()._randn_rows(x, N)
+    noise = gs._randn_rows(x, N)
     with torch.no_grad():
         out, rec = model.sample_native("euler", state, x, goal, sched(), noise=noise, bounds=(lo, hi), record=True, pin=pin,
                                        **KINDS["euler"])
@@ -151,7 +151,7 @@ def test_device_schedule_with_a_pin(name, monkeypatch):
     no_forward(monkeypatch)
     torch.manual_seed(11)
     with torch.no_grad():
-        got = getattr(gs(), "sample_" + name)(model, state, x, goal, sched().cuda(), extra_args={"pin": pin}, **KINDS.get(name, {}))
+        got = getattr(gs, "sample_" + name)(model, state, x, goal, sched().cuda(), extra_args={"pin": pin}, **KINDS.get(name, {}))
     assert_close(got.cpu(), want.cpu(), what=f"{name}, sigmas on the device")
 
 
@@ -272,15 +272,15 @@ def test_dpm_adaptive_with_a_pin_runs_the_host_loop_and_matches_float64(monkeypa
     omodel, ostate, ogoal, ox, _ = cpu.oracle_case(2)
     _, known, pin, _ = cpu.oracle_loops("ddim", 2)
     with torch.no_grad():
-        want, winfo = gs().sample_dpm_adaptive(omodel, ostate, ox, ogoal, SMIN, SMAX, extra_args={"pin": pin}, return_info=True)
-        free = gs().sample_dpm_adaptive(omodel, ostate, ox, ogoal, SMIN, SMAX)
+        want, winfo = gs.sample_dpm_adaptive(omodel, ostate, ox, ogoal, SMIN, SMAX, extra_args={"pin": pin}, return_info=True)
+        free = gs.sample_dpm_adaptive(omodel, ostate, ox, ogoal, SMIN, SMAX)
     assert float((want - free)[:, :cpu.HARD].abs().max()) > 100 * (ATOL + RTOL * float(want.abs().max()))
     model, state, goal, x = inputs(2)
     calls, fwd = [], GCDenoiser.forward
     monkeypatch.setattr(GCDenoiser, "forward", lambda self, *a, **k: calls.append(k.get("pin")) or fwd(self, *a, **k))
     monkeypatch.setattr(GCDenoiser, "sample_dpm_adaptive_native", lambda *a, **k: pytest.fail("the native call takes no pin"))
     with torch.no_grad():
-        got, info = gs().sample_dpm_adaptive(model, state, x, goal, SMIN, SMAX, extra_args={"pin": pin}, return_info=True)
+        got, info = gs.sample_dpm_adaptive(model, state, x, goal, SMIN, SMAX, extra_args={"pin": pin}, return_info=True)
     print(f"dpm_adaptive: {info} on the GPU, {winfo} in float64")
     assert calls and calls[0] is pin, "the host loop did not hand the pin to forward"
     assert info == winfo
@@ -356,7 +356,7 @@ def test_plain_c_client_with_a_pin_matches_the_facade(tmp_path):
     cfg = model.inner_model._hip_config(0.5)
     B, n_steps = 2, 5
     state, goal, noise = guid.inputs("mdtv_default", B, 27)
-    sig = gs().get_sigmas_exponential(n_steps, 0.01, 80.0)
+    sig = gs.get_sigmas_exponential(n_steps, 0.01, 80.0)
     x_T = noise * 80.0
     prev = guid.inputs("mdtv_default", B, 28)[2]
     pin = ActionPin.overlap(prev, executed=4, hard=2, soft=3)

@@ -309,10 +309,10 @@ def test_candidates_call_takes_the_pair_projection():
     L.mdt_op_set_mlp_split(1)
     try:
         with torch.no_grad():
-            got = gs().sample_ddim(model, cuda(state), x.cuda(), goal.cuda(), sched(), extra_args={"candidates": K}).clone()
-            plain = gs().sample_ddim(model, cuda(wide), x.cuda(), wide_goal.cuda(), sched()).clone()
+            got = gs.sample_ddim(model, cuda(state), x.cuda(), goal.cuda(), sched(), extra_args={"candidates": K}).clone()
+            plain = gs.sample_ddim(model, cuda(wide), x.cuda(), wide_goal.cuda(), sched()).clone()
             L.mdt_op_set_mlp_split(0)
-            fp32 = gs().sample_ddim(model, cuda(state), x.cuda(), goal.cuda(), sched(), extra_args={"candidates": K}).clone()
+            fp32 = gs.sample_ddim(model, cuda(state), x.cuda(), goal.cuda(), sched(), extra_args={"candidates": K}).clone()
     finally:
         L.mdt_op_set_mlp_split(-1)
     assert tuple(got.shape)[0] == B * K

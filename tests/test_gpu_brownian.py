@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from mdt_policy_amd import _lib
+from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from tests.helpers import assert_close, cfg_of, inputs_of, load_fixture, params_of
 
 pytestmark = pytest.mark.gpu
@@ -33,11 +34,6 @@ def gpu_inputs(meta, B, seed):
     return state, goal.cuda(), noise.cuda()
 
 
-def gs():
-    from mdt_policy_amd.models.edm_diffusion import gc_sampling
-    return gc_sampling
-
-
 def _no_forward(monkeypatch):
     from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
 
@@ -58,7 +54,7 @@ def _seed_of(k):
 
 
 def _loop_sampler(x, sig, seed):
-    return gs().NativeBrownianTreeNoiseSampler(x, sig[sig > 0].min(), sig.max(), seed=seed)
+    return gs.NativeBrownianTreeNoiseSampler(x, sig[sig > 0].min(), sig.max(), seed=seed)
 
 
 def test_device_noise_equals_the_host_helper():
@@ -97,7 +93,7 @@ def _points(sig, r):
 def test_default_noise_runs_natively_and_matches_the_host_loop(B, monkeypatch):
     meta, model = _model()
     state, goal, noise = gpu_inputs(meta, B, 900 + B)
-    g = gs()
+    g = gs
     x = noise * 80.0
     for k, (sched, kw) in enumerate(CASES):
         sig = (g.get_sigmas_exponential if sched == "exp" else g.get_sigmas_karras)(6, 0.001, 80.0)
@@ -120,7 +116,7 @@ def test_default_noise_runs_natively_and_matches_the_host_loop(B, monkeypatch):
 def test_seeded_calls_repeat_and_the_next_call_differs(monkeypatch):
     meta, model = _model()
     state, goal, noise = gpu_inputs(meta, 16, 31)
-    g = gs()
+    g = gs
     sig = g.get_sigmas_exponential(10, 0.001, 80.0).cuda()
     _no_forward(monkeypatch)
     with torch.no_grad():
@@ -136,7 +132,7 @@ def test_seeded_calls_repeat_and_the_next_call_differs(monkeypatch):
 def test_device_schedule_tree_call_captures_on_a_stream():
     meta, model = _model()
     state, goal, noise = gpu_inputs(meta, 4, 41)
-    sig = gs().get_sigmas_karras(8, 0.001, 80.0).cuda()
+    sig = gs.get_sigmas_karras(8, 0.001, 80.0).cuda()
     seeds = torch.tensor([_seed_of(5)], dtype=torch.int64, device="cuda")
     x = noise * 80.0
     with torch.no_grad():
@@ -158,7 +154,7 @@ def test_device_schedule_tree_call_captures_on_a_stream():
 def test_rollout_sized_calls_replay_with_each_calls_seed(monkeypatch):
     meta, model = _model()
     state, goal, noise = gpu_inputs(meta, 1, 51)
-    g = gs()
+    g = gs
     sig = g.get_sigmas_exponential(10, 0.001, 80.0)
     model.__dict__.pop("_graphed_native", None)
     model.__dict__.pop("_graph_seen", None)
@@ -181,7 +177,7 @@ def test_rollout_sized_calls_replay_with_each_calls_seed(monkeypatch):
 def test_guided_default_noise_is_native_and_matches_the_guided_host_loop(monkeypatch):
     meta, model = _model()
     state, goal, noise = gpu_inputs(meta, 3, 61)
-    g = gs()
+    g = gs
     sig = g.get_sigmas_exponential(6, 0.01, 80.0)
     x = noise * 80.0
     lam = 2.0
@@ -199,7 +195,7 @@ def test_per_sample_seeds_through_the_sampler(monkeypatch):
     meta, model = _model()
     B = 7
     state, goal, noise = gpu_inputs(meta, B, 71)
-    g = gs()
+    g = gs
     sig = g.get_sigmas_karras(6, 0.001, 80.0)
     x = noise * 80.0
     seeds = [1000 + 17 * b for b in range(B)]

@@ -18,9 +18,11 @@ import pytest
 import torch
 
 from mdt_policy_amd import _lib, configs, synthetic
+from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from mdt_policy_amd.utils.action_pin import ActionPin
 from oracle import mdt_oracle as O
-from tests.helpers import assert_close
+from tests.family import Family
+from tests.helpers import assert_close, cuda, observation, to
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +39,8 @@ CONFIGS = {
     "sigma_token": dict(cfg=configs.mdtv_tiny(use_ada_conditioning=False), arch="mdtv", proprio=False),
     "mdt_tiny": dict(cfg=configs.mdt_tiny(), arch="mdt", proprio=False),
 }
-_MODELS, _REFS = {}, {}
+_REFS = {}
+model_of = Family(None, CONFIGS).model_of   # (model, float32 state dict): 'rich' synthetic weights
 
 
 @pytest.fixture(autouse=True)
@@ -46,46 +49,17 @@ def _inference():
         yield
 
 
-def gs():
-    from mdt_policy_amd.models.edm_diffusion import gc_sampling
-    return gc_sampling
-
-
 def sched():
-    return gs().get_sigmas_exponential(N, SMIN, SMAX)
-
-
-def model_of(name):
-    """(GCDenoiser on cuda:0 in eval mode, its float32 state dict): 'rich' synthetic weights."""
-    if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        torch.manual_seed(0)
-        m = GCDenoiser(CONFIGS[name]["cfg"], 0.5)
-        shapes = [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
-        P = {k: torch.from_numpy(v) for k, v in synthetic.fill_state_dict(shapes, 5, "rich").items()}
-        m.load_state_dict(P, strict=False)
-        _MODELS[name] = (m.cuda().eval(), P)
-    return _MODELS[name]
+    return gs.get_sigmas_exponential(N, SMIN, SMAX)
 
 
 def case(name, B, K, seed=None):
     """Host inputs of a (B, K) call: state and goal per observation, x_T per chunk, and the two replicated with repeat_interleave."""
     e = CONFIGS[name]
     seed = 1000 + 17 * B + K if seed is None else seed
-    t = {k: torch.from_numpy(v) for k, v in synthetic.sampler_inputs(B, e["cfg"], seed, e["arch"]).items()}
-    if e["arch"] == "mdtv":
-        state = {"state_images": t["state_images"], "modality": "lang"}
-    else:
-        state = {"static": t["static"], "gripper": t["gripper"], "modality": "lang"}
-    if e["proprio"]:
-        state["state_obs"] = torch.from_numpy(synthetic.normal("state_obs", (B, 1, e["cfg"]["proprio_dim"]), seed))
+    state, goal, _ = observation(e["cfg"], e["arch"], e["proprio"], B, seed)
     x = torch.from_numpy(synthetic.sampler_inputs(B * K, e["cfg"], seed + 1, e["arch"])["noise"]) * SMAX
-    wide = {k: (v.repeat_interleave(K, 0) if torch.is_tensor(v) else v) for k, v in state.items()}
-    return state, t["goal"], x, wide, t["goal"].repeat_interleave(K, 0)
-
-
-def cuda(state):
-    return {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in state.items()}
+    return state, goal, x, to(state, lambda v: v.repeat_interleave(K, 0)), goal.repeat_interleave(K, 0)
 
 
 def no_forward(mp):
@@ -110,9 +84,9 @@ def check_ddim(name, B, K, monkeypatch):
     want = oracle(name, O.sample_ddim, wide, x, wide_goal)
     no_forward(monkeypatch)
     with torch.no_grad():
-        got = gs().sample_ddim(model, cuda(state), x.cuda(), goal.cuda(), sched(), extra_args={"candidates": K})
+        got = gs.sample_ddim(model, cuda(state), x.cuda(), goal.cuda(), sched(), extra_args={"candidates": K})
         ctx = model.inner_model.latent_encoder_emb
-        plain = gs().sample_ddim(model, cuda(wide), x.cuda(), wide_goal.cuda(), sched())
+        plain = gs.sample_ddim(model, cuda(wide), x.cuda(), wide_goal.cuda(), sched())
     e = model._engine(state=cuda(state))
     assert tuple(got.shape) == (B * K, e.Ta, e.A) and tuple(ctx.shape) == (B, e.Te, e.D)
     assert_close(got.cpu(), want, what=f"{name} ({B}, {K}) against float64")
@@ -143,7 +117,7 @@ def test_ddim_on_the_explicit_cross_attention(name, B, K, monkeypatch):
 def run_kind(kind, model, state, x, goal, extra_args=None, **kw):
     torch.manual_seed(23)  # the noise rows of the ancestral kinds: one draw per step in the action's shape, so per chunk
     with torch.no_grad():
-        return getattr(gs(), "sample_" + kind)(model, state, x, goal, sched(), extra_args=extra_args, **kw)
+        return getattr(gs, "sample_" + kind)(model, state, x, goal, sched(), extra_args=extra_args, **kw)
 
 
 @pytest.mark.parametrize("kind", ["heun", "euler_ancestral", "dpmpp_2m", "dpmpp_sde"])
@@ -155,7 +129,7 @@ def test_plan_kinds(kind, monkeypatch):
     kw = {}
     if kind == "dpmpp_sde":  # tree noise, one tree per chunk: B*K seeds
         sig = sched()
-        kw["noise_sampler"] = gs().NativeBrownianTreeNoiseSampler(x.cuda(), sig[sig > 0].min(), sig.max(),
+        kw["noise_sampler"] = gs.NativeBrownianTreeNoiseSampler(x.cuda(), sig[sig > 0].min(), sig.max(),
                                                                  seed=[101 + i for i in range(B * K)])
     got = run_kind(kind, model, cuda(state), x.cuda(), goal.cuda(), {"candidates": K}, **kw)
     plain = run_kind(kind, model, cuda(wide), x.cuda(), wide_goal.cuda(), None, **kw)
@@ -301,7 +275,7 @@ def test_the_context_is_the_plain_calls_at_batch_b(name, B, K, lam):
 
 def test_repeats_replay_a_graph_with_the_eager_bits(monkeypatch):
     model, _ = model_of("mdtv_tiny")
-    g = gs()
+    g = gs
     monkeypatch.setattr(g, "_GRAPH_MODE", "auto")  # the rollout rule: chunks <= 8, from the third identical call on
     monkeypatch.setattr(g, "_GRAPH_SAMPLER", False)
     model.__dict__.pop("_graphed_samplers", None)
@@ -339,9 +313,9 @@ def test_a_four_dimensional_action_gives_the_same_bits_in_its_shape():
         flat = model.sample_ddim(state, x, goal, sched(), candidates=K)
         four = model.sample_ddim(state, x4, goal, sched(), candidates=K)
         torch.manual_seed(4)
-        flat_e = gs().sample_euler_ancestral(model, state, x, goal, sched(), extra_args={"candidates": K})
+        flat_e = gs.sample_euler_ancestral(model, state, x, goal, sched(), extra_args={"candidates": K})
         torch.manual_seed(4)
-        four_e = gs().sample_euler_ancestral(model, state, x4, goal, sched(), extra_args={"candidates": K})
+        four_e = gs.sample_euler_ancestral(model, state, x4, goal, sched(), extra_args={"candidates": K})
     assert tuple(four.shape) == tuple(x4.shape) and torch.equal(four.reshape(flat.shape), flat)
     assert tuple(four_e.shape) == tuple(x4.shape) and torch.equal(four_e.reshape(flat_e.shape), flat_e)
 

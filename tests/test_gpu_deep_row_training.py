@@ -14,11 +14,12 @@ import time
 import pytest
 import torch
 
-from mdt_policy_amd import configs, synthetic
+from mdt_policy_amd import synthetic
 from oracle import mdt_oracle as O
 from tests.deep_row_configs import DEEP_DROPOUT, DEEP_ENVELOPE, DEEP_REUSE, DEEP_SPEC, DEEP_SPLIT_OFF, DEEP_STEPS, rows_of
-from tests.helpers import assert_close, params_of
-from tests.test_gpu_wide_actions import SEEDS, hip_step, to
+from tests.family import Family
+from tests.helpers import assert_close, params_of, to
+from tests.test_gpu_wide_actions import SEEDS, hip_step
 
 pytestmark = pytest.mark.gpu
 
@@ -28,13 +29,8 @@ STEPS = [s for s in DEEP_STEPS if s != DEEP_SPLIT_OFF] + [DEEP_SPLIT_OFF]
 assert sorted(STEPS) == sorted(DEEP_STEPS)
 
 
-def meta_of(name):
-    """A fixture-style meta (tests/helpers.py: cfg_of, params_of) of a case."""
-    from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-    arch, factory, ov, proprio = DEEP_SPEC[name]
-    sd = GCDenoiser(configs.NAMED[factory](**ov), 0.5).state_dict()
-    return dict(config=factory, overrides=ov, arch=arch, proprio=proprio, B=2, modality="lang", profile="rich",
-                state_dict=[[k, list(v.shape)] for k, v in sd.items()], **SEEDS)
+F = Family(DEEP_SPEC, DEEP_ENVELOPE, SEEDS)   # the metas and observations; every test builds its own model (fresh_model)
+meta_of = F.meta_of
 
 
 def fresh_model(name, meta=None):
@@ -47,17 +43,9 @@ def fresh_model(name, meta=None):
 
 def inputs(name, B, seed):
     """(state, goal, loss inputs) on the host; state_obs (B, 1, proprio_dim) when the case switches the token on."""
-    e = DEEP_ENVELOPE[name]
-    cfg = e["cfg"]
-    t = {k: torch.from_numpy(v) for k, v in synthetic.sampler_inputs(B, cfg, seed, e["arch"]).items()}
-    if e["arch"] == "mdtv":
-        state = {"state_images": t["state_images"], "modality": "lang"}
-    else:
-        state = {"static": t["static"], "gripper": t["gripper"], "modality": "lang"}
-    if e["proprio"]:
-        state["state_obs"] = torch.from_numpy(synthetic.normal("state_obs", (B, 1, cfg["proprio_dim"]), seed))
-    li = {k: torch.from_numpy(v) for k, v in synthetic.loss_inputs(B, cfg, seed + 1).items()}
-    return state, t["goal"], li
+    state, goal, _ = F.inputs(name, B, seed)
+    li = {k: torch.from_numpy(v) for k, v in synthetic.loss_inputs(B, DEEP_ENVELOPE[name]["cfg"], seed + 1).items()}
+    return state, goal, li
 
 
 def oracle_step(name, B):

@@ -18,9 +18,10 @@ import pytest
 import torch
 
 from mdt_policy_amd import _lib, configs, synthetic
+from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from tests.envelope_configs import ENVELOPE
 from tests.guarded import GuardedSet, same_bits
-from tests.helpers import assert_close, cfg_of, load_fixture, params_of
+from tests.helpers import assert_close, cfg_of, cuda, load_fixture, observation, params_of, rich_model
 from tests.long_chunk_configs import LONG_ENVELOPE
 from tests.long_context_configs import CTX_ENVELOPE
 from tests.score_oracle import residual_score
@@ -37,11 +38,6 @@ _MODELS, _REFS = {}, {}
 def _inference():
     with torch.no_grad():
         yield
-
-
-def gs():
-    from mdt_policy_amd.models.edm_diffusion import gc_sampling
-    return gc_sampling
 
 
 def levels_of(S):
@@ -69,14 +65,14 @@ def entry(name):
 def model_of(name):
     """(GCDenoiser on cuda:0 in eval mode, its float32 state dict)"""
     if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
         cfg, _, _, P = entry(name)
-        torch.manual_seed(0)
-        m = GCDenoiser(cfg, 0.5)
         if P is None:
-            shapes = [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
-            P = {k: torch.from_numpy(v) for k, v in synthetic.fill_state_dict(shapes, 5, "rich").items()}
-        m.load_state_dict(P, strict=False)
+            m, P = rich_model(cfg)
+        else:   # a fixture's own weights
+            from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
+            torch.manual_seed(0)
+            m = GCDenoiser(cfg, 0.5)
+            m.load_state_dict(P, strict=False)
         _MODELS[name] = (m.cuda().eval(), P)
     return _MODELS[name]
 
@@ -85,20 +81,10 @@ def case(name, B, K, S, M, seed=None):
     """Host inputs: state and goal per observation, x0 (B*K, Ta, A), levels, noise (S, M, Ta, A)."""
     cfg, arch, proprio, _ = entry(name)
     seed = 2000 + 31 * B + 7 * K + 3 * S + M if seed is None else seed
-    t = {k: torch.from_numpy(v) for k, v in synthetic.sampler_inputs(B, cfg, seed, arch).items()}
-    if arch == "mdtv":
-        state = {"state_images": t["state_images"], "modality": "lang"}
-    else:
-        state = {"static": t["static"], "gripper": t["gripper"], "modality": "lang"}
-    if proprio:
-        state["state_obs"] = torch.from_numpy(synthetic.normal("state_obs", (B, 1, cfg["proprio_dim"]), seed))
+    state, goal, _ = observation(cfg, arch, proprio, B, seed)
     x0 = torch.from_numpy(synthetic.loss_inputs(B * K, cfg, seed + 1)["actions"])
     noise = torch.from_numpy(synthetic.normal("score_noise", (S, M) + tuple(x0.shape[1:]), seed + 2))
-    return state, t["goal"], x0, levels_of(S), noise
-
-
-def cuda(state):
-    return {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in state.items()}
+    return state, goal, x0, levels_of(S), noise
 
 
 def reference(name, B, K, S, M):
@@ -120,7 +106,7 @@ def native(name, B, K, S, M, weights=None, layout4=False):
     model, _ = model_of(name)
     state, goal, x0, levels, noise = case(name, B, K, S, M)
     x = x0.reshape((B, K) + tuple(x0.shape[1:])) if layout4 else x0
-    return gs().denoising_score(model, cuda(state), x.cuda(), goal.cuda(), levels, extra_args={"candidates": K}, noise=noise.cuda(),
+    return gs.denoising_score(model, cuda(state), x.cuda(), goal.cuda(), levels, extra_args={"candidates": K}, noise=noise.cuda(),
                                 weights=weights)
 
 
@@ -171,7 +157,7 @@ def test_a_chunk_alone_scores_like_the_same_chunk_among_three():
     among = native(name, B, K, S, M).cpu().double().reshape(B, K)
     _, bound = reference(name, B, K, S, M)
     for k in range(K):
-        alone = gs().denoising_score(model, cuda(state), x0[k::K].cuda(), goal.cuda(), levels, noise=noise.cuda()).cpu().double()
+        alone = gs.denoising_score(model, cuda(state), x0[k::K].cuda(), goal.cuda(), levels, noise=noise.cuda()).cpu().double()
         err = (alone - among[:, k]).abs()
         print(f"chunk {k} alone against among {K}: {float(err.max()):.3e} / bound {float(bound.reshape(B, K)[:, k].min()):.3e}")
         assert bool((err <= bound.reshape(B, K)[:, k]).all())
@@ -198,7 +184,7 @@ def test_best_candidates_takes_the_score_as_it_is():
     name, B, K = "mdtv_tiny", 3, 3
     _, _, x0, _, _ = case(name, B, K, 3, 2)
     score = native(name, B, K, 3, 2)
-    best, index = gs().best_candidates(x0.cuda(), score, K)
+    best, index = gs.best_candidates(x0.cuda(), score, K)
     want = score.reshape(B, K).argmax(1)
     assert torch.equal(index, want)
     assert torch.equal(best.cpu(), x0.reshape((B, K) + tuple(x0.shape[1:]))[torch.arange(B), want.cpu()])

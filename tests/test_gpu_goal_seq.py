@@ -12,71 +12,33 @@ import torch
 
 from mdt_policy_amd import configs, synthetic
 from oracle import mdt_oracle as O
+from tests.family import Family
 from tests.goal_seq_configs import GOAL_ENVELOPE, GOAL_GOLDEN, GOAL_SPEC, GOAL_TE, goal_rows
-from tests.helpers import assert_close, envelope_params, load_fixture, params_of
+from tests.helpers import assert_close, envelope_params, load_fixture, params_of, to
 
 pytestmark = pytest.mark.gpu
 
 NAMES = sorted(GOAL_ENVELOPE)
 SEEDS = dict(weight_seed=231, input_seed=232, loss_seed=233, ctx_seed=234, obs_seed=235)   # the recorder's
-_MODELS = {}
 
 
-def meta_of(name, overrides=None):
-    """A fixture-style meta (tests/helpers.py: cfg_of, params_of, inputs_of) of a case, recorded or not."""
-    from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-    arch, factory, ov, proprio = GOAL_SPEC[name]
-    ov = dict(ov, **(overrides or {}))
-    sd = GCDenoiser(configs.NAMED[factory](**ov), 0.5).state_dict()
-    return dict(config=factory, overrides=ov, arch=arch, proprio=proprio, B=2, modality="lang", profile="rich",
-                state_dict=[[k, list(v.shape)] for k, v in sd.items()], **SEEDS)
+class GoalFamily(Family):
+    def inputs(self, name, B, seed, dtype=torch.float32, cfg=None):
+        """(state, goal (B, G, goal_dim), noise) on the host; state_obs (B, 1, proprio_dim) when the case switches the token on."""
+        cfg = cfg or GOAL_ENVELOPE[name]["cfg"]
+        state, goal, noise = super().inputs(name, B, seed, dtype, cfg)
+        assert tuple(goal.shape) == (B, cfg["goal_seq_len"], cfg["goal_dim"])
+        return state, goal, noise
+
+    def hip_sample(self, name, B, seed, sig):
+        out = super().hip_sample(name, B, seed, sig)
+        ctx = self.model_of(name)[0].inner_model.latent_encoder_emb
+        assert tuple(ctx.shape) == (B, GOAL_TE[name], GOAL_ENVELOPE[name]["cfg"]["embed_dim"])
+        return out
 
 
-def model_of(name):
-    """(GCDenoiser on cuda:0 in eval mode, its meta) -- the 'rich' weights of the recorder."""
-    if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        meta = meta_of(name)
-        m = GCDenoiser(GOAL_ENVELOPE[name]["cfg"], 0.5)
-        m.load_state_dict(params_of(meta))
-        _MODELS[name] = (m.cuda().eval(), meta)
-    return _MODELS[name]
-
-
-def inputs(name, B, seed, dtype=torch.float32, cfg=None):
-    """(state, goal (B, G, goal_dim), noise) on the host; state_obs (B, 1, proprio_dim) when the case switches the token on."""
-    e = GOAL_ENVELOPE[name]
-    cfg = cfg or e["cfg"]
-    t = {k: torch.from_numpy(v).to(dtype) for k, v in synthetic.sampler_inputs(B, cfg, seed, e["arch"]).items()}
-    if e["arch"] == "mdtv":
-        state = {"state_images": t["state_images"], "modality": "lang"}
-    else:
-        state = {"static": t["static"], "gripper": t["gripper"], "modality": "lang"}
-    if e["proprio"]:
-        state["state_obs"] = torch.from_numpy(synthetic.normal("state_obs", (B, 1, cfg["proprio_dim"]), seed)).to(dtype)
-    assert tuple(t["goal"].shape) == (B, cfg["goal_seq_len"], cfg["goal_dim"])
-    return state, t["goal"], t["noise"]
-
-
-def to(state, fn):
-    return {k: (fn(v) if torch.is_tensor(v) else v) for k, v in state.items()}
-
-
-def oracle_sample(name, B, seed, sig):
-    e = GOAL_ENVELOPE[name]
-    _, meta = model_of(name)
-    st, goal, noise = inputs(name, B, seed, torch.float64)
-    return O.sample_ddim(params_of(meta, torch.float64), e["cfg"], st, noise * 80.0, goal, sig, arch=e["arch"], hoist=True)
-
-
-def hip_sample(name, B, seed, sig):
-    from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
-    model, _ = model_of(name)
-    state, goal, noise = inputs(name, B, seed)
-    with torch.no_grad():
-        out = gs.sample_ddim(model, to(state, torch.Tensor.cuda), noise.cuda() * 80.0, goal.cuda(), sig.cuda()).cpu()
-    assert tuple(model.inner_model.latent_encoder_emb.shape) == (B, GOAL_TE[name], GOAL_ENVELOPE[name]["cfg"]["embed_dim"])
-    return out
+F = GoalFamily(GOAL_SPEC, GOAL_ENVELOPE, SEEDS)
+meta_of, model_of, inputs, oracle_sample, hip_sample = F.meta_of, F.model_of, F.inputs, F.oracle_sample, F.hip_sample
 
 
 # ------------------------------------------------------------------------------------------------------------ 1. recordings

@@ -16,15 +16,16 @@ import numpy as np
 import pytest
 import torch
 
-from mdt_policy_amd import configs, synthetic
+from mdt_policy_amd import synthetic
 from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from mdt_policy_amd.utils.action_pin import ActionPin
 from mdt_policy_amd.utils.action_steer import ActionSteer
 from tests import sampler_envelope as E
 from tests import test_gpu_guidance as guid
+from tests.family import OptionFamily
 from tests.goal_seq_configs import GOAL_SPEC, GOAL_TE, goal_rows
 from tests.guarded import same_bits
-from tests.helpers import ATOL, RTOL, assert_close, cfg_of, inputs_of, params_of
+from tests.helpers import ATOL, RTOL, assert_close, cfg_of, cuda, params_of
 from tests.score_oracle import residual_score
 from tests.test_gpu_loglik_native import LL, check_info, chunks_of, parent_path, signs
 from tests.test_gpu_native_samplers import _host_loop
@@ -35,59 +36,19 @@ pytestmark = pytest.mark.gpu
 NAMES = ["g2_shipped", "g3_plain", "mdt_g3_pos"]
 B = 2
 EPS32 = float(np.finfo(np.float32).eps)
-_META, _MODELS, _ORACLES, _LOOPS = {}, {}, {}, {}
+assert not any(GOAL_SPEC[n][3] for n in NAMES)
 
 
-def meta_of(name):
-    """What a golden fixture's meta holds, for tests/helpers.py (cfg_of, params_of, inputs_of) and the helpers built on them."""
-    if name not in _META:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        arch, factory, ov, proprio = GOAL_SPEC[name]
-        assert not proprio
-        sd = GCDenoiser(configs.NAMED[factory](**ov), 0.5).state_dict()
-        _META[name] = dict(config=factory, overrides=ov, arch=arch, B=B, modality="lang", weight_seed=5, profile="rich",
-                           input_seed=E.SEED, loss_seed=62, ctx_seed=63, state_dict=[[k, list(v.shape)] for k, v in sd.items()])
-    return _META[name]
+class GoalOptions(OptionFamily):
+    def case(self, name, batch=B, seed=E.SEED):
+        """(state, goal (batch, G, goal_dim), x_T, fixed noise) in float32 on the host; x_T = 80 noise."""
+        state, goal, x, fixed = super().case(name, batch, seed)
+        assert tuple(goal.shape) == (batch, goal_rows(name), cfg_of(self.meta_of(name))["goal_dim"])
+        return state, goal, x, fixed
 
 
-def model_of(name):
-    if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        meta = meta_of(name)
-        m = GCDenoiser(cfg_of(meta), 0.5)
-        m.load_state_dict(params_of(meta))
-        _MODELS[name] = m.cuda().eval()
-    return _MODELS[name]
-
-
-def oracle_of(name):
-    if name not in _ORACLES:
-        meta = meta_of(name)
-        _ORACLES[name] = E.EnvelopeOracle(name, case=dict(cfg=cfg_of(meta), arch=meta["arch"]), P=params_of(meta))
-    return _ORACLES[name]
-
-
-def case(name, batch=B, seed=E.SEED):
-    """(state, goal (batch, G, goal_dim), x_T, fixed noise) in float32 on the host; x_T = 80 noise."""
-    state, goal, noise = inputs_of(dict(meta_of(name), input_seed=seed), batch=batch)
-    assert tuple(goal.shape) == (batch, goal_rows(name), cfg_of(meta_of(name))["goal_dim"])
-    fixed = torch.from_numpy(synthetic.normal("sde_noise", tuple(noise.shape), seed + 100))
-    return state, goal, noise * E.SMAX, fixed
-
-
-def cuda(t):
-    if isinstance(t, dict):
-        return {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in t.items()}
-    return t.cuda()
-
-
-def float64_loop(name, kind, extra=None):
-    """The float64 host loop of one sampler kind, computed once per (name, kind, options) and left unchanged."""
-    key = (name, kind, tuple(sorted((k, v if isinstance(v, float) else "") for k, v in (extra or {}).items())))
-    if key not in _LOOPS:
-        state, goal, x, fixed = case(name)
-        _LOOPS[key] = E.run(kind, oracle_of(name), E.wide(state), E.wide(x), E.wide(goal), E.wide(fixed), extra_args=dict(extra or {}))
-    return _LOOPS[key]
+F = GoalOptions(GOAL_SPEC, dict(weight_seed=5, input_seed=E.SEED, loss_seed=62, ctx_seed=63), B)
+meta_of, model_of, oracle_of, case, float64_loop = F.meta_of, F.model_of, F.oracle_of, F.case, F.float64_loop
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -15,10 +15,12 @@ import numpy as np
 import pytest
 import torch
 
-from mdt_policy_amd import _lib, configs, synthetic
+from mdt_policy_amd import _lib, configs
+from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from oracle import mdt_oracle as O
 from tests.envelope_configs import ENVELOPE
-from tests.helpers import assert_close
+from tests.family import Family
+from tests.helpers import assert_close, cuda  # noqa: F401 -- cuda: read as guid.cuda by other modules
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,40 +42,14 @@ FULL = [1, 16, 17, 39, 72, 128]
 BATCHES = {"mdtv_default": FULL, "mlp_head": [1, 17, 39, 72], "mdt_default": [1, 17, 39], "plain": [1, 17, 39],
            "h1_d64_min": [1, 17, 39, 800]}  # Ta = 1: 2B * 1 rows cross 1401 at B = 800
 LAMBDAS = (0.0, 0.5, 3.0)
-_MODELS = {}
 
 
 def tol(lam):
     return dict(rtol=1e-3, atol=1e-4 * (abs(lam) + abs(1 - lam)))
 
 
-def model_of(name):
-    if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        torch.manual_seed(0)
-        m = GCDenoiser(CASES[name]["cfg"], 0.5)
-        shapes = [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
-        P = {k: torch.from_numpy(v) for k, v in synthetic.fill_state_dict(shapes, 5, "rich").items()}
-        m.load_state_dict(P, strict=False)
-        _MODELS[name] = (m.cuda().eval(), P)
-    return _MODELS[name]
-
-
-def inputs(name, B, seed, dtype=torch.float32):
-    e = CASES[name]
-    cfg = e["cfg"]
-    t = {k: torch.from_numpy(v).to(dtype) for k, v in synthetic.sampler_inputs(B, cfg, seed, e["arch"]).items()}
-    if e["arch"] == "mdtv":
-        state = {"state_images": t["state_images"], "modality": "lang"}
-    else:
-        state = {"static": t["static"], "gripper": t["gripper"], "modality": "lang"}
-    if e["proprio"]:
-        state["state_obs"] = torch.from_numpy(synthetic.normal("state_obs", (B, 1, cfg["proprio_dim"]), seed)).to(dtype)
-    return state, t["goal"], t["noise"]
-
-
-def cuda(state):
-    return {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in state.items()}
+F = Family(None, CASES)   # (model, float32 state dict): 'rich' synthetic weights
+model_of, inputs, _MODELS = F.model_of, F.inputs, F._models   # _MODELS: tests/test_sampler_envelope.py puts host weights in
 
 
 def oracle_guided_ddim(name, B, seed, sig, lam):
@@ -94,11 +70,6 @@ def oracle_guided_ddim(name, B, seed, sig, lam):
     return x
 
 
-def gs():
-    from mdt_policy_amd.models.edm_diffusion import gc_sampling
-    return gc_sampling
-
-
 def _no_forward(monkeypatch):
     from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
 
@@ -114,7 +85,7 @@ GUIDED_NAMES = sorted(n for n in CASES if n not in ("nogoal_proprio", "mdt_nogoa
 def test_guided_ddim_against_float64(name, monkeypatch):
     """3-step guided sample_ddim at lambda 0 / 0.5 / 3 against float64 across the batches of BATCHES (default: 1 and 17)."""
     model, _ = model_of(name)
-    sig = gs().get_sigmas_exponential(3, 0.01, 80.0)
+    sig = gs.get_sigmas_exponential(3, 0.01, 80.0)
     _no_forward(monkeypatch)
     for j, B in enumerate(BATCHES.get(name, [1, 17])):
         lams = LAMBDAS if B <= 17 else (LAMBDAS[j % 3],)  # every weight at the small batches, one each above
@@ -122,7 +93,7 @@ def test_guided_ddim_against_float64(name, monkeypatch):
             state, goal, noise = inputs(name, B, 40 + B)
             want = oracle_guided_ddim(name, B, 40 + B, sig, lam)
             with torch.no_grad():
-                got = gs().sample_ddim(model, cuda(state), noise.cuda() * 80.0, goal.cuda(), sig.cuda(),
+                got = gs.sample_ddim(model, cuda(state), noise.cuda() * 80.0, goal.cuda(), sig.cuda(),
                                        extra_args={"cond_lambda": lam}).cpu()
             assert_close(got, want, what=f"{name} B = {B} lambda = {lam}", **tol(lam))
 
@@ -133,14 +104,14 @@ def test_guided_ddim_graph_replay_is_keyed_by_lambda(name):
     model, _ = model_of(name)
     model.__dict__.pop("_graphed_samplers", None)
     model.__dict__.pop("_graph_seen", None)
-    sig = gs().get_sigmas_exponential(10, 0.01, 80.0)
+    sig = gs.get_sigmas_exponential(10, 0.01, 80.0)
     seeds = (7, 8)
     for lam, calls in ((3.0, 4), (0.5, 3)):
         want = {s: oracle_guided_ddim(name, 1, s, sig, lam) for s in seeds}
         for i in range(calls):
             state, goal, noise = inputs(name, 1, seeds[i % 2])
             with torch.no_grad():
-                got = gs().sample_ddim(model, cuda(state), noise.cuda() * 80.0, goal.cuda(), sig,
+                got = gs.sample_ddim(model, cuda(state), noise.cuda() * 80.0, goal.cuda(), sig,
                                        extra_args={"cond_lambda": lam}).cpu()
             assert_close(got, want[seeds[i % 2]], what=f"{name} lambda {lam} call {i}", **tol(lam))
         assert any(g.cond_lambda == lam for g in model.__dict__.get("_graphed_samplers", [])), f"no graph for lambda {lam}"
@@ -160,8 +131,8 @@ def test_other_kinds_guided_native_against_guided_host_loop(name, kind, kw, monk
     state, goal, noise = inputs(name, B, 21)
     state = cuda(state)
     x, goal = noise.cuda() * 80.0, goal.cuda()
-    sig = gs().get_sigmas_exponential(6, 0.01, 80.0)
-    fn = getattr(gs(), "sample_" + kind)
+    sig = gs.get_sigmas_exponential(6, 0.01, 80.0)
+    fn = getattr(gs, "sample_" + kind)
     kw = dict(kw)
     if kind == "dpmpp_sde":  # a seeded sampler: the native path draws its values up front in the loop's order
         kw["noise_sampler"] = lambda s0, s1: torch.randn(x.shape, device=x.device)
@@ -181,7 +152,7 @@ def test_dpm_fast_and_adaptive_guided_native_against_guided_host_loop(monkeypatc
     state, goal, noise = inputs("mdtv_default", 3, 22)
     state = cuda(state)
     x, goal = noise.cuda() * 80.0, goal.cuda()
-    g = gs()
+    g = gs
     with torch.no_grad():
         for eta in (0.0, 1.0):
             kw = dict(eta=eta, noise_sampler=lambda s0, s1: torch.randn(x.shape, device=x.device))
@@ -212,17 +183,17 @@ def test_lambda_one_and_goal_less_models_give_the_unguided_bits(name):
     model, _ = model_of(name)
     state, goal, noise = inputs(name, 5, 23)
     state, x, goal = cuda(state), noise.cuda() * 80.0, goal.cuda()
-    sig = gs().get_sigmas_exponential(5, 0.01, 80.0)
+    sig = gs.get_sigmas_exponential(5, 0.01, 80.0)
     with torch.no_grad():
-        base = gs().sample_ddim(model, state, x, goal, sig)
-        assert torch.equal(gs().sample_ddim(model, state, x, goal, sig, extra_args={"cond_lambda": 1.0}), base)
+        base = gs.sample_ddim(model, state, x, goal, sig)
+        assert torch.equal(gs.sample_ddim(model, state, x, goal, sig, extra_args={"cond_lambda": 1.0}), base)
         assert torch.equal(_engine_call(model, state, x, goal, sig, 1.0), base)  # the C guided entry point at lambda = 1
-        base_e = gs().sample_euler(model, state, x, goal, sig)
-        assert torch.equal(gs().sample_euler(model, state, x, goal, sig, extra_args={"cond_lambda": 1.0}), base_e)
+        base_e = gs.sample_euler(model, state, x, goal, sig)
+        assert torch.equal(gs.sample_euler(model, state, x, goal, sig, extra_args={"cond_lambda": 1.0}), base_e)
         if name in ("nogoal_proprio", "mdt_nogoal"):
             assert torch.equal(_engine_call(model, state, x, goal, sig, 2.0), base)
-            assert torch.equal(gs().sample_ddim(model, state, x, goal, sig, extra_args={"cond_lambda": 2.0}), base)
-            assert torch.equal(gs().sample_euler(model, state, x, goal, sig, extra_args={"cond_lambda": 2.0}), base_e)
+            assert torch.equal(gs.sample_ddim(model, state, x, goal, sig, extra_args={"cond_lambda": 2.0}), base)
+            assert torch.equal(gs.sample_euler(model, state, x, goal, sig, extra_args={"cond_lambda": 2.0}), base_e)
 
 
 @pytest.mark.parametrize("name", ["mdtv_default", "mdt_default"])
@@ -230,12 +201,12 @@ def test_lambda_zero_is_the_unconditional_model(name, monkeypatch):
     model, _ = model_of(name)
     state, goal, noise = inputs(name, 4, 24)
     state, x, goal = cuda(state), noise.cuda() * 80.0, goal.cuda()
-    sig = gs().get_sigmas_exponential(5, 0.01, 80.0)
+    sig = gs.get_sigmas_exponential(5, 0.01, 80.0)
     with torch.no_grad():
-        want = gs().sample_ddim(model, state, x, goal, sig, extra_args={"uncond": True}).cpu()
+        want = gs.sample_ddim(model, state, x, goal, sig, extra_args={"uncond": True}).cpu()
         with monkeypatch.context() as mp:
             _no_forward(mp)
-            got = gs().sample_ddim(model, state, x, goal, sig, extra_args={"cond_lambda": 0.0}).cpu()
+            got = gs.sample_ddim(model, state, x, goal, sig, extra_args={"cond_lambda": 0.0}).cpu()
     assert_close(got, want, what=name)
 
 
@@ -244,7 +215,7 @@ def test_batch_independence_and_context(name):
     model, _ = model_of(name)
     lam = 2.5
     state, goal, noise = inputs(name, 3, 25)
-    sig = gs().get_sigmas_exponential(4, 0.01, 80.0)
+    sig = gs.get_sigmas_exponential(4, 0.01, 80.0)
     im = model.inner_model
     with torch.no_grad():
         s3, x3, g3 = cuda(state), noise.cuda() * 80.0, goal.cuda()
@@ -264,7 +235,7 @@ def test_non_finite_lambda_is_refused_and_the_handle_stays_usable():
     model, _ = model_of("mdtv_default")
     state, goal, noise = inputs("mdtv_default", 2, 26)
     state, x, goal = cuda(state), noise.cuda() * 80.0, goal.cuda()
-    sig = gs().get_sigmas_exponential(3, 0.01, 80.0)
+    sig = gs.get_sigmas_exponential(3, 0.01, 80.0)
     tok = state["state_images"].contiguous()
     out = torch.empty_like(x)
     arr = (C.c_float * 4)(*[float(v) for v in sig])
@@ -273,9 +244,9 @@ def test_non_finite_lambda_is_refused_and_the_handle_stays_usable():
         lib = eng.lib
         for bad in (float("nan"), float("inf"), -float("inf")):
             with pytest.raises(ValueError):
-                gs().sample_ddim(model, state, x, goal, sig, extra_args={"cond_lambda": bad})
+                gs.sample_ddim(model, state, x, goal, sig, extra_args={"cond_lambda": bad})
             with pytest.raises(ValueError):
-                gs().sample_euler(model, state, x, goal, sig, extra_args={"cond_lambda": bad})
+                gs.sample_euler(model, state, x, goal, sig, extra_args={"cond_lambda": bad})
             with pytest.raises(ValueError):
                 model(state, x, goal, sig[:1].cuda(), cond_lambda=bad)
             st = lib.mdt_sample_ddim_guided(eng.handle, tok.data_ptr(), None, goal.data_ptr(), _lib.MODALITY["lang"], x.data_ptr(),
@@ -284,7 +255,7 @@ def test_non_finite_lambda_is_refused_and_the_handle_stays_usable():
         with pytest.raises(ValueError):
             model(state, x, goal, sig[:1].cuda(), cond_lambda=2.0, uncond=True)
         want = oracle_guided_ddim("mdtv_default", 2, 26, sig, 2.0)
-        got = gs().sample_ddim(model, state, x, goal, sig, extra_args={"cond_lambda": 2.0}).cpu()
+        got = gs.sample_ddim(model, state, x, goal, sig, extra_args={"cond_lambda": 2.0}).cpu()
     assert_close(got, want, what="after refusals", **tol(2.0))
 
 
@@ -300,7 +271,7 @@ def test_plain_c_client_matches_the_facade(tmp_path):
     cfg = model.inner_model._hip_config(0.5)
     B, n_steps, lam = 2, 5, 2.5
     state, goal, noise = inputs("mdtv_default", B, 27)
-    sig = gs().get_sigmas_exponential(n_steps, 0.01, 80.0)
+    sig = gs.get_sigmas_exponential(n_steps, 0.01, 80.0)
     x_T = noise * 80.0
     blob = tmp_path / "blob.bin"
     allf = [n for n, _ in _lib.MDTConfig._fields_]
@@ -324,6 +295,6 @@ def test_plain_c_client_matches_the_facade(tmp_path):
     assert "gfx950" in r.stdout
     got = np.fromfile(out, dtype=np.float32).reshape(tuple(x_T.shape))
     with torch.no_grad():
-        want = gs().sample_ddim(model, cuda(state), x_T.cuda(), goal.cuda(), sig, extra_args={"cond_lambda": lam}).cpu().numpy()
+        want = gs.sample_ddim(model, cuda(state), x_T.cuda(), goal.cuda(), sig, extra_args={"cond_lambda": lam}).cpu().numpy()
     np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6)
     assert math.isfinite(float(np.abs(got).max()))

@@ -14,7 +14,7 @@ that test's reference and tolerance:
 import pytest
 import torch
 
-from mdt_policy_amd import configs, synthetic
+from mdt_policy_amd import synthetic
 from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from mdt_policy_amd.utils.action_pin import ActionPin
 from mdt_policy_amd.utils.action_steer import ActionSteer
@@ -22,7 +22,8 @@ from tests import sampler_envelope as E
 from tests import test_gpu_denoise_grad as DG
 from tests import test_gpu_guidance as guid
 from tests import test_gpu_train_dropout as TD
-from tests.helpers import ATOL, RTOL, assert_close, cfg_of, inputs_of, params_of
+from tests.family import OptionFamily
+from tests.helpers import ATOL, RTOL, assert_close, cfg_of, cuda, inputs_of
 from tests.test_gpu_brownian import _loop_sampler, _seed_of
 from tests.test_gpu_loglik_native import LL, check_info, chunks_of, parent_path, signs
 from tests.test_gpu_native_samplers import _host_loop
@@ -37,66 +38,17 @@ OPTION_CASES = {
 }
 NAMES = sorted(OPTION_CASES)
 B = 2
-_META, _MODELS, _ORACLES = {}, {}, {}
 
 
-def meta_of(name):
-    """What a golden fixture's meta holds, for tests/helpers.py (cfg_of, params_of, inputs_of) and the helpers built on them."""
-    if name not in _META:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        ov = OPTION_CASES[name]
-        sd = GCDenoiser(configs.mdtv_default(**ov), 0.5).state_dict()
-        _META[name] = dict(config="mdtv_default", overrides=ov, arch="mdtv", B=B, modality="lang", weight_seed=5, profile="rich",
-                           input_seed=E.SEED, loss_seed=62, ctx_seed=63, state_dict=[[k, list(v.shape)] for k, v in sd.items()])
-    return _META[name]
+class _Spec(dict):
+    """OPTION_CASES as a SPEC table, read at call time: tests/test_gpu_steer_plan_envelope.py adds a row after the import."""
+
+    def __missing__(self, name):
+        return "mdtv", "mdtv_default", OPTION_CASES[name], False
 
 
-def model_of(name):
-    if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        meta = meta_of(name)
-        m = GCDenoiser(cfg_of(meta), 0.5)
-        m.load_state_dict(params_of(meta))
-        _MODELS[name] = m.cuda().eval()
-    return _MODELS[name]
-
-
-def oracle_of(name):
-    if name not in _ORACLES:
-        meta = meta_of(name)
-        _ORACLES[name] = E.EnvelopeOracle(name, case=dict(cfg=cfg_of(meta), arch="mdtv"), P=params_of(meta))
-    return _ORACLES[name]
-
-
-def case(name, batch=B, seed=E.SEED):
-    """(state, goal, x_T, fixed noise) in float32 on the host; x_T = 80 noise."""
-    state, goal, noise = inputs_of(dict(meta_of(name), input_seed=seed), batch=batch)
-    fixed = torch.from_numpy(synthetic.normal("sde_noise", tuple(noise.shape), seed + 100))
-    return state, goal, noise * E.SMAX, fixed
-
-
-def cuda(t):
-    if isinstance(t, dict):
-        return {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in t.items()}
-    return t.cuda()
-
-
-def both_runs(name, kind, monkeypatch, extra=None, repeat=1):
-    """(native result, float64 host-loop result) of one sampler kind; ``repeat`` = K: K chunks per observation."""
-    state, goal, _, _ = case(name)
-    _, _, x, fixed = case(name, B * repeat)
-    ea = dict(extra or {})
-    ost, og = state, goal
-    if repeat > 1:
-        ost = {k: (v.repeat_interleave(repeat, 0) if torch.is_tensor(v) else v) for k, v in state.items()}
-        og = goal.repeat_interleave(repeat, 0)
-    want = E.run(kind, oracle_of(name), E.wide(ost), E.wide(x), E.wide(og), E.wide(fixed), extra_args=dict(ea))
-    if repeat > 1:
-        ea["candidates"] = repeat
-    with monkeypatch.context() as mp:
-        no_forward(mp)
-        got = E.run(kind, model_of(name), cuda(state), x.cuda(), goal.cuda(), fixed.cuda(), extra_args=ea).cpu()
-    return got, want
+F = OptionFamily(_Spec(), dict(weight_seed=5, input_seed=E.SEED, loss_seed=62, ctx_seed=63), B)
+meta_of, model_of, oracle_of, case, both_runs = F.meta_of, F.model_of, F.oracle_of, F.case, F.both_runs
 
 
 @pytest.mark.parametrize("kind", ["heun", "dpmpp_2m"])

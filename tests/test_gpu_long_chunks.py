@@ -6,27 +6,16 @@ import torch
 
 from mdt_policy_amd import synthetic
 from oracle import mdt_oracle as O
-from tests.helpers import assert_close
+from tests.family import Family
+from tests.helpers import assert_close, to
 from tests.long_chunk_configs import LONG_ENVELOPE
 
 pytestmark = pytest.mark.gpu
 
 NAMES = sorted(LONG_ENVELOPE)
-_MODELS = {}
-
-
-def model_of(name):
-    """(GCDenoiser on cuda:0 in eval mode, its float32 state dict) -- 'rich' synthetic weights."""
-    if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        cfg = LONG_ENVELOPE[name]["cfg"]
-        torch.manual_seed(0)
-        m = GCDenoiser(cfg, 0.5)
-        shapes = [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
-        P = {k: torch.from_numpy(v) for k, v in synthetic.fill_state_dict(shapes, 5, "rich").items()}
-        m.load_state_dict(P, strict=False)
-        _MODELS[name] = (m.cuda().eval(), P)
-    return _MODELS[name]
+F = Family(None, LONG_ENVELOPE)   # (model, float32 state dict): 'rich' synthetic weights
+model_of, inputs = F.model_of, F.inputs
+oracle_sample = lambda name, sampler, B, seed, sig: F.oracle_sample(name, B, seed, sig, sampler)  # noqa: E731
 
 
 def batches(cfg):
@@ -42,31 +31,6 @@ def batches(cfg):
     if cfg["embed_dim"] == 128:
         bs.add(70)
     return sorted(bs)
-
-
-def inputs(name, B, seed, dtype=torch.float32):
-    """(state, goal, noise) on the host; state_obs (B, 1, proprio_dim) when the case switches the token on."""
-    e = LONG_ENVELOPE[name]
-    cfg = e["cfg"]
-    t = {k: torch.from_numpy(v).to(dtype) for k, v in synthetic.sampler_inputs(B, cfg, seed, e["arch"]).items()}
-    if e["arch"] == "mdtv":
-        state = {"state_images": t["state_images"], "modality": "lang"}
-    else:
-        state = {"static": t["static"], "gripper": t["gripper"], "modality": "lang"}
-    if e["proprio"]:
-        state["state_obs"] = torch.from_numpy(synthetic.normal("state_obs", (B, 1, cfg["proprio_dim"]), seed)).to(dtype)
-    return state, t["goal"], t["noise"]
-
-
-def to(state, fn):
-    return {k: (fn(v) if torch.is_tensor(v) else v) for k, v in state.items()}
-
-
-def oracle_sample(name, sampler, B, seed, sig):
-    e = LONG_ENVELOPE[name]
-    _, P = model_of(name)
-    state, goal, noise = inputs(name, B, seed, torch.float64)
-    return sampler(O.to_dtype(P, torch.float64), e["cfg"], state, noise * 80.0, goal, sig, arch=e["arch"], hoist=True)
 
 
 def test_the_batches_reach_every_dispatcher_regime():

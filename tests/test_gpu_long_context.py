@@ -9,66 +9,19 @@ test_gpu_parity.py), the loss to 1e-3 relative and every gradient to rtol 2e-3, 
 import pytest
 import torch
 
-from mdt_policy_amd import configs, synthetic
+from mdt_policy_amd import synthetic
 from oracle import mdt_oracle as O
-from tests.helpers import assert_close, load_fixture, params_of
+from tests.family import Family
+from tests.helpers import assert_close, load_fixture, params_of, to
 from tests.long_context_configs import CTX_ENVELOPE, CTX_GOLDEN, CTX_SHAPES, CTX_SPEC
 
 pytestmark = pytest.mark.gpu
 
 NAMES = sorted(CTX_ENVELOPE)
 SEEDS = dict(weight_seed=211, input_seed=212, loss_seed=213, ctx_seed=214, obs_seed=215)   # the recorder's
-_MODELS = {}
-
-
-def meta_of(name):
-    """A fixture-style meta (tests/helpers.py: cfg_of, params_of, inputs_of) of a case, recorded or not."""
-    from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-    arch, factory, ov, proprio = CTX_SPEC[name]
-    sd = GCDenoiser(configs.NAMED[factory](**ov), 0.5).state_dict()
-    return dict(config=factory, overrides=ov, arch=arch, proprio=proprio, B=2, modality="lang", profile="rich",
-                state_dict=[[k, list(v.shape)] for k, v in sd.items()], **SEEDS)
-
-
-def model_of(name):
-    """(GCDenoiser on cuda:0 in eval mode, its meta) -- the 'rich' weights of the recorder."""
-    if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        meta = meta_of(name)
-        m = GCDenoiser(CTX_ENVELOPE[name]["cfg"], 0.5)
-        m.load_state_dict(params_of(meta))
-        _MODELS[name] = (m.cuda().eval(), meta)
-    return _MODELS[name]
-
-
-def inputs(name, B, seed, dtype=torch.float32):
-    """(state, goal, noise) on the host; state_obs (B, 1, proprio_dim) when the case switches the token on."""
-    e = CTX_ENVELOPE[name]
-    cfg = e["cfg"]
-    t = {k: torch.from_numpy(v).to(dtype) for k, v in synthetic.sampler_inputs(B, cfg, seed, e["arch"]).items()}
-    state = {"state_images": t["state_images"], "modality": "lang"}
-    if e["proprio"]:
-        state["state_obs"] = torch.from_numpy(synthetic.normal("state_obs", (B, 1, cfg["proprio_dim"]), seed)).to(dtype)
-    return state, t["goal"], t["noise"]
-
-
-def to(state, fn):
-    return {k: (fn(v) if torch.is_tensor(v) else v) for k, v in state.items()}
-
-
-def oracle_sample(name, B, seed, sig, state=None):
-    e = CTX_ENVELOPE[name]
-    _, meta = model_of(name)
-    st, goal, noise = inputs(name, B, seed, torch.float64)
-    return O.sample_ddim(params_of(meta, torch.float64), e["cfg"], state or st, noise * 80.0, goal, sig, arch=e["arch"], hoist=True)
-
-
-def hip_sample(name, B, seed, sig):
-    from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
-    model, _ = model_of(name)
-    state, goal, noise = inputs(name, B, seed)
-    with torch.no_grad():
-        return gs.sample_ddim(model, to(state, torch.Tensor.cuda), noise.cuda() * 80.0, goal.cuda(), sig.cuda()).cpu()
+assert all(e["arch"] == "mdtv" for e in CTX_ENVELOPE.values())   # every state here is state_images
+F = Family(CTX_SPEC, CTX_ENVELOPE, SEEDS)
+meta_of, model_of, inputs, oracle_sample, hip_sample = F.meta_of, F.model_of, F.inputs, F.oracle_sample, F.hip_sample
 
 
 @pytest.mark.parametrize("name", CTX_GOLDEN)

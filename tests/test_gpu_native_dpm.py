@@ -31,7 +31,7 @@ def test_dpm_fast_takes_the_native_route(eta, monkeypatch):
     _no_forward(monkeypatch)
     with torch.no_grad():
         torch.manual_seed(5)
-        out = gs().sample_dpm_fast(model, state, noise * 80.0, goal, 0.001, 80.0, 10, eta=eta)
+        out = gs.sample_dpm_fast(model, state, noise * 80.0, goal, 0.001, 80.0, 10, eta=eta)
     assert out.shape == noise.shape and bool(torch.isfinite(out).all())
 
 
@@ -42,7 +42,7 @@ def test_g7c_dpm_fast_goldens_on_the_native_path(monkeypatch):
     _no_forward(monkeypatch)
     with torch.no_grad():
         for nfe in (9, 10, 11):
-            out = gs().sample_dpm_fast(model, state, noise * 80.0, goal, 0.001, 80.0, nfe, noise_sampler=lambda s0, s1: None)
+            out = gs.sample_dpm_fast(model, state, noise * 80.0, goal, 0.001, 80.0, nfe, noise_sampler=lambda s0, s1: None)
             assert_close(out.cpu(), fx[f"dpm_fast_nfe{nfe}"], what=f"dpm_fast nfe={nfe}")
 
 
@@ -51,7 +51,7 @@ def test_dpm_fast_native_matches_the_host_loop_on_the_conditioning_variants(vari
     meta, _ = load_fixture(f"{variant}.npz")
     model = build(meta)
     state, goal, noise = gpu_inputs(meta)
-    g = gs()
+    g = gs
     im = model.inner_model
     with torch.no_grad():
         for n in NS:
@@ -68,7 +68,7 @@ def test_dpm_fast_native_matches_the_host_loop_across_batch_sizes_and_eta(B):
     meta, _ = load_fixture("g3_b256_lang.npz")
     model = build(meta)
     state, goal, noise = gpu_inputs(meta, B=B, seed=500 + B)
-    g = gs()
+    g = gs
     with torch.no_grad():
         for n in NS:
             for eta in (0.0, 0.5):
@@ -99,7 +99,7 @@ def test_dpm_fast_rollout_sized_calls_replay_a_graph_equal_to_eager(eta):
     meta, _ = load_fixture("g7c_samplers.npz")
     model = build(meta)
     state, goal, noise = gpu_inputs(meta, B=1, seed=43)
-    g = gs()
+    g = gs
     model.__dict__.pop("_graphed_native", None)
     model.__dict__.pop("_graph_seen", None)
     outs, nexts = [], []

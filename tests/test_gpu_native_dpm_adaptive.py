@@ -27,7 +27,7 @@ def test_dpm_adaptive_takes_the_native_route(order, monkeypatch):
     state, goal, noise = gpu_inputs(meta)
     _no_forward(monkeypatch)
     with torch.no_grad():
-        out, info = gs().sample_dpm_adaptive(model, state, noise * 80.0, goal, 0.01, 80.0, order=order, return_info=True)
+        out, info = gs.sample_dpm_adaptive(model, state, noise * 80.0, goal, 0.01, 80.0, order=order, return_info=True)
     assert out.shape == noise.shape and bool(torch.isfinite(out).all())
     assert info["nfe"] == order * info["steps"] and info["n_accept"] > 0
 
@@ -37,7 +37,7 @@ def test_dpm_adaptive_native_matches_the_host_loop(B):
     meta, _ = load_fixture("g3_b256_lang.npz")
     model = build(meta)
     state, goal, noise = gpu_inputs(meta, B=B, seed=700 + B)
-    g = gs()
+    g = gs
     im = model.inner_model
     saw_reject = False
     with torch.no_grad():
@@ -62,7 +62,7 @@ def test_dpm_adaptive_native_on_a_conditioning_variant():
     meta, _ = load_fixture("g8_no_ada.npz")  # use_ada_conditioning=False: the encoder runs per evaluation
     model = build(meta)
     state, goal, noise = gpu_inputs(meta)
-    g = gs()
+    g = gs
     im = model.inner_model
     with torch.no_grad():
         want, winfo = _host_loop(g.sample_dpm_adaptive, model, state, noise * 80.0, goal, 0.01, 80.0, return_info=True)
@@ -82,5 +82,5 @@ def test_dpm_adaptive_native_stops_on_nan_instead_of_looping():
     x[0, 0, 0] = float("nan")
     t0 = time.perf_counter()
     with torch.no_grad(), pytest.raises(_lib.MDTHipError, match="stopped"):
-        gs().sample_dpm_adaptive(model, state, x, goal, 0.01, 80.0)
+        gs.sample_dpm_adaptive(model, state, x, goal, 0.01, 80.0)
     assert time.perf_counter() - t0 < 30.0

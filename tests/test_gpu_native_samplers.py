@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from mdt_policy_amd import synthetic
+from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from tests.helpers import assert_close, cfg_of, inputs_of, load_fixture, params_of
 
 pytestmark = pytest.mark.gpu
@@ -27,11 +28,6 @@ def gpu_inputs(meta, B=None, seed=None):
     state, goal, noise = inputs_of(m)
     state = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in state.items()}
     return state, goal.cuda(), noise.cuda()
-
-
-def gs():
-    from mdt_policy_amd.models.edm_diffusion import gc_sampling
-    return gc_sampling
 
 
 def _no_forward(monkeypatch):
@@ -59,7 +55,7 @@ def test_g7_goldens_on_the_native_path(name, sched, monkeypatch):
     model = build(meta)
     state, goal, noise = gpu_inputs(meta)
     _no_forward(monkeypatch)
-    g = gs()
+    g = gs
     sig = (g.get_sigmas_exponential if sched == "exp" else g.get_sigmas_karras)(10, 0.001, 80.0)
     with torch.no_grad():
         out = getattr(g, "sample_" + name)(model, state, noise * 80.0, goal, sig)
@@ -75,7 +71,7 @@ def test_g7b_goldens_on_the_native_path(name, kw, key, monkeypatch):
     model = build(meta)
     state, goal, noise = gpu_inputs(meta)
     _no_forward(monkeypatch)
-    g = gs()
+    g = gs
     with torch.no_grad():
         out = getattr(g, "sample_" + name)(model, state, noise * 80.0, goal, g.get_sigmas_exponential(10, 0.001, 80.0), **kw)
     assert_close(out.cpu(), fx[key], what=key)
@@ -86,7 +82,7 @@ def test_g7c_dpmpp_sde_goldens_on_the_native_path(monkeypatch):
     model = build(meta)
     state, goal, noise = gpu_inputs(meta)
     _no_forward(monkeypatch)
-    g = gs()
+    g = gs
     x0 = noise * 80.0
     fixed = torch.from_numpy(synthetic.normal("sde_noise", tuple(x0.shape), meta["noise_seed"])).cuda()
     sig = g.get_sigmas_exponential(10, 0.001, 80.0)
@@ -102,7 +98,7 @@ def test_native_matches_the_host_loop_on_the_conditioning_variants(variant):
     meta, _ = load_fixture(f"{variant}.npz")
     model = build(meta)
     state, goal, noise = gpu_inputs(meta)
-    g = gs()
+    g = gs
     sig = g.get_sigmas_karras(5, 0.01, 80.0)
     im = model.inner_model
     with torch.no_grad():
@@ -120,7 +116,7 @@ def test_native_matches_the_host_loop_across_batch_sizes_and_schedule_placement(
     meta, _ = load_fixture("g3_b256_lang.npz")
     model = build(meta)
     state, goal, noise = gpu_inputs(meta, B=B, seed=300 + B)
-    g = gs()
+    g = gs
     sig = g.get_sigmas_exponential(6, 0.001, 80.0)
     with torch.no_grad():
         for name, kw in DETERMINISTIC + [("euler_ancestral", dict(eta=1.)), ("heun", dict(s_churn=1.0))]:
@@ -140,7 +136,7 @@ def test_seeded_native_call_follows_the_host_loops_random_stream(name, kw):
     meta, _ = load_fixture("g7b_samplers.npz")
     model = build(meta)
     state, goal, noise = gpu_inputs(meta)
-    g = gs()
+    g = gs
     fn = getattr(g, "sample_" + name)
     sig = g.get_sigmas_exponential(10, 0.001, 80.0)
     with torch.no_grad():
@@ -158,7 +154,7 @@ def test_device_schedule_call_captures_into_a_graph_and_replays_equal_to_eager()
     meta, _ = load_fixture("g7_samplers.npz")
     model = build(meta)
     state, goal, noise = gpu_inputs(meta)
-    g = gs()
+    g = gs
     sig = g.get_sigmas_karras(10, 0.001, 80.0).cuda()
     x = noise * 80.0
     with torch.no_grad():
@@ -187,7 +183,7 @@ def test_rollout_sized_calls_go_through_the_graph_path(name, kw, deterministic):
     meta, _ = load_fixture("g7_samplers.npz")
     model = build(meta)
     state, goal, noise = gpu_inputs(meta, B=1, seed=41)
-    g = gs()
+    g = gs
     fn = getattr(g, "sample_" + name)
     sig = g.get_sigmas_exponential(10, 0.001, 80.0)
     model.__dict__.pop("_graphed_native", None)

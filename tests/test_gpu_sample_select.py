@@ -12,16 +12,16 @@ contexts where the stand-alone scorer's runs B.
 Cases (B, K, S, M): (1, 1, 1, 1); (3, 5, 3, 2); (2, 40, 2, 2) = 320 score rows; and (1, 8, 16, 2) at the shipped MDT-V width with
 the library's synthetic weights: 8 sampler rows in the small-batch regime, 256 score samples = 2560 rows on the pair-split
 launches.  The schedule has four steps."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
 from mdt_policy_amd import _lib, configs, synthetic
+from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from tests.guarded import same_bits
-from tests.helpers import cfg_of, load_fixture, params_of
+from tests.helpers import cfg_of, cuda, load_fixture, observation, params_of, rich_model
 from tests.score_oracle import residual_score
+from tests.test_gpu_denoising_score import levels_of
 
 pytestmark = pytest.mark.gpu
 
@@ -39,15 +39,6 @@ def _inference():
         yield
 
 
-def gs():
-    from mdt_policy_amd.models.edm_diffusion import gc_sampling
-    return gc_sampling
-
-
-def levels_of(S):
-    return [SMIN] if S == 1 else [math.exp(v) for v in np.linspace(math.log(SMAX), math.log(SMIN), S)]
-
-
 def entry(name):
     """(cfg, arch, float32 state dict or None for 'rich' synthetic weights)"""
     if name in ("mdtv_tiny", "mdt_tiny"):
@@ -60,14 +51,14 @@ def entry(name):
 
 def model_of(name):
     if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
         cfg, _, P = entry(name)
-        torch.manual_seed(0)
-        m = GCDenoiser(cfg, 0.5)
         if P is None:
-            shapes = [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
-            P = {k: torch.from_numpy(v) for k, v in synthetic.fill_state_dict(shapes, 5, "rich").items()}
-        m.load_state_dict(P, strict=False)
+            m, P = rich_model(cfg)
+        else:   # a fixture's own weights
+            from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
+            torch.manual_seed(0)
+            m = GCDenoiser(cfg, 0.5)
+            m.load_state_dict(P, strict=False)
         _MODELS[name] = (m.cuda().eval(), P)
     return _MODELS[name]
 
@@ -77,11 +68,7 @@ def case(name, B, K, S, M, seed=None):
     sampler's noise rows (N_STEPS, B*K, Ta, A), a pin per chunk; and the host copies of state and goal for the oracle."""
     cfg, arch, _ = entry(name)
     seed = 3000 + 31 * B + 7 * K + 3 * S + M if seed is None else seed
-    t = {k: torch.from_numpy(v) for k, v in synthetic.sampler_inputs(B, cfg, seed, arch).items()}
-    if arch == "mdtv":
-        state = {"state_images": t["state_images"], "modality": "lang"}
-    else:
-        state = {"static": t["static"], "gripper": t["gripper"], "modality": "lang"}
+    state, goal, _ = observation(cfg, arch, False, B, seed)
     shape = tuple(torch.from_numpy(synthetic.loss_inputs(1, cfg, seed)["actions"]).shape[1:])
     x_T = SMAX * torch.from_numpy(synthetic.normal("x_T", (B * K,) + shape, seed + 1))
     snoise = torch.from_numpy(synthetic.normal("score_noise", (S, M) + shape, seed + 2))
@@ -90,10 +77,9 @@ def case(name, B, K, S, M, seed=None):
     keep = torch.zeros((B * K,) + shape)
     keep[:, :2] = 1.0
     keep[:, 2] = 0.5
-    dev = lambda s: {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in s.items()}
-    return dict(state=dev(state), goal=t["goal"].cuda(), x_T=x_T.cuda(), levels=levels_of(S), snoise=snoise.cuda(), rows=rows.cuda(),
-                pin=(known.cuda(), keep.cuda()), host_state=state, host_goal=t["goal"],
-                sig=gs().get_sigmas_exponential(N_STEPS, SMIN, SMAX))
+    return dict(state=cuda(state), goal=goal.cuda(), x_T=x_T.cuda(), levels=levels_of(S), snoise=snoise.cuda(), rows=rows.cuda(),
+                pin=(known.cuda(), keep.cuda()), host_state=state, host_goal=goal,
+                sig=gs.get_sigmas_exponential(N_STEPS, SMIN, SMAX))
 
 
 def three_calls(model, c, K, kind, pin=None, lam=None):
@@ -105,7 +91,7 @@ def three_calls(model, c, K, kind, pin=None, lam=None):
                                      noise=c["rows"] if kind == "euler_ancestral" else None, **kw)
     ctx = model.inner_model.latent_encoder_emb.clone()
     scores = model.denoising_score(c["state"], chunks, c["goal"], c["levels"], c["snoise"], candidates=K)
-    best, index = gs().best_candidates(chunks, scores, K)
+    best, index = gs.best_candidates(chunks, scores, K)
     return best, index, scores, chunks, ctx
 
 
@@ -178,7 +164,7 @@ def test_a_guided_call_scores_the_conditional_model(name, B, K, S, M, kind):
     print(f"{name} {kind} guided (B, K, S, M)=({B}, {K}, {S}, {M}): |score - float64| {float(err[i]):.3e} / bound {float(bound[i]):.3e}; "
           f"bits equal to the stand-alone scorer: {same_bits(scores, want[2])}")
     assert bool((err <= bound).all()), (err.tolist(), bound.tolist())
-    want_best, want_index = gs().best_candidates(chunks, scores, K)
+    want_best, want_index = gs.best_candidates(chunks, scores, K)
     assert torch.equal(index, want_index) and same_bits(best, want_best)
     assert same_bits(best, chunks.reshape(B, K, *chunks.shape[1:])[torch.arange(B), index])
 
@@ -200,10 +186,10 @@ def test_the_layout_of_action_is_the_layout_of_the_results():
     name, B, K, S, M = "mdtv_tiny", 3, 5, 3, 2
     model, _ = model_of(name)
     c = case(name, B, K, S, M)
-    flat = gs().sample_select(model, c["state"], c["x_T"], c["goal"], c["sig"], c["levels"], noise=c["snoise"],
+    flat = gs.sample_select(model, c["state"], c["x_T"], c["goal"], c["sig"], c["levels"], noise=c["snoise"],
                               extra_args={"candidates": K})
     x4 = c["x_T"].reshape(B, K, *c["x_T"].shape[1:])
-    grid = gs().sample_select(model, c["state"], x4, c["goal"], c["sig"], c["levels"], noise=c["snoise"], extra_args={"candidates": K})
+    grid = gs.sample_select(model, c["state"], x4, c["goal"], c["sig"], c["levels"], noise=c["snoise"], extra_args={"candidates": K})
     assert tuple(flat[2].shape) == (B * K,) and tuple(grid[2].shape) == (B, K) and grid[3].shape == x4.shape
     assert tuple(grid[0].shape) == (B,) + tuple(c["x_T"].shape[1:]) and grid[1].dtype == torch.int64
     for a, b in zip(flat, grid):
@@ -240,7 +226,7 @@ def test_a_captured_call_replays_the_eager_bits_and_the_workspace_stays():
 def test_the_facade_replays_the_third_identical_call(monkeypatch):
     name, B, K, S, M = "mdtv_tiny", 1, 8, 3, 2
     model, _ = model_of(name)
-    g = gs()
+    g = gs
     monkeypatch.setattr(g, "_GRAPH_MODE", "auto")
     monkeypatch.setattr(g, "_GRAPH_SAMPLER", False)
     for k in ("_graphed_select", "_graph_seen", "_graph_failed"):

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from mdt_policy_amd import _lib
+from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from tests import raw_sampler as raw
 from tests.helpers import ATOL, RTOL, assert_close, cfg_of, inputs_of, load_fixture, params_of
 
@@ -30,11 +31,6 @@ KINDS = {"euler": dict(s_churn=1.0), "euler_ancestral": {}, "heun": dict(s_churn
          "dpm_fast": {}}
 NEVER_CLIPS = ("dpmpp_2m", "dpm_fast")
 _MODEL, _REFS = {}, {}
-
-
-def gs():
-    from mdt_policy_amd.models.edm_diffusion import gc_sampling
-    return gc_sampling
 
 
 def ActionBounds(*args, **kw):  # noqa: N802 -- imported where it is used: without the feature every case fails on its own
@@ -73,12 +69,12 @@ class ClampOnly:
 
 
 def sched():
-    return gs().get_sigmas_exponential(N, SMIN, SMAX)
+    return gs.get_sigmas_exponential(N, SMIN, SMAX)
 
 
 def run(name, model, state, x, goal, sig, seed=11, **kw):
     """One seeded sampler call through gc_sampling.  dpmpp_sde gets pre-drawn noise rows handed out in call order."""
-    g = gs()
+    g = gs
     torch.manual_seed(seed)
     kw = dict(KINDS[name], **kw)
     if name == "dpmpp_sde" and "noise_sampler" not in kw:
@@ -185,7 +181,7 @@ def test_guided_call_with_bounds_equals_the_guided_host_loop(name, monkeypatch):
 def test_dpmpp_sde_with_tree_noise_and_bounds(monkeypatch):
     model, state, goal, x = inputs(2)
     sig = sched()
-    tree = gs().NativeBrownianTreeNoiseSampler(x, sig[sig > 0].min(), sig.max(), seed=[17, 18])
+    tree = gs.NativeBrownianTreeNoiseSampler(x, sig[sig > 0].min(), sig.max(), seed=[17, 18])
     model, state, goal, x, lo, hi, want = reference("dpmpp_sde", 2, noise_sampler=tree)
     no_forward(monkeypatch)
     got = run("dpmpp_sde", model, state, x, goal, sig, scaler=ActionBounds(lo, hi), noise_sampler=tree)
@@ -242,7 +238,7 @@ def test_rollout_sized_calls_with_bounds_replay_a_graph_that_reads_the_current_b
 @pytest.mark.parametrize("name", ["heun", "lms"])
 def test_record_is_what_a_callback_sees(name):
     model, state, goal, x, lo, hi, _ = reference(name, 2)
-    g, sig, kw = gs(), sched(), KINDS[name]
+    g, sig, kw = gs, sched(), KINDS[name]
     seen = []
     scaler = ClampOnly(lo, hi)
     run(name, model, state, x, goal, sig, scaler=scaler, callback=lambda d: seen.append({k: (v.clone() if torch.is_tensor(v) else v)
@@ -300,7 +296,7 @@ def test_guided_record_holds_the_combined_denoiser():
     run("euler", model, state, x, goal, sched(), scaler=ClampOnly(lo, hi), extra_args={"cond_lambda": lam},
         callback=lambda d: seen.append((d["x"].clone(), d["denoised"].clone())))
     torch.manual_seed(11)  # run()'s seed
-    noise = gs()._randn_rows(x, N)
+    noise = gs._randn_rows(x, N)
     with torch.no_grad():
         out, rec = model.sample_native("euler", state, x, goal, sched().cuda(), noise=noise, bounds=(lo, hi), record=True,
                                        cond_lambda=lam, **KINDS["euler"])
@@ -353,7 +349,7 @@ def test_bounds_on_the_shipped_schedule(name, monkeypatch):
     """Ten steps down to sigma_min = 0.001, what a rollout runs: the last steps move the state by ~sigma, so their clip_output
     calls change few elements -- the 10 % condition is asserted on the steps where the host loop meets it (the first ones), and
     every call must still change something, so the clamp at small sigma is compared too."""
-    g = gs()
+    g = gs
     model, state, goal, x = inputs(2)
     sig = g.get_sigmas_exponential(10, 0.001, SMAX)
     kw = dict(KINDS[name])
@@ -378,7 +374,7 @@ def test_bounds_on_the_shipped_schedule(name, monkeypatch):
 def test_record_with_pass_evaluations_on_a_device_schedule():
     """A schedule so steep that sigma_down rounds to 0 before the last step: the loop skips the second evaluation there, the
     plan pads it with a pass evaluation, and on a device schedule the record's rows are placed by the structure alone."""
-    g = gs()
+    g = gs
     model, state, goal, x = inputs(2)
     sig = torch.tensor([SMAX, 1e-30, 1e-31, 0.0])
     plan = _lib.sampler_plan("dpm_2_ancestral", sig)

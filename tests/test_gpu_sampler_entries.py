@@ -25,7 +25,7 @@ def case():
     torch.manual_seed(23)
     noise = torch.randn(N, *x.shape, device=x.device)
     seeds = torch.tensor([17, 18], dtype=torch.int64, device=x.device)
-    return model, state, goal, x, gs().get_sigmas_exponential(N, SMIN, SMAX), noise, seeds
+    return model, state, goal, x, gs.get_sigmas_exponential(N, SMIN, SMAX), noise, seeds
 
 
 def facade(name, model, state, goal, x, sig, noise, seeds, lam):

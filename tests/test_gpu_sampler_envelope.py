@@ -29,7 +29,7 @@ from mdt_policy_amd import synthetic
 from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from tests import sampler_envelope as E
 from tests import test_gpu_guidance as guid
-from tests.helpers import ATOL, RTOL, assert_close
+from tests.helpers import ATOL, RTOL, assert_close, cuda
 from tests.test_gpu_config_envelope import model_of
 from tests.test_gpu_loglik_native import LL, check_info
 from tests.test_gpu_sampler_bounds import no_forward
@@ -38,12 +38,6 @@ pytestmark = pytest.mark.gpu
 B = 3
 SELECTS_LAST = ("ddim", "dpmpp_2m")  # the last update is x' = D'
 PIN_CASES = [(kind, B) for kind in E.KINDS] + [("heun", 40)]  # 40: past the 32-sample attention threshold
-
-
-def cuda(t):
-    if isinstance(t, dict):
-        return {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in t.items()}
-    return t.cuda()
 
 
 def gpu_case(name, batch, repeat=1):

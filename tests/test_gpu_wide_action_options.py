@@ -11,13 +11,13 @@ each option checked the way its own test checks it at action_dim <= 16, with tha
 import pytest
 import torch
 
-from mdt_policy_amd import configs, synthetic
 from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from mdt_policy_amd.utils.action_pin import ActionPin
 from mdt_policy_amd.utils.action_steer import ActionSteer
 from tests import sampler_envelope as E
 from tests import test_gpu_guidance as guid
-from tests.helpers import ATOL, RTOL, assert_close, cfg_of, inputs_of, params_of
+from tests.family import OptionFamily
+from tests.helpers import ATOL, RTOL, assert_close, cuda
 from tests.test_gpu_brownian import _loop_sampler, _seed_of
 from tests.test_gpu_loglik_native import LL, check_info, chunks_of, parent_path, signs
 from tests.test_gpu_native_dpm import _close
@@ -29,86 +29,10 @@ pytestmark = pytest.mark.gpu
 
 NAMES = ["a17", "a64_ta24_rope_hd64"]
 B = 2
-_META, _MODELS, _ORACLES, _LOOPS = {}, {}, {}, {}
-
-
-def meta_of(name):
-    """What a golden fixture's meta holds, for tests/helpers.py (cfg_of, params_of, inputs_of) and the helpers built on them."""
-    if name not in _META:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        arch, factory, ov, proprio = WIDE_SPEC[name]
-        assert arch == "mdtv" and not proprio
-        sd = GCDenoiser(configs.NAMED[factory](**ov), 0.5).state_dict()
-        _META[name] = dict(config=factory, overrides=ov, arch=arch, B=B, modality="lang", weight_seed=5, profile="rich",
-                           input_seed=E.SEED, state_dict=[[k, list(v.shape)] for k, v in sd.items()])
-    return _META[name]
-
-
-def model_of(name):
-    if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        meta = meta_of(name)
-        m = GCDenoiser(cfg_of(meta), 0.5)
-        m.load_state_dict(params_of(meta))
-        _MODELS[name] = m.cuda().eval()
-    return _MODELS[name]
-
-
-def oracle_of(name):
-    if name not in _ORACLES:
-        meta = meta_of(name)
-        _ORACLES[name] = E.EnvelopeOracle(name, case=dict(cfg=cfg_of(meta), arch="mdtv"), P=params_of(meta))
-    return _ORACLES[name]
-
-
-def case(name, batch=B, seed=E.SEED):
-    """(state, goal, x_T, fixed noise) in float32 on the host; x_T = 80 noise."""
-    state, goal, noise = inputs_of(dict(meta_of(name), input_seed=seed), batch=batch)
-    fixed = torch.from_numpy(synthetic.normal("sde_noise", tuple(noise.shape), seed + 100))
-    return state, goal, noise * E.SMAX, fixed
-
-
-def cuda(t):
-    if isinstance(t, dict):
-        return {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in t.items()}
-    return t.cuda()
-
-
-def float64_loop(name, kind, extra=None, repeat=1):
-    """The float64 host loop of one sampler kind, computed once per (name, kind, options) and left unchanged."""
-    key = (name, kind, repeat, tuple(sorted((k, v if isinstance(v, float) else "") for k, v in (extra or {}).items())))
-    if key not in _LOOPS:
-        state, goal, _, _ = case(name)
-        _, _, x, fixed = case(name, B * repeat)
-        if repeat > 1:
-            state = {k: (v.repeat_interleave(repeat, 0) if torch.is_tensor(v) else v) for k, v in state.items()}
-            goal = goal.repeat_interleave(repeat, 0)
-        _LOOPS[key] = E.run(kind, oracle_of(name), E.wide(state), E.wide(x), E.wide(goal), E.wide(fixed), extra_args=dict(extra or {}))
-    return _LOOPS[key]
-
-
-def both_runs(name, kind, monkeypatch, extra=None, repeat=1):
-    """(native result, float64 host-loop result) of one sampler kind; ``repeat`` = K: K chunks per observation."""
-    want = float64_loop(name, kind, extra, repeat)
-    state, goal, _, _ = case(name)
-    _, _, x, fixed = case(name, B * repeat)
-    ea = dict(extra or {})
-    if repeat > 1:
-        ea["candidates"] = repeat
-    with monkeypatch.context() as mp:
-        no_forward(mp)
-        got = E.run(kind, model_of(name), cuda(state), x.cuda(), goal.cuda(), fixed.cuda(), extra_args=ea).cpu()
-    return got, want
-
-
-def known_of(name):
-    """Known actions: the negated unpinned float64 DDIM result of another noise seed."""
-    key = (name, "known")
-    if key not in _LOOPS:
-        state, goal, _, fixed = case(name)
-        _, _, x_other, _ = case(name, seed=E.OTHER_SEED)
-        _LOOPS[key] = -E.run("ddim", oracle_of(name), E.wide(state), E.wide(x_other), E.wide(goal), E.wide(fixed))
-    return _LOOPS[key]
+assert all(WIDE_SPEC[n][0] == "mdtv" and not WIDE_SPEC[n][3] for n in NAMES)
+F = OptionFamily(WIDE_SPEC, dict(weight_seed=5, input_seed=E.SEED), B)
+meta_of, model_of, oracle_of, case = F.meta_of, F.model_of, F.oracle_of, F.case
+float64_loop, both_runs, known_of = F.float64_loop, F.both_runs, F.known_of
 
 
 @pytest.mark.parametrize("kind", ["heun", "dpmpp_2m"])

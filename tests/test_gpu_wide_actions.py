@@ -9,63 +9,19 @@ test_gpu_parity.py), the loss to 1e-3 relative and every gradient to rtol 2e-3, 
 import pytest
 import torch
 
-from mdt_policy_amd import configs, synthetic
+from mdt_policy_amd import synthetic
 from oracle import mdt_oracle as O
-from tests.helpers import assert_close, load_fixture, params_of
+from tests.family import Family
+from tests.helpers import assert_close, load_fixture, params_of, to
 from tests.wide_action_configs import WIDE_ENVELOPE, WIDE_GOLDEN, WIDE_SPEC
 
 pytestmark = pytest.mark.gpu
 
 NAMES = sorted(WIDE_ENVELOPE)
 SEEDS = dict(weight_seed=201, input_seed=202, loss_seed=203, ctx_seed=204, obs_seed=205)   # the recorder's
-_MODELS = {}
-
-
-def meta_of(name):
-    """A fixture-style meta (tests/helpers.py: cfg_of, params_of, inputs_of) of a case, recorded or not."""
-    from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-    arch, factory, ov, proprio = WIDE_SPEC[name]
-    sd = GCDenoiser(configs.NAMED[factory](**ov), 0.5).state_dict()
-    return dict(config=factory, overrides=ov, arch=arch, proprio=proprio, B=2, modality="lang", profile="rich",
-                state_dict=[[k, list(v.shape)] for k, v in sd.items()], **SEEDS)
-
-
-def model_of(name):
-    """(GCDenoiser on cuda:0 in eval mode, its meta) -- the 'rich' weights of the recorder."""
-    if name not in _MODELS:
-        from mdt_policy_amd.models.edm_diffusion.score_wrappers import GCDenoiser
-        meta = meta_of(name)
-        m = GCDenoiser(WIDE_ENVELOPE[name]["cfg"], 0.5)
-        m.load_state_dict(params_of(meta))
-        _MODELS[name] = (m.cuda().eval(), meta)
-    return _MODELS[name]
-
-
-def inputs(name, B, seed, dtype=torch.float32):
-    """(state, goal, noise) on the host; state_obs (B, 1, proprio_dim) when the case switches the token on (drawn at `seed`; at
-    the recorder's input_seed at the recorder's obs_seed, so that seed gives the recorded inputs)."""
-    e = WIDE_ENVELOPE[name]
-    cfg = e["cfg"]
-    t = {k: torch.from_numpy(v).to(dtype) for k, v in synthetic.sampler_inputs(B, cfg, seed, e["arch"]).items()}
-    if e["arch"] == "mdtv":
-        state = {"state_images": t["state_images"], "modality": "lang"}
-    else:
-        state = {"static": t["static"], "gripper": t["gripper"], "modality": "lang"}
-    if e["proprio"]:
-        obs_seed = SEEDS["obs_seed"] if seed == SEEDS["input_seed"] else seed
-        state["state_obs"] = torch.from_numpy(synthetic.normal("state_obs", (B, 1, cfg["proprio_dim"]), obs_seed)).to(dtype)
-    return state, t["goal"], t["noise"]
-
-
-def to(state, fn):
-    return {k: (fn(v) if torch.is_tensor(v) else v) for k, v in state.items()}
-
-
-def oracle_sample(name, B, seed, sig):
-    e = WIDE_ENVELOPE[name]
-    _, meta = model_of(name)
-    state, goal, noise = inputs(name, B, seed, torch.float64)
-    return O.sample_ddim(params_of(meta, torch.float64), e["cfg"], state, noise * 80.0, goal, sig, arch=e["arch"], hoist=True)
+# state_obs at the recorder's input_seed is drawn at its obs_seed, so that seed gives the recorded inputs
+F = Family(WIDE_SPEC, WIDE_ENVELOPE, SEEDS, recorded_obs=True)
+meta_of, model_of, inputs, oracle_sample = F.meta_of, F.model_of, F.inputs, F.oracle_sample
 
 
 @pytest.mark.parametrize("name", WIDE_GOLDEN)

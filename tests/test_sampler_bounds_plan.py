@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from mdt_policy_amd import _lib
+from mdt_policy_amd.models.edm_diffusion import gc_sampling as gs
 from mdt_policy_amd.utils.action_bounds import ActionBounds
 
 KINDS = ["euler", "euler_ancestral", "heun", "dpm_2", "dpm_2_ancestral", "lms", "dpmpp_2s", "dpmpp_2s_ancestral", "dpmpp_2m",
@@ -15,11 +16,6 @@ KINDS = ["euler", "euler_ancestral", "heun", "dpm_2", "dpm_2_ancestral", "lms", 
 VARIANTS = {"euler": [{}, dict(s_churn=2.0)], "heun": [{}, dict(s_churn=2.0)], "dpm_2": [{}, dict(s_churn=2.0)],
             "euler_ancestral": [{}, dict(eta=0.)], "dpm_2_ancestral": [{}, dict(eta=0.)], "dpmpp_2s_ancestral": [{}, dict(eta=0.)],
             "dpmpp_sde": [{}, dict(eta=0.)], "dpm_fast": [{}, dict(eta=0.5)]}
-
-
-def gs():
-    from mdt_policy_amd.models.edm_diffusion import gc_sampling
-    return gc_sampling
 
 
 def test_the_plan_structs_keep_their_sizes():
@@ -30,7 +26,7 @@ def test_the_plan_structs_keep_their_sizes():
     # evaluation after it and the bytes after the struct are untouched
     buf = (C.c_char * (C.sizeof(_lib.SamplerPlan) + 64))(*([0x5a] * (C.sizeof(_lib.SamplerPlan) + 64)))
     plan = _lib.SamplerPlan.from_buffer(buf)
-    sig = gs().get_sigmas_exponential(64, 0.001, 80.0)
+    sig = gs.get_sigmas_exponential(64, 0.001, 80.0)
     arr = (C.c_float * 65)(*[float(v) for v in sig])
     _lib.check(_lib.load().mdt_sampler_plan(_lib.SAMPLER_KIND["heun"], None, arr, 64, C.byref(plan)))
     assert plan.n_evals == 127 and plan.e[126].ends_step == 1 and plan.e[126].step == 63
@@ -54,7 +50,7 @@ def _check_marks(plan, steps, what):
 @pytest.mark.parametrize("n", [1, 2, 3, 5])
 @pytest.mark.parametrize("kind", KINDS)
 def test_every_step_has_one_first_and_one_last_evaluation(kind, n):
-    sig = gs().get_sigmas_exponential(n, 0.001, 80.0)
+    sig = gs.get_sigmas_exponential(n, 0.001, 80.0)
     for kw in VARIANTS.get(kind, [{}]):
         _check_marks(_lib.sampler_plan(kind, sig, **kw), n, f"{kind} n={n} {kw}")
 
@@ -152,7 +148,7 @@ def _denoiser():
 
 
 def test_a_scaler_with_bounds_keeps_the_native_call():
-    g = gs()
+    g = gs
     sig = g.get_sigmas_exponential(4, 0.001, 80.0)
     model = _denoiser()
     assert g._native_ok(model, sig, None, None, None)
@@ -166,7 +162,7 @@ def test_replay_callback_hands_out_the_loops_dicts():
     rec = {"x": torch.arange(24.).view(3, 2, 2, 2), "denoised": -torch.arange(24.).view(3, 2, 2, 2),
            "sigma": torch.tensor([3.0, 2.0, 1.0]), "sigma_hat": torch.tensor([3.5, 2.0, 1.0])}
     seen = []
-    gs().replay_callback(rec, seen.append)
+    gs.replay_callback(rec, seen.append)
     assert [d["i"] for d in seen] == [0, 1, 2]
     for i, d in enumerate(seen):
         assert set(d) == {"x", "i", "sigma", "sigma_hat", "denoised"}
@@ -176,7 +172,7 @@ def test_replay_callback_hands_out_the_loops_dicts():
 
 def test_record_sigmas_of_a_host_schedule_are_the_loops():
     from mdt_policy_amd.models.edm_diffusion.score_wrappers import _record_sigmas
-    sig = gs().get_sigmas_exponential(4, 0.01, 80.0)
+    sig = gs.get_sigmas_exponential(4, 0.01, 80.0)
     s, h = _record_sigmas("heun", sig, None, dict(s_churn=2.0))
     assert torch.equal(s, sig[:-1])
     gamma = min(2.0 / 4, 2 ** 0.5 - 1)

@@ -10,7 +10,7 @@ import torch
 
 from mdt_policy_amd import synthetic
 from oracle import mdt_oracle as O
-from tests.helpers import assert_close, cfg_of, inputs_of, load_fixture, params_of
+from tests.helpers import assert_close, cfg_of, load_fixture, observation, params_of
 from tests.test_long_chunks_golden import recorded_summaries
 from tests.test_oracle_golden import TIGHT
 from tests.test_train_grads import check_summaries, oracle_total, summary
@@ -19,10 +19,8 @@ from tests.wide_action_configs import WIDE_GOLDEN
 
 def case_inputs(meta):
     cfg = cfg_of(meta)
-    state, goal, noise = inputs_of(meta)
-    if meta["proprio"]:
-        state["state_obs"] = torch.from_numpy(synthetic.normal("state_obs", (meta["B"], 1, cfg["proprio_dim"]), meta["obs_seed"]))
-    return cfg, state, goal, noise
+    state, goal, noise = observation(cfg, meta["arch"], meta["proprio"], meta["B"], meta["input_seed"], obs_seed=meta["obs_seed"])
+    return cfg, dict(state, modality=meta["modality"]), goal, noise
 
 
 @pytest.mark.parametrize("name", WIDE_GOLDEN)

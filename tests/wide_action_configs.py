@@ -2,8 +2,7 @@
 tests/long_chunk_configs.py.  Shared by the GPU tests (tests/test_gpu_wide_actions.py, tests/test_gpu_wide_action_options.py), the
 CPU check that mdt_create's validation accepts every one of them (tests/test_cpu_wide_actions_abi.py) and the recorder
 tests/golden/make_golden_wide.py."""
-from mdt_policy_amd import configs
-from tests.envelope_configs import _case
+from tests.envelope_configs import SHIPPED_MDT_CONFIG as _BASE, envelope_of
 
 # name -> (architecture, configs factory, overrides, proprio): the form the golden fixtures' meta records (tests/helpers.py: cfg_of)
 WIDE_SPEC = {
@@ -29,15 +28,12 @@ WIDE_SPEC = {
                                                         action_seq_len=24, action_dim=64), False),
 }
 
-WIDE_ENVELOPE = {name: _case(configs.NAMED[factory](**ov), arch=arch, proprio=prop) for name, (arch, factory, ov, prop) in WIDE_SPEC.items()}
+WIDE_ENVELOPE = envelope_of(WIDE_SPEC)
 
 # recorded from the reference by tests/golden/make_golden_wide.py at B = 2 (tests/golden/g20_wide_<name>.npz)
 WIDE_GOLDEN = ["a17", "a64", "a24_mlp_head_proprio", "mdt_a20_d512", "a48_plain"]
 WIDE_GOLDEN_B = 2
 
-_BASE = dict(arch=0, embed_dim=384, n_heads=8, n_enc_layers=1, n_dec_layers=2, action_dim=7, obs_dim=384, goal_dim=512, n_obs_token=3,
-             goal_seq_len=1, action_seq_len=10, use_mlp_goal=1, use_modality_encoder=1, use_abs_pos_emb=1, use_rot_embed=0,
-             use_ada_conditioning=1, use_noise_encoder=0, linear_output=1, bias=0, sigma_data=0.5)
 # mdt_config fields mdt_create refuses -> status (2 = MDT_ERR_UNSUPPORTED)
 WIDE_REFUSED_AT_CREATE = [
     (dict(_BASE, action_dim=65), 2),   # past the top of the range
